@@ -13,11 +13,18 @@ one GPU runs on every shard, per-round partial sums and partial commitments cros
 strong scaling, value = ms per proof.  `--mode replicas` instead lets every rank prove its own batch (weak scaling, no
 data-path collective).
 
-Extra objects on the line:
+A plain run sets up, warms up, times the --steps proofs and prints the line.  `--full` adds what the headline does not
+need, each piece still switched off by its --no-* option:
   roofline      the kernel with the largest total time in a separately profiled prove: SURVEY.md §8(d) algorithmic
                 bytes / HIP-event time (ctx stream), against 8 TB/s HBM
   alu           the same launches against the Fr-multiplication peak (the field arithmetic is integer-ALU bound)
+  two_proofs_in_flight  N = 1: throughput with two independent proofs on the GPU
   cpu_baseline  the C++ oracle (reference algorithms, all host cores) on a bounded sample, proof bytes compared
+  N > 1: replicas, the comm_round x shard_exchange_log A/B, two sharded proofs in flight, configs[3], memory by rank, and
+  the sharded proof compared byte for byte with the single-GPU prover's.
+
+`--dump-outputs DIR` writes what the last timed step handed its caller - the proof bytes, one float64 per byte - as
+DIR/proof.npy.  The inputs (lookup columns, SRS trapdoor, circuit) are seeded: the same arguments give the same proof.
 """
 import argparse
 import ctypes as C
@@ -75,10 +82,26 @@ def parse():
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="start the ranks, form the process group, add up the ranks and print {n_gpus, sum} - no GPU work "
                          "(tests/test_dist.py: the launch path of --gpus N on a CPU-only machine)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need (profiled prove, two proofs in flight, "
+                         "CPU baseline; N > 1: the extra objects and the comparison with the single-GPU proof); without "
+                         "it --no-cpu-baseline --no-profile --no-inflight --no-extra are implied")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the proof of the last timed step to DIR/proof.npy (float64, one element per byte)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if not args.log_n:
         args.log_n = 20 if args.workload == "hyperplonk" else 24
+    if not args.full:
+        args.no_cpu_baseline = args.no_profile = args.no_inflight = args.no_extra = True
     return args
+
+
+def dump_outputs(dirname, proof):
+    """--dump-outputs: the proof bytes of the last timed step, one float64 per byte (exact)"""
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "proof.npy"), np.frombuffer(proof, dtype=np.uint8).astype(np.float64))
 
 
 def make_table(hl, kind):
@@ -451,6 +474,8 @@ def main_hyperplonk(args, hdist, dist, rank, local_rank, world):
     elapsed = hdist.max_over_ranks(dist, time.perf_counter() - t0)
     hdist.barrier(dist)
     ms_per_step = elapsed * 1e3 / max(args.steps, 1)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, tr.into_proof())
     if rank == 0:
         out = {
             "metric": "hyperplonk_prove_time_ms", "value": round(ms_per_step / (1 if sharded else world), 3), "unit": "ms",
@@ -492,7 +517,8 @@ def main_hyperplonk(args, hdist, dist, rank, local_rank, world):
         stats = hl.comm_stats(ctx)
         if rank == 0:
             out["comm_collectives_per_run"] = stats
-            out["sharded_proof_equals_single_gpu"] = prove(single=True).into_proof() == tr.into_proof()
+            if args.full:
+                out["sharded_proof_equals_single_gpu"] = prove(single=True).into_proof() == tr.into_proof()
         if not args.no_extra:
             # TWO sharded proofs in flight per rank (main(): sharded_two_in_flight): a second ctx with its own communicator, a
             # host thread each - at this size a sharded proof IS its latency-bound floor, which a second proof fills
@@ -697,6 +723,8 @@ def main():
     ms_per_step, tr = timed(args.steps, args.warmup, live=not args.no_profile)
     phases = hl.lasso_last_timing(ctx)
     proof = tr.into_proof()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, proof)
     proofs_per_step = 1 if sharded else world
 
     out = None
@@ -750,7 +778,7 @@ def main():
             dom = dominant(aggs)
             out["roofline"], out["alu"], out["kernels"] = roofline_objects(
                 hl, ctx, aggs, pmc_traffic(dom["name"], n, args.table, world, dom["launches"]), live_box.get("acc"), args.steps)
-    if world > 1:
+    if world > 1 and args.full:
         # device memory per rank after the headline's proofs (the workspace arena's high-water mark; SRS and lookup columns are
         # on top of it): gathered over the control plane
         mem = hdist.gather_objects(dist, hl.memory_stats(ctx))
@@ -766,7 +794,7 @@ def main():
         stats = hl.comm_stats(ctx)
         if rank == 0:
             out["comm_collectives_per_run"] = stats
-            if n <= 26:
+            if args.full and n <= 26:
                 full = [ctx.upload(c.tobytes()) for c in gen_dims(table, n, 0)]
                 out["sharded_proof_equals_single_gpu"] = prove(bufs=full, single=True).into_proof() == proof
                 del full

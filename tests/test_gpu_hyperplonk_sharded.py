@@ -185,7 +185,7 @@ def test_bench_hyperplonk_keccak_two_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(LH_DEVICE="0", LH_DIST_BACKEND="gloo")
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--workload", "hyperplonk", "--lookup", "lasso", "--circuit",
-                        "keccak", "--log-n", "17", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-profile"],
+                        "keccak", "--log-n", "17", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-profile"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -510,7 +510,7 @@ def test_bench_gpus_2_without_a_launcher():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(LH_DEVICE="0", LH_DIST_BACKEND="gloo")
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--log-n", "17", "--table",
-                        "range", "--no-cpu-baseline", "--no-inflight", "--no-extra", "--no-profile"], cwd=root, env=env,
+                        "range", "--full", "--no-cpu-baseline", "--no-inflight", "--no-extra", "--no-profile"], cwd=root, env=env,
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -535,7 +535,7 @@ def test_bench_two_ranks_launched_like_the_driver():
         env = dict(os.environ, LH_DEVICE="0", LH_DIST_BACKEND="gloo")
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1",
-               "--log-n", "17", "--table", "range", "--no-cpu-baseline", "--no-inflight"] + \
+               "--log-n", "17", "--table", "range", "--full", "--no-cpu-baseline", "--no-inflight"] + \
             ([] if "--extra" in extra else ["--no-extra"]) + [e for e in extra if e != "--extra"]
         r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
         assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]

@@ -5,7 +5,7 @@ O=gpurun_out
 FLAGS="-O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-unknown-pragmas -Wno-unused-result --offload-arch=gfx950 -munsafe-fp-atomics"
 for g in 2 4 2 4; do
   ( cd halo2-lasso_amd/csrc && /opt/rocm/bin/hipcc $FLAGS -DLH_PP_GROUP=$g -c kernels_sumcheck.hip -o kernels_sumcheck.o 2>/dev/null && make 2>/dev/null | tail -1 > /dev/null )
-  python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-inflight > $O/ab_ppg_$g.json 2> $O/ab_ppg.err
+  python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-inflight > $O/ab_ppg_$g.json 2> $O/ab_ppg.err
   python3 -c "
 import json; d=json.load(open('$O/ab_ppg_$g.json'))
 k={x['name']:x['ms'] for x in d['kernels']}

@@ -3,7 +3,7 @@
 # usage: tools/ab_window_tables.sh [levels...]   (default 0 20 22; writes gpurun_out/r03_wt_*.json)
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
-B="--steps 10 --warmup 3 --no-cpu-baseline --no-inflight --no-extra"
+B="--full --steps 10 --warmup 3 --no-cpu-baseline --no-inflight --no-extra"
 LEVELS="${@:-0 20 22}"
 for rep in a b; do
 for wt in $LEVELS; do

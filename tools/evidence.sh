@@ -6,15 +6,15 @@ export TMPDIR=/tmp
 O=gpurun_out
 R=${R:-r06}
 mkdir -p $O
-python3 bench.py --steps 20 --warmup 5 > $O/${R}_bench_and_2p24.json 2> $O/${R}_bench_and_2p24.err
-python3 bench.py --log-n 20 --table range --steps 20 --warmup 5 > $O/${R}_bench_2p20.json 2>> $O/${R}_bench.err
-python3 bench.py --log-n 16 --table range --steps 20 --warmup 5 > $O/${R}_bench_2p16.json 2>> $O/${R}_bench.err
-python3 bench.py --log-n 24 --table range --steps 10 --warmup 3 --no-cpu-baseline > $O/${R}_bench_range_2p24.json 2>> $O/${R}_bench.err
-python3 bench.py --log-n 24 --table xor --steps 10 --warmup 3 --no-cpu-baseline --no-inflight > $O/${R}_bench_xor_2p24.json 2>> $O/${R}_bench.err
-python3 bench.py --workload hyperplonk --log-n 20 > $O/${R}_bench_hyperplonk_2p20.json 2>> $O/${R}_bench.err
-python3 bench.py --workload hyperplonk --lookup lasso --log-n 20 > $O/${R}_bench_hyperplonk_lasso_2p20.json 2>> $O/${R}_bench.err
-python3 bench.py --workload hyperplonk --lookup lasso --circuit keccak --log-n 20 > $O/${R}_bench_hyperplonk_keccak_2p20.json 2>> $O/${R}_bench.err
-for n in 17 18 19 22 26; do python3 bench.py --log-n $n --table range --steps 5 --warmup 2 --no-cpu-baseline --no-inflight > $O/${R}_bench_range_2p$n.json 2>> $O/${R}_bench.err; done
+python3 bench.py --full --steps 20 --warmup 5 > $O/${R}_bench_and_2p24.json 2> $O/${R}_bench_and_2p24.err
+python3 bench.py --full --log-n 20 --table range --steps 20 --warmup 5 > $O/${R}_bench_2p20.json 2>> $O/${R}_bench.err
+python3 bench.py --full --log-n 16 --table range --steps 20 --warmup 5 > $O/${R}_bench_2p16.json 2>> $O/${R}_bench.err
+python3 bench.py --full --log-n 24 --table range --steps 10 --warmup 3 --no-cpu-baseline > $O/${R}_bench_range_2p24.json 2>> $O/${R}_bench.err
+python3 bench.py --full --log-n 24 --table xor --steps 10 --warmup 3 --no-cpu-baseline --no-inflight > $O/${R}_bench_xor_2p24.json 2>> $O/${R}_bench.err
+python3 bench.py --full --workload hyperplonk --log-n 20 > $O/${R}_bench_hyperplonk_2p20.json 2>> $O/${R}_bench.err
+python3 bench.py --full --workload hyperplonk --lookup lasso --log-n 20 > $O/${R}_bench_hyperplonk_lasso_2p20.json 2>> $O/${R}_bench.err
+python3 bench.py --full --workload hyperplonk --lookup lasso --circuit keccak --log-n 20 > $O/${R}_bench_hyperplonk_keccak_2p20.json 2>> $O/${R}_bench.err
+for n in 17 18 19 22 26; do python3 bench.py --full --log-n $n --table range --steps 5 --warmup 2 --no-cpu-baseline --no-inflight > $O/${R}_bench_range_2p$n.json 2>> $O/${R}_bench.err; done
 python3 tools/sharded_rank_profile.py --configs and24,range26,keccak20 --worlds 1,2,4,8 --in-flight 2 --out $O/${R}_sharded_rank_ms.json > $O/${R}_rank.log 2>&1
 # rocprofv3 kernel trace + stats of the default command (the program itself after --: no env / shell hop)
 rm -rf $O/${R}_prof_stats
@@ -52,6 +52,6 @@ python3 tools/isa_audit.py kernels_sumcheck.hip 'sc_round_pp_kernel|sc_round_ope
 python3 tools/isa_audit.py msm.hip 'msm_accumulate0_kernel' >> $O/${R}_isa_audit.txt 2>&1
 if [ "${FULLSIZE:-0}" = "1" ]; then
   # configs[3] at FULL size against the C++ oracle's bytes (2^26 range-check lookups, ~4 min of host time)
-  python3 bench.py --log-n 26 --table range --steps 3 --warmup 1 --cpu-sample-log-n 26 --no-inflight --no-profile > $O/${R}_bench_range_2p26_fullsize_cpu.json 2>> $O/${R}_bench.err
+  python3 bench.py --full --log-n 26 --table range --steps 3 --warmup 1 --cpu-sample-log-n 26 --no-inflight --no-profile > $O/${R}_bench_range_2p26_fullsize_cpu.json 2>> $O/${R}_bench.err
   python3 -c "import json; d=json.load(open('$O/${R}_bench_range_2p26_fullsize_cpu.json')); print('2^26 full size:', d['value'], d['cpu_baseline'])"
 fi
