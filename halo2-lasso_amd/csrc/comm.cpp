@@ -142,9 +142,8 @@ void comm_attach_rccl(Ctx& c, int rank, int size, const uint8_t id_bytes[LH_RCCL
 void comm_probe_host_recv(Ctx& c) {
   c.comm_host_recv_ok = true;
   if (!c.rccl_comm) return;
-  static const bool skip = [] { const char* e = getenv("LH_COMM_PROBE"); return e && atoi(e) == 0; }();
-  static const bool force_fail = [] { const char* e = getenv("LH_COMM_PROBE_FAIL"); return e && atoi(e) != 0; }();
-  if (skip) return;
+  if (knob(Knob::COMM_PROBE) == 0) return;
+  const bool force_fail = knob(Knob::COMM_PROBE_FAIL) != 0;
   const RcclApi& api = rccl();
   const size_t R = (size_t)c.comm.size, n = 16;
   if (!c.lanes_host) {
@@ -204,11 +203,10 @@ void comm_attach_loopback(Ctx& c, int rank, int size, size_t shard_bit) {
   c.shard_bit = shard_bit;
 }
 
-static const bool COMM_DEBUG = getenv("LH_COMM_DEBUG") != nullptr;  // one stderr line per collective (development)
 static void comm_trace(Ctx& c, const char* what, size_t bytes) {
   c.comm_phase_stats[c.comm_phase & 7][0]++;
   c.comm_phase_stats[c.comm_phase & 7][1] += bytes;
-  if (COMM_DEBUG)
+  if (knob(Knob::COMM_DEBUG) != 0)  // one stderr line per collective (development)
     fprintf(stderr, "[comm %d/%d] #%llu %s %zu B\n", c.comm.rank, c.comm.size,
             (unsigned long long)(c.comm_stats[0] + c.comm_stats[1]), what, bytes);
 }
@@ -292,17 +290,11 @@ void comm_all_to_all_multi(Ctx& c, size_t nbuf, const void* const* d_send, const
   comm_trace(c, "all_to_all_v", total * elem);
   // LH_COMM_A2A=allgather: stage the personalised exchange through ncclAllGather under RCCL as well (a fallback should
   // grouped send / recv misbehave on some fabric; R times the traffic)
-  static const bool a2a_by_gather = [] {
-    const char* e = getenv("LH_COMM_A2A");
-    return e && strcmp(e, "allgather") == 0;
-  }();
+  const bool a2a_by_gather = knob(Knob::COMM_A2A) != 0;
   // LH_COMM_A2A_SELF=1 (tests): the segment a rank keeps for itself ALSO travels by ncclSend / ncclRecv - on a one-GPU box
   // the only way the grouped point-to-point path (symbols, group semantics, stream ordering) ever executes before the
   // first multi-GPU run
-  static const bool a2a_self = [] {
-    const char* e = getenv("LH_COMM_A2A_SELF");
-    return e && atoi(e) != 0;
-  }();
+  const bool a2a_self = knob(Knob::COMM_A2A_SELF) != 0;
   if (c.rccl_comm && !a2a_by_gather) {
     const RcclApi& api = rccl();
     c.comm_stats[0]++;
@@ -399,7 +391,7 @@ void comm_sum_lanes(Ctx& c, uint64_t* d_lanes, uint64_t* d_scratch, size_t count
   }
   // every lane validates itself: wait until each carries the ranks' tags
   // (bounded: a peer that never arrives - hipErrorNotReady for ever - must not hang this rank: LH_COMM_WAIT_TIMEOUT_MS)
-  static const long wait_ms = [] { const char* e = getenv("LH_COMM_WAIT_TIMEOUT_MS"); return e && atol(e) > 0 ? atol(e) : 30000L; }();
+  const long wait_ms = (long)knob(Knob::COMM_WAIT_TIMEOUT_MS);
   const auto wait_t0 = std::chrono::steady_clock::now();
   const uint64_t expect = ((uint64_t)R * c.sc_tag) & 0xffffffull;
   for (size_t i = 0; i < n; i++) {

@@ -2,6 +2,7 @@
 #include <string.h>
 #include <stdlib.h>
 #include <ctype.h>
+#include <errno.h>
 #include <sched.h>
 #include <atomic>
 #include <condition_variable>
@@ -98,20 +99,104 @@ bool Options::in_range(const char* name, int64_t value) {
   return false;
 }
 
+// The one parse of an environment value, options and knobs: false when `name` is unset, empty, not a number (an integer
+// unless `real`) or outside [lo, hi] - ignored, loudly (nobody is there to take an error; with `said`: once).
+static bool env_number(const char* name, bool real, double lo, double hi, double& out, std::atomic<bool>* said = nullptr) {
+  const char* e = getenv(name);
+  if (!e || !*e) return false;
+  char* end = nullptr;
+  errno = 0;
+  const double v = real ? strtod(e, &end) : (double)strtoll(e, &end, 10);
+  if (end != e && *end == 0 && errno == 0 && v >= lo && v <= hi) {
+    out = v;
+    return true;
+  }
+  if (!said || !said->exchange(true))
+    fprintf(stderr, "[lasso-hip] %s=%s is outside [%lld, %lld]: ignored\n", name, e, (long long)lo, (long long)hi);
+  return false;
+}
+
 Options::Options() {
   for (const auto& o : OPTION_TABLE) {
     std::string env = "LH_";
     for (const char* p = o.name; *p; p++) env.push_back((char)toupper((unsigned char)*p));
-    const char* e = getenv(env.c_str());
-    if (!e || !*e) continue;
-    const int64_t v = (int64_t)atoll(e);
-    if (v < o.lo || v > o.hi) {  // (an environment default out of range is ignored, loudly: nobody is there to take an error)
-      fprintf(stderr, "[lasso-hip] %s=%s is outside [%lld, %lld]: ignored\n", env.c_str(), e, (long long)o.lo, (long long)o.hi);
-      continue;
-    }
-    this->*o.field = v;
+    double v;
+    if (!env_number(env.c_str(), false, (double)o.lo, (double)o.hi, v)) continue;
+    this->*o.field = (int64_t)v;
     if (o.field == &Options::open_small_min_vars) open_small_min_vars_forced = true;
   }
+}
+
+// (row i is Knob i: tests/test_knobs.py holds the two lists to the same order)
+enum KnobKind { INT, REAL, WORD, PATH };
+static constexpr struct KnobRow {
+  const char* env;
+  KnobKind kind;
+  double dflt, lo, hi;  // (a switch is an INT in [0, 1]; WORD: 1 when the value is `word`)
+  bool live;            // read at every use (tests change it within a process), not once
+  const char* word;
+} KNOB_TABLE[] = {
+    // thresholds between code paths
+    {"LH_SC_TAIL_G", INT, 0, 0, 1024},                 // workgroups of the resident tail (0: by size)
+    {"LH_MSM_C_OFF", INT, 4, -32, 32},                 // MSM window: floor(log2 n) - this, at most LH_MSM_C_MAX
+    {"LH_MSM_C_MAX", INT, 17, 1, 31},
+    {"LH_MSM_K2", INT, 4, 2, 64},                      // fan-in of the linear continuation levels
+    {"LH_MSM_SEG", INT, 0, 0, 256},                    // buckets per reduction segment (0: by size)
+    {"LH_MSM_SLAB_LOG", INT, 16, 0, 31},               // jobs of >= 2^this points: sorted slab by slab
+    {"LH_MSM_TREE_MAX", INT, 262144, 0, 1 << 30},      // continuation lists up to this: trees (0: never)
+    {"LH_MSM_QUAD_MAX", INT, 262144, 0, 1 << 30},      // lists / segments up to this: a quad of lanes each (0: never)
+    {"LH_MSM_TWO_LEVEL", INT, 1, 0, 1},                // two-level bucket reduction
+    {"LH_MSM_HALF_MIN_LOG", INT, 24, 0, 63},           // batches of >= 2^this entries: two halves
+    {"LH_MSM_HALF_COVER", INT, 12, 0, 1 << 20},        // second-half entries per first-half bucket
+    {"LH_EXPR_MONOMIALS", INT, 0, 0, 1},               // sum of monomials, not the register program
+    {"LH_EXPR_JIT_MIN_VARS", INT, 16, 0, 64},          // smallest sum-check with a compiled kernel
+    {"LH_EXPR_EF_MIN_VARS", INT, 14, 2, 64},           // smallest eq-factored expression sum-check
+    // A/B switches of round 6's routes (the bytes never depend on them)
+    {"LH_FIN_LANES_MIN_BYTES", REAL, 0, -1, 1e18},     // -1: no launch hands over in lanes
+    {"LH_SC_U32", INT, 1, 0, 1}, {"LH_OPEN_U32_ROUNDS", INT, 1, 0, 1}, {"LH_OPEN_FOLD_COLS", INT, 1, 0, 1},
+    // operation
+    {"LH_HOST_THREADS", INT, 48, 0, 4096},             // host pool threads, the caller's included
+    {"LH_JIT_CACHE", INT, 1, 0, 1}, {"LH_JIT_CACHE_DIR", PATH, 0, 0, 0},
+    {"LH_EXPR_JIT", INT, 1, 0, 1},                     // 0: always interpret
+    {"LH_SC_TAIL_TIMEOUT_MS", REAL, 2000, 0, 1e7, true}, {"LH_GKR_START_TIMEOUT_MS", REAL, 25, 0, 1e7, true},
+    {"LH_COMM_WAIT_TIMEOUT_MS", INT, 30000, 1, 1e9}, {"LH_COMM_A2A", WORD, 0, 0, 1, false, "allgather"},
+    {"LH_COMM_PROBE", INT, 1, 0, 1},
+    // diagnostics (stderr)
+    {"LH_HOST_TRACE", INT, 0, 0, 1, true}, {"LH_SC_TAIL_TRACE", INT, 0, 0, 1}, {"LH_GKR_TRACE", INT, 0, 0, 1},
+    {"LH_SC_DEBUG", INT, 0, 0, 1}, {"LH_MSM_DEBUG", INT, 0, 0, 1}, {"LH_HP_DEBUG", INT, 0, 0, 1}, {"LH_COMM_DEBUG", INT, 0, 0, 1},
+    {"LH_OPEN_SMALL_CHECK", INT, 0, 0, 1},
+    // test hooks
+    {"LH_COMM_A2A_SELF", INT, 0, 0, 1}, {"LH_COMM_PROBE_FAIL", INT, 0, 0, 1}, {"LH_SHARDED_COUNTERS_MIN_R", INT, 2, 1, 1 << 20},
+};
+static_assert(sizeof(KNOB_TABLE) / sizeof(KNOB_TABLE[0]) == (size_t)Knob::COUNT, "KNOB_TABLE: one row per Knob");
+
+static double knob_read(const KnobRow& r, std::atomic<bool>* said) {
+  double v = r.dflt;
+  if (r.kind != WORD) {
+    env_number(r.env, r.kind == REAL, r.lo, r.hi, v, said);
+  } else if (const char* e = getenv(r.env)) {
+    if (strcmp(e, r.word) == 0) v = 1;
+    else if (*e && (!said || !said->exchange(true))) fprintf(stderr, "[lasso-hip] %s=%s is outside [%s]: ignored\n", r.env, e, r.word);
+  }
+  return v;
+}
+
+double knob(Knob k) {
+  constexpr size_t N = (size_t)Knob::COUNT;
+  static const std::vector<double> once = [] {
+    std::vector<double> v(N);
+    for (size_t i = 0; i < N; i++)
+      if (!KNOB_TABLE[i].live && KNOB_TABLE[i].kind != PATH) v[i] = knob_read(KNOB_TABLE[i], nullptr);
+    return v;
+  }();
+  static std::atomic<bool> said[N];  // (a live knob's bad value is reported once, too)
+  const KnobRow& r = KNOB_TABLE[(size_t)k];
+  return r.live ? knob_read(r, &said[(size_t)k]) : once[(size_t)k];
+}
+
+const char* knob_text(Knob k) {
+  const char* e = KNOB_TABLE[(size_t)k].kind == PATH ? getenv(KNOB_TABLE[(size_t)k].env) : nullptr;
+  return e && *e ? e : nullptr;
 }
 
 void Ctx::host_stamp(const char* tag) {
@@ -215,7 +300,7 @@ ScFinishArgs Ctx::finish_for(uint32_t grid, Fr* out_host, uint32_t seq, double s
   // Every launch hands over in lanes (measured on 2^24 AND lookups: no launch 58.9-59.0 ms, launches that store >= 2^28 bytes
   // 58.0, >= 2^25 bytes 57.4, every launch 57.1; 2^22 range 15.67 / 15.37 / 15.30; 2^20: within the noise).
   // LH_FIN_LANES_MIN_BYTES: the smallest launch (by the bytes its workgroups store) that does - development A/B; -1: none
-  static const double lanes_min = getenv("LH_FIN_LANES_MIN_BYTES") ? atof(getenv("LH_FIN_LANES_MIN_BYTES")) : 0.0;
+  const double lanes_min = knob(Knob::FIN_LANES_MIN_BYTES);
   const bool lanes = lanes_min >= 0 && stored_bytes >= lanes_min && grid > 1 && (uint64_t)grid * 16 <= FIN_LANE_SUMS;
   ScFinishArgs f{ticket, (uint32_t)(ticket_base + grid - 1), out_host, flag, seq, nullptr, 0, lanes ? fin_lanes : nullptr};
   if (sc_redirect) f.out_host = sc_redirect, f.flag = ticket + 8, f.wide = sc_wide, f.tag = sc_tag;  // sharded round: a device word nobody waits on
@@ -435,8 +520,7 @@ struct HostPool {
     unsigned hw = usable_cpus();
     // (an MSM batch hands ~25-40 window combines of ~70 us each to this pool at the end of a commit or an opening - the
     // GPU idles meanwhile: one round of them, not three, where the host has the cores; LH_HOST_THREADS overrides)
-    unsigned cap = 47;
-    if (const char* e = getenv("LH_HOST_THREADS")) cap = (unsigned)std::max(0, atoi(e) - 1);
+    const unsigned cap = (unsigned)std::max(0, (int)knob(Knob::HOST_THREADS) - 1);
     workers = hw > 1 ? std::min(cap, hw - 1) : 0;
     for (unsigned i = 0; i < workers; i++) std::thread([this] { worker(); }).detach();
   }

@@ -153,6 +153,23 @@ struct Options {
   int64_t* find(const char* name);
   static bool in_range(const char* name, int64_t value);  // the range lh_ctx_set_option accepts
 };
+
+// ------------------------------------------------------------------ process-wide knobs
+// Every other LH_* variable the library reads: one row each in KNOB_TABLE (dev.cpp: name, kind, default, accepted range),
+// parsed like the options' defaults (unset or empty: the default; unparsable or out of range: the default and one line on
+// stderr).  Read on first use and kept for the process, except the rows the table marks live (read at every use).
+enum class Knob {  // (grouped as the table: thresholds, A/B switches, operation, diagnostics, test hooks)
+  SC_TAIL_G, MSM_C_OFF, MSM_C_MAX, MSM_K2, MSM_SEG, MSM_SLAB_LOG, MSM_TREE_MAX, MSM_QUAD_MAX, MSM_TWO_LEVEL, MSM_HALF_MIN_LOG,
+  MSM_HALF_COVER, EXPR_MONOMIALS, EXPR_JIT_MIN_VARS, EXPR_EF_MIN_VARS,
+  FIN_LANES_MIN_BYTES, SC_U32, OPEN_U32_ROUNDS, OPEN_FOLD_COLS,
+  HOST_THREADS, JIT_CACHE, JIT_CACHE_DIR, EXPR_JIT, SC_TAIL_TIMEOUT_MS, GKR_START_TIMEOUT_MS, COMM_WAIT_TIMEOUT_MS, COMM_A2A,
+  COMM_PROBE,
+  HOST_TRACE, SC_TAIL_TRACE, GKR_TRACE, SC_DEBUG, MSM_DEBUG, HP_DEBUG, COMM_DEBUG, OPEN_SMALL_CHECK,
+  COMM_A2A_SELF, COMM_PROBE_FAIL, SHARDED_COUNTERS_MIN_R,
+  COUNT
+};
+double knob(Knob k);            // the value (switches 0 / 1; LH_COMM_A2A: 1 = allgather)
+const char* knob_text(Knob k);  // a path knob's value (nullptr: unset or empty)
 struct RouteStats {  // lh_lasso_route (include/lasso_hip.h): counters of the last Lasso prove on the ctx
   uint32_t v[LH_LASSO_ROUTE_WORDS] = {0};
   enum { OPEN_DEPTH, OPEN_PASSES, EF_ROUNDS, STD_ROUNDS, RW_ROUNDS, TAILS, TAIL_ROUNDS, PACKED_TS, DERIVED, SORTED_REUSE,
@@ -860,7 +877,6 @@ void k_msm_window_table(Ctx&, const G1Affine* bases, size_t n, uint32_t cbits, u
 // Returns whether the host waited for the ctx's stream on the way (false only for a batch without a single entry and with every
 // width promised: then nothing queued before the call is known to have run).
 bool msm_batch(Ctx&, const MsmJob* jobs, size_t num_jobs, G1Affine* out_host, const std::function<void()>* overlap = nullptr);
-int msm_slab_log();  // jobs of >= 2^this points are sorted slab by slab (and can take MsmJob::sorted_*)
 // out[i] = scalars[i] * G (fixed-base), normalised to affine; all on device
 void k_fixed_base_mul_g(Ctx&, const Fr* scalars, size_t n, G1Affine* out);
 

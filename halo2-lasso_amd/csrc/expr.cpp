@@ -387,14 +387,10 @@ SumCheckResult sum_check_prove_expr(Ctx& c, size_t num_vars, const lh_expr& expr
   // the streaming rounds evaluate C alone at one point fewer, weighted with ONE entry of a halving eq level per pair,
   // instead of E over a streamed and bound eq table; the host rebuilds the reference's message.  Single-GPU sum-checks
   // of >= 2^14 rows through the register program; LH_SC_EQ_FACTORING=0 / option sc_eq_factoring switch it off.
-  static const bool use_prog = !(getenv("LH_EXPR_MONOMIALS") && atoi(getenv("LH_EXPR_MONOMIALS")));
+  const bool use_prog = knob(Knob::EXPR_MONOMIALS) == 0;
   EqFactorShape shp;
   // (below 2^14 rows the rounds are latency-bound and the levels' set-up is not worth it; LH_EXPR_EF_MIN_VARS: tests)
-  static const size_t ef_min_vars = [] {
-    const char* e = getenv("LH_EXPR_EF_MIN_VARS");
-    return e && atoi(e) >= 2 ? (size_t)atoi(e) : (size_t)14;
-  }();
-  if (c.opt.sc_eq_factoring != 0 && use_prog && !sharded && num_vars >= ef_min_vars)
+  if (c.opt.sc_eq_factoring != 0 && use_prog && !sharded && num_vars >= (size_t)knob(Knob::EXPR_EF_MIN_VARS))
     shp = find_eq_factor_shape(expr, challenges, num_challenges, ex);
   if (shp.ok) {  // (1 - y_j) must be invertible in every round
     const HFr* y = ys + (size_t)ex.atoms[shp.eq_atom].a * num_vars;
@@ -513,7 +509,7 @@ SumCheckResult sum_check_prove_expr(Ctx& c, size_t num_vars, const lh_expr& expr
       lh_expr sub = expr;
       sub.num_nodes = (size_t)shp.c_node + 1;  // (a node only refers to earlier nodes: C's subtree lies in this prefix)
       progc = compile_program(sub, challenges, num_challenges, leaf_table, table_of[shp.eq_atom]);
-      if (progc.ok && getenv("LH_HP_DEBUG"))
+      if (progc.ok && knob(Knob::HP_DEBUG) != 0)
         fprintf(stderr, "[expr] factored: eq * C with C of degree %d in %zu instructions, %zu linear atoms beside it\n", shp.c_degree,
                 progc.code.size() / 2, shp.lin.size());
     }
@@ -524,7 +520,7 @@ SumCheckResult sum_check_prove_expr(Ctx& c, size_t num_vars, const lh_expr& expr
       tables[(size_t)table_of[shp.eq_atom]] = eq;
       shp.ok = false;
     }
-    if (prog.ok && getenv("LH_HP_DEBUG")) {
+    if (prog.ok && knob(Knob::HP_DEBUG) != 0) {
       size_t muls = 0, atoms = 0;
       for (size_t i = 0; i < prog.code.size(); i += 2) {
         const uint32_t w0 = prog.code[i];

@@ -509,10 +509,8 @@ __device__ __forceinline__ Fp<P> dot_scan(const Fp<P>* a, const Fp<P>* b) {
 // The same two routines with ONE asm block per column (ff_cols.inc, generated by tools/gen_ff_cols.py): after every asm
 // block whose result the next instruction reads the compiler's hazard recogniser puts an `s_nop 0` (it must assume a
 // dst_sel write), which with a block per multiply-add was 136 + ~16 extra issue slots next to the 307 instructions of a
-// product.  Same instructions otherwise, same results (tools/ubench/mul_cols.hip).
-#ifndef LH_FF_COLS
-#define LH_FF_COLS 1
-#endif
+// product.  Same instructions otherwise, same results: mul / dot below use these, the two above are the reference
+// tools/ubench/mul_cols.hip and dot_check.hip check them against.
 #include "ff_cols.inc"
 // (the next column's first block writes `top` afresh - the carry of its first multiply-add - so it is not zeroed here)
 #define LH_COL_STEP_LO(k)                       \
@@ -592,7 +590,7 @@ __device__ __forceinline__ Fp<P> dot_scan_cols(const Fp<P>* a, const Fp<P>* b) {
 template <class P>
 LH_HD Fp<P> mul(const Fp<P>& a, const Fp<P>& b) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  return LH_FF_COLS ? mul_scan_cols(a, b) : mul_scan(a, b);
+  return mul_scan_cols(a, b);
 #else
   return mul_cios(a, b);
 #endif
@@ -602,7 +600,7 @@ LH_HD Fp<P> mul(const Fp<P>& a, const Fp<P>& b) {
 template <class P, int K>
 LH_HD Fp<P> dot(const Fp<P>* a, const Fp<P>* b) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  return LH_FF_COLS ? dot_scan_cols<P, K>(a, b) : dot_scan<P, K>(a, b);
+  return dot_scan_cols<P, K>(a, b);
 #else
   Fp<P> s = mul_cios(a[0], b[0]);
   for (int j = 1; j < K; j++) s = add_generic(s, mul_cios(a[j], b[j]));

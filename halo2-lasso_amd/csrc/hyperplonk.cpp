@@ -152,7 +152,7 @@ struct PhaseTimer {  // LH_HP_DEBUG=1: wall-clock per phase on stderr (developme
   static double now() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
   }
-  explicit PhaseTimer(Ctx& c_) : c(c_), on(getenv("LH_HP_DEBUG") != nullptr), t(now()) {}
+  explicit PhaseTimer(Ctx& c_) : c(c_), on(knob(Knob::HP_DEBUG) != 0), t(now()) {}
   void lap(const char* what) {
     if (!on) return;
     c.sync();

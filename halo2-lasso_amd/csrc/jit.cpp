@@ -318,10 +318,9 @@ bool make_dirs(const std::string& path) {  // mkdir -p
 }
 const std::string& disk_dir() {  // empty: no disk cache
   static const std::string dir = [] {
-    const char* on = getenv("LH_JIT_CACHE");
-    if (on && atoi(on) == 0) return std::string();
+    if (knob(Knob::JIT_CACHE) == 0) return std::string();
     std::string d;
-    if (const char* e = getenv("LH_JIT_CACHE_DIR")) d = e;
+    if (const char* e = knob_text(Knob::JIT_CACHE_DIR)) d = e;
     else if (const char* x = getenv("XDG_CACHE_HOME")) d = std::string(x) + "/lasso_hip/jit";
     else if (const char* h = getenv("HOME")) d = std::string(h) + "/.cache/lasso_hip/jit";
     if (d.empty() || !make_dirs(d)) return std::string();
@@ -409,15 +408,8 @@ void disk_store(const std::string& path, const std::string& src, const std::stri
 }  // namespace
 
 bool jit_enabled(size_t num_vars) {
-  static const int on = [] {
-    const char* e = getenv("LH_EXPR_JIT");  // 0: always interpret
-    return e ? atoi(e) : 1;
-  }();
-  static const size_t min_vars = [] {
-    const char* e = getenv("LH_EXPR_JIT_MIN_VARS");  // smaller sum-checks are not worth seconds of compilation
-    return e ? (size_t)atoll(e) : (size_t)16;
-  }();
-  return on && num_vars >= min_vars;
+  // (smaller sum-checks than LH_EXPR_JIT_MIN_VARS are not worth seconds of compilation)
+  return knob(Knob::EXPR_JIT) != 0 && num_vars >= (size_t)knob(Knob::EXPR_JIT_MIN_VARS);
 }
 
 const JitKernel* jit_sc_round(const Ctx& c, const uint32_t* code, size_t num_instrs, uint32_t num_regs, uint32_t result_reg,
@@ -472,7 +464,7 @@ const JitKernel* jit_sc_round(const Ctx& c, const uint32_t* code, size_t num_ins
   int per_cu = 0;
   if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k->fn, (int)k->threads, 0) == hipSuccess && per_cu > 0)
     k->blocks_per_cu = (unsigned)per_cu;
-  if (getenv("LH_HP_DEBUG")) {
+  if (knob(Knob::HP_DEBUG) != 0) {
     int vgprs = 0, scratch = 0;
     (void)hipFuncGetAttribute(&vgprs, HIP_FUNC_ATTRIBUTE_NUM_REGS, k->fn);
     (void)hipFuncGetAttribute(&scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, k->fn);

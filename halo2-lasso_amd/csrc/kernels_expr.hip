@@ -380,8 +380,7 @@ void k_sc_round_prog(Ctx& c, const ProgRound& pr, int degree, size_t size, Fr* e
     }
     per_cu = vm_per_cu[degree];
   }
-  static const bool dbg = getenv("LH_HP_DEBUG") != nullptr;
-  if (dbg && size >= ((size_t)1 << 18)) fprintf(stderr, "[expr] round kernel: %d workgroups of %u threads per CU\n", per_cu, threads);
+  if (knob(Knob::HP_DEBUG) != 0 && size >= ((size_t)1 << 18)) fprintf(stderr, "[expr] round kernel: %d workgroups of %u threads per CU\n", per_cu, threads);
   // compiled form: one wave per workgroup and a grid of (g, degree) workgroups, all of which draw a ticket
   const size_t cap = jit ? std::max<size_t>(1, (size_t)c.num_cus * (size_t)per_cu / (size_t)degree) : (size_t)c.num_cus * (size_t)per_cu;
   if (g > cap) g = cap;

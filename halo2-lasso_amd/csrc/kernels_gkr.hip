@@ -434,16 +434,12 @@ void k_gkr_resident_launch(Ctx& c, const GkrLayerDev* layers, size_t num_layers,
   a.msg_host = msg_host;
   a.out_host = out_host;
   a.flag = c.flag;
-  const char* tmo = getenv("LH_SC_TAIL_TIMEOUT_MS");
-  const double ms = tmo && *tmo ? atof(tmo) : 2000.0;
-  a.poll_ticks = (uint64_t)(ms * (double)c.wall_clock_khz);
-  const char* smo = getenv("LH_GKR_START_TIMEOUT_MS");
-  a.start_ticks = (uint64_t)((smo && *smo ? atof(smo) : 25.0) * (double)c.wall_clock_khz);
+  a.poll_ticks = (uint64_t)(knob(Knob::SC_TAIL_TIMEOUT_MS) * (double)c.wall_clock_khz);
+  a.start_ticks = (uint64_t)(knob(Knob::GKR_START_TIMEOUT_MS) * (double)c.wall_clock_khz);
   a.start_word = c.ticket + 10;  // (word 0: tickets, word 8: the sharded rounds' device flag, words 32..: the tail's relay)
   a.start_id = layers[0].seq;    // (sequence numbers only grow: no two launches of a ctx share one)
-  static const bool trace_on = getenv("LH_GKR_TRACE") != nullptr;
   a.trace = nullptr;
-  if (trace_on) {
+  if (knob(Knob::GKR_TRACE) != 0) {
     const size_t words = ((size_t)GKR_MAX_VARS + GKR_TRACE_ROUNDS) * 8;
     a.trace = (uint64_t*)c.arena.alloc(words * sizeof(uint64_t));
     LH_HIP(hipMemsetAsync(a.trace, 0, words * sizeof(uint64_t), c.stream));

@@ -72,14 +72,9 @@ __device__ __forceinline__ void finish_round(const ScFinish& f, const Fr* __rest
 
 // Occupancy of the streaming round kernels: the degree-2 instantiations (GKR layers, Surge, the batch opening: the
 // ones that run at 2^24) are asked for 4 waves per SIMD instead of the 3 the register allocator settles on by itself
-// (measured 2^24 AND proof: -0.9 ms, tools/ab_waves.sh); higher degrees would spill heavily and keep the default.
-#ifndef LH_SC_WAVES_D2
-#define LH_SC_WAVES_D2 4
-#endif
-#define LH_SC_WAVES_ATTR(D) \
-  __attribute__((amdgpu_waves_per_eu((D) <= 2 && LH_SC_WAVES_D2 ? LH_SC_WAVES_D2 : 1, (D) <= 2 && LH_SC_WAVES_D2 ? LH_SC_WAVES_D2 : 8)))
+// (measured 2^24 AND proof: -0.9 ms, tools/history/ab_waves.sh); higher degrees would spill heavily and keep the default.
 template <int D, bool BIND>
-__global__ __launch_bounds__(256) LH_SC_WAVES_ATTR(D) void sc_round_kernel(ScArgs a, size_t size, uint32_t tp,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(D <= 2 ? 4 : 1, D <= 2 ? 4 : 8))) void sc_round_kernel(ScArgs a, size_t size, uint32_t tp,
                                                        Fr* __restrict__ partials, ScFinish fin) {
   __shared__ Fr lds[4];
   const ScRound& rd = a.rd;
@@ -196,19 +191,8 @@ __device__ __forceinline__ void reduce_by_parity(const Fr& acc, bool odd, Fr* ld
 }
 
 // q(1), q(2) of  sum_b eq_level[b] * sum_m coeff_m prod_k table_{m,k}  (ScRound with eq_level): partials[.][0] = q(1)
-// occupancy hints of the entry-per-lane kernels (waves per SIMD; 0 = the register allocator's choice): A/B knobs at build time
-#ifndef LH_E_WAVES_E2
-#define LH_E_WAVES_E2 0
-#endif
-#ifndef LH_E_WAVES_OPEN
-#define LH_E_WAVES_OPEN 0
-#endif
-#ifndef LH_E_WAVES_RW
-#define LH_E_WAVES_RW 0
-#endif
-#define LH_E_WAVES_ATTR(W) __attribute__((amdgpu_waves_per_eu((W) ? (W) : 1, (W) ? (W) : 8)))
 template <bool BIND>
-__global__ __launch_bounds__(256) LH_E_WAVES_ATTR(LH_E_WAVES_E2) void sc_round_e2_kernel(ScArgs a, size_t size, Fr* __restrict__ partials, ScFinish fin) {
+__global__ __launch_bounds__(256) void sc_round_e2_kernel(ScArgs a, size_t size, Fr* __restrict__ partials, ScFinish fin) {
   __shared__ Fr lds[4];
   const ScRound& rd = a.rd;
   Fr acc = Fr::zero();
@@ -249,11 +233,9 @@ __global__ __launch_bounds__(256) LH_E_WAVES_ATTR(LH_E_WAVES_E2) void sc_round_e
 // Loads first: the entries of a PAIR of terms (four tables, eight 32-byte entries per lane when binding) are requested
 // before anything is computed or stored - written table by table (load, bind, store, next table) the stores keep the
 // compiler from moving the next table's loads up, and a wave has one table's 4 KB in flight at a time.
-#ifndef LH_PP_WAVES
-#define LH_PP_WAVES 3  // (build-time A/B knob, tools/ab_pp_waves.sh: 4 fits 128 registers with 100 B of spills)
-#endif
+// (3 waves per SIMD: 4 fits 128 registers with 100 B of spills, tools/history/ab_pp_waves.sh)
 template <bool BIND>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LH_PP_WAVES, 8))) void sc_round_pp_kernel(ScArgs a, size_t size, Fr* __restrict__ partials, ScFinish fin) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) void sc_round_pp_kernel(ScArgs a, size_t size, Fr* __restrict__ partials, ScFinish fin) {
   __shared__ Fr lds[4];
   const ScRound& rd = a.rd;
   Fr acc = Fr::zero();
@@ -264,13 +246,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LH_PP_WAVES
   const Fr rch = rd.r;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (size_t)gridDim.x * blockDim.x) {
     Fr s = Fr::zero();
-#ifndef LH_PP_GROUP
-#define LH_PP_GROUP 4  // terms per shared reduction (build-time A/B knob: 2 = a reduction per pair of terms, fewer registers)
-#endif
-    for (uint32_t m0 = 0; m0 < K; m0 += LH_PP_GROUP) {
-      Fr av[LH_PP_GROUP], bv[LH_PP_GROUP];
+    // terms per shared reduction: 4 (2, a reduction per pair of terms, is slower: tools/history/ab_pp_group.sh)
+    for (uint32_t m0 = 0; m0 < K; m0 += 4) {
+      Fr av[4], bv[4];
 #pragma unroll
-      for (int h2 = 0; h2 < LH_PP_GROUP / 2; h2++) {
+      for (int h2 = 0; h2 < 2; h2++) {
         // the four tables of terms m0 + 2 h2, m0 + 2 h2 + 1 (a term past the end reads term 0's tables again, unused)
         const uint32_t ma = m0 + 2 * h2, mb = ma + 1;
         const bool va = ma < K, vb = mb < K;
@@ -307,7 +287,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LH_PP_WAVES
         av[2 * h2 + 1] = vb ? at_lane_point(x2, odd) : Fr::zero();
         bv[2 * h2 + 1] = vb ? at_lane_point(x3, odd) : Fr::zero();
       }
-      s = add(s, dot<FrParams, LH_PP_GROUP>(av, bv));
+      s = add(s, dot<FrParams, 4>(av, bv));
     }
     acc = add(acc, mul(s, rd.eq_level[i >> 1]));
   }
@@ -663,10 +643,7 @@ static uint32_t tail_red_entries(const ScRound& rd, int degree, size_t n) {
 // workgroups of a resident tail over tables of n0 entries: slices of ~32 entries (about one multiplication per lane and
 // round), at most TAIL_MAX_G
 static uint32_t tail_workgroups(size_t n0) {
-  static const int forced = [] {
-    const char* e = getenv("LH_SC_TAIL_G");  // development: 1 = always a single workgroup
-    return e ? atoi(e) : 0;
-  }();
+  const int forced = (int)knob(Knob::SC_TAIL_G);  // development: 1 = always a single workgroup
   uint32_t G = 1;
   while (G < TAIL_MAX_G && (size_t)G * 64 <= n0) G <<= 1;
   if (forced > 0) {
@@ -734,12 +711,9 @@ void k_sc_tail_launch(Ctx& c, const ScRound& rd, int degree, size_t n0, bool fir
   a.mbox = c.mbox();
   // bounded wait per challenge: LH_SC_TAIL_TIMEOUT_MS (default 2000) in ticks of the device's constant-rate counter
   // (hipDeviceAttributeWallClockRate, 100 MHz on gfx950).  When it expires the host resumes with launched rounds.
-  const char* tmo = getenv("LH_SC_TAIL_TIMEOUT_MS");
-  const double ms = tmo && *tmo ? atof(tmo) : 2000.0;
-  a.poll_ticks = (uint64_t)(ms * (double)c.wall_clock_khz);
-  static const bool trace_on = getenv("LH_SC_TAIL_TRACE") != nullptr;
+  a.poll_ticks = (uint64_t)(knob(Knob::SC_TAIL_TIMEOUT_MS) * (double)c.wall_clock_khz);
   a.trace = nullptr;
-  if (trace_on) {
+  if (knob(Knob::SC_TAIL_TRACE) != 0) {
     a.trace = (uint64_t*)c.arena.alloc(32 * 8 * sizeof(uint64_t));
     LH_HIP(hipMemsetAsync(a.trace, 0, 32 * 8 * sizeof(uint64_t), c.stream));
     c.tail_trace = a.trace;
@@ -758,15 +732,8 @@ void k_sc_tail_resync(Ctx& c) {
   c.ticket_base = v;
 }
 
-static size_t sc_lds_max_items() {
-  static const size_t lds_max = [] {
-    const char* e = getenv("LH_SC_LDS_MAX_ITEMS");  // tuning knob: (pairs * terms) up to which the LDS kernel is used
-    return e ? (size_t)atoll(e) : ((size_t)1 << 16);
-  }();
-  return lds_max;
-}
-bool k_sc_round_streams(const ScRound& rd, int degree, size_t size) {
-  return !(rd.num_terms * (uint32_t)degree <= 256 && size * rd.num_terms <= sc_lds_max_items());
+bool k_sc_round_streams(const ScRound& rd, int degree, size_t size) {  // (up to 2^16 pairs * terms: the LDS kernel)
+  return !(rd.num_terms * (uint32_t)degree <= 256 && size * rd.num_terms <= ((size_t)1 << 16));
 }
 
 // Every level of a factored eq table (host.hpp EqFactoring: E_{j+1}[b] = E_j[2b] + E_j[2b+1]) in a few launches instead of
@@ -831,24 +798,12 @@ void k_eq_levels(Ctx& c, const Fr* in, size_t n_in, Fr* const* levels, size_t nl
   }
 }
 
-// workgroups per CU of the entry-per-lane round kernels (grid-stride loops; tuning knob LH_SC_ENTRY_BLOCKS)
-static size_t sc_entry_blocks_per_cu() {
-  static const size_t v = [] {
-    const char* e = getenv("LH_SC_ENTRY_BLOCKS");
-    return e && atoi(e) > 0 ? (size_t)atoi(e) : (size_t)8;
-  }();
-  return v;
-}
-
 // grid of an entry-per-lane round kernel over `entries` bound entries: every workgroup ends with block reductions, a ticket
-// and 8 lanes per partial sum for the finishing workgroup to collect, so a launch of few entries gives a lane
-// LH_SC_ENTRIES_PER_LANE of them (default 4) rather than one - but never fewer than two workgroups per CU
+// and 8 lanes per partial sum for the finishing workgroup to collect, so a launch of few entries gives a lane 4 of them
+// rather than one - but never fewer than two workgroups per CU, and at most 8 workgroups per CU (grid-stride loops)
 static size_t sc_entry_grid(const Ctx& c, size_t entries) {
-  static const size_t per_lane = [] {
-    const char* e = getenv("LH_SC_ENTRIES_PER_LANE");
-    return e && atoi(e) > 0 ? (size_t)atoi(e) : (size_t)4;
-  }();
-  const size_t full = (entries + 255) / 256, cap = (size_t)c.num_cus * sc_entry_blocks_per_cu();
+  constexpr size_t per_lane = 4;
+  const size_t full = (entries + 255) / 256, cap = (size_t)c.num_cus * 8;
   size_t g = (entries + 256 * per_lane - 1) / (256 * per_lane);
   g = std::max(g, std::min(full, (size_t)c.num_cus * 2));
   return std::max<size_t>(1, std::min(std::min(g, full), cap));
@@ -860,7 +815,7 @@ static size_t sc_entry_grid(const Ctx& c, size_t entries) {
 // (the number of terms is a template parameter: an accumulator array indexed by a run-time term count lives in scratch
 // memory - 400 B per lane of spills doubled the kernel's HBM writes)
 template <int M, bool BIND>
-__global__ __launch_bounds__(256) LH_E_WAVES_ATTR(LH_E_WAVES_OPEN) void sc_round_open_kernel(ScOpenRound rd, size_t size, Fr* __restrict__ partials, ScFinish fin) {
+__global__ __launch_bounds__(256) void sc_round_open_kernel(ScOpenRound rd, size_t size, Fr* __restrict__ partials, ScFinish fin) {
   // one lane per bound entry (see sc_round_e2_kernel): q_m(0) = sum_b E_m[b] v0 comes from the even lanes, q_m(1) from the
   // odd ones - no exchange between lanes at all
   __shared__ Fr lds[4];
@@ -933,7 +888,7 @@ void k_sc_round_open(Ctx& c, const ScOpenRound& rd, bool bind, size_t size, Fr* 
 // products of a lane share one Montgomery reduction (ff.cuh dot): 2 P -> P + ~0.6 P products (fold round: the P
 // multiplications by cs are the fold itself).
 template <int P, bool BIND, bool FOLD>
-__global__ __launch_bounds__(256) LH_E_WAVES_ATTR(LH_E_WAVES_RW) void sc_round_rw_kernel(ScRwRound rd, size_t size, Fr* __restrict__ partials, ScFinish fin) {
+__global__ __launch_bounds__(256) void sc_round_rw_kernel(ScRwRound rd, size_t size, Fr* __restrict__ partials, ScFinish fin) {
   // one lane per bound entry (see sc_round_e2_kernel): odd lanes evaluate X = 1, even lanes X = 2
   __shared__ Fr lds[4];
   Fr acc = Fr::zero();
@@ -1085,11 +1040,7 @@ void k_sc_round(Ctx& c, const ScRound& rd, int degree, bool bind, size_t size, F
 
   // large rounds: one thread per pair keeps everything in registers; in between, one thread per
   // (pair, term) so that a launch that cannot fill the chip is not also a long dependent chain
-  static const size_t tp_max = [] {
-    const char* e = getenv("LH_SC_TP_MAX_ITEMS");
-    return e ? (size_t)atoll(e) : ((size_t)1 << 17);
-  }();
-  const uint32_t tp = (rd.num_terms > 1 && size * rd.num_terms <= tp_max) ? rd.num_terms : 1u;
+  const uint32_t tp = (rd.num_terms > 1 && size * rd.num_terms <= ((size_t)1 << 17)) ? rd.num_terms : 1u;
   if (degree == 2 && rd.eq_level && tp == 1) {
     // the factored degree-2 rounds (GKR layers, Surge over one table): one lane per bound entry
     size_t g2 = sc_entry_grid(c, 2 * size);

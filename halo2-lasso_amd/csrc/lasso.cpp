@@ -182,10 +182,7 @@ LassoColumns lasso_witness_columns(Ctx& c, const lh_lasso_table& tb, size_t n, c
   }
   // LH_SHARDED_COUNTERS_MIN_R=1 (tests): a world of one takes the repartitioned counters too (the personalised exchange
   // then has one peer, itself: the transport's point-to-point path on a one-GPU box)
-  static const size_t counters_min_r = [] {
-    const char* e = getenv("LH_SHARDED_COUNTERS_MIN_R");
-    return e && atoi(e) >= 1 ? (size_t)atoi(e) : (size_t)2;
-  }();
+  const size_t counters_min_r = (size_t)knob(Knob::SHARDED_COUNTERS_MIN_R);
   keep_sorted = keep_sorted && !(sh.on && sh.R >= counters_min_r);
   if (sh.on && sh.R >= counters_min_r) {
     lasso_counters_sharded(c, sh, d_dims, cc, n, l, w.rts.data(), w.fcs.data());
@@ -477,7 +474,7 @@ void lasso_prove(Ctx& c, const LassoPcs& pcs, const lh_lasso_table& tb, size_t n
   Fr* a = nullptr;
   uint32_t* a_small = nullptr;
   // (the sorted dim columns only pay off where the MSM sorts slab by slab: msm.hip LH_MSM_SLAB_LOG)
-  LassoColumns w = lasso_witness_columns(c, tb, n, d_dims, &a, &a_small, (int)n >= msm_slab_log());
+  LassoColumns w = lasso_witness_columns(c, tb, n, d_dims, &a, &a_small, n >= (size_t)knob(Knob::MSM_SLAB_LOG));
   std::vector<uint32_t*>&rts = w.rts, &fcs = w.fcs, &E = w.E;
   lap(0);
   // ---- 0/1: domain separation + commitments (one batched MSM)

@@ -179,8 +179,7 @@ HFr mkzg_open(Ctx& c, const Srs& srs, const Fr* d_poly, size_t num_vars, const H
   }
   // development (LH_OPEN_SMALL_CHECK): the column-wise levels whose quotient exists are committed the plain way too and
   // compared (stderr)
-  static const bool self_check_env = getenv("LH_OPEN_SMALL_CHECK") != nullptr;
-  const bool self_check = self_check_env && small;
+  const bool self_check = knob(Knob::OPEN_SMALL_CHECK) != 0 && small;
   const size_t check_from = d_poly ? 0 : 1;  // (the first fold of a lazy g' leaves no quotient to compare with)
   // quotients back to back: the sharded levels (local halves) from the top down, then - replicated - the flat layout of
   // the small levels (q_i at offset 2^i - 1)
@@ -200,7 +199,7 @@ HFr mkzg_open(Ctx& c, const Srs& srs, const Fr* d_poly, size_t num_vars, const H
       std::vector<Fr> cf;
       for (size_t k = 0; k < small->cols.size(); k++)
         if (!small->coef[k].is_zero()) cp.push_back(small->cols[k].ptr), cl.push_back(small->cols[k].len), cf.push_back(dev(small->coef[k]));
-      static const bool from_cols = !(getenv("LH_OPEN_FOLD_COLS") && atoi(getenv("LH_OPEN_FOLD_COLS")) == 0);  // (development A/B)
+      const bool from_cols = knob(Knob::OPEN_FOLD_COLS) != 0;  // (development A/B)
       if (!(from_cols && !cp.empty() && k_lincomb_fold_small(c, cp.data(), cl.data(), cf.data(), cp.size(), half, dev(point[i]), dst))) {
         if (small->ensure_merged) small->ensure_merged();
         k_lincomb_fold(c, small->merged.data(), small->merged_w.data(), small->merged.size(), half, dev(point[i]), dst);

@@ -592,34 +592,16 @@ __global__ void msm_derived_gather_kernel(MsmDerivedDev dd, const G1Xyzz* __rest
 }
 
 // ------------------------------------------------------------------ host driver
-static int env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e && *e ? atoi(e) : dflt;
-}
-// tuning knobs (development): window = floor(log2 n) - LH_MSM_C_OFF capped at LH_MSM_C_MAX; LH_MSM_K = entries per
-// accumulate thread (0: by batch size)
-static const int MSM_C_OFF = env_int("LH_MSM_C_OFF", 4), MSM_C_MAX = env_int("LH_MSM_C_MAX", 17),
-                 MSM_K = env_int("LH_MSM_K", 0),
-                 MSM_QUAD_MAX = env_int("LH_MSM_QUAD_MAX", 262144);  // lists / segment counts up to which a quad of lanes
-                                                                      // shares one curve addition (0: never)
-
-int msm_slab_log() {
-  // (2^23 while every slab was a library call of its own; the batched sort has no per-slab cost: 2^16, tools sweep in
-  // profiles/README.md round 3)
-  static const int v = env_int("LH_MSM_SLAB_LOG", 16);
-  return v;
-}
 
 // the continuation levels of one list: linear levels (fan-in K2) while the list is long, tree levels at the end
 static void msm_continuation_levels(Ctx& c, hipStream_t stream, const uint32_t* ckey, const G1Xyzz* cpt, size_t n_in, G1Xyzz* buckets,
                                     uint32_t* cnt) {
-  static const int MSM_K2 = env_int("LH_MSM_K2", 4);  // continuation fan-in: a level costs ~K2 dependent additions, there
-                                                      // are log_K2(chunks) levels; swept 2..16, 3-4 is best (2^16: 10.1 -> 9.3 ms)
-  static const int TREE_MAX = env_int("LH_MSM_TREE_MAX", 262144);  // lists of up to this many slots go by trees (0: never; sweep: profiles/r04_ab_msm_tree.txt)
-  const uint32_t K2 = (uint32_t)MSM_K2;
+  // continuation fan-in K2: a level costs ~K2 dependent additions, there are log_K2(chunks) levels; swept 2..16, 3-4 is
+  // best (2^16: 10.1 -> 9.3 ms).  Lists of up to LH_MSM_TREE_MAX slots go by trees (sweep: profiles/r04_ab_msm_tree.txt)
+  const uint32_t K2 = (uint32_t)knob(Knob::MSM_K2);
   int lvl = 0;
   while (true) {
-    const bool tree = n_in <= (size_t)TREE_MAX;
+    const bool tree = n_in <= (size_t)knob(Knob::MSM_TREE_MAX);
     const size_t fan = tree ? (size_t)64 : (size_t)K2;  // (256-slot tiles measured slower: profiles/r04_ab_msm_tree.txt)
     const size_t nc = (n_in + fan - 1) / fan;
     uint32_t* okey = c.arena.alloc_n<uint32_t>(nc);
@@ -627,7 +609,7 @@ static void msm_continuation_levels(Ctx& c, hipStream_t stream, const uint32_t* 
     if (tree)
       hipLaunchKernelGGL((msm_accumulate_tree_quad_kernel<64>), dim3((unsigned)std::min<size_t>(nc, 1 << 16)), dim3(256), 0,
                          stream, ckey, cpt, n_in, buckets, okey, opt, cnt + lvl, cnt + lvl + 1);
-    else if (n_in <= (size_t)MSM_QUAD_MAX)  // far below one wave per SIMD: a quad of lanes per entry
+    else if (n_in <= (size_t)knob(Knob::MSM_QUAD_MAX))  // far below one wave per SIMD: a quad of lanes per entry (0: never)
       hipLaunchKernelGGL(msm_accumulate_n_quad_kernel, dim3((unsigned)((4 * n_in + 127) / 128)), dim3(128), 0, stream,
                          ckey, cpt, n_in, K2, buckets, okey, opt, cnt + lvl, cnt + lvl + 1);
     else
@@ -645,9 +627,9 @@ static void msm_continuation_levels(Ctx& c, hipStream_t stream, const uint32_t* 
 static uint32_t pick_window(size_t n, uint32_t bits) {
   uint32_t lg = 0;
   while (((size_t)1 << (lg + 1)) <= n) lg++;
-  int c = (int)lg - MSM_C_OFF;
+  int c = (int)lg - (int)knob(Knob::MSM_C_OFF);
   if (c < 4) c = 4;
-  if (c > MSM_C_MAX) c = MSM_C_MAX;
+  if (c > (int)knob(Knob::MSM_C_MAX)) c = (int)knob(Knob::MSM_C_MAX);
   if ((uint32_t)c > bits) c = (int)bits;
   return (uint32_t)c;
 }
@@ -727,8 +709,8 @@ static std::vector<char> msm_pick_split(Ctx& c, const MsmJob* jobs, const std::v
     if (parent[j] >= 0) T[parent[j]] += T[j], T[j] = 0;
   }
   // (LH_MSM_HALF_MIN_LOG below 16 is a test shape: every batch with two jobs that have entries is split, whatever its size)
-  static const size_t min_entries = (size_t)env_int("LH_MSM_HALF_MIN_LOG", 24);
-  static const int cover = env_int("LH_MSM_HALF_COVER", 12);  // entries of the second half per bucket of the first
+  const size_t min_entries = (size_t)knob(Knob::MSM_HALF_MIN_LOG);
+  const size_t cover = (size_t)knob(Knob::MSM_HALF_COVER);  // entries of the second half per bucket of the first
   const bool forced = min_entries < 16;  // (16 .. 23: a lower threshold with the floors below in force - measurements)
   if (Et < ((size_t)1 << min_entries) || (!forced && Tt < ((size_t)1 << 17))) return {};
   std::vector<size_t> order;
@@ -740,7 +722,7 @@ static std::vector<char> msm_pick_split(Ctx& c, const MsmJob* jobs, const std::v
   });
   size_t Eb = 0, Tb = 0, taken = 0;
   for (size_t j : order) {
-    if (Eb >= (size_t)cover * (Tt - Tb) || taken + 1 == order.size()) break;
+    if (Eb >= cover * (Tt - Tb) || taken + 1 == order.size()) break;
     second[j] = 1, Eb += E[j], Tb += T[j], taken++;
   }
   // worth it only when the first half has tails to hide and both halves still fill the chip
@@ -775,14 +757,14 @@ static void msm_plan_sub(Ctx& c, const MsmJob* jobs, MsmSub& s, const MsmSub* wh
       const uint32_t cw = pick_window(in.n, bits);
       est += ((size_t)(bits + cw) / cw) << (in.scalars_u32 ? cw : cw - 1);
     }
-    static const int forced = env_int("LH_MSM_SEG", 0);
-    seg_size = forced ? (uint32_t)forced : est <= ((size_t)1 << 18) ? 4u : est <= ((size_t)1 << 20) ? 8u : 16u;
+    const uint32_t forced = (uint32_t)knob(Knob::MSM_SEG);
+    seg_size = forced ? forced : est <= ((size_t)1 << 18) ? 4u : est <= ((size_t)1 << 20) ? 8u : 16u;
     if (whole) seg_size = whole->seg_size;
     s.seg_size = seg_size;
   }
   uint32_t key = 0, seg = 0, win = 0;
   // a job of >= 2^LH_MSM_SLAB_LOG points sorts each of its (window) slabs by the digit bits alone
-  static const int slab_log = msm_slab_log();
+  const int slab_log = (int)knob(Knob::MSM_SLAB_LOG);  // (2^16: sweep in profiles/README.md round 3)
   for (size_t j = 0; j < nj; j++) {
     const MsmJob& in = jobs[s.idx[j]];
     MsmJobDev& jd = plan.job[j];
@@ -850,15 +832,15 @@ static void msm_plan_sub(Ctx& c, const MsmJob* jobs, MsmSub& s, const MsmSub* wh
       if (!pass) s.small_entries = s.max_entries;
     }
   s.nbuckets = key, s.nsegs = seg, s.nwins = win;
-  if (getenv("LH_MSM_DEBUG"))
+  if (knob(Knob::MSM_DEBUG) != 0)
     for (size_t j = 0; j < nj; j++)
       fprintf(stderr, "[msm] job %zu n %u bits %u c %u W %u entries %zu%s%s%s%s\n", s.idx[j], plan.job[j].n, s.bits[j], plan.job[j].c,
               plan.job[j].W, (size_t)plan.job[j].n * plan.job[j].W, plan.job[j].is_signed ? " fr" : " u32",
               s.derived[j] ? " derived" : "", plan.job[j].merged ? " table" : "", plan.job[j].pack_shift ? " packed" : "");
   // two-level reduction: throughput-bound batches (the plain segment kernel runs), jobs whose windows hold at least
   // MSM_GROUP^2 segments, packed jobs only when a group never straddles a change of the high part
-  static const int two_level_on = env_int("LH_MSM_TWO_LEVEL", 1);
-  const bool plain_reduce = whole ? whole->plain_reduce : s.nsegs > (size_t)MSM_QUAD_MAX / 2;
+  const bool two_level_on = knob(Knob::MSM_TWO_LEVEL) != 0;
+  const bool plain_reduce = whole ? whole->plain_reduce : s.nsegs > (size_t)knob(Knob::MSM_QUAD_MAX) / 2;
   s.plain_reduce = plain_reduce;
   s.ngroups = 0;
   for (size_t j = 0; j < nj; j++) {
@@ -892,10 +874,9 @@ static void msm_plan_sub(Ctx& c, const MsmJob* jobs, MsmSub& s, const MsmSub* wh
   s.total_pts = s.full_pts = 0;
   for (size_t j = 0; j < nj; j++) s.total_pts += plan.job[j].n, s.full_pts += plan.job[j].is_u32 ? 0 : plan.job[j].n;
   // entries per accumulate thread: enough chunks to fill the chip, few enough that the continuation list stays small
-  // (measured: tools/msm_sweep.sh; 2^24 lookups 141 -> 132 ms with K 32 -> 128)
+  // (measured: tools/history/msm_sweep.sh; 2^24 lookups 141 -> 132 ms with K 32 -> 128)
   const size_t me = s.max_entries;
   s.K = me > ((size_t)1 << 26) ? 128 : me > ((size_t)1 << 25) ? 64 : me > ((size_t)1 << 23) ? 32 : me > ((size_t)1 << 21) ? 16 : me > ((size_t)1 << 18) ? 8 : 4;
-  if (MSM_K > 0) s.K = (uint32_t)MSM_K;
   if (whole) s.K = whole->K;
   s.nchunks = (me + s.K - 1) / s.K;
   s.wins.assign(s.nshares, G1Xyzz::identity());
@@ -1262,7 +1243,7 @@ bool msm_batch(Ctx& c, const MsmJob* jobs, size_t num_jobs, G1Affine* out_host, 
       }
       c.host_stamp("msm:window_sums");
       for (MsmSub& s : subs) {
-        if (getenv("LH_MSM_DEBUG")) {
+        if (knob(Knob::MSM_DEBUG) != 0) {
           uint32_t h_cnt[16];
           c.d2h(h_cnt, s.lvl_cnt, sizeof(h_cnt));
           fprintf(stderr, "[msm] jobs %zu entries %zu K %u nchunks %zu buckets %zu%s | continuation counts:", s.idx.size(), s.max_entries,

@@ -374,7 +374,7 @@ SumCheckResult sum_check_loop(Ctx& c, int prover_kind, size_t num_vars, int degr
       rd.r = dev(r_prev);
       const uint32_t seq0 = c.flag_seq + 1;
       c.flag_seq += (uint32_t)rounds + 1;
-      static const bool tail_debug = getenv("LH_SC_DEBUG") != nullptr;
+      const bool tail_debug = knob(Knob::SC_DEBUG) != 0;
       const auto t_tail = std::chrono::steady_clock::now();
       ProfScope ps(c, "sc_tail", 0, 0, (double)n0);
       struct Guard {  // never leave the kernel polling: tell it to go, then wait until it is gone
@@ -779,7 +779,7 @@ static SumCheckResult sum_check_prove_impl(Ctx& c, int prover_kind, size_t num_v
   Fr u32_r0;
   bool u32_bound = false;
   if (u32.col) {
-    static const bool u32_off = getenv("LH_SC_U32") && atoi(getenv("LH_SC_U32")) == 0;  // (development A/B)
+    const bool u32_off = knob(Knob::SC_U32) == 0;  // (development A/B)
     u32_rounds = !u32_off && use_ef && !ef.per_term && !sharded && !rw && num_polys == 1 && rd.num_terms == 1 && rd.nfac[0] == 1 &&
                  rd.fac[0][0] == 0 && rd.coeff_is_one[0] && degree == 2 && sum_is_exact && streams2 && num_vars >= 6 &&
                  k_sc_round_streams(rd, degree, len0 >> 3) &&
@@ -792,12 +792,11 @@ static SumCheckResult sum_check_prove_impl(Ctx& c, int prover_kind, size_t num_v
   std::vector<Fr> u32t_sums;  // [term][4]: sum over the term's columns of w_k S_t(col_k)
   Fr u32t_r0;
   if (!u32t.polys.empty()) {
-    static const bool u32t_off = getenv("LH_OPEN_U32_ROUNDS") && atoi(getenv("LH_OPEN_U32_ROUNDS")) == 0;  // (development A/B)
+    const bool u32t_off = knob(Knob::OPEN_U32_ROUNDS) == 0;  // (development A/B)
     LH_REQUIRE(u32t.polys.size() == num_polys, LH_ERR_ARG, "sum-check: the column hint does not match the polys");
     // (from 2^22 entries on: below that the ~11 quad-sum launches of a proof are latency - 2^20 AND 11.35 -> 12.1 ms, 2^20 range
-    //  +0.15, 2^21 even, 2^22 range -0.25 ms; LH_OPEN_U32_MIN_VARS: development A/B)
-    static const size_t u32t_min_vars = getenv("LH_OPEN_U32_MIN_VARS") ? (size_t)atoi(getenv("LH_OPEN_U32_MIN_VARS")) : 22;
-    bool ok = !u32t_off && use_ef && ef.per_term && !sharded && degree == 2 && streams2 && num_vars >= u32t_min_vars &&
+    //  +0.15, 2^21 even, 2^22 range -0.25 ms; profiles/README.md round 6)
+    bool ok = !u32t_off && use_ef && ef.per_term && !sharded && degree == 2 && streams2 && num_vars >= 22 &&
               k_sc_round_streams(rd, degree, len0 >> 3) &&
               (len0 >> 2) > std::max<size_t>(k_sc_tail_capacity(c, rd, degree), (size_t)GKR_CAP * GKR_CAP);
     for (const Ctx::ScU32Terms::Poly& pl : u32t.polys) {

@@ -526,15 +526,14 @@ print("proof", hashlib.sha256(t.into_proof()).hexdigest())
 @pytest.mark.heavy(est=5)
 def test_round6_route_switches_change_the_route_not_the_bytes():
     """Round 6's routes each have an environment switch for A/B timing: the fence-free hand-off of the round
-    kernels, Surge's and the batch opening's first rounds from the 32-bit columns, the opening's fold from the columns, the
-    sort's XCD tile order.  A 2^22 range-check proof made with all of them OFF (a child process: they are read once) is byte
+    kernels, Surge's and the batch opening's first rounds from the 32-bit columns, the opening's fold from the columns.  A
+    2^22 range-check proof made with all of them OFF (a child process: they are read once) is byte
     for byte the proof made with the defaults - which test_lasso_default_route_at_2p21_matches_cpp_oracle pins to the oracle."""
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    off = {"LH_FIN_LANES_MIN_BYTES": "-1", "LH_SC_U32": "0", "LH_OPEN_U32_ROUNDS": "0", "LH_OPEN_FOLD_COLS": "0",
-           "LH_SORT_XCD_ORDER": "0"}
+    off = {"LH_FIN_LANES_MIN_BYTES": "-1", "LH_SC_U32": "0", "LH_OPEN_U32_ROUNDS": "0", "LH_OPEN_FOLD_COLS": "0"}
     got = []
     for env in ({}, off):
         r = subprocess.run([sys.executable, "-c", _ROUTE_HASH % root, "22", "range"], cwd=root, env=dict(os.environ, **env),
