@@ -47,6 +47,17 @@ pub struct lh_transcript {
     pub read_commitment: Option<G1OutCb>,
 }
 
+pub type HashCb = unsafe extern "C" fn(*mut c_void, *const u8) -> c_int;
+pub type HashOutCb = unsafe extern "C" fn(*mut c_void, *mut u8) -> c_int;
+
+// TranscriptWrite / TranscriptRead<Output<Keccak256>, Fr> (transcript.rs:240-265): 32 raw bytes, not absorbed
+#[repr(C)]
+pub struct lh_hash_transcript {
+    pub user: *mut c_void,
+    pub write_hash: Option<HashCb>,
+    pub read_hash: Option<HashOutCb>,
+}
+
 #[repr(C)]
 pub struct lh_sop {
     pub num_terms: u32,
@@ -283,4 +294,36 @@ extern "C" {
                                out: *mut core::ffi::c_char, cap: usize, len: *mut usize) -> lh_status;
     // Zeromorph over univariate KZG: lh_ukzg_setup, lh_usrs_*, lh_zeromorph_* follow the same shapes
     // (include/lasso_hip.h, section f3) and are bound the same way when HyperPlonk<Zeromorph<..>> is wanted.
+    // Brakedown (include/lasso_hip.h, section f4); params and commitments are opaque here
+    pub fn lh_keccak_transcript_hash_io(t: *mut lh_transcript, out: *mut lh_hash_transcript) -> lh_status;
+    pub fn lh_brakedown_setup(ctx: *mut lh_ctx, num_vars: usize, spec: c_int, seed32: *const u8,
+                              out: *mut *mut c_void) -> lh_status;
+    pub fn lh_brakedown_derive(num_vars: usize, spec: c_int, out: *mut *mut c_void) -> lh_status;
+    pub fn lh_brakedown_param_info(pp: *const c_void, row_len: *mut usize, num_rows: *mut usize,
+                                   codeword_len: *mut usize, num_column_opening: *mut usize,
+                                   num_proximity_testing: *mut usize) -> lh_status;
+    pub fn lh_brakedown_trim(pp: *const c_void, poly_size: usize) -> lh_status;
+    pub fn lh_brakedown_param_free(pp: *mut c_void);
+    pub fn lh_brakedown_encode(pp: *const c_void, msg: *const Fr, out: *mut Fr) -> lh_status;
+    pub fn lh_brakedown_commit(ctx: *mut lh_ctx, pp: *const c_void, d_poly: *const Fr, num_vars: usize,
+                               out: *mut *mut c_void) -> lh_status;
+    pub fn lh_brakedown_batch_commit(ctx: *mut lh_ctx, pp: *const c_void, d_polys: *const *const Fr, num_polys: usize,
+                                     num_vars: usize, out: *mut *mut c_void) -> lh_status;
+    pub fn lh_brakedown_comm_root(comm: *const c_void, out32: *mut u8) -> lh_status;
+    pub fn lh_brakedown_comm_rows(ctx: *mut lh_ctx, comm: *const c_void, out: *mut Fr) -> lh_status;
+    pub fn lh_brakedown_comm_rows_device(comm: *const c_void, d_out: *mut *mut Fr) -> lh_status;
+    pub fn lh_brakedown_comm_free(comm: *mut c_void);
+    pub fn lh_brakedown_open(ctx: *mut lh_ctx, pp: *const c_void, d_poly: *const Fr, num_vars: usize, comm: *mut c_void,
+                             point: *const Fr, t: *mut lh_transcript, ht: *mut lh_hash_transcript) -> lh_status;
+    pub fn lh_brakedown_batch_open(ctx: *mut lh_ctx, pp: *const c_void, num_vars: usize, d_polys: *const *const Fr,
+                                   comms: *const *mut c_void, num_polys: usize, points: *const Fr, num_points: usize,
+                                   evals: *const lh_evaluation, num_evals: usize, t: *mut lh_transcript,
+                                   ht: *mut lh_hash_transcript) -> lh_status;
+    pub fn lh_brakedown_read_commitments(pp: *const c_void, num: usize, ht: *mut lh_hash_transcript,
+                                         out: *mut u8) -> lh_status;
+    pub fn lh_brakedown_verify(pp: *const c_void, root32: *const u8, point: *const Fr, num_vars: usize,
+                               eval: *const Fr, t: *mut lh_transcript, ht: *mut lh_hash_transcript) -> lh_status;
+    pub fn lh_brakedown_batch_verify(pp: *const c_void, num_vars: usize, roots: *const u8, num_comms: usize,
+                                     points: *const Fr, num_points: usize, evals: *const lh_evaluation,
+                                     num_evals: usize, t: *mut lh_transcript, ht: *mut lh_hash_transcript) -> lh_status;
 }

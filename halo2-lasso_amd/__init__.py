@@ -304,6 +304,27 @@ class Keccak256Transcript:
         for pt in pts:
             self.write_commitment(pt)
 
+    def hash_io(self):
+        """the lh_hash_transcript of this transcript: TranscriptWrite/Read<Output<Keccak256>, Fr>"""
+        if getattr(self, "_hio", None) is None:
+            hio = _ffi.lh_hash_transcript()
+            _check(self.lib.lh_keccak_transcript_hash_io(self.p, C.byref(hio)))
+            self._hio = hio
+        return self._hio
+
+    def write_hash(self, h):
+        """32 raw bytes into the stream, not absorbed (util/transcript.rs:259-265)"""
+        h = bytes(h)
+        if len(h) != 32:
+            raise ArgumentError("a Keccak-256 output is 32 bytes")
+        hio = self.hash_io()
+        _check(hio.write_hash(hio.user, (C.c_uint8 * 32).from_buffer_copy(h)))
+
+    def read_hash(self):
+        hio, out = self.hash_io(), (C.c_uint8 * 32)()
+        _check(hio.read_hash(hio.user, out))
+        return bytes(out)
+
     def into_proof(self):
         ptr, n = C.POINTER(C.c_uint8)(), C.c_size_t()
         _check(self.lib.lh_keccak_transcript_proof(self.p, C.byref(ptr), C.byref(n)))
@@ -847,6 +868,162 @@ class Zeromorph:
         flat = [v for p in points for v in p]
         _check(vp.lib.lh_zeromorph_batch_verify(vp.h, num_vars, _g1_array(comms), len(comms), _fr_array(flat),
                                                 len(points), _evaluations(evals), len(evals), transcript.p))
+
+
+# ------------------------------------------------------------------ pcs::multilinear::brakedown
+class BrakedownParam:
+    """MultilinearBrakedownParams (pcs/multilinear/brakedown.rs:35-41): the code's parameters and sparse matrices, drawn
+    from a 32-byte seed (DESIGN.md §12).  Set up with a Context the matrices are also on its device (prover param);
+    it is its own prover and verifier param, as in the reference."""
+
+    def __init__(self, ctx, handle, num_vars, spec):
+        self.ctx, self.h, self.num_vars, self.spec = ctx, handle, num_vars, spec
+        self.lib = _ffi.load()
+        v = [C.c_size_t() for _ in range(5)]
+        _check(self.lib.lh_brakedown_param_info(self.h, *[C.byref(x) for x in v]))
+        (self.row_len, self.num_rows, self.codeword_len, self.num_column_opening,
+         self.num_proximity_testing) = [x.value for x in v]
+
+    def info(self):
+        return (self.row_len, self.num_rows, self.codeword_len, self.num_column_opening, self.num_proximity_testing)
+
+    def encode(self, msg):
+        """LinearCodes::encode on the host (util/code/brakedown.rs:88-125): row_len values -> codeword_len values"""
+        if len(msg) != self.row_len:
+            raise ArgumentError("brakedown encode: expected %d values" % self.row_len)
+        out = (lh_fr * self.codeword_len)()
+        _check(self.lib.lh_brakedown_encode(self.h, _fr_array(msg), out))
+        return _fr_list(out, self.codeword_len)
+
+    def free(self):
+        if self.h:
+            self.lib.lh_brakedown_param_free(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class BrakedownVerifierParam(BrakedownParam):
+    """the host-only param a verifier holds (setup without a device)"""
+
+    @classmethod
+    def derive(cls, num_vars, spec):
+        """the parameters alone, without matrices: info() and trim only"""
+        h = C.c_void_p()
+        _check(_ffi.load().lh_brakedown_derive(num_vars, spec, C.byref(h)))
+        return cls(None, h, num_vars, spec)
+
+    @classmethod
+    def setup(cls, num_vars, spec, seed):
+        h = C.c_void_p()
+        _check(_ffi.load().lh_brakedown_setup(None, num_vars, spec, bytes(seed), C.byref(h)))
+        return cls(None, h, num_vars, spec)
+
+
+class BrakedownCommitment:
+    """MultilinearBrakedownCommitment (brakedown.rs:55-60): the encoded rows and the Merkle tree stay on the device"""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.h, self.lib = ctx, handle, _ffi.load()
+        root = C.create_string_buffer(32)
+        _check(self.lib.lh_brakedown_comm_root(self.h, root))
+        self.root = root.raw
+
+    def rows(self, num_rows, codeword_len):
+        out = C.create_string_buffer(32 * num_rows * codeword_len)
+        _check(self.lib.lh_brakedown_comm_rows(self.ctx.h, self.h, out))
+        return frs_from_bytes(out.raw)
+
+    def rows_device_ptr(self):
+        p = C.c_void_p()
+        _check(self.lib.lh_brakedown_comm_rows_device(self.h, C.byref(p)))
+        return p.value
+
+    def free(self):
+        if self.h:
+            self.lib.lh_brakedown_comm_free(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class Brakedown:
+    """MultilinearBrakedown<bn256::Fr, Keccak256, BrakedownSpec1..6> (pcs/multilinear/brakedown.rs:89-417)"""
+
+    @staticmethod
+    def setup(ctx, num_vars, spec, seed):
+        """setup with poly_size = 2^num_vars; the matrices from `seed` (32 bytes) instead of an RngCore"""
+        h = C.c_void_p()
+        _check(_ffi.load().lh_brakedown_setup(ctx.h if ctx is not None else None, num_vars, spec, bytes(seed),
+                                              C.byref(h)))
+        return BrakedownParam(ctx, h, num_vars, spec)
+
+    @staticmethod
+    def trim(param, poly_size):
+        """brakedown.rs:112-126: (pp, vp) = (param, param) when poly_size == 2^num_vars, else InvalidPcsParam"""
+        _check(param.lib.lh_brakedown_trim(param.h, poly_size))
+        return param, param
+
+    @staticmethod
+    def batch_commit(pp, polys):
+        if not polys:
+            return []
+        out = (C.c_void_p * len(polys))()
+        _check(pp.lib.lh_brakedown_batch_commit(pp.ctx.h, pp.h, _ptr_array(polys), len(polys), polys[0].num_vars, out))
+        return [BrakedownCommitment(pp.ctx, C.c_void_p(out[i])) for i in range(len(polys))]
+
+    @staticmethod
+    def commit(pp, poly):
+        return Brakedown.batch_commit(pp, [poly])[0]
+
+    @staticmethod
+    def batch_commit_and_write(pp, polys, transcript):
+        """roots written as raw stream bytes, not absorbed (util/transcript.rs:259-265)"""
+        comms = Brakedown.batch_commit(pp, polys)
+        for c in comms:
+            transcript.write_hash(c.root)
+        return comms
+
+    @staticmethod
+    def open(pp, poly, comm, point, transcript):
+        _check(pp.lib.lh_brakedown_open(pp.ctx.h, pp.h, poly.ptr, poly.num_vars, comm.h, _fr_array(point), transcript.p,
+                                        C.byref(transcript.hash_io())))
+
+    @staticmethod
+    def batch_open(pp, num_vars, polys, comms, points, evals, transcript):
+        for p in points:
+            if len(p) != num_vars:
+                raise InvalidPcsParam("Invalid point (expect point to have %d variates but got %d)" % (num_vars, len(p)))
+        flat = [v for p in points for v in p]
+        _check(pp.lib.lh_brakedown_batch_open(pp.ctx.h, pp.h, num_vars, _ptr_array(polys), _ptr_array([c.h.value for c in comms]), len(polys),
+                                              _fr_array(flat), len(points), _evaluations(evals), len(evals),
+                                              transcript.p, C.byref(transcript.hash_io())))
+
+    @staticmethod
+    def read_commitments(vp, num, transcript):
+        out = C.create_string_buffer(32 * max(num, 1))
+        _check(vp.lib.lh_brakedown_read_commitments(vp.h, num, C.byref(transcript.hash_io()), out))
+        return [out.raw[32 * i:32 * i + 32] for i in range(num)]
+
+    @staticmethod
+    def verify(vp, root, point, eval_, transcript):
+        _check(vp.lib.lh_brakedown_verify(vp.h, bytes(root), _fr_array(point), len(point), _fr_array([eval_]),
+                                          transcript.p, C.byref(transcript.hash_io())))
+
+    @staticmethod
+    def batch_verify(vp, num_vars, roots, points, evals, transcript):
+        flat = [v for p in points for v in p]
+        _check(vp.lib.lh_brakedown_batch_verify(vp.h, num_vars, b"".join(bytes(r) for r in roots), len(roots),
+                                                _fr_array(flat), len(points), _evaluations(evals), len(evals),
+                                                transcript.p, C.byref(transcript.hash_io())))
 
 
 # ------------------------------------------------------------------ Lasso

@@ -121,6 +121,13 @@ class lh_transcript(C.Structure):
                 ("read_field_element", _FE_CB), ("read_commitment", _G1_CB)]
 
 
+_HASH_W_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint8))
+
+
+class lh_hash_transcript(C.Structure):
+    _fields_ = [("user", C.c_void_p), ("write_hash", _HASH_W_CB), ("read_hash", _HASH_W_CB)]
+
+
 class lh_g2(C.Structure):
     _fields_ = [("x_c0", C.c_uint64 * 4), ("x_c1", C.c_uint64 * 4), ("y_c0", C.c_uint64 * 4), ("y_c1", C.c_uint64 * 4)]
 
@@ -253,6 +260,30 @@ SIGNATURES = {
                                                         C.POINTER(C.POINTER(lh_fr)), C.POINTER(lh_transcript)]),
     "lh_debug_jit_source": (C.c_int, [C.POINTER(C.c_uint32), _SZ, C.c_uint32, C.c_uint32, C.c_int, C.c_char_p, _SZ,
                                       C.POINTER(_SZ)]),
+    "lh_keccak_transcript_hash_io": (C.c_int, [C.POINTER(lh_transcript), C.POINTER(lh_hash_transcript)]),
+    "lh_brakedown_setup": (C.c_int, [_P, _SZ, C.c_int, C.c_char_p, C.POINTER(_P)]),
+    "lh_brakedown_derive": (C.c_int, [_SZ, C.c_int, C.POINTER(_P)]),
+    "lh_brakedown_param_info": (C.c_int, [_P, C.POINTER(_SZ), C.POINTER(_SZ), C.POINTER(_SZ), C.POINTER(_SZ),
+                                          C.POINTER(_SZ)]),
+    "lh_brakedown_trim": (C.c_int, [_P, _SZ]),
+    "lh_brakedown_param_free": (None, [_P]),
+    "lh_brakedown_encode": (C.c_int, [_P, C.POINTER(lh_fr), C.POINTER(lh_fr)]),
+    "lh_brakedown_commit": (C.c_int, [_P, _P, _P, _SZ, C.POINTER(_P)]),
+    "lh_brakedown_batch_commit": (C.c_int, [_P, _P, C.POINTER(_P), _SZ, _SZ, C.POINTER(_P)]),
+    "lh_brakedown_comm_root": (C.c_int, [_P, C.c_char_p]),
+    "lh_brakedown_comm_rows": (C.c_int, [_P, _P, _P]),
+    "lh_brakedown_comm_rows_device": (C.c_int, [_P, C.POINTER(_P)]),
+    "lh_brakedown_comm_free": (None, [_P]),
+    "lh_brakedown_open": (C.c_int, [_P, _P, _P, _SZ, _P, C.POINTER(lh_fr), C.POINTER(lh_transcript),
+                                    C.POINTER(lh_hash_transcript)]),
+    "lh_brakedown_batch_open": (C.c_int, [_P, _P, _SZ, C.POINTER(_P), C.POINTER(_P), _SZ, C.POINTER(lh_fr), _SZ,
+                                          C.POINTER(lh_evaluation), _SZ, C.POINTER(lh_transcript),
+                                          C.POINTER(lh_hash_transcript)]),
+    "lh_brakedown_read_commitments": (C.c_int, [_P, _SZ, C.POINTER(lh_hash_transcript), C.c_char_p]),
+    "lh_brakedown_verify": (C.c_int, [_P, C.c_char_p, C.POINTER(lh_fr), _SZ, C.POINTER(lh_fr), C.POINTER(lh_transcript),
+                                      C.POINTER(lh_hash_transcript)]),
+    "lh_brakedown_batch_verify": (C.c_int, [_P, _SZ, C.c_char_p, _SZ, C.POINTER(lh_fr), _SZ, C.POINTER(lh_evaluation),
+                                            _SZ, C.POINTER(lh_transcript), C.POINTER(lh_hash_transcript)]),
     "lh_profile_enable": (C.c_int, [_P, C.c_int]),
     "lh_profile_read": (C.c_int, [_P, C.POINTER(lh_prof_rec), _SZ, C.POINTER(_SZ)]),
 }

@@ -1,0 +1,361 @@
+// Brakedown PCS, prover half: MultilinearBrakedown<Fr, Keccak256, BrakedownSpec1..6> (reference
+// pcs/multilinear/brakedown.rs:89-300) over the expander code of util/code/brakedown.rs.
+//   parameters  the spec's formulas in IEEE double (code/brakedown.rs:128-251), row_len by the smallest proof_size;
+//   matrices    a seeded sampler of this library's own, in the reference's draw order;
+//   commit      every row encoded at once, one launch per cascade stage, then the column leaves and the Merkle tree;
+//   open        the combined rows in one pass, then the column openings (paths from a host copy of the tree).
+// Restated in tests/brakedown_ref.py, which the tests compare against byte for byte.
+#include "brakedown.hpp"
+#include <math.h>
+#include <algorithm>
+#include <memory>
+
+namespace lh {
+
+// ------------------------------------------------------------------ parameters
+namespace {
+const double LAMBDA = 128.0;
+const size_t LOG2_Q = 254;  // bn256::Fr::NUM_BITS
+struct Spec {
+  double alpha, beta, r;
+};
+const Spec SPECS[6] = {{0.1195, 0.0284, 1.420}, {0.1380, 0.0444, 1.470}, {0.1780, 0.0610, 1.521},
+                       {0.2000, 0.0820, 1.640}, {0.2110, 0.0970, 1.616}, {0.2380, 0.1205, 1.720}};
+
+size_t ceil_(double v) { return v > 0 ? (size_t)ceil(v) : 0; }  // `v.ceil() as usize` saturates at 0
+double h(double p) {
+  const double q = 1.0 - p;
+  return -p * log2(p) - q * log2(q);
+}
+double mu(const Spec& s) { return s.r - 1.0 - s.r * s.alpha; }
+double nu(const Spec& s) { return s.beta + s.alpha * s.beta + 0.03; }
+size_t c_n(const Spec& s, size_t n_) {
+  const double a = s.alpha, b = s.beta, n = (double)n_;
+  return std::min(std::max(ceil_(1.28 * b * n), ceil_(b * n) + 4),
+                  ceil_(((110.0 / n) + h(b) + a * h(1.28 * b / a)) / (b * log2(a / (1.28 * b)))));
+}
+size_t d_n(const Spec& s, size_t log2_q, size_t n_) {
+  const double a = s.alpha, b = s.beta, r = s.r, m = mu(s), v = nu(s), n = (double)n_;
+  return std::min(ceil_((2.0 * b + ((r - 1.0) + 110.0 / n) / (double)log2_q) * n),
+                  ceil_((r * a * h(b / r) + m * h(v / m) + 110.0 / n) / (a * b * log2(m / v))));
+}
+size_t num_column_opening(const Spec& s) { return ceil_(-LAMBDA / log2(1.0 - (s.beta / s.r) / 3.0)); }
+
+void dimensions(const Spec& s, size_t n, size_t n_0, std::vector<BdDim>& a, std::vector<BdDim>& b) {
+  LH_REQUIRE(n > n_0, LH_ERR_ARG, "brakedown: row length must exceed n_0");
+  a.clear(), b.clear();
+  for (size_t cur = n; cur > n_0;) {
+    const size_t nxt = ceil_((double)cur * s.alpha);
+    a.push_back(BdDim{cur, nxt, std::min(c_n(s, cur), nxt)});
+    cur = nxt;
+  }
+  for (const BdDim& d : a) {
+    const size_t n_prime = ceil_((double)d.m * s.r), total = ceil_((double)d.n * s.r);
+    LH_REQUIRE(total >= d.n + n_prime, LH_ERR_ARG, "brakedown: code dimensions underflow (num_vars too small)");
+    const size_t m_prime = total - d.n - n_prime;
+    b.push_back(BdDim{n_prime, m_prime, std::min(d_n(s, LOG2_Q, d.n), m_prime)});
+  }
+}
+size_t codeword_len(const Spec& s, size_t n, size_t n_0) {
+  std::vector<BdDim> a, b;
+  dimensions(s, n, n_0, a, b);
+  size_t len = a[0].n + b.back().n;
+  for (size_t k = 0; k + 1 < a.size(); k++) len += a[k].m;
+  for (const BdDim& d : b) len += d.m;
+  return len;
+}
+size_t num_proximity_testing(const Spec& s, size_t n, size_t n_0) {
+  return ceil_(LAMBDA / ((double)LOG2_Q - log2((double)codeword_len(s, n, n_0))));
+}
+size_t proof_size(const Spec& s, size_t n_0, size_t c, size_t r) {
+  return (1 + num_proximity_testing(s, c, n_0)) * c + num_column_opening(s) * r;
+}
+size_t log2_ceil(size_t v) {
+  size_t k = 0;
+  while (((size_t)1 << k) < v) k++;
+  return k;
+}
+
+// ------------------------------------------------------------------ the sampler
+struct WordStream {
+  uint8_t seed[32];
+  uint64_t block = 0;
+  uint64_t words[4];
+  int pos = 4;
+  uint64_t next() {
+    if (pos == 4) {
+      uint8_t msg[40], out[32];
+      memcpy(msg, seed, 32);
+      for (int i = 0; i < 8; i++) msg[32 + i] = (uint8_t)(block >> (8 * i));
+      block++;
+      Keccak256 k;
+      k.update(msg, 40);
+      k.finalize_reset(out);
+      memcpy(words, out, 32);
+      pos = 0;
+    }
+    return words[pos++];
+  }
+  uint64_t uniform(uint64_t m) {
+    const unsigned __int128 limit = (((unsigned __int128)1) << 64) / m * m;
+    for (;;) {
+      const uint64_t w = next();
+      if ((unsigned __int128)w < limit) return w % m;
+    }
+  }
+  HFr field() {  // eight words as a little-endian 512-bit integer, reduced mod r
+    uint64_t lo[4], hi[4];
+    for (auto& w : lo) w = next();
+    for (auto& w : hi) w = next();
+    uint8_t b[32];
+    memcpy(b, lo, 32);
+    const HFr l = host::fr_mod_from_le_bytes(b);
+    memcpy(b, hi, 32);
+    const HFr hh = host::fr_mod_from_le_bytes(b);
+    const HFr two256 = HFr::from_canonical(host::FrTag::R1);  // 2^256 mod r
+    return l + hh * two256;
+  }
+};
+
+void sample(WordStream& ws, BdMatrix& mat) {  // SparseMatrix::new (code/brakedown.rs:279-297)
+  const BdDim& d = mat.dim;
+  mat.cols.resize(d.n * d.d);
+  mat.coeffs.resize(d.n * d.d);
+  std::vector<uint32_t> cols;
+  for (size_t i = 0; i < d.n; i++) {
+    cols.clear();
+    while (cols.size() < d.d) {
+      const uint32_t c = (uint32_t)ws.uniform(d.m);
+      if (std::find(cols.begin(), cols.end(), c) == cols.end()) cols.push_back(c);
+    }
+    std::sort(cols.begin(), cols.end());
+    for (size_t k = 0; k < d.d; k++) {
+      mat.cols[i * d.d + k] = cols[k];
+      mat.coeffs[i * d.d + k] = ws.field();
+    }
+  }
+}
+
+void upload(Ctx& c, BdMatrix& mat) {  // transposed CSR, grouped by output index, inputs ascending
+  const BdDim& d = mat.dim;
+  std::vector<uint32_t> ptr(d.m + 1, 0), idx(d.n * d.d);
+  std::vector<HFr> val(d.n * d.d);
+  for (uint32_t col : mat.cols) ptr[col + 1]++;
+  for (size_t j = 0; j < d.m; j++) ptr[j + 1] += ptr[j];
+  std::vector<uint32_t> fill(ptr.begin(), ptr.end() - 1);
+  for (size_t i = 0; i < d.n; i++)
+    for (size_t k = 0; k < d.d; k++) {
+      const uint32_t e = fill[mat.cols[i * d.d + k]]++;
+      idx[e] = (uint32_t)i;
+      val[e] = mat.coeffs[i * d.d + k];
+    }
+  LH_HIP(hipMalloc((void**)&mat.d_ptr, ptr.size() * 4));
+  LH_HIP(hipMalloc((void**)&mat.d_idx, std::max<size_t>(idx.size(), 1) * 4));
+  LH_HIP(hipMalloc((void**)&mat.d_val, std::max<size_t>(val.size(), 1) * 32));
+  LH_HIP(hipMemcpyAsync(mat.d_ptr, ptr.data(), ptr.size() * 4, hipMemcpyHostToDevice, c.stream));
+  if (!idx.empty()) {
+    LH_HIP(hipMemcpyAsync(mat.d_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, c.stream));
+    LH_HIP(hipMemcpyAsync(mat.d_val, val.data(), val.size() * 32, hipMemcpyHostToDevice, c.stream));
+  }
+  c.sync();
+}
+}  // namespace
+
+BdParam::~BdParam() {
+  if (device < 0) return;
+  (void)hipSetDevice(device);
+  for (auto* v : {&a, &b})
+    for (BdMatrix& m : *v) {
+      if (m.d_ptr) (void)hipFree(m.d_ptr);
+      if (m.d_idx) (void)hipFree(m.d_idx);
+      if (m.d_val) (void)hipFree(m.d_val);
+    }
+}
+BdComm::~BdComm() {
+  if (device < 0) return;
+  (void)hipSetDevice(device);
+  if (d_rows) (void)hipFree(d_rows);
+  if (d_hashes) (void)hipFree(d_hashes);
+}
+
+void brakedown_derive(BdParam& p, size_t num_vars, int spec) {
+  LH_REQUIRE(spec >= 1 && spec <= 6, LH_ERR_ARG, "brakedown: spec must be 1..6");
+  LH_REQUIRE(num_vars >= 1 && num_vars <= 40, LH_ERR_ARG, "brakedown: num_vars must be 1..40");
+  const Spec& s = SPECS[spec - 1];
+  p.spec = spec, p.num_vars = num_vars;
+  p.n_0 = std::min<size_t>(20, ((size_t)1 << num_vars) - 1);  // brakedown.rs:102
+  size_t best = SIZE_MAX, row_len = 0;
+  for (size_t log2_n = log2_ceil(p.n_0 + 1); log2_n <= num_vars; log2_n++) {  // Brakedown::new_multilinear
+    const size_t ps = proof_size(s, p.n_0, (size_t)1 << log2_n, (size_t)1 << (num_vars - log2_n));
+    if (ps < best) best = ps, row_len = (size_t)1 << log2_n;
+  }
+  p.row_len = row_len;
+  p.num_rows = ((size_t)1 << num_vars) / row_len;
+  std::vector<BdDim> a, b;
+  dimensions(s, row_len, p.n_0, a, b);
+  p.a.assign(a.size(), BdMatrix());
+  p.b.assign(b.size(), BdMatrix());
+  for (size_t k = 0; k < a.size(); k++) p.a[k].dim = a[k], p.b[k].dim = b[k];
+  p.codeword_len = codeword_len(s, row_len, p.n_0);
+  p.num_column_opening = num_column_opening(s);
+  p.num_proximity_testing = num_proximity_testing(s, row_len, p.n_0);
+  p.depth = log2_ceil(p.codeword_len);
+  LH_REQUIRE(p.codeword_len < ((size_t)1 << 32), LH_ERR_ARG, "brakedown: codeword too long");
+}
+
+BdParam* brakedown_setup(Ctx* c, size_t num_vars, int spec, const uint8_t seed[32]) {
+  std::unique_ptr<BdParam> p(new BdParam());
+  brakedown_derive(*p, num_vars, spec);
+  WordStream ws;
+  memcpy(ws.seed, seed, 32);
+  for (size_t k = 0; k < p->a.size(); k++) sample(ws, p->a[k]), sample(ws, p->b[k]);  // a[0], b[0], a[1], b[1], ..
+  if (c) {
+    p->device = c->device;
+    for (size_t k = 0; k < p->a.size(); k++) upload(*c, p->a[k]), upload(*c, p->b[k]);
+  }
+  return p.release();
+}
+
+void brakedown_trim(const BdParam& p, size_t poly_size) {
+  LH_REQUIRE(poly_size && !(poly_size & (poly_size - 1)), LH_ERR_ARG, "brakedown: poly_size must be a power of two");
+  LH_REQUIRE(poly_size == ((size_t)1 << p.num_vars), LH_ERR_INVALID_PCS_PARAM,
+             "Can't trim MultilinearBrakedownParams into different poly_size");
+}
+
+// ------------------------------------------------------------------ host encoder (code/brakedown.rs:88-125)
+static void dot_into(const BdMatrix& mat, const HFr* in, HFr* out) {
+  const size_t d = mat.dim.d;
+  for (size_t i = 0; i < mat.dim.n; i++)
+    for (size_t k = 0; k < d; k++) out[mat.cols[i * d + k]] += in[i] * mat.coeffs[i * d + k];
+}
+
+void brakedown_encode_host(const BdParam& p, HFr* t) {
+  LH_REQUIRE(!p.a.empty() && p.a[0].cols.size() == p.a[0].dim.n * p.a[0].dim.d, LH_ERR_ARG,
+             "brakedown: parameters without matrices");
+  for (size_t i = p.row_len; i < p.codeword_len; i++) t[i] = HFr::zero();
+  size_t in_off = 0;
+  for (size_t k = 0; k + 1 < p.a.size(); k++) {
+    dot_into(p.a[k], t + in_off, t + in_off + p.a[k].dim.n);
+    in_off += p.a[k].dim.n;
+  }
+  const BdMatrix &al = p.a.back(), &bl = p.b.back();
+  std::vector<HFr> tmp(al.dim.m, HFr::zero());
+  dot_into(al, t + in_off, tmp.data());
+  for (size_t x = 0; x < bl.dim.n; x++) {  // reed_solomon_into: horner(tmp, x) at x = 1, 2, ..
+    const HFr xv = HFr::from_u64(x + 1);
+    HFr acc = HFr::zero();
+    for (size_t k = tmp.size(); k-- > 0;) acc = acc * xv + tmp[k];
+    t[in_off + al.dim.n + x] = acc;
+  }
+  size_t out_off = in_off + al.dim.n + bl.dim.n;
+  in_off += al.dim.n + al.dim.m;
+  for (size_t k = p.a.size(); k-- > 0;) {
+    in_off -= p.a[k].dim.m;
+    dot_into(p.b[k], t + in_off, t + out_off);
+    out_off += p.b[k].dim.m;
+  }
+}
+
+// ------------------------------------------------------------------ commit (brakedown.rs:130-206)
+static void check_vars(const BdParam& p, size_t num_vars, const char* what) {
+  if (num_vars != p.num_vars)  // validate_input (pcs/multilinear.rs:27-70) at the only size a Brakedown param takes
+    throw Error(LH_ERR_INVALID_PCS_PARAM, std::string("Invalid poly or point to ") + what + " (param supports " +
+                                              std::to_string(p.num_vars) + " variates but got " +
+                                              std::to_string(num_vars) + ")");
+}
+
+BdComm* brakedown_commit(Ctx& c, const BdParam& p, const Fr* d_poly, size_t num_vars) {
+  check_vars(p, num_vars, "commit");
+  LH_REQUIRE(p.device == c.device, LH_ERR_ARG, "brakedown: parameters were not set up on this ctx's device");
+  const size_t R = p.num_rows, cw = p.codeword_len, width = (size_t)1 << p.depth;
+  std::unique_ptr<BdComm> comm(new BdComm());
+  comm->num_rows = R, comm->codeword_len = cw, comm->depth = p.depth, comm->device = c.device;
+  LH_HIP(hipMalloc((void**)&comm->d_rows, R * cw * sizeof(Fr)));
+  LH_HIP(hipMalloc((void**)&comm->d_hashes, ((2 * width) - 1) * 32));
+  Fr* rows = comm->d_rows;
+  // row r's message is poly[r * row_len ..]
+  LH_HIP(hipMemcpy2DAsync(rows, cw * sizeof(Fr), d_poly, p.row_len * sizeof(Fr), p.row_len * sizeof(Fr), R,
+                          hipMemcpyDeviceToDevice, c.stream));
+  // the cascade: a[k] forward, the Reed-Solomon tail, b[k] in reverse
+  size_t in_off = 0;
+  for (size_t k = 0; k + 1 < p.a.size(); k++) {
+    k_bd_gather(c, rows, R, cw, in_off, in_off + p.a[k].dim.n, p.a[k]);
+    in_off += p.a[k].dim.n;
+  }
+  const BdMatrix &al = p.a.back(), &bl = p.b.back();
+  k_bd_reed_solomon(c, rows, R, cw, in_off, al, bl.dim.n);
+  size_t out_off = in_off + al.dim.n + bl.dim.n;
+  in_off += al.dim.n + al.dim.m;
+  for (size_t k = p.a.size(); k-- > 0;) {
+    in_off -= p.a[k].dim.m;
+    k_bd_gather(c, rows, R, cw, in_off, out_off, p.b[k]);
+    out_off += p.b[k].dim.m;
+  }
+  LH_REQUIRE(in_off == p.row_len && out_off == cw, LH_ERR_ARG, "brakedown: cascade does not tile the codeword");
+  // column leaves, then one launch per tree level
+  k_bd_hash_columns(c, rows, R, cw, width, comm->d_hashes);
+  size_t off = 0;
+  for (size_t w = width; w > 1; w >>= 1) {
+    k_bd_merkle_level(c, comm->d_hashes + 4 * off, w / 2, comm->d_hashes + 4 * (off + w));
+    off += w;
+  }
+  c.d2h(comm->root, comm->d_hashes + 4 * off, 32);
+  return comm.release();
+}
+
+// ------------------------------------------------------------------ open (brakedown.rs:212-276)
+void brakedown_open(Ctx& c, const BdParam& p, const Fr* d_poly, size_t num_vars, BdComm& comm, const HFr* point,
+                    Transcript& tr, HashTranscript& ht) {
+  check_vars(p, num_vars, "open");
+  LH_REQUIRE(comm.num_rows == p.num_rows && comm.codeword_len == p.codeword_len && comm.device == c.device, LH_ERR_ARG,
+             "brakedown: commitment does not belong to these parameters");
+  const size_t R = p.num_rows, row_len = p.row_len, cw = p.codeword_len, k_rows = log2_ceil(R);
+  ArenaScope scope(c.arena);
+  std::vector<HFr> row(row_len);
+  if (R > 1) {
+    // point_to_tensor: (hi, lo) split at len - log2(num_rows); t_0 = eq(lo) weighs the rows
+    const std::vector<HFr> t_0 = host_eq_xy(std::vector<HFr>(point + num_vars - k_rows, point + num_vars));
+    Fr* coeffs = c.arena.alloc_n<Fr>(2 * R);
+    Fr* out = c.arena.alloc_n<Fr>(2 * row_len);
+    std::vector<HFr> both(2 * row_len);
+    for (size_t k = 0; k < p.num_proximity_testing; k++) {
+      const std::vector<HFr> cs = tr.squeeze_challenges(R);
+      const bool last = k + 1 == p.num_proximity_testing;  // the last proximity row and the t_0 row share one pass
+      LH_HIP(hipMemcpyAsync(coeffs, cs.data(), R * 32, hipMemcpyHostToDevice, c.stream));
+      if (last) LH_HIP(hipMemcpyAsync(coeffs + R, t_0.data(), R * 32, hipMemcpyHostToDevice, c.stream));
+      k_bd_combine(c, d_poly, R, row_len, coeffs, last ? 2 : 1, out);
+      c.d2h(both.data(), out, (last ? 2 : 1) * row_len * 32);
+      tr.write_field_elements(std::vector<HFr>(both.begin(), both.begin() + row_len));
+    }
+    std::copy(both.begin() + row_len, both.end(), row.begin());
+  } else {
+    c.d2h(row.data(), d_poly, row_len * 32);  // num_rows == 1: the t_0 row is the polynomial itself
+  }
+  tr.write_field_elements(row);
+
+  // the paths are read from a host copy of the tree; each column is fetched as it is squeezed (the next index depends on
+  // the entries this one absorbs)
+  if (comm.host_tree.empty()) {
+    comm.host_tree.resize(4 * ((2 << p.depth) - 1));
+    c.d2h(comm.host_tree.data(), comm.d_hashes, comm.host_tree.size() * 8);
+  }
+  HFr* col = (HFr*)c.pin(R * 32);
+  std::vector<HFr> items(R);
+  for (size_t i = 0; i < p.num_column_opening; i++) {
+    uint8_t repr[32];
+    tr.squeeze_challenge().to_repr(repr);  // squeeze_challenge_idx (brakedown.rs:427-435)
+    const size_t column = (size_t)(((uint32_t)repr[0] | (uint32_t)repr[1] << 8 | (uint32_t)repr[2] << 16 |
+                                    (uint32_t)repr[3] << 24) % cw);
+    LH_HIP(hipMemcpy2DAsync(col, 32, comm.d_rows + column, cw * sizeof(Fr), 32, R, hipMemcpyDeviceToHost, c.stream));
+    c.sync();
+    items.assign(col, col + R);
+    tr.write_field_elements(items);
+    size_t offset = 0;
+    for (size_t idx = 0; idx < p.depth; idx++) {
+      ht.write_hash((const uint8_t*)(comm.host_tree.data() + 4 * (offset + ((column >> idx) ^ 1))));
+      offset += (size_t)1 << (p.depth - idx);
+    }
+  }
+}
+
+}  // namespace lh

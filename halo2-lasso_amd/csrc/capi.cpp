@@ -1,5 +1,6 @@
 // extern "C" boundary: thin wrappers translating C++ exceptions into lh_status codes.
 #include "host.hpp"
+#include "brakedown.hpp"
 #include <memory>
 
 using namespace lh;
@@ -18,6 +19,12 @@ struct lh_usrs {
 };
 struct lh_zm_vp {
   ZmVerifierParams* p;
+};
+struct lh_brakedown_param {
+  BdParam p;
+};
+struct lh_brakedown_comm {
+  BdComm c;
 };
 
 #define LH_TRY try {
@@ -1024,6 +1031,187 @@ lh_status lh_zeromorph_batch_verify(const lh_zm_vp* vp, size_t num_vars, const l
   Transcript tr(t);
   zeromorph_batch_verify(*vp->p, num_vars, (const HG1*)comms, num_comms, (const HFr*)points, num_points, evals,
                          num_evals, tr);
+  LH_CATCH
+}
+
+// ---------------------------------------------------------------- Brakedown
+lh_status lh_keccak_transcript_hash_io(lh_transcript* t, lh_hash_transcript* out) {
+  LH_TRY
+  NEED(t);
+  NEED(out);
+  LH_REQUIRE(keccak_transcript_hash_io(t, out), LH_ERR_ARG, "not the built-in Keccak256 transcript");
+  LH_CATCH
+}
+lh_status lh_brakedown_setup(lh_ctx* ctx, size_t num_vars, int spec, const uint8_t* seed32, lh_brakedown_param** out) {
+  LH_TRY
+  NEED(seed32);
+  NEED(out);
+  std::unique_ptr<DeviceGuard> guard(ctx ? new DeviceGuard(ctx->c.device) : nullptr);
+  std::unique_ptr<BdParam> p(brakedown_setup(ctx ? &ctx->c : nullptr, num_vars, spec, seed32));
+  std::unique_ptr<lh_brakedown_param> w(new lh_brakedown_param());
+  std::swap(w->p, *p);  // (the moved-from param owns nothing on the device)
+  p->device = -1;
+  *out = w.release();
+  LH_CATCH
+}
+lh_status lh_brakedown_derive(size_t num_vars, int spec, lh_brakedown_param** out) {
+  LH_TRY
+  NEED(out);
+  std::unique_ptr<lh_brakedown_param> w(new lh_brakedown_param());
+  brakedown_derive(w->p, num_vars, spec);
+  *out = w.release();
+  LH_CATCH
+}
+lh_status lh_brakedown_param_info(const lh_brakedown_param* pp, size_t* row_len, size_t* num_rows, size_t* codeword_len,
+                                  size_t* num_column_opening, size_t* num_proximity_testing) {
+  LH_TRY
+  NEED(pp);
+  NEED(row_len);
+  NEED(num_rows);
+  NEED(codeword_len);
+  NEED(num_column_opening);
+  NEED(num_proximity_testing);
+  *row_len = pp->p.row_len, *num_rows = pp->p.num_rows, *codeword_len = pp->p.codeword_len;
+  *num_column_opening = pp->p.num_column_opening, *num_proximity_testing = pp->p.num_proximity_testing;
+  LH_CATCH
+}
+lh_status lh_brakedown_trim(const lh_brakedown_param* pp, size_t poly_size) {
+  LH_TRY
+  NEED(pp);
+  brakedown_trim(pp->p, poly_size);
+  LH_CATCH
+}
+void lh_brakedown_param_free(lh_brakedown_param* pp) { delete pp; }
+lh_status lh_brakedown_encode(const lh_brakedown_param* pp, const lh_fr* msg, lh_fr* out) {
+  LH_TRY
+  NEED(pp);
+  NEED(msg);
+  NEED(out);
+  std::vector<HFr> cw(pp->p.codeword_len);
+  memcpy(cw.data(), msg, pp->p.row_len * 32);
+  brakedown_encode_host(pp->p, cw.data());
+  memcpy(out, cw.data(), cw.size() * 32);
+  LH_CATCH
+}
+lh_status lh_brakedown_commit(lh_ctx* ctx, const lh_brakedown_param* pp, const lh_fr* d_poly, size_t num_vars,
+                              lh_brakedown_comm** out) {
+  return lh_brakedown_batch_commit(ctx, pp, d_poly ? &d_poly : nullptr, 1, num_vars, out);
+}
+lh_status lh_brakedown_batch_commit(lh_ctx* ctx, const lh_brakedown_param* pp, const lh_fr* const* d_polys,
+                                    size_t num_polys, size_t num_vars, lh_brakedown_comm** out) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(pp);
+  NEED_N(d_polys, num_polys);
+  NEED_N(out, num_polys);
+  for (size_t i = 0; i < num_polys; i++) LH_REQUIRE(d_polys[i], LH_ERR_ARG, "null argument: d_polys[i]");
+  std::vector<std::unique_ptr<lh_brakedown_comm>> comms;
+  for (size_t i = 0; i < num_polys; i++) {  // batch_commit is one commit per poly (brakedown.rs:198-210)
+    std::unique_ptr<BdComm> c(brakedown_commit(ctx->c, pp->p, (const Fr*)d_polys[i], num_vars));
+    std::unique_ptr<lh_brakedown_comm> w(new lh_brakedown_comm());
+    std::swap(w->c, *c);
+    c->device = -1;
+    comms.push_back(std::move(w));
+  }
+  for (size_t i = 0; i < num_polys; i++) out[i] = comms[i].release();
+  LH_CATCH
+}
+lh_status lh_brakedown_comm_root(const lh_brakedown_comm* comm, uint8_t* out32) {
+  LH_TRY
+  NEED(comm);
+  NEED(out32);
+  memcpy(out32, comm->c.root, 32);
+  LH_CATCH
+}
+lh_status lh_brakedown_comm_rows(lh_ctx* ctx, const lh_brakedown_comm* comm, lh_fr* out) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(comm);
+  NEED(out);
+  LH_HIP(hipMemcpyAsync(out, comm->c.d_rows, comm->c.num_rows * comm->c.codeword_len * 32, hipMemcpyDeviceToHost,
+                        ctx->c.stream));
+  ctx->c.sync();
+  LH_CATCH
+}
+lh_status lh_brakedown_comm_rows_device(const lh_brakedown_comm* comm, lh_fr** d_out) {
+  LH_TRY
+  NEED(comm);
+  NEED(d_out);
+  *d_out = (lh_fr*)comm->c.d_rows;
+  LH_CATCH
+}
+void lh_brakedown_comm_free(lh_brakedown_comm* comm) { delete comm; }
+lh_status lh_brakedown_open(lh_ctx* ctx, const lh_brakedown_param* pp, const lh_fr* d_poly, size_t num_vars,
+                            lh_brakedown_comm* comm, const lh_fr* point, lh_transcript* t, lh_hash_transcript* ht) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(pp);
+  NEED(d_poly);
+  NEED(comm);
+  NEED_N(point, num_vars);
+  Transcript tr(t);
+  HashTranscript h(ht);
+  brakedown_open(ctx->c, pp->p, (const Fr*)d_poly, num_vars, comm->c, (const HFr*)point, tr, h);
+  LH_CATCH
+}
+lh_status lh_brakedown_batch_open(lh_ctx* ctx, const lh_brakedown_param* pp, size_t num_vars, const lh_fr* const* d_polys,
+                                  lh_brakedown_comm* const* comms, size_t num_polys, const lh_fr* points,
+                                  size_t num_points, const lh_evaluation* evals, size_t num_evals, lh_transcript* t,
+                                  lh_hash_transcript* ht) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(pp);
+  NEED_N(d_polys, num_polys);
+  NEED_N(comms, num_polys);
+  NEED_N(points, num_points);
+  NEED_N(evals, num_evals);
+  Transcript tr(t);
+  HashTranscript h(ht);
+  for (size_t i = 0; i < num_evals; i++) {  // one open per evaluation (brakedown.rs:278-300)
+    const lh_evaluation& e = evals[i];
+    LH_REQUIRE(e.poly < num_polys && e.point < num_points && d_polys[e.poly] && comms[e.poly], LH_ERR_ARG,
+               "brakedown batch_open: evaluation out of range");
+    brakedown_open(ctx->c, pp->p, (const Fr*)d_polys[e.poly], num_vars, comms[e.poly]->c,
+                   (const HFr*)points + (size_t)e.point * num_vars, tr, h);
+  }
+  LH_CATCH
+}
+lh_status lh_brakedown_read_commitments(const lh_brakedown_param* pp, size_t num, lh_hash_transcript* ht, uint8_t* out) {
+  LH_TRY
+  NEED(pp);
+  NEED_N(out, num);
+  HashTranscript h(ht);
+  for (size_t i = 0; i < num; i++) h.read_hash(out + 32 * i);
+  LH_CATCH
+}
+lh_status lh_brakedown_verify(const lh_brakedown_param* pp, const uint8_t* root32, const lh_fr* point, size_t num_vars,
+                              const lh_fr* eval, lh_transcript* t, lh_hash_transcript* ht) {
+  LH_TRY
+  NEED(pp);
+  NEED(root32);
+  NEED(eval);
+  NEED_N(point, num_vars);
+  Transcript tr(t);
+  HashTranscript h(ht);
+  HFr e;
+  memcpy(&e, eval, 32);
+  brakedown_verify(pp->p, root32, (const HFr*)point, num_vars, e, tr, h);
+  LH_CATCH
+}
+lh_status lh_brakedown_batch_verify(const lh_brakedown_param* pp, size_t num_vars, const uint8_t* roots, size_t num_comms,
+                                    const lh_fr* points, size_t num_points, const lh_evaluation* evals,
+                                    size_t num_evals, lh_transcript* t, lh_hash_transcript* ht) {
+  LH_TRY
+  NEED(pp);
+  NEED_N(roots, num_comms);
+  NEED_N(points, num_points);
+  NEED_N(evals, num_evals);
+  Transcript tr(t);
+  HashTranscript h(ht);
+  for (size_t i = 0; i < num_evals; i++) {
+    const lh_evaluation& e = evals[i];
+    LH_REQUIRE(e.poly < num_comms && e.point < num_points, LH_ERR_ARG, "brakedown batch_verify: evaluation out of range");
+    HFr v;
+    memcpy(&v, &e.value, 32);
+    brakedown_verify(pp->p, roots + 32 * (size_t)e.poly, (const HFr*)points + (size_t)e.point * num_vars, num_vars, v,
+                     tr, h);
+  }
   LH_CATCH
 }
 

@@ -1,0 +1,224 @@
+// Kernels of the Brakedown PCS (reference util/code/brakedown.rs:88-125, pcs/multilinear/brakedown.rs:130-276).
+//   bd_gather        one sparse-matrix stage of the encoder, all rows at once: out[j] = sum_e in[idx[e]] val[e] over the
+//                    transposed CSR group of output j (a gather: no atomics, a fixed summation order)
+//   bd_reed_solomon  the cascade's tail, one workgroup per row: tmp = a_last . in in LDS, then horner(tmp, x), x = 1, 2, ..
+//   bd_hash_columns  keccak256(to_repr(rows[0][c]) || .. || to_repr(rows[R-1][c])), one thread per column, the state in
+//                    registers; leaves from codeword_len up to 2^depth are zero
+//   bd_merkle_level  parent = keccak256(left || right)
+//   bd_combine       the proximity row(s) and the t_0 row in one pass over the polynomial
+#include <hip/hip_runtime.h>
+#include "brakedown.hpp"
+
+namespace lh {
+
+#define GSTRIDE(i, n) \
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (size_t)gridDim.x * blockDim.x)
+static inline dim3 grid_for(size_t n, int block = 256, size_t cap = 8192) {
+  size_t g = (n + block - 1) / block;
+  if (g < 1) g = 1;
+  if (g > cap) g = cap;
+  return dim3((unsigned)g);
+}
+
+// ------------------------------------------------------------------ encoder stages
+__global__ void bd_gather_kernel(Fr* __restrict__ rows, size_t num_rows, size_t cw, size_t in_off, size_t out_off,
+                                 size_t m, const uint32_t* __restrict__ ptr, const uint32_t* __restrict__ idx,
+                                 const Fr* __restrict__ val) {
+  GSTRIDE(t, num_rows * m) {
+    const size_t r = t / m, j = t - r * m;
+    const Fr* in = rows + r * cw + in_off;
+    Fr acc = Fr::zero();
+    for (uint32_t e = ptr[j], end = ptr[j + 1]; e < end; e++) acc = add(acc, mul(in[idx[e]], val[e]));
+    rows[r * cw + out_off + j] = acc;
+  }
+}
+void k_bd_gather(Ctx& c, Fr* rows, size_t num_rows, size_t cw, size_t in_off, size_t out_off, const BdMatrix& mat) {
+  const size_t m = mat.dim.m;
+  if (!m || !num_rows) return;
+  ProfScope ps(c, "bd_gather", 64.0 * num_rows * mat.dim.n * mat.dim.d, (double)num_rows * mat.dim.n * mat.dim.d,
+               (double)num_rows * m);
+  hipLaunchKernelGGL(bd_gather_kernel, grid_for(num_rows * m), 256, 0, c.stream, rows, num_rows, cw, in_off, out_off, m,
+                     mat.d_ptr, mat.d_idx, mat.d_val);
+}
+
+constexpr int BD_RS_MAX = 64;  // a_last.m <= n_0 <= 20 (dimensions stop at n <= n_0)
+__global__ void bd_reed_solomon_kernel(Fr* __restrict__ rows, size_t cw, size_t in_off, size_t an, size_t am, size_t bn,
+                                       const uint32_t* __restrict__ ptr, const uint32_t* __restrict__ idx,
+                                       const Fr* __restrict__ val) {
+  __shared__ Fr tmp[BD_RS_MAX];
+  Fr* row = rows + (size_t)blockIdx.x * cw;
+  const Fr* in = row + in_off;
+  for (size_t j = threadIdx.x; j < am; j += blockDim.x) {
+    Fr acc = Fr::zero();
+    for (uint32_t e = ptr[j], end = ptr[j + 1]; e < end; e++) acc = add(acc, mul(in[idx[e]], val[e]));
+    tmp[j] = acc;
+  }
+  __syncthreads();
+  for (size_t x = threadIdx.x; x < bn; x += blockDim.x) {
+    const Fr xv = from_u64<FrParams>(x + 1);
+    Fr acc = Fr::zero();
+    for (size_t k = am; k-- > 0;) acc = add(mul(acc, xv), tmp[k]);
+    row[in_off + an + x] = acc;
+  }
+}
+void k_bd_reed_solomon(Ctx& c, Fr* rows, size_t num_rows, size_t cw, size_t in_off, const BdMatrix& a_last, size_t bn) {
+  LH_REQUIRE(a_last.dim.m <= (size_t)BD_RS_MAX, LH_ERR_ARG, "brakedown: Reed-Solomon message too long");
+  if (!num_rows) return;
+  ProfScope ps(c, "bd_reed_solomon", 64.0 * num_rows * (a_last.dim.n * a_last.dim.d + bn * a_last.dim.m),
+               (double)num_rows * (a_last.dim.n * a_last.dim.d + bn * a_last.dim.m), (double)num_rows * bn);
+  hipLaunchKernelGGL(bd_reed_solomon_kernel, dim3((unsigned)num_rows), 64, 0, c.stream, rows, cw, in_off, a_last.dim.n,
+                     a_last.dim.m, bn, a_last.d_ptr, a_last.d_idx, a_last.d_val);
+}
+
+// ------------------------------------------------------------------ Keccak-f[1600], the 25 lanes in registers
+__constant__ uint64_t BD_RC[24] = {
+    0x0000000000000001ull, 0x0000000000008082ull, 0x800000000000808Aull, 0x8000000080008000ull,
+    0x000000000000808Bull, 0x0000000080000001ull, 0x8000000080008081ull, 0x8000000000008009ull,
+    0x000000000000008Aull, 0x0000000000000088ull, 0x0000000080008009ull, 0x000000008000000Aull,
+    0x000000008000808Bull, 0x800000000000008Bull, 0x8000000000008089ull, 0x8000000000008003ull,
+    0x8000000000008002ull, 0x8000000000000080ull, 0x000000000000800Aull, 0x800000008000000Aull,
+    0x8000000080008081ull, 0x8000000000008080ull, 0x0000000080000001ull, 0x8000000080008008ull};
+
+__device__ __forceinline__ uint64_t rotl64(uint64_t v, int n) { return n ? (v << n) | (v >> (64 - n)) : v; }
+
+// every array index below is a compile-time constant once the loops are unrolled: the state never leaves registers
+__device__ __forceinline__ void keccak_f1600(uint64_t (&a)[25]) {
+  constexpr int RHO[25] = {0, 1, 62, 28, 27, 36, 44, 6, 55, 20, 3, 10, 43, 25, 39, 41, 45, 15, 21, 8, 18, 2, 61, 56, 14};
+#pragma unroll 1
+  for (int rnd = 0; rnd < 24; rnd++) {
+    uint64_t c[5], b[25];
+#pragma unroll
+    for (int x = 0; x < 5; x++) c[x] = a[x] ^ a[x + 5] ^ a[x + 10] ^ a[x + 15] ^ a[x + 20];
+#pragma unroll
+    for (int x = 0; x < 5; x++) {
+      const uint64_t d = c[(x + 4) % 5] ^ rotl64(c[(x + 1) % 5], 1);
+#pragma unroll
+      for (int y = 0; y < 5; y++) b[y + 5 * ((2 * x + 3 * y) % 5)] = rotl64(a[x + 5 * y] ^ d, RHO[x + 5 * y]);
+    }
+#pragma unroll
+    for (int y = 0; y < 5; y++)
+#pragma unroll
+      for (int x = 0; x < 5; x++) a[x + 5 * y] = b[x + 5 * y] ^ (~b[(x + 1) % 5 + 5 * y] & b[(x + 2) % 5 + 5 * y]);
+    a[0] ^= BD_RC[rnd];
+  }
+}
+
+__device__ __forceinline__ void store_digest(uint64_t* out, const uint64_t (&a)[25]) {
+  ulonglong2* o = (ulonglong2*)out;  // two 16-byte vector stores
+  o[0] = make_ulonglong2(a[0], a[1]);
+  o[1] = make_ulonglong2(a[2], a[3]);
+}
+
+// Column c's message is num_rows elements of 4 words; 17 elements = 68 words = exactly 4 rate blocks of 17 lanes, so with
+// the block's place in its group of 17 elements (BI) a template parameter every word's lane is a compile-time constant.
+// `cnt` elements of the group are data; on the last group the padding follows them (0x01 after the data, 0x80 in the last
+// byte of the padding block).  An element that straddles two blocks is loaded by both.
+template <int BI>
+__device__ __forceinline__ void bd_absorb_block(uint64_t (&a)[25], const Fr* col, size_t cw, int cnt, bool last,
+                                                bool pad_block) {
+  constexpr int first = 17 * BI, k0 = first / 4, k1 = (first + 16) / 4;
+#pragma unroll
+  for (int k = k0; k <= k1; k++) {
+    uint64_t w[4] = {0, 0, 0, 0};
+    if (k < cnt) {
+      const Fr v = from_mont(col[(size_t)k * cw]);  // to_repr: canonical, little-endian
+#pragma unroll
+      for (int t = 0; t < 4; t++) w[t] = (uint64_t)v.l[2 * t] | ((uint64_t)v.l[2 * t + 1] << 32);
+    }
+#pragma unroll
+    for (int t = 0; t < 4; t++) {
+      const int pos = 4 * k + t;
+      if (pos < first || pos > first + 16) continue;
+      uint64_t v = w[t];
+      if (last && pos == 4 * cnt) v ^= 0x01ull;
+      a[pos - first] ^= v;
+    }
+  }
+  if (pad_block) a[16] ^= 0x80ull << 56;
+}
+
+// (64-thread workgroups: the state, the permutation's temporaries and a Montgomery product fit without spilling)
+__global__ void __launch_bounds__(64)
+    bd_hash_columns_kernel(const Fr* __restrict__ rows, size_t num_rows, size_t cw, size_t width, uint64_t* __restrict__ leaves) {
+  GSTRIDE(c, width) {
+    uint64_t a[25];
+#pragma unroll
+    for (int i = 0; i < 25; i++) a[i] = 0;
+    if (c < cw) {
+      const size_t full = num_rows / 17;
+      for (size_t g = 0; g <= full; g++) {
+        const Fr* col = rows + g * 17 * cw + c;
+        const bool last = g == full;
+        const int cnt = last ? (int)(num_rows - full * 17) : 17, pad = (4 * cnt) / 17, nblk = last ? pad + 1 : 4;
+#pragma unroll 1
+        for (int bi = 0; bi < nblk; bi++) {
+          const bool pb = last && bi == pad;
+          switch (bi) {
+            case 0: bd_absorb_block<0>(a, col, cw, cnt, last, pb); break;
+            case 1: bd_absorb_block<1>(a, col, cw, cnt, last, pb); break;
+            case 2: bd_absorb_block<2>(a, col, cw, cnt, last, pb); break;
+            default: bd_absorb_block<3>(a, col, cw, cnt, last, pb); break;
+          }
+          keccak_f1600(a);
+        }
+      }
+    }
+    store_digest(leaves + 4 * c, a);  // (the zero leaves past codeword_len: a is still all zero)
+  }
+}
+void k_bd_hash_columns(Ctx& c, const Fr* rows, size_t num_rows, size_t cw, size_t width, uint64_t* leaves) {
+  ProfScope ps(c, "bd_hash_columns", 32.0 * num_rows * cw + 32.0 * width, 0, (double)cw);
+  hipLaunchKernelGGL(bd_hash_columns_kernel, grid_for(width, 64, 1 << 16), 64, 0, c.stream, rows, num_rows, cw, width,
+                     leaves);
+}
+
+__global__ void __launch_bounds__(64)
+    bd_merkle_level_kernel(const uint64_t* __restrict__ in, size_t out_n, uint64_t* __restrict__ out) {
+  GSTRIDE(i, out_n) {
+    uint64_t a[25];
+    const ulonglong2* src = (const ulonglong2*)(in + 8 * i);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const ulonglong2 v = src[k];
+      a[2 * k] = v.x, a[2 * k + 1] = v.y;
+    }
+#pragma unroll
+    for (int k = 8; k < 25; k++) a[k] = 0;
+    a[8] = 0x01ull;
+    a[16] = 0x80ull << 56;
+    keccak_f1600(a);
+    store_digest(out + 4 * i, a);
+  }
+}
+void k_bd_merkle_level(Ctx& c, const uint64_t* in, size_t out_n, uint64_t* out) {
+  ProfScope ps(c, "bd_merkle_level", 96.0 * out_n, 0, (double)out_n);
+  hipLaunchKernelGGL(bd_merkle_level_kernel, grid_for(out_n, 64, 1 << 16), 64, 0, c.stream, in, out_n, out);
+}
+
+// ------------------------------------------------------------------ open: combined rows
+constexpr int BD_MAX_SETS = 4;
+__global__ void bd_combine_kernel(const Fr* __restrict__ poly, size_t num_rows, size_t row_len,
+                                  const Fr* __restrict__ coeffs, int num_sets, Fr* __restrict__ out) {
+  GSTRIDE(col, row_len) {
+    Fr acc[BD_MAX_SETS];
+#pragma unroll
+    for (int k = 0; k < BD_MAX_SETS; k++) acc[k] = Fr::zero();
+    for (size_t r = 0; r < num_rows; r++) {
+      const Fr x = poly[r * row_len + col];
+#pragma unroll
+      for (int k = 0; k < BD_MAX_SETS; k++)
+        if (k < num_sets) acc[k] = add(acc[k], mul(coeffs[k * num_rows + r], x));
+    }
+#pragma unroll
+    for (int k = 0; k < BD_MAX_SETS; k++)
+      if (k < num_sets) out[k * row_len + col] = acc[k];
+  }
+}
+void k_bd_combine(Ctx& c, const Fr* poly, size_t num_rows, size_t row_len, const Fr* coeffs, int num_sets, Fr* out) {
+  LH_REQUIRE(num_sets >= 1 && num_sets <= BD_MAX_SETS, LH_ERR_ARG, "brakedown: too many combinations in one pass");
+  ProfScope ps(c, "bd_combine", 32.0 * num_rows * row_len, (double)num_sets * num_rows * row_len, (double)row_len);
+  hipLaunchKernelGGL(bd_combine_kernel, grid_for(row_len), 256, 0, c.stream, poly, num_rows, row_len, coeffs, num_sets,
+                     out);
+}
+
+}  // namespace lh

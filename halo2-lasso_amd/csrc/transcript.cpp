@@ -165,6 +165,28 @@ static int kt_read_comm(void* u, lh_g1* out) {
   return kt_common_comm(u, out);
 }
 
+// TranscriptWrite / TranscriptRead<Output<Keccak256>, Fr> (transcript.rs:240-265): a hash is 32 raw stream bytes and is
+// NOT absorbed - the reference's behaviour, which the Brakedown roots and Merkle paths inherit
+static int kt_write_hash(void* u, const uint8_t* hash) {
+  auto* t = (KeccakTranscript*)u;
+  t->stream.insert(t->stream.end(), hash, hash + 32);
+  return LH_OK;
+}
+static int kt_read_hash(void* u, uint8_t* out) {
+  auto* t = (KeccakTranscript*)u;
+  if (t->stream.size() - t->pos < 32) return read_failed(READ_EOF, "");
+  memcpy(out, t->stream.data() + t->pos, 32);
+  t->pos += 32;
+  return LH_OK;
+}
+bool keccak_transcript_hash_io(lh_transcript* t, lh_hash_transcript* out) {
+  if (t->write_field_element != kt_write_fe) return false;  // not the built-in transcript
+  out->user = t->user;
+  out->write_hash = kt_write_hash;
+  out->read_hash = kt_read_hash;
+  return true;
+}
+
 KeccakTranscript::KeccakTranscript() {
   vt.user = this;
   vt.write_field_element = kt_write_fe;

@@ -5,12 +5,14 @@
 //   HyperPlonk::verify                     backend/hyperplonk.rs:293-362, hyperplonk/verifier.rs:39-182,
 //                                          piop/sum_check.rs:60-125, poly/multilinear.rs:433-475
 //   Lasso verify                           oracle/pyref/lasso.py (the build's own protocol; no reference code)
+//   MultilinearBrakedown::verify           pcs/multilinear/brakedown.rs:315-396 (two rows re-encoded on the host)
 #include <map>
 #include <set>
 #include <string>
 #include "host.hpp"
 #include "expr.hpp"
 #include "pairing.hpp"
+#include "brakedown.hpp"
 
 namespace lh {
 
@@ -707,6 +709,64 @@ void lasso_verify(const PcsBatchVerify& batch_verify, const lh_lasso_table& tb, 
     points.insert(points.end(), nv - pt->size(), HFr::zero());
   }
   batch_verify(nv, comms.data(), comms.size(), points.data(), 4, evals.data(), evals.size(), tr);
+}
+
+// ------------------------------------------------------------------ Brakedown (pcs/multilinear/brakedown.rs:315-396)
+void brakedown_verify(const BdParam& p, const uint8_t root[32], const HFr* point, size_t num_vars, const HFr& eval,
+                      Transcript& tr, HashTranscript& ht) {
+  if (num_vars != p.num_vars)
+    throw Error(LH_ERR_INVALID_PCS_PARAM, "Invalid poly or point to verify (param supports " +
+                                              std::to_string(p.num_vars) + " variates but got " +
+                                              std::to_string(num_vars) + ")");
+  const size_t R = p.num_rows, row_len = p.row_len, cw = p.codeword_len;
+  size_t k_rows = 0;
+  while (((size_t)1 << k_rows) < R) k_rows++;
+  const std::vector<HFr> t_0 = host_eq_xy(std::vector<HFr>(point + num_vars - k_rows, point + num_vars));
+  const std::vector<HFr> t_1 = host_eq_xy(std::vector<HFr>(point, point + num_vars - k_rows));
+  std::vector<std::pair<std::vector<HFr>, std::vector<HFr>>> combined;  // (coefficients, encoded row)
+  auto read_row = [&](std::vector<HFr> coeffs) {
+    std::vector<HFr> row = tr.read_field_elements(row_len);
+    row.resize(cw);
+    brakedown_encode_host(p, row.data());
+    combined.emplace_back(std::move(coeffs), std::move(row));
+  };
+  if (R > 1) read_row(tr.squeeze_challenges(R));
+  read_row(t_0);
+  for (size_t i = 0; i < p.num_column_opening; i++) {
+    uint8_t repr[32];
+    tr.squeeze_challenge().to_repr(repr);
+    const size_t column = (size_t)(((uint32_t)repr[0] | (uint32_t)repr[1] << 8 | (uint32_t)repr[2] << 16 |
+                                    (uint32_t)repr[3] << 24) % cw);
+    const std::vector<HFr> items = tr.read_field_elements(R);
+    std::vector<uint8_t> path(32 * p.depth);
+    for (size_t k = 0; k < p.depth; k++) ht.read_hash(path.data() + 32 * k);
+    for (const auto& cr : combined) {  // proximity
+      HFr item = items[0];
+      if (R > 1) {
+        item = HFr::zero();
+        for (size_t r = 0; r < R; r++) item += cr.first[r] * items[r];
+      }
+      if (item != cr.second[column]) throw Error(LH_ERR_INVALID_PCS_OPEN, "Proximity failure");
+    }
+    Keccak256 hasher;  // merkle tree opening
+    uint8_t out[32], buf[64];
+    for (const HFr& x : items) {
+      x.to_repr(repr);
+      hasher.update(repr, 32);
+    }
+    hasher.finalize_reset(out);
+    for (size_t k = 0; k < p.depth; k++) {
+      const bool left = ((column >> k) & 1) == 0;
+      memcpy(buf + (left ? 0 : 32), out, 32);
+      memcpy(buf + (left ? 32 : 0), path.data() + 32 * k, 32);
+      hasher.update(buf, 64);
+      hasher.finalize_reset(out);
+    }
+    if (memcmp(out, root, 32) != 0) throw Error(LH_ERR_INVALID_PCS_OPEN, "Invalid merkle tree opening");
+  }
+  HFr acc = HFr::zero();  // consistency
+  for (size_t c = 0; c < row_len; c++) acc += combined.back().second[c] * t_1[c];
+  if (acc != eval) throw Error(LH_ERR_INVALID_PCS_OPEN, "Consistency failure");
 }
 
 }  // namespace lh

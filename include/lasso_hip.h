@@ -577,6 +577,67 @@ lh_status lh_hyperplonk_verify_phases_zeromorph(const lh_zm_vp*, const lh_hp_vpa
                                                 const size_t* num_witness_polys, const size_t* num_challenges,
                                                 const lh_fr* const* instances, lh_transcript* t);
 
+/* ---------------------------------------------------------------- f4: Brakedown (transparent, no SRS)
+ * PolynomialCommitmentScheme for MultilinearBrakedown<bn256::Fr, Keccak256, BrakedownSpec1..6>
+ * (pcs/multilinear/brakedown.rs:89-417, util/code/brakedown.rs): 2^num_vars evaluations as num_rows rows of row_len,
+ * each row encoded by the expander code to codeword_len entries, the columns hashed with Keccak-256 into a Merkle tree.
+ * The sparse matrices are drawn from a 32-byte seed by this library's sampler instead of a caller's
+ * RngCore.  Commitments are 32-byte roots; they and the Merkle paths cross the transcript through lh_hash_transcript. */
+typedef struct lh_hash_transcript {
+  void* user;
+  int (*write_hash)(void* user, const uint8_t* hash32); /* TranscriptWrite<Output<Keccak256>, F>, transcript.rs:259-265 */
+  int (*read_hash)(void* user, uint8_t* out32);          /* TranscriptRead<Output<Keccak256>, F>, transcript.rs:249-257 */
+} lh_hash_transcript;
+/* the hash half of the built-in Keccak256Transcript: 32 raw bytes in the stream, not absorbed (transcript.rs:240-265).
+ * LH_ERR_ARG for a callback table that is not the built-in transcript. */
+lh_status lh_keccak_transcript_hash_io(lh_transcript* t, lh_hash_transcript* out);
+typedef struct lh_brakedown_param lh_brakedown_param; /* MultilinearBrakedownParams (brakedown.rs:35-41) */
+typedef struct lh_brakedown_comm lh_brakedown_comm;   /* MultilinearBrakedownCommitment (brakedown.rs:55-60) */
+/* setup (brakedown.rs:101-110) with poly_size = 2^num_vars, spec 1..6.  ctx NULL: host only (a verifier's param);
+ * with a ctx the matrices are also uploaded, transposed, for the device encoder.  LH_ERR_ARG where the reference's
+ * code dimensions do not exist (num_vars 1 with specs 1 and 2). */
+lh_status lh_brakedown_setup(lh_ctx* ctx, size_t num_vars, int spec, const uint8_t* seed32, lh_brakedown_param** out);
+/* the parameters alone, without matrices (no seed, nothing sampled): param_info and trim only */
+lh_status lh_brakedown_derive(size_t num_vars, int spec, lh_brakedown_param** out);
+/* row_len, num_rows, codeword_len (LinearCodes, code/mod.rs), num_column_opening, num_proximity_testing */
+lh_status lh_brakedown_param_info(const lh_brakedown_param*, size_t* row_len, size_t* num_rows, size_t* codeword_len,
+                                  size_t* num_column_opening, size_t* num_proximity_testing);
+/* trim (brakedown.rs:112-126): the param is its own prover and verifier param; LH_ERR_INVALID_PCS_PARAM unless
+ * poly_size == 2^num_vars */
+lh_status lh_brakedown_trim(const lh_brakedown_param*, size_t poly_size);
+void lh_brakedown_param_free(lh_brakedown_param*);
+/* LinearCodes::encode (code/brakedown.rs:88-125) on the host: msg has row_len entries, out codeword_len */
+lh_status lh_brakedown_encode(const lh_brakedown_param*, const lh_fr* msg, lh_fr* out);
+/* commit / batch_commit (brakedown.rs:128-210): the rows and the tree stay on the ctx's device in the commitment */
+lh_status lh_brakedown_commit(lh_ctx*, const lh_brakedown_param*, const lh_fr* d_poly, size_t num_vars,
+                              lh_brakedown_comm** out);
+lh_status lh_brakedown_batch_commit(lh_ctx*, const lh_brakedown_param*, const lh_fr* const* d_polys, size_t num_polys,
+                                    size_t num_vars, lh_brakedown_comm** out);
+lh_status lh_brakedown_comm_root(const lh_brakedown_comm*, uint8_t* out32); /* AsRef<[Output<H>]> (brakedown.rs:83-87) */
+/* MultilinearBrakedownCommitment::rows (brakedown.rs:70-72): num_rows x codeword_len, row-major, a download */
+lh_status lh_brakedown_comm_rows(lh_ctx*, const lh_brakedown_comm*, lh_fr* out);
+/* the device address of the rows (tests: a change made after commit) */
+lh_status lh_brakedown_comm_rows_device(const lh_brakedown_comm*, lh_fr** d_out);
+void lh_brakedown_comm_free(lh_brakedown_comm*);
+/* open (brakedown.rs:212-276) */
+lh_status lh_brakedown_open(lh_ctx*, const lh_brakedown_param*, const lh_fr* d_poly, size_t num_vars,
+                            lh_brakedown_comm* comm, const lh_fr* point, lh_transcript* t, lh_hash_transcript* ht);
+/* batch_open (brakedown.rs:278-300): one open per evaluation, in order */
+lh_status lh_brakedown_batch_open(lh_ctx*, const lh_brakedown_param*, size_t num_vars, const lh_fr* const* d_polys,
+                                  lh_brakedown_comm* const* comms, size_t num_polys, const lh_fr* points,
+                                  size_t num_points, const lh_evaluation* evals, size_t num_evals, lh_transcript* t,
+                                  lh_hash_transcript* ht);
+/* read_commitments (brakedown.rs:302-313): num roots of 32 bytes */
+lh_status lh_brakedown_read_commitments(const lh_brakedown_param*, size_t num, lh_hash_transcript* ht, uint8_t* out);
+/* verify (brakedown.rs:315-396), host only; LH_ERR_INVALID_PCS_OPEN with "Proximity failure",
+ * "Invalid merkle tree opening" or "Consistency failure" */
+lh_status lh_brakedown_verify(const lh_brakedown_param*, const uint8_t* root32, const lh_fr* point, size_t num_vars,
+                              const lh_fr* eval, lh_transcript* t, lh_hash_transcript* ht);
+/* batch_verify (brakedown.rs:398-417): one verify per evaluation; roots: num_comms x 32 bytes */
+lh_status lh_brakedown_batch_verify(const lh_brakedown_param*, size_t num_vars, const uint8_t* roots, size_t num_comms,
+                                    const lh_fr* points, size_t num_points, const lh_evaluation* evals,
+                                    size_t num_evals, lh_transcript* t, lh_hash_transcript* ht);
+
 /* development / tests: the HIP source the runtime compiler (csrc/jit.cpp) is given for a register program - words
  * {op | dst << 4 | a.kind << 8 | b.kind << 10, a.idx | b.idx << 16} with op ADD 0, SUB 1, MUL 2, NEG 3, MOV 4 and operand
  * kinds register 0, table 1, constant 2 (csrc/dev.hpp PROG_*).  Host code only (no GPU needed): tests/test_jit_source.py
