@@ -115,23 +115,23 @@ LH_HD uint32_t add_raw(Fp<P>& r, const Fp<P>& a, const Fp<P>& b) {
   return c;
 }
 
-// r = a - p ; returns borrow (1 if a < p)
-template <class P>
+// r = a - p ; returns borrow (1 if a < p).  (M: the modulus provider, Twice<P> for the lazy forms)
+template <class P, class M = P>
 LH_HD uint32_t sub_mod_raw(Fp<P>& r, const Fp<P>& a) {
   uint32_t bw = 0;
 #pragma unroll
   for (int i = 0; i < 8; i++) {
-    uint64_t s = (uint64_t)a.l[i] - P::mod(i) - bw;
+    uint64_t s = (uint64_t)a.l[i] - M::mod(i) - bw;
     r.l[i] = (uint32_t)s;
     bw = (uint32_t)(s >> 63);
   }
   return bw;
 }
 
-template <class P>
+template <class P, class M = P>
 LH_HD Fp<P> reduce_once_generic(const Fp<P>& a) {
   Fp<P> t;
-  uint32_t bw = sub_mod_raw(t, a);
+  uint32_t bw = sub_mod_raw<P, M>(t, a);
   Fp<P> r;
 #pragma unroll
   for (int i = 0; i < 8; i++) r.l[i] = bw ? a.l[i] : t.l[i];
@@ -145,7 +145,7 @@ LH_HD Fp<P> add_generic(const Fp<P>& a, const Fp<P>& b) {
   return reduce_once_generic(s);
 }
 
-template <class P>
+template <class P, class M = P>
 LH_HD Fp<P> sub_generic(const Fp<P>& a, const Fp<P>& b) {
   Fp<P> d;
   uint32_t bw = 0;
@@ -160,7 +160,7 @@ LH_HD Fp<P> sub_generic(const Fp<P>& a, const Fp<P>& b) {
   Fp<P> r;
 #pragma unroll
   for (int i = 0; i < 8; i++) {
-    uint64_t s = (uint64_t)d.l[i] + (P::mod(i) & mask) + c;
+    uint64_t s = (uint64_t)d.l[i] + (M::mod(i) & mask) + c;
     r.l[i] = (uint32_t)s;
     c = (uint32_t)(s >> 32);
   }
@@ -677,17 +677,26 @@ __device__ __forceinline__ bool is_zero_lazy(const Fp<P>& a) {  // a = 0 mod p f
 #undef LH_MAC
 #undef LH_MACS
 #elif defined(__HIPCC__)
-// (the host pass over device code only needs the names: canonical arithmetic is a valid lazy arithmetic)
+// Host forms with the same contract (values in [0, 2 p)): mul_cios of two such values stays below 2 p before its final
+// subtraction, so its result is canonical; additions and subtractions keep the range with 2 p as the modulus.
 template <class P>
 LH_HD Fp<P> mul_lazy(const Fp<P>& a, const Fp<P>& b) { return mul(a, b); }
 template <class P>
-LH_HD Fp<P> add_lazy(const Fp<P>& a, const Fp<P>& b) { return add(a, b); }
+LH_HD Fp<P> add_lazy(const Fp<P>& a, const Fp<P>& b) {
+  Fp<P> s;
+  add_raw(s, a, b);  // < 4 p < 2^256
+  return reduce_once_generic<P, Twice<P>>(s);
+}
 template <class P>
-LH_HD Fp<P> sub_lazy(const Fp<P>& a, const Fp<P>& b) { return sub(a, b); }
+LH_HD Fp<P> sub_lazy(const Fp<P>& a, const Fp<P>& b) { return sub_generic<P, Twice<P>>(a, b); }
 template <class P>
-LH_HD Fp<P> canon(const Fp<P>& a) { return a; }
+LH_HD Fp<P> canon(const Fp<P>& a) { return reduce_once_generic(a); }
 template <class P>
-LH_HD bool is_zero_lazy(const Fp<P>& a) { return a.is_zero(); }
+LH_HD bool is_zero_lazy(const Fp<P>& a) {
+  bool m = true;
+  for (int i = 0; i < 8; i++) m = m && a.l[i] == P::mod(i);
+  return a.is_zero() || m;
+}
 #endif
 
 template <class P>

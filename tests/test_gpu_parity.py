@@ -12,6 +12,7 @@ import zlib
 
 import pytest
 
+import field_edges
 from oracle.pyref import curve, gkr as o_gkr, kzg as o_kzg, lasso as o_lasso, sum_check as o_sc
 from oracle.pyref import expression as ex
 from oracle.pyref.field import R_MOD as P, batch_invert
@@ -31,8 +32,10 @@ EDGE = [0, 1, 2, P - 1, P - 2, (1 << 253), (1 << 32) - 1, 1 << 32, (1 << 64) - 1
 # ------------------------------------------------------------------ a1: Fr arithmetic
 def test_fr_binops(hl, ctx):
     rng = random.Random(1)
-    a = EDGE + rand_fr(rng, 500) + EDGE[::-1]
-    b = EDGE[::-1] + rand_fr(rng, 500) + EDGE
+    # then every pair of the stored-limb edge table: the values whose Montgomery forms have those limbs
+    se = [s * pow(1 << 256, -1, P) % P for s in field_edges.stored_edges(P)]
+    a = EDGE + rand_fr(rng, 500) + EDGE[::-1] + [x for x in se for _ in se]
+    b = EDGE[::-1] + rand_fr(rng, 500) + EDGE + [y for _ in se for y in se]
     da, db = ctx.upload(hl.frs_to_bytes(a)), ctx.upload(hl.frs_to_bytes(b))
     out = ctx.alloc(32 * len(a))
     for fn, op in ((ctx.lib.lh_fr_add, lambda x, y: (x + y) % P), (ctx.lib.lh_fr_sub, lambda x, y: (x - y) % P),
