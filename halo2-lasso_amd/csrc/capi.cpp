@@ -124,7 +124,7 @@ void lh_ctx_destroy(lh_ctx* ctx) {
   } catch (...) {
   }
   if (ctx->c.helper_handle) {
-    lh_ctx_destroy((lh_ctx*)ctx->c.helper_handle);
+    lh_ctx_destroy(ctx->c.helper_handle);
     ctx->c.helper_handle = nullptr, ctx->c.helper = nullptr;
   }
   delete ctx->c.worker;  // (joins; after the precommit it may still be running was cancelled above)
@@ -556,7 +556,7 @@ lh_status lh_lasso_prove(lh_ctx* ctx, const lh_srs* srs, const lh_lasso_table* t
   NEED(table);
   NEED(d_dims);
   Transcript tr(t);
-  lasso_prove(ctx->c, lasso_mkzg_pcs(ctx->c, srs->s), *table, num_vars, d_dims, tr);
+  lasso_prove(ctx->c, mkzg_pcs(ctx->c, srs->s), *table, num_vars, d_dims, tr);
   LH_CATCH
 }
 lh_status lh_lasso_last_timing(lh_ctx* ctx, double* out_ms) {
@@ -766,11 +766,7 @@ lh_status lh_hyperplonk_prove_sharded(lh_ctx* ctx, const lh_srs* srs, const lh_h
   LH_REQUIRE(c.has_comm, LH_ERR_ARG, "lh_hyperplonk_prove_sharded: no communicator attached");
   const size_t R = (size_t)c.comm.size;
   LH_REQUIRE(R >= 1 && (R & (R - 1)) == 0, LH_ERR_ARG, "sharded prove: the number of ranks must be a power of two");
-  struct Active {
-    Ctx& c;
-    explicit Active(Ctx& c_) : c(c_) { c.shard_active = true; }
-    ~Active() { c.shard_active = false; }
-  } active(c);
+  ShardActive active(c);
   Transcript tr(t);
   hyperplonk_prove(c, mkzg_pcs(c, srs->s), *pp, (const HFr* const*)instances, (const Fr* const*)d_witness_polys, tr);
   LH_CATCH
@@ -1222,7 +1218,7 @@ lh_status lh_lasso_prove_zeromorph(lh_ctx* ctx, const lh_usrs* srs, size_t poly_
   NEED(table);
   NEED(d_dims);
   Transcript tr(t);
-  lasso_prove(ctx->c, lasso_zeromorph_pcs(ctx->c, srs->s, poly_size), *table, num_vars, d_dims, tr);
+  lasso_prove(ctx->c, zeromorph_pcs(ctx->c, srs->s, poly_size), *table, num_vars, d_dims, tr);
   LH_CATCH
 }
 lh_status lh_lasso_verify_zeromorph(const lh_zm_vp* vp, const lh_lasso_table* table, size_t num_vars, lh_transcript* t) {

@@ -191,6 +191,7 @@ class HostWorker {
 };
 
 // ------------------------------------------------------------------ context
+struct OpenPrecommit;  // open_columns.hpp
 struct Ctx {
   Options opt;
   RouteStats route;
@@ -219,27 +220,6 @@ struct Ctx {
   // gkr, evals, open; 7 = outside a Lasso prove): [phase][0] collectives, [phase][1] bytes this rank contributed
   uint64_t comm_phase_stats[8][2] = {};
   int comm_phase = 7;
-  // hint for the NEXT sum_check_prove (consumed and cleared at its entry): its single table d_polys[0] has NOT been written -
-  // its values are this 32-bit column.  The sum-check either runs its first three rounds from the column (sumcheck.cpp: the
-  // sums of k_inner_products_small_quads are rounds 0 and 1, k_sc_round_u32_bind2 is round 2) or fills the table itself.
-  struct ScU32 {
-    const uint32_t* col = nullptr;
-    bool have_sums = false;
-    Fr odd, s2, s3;  // (when have_sums: out_host[1..3] of k_inner_products_small_quads against the sum-check's E_0)
-  } sc_u32;
-  // hint for the NEXT sum-check of the batch-opening shape sum_m eq(y_m, .) poly_m (consumed and cleared at its entry):
-  // poly b = sum_k w[k] col[k] over 32-bit columns (entries beyond len[k] are zero) and d_polys[b] has NOT been written.  The
-  // sum-check runs its first three rounds from the columns (sumcheck.cpp: k_inner_products_quads, k_lincomb_bind2) or
-  // fills the tables itself (k_lincomb_mixed) and says so in `built`.
-  struct ScU32Terms {
-    struct Poly {
-      std::vector<const uint32_t*> col;
-      std::vector<size_t> len;
-      std::vector<Fr> w;
-    };
-    std::vector<Poly> polys;  // empty: no hint
-    bool built = false;       // out: the tables of d_polys hold the polys in full
-  } sc_u32_terms;
   // sharded sum-check rounds: the round kernel leaves its D sums in this DEVICE buffer (and "publishes" to a device
   // word) instead of pinned host memory; the all-gather and the sum-and-publish kernel follow on the stream
   Fr* sc_redirect = nullptr;
@@ -252,7 +232,6 @@ struct Ctx {
   void wait_round(uint32_t seq) {  // the host's wait for a round kernel's sums (nothing to wait for when they stay on the device)
     if (!sc_redirect) wait_flag(seq);
   }
-  bool last_round_folded = false;  // k_sc_round: the launch it chose folded the coefficients into the left factors (ScRound::pp)
   uint64_t* tail_trace = nullptr;  // development: device stamps of the last resident tail (LH_SC_TAIL_TRACE)
   // development (LH_HOST_TRACE=1): host wall-clock stamps at named points of a prove, printed (deltas in us) when the prove
   // ends - where the host's share of a gap between two kernels goes
@@ -289,17 +268,14 @@ struct Ctx {
   // the opening (open_columns.cpp open_precommit_*): both owned by this ctx
   bool is_helper = false;  // this ctx is somebody's helper: its throughput kernels leave wave slots to the owner's stream
   Ctx* helper = nullptr;
-  void* helper_handle = nullptr;
-  void* precommit = nullptr;
+  lh_ctx* helper_handle = nullptr;
+  OpenPrecommit* precommit = nullptr;
   HostWorker* worker = nullptr;   // the host thread that drives THIS ctx when it is somebody's helper (created on first use)
   hipEvent_t handoff_ev = nullptr;  // recorded on this ctx's stream where a helper's stream may start reading its columns
   // phase boundaries of the last Lasso prove as events on the stream (no host sync at a boundary: lasso.cpp lap)
   hipEvent_t phase_ev[LH_LASSO_NUM_PHASES] = {};
   bool phase_ev_pending = false;
   void phase_times_resolve();  // events -> lasso_ms (waits for the last one)
-  // called once (and cleared) when a grand-product argument has built its trees and starts its layer sum-checks: the
-  // latency-bound stretch of a Lasso prove, where lasso_prove starts the opening's precommit
-  std::function<void()> gkr_hook;
   hipEvent_t prof_ev[2] = {nullptr, nullptr};
   void* pin(size_t bytes);  // grows the pinned buffer if needed
   // small device -> host download through a second pinned staging buffer, synchronising: an async copy into
@@ -357,6 +333,12 @@ struct Ctx {
   void wait_chunks(const struct TailChunk* chunks, size_t count, uint32_t seq, Fr* out);
   // the same; false (nothing copied) when the first chunk carries `alt` instead
   bool wait_chunks_or(const struct TailChunk* chunks, size_t count, uint32_t seq, uint32_t alt, Fr* out);
+};
+
+struct ShardActive {  // Ctx::shard_active for the duration of one sharded prove, whatever way it ends
+  Ctx& c;
+  explicit ShardActive(Ctx& c_) : c(c_) { c.shard_active = true; }
+  ~ShardActive() { c.shard_active = false; }
 };
 
 // Geometry of a proof sharded over R = 2^rho ranks.  A table of 2^m entries is split on the index bits
@@ -619,7 +601,8 @@ struct ScRound {
   uint8_t pp;
 };
 // evals_host[0..degree) receives sum_b expr at X = 1..degree (X = 0 is derived by the caller)
-void k_sc_round(Ctx&, const ScRound& rd, int degree, bool bind, size_t size, Fr* evals_host);
+// -> the launch it chose folded the coefficients into the left factors (ScRound::pp == 2 and a kernel that does fold)
+bool k_sc_round(Ctx&, const ScRound& rd, int degree, bool bind, size_t size, Fr* evals_host);
 // true when k_sc_round would run the streaming one-thread-per-pair kernel for this shape (not the LDS-staged one)
 bool k_sc_round_streams(const ScRound& rd, int degree, size_t size);
 // out[i] = in[2 i] + in[2 i + 1]: the eq table over one variable less (eq factoring)

@@ -100,8 +100,10 @@ FracSumCheckResult prove_fractional_sum_check(Ctx& c, size_t B, size_t num_vars,
         polys.push_back(lq[h][b]);
         polys.push_back(lq[h][b] + half);
       }
+      ScOptions so;
+      so.sum_is_exact = true;
       SumCheckResult sc = sum_check_prove(c, LH_SC_EVALUATIONS, nv, expr, polys.data(), polys.size(), y.data(), 1,
-                                          claim, tr, true);
+                                          claim, tr, so);
       x = sc.challenges;
       evals = sc.evals;
     }
@@ -121,7 +123,8 @@ FracSumCheckResult prove_fractional_sum_check(Ctx& c, size_t B, size_t num_vars,
 // ------------------------------------------------------------------ grand product (Lasso memory check)
 // Product-only layered circuit; schedule in oracle/pyref/gkr.py::prove_grand_product.
 GrandProductResult prove_grand_product(Ctx& c, size_t B, const Fr* const* d_leaves, const size_t* num_vars,
-                                       Transcript& tr, const Fr* const* d_level_up, const uint8_t* plus_one) {
+                                       Transcript& tr, const Fr* const* d_level_up, const uint8_t* plus_one,
+                                       const std::function<void()>& trees_built) {
   LH_REQUIRE(B != 0, LH_ERR_ARG, "grand product: no trees");
   size_t max_depth = 0;
   for (size_t b = 0; b < B; b++) {
@@ -248,14 +251,11 @@ GrandProductResult prove_grand_product(Ctx& c, size_t B, const Fr* const* d_leav
     }
     resident_layers.swap(layers);
   }
-  if (c.gkr_hook) {  // (the trees are built: from here on the small layers leave most of the chip idle)
-    // (before the resident launch: what the hook starts on another stream waits for an event recorded HERE on this
-    // ctx's stream - behind the resident kernel it would wait for the whole resident phase.  Later starts - at the layer
-    // with 2^12 .. 2^21 entries - were measured in rounds 3 and 4 and are monotonically worse: profiles/README.md)
-    std::function<void()> hook;
-    hook.swap(c.gkr_hook);
-    hook();
-  }
+  // (the trees are built: from here on the small layers leave most of the chip idle)
+  // (before the resident launch: what the callback starts on another stream waits for an event recorded HERE on this
+  // ctx's stream - behind the resident kernel it would wait for the whole resident phase.  Later starts - at the layer
+  // with 2^12 .. 2^21 entries - were measured in rounds 3 and 4 and are monotonically worse: profiles/README.md)
+  if (trees_built) trees_built();
   if (!resident_layers.empty()) resident.launch(resident_layers);
   for (size_t h = 0; h < max_depth; h++) {
     std::vector<size_t> active;
@@ -309,6 +309,8 @@ GrandProductResult prove_grand_product(Ctx& c, size_t B, const Fr* const* d_leav
       memset(&expr, 0, sizeof(expr));
       expr.global_eq = 0;
       std::vector<const Fr*> polys;
+      ScOptions so;
+      so.sum_is_exact = true, so.sharded = layer_sh;
       // leaf layer of (A, A + 1) tree pairs (`plus_one`): every active tree is at its leaf level and they pair up
       bool pairs = plus_one != nullptr && active.size() % 2 == 0 && active.size() / 2 <= (size_t)SC_RW_MAX_PAIRS;
       for (size_t k = 0; k < active.size() && pairs; k++) {
@@ -346,8 +348,8 @@ GrandProductResult prove_grand_product(Ctx& c, size_t B, const Fr* const* d_leav
         }
         memcpy(&expr.coeff[t], &cw_sum, 32), expr.num_factors[t] = 0, t++;
         expr.num_terms = t;
-        SumCheckResult sc = sum_check_prove(c, LH_SC_EVALUATIONS, h, expr, polys.data(), polys.size(), y.data(), 1, claim, tr,
-                                            true, degenerate ? nullptr : &rw, layer_sh);
+        so.rw = degenerate ? nullptr : &rw;
+        SumCheckResult sc = sum_check_prove(c, LH_SC_EVALUATIONS, h, expr, polys.data(), polys.size(), y.data(), 1, claim, tr, so);
         x = sc.challenges;
         for (size_t i = 0; i < P; i++) {  // evaluations of the B tables: those of the A tables + 1
           const HFr l = sc.evals[2 * i], r = sc.evals[2 * i + 1];
@@ -368,8 +370,7 @@ GrandProductResult prove_grand_product(Ctx& c, size_t B, const Fr* const* d_leav
         polys.push_back(level[b][h] + half);
       }
       expr.num_terms = (uint32_t)active.size();
-      SumCheckResult sc = sum_check_prove(c, LH_SC_EVALUATIONS, h, expr, polys.data(), polys.size(), y.data(), 1, claim, tr,
-                                          true, nullptr, layer_sh);
+      SumCheckResult sc = sum_check_prove(c, LH_SC_EVALUATIONS, h, expr, polys.data(), polys.size(), y.data(), 1, claim, tr, so);
       x = sc.challenges;
       evals = sc.evals;
       }

@@ -117,6 +117,7 @@ std::vector<HFr> evaluate_polys(Ctx&, const Fr* const* d_polys, size_t count, si
 struct SumCheckResult {
   std::vector<HFr> challenges;  // x
   std::vector<HFr> evals;       // every poly at x (classic.rs:143-149)
+  bool u32_terms_built = false;  // given ScOptions::u32_terms: the tables of d_polys hold the polys in full
 };
 // `sum_is_exact`: the caller computed `sum` from these very tables (the provers' internal sum-checks: Surge, the GKR
 // layers): eq factoring then trusts it from round 0 on; a claim from outside (the C-ABI) is checked first (EqFactoring)
@@ -127,11 +128,38 @@ struct ScRwPairs {
   HFr cs[SC_RW_MAX_PAIRS], k[SC_RW_MAX_PAIRS];
   HFr const_total;  // sum of the constants the factorisation leaves behind: added to q at every point
 };
-SumCheckResult sum_check_prove(Ctx&, int prover_kind, size_t num_vars, const lh_sop& expr, const Fr* const* d_polys,
-                               size_t num_polys, const HFr* ys, size_t num_ys, const HFr& sum, Transcript& tr,
-                               bool sum_is_exact = false, const ScRwPairs* rw = nullptr, bool sharded = false);
+// `u32` (optional): the single table d_polys[0] has NOT been written - its values are this 32-bit column.  The sum-check
+// either runs its first three rounds from the column (sumcheck.cpp: the sums of k_inner_products_small_quads are rounds 0
+// and 1, k_sc_round_u32_bind2 is round 2) or fills the table itself.
+struct ScU32 {
+  const uint32_t* col = nullptr;
+  bool have_sums = false;
+  Fr odd, s2, s3;  // (when have_sums: out_host[1..3] of k_inner_products_small_quads against the sum-check's E_0)
+};
+// `u32_terms` (optional), for the batch-opening shape sum_m eq(y_m, .) poly_m: poly b = sum_k w[k] col[k] over 32-bit
+// columns (entries beyond len[k] are zero) and d_polys[b] has NOT been written.  The sum-check runs its first three rounds
+// from the columns (sumcheck.cpp: k_inner_products_quads, k_lincomb_bind2) or fills the tables itself (k_lincomb_mixed)
+// and says so in SumCheckResult::u32_terms_built.
+struct ScU32Terms {
+  struct Poly {
+    std::vector<const uint32_t*> col;
+    std::vector<size_t> len;
+    std::vector<Fr> w;
+  };
+  std::vector<Poly> polys;
+};
 // `sharded` (inside a sharded proof, dev.hpp Shard): d_polys are this rank's shards of num_vars-variable tables; same
 // messages, same result on every rank
+struct ScOptions {
+  bool sum_is_exact = false;
+  bool sharded = false;
+  const ScRwPairs* rw = nullptr;
+  const ScU32* u32 = nullptr;
+  const ScU32Terms* u32_terms = nullptr;
+};
+SumCheckResult sum_check_prove(Ctx&, int prover_kind, size_t num_vars, const lh_sop& expr, const Fr* const* d_polys,
+                               size_t num_polys, const HFr* ys, size_t num_ys, const HFr& sum, Transcript& tr,
+                               const ScOptions& opt = ScOptions());
 
 // eq table of y[1..num_vars) (2^(num_vars-1) entries), shared through Ctx::eq_half_cache within one proof; `sharded`: this
 // rank's shard of it with the rank's factor of the shard coordinates multiplied in
@@ -224,9 +252,12 @@ struct GrandProductResult {
 // plus_one (optional): plus_one[b] != 0 says that tree b's leaves are tree (b - 1)'s leaves + 1, entry by entry (same
 // depth; Lasso's write set over its read set).  The leaf layer of such a pair then runs over tree (b - 1)'s tables
 // alone (dev.hpp ScRwRound) and d_leaves[b] is never read (it may be null; d_level_up[b] must be given).
+// `trees_built` (optional) is called once, when the trees are built and the layer sum-checks start: the latency-bound
+// stretch of a Lasso prove, where lasso_prove starts the opening's precommit
 GrandProductResult prove_grand_product(Ctx&, size_t num_trees, const Fr* const* d_leaves, const size_t* num_vars,
                                        Transcript& tr, const Fr* const* d_level_up = nullptr,
-                                       const uint8_t* plus_one = nullptr);
+                                       const uint8_t* plus_one = nullptr,
+                                       const std::function<void()>& trees_built = nullptr);
 
 // ------------------------------------------------------------------ pcs::multilinear::kzg
 struct Srs {
@@ -286,7 +317,7 @@ struct SmallOpen {
   std::vector<const Fr*> merged;
   std::vector<Fr> merged_w;
   // the merged tables may not have been written yet (the batch opening's sum-check ran from the columns: sumcheck.cpp,
-  // Ctx::sc_u32_terms): whoever needs them calls this first (null: they are there)
+  // ScOptions::u32_terms): whoever needs them calls this first (null: they are there)
   std::function<void()> ensure_merged;
 };
 // Options::open_precommit: commit the challenge-free half of the coming batch opening's column route on the ctx's helper
@@ -328,13 +359,19 @@ void zeromorph_batch_verify(const ZmVerifierParams&, size_t num_vars, const HG1*
                             const HFr* points, size_t num_points, const lh_evaluation* evals, size_t num_evals,
                             Transcript& tr);
 
-// ------------------------------------------------------------------ Lasso
-// what the Lasso prover needs from its PCS: bases whose first 2^nv points commit a zero-padded table of 2^nv entries
-// (the eq basis of level nv, or the powers of s), the largest nv they cover, and batch_open
-struct LassoPcs {
+// what the provers (Lasso, HyperPlonk and its Lasso lookups) need from their PCS: the PolynomialCommitmentScheme the
+// backend is generic over (backend/hyperplonk.rs:76-95), plus the bases themselves for the small-valued Lasso columns
+struct Pcs {
+  std::function<std::vector<HG1>(const Fr* const* d_polys, size_t num_polys, size_t num_vars)> batch_commit;
+  // bases whose first 2^nv points commit a zero-padded table of 2^nv entries (the eq basis of level nv, or the powers of
+  // s): the small-valued Lasso columns are committed as u32 MSMs against them.  nv <= max_vars is the caller's check
+  // (LH_ERR_INVALID_PCS_PARAM, "Too many variates of poly to commit")
   std::function<const G1Affine*(size_t nv)> commit_bases;
-  std::function<const G1Affine*(size_t nv)> shard_bases;  // this rank's share of them (sharded proofs; null: unsupported)
-  size_t max_vars;
+  // one proof over several GPUs (dev.hpp Shard): this rank's share of commit_bases; batch_commit / batch_open then take
+  // this rank's shards and add the ranks' partial commitments (null: this PCS does not shard)
+  std::function<const G1Affine*(size_t nv)> shard_bases;
+  size_t max_vars = 0;
+  // small (null allowed): the polys that came as small-valued u32 columns (SmallPoly above)
   std::function<void(size_t num_vars, const Fr* const* d_polys, size_t num_polys, const HFr* points, size_t num_points,
                      const lh_evaluation* evals, size_t num_evals, Transcript& tr, const SmallPoly* small)>
       batch_open;
@@ -342,8 +379,10 @@ struct LassoPcs {
   std::function<void(size_t num_vars, const SmallPoly* small, size_t num_polys, const lh_evaluation* evals, size_t num_evals)>
       precommit;
 };
-LassoPcs lasso_mkzg_pcs(Ctx&, const Srs&);
-LassoPcs lasso_zeromorph_pcs(Ctx&, const USrs&, size_t poly_size);
+Pcs mkzg_pcs(Ctx&, const Srs&);                            // mkzg.cpp
+Pcs zeromorph_pcs(Ctx&, const USrs&, size_t poly_size);    // zeromorph.cpp
+
+// ------------------------------------------------------------------ Lasso
 // pieces of the argument shared by the standalone prover (lasso.cpp) and HyperPlonk's Lasso lookups (hyperplonk.cpp)
 struct LassoColumns {  // small-valued witness columns as u32 (arena memory of the caller's scope)
   std::vector<uint32_t*> rts, fcs, E;
@@ -394,11 +433,12 @@ LassoColumns lasso_witness_columns(Ctx&, const lh_lasso_table&, size_t n, const 
 // `a`: the output column as field elements, or null with `a_small` given
 LassoClaims lasso_argue(Ctx&, const lh_lasso_table&, size_t n, const LassoColumns& w, const uint32_t* const* d_dims,
                         const Fr* a, const Fr* const* E_fr, Transcript& tr,
-                        const std::function<void(int)>& lap = nullptr, const uint32_t* a_small = nullptr);
+                        const std::function<void(int)>& lap = nullptr, const uint32_t* a_small = nullptr,
+                        const std::function<void()>& trees_built = nullptr);
 // commitment framing of the Lasso argument: identity mask as one field element, then the non-identity commitments
 void lasso_write_commitments(Transcript& tr, const std::vector<HG1>& comms);
 std::vector<HG1> lasso_read_commitments(Transcript& tr, size_t count);
-void lasso_prove(Ctx&, const LassoPcs&, const lh_lasso_table& table, size_t num_vars, const uint32_t* const* d_dims,
+void lasso_prove(Ctx&, const Pcs&, const lh_lasso_table& table, size_t num_vars, const uint32_t* const* d_dims,
                  Transcript& tr);
 void lasso_prove_sharded(Ctx&, const Srs&, const lh_lasso_table& table, size_t num_vars,
                          const uint32_t* const* d_dims, Transcript& tr);
@@ -430,23 +470,7 @@ void hyperplonk_verify_phases(const PcsBatchVerify& batch_verify, const lh_hp_vp
                               const HFr* const* instances, Transcript& tr);
 
 // ------------------------------------------------------------------ HyperPlonk (hyperplonk.cpp)
-// the PolynomialCommitmentScheme the backend is generic over (backend/hyperplonk.rs:76-95)
-struct PcsProver {
-  std::function<std::vector<HG1>(const Fr* const* d_polys, size_t num_polys, size_t num_vars)> batch_commit;
-  // bases whose first 2^nv points commit a (zero-padded) table of 2^nv entries: the small-valued Lasso columns are
-  // committed as u32 MSMs against them
-  std::function<const G1Affine*(size_t nv)> commit_bases;
-  std::function<void(size_t num_vars, const Fr* const* d_polys, size_t num_polys, const HFr* points, size_t num_points,
-                     const lh_evaluation* evals, size_t num_evals, Transcript& tr)>
-      batch_open;
-  // one proof over several GPUs (dev.hpp Shard): batch_commit / batch_open take this rank's shards and add the ranks'
-  // partial commitments; shard_bases: this rank's share of commit_bases
-  bool sharded_ok = false;
-  std::function<const G1Affine*(size_t nv)> shard_bases;
-};
-PcsProver mkzg_pcs(Ctx&, const Srs&);
-PcsProver zeromorph_pcs(Ctx&, const USrs&, size_t poly_size);
-void hyperplonk_prove(Ctx&, const PcsProver&, const lh_hp_param& pp, const HFr* const* instances,
+void hyperplonk_prove(Ctx&, const Pcs&, const lh_hp_param& pp, const HFr* const* instances,
                       const Fr* const* d_witness, Transcript& tr);
 // multi-phase circuits (hyperplonk.rs:185-205): phase r synthesizes num_witness_polys[r] device tables from the
 // challenges of the earlier phases (PlonkishCircuit::synthesize, backend.rs:139), then num_challenges[r] are squeezed
@@ -454,7 +478,7 @@ struct HpPhases {
   std::vector<size_t> num_witness_polys, num_challenges;
   std::function<std::vector<const Fr*>(size_t round, const std::vector<HFr>& challenges)> synthesize;
 };
-void hyperplonk_prove_phases(Ctx&, const PcsProver&, const lh_hp_param& pp, const HpPhases& phases,
+void hyperplonk_prove_phases(Ctx&, const Pcs&, const lh_hp_param& pp, const HpPhases& phases,
                              const HFr* const* instances, Transcript& tr);
 
 }  // namespace lh

@@ -113,37 +113,6 @@ static void compressed_poly(Ctx& c, const lh_expr* exprs, size_t width, const st
 }
 
 // ------------------------------------------------------------------ HyperPlonk::prove
-PcsProver mkzg_pcs(Ctx& c, const Srs& srs) {
-  PcsProver p;
-  p.batch_commit = [&c, &srs](const Fr* const* polys, size_t n, size_t nv) { return mkzg_batch_commit(c, srs, polys, n, nv); };
-  p.sharded_ok = true;  // (mkzg_batch_commit / mkzg_batch_open read the ctx's Shard geometry)
-  p.shard_bases = [&c, &srs](size_t nv) { return srs_shard_level(c, srs, nv); };
-  p.commit_bases = [&srs](size_t nv) {
-    LH_REQUIRE(nv <= srs.num_vars, LH_ERR_INVALID_PCS_PARAM, "Too many variates of poly to commit");
-    return srs.eq(nv);
-  };
-  p.batch_open = [&c, &srs](size_t nv, const Fr* const* polys, size_t n, const HFr* points, size_t np,
-                            const lh_evaluation* evals, size_t ne, Transcript& tr) {
-    mkzg_batch_open(c, srs, nv, polys, n, points, np, evals, ne, tr);
-  };
-  return p;
-}
-PcsProver zeromorph_pcs(Ctx& c, const USrs& srs, size_t poly_size) {
-  PcsProver p;
-  p.batch_commit = [&c, &srs, poly_size](const Fr* const* polys, size_t n, size_t nv) {
-    return zeromorph_batch_commit(c, srs, poly_size, polys, n, nv);
-  };
-  p.commit_bases = [&srs, poly_size](size_t nv) {
-    LH_REQUIRE(((size_t)1 << nv) <= poly_size, LH_ERR_INVALID_PCS_PARAM, "Too many variates of poly to commit");
-    return (const G1Affine*)srs.d_powers;
-  };
-  p.batch_open = [&c, &srs, poly_size](size_t nv, const Fr* const* polys, size_t n, const HFr* points, size_t np,
-                                       const lh_evaluation* evals, size_t ne, Transcript& tr) {
-    zeromorph_batch_open(c, srs, poly_size, nv, polys, n, points, np, evals, ne, tr);
-  };
-  return p;
-}
-
 namespace {
 struct PhaseTimer {  // LH_HP_DEBUG=1: wall-clock per phase on stderr (development aid)
   Ctx& c;
@@ -163,7 +132,7 @@ struct PhaseTimer {  // LH_HP_DEBUG=1: wall-clock per phase on stderr (developme
 };
 }  // namespace
 
-void hyperplonk_prove(Ctx& c, const PcsProver& pcs, const lh_hp_param& pp, const HFr* const* instances,
+void hyperplonk_prove(Ctx& c, const Pcs& pcs, const lh_hp_param& pp, const HFr* const* instances,
                       const Fr* const* d_witness, Transcript& tr) {
   // single phase: synthesize(0, []) = d_witness
   HpPhases ph;
@@ -175,7 +144,7 @@ void hyperplonk_prove(Ctx& c, const PcsProver& pcs, const lh_hp_param& pp, const
   hyperplonk_prove_phases(c, pcs, pp, ph, instances, tr);
 }
 
-void hyperplonk_prove_phases(Ctx& c, const PcsProver& pcs, const lh_hp_param& pp, const HpPhases& ph,
+void hyperplonk_prove_phases(Ctx& c, const Pcs& pcs, const lh_hp_param& pp, const HpPhases& ph,
                              const HFr* const* instances, Transcript& tr) {
   PhaseTimer pt(c);
   LH_REQUIRE(ph.num_witness_polys.size() == ph.num_challenges.size() && ph.synthesize, LH_ERR_ARG,
@@ -196,7 +165,7 @@ void hyperplonk_prove_phases(Ctx& c, const PcsProver& pcs, const lh_hp_param& pp
     LH_REQUIRE(sh.j >= 1 && sh.sharded(nv), LH_ERR_ARG, "sharded hyperplonk: the circuit is too small for this shard geometry");
     LH_REQUIRE(pp.num_lookups == 0, LH_ERR_ARG,
                "sharded hyperplonk: LogUp lookups do not shard (global sort-merge join); use Lasso lookups or replicas");
-    LH_REQUIRE(pcs.sharded_ok, LH_ERR_ARG, "sharded hyperplonk: implemented for multilinear KZG");
+    LH_REQUIRE(pcs.shard_bases != nullptr, LH_ERR_ARG, "sharded hyperplonk: implemented for multilinear KZG");
   }
   auto local_row = [&](size_t g, size_t* loc) {  // global row -> this rank's local index (false: another rank's row)
     if (!shn) {
@@ -269,6 +238,7 @@ void hyperplonk_prove_phases(Ctx& c, const PcsProver& pcs, const lh_hp_param& pp
       LH_REQUIRE(total <= LH_HP_LASSO_MAX_COMMITMENTS, LH_ERR_ARG,
                  "hyperplonk: the Lasso lookups of one circuit commit to more than 63 polys (sum of 2 * chunks + memories)");
     }
+    LH_REQUIRE(nv <= pcs.max_vars, LH_ERR_INVALID_PCS_PARAM, "Too many variates of poly to commit");
     const G1Affine* bases = shn ? pcs.shard_bases(nv) : pcs.commit_bases(nv);
     const G1Affine* bases_full = pcs.commit_bases(nv);
     std::vector<MsmJob>& jobs = lasso_jobs;
@@ -535,7 +505,7 @@ void hyperplonk_prove_phases(Ctx& c, const PcsProver& pcs, const lh_hp_param& pp
     for (size_t j = 0; j < cc; j++) push(base + cc + alpha + j, p0 + 3, cl.ev_l[j]);
   }
   if (!lasso.empty()) pt.lap("lasso lookups");
-  pcs.batch_open(nv, polys.data(), polys.size(), points.data(), num_points, evals.data(), evals.size(), tr);
+  pcs.batch_open(nv, polys.data(), polys.size(), points.data(), num_points, evals.data(), evals.size(), tr, nullptr);
   pt.lap("batch open");
   c.host_stamps_print();  // (LH_HOST_TRACE: the stamps of this prove's MSM batches and openings)
 }

@@ -964,8 +964,7 @@ void k_sc_round_rw(Ctx& c, const ScRwRound& rd, bool bind, size_t size, Fr* out_
   c.wait_round(seq);
 }
 
-void k_sc_round(Ctx& c, const ScRound& rd, int degree, bool bind, size_t size, Fr* evals_host) {
-  c.last_round_folded = false;  // (set below when the product-pair kernel ran a folding round: ScRound::pp == 2)
+bool k_sc_round(Ctx& c, const ScRound& rd, int degree, bool bind, size_t size, Fr* evals_host) {
   LH_REQUIRE(degree >= 1 && degree <= 6, LH_ERR_ARG, "sum-check degree must be in 1..6");
   LH_REQUIRE(size >= 1, LH_ERR_ARG, "sum-check round over an empty table");
   ScArgs a;
@@ -1035,7 +1034,7 @@ void k_sc_round(Ctx& c, const ScRound& rd, int degree, bool bind, size_t size, F
       }
     }
     c.wait_round(seq);
-    return;
+    return false;
   }
 
   // large rounds: one thread per pair keeps everything in registers; in between, one thread per
@@ -1046,7 +1045,6 @@ void k_sc_round(Ctx& c, const ScRound& rd, int degree, bool bind, size_t size, F
     size_t g2 = sc_entry_grid(c, 2 * size);
     Fr* partials = g2 == 1 ? evals_host : c.arena.alloc_n<Fr>(g2 * 2);
     const ScFinish kflag = finish(g2, true);
-    c.last_round_folded = rd.pp == 2 && bind;
     if (rd.pp) {
       // products per pair: binds, one per coefficient still applied on the way, ~0.62 per term for the shared reductions
       // (two points), the eq entry
@@ -1060,7 +1058,7 @@ void k_sc_round(Ctx& c, const ScRound& rd, int degree, bool bind, size_t size, F
       else hipLaunchKernelGGL((sc_round_e2_kernel<false>), dim3((unsigned)g2), dim3(256), 0, c.stream, a, size, partials, kflag);
     }
     c.wait_round(seq);
-    return;
+    return rd.pp == 2 && bind;  // (the product-pair kernel ran a folding round)
   }
   size_t g = (size * tp + 255) / 256;
   size_t cap = (size_t)c.num_cus * 4;
@@ -1081,6 +1079,7 @@ void k_sc_round(Ctx& c, const ScRound& rd, int degree, bool bind, size_t size, F
     }
   }
   c.wait_round(seq);
+  return false;
 }
 
 }  // namespace lh

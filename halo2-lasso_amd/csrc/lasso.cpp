@@ -12,33 +12,6 @@ static double now_ms() {
   return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
 }
 
-LassoPcs lasso_mkzg_pcs(Ctx& c, const Srs& srs) {
-  LassoPcs p;
-  p.commit_bases = [&srs](size_t nv) { return srs.eq(nv); };
-  p.shard_bases = [&c, &srs](size_t nv) { return srs_shard_level(c, srs, nv); };
-  p.max_vars = srs.num_vars;
-  p.batch_open = [&c, &srs](size_t nv, const Fr* const* polys, size_t np, const HFr* points, size_t npts,
-                            const lh_evaluation* evals, size_t ne, Transcript& tr, const SmallPoly* small) {
-    mkzg_batch_open(c, srs, nv, polys, np, points, npts, evals, ne, tr, small);
-  };
-  p.precommit = [&c, &srs](size_t nv, const SmallPoly* small, size_t np, const lh_evaluation* evals, size_t ne) {
-    open_precommit_start(c, srs, nv, small, np, evals, ne);
-  };
-  return p;
-}
-LassoPcs lasso_zeromorph_pcs(Ctx& c, const USrs& srs, size_t poly_size) {
-  LH_REQUIRE(poly_size >= 1 && poly_size <= srs.size, LH_ERR_INVALID_PCS_PARAM, "Too large poly_size to trim to");
-  LassoPcs p;
-  p.commit_bases = [&srs](size_t) { return (const G1Affine*)srs.d_powers; };
-  p.max_vars = 0;
-  while (((size_t)2 << p.max_vars) <= poly_size) p.max_vars++;
-  p.batch_open = [&c, &srs, poly_size](size_t nv, const Fr* const* polys, size_t np, const HFr* points, size_t npts,
-                                       const lh_evaluation* evals, size_t ne, Transcript& tr, const SmallPoly* small) {
-    zeromorph_batch_open(c, srs, poly_size, nv, polys, np, points, npts, evals, ne, tr, small);
-  };
-  return p;
-}
-
 // Commitment framing of the Lasso argument (oracle/pyref/lasso.py write_commitments / read_commitments).  A committed
 // column that is identically zero commits to the identity - the high-limb dim of a 32-bit range check whose values are
 // all below 2^16, read_ts when the indices are pairwise distinct - and the reference's transcript cannot encode the
@@ -252,10 +225,11 @@ LassoColumns lasso_witness_columns(Ctx& c, const lh_lasso_table& tb, size_t n, c
 }
 
 // Steps 2-7 of the argument (oracle/pyref/lasso.py argue): Surge sum-check, memory-checking grand products,
-// evaluations.  The Fr tables hold at least 2^n (fcs_fr: 2^l) entries; `lap` (optional) receives phase boundaries.
+// evaluations.  The Fr tables hold at least 2^n (fcs_fr: 2^l) entries; `lap` (optional) receives phase boundaries,
+// `trees_built` (optional) is prove_grand_product's.
 LassoClaims lasso_argue(Ctx& c, const lh_lasso_table& tb, size_t n, const LassoColumns& w, const uint32_t* const* d_dims,
                         const Fr* a, const Fr* const* E_fr, Transcript& tr, const std::function<void(int)>& lap,
-                        const uint32_t* a_small) {
+                        const uint32_t* a_small, const std::function<void()>& trees_built) {
   const size_t cc = tb.num_chunks, l = tb.chunk_bits, alpha = tb.num_memories;
   // inside a sharded proof (dev.hpp Shard) every n-variable column is this rank's shard (N entries); sums over a column -
   // evaluations, round messages - are partial sums added over the ranks; the 2^l-entry subtable side is replicated
@@ -304,17 +278,17 @@ LassoClaims lasso_argue(Ctx& c, const lh_lasso_table& tb, size_t n, const LassoC
     {
       ArenaScope scope(c.arena);
       const Fr* a_tab = a;
-      struct HintGuard {  // the hint is this sum-check's alone, whatever way it ends
-        Ctx& c;
-        ~HintGuard() { c.sc_u32 = Ctx::ScU32(); }
-      } hint_guard{c};
+      ScU32 u32;
+      ScOptions so;
+      so.sum_is_exact = true, so.sharded = shn;
       if (!a_tab) {
         // no field-element view of the output column: the sum-check runs its first three rounds from the 32-bit column where
-        // it can (a_sums above are rounds 0 and 1) and fills this table itself where it cannot (dev.hpp Ctx::sc_u32)
+        // it can (a_sums above are rounds 0 and 1) and fills this table itself where it cannot (host.hpp ScU32)
         a_tab = c.arena.alloc_n<Fr>(N);
-        c.sc_u32.col = a_small;
-        c.sc_u32.have_sums = have_a_sums;
-        if (have_a_sums) c.sc_u32.odd = a_sums[1], c.sc_u32.s2 = a_sums[2], c.sc_u32.s3 = a_sums[3];
+        u32.col = a_small;
+        u32.have_sums = have_a_sums;
+        if (have_a_sums) u32.odd = a_sums[1], u32.s2 = a_sums[2], u32.s3 = a_sums[3];
+        so.u32 = &u32;
       }
       lh_sop one_term;
       memset(&one_term, 0, sizeof(one_term));
@@ -324,7 +298,7 @@ LassoClaims lasso_argue(Ctx& c, const lh_lasso_table& tb, size_t n, const LassoC
       memcpy(&one_term.coeff[0], &one, 32);
       one_term.num_factors[0] = 1;
       one_term.factor[0][0] = 0;
-      sc = sum_check_prove(c, LH_SC_EVALUATIONS, n, one_term, &a_tab, 1, cl.r.data(), 1, cl.v, tr, true, nullptr, shn);
+      sc = sum_check_prove(c, LH_SC_EVALUATIONS, n, one_term, &a_tab, 1, cl.r.data(), 1, cl.v, tr, so);
     }
     std::vector<const uint32_t*> cols(w.E.begin(), w.E.end());
     sc.evals.assign(alpha, HFr::zero());
@@ -348,7 +322,9 @@ LassoClaims lasso_argue(Ctx& c, const lh_lasso_table& tb, size_t n, const LassoC
       surge.num_factors[m] = tb.g_num_factors[m];
       for (int k = 0; k < LH_SC_MAX_FACTORS; k++) surge.factor[m][k] = tb.g_factor[m][k];
     }
-    sc = sum_check_prove(c, LH_SC_EVALUATIONS, n, surge, E_fr, alpha, cl.r.data(), 1, cl.v, tr, true, nullptr, shn);
+    ScOptions so;
+    so.sum_is_exact = true, so.sharded = shn;
+    sc = sum_check_prove(c, LH_SC_EVALUATIONS, n, surge, E_fr, alpha, cl.r.data(), 1, cl.v, tr, so);
   }
   cl.r_z = sc.challenges;
   cl.e_rz = sc.evals;
@@ -390,7 +366,7 @@ LassoClaims lasso_argue(Ctx& c, const lh_lasso_table& tb, size_t n, const LassoC
       depths[2 * alpha + 2 * i] = depths[2 * alpha + 2 * i + 1] = l;
     }
     if (lap) lap(3);
-    GrandProductResult gp = prove_grand_product(c, 4 * alpha, leaves.data(), depths.data(), tr, level_up.data(), plus_one.data());
+    GrandProductResult gp = prove_grand_product(c, 4 * alpha, leaves.data(), depths.data(), tr, level_up.data(), plus_one.data(), trees_built);
     cl.r_N = gp.points[0];
     cl.r_M = gp.points[2 * alpha];
   }
@@ -426,7 +402,7 @@ LassoClaims lasso_argue(Ctx& c, const lh_lasso_table& tb, size_t n, const LassoC
   return cl;
 }
 
-void lasso_prove(Ctx& c, const LassoPcs& pcs, const lh_lasso_table& tb, size_t n, const uint32_t* const* d_dims,
+void lasso_prove(Ctx& c, const Pcs& pcs, const lh_lasso_table& tb, size_t n, const uint32_t* const* d_dims,
                  Transcript& tr) {
   lasso_check_table(tb);
   const size_t cc = tb.num_chunks, l = tb.chunk_bits, alpha = tb.num_memories;
@@ -679,19 +655,17 @@ void lasso_prove(Ctx& c, const LassoPcs& pcs, const lh_lasso_table& tb, size_t n
   // the sum-checks (Options::open_precommit)
   struct PrecommitGuard {  // (a prove that fails on the way drops what was started)
     Ctx& c;
-    ~PrecommitGuard() {
-      c.gkr_hook = nullptr;
-      open_precommit_cancel(c);
-    }
+    ~PrecommitGuard() { open_precommit_cancel(c); }
   } precommit_guard{c};
-  // (started when the memory-checking argument has built its product trees - Ctx::gkr_hook: beside the Surge rounds and the
-  // tree kernels, which stream at the HBM bound, the helper's sorts only get in the way: tree_up 1.2 -> 5.0 ms per proof)
-  if (pcs.precommit)
-    c.gkr_hook = [&] { pcs.precommit(nv, small.data(), small.size(), evs.data(), evs.size()); };
+  // (started when the memory-checking argument has built its product trees - prove_grand_product's trees_built: beside the
+  // Surge rounds and the tree kernels, which stream at the HBM bound, the helper's sorts only get in the way: tree_up 1.2 ->
+  // 5.0 ms per proof)
+  std::function<void()> precommit;
+  if (pcs.precommit) precommit = [&] { pcs.precommit(nv, small.data(), small.size(), evs.data(), evs.size()); };
 
   // ---- 2-7: Surge, memory checking, evaluations
   c.host_stamp("argue:start");
-  LassoClaims cl = lasso_argue(c, tb, n, w, d_dims, polys_n[0], E_fr, tr, lap, a_small);
+  LassoClaims cl = lasso_argue(c, tb, n, w, d_dims, polys_n[0], E_fr, tr, lap, a_small, precommit);
   c.host_stamp("argue:end");
   const std::vector<HFr>&r = cl.r, &r_z = cl.r_z, &r_N = cl.r_N, &r_M = cl.r_M, &ev_n = cl.ev_n, &ev_l = cl.ev_l;
   const HFr& v = cl.v;
@@ -731,12 +705,8 @@ void lasso_prove_sharded(Ctx& c, const Srs& srs, const lh_lasso_table& tb, size_
   LH_REQUIRE(c.has_comm, LH_ERR_ARG, "lasso_prove_sharded: no communicator attached");
   const size_t R = (size_t)c.comm.size;
   LH_REQUIRE(R >= 1 && (R & (R - 1)) == 0, LH_ERR_ARG, "sharded prove: the number of ranks must be a power of two");
-  struct Active {
-    Ctx& c;
-    explicit Active(Ctx& c_) : c(c_) { c.shard_active = true; }
-    ~Active() { c.shard_active = false; }
-  } active(c);
-  lasso_prove(c, lasso_mkzg_pcs(c, srs), tb, n, d_dims_local, tr);
+  ShardActive active(c);
+  lasso_prove(c, mkzg_pcs(c, srs), tb, n, d_dims_local, tr);
 }
 
 }  // namespace lh

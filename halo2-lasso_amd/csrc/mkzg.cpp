@@ -372,11 +372,11 @@ void additive_batch_open(Ctx& c, size_t num_vars, const Fr* const* d_polys, size
   // merged_j = sum_{i : point(i) = j} eq_xt[i] * poly_i  (:155-170; the lazy first scalar there is a
   // representation detail, every field value below is the same)
   // Every opened poly a 32-bit column and an opening that takes them as columns (one GPU): the merged tables are not even
-  // written - the sum-check gets the columns and their weights (Ctx::sc_u32_terms), runs its first three rounds from them
+  // written - the sum-check gets the columns and their weights (ScOptions::u32_terms), runs its first three rounds from them
   // and binds the merged polys twice in one pass; whoever still needs a table in full (the plain opening route) makes it then.
   bool all_small = small != nullptr && open_small != nullptr && !sharded;
   for (size_t i = 0; i < num_evals && all_small; i++) all_small = small[evals[i].poly].ptr != nullptr;
-  Ctx::ScU32Terms hint;
+  ScU32Terms hint;
   std::vector<const Fr*> merged(num_points);
   for (size_t j = 0; j < num_points; j++) {
     std::vector<const Fr*> src;
@@ -397,7 +397,7 @@ void additive_batch_open(Ctx& c, size_t num_vars, const Fr* const* d_polys, size
       }
     LH_REQUIRE(!src.empty() || !sm.empty(), LH_ERR_ARG, "batch open: a point without evaluations");
     Fr* m = c.arena.alloc_n<Fr>(n);
-    if (all_small) hint.polys.push_back(Ctx::ScU32Terms::Poly{sm, sm_len, wsm});
+    if (all_small) hint.polys.push_back(ScU32Terms::Poly{sm, sm_len, wsm});
     else if (sm.empty()) k_lincomb(c, src.data(), w.data(), src.size(), n, m);
     else k_lincomb_mixed(c, src.data(), w.data(), src.size(), sm.data(), sm_len.data(), wsm.data(), sm.size(), n, m);
     merged[j] = m;
@@ -406,7 +406,7 @@ void additive_batch_open(Ctx& c, size_t num_vars, const Fr* const* d_polys, size
   auto ensure_merged = [&] {
     if (merged_there) return;
     for (size_t j = 0; j < num_points; j++) {
-      const Ctx::ScU32Terms::Poly& pl = hint.polys[j];
+      const ScU32Terms::Poly& pl = hint.polys[j];
       k_lincomb_mixed(c, nullptr, nullptr, 0, pl.col.data(), pl.len.data(), pl.w.data(), pl.col.size(), n, const_cast<Fr*>(merged[j]));
     }
     merged_there = true;
@@ -428,14 +428,12 @@ void additive_batch_open(Ctx& c, size_t num_vars, const Fr* const* d_polys, size
     memcpy(&v, &evals[i].value, 32);
     tilde_gs_sum += v * eq_xt[i];
   }
-  struct HintGuard {  // the hint is this sum-check's alone, whatever way it ends
-    Ctx& c;
-    ~HintGuard() { c.sc_u32_terms = Ctx::ScU32Terms(); }
-  } hint_guard{c};
-  if (all_small) c.sc_u32_terms = hint;
+  ScOptions so;
+  so.sharded = sharded;
+  if (all_small) so.u32_terms = &hint;
   SumCheckResult sc = sum_check_prove(c, LH_SC_COEFFICIENTS, num_vars, expr, merged.data(), num_points, points,
-                                      num_points, tilde_gs_sum, tr, false, nullptr, sharded);
-  if (all_small) merged_there = c.sc_u32_terms.built;
+                                      num_points, tilde_gs_sum, tr, so);
+  if (all_small) merged_there = sc.u32_terms_built;
   // g' = sum_j eq_xy_eval(challenges, z_j) * merged_j  (:200-213)
   std::vector<Fr> w(num_points);
   for (size_t j = 0; j < num_points; j++)
@@ -469,5 +467,21 @@ void mkzg_batch_open(Ctx& c, const Srs& srs, size_t num_vars, const Fr* const* d
       [&](const Fr* g_prime, const HFr* point, const SmallOpen& so) { mkzg_open(c, srs, g_prime, num_vars, point, tr, &so); });
 }
 
+
+Pcs mkzg_pcs(Ctx& c, const Srs& srs) {  // (mkzg_batch_commit / mkzg_batch_open read the ctx's Shard geometry)
+  Pcs p;
+  p.batch_commit = [&c, &srs](const Fr* const* polys, size_t np, size_t nv) { return mkzg_batch_commit(c, srs, polys, np, nv); };
+  p.commit_bases = [&srs](size_t nv) { return srs.eq(nv); };
+  p.shard_bases = [&c, &srs](size_t nv) { return srs_shard_level(c, srs, nv); };
+  p.max_vars = srs.num_vars;
+  p.batch_open = [&c, &srs](size_t nv, const Fr* const* polys, size_t np, const HFr* points, size_t npts,
+                            const lh_evaluation* evals, size_t ne, Transcript& tr, const SmallPoly* small) {
+    mkzg_batch_open(c, srs, nv, polys, np, points, npts, evals, ne, tr, small);
+  };
+  p.precommit = [&c, &srs](size_t nv, const SmallPoly* small, size_t np, const lh_evaluation* evals, size_t ne) {
+    open_precommit_start(c, srs, nv, small, np, evals, ne);
+  };
+  return p;
+}
 
 }  // namespace lh

@@ -182,7 +182,7 @@ bool column_route_on(const Ctx& c, const std::vector<SmallPoly>& cols, const std
 
 void open_precommit_cancel(Ctx& c) {
   if (!c.precommit) return;
-  delete (OpenPrecommit*)c.precommit;  // (joins)
+  delete c.precommit;  // (joins)
   c.precommit = nullptr;
 }
 // the columns of a batch opening whose polys are all small-valued columns: `used` polys, a linear column's coefficient
@@ -293,7 +293,7 @@ void open_precommit_start(Ctx& c, const Srs& srs, size_t num_vars, const SmallPo
 std::unique_ptr<OpenPrecommit> open_precommit_take(Ctx& c, const Srs& srs, size_t num_vars,
                                                           const std::vector<SmallPoly>& cols, const std::vector<char>& zero,
                                                           const ColumnPlan& own) {
-  std::unique_ptr<OpenPrecommit> pc((OpenPrecommit*)c.precommit);
+  std::unique_ptr<OpenPrecommit> pc(c.precommit);
   c.precommit = nullptr;
   if (!pc) return nullptr;
   pc->join();

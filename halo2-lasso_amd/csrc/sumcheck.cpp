@@ -493,10 +493,14 @@ SumCheckResult sum_check_loop(Ctx& c, int prover_kind, size_t num_vars, int degr
       // (the device buffers hold 16 sums: degree <= 6, at most SC_OPEN_MAX_TERMS = 6 factored terms)
       const size_t nvals = !ef_on ? (size_t)degree : ef->per_term ? 2 * ef->eqs.size() : (size_t)degree - 1;
       LH_REQUIRE(nvals >= 1 && nvals <= 16, LH_ERR_ARG, "sharded sum-check: too many partial sums per round");
-      c.sc_redirect = d_part;
       uint64_t* d_lanes = (uint64_t*)d_all;  // [0, 128): this rank's lanes, [128, 256): the sums (comm_round 2)
-      if (lanes) c.sc_wide = d_lanes, c.sc_tag = comm_next_tag(c);
-      try {
+      {
+        struct Redirect {  // the launch mode of this round's kernel alone, whatever way the launcher returns
+          Ctx& c;
+          ~Redirect() { c.sc_redirect = nullptr, c.sc_wide = nullptr; }
+        } redirect{c};
+        c.sc_redirect = d_part;
+        if (lanes) c.sc_wide = d_lanes, c.sc_tag = comm_next_tag(c);
         if (ef_on) {
           ef->add_const = HFr::zero();
           ef->round(cur.data(), dst.data(), dev(r_prev), bind, size, round, (int)nvals, evals_host);
@@ -504,11 +508,7 @@ SumCheckResult sum_check_loop(Ctx& c, int prover_kind, size_t num_vars, int degr
         } else {
           round_fn(cur.data(), dst.data(), dev(r_prev), bind, size, evals_host);
         }
-      } catch (...) {
-        c.sc_redirect = nullptr, c.sc_wide = nullptr;
-        throw;
       }
-      c.sc_redirect = nullptr, c.sc_wide = nullptr;
       c.route.v[RouteStats::SHARDED_ROUNDS]++;
       c.route.v[factored_round ? RouteStats::EF_ROUNDS : RouteStats::STD_ROUNDS]++;
       if (lanes) {
@@ -623,10 +623,16 @@ SumCheckResult sum_check_loop(Ctx& c, int prover_kind, size_t num_vars, int degr
 // of all ranks are added; once the residual tables are small (at the latest before round shard_bit, when the shard bits
 // would become the pair bit) they are bound once more, exchanged, and the remaining rounds run replicated on every rank.
 // The transcript sees exactly the single-GPU messages.
-static SumCheckResult sum_check_prove_impl(Ctx& c, int prover_kind, size_t num_vars, const lh_sop& expr,
-                                           const Fr* const* d_polys, size_t num_polys, const HFr* ys, size_t num_ys,
-                                           const HFr& sum, Transcript& tr, bool sharded, bool sum_is_exact = false,
-                                           const ScRwPairs* rw = nullptr) {
+SumCheckResult sum_check_prove(Ctx& c, int prover_kind, size_t num_vars, const lh_sop& expr, const Fr* const* d_polys,
+                               size_t num_polys, const HFr* ys, size_t num_ys, const HFr& sum, Transcript& tr,
+                               const ScOptions& opt) {
+  const bool sharded = opt.sharded, sum_is_exact = opt.sum_is_exact;
+  const ScRwPairs* const rw = opt.rw;
+  if (rw)
+    LH_REQUIRE(rw->num_pairs >= 1 && rw->num_pairs <= (uint32_t)SC_RW_MAX_PAIRS && num_polys == 2 * (size_t)rw->num_pairs &&
+                   expr.global_eq >= 0 && sum_is_exact,
+               LH_ERR_ARG, "sum-check: tree-pair rounds over the wrong shape");
+  if (sharded) LH_REQUIRE(c.shard_active && c.has_comm, LH_ERR_ARG, "sharded sum-check outside a sharded proof");
   LH_REQUIRE(num_vars > 0, LH_ERR_ARG, "sum-check needs num_vars > 0");  // classic.rs:42 assert
   const size_t T = num_polys + num_ys;
   LH_REQUIRE(T <= (size_t)SC_MAX_TABLES, LH_ERR_ARG, "sum-check: too many tables for one round kernel");
@@ -667,10 +673,9 @@ static SumCheckResult sum_check_prove_impl(Ctx& c, int prover_kind, size_t num_v
 
   ArenaScope scope(c.arena);
   const size_t len0 = (size_t)1 << (num_vars - rho);
-  const Ctx::ScU32 u32 = c.sc_u32;  // (dev.hpp: poly 0 still is a 32-bit column; decided below who turns it into field elements)
-  c.sc_u32 = Ctx::ScU32();
-  Ctx::ScU32Terms u32t;  // (dev.hpp: the polys still are combinations of 32-bit columns)
-  std::swap(u32t, c.sc_u32_terms);
+  const ScU32 u32 = opt.u32 ? *opt.u32 : ScU32();  // (host.hpp: poly 0 still is a 32-bit column; decided below who turns it into field elements)
+  static const ScU32Terms no_terms;
+  const ScU32Terms& u32t = opt.u32_terms ? *opt.u32_terms : no_terms;  // (host.hpp: the polys still are combinations of 32-bit columns)
   bool u32t_rounds = false, u32t_bound = false;
   bool u32_rounds = false;
   std::vector<const Fr*> cur(T);
@@ -775,7 +780,7 @@ static SumCheckResult sum_check_prove_impl(Ctx& c, int prover_kind, size_t num_v
   // rounds 0 and 1 need no challenge (k_inner_products_small_quads: the caller's, or made here), round 2 binds r0 and r1 from
   // the column (k_sc_round_u32_bind2); from round 3 on the table is field elements.  Round 1 binds nothing: the loop's
   // table pointer of that round names memory nobody reads.
-  Ctx::ScU32 u32s = u32;
+  ScU32 u32s = u32;
   Fr u32_r0;
   bool u32_bound = false;
   if (u32.col) {
@@ -799,17 +804,16 @@ static SumCheckResult sum_check_prove_impl(Ctx& c, int prover_kind, size_t num_v
     bool ok = !u32t_off && use_ef && ef.per_term && !sharded && degree == 2 && streams2 && num_vars >= 22 &&
               k_sc_round_streams(rd, degree, len0 >> 3) &&
               (len0 >> 2) > std::max<size_t>(k_sc_tail_capacity(c, rd, degree), (size_t)GKR_CAP * GKR_CAP);
-    for (const Ctx::ScU32Terms::Poly& pl : u32t.polys) {
+    for (const ScU32Terms::Poly& pl : u32t.polys) {
       ok = ok && !pl.col.empty() && pl.col.size() <= 24;
       for (size_t ln : pl.len) ok = ok && ln % 4 == 0;
     }
     u32t_rounds = ok;
     if (!ok)
       for (size_t b = 0; b < num_polys; b++) {
-        const Ctx::ScU32Terms::Poly& pl = u32t.polys[b];
+        const ScU32Terms::Poly& pl = u32t.polys[b];
         k_lincomb_mixed(c, nullptr, nullptr, 0, pl.col.data(), pl.len.data(), pl.w.data(), pl.col.size(), len0, const_cast<Fr*>(d_polys[b]));
       }
-    c.sc_u32_terms.built = !ok;
   }
   const bool pp_shape = use_ef && !ef.per_term && pp_terms;
   std::vector<HFr> pp_folded;  // the coefficients that went into the left factors (empty: not folded)
@@ -915,8 +919,7 @@ static SumCheckResult sum_check_prove_impl(Ctx& c, int prover_kind, size_t num_v
         g.eq_level = ef.eqs[0].level[round];
         g.pp = pp_shape && points == 2 ? 1 : 0;
         if (g.pp && bind && pp_folded.empty() && c.opt.sc_pp_fold == 1) g.pp = 2;  // this round stores l'_m = c_m l_m
-        k_sc_round(c, g, points, bind, size, out_host);
-        if (g.pp == 2 && c.last_round_folded) {  // (the launch that was chosen for this size did fold)
+        if (k_sc_round(c, g, points, bind, size, out_host)) {  // (the launch that was chosen for this size did fold)
           pp_folded.resize(rd.num_terms);
           for (uint32_t m = 0; m < rd.num_terms; m++) {
             memcpy(&pp_folded[m], &rd.coeff[m], 32);
@@ -936,7 +939,7 @@ static SumCheckResult sum_check_prove_impl(Ctx& c, int prover_kind, size_t num_v
           Fr* d_s = c.arena.alloc_n<Fr>(4 * total);
           size_t off = 0;
           for (uint32_t m = 0; m < M; m++) {
-            const Ctx::ScU32Terms::Poly& pl = u32t.polys[term_poly[m]];
+            const ScU32Terms::Poly& pl = u32t.polys[term_poly[m]];
             k_inner_products_quads(c, pl.col.data(), pl.len.data(), pl.col.size(), ef.eqs[m].level[1], size >> 1, d_s + 4 * off);
             off += pl.col.size();
           }
@@ -945,7 +948,7 @@ static SumCheckResult sum_check_prove_impl(Ctx& c, int prover_kind, size_t num_v
           u32t_sums.assign(4 * (size_t)M, dev(HFr::zero()));
           off = 0;
           for (uint32_t m = 0; m < M; m++) {
-            const Ctx::ScU32Terms::Poly& pl = u32t.polys[term_poly[m]];
+            const ScU32Terms::Poly& pl = u32t.polys[term_poly[m]];
             HFr t4[4] = {HFr::zero(), HFr::zero(), HFr::zero(), HFr::zero()};
             for (size_t k = 0; k < pl.col.size(); k++)
               for (int t = 0; t < 4; t++) t4[t] += hst(pl.w[k]) * hst(hs[4 * (off + k) + t]);
@@ -967,7 +970,7 @@ static SumCheckResult sum_check_prove_impl(Ctx& c, int prover_kind, size_t num_v
         } else {
           Fr* two = (Fr*)c.pin(65536) + 1024;  // (behind the argument block of k_lincomb_bind2; a launch per term)
           for (uint32_t m = 0; m < M; m++) {
-            const Ctx::ScU32Terms::Poly& pl = u32t.polys[term_poly[m]];
+            const ScU32Terms::Poly& pl = u32t.polys[term_poly[m]];
             k_lincomb_bind2(c, pl.col.data(), pl.len.data(), pl.w.data(), pl.col.size(), u32t_r0, r, ef.eqs[m].level[2], size,
                             out[term_poly[m]], two);
             out_host[2 * m] = two[0], out_host[2 * m + 1] = two[1];
@@ -1044,6 +1047,7 @@ static SumCheckResult sum_check_prove_impl(Ctx& c, int prover_kind, size_t num_v
                                       use_ef ? &ef : nullptr);
   LH_REQUIRE(!u32_rounds || u32_bound, LH_ERR_DEVICE, "sum-check: the 32-bit column was never bound");
   LH_REQUIRE(!u32t_rounds || u32t_bound, LH_ERR_DEVICE, "sum-check: the 32-bit columns were never bound");
+  res.u32_terms_built = !u32t.polys.empty() && !u32t_rounds;
   if (rw_folded) {
     // l' = cs (l + k), r' = r + k came out: l = l' / cs - k, r = r' - k (one inversion for the coefficients)
     const size_t K = rw->num_pairs;
@@ -1071,18 +1075,5 @@ static SumCheckResult sum_check_prove_impl(Ctx& c, int prover_kind, size_t num_v
   }
   return res;
 }
-
-SumCheckResult sum_check_prove(Ctx& c, int prover_kind, size_t num_vars, const lh_sop& expr,
-                               const Fr* const* d_polys, size_t num_polys, const HFr* ys, size_t num_ys,
-                               const HFr& sum, Transcript& tr, bool sum_is_exact, const ScRwPairs* rw, bool sharded) {
-  if (rw)
-    LH_REQUIRE(rw->num_pairs >= 1 && rw->num_pairs <= (uint32_t)SC_RW_MAX_PAIRS && num_polys == 2 * (size_t)rw->num_pairs &&
-                   expr.global_eq >= 0 && sum_is_exact,
-               LH_ERR_ARG, "sum-check: tree-pair rounds over the wrong shape");
-  if (sharded) LH_REQUIRE(c.shard_active && c.has_comm, LH_ERR_ARG, "sharded sum-check outside a sharded proof");
-  return sum_check_prove_impl(c, prover_kind, num_vars, expr, d_polys, num_polys, ys, num_ys, sum, tr, sharded, sum_is_exact,
-                              rw);
-}
-
 
 }  // namespace lh

@@ -121,4 +121,19 @@ void zeromorph_batch_open(Ctx& c, const USrs& srs, size_t poly_size, size_t num_
       [&](const Fr* g_prime, const HFr* point) { zeromorph_open(c, srs, poly_size, g_prime, num_vars, point, tr); }, small);
 }
 
+Pcs zeromorph_pcs(Ctx& c, const USrs& srs, size_t poly_size) {
+  LH_REQUIRE(poly_size >= 1 && poly_size <= srs.size, LH_ERR_INVALID_PCS_PARAM, "Too large poly_size to trim to");
+  Pcs p;
+  p.batch_commit = [&c, &srs, poly_size](const Fr* const* polys, size_t np, size_t nv) {
+    return zeromorph_batch_commit(c, srs, poly_size, polys, np, nv);
+  };
+  p.commit_bases = [&srs](size_t) { return (const G1Affine*)srs.d_powers; };
+  while (((size_t)2 << p.max_vars) <= poly_size) p.max_vars++;
+  p.batch_open = [&c, &srs, poly_size](size_t nv, const Fr* const* polys, size_t np, const HFr* points, size_t npts,
+                                       const lh_evaluation* evals, size_t ne, Transcript& tr, const SmallPoly* small) {
+    zeromorph_batch_open(c, srs, poly_size, nv, polys, np, points, npts, evals, ne, tr, small);
+  };
+  return p;
+}
+
 }  // namespace lh
