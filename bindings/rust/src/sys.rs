@@ -294,6 +294,42 @@ extern "C" {
                                out: *mut core::ffi::c_char, cap: usize, len: *mut usize) -> lh_status;
     // Zeromorph over univariate KZG: lh_ukzg_setup, lh_usrs_*, lh_zeromorph_* follow the same shapes
     // (include/lasso_hip.h, section f3) and are bound the same way when HyperPlonk<Zeromorph<..>> is wanted.
+    // Univariate KZG on its own and Gemini over it (include/lasso_hip.h, section f3b); lh_usrs / lh_ukzg_vp are opaque here
+    pub fn lh_ukzg_batch_commit(ctx: *mut lh_ctx, srs: *const c_void, poly_size: usize, d_polys: *const *const Fr,
+                                lens: *const usize, num_polys: usize, out_comms: *mut G1Affine) -> lh_status;
+    pub fn lh_ukzg_open(ctx: *mut lh_ctx, srs: *const c_void, poly_size: usize, d_poly: *const Fr, len: usize,
+                        point: *const Fr, t: *mut lh_transcript) -> lh_status;
+    pub fn lh_ukzg_batch_open(ctx: *mut lh_ctx, srs: *const c_void, poly_size: usize, d_polys: *const *const Fr,
+                              lens: *const usize, num_polys: usize, points: *const Fr, num_points: usize,
+                              evals: *const lh_evaluation, num_evals: usize, t: *mut lh_transcript) -> lh_status;
+    pub fn lh_ukzg_vp_setup(s: *const Fr, out: *mut *mut c_void) -> lh_status;
+    pub fn lh_ukzg_vp_free(vp: *mut c_void);
+    pub fn lh_ukzg_verify(vp: *const c_void, comm: *const G1Affine, point: *const Fr, eval: *const Fr,
+                          t: *mut lh_transcript) -> lh_status;
+    pub fn lh_ukzg_batch_verify(vp: *const c_void, comms: *const G1Affine, num_comms: usize, points: *const Fr,
+                                num_points: usize, evals: *const lh_evaluation, num_evals: usize,
+                                t: *mut lh_transcript) -> lh_status;
+    pub fn lh_gemini_batch_commit(ctx: *mut lh_ctx, srs: *const c_void, poly_size: usize, d_polys: *const *const Fr,
+                                  num_polys: usize, num_vars: usize, out_comms: *mut G1Affine) -> lh_status;
+    pub fn lh_gemini_open(ctx: *mut lh_ctx, srs: *const c_void, poly_size: usize, d_poly: *const Fr, num_vars: usize,
+                          point: *const Fr, t: *mut lh_transcript) -> lh_status;
+    pub fn lh_gemini_batch_open(ctx: *mut lh_ctx, srs: *const c_void, poly_size: usize, num_vars: usize,
+                                d_polys: *const *const Fr, num_polys: usize, points: *const Fr, num_points: usize,
+                                evals: *const lh_evaluation, num_evals: usize, t: *mut lh_transcript) -> lh_status;
+    pub fn lh_gemini_verify(vp: *const c_void, comm: *const G1Affine, point: *const Fr, num_vars: usize, eval: *const Fr,
+                            t: *mut lh_transcript) -> lh_status;
+    pub fn lh_gemini_batch_verify(vp: *const c_void, num_vars: usize, comms: *const G1Affine, num_comms: usize,
+                                  points: *const Fr, num_points: usize, evals: *const lh_evaluation, num_evals: usize,
+                                  t: *mut lh_transcript) -> lh_status;
+    pub fn lh_lasso_prove_gemini(ctx: *mut lh_ctx, srs: *const c_void, poly_size: usize, table: *const lh_lasso_table,
+                                 num_vars: usize, d_dims: *const *const u32, t: *mut lh_transcript) -> lh_status;
+    pub fn lh_lasso_verify_gemini(vp: *const c_void, table: *const lh_lasso_table, num_vars: usize,
+                                  t: *mut lh_transcript) -> lh_status;
+    pub fn lh_hyperplonk_prove_gemini(ctx: *mut lh_ctx, srs: *const c_void, poly_size: usize, pp: *const lh_hp_param,
+                                      instances: *const *const Fr, d_witness_polys: *const *const Fr,
+                                      t: *mut lh_transcript) -> lh_status;
+    pub fn lh_hyperplonk_verify_gemini(vp: *const c_void, hvp: *const lh_hp_vparam, instances: *const *const Fr,
+                                       t: *mut lh_transcript) -> lh_status;
     // Brakedown (include/lasso_hip.h, section f4); params and commitments are opaque here
     pub fn lh_keccak_transcript_hash_io(t: *mut lh_transcript, out: *mut lh_hash_transcript) -> lh_status;
     pub fn lh_brakedown_setup(ctx: *mut lh_ctx, num_vars: usize, spec: c_int, seed32: *const u8,

@@ -716,7 +716,8 @@ def sum_check_verify(prover, num_vars, degree, sum_, transcript):
 def lasso_verify(vp, table, num_vars, transcript):
     """Verifier of the Lasso argument (oracle/pyref/lasso.py:219-261).  A Keccak256Transcript must be fully consumed."""
     t = table.to_c()
-    fn = vp.lib.lh_lasso_verify_zeromorph if isinstance(vp, ZeromorphVerifierParam) else vp.lib.lh_lasso_verify
+    fn = vp.lib.lh_lasso_verify_zeromorph if isinstance(vp, ZeromorphVerifierParam) else \
+        vp.lib.lh_lasso_verify_gemini if isinstance(vp, GeminiVerifierParam) else vp.lib.lh_lasso_verify
     _check(fn(vp.h, C.byref(t), num_vars, transcript.p))
     if isinstance(transcript, Keccak256Transcript) and transcript.remaining():
         raise InvalidSnark("trailing bytes in proof")
@@ -868,6 +869,216 @@ class Zeromorph:
         flat = [v for p in points for v in p]
         _check(vp.lib.lh_zeromorph_batch_verify(vp.h, num_vars, _g1_array(comms), len(comms), _fr_array(flat),
                                                 len(points), _evaluations(evals), len(evals), transcript.p))
+
+
+# ------------------------------------------------------------------ pcs::univariate::kzg on its own, pcs::multilinear::gemini over it
+class UnivariatePolynomial:
+    """UnivariatePolynomial in the coefficient basis: `len` coefficients in a device buffer (fixed length: leading zero
+    coefficients are kept, they change no commitment)"""
+
+    def __init__(self, ctx, buf, length):
+        self.ctx, self.buf, self.len = ctx, buf, length
+
+    @classmethod
+    def from_ints(cls, ctx, coeffs):
+        return cls(ctx, ctx.upload(frs_to_bytes(coeffs)) if coeffs else None, len(coeffs))
+
+    @property
+    def ptr(self):
+        return self.buf.ptr if self.buf is not None else None
+
+
+class UnivariateKzgProverParam:
+    """UnivariateKzgProverParam (univariate/kzg.rs:68-88) = the device SRS + the trim size"""
+
+    def __init__(self, params, poly_size):
+        self.params, self.poly_size, self.ctx = params, poly_size, params.ctx
+
+
+class UnivariateKzgVerifierParam:
+    """UnivariateKzgVerifierParam (univariate/kzg.rs:90-120): (g1, g2, [s]_2), host only"""
+
+    def __init__(self, handle):
+        self.lib, self.h = _ffi.load(), handle
+
+    @classmethod
+    def setup(cls, s):
+        h = C.c_void_p()
+        _check(_ffi.load().lh_ukzg_vp_setup(_fr_array([s]), C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def new(cls, g1, g2, s_g2):
+        h, a = C.c_void_p(), _ffi.lh_g1()
+        C.memmove(C.byref(a), g1_to_bytes(g1), 64)
+        gs = []
+        for p in (g2, s_g2):
+            b = _ffi.lh_g2()
+            C.memmove(C.byref(b), g2_to_bytes(p), 128)
+            gs.append(b)
+        _check(_ffi.load().lh_ukzg_vp_new(C.byref(a), C.byref(gs[0]), C.byref(gs[1]), C.byref(h)))
+        return cls(h)
+
+    def export(self):
+        a, b, c_ = _ffi.lh_g1(), _ffi.lh_g2(), _ffi.lh_g2()
+        _check(self.lib.lh_ukzg_vp_export(self.h, C.byref(a), C.byref(b), C.byref(c_)))
+        return g1_from_bytes(bytes(a)), g2_from_bytes(bytes(b)), g2_from_bytes(bytes(c_))
+
+    def free(self):
+        if self.h:
+            self.lib.lh_ukzg_vp_free(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def _upoly_arrays(polys):
+    ptrs = (C.c_void_p * max(len(polys), 1))(*[p.ptr for p in polys])
+    lens = (C.c_size_t * max(len(polys), 1))(*[p.len for p in polys])
+    return ptrs, lens
+
+
+class UnivariateKzg:
+    """UnivariateKzg<Bn256> (pcs/univariate/kzg.rs:161-555); points are field elements"""
+
+    setup = staticmethod(lambda ctx, s, poly_size: Zeromorph.setup(ctx, s, poly_size))
+    upload = staticmethod(lambda ctx, powers: Zeromorph.upload(ctx, powers))
+    PROVER_PARAM = UnivariateKzgProverParam
+
+    @classmethod
+    def trim(cls, params, poly_size):
+        """kzg.rs:220-240 (prover half)"""
+        if params.size < poly_size:
+            raise InvalidPcsParam("Too large poly_size to trim to (param supports poly_size up to %d but got %d)"
+                                  % (params.size, poly_size))
+        return cls.PROVER_PARAM(params, poly_size)
+
+    @staticmethod
+    def batch_commit(pp, polys):
+        if not polys:
+            return []
+        out = (lh_g1 * len(polys))()
+        ptrs, lens = _upoly_arrays(polys)
+        _check(pp.ctx.lib.lh_ukzg_batch_commit(pp.ctx.h, pp.params.h, pp.poly_size, ptrs, lens, len(polys), out))
+        raw = C.string_at(out, 64 * len(polys))
+        return [g1_from_bytes(raw[64 * i:64 * i + 64]) for i in range(len(polys))]
+
+    @staticmethod
+    def commit(pp, poly):
+        return UnivariateKzg.batch_commit(pp, [poly])[0]
+
+    @staticmethod
+    def batch_commit_and_write(pp, polys, transcript):
+        comms = UnivariateKzg.batch_commit(pp, polys)
+        transcript.write_commitments(comms)
+        return comms
+
+    @staticmethod
+    def open(pp, poly, point, transcript):
+        _check(pp.ctx.lib.lh_ukzg_open(pp.ctx.h, pp.params.h, pp.poly_size, poly.ptr, poly.len, _fr_array([point]),
+                                       transcript.p))
+
+    @staticmethod
+    def batch_open(pp, polys, points, evals, transcript):
+        ptrs, lens = _upoly_arrays(polys)
+        _check(pp.ctx.lib.lh_ukzg_batch_open(pp.ctx.h, pp.params.h, pp.poly_size, ptrs, lens, len(polys),
+                                             _fr_array(points), len(points), _evaluations(evals), len(evals),
+                                             transcript.p))
+
+    @staticmethod
+    def verify(vp, comm, point, eval_, transcript):
+        _check(vp.lib.lh_ukzg_verify(vp.h, _g1_array([comm]), _fr_array([point]), _fr_array([eval_]), transcript.p))
+
+    @staticmethod
+    def batch_verify(vp, comms, points, evals, transcript):
+        _check(vp.lib.lh_ukzg_batch_verify(vp.h, _g1_array(comms), len(comms), _fr_array(points), len(points),
+                                           _evaluations(evals), len(evals), transcript.p))
+
+
+class GeminiProverParam(UnivariateKzgProverParam):
+    """Gemini's ProverParam is UnivariateKzg's (gemini.rs:36-37); a type of its own so that provers can dispatch on it"""
+
+
+class GeminiVerifierParam(UnivariateKzgVerifierParam):
+    """Gemini's VerifierParam is UnivariateKzg's (gemini.rs:38)"""
+
+
+class Gemini:
+    """Gemini<UnivariateKzg<Bn256>> (pcs/multilinear/gemini.rs:29-211): the method set of Zeromorph"""
+
+    setup = staticmethod(lambda ctx, s, poly_size: Zeromorph.setup(ctx, s, poly_size))
+    upload = staticmethod(lambda ctx, powers: Zeromorph.upload(ctx, powers))
+
+    @staticmethod
+    def trim(params, poly_size):
+        if params.size < poly_size:
+            raise InvalidPcsParam("Too large poly_size to trim to (param supports poly_size up to %d but got %d)"
+                                  % (params.size, poly_size))
+        return GeminiProverParam(params, poly_size)
+
+    @staticmethod
+    def batch_commit(pp, polys):
+        if not polys:
+            return []
+        out = (lh_g1 * len(polys))()
+        _check(pp.ctx.lib.lh_gemini_batch_commit(pp.ctx.h, pp.params.h, pp.poly_size, _ptr_array(polys), len(polys),
+                                                 polys[0].num_vars, out))
+        raw = C.string_at(out, 64 * len(polys))
+        return [g1_from_bytes(raw[64 * i:64 * i + 64]) for i in range(len(polys))]
+
+    @staticmethod
+    def commit(pp, poly):
+        return Gemini.batch_commit(pp, [poly])[0]
+
+    @staticmethod
+    def batch_commit_and_write(pp, polys, transcript):
+        comms = Gemini.batch_commit(pp, polys)
+        transcript.write_commitments(comms)
+        return comms
+
+    @staticmethod
+    def open(pp, poly, point, transcript):
+        _check(pp.ctx.lib.lh_gemini_open(pp.ctx.h, pp.params.h, pp.poly_size, poly.ptr, poly.num_vars, _fr_array(point),
+                                         transcript.p))
+
+    @staticmethod
+    def folds(ctx, poly, point):
+        """the folds fs[1..] of an opening at `point`, as lists of ints (tests)"""
+        n = poly.num_vars
+        if n < 2:
+            return []
+        out = ctx.alloc(32 * ((1 << n) - 2))
+        _check(ctx.lib.lh_gemini_folds(ctx.h, poly.ptr, n, _fr_array(point), out.ptr))
+        flat, res, off = frs_from_bytes(out.read()), [], 0
+        for i in range(1, n):
+            res.append(flat[off:off + (1 << (n - i))])
+            off += 1 << (n - i)
+        return res
+
+    @staticmethod
+    def batch_open(pp, num_vars, polys, points, evals, transcript):
+        for p in points:
+            if len(p) != num_vars:
+                raise InvalidPcsParam("Invalid point (expect point to have %d variates but got %d)" % (num_vars, len(p)))
+        flat = [v for p in points for v in p]
+        _check(pp.ctx.lib.lh_gemini_batch_open(pp.ctx.h, pp.params.h, pp.poly_size, num_vars, _ptr_array(polys),
+                                               len(polys), _fr_array(flat), len(points), _evaluations(evals), len(evals),
+                                               transcript.p))
+
+    @staticmethod
+    def verify(vp, comm, point, eval_, transcript):
+        _check(vp.lib.lh_gemini_verify(vp.h, _g1_array([comm]), _fr_array(point), len(point), _fr_array([eval_]),
+                                       transcript.p))
+
+    @staticmethod
+    def batch_verify(vp, num_vars, comms, points, evals, transcript):
+        flat = [v for p in points for v in p]
+        _check(vp.lib.lh_gemini_batch_verify(vp.h, num_vars, _g1_array(comms), len(comms), _fr_array(flat), len(points),
+                                             _evaluations(evals), len(evals), transcript.p))
 
 
 # ------------------------------------------------------------------ pcs::multilinear::brakedown
@@ -1066,9 +1277,9 @@ def lasso_prove(pp, table, num_vars, dims, transcript):
             or len(table.g_terms) > _ffi.LH_LASSO_MAX_TERMS:
         raise ArgumentError("table too large")
     t = table.to_c()
-    if isinstance(pp, ZeromorphProverParam):
-        _check(pp.ctx.lib.lh_lasso_prove_zeromorph(pp.ctx.h, pp.params.h, pp.poly_size, C.byref(t), num_vars,
-                                                   _ptr_array(dims), transcript.p))
+    if isinstance(pp, (ZeromorphProverParam, GeminiProverParam)):
+        fn = pp.ctx.lib.lh_lasso_prove_gemini if isinstance(pp, GeminiProverParam) else pp.ctx.lib.lh_lasso_prove_zeromorph
+        _check(fn(pp.ctx.h, pp.params.h, pp.poly_size, C.byref(t), num_vars, _ptr_array(dims), transcript.p))
         return
     _check(pp.ctx.lib.lh_lasso_prove(pp.ctx.h, pp.h, C.byref(t), num_vars, _ptr_array(dims), transcript.p))
 

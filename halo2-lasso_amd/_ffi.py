@@ -258,6 +258,38 @@ SIGNATURES = {
                                                        C.POINTER(lh_hp_circuit), C.POINTER(lh_transcript)]),
     "lh_hyperplonk_verify_phases_zeromorph": (C.c_int, [_P, C.POINTER(lh_hp_vparam), _SZ, C.POINTER(_SZ), C.POINTER(_SZ),
                                                         C.POINTER(C.POINTER(lh_fr)), C.POINTER(lh_transcript)]),
+    "lh_ukzg_batch_commit": (C.c_int, [_P, _P, _SZ, C.POINTER(_P), C.POINTER(_SZ), _SZ, C.POINTER(lh_g1)]),
+    "lh_ukzg_open": (C.c_int, [_P, _P, _SZ, _P, _SZ, C.POINTER(lh_fr), C.POINTER(lh_transcript)]),
+    "lh_ukzg_batch_open": (C.c_int, [_P, _P, _SZ, C.POINTER(_P), C.POINTER(_SZ), _SZ, C.POINTER(lh_fr), _SZ,
+                                     C.POINTER(lh_evaluation), _SZ, C.POINTER(lh_transcript)]),
+    "lh_ukzg_vp_setup": (C.c_int, [C.POINTER(lh_fr), C.POINTER(_P)]),
+    "lh_ukzg_vp_new": (C.c_int, [C.POINTER(lh_g1), C.POINTER(lh_g2), C.POINTER(lh_g2), C.POINTER(_P)]),
+    "lh_ukzg_vp_export": (C.c_int, [_P, C.POINTER(lh_g1), C.POINTER(lh_g2), C.POINTER(lh_g2)]),
+    "lh_ukzg_vp_free": (None, [_P]),
+    "lh_ukzg_verify": (C.c_int, [_P, C.POINTER(lh_g1), C.POINTER(lh_fr), C.POINTER(lh_fr), C.POINTER(lh_transcript)]),
+    "lh_ukzg_batch_verify": (C.c_int, [_P, C.POINTER(lh_g1), _SZ, C.POINTER(lh_fr), _SZ, C.POINTER(lh_evaluation), _SZ,
+                                       C.POINTER(lh_transcript)]),
+    "lh_gemini_batch_commit": (C.c_int, [_P, _P, _SZ, C.POINTER(_P), _SZ, _SZ, C.POINTER(lh_g1)]),
+    "lh_gemini_open": (C.c_int, [_P, _P, _SZ, _P, _SZ, C.POINTER(lh_fr), C.POINTER(lh_transcript)]),
+    "lh_gemini_batch_open": (C.c_int, [_P, _P, _SZ, _SZ, C.POINTER(_P), _SZ, C.POINTER(lh_fr), _SZ,
+                                       C.POINTER(lh_evaluation), _SZ, C.POINTER(lh_transcript)]),
+    "lh_gemini_folds": (C.c_int, [_P, _P, _SZ, C.POINTER(lh_fr), _P]),
+    "lh_gemini_verify": (C.c_int, [_P, C.POINTER(lh_g1), C.POINTER(lh_fr), _SZ, C.POINTER(lh_fr),
+                                   C.POINTER(lh_transcript)]),
+    "lh_gemini_batch_verify": (C.c_int, [_P, _SZ, C.POINTER(lh_g1), _SZ, C.POINTER(lh_fr), _SZ,
+                                         C.POINTER(lh_evaluation), _SZ, C.POINTER(lh_transcript)]),
+    "lh_lasso_prove_gemini": (C.c_int, [_P, _P, _SZ, C.POINTER(lh_lasso_table), _SZ, C.POINTER(_P),
+                                        C.POINTER(lh_transcript)]),
+    "lh_lasso_verify_gemini": (C.c_int, [_P, C.POINTER(lh_lasso_table), _SZ, C.POINTER(lh_transcript)]),
+    "lh_hyperplonk_prove_gemini": (C.c_int, [_P, _P, _SZ, C.POINTER(lh_hp_param), C.POINTER(C.POINTER(lh_fr)),
+                                             C.POINTER(_P), C.POINTER(lh_transcript)]),
+    "lh_hyperplonk_verify_gemini": (C.c_int, [_P, C.POINTER(lh_hp_vparam), C.POINTER(C.POINTER(lh_fr)),
+                                              C.POINTER(lh_transcript)]),
+    "lh_hyperplonk_prove_phases_gemini": (C.c_int, [_P, _P, _SZ, C.POINTER(lh_hp_param), _SZ, C.POINTER(_SZ),
+                                                    C.POINTER(_SZ), C.POINTER(C.POINTER(lh_fr)),
+                                                    C.POINTER(lh_hp_circuit), C.POINTER(lh_transcript)]),
+    "lh_hyperplonk_verify_phases_gemini": (C.c_int, [_P, C.POINTER(lh_hp_vparam), _SZ, C.POINTER(_SZ), C.POINTER(_SZ),
+                                                     C.POINTER(C.POINTER(lh_fr)), C.POINTER(lh_transcript)]),
     "lh_debug_jit_source": (C.c_int, [C.POINTER(C.c_uint32), _SZ, C.c_uint32, C.c_uint32, C.c_int, C.c_char_p, _SZ,
                                       C.POINTER(_SZ)]),
     "lh_keccak_transcript_hash_io": (C.c_int, [C.POINTER(lh_transcript), C.POINTER(lh_hash_transcript)]),

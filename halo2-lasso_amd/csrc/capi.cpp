@@ -20,6 +20,9 @@ struct lh_usrs {
 struct lh_zm_vp {
   ZmVerifierParams* p;
 };
+struct lh_ukzg_vp {
+  UkzgVerifierParams* p;
+};
 struct lh_brakedown_param {
   BdParam p;
 };
@@ -1284,6 +1287,248 @@ lh_status lh_hyperplonk_verify_phases_zeromorph(const lh_zm_vp* vp, const lh_hp_
              Transcript& t2) { zeromorph_batch_verify(pcs, nv, comms, nc, points, np, evals, ne, t2); },
       *hvp, std::vector<size_t>(num_witness_polys, num_witness_polys + num_phases),
       std::vector<size_t>(num_challenges, num_challenges + num_phases), (const HFr* const*)instances, tr);
+  LH_CATCH
+}
+
+// ---------------------------------------------------------------- univariate KZG on its own, Gemini over it
+static std::vector<UPoly> upolys_of(const lh_fr* const* d_polys, const size_t* lens, size_t num_polys) {
+  std::vector<UPoly> polys(num_polys);
+  for (size_t i = 0; i < num_polys; i++) {
+    LH_REQUIRE(d_polys[i] != nullptr || lens[i] == 0, LH_ERR_ARG, "null argument: d_polys[i]");
+    polys[i] = UPoly{(const Fr*)d_polys[i], lens[i]};
+  }
+  return polys;
+}
+lh_status lh_ukzg_batch_commit(lh_ctx* ctx, const lh_usrs* srs, size_t poly_size, const lh_fr* const* d_polys,
+                               const size_t* lens, size_t num_polys, lh_g1* out_comms) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(srs);
+  NEED_N(d_polys, num_polys);
+  NEED_N(lens, num_polys);
+  NEED_N(out_comms, num_polys);
+  const std::vector<UPoly> polys = upolys_of(d_polys, lens, num_polys);
+  std::vector<HG1> c = ukzg_batch_commit(ctx->c, srs->s, poly_size, polys.data(), num_polys);
+  if (num_polys) memcpy(out_comms, c.data(), 64 * num_polys);
+  LH_CATCH
+}
+lh_status lh_ukzg_open(lh_ctx* ctx, const lh_usrs* srs, size_t poly_size, const lh_fr* d_poly, size_t len,
+                       const lh_fr* point, lh_transcript* t) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(srs);
+  NEED_N(d_poly, len);
+  NEED(point);
+  Transcript tr(t);
+  HFr x;
+  memcpy(&x, point, 32);
+  ukzg_open(ctx->c, srs->s, poly_size, UPoly{(const Fr*)d_poly, len}, x, tr);
+  LH_CATCH
+}
+lh_status lh_ukzg_batch_open(lh_ctx* ctx, const lh_usrs* srs, size_t poly_size, const lh_fr* const* d_polys,
+                             const size_t* lens, size_t num_polys, const lh_fr* points, size_t num_points,
+                             const lh_evaluation* evals, size_t num_evals, lh_transcript* t) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(srs);
+  NEED_N(d_polys, num_polys);
+  NEED_N(lens, num_polys);
+  NEED_N(points, num_points);
+  NEED_N(evals, num_evals);
+  Transcript tr(t);
+  const std::vector<UPoly> polys = upolys_of(d_polys, lens, num_polys);
+  ukzg_batch_open(ctx->c, srs->s, poly_size, polys.data(), num_polys, (const HFr*)points, num_points, evals, num_evals, tr);
+  LH_CATCH
+}
+lh_status lh_ukzg_vp_setup(const lh_fr* s, lh_ukzg_vp** out) {
+  LH_TRY
+  NEED(s);
+  NEED(out);
+  HFr sv;
+  memcpy(&sv, s, 32);
+  *out = new lh_ukzg_vp{ukzg_vp_setup(sv)};
+  LH_CATCH
+}
+lh_status lh_ukzg_vp_new(const lh_g1* g1, const lh_g2* g2, const lh_g2* s_g2, lh_ukzg_vp** out) {
+  LH_TRY
+  NEED(g1);
+  NEED(g2);
+  NEED(s_g2);
+  NEED(out);
+  *out = new lh_ukzg_vp{ukzg_vp_new(*g1, *g2, *s_g2)};
+  LH_CATCH
+}
+lh_status lh_ukzg_vp_export(const lh_ukzg_vp* vp, lh_g1* g1, lh_g2* g2, lh_g2* s_g2) {
+  LH_TRY
+  NEED(vp);
+  NEED(g1);
+  NEED(g2);
+  NEED(s_g2);
+  ukzg_vp_export(*vp->p, g1, g2, s_g2);
+  LH_CATCH
+}
+void lh_ukzg_vp_free(lh_ukzg_vp* vp) {
+  if (!vp) return;
+  ukzg_vp_free(vp->p);
+  delete vp;
+}
+lh_status lh_ukzg_verify(const lh_ukzg_vp* vp, const lh_g1* comm, const lh_fr* point, const lh_fr* eval, lh_transcript* t) {
+  LH_TRY
+  NEED(vp);
+  NEED(comm);
+  NEED(point);
+  NEED(eval);
+  Transcript tr(t);
+  HG1 c;
+  memcpy(&c, comm, sizeof(c));
+  HFr x, e;
+  memcpy(&x, point, 32);
+  memcpy(&e, eval, 32);
+  ukzg_verify(*vp->p, c, x, e, tr);
+  LH_CATCH
+}
+lh_status lh_ukzg_batch_verify(const lh_ukzg_vp* vp, const lh_g1* comms, size_t num_comms, const lh_fr* points,
+                               size_t num_points, const lh_evaluation* evals, size_t num_evals, lh_transcript* t) {
+  LH_TRY
+  NEED(vp);
+  NEED_N(comms, num_comms);
+  NEED_N(points, num_points);
+  NEED_N(evals, num_evals);
+  Transcript tr(t);
+  ukzg_batch_verify(*vp->p, (const HG1*)comms, num_comms, (const HFr*)points, num_points, evals, num_evals, tr);
+  LH_CATCH
+}
+lh_status lh_gemini_batch_commit(lh_ctx* ctx, const lh_usrs* srs, size_t poly_size, const lh_fr* const* d_polys,
+                                 size_t num_polys, size_t num_vars, lh_g1* out_comms) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(srs);
+  NEED_N(d_polys, num_polys);
+  NEED_N(out_comms, num_polys);
+  for (size_t i = 0; i < num_polys; i++) NEED(d_polys[i]);
+  std::vector<HG1> c = gemini_batch_commit(ctx->c, srs->s, poly_size, (const Fr* const*)d_polys, num_polys, num_vars);
+  if (num_polys) memcpy(out_comms, c.data(), 64 * num_polys);
+  LH_CATCH
+}
+lh_status lh_gemini_open(lh_ctx* ctx, const lh_usrs* srs, size_t poly_size, const lh_fr* d_poly, size_t num_vars,
+                         const lh_fr* point, lh_transcript* t) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(srs);
+  NEED(d_poly);
+  NEED_N(point, num_vars);
+  Transcript tr(t);
+  gemini_open(ctx->c, srs->s, poly_size, (const Fr*)d_poly, num_vars, (const HFr*)point, tr);
+  LH_CATCH
+}
+lh_status lh_gemini_batch_open(lh_ctx* ctx, const lh_usrs* srs, size_t poly_size, size_t num_vars,
+                               const lh_fr* const* d_polys, size_t num_polys, const lh_fr* points, size_t num_points,
+                               const lh_evaluation* evals, size_t num_evals, lh_transcript* t) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(srs);
+  NEED_N(d_polys, num_polys);
+  NEED_N(points, num_points);
+  NEED_N(evals, num_evals);
+  Transcript tr(t);
+  gemini_batch_open(ctx->c, srs->s, poly_size, num_vars, (const Fr* const*)d_polys, num_polys, (const HFr*)points,
+                    num_points, evals, num_evals, tr);
+  LH_CATCH
+}
+lh_status lh_gemini_folds(lh_ctx* ctx, const lh_fr* d_poly, size_t num_vars, const lh_fr* point, lh_fr* d_out) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(d_poly);
+  NEED_N(point, num_vars);
+  NEED_N(d_out, num_vars > 1);
+  gemini_folds(ctx->c, (const Fr*)d_poly, num_vars, (const HFr*)point, (Fr*)d_out);
+  ctx->c.sync();
+  LH_CATCH
+}
+lh_status lh_gemini_verify(const lh_ukzg_vp* vp, const lh_g1* comm, const lh_fr* point, size_t num_vars,
+                           const lh_fr* eval, lh_transcript* t) {
+  LH_TRY
+  NEED(vp);
+  NEED(comm);
+  NEED(eval);
+  NEED_N(point, num_vars);
+  Transcript tr(t);
+  HG1 c;
+  memcpy(&c, comm, sizeof(c));
+  HFr e;
+  memcpy(&e, eval, 32);
+  gemini_verify(*vp->p, c, (const HFr*)point, num_vars, e, tr);
+  LH_CATCH
+}
+lh_status lh_gemini_batch_verify(const lh_ukzg_vp* vp, size_t num_vars, const lh_g1* comms, size_t num_comms,
+                                 const lh_fr* points, size_t num_points, const lh_evaluation* evals, size_t num_evals,
+                                 lh_transcript* t) {
+  LH_TRY
+  NEED(vp);
+  NEED_N(comms, num_comms);
+  NEED_N(points, num_points);
+  NEED_N(evals, num_evals);
+  Transcript tr(t);
+  gemini_batch_verify(*vp->p, num_vars, (const HG1*)comms, num_comms, (const HFr*)points, num_points, evals, num_evals, tr);
+  LH_CATCH
+}
+static PcsBatchVerify gemini_verifier(const UkzgVerifierParams& pcs) {
+  return [&pcs](size_t nv, const HG1* comms, size_t nc, const HFr* points, size_t np, const lh_evaluation* evals, size_t ne,
+                Transcript& t2) { gemini_batch_verify(pcs, nv, comms, nc, points, np, evals, ne, t2); };
+}
+lh_status lh_lasso_prove_gemini(lh_ctx* ctx, const lh_usrs* srs, size_t poly_size, const lh_lasso_table* table,
+                                size_t num_vars, const uint32_t* const* d_dims, lh_transcript* t) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(srs);
+  NEED(table);
+  NEED(d_dims);
+  Transcript tr(t);
+  lasso_prove(ctx->c, gemini_pcs(ctx->c, srs->s, poly_size), *table, num_vars, d_dims, tr);
+  LH_CATCH
+}
+lh_status lh_lasso_verify_gemini(const lh_ukzg_vp* vp, const lh_lasso_table* table, size_t num_vars, lh_transcript* t) {
+  LH_TRY
+  NEED(vp);
+  NEED(table);
+  Transcript tr(t);
+  lasso_verify(gemini_verifier(*vp->p), *table, num_vars, tr);
+  LH_CATCH
+}
+lh_status lh_hyperplonk_prove_gemini(lh_ctx* ctx, const lh_usrs* srs, size_t poly_size, const lh_hp_param* pp,
+                                     const lh_fr* const* instances, const lh_fr* const* d_witness_polys, lh_transcript* t) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(srs);
+  NEED(pp);
+  NEED_N(d_witness_polys, pp->num_witness_polys);
+  Transcript tr(t);
+  hyperplonk_prove(ctx->c, gemini_pcs(ctx->c, srs->s, poly_size), *pp, (const HFr* const*)instances,
+                   (const Fr* const*)d_witness_polys, tr);
+  LH_CATCH
+}
+lh_status lh_hyperplonk_verify_gemini(const lh_ukzg_vp* vp, const lh_hp_vparam* hvp, const lh_fr* const* instances,
+                                      lh_transcript* t) {
+  LH_TRY
+  NEED(vp);
+  NEED(hvp);
+  Transcript tr(t);
+  hyperplonk_verify(gemini_verifier(*vp->p), *hvp, (const HFr* const*)instances, tr);
+  LH_CATCH
+}
+lh_status lh_hyperplonk_prove_phases_gemini(lh_ctx* ctx, const lh_usrs* srs, size_t poly_size, const lh_hp_param* pp,
+                                            size_t num_phases, const size_t* num_witness_polys, const size_t* num_challenges,
+                                            const lh_fr* const* instances, const lh_hp_circuit* circuit, lh_transcript* t) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(srs);
+  NEED(pp);
+  NEED(circuit);
+  Transcript tr(t);
+  const HpPhases ph = hp_phases_of(pp, num_phases, num_witness_polys, num_challenges, circuit);
+  hyperplonk_prove_phases(ctx->c, gemini_pcs(ctx->c, srs->s, poly_size), *pp, ph, (const HFr* const*)instances, tr);
+  LH_CATCH
+}
+lh_status lh_hyperplonk_verify_phases_gemini(const lh_ukzg_vp* vp, const lh_hp_vparam* hvp, size_t num_phases,
+                                             const size_t* num_witness_polys, const size_t* num_challenges,
+                                             const lh_fr* const* instances, lh_transcript* t) {
+  LH_TRY
+  NEED(vp);
+  NEED(hvp);
+  LH_REQUIRE(num_phases == 0 || (num_witness_polys && num_challenges), LH_ERR_ARG, "null argument: phases");
+  Transcript tr(t);
+  hyperplonk_verify_phases(gemini_verifier(*vp->p), *hvp, std::vector<size_t>(num_witness_polys, num_witness_polys + num_phases),
+                           std::vector<size_t>(num_challenges, num_challenges + num_phases), (const HFr* const*)instances, tr);
   LH_CATCH
 }
 

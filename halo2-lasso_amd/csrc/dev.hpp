@@ -793,6 +793,38 @@ void k_zm_combine(Ctx&, const Fr* poly, const Fr* q_hat, const Fr* q, size_t num
 // out[i] = sum_{j >= i} f_j x^(j - i): out[1..] is the quotient of f by (X - x), out[0] = f(x)
 void k_suffix_horner(Ctx&, const Fr* f, size_t n, const Fr& x, Fr* out);
 
+// ------------------------------------------------------------------ Gemini / batched univariate KZG (kernels_gemini.hip)
+constexpr int GM_MAX_VARS = 32;
+constexpr size_t GM_TAIL_IN = 1024;   // folds of at most this many input coefficients run inside one workgroup's LDS
+constexpr size_t GM_CHUNK = 64;       // positions per thread of the batched suffix Horner
+constexpr uint32_t GM_MAX_STRIDE = 2;
+// folds[off_i ..] = fs[i], i = 1 .. num_vars - 1 (2^(num_vars - i) coefficients; off_1 = 0, off_{i+1} = off_i + 2^(num_vars - i)):
+// fs[i][j] = fs[i-1][2j] + xs[i-1] (fs[i-1][2j+1] - fs[i-1][2j]), fs[0] = poly; xs: host array of num_vars - 1 elements
+void k_gm_fold_chain(Ctx&, const Fr* poly, size_t num_vars, const Fr* xs, Fr* folds);
+struct GmEvalSeg {
+  const Fr* f;
+  size_t len;  // even
+  Fr x2;
+};
+// out (host) [2 s], [2 s + 1] = sum_j f_s[2j] x2_s^j, sum_j f_s[2j+1] x2_s^j; synchronises
+void k_gm_eval_even_odd(Ctx&, const GmEvalSeg* segs, size_t count, Fr* out);
+struct GmHornerSeg {
+  const Fr* f;
+  Fr* out;  // len entries, may not alias f
+  size_t len;
+  uint32_t stride;  // 1 or 2
+  Fr x;
+};
+// out[i] = f[i] + x out[i + stride] (zero beyond len): out[stride..] = the quotient of f by X^stride - x, out[..stride] the remainder
+void k_gm_suffix_horner(Ctx&, const GmHornerSeg* segs, size_t count);
+struct GmTerm {
+  const Fr* p;
+  size_t len;
+  Fr w;
+};
+// out[j] = sum_{k : j < len_k} w_k p_k[j], j < n (out aliases no term)
+void k_gm_combine(Ctx&, const GmTerm* terms, size_t count, size_t n, Fr* out);
+
 // ------------------------------------------------------------------ radix sort (sort.hip)
 // stable sort of (u32 key, u32 value) pairs by the low `bits` bits of the key; inputs are preserved
 struct SortSlab {

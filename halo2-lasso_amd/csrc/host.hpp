@@ -359,6 +359,54 @@ void zeromorph_batch_verify(const ZmVerifierParams&, size_t num_vars, const HG1*
                             const HFr* points, size_t num_points, const lh_evaluation* evals, size_t num_evals,
                             Transcript& tr);
 
+// ------------------------------------------------------------------ pcs::univariate::kzg on its own, pcs::multilinear::gemini over it
+// (gemini.cpp; verifiers in verifier.cpp).  `poly_size` is the trim size (univariate/kzg.rs:220-240): pp = powers[..poly_size].
+// A univariate poly is a coefficient vector of FIXED length on the device: the reference drops leading zero coefficients,
+// which changes no commitment (a zero scalar contributes the identity), and checks degrees after dropping them; here the
+// length itself must fit the param.
+struct UPoly {
+  const Fr* d;
+  size_t len;
+};
+std::vector<HG1> ukzg_batch_commit(Ctx&, const USrs&, size_t poly_size, const UPoly* polys, size_t num_polys);
+void ukzg_open(Ctx&, const USrs&, size_t poly_size, const UPoly& poly, const HFr& point, Transcript& tr);
+void ukzg_batch_open(Ctx&, const USrs&, size_t poly_size, const UPoly* polys, size_t num_polys, const HFr* points,
+                     size_t num_points, const lh_evaluation* evals, size_t num_evals, Transcript& tr);
+// univariate/kzg.rs:422-555, shared by prover and verifier (host only)
+struct UkzgEvalSet {
+  std::vector<size_t> polys, points, diffs;
+  std::vector<std::vector<HFr>> evals;  // per poly, in the order of `points`
+};
+struct UkzgEvalSets {
+  std::vector<UkzgEvalSet> sets;
+  std::vector<size_t> superset;  // ascending
+};
+UkzgEvalSets ukzg_eval_sets(const lh_evaluation* evals, size_t num_evals);
+HFr ukzg_vanishing_eval(const std::vector<size_t>& idx, const HFr* points, const HFr& z);
+// -> (normalized set scalars, normalizer)
+std::pair<std::vector<HFr>, HFr> ukzg_set_scalars(const std::vector<UkzgEvalSet>& sets, const std::vector<HFr>& powers_of_gamma,
+                                                  const HFr* points, const HFr& z);
+std::vector<HG1> gemini_batch_commit(Ctx&, const USrs&, size_t poly_size, const Fr* const* d_polys, size_t num_polys,
+                                     size_t num_vars);
+void gemini_open(Ctx&, const USrs&, size_t poly_size, const Fr* d_poly, size_t num_vars, const HFr* point, Transcript& tr);
+void gemini_batch_open(Ctx&, const USrs&, size_t poly_size, size_t num_vars, const Fr* const* d_polys, size_t num_polys,
+                       const HFr* points, size_t num_points, const lh_evaluation* evals, size_t num_evals, Transcript& tr,
+                       const SmallPoly* small = nullptr);
+// development / tests: the folds fs[1..] of a Gemini opening in their arena layout (2^num_vars - 2 coefficients)
+void gemini_folds(Ctx&, const Fr* d_poly, size_t num_vars, const HFr* point, Fr* d_out);
+struct UkzgVerifierParams;  // UnivariateKzgVerifierParam (univariate/kzg.rs:90-120): g1, g2, [s]_2
+UkzgVerifierParams* ukzg_vp_setup(const HFr& s);
+UkzgVerifierParams* ukzg_vp_new(const lh_g1& g1, const lh_g2& g2, const lh_g2& s_g2);
+void ukzg_vp_export(const UkzgVerifierParams&, lh_g1* g1, lh_g2* g2, lh_g2* s_g2);
+void ukzg_vp_free(UkzgVerifierParams*);
+void ukzg_verify(const UkzgVerifierParams&, const HG1& comm, const HFr& point, const HFr& eval, Transcript& tr);
+void ukzg_batch_verify(const UkzgVerifierParams&, const HG1* comms, size_t num_comms, const HFr* points, size_t num_points,
+                       const lh_evaluation* evals, size_t num_evals, Transcript& tr);
+void gemini_verify(const UkzgVerifierParams&, const HG1& comm, const HFr* point, size_t num_vars, const HFr& eval,
+                   Transcript& tr);
+void gemini_batch_verify(const UkzgVerifierParams&, size_t num_vars, const HG1* comms, size_t num_comms, const HFr* points,
+                         size_t num_points, const lh_evaluation* evals, size_t num_evals, Transcript& tr);
+
 // what the provers (Lasso, HyperPlonk and its Lasso lookups) need from their PCS: the PolynomialCommitmentScheme the
 // backend is generic over (backend/hyperplonk.rs:76-95), plus the bases themselves for the small-valued Lasso columns
 struct Pcs {
@@ -381,6 +429,7 @@ struct Pcs {
 };
 Pcs mkzg_pcs(Ctx&, const Srs&);                            // mkzg.cpp
 Pcs zeromorph_pcs(Ctx&, const USrs&, size_t poly_size);    // zeromorph.cpp
+Pcs gemini_pcs(Ctx&, const USrs&, size_t poly_size);       // gemini.cpp
 
 // ------------------------------------------------------------------ Lasso
 // pieces of the argument shared by the standalone prover (lasso.cpp) and HyperPlonk's Lasso lookups (hyperplonk.cpp)

@@ -6,6 +6,8 @@
 //                                          piop/sum_check.rs:60-125, poly/multilinear.rs:433-475
 //   Lasso verify                           oracle/pyref/lasso.py (the build's own protocol; no reference code)
 //   MultilinearBrakedown::verify           pcs/multilinear/brakedown.rs:315-396 (two rows re-encoded on the host)
+//   UnivariateKzg / Gemini verify          pcs/univariate/kzg.rs:366-555, pcs/multilinear/gemini.rs:165-211
+#include <algorithm>
 #include <map>
 #include <set>
 #include <string>
@@ -220,6 +222,203 @@ void zeromorph_batch_verify(const ZmVerifierParams& vp, size_t num_vars, const H
                             Transcript& tr) {
   additive_batch_verify(num_vars, comms, num_comms, points, num_points, evals, num_evals, tr,
                         [&](const HG1& comm, const HFr* x, const HFr& eval) { zeromorph_verify(vp, comm, x, num_vars, eval, tr); });
+}
+
+// ------------------------------------------------------------------ UnivariateKzg::{verify, batch_verify} (univariate/kzg.rs:366-555)
+struct UkzgVerifierParams {
+  HG1 g1;
+  G2Affine g2, s_g2;
+};
+UkzgVerifierParams* ukzg_vp_setup(const HFr& s) {
+  auto* vp = new UkzgVerifierParams();
+  vp->g1 = HG1{host::Fq::from_u64(1), host::Fq::from_u64(2)};
+  vp->g2 = host::g2_generator();
+  vp->s_g2 = host::g2_to_affine(host::g2_mul(host::g2_from_affine(vp->g2), s));
+  return vp;
+}
+UkzgVerifierParams* ukzg_vp_new(const lh_g1& g1, const lh_g2& g2, const lh_g2& s_g2) {
+  auto* vp = new UkzgVerifierParams();
+  memcpy(&vp->g1, &g1, sizeof(HG1));
+  vp->g2 = g2_from_c(g2), vp->s_g2 = g2_from_c(s_g2);
+  if (!host::g2_is_on_curve(vp->g2) || !host::g2_is_on_curve(vp->s_g2)) {
+    delete vp;
+    throw Error(LH_ERR_SERIALIZATION, "verifier params: G2 point not on the curve");
+  }
+  return vp;
+}
+void ukzg_vp_export(const UkzgVerifierParams& vp, lh_g1* g1, lh_g2* g2, lh_g2* s_g2) {
+  if (g1) memcpy(g1, &vp.g1, sizeof(HG1));
+  if (g2) *g2 = g2_to_c(vp.g2);
+  if (s_g2) *s_g2 = g2_to_c(vp.s_g2);
+}
+void ukzg_vp_free(UkzgVerifierParams* vp) { delete vp; }
+
+// kzg.rs:366-378: c = pi * point + comm - g1 * eval;  e(c, -g2) e(pi, [s]_2) == 1
+void ukzg_verify(const UkzgVerifierParams& vp, const HG1& comm, const HFr& point, const HFr& eval, Transcript& tr) {
+  const HG1 pi = tr.read_commitment();
+  host::G1Xyzz c = host::g1_mul(host::g1_from_affine(pi), point);
+  c = host::g1_add(c, host::g1_from_affine(comm));
+  c = host::g1_add(c, host::g1_mul(host::g1_from_affine(HG1{vp.g1.x, -vp.g1.y}), eval));
+  if (!host::pairings_product_is_identity({{host::g1_to_affine(c), host::g2_neg(vp.g2)}, {pi, vp.s_g2}}))
+    throw Error(LH_ERR_INVALID_PCS_OPEN, "Invalid univariate KZG open");
+}
+
+// kzg.rs:454-512: polys grouped by their point set (as a set), in order of first appearance
+UkzgEvalSets ukzg_eval_sets(const lh_evaluation* evals, size_t num_evals) {
+  struct Shift {
+    size_t poly;
+    std::vector<size_t> points;
+    std::vector<HFr> values;
+  };
+  std::vector<Shift> shifts;
+  std::set<size_t> superset;
+  for (size_t i = 0; i < num_evals; i++) {
+    const size_t poly = evals[i].poly, point = evals[i].point;
+    HFr v;
+    memcpy(&v, &evals[i].value, 32);
+    size_t pos = 0;
+    while (pos < shifts.size() && shifts[pos].poly != poly) pos++;
+    if (pos == shifts.size()) {
+      shifts.push_back(Shift{poly, {point}, {v}});
+    } else if (std::find(shifts[pos].points.begin(), shifts[pos].points.end(), point) == shifts[pos].points.end()) {
+      shifts[pos].points.push_back(point);
+      shifts[pos].values.push_back(v);
+    }
+    superset.insert(point);
+  }
+  UkzgEvalSets out;
+  out.superset.assign(superset.begin(), superset.end());
+  for (const Shift& sh : shifts) {
+    const std::set<size_t> key(sh.points.begin(), sh.points.end());
+    size_t pos = 0;
+    while (pos < out.sets.size() && std::set<size_t>(out.sets[pos].points.begin(), out.sets[pos].points.end()) != key) pos++;
+    if (pos == out.sets.size()) {
+      UkzgEvalSet st;
+      st.polys = {sh.poly}, st.points = sh.points, st.evals = {sh.values};
+      for (size_t idx : out.superset)
+        if (!key.count(idx)) st.diffs.push_back(idx);
+      out.sets.push_back(std::move(st));
+    } else {
+      UkzgEvalSet& st = out.sets[pos];
+      if (std::find(st.polys.begin(), st.polys.end(), sh.poly) != st.polys.end()) continue;
+      st.polys.push_back(sh.poly);
+      std::vector<HFr> ev;
+      for (size_t lhs : st.points) ev.push_back(sh.values[std::find(sh.points.begin(), sh.points.end(), lhs) - sh.points.begin()]);
+      st.evals.push_back(std::move(ev));
+    }
+  }
+  return out;
+}
+HFr ukzg_vanishing_eval(const std::vector<size_t>& idx, const HFr* points, const HFr& z) {
+  HFr acc = HFr::one();
+  for (size_t i : idx) acc *= z - points[i];
+  return acc;
+}
+// kzg.rs:514-533: normalised by the first set's scalar (fflonk), one when that is zero
+std::pair<std::vector<HFr>, HFr> ukzg_set_scalars(const std::vector<UkzgEvalSet>& sets, const std::vector<HFr>& powers_of_gamma,
+                                                  const HFr* points, const HFr& z) {
+  std::vector<HFr> vde(sets.size());
+  for (size_t s = 0; s < sets.size(); s++) vde[s] = ukzg_vanishing_eval(sets[s].diffs, points, z);
+  const HFr normalizer = vde[0].is_zero() ? HFr::one() : vde[0].inv();
+  std::vector<HFr> out(sets.size());
+  for (size_t s = 0; s < sets.size(); s++) out[s] = normalizer * vde[s] * powers_of_gamma[s];
+  return {out, normalizer};
+}
+// arithmetic.rs:108-136
+static std::vector<HFr> barycentric_weights(const std::vector<HFr>& points) {
+  std::vector<HFr> w(points.size());
+  for (size_t j = 0; j < points.size(); j++) {
+    HFr acc = HFr::one();
+    for (size_t i = 0; i < points.size(); i++)
+      if (i != j) acc *= points[j] - points[i];
+    w[j] = acc.inv();
+  }
+  return w;
+}
+static HFr barycentric_interpolate(const std::vector<HFr>& weights, const std::vector<HFr>& points, const std::vector<HFr>& evals,
+                                   const HFr& x) {
+  HFr sum = HFr::zero(), acc = HFr::zero();
+  for (size_t i = 0; i < points.size(); i++) {
+    const HFr coeff = (x - points[i]).inv() * weights[i];
+    sum += coeff;
+    acc += coeff * evals[i];
+  }
+  LH_REQUIRE(!sum.is_zero(), LH_ERR_INVALID_PCS_OPEN, "Invalid univariate KZG open");  // (the reference unwraps the inverse)
+  return acc * sum.inv();
+}
+
+void ukzg_batch_verify(const UkzgVerifierParams& vp, const HG1* comms, size_t num_comms, const HFr* points, size_t num_points,
+                       const lh_evaluation* evals, size_t num_evals, Transcript& tr) {
+  LH_REQUIRE(num_evals >= 1, LH_ERR_ARG, "univariate batch verify: no evaluations");
+  for (size_t i = 0; i < num_evals; i++)
+    LH_REQUIRE(evals[i].poly < num_comms && evals[i].point < num_points, LH_ERR_ARG, "univariate batch verify: bad evaluation");
+  const UkzgEvalSets es = ukzg_eval_sets(evals, num_evals);
+  const std::vector<UkzgEvalSet>& sets = es.sets;
+  const HFr beta = tr.squeeze_challenge(), gamma = tr.squeeze_challenge();
+  const HG1 q_comm = tr.read_commitment();
+  const HFr z = tr.squeeze_challenge();
+  size_t max_set_len = 0;
+  for (auto& s : sets) max_set_len = std::max(max_set_len, s.polys.size());
+  std::vector<HFr> pob(max_set_len), pog(sets.size());
+  pob[0] = HFr::one();
+  for (size_t i = 1; i < max_set_len; i++) pob[i] = pob[i - 1] * beta;
+  pog[0] = HFr::one();
+  for (size_t i = 1; i < sets.size(); i++) pog[i] = pog[i - 1] * gamma;
+  auto sc = ukzg_set_scalars(sets, pog, points, z);
+  std::vector<HFr> scalars(num_comms, HFr::zero());  // comm_scalars (kzg.rs:541-555)
+  for (size_t s = 0; s < sets.size(); s++)
+    for (size_t k = 0; k < sets[s].polys.size(); k++) scalars[sets[s].polys[k]] = sc.first[s] * pob[k];
+  const HFr q_scalar = -(ukzg_vanishing_eval(es.superset, points, z) * sc.second);
+  host::G1Xyzz f = host::g1_mul(host::g1_from_affine(q_comm), q_scalar);
+  for (size_t i = 0; i < num_comms; i++)
+    if (!scalars[i].is_zero()) f = host::g1_add(f, host::g1_mul(host::g1_from_affine(comms[i]), scalars[i]));
+  HFr eval = HFr::zero();
+  for (size_t s = 0; s < sets.size(); s++) {  // r_eval (kzg.rs:442-451)
+    std::vector<HFr> pts;
+    for (size_t i : sets[s].points) pts.push_back(points[i]);
+    const std::vector<HFr> w = barycentric_weights(pts);
+    HFr r = HFr::zero();
+    for (size_t k = 0; k < sets[s].evals.size(); k++) r += pob[k] * barycentric_interpolate(w, pts, sets[s].evals[k], z);
+    eval += sc.first[s] * r;
+  }
+  ukzg_verify(vp, host::g1_to_affine(f), z, eval, tr);
+}
+
+// ------------------------------------------------------------------ Gemini::{verify, batch_verify} (gemini.rs:165-211)
+void gemini_verify(const UkzgVerifierParams& vp, const HG1& comm, const HFr* point, size_t num_vars, const HFr& eval,
+                   Transcript& tr) {
+  LH_REQUIRE(num_vars >= 1 && num_vars < 64, LH_ERR_ARG, "gemini verify: bad num_vars");
+  std::vector<HG1> comms{comm};
+  for (const HG1& p : tr.read_commitments(num_vars - 1)) comms.push_back(p);
+  const HFr beta = tr.squeeze_challenge();
+  std::vector<HFr> sq(num_vars);
+  sq[0] = beta;
+  for (size_t i = 1; i < num_vars; i++) sq[i] = sq[i - 1].sqr();
+  const std::vector<HFr> evs = tr.read_field_elements(num_vars);
+  const HFr one = HFr::one();
+  HFr eval_0 = eval;
+  for (size_t i = num_vars; i-- > 0;) {
+    const HFr den = (one - point[i]) * sq[i] + point[i];
+    LH_REQUIRE(!den.is_zero(), LH_ERR_INVALID_PCS_OPEN, "Invalid univariate KZG open");  // (the reference unwraps the inverse)
+    eval_0 = (sq[i].dbl() * eval_0 - ((one - point[i]) * sq[i] - point[i]) * evs[i]) * den.inv();
+  }
+  std::vector<lh_evaluation> evals(num_vars + 1);
+  auto set_eval = [&](size_t k, size_t poly, size_t pt, const HFr& v) {
+    evals[k].poly = (uint32_t)poly, evals[k].point = (uint32_t)pt;
+    memcpy(&evals[k].value, &v, 32);
+  };
+  set_eval(0, 0, 0, eval_0);
+  set_eval(1, 0, 1, evs[0]);
+  for (size_t i = 1; i < num_vars; i++) set_eval(i + 1, i, i + 1, evs[i]);
+  std::vector<HFr> points(num_vars + 1);
+  points[0] = beta;
+  for (size_t i = 0; i < num_vars; i++) points[i + 1] = -sq[i];
+  ukzg_batch_verify(vp, comms.data(), comms.size(), points.data(), points.size(), evals.data(), evals.size(), tr);
+}
+void gemini_batch_verify(const UkzgVerifierParams& vp, size_t num_vars, const HG1* comms, size_t num_comms, const HFr* points,
+                         size_t num_points, const lh_evaluation* evals, size_t num_evals, Transcript& tr) {
+  additive_batch_verify(num_vars, comms, num_comms, points, num_points, evals, num_evals, tr,
+                        [&](const HG1& comm, const HFr* x, const HFr& eval) { gemini_verify(vp, comm, x, num_vars, eval, tr); });
 }
 
 // ------------------------------------------------------------------ expressions on the host

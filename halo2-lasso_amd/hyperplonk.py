@@ -129,8 +129,10 @@ class HyperPlonkProverParam:
 
 
 def _pcs_of(pcs_pp):
-    """the PolynomialCommitmentScheme a param belongs to: MultilinearKzg or Zeromorph (backend/hyperplonk.rs:76-95)"""
-    from . import MultilinearKzg, Zeromorph, ZeromorphProverParam
+    """the PolynomialCommitmentScheme a param belongs to: MultilinearKzg, Zeromorph or Gemini (backend/hyperplonk.rs:76-95)"""
+    from . import MultilinearKzg, Zeromorph, ZeromorphProverParam, Gemini, GeminiProverParam
+    if isinstance(pcs_pp, GeminiProverParam):
+        return Gemini
     return Zeromorph if isinstance(pcs_pp, ZeromorphProverParam) else MultilinearKzg
 
 
@@ -237,7 +239,10 @@ class HyperPlonk:
         prm.num_lasso_lookups, prm.lasso_lookups = len(info.lasso_lookups), lasso_arr
         inst_arrays = [_fr_array(i) for i in instances]
         inst = (C.POINTER(lh_fr) * max(len(instances), 1))(*[C.cast(a, C.POINTER(lh_fr)) for a in inst_arrays])
-        from . import ZeromorphProverParam
+        from . import ZeromorphProverParam, GeminiProverParam
+        lib = ctx.lib
+        univariate = isinstance(pp.pcs, (ZeromorphProverParam, GeminiProverParam))  # PCS over the univariate SRS + trim size
+        gemini = isinstance(pp.pcs, GeminiProverParam)
         if multi:
             from . import fr_from_bytes
             alive, failure = [], []
@@ -260,9 +265,9 @@ class HyperPlonk:
             nph = len(info.num_witness_polys)
             nw = (C.c_size_t * max(nph, 1))(*info.num_witness_polys)
             nc = (C.c_size_t * max(nph, 1))(*info.num_challenges)
-            if isinstance(pp.pcs, ZeromorphProverParam):
-                rc = ctx.lib.lh_hyperplonk_prove_phases_zeromorph(ctx.h, pp.pcs.params.h, pp.pcs.poly_size, C.byref(prm), nph,
-                                                                  nw, nc, inst, C.byref(circ), transcript.p)
+            if univariate:
+                fn = lib.lh_hyperplonk_prove_phases_gemini if gemini else lib.lh_hyperplonk_prove_phases_zeromorph
+                rc = fn(ctx.h, pp.pcs.params.h, pp.pcs.poly_size, C.byref(prm), nph, nw, nc, inst, C.byref(circ), transcript.p)
             else:
                 rc = ctx.lib.lh_hyperplonk_prove_phases(ctx.h, pp.pcs.h, C.byref(prm), nph, nw, nc, inst, C.byref(circ),
                                                         transcript.p)
@@ -272,13 +277,13 @@ class HyperPlonk:
             return
         wit = _ptr_array(witness_polys)
         if sharded:
-            if isinstance(pp.pcs, ZeromorphProverParam):
+            if univariate:
                 raise NotImplementedError("the sharded prove is wired for multilinear KZG")
             _check(ctx.lib.lh_hyperplonk_prove_sharded(ctx.h, pp.pcs.h, C.byref(prm), inst, wit, transcript.p))
             return
-        if isinstance(pp.pcs, ZeromorphProverParam):
-            _check(ctx.lib.lh_hyperplonk_prove_zeromorph(ctx.h, pp.pcs.params.h, pp.pcs.poly_size, C.byref(prm), inst, wit,
-                                                         transcript.p))
+        if univariate:
+            fn = lib.lh_hyperplonk_prove_gemini if gemini else lib.lh_hyperplonk_prove_zeromorph
+            _check(fn(ctx.h, pp.pcs.params.h, pp.pcs.poly_size, C.byref(prm), inst, wit, transcript.p))
         else:
             _check(ctx.lib.lh_hyperplonk_prove(ctx.h, pp.pcs.h, C.byref(prm), inst, wit, transcript.p))
 
@@ -305,17 +310,17 @@ class HyperPlonk:
         prm.num_permutation_polys, prm.permutation_comms = len(vp.permutation_comms), perm
         inst_arrays = [_fr_array(i) for i in instances]
         inst = (C.POINTER(lh_fr) * max(len(instances), 1))(*[C.cast(a, C.POINTER(lh_fr)) for a in inst_arrays])
-        from . import ZeromorphVerifierParam
+        from . import ZeromorphVerifierParam, GeminiVerifierParam
+        suffix = "_zeromorph" if isinstance(vp.pcs, ZeromorphVerifierParam) else \
+            "_gemini" if isinstance(vp.pcs, GeminiVerifierParam) else ""
         if len(info.num_witness_polys) != 1:
             nph = len(info.num_witness_polys)
             nw = (C.c_size_t * max(nph, 1))(*info.num_witness_polys)
             nc = (C.c_size_t * max(nph, 1))(*info.num_challenges)
-            fn = vp.pcs.lib.lh_hyperplonk_verify_phases_zeromorph if isinstance(vp.pcs, ZeromorphVerifierParam) \
-                else vp.pcs.lib.lh_hyperplonk_verify_phases
+            fn = getattr(vp.pcs.lib, "lh_hyperplonk_verify_phases" + suffix)
             _check(fn(vp.pcs.h, C.byref(prm), nph, nw, nc, inst, transcript.p))
             return
-        fn = vp.pcs.lib.lh_hyperplonk_verify_zeromorph if isinstance(vp.pcs, ZeromorphVerifierParam) \
-            else vp.pcs.lib.lh_hyperplonk_verify
+        fn = getattr(vp.pcs.lib, "lh_hyperplonk_verify" + suffix)
         _check(fn(vp.pcs.h, C.byref(prm), inst, transcript.p))
 
 

@@ -577,6 +577,68 @@ lh_status lh_hyperplonk_verify_phases_zeromorph(const lh_zm_vp*, const lh_hp_vpa
                                                 const size_t* num_witness_polys, const size_t* num_challenges,
                                                 const lh_fr* const* instances, lh_transcript* t);
 
+/* ---------------------------------------------------------------- f3b: univariate KZG on its own, Gemini over it
+ * PolynomialCommitmentScheme for UnivariateKzg<Bn256> (pcs/univariate/kzg.rs:161-555, with the SHPLONK-style batched
+ * opening of several polys at several points) and for Gemini<UnivariateKzg<Bn256>> (pcs/multilinear/gemini.rs:29-211) over
+ * the same lh_usrs.  `poly_size` is the trim size (kzg.rs:220-240): pp = powers[..poly_size].  A univariate poly is a
+ * coefficient vector of `len` field elements on the device; the reference drops leading zero coefficients before it checks
+ * a degree, here `len` itself must be <= poly_size (LH_ERR_INVALID_PCS_PARAM "Too large degree of poly to commit|open").
+ * A commitment that is the identity cannot cross a transcript (util/transcript.rs:172-179): LH_ERR_TRANSCRIPT, as there. */
+/* UnivariateKzg::batch_commit (kzg.rs:254-262) */
+lh_status lh_ukzg_batch_commit(lh_ctx*, const lh_usrs*, size_t poly_size, const lh_fr* const* d_polys, const size_t* lens,
+                               size_t num_polys, lh_g1* out_comms);
+/* UnivariateKzg::open (kzg.rs:264-299): writes the commitment of poly div (X - point) */
+lh_status lh_ukzg_open(lh_ctx*, const lh_usrs*, size_t poly_size, const lh_fr* d_poly, size_t len, const lh_fr* point,
+                       lh_transcript* t);
+/* UnivariateKzg::batch_open (kzg.rs:301-354): points are field elements, evals (poly, point, value) triples */
+lh_status lh_ukzg_batch_open(lh_ctx*, const lh_usrs*, size_t poly_size, const lh_fr* const* d_polys, const size_t* lens,
+                             size_t num_polys, const lh_fr* points, size_t num_points, const lh_evaluation* evals,
+                             size_t num_evals, lh_transcript* t);
+/* verifier half (host only): UnivariateKzgVerifierParam = (g1, g2, [s]_2) (kzg.rs:90-120) */
+typedef struct lh_ukzg_vp lh_ukzg_vp;
+lh_status lh_ukzg_vp_setup(const lh_fr* s, lh_ukzg_vp** out);
+lh_status lh_ukzg_vp_new(const lh_g1* g1, const lh_g2* g2, const lh_g2* s_g2, lh_ukzg_vp** out);
+lh_status lh_ukzg_vp_export(const lh_ukzg_vp*, lh_g1* g1, lh_g2* g2, lh_g2* s_g2);
+void lh_ukzg_vp_free(lh_ukzg_vp*);
+/* UnivariateKzg::verify (kzg.rs:366-378): LH_ERR_INVALID_PCS_OPEN "Invalid univariate KZG open" on a failed pairing check */
+lh_status lh_ukzg_verify(const lh_ukzg_vp*, const lh_g1* comm, const lh_fr* point, const lh_fr* eval, lh_transcript* t);
+/* UnivariateKzg::batch_verify (kzg.rs:380-419) */
+lh_status lh_ukzg_batch_verify(const lh_ukzg_vp*, const lh_g1* comms, size_t num_comms, const lh_fr* points,
+                               size_t num_points, const lh_evaluation* evals, size_t num_evals, lh_transcript* t);
+/* Gemini::batch_commit (gemini.rs:56-76): the same bytes as lh_zeromorph_batch_commit */
+lh_status lh_gemini_batch_commit(lh_ctx*, const lh_usrs*, size_t poly_size, const lh_fr* const* d_polys, size_t num_polys,
+                                 size_t num_vars, lh_g1* out_comms);
+/* Gemini::open (gemini.rs:78-138): writes n - 1 fold commitments, n evaluations, [q] and the KZG proof (96 n + 64 bytes) */
+lh_status lh_gemini_open(lh_ctx*, const lh_usrs*, size_t poly_size, const lh_fr* d_poly, size_t num_vars,
+                         const lh_fr* point, lh_transcript* t);
+/* Gemini::batch_open (gemini.rs:140-155, additive::batch_open) */
+lh_status lh_gemini_batch_open(lh_ctx*, const lh_usrs*, size_t poly_size, size_t num_vars, const lh_fr* const* d_polys,
+                               size_t num_polys, const lh_fr* points, size_t num_points, const lh_evaluation* evals,
+                               size_t num_evals, lh_transcript* t);
+/* the folds fs[1..] of that opening (gemini.rs:100-108), flat: fs[i] (2^(n-i) coefficients) behind fs[i-1], 2^n - 2 in all */
+lh_status lh_gemini_folds(lh_ctx*, const lh_fr* d_poly, size_t num_vars, const lh_fr* point, lh_fr* d_out);
+/* Gemini::verify / batch_verify (gemini.rs:165-211) */
+lh_status lh_gemini_verify(const lh_ukzg_vp*, const lh_g1* comm, const lh_fr* point, size_t num_vars, const lh_fr* eval,
+                           lh_transcript* t);
+lh_status lh_gemini_batch_verify(const lh_ukzg_vp*, size_t num_vars, const lh_g1* comms, size_t num_comms,
+                                 const lh_fr* points, size_t num_points, const lh_evaluation* evals, size_t num_evals,
+                                 lh_transcript* t);
+/* Lasso and HyperPlonk<Gemini<UnivariateKzg<Bn256>>> (backend/hyperplonk.rs:425): arguments as the _zeromorph entries */
+lh_status lh_lasso_prove_gemini(lh_ctx*, const lh_usrs*, size_t poly_size, const lh_lasso_table*, size_t num_vars,
+                                const uint32_t* const* d_dims, lh_transcript* t);
+lh_status lh_lasso_verify_gemini(const lh_ukzg_vp*, const lh_lasso_table*, size_t num_vars, lh_transcript* t);
+lh_status lh_hyperplonk_prove_gemini(lh_ctx*, const lh_usrs*, size_t poly_size, const lh_hp_param*,
+                                     const lh_fr* const* instances, const lh_fr* const* d_witness_polys, lh_transcript* t);
+lh_status lh_hyperplonk_verify_gemini(const lh_ukzg_vp*, const lh_hp_vparam*, const lh_fr* const* instances,
+                                      lh_transcript* t);
+lh_status lh_hyperplonk_prove_phases_gemini(lh_ctx*, const lh_usrs*, size_t poly_size, const lh_hp_param*,
+                                            size_t num_phases, const size_t* num_witness_polys,
+                                            const size_t* num_challenges, const lh_fr* const* instances,
+                                            const lh_hp_circuit* circuit, lh_transcript* t);
+lh_status lh_hyperplonk_verify_phases_gemini(const lh_ukzg_vp*, const lh_hp_vparam*, size_t num_phases,
+                                             const size_t* num_witness_polys, const size_t* num_challenges,
+                                             const lh_fr* const* instances, lh_transcript* t);
+
 /* ---------------------------------------------------------------- f4: Brakedown (transparent, no SRS)
  * PolynomialCommitmentScheme for MultilinearBrakedown<bn256::Fr, Keccak256, BrakedownSpec1..6>
  * (pcs/multilinear/brakedown.rs:89-417, util/code/brakedown.rs): 2^num_vars evaluations as num_rows rows of row_len,
