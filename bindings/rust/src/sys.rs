@@ -330,6 +330,59 @@ extern "C" {
                                       t: *mut lh_transcript) -> lh_status;
     pub fn lh_hyperplonk_verify_gemini(vp: *const c_void, hvp: *const lh_hp_vparam, instances: *const *const Fr,
                                        t: *mut lh_transcript) -> lh_status;
+    // The multilinear IPA over bn256::G1Affine (include/lasso_hip.h, section f5); lh_ipa_param is opaque here
+    pub fn lh_ipa_setup(ctx: *mut lh_ctx, poly_size: usize, out: *mut *mut c_void) -> lh_status;
+    pub fn lh_ipa_param_free(ctx: *mut lh_ctx, param: *mut c_void);
+    pub fn lh_ipa_param_size(param: *const c_void) -> usize;
+    pub fn lh_ipa_param_download(ctx: *mut lh_ctx, param: *const c_void, g: *mut G1Affine, h: *mut G1Affine) -> lh_status;
+    pub fn lh_ipa_batch_commit(ctx: *mut lh_ctx, param: *const c_void, poly_size: usize, d_polys: *const *const Fr,
+                               num_polys: usize, num_vars: usize, out_comms: *mut G1Affine) -> lh_status;
+    pub fn lh_ipa_open(ctx: *mut lh_ctx, param: *const c_void, poly_size: usize, d_poly: *const Fr, num_vars: usize,
+                       point: *const Fr, t: *mut lh_transcript) -> lh_status;
+    pub fn lh_ipa_batch_open(ctx: *mut lh_ctx, param: *const c_void, poly_size: usize, num_vars: usize,
+                             d_polys: *const *const Fr, num_polys: usize, points: *const Fr, num_points: usize,
+                             evals: *const lh_evaluation, num_evals: usize, t: *mut lh_transcript) -> lh_status;
+    pub fn lh_ipa_verify(param: *const c_void, poly_size: usize, comm: *const G1Affine, point: *const Fr, num_vars: usize,
+                         eval: *const Fr, t: *mut lh_transcript) -> lh_status;
+    pub fn lh_ipa_batch_verify(param: *const c_void, poly_size: usize, num_vars: usize, comms: *const G1Affine,
+                               num_comms: usize, points: *const Fr, num_points: usize, evals: *const lh_evaluation,
+                               num_evals: usize, t: *mut lh_transcript) -> lh_status;
+    pub fn lh_g1_axpy(ctx: *mut lh_ctx, d_a: *const G1Affine, d_b: *const G1Affine, n: usize, s: *const Fr,
+                      d_out: *mut G1Affine) -> lh_status;
+    pub fn lh_lasso_prove_ipa(ctx: *mut lh_ctx, param: *const c_void, poly_size: usize, table: *const lh_lasso_table,
+                              num_vars: usize, d_dims: *const *const u32, t: *mut lh_transcript) -> lh_status;
+    pub fn lh_lasso_verify_ipa(param: *const c_void, poly_size: usize, table: *const lh_lasso_table, num_vars: usize,
+                               t: *mut lh_transcript) -> lh_status;
+    pub fn lh_hyperplonk_prove_ipa(ctx: *mut lh_ctx, param: *const c_void, poly_size: usize, pp: *const lh_hp_param,
+                                   instances: *const *const Fr, d_witness_polys: *const *const Fr,
+                                   t: *mut lh_transcript) -> lh_status;
+    pub fn lh_hyperplonk_verify_ipa(param: *const c_void, poly_size: usize, hvp: *const lh_hp_vparam,
+                                    instances: *const *const Fr, t: *mut lh_transcript) -> lh_status;
+    pub fn lh_hyperplonk_prove_phases_ipa(ctx: *mut lh_ctx, param: *const c_void, poly_size: usize, pp: *const lh_hp_param,
+                                          num_phases: usize, num_witness_polys: *const usize, num_challenges: *const usize,
+                                          instances: *const *const Fr, circuit: *const lh_hp_circuit,
+                                          t: *mut lh_transcript) -> lh_status;
+    pub fn lh_hyperplonk_verify_phases_ipa(param: *const c_void, poly_size: usize, hvp: *const lh_hp_vparam, num_phases: usize,
+                                           num_witness_polys: *const usize, num_challenges: *const usize,
+                                           instances: *const *const Fr, t: *mut lh_transcript) -> lh_status;
+    // Hyrax on top of the IPA (same section); its param is an lh_ipa_param
+    pub fn lh_hyrax_setup(ctx: *mut lh_ctx, poly_size: usize, batch_size: usize, out: *mut *mut c_void) -> lh_status;
+    pub fn lh_hyrax_dims(poly_size: usize, batch_size: usize, num_vars: *mut usize, batch_num_vars: *mut usize,
+                         row_num_vars: *mut usize) -> lh_status;
+    pub fn lh_hyrax_trim(param: *const c_void, poly_size: usize, batch_size: usize, row_num_vars: *mut usize,
+                         num_chunks: *mut usize) -> lh_status;
+    pub fn lh_hyrax_batch_commit(ctx: *mut lh_ctx, param: *const c_void, poly_size: usize, batch_size: usize,
+                                 d_polys: *const *const Fr, num_polys: usize, num_vars: usize, out_comms: *mut G1Affine) -> lh_status;
+    pub fn lh_hyrax_open(ctx: *mut lh_ctx, param: *const c_void, poly_size: usize, batch_size: usize, d_poly: *const Fr,
+                         num_vars: usize, point: *const Fr, t: *mut lh_transcript) -> lh_status;
+    pub fn lh_hyrax_batch_open(ctx: *mut lh_ctx, param: *const c_void, poly_size: usize, batch_size: usize, num_vars: usize,
+                               d_polys: *const *const Fr, num_polys: usize, points: *const Fr, num_points: usize,
+                               evals: *const lh_evaluation, num_evals: usize, t: *mut lh_transcript) -> lh_status;
+    pub fn lh_hyrax_verify(param: *const c_void, poly_size: usize, batch_size: usize, comm: *const G1Affine, point: *const Fr,
+                           num_vars: usize, eval: *const Fr, t: *mut lh_transcript) -> lh_status;
+    pub fn lh_hyrax_batch_verify(param: *const c_void, poly_size: usize, batch_size: usize, num_vars: usize,
+                                 comms: *const G1Affine, num_comms: usize, points: *const Fr, num_points: usize,
+                                 evals: *const lh_evaluation, num_evals: usize, t: *mut lh_transcript) -> lh_status;
     // Brakedown (include/lasso_hip.h, section f4); params and commitments are opaque here
     pub fn lh_keccak_transcript_hash_io(t: *mut lh_transcript, out: *mut lh_hash_transcript) -> lh_status;
     pub fn lh_brakedown_setup(ctx: *mut lh_ctx, num_vars: usize, spec: c_int, seed32: *const u8,

@@ -716,9 +716,12 @@ def sum_check_verify(prover, num_vars, degree, sum_, transcript):
 def lasso_verify(vp, table, num_vars, transcript):
     """Verifier of the Lasso argument (oracle/pyref/lasso.py:219-261).  A Keccak256Transcript must be fully consumed."""
     t = table.to_c()
-    fn = vp.lib.lh_lasso_verify_zeromorph if isinstance(vp, ZeromorphVerifierParam) else \
-        vp.lib.lh_lasso_verify_gemini if isinstance(vp, GeminiVerifierParam) else vp.lib.lh_lasso_verify
-    _check(fn(vp.h, C.byref(t), num_vars, transcript.p))
+    if isinstance(vp, IpaParam):
+        _check(vp.lib.lh_lasso_verify_ipa(vp.params.h, vp.poly_size, C.byref(t), num_vars, transcript.p))
+    else:
+        fn = vp.lib.lh_lasso_verify_zeromorph if isinstance(vp, ZeromorphVerifierParam) else \
+            vp.lib.lh_lasso_verify_gemini if isinstance(vp, GeminiVerifierParam) else vp.lib.lh_lasso_verify
+        _check(fn(vp.h, C.byref(t), num_vars, transcript.p))
     if isinstance(transcript, Keccak256Transcript) and transcript.remaining():
         raise InvalidSnark("trailing bytes in proof")
 
@@ -1081,6 +1084,204 @@ class Gemini:
                                              _evaluations(evals), len(evals), transcript.p))
 
 
+# ------------------------------------------------------------------ pcs::multilinear::ipa over bn256::G1Affine
+class IpaParams:
+    """MultilinearIpaParams (pcs/multilinear/ipa.rs:25-44): g (2^num_vars points) and h from the library's hash-to-point
+    (DESIGN.md §14).  Set up with a Context g is derived on and stays on its device (prover param); without one it is on
+    the host (verifier param)."""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.lib, self.h = ctx, _ffi.load(), handle
+        self.size = self.lib.lh_ipa_param_size(handle)
+
+    def download(self):
+        """-> (g, h) as affine points"""
+        out, h = C.create_string_buffer(64 * self.size), lh_g1()
+        _check(self.lib.lh_ipa_param_download(self.ctx.h if self.ctx is not None else None, self.h, out, C.byref(h)))
+        raw = out.raw
+        return [g1_from_bytes(raw[64 * i:64 * i + 64]) for i in range(self.size)], g1_from_bytes(bytes(h))
+
+    def free(self):
+        if self.h:
+            self.lib.lh_ipa_param_free(self.ctx.h if self.ctx is not None else None, self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class IpaParam:
+    """a trimmed MultilinearIpaParams (ipa.rs:129-145): the params and the trim size; prover and verifier param at once"""
+
+    def __init__(self, params, poly_size):
+        self.params, self.poly_size, self.ctx, self.lib = params, poly_size, params.ctx, params.lib
+
+
+class Ipa:
+    """MultilinearIpa<bn256::G1Affine> (pcs/multilinear/ipa.rs:23-337): transparent and additive; the method set of Gemini"""
+
+    @staticmethod
+    def setup(ctx, poly_size):
+        """ipa.rs:98-127; ctx None: a host-only (verifier) param"""
+        h = C.c_void_p()
+        _check(_ffi.load().lh_ipa_setup(ctx.h if ctx is not None else None, poly_size, C.byref(h)))
+        return IpaParams(ctx, h)
+
+    @staticmethod
+    def trim(params, poly_size):
+        if poly_size < 1 or poly_size & (poly_size - 1):
+            raise ArgumentError("poly_size must be a power of two")
+        if params.size < poly_size:
+            raise InvalidPcsParam("Too many variates to trim (param supports variates up to %d but got %d)"
+                                  % (params.size.bit_length() - 1, poly_size.bit_length() - 1))
+        return IpaParam(params, poly_size)
+
+    @staticmethod
+    def batch_commit(pp, polys):
+        if not polys:
+            return []
+        out = (lh_g1 * len(polys))()
+        _check(pp.lib.lh_ipa_batch_commit(pp.ctx.h, pp.params.h, pp.poly_size, _ptr_array(polys), len(polys),
+                                          polys[0].num_vars, out))
+        raw = C.string_at(out, 64 * len(polys))
+        return [g1_from_bytes(raw[64 * i:64 * i + 64]) for i in range(len(polys))]
+
+    @staticmethod
+    def commit(pp, poly):
+        return Ipa.batch_commit(pp, [poly])[0]
+
+    @staticmethod
+    def batch_commit_and_write(pp, polys, transcript):
+        comms = Ipa.batch_commit(pp, polys)
+        transcript.write_commitments(comms)
+        return comms
+
+    @staticmethod
+    def open(pp, poly, point, transcript):
+        _check(pp.lib.lh_ipa_open(pp.ctx.h, pp.params.h, pp.poly_size, poly.ptr, poly.num_vars, _fr_array(point),
+                                  transcript.p))
+
+    @staticmethod
+    def batch_open(pp, num_vars, polys, points, evals, transcript):
+        for p in points:
+            if len(p) != num_vars:
+                raise InvalidPcsParam("Invalid point (expect point to have %d variates but got %d)" % (num_vars, len(p)))
+        flat = [v for p in points for v in p]
+        _check(pp.lib.lh_ipa_batch_open(pp.ctx.h, pp.params.h, pp.poly_size, num_vars, _ptr_array(polys), len(polys),
+                                        _fr_array(flat), len(points), _evaluations(evals), len(evals), transcript.p))
+
+    @staticmethod
+    def verify(vp, comm, point, eval_, transcript):
+        _check(vp.lib.lh_ipa_verify(vp.params.h, vp.poly_size, _g1_array([comm]), _fr_array(point), len(point),
+                                    _fr_array([eval_]), transcript.p))
+
+    @staticmethod
+    def batch_verify(vp, num_vars, comms, points, evals, transcript):
+        flat = [v for p in points for v in p]
+        _check(vp.lib.lh_ipa_batch_verify(vp.params.h, vp.poly_size, num_vars, _g1_array(comms), len(comms),
+                                          _fr_array(flat), len(points), _evaluations(evals), len(evals), transcript.p))
+
+    @staticmethod
+    def g1_axpy(ctx, a, b, s):
+        """the base fold of a round as a primitive: [a[j] + s b[j]] for lists of affine points (None = identity)"""
+        n = len(a)
+        da, db = ctx.upload(b"".join(g1_to_bytes(p) for p in a)), ctx.upload(b"".join(g1_to_bytes(p) for p in b))
+        out = ctx.alloc(64 * n)
+        _check(ctx.lib.lh_g1_axpy(ctx.h, da.ptr, db.ptr, n, _fr_array([s]), out.ptr))
+        raw = out.read()
+        return [g1_from_bytes(raw[64 * i:64 * i + 64]) for i in range(n)]
+
+
+class HyraxParam:
+    """a trimmed MultilinearHyraxParams (hyrax.rs:26-62): the inner IPA params and the trim arguments; prover and verifier
+    param at once"""
+
+    def __init__(self, params, poly_size, batch_size):
+        self.params, self.poly_size, self.batch_size, self.ctx, self.lib = params, poly_size, batch_size, params.ctx, params.lib
+        self.num_vars, self.batch_num_vars, self.row_num_vars = Hyrax.dims(poly_size, batch_size)
+        self.num_chunks = 1 << (self.num_vars - self.row_num_vars)
+
+
+class Hyrax:
+    """MultilinearHyrax<bn256::G1Affine> (pcs/multilinear/hyrax.rs:23-321); a commitment is a list of num_chunks points"""
+
+    @staticmethod
+    def dims(poly_size, batch_size):
+        """-> (num_vars, batch_num_vars, row_num_vars) (hyrax.rs:125-127)"""
+        a, b, c_ = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        _check(_ffi.load().lh_hyrax_dims(poly_size, batch_size, C.byref(a), C.byref(b), C.byref(c_)))
+        return a.value, b.value, c_.value
+
+    @staticmethod
+    def setup(ctx, poly_size, batch_size):
+        """hyrax.rs:121-137 -> the inner IpaParams (2^row_num_vars generators); ctx None: a host-only (verifier) param"""
+        h = C.c_void_p()
+        _check(_ffi.load().lh_hyrax_setup(ctx.h if ctx is not None else None, poly_size, batch_size, C.byref(h)))
+        return IpaParams(ctx, h)
+
+    @staticmethod
+    def trim(params, poly_size, batch_size):
+        _check(params.lib.lh_hyrax_trim(params.h, poly_size, batch_size, None, None))
+        return HyraxParam(params, poly_size, batch_size)
+
+    @staticmethod
+    def batch_commit(pp, polys):
+        if not polys:
+            return []
+        k = pp.num_chunks
+        out = (lh_g1 * (len(polys) * k))()
+        _check(pp.lib.lh_hyrax_batch_commit(pp.ctx.h, pp.params.h, pp.poly_size, pp.batch_size, _ptr_array(polys), len(polys),
+                                            polys[0].num_vars, out))
+        raw = C.string_at(out, 64 * len(polys) * k)
+        pts = [g1_from_bytes(raw[64 * i:64 * i + 64]) for i in range(len(polys) * k)]
+        return [pts[i * k:(i + 1) * k] for i in range(len(polys))]
+
+    @staticmethod
+    def commit(pp, poly):
+        return Hyrax.batch_commit(pp, [poly])[0]
+
+    @staticmethod
+    def batch_commit_and_write(pp, polys, transcript):
+        comms = Hyrax.batch_commit(pp, polys)
+        for comm in comms:
+            transcript.write_commitments(comm)
+        return comms
+
+    @staticmethod
+    def open(pp, poly, point, transcript):
+        _check(pp.lib.lh_hyrax_open(pp.ctx.h, pp.params.h, pp.poly_size, pp.batch_size, poly.ptr, poly.num_vars,
+                                    _fr_array(point), transcript.p))
+
+    @staticmethod
+    def batch_open(pp, num_vars, polys, points, evals, transcript):
+        for p in points:
+            if len(p) != num_vars:
+                raise InvalidPcsParam("Invalid point (expect point to have %d variates but got %d)" % (num_vars, len(p)))
+        flat = [v for p in points for v in p]
+        _check(pp.lib.lh_hyrax_batch_open(pp.ctx.h, pp.params.h, pp.poly_size, pp.batch_size, num_vars, _ptr_array(polys),
+                                          len(polys), _fr_array(flat), len(points), _evaluations(evals), len(evals),
+                                          transcript.p))
+
+    @staticmethod
+    def verify(vp, comm, point, eval_, transcript):
+        if len(comm) != vp.num_chunks:
+            raise ArgumentError("expected a commitment of %d points" % vp.num_chunks)  # assert_eq! hyrax.rs:295
+        _check(vp.lib.lh_hyrax_verify(vp.params.h, vp.poly_size, vp.batch_size, _g1_array(comm), _fr_array(point), len(point),
+                                      _fr_array([eval_]), transcript.p))
+
+    @staticmethod
+    def batch_verify(vp, num_vars, comms, points, evals, transcript):
+        if any(len(cm) != vp.num_chunks for cm in comms):
+            raise ArgumentError("expected commitments of %d points" % vp.num_chunks)
+        flat = [v for p in points for v in p]
+        _check(vp.lib.lh_hyrax_batch_verify(vp.params.h, vp.poly_size, vp.batch_size, num_vars,
+                                            _g1_array([p for cm in comms for p in cm]), len(comms), _fr_array(flat), len(points),
+                                            _evaluations(evals), len(evals), transcript.p))
+
+
 # ------------------------------------------------------------------ pcs::multilinear::brakedown
 class BrakedownParam:
     """MultilinearBrakedownParams (pcs/multilinear/brakedown.rs:35-41): the code's parameters and sparse matrices, drawn
@@ -1277,8 +1478,9 @@ def lasso_prove(pp, table, num_vars, dims, transcript):
             or len(table.g_terms) > _ffi.LH_LASSO_MAX_TERMS:
         raise ArgumentError("table too large")
     t = table.to_c()
-    if isinstance(pp, (ZeromorphProverParam, GeminiProverParam)):
-        fn = pp.ctx.lib.lh_lasso_prove_gemini if isinstance(pp, GeminiProverParam) else pp.ctx.lib.lh_lasso_prove_zeromorph
+    if isinstance(pp, (ZeromorphProverParam, GeminiProverParam, IpaParam)):
+        fn = pp.ctx.lib.lh_lasso_prove_ipa if isinstance(pp, IpaParam) else \
+            pp.ctx.lib.lh_lasso_prove_gemini if isinstance(pp, GeminiProverParam) else pp.ctx.lib.lh_lasso_prove_zeromorph
         _check(fn(pp.ctx.h, pp.params.h, pp.poly_size, C.byref(t), num_vars, _ptr_array(dims), transcript.p))
         return
     _check(pp.ctx.lib.lh_lasso_prove(pp.ctx.h, pp.h, C.byref(t), num_vars, _ptr_array(dims), transcript.p))

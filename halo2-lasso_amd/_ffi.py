@@ -290,6 +290,42 @@ SIGNATURES = {
                                                     C.POINTER(lh_hp_circuit), C.POINTER(lh_transcript)]),
     "lh_hyperplonk_verify_phases_gemini": (C.c_int, [_P, C.POINTER(lh_hp_vparam), _SZ, C.POINTER(_SZ), C.POINTER(_SZ),
                                                      C.POINTER(C.POINTER(lh_fr)), C.POINTER(lh_transcript)]),
+    "lh_ipa_setup": (C.c_int, [_P, _SZ, C.POINTER(_P)]),
+    "lh_ipa_param_free": (None, [_P, _P]),
+    "lh_ipa_param_size": (_SZ, [_P]),
+    "lh_ipa_param_download": (C.c_int, [_P, _P, C.c_char_p, C.POINTER(lh_g1)]),
+    "lh_ipa_batch_commit": (C.c_int, [_P, _P, _SZ, C.POINTER(_P), _SZ, _SZ, C.POINTER(lh_g1)]),
+    "lh_ipa_open": (C.c_int, [_P, _P, _SZ, _P, _SZ, C.POINTER(lh_fr), C.POINTER(lh_transcript)]),
+    "lh_ipa_batch_open": (C.c_int, [_P, _P, _SZ, _SZ, C.POINTER(_P), _SZ, C.POINTER(lh_fr), _SZ,
+                                    C.POINTER(lh_evaluation), _SZ, C.POINTER(lh_transcript)]),
+    "lh_ipa_verify": (C.c_int, [_P, _SZ, C.POINTER(lh_g1), C.POINTER(lh_fr), _SZ, C.POINTER(lh_fr),
+                                C.POINTER(lh_transcript)]),
+    "lh_ipa_batch_verify": (C.c_int, [_P, _SZ, _SZ, C.POINTER(lh_g1), _SZ, C.POINTER(lh_fr), _SZ,
+                                      C.POINTER(lh_evaluation), _SZ, C.POINTER(lh_transcript)]),
+    "lh_g1_axpy": (C.c_int, [_P, _P, _P, _SZ, C.POINTER(lh_fr), _P]),
+    "lh_hyrax_setup": (C.c_int, [_P, _SZ, _SZ, C.POINTER(_P)]),
+    "lh_hyrax_dims": (C.c_int, [_SZ, _SZ, C.POINTER(_SZ), C.POINTER(_SZ), C.POINTER(_SZ)]),
+    "lh_hyrax_trim": (C.c_int, [_P, _SZ, _SZ, C.POINTER(_SZ), C.POINTER(_SZ)]),
+    "lh_hyrax_batch_commit": (C.c_int, [_P, _P, _SZ, _SZ, C.POINTER(_P), _SZ, _SZ, C.POINTER(lh_g1)]),
+    "lh_hyrax_open": (C.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, C.POINTER(lh_fr), C.POINTER(lh_transcript)]),
+    "lh_hyrax_batch_open": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, C.POINTER(_P), _SZ, C.POINTER(lh_fr), _SZ,
+                                      C.POINTER(lh_evaluation), _SZ, C.POINTER(lh_transcript)]),
+    "lh_hyrax_verify": (C.c_int, [_P, _SZ, _SZ, C.POINTER(lh_g1), C.POINTER(lh_fr), _SZ, C.POINTER(lh_fr),
+                                  C.POINTER(lh_transcript)]),
+    "lh_hyrax_batch_verify": (C.c_int, [_P, _SZ, _SZ, _SZ, C.POINTER(lh_g1), _SZ, C.POINTER(lh_fr), _SZ,
+                                        C.POINTER(lh_evaluation), _SZ, C.POINTER(lh_transcript)]),
+    "lh_lasso_prove_ipa": (C.c_int, [_P, _P, _SZ, C.POINTER(lh_lasso_table), _SZ, C.POINTER(_P),
+                                     C.POINTER(lh_transcript)]),
+    "lh_lasso_verify_ipa": (C.c_int, [_P, _SZ, C.POINTER(lh_lasso_table), _SZ, C.POINTER(lh_transcript)]),
+    "lh_hyperplonk_prove_ipa": (C.c_int, [_P, _P, _SZ, C.POINTER(lh_hp_param), C.POINTER(C.POINTER(lh_fr)),
+                                          C.POINTER(_P), C.POINTER(lh_transcript)]),
+    "lh_hyperplonk_verify_ipa": (C.c_int, [_P, _SZ, C.POINTER(lh_hp_vparam), C.POINTER(C.POINTER(lh_fr)),
+                                           C.POINTER(lh_transcript)]),
+    "lh_hyperplonk_prove_phases_ipa": (C.c_int, [_P, _P, _SZ, C.POINTER(lh_hp_param), _SZ, C.POINTER(_SZ),
+                                                 C.POINTER(_SZ), C.POINTER(C.POINTER(lh_fr)),
+                                                 C.POINTER(lh_hp_circuit), C.POINTER(lh_transcript)]),
+    "lh_hyperplonk_verify_phases_ipa": (C.c_int, [_P, _SZ, C.POINTER(lh_hp_vparam), _SZ, C.POINTER(_SZ), C.POINTER(_SZ),
+                                                  C.POINTER(C.POINTER(lh_fr)), C.POINTER(lh_transcript)]),
     "lh_debug_jit_source": (C.c_int, [C.POINTER(C.c_uint32), _SZ, C.c_uint32, C.c_uint32, C.c_int, C.c_char_p, _SZ,
                                       C.POINTER(_SZ)]),
     "lh_keccak_transcript_hash_io": (C.c_int, [C.POINTER(lh_transcript), C.POINTER(lh_hash_transcript)]),

@@ -23,6 +23,9 @@ struct lh_zm_vp {
 struct lh_ukzg_vp {
   UkzgVerifierParams* p;
 };
+struct lh_ipa_param {
+  IpaParams* p;
+};
 struct lh_brakedown_param {
   BdParam p;
 };
@@ -1528,6 +1531,275 @@ lh_status lh_hyperplonk_verify_phases_gemini(const lh_ukzg_vp* vp, const lh_hp_v
   LH_REQUIRE(num_phases == 0 || (num_witness_polys && num_challenges), LH_ERR_ARG, "null argument: phases");
   Transcript tr(t);
   hyperplonk_verify_phases(gemini_verifier(*vp->p), *hvp, std::vector<size_t>(num_witness_polys, num_witness_polys + num_phases),
+                           std::vector<size_t>(num_challenges, num_challenges + num_phases), (const HFr* const*)instances, tr);
+  LH_CATCH
+}
+
+// ---------------------------------------------------------------- the multilinear IPA over bn256::G1Affine
+lh_status lh_ipa_setup(lh_ctx* ctx, size_t poly_size, lh_ipa_param** out) {
+  LH_TRY
+  NEED(out);
+  if (ctx) {
+    DeviceGuard device_guard_(ctx->c.device);
+    *out = new lh_ipa_param{ipa_setup(&ctx->c, poly_size)};
+  } else {
+    *out = new lh_ipa_param{ipa_setup(nullptr, poly_size)};
+  }
+  LH_CATCH
+}
+void lh_ipa_param_free(lh_ctx* ctx, lh_ipa_param* param) {
+  if (!param) return;
+  if (ctx) (void)hipStreamSynchronize(ctx->c.stream);
+  ipa_free(param->p);
+  delete param;
+}
+size_t lh_ipa_param_size(const lh_ipa_param* param) { return param ? (size_t)1 << param->p->num_vars : 0; }
+lh_status lh_ipa_param_download(lh_ctx* ctx, const lh_ipa_param* param, lh_g1* g, lh_g1* h) {
+  LH_TRY
+  NEED(param);
+  const size_t size = (size_t)1 << param->p->num_vars;
+  if (g) {
+    if (param->p->d_g) {
+      NEED_CTX(ctx);
+      LH_HIP(hipMemcpyAsync(g, param->p->d_g, size * sizeof(G1Affine), hipMemcpyDeviceToHost, ctx->c.stream));
+      ctx->c.sync();
+    } else {
+      memcpy(g, ipa_host_g(*param->p).data(), size * sizeof(HG1));
+    }
+  }
+  if (h) memcpy(h, &param->p->h, sizeof(HG1));
+  LH_CATCH
+}
+lh_status lh_ipa_batch_commit(lh_ctx* ctx, const lh_ipa_param* param, size_t poly_size, const lh_fr* const* d_polys,
+                              size_t num_polys, size_t num_vars, lh_g1* out_comms) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(param);
+  NEED_N(d_polys, num_polys);
+  NEED_N(out_comms, num_polys);
+  for (size_t i = 0; i < num_polys; i++) NEED(d_polys[i]);
+  std::vector<HG1> c = ipa_batch_commit(ctx->c, *param->p, poly_size, (const Fr* const*)d_polys, num_polys, num_vars);
+  if (num_polys) memcpy(out_comms, c.data(), 64 * num_polys);
+  LH_CATCH
+}
+lh_status lh_ipa_open(lh_ctx* ctx, const lh_ipa_param* param, size_t poly_size, const lh_fr* d_poly, size_t num_vars,
+                      const lh_fr* point, lh_transcript* t) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(param);
+  NEED(d_poly);
+  NEED_N(point, num_vars);
+  Transcript tr(t);
+  ipa_open(ctx->c, *param->p, poly_size, (const Fr*)d_poly, num_vars, (const HFr*)point, tr);
+  LH_CATCH
+}
+lh_status lh_ipa_batch_open(lh_ctx* ctx, const lh_ipa_param* param, size_t poly_size, size_t num_vars,
+                            const lh_fr* const* d_polys, size_t num_polys, const lh_fr* points, size_t num_points,
+                            const lh_evaluation* evals, size_t num_evals, lh_transcript* t) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(param);
+  NEED_N(d_polys, num_polys);
+  NEED_N(points, num_points);
+  NEED_N(evals, num_evals);
+  for (size_t i = 0; i < num_polys; i++) NEED(d_polys[i]);
+  Transcript tr(t);
+  ipa_batch_open(ctx->c, *param->p, poly_size, num_vars, (const Fr* const*)d_polys, num_polys, (const HFr*)points, num_points,
+                 evals, num_evals, tr);
+  LH_CATCH
+}
+lh_status lh_ipa_verify(const lh_ipa_param* param, size_t poly_size, const lh_g1* comm, const lh_fr* point, size_t num_vars,
+                        const lh_fr* eval, lh_transcript* t) {
+  LH_TRY
+  NEED(param);
+  NEED(comm);
+  NEED(eval);
+  NEED_N(point, num_vars);
+  Transcript tr(t);
+  HG1 c;
+  memcpy(&c, comm, sizeof(c));
+  HFr e;
+  memcpy(&e, eval, 32);
+  ipa_verify(*param->p, poly_size, c, (const HFr*)point, num_vars, e, tr);
+  LH_CATCH
+}
+lh_status lh_ipa_batch_verify(const lh_ipa_param* param, size_t poly_size, size_t num_vars, const lh_g1* comms, size_t num_comms,
+                              const lh_fr* points, size_t num_points, const lh_evaluation* evals, size_t num_evals,
+                              lh_transcript* t) {
+  LH_TRY
+  NEED(param);
+  NEED_N(comms, num_comms);
+  NEED_N(points, num_points);
+  NEED_N(evals, num_evals);
+  Transcript tr(t);
+  ipa_batch_verify(*param->p, poly_size, num_vars, (const HG1*)comms, num_comms, (const HFr*)points, num_points, evals, num_evals,
+                   tr);
+  LH_CATCH
+}
+lh_status lh_g1_axpy(lh_ctx* ctx, const lh_g1* d_a, const lh_g1* d_b, size_t n, const lh_fr* s, lh_g1* d_out) {
+  LH_TRY NEED_CTX(ctx);
+  NEED_N(d_a, n);
+  NEED_N(d_b, n);
+  NEED_N(d_out, n);
+  NEED(s);
+  Fr sv;
+  memcpy(&sv, s, 32);
+  k_g1_axpy(ctx->c, (const G1Affine*)d_a, (const G1Affine*)d_b, n, sv, (G1Affine*)d_out);
+  ctx->c.sync();
+  LH_CATCH
+}
+// ---------------------------------------------------------------- Hyrax on top of the IPA
+lh_status lh_hyrax_setup(lh_ctx* ctx, size_t poly_size, size_t batch_size, lh_ipa_param** out) {
+  LH_TRY
+  NEED(out);
+  const HyraxDims d = hyrax_dims(poly_size, batch_size);
+  if (ctx) {
+    DeviceGuard device_guard_(ctx->c.device);
+    *out = new lh_ipa_param{ipa_setup(&ctx->c, (size_t)1 << d.row_num_vars)};
+  } else {
+    *out = new lh_ipa_param{ipa_setup(nullptr, (size_t)1 << d.row_num_vars)};
+  }
+  LH_CATCH
+}
+lh_status lh_hyrax_dims(size_t poly_size, size_t batch_size, size_t* num_vars, size_t* batch_num_vars, size_t* row_num_vars) {
+  LH_TRY
+  const HyraxDims d = hyrax_dims(poly_size, batch_size);
+  if (num_vars) *num_vars = d.num_vars;
+  if (batch_num_vars) *batch_num_vars = d.batch_num_vars;
+  if (row_num_vars) *row_num_vars = d.row_num_vars;
+  LH_CATCH
+}
+lh_status lh_hyrax_trim(const lh_ipa_param* param, size_t poly_size, size_t batch_size, size_t* row_num_vars, size_t* num_chunks) {
+  LH_TRY
+  NEED(param);
+  const HyraxDims d = hyrax_trim(*param->p, poly_size, batch_size);
+  if (row_num_vars) *row_num_vars = d.row_num_vars;
+  if (num_chunks) *num_chunks = d.num_chunks();
+  LH_CATCH
+}
+lh_status lh_hyrax_batch_commit(lh_ctx* ctx, const lh_ipa_param* param, size_t poly_size, size_t batch_size,
+                                const lh_fr* const* d_polys, size_t num_polys, size_t num_vars, lh_g1* out_comms) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(param);
+  NEED_N(d_polys, num_polys);
+  NEED_N(out_comms, num_polys);
+  for (size_t i = 0; i < num_polys; i++) NEED(d_polys[i]);
+  std::vector<HG1> c = hyrax_batch_commit(ctx->c, *param->p, poly_size, batch_size, (const Fr* const*)d_polys, num_polys, num_vars);
+  if (!c.empty()) memcpy(out_comms, c.data(), 64 * c.size());
+  LH_CATCH
+}
+lh_status lh_hyrax_open(lh_ctx* ctx, const lh_ipa_param* param, size_t poly_size, size_t batch_size, const lh_fr* d_poly,
+                        size_t num_vars, const lh_fr* point, lh_transcript* t) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(param);
+  NEED(d_poly);
+  NEED_N(point, num_vars);
+  Transcript tr(t);
+  hyrax_open(ctx->c, *param->p, poly_size, batch_size, (const Fr*)d_poly, num_vars, (const HFr*)point, tr);
+  LH_CATCH
+}
+lh_status lh_hyrax_batch_open(lh_ctx* ctx, const lh_ipa_param* param, size_t poly_size, size_t batch_size, size_t num_vars,
+                              const lh_fr* const* d_polys, size_t num_polys, const lh_fr* points, size_t num_points,
+                              const lh_evaluation* evals, size_t num_evals, lh_transcript* t) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(param);
+  NEED_N(d_polys, num_polys);
+  NEED_N(points, num_points);
+  NEED_N(evals, num_evals);
+  for (size_t i = 0; i < num_polys; i++) NEED(d_polys[i]);
+  Transcript tr(t);
+  hyrax_batch_open(ctx->c, *param->p, poly_size, batch_size, num_vars, (const Fr* const*)d_polys, num_polys, (const HFr*)points,
+                   num_points, evals, num_evals, tr);
+  LH_CATCH
+}
+lh_status lh_hyrax_verify(const lh_ipa_param* param, size_t poly_size, size_t batch_size, const lh_g1* comm, const lh_fr* point,
+                          size_t num_vars, const lh_fr* eval, lh_transcript* t) {
+  LH_TRY
+  NEED(param);
+  NEED(comm);
+  NEED(eval);
+  NEED_N(point, num_vars);
+  Transcript tr(t);
+  HFr e;
+  memcpy(&e, eval, 32);
+  hyrax_verify(*param->p, poly_size, batch_size, (const HG1*)comm, (const HFr*)point, num_vars, e, tr);
+  LH_CATCH
+}
+lh_status lh_hyrax_batch_verify(const lh_ipa_param* param, size_t poly_size, size_t batch_size, size_t num_vars,
+                                const lh_g1* comms, size_t num_comms, const lh_fr* points, size_t num_points,
+                                const lh_evaluation* evals, size_t num_evals, lh_transcript* t) {
+  LH_TRY
+  NEED(param);
+  NEED_N(comms, num_comms);
+  NEED_N(points, num_points);
+  NEED_N(evals, num_evals);
+  Transcript tr(t);
+  hyrax_batch_verify(*param->p, poly_size, batch_size, num_vars, (const HG1*)comms, num_comms, (const HFr*)points, num_points,
+                     evals, num_evals, tr);
+  LH_CATCH
+}
+static PcsBatchVerify ipa_verifier(const IpaParams& pcs, size_t poly_size) {
+  return [&pcs, poly_size](size_t nv, const HG1* comms, size_t nc, const HFr* points, size_t np, const lh_evaluation* evals,
+                           size_t ne, Transcript& t2) { ipa_batch_verify(pcs, poly_size, nv, comms, nc, points, np, evals, ne, t2); };
+}
+lh_status lh_lasso_prove_ipa(lh_ctx* ctx, const lh_ipa_param* param, size_t poly_size, const lh_lasso_table* table,
+                             size_t num_vars, const uint32_t* const* d_dims, lh_transcript* t) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(param);
+  NEED(table);
+  NEED(d_dims);
+  Transcript tr(t);
+  lasso_prove(ctx->c, ipa_pcs(ctx->c, *param->p, poly_size), *table, num_vars, d_dims, tr);
+  LH_CATCH
+}
+lh_status lh_lasso_verify_ipa(const lh_ipa_param* param, size_t poly_size, const lh_lasso_table* table, size_t num_vars,
+                              lh_transcript* t) {
+  LH_TRY
+  NEED(param);
+  NEED(table);
+  Transcript tr(t);
+  lasso_verify(ipa_verifier(*param->p, poly_size), *table, num_vars, tr);
+  LH_CATCH
+}
+lh_status lh_hyperplonk_prove_ipa(lh_ctx* ctx, const lh_ipa_param* param, size_t poly_size, const lh_hp_param* pp,
+                                  const lh_fr* const* instances, const lh_fr* const* d_witness_polys, lh_transcript* t) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(param);
+  NEED(pp);
+  NEED_N(d_witness_polys, pp->num_witness_polys);
+  Transcript tr(t);
+  hyperplonk_prove(ctx->c, ipa_pcs(ctx->c, *param->p, poly_size), *pp, (const HFr* const*)instances,
+                   (const Fr* const*)d_witness_polys, tr);
+  LH_CATCH
+}
+lh_status lh_hyperplonk_verify_ipa(const lh_ipa_param* param, size_t poly_size, const lh_hp_vparam* hvp,
+                                   const lh_fr* const* instances, lh_transcript* t) {
+  LH_TRY
+  NEED(param);
+  NEED(hvp);
+  Transcript tr(t);
+  hyperplonk_verify(ipa_verifier(*param->p, poly_size), *hvp, (const HFr* const*)instances, tr);
+  LH_CATCH
+}
+lh_status lh_hyperplonk_prove_phases_ipa(lh_ctx* ctx, const lh_ipa_param* param, size_t poly_size, const lh_hp_param* pp,
+                                         size_t num_phases, const size_t* num_witness_polys, const size_t* num_challenges,
+                                         const lh_fr* const* instances, const lh_hp_circuit* circuit, lh_transcript* t) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(param);
+  NEED(pp);
+  NEED(circuit);
+  Transcript tr(t);
+  const HpPhases ph = hp_phases_of(pp, num_phases, num_witness_polys, num_challenges, circuit);
+  hyperplonk_prove_phases(ctx->c, ipa_pcs(ctx->c, *param->p, poly_size), *pp, ph, (const HFr* const*)instances, tr);
+  LH_CATCH
+}
+lh_status lh_hyperplonk_verify_phases_ipa(const lh_ipa_param* param, size_t poly_size, const lh_hp_vparam* hvp, size_t num_phases,
+                                          const size_t* num_witness_polys, const size_t* num_challenges,
+                                          const lh_fr* const* instances, lh_transcript* t) {
+  LH_TRY
+  NEED(param);
+  NEED(hvp);
+  LH_REQUIRE(num_phases == 0 || (num_witness_polys && num_challenges), LH_ERR_ARG, "null argument: phases");
+  Transcript tr(t);
+  hyperplonk_verify_phases(ipa_verifier(*param->p, poly_size), *hvp,
+                           std::vector<size_t>(num_witness_polys, num_witness_polys + num_phases),
                            std::vector<size_t>(num_challenges, num_challenges + num_phases), (const HFr* const*)instances, tr);
   LH_CATCH
 }

@@ -825,6 +825,22 @@ struct GmTerm {
 // out[j] = sum_{k : j < len_k} w_k p_k[j], j < n (out aliases no term)
 void k_gm_combine(Ctx&, const GmTerm* terms, size_t count, size_t n, Fr* out);
 
+// ------------------------------------------------------------------ multilinear IPA (kernels_ipa.hip)
+// out[j] = g[first + j] of the library's hash-to-point, j < n; queued on the stream
+void k_ipa_generators(Ctx&, size_t first, size_t n, G1Affine* out);
+// the base fold: out[j] = a[j] + s b[j], affine (identity = (0,0)); out may be a (not b).  Temporary storage from the arena.
+void k_g1_axpy(Ctx&, const G1Affine* a, const G1Affine* b, size_t n, const Fr& s, G1Affine* out);
+constexpr size_t IPA_CROSS_BLOCKS = 1024;
+// d_out[0] = <coeffs[mid..2 mid), zs[..mid)>, d_out[1] = <coeffs[..mid), zs[mid..2 mid)> (DEVICE, queued on the stream);
+// d_partials: 2 IPA_CROSS_BLOCKS elements of scratch
+void k_ipa_cross(Ctx&, const Fr* coeffs, const Fr* zs, size_t mid, Fr* d_partials, Fr* d_out);
+// out_c[i] = coeffs[i] + xi_inv coeffs[mid + i], out_z[i] = zs[i] + xi zs[mid + i], i < mid (in place allowed)
+void k_ipa_fold_fr(Ctx&, const Fr* coeffs, const Fr* zs, size_t mid, const Fr& xi_inv, const Fr& xi, Fr* out_c, Fr* out_z);
+
+// Hyrax's row combination (fix_last_vars, hyrax.rs:243): out[c] = sum_r w[r] poly[r row_len + c], c < row_len, r < rows;
+// w on the device; temporary storage from the arena
+void k_hyrax_combine(Ctx&, const Fr* poly, const Fr* w, size_t rows, size_t row_len, Fr* out);
+
 // ------------------------------------------------------------------ radix sort (sort.hip)
 // stable sort of (u32 key, u32 value) pairs by the low `bits` bits of the key; inputs are preserved
 struct SortSlab {

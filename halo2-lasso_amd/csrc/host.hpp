@@ -407,6 +407,57 @@ void gemini_verify(const UkzgVerifierParams&, const HG1& comm, const HFr* point,
 void gemini_batch_verify(const UkzgVerifierParams&, size_t num_vars, const HG1* comms, size_t num_comms, const HFr* points,
                          size_t num_points, const lh_evaluation* evals, size_t num_evals, Transcript& tr);
 
+// ------------------------------------------------------------------ pcs::multilinear::ipa over bn256::G1Affine (ipa.cpp;
+// verifier in verifier.cpp).  MultilinearIpaParams (ipa.rs:25-44) is prover and verifier param at once: g on the device
+// when set up with a ctx, on the host when not (or on first use by a verifier); `poly_size` is the trim size (a prefix of g).
+struct IpaParams {
+  size_t num_vars = 0;
+  G1Affine* d_g = nullptr;
+  int device = -1;  // the device d_g lives on
+  HG1 h;
+  mutable std::vector<HG1> host_g;  // through ipa_host_g
+  mutable std::mutex mu;
+};
+HG1 ipa_hash_to_point(const uint8_t* message, size_t len);
+IpaParams* ipa_setup(Ctx* c, size_t poly_size);             // c null: host only
+void ipa_free(IpaParams*);
+const std::vector<HG1>& ipa_host_g(const IpaParams&);
+size_t ipa_trim_vars(const IpaParams&, size_t poly_size);   // ipa.rs:129-145 -> num_vars of the trimmed param
+std::vector<HG1> ipa_batch_commit(Ctx&, const IpaParams&, size_t poly_size, const Fr* const* d_polys, size_t num_polys,
+                                  size_t num_vars);
+void ipa_open(Ctx&, const IpaParams&, size_t poly_size, const Fr* d_poly, size_t num_vars, const HFr* point, Transcript& tr);
+void ipa_batch_open(Ctx&, const IpaParams&, size_t poly_size, size_t num_vars, const Fr* const* d_polys, size_t num_polys,
+                    const HFr* points, size_t num_points, const lh_evaluation* evals, size_t num_evals, Transcript& tr,
+                    const SmallPoly* small = nullptr);
+// variable_base_msm on the host (bucket method, windows over the host pool): the IPA verifier's 2 n + 2^n + 1 terms
+HG1 host_msm(const HFr* scalars, const HG1* bases, size_t n);
+void ipa_verify(const IpaParams&, size_t poly_size, const HG1& comm, const HFr* point, size_t num_vars, const HFr& eval,
+                Transcript& tr);
+void ipa_batch_verify(const IpaParams&, size_t poly_size, size_t num_vars, const HG1* comms, size_t num_comms, const HFr* points,
+                      size_t num_points, const lh_evaluation* evals, size_t num_evals, Transcript& tr);
+
+// pcs::multilinear::hyrax on top of it (hyrax.rs:23-321): a table of 2^num_vars entries as 2^(num_vars - row_num_vars) rows of
+// 2^row_num_vars, one IPA commitment per row; MultilinearHyraxParams = these dimensions + an IpaParams of 2^row_num_vars.
+// A commitment is a VECTOR of num_chunks points, so Hyrax has the PCS surface but no Pcs factory (Pcs is typed on one point).
+struct HyraxDims {
+  size_t num_vars = 0, batch_num_vars = 0, row_num_vars = 0;
+  size_t num_chunks() const { return (size_t)1 << (num_vars - row_num_vars); }
+};
+HyraxDims hyrax_dims(size_t poly_size, size_t batch_size);                        // hyrax.rs:121-127 (asserts: LH_ERR_ARG)
+HyraxDims hyrax_trim(const IpaParams&, size_t poly_size, size_t batch_size);      // hyrax.rs:139-167
+// -> num_polys x num_chunks points, poly-major, rows in order (hyrax.rs:199-220)
+std::vector<HG1> hyrax_batch_commit(Ctx&, const IpaParams&, size_t poly_size, size_t batch_size, const Fr* const* d_polys,
+                                    size_t num_polys, size_t num_vars);
+void hyrax_open(Ctx&, const IpaParams&, size_t poly_size, size_t batch_size, const Fr* d_poly, size_t num_vars, const HFr* point,
+                Transcript& tr);
+void hyrax_batch_open(Ctx&, const IpaParams&, size_t poly_size, size_t batch_size, size_t num_vars, const Fr* const* d_polys,
+                      size_t num_polys, const HFr* points, size_t num_points, const lh_evaluation* evals, size_t num_evals,
+                      Transcript& tr);
+void hyrax_verify(const IpaParams&, size_t poly_size, size_t batch_size, const HG1* comm, const HFr* point, size_t num_vars,
+                  const HFr& eval, Transcript& tr);
+void hyrax_batch_verify(const IpaParams&, size_t poly_size, size_t batch_size, size_t num_vars, const HG1* comms, size_t num_comms,
+                        const HFr* points, size_t num_points, const lh_evaluation* evals, size_t num_evals, Transcript& tr);
+
 // what the provers (Lasso, HyperPlonk and its Lasso lookups) need from their PCS: the PolynomialCommitmentScheme the
 // backend is generic over (backend/hyperplonk.rs:76-95), plus the bases themselves for the small-valued Lasso columns
 struct Pcs {
@@ -430,6 +481,7 @@ struct Pcs {
 Pcs mkzg_pcs(Ctx&, const Srs&);                            // mkzg.cpp
 Pcs zeromorph_pcs(Ctx&, const USrs&, size_t poly_size);    // zeromorph.cpp
 Pcs gemini_pcs(Ctx&, const USrs&, size_t poly_size);       // gemini.cpp
+Pcs ipa_pcs(Ctx&, const IpaParams&, size_t poly_size);     // ipa.cpp (no shard_bases, no precommit)
 
 // ------------------------------------------------------------------ Lasso
 // pieces of the argument shared by the standalone prover (lasso.cpp) and HyperPlonk's Lasso lookups (hyperplonk.cpp)

@@ -129,9 +129,13 @@ void mkzg_verify(const VerifierParams& vp, const HG1& comm, const HFr* point, si
 }
 
 // additive::batch_verify (pcs/multilinear.rs:237-276), generic over the PCS
-static void additive_batch_verify(size_t num_vars, const HG1* comms, size_t num_comms, const HFr* points,
-                                  size_t num_points, const lh_evaluation* evals, size_t num_evals, Transcript& tr,
-                                  const std::function<void(const HG1&, const HFr*, const HFr&)>& verify) {
+// the part every commitment type shares: -> (scalar of every evaluation's commitment, challenges x, g'(x))
+struct AdditiveClaim {
+  std::vector<HFr> scalars, x;
+  HFr eval;
+};
+static AdditiveClaim additive_batch_claim(size_t num_vars, size_t num_comms, const HFr* points, size_t num_points,
+                                          const lh_evaluation* evals, size_t num_evals, Transcript& tr) {
   for (size_t i = 0; i < num_evals; i++)
     LH_REQUIRE(evals[i].poly < num_comms && evals[i].point < num_points, LH_ERR_ARG, "batch verify: bad evaluation");
   size_t ell = 0;
@@ -148,10 +152,33 @@ static void additive_batch_verify(size_t num_vars, const HG1* comms, size_t num_
   const std::vector<HFr>& x = res.second;
   std::vector<HFr> eq_evals(num_points);
   for (size_t j = 0; j < num_points; j++) eq_evals[j] = host_eq_xy_eval(x.data(), points + j * num_vars, num_vars);
+  AdditiveClaim out;
+  out.x = x, out.eval = res.first;
+  for (size_t i = 0; i < num_evals; i++) out.scalars.push_back(eq_evals[evals[i].point] * eq_xt[i]);
+  return out;
+}
+static void additive_batch_verify(size_t num_vars, const HG1* comms, size_t num_comms, const HFr* points,
+                                  size_t num_points, const lh_evaluation* evals, size_t num_evals, Transcript& tr,
+                                  const std::function<void(const HG1&, const HFr*, const HFr&)>& verify) {
+  const AdditiveClaim cl = additive_batch_claim(num_vars, num_comms, points, num_points, evals, num_evals, tr);
   host::G1Xyzz acc = host::G1Xyzz::identity();  // sum_with_scalar (kzg.rs:138-149)
   for (size_t i = 0; i < num_evals; i++)
-    acc = host::g1_add(acc, host::g1_mul(host::g1_from_affine(comms[evals[i].poly]), eq_evals[evals[i].point] * eq_xt[i]));
-  verify(host::g1_to_affine(acc), x.data(), res.first);
+    acc = host::g1_add(acc, host::g1_mul(host::g1_from_affine(comms[evals[i].poly]), cl.scalars[i]));
+  verify(host::g1_to_affine(acc), cl.x.data(), cl.eval);
+}
+// the same over commitments that are vectors of `chunks` points (Hyrax's sum_with_scalar, hyrax.rs:80-107: chunk by chunk)
+static void additive_batch_verify_chunks(size_t num_vars, const HG1* comms, size_t num_comms, size_t chunks, const HFr* points,
+                                         size_t num_points, const lh_evaluation* evals, size_t num_evals, Transcript& tr,
+                                         const std::function<void(const HG1*, const HFr*, const HFr&)>& verify) {
+  const AdditiveClaim cl = additive_batch_claim(num_vars, num_comms, points, num_points, evals, num_evals, tr);
+  std::vector<host::G1Xyzz> acc(chunks, host::G1Xyzz::identity());
+  host_parallel_for(chunks, [&](size_t k) {
+    for (size_t i = 0; i < num_evals; i++)
+      acc[k] = host::g1_add(acc[k], host::g1_mul(host::g1_from_affine(comms[(size_t)evals[i].poly * chunks + k]), cl.scalars[i]));
+  });
+  std::vector<HG1> sum(chunks);
+  host::g1_batch_to_affine(acc.data(), chunks, sum.data());
+  verify(sum.data(), cl.x.data(), cl.eval);
 }
 
 void mkzg_batch_verify(const VerifierParams& vp, size_t num_vars, const HG1* comms, size_t num_comms,
@@ -419,6 +446,122 @@ void gemini_batch_verify(const UkzgVerifierParams& vp, size_t num_vars, const HG
                          size_t num_points, const lh_evaluation* evals, size_t num_evals, Transcript& tr) {
   additive_batch_verify(num_vars, comms, num_comms, points, num_points, evals, num_evals, tr,
                         [&](const HG1& comm, const HFr* x, const HFr& eval) { gemini_verify(vp, comm, x, num_vars, eval, tr); });
+}
+
+// ------------------------------------------------------------------ MultilinearIpa::{verify, batch_verify} (ipa.rs:269-337)
+// variable_base_msm: the bucket method, one window per item of the host pool; only the affine sum is observable
+HG1 host_msm(const HFr* scalars, const HG1* bases, size_t n) {
+  if (!n) return HG1{host::Fq::zero(), host::Fq::zero()};
+  size_t lg = 0;
+  while (((size_t)2 << lg) <= n) lg++;
+  const size_t c = std::min<size_t>(std::max<size_t>(lg > 2 ? lg - 2 : 1, 2), 13), windows = (254 + c - 1) / c;
+  std::vector<uint64_t> canon(4 * n);
+  for (size_t i = 0; i < n; i++) scalars[i].to_canonical(&canon[4 * i]);
+  std::vector<host::G1Xyzz> sums(windows);
+  host_parallel_for(windows, [&](size_t w) {
+    std::vector<host::G1Xyzz> buckets(((size_t)1 << c) - 1, host::G1Xyzz::identity());
+    const size_t bit = w * c;
+    for (size_t i = 0; i < n; i++) {
+      if (bases[i].is_identity()) continue;
+      const uint64_t* k = &canon[4 * i];
+      uint64_t d = k[bit >> 6] >> (bit & 63);
+      if ((bit & 63) + c > 64 && (bit >> 6) < 3) d |= k[(bit >> 6) + 1] << (64 - (bit & 63));
+      d &= ((uint64_t)1 << c) - 1;
+      if (d) buckets[d - 1] = host::g1_add(buckets[d - 1], host::g1_from_affine(bases[i]));
+    }
+    host::G1Xyzz run = host::G1Xyzz::identity(), acc = host::G1Xyzz::identity();
+    for (size_t b = buckets.size(); b-- > 0;) {
+      run = host::g1_add(run, buckets[b]);
+      acc = host::g1_add(acc, run);
+    }
+    sums[w] = acc;
+  });
+  host::G1Xyzz total = host::G1Xyzz::identity();
+  for (size_t w = windows; w-- > 0;) {
+    for (size_t k = 0; k < c; k++) total = host::g1_dbl(total);
+    total = host::g1_add(total, sums[w]);
+  }
+  return host::g1_to_affine(total);
+}
+
+void ipa_verify(const IpaParams& vp, size_t poly_size, const HG1& comm, const HFr* point, size_t num_vars, const HFr& eval,
+                Transcript& tr) {
+  const size_t n = ipa_trim_vars(vp, poly_size);
+  // (h_coeffs has 2^n entries for the PARAM's n and is evaluated at the point: the reference panics on any other length)
+  LH_REQUIRE(num_vars == n, LH_ERR_ARG, "ipa verify: the point must have as many variables as the (trimmed) param");
+  const std::vector<HG1>& g = ipa_host_g(vp);
+  const HFr xi_0 = tr.squeeze_challenge();
+  std::vector<HG1> bases(2 * n);
+  std::vector<HFr> xis(n);
+  for (size_t i = 0; i < n; i++) {
+    bases[i] = tr.read_commitment();
+    bases[n + i] = tr.read_commitment();
+    xis[i] = tr.squeeze_challenge();
+  }
+  const HFr neg_c = -tr.read_field_element();
+  std::vector<HFr> scalars(2 * n);
+  {  // batch_invert (zeros stay zero, as ff's BatchInvert leaves them)
+    std::vector<HFr> pre(n + 1);
+    pre[0] = HFr::one();
+    for (size_t i = 0; i < n; i++) pre[i + 1] = xis[i].is_zero() ? pre[i] : pre[i] * xis[i];
+    HFr inv = pre[n].inv();
+    for (size_t i = n; i-- > 0;) {
+      if (xis[i].is_zero()) {
+        scalars[i] = HFr::zero();
+        continue;
+      }
+      scalars[i] = inv * pre[i];
+      inv = inv * xis[i];
+    }
+  }
+  for (size_t i = 0; i < n; i++) scalars[n + i] = xis[i];
+  // h_coeffs (ipa.rs:319-337)
+  const size_t size = (size_t)1 << n;
+  std::vector<HFr> h(size);
+  h[0] = neg_c;
+  for (size_t i = 0, len = 1; i < n; i++, len <<= 1)
+    for (size_t j = 0; j < len; j++) h[len + j] = h[j] * xis[n - 1 - i];
+  std::vector<HFr> fold(h);  // neg_c_h.evaluate(point) (multilinear.rs:137-156)
+  for (size_t i = 0, len = size >> 1; i < n; i++, len >>= 1)
+    for (size_t j = 0; j < len; j++) fold[j] = fold[2 * j] + point[i] * (fold[2 * j + 1] - fold[2 * j]);
+  const HFr u = xi_0 * (fold[0] + eval);
+  scalars.insert(scalars.end(), h.begin(), h.end());
+  bases.insert(bases.end(), g.begin(), g.begin() + size);
+  scalars.push_back(u);
+  bases.push_back(vp.h);
+  const HG1 sum = host_msm(scalars.data(), bases.data(), scalars.size());
+  if (!host::g1_add(host::g1_from_affine(sum), host::g1_from_affine(comm)).is_identity())
+    throw Error(LH_ERR_INVALID_PCS_OPEN, "Invalid multilinear IPA open");
+}
+void ipa_batch_verify(const IpaParams& vp, size_t poly_size, size_t num_vars, const HG1* comms, size_t num_comms, const HFr* points,
+                      size_t num_points, const lh_evaluation* evals, size_t num_evals, Transcript& tr) {
+  additive_batch_verify(num_vars, comms, num_comms, points, num_points, evals, num_evals, tr, [&](const HG1& comm, const HFr* x, const HFr& eval) {
+    ipa_verify(vp, poly_size, comm, x, num_vars, eval, tr);
+  });
+}
+
+// ------------------------------------------------------------------ MultilinearHyrax::{verify, batch_verify} (hyrax.rs:288-320)
+void hyrax_verify(const IpaParams& vp, size_t poly_size, size_t batch_size, const HG1* comm, const HFr* point, size_t num_vars,
+                  const HFr& eval, Transcript& tr) {
+  const HyraxDims d = hyrax_trim(vp, poly_size, batch_size);
+  LH_REQUIRE(num_vars == d.num_vars, LH_ERR_ARG, "hyrax verify: the point must have as many variables as the (trimmed) param");
+  const size_t chunks = d.num_chunks();
+  HG1 row = comm[0];  // hi empty: the commitment is its single row (hyrax.rs:299-301)
+  if (chunks > 1) {
+    const std::vector<HFr> w = host_eq_xy(std::vector<HFr>(point + d.row_num_vars, point + num_vars));
+    row = host_msm(w.data(), comm, chunks);
+  }
+  ipa_verify(vp, (size_t)1 << d.row_num_vars, row, point, d.row_num_vars, eval, tr);
+}
+void hyrax_batch_verify(const IpaParams& vp, size_t poly_size, size_t batch_size, size_t num_vars, const HG1* comms,
+                        size_t num_comms, const HFr* points, size_t num_points, const lh_evaluation* evals, size_t num_evals,
+                        Transcript& tr) {
+  const HyraxDims d = hyrax_trim(vp, poly_size, batch_size);
+  LH_REQUIRE(num_vars == d.num_vars, LH_ERR_ARG, "hyrax batch verify: num_vars differs from the (trimmed) param's");
+  additive_batch_verify_chunks(num_vars, comms, num_comms, d.num_chunks(), points, num_points, evals, num_evals, tr,
+                               [&](const HG1* comm, const HFr* x, const HFr& eval) {
+                                 hyrax_verify(vp, poly_size, batch_size, comm, x, num_vars, eval, tr);
+                               });
 }
 
 // ------------------------------------------------------------------ expressions on the host

@@ -129,8 +129,10 @@ class HyperPlonkProverParam:
 
 
 def _pcs_of(pcs_pp):
-    """the PolynomialCommitmentScheme a param belongs to: MultilinearKzg, Zeromorph or Gemini (backend/hyperplonk.rs:76-95)"""
-    from . import MultilinearKzg, Zeromorph, ZeromorphProverParam, Gemini, GeminiProverParam
+    """the PolynomialCommitmentScheme a param belongs to: MultilinearKzg, Zeromorph, Gemini or Ipa (backend/hyperplonk.rs:76-95)"""
+    from . import MultilinearKzg, Zeromorph, ZeromorphProverParam, Gemini, GeminiProverParam, Ipa, IpaParam
+    if isinstance(pcs_pp, IpaParam):
+        return Ipa
     if isinstance(pcs_pp, GeminiProverParam):
         return Gemini
     return Zeromorph if isinstance(pcs_pp, ZeromorphProverParam) else MultilinearKzg
@@ -239,10 +241,11 @@ class HyperPlonk:
         prm.num_lasso_lookups, prm.lasso_lookups = len(info.lasso_lookups), lasso_arr
         inst_arrays = [_fr_array(i) for i in instances]
         inst = (C.POINTER(lh_fr) * max(len(instances), 1))(*[C.cast(a, C.POINTER(lh_fr)) for a in inst_arrays])
-        from . import ZeromorphProverParam, GeminiProverParam
+        from . import ZeromorphProverParam, GeminiProverParam, IpaParam
         lib = ctx.lib
-        univariate = isinstance(pp.pcs, (ZeromorphProverParam, GeminiProverParam))  # PCS over the univariate SRS + trim size
-        gemini = isinstance(pp.pcs, GeminiProverParam)
+        # PCS whose param is (params, trim size): over the univariate SRS, or the IPA
+        univariate = isinstance(pp.pcs, (ZeromorphProverParam, GeminiProverParam, IpaParam))
+        gemini, ipa = isinstance(pp.pcs, GeminiProverParam), isinstance(pp.pcs, IpaParam)
         if multi:
             from . import fr_from_bytes
             alive, failure = [], []
@@ -266,7 +269,8 @@ class HyperPlonk:
             nw = (C.c_size_t * max(nph, 1))(*info.num_witness_polys)
             nc = (C.c_size_t * max(nph, 1))(*info.num_challenges)
             if univariate:
-                fn = lib.lh_hyperplonk_prove_phases_gemini if gemini else lib.lh_hyperplonk_prove_phases_zeromorph
+                fn = lib.lh_hyperplonk_prove_phases_ipa if ipa else \
+                    lib.lh_hyperplonk_prove_phases_gemini if gemini else lib.lh_hyperplonk_prove_phases_zeromorph
                 rc = fn(ctx.h, pp.pcs.params.h, pp.pcs.poly_size, C.byref(prm), nph, nw, nc, inst, C.byref(circ), transcript.p)
             else:
                 rc = ctx.lib.lh_hyperplonk_prove_phases(ctx.h, pp.pcs.h, C.byref(prm), nph, nw, nc, inst, C.byref(circ),
@@ -282,7 +286,8 @@ class HyperPlonk:
             _check(ctx.lib.lh_hyperplonk_prove_sharded(ctx.h, pp.pcs.h, C.byref(prm), inst, wit, transcript.p))
             return
         if univariate:
-            fn = lib.lh_hyperplonk_prove_gemini if gemini else lib.lh_hyperplonk_prove_zeromorph
+            fn = lib.lh_hyperplonk_prove_ipa if ipa else \
+                lib.lh_hyperplonk_prove_gemini if gemini else lib.lh_hyperplonk_prove_zeromorph
             _check(fn(ctx.h, pp.pcs.params.h, pp.pcs.poly_size, C.byref(prm), inst, wit, transcript.p))
         else:
             _check(ctx.lib.lh_hyperplonk_prove(ctx.h, pp.pcs.h, C.byref(prm), inst, wit, transcript.p))
@@ -310,18 +315,20 @@ class HyperPlonk:
         prm.num_permutation_polys, prm.permutation_comms = len(vp.permutation_comms), perm
         inst_arrays = [_fr_array(i) for i in instances]
         inst = (C.POINTER(lh_fr) * max(len(instances), 1))(*[C.cast(a, C.POINTER(lh_fr)) for a in inst_arrays])
-        from . import ZeromorphVerifierParam, GeminiVerifierParam
+        from . import ZeromorphVerifierParam, GeminiVerifierParam, IpaParam
         suffix = "_zeromorph" if isinstance(vp.pcs, ZeromorphVerifierParam) else \
-            "_gemini" if isinstance(vp.pcs, GeminiVerifierParam) else ""
+            "_gemini" if isinstance(vp.pcs, GeminiVerifierParam) else "_ipa" if isinstance(vp.pcs, IpaParam) else ""
+        # (the IPA's verifier param is its params and the trim size)
+        pcs_args = (vp.pcs.params.h, vp.pcs.poly_size) if isinstance(vp.pcs, IpaParam) else (vp.pcs.h,)
         if len(info.num_witness_polys) != 1:
             nph = len(info.num_witness_polys)
             nw = (C.c_size_t * max(nph, 1))(*info.num_witness_polys)
             nc = (C.c_size_t * max(nph, 1))(*info.num_challenges)
             fn = getattr(vp.pcs.lib, "lh_hyperplonk_verify_phases" + suffix)
-            _check(fn(vp.pcs.h, C.byref(prm), nph, nw, nc, inst, transcript.p))
+            _check(fn(*pcs_args, C.byref(prm), nph, nw, nc, inst, transcript.p))
             return
         fn = getattr(vp.pcs.lib, "lh_hyperplonk_verify" + suffix)
-        _check(fn(vp.pcs.h, C.byref(prm), inst, transcript.p))
+        _check(fn(*pcs_args, C.byref(prm), inst, transcript.p))
 
 
 # ------------------------------------------------------------------ the reference's sample circuits

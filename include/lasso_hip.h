@@ -700,6 +700,92 @@ lh_status lh_brakedown_batch_verify(const lh_brakedown_param*, size_t num_vars, 
                                     const lh_fr* points, size_t num_points, const lh_evaluation* evals,
                                     size_t num_evals, lh_transcript* t, lh_hash_transcript* ht);
 
+/* ---------------------------------------------------------------- f5: the multilinear IPA (transparent AND additive)
+ * PolynomialCommitmentScheme for MultilinearIpa<bn256::G1Affine> (pcs/multilinear/ipa.rs:23-337): no trusted setup, no
+ * pairing, commitments are G1 points - so additive::batch_open, Lasso and HyperPlonk apply to it as to the KZG family.
+ * The generators are this library's own hash-to-point under the reference's domain and messages (the
+ * reference's hash_to_curve belongs to a curve-library branch whose bytes cannot be pinned).  MultilinearIpaParams is
+ * prover and verifier param at once; `poly_size` is the trim size (ipa.rs:129-145: a prefix of g), a power of two >= 2.
+ * An opening is 128 num_vars + 32 bytes.  An L or R that is the identity (a table whose upper half is zero) cannot cross
+ * a transcript (util/transcript.rs:172-179): LH_ERR_TRANSCRIPT after the bytes written by then, as there; a zero
+ * challenge (the reference unwraps its inverse) is LH_ERR_ARG. */
+typedef struct lh_ipa_param lh_ipa_param; /* MultilinearIpaParams (ipa.rs:25-44) */
+/* setup (ipa.rs:98-127), poly_size a power of two in 2 .. 2^32 (num_vars 0 is LH_ERR_ARG: the reference's verifier
+ * asserts on it).  With a ctx g is derived by a kernel and stays on the device (prover param); ctx NULL: on the host
+ * (verifier param).  A param with device bases derives its host copy on first use by a verifier. */
+lh_status lh_ipa_setup(lh_ctx* ctx, size_t poly_size, lh_ipa_param** out);
+void lh_ipa_param_free(lh_ctx* ctx, lh_ipa_param*); /* ctx may be NULL for a host-only param */
+size_t lh_ipa_param_size(const lh_ipa_param*);      /* 2^num_vars */
+/* MultilinearIpaParams::g / ::h (ipa.rs:37-43): g (size points; a download when they are on the device - ctx needed then)
+ * and h; either may be NULL */
+lh_status lh_ipa_param_download(lh_ctx* ctx, const lh_ipa_param*, lh_g1* g, lh_g1* h);
+/* commit / batch_commit (ipa.rs:147-168); tables of fewer variables than the param are committed against a prefix of g
+ * (= their zero-padded table).  LH_ERR_INVALID_PCS_PARAM "Too many variates to trim" / "Too many variates of poly to .." */
+lh_status lh_ipa_batch_commit(lh_ctx*, const lh_ipa_param*, size_t poly_size, const lh_fr* const* d_polys, size_t num_polys,
+                              size_t num_vars, lh_g1* out_comms);
+/* open (ipa.rs:170-241): num_vars rounds of (L, R), then the last coefficient; num_vars must equal log2(poly_size) */
+lh_status lh_ipa_open(lh_ctx*, const lh_ipa_param*, size_t poly_size, const lh_fr* d_poly, size_t num_vars,
+                      const lh_fr* point, lh_transcript* t);
+/* batch_open (ipa.rs:243-254, additive::batch_open) */
+lh_status lh_ipa_batch_open(lh_ctx*, const lh_ipa_param*, size_t poly_size, size_t num_vars, const lh_fr* const* d_polys,
+                            size_t num_polys, const lh_fr* points, size_t num_points, const lh_evaluation* evals,
+                            size_t num_evals, lh_transcript* t);
+/* verify / batch_verify (ipa.rs:269-316), host only: one MSM of 2 num_vars + 2^num_vars + 1 terms;
+ * LH_ERR_INVALID_PCS_OPEN "Invalid multilinear IPA open" */
+lh_status lh_ipa_verify(const lh_ipa_param*, size_t poly_size, const lh_g1* comm, const lh_fr* point, size_t num_vars,
+                        const lh_fr* eval, lh_transcript* t);
+lh_status lh_ipa_batch_verify(const lh_ipa_param*, size_t poly_size, size_t num_vars, const lh_g1* comms, size_t num_comms,
+                              const lh_fr* points, size_t num_points, const lh_evaluation* evals, size_t num_evals,
+                              lh_transcript* t);
+/* the base fold of an opening's round (ipa.rs:216-222) as a primitive: d_out[j] = d_a[j] + s d_b[j], j < n, affine
+ * (identity = (0,0)); d_out may be d_a */
+lh_status lh_g1_axpy(lh_ctx*, const lh_g1* d_a, const lh_g1* d_b, size_t n, const lh_fr* s, lh_g1* d_out);
+/* MultilinearHyrax<bn256::G1Affine> on top of it (pcs/multilinear/hyrax.rs:23-321): a table of 2^num_vars entries as
+ * num_chunks = 2^(num_vars - row_num_vars) rows of 2^row_num_vars, one IPA commitment per row, with
+ * batch_num_vars = log2(next_pow2(poly_size batch_size)) and row_num_vars = ceil(batch_num_vars / 2).  MultilinearHyraxParams
+ * is those dimensions and an IPA param of 2^row_num_vars: an lh_ipa_param here, with (poly_size, batch_size) as the trim
+ * arguments of every entry.  A commitment is num_chunks points, row 0 first; `comms` arrays are commitment-major.  Polys
+ * must have exactly the (trimmed) param's num_vars.  Hyrax has no Lasso / HyperPlonk entries: their PCS interface is
+ * typed on one point per poly. */
+/* setup (hyrax.rs:121-137): LH_ERR_ARG unless poly_size is a power of two and 0 < batch_size <= poly_size; ctx as lh_ipa_setup */
+lh_status lh_hyrax_setup(lh_ctx* ctx, size_t poly_size, size_t batch_size, lh_ipa_param** out);
+/* the dimensions setup and trim derive (hyrax.rs:125-127); outputs may be NULL */
+lh_status lh_hyrax_dims(size_t poly_size, size_t batch_size, size_t* num_vars, size_t* batch_num_vars, size_t* row_num_vars);
+/* trim (hyrax.rs:139-167): LH_ERR_INVALID_PCS_PARAM "Too many variates to trim" when the param's rows are too short */
+lh_status lh_hyrax_trim(const lh_ipa_param*, size_t poly_size, size_t batch_size, size_t* row_num_vars, size_t* num_chunks);
+/* commit / batch_commit (hyrax.rs:169-221): every row of every poly is a job of one batched MSM; out_comms: num_polys x
+ * num_chunks points */
+lh_status lh_hyrax_batch_commit(lh_ctx*, const lh_ipa_param*, size_t poly_size, size_t batch_size, const lh_fr* const* d_polys,
+                                size_t num_polys, size_t num_vars, lh_g1* out_comms);
+/* open (hyrax.rs:224-258): the row combination sum_r eq(hi)[r] row_r in one pass, then the IPA opening of it at lo */
+lh_status lh_hyrax_open(lh_ctx*, const lh_ipa_param*, size_t poly_size, size_t batch_size, const lh_fr* d_poly, size_t num_vars,
+                        const lh_fr* point, lh_transcript* t);
+/* batch_open (hyrax.rs:260-271, additive::batch_open) */
+lh_status lh_hyrax_batch_open(lh_ctx*, const lh_ipa_param*, size_t poly_size, size_t batch_size, size_t num_vars,
+                              const lh_fr* const* d_polys, size_t num_polys, const lh_fr* points, size_t num_points,
+                              const lh_evaluation* evals, size_t num_evals, lh_transcript* t);
+/* verify / batch_verify (hyrax.rs:288-320), host only: the MSM of the row commitments by eq(hi), then the IPA's verify;
+ * batch_verify sums the vector commitments chunk by chunk (sum_with_scalar, hyrax.rs:80-107) */
+lh_status lh_hyrax_verify(const lh_ipa_param*, size_t poly_size, size_t batch_size, const lh_g1* comm, const lh_fr* point,
+                          size_t num_vars, const lh_fr* eval, lh_transcript* t);
+lh_status lh_hyrax_batch_verify(const lh_ipa_param*, size_t poly_size, size_t batch_size, size_t num_vars, const lh_g1* comms,
+                                size_t num_comms, const lh_fr* points, size_t num_points, const lh_evaluation* evals,
+                                size_t num_evals, lh_transcript* t);
+/* Lasso and HyperPlonk<MultilinearIpa<bn256::G1Affine>> (backend/hyperplonk.rs:76-95): arguments as the _gemini entries */
+lh_status lh_lasso_prove_ipa(lh_ctx*, const lh_ipa_param*, size_t poly_size, const lh_lasso_table*, size_t num_vars,
+                             const uint32_t* const* d_dims, lh_transcript* t);
+lh_status lh_lasso_verify_ipa(const lh_ipa_param*, size_t poly_size, const lh_lasso_table*, size_t num_vars, lh_transcript* t);
+lh_status lh_hyperplonk_prove_ipa(lh_ctx*, const lh_ipa_param*, size_t poly_size, const lh_hp_param*,
+                                  const lh_fr* const* instances, const lh_fr* const* d_witness_polys, lh_transcript* t);
+lh_status lh_hyperplonk_verify_ipa(const lh_ipa_param*, size_t poly_size, const lh_hp_vparam*, const lh_fr* const* instances,
+                                   lh_transcript* t);
+lh_status lh_hyperplonk_prove_phases_ipa(lh_ctx*, const lh_ipa_param*, size_t poly_size, const lh_hp_param*, size_t num_phases,
+                                         const size_t* num_witness_polys, const size_t* num_challenges,
+                                         const lh_fr* const* instances, const lh_hp_circuit* circuit, lh_transcript* t);
+lh_status lh_hyperplonk_verify_phases_ipa(const lh_ipa_param*, size_t poly_size, const lh_hp_vparam*, size_t num_phases,
+                                          const size_t* num_witness_polys, const size_t* num_challenges,
+                                          const lh_fr* const* instances, lh_transcript* t);
+
 /* development / tests: the HIP source the runtime compiler (csrc/jit.cpp) is given for a register program - words
  * {op | dst << 4 | a.kind << 8 | b.kind << 10, a.idx | b.idx << 16} with op ADD 0, SUB 1, MUL 2, NEG 3, MOV 4 and operand
  * kinds register 0, table 1, constant 2 (csrc/dev.hpp PROG_*).  Host code only (no GPU needed): tests/test_jit_source.py
