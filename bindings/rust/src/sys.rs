@@ -82,6 +82,13 @@ pub struct lh_expr_node { pub op: u32, pub a: i32, pub b: i32, pub reserved: u32
 #[repr(C)] #[derive(Clone, Copy)]
 pub struct lh_expr { pub nodes: *const lh_expr_node, pub num_nodes: usize }
 
+// (development) one stable sort of lh_debug_sort_pairs: keys u32 or u64 by key_bytes, d_vals_in null = positions
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct lh_debug_sort_slab {
+    pub d_keys_in: *const c_void, pub d_keys_out: *mut c_void, pub d_vals_in: *const u32, pub d_vals_out: *mut u32,
+    pub n: usize, pub bits: u32, pub first_bit: u32,
+}
+
 #[repr(C)] #[derive(Clone, Copy)]
 pub struct lh_evaluation { pub poly: u32, pub point: u32, pub value: Fr }
 
@@ -292,6 +299,13 @@ extern "C" {
     // (development) the source text of a runtime-compiled round kernel
     pub fn lh_debug_jit_source(code: *const u32, num_instrs: usize, num_regs: u32, result_reg: u32, degree: i32,
                                out: *mut core::ffi::c_char, cap: usize, len: *mut usize) -> lh_status;
+    // (development) the radix sort and the Lasso access counters on their own; lh_debug_sort_plan is host only
+    pub fn lh_debug_sort_pairs(ctx: *mut lh_ctx, key_bytes: i32, slabs: *const lh_debug_sort_slab, count: usize) -> lh_status;
+    pub fn lh_debug_lasso_counters(ctx: *mut lh_ctx, d_dims: *const *const u32, num_cols: usize, n: usize, m: usize,
+                                   d_read_ts: *const *mut u32, d_final_cts: *const *mut u32,
+                                   d_keep_sorted: *const *mut u32, d_keep_index: *const *mut u32) -> lh_status;
+    pub fn lh_debug_sort_plan(n: usize, bits: u32, key_bytes: i32, passes: *mut u32, rb: *mut u32,
+                              temp_bytes: *mut usize) -> lh_status;
     // Zeromorph over univariate KZG: lh_ukzg_setup, lh_usrs_*, lh_zeromorph_* follow the same shapes
     // (include/lasso_hip.h, section f3) and are bound the same way when HyperPlonk<Zeromorph<..>> is wanted.
     // Univariate KZG on its own and Gemini over it (include/lasso_hip.h, section f3b); lh_usrs / lh_ukzg_vp are opaque here

@@ -104,6 +104,11 @@ class lh_comm(C.Structure):
                 ("all_gather_device", _AGD_CB)]
 
 
+class lh_debug_sort_slab(C.Structure):  # (development: lh_debug_sort_pairs)
+    _fields_ = [("d_keys_in", C.c_void_p), ("d_keys_out", C.c_void_p), ("d_vals_in", C.c_void_p), ("d_vals_out", C.c_void_p),
+                ("n", C.c_size_t), ("bits", C.c_uint32), ("first_bit", C.c_uint32)]
+
+
 class lh_prof_rec(C.Structure):
     _fields_ = [("name", C.c_char * 40), ("ms", C.c_double), ("bytes", C.c_double), ("muls", C.c_double),
                 ("items", C.c_double)]
@@ -328,6 +333,10 @@ SIGNATURES = {
                                                   C.POINTER(C.POINTER(lh_fr)), C.POINTER(lh_transcript)]),
     "lh_debug_jit_source": (C.c_int, [C.POINTER(C.c_uint32), _SZ, C.c_uint32, C.c_uint32, C.c_int, C.c_char_p, _SZ,
                                       C.POINTER(_SZ)]),
+    "lh_debug_sort_pairs": (C.c_int, [_P, C.c_int, C.POINTER(lh_debug_sort_slab), _SZ]),
+    "lh_debug_lasso_counters": (C.c_int, [_P, C.POINTER(_P), _SZ, _SZ, _SZ, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P),
+                                          C.POINTER(_P)]),
+    "lh_debug_sort_plan": (C.c_int, [_SZ, C.c_uint, C.c_int, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(_SZ)]),
     "lh_keccak_transcript_hash_io": (C.c_int, [C.POINTER(lh_transcript), C.POINTER(lh_hash_transcript)]),
     "lh_brakedown_setup": (C.c_int, [_P, _SZ, C.c_int, C.c_char_p, C.POINTER(_P)]),
     "lh_brakedown_derive": (C.c_int, [_SZ, C.c_int, C.POINTER(_P)]),

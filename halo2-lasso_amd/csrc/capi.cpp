@@ -1820,6 +1820,63 @@ lh_status lh_debug_jit_source(const uint32_t* code, size_t num_instrs, uint32_t 
   LH_CATCH
 }
 
+// (development) the radix sort and the Lasso access counters on their own: tests/test_gpu_sort.py
+lh_status lh_debug_sort_pairs(lh_ctx* ctx, int key_bytes, const lh_debug_sort_slab* slabs, size_t count) {
+  LH_TRY NEED_CTX(ctx);
+  NEED_N(slabs, count);
+  LH_REQUIRE(key_bytes == 4 || key_bytes == 8, LH_ERR_ARG, "debug sort: key_bytes is 4 or 8");
+  LH_REQUIRE(key_bytes == 4 || count == 1, LH_ERR_ARG, "debug sort: u64 keys sort one slab per call");
+  // (a shift by the key width or more is undefined in the kernels: refused here, before anything is launched)
+  for (size_t i = 0; i < count; i++) {
+    const lh_debug_sort_slab& s = slabs[i];
+    LH_REQUIRE(s.bits >= 1 && s.bits <= 8u * key_bytes && s.first_bit <= 8u * key_bytes - s.bits, LH_ERR_ARG,
+               "debug sort: the sorted bits [first_bit, first_bit + bits) must be a non-empty range inside the key");
+    LH_REQUIRE(key_bytes == 4 || s.first_bit == 0, LH_ERR_ARG, "debug sort: u64 keys sort from bit 0");
+    LH_REQUIRE(s.n == 0 || (s.d_keys_in && s.d_keys_out && s.d_vals_out), LH_ERR_ARG, "null argument: sort slab buffers");
+    LH_REQUIRE(s.n < ((size_t)1 << 32), LH_ERR_ARG, "debug sort: too many pairs");
+  }
+  ArenaScope scope(ctx->c.arena);
+  if (key_bytes == 4) {
+    std::vector<SortSlab> v(count);
+    for (size_t i = 0; i < count; i++)
+      v[i] = SortSlab{(const uint32_t*)slabs[i].d_keys_in, (uint32_t*)slabs[i].d_keys_out, slabs[i].d_vals_in,
+                      slabs[i].d_vals_out, slabs[i].n, slabs[i].bits, slabs[i].first_bit};
+    sort_pairs_u32_batched(ctx->c, v.data(), count);
+  } else {
+    sort_pairs_u64(ctx->c, (const uint64_t*)slabs[0].d_keys_in, (uint64_t*)slabs[0].d_keys_out, slabs[0].d_vals_in,
+                   slabs[0].d_vals_out, slabs[0].n, slabs[0].bits);
+  }
+  ctx->c.sync();
+  LH_CATCH
+}
+lh_status lh_debug_lasso_counters(lh_ctx* ctx, const uint32_t* const* d_dims, size_t num_cols, size_t n, size_t m,
+                                  uint32_t* const* d_read_ts, uint32_t* const* d_final_cts, uint32_t* const* d_keep_sorted,
+                                  uint32_t* const* d_keep_index) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(d_dims);
+  NEED(d_read_ts);
+  NEED(d_final_cts);
+  LH_REQUIRE(num_cols >= 1 && num_cols <= (size_t)LH_LASSO_MAX_CHUNKS, LH_ERR_ARG, "debug counters: bad column count");
+  LH_REQUIRE(m >= 1 && m <= ((size_t)1 << 32) && n < ((size_t)1 << 32), LH_ERR_ARG, "debug counters: bad shape");
+  for (size_t j = 0; j < num_cols; j++) {
+    LH_REQUIRE(d_final_cts[j] && (n == 0 || (d_dims[j] && d_read_ts[j])), LH_ERR_ARG, "null argument: counter columns");
+    LH_REQUIRE(n == 0 || ((!d_keep_sorted || d_keep_sorted[j]) && (!d_keep_index || d_keep_index[j])), LH_ERR_ARG,
+               "null argument: keep_sorted / keep_index column");
+  }
+  k_lasso_counters(ctx->c, d_dims, num_cols, n, m, d_read_ts, d_final_cts, d_keep_sorted, d_keep_index);
+  ctx->c.sync();
+  LH_CATCH
+}
+lh_status lh_debug_sort_plan(size_t n, unsigned bits, int key_bytes, unsigned* passes, unsigned rb[8], size_t* temp_bytes) {
+  LH_TRY
+  NEED(passes);
+  NEED(rb);
+  NEED(temp_bytes);
+  LH_REQUIRE(key_bytes == 4 || key_bytes == 8, LH_ERR_ARG, "debug sort: key_bytes is 4 or 8");
+  sort_plan(n, bits, (size_t)key_bytes, passes, rb, temp_bytes);
+  LH_CATCH
+}
+
 lh_status lh_profile_enable(lh_ctx* ctx, int on) {
   LH_TRY NEED_CTX(ctx);
   ctx->c.sync();

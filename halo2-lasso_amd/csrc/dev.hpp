@@ -852,13 +852,18 @@ struct SortSlab {
   unsigned bits;
   unsigned first_bit = 0;
 };
-// (vals_in == nullptr: the values are the positions 0 .. n - 1; the sort is by the key bits [first_bit, first_bit + bits))
+// (vals_in == nullptr: the values are the positions 0 .. n - 1; the sort is by the key bits [first_bit, first_bit + bits),
+// which must end inside the key: LH_ERR_ARG otherwise; `bits` above the key width count as the key width)
 void sort_pairs_u32(Ctx&, const uint32_t* keys_in, uint32_t* keys_out, const uint32_t* vals_in, uint32_t* vals_out, size_t n,
                     unsigned bits, unsigned first_bit = 0);
 // `count` independent sorts as ONE launch set per radix pass (temporary storage from the arena: the caller's ArenaScope)
 void sort_pairs_u32_batched(Ctx&, const SortSlab* slabs, size_t count);
+// (by the low `bits` bits of a u64 key; every caller today passes 64)
 void sort_pairs_u64(Ctx&, const uint64_t* keys_in, uint64_t* keys_out, const uint32_t* vals_in, uint32_t* vals_out, size_t n,
                     unsigned bits);
+// the plan of one slab (host only; lh_debug_sort_plan): passes, the digit width of every pass (rb[passes .. 8) = 0) and the
+// arena bytes the sort takes
+void sort_plan(size_t n, unsigned bits, size_t key_bytes, unsigned* passes, unsigned rb[8], size_t* temp_bytes);
 
 // ------------------------------------------------------------------ MSM (msm.hip)
 struct MsmJob {

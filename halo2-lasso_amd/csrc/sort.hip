@@ -12,8 +12,9 @@
 // 20 B per pair and pass (4 B histogram read, 8 B in, 8 B out) against onesweep's 16 B + a shared 4 B; 2^24 pairs with
 // 16-bit keys: 0.27 ms against 0.31 ms for the library (MI355X), identical (stable) order.  Key widths that are not a
 // multiple of 8 are split evenly (17 bits: 6 + 6 + 5), which shrinks the ranking tables and lengthens the runs.
-// Keys are u32 or u64 (the sharded access counters sort a 37-45-bit (address, global index) key); a batch of independent
-// sorts - the (job, window) slabs of an MSM batch - runs as ONE launch set per pass.
+// Keys are u32 or u64 (any width up to the key's is sorted; the one u64 caller today, LogUp's sort-merge join in
+// kernels_plonk.hip, sorts all 64 bits); a batch of independent sorts - the (job, window) slabs of an MSM batch - runs as
+// ONE launch set per pass.  tests/test_gpu_sort.py runs the sort on its own through lh_debug_sort_pairs.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdlib>
@@ -305,7 +306,7 @@ size_t rs_batch_bytes(const RsJob* slabs, size_t count, size_t key_bytes) {
   return bytes;
 }
 template <class K>
-void rs_sort_batch(Ctx& c, const RsJob* slabs, size_t count, void* temp) {
+void rs_sort_batch(Ctx& c, const RsJob* slabs, size_t count, void* temp, size_t temp_bytes) {
   const int side = 0;  // (one pinned descriptor staging per ctx)
   const size_t key_bytes = sizeof(K);
   hipStream_t stream = c.stream;
@@ -317,6 +318,9 @@ void rs_sort_batch(Ctx& c, const RsJob* slabs, size_t count, void* temp) {
   for (size_t i = 0; i < count; i++) {
     if (!slabs[i].n) continue;
     const RsPlan p = rs_plan(slabs[i].n, slabs[i].bits, key_bytes);
+    unsigned sorted_bits = 0;
+    for (unsigned k = 0; k < p.passes; k++) sorted_bits += p.rb[k];
+    LH_REQUIRE(slabs[i].first_bit + sorted_bits <= 8 * key_bytes, LH_ERR_ARG, "sort: the sorted bits end above the key");
     LH_REQUIRE(p.ntiles < ((size_t)1 << 31) && (size_t)tiles + p.ntiles < ((size_t)1 << 31), LH_ERR_ARG, "sort: too many pairs");
     RsSlab s;
     s.kin = slabs[i].keys_in, s.vin = slabs[i].vals_in, s.kout = slabs[i].keys_out, s.vout = slabs[i].vals_out;
@@ -331,6 +335,8 @@ void rs_sort_batch(Ctx& c, const RsJob* slabs, size_t count, void* temp) {
     max_passes = std::max(max_passes, p.passes);
     host.push_back(s);
   }
+  // (rs_batch_bytes and the carving above account for the space separately)
+  LH_REQUIRE((size_t)(cur - (char*)temp) <= temp_bytes, LH_ERR_ARG, "sort: the slabs' temporaries overrun rs_batch_bytes");
   if (host.empty()) return;
   // (the descriptors go up through a pinned staging buffer of their own - Ctx::pin holds round messages and MSM tables that
   // may still be in flight; an async copy out of pageable memory would pin pages on the fly)
@@ -368,24 +374,35 @@ void sort_pairs_u32_batched(Ctx& c, const SortSlab* slabs, size_t count) {
   std::vector<RsJob> jobs(count);
   for (size_t i = 0; i < count; i++)
     jobs[i] = RsJob{slabs[i].keys_in, slabs[i].keys_out, slabs[i].vals_in, slabs[i].vals_out, slabs[i].n, slabs[i].bits, slabs[i].first_bit};
-  void* temp = c.arena.alloc(rs_batch_bytes(jobs.data(), count, 4));  // caller's ArenaScope releases it
-  rs_sort_batch<uint32_t>(c, jobs.data(), count, temp);
+  const size_t bytes = rs_batch_bytes(jobs.data(), count, 4);
+  void* temp = c.arena.alloc(bytes);  // caller's ArenaScope releases it
+  rs_sort_batch<uint32_t>(c, jobs.data(), count, temp, bytes);
 }
 
 void sort_pairs_u32(Ctx& c, const uint32_t* keys_in, uint32_t* keys_out, const uint32_t* vals_in, uint32_t* vals_out,
                     size_t n, unsigned bits, unsigned first_bit) {
   RsJob one{keys_in, keys_out, vals_in, vals_out, n, bits};
   one.first_bit = first_bit;
-  void* temp = c.arena.alloc(rs_batch_bytes(&one, 1, 4));  // caller's ArenaScope releases it
-  rs_sort_batch<uint32_t>(c, &one, 1, temp);
+  const size_t bytes = rs_batch_bytes(&one, 1, 4);
+  void* temp = c.arena.alloc(bytes);  // caller's ArenaScope releases it
+  rs_sort_batch<uint32_t>(c, &one, 1, temp, bytes);
 }
 
-// 64-bit keys (the sharded access counters sort (address, global lookup index) on the address owner: 37-45 bits)
+// 64-bit keys, sorted by their low `bits` bits (LogUp's sort-merge join: 64)
 void sort_pairs_u64(Ctx& c, const uint64_t* keys_in, uint64_t* keys_out, const uint32_t* vals_in, uint32_t* vals_out,
                     size_t n, unsigned bits) {
   const RsJob one{keys_in, keys_out, vals_in, vals_out, n, bits};
-  void* temp = c.arena.alloc(rs_batch_bytes(&one, 1, 8));
-  rs_sort_batch<uint64_t>(c, &one, 1, temp);
+  const size_t bytes = rs_batch_bytes(&one, 1, 8);
+  void* temp = c.arena.alloc(bytes);
+  rs_sort_batch<uint64_t>(c, &one, 1, temp, bytes);
+}
+
+void sort_plan(size_t n, unsigned bits, size_t key_bytes, unsigned* passes, unsigned rb[8], size_t* temp_bytes) {
+  const RsPlan p = rs_plan(n, bits, key_bytes);
+  *passes = p.passes;
+  for (int k = 0; k < 8; k++) rb[k] = p.rb[k];
+  const RsJob one{nullptr, nullptr, nullptr, nullptr, n, bits};
+  *temp_bytes = rs_batch_bytes(&one, 1, key_bytes);
 }
 
 }  // namespace lh

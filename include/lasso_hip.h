@@ -793,6 +793,31 @@ lh_status lh_hyperplonk_verify_phases_ipa(const lh_ipa_param*, size_t poly_size,
 lh_status lh_debug_jit_source(const uint32_t* code, size_t num_instrs, uint32_t num_regs, uint32_t result_reg, int degree,
                               char* out, size_t cap, size_t* len);
 
+/* development / tests: the device radix sort (csrc/sort.hip) and the Lasso access counters on their own, for
+ * tests/test_gpu_sort.py.  A slab is one stable sort of n (key, u32 value) pairs by the key bits [first_bit, first_bit +
+ * bits): whole keys are carried along, inputs are preserved, d_vals_in == NULL means values = positions 0 .. n - 1.
+ * key_bytes 4: `count` slabs as one batch (one launch set per radix pass).  key_bytes 8: count == 1 and first_bit == 0.
+ * Refused with LH_ERR_ARG before anything is launched: another key_bytes, bits == 0, first_bit + bits > 8 key_bytes, a
+ * null pointer with n > 0.  Temporary storage comes from the ctx's arena; the call returns after the sorts have finished. */
+typedef struct lh_debug_sort_slab {
+  const void* d_keys_in;
+  void* d_keys_out;
+  const uint32_t* d_vals_in;
+  uint32_t* d_vals_out;
+  size_t n;
+  uint32_t bits, first_bit;
+} lh_debug_sort_slab;
+lh_status lh_debug_sort_pairs(lh_ctx*, int key_bytes, const lh_debug_sort_slab* slabs, size_t count);
+/* num_cols columns of n addresses below m: d_read_ts[c][i] = earlier accesses of d_dims[c][i] in column c (n entries),
+ * d_final_cts[c][a] = accesses of a (m entries); d_keep_sorted / d_keep_index (both or either may be NULL, else one pointer
+ * per column): the column in ascending (stable) order and the positions it came from.  An address >= m: LH_ERR_ARG. */
+lh_status lh_debug_lasso_counters(lh_ctx*, const uint32_t* const* d_dims, size_t num_cols, size_t n, size_t m,
+                                  uint32_t* const* d_read_ts, uint32_t* const* d_final_cts, uint32_t* const* d_keep_sorted,
+                                  uint32_t* const* d_keep_index);
+/* the pass plan of one slab (host only, no GPU needed): the number of radix passes, the digit width of each (rb[passes ..
+ * 8) = 0; `bits` above the key width count as the key width) and the temporary device bytes the sort takes */
+lh_status lh_debug_sort_plan(size_t n, unsigned bits, int key_bytes, unsigned* passes, unsigned rb[8], size_t* temp_bytes);
+
 /* ---------------------------------------------------------------- measurement (bench.py)
  * Per-kernel HIP-event timing on the ctx stream.  While enabled every instrumented launch is
  * synchronised, so whole-prove wall time is NOT representative; use a separate pass. */
