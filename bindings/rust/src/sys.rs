@@ -363,6 +363,26 @@ extern "C" {
                                num_evals: usize, t: *mut lh_transcript) -> lh_status;
     pub fn lh_g1_axpy(ctx: *mut lh_ctx, d_a: *const G1Affine, d_b: *const G1Affine, n: usize, s: *const Fr,
                       d_out: *mut G1Affine) -> lh_status;
+    pub fn lh_g1_rows_msm(ctx: *mut lh_ctx, d_scalars: *const c_void, scalars_u32: c_int, bits: u32, n: usize, row_len: usize,
+                          d_bases: *const G1Affine, out_rows: *mut G1Affine) -> lh_status;
+    pub fn lh_lasso_prove_hyrax(ctx: *mut lh_ctx, param: *const c_void, poly_size: usize, batch_size: usize,
+                                table: *const lh_lasso_table, num_vars: usize, d_dims: *const *const u32,
+                                t: *mut lh_transcript) -> lh_status;
+    pub fn lh_lasso_verify_hyrax(param: *const c_void, poly_size: usize, batch_size: usize, table: *const lh_lasso_table,
+                                 num_vars: usize, t: *mut lh_transcript) -> lh_status;
+    pub fn lh_hyperplonk_prove_hyrax(ctx: *mut lh_ctx, param: *const c_void, poly_size: usize, batch_size: usize,
+                                     pp: *const lh_hp_param, instances: *const *const Fr, d_witness_polys: *const *const Fr,
+                                     t: *mut lh_transcript) -> lh_status;
+    pub fn lh_hyperplonk_verify_hyrax(param: *const c_void, poly_size: usize, batch_size: usize, hvp: *const lh_hp_vparam,
+                                      instances: *const *const Fr, t: *mut lh_transcript) -> lh_status;
+    pub fn lh_hyperplonk_prove_phases_hyrax(ctx: *mut lh_ctx, param: *const c_void, poly_size: usize, batch_size: usize,
+                                            pp: *const lh_hp_param, num_phases: usize, num_witness_polys: *const usize,
+                                            num_challenges: *const usize, instances: *const *const Fr,
+                                            circuit: *const lh_hp_circuit, t: *mut lh_transcript) -> lh_status;
+    pub fn lh_hyperplonk_verify_phases_hyrax(param: *const c_void, poly_size: usize, batch_size: usize,
+                                             hvp: *const lh_hp_vparam, num_phases: usize, num_witness_polys: *const usize,
+                                             num_challenges: *const usize, instances: *const *const Fr,
+                                             t: *mut lh_transcript) -> lh_status;
     pub fn lh_lasso_prove_ipa(ctx: *mut lh_ctx, param: *const c_void, poly_size: usize, table: *const lh_lasso_table,
                               num_vars: usize, d_dims: *const *const u32, t: *mut lh_transcript) -> lh_status;
     pub fn lh_lasso_verify_ipa(param: *const c_void, poly_size: usize, table: *const lh_lasso_table, num_vars: usize,

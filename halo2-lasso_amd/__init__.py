@@ -716,7 +716,9 @@ def sum_check_verify(prover, num_vars, degree, sum_, transcript):
 def lasso_verify(vp, table, num_vars, transcript):
     """Verifier of the Lasso argument (oracle/pyref/lasso.py:219-261).  A Keccak256Transcript must be fully consumed."""
     t = table.to_c()
-    if isinstance(vp, IpaParam):
+    if isinstance(vp, HyraxParam):
+        _check(vp.lib.lh_lasso_verify_hyrax(vp.params.h, vp.poly_size, vp.batch_size, C.byref(t), num_vars, transcript.p))
+    elif isinstance(vp, IpaParam):
         _check(vp.lib.lh_lasso_verify_ipa(vp.params.h, vp.poly_size, C.byref(t), num_vars, transcript.p))
     else:
         fn = vp.lib.lh_lasso_verify_zeromorph if isinstance(vp, ZeromorphVerifierParam) else \
@@ -1240,6 +1242,18 @@ class Hyrax:
         return [pts[i * k:(i + 1) * k] for i in range(len(polys))]
 
     @staticmethod
+    def rows_msm(ctx, scalars_buf, n, row_len, bases_buf, u32=False, bits=0):
+        """the row commitments as a primitive: [sum_c s[r row_len + c] bases[c]] for the ceil(n / row_len) rows of a device
+        array of n scalars (Fr, or u32 values below 2^bits), against row_len device points (None = identity)"""
+        if row_len < 1:
+            raise ArgumentError("row_len must be at least 1")
+        rows = (n + row_len - 1) // row_len
+        out = (lh_g1 * max(rows, 1))()
+        _check(ctx.lib.lh_g1_rows_msm(ctx.h, scalars_buf.ptr, 1 if u32 else 0, bits, n, row_len, bases_buf.ptr, out))
+        raw = C.string_at(out, 64 * rows)
+        return [g1_from_bytes(raw[64 * i:64 * i + 64]) for i in range(rows)]
+
+    @staticmethod
     def commit(pp, poly):
         return Hyrax.batch_commit(pp, [poly])[0]
 
@@ -1478,6 +1492,10 @@ def lasso_prove(pp, table, num_vars, dims, transcript):
             or len(table.g_terms) > _ffi.LH_LASSO_MAX_TERMS:
         raise ArgumentError("table too large")
     t = table.to_c()
+    if isinstance(pp, HyraxParam):
+        _check(pp.ctx.lib.lh_lasso_prove_hyrax(pp.ctx.h, pp.params.h, pp.poly_size, pp.batch_size, C.byref(t), num_vars,
+                                               _ptr_array(dims), transcript.p))
+        return
     if isinstance(pp, (ZeromorphProverParam, GeminiProverParam, IpaParam)):
         fn = pp.ctx.lib.lh_lasso_prove_ipa if isinstance(pp, IpaParam) else \
             pp.ctx.lib.lh_lasso_prove_gemini if isinstance(pp, GeminiProverParam) else pp.ctx.lib.lh_lasso_prove_zeromorph

@@ -308,6 +308,10 @@ SIGNATURES = {
     "lh_ipa_batch_verify": (C.c_int, [_P, _SZ, _SZ, C.POINTER(lh_g1), _SZ, C.POINTER(lh_fr), _SZ,
                                       C.POINTER(lh_evaluation), _SZ, C.POINTER(lh_transcript)]),
     "lh_g1_axpy": (C.c_int, [_P, _P, _P, _SZ, C.POINTER(lh_fr), _P]),
+    "lh_lasso_prove_hyrax": (C.c_int, [_P, _P, _SZ, _SZ, C.POINTER(lh_lasso_table), _SZ, C.POINTER(_P),
+                                       C.POINTER(lh_transcript)]),
+    "lh_lasso_verify_hyrax": (C.c_int, [_P, _SZ, _SZ, C.POINTER(lh_lasso_table), _SZ, C.POINTER(lh_transcript)]),
+    "lh_g1_rows_msm": (C.c_int, [_P, _P, C.c_int, C.c_uint32, _SZ, _SZ, _P, C.POINTER(lh_g1)]),
     "lh_hyrax_setup": (C.c_int, [_P, _SZ, _SZ, C.POINTER(_P)]),
     "lh_hyrax_dims": (C.c_int, [_SZ, _SZ, C.POINTER(_SZ), C.POINTER(_SZ), C.POINTER(_SZ)]),
     "lh_hyrax_trim": (C.c_int, [_P, _SZ, _SZ, C.POINTER(_SZ), C.POINTER(_SZ)]),
@@ -324,12 +328,21 @@ SIGNATURES = {
     "lh_lasso_verify_ipa": (C.c_int, [_P, _SZ, C.POINTER(lh_lasso_table), _SZ, C.POINTER(lh_transcript)]),
     "lh_hyperplonk_prove_ipa": (C.c_int, [_P, _P, _SZ, C.POINTER(lh_hp_param), C.POINTER(C.POINTER(lh_fr)),
                                           C.POINTER(_P), C.POINTER(lh_transcript)]),
+    "lh_hyperplonk_prove_hyrax": (C.c_int, [_P, _P, _SZ, _SZ, C.POINTER(lh_hp_param), C.POINTER(C.POINTER(lh_fr)),
+                                          C.POINTER(_P), C.POINTER(lh_transcript)]),
     "lh_hyperplonk_verify_ipa": (C.c_int, [_P, _SZ, C.POINTER(lh_hp_vparam), C.POINTER(C.POINTER(lh_fr)),
+                                           C.POINTER(lh_transcript)]),
+    "lh_hyperplonk_verify_hyrax": (C.c_int, [_P, _SZ, _SZ, C.POINTER(lh_hp_vparam), C.POINTER(C.POINTER(lh_fr)),
                                            C.POINTER(lh_transcript)]),
     "lh_hyperplonk_prove_phases_ipa": (C.c_int, [_P, _P, _SZ, C.POINTER(lh_hp_param), _SZ, C.POINTER(_SZ),
                                                  C.POINTER(_SZ), C.POINTER(C.POINTER(lh_fr)),
                                                  C.POINTER(lh_hp_circuit), C.POINTER(lh_transcript)]),
+    "lh_hyperplonk_prove_phases_hyrax": (C.c_int, [_P, _P, _SZ, _SZ, C.POINTER(lh_hp_param), _SZ, C.POINTER(_SZ),
+                                                 C.POINTER(_SZ), C.POINTER(C.POINTER(lh_fr)),
+                                                 C.POINTER(lh_hp_circuit), C.POINTER(lh_transcript)]),
     "lh_hyperplonk_verify_phases_ipa": (C.c_int, [_P, _SZ, C.POINTER(lh_hp_vparam), _SZ, C.POINTER(_SZ), C.POINTER(_SZ),
+                                                  C.POINTER(C.POINTER(lh_fr)), C.POINTER(lh_transcript)]),
+    "lh_hyperplonk_verify_phases_hyrax": (C.c_int, [_P, _SZ, _SZ, C.POINTER(lh_hp_vparam), _SZ, C.POINTER(_SZ), C.POINTER(_SZ),
                                                   C.POINTER(C.POINTER(lh_fr)), C.POINTER(lh_transcript)]),
     "lh_debug_jit_source": (C.c_int, [C.POINTER(C.c_uint32), _SZ, C.c_uint32, C.c_uint32, C.c_int, C.c_char_p, _SZ,
                                       C.POINTER(_SZ)]),

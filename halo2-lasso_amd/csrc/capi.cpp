@@ -1645,6 +1645,16 @@ lh_status lh_g1_axpy(lh_ctx* ctx, const lh_g1* d_a, const lh_g1* d_b, size_t n, 
   ctx->c.sync();
   LH_CATCH
 }
+lh_status lh_g1_rows_msm(lh_ctx* ctx, const void* d_scalars, int scalars_u32, uint32_t bits, size_t n, size_t row_len,
+                         const lh_g1* d_bases, lh_g1* out_rows) {
+  LH_TRY NEED_CTX(ctx);
+  if (row_len == 0) throw Error(LH_ERR_ARG, "rows msm: row_len must be at least 1");
+  NEED_N(d_scalars, n);
+  NEED_N(d_bases, n);
+  NEED_N(out_rows, n);
+  k_g1_rows_msm(ctx->c, d_scalars, scalars_u32 != 0, bits, n, row_len, (const G1Affine*)d_bases, nullptr, 0, 0, (G1Affine*)out_rows);
+  LH_CATCH
+}
 // ---------------------------------------------------------------- Hyrax on top of the IPA
 lh_status lh_hyrax_setup(lh_ctx* ctx, size_t poly_size, size_t batch_size, lh_ipa_param** out) {
   LH_TRY
@@ -1738,6 +1748,102 @@ lh_status lh_hyrax_batch_verify(const lh_ipa_param* param, size_t poly_size, siz
 static PcsBatchVerify ipa_verifier(const IpaParams& pcs, size_t poly_size) {
   return [&pcs, poly_size](size_t nv, const HG1* comms, size_t nc, const HFr* points, size_t np, const lh_evaluation* evals,
                            size_t ne, Transcript& t2) { ipa_batch_verify(pcs, poly_size, nv, comms, nc, points, np, evals, ne, t2); };
+}
+// Hyrax commits only tables of exactly the param's num_vars (hyrax.rs groups rows by the param's count)
+static void hyrax_lasso_vars(const IpaParams& p, size_t poly_size, size_t batch_size, const lh_lasso_table& tb, size_t num_vars) {
+  const HyraxDims d = hyrax_trim(p, poly_size, batch_size);
+  LH_REQUIRE(std::max<size_t>(num_vars, tb.chunk_bits) == d.num_vars, LH_ERR_ARG,
+             "lasso over hyrax: max(num_vars, chunk_bits) must equal log2(poly_size) (Hyrax commits only tables of the param's size)");
+}
+lh_status lh_lasso_prove_hyrax(lh_ctx* ctx, const lh_ipa_param* param, size_t poly_size, size_t batch_size,
+                               const lh_lasso_table* table, size_t num_vars, const uint32_t* const* d_dims, lh_transcript* t) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(param);
+  NEED(table);
+  NEED(d_dims);
+  Transcript tr(t);
+  hyrax_lasso_vars(*param->p, poly_size, batch_size, *table, num_vars);
+  lasso_prove(ctx->c, hyrax_pcs(ctx->c, *param->p, poly_size, batch_size), *table, num_vars, d_dims, tr);
+  LH_CATCH
+}
+lh_status lh_lasso_verify_hyrax(const lh_ipa_param* param, size_t poly_size, size_t batch_size, const lh_lasso_table* table,
+                                size_t num_vars, lh_transcript* t) {
+  LH_TRY
+  NEED(param);
+  NEED(table);
+  Transcript tr(t);
+  hyrax_lasso_vars(*param->p, poly_size, batch_size, *table, num_vars);
+  const IpaParams& pcs = *param->p;
+  const PcsBatchVerify bv = [&pcs, poly_size, batch_size](size_t nv, const HG1* comms, size_t nc, const HFr* points, size_t np,
+                                                           const lh_evaluation* evals, size_t ne, Transcript& t2) {
+    hyrax_batch_verify(pcs, poly_size, batch_size, nv, comms, nc, points, np, evals, ne, t2);
+  };
+  lasso_verify(bv, *table, num_vars, tr, hyrax_trim(pcs, poly_size, batch_size).num_chunks());
+  LH_CATCH
+}
+static PcsBatchVerify hyrax_verifier(const IpaParams& pcs, size_t poly_size, size_t batch_size) {
+  return [&pcs, poly_size, batch_size](size_t nv, const HG1* comms, size_t nc, const HFr* points, size_t np, const lh_evaluation* evals,
+                                       size_t ne, Transcript& t2) {
+    hyrax_batch_verify(pcs, poly_size, batch_size, nv, comms, nc, points, np, evals, ne, t2);
+  };
+}
+// Hyrax commits only polys of exactly the param's num_vars: the circuit's k
+static size_t hyrax_hp_chunks(const IpaParams& p, size_t poly_size, size_t batch_size, size_t num_vars) {
+  const HyraxDims d = hyrax_trim(p, poly_size, batch_size);
+  LH_REQUIRE(num_vars == d.num_vars, LH_ERR_ARG,
+             "hyperplonk over hyrax: the circuit's num_vars must equal log2(poly_size) (Hyrax commits only tables of the param's size)");
+  return d.num_chunks();
+}
+lh_status lh_hyperplonk_prove_hyrax(lh_ctx* ctx, const lh_ipa_param* param, size_t poly_size, size_t batch_size,
+                                    const lh_hp_param* pp, const lh_fr* const* instances, const lh_fr* const* d_witness_polys,
+                                    lh_transcript* t) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(param);
+  NEED(pp);
+  NEED_N(d_witness_polys, pp->num_witness_polys);
+  Transcript tr(t);
+  hyrax_hp_chunks(*param->p, poly_size, batch_size, pp->num_vars);
+  hyperplonk_prove(ctx->c, hyrax_pcs(ctx->c, *param->p, poly_size, batch_size), *pp, (const HFr* const*)instances,
+                   (const Fr* const*)d_witness_polys, tr);
+  LH_CATCH
+}
+lh_status lh_hyperplonk_verify_hyrax(const lh_ipa_param* param, size_t poly_size, size_t batch_size, const lh_hp_vparam* hvp,
+                                     const lh_fr* const* instances, lh_transcript* t) {
+  LH_TRY
+  NEED(param);
+  NEED(hvp);
+  Transcript tr(t);
+  const size_t chunks = hyrax_hp_chunks(*param->p, poly_size, batch_size, hvp->num_vars);
+  hyperplonk_verify(hyrax_verifier(*param->p, poly_size, batch_size), *hvp, (const HFr* const*)instances, tr, chunks);
+  LH_CATCH
+}
+lh_status lh_hyperplonk_prove_phases_hyrax(lh_ctx* ctx, const lh_ipa_param* param, size_t poly_size, size_t batch_size,
+                                           const lh_hp_param* pp, size_t num_phases, const size_t* num_witness_polys,
+                                           const size_t* num_challenges, const lh_fr* const* instances,
+                                           const lh_hp_circuit* circuit, lh_transcript* t) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(param);
+  NEED(pp);
+  NEED(circuit);
+  Transcript tr(t);
+  hyrax_hp_chunks(*param->p, poly_size, batch_size, pp->num_vars);
+  const HpPhases ph = hp_phases_of(pp, num_phases, num_witness_polys, num_challenges, circuit);
+  hyperplonk_prove_phases(ctx->c, hyrax_pcs(ctx->c, *param->p, poly_size, batch_size), *pp, ph, (const HFr* const*)instances, tr);
+  LH_CATCH
+}
+lh_status lh_hyperplonk_verify_phases_hyrax(const lh_ipa_param* param, size_t poly_size, size_t batch_size, const lh_hp_vparam* hvp,
+                                            size_t num_phases, const size_t* num_witness_polys, const size_t* num_challenges,
+                                            const lh_fr* const* instances, lh_transcript* t) {
+  LH_TRY
+  NEED(param);
+  NEED(hvp);
+  LH_REQUIRE(num_phases == 0 || (num_witness_polys && num_challenges), LH_ERR_ARG, "null argument: phases");
+  Transcript tr(t);
+  const size_t chunks = hyrax_hp_chunks(*param->p, poly_size, batch_size, hvp->num_vars);
+  hyperplonk_verify_phases(hyrax_verifier(*param->p, poly_size, batch_size), *hvp,
+                           std::vector<size_t>(num_witness_polys, num_witness_polys + num_phases),
+                           std::vector<size_t>(num_challenges, num_challenges + num_phases), (const HFr* const*)instances, tr, chunks);
+  LH_CATCH
 }
 lh_status lh_lasso_prove_ipa(lh_ctx* ctx, const lh_ipa_param* param, size_t poly_size, const lh_lasso_table* table,
                              size_t num_vars, const uint32_t* const* d_dims, lh_transcript* t) {

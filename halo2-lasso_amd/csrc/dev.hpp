@@ -149,6 +149,9 @@ struct Options {
                                        // r on the host, no kernel behind the collective); 2 = the same all-reduce into
                                        // device memory followed by a copy to the host (should a fabric refuse host memory
                                        // as a receive buffer).  Same proof bytes; unmeasured on more than one GPU.
+  int64_t hyrax_rows = 1;              // Hyrax commits every row of every poly with the row kernels (kernels_hyrax.hip: one bucket
+                                       // set per row over the generators' window table, no host wait between rows); 0: one
+                                       // msm_batch job per row
   Options();                           // environment defaults (dev.cpp)
   int64_t* find(const char* name);
   static bool in_range(const char* name, int64_t value);  // the range lh_ctx_set_option accepts
@@ -840,6 +843,26 @@ void k_ipa_fold_fr(Ctx&, const Fr* coeffs, const Fr* zs, size_t mid, const Fr& x
 // Hyrax's row combination (fix_last_vars, hyrax.rs:243): out[c] = sum_r w[r] poly[r row_len + c], c < row_len, r < rows;
 // w on the device; temporary storage from the arena
 void k_hyrax_combine(Ctx&, const Fr* poly, const Fr* w, size_t rows, size_t row_len, Fr* out);
+
+// ------------------------------------------------------------------ Hyrax's row commitments (kernels_hyrax.hip)
+// out_host[r] = sum_{c < row_len} s[r row_len + c] bases[c], r < ceil(n / row_len): the rows of a flat array of n scalars, Fr
+// (Montgomery) or u32 with every value < 2^bits (bits in 1..32); a partial last row is padded with zeros; affine, the identity
+// as (0, 0).  win_table: the window table of `bases` (k_msm_window_table over row_len points, cbits = 8, W >= the windows the
+// column needs: g1_rows_msm_windows) or null - then a temporary one is built in the arena.  Synchronises.
+void k_g1_rows_msm(Ctx&, const void* scalars, bool u32, uint32_t bits, size_t n, size_t row_len, const G1Affine* bases,
+                   const G1Affine* win_table, uint32_t cbits, uint32_t W, G1Affine* out_host);
+// the same for a batch of columns over the same bases in one launch set: column i gives rows_per_col points at
+// out_host[i rows_per_col ..]; the rows beyond its n entries launch no work and come out as identities
+struct RowsMsmCol {
+  const void* scalars;
+  bool u32;
+  uint32_t bits;
+  size_t n;
+};
+void k_g1_rows_msm_batch(Ctx&, const RowsMsmCol* cols, size_t num_cols, size_t rows_per_col, size_t row_len, const G1Affine* bases,
+                         const G1Affine* win_table, uint32_t cbits, uint32_t W, G1Affine* out_host);
+uint32_t g1_rows_msm_windows(bool u32, uint32_t bits);  // 8-bit windows of a column: 32 for Fr, ceil(bits / 8) for u32
+size_t g1_rows_msm_segment(bool u32);                   // columns of a row one workgroup takes: 256 for Fr, 2048 for u32
 
 // ------------------------------------------------------------------ radix sort (sort.hip)
 // stable sort of (u32 key, u32 value) pairs by the low `bits` bits of the key; inputs are preserved

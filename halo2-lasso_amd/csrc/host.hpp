@@ -417,11 +417,15 @@ struct IpaParams {
   HG1 h;
   mutable std::vector<HG1> host_g;  // through ipa_host_g
   mutable std::mutex mu;
+  // window tables of prefixes of g for the row kernels (dev.hpp k_g1_rows_msm): key = row_len, entry w row_len + i =
+  // 2^(8 w) g[i], w < 32; built on first use (ipa.cpp ipa_rows_table), freed with the param
+  mutable std::map<size_t, G1Affine*> rows_tables;
 };
 HG1 ipa_hash_to_point(const uint8_t* message, size_t len);
 IpaParams* ipa_setup(Ctx* c, size_t poly_size);             // c null: host only
 void ipa_free(IpaParams*);
 const std::vector<HG1>& ipa_host_g(const IpaParams&);
+const G1Affine* ipa_rows_table(Ctx&, const IpaParams&, size_t row_len);  // the window table of g[0 .. row_len) (ipa.cpp)
 size_t ipa_trim_vars(const IpaParams&, size_t poly_size);   // ipa.rs:129-145 -> num_vars of the trimmed param
 std::vector<HG1> ipa_batch_commit(Ctx&, const IpaParams&, size_t poly_size, const Fr* const* d_polys, size_t num_polys,
                                   size_t num_vars);
@@ -438,7 +442,7 @@ void ipa_batch_verify(const IpaParams&, size_t poly_size, size_t num_vars, const
 
 // pcs::multilinear::hyrax on top of it (hyrax.rs:23-321): a table of 2^num_vars entries as 2^(num_vars - row_num_vars) rows of
 // 2^row_num_vars, one IPA commitment per row; MultilinearHyraxParams = these dimensions + an IpaParams of 2^row_num_vars.
-// A commitment is a VECTOR of num_chunks points, so Hyrax has the PCS surface but no Pcs factory (Pcs is typed on one point).
+// A commitment is a VECTOR of num_chunks points: Pcs::chunks (hyrax_pcs below).
 struct HyraxDims {
   size_t num_vars = 0, batch_num_vars = 0, row_num_vars = 0;
   size_t num_chunks() const { return (size_t)1 << (num_vars - row_num_vars); }
@@ -452,7 +456,7 @@ void hyrax_open(Ctx&, const IpaParams&, size_t poly_size, size_t batch_size, con
                 Transcript& tr);
 void hyrax_batch_open(Ctx&, const IpaParams&, size_t poly_size, size_t batch_size, size_t num_vars, const Fr* const* d_polys,
                       size_t num_polys, const HFr* points, size_t num_points, const lh_evaluation* evals, size_t num_evals,
-                      Transcript& tr);
+                      Transcript& tr, const SmallPoly* small = nullptr);
 void hyrax_verify(const IpaParams&, size_t poly_size, size_t batch_size, const HG1* comm, const HFr* point, size_t num_vars,
                   const HFr& eval, Transcript& tr);
 void hyrax_batch_verify(const IpaParams&, size_t poly_size, size_t batch_size, size_t num_vars, const HG1* comms, size_t num_comms,
@@ -460,8 +464,21 @@ void hyrax_batch_verify(const IpaParams&, size_t poly_size, size_t batch_size, s
 
 // what the provers (Lasso, HyperPlonk and its Lasso lookups) need from their PCS: the PolynomialCommitmentScheme the
 // backend is generic over (backend/hyperplonk.rs:76-95), plus the bases themselves for the small-valued Lasso columns
+// a column for Pcs::commit_columns: `len` <= 2^nv entries, Fr (Montgomery) or u32 with every value < 2^known_bits (1..32),
+// committed as the table zero-padded to nv variables
+struct PcsColumn {
+  const void* data;
+  bool u32;
+  size_t len;
+  uint32_t known_bits;
+};
 struct Pcs {
+  // points per commitment (Hyrax: its num_chunks row commitments); batch_commit returns num_polys * chunks points,
+  // poly-major, rows in order - what the scheme's batch_commit_and_write writes
+  size_t chunks = 1;
   std::function<std::vector<HG1>(const Fr* const* d_polys, size_t num_polys, size_t num_vars)> batch_commit;
+  // optional (schemes without commit_bases: Hyrax): commits (small-valued) columns directly -> num_cols * chunks points
+  std::function<std::vector<HG1>(const PcsColumn* cols, size_t num_cols, size_t nv)> commit_columns;
   // bases whose first 2^nv points commit a zero-padded table of 2^nv entries (the eq basis of level nv, or the powers of
   // s): the small-valued Lasso columns are committed as u32 MSMs against them.  nv <= max_vars is the caller's check
   // (LH_ERR_INVALID_PCS_PARAM, "Too many variates of poly to commit")
@@ -482,6 +499,9 @@ Pcs mkzg_pcs(Ctx&, const Srs&);                            // mkzg.cpp
 Pcs zeromorph_pcs(Ctx&, const USrs&, size_t poly_size);    // zeromorph.cpp
 Pcs gemini_pcs(Ctx&, const USrs&, size_t poly_size);       // gemini.cpp
 Pcs ipa_pcs(Ctx&, const IpaParams&, size_t poly_size);     // ipa.cpp (no shard_bases, no precommit)
+// ipa.cpp: commitments of num_chunks points, commit_columns instead of commit_bases; commits only polys of exactly
+// log2(poly_size) variables (LH_ERR_ARG otherwise)
+Pcs hyrax_pcs(Ctx&, const IpaParams&, size_t poly_size, size_t batch_size);
 
 // ------------------------------------------------------------------ Lasso
 // pieces of the argument shared by the standalone prover (lasso.cpp) and HyperPlonk's Lasso lookups (hyperplonk.cpp)
@@ -536,9 +556,10 @@ LassoClaims lasso_argue(Ctx&, const lh_lasso_table&, size_t n, const LassoColumn
                         const Fr* a, const Fr* const* E_fr, Transcript& tr,
                         const std::function<void(int)>& lap = nullptr, const uint32_t* a_small = nullptr,
                         const std::function<void()>& trees_built = nullptr);
-// commitment framing of the Lasso argument: identity mask as one field element, then the non-identity commitments
-void lasso_write_commitments(Transcript& tr, const std::vector<HG1>& comms);
-std::vector<HG1> lasso_read_commitments(Transcript& tr, size_t count);
+// commitment framing of the Lasso argument: identity masks (one field element per 63 points of the count * chunks points,
+// flattened commitment-major), then the non-identity points
+void lasso_write_commitments(Transcript& tr, const std::vector<HG1>& comms, size_t chunks = 1);
+std::vector<HG1> lasso_read_commitments(Transcript& tr, size_t count, size_t chunks = 1);
 void lasso_prove(Ctx&, const Pcs&, const lh_lasso_table& table, size_t num_vars, const uint32_t* const* d_dims,
                  Transcript& tr);
 void lasso_prove_sharded(Ctx&, const Srs&, const lh_lasso_table& table, size_t num_vars,
@@ -561,14 +582,17 @@ void mkzg_batch_verify(const VerifierParams&, size_t num_vars, const HG1* comms,
 // -> (final claim, challenges)
 std::pair<HFr, std::vector<HFr>> sum_check_verify(int prover_kind, size_t num_vars, size_t degree, const HFr& sum,
                                                   Transcript& tr);
-void lasso_verify(const PcsBatchVerify& batch_verify, const lh_lasso_table& table, size_t num_vars, Transcript& tr);
+// chunks: points per commitment (the batch_verify then gets count commitments of `chunks` points each, commitment-major)
+void lasso_verify(const PcsBatchVerify& batch_verify, const lh_lasso_table& table, size_t num_vars, Transcript& tr,
+                  size_t chunks = 1);
 // the verifier's side of lasso_argue: Surge and memory-checking identities; claims left to check against commitments
 LassoClaims lasso_check(const lh_lasso_table& table, size_t num_vars, Transcript& tr);
+// chunks: points per commitment (vp's preprocess_comms / permutation_comms then hold that many per poly, poly-major)
 void hyperplonk_verify(const PcsBatchVerify& batch_verify, const lh_hp_vparam& vp, const HFr* const* instances,
-                       Transcript& tr);
+                       Transcript& tr, size_t chunks = 1);
 void hyperplonk_verify_phases(const PcsBatchVerify& batch_verify, const lh_hp_vparam& vp,
                               const std::vector<size_t>& num_witness_polys, const std::vector<size_t>& num_challenges,
-                              const HFr* const* instances, Transcript& tr);
+                              const HFr* const* instances, Transcript& tr, size_t chunks = 1);
 
 // ------------------------------------------------------------------ HyperPlonk (hyperplonk.cpp)
 void hyperplonk_prove(Ctx&, const Pcs&, const lh_hp_param& pp, const HFr* const* instances,

@@ -227,6 +227,7 @@ void hyperplonk_prove_phases(Ctx& c, const Pcs& pcs, const lh_hp_param& pp, cons
   };
   std::vector<LassoState> lasso(pp.num_lasso_lookups);
   std::vector<MsmJob> lasso_jobs;  // the Lasso columns' commitments (u32 MSMs), filled by lasso_prepare
+  std::vector<PcsColumn> lasso_cols;  // the same columns for a Pcs::commit_columns scheme
   auto lasso_prepare = [&] {
     if (!pp.num_lasso_lookups) return;
     LH_REQUIRE(pp.lasso_lookups != nullptr, LH_ERR_ARG, "hyperplonk: lasso_lookups is null");
@@ -239,8 +240,10 @@ void hyperplonk_prove_phases(Ctx& c, const Pcs& pcs, const lh_hp_param& pp, cons
                  "hyperplonk: the Lasso lookups of one circuit commit to more than 63 polys (sum of 2 * chunks + memories)");
     }
     LH_REQUIRE(nv <= pcs.max_vars, LH_ERR_INVALID_PCS_PARAM, "Too many variates of poly to commit");
-    const G1Affine* bases = shn ? pcs.shard_bases(nv) : pcs.commit_bases(nv);
-    const G1Affine* bases_full = pcs.commit_bases(nv);
+    // (a scheme that commits columns itself - Pcs::commit_columns, Hyrax - gets them as lasso_cols instead of MSM jobs)
+    const bool by_cols = (bool)pcs.commit_columns;
+    const G1Affine* bases = by_cols ? nullptr : shn ? pcs.shard_bases(nv) : pcs.commit_bases(nv);
+    const G1Affine* bases_full = by_cols ? nullptr : pcs.commit_bases(nv);
     std::vector<MsmJob>& jobs = lasso_jobs;
     uint32_t bad_input = 0;        // sharded: a rank that finds an invalid lookup must not leave its peers in a collective
     for (size_t k = 0; k < pp.num_lasso_lookups; k++) {
@@ -298,6 +301,14 @@ void hyperplonk_prove_phases(Ctx& c, const Pcs& pcs, const lh_hp_param& pp, cons
           const size_t first = sh.rank << sh.j;
           st.fcs_fr.push_back(first < M ? fr_view(st.cols.fcs[j] + first, std::min(M - first, (size_t)1 << sh.j)) : fr_view(st.cols.fcs[j], 0));
         }
+      }
+      if (by_cols) {
+        for (size_t j = 0; j < cc; j++) lasso_cols.push_back(PcsColumn{st.cols.rts[j], true, n_loc, 32});
+        for (size_t i = 0; i < alpha; i++)
+          lasso_cols.push_back(PcsColumn{st.cols.E[i], true, n_loc,
+                                         (uint32_t)(tb.memory_subtable[i] == LH_SUBTABLE_IDENTITY ? l : std::max<size_t>(l / 2, 1))});
+        for (size_t j = 0; j < cc; j++) lasso_cols.push_back(PcsColumn{st.cols.fcs[j], true, M, 32});
+        continue;
       }
       for (size_t j = 0; j < cc; j++) jobs.push_back(MsmJob{st.cols.rts[j], true, bases, n_loc});
       for (size_t i = 0; i < alpha; i++) jobs.push_back(MsmJob{st.cols.E[i], true, bases, n_loc});
@@ -371,11 +382,15 @@ void hyperplonk_prove_phases(Ctx& c, const Pcs& pcs, const lh_hp_param& pp, cons
   if (pp.num_lasso_lookups) {
     if (!lasso_committed) {
       lasso_prepare();
-      lasso_comms.resize(lasso_jobs.size());
-      msm_batch(c, lasso_jobs.data(), lasso_jobs.size(), (G1Affine*)lasso_comms.data());
-      if (shn) comm_sum_points(c, lasso_comms.data(), lasso_comms.size());  // the ranks' partial commitments -> their sums
+      if (pcs.commit_columns) {
+        lasso_comms = pcs.commit_columns(lasso_cols.data(), lasso_cols.size(), nv);
+      } else {
+        lasso_comms.resize(lasso_jobs.size());
+        msm_batch(c, lasso_jobs.data(), lasso_jobs.size(), (G1Affine*)lasso_comms.data());
+        if (shn) comm_sum_points(c, lasso_comms.data(), lasso_comms.size());  // the ranks' partial commitments -> their sums
+      }
     }
-    lasso_write_commitments(tr, lasso_comms);
+    lasso_write_commitments(tr, lasso_comms, pcs.chunks);
   }
 
   pt.lap("lookup compressed + m + commit");

@@ -125,6 +125,7 @@ void ipa_free(IpaParams* p) {
   if (p->d_g) {
     OnDevice on(p->device);
     (void)hipFree(p->d_g);
+    for (auto& kv : p->rows_tables) (void)hipFree(kv.second);
   }
   delete p;
 }
@@ -251,7 +252,35 @@ HyraxDims hyrax_trim(const IpaParams& p, size_t poly_size, size_t batch_size) {
   return d;
 }
 
-// every row of every poly is a job of ONE msm_batch over g (msm_batch itself plans 48 jobs at a time: its existing behaviour)
+// the window table of g[0 .. row_len) the row kernels file their terms from (dev.hpp k_g1_rows_msm): 32 windows of 8 bits,
+// row_len * 2 KiB - 8 MiB at the 4096 columns of a 2^24-entry table; built on first use by the ctx that asks, kept on the param.
+// One entry per distinct row_len (i.e. per trim / batch size used with the param), never evicted before ipa_free: a handful of
+// tables of a few MiB today.  The param's mutex is held while a table is built (a hipMalloc, one kernel, a sync): a second
+// caller needs that very table, and nothing else of the param is touched while a commit runs.
+constexpr uint32_t HYRAX_ROWS_CBITS = 8, HYRAX_ROWS_W = 32;
+const G1Affine* ipa_rows_table(Ctx& c, const IpaParams& p, size_t row_len) {
+  const G1Affine* g = device_g(p);
+  // (the table is built by this ctx's stream and lives beside g: both on the param's device)
+  LH_REQUIRE(c.device == p.device, LH_ERR_ARG, "hyrax commit: the ctx and the param's bases are on different devices");
+  OnDevice on(p.device);
+  std::lock_guard<std::mutex> lk(p.mu);
+  auto it = p.rows_tables.find(row_len);
+  if (it != p.rows_tables.end()) return it->second;
+  G1Affine* t = nullptr;
+  LH_HIP(hipMalloc((void**)&t, row_len * HYRAX_ROWS_W * sizeof(G1Affine)));
+  try {
+    k_msm_window_table(c, g, row_len, HYRAX_ROWS_CBITS, HYRAX_ROWS_W, t);
+    c.sync();
+  } catch (...) {
+    (void)hipFree(t);
+    throw;
+  }
+  p.rows_tables[row_len] = t;
+  return t;
+}
+
+// Options::hyrax_rows 1: every row of every poly in ONE call of the row kernels (kernels_hyrax.hip); 0: every row a job of
+// ONE msm_batch over g (msm_batch itself plans 48 jobs at a time).  The same points either way.
 std::vector<HG1> hyrax_batch_commit(Ctx& c, const IpaParams& p, size_t poly_size, size_t batch_size, const Fr* const* d_polys,
                                     size_t num_polys, size_t num_vars) {
   const HyraxDims d = hyrax_trim(p, poly_size, batch_size);
@@ -262,6 +291,13 @@ std::vector<HG1> hyrax_batch_commit(Ctx& c, const IpaParams& p, size_t poly_size
   std::vector<HG1> out(num_polys * chunks);
   if (!num_polys) return out;
   const G1Affine* g = device_g(p);
+  if (c.opt.hyrax_rows) {
+    std::vector<RowsMsmCol> cols(num_polys);
+    for (size_t i = 0; i < num_polys; i++) cols[i] = RowsMsmCol{d_polys[i], false, 0, chunks * row_len};
+    k_g1_rows_msm_batch(c, cols.data(), num_polys, chunks, row_len, g, ipa_rows_table(c, p, row_len), HYRAX_ROWS_CBITS, HYRAX_ROWS_W,
+                        (G1Affine*)out.data());
+    return out;
+  }
   std::vector<MsmJob> jobs;
   jobs.reserve(out.size());
   for (size_t i = 0; i < num_polys; i++)
@@ -293,11 +329,60 @@ void hyrax_open(Ctx& c, const IpaParams& p, size_t poly_size, size_t batch_size,
 
 void hyrax_batch_open(Ctx& c, const IpaParams& p, size_t poly_size, size_t batch_size, size_t num_vars, const Fr* const* d_polys,
                       size_t num_polys, const HFr* points, size_t num_points, const lh_evaluation* evals, size_t num_evals,
-                      Transcript& tr) {
+                      Transcript& tr, const SmallPoly* small) {
   const HyraxDims d = hyrax_trim(p, poly_size, batch_size);
   check_vars(d.num_vars, num_vars, "open");
-  additive_batch_open(c, num_vars, d_polys, num_polys, points, num_points, evals, num_evals, tr,
-                      [&](const Fr* g_prime, const HFr* point) { hyrax_open(c, p, poly_size, batch_size, g_prime, num_vars, point, tr); });
+  additive_batch_open(
+      c, num_vars, d_polys, num_polys, points, num_points, evals, num_evals, tr,
+      [&](const Fr* g_prime, const HFr* point) { hyrax_open(c, p, poly_size, batch_size, g_prime, num_vars, point, tr); }, small);
+}
+
+// columns of at most 2^num_vars entries, zero-padded: rows beyond a column's length are identities and cost nothing
+static std::vector<HG1> hyrax_commit_columns(Ctx& c, const IpaParams& p, const HyraxDims& d, const PcsColumn* cols, size_t num_cols,
+                                             size_t nv) {
+  LH_REQUIRE(nv == d.num_vars, LH_ERR_ARG, "hyrax commit: the poly must have as many variables as the (trimmed) param");
+  const size_t chunks = d.num_chunks(), row_len = (size_t)1 << d.row_num_vars;
+  std::vector<HG1> out(num_cols * chunks, HG1{host::Fq::zero(), host::Fq::zero()});
+  if (!num_cols) return out;
+  const G1Affine* g = device_g(p);
+  for (size_t i = 0; i < num_cols; i++) LH_REQUIRE(cols[i].len <= chunks * row_len, LH_ERR_ARG, "hyrax commit: a column is longer than the table");
+  if (c.opt.hyrax_rows) {
+    std::vector<RowsMsmCol> rc(num_cols);
+    for (size_t i = 0; i < num_cols; i++) rc[i] = RowsMsmCol{cols[i].data, cols[i].u32, cols[i].known_bits, cols[i].len};
+    k_g1_rows_msm_batch(c, rc.data(), num_cols, chunks, row_len, g, ipa_rows_table(c, p, row_len), HYRAX_ROWS_CBITS, HYRAX_ROWS_W,
+                        (G1Affine*)out.data());
+    return out;
+  }
+  std::vector<MsmJob> jobs;
+  std::vector<size_t> slot;
+  for (size_t i = 0; i < num_cols; i++)
+    for (size_t r = 0; r * row_len < cols[i].len; r++) {
+      const size_t first = r * row_len;
+      MsmJob jb{(const char*)cols[i].data + first * (cols[i].u32 ? 4 : 32), cols[i].u32, g, std::min(row_len, cols[i].len - first)};
+      jb.known_bits = cols[i].u32 ? cols[i].known_bits : 0;
+      jobs.push_back(jb), slot.push_back(i * chunks + r);
+    }
+  std::vector<HG1> part(jobs.size());
+  if (!jobs.empty()) msm_batch(c, jobs.data(), jobs.size(), (G1Affine*)part.data());
+  for (size_t k = 0; k < jobs.size(); k++) out[slot[k]] = part[k];
+  return out;
+}
+
+Pcs hyrax_pcs(Ctx& c, const IpaParams& p, size_t poly_size, size_t batch_size) {
+  const HyraxDims d = hyrax_trim(p, poly_size, batch_size);
+  device_g(p);
+  Pcs pcs;
+  pcs.max_vars = d.num_vars;
+  pcs.chunks = d.num_chunks();
+  pcs.batch_commit = [&c, &p, poly_size, batch_size](const Fr* const* polys, size_t np, size_t nv) {
+    return hyrax_batch_commit(c, p, poly_size, batch_size, polys, np, nv);
+  };
+  pcs.commit_columns = [&c, &p, d](const PcsColumn* cols, size_t nc, size_t nv) { return hyrax_commit_columns(c, p, d, cols, nc, nv); };
+  pcs.batch_open = [&c, &p, poly_size, batch_size](size_t nv, const Fr* const* polys, size_t np, const HFr* points, size_t npts,
+                                                   const lh_evaluation* evals, size_t ne, Transcript& tr, const SmallPoly* small) {
+    hyrax_batch_open(c, p, poly_size, batch_size, nv, polys, np, points, npts, evals, ne, tr, small);
+  };
+  return pcs;
 }
 
 }  // namespace lh

@@ -17,26 +17,38 @@ static double now_ms() {
 // all below 2^16, read_ts when the indices are pairwise distinct - and the reference's transcript cannot encode the
 // identity (util/transcript.rs:172-179,216-219).  So: ONE field element whose bit i says that commitment i is the
 // identity, then the other commitments in order; only calls every TranscriptWrite / TranscriptRead offers.
-void lasso_write_commitments(Transcript& tr, const std::vector<HG1>& comms) {
-  LH_REQUIRE(comms.size() < 64, LH_ERR_ARG, "lasso: too many commitments for the identity mask");
-  uint64_t mask = 0;
-  for (size_t i = 0; i < comms.size(); i++)
-    if (comms[i].is_identity()) mask |= (uint64_t)1 << i;
-  tr.write_field_element(HFr::from_u64(mask));
+// Commitments of `chunks` points (Pcs::chunks, Hyrax's rows): the count * chunks points are flattened commitment-major
+// and framed by ceil(total / 63) mask elements written FIRST, mask k covering the positions 63 k .. 63 k + 62 - for
+// chunks = 1 (count <= 63) exactly the one-mask framing above.
+void lasso_write_commitments(Transcript& tr, const std::vector<HG1>& comms, size_t chunks) {
+  LH_REQUIRE(chunks >= 1 && comms.size() % chunks == 0 && comms.size() / chunks < 64, LH_ERR_ARG,
+             "lasso: too many commitments for the identity mask");
+  for (size_t k = 0; 63 * k < comms.size(); k++) {
+    uint64_t mask = 0;
+    for (size_t i = 0; i < 63 && 63 * k + i < comms.size(); i++)
+      if (comms[63 * k + i].is_identity()) mask |= (uint64_t)1 << i;
+    tr.write_field_element(HFr::from_u64(mask));
+  }
   for (const HG1& cm : comms)
     if (!cm.is_identity()) tr.write_commitment(cm);
 }
 
-std::vector<HG1> lasso_read_commitments(Transcript& tr, size_t count) {
-  LH_REQUIRE(count < 64, LH_ERR_ARG, "lasso: too many commitments for the identity mask");
-  const HFr m = tr.read_field_element();
-  uint64_t canon[4];
-  m.to_canonical(canon);
-  if (canon[1] || canon[2] || canon[3] || (canon[0] >> count))
-    throw Error(LH_ERR_INVALID_SNARK, "lasso: commitment mask out of range");
-  std::vector<HG1> comms(count);
-  for (size_t i = 0; i < count; i++)
-    comms[i] = (canon[0] >> i) & 1 ? HG1{host::Fq::zero(), host::Fq::zero()} : tr.read_commitment();
+std::vector<HG1> lasso_read_commitments(Transcript& tr, size_t count, size_t chunks) {
+  LH_REQUIRE(count < 64 && chunks >= 1, LH_ERR_ARG, "lasso: too many commitments for the identity mask");
+  const size_t total = count * chunks;
+  std::vector<uint64_t> masks;
+  for (size_t k = 0; 63 * k < total; k++) {
+    const HFr m = tr.read_field_element();
+    uint64_t canon[4];
+    m.to_canonical(canon);
+    const size_t width = std::min<size_t>(63, total - 63 * k);
+    if (canon[1] || canon[2] || canon[3] || (canon[0] >> width))
+      throw Error(LH_ERR_INVALID_SNARK, "lasso: commitment mask out of range");
+    masks.push_back(canon[0]);
+  }
+  std::vector<HG1> comms(total);
+  for (size_t i = 0; i < total; i++)
+    comms[i] = (masks[i / 63] >> (i % 63)) & 1 ? HG1{host::Fq::zero(), host::Fq::zero()} : tr.read_commitment();
   return comms;
 }
 
@@ -458,7 +470,33 @@ void lasso_prove(Ctx& c, const Pcs& pcs, const lh_lasso_table& tb, size_t n, con
   tr.common_field_element(HFr::from_u64(l));
   tr.common_field_element(HFr::from_u64(cc));
   tr.common_field_element(HFr::from_u64(alpha));
-  {
+  if (pcs.commit_columns) {
+    // a scheme that commits columns itself (Hyrax: vectors of row commitments): a from its 32-bit form when there is one,
+    // dim / read_ts / E / final_cts as u32 columns with the bounds known here; E_i of an identity subtable IS dim_j.  The
+    // derived, packed and sorted-reuse routes are msm_batch features: their counters stay 0.
+    auto bits_of = [](uint32_t v) { return v ? 32u - (uint32_t)__builtin_clz(v) : 1u; };
+    {
+      std::vector<const uint32_t*> cols(fcs.begin(), fcs.end());
+      k_or_u32(c, cols.data(), cc, M, count_ors.data());  // (the access counts bound the timestamps)
+    }
+    const size_t total = 1 + 3 * cc + alpha, k = pcs.chunks;
+    std::vector<PcsColumn> cols(total, PcsColumn{nullptr, true, 0, 1});
+    cols[0] = a_small ? PcsColumn{a_small, true, N, 32} : PcsColumn{a, false, N, 0};
+    for (size_t j = 0; j < cc; j++) {
+      cols[1 + j] = PcsColumn{d_dims[j], true, N, (uint32_t)l};
+      cols[1 + cc + j] = PcsColumn{rts[j], true, N, bits_of(count_ors[j])};
+      cols[1 + 2 * cc + alpha + j] = PcsColumn{fcs[j], true, M, bits_of(count_ors[j])};
+    }
+    for (size_t i = 0; i < alpha; i++)
+      if (tb.memory_subtable[i] != LH_SUBTABLE_IDENTITY) cols[1 + 2 * cc + i] = PcsColumn{E[i], true, N, (uint32_t)std::max<size_t>(l / 2, 1)};
+    std::vector<HG1> comms = pcs.commit_columns(cols.data(), total, nv);
+    LH_REQUIRE(comms.size() == total * k, LH_ERR_ARG, "lasso: commit_columns returned the wrong number of points");
+    for (size_t i = 0; i < alpha; i++)
+      if (tb.memory_subtable[i] == LH_SUBTABLE_IDENTITY)
+        std::copy(comms.begin() + (1 + tb.memory_chunk[i]) * k, comms.begin() + (2 + tb.memory_chunk[i]) * k,
+                  comms.begin() + (1 + 2 * cc + i) * k);
+    lasso_write_commitments(tr, comms, k);
+  } else {
     // zero padding adds nothing to an MSM: commit the unpadded columns against the first entries of the bases.
     // Commitments are linear, so columns that are linear in others need no MSM of their own (same group elements,
     // same proof bytes): E_i = dim_j for an identity subtable, and a = sum_m coeff_m E_{f(m)} when g is linear

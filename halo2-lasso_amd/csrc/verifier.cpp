@@ -699,13 +699,16 @@ static HFr rotation_eval(const std::vector<HFr>& x, int rotation, const std::vec
 static void lasso_verify_check_table(const lh_lasso_table& tb, size_t n);
 
 void hyperplonk_verify(const PcsBatchVerify& batch_verify, const lh_hp_vparam& vp, const HFr* const* instances,
-                       Transcript& tr) {
-  hyperplonk_verify_phases(batch_verify, vp, {vp.num_witness_polys}, {vp.num_challenges}, instances, tr);
+                       Transcript& tr, size_t chunks) {
+  hyperplonk_verify_phases(batch_verify, vp, {vp.num_witness_polys}, {vp.num_challenges}, instances, tr, chunks);
 }
 
 void hyperplonk_verify_phases(const PcsBatchVerify& batch_verify, const lh_hp_vparam& vp,
                               const std::vector<size_t>& phase_witness_polys, const std::vector<size_t>& phase_challenges,
-                              const HFr* const* instances, Transcript& tr) {
+                              const HFr* const* instances, Transcript& tr, size_t chunks) {
+  // chunks: points per commitment (Hyrax's rows; 1 otherwise) - every commitment is read as that many points, the verifier
+  // param holds that many per poly, and batch_verify gets the commitments as vectors, commitment-major
+  LH_REQUIRE(chunks >= 1, LH_ERR_ARG, "hyperplonk: chunks must be at least 1");
   const size_t nv = vp.num_vars;
   LH_REQUIRE(phase_witness_polys.size() == phase_challenges.size(), LH_ERR_ARG, "hyperplonk: phases are malformed");
   {
@@ -723,13 +726,13 @@ void hyperplonk_verify_phases(const PcsBatchVerify& batch_verify, const lh_hp_vp
   std::vector<HG1> witness_comms;
   std::vector<HFr> challenges;
   for (size_t r = 0; r < phase_witness_polys.size(); r++) {
-    std::vector<HG1> cm = tr.read_commitments(phase_witness_polys[r]);
+    std::vector<HG1> cm = tr.read_commitments(phase_witness_polys[r] * chunks);
     witness_comms.insert(witness_comms.end(), cm.begin(), cm.end());
     std::vector<HFr> ch = tr.squeeze_challenges(phase_challenges[r]);
     challenges.insert(challenges.end(), ch.begin(), ch.end());
   }
   HFr beta = tr.squeeze_challenge();
-  std::vector<HG1> m_comms = tr.read_commitments(vp.num_lookups);
+  std::vector<HG1> m_comms = tr.read_commitments(vp.num_lookups * chunks);
   // Lasso lookups (oracle/pyref/hyperplonk.py LassoLookup): read_ts | E | final_cts per lookup, identity-mask framing
   std::vector<HG1> lasso_comms;
   if (vp.num_lasso_lookups) {
@@ -741,10 +744,10 @@ void hyperplonk_verify_phases(const PcsBatchVerify& batch_verify, const lh_hp_vp
       if (lk.table.chunk_bits > nv) throw Error(LH_ERR_INVALID_SNARK, "Lasso subtable larger than the circuit");
       count += 2 * lk.table.num_chunks + lk.table.num_memories;
     }
-    lasso_comms = lasso_read_commitments(tr, count);
+    lasso_comms = lasso_read_commitments(tr, count, chunks);
   }
   HFr gamma = tr.squeeze_challenge();
-  std::vector<HG1> hz_comms = tr.read_commitments(vp.num_lookups + vp.num_permutation_z_polys);
+  std::vector<HG1> hz_comms = tr.read_commitments((vp.num_lookups + vp.num_permutation_z_polys) * chunks);
   HFr alpha = tr.squeeze_challenge();
   std::vector<HFr> y = tr.squeeze_challenges(nv);
   challenges.push_back(beta);
@@ -830,14 +833,14 @@ void hyperplonk_verify_phases(const PcsBatchVerify& batch_verify, const lh_hp_vp
       evals.push_back(e);
     }
   }
-  std::vector<HG1> comms(vp.num_instance_polys, HG1{host::Fq::zero(), host::Fq::zero()});  // Commitment::default()
-  for (size_t i = 0; i < vp.num_preprocess_polys; i++) {
+  std::vector<HG1> comms(vp.num_instance_polys * chunks, HG1{host::Fq::zero(), host::Fq::zero()});  // Commitment::default()
+  for (size_t i = 0; i < vp.num_preprocess_polys * chunks; i++) {
     HG1 p;
     memcpy(&p, &vp.preprocess_comms[i], sizeof(p));
     comms.push_back(p);
   }
   comms.insert(comms.end(), witness_comms.begin(), witness_comms.end());
-  for (size_t i = 0; i < vp.num_permutation_polys; i++) {
+  for (size_t i = 0; i < vp.num_permutation_polys * chunks; i++) {
     HG1 p;
     memcpy(&p, &vp.permutation_comms[i], sizeof(p));
     comms.push_back(p);
@@ -845,7 +848,7 @@ void hyperplonk_verify_phases(const PcsBatchVerify& batch_verify, const lh_hp_vp
   comms.insert(comms.end(), m_comms.begin(), m_comms.end());
   comms.insert(comms.end(), hz_comms.begin(), hz_comms.end());
   // Lasso lookups: the argument's checks, then its claims join the one batch verification
-  size_t base = comms.size();
+  size_t base = comms.size() / chunks;  // (poly indices count commitments, not points)
   comms.insert(comms.end(), lasso_comms.begin(), lasso_comms.end());
   for (size_t k = 0; k < vp.num_lasso_lookups; k++) {
     const lh_hp_lasso_lookup& lk = vp.lasso_lookups[k];
@@ -854,7 +857,7 @@ void hyperplonk_verify_phases(const PcsBatchVerify& batch_verify, const lh_hp_vp
     // the prover's range (hyperplonk.cpp): preprocess and witness polys - instance polys have no commitment to open, the
     // polys after the witness do not exist yet when the lookup's columns are read
     const size_t first_committed = vp.num_instance_polys;
-    const size_t end_committed = vp.num_instance_polys + vp.num_preprocess_polys + witness_comms.size();
+    const size_t end_committed = vp.num_instance_polys + vp.num_preprocess_polys + witness_comms.size() / chunks;
     LH_REQUIRE(lk.output_poly >= first_committed && lk.output_poly < end_committed, LH_ERR_ARG, "hyperplonk: lasso output poly out of range");
     for (size_t j = 0; j < cc; j++)
       LH_REQUIRE(lk.chunk_polys[j] >= first_committed && lk.chunk_polys[j] < end_committed, LH_ERR_ARG,
@@ -881,7 +884,7 @@ void hyperplonk_verify_phases(const PcsBatchVerify& batch_verify, const lh_hp_vp
     for (size_t j = 0; j < cc; j++) push(base + cc + alpha + j, p0 + 3, cl.ev_l[j]);
     base += 2 * cc + alpha;
   }
-  batch_verify(nv, comms.data(), comms.size(), points.data(), num_points, evals.data(), evals.size(), tr);
+  batch_verify(nv, comms.data(), comms.size() / chunks, points.data(), num_points, evals.data(), evals.size(), tr);
 }
 
 // ------------------------------------------------------------------ Lasso verify (oracle/pyref/lasso.py:219-261)
@@ -1022,12 +1025,12 @@ LassoClaims lasso_check(const lh_lasso_table& tb, size_t n, Transcript& tr) {
   return cl;
 }
 
-void lasso_verify(const PcsBatchVerify& batch_verify, const lh_lasso_table& tb, size_t n, Transcript& tr) {
+void lasso_verify(const PcsBatchVerify& batch_verify, const lh_lasso_table& tb, size_t n, Transcript& tr, size_t chunks) {
   lasso_verify_check_table(tb, n);
   const size_t c = tb.num_chunks, l = tb.chunk_bits, alpha = tb.num_memories;
   for (size_t v : {n, l, c, alpha}) tr.common_field_element(HFr::from_u64(v));
   const size_t nv = std::max(n, l);
-  std::vector<HG1> comms = lasso_read_commitments(tr, 1 + 3 * c + alpha);
+  std::vector<HG1> comms = lasso_read_commitments(tr, 1 + 3 * c + alpha, chunks);
   LassoClaims cl = lasso_check(tb, n, tr);
   const HFr *dim_e = &cl.ev_n[0], *rts_e = &cl.ev_n[c], *e_e = &cl.ev_n[2 * c], *fc_e = &cl.ev_l[0];
 
@@ -1050,7 +1053,7 @@ void lasso_verify(const PcsBatchVerify& batch_verify, const lh_lasso_table& tb, 
     points.insert(points.end(), pt->begin(), pt->end());
     points.insert(points.end(), nv - pt->size(), HFr::zero());
   }
-  batch_verify(nv, comms.data(), comms.size(), points.data(), 4, evals.data(), evals.size(), tr);
+  batch_verify(nv, comms.data(), comms.size() / chunks, points.data(), 4, evals.data(), evals.size(), tr);
 }
 
 // ------------------------------------------------------------------ Brakedown (pcs/multilinear/brakedown.rs:315-396)

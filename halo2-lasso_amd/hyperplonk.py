@@ -128,9 +128,21 @@ class HyperPlonkProverParam:
     """hyperplonk.rs:38-55"""
 
 
+def batch_size(info):
+    """preprocessor.rs:13-23: the largest number of polys HyperPlonk commits or opens in one batch, summed over its rounds -
+    what HyperPlonk::setup passes to Pcs::setup (Hyrax sizes its rows by it): preprocess + permutation polys, every phase's
+    witness polys, the lookups' m polys, the lookups' h polys + the permutation z polys"""
+    num_lookups, num_perm = len(info.lookups), len(info.permutation_polys())
+    return (len(info.preprocess_polys) + num_perm + sum(info.num_witness_polys) + num_lookups +
+            num_lookups + -(-num_perm // (max_degree(info) - 1)))
+
+
 def _pcs_of(pcs_pp):
-    """the PolynomialCommitmentScheme a param belongs to: MultilinearKzg, Zeromorph, Gemini or Ipa (backend/hyperplonk.rs:76-95)"""
-    from . import MultilinearKzg, Zeromorph, ZeromorphProverParam, Gemini, GeminiProverParam, Ipa, IpaParam
+    """the PolynomialCommitmentScheme a param belongs to: MultilinearKzg, Zeromorph, Gemini, Ipa or Hyrax
+    (backend/hyperplonk.rs:76-95); over Hyrax a commitment is a list of num_chunks points"""
+    from . import MultilinearKzg, Zeromorph, ZeromorphProverParam, Gemini, GeminiProverParam, Ipa, IpaParam, Hyrax, HyraxParam
+    if isinstance(pcs_pp, HyraxParam):
+        return Hyrax
     if isinstance(pcs_pp, IpaParam):
         return Ipa
     if isinstance(pcs_pp, GeminiProverParam):
@@ -241,8 +253,10 @@ class HyperPlonk:
         prm.num_lasso_lookups, prm.lasso_lookups = len(info.lasso_lookups), lasso_arr
         inst_arrays = [_fr_array(i) for i in instances]
         inst = (C.POINTER(lh_fr) * max(len(instances), 1))(*[C.cast(a, C.POINTER(lh_fr)) for a in inst_arrays])
-        from . import ZeromorphProverParam, GeminiProverParam, IpaParam
+        from . import ZeromorphProverParam, GeminiProverParam, IpaParam, HyraxParam
         lib = ctx.lib
+        if isinstance(pp.pcs, HyraxParam):  # (params, trim size, batch size)
+            head = (ctx.h, pp.pcs.params.h, pp.pcs.poly_size, pp.pcs.batch_size, C.byref(prm))
         # PCS whose param is (params, trim size): over the univariate SRS, or the IPA
         univariate = isinstance(pp.pcs, (ZeromorphProverParam, GeminiProverParam, IpaParam))
         gemini, ipa = isinstance(pp.pcs, GeminiProverParam), isinstance(pp.pcs, IpaParam)
@@ -268,7 +282,9 @@ class HyperPlonk:
             nph = len(info.num_witness_polys)
             nw = (C.c_size_t * max(nph, 1))(*info.num_witness_polys)
             nc = (C.c_size_t * max(nph, 1))(*info.num_challenges)
-            if univariate:
+            if isinstance(pp.pcs, HyraxParam):
+                rc = lib.lh_hyperplonk_prove_phases_hyrax(*head, nph, nw, nc, inst, C.byref(circ), transcript.p)
+            elif univariate:
                 fn = lib.lh_hyperplonk_prove_phases_ipa if ipa else \
                     lib.lh_hyperplonk_prove_phases_gemini if gemini else lib.lh_hyperplonk_prove_phases_zeromorph
                 rc = fn(ctx.h, pp.pcs.params.h, pp.pcs.poly_size, C.byref(prm), nph, nw, nc, inst, C.byref(circ), transcript.p)
@@ -285,7 +301,9 @@ class HyperPlonk:
                 raise NotImplementedError("the sharded prove is wired for multilinear KZG")
             _check(ctx.lib.lh_hyperplonk_prove_sharded(ctx.h, pp.pcs.h, C.byref(prm), inst, wit, transcript.p))
             return
-        if univariate:
+        if isinstance(pp.pcs, HyraxParam):
+            _check(lib.lh_hyperplonk_prove_hyrax(*head, inst, wit, transcript.p))
+        elif univariate:
             fn = lib.lh_hyperplonk_prove_ipa if ipa else \
                 lib.lh_hyperplonk_prove_gemini if gemini else lib.lh_hyperplonk_prove_zeromorph
             _check(fn(ctx.h, pp.pcs.params.h, pp.pcs.poly_size, C.byref(prm), inst, wit, transcript.p))
@@ -310,16 +328,21 @@ class HyperPlonk:
         prm.expression = ce
         lasso_arr = _lasso_lookups_c(info)
         prm.num_lasso_lookups, prm.lasso_lookups = len(info.lasso_lookups), lasso_arr
-        pre, perm = _g1_array(vp.preprocess_comms), _g1_array(vp.permutation_comms)
+        from . import HyraxParam
+        hyrax = isinstance(vp.pcs, HyraxParam)
+        flat = (lambda comms: [p for cm in comms for p in cm]) if hyrax else list  # (over Hyrax: num_chunks points per poly)
+        pre, perm = _g1_array(flat(vp.preprocess_comms)), _g1_array(flat(vp.permutation_comms))
         prm.num_preprocess_polys, prm.preprocess_comms = len(vp.preprocess_comms), pre
         prm.num_permutation_polys, prm.permutation_comms = len(vp.permutation_comms), perm
         inst_arrays = [_fr_array(i) for i in instances]
         inst = (C.POINTER(lh_fr) * max(len(instances), 1))(*[C.cast(a, C.POINTER(lh_fr)) for a in inst_arrays])
         from . import ZeromorphVerifierParam, GeminiVerifierParam, IpaParam
         suffix = "_zeromorph" if isinstance(vp.pcs, ZeromorphVerifierParam) else \
-            "_gemini" if isinstance(vp.pcs, GeminiVerifierParam) else "_ipa" if isinstance(vp.pcs, IpaParam) else ""
-        # (the IPA's verifier param is its params and the trim size)
-        pcs_args = (vp.pcs.params.h, vp.pcs.poly_size) if isinstance(vp.pcs, IpaParam) else (vp.pcs.h,)
+            "_gemini" if isinstance(vp.pcs, GeminiVerifierParam) else "_hyrax" if hyrax else \
+            "_ipa" if isinstance(vp.pcs, IpaParam) else ""
+        # (the IPA's verifier param is its params and the trim size; Hyrax's also the batch size)
+        pcs_args = (vp.pcs.params.h, vp.pcs.poly_size, vp.pcs.batch_size) if hyrax else \
+            (vp.pcs.params.h, vp.pcs.poly_size) if isinstance(vp.pcs, IpaParam) else (vp.pcs.h,)
         if len(info.num_witness_polys) != 1:
             nph = len(info.num_witness_polys)
             nw = (C.c_size_t * max(nph, 1))(*info.num_witness_polys)

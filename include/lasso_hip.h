@@ -282,6 +282,9 @@ lh_status lh_lasso_last_timing(lh_ctx*, double* out_ms);
  *                             bind and go on as such rounds; 0: sc_round_e2_kernel / sc_round_rw_kernel in every round
  *                             2: the product-pair kernel in every streaming round of the generic layers WITHOUT the fold
  *                             (the coefficients are applied to the lane's value, the tables stay as they are; a test shape)
+ *   hyrax_rows           1    a Hyrax commit runs every row of every poly through the row kernels (csrc/kernels_hyrax.hip: the
+ *                             terms of a row go into one bucket set over the generators' window table, nothing waits on
+ *                             the host between rows); 0: one job of the batched MSM per row (48 jobs per planning pass)
  *   comm_round           0    how the partial sums of a sharded sum-check round are combined over the ranks:
  *                             0 = ncclAllGather of every rank's sums + a one-thread sum-and-publish kernel;
  *                             1 = ONE collective: the round kernel leaves its sums as u64 lanes (32-bit limb | tag << 40),
@@ -740,21 +743,29 @@ lh_status lh_ipa_batch_verify(const lh_ipa_param*, size_t poly_size, size_t num_
 /* the base fold of an opening's round (ipa.rs:216-222) as a primitive: d_out[j] = d_a[j] + s d_b[j], j < n, affine
  * (identity = (0,0)); d_out may be d_a */
 lh_status lh_g1_axpy(lh_ctx*, const lh_g1* d_a, const lh_g1* d_b, size_t n, const lh_fr* s, lh_g1* d_out);
+/* the row commitments of a Hyrax commit (hyrax.rs:199-220) as a primitive: out_rows[r] = sum_{c < row_len}
+ * s[r row_len + c] d_bases[c] for the ceil(n / row_len) rows of a flat DEVICE array of n scalars - lh_fr in Montgomery form, or
+ * uint32_t with every value < 2^bits (scalars_u32 != 0, bits in 1..32; larger values lose their upper bits).  A partial last
+ * row counts as padded with zeros.  d_bases: row_len device points; out_rows: HOST, affine, the identity as (0, 0).  One
+ * launch set for all rows (csrc/kernels_hyrax.hip); the window table of the bases is built in workspace memory per call
+ * (lh_hyrax_batch_commit keeps the generators' on the param).  LH_ERR_ARG for row_len 0 or bits outside 1..32 */
+lh_status lh_g1_rows_msm(lh_ctx*, const void* d_scalars, int scalars_u32, uint32_t bits, size_t n, size_t row_len,
+                         const lh_g1* d_bases, lh_g1* out_rows);
 /* MultilinearHyrax<bn256::G1Affine> on top of it (pcs/multilinear/hyrax.rs:23-321): a table of 2^num_vars entries as
  * num_chunks = 2^(num_vars - row_num_vars) rows of 2^row_num_vars, one IPA commitment per row, with
  * batch_num_vars = log2(next_pow2(poly_size batch_size)) and row_num_vars = ceil(batch_num_vars / 2).  MultilinearHyraxParams
  * is those dimensions and an IPA param of 2^row_num_vars: an lh_ipa_param here, with (poly_size, batch_size) as the trim
  * arguments of every entry.  A commitment is num_chunks points, row 0 first; `comms` arrays are commitment-major.  Polys
- * must have exactly the (trimmed) param's num_vars.  Hyrax has no Lasso / HyperPlonk entries: their PCS interface is
- * typed on one point per poly. */
+ * must have exactly the (trimmed) param's num_vars.  Lasso and HyperPlonk prove over Hyrax through the _hyrax entries
+ * below. */
 /* setup (hyrax.rs:121-137): LH_ERR_ARG unless poly_size is a power of two and 0 < batch_size <= poly_size; ctx as lh_ipa_setup */
 lh_status lh_hyrax_setup(lh_ctx* ctx, size_t poly_size, size_t batch_size, lh_ipa_param** out);
 /* the dimensions setup and trim derive (hyrax.rs:125-127); outputs may be NULL */
 lh_status lh_hyrax_dims(size_t poly_size, size_t batch_size, size_t* num_vars, size_t* batch_num_vars, size_t* row_num_vars);
 /* trim (hyrax.rs:139-167): LH_ERR_INVALID_PCS_PARAM "Too many variates to trim" when the param's rows are too short */
 lh_status lh_hyrax_trim(const lh_ipa_param*, size_t poly_size, size_t batch_size, size_t* row_num_vars, size_t* num_chunks);
-/* commit / batch_commit (hyrax.rs:169-221): every row of every poly is a job of one batched MSM; out_comms: num_polys x
- * num_chunks points */
+/* commit / batch_commit (hyrax.rs:169-221): every row of every poly in one call of the row kernels (option hyrax_rows;
+ * 0: every row a job of one batched MSM - the same points); out_comms: num_polys x num_chunks points */
 lh_status lh_hyrax_batch_commit(lh_ctx*, const lh_ipa_param*, size_t poly_size, size_t batch_size, const lh_fr* const* d_polys,
                                 size_t num_polys, size_t num_vars, lh_g1* out_comms);
 /* open (hyrax.rs:224-258): the row combination sum_r eq(hi)[r] row_r in one pass, then the IPA opening of it at lo */
@@ -771,6 +782,33 @@ lh_status lh_hyrax_verify(const lh_ipa_param*, size_t poly_size, size_t batch_si
 lh_status lh_hyrax_batch_verify(const lh_ipa_param*, size_t poly_size, size_t batch_size, size_t num_vars, const lh_g1* comms,
                                 size_t num_comms, const lh_fr* points, size_t num_points, const lh_evaluation* evals,
                                 size_t num_evals, lh_transcript* t);
+/* Lasso over MultilinearHyrax: arguments as the _ipa entries plus batch_size after poly_size.  max(num_vars, chunk_bits)
+ * must equal log2(poly_size) (LH_ERR_ARG otherwise: Hyrax commits only tables of the param's size); a param whose rows are
+ * too short is LH_ERR_INVALID_PCS_PARAM "Too many variates to trim".  The commitments are vectors of num_chunks points,
+ * framed as count * num_chunks points commitment-major: ceil(total / 63) identity masks first (mask k covers the positions
+ * 63 k .. 63 k + 62), then the non-identity points; a mask with a bit at or above its width is LH_ERR_INVALID_SNARK
+ * "commitment mask out of range".  With num_chunks = 1 this is the framing of every other scheme, bit for bit. */
+lh_status lh_lasso_prove_hyrax(lh_ctx*, const lh_ipa_param*, size_t poly_size, size_t batch_size, const lh_lasso_table*,
+                               size_t num_vars, const uint32_t* const* d_dims, lh_transcript* t);
+lh_status lh_lasso_verify_hyrax(const lh_ipa_param*, size_t poly_size, size_t batch_size, const lh_lasso_table*, size_t num_vars,
+                                lh_transcript* t);
+/* HyperPlonk<MultilinearHyrax<bn256::G1Affine>> (backend/hyperplonk.rs:421-426): arguments as the _ipa entries plus
+ * batch_size after poly_size (what HyperPlonk::setup hands Pcs::setup: preprocessor.rs:13-23, Python hyperplonk.batch_size).
+ * The circuit's num_vars must equal log2(poly_size) (LH_ERR_ARG).  Every commitment is num_chunks points: lh_hp_vparam's
+ * preprocess_comms / permutation_comms hold num_chunks points per poly, poly-major; the witness, m, h and z commitments are
+ * written plainly, as the reference writes them, so a ROW of such a poly that is identically zero (an identity row
+ * commitment) ends the prove with LH_ERR_TRANSCRIPT after the bytes written by then - a property of the reference's
+ * transcript; the Lasso lookups' commitments are framed as in lh_lasso_prove_hyrax. */
+lh_status lh_hyperplonk_prove_hyrax(lh_ctx*, const lh_ipa_param*, size_t poly_size, size_t batch_size, const lh_hp_param*,
+                                    const lh_fr* const* instances, const lh_fr* const* d_witness_polys, lh_transcript* t);
+lh_status lh_hyperplonk_verify_hyrax(const lh_ipa_param*, size_t poly_size, size_t batch_size, const lh_hp_vparam*,
+                                     const lh_fr* const* instances, lh_transcript* t);
+lh_status lh_hyperplonk_prove_phases_hyrax(lh_ctx*, const lh_ipa_param*, size_t poly_size, size_t batch_size, const lh_hp_param*,
+                                           size_t num_phases, const size_t* num_witness_polys, const size_t* num_challenges,
+                                           const lh_fr* const* instances, const lh_hp_circuit* circuit, lh_transcript* t);
+lh_status lh_hyperplonk_verify_phases_hyrax(const lh_ipa_param*, size_t poly_size, size_t batch_size, const lh_hp_vparam*,
+                                            size_t num_phases, const size_t* num_witness_polys, const size_t* num_challenges,
+                                            const lh_fr* const* instances, lh_transcript* t);
 /* Lasso and HyperPlonk<MultilinearIpa<bn256::G1Affine>> (backend/hyperplonk.rs:76-95): arguments as the _gemini entries */
 lh_status lh_lasso_prove_ipa(lh_ctx*, const lh_ipa_param*, size_t poly_size, const lh_lasso_table*, size_t num_vars,
                              const uint32_t* const* d_dims, lh_transcript* t);
