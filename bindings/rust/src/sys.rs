@@ -89,6 +89,23 @@ pub struct lh_debug_sort_slab {
     pub n: usize, pub bits: u32, pub first_bit: u32,
 }
 
+// (development) lh_debug_u32_columns: the 32-bit column kernels one operation at a time (op = LH_U32_*)
+pub const LH_U32_INNER_PRODUCTS_SMALL: i32 = 0;
+pub const LH_U32_INNER_PRODUCTS_SMALL_HALF: i32 = 1;
+pub const LH_U32_INNER_PRODUCTS_SMALL_QUADS: i32 = 2;
+pub const LH_U32_INNER_PRODUCTS_QUADS: i32 = 3;
+pub const LH_U32_LINCOMB_MIXED: i32 = 4;
+pub const LH_U32_LINCOMB_FOLD_SMALL: i32 = 5;
+pub const LH_U32_LINCOMB_BIND2: i32 = 6;
+pub const LH_U32_SC_ROUND_BIND2: i32 = 7;
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct lh_debug_u32_args {
+    pub d_cols: *const *const u32, pub lens: *const usize, pub w: *const Fr, pub count: usize,
+    pub d_weights: *const Fr, pub n: usize,
+    pub d_fr: *const *const Fr, pub w_fr: *const Fr, pub num_fr: usize,
+    pub r0: Fr, pub r1: Fr, pub d_out: *mut Fr, pub out_host: *mut Fr, pub taken: *mut i32,
+}
+
 #[repr(C)] #[derive(Clone, Copy)]
 pub struct lh_evaluation { pub poly: u32, pub point: u32, pub value: Fr }
 
@@ -262,6 +279,7 @@ extern "C" {
     pub fn lh_ctx_comm_stats(ctx: *mut lh_ctx, out: *mut u64) -> lh_status;
     pub fn lh_ctx_comm_phase_stats(ctx: *mut lh_ctx, out: *mut u64, reset: c_int) -> lh_status;
     pub fn lh_ctx_memory_stats(ctx: *mut lh_ctx, out: *mut u64) -> lh_status;
+    pub fn lh_ctx_compute_units(ctx: *mut lh_ctx, out: *mut usize) -> lh_status;
     pub fn lh_ctx_host_cpus(ctx: *mut lh_ctx, bus_id: *mut c_char, bus_id_cap: usize, cpulist: *mut c_char, cpulist_cap: usize) -> lh_status;
     pub fn lh_shard_extract(ctx: *mut lh_ctx, d_global: *const c_void, n_local: usize, shard_bit: usize, rho: usize,
                             rank: usize, elem_bytes: usize, d_local: *mut c_void) -> lh_status;
@@ -306,6 +324,8 @@ extern "C" {
                                    d_keep_sorted: *const *mut u32, d_keep_index: *const *mut u32) -> lh_status;
     pub fn lh_debug_sort_plan(n: usize, bits: u32, key_bytes: i32, passes: *mut u32, rb: *mut u32,
                               temp_bytes: *mut usize) -> lh_status;
+    // (development) the 32-bit column kernels on their own
+    pub fn lh_debug_u32_columns(ctx: *mut lh_ctx, op: i32, args: *const lh_debug_u32_args) -> lh_status;
     // Zeromorph over univariate KZG: lh_ukzg_setup, lh_usrs_*, lh_zeromorph_* follow the same shapes
     // (include/lasso_hip.h, section f3) and are bound the same way when HyperPlonk<Zeromorph<..>> is wanted.
     // Univariate KZG on its own and Gemini over it (include/lasso_hip.h, section f3b); lh_usrs / lh_ukzg_vp are opaque here

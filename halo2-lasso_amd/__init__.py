@@ -160,6 +160,12 @@ class Context:
     def sync(self):
         _check(self.lib.lh_ctx_sync(self.h))
 
+    def compute_units(self):
+        """the compute units of the ctx's device (lh_ctx_compute_units)"""
+        n = C.c_size_t()
+        _check(self.lib.lh_ctx_compute_units(self.h, C.byref(n)))
+        return n.value
+
     def host_cpus(self):
         """(PCI address of the ctx's device, the CPUs on its NUMA node as a set) - lh_ctx_host_cpus; the set is empty where
         the system does not say"""

@@ -109,6 +109,18 @@ class lh_debug_sort_slab(C.Structure):  # (development: lh_debug_sort_pairs)
                 ("n", C.c_size_t), ("bits", C.c_uint32), ("first_bit", C.c_uint32)]
 
 
+class lh_debug_u32_args(C.Structure):  # (development: lh_debug_u32_columns)
+    _fields_ = [("d_cols", C.POINTER(C.c_void_p)), ("lens", C.POINTER(C.c_size_t)), ("w", C.POINTER(lh_fr)),
+                ("count", C.c_size_t), ("d_weights", C.c_void_p), ("n", C.c_size_t),
+                ("d_fr", C.POINTER(C.c_void_p)), ("w_fr", C.POINTER(lh_fr)), ("num_fr", C.c_size_t),
+                ("r0", lh_fr), ("r1", lh_fr), ("d_out", C.c_void_p), ("out_host", C.POINTER(lh_fr)),
+                ("taken", C.POINTER(C.c_int))]
+
+
+LH_U32_OPS = ("inner_products_small", "inner_products_small_half", "inner_products_small_quads", "inner_products_quads",
+              "lincomb_mixed", "lincomb_fold_small", "lincomb_bind2", "sc_round_u32_bind2")  # index = the op code
+
+
 class lh_prof_rec(C.Structure):
     _fields_ = [("name", C.c_char * 40), ("ms", C.c_double), ("bytes", C.c_double), ("muls", C.c_double),
                 ("items", C.c_double)]
@@ -203,6 +215,7 @@ SIGNATURES = {
     "lh_ctx_comm_stats": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "lh_ctx_comm_phase_stats": (C.c_int, [_P, C.POINTER(C.c_uint64), C.c_int]),
     "lh_ctx_memory_stats": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    "lh_ctx_compute_units": (C.c_int, [_P, C.POINTER(C.c_size_t)]),
     "lh_ctx_host_cpus": (C.c_int, [_P, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t]),
     "lh_lasso_prove_sharded": (C.c_int, [_P, _P, C.POINTER(lh_lasso_table), _SZ, C.POINTER(_P),
                                          C.POINTER(lh_transcript)]),
@@ -350,6 +363,7 @@ SIGNATURES = {
     "lh_debug_lasso_counters": (C.c_int, [_P, C.POINTER(_P), _SZ, _SZ, _SZ, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P),
                                           C.POINTER(_P)]),
     "lh_debug_sort_plan": (C.c_int, [_SZ, C.c_uint, C.c_int, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(_SZ)]),
+    "lh_debug_u32_columns": (C.c_int, [_P, C.c_int, C.POINTER(lh_debug_u32_args)]),
     "lh_keccak_transcript_hash_io": (C.c_int, [C.POINTER(lh_transcript), C.POINTER(lh_hash_transcript)]),
     "lh_brakedown_setup": (C.c_int, [_P, _SZ, C.c_int, C.c_char_p, C.POINTER(_P)]),
     "lh_brakedown_derive": (C.c_int, [_SZ, C.c_int, C.POINTER(_P)]),

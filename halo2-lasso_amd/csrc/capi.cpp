@@ -667,6 +667,12 @@ lh_status lh_ctx_memory_stats(lh_ctx* ctx, uint64_t out[4]) {
   out[2] = free_b, out[3] = total_b;
   LH_CATCH
 }
+lh_status lh_ctx_compute_units(lh_ctx* ctx, size_t* out) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(out);
+  *out = (size_t)ctx->c.num_cus;
+  LH_CATCH
+}
 lh_status lh_ctx_host_cpus(lh_ctx* ctx, char* bus_id, size_t bus_id_cap, char* cpulist, size_t cpulist_cap) {
   LH_TRY NEED_CTX(ctx);
   NEED(bus_id);
@@ -1980,6 +1986,81 @@ lh_status lh_debug_sort_plan(size_t n, unsigned bits, int key_bytes, unsigned* p
   NEED(temp_bytes);
   LH_REQUIRE(key_bytes == 4 || key_bytes == 8, LH_ERR_ARG, "debug sort: key_bytes is 4 or 8");
   sort_plan(n, bits, (size_t)key_bytes, passes, rb, temp_bytes);
+  LH_CATCH
+}
+
+// (development) the 32-bit column kernels (kernels_poly.hip, "small-valued columns") one launch set at a time:
+// tests/test_gpu_u32_columns.py.  Everything is checked before anything is launched.
+lh_status lh_debug_u32_columns(lh_ctx* ctx, int op, const lh_debug_u32_args* a) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(a);
+  Ctx& c = ctx->c;
+  LH_REQUIRE(op >= LH_U32_INNER_PRODUCTS_SMALL && op <= LH_U32_SC_ROUND_BIND2, LH_ERR_ARG, "debug u32 columns: unknown operation");
+  LH_REQUIRE(a->n >= 1 && a->n < ((size_t)1 << 31), LH_ERR_ARG, "debug u32 columns: n must be in [1, 2^31)");
+  const bool one_col = op == LH_U32_INNER_PRODUCTS_SMALL_QUADS || op == LH_U32_SC_ROUND_BIND2;
+  const bool has_lens = op == LH_U32_INNER_PRODUCTS_QUADS || op == LH_U32_LINCOMB_MIXED || op == LH_U32_LINCOMB_FOLD_SMALL ||
+                        op == LH_U32_LINCOMB_BIND2;
+  const bool has_w = op == LH_U32_LINCOMB_MIXED || op == LH_U32_LINCOMB_FOLD_SMALL || op == LH_U32_LINCOMB_BIND2;
+  const bool quads = op == LH_U32_INNER_PRODUCTS_SMALL_QUADS || op == LH_U32_INNER_PRODUCTS_QUADS || op == LH_U32_LINCOMB_BIND2 ||
+                     op == LH_U32_SC_ROUND_BIND2;  // (the kernels that read a column as uint4)
+  const bool sums = op != LH_U32_INNER_PRODUCTS_QUADS && op != LH_U32_LINCOMB_MIXED && op != LH_U32_LINCOMB_FOLD_SMALL;
+  LH_REQUIRE(!one_col || a->count == 1, LH_ERR_ARG, "debug u32 columns: this operation takes one column");
+  if (op == LH_U32_LINCOMB_MIXED)
+    LH_REQUIRE(a->num_fr <= (size_t)LCM_MAX_FR && a->count <= (size_t)LCM_MAX_SMALL, LH_ERR_ARG, "debug u32 columns: too many inputs");
+  else if (op == LH_U32_LINCOMB_BIND2)
+    LH_REQUIRE(a->count >= 1 && a->count <= (size_t)LCB_MAX, LH_ERR_ARG, "debug u32 columns: bad column count");
+  else
+    LH_REQUIRE(a->count <= 1024, LH_ERR_ARG, "debug u32 columns: bad column count");
+  NEED_N(a->d_cols, a->count);
+  if (has_lens) NEED_N(a->lens, a->count);
+  if (has_w) NEED_N(a->w, a->count);
+  for (size_t k = 0; k < a->count; k++) {
+    LH_REQUIRE(a->d_cols[k] != nullptr, LH_ERR_ARG, "null argument: a column");
+    if (quads) {
+      LH_REQUIRE((uintptr_t)a->d_cols[k] % 16 == 0, LH_ERR_ARG, "debug u32 columns: a column read as uint4 must be 16-byte aligned");
+      LH_REQUIRE(!has_lens || a->lens[k] % 4 == 0, LH_ERR_ARG, "debug u32 columns: a column read as uint4 must have a multiple of 4 entries");
+    }
+  }
+  if (op != LH_U32_LINCOMB_MIXED && op != LH_U32_LINCOMB_FOLD_SMALL) NEED(a->d_weights);
+  if (op == LH_U32_LINCOMB_MIXED) {
+    NEED_N(a->d_fr, a->num_fr);
+    NEED_N(a->w_fr, a->num_fr);
+    for (size_t k = 0; k < a->num_fr; k++) LH_REQUIRE(a->d_fr[k] != nullptr, LH_ERR_ARG, "null argument: a field-element table");
+  }
+  if (op == LH_U32_LINCOMB_FOLD_SMALL) NEED(a->taken);
+  if (sums) NEED_N(a->out_host, op == LH_U32_INNER_PRODUCTS_SMALL || op == LH_U32_INNER_PRODUCTS_SMALL_HALF ? a->count : 1);
+  if (op >= LH_U32_INNER_PRODUCTS_QUADS) NEED(a->d_out);
+  const uint32_t* const* cols = a->d_cols;
+  const Fr* dw = (const Fr*)a->d_weights;
+  Fr r0, r1;
+  memcpy(&r0, &a->r0, 32);
+  memcpy(&r1, &a->r1, 32);
+  ArenaScope scope(c.arena);  // (k_inner_products_quads leaves its partial sums to the caller's scope)
+  switch (op) {
+    case LH_U32_INNER_PRODUCTS_SMALL: k_inner_products_small(c, cols, a->count, dw, a->n, (Fr*)a->out_host); break;
+    case LH_U32_INNER_PRODUCTS_SMALL_HALF: k_inner_products_small_half(c, cols, a->count, dw, a->n, r0, (Fr*)a->out_host); break;
+    case LH_U32_INNER_PRODUCTS_SMALL_QUADS: k_inner_products_small_quads(c, cols[0], dw, a->n, (Fr*)a->out_host); break;
+    case LH_U32_INNER_PRODUCTS_QUADS: k_inner_products_quads(c, cols, a->lens, a->count, dw, a->n, (Fr*)a->d_out); break;
+    case LH_U32_LINCOMB_MIXED:
+      k_lincomb_mixed(c, (const Fr* const*)a->d_fr, (const Fr*)a->w_fr, a->num_fr, cols, a->lens, (const Fr*)a->w, a->count, a->n,
+                      (Fr*)a->d_out);
+      break;
+    case LH_U32_LINCOMB_FOLD_SMALL:  // (false - no columns, too many, nothing to fold - is the caller's cue for the other route)
+      *a->taken = k_lincomb_fold_small(c, cols, a->lens, (const Fr*)a->w, a->count, a->n, r0, (Fr*)a->d_out) ? 1 : 0;
+      break;
+    default: {
+      // the round sums land in pinned memory of the ctx, behind the argument block of k_lincomb_bind2 (as sumcheck.cpp does)
+      Fr* two = (Fr*)c.pin(65536) + 1024;
+      if (op == LH_U32_LINCOMB_BIND2) {
+        k_lincomb_bind2(c, cols, a->lens, (const Fr*)a->w, a->count, r0, r1, dw, a->n, (Fr*)a->d_out, two);
+        memcpy(a->out_host, two, 64);
+      } else {
+        k_sc_round_u32_bind2(c, cols[0], dw, r0, r1, a->n, (Fr*)a->d_out, two);
+        memcpy(a->out_host, two, 32);
+      }
+    }
+  }
+  c.sync();
   LH_CATCH
 }
 

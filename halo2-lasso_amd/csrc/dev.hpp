@@ -443,9 +443,10 @@ bool k_lincomb_fold_small(Ctx&, const uint32_t* const* cols, const size_t* lens,
                           const Fr& x, Fr* out);
 // out[i] = <polys[i], weights>, i < count ; result on host
 void k_inner_products(Ctx&, const Fr* const* polys, size_t count, const Fr* weights, size_t n, Fr* out_host);
-// same with u32-valued polys
-void k_inner_products_u32(Ctx&, const uint32_t* const* polys, size_t count, const Fr* weights, size_t n,
-                          Fr* out_host);
+// the most inputs a launch of the 32-bit column kernels takes (their argument blocks travel through memory)
+constexpr int LCM_MAX_FR = 8, LCM_MAX_SMALL = 24;  // k_lincomb_mixed
+constexpr int LCF_MAX = 24;                        // k_lincomb_fold_small
+constexpr int LCB_MAX = 24;                        // k_lincomb_bind2
 // small-valued columns without their field-element views: 8 multiply-adds per term into a wide accumulator
 void k_inner_products_small(Ctx&, const uint32_t* const* polys, size_t count, const Fr* weights, size_t n, Fr* out_host);
 // the same against eq(y) given as the eq table of y[1..] (`half` entries) and y0

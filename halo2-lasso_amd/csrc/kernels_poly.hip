@@ -478,23 +478,13 @@ void k_lincomb(Ctx& c, const Fr* const* polys, const Fr* w, size_t count, size_t
 // ------------------------------------------------------------------ inner products <poly_i, weights>
 constexpr int IP_MAX = 16;
 struct IpPack {
-  const void* p[IP_MAX];
+  const Fr* p[IP_MAX];
 };
-template <bool U32>
 __global__ void inner_products_kernel(IpPack pk, const Fr* __restrict__ w, size_t n, Fr* __restrict__ partials) {
   __shared__ Fr lds[4];
-  const void* src = pk.p[blockIdx.y];
+  const Fr* src = pk.p[blockIdx.y];
   Fr acc = Fr::zero();
-  GSTRIDE(i, n) {
-    Fr v;
-    if (U32) {
-      // small value * weight: weights are Montgomery, v canonical small -> mul(to_mont(v), w)
-      v = from_u64<FrParams>(((const uint32_t*)src)[i]);
-    } else {
-      v = ((const Fr*)src)[i];
-    }
-    acc = add(acc, mul(v, w[i]));
-  }
+  GSTRIDE(i, n) acc = add(acc, mul(src[i], w[i]));
   acc = block_reduce_sum(acc, lds);
   if (threadIdx.x == 0) partials[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = acc;
 }
@@ -505,9 +495,7 @@ __global__ void reduce_rows_kernel(const Fr* __restrict__ partials, int per_row,
   acc = block_reduce_sum(acc, lds);
   if (threadIdx.x == 0) out[blockIdx.x] = acc;
 }
-template <bool U32>
-static void inner_products_impl(Ctx& c, const void* const* polys, size_t count, const Fr* weights, size_t n,
-                                Fr* out_host) {
+void k_inner_products(Ctx& c, const Fr* const* polys, size_t count, const Fr* weights, size_t n, Fr* out_host) {
   ProfScope ps(c, "inner_products", 32.0 * n * (count + 1), 1.0 * n * count, (double)n);
   if (!count) return;
   ArenaScope scope(c.arena);
@@ -520,17 +508,10 @@ static void inner_products_impl(Ctx& c, const void* const* polys, size_t count, 
     for (int i = 0; i < k; i++) pk.p[i] = polys[base + i];
     dim3 gg = g;
     gg.y = k;
-    hipLaunchKernelGGL(inner_products_kernel<U32>, gg, 256, 0, c.stream, pk, weights, n, partials);
+    hipLaunchKernelGGL(inner_products_kernel, gg, 256, 0, c.stream, pk, weights, n, partials);
     hipLaunchKernelGGL(reduce_rows_kernel, k, 256, 0, c.stream, partials, (int)g.x, d_out + base);
   }
   c.d2h(out_host, d_out, count * sizeof(Fr));
-}
-void k_inner_products(Ctx& c, const Fr* const* polys, size_t count, const Fr* weights, size_t n, Fr* out_host) {
-  inner_products_impl<false>(c, (const void* const*)polys, count, weights, n, out_host);
-}
-void k_inner_products_u32(Ctx& c, const uint32_t* const* polys, size_t count, const Fr* weights, size_t n,
-                          Fr* out_host) {
-  inner_products_impl<true>(c, (const void* const*)polys, count, weights, n, out_host);
 }
 
 // ------------------------------------------------------------------ small-valued columns (Lasso's dim / read_ts / E / final_cts)
@@ -551,7 +532,6 @@ static Fr prescale_r(const Fr& w) {
 }
 
 // out[i] = sum_k w_k fr_k[i] + sum_k w'_k u32_k[i]  (u32 columns of their own lengths, zero beyond)
-constexpr int LCM_MAX_FR = 8, LCM_MAX_SMALL = 24;
 struct LcMixed {
   const Fr* fr[LCM_MAX_FR];
   Fr wfr[LCM_MAX_FR];
@@ -594,7 +574,6 @@ void k_lincomb_mixed(Ctx& c, const Fr* const* fr, const Fr* wfr, size_t num_fr, 
 // view: out[i] = (1 - x) g[i] + x g[i + half] is 2 x 8 multiply-adds per column into one wide accumulator and ONE Montgomery
 // reduction (the weights coef_k (1 - x), coef_k x arrive times R).  Reads 8 B per column and output entry where the fold of
 // the batch opening's merged tables (k_lincomb_fold) read 64 B per table: 2^24 AND lookups, 12 columns against 4 tables.
-constexpr int LCF_MAX = 24;
 struct LcFoldSmall {
   const uint32_t* p[LCF_MAX];
   uint64_t len[LCF_MAX];
@@ -823,7 +802,6 @@ void k_inner_products_quads(Ctx& c, const uint32_t* const* cols, const size_t* l
 //   out[i] = sum_k w_k ((1-r1)(1-r0) col_k[4i] + (1-r1) r0 col_k[4i+1] + r1 (1-r0) col_k[4i+2] + r1 r0 col_k[4i+3]),
 // 4 x 8 multiply-adds per column and ONE Montgomery reduction per bound entry (the 4 weights of a column arrive times R) -
 // and the round's q(0), q(1) = sum_b eq_level[b] out[2b + e] from the even / odd lanes.
-constexpr int LCB_MAX = 24;
 struct LcBind2 {
   const uint32_t* p[LCB_MAX];
   uint64_t quads[LCB_MAX];

@@ -368,6 +368,9 @@ lh_status lh_ctx_comm_phase_stats(lh_ctx*, uint64_t out[16], int reset);
  * ctx's workspace arena in bytes (the prover's temporaries; its helper ctx's arena included), out[1] = bytes the arena
  * holds from the device now, out[2] / out[3] = free / total bytes of the device as the runtime reports them (all processes) */
 lh_status lh_ctx_memory_stats(lh_ctx*, uint64_t out[4]);
+/* the compute units of the ctx's device: what the kernels size their capped grids by (8 workgroups per unit for the round
+ * kernels) - a test that wants a launch to stride asks here */
+lh_status lh_ctx_compute_units(lh_ctx*, size_t* out);
 /* the CPUs next to the ctx's device: its PCI address ("0000:72:00.0") into bus_id and the kernel's list of the CPUs on its
  * NUMA node ("0-63,128-191", sysfs local_cpulist) into cpulist - empty where the system does not say.  A deployment binds
  * the thread that proves to them (one process per GPU, bound to the GPU's node): the small proofs are a few hundred PCIe
@@ -855,6 +858,51 @@ lh_status lh_debug_lasso_counters(lh_ctx*, const uint32_t* const* d_dims, size_t
 /* the pass plan of one slab (host only, no GPU needed): the number of radix passes, the digit width of each (rb[passes ..
  * 8) = 0; `bits` above the key width count as the key width) and the temporary device bytes the sort takes */
 lh_status lh_debug_sort_plan(size_t n, unsigned bits, int key_bytes, unsigned* passes, unsigned rb[8], size_t* temp_bytes);
+
+/* development / tests: the kernels that work on 32-bit columns without their field-element views (csrc/kernels_poly.hip,
+ * "small-valued columns"), one host function per operation, for tests/test_gpu_u32_columns.py.  Pointers named d_ are
+ * device memory of lh_alloc; field elements are passed as everywhere in this header.  `n` is the operation's size:
+ *   INNER_PRODUCTS_SMALL        out_host[k] = <d_cols[k], d_weights>, n entries each
+ *   INNER_PRODUCTS_SMALL_HALF   out_host[k] = <d_cols[k], eq(y)> over 2 n entries; d_weights = eq(y[1..]) (n entries), r0 = y0
+ *   INNER_PRODUCTS_SMALL_QUADS  one column of 4 n entries, d_weights = e0 (2 n entries); out_host[0..3] = sum_b e0[b] col[2b],
+ *                               sum_b e0[b] col[2b+1], sum_q (e0[2q] + e0[2q+1]) col[4q+2], the same with col[4q+3]
+ *   INNER_PRODUCTS_QUADS        d_out[4 k + t] = sum_{q < n} d_weights[q] d_cols[k][4 q + t]; entries from lens[k] on are zero
+ *   LINCOMB_MIXED               d_out[i] = sum_k w_fr[k] d_fr[k][i] + sum_k w[k] d_cols[k][i], i < n (zero from lens[k] on)
+ *   LINCOMB_FOLD_SMALL          d_out[i] = (1 - r0) g[i] + r0 g[i + n], g = sum_k w[k] d_cols[k] (zero from lens[k] on), i < n;
+ *                               *taken = 0 and nothing written when count is 0 or above 24
+ *   LINCOMB_BIND2               d_out[i] = sum_k w[k] (d_cols[k][4i .. 4i+3] bound with (r0, r1)), i < 2 n; out_host[e] =
+ *                               sum_{b < n} d_weights[b] d_out[2b + e], e = 0, 1
+ *   SC_ROUND_BIND2              the same of one column with weight one; out_host[0] = sum_{b < n} d_weights[b] d_out[2b + 1]
+ * Refused with LH_ERR_ARG before anything is launched: a null pointer that the operation reads or writes, n == 0, more inputs
+ * than a launch takes (LINCOMB_MIXED: 8 tables and 24 columns, LINCOMB_BIND2: 24 columns), and for the operations that read a
+ * column 16 bytes at a time (the two QUADS and the two BIND2) a column that is not 16-byte aligned or a length that is no
+ * multiple of 4.  The call returns after the stream has drained. */
+enum {
+  LH_U32_INNER_PRODUCTS_SMALL = 0,
+  LH_U32_INNER_PRODUCTS_SMALL_HALF = 1,
+  LH_U32_INNER_PRODUCTS_SMALL_QUADS = 2,
+  LH_U32_INNER_PRODUCTS_QUADS = 3,
+  LH_U32_LINCOMB_MIXED = 4,
+  LH_U32_LINCOMB_FOLD_SMALL = 5,
+  LH_U32_LINCOMB_BIND2 = 6,
+  LH_U32_SC_ROUND_BIND2 = 7
+};
+typedef struct lh_debug_u32_args {
+  const uint32_t* const* d_cols; /* `count` columns */
+  const size_t* lens;            /* their lengths in entries (the operations that say "lens" above) */
+  const lh_fr* w;                /* their weights, host (LINCOMB_*) */
+  size_t count;
+  const lh_fr* d_weights;        /* the weight / eq table */
+  size_t n;
+  const lh_fr* const* d_fr;      /* LINCOMB_MIXED: num_fr tables of n field elements and their weights (host) */
+  const lh_fr* w_fr;
+  size_t num_fr;
+  lh_fr r0, r1;
+  lh_fr* d_out;
+  lh_fr* out_host;
+  int* taken;                    /* LINCOMB_FOLD_SMALL */
+} lh_debug_u32_args;
+lh_status lh_debug_u32_columns(lh_ctx*, int op, const lh_debug_u32_args*);
 
 /* ---------------------------------------------------------------- measurement (bench.py)
  * Per-kernel HIP-event timing on the ctx stream.  While enabled every instrumented launch is

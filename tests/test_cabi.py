@@ -33,6 +33,7 @@ def test_struct_layouts(hl):
         or C.sizeof(_ffi.lh_lasso_table) % 8 == 0
     assert C.sizeof(_ffi.lh_transcript) == 8 * C.sizeof(C.c_void_p)
     assert C.sizeof(_ffi.lh_g2) == 128
+    assert C.sizeof(_ffi.lh_debug_u32_args) == 9 * 8 + 2 * 32 + 3 * 8 and _ffi.lh_debug_u32_args.r0.offset == 72
 
 
 def test_marshalling(hl):
@@ -130,12 +131,30 @@ def test_null_arguments_are_errors_not_crashes(hl, ctx):
         lib.lh_evaluate(h, None, 1, 3, (_ffi.lh_fr * 3)(), C.byref(fr)),
         lib.lh_lincomb(h, (C.c_void_p * 1)(poly.ptr), None, 1, 8, poly.ptr),
         lib.lh_upload(h, None, b"1234", 4),
+        lib.lh_ctx_compute_units(h, None),
         lib.lh_download(h, None, poly.ptr, 4),
         lib.lh_zeromorph_open(h, None, 8, poly.ptr, 3, (_ffi.lh_fr * 3)(), tr.p),
         lib.lh_zeromorph_batch_commit(h, None, 8, (C.c_void_p * 1)(poly.ptr), 1, 3, C.byref(out)),
     ]
     assert bad == [_ffi.LH_ERR_ARG] * len(bad), bad
     assert b"null argument" in lib.lh_last_error() or b"transcript" in lib.lh_last_error()
+    # the test-only entry of the 32-bit column kernels: every pointer of its argument block that an operation uses
+    col, dst = ctx.upload(bytes(64)), ctx.alloc(4 * 32)
+    taken, sums = C.c_int(0), (_ffi.lh_fr * 4)()
+    full = dict(d_cols=(C.c_void_p * 1)(col.ptr), lens=(C.c_size_t * 1)(4), w=(_ffi.lh_fr * 1)(), count=1, d_weights=poly.ptr,
+                n=1, d_fr=(C.c_void_p * 1)(poly.ptr), w_fr=(_ffi.lh_fr * 1)(), num_fr=1, d_out=dst.ptr, out_host=sums,
+                taken=C.pointer(taken))
+    used = {"d_cols": range(8), "lens": (3, 4, 5, 6), "w": (4, 5, 6), "d_weights": (0, 1, 2, 3, 6, 7), "d_fr": (4,), "w_fr": (4,),
+            "d_out": (3, 4, 5, 6, 7), "out_host": (0, 1, 2, 6, 7), "taken": (5,)}
+    bad = [lib.lh_debug_u32_columns(None, 0, C.byref(_ffi.lh_debug_u32_args(**full))), lib.lh_debug_u32_columns(h, 0, None)]
+    for field, ops in used.items():
+        for op in ops:
+            bad.append(lib.lh_debug_u32_columns(h, op, C.byref(_ffi.lh_debug_u32_args(**{k: v for k, v in full.items() if k != field}))))
+            assert b"null argument" in lib.lh_last_error(), (field, op, lib.lh_last_error())
+    bad.append(lib.lh_debug_u32_columns(h, 0, C.byref(_ffi.lh_debug_u32_args(**dict(full, d_cols=(C.c_void_p * 1)(None))))))
+    assert bad == [_ffi.LH_ERR_ARG] * len(bad), bad
+    for op in range(8):  # ... and with everything in place each operation runs
+        assert lib.lh_debug_u32_columns(h, op, C.byref(_ffi.lh_debug_u32_args(**full))) == _ffi.LH_OK, (op, lib.lh_last_error())
     # an empty vector may be NULL: nothing to read, nothing written
     assert lib.lh_mkzg_batch_commit(h, pp.h, None, 0, 3, None) == _ffi.LH_OK
     assert lib.lh_fr_add(h, None, None, 0, None) == _ffi.LH_OK
