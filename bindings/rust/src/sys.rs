@@ -469,4 +469,26 @@ extern "C" {
     pub fn lh_brakedown_batch_verify(pp: *const c_void, num_vars: usize, roots: *const u8, num_comms: usize,
                                      points: *const Fr, num_points: usize, evals: *const lh_evaluation,
                                      num_evals: usize, t: *mut lh_transcript, ht: *mut lh_hash_transcript) -> lh_status;
+    pub fn lh_brakedown_comm_tree(ctx: *mut lh_ctx, comm: *const c_void, out: *mut u8) -> lh_status;
+    pub fn lh_brakedown_comm_stage(ctx: *mut lh_ctx, pp: *const c_void, comm: *const c_void, out: *mut Fr) -> lh_status;
+    // HyperPlonk over Brakedown: the commitments of the preprocess and permutation polys on the prove side, their roots
+    // (32 bytes each) on the verify side; hvp's two point arrays are ignored
+    pub fn lh_hyperplonk_prove_brakedown(ctx: *mut lh_ctx, param: *const c_void, pp: *const lh_hp_param,
+                                         preprocess_comms: *const *mut c_void, permutation_comms: *const *mut c_void,
+                                         instances: *const *const Fr, d_witness_polys: *const *const Fr,
+                                         t: *mut lh_transcript, ht: *mut lh_hash_transcript) -> lh_status;
+    pub fn lh_hyperplonk_prove_phases_brakedown(ctx: *mut lh_ctx, param: *const c_void, pp: *const lh_hp_param,
+                                                preprocess_comms: *const *mut c_void, permutation_comms: *const *mut c_void,
+                                                num_phases: usize, num_witness_polys: *const usize,
+                                                num_challenges: *const usize, instances: *const *const Fr,
+                                                circuit: *const lh_hp_circuit, t: *mut lh_transcript,
+                                                ht: *mut lh_hash_transcript) -> lh_status;
+    pub fn lh_hyperplonk_verify_brakedown(param: *const c_void, hvp: *const lh_hp_vparam, preprocess_roots: *const u8,
+                                          permutation_roots: *const u8, instances: *const *const Fr, t: *mut lh_transcript,
+                                          ht: *mut lh_hash_transcript) -> lh_status;
+    pub fn lh_hyperplonk_verify_phases_brakedown(param: *const c_void, hvp: *const lh_hp_vparam, preprocess_roots: *const u8,
+                                                 permutation_roots: *const u8, num_phases: usize,
+                                                 num_witness_polys: *const usize, num_challenges: *const usize,
+                                                 instances: *const *const Fr, t: *mut lh_transcript,
+                                                 ht: *mut lh_hash_transcript) -> lh_status;
 }

@@ -1375,6 +1375,19 @@ class BrakedownCommitment:
         _check(self.lib.lh_brakedown_comm_rows_device(self.h, C.byref(p)))
         return p.value
 
+    def tree(self, codeword_len):
+        """the Merkle tree as raw bytes: (2 << depth) - 1 digests of 32 bytes, leaves first, the root last"""
+        n = (2 << (codeword_len - 1).bit_length()) - 1
+        out = C.create_string_buffer(32 * n)
+        _check(self.lib.lh_brakedown_comm_tree(self.ctx.h, self.h, out))
+        return out.raw
+
+    def staged(self, pp):
+        """the matrix as the staged open reads it: codeword_len x num_rows, column-major, as raw bytes"""
+        out = C.create_string_buffer(32 * pp.num_rows * pp.codeword_len)
+        _check(self.lib.lh_brakedown_comm_stage(self.ctx.h, pp.h, self.h, out))
+        return out.raw
+
     def free(self):
         if self.h:
             self.lib.lh_brakedown_comm_free(self.h)
@@ -1414,7 +1427,9 @@ class Brakedown:
 
     @staticmethod
     def commit(pp, poly):
-        return Brakedown.batch_commit(pp, [poly])[0]
+        out = C.c_void_p()
+        _check(pp.lib.lh_brakedown_commit(pp.ctx.h, pp.h, poly.ptr, poly.num_vars, C.byref(out)))
+        return BrakedownCommitment(pp.ctx, out)
 
     @staticmethod
     def batch_commit_and_write(pp, polys, transcript):

@@ -377,7 +377,22 @@ SIGNATURES = {
     "lh_brakedown_comm_root": (C.c_int, [_P, C.c_char_p]),
     "lh_brakedown_comm_rows": (C.c_int, [_P, _P, _P]),
     "lh_brakedown_comm_rows_device": (C.c_int, [_P, C.POINTER(_P)]),
+    "lh_brakedown_comm_tree": (C.c_int, [_P, _P, C.c_char_p]),
+    "lh_brakedown_comm_stage": (C.c_int, [_P, _P, _P, _P]),
     "lh_brakedown_comm_free": (None, [_P]),
+    "lh_hyperplonk_prove_brakedown": (C.c_int, [_P, _P, C.POINTER(lh_hp_param), C.POINTER(_P), C.POINTER(_P),
+                                                C.POINTER(C.POINTER(lh_fr)), C.POINTER(_P), C.POINTER(lh_transcript),
+                                                C.POINTER(lh_hash_transcript)]),
+    "lh_hyperplonk_prove_phases_brakedown": (C.c_int, [_P, _P, C.POINTER(lh_hp_param), C.POINTER(_P), C.POINTER(_P), _SZ,
+                                                       C.POINTER(_SZ), C.POINTER(_SZ), C.POINTER(C.POINTER(lh_fr)),
+                                                       C.POINTER(lh_hp_circuit), C.POINTER(lh_transcript),
+                                                       C.POINTER(lh_hash_transcript)]),
+    "lh_hyperplonk_verify_brakedown": (C.c_int, [_P, C.POINTER(lh_hp_vparam), C.c_char_p, C.c_char_p,
+                                                 C.POINTER(C.POINTER(lh_fr)), C.POINTER(lh_transcript),
+                                                 C.POINTER(lh_hash_transcript)]),
+    "lh_hyperplonk_verify_phases_brakedown": (C.c_int, [_P, C.POINTER(lh_hp_vparam), C.c_char_p, C.c_char_p, _SZ,
+                                                        C.POINTER(_SZ), C.POINTER(_SZ), C.POINTER(C.POINTER(lh_fr)),
+                                                        C.POINTER(lh_transcript), C.POINTER(lh_hash_transcript)]),
     "lh_brakedown_open": (C.c_int, [_P, _P, _P, _SZ, _P, C.POINTER(lh_fr), C.POINTER(lh_transcript),
                                     C.POINTER(lh_hash_transcript)]),
     "lh_brakedown_batch_open": (C.c_int, [_P, _P, _SZ, C.POINTER(_P), C.POINTER(_P), _SZ, C.POINTER(lh_fr), _SZ,

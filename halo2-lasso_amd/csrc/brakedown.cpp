@@ -8,6 +8,7 @@
 #include "brakedown.hpp"
 #include <math.h>
 #include <algorithm>
+#include <map>
 #include <memory>
 
 namespace lh {
@@ -173,9 +174,13 @@ BdParam::~BdParam() {
 }
 BdComm::~BdComm() {
   if (device < 0) return;
+  if (slab || borrowed) return;  // (a batch's allocation goes with its last commitment; borrowed memory is the caller's)
   (void)hipSetDevice(device);
   if (d_rows) (void)hipFree(d_rows);
   if (d_hashes) (void)hipFree(d_hashes);
+}
+BdStage::~BdStage() {
+  if (cols) (void)hipHostFree(cols);
 }
 
 void brakedown_derive(BdParam& p, size_t num_vars, int spec) {
@@ -264,19 +269,9 @@ static void check_vars(const BdParam& p, size_t num_vars, const char* what) {
                                               std::to_string(num_vars) + ")");
 }
 
-BdComm* brakedown_commit(Ctx& c, const BdParam& p, const Fr* d_poly, size_t num_vars) {
-  check_vars(p, num_vars, "commit");
-  LH_REQUIRE(p.device == c.device, LH_ERR_ARG, "brakedown: parameters were not set up on this ctx's device");
-  const size_t R = p.num_rows, cw = p.codeword_len, width = (size_t)1 << p.depth;
-  std::unique_ptr<BdComm> comm(new BdComm());
-  comm->num_rows = R, comm->codeword_len = cw, comm->depth = p.depth, comm->device = c.device;
-  LH_HIP(hipMalloc((void**)&comm->d_rows, R * cw * sizeof(Fr)));
-  LH_HIP(hipMalloc((void**)&comm->d_hashes, ((2 * width) - 1) * 32));
-  Fr* rows = comm->d_rows;
-  // row r's message is poly[r * row_len ..]
-  LH_HIP(hipMemcpy2DAsync(rows, cw * sizeof(Fr), d_poly, p.row_len * sizeof(Fr), p.row_len * sizeof(Fr), R,
-                          hipMemcpyDeviceToDevice, c.stream));
-  // the cascade: a[k] forward, the Reed-Solomon tail, b[k] in reverse
+// the cascade over `R` rows that hold their messages: a[k] forward, the Reed-Solomon tail, b[k] in reverse
+static void encode_rows(Ctx& c, const BdParam& p, Fr* rows, size_t R) {
+  const size_t cw = p.codeword_len;
   size_t in_off = 0;
   for (size_t k = 0; k + 1 < p.a.size(); k++) {
     k_bd_gather(c, rows, R, cw, in_off, in_off + p.a[k].dim.n, p.a[k]);
@@ -292,6 +287,21 @@ BdComm* brakedown_commit(Ctx& c, const BdParam& p, const Fr* d_poly, size_t num_
     out_off += p.b[k].dim.m;
   }
   LH_REQUIRE(in_off == p.row_len && out_off == cw, LH_ERR_ARG, "brakedown: cascade does not tile the codeword");
+}
+
+BdComm* brakedown_commit(Ctx& c, const BdParam& p, const Fr* d_poly, size_t num_vars) {
+  check_vars(p, num_vars, "commit");
+  LH_REQUIRE(p.device == c.device, LH_ERR_ARG, "brakedown: parameters were not set up on this ctx's device");
+  const size_t R = p.num_rows, cw = p.codeword_len, width = (size_t)1 << p.depth;
+  std::unique_ptr<BdComm> comm(new BdComm());
+  comm->num_rows = R, comm->codeword_len = cw, comm->depth = p.depth, comm->device = c.device;
+  LH_HIP(hipMalloc((void**)&comm->d_rows, R * cw * sizeof(Fr)));
+  LH_HIP(hipMalloc((void**)&comm->d_hashes, ((2 * width) - 1) * 32));
+  Fr* rows = comm->d_rows;
+  // row r's message is poly[r * row_len ..]
+  LH_HIP(hipMemcpy2DAsync(rows, cw * sizeof(Fr), d_poly, p.row_len * sizeof(Fr), p.row_len * sizeof(Fr), R,
+                          hipMemcpyDeviceToDevice, c.stream));
+  encode_rows(c, p, rows, R);
   // column leaves, then one launch per tree level
   k_bd_hash_columns(c, rows, R, cw, width, comm->d_hashes);
   size_t off = 0;
@@ -303,10 +313,90 @@ BdComm* brakedown_commit(Ctx& c, const BdParam& p, const Fr* d_poly, size_t num_
   return comm.release();
 }
 
+// ------------------------------------------------------------------ batch commit: P polys, the launches of one
+// The slab: P * num_rows rows of codeword_len, then P trees of (2 << depth) - 1 digests, then P roots gathered for the copy.
+static size_t batch_rows_bytes(const BdParam& p, size_t P) {
+  return (P * p.num_rows * p.codeword_len * sizeof(Fr) + 255) & ~(size_t)255;
+}
+static size_t batch_tree_words(const BdParam& p) { return 4 * (((size_t)2 << p.depth) - 1); }
+size_t brakedown_batch_bytes(const BdParam& p, size_t P) {
+  return batch_rows_bytes(p, P) + ((P * batch_tree_words(p) * 8 + 255) & ~(size_t)255) + ((P * 32 + 255) & ~(size_t)255) +
+         ((P * sizeof(Fr*) + 255) & ~(size_t)255);
+}
+
+std::vector<std::unique_ptr<BdComm>> brakedown_batch_commit(Ctx& c, const BdParam& p, const Fr* const* d_polys, size_t P,
+                                                            size_t num_vars, void* slab_mem) {
+  std::vector<std::unique_ptr<BdComm>> comms;
+  if (!P) return comms;
+  check_vars(p, num_vars, "commit");
+  LH_REQUIRE(p.device == c.device, LH_ERR_ARG, "brakedown: parameters were not set up on this ctx's device");
+  const size_t R = p.num_rows, cw = p.codeword_len, width = (size_t)1 << p.depth, tree_words = batch_tree_words(p);
+  std::shared_ptr<void> owner;
+  if (!slab_mem) {
+    const int device = c.device;
+    LH_HIP(hipMalloc(&slab_mem, brakedown_batch_bytes(p, P)));
+    owner = std::shared_ptr<void>(slab_mem, [device](void* q) {
+      (void)hipSetDevice(device);
+      (void)hipFree(q);
+    });
+  }
+  Fr* rows = (Fr*)slab_mem;
+  uint64_t* trees = (uint64_t*)((char*)slab_mem + batch_rows_bytes(p, P));
+  uint64_t* d_roots = (uint64_t*)((char*)trees + ((P * tree_words * 8 + 255) & ~(size_t)255));
+  const Fr** d_ptrs = (const Fr**)((char*)d_roots + ((P * 32 + 255) & ~(size_t)255));
+  LH_HIP(hipMemcpyAsync(d_ptrs, d_polys, P * sizeof(Fr*), hipMemcpyHostToDevice, c.stream));
+  k_bd_load_rows(c, d_ptrs, P, R, p.row_len, cw, rows);
+  encode_rows(c, p, rows, P * R);  // (rows are independent: the slab is P * R of them)
+  k_bd_hash_columns_batch(c, rows, P, R, cw, width, trees, tree_words);
+  size_t off = 0;
+  for (size_t w = width; w > 1; w >>= 1) {
+    k_bd_merkle_level_batch(c, trees, P, tree_words, 4 * off, w / 2, 4 * (off + w));
+    off += w;
+  }
+  k_bd_gather_roots(c, trees, P, tree_words, 4 * off, d_roots);
+  std::vector<uint8_t> roots(32 * P);
+  c.d2h(roots.data(), d_roots, 32 * P);  // (synchronises: the caller's pointer table has been read by then)
+  for (size_t i = 0; i < P; i++) {
+    std::unique_ptr<BdComm> comm(new BdComm());
+    comm->num_rows = R, comm->codeword_len = cw, comm->depth = p.depth, comm->device = c.device;
+    comm->d_rows = rows + i * R * cw, comm->d_hashes = trees + i * tree_words;
+    comm->slab = owner, comm->borrowed = !owner;
+    memcpy(comm->root, roots.data() + 32 * i, 32);
+    comms.push_back(std::move(comm));
+  }
+  return comms;
+}
+
 // ------------------------------------------------------------------ open (brakedown.rs:212-276)
+void brakedown_stage(Ctx& c, const BdParam& p, const BdComm& comm, BdStage& st) {
+  LH_REQUIRE(comm.num_rows == p.num_rows && comm.codeword_len == p.codeword_len && comm.device == c.device, LH_ERR_ARG,
+             "brakedown: commitment does not belong to these parameters");
+  if (st.of == &comm) return;
+  const size_t R = p.num_rows, cw = p.codeword_len, bytes = R * cw * sizeof(Fr);
+  st.of = nullptr;
+  if (bytes > st.capacity) {
+    if (st.cols) (void)hipHostFree(st.cols);
+    st.cols = nullptr, st.capacity = 0;
+    LH_HIP(hipHostMalloc((void**)&st.cols, bytes, hipHostMallocDefault));
+    st.capacity = bytes;
+  }
+  if (R == 1) {  // the row is its own transpose
+    LH_HIP(hipMemcpyAsync(st.cols, comm.d_rows, bytes, hipMemcpyDeviceToHost, c.stream));
+    c.sync();
+  } else {
+    ArenaScope scope(c.arena);
+    Fr* t = c.arena.alloc_n<Fr>(R * cw);
+    k_bd_stage_columns(c, comm.d_rows, R, cw, t);
+    LH_HIP(hipMemcpyAsync(st.cols, t, bytes, hipMemcpyDeviceToHost, c.stream));
+    c.sync();
+  }
+  st.of = &comm;
+}
+
 void brakedown_open(Ctx& c, const BdParam& p, const Fr* d_poly, size_t num_vars, BdComm& comm, const HFr* point,
-                    Transcript& tr, HashTranscript& ht) {
+                    Transcript& tr, HashTranscript& ht, const BdStage* staged) {
   check_vars(p, num_vars, "open");
+  LH_REQUIRE(!staged || staged->of == &comm, LH_ERR_ARG, "brakedown: the staged matrix is another commitment's");
   LH_REQUIRE(comm.num_rows == p.num_rows && comm.codeword_len == p.codeword_len && comm.device == c.device, LH_ERR_ARG,
              "brakedown: commitment does not belong to these parameters");
   const size_t R = p.num_rows, row_len = p.row_len, cw = p.codeword_len, k_rows = log2_ceil(R);
@@ -339,15 +429,19 @@ void brakedown_open(Ctx& c, const BdParam& p, const Fr* d_poly, size_t num_vars,
     comm.host_tree.resize(4 * ((2 << p.depth) - 1));
     c.d2h(comm.host_tree.data(), comm.d_hashes, comm.host_tree.size() * 8);
   }
-  HFr* col = (HFr*)c.pin(R * 32);
+  HFr* col = staged ? nullptr : (HFr*)c.pin(R * 32);
   std::vector<HFr> items(R);
   for (size_t i = 0; i < p.num_column_opening; i++) {
     uint8_t repr[32];
     tr.squeeze_challenge().to_repr(repr);  // squeeze_challenge_idx (brakedown.rs:427-435)
     const size_t column = (size_t)(((uint32_t)repr[0] | (uint32_t)repr[1] << 8 | (uint32_t)repr[2] << 16 |
                                     (uint32_t)repr[3] << 24) % cw);
-    LH_HIP(hipMemcpy2DAsync(col, 32, comm.d_rows + column, cw * sizeof(Fr), 32, R, hipMemcpyDeviceToHost, c.stream));
-    c.sync();
+    if (staged) {
+      col = staged->cols + column * R;
+    } else {
+      LH_HIP(hipMemcpy2DAsync(col, 32, comm.d_rows + column, cw * sizeof(Fr), 32, R, hipMemcpyDeviceToHost, c.stream));
+      c.sync();
+    }
     items.assign(col, col + R);
     tr.write_field_elements(items);
     size_t offset = 0;
@@ -356,6 +450,72 @@ void brakedown_open(Ctx& c, const BdParam& p, const Fr* d_poly, size_t num_vars,
       offset += (size_t)1 << (p.depth - idx);
     }
   }
+}
+
+// ------------------------------------------------------------------ the provers' PCS (backend/hyperplonk.rs:76-95)
+namespace {
+struct BdStore {
+  std::map<const Fr*, BdComm*> by_poly;
+  std::vector<std::unique_ptr<BdComm>> own;  // (views into arena slabs of the proof's scope: nothing to free on the device)
+  BdStage stage;
+};
+}  // namespace
+
+Pcs brakedown_pcs(Ctx& c, const BdParam& p, HashTranscript& ht, const std::vector<BdGiven>& given) {
+  std::shared_ptr<BdStore> store(new BdStore());
+  for (const BdGiven& g : given) {
+    LH_REQUIRE(g.d_poly && g.comm, LH_ERR_ARG, "brakedown: null poly or commitment");
+    store->by_poly[g.d_poly] = g.comm;
+  }
+  Pcs pcs;
+  pcs.max_vars = p.num_vars;
+  pcs.commit_and_write = [&c, &p, &ht, store](const Fr* const* polys, size_t np, size_t nv, Transcript&) {
+    if (!np) return;
+    void* slab = c.arena.alloc(brakedown_batch_bytes(p, np));  // released with the prove's ArenaScope
+    std::vector<std::unique_ptr<BdComm>> comms = brakedown_batch_commit(c, p, polys, np, nv, slab);
+    for (size_t i = 0; i < np; i++) {
+      ht.write_hash(comms[i]->root);
+      store->by_poly[polys[i]] = comms[i].get();
+      store->own.push_back(std::move(comms[i]));
+    }
+  };
+  pcs.batch_open = [&c, &p, &ht, store](size_t nv, const Fr* const* polys, size_t np, const HFr* points, size_t npts,
+                                        const lh_evaluation* evals, size_t ne, Transcript& tr, const SmallPoly*) {
+    for (size_t i = 0; i < ne; i++) {  // (poly-major: a poly queried at several points is staged once)
+      const lh_evaluation& e = evals[i];
+      LH_REQUIRE(e.poly < np && e.point < npts && polys[e.poly], LH_ERR_ARG, "brakedown batch_open: evaluation out of range");
+      auto it = store->by_poly.find(polys[e.poly]);
+      LH_REQUIRE(it != store->by_poly.end(), LH_ERR_ARG, "brakedown batch_open: no commitment for an opened poly");
+      brakedown_stage(c, p, *it->second, store->stage);
+      brakedown_open(c, p, polys[e.poly], nv, *it->second, points + (size_t)e.point * nv, tr, ht, &store->stage);
+    }
+  };
+  return pcs;
+}
+
+void brakedown_hyperplonk_prove_phases(Ctx& c, const BdParam& p, const lh_hp_param& pp, BdComm* const* preprocess_comms,
+                                       BdComm* const* permutation_comms, const HpPhases& ph, const HFr* const* instances,
+                                       Transcript& tr, HashTranscript& ht) {
+  LH_REQUIRE(pp.num_lasso_lookups == 0, LH_ERR_ARG,
+             "hyperplonk over brakedown: Lasso lookups are not supported (their column commitments are points)");
+  LH_REQUIRE(!Shard(c).on, LH_ERR_ARG, "hyperplonk over brakedown: sharded proves are not supported");
+  LH_REQUIRE(pp.num_vars == p.num_vars, LH_ERR_ARG,
+             "hyperplonk over brakedown: the circuit has " + std::to_string(pp.num_vars) + " variables, the param " +
+                 std::to_string(p.num_vars));
+  LH_REQUIRE(p.device == c.device, LH_ERR_ARG, "brakedown: parameters were not set up on this ctx's device");
+  std::vector<BdGiven> given;
+  for (size_t i = 0; i < pp.num_preprocess_polys; i++) {
+    LH_REQUIRE(pp.d_preprocess_polys && pp.d_preprocess_polys[i] && preprocess_comms[i], LH_ERR_ARG,
+               "null argument: preprocess poly or commitment");
+    given.push_back(BdGiven{(const Fr*)pp.d_preprocess_polys[i], preprocess_comms[i]});
+  }
+  for (size_t i = 0; i < pp.num_permutation_polys; i++) {
+    LH_REQUIRE(pp.d_permutation_polys && pp.d_permutation_polys[i] && permutation_comms[i], LH_ERR_ARG,
+               "null argument: permutation poly or commitment");
+    given.push_back(BdGiven{(const Fr*)pp.d_permutation_polys[i], permutation_comms[i]});
+  }
+  const Pcs pcs = brakedown_pcs(c, p, ht, given);  // (dies with this frame, also when the prove throws)
+  hyperplonk_prove_phases(c, pcs, pp, ph, instances, tr);
 }
 
 }  // namespace lh

@@ -2,6 +2,7 @@
 // sampler, the host encoder, and the device-resident commitment.  Kernels in kernels_brakedown.hip; the prover half in
 // brakedown.cpp, the verifier in verifier.cpp.  DESIGN.md §12.
 #pragma once
+#include <memory>
 #include "host.hpp"
 
 namespace lh {
@@ -38,7 +39,24 @@ struct BdComm {
   uint64_t* d_hashes = nullptr; // (2 << depth) - 1 digests of 4 words: leaves, then each level up, the root last
   uint8_t root[32];
   std::vector<uint64_t> host_tree;  // filled by the first open: the paths are read on the host
+  // a commitment of a batch (brakedown_batch_commit): d_rows / d_hashes point into the batch's one allocation, which the
+  // last commitment of the batch frees; or into memory the caller owns (`borrowed`: an arena slab of a proof)
+  std::shared_ptr<void> slab;
+  bool borrowed = false;
   ~BdComm();
+};
+
+// The encoded matrix of ONE commitment on the host, column-major (column c's num_rows entries at c * num_rows), in pinned
+// memory: every column of every open of that commitment is then a host read (brakedown_open's `staged`).  Staging another
+// commitment replaces it; the buffer grows to the largest matrix staged and is freed with this object.
+struct BdStage {
+  const BdComm* of = nullptr;
+  HFr* cols = nullptr;
+  size_t capacity = 0;  // bytes
+  BdStage() = default;
+  BdStage(const BdStage&) = delete;
+  BdStage& operator=(const BdStage&) = delete;
+  ~BdStage();
 };
 
 // TranscriptWrite / TranscriptRead<Output<Keccak256>, Fr> (util/transcript.rs:240-265): raw 32 bytes, not absorbed
@@ -64,16 +82,54 @@ void brakedown_trim(const BdParam& p, size_t poly_size);
 // LinearCodes::encode: `cw` holds the message in its first row_len entries and gets the codeword
 void brakedown_encode_host(const BdParam& p, HFr* cw);
 BdComm* brakedown_commit(Ctx& c, const BdParam& p, const Fr* d_poly, size_t num_vars);
+// P commits in the launches of one (kernels_brakedown.hip): rows, trees and roots bit-identical to P brakedown_commit
+// calls, the roots back in one copy.  `slab` null: one allocation for the batch, shared by the commitments; otherwise the
+// caller's memory of brakedown_batch_bytes (256-byte aligned), which outlives them.
+size_t brakedown_batch_bytes(const BdParam& p, size_t num_polys);
+std::vector<std::unique_ptr<BdComm>> brakedown_batch_commit(Ctx& c, const BdParam& p, const Fr* const* d_polys,
+                                                            size_t num_polys, size_t num_vars, void* slab = nullptr);
+// `staged` (optional): the commitment's matrix on the host (brakedown_stage): the column openings read it instead of
+// fetching every column from the device; the bytes written are the same
 void brakedown_open(Ctx& c, const BdParam& p, const Fr* d_poly, size_t num_vars, BdComm& comm, const HFr* point,
-                    Transcript& tr, HashTranscript& ht);
+                    Transcript& tr, HashTranscript& ht, const BdStage* staged = nullptr);
+// bd_stage_columns, then one device-to-host copy (num_rows == 1: the row itself, no launch); a no-op when `comm` is staged
+void brakedown_stage(Ctx& c, const BdParam& p, const BdComm& comm, BdStage& st);
 void brakedown_verify(const BdParam& p, const uint8_t root[32], const HFr* point, size_t num_vars, const HFr& eval,
                       Transcript& tr, HashTranscript& ht);
+
+// HyperPlonk over Brakedown (DESIGN.md §12 "Provers").  The Pcs of the prover: commit_and_write commits a phase's polys as
+// one batch into an arena slab of the proof's scope and writes the raw roots through `ht` (no Fiat-Shamir state changes);
+// batch_open is one open per evaluation in order (brakedown.rs:278-300), the commitment of a poly found by its device
+// pointer - the ones made here, or `given` (the preprocess and permutation polys, committed once by the caller) - and its
+// columns read from the staged matrix.  What the proof committed, and the pinned staging, go with the returned object.
+struct BdGiven {
+  const Fr* d_poly;
+  BdComm* comm;
+};
+Pcs brakedown_pcs(Ctx& c, const BdParam& p, HashTranscript& ht, const std::vector<BdGiven>& given);
+// refuses (LH_ERR_ARG) Lasso lookups, a sharded ctx and a circuit of another size than the param's
+void brakedown_hyperplonk_prove_phases(Ctx& c, const BdParam& p, const lh_hp_param& pp, BdComm* const* preprocess_comms,
+                                       BdComm* const* permutation_comms, const HpPhases& ph, const HFr* const* instances,
+                                       Transcript& tr, HashTranscript& ht);
+// verifier.cpp: the roots of the witness, m, h and z polys read with read_hash, the preprocess and permutation roots from
+// the caller (vp's two lh_g1 arrays are ignored), brakedown_verify once per evaluation
+void brakedown_hyperplonk_verify_phases(const BdParam& p, const lh_hp_vparam& vp, const uint8_t* preprocess_roots,
+                                        const uint8_t* permutation_roots, const std::vector<size_t>& num_witness_polys,
+                                        const std::vector<size_t>& num_challenges, const HFr* const* instances,
+                                        Transcript& tr, HashTranscript& ht);
 
 // kernels_brakedown.hip
 void k_bd_gather(Ctx&, Fr* rows, size_t num_rows, size_t cw, size_t in_off, size_t out_off, const BdMatrix& mat);
 void k_bd_reed_solomon(Ctx&, Fr* rows, size_t num_rows, size_t cw, size_t in_off, const BdMatrix& a_last, size_t bn);
 void k_bd_hash_columns(Ctx&, const Fr* rows, size_t num_rows, size_t cw, size_t width, uint64_t* leaves);
 void k_bd_merkle_level(Ctx&, const uint64_t* in, size_t out_n, uint64_t* out);
+void k_bd_load_rows(Ctx&, const Fr* const* d_polys, size_t num_polys, size_t num_rows, size_t row_len, size_t cw, Fr* rows);
+void k_bd_hash_columns_batch(Ctx&, const Fr* rows, size_t num_polys, size_t num_rows, size_t cw, size_t width,
+                             uint64_t* trees, size_t tree_stride);
+void k_bd_merkle_level_batch(Ctx&, uint64_t* trees, size_t num_polys, size_t tree_stride, size_t in_off, size_t out_n,
+                             size_t out_off);
+void k_bd_gather_roots(Ctx&, const uint64_t* trees, size_t num_polys, size_t tree_stride, size_t root_off, uint64_t* out);
+void k_bd_stage_columns(Ctx&, const Fr* rows, size_t num_rows, size_t cw, Fr* out);
 void k_bd_combine(Ctx&, const Fr* poly, size_t num_rows, size_t row_len, const Fr* coeffs, int num_sets, Fr* out);
 
 }  // namespace lh

@@ -1101,20 +1101,23 @@ lh_status lh_brakedown_encode(const lh_brakedown_param* pp, const lh_fr* msg, lh
   memcpy(out, cw.data(), cw.size() * 32);
   LH_CATCH
 }
-lh_status lh_brakedown_commit(lh_ctx* ctx, const lh_brakedown_param* pp, const lh_fr* d_poly, size_t num_vars,
-                              lh_brakedown_comm** out) {
-  return lh_brakedown_batch_commit(ctx, pp, d_poly ? &d_poly : nullptr, 1, num_vars, out);
-}
-lh_status lh_brakedown_batch_commit(lh_ctx* ctx, const lh_brakedown_param* pp, const lh_fr* const* d_polys,
-                                    size_t num_polys, size_t num_vars, lh_brakedown_comm** out) {
+// `as_batch`: the polys as one batch of launches (brakedown.cpp brakedown_batch_commit); lh_brakedown_commit keeps its own
+// kernels and launch shape
+static lh_status bd_commit_entry(lh_ctx* ctx, const lh_brakedown_param* pp, const lh_fr* const* d_polys, size_t num_polys,
+                                 size_t num_vars, lh_brakedown_comm** out, bool as_batch) {
   LH_TRY NEED_CTX(ctx);
   NEED(pp);
   NEED_N(d_polys, num_polys);
   NEED_N(out, num_polys);
   for (size_t i = 0; i < num_polys; i++) LH_REQUIRE(d_polys[i], LH_ERR_ARG, "null argument: d_polys[i]");
   std::vector<std::unique_ptr<lh_brakedown_comm>> comms;
-  for (size_t i = 0; i < num_polys; i++) {  // batch_commit is one commit per poly (brakedown.rs:198-210)
-    std::unique_ptr<BdComm> c(brakedown_commit(ctx->c, pp->p, (const Fr*)d_polys[i], num_vars));
+  // batch_commit is one commit per poly (brakedown.rs:198-210): as one batch of launches, or literally
+  std::vector<std::unique_ptr<BdComm>> batch;
+  if (as_batch && num_polys && ctx->c.opt.brakedown_batch_commit)
+    batch = brakedown_batch_commit(ctx->c, pp->p, (const Fr* const*)d_polys, num_polys, num_vars);
+  for (size_t i = 0; i < num_polys; i++) {
+    std::unique_ptr<BdComm> c(batch.empty() ? brakedown_commit(ctx->c, pp->p, (const Fr*)d_polys[i], num_vars)
+                                            : batch[i].release());
     std::unique_ptr<lh_brakedown_comm> w(new lh_brakedown_comm());
     std::swap(w->c, *c);
     c->device = -1;
@@ -1122,6 +1125,14 @@ lh_status lh_brakedown_batch_commit(lh_ctx* ctx, const lh_brakedown_param* pp, c
   }
   for (size_t i = 0; i < num_polys; i++) out[i] = comms[i].release();
   LH_CATCH
+}
+lh_status lh_brakedown_commit(lh_ctx* ctx, const lh_brakedown_param* pp, const lh_fr* d_poly, size_t num_vars,
+                              lh_brakedown_comm** out) {
+  return bd_commit_entry(ctx, pp, d_poly ? &d_poly : nullptr, 1, num_vars, out, false);
+}
+lh_status lh_brakedown_batch_commit(lh_ctx* ctx, const lh_brakedown_param* pp, const lh_fr* const* d_polys,
+                                    size_t num_polys, size_t num_vars, lh_brakedown_comm** out) {
+  return bd_commit_entry(ctx, pp, d_polys, num_polys, num_vars, out, true);
 }
 lh_status lh_brakedown_comm_root(const lh_brakedown_comm* comm, uint8_t* out32) {
   LH_TRY
@@ -1144,6 +1155,25 @@ lh_status lh_brakedown_comm_rows_device(const lh_brakedown_comm* comm, lh_fr** d
   NEED(comm);
   NEED(d_out);
   *d_out = (lh_fr*)comm->c.d_rows;
+  LH_CATCH
+}
+lh_status lh_brakedown_comm_tree(lh_ctx* ctx, const lh_brakedown_comm* comm, uint8_t* out) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(comm);
+  NEED(out);
+  LH_HIP(hipMemcpyAsync(out, comm->c.d_hashes, (((size_t)2 << comm->c.depth) - 1) * 32, hipMemcpyDeviceToHost,
+                        ctx->c.stream));
+  ctx->c.sync();
+  LH_CATCH
+}
+lh_status lh_brakedown_comm_stage(lh_ctx* ctx, const lh_brakedown_param* pp, const lh_brakedown_comm* comm, lh_fr* out) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(pp);
+  NEED(comm);
+  NEED(out);
+  BdStage st;
+  brakedown_stage(ctx->c, pp->p, comm->c, st);
+  memcpy(out, st.cols, comm->c.num_rows * comm->c.codeword_len * 32);
   LH_CATCH
 }
 void lh_brakedown_comm_free(lh_brakedown_comm* comm) { delete comm; }
@@ -1171,12 +1201,15 @@ lh_status lh_brakedown_batch_open(lh_ctx* ctx, const lh_brakedown_param* pp, siz
   NEED_N(evals, num_evals);
   Transcript tr(t);
   HashTranscript h(ht);
+  BdStage stage;  // (option brakedown_staged_open; freed with this call)
+  const bool staged = ctx->c.opt.brakedown_staged_open != 0;
   for (size_t i = 0; i < num_evals; i++) {  // one open per evaluation (brakedown.rs:278-300)
     const lh_evaluation& e = evals[i];
     LH_REQUIRE(e.poly < num_polys && e.point < num_points && d_polys[e.poly] && comms[e.poly], LH_ERR_ARG,
                "brakedown batch_open: evaluation out of range");
+    if (staged) brakedown_stage(ctx->c, pp->p, comms[e.poly]->c, stage);
     brakedown_open(ctx->c, pp->p, (const Fr*)d_polys[e.poly], num_vars, comms[e.poly]->c,
-                   (const HFr*)points + (size_t)e.point * num_vars, tr, h);
+                   (const HFr*)points + (size_t)e.point * num_vars, tr, h, staged ? &stage : nullptr);
   }
   LH_CATCH
 }
@@ -1221,6 +1254,86 @@ lh_status lh_brakedown_batch_verify(const lh_brakedown_param* pp, size_t num_var
                      tr, h);
   }
   LH_CATCH
+}
+
+// HyperPlonk over Brakedown (brakedown.cpp brakedown_pcs; the verifier in verifier.cpp)
+static std::vector<BdComm*> bd_comms_of(lh_brakedown_comm* const* comms, size_t n, const char* what) {
+  LH_REQUIRE(comms != nullptr || n == 0, LH_ERR_ARG, std::string("null argument: ") + what);
+  std::vector<BdComm*> v(n);
+  for (size_t i = 0; i < n; i++) {
+    LH_REQUIRE(comms[i], LH_ERR_ARG, std::string("null argument: ") + what + "[i]");
+    v[i] = &comms[i]->c;
+  }
+  return v;
+}
+lh_status lh_hyperplonk_prove_brakedown(lh_ctx* ctx, const lh_brakedown_param* bp, const lh_hp_param* pp,
+                                        lh_brakedown_comm* const* preprocess_comms,
+                                        lh_brakedown_comm* const* permutation_comms, const lh_fr* const* instances,
+                                        const lh_fr* const* d_witness_polys, lh_transcript* t, lh_hash_transcript* ht) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(bp);
+  NEED(pp);
+  NEED_N(d_witness_polys, pp->num_witness_polys);
+  NEED_N(instances, pp->num_instance_polys);
+  const std::vector<BdComm*> pre = bd_comms_of(preprocess_comms, pp->num_preprocess_polys, "preprocess_comms"),
+                             perm = bd_comms_of(permutation_comms, pp->num_permutation_polys, "permutation_comms");
+  Transcript tr(t);
+  HashTranscript h(ht);
+  HpPhases ph;  // single phase: synthesize(0, []) = d_witness_polys
+  ph.num_witness_polys = {pp->num_witness_polys};
+  ph.num_challenges = {pp->num_challenges};
+  ph.synthesize = [&](size_t, const std::vector<HFr>&) {
+    return std::vector<const Fr*>((const Fr* const*)d_witness_polys, (const Fr* const*)d_witness_polys + pp->num_witness_polys);
+  };
+  brakedown_hyperplonk_prove_phases(ctx->c, bp->p, *pp, pre.data(), perm.data(), ph, (const HFr* const*)instances, tr, h);
+  LH_CATCH
+}
+lh_status lh_hyperplonk_prove_phases_brakedown(lh_ctx* ctx, const lh_brakedown_param* bp, const lh_hp_param* pp,
+                                               lh_brakedown_comm* const* preprocess_comms,
+                                               lh_brakedown_comm* const* permutation_comms, size_t num_phases,
+                                               const size_t* num_witness_polys, const size_t* num_challenges,
+                                               const lh_fr* const* instances, const lh_hp_circuit* circuit, lh_transcript* t,
+                                               lh_hash_transcript* ht) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(bp);
+  NEED(pp);
+  NEED(circuit);
+  NEED_N(instances, pp->num_instance_polys);
+  const std::vector<BdComm*> pre = bd_comms_of(preprocess_comms, pp->num_preprocess_polys, "preprocess_comms"),
+                             perm = bd_comms_of(permutation_comms, pp->num_permutation_polys, "permutation_comms");
+  Transcript tr(t);
+  HashTranscript h(ht);
+  const HpPhases ph = hp_phases_of(pp, num_phases, num_witness_polys, num_challenges, circuit);
+  brakedown_hyperplonk_prove_phases(ctx->c, bp->p, *pp, pre.data(), perm.data(), ph, (const HFr* const*)instances, tr, h);
+  LH_CATCH
+}
+lh_status lh_hyperplonk_verify_phases_brakedown(const lh_brakedown_param* bp, const lh_hp_vparam* hvp,
+                                                const uint8_t* preprocess_roots, const uint8_t* permutation_roots,
+                                                size_t num_phases, const size_t* num_witness_polys,
+                                                const size_t* num_challenges, const lh_fr* const* instances, lh_transcript* t,
+                                                lh_hash_transcript* ht) {
+  LH_TRY
+  NEED(bp);
+  NEED(hvp);
+  NEED_N(preprocess_roots, hvp->num_preprocess_polys);
+  NEED_N(permutation_roots, hvp->num_permutation_polys);
+  NEED_N(instances, hvp->num_instance_polys);
+  LH_REQUIRE(num_phases == 0 || (num_witness_polys && num_challenges), LH_ERR_ARG, "null argument: phases");
+  Transcript tr(t);
+  HashTranscript h(ht);
+  brakedown_hyperplonk_verify_phases(bp->p, *hvp, preprocess_roots, permutation_roots,
+                                     std::vector<size_t>(num_witness_polys, num_witness_polys + num_phases),
+                                     std::vector<size_t>(num_challenges, num_challenges + num_phases),
+                                     (const HFr* const*)instances, tr, h);
+  LH_CATCH
+}
+lh_status lh_hyperplonk_verify_brakedown(const lh_brakedown_param* bp, const lh_hp_vparam* hvp, const uint8_t* preprocess_roots,
+                                         const uint8_t* permutation_roots, const lh_fr* const* instances, lh_transcript* t,
+                                         lh_hash_transcript* ht) {
+  if (!hvp) return lh_hyperplonk_verify_phases_brakedown(bp, hvp, preprocess_roots, permutation_roots, 0, nullptr, nullptr,
+                                                         instances, t, ht);
+  return lh_hyperplonk_verify_phases_brakedown(bp, hvp, preprocess_roots, permutation_roots, 1, &hvp->num_witness_polys,
+                                               &hvp->num_challenges, instances, t, ht);
 }
 
 lh_status lh_lasso_prove_zeromorph(lh_ctx* ctx, const lh_usrs* srs, size_t poly_size, const lh_lasso_table* table,

@@ -152,6 +152,8 @@ struct Options {
   int64_t hyrax_rows = 1;              // Hyrax commits every row of every poly with the row kernels (kernels_hyrax.hip: one bucket
                                        // set per row over the generators' window table, no host wait between rows); 0: one
                                        // msm_batch job per row
+  int64_t brakedown_batch_commit = 1;  // lh_brakedown_batch_commit runs its polys as one batch (brakedown.cpp); 0: a commit each
+  int64_t brakedown_staged_open = 0;   // lh_brakedown_batch_open reads the opened columns from the matrix staged on the host
   Options();                           // environment defaults (dev.cpp)
   int64_t* find(const char* name);
   static bool in_range(const char* name, int64_t value);  // the range lh_ctx_set_option accepts

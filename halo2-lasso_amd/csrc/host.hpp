@@ -106,6 +106,9 @@ struct Transcript {
 typedef std::function<void(size_t num_vars, const HG1* comms, size_t num_comms, const HFr* points, size_t num_points,
                            const lh_evaluation* evals, size_t num_evals, Transcript& tr)>
     PcsBatchVerify;
+// optional, for a PCS whose commitments are not G1 points (Brakedown: 32-byte Merkle roots that cross the transcript
+// unabsorbed): reads n commitments, each into the first bytes of a 64-byte HG1 slot that only its own batch_verify interprets
+typedef std::function<std::vector<HG1>(Transcript& tr, size_t n)> PcsReadCommitments;
 
 // ------------------------------------------------------------------ poly helpers (host side, tiny inputs)
 std::vector<HFr> host_eq_xy(const std::vector<HFr>& y);           // multilinear.rs:91-127
@@ -477,6 +480,10 @@ struct Pcs {
   // poly-major, rows in order - what the scheme's batch_commit_and_write writes
   size_t chunks = 1;
   std::function<std::vector<HG1>(const Fr* const* d_polys, size_t num_polys, size_t num_vars)> batch_commit;
+  // optional (a scheme whose commitment is not a vector of points - Brakedown: device-resident rows and a Merkle tree):
+  // commits the polys and writes the commitments itself, used in place of batch_commit + Transcript::write_commitments;
+  // the scheme keeps what it committed and its batch_open finds the commitment of an opened poly by its device pointer
+  std::function<void(const Fr* const* d_polys, size_t num_polys, size_t num_vars, Transcript& tr)> commit_and_write;
   // optional (schemes without commit_bases: Hyrax): commits (small-valued) columns directly -> num_cols * chunks points
   std::function<std::vector<HG1>(const PcsColumn* cols, size_t num_cols, size_t nv)> commit_columns;
   // bases whose first 2^nv points commit a zero-padded table of 2^nv entries (the eq basis of level nv, or the powers of
@@ -502,6 +509,7 @@ Pcs ipa_pcs(Ctx&, const IpaParams&, size_t poly_size);     // ipa.cpp (no shard_
 // ipa.cpp: commitments of num_chunks points, commit_columns instead of commit_bases; commits only polys of exactly
 // log2(poly_size) variables (LH_ERR_ARG otherwise)
 Pcs hyrax_pcs(Ctx&, const IpaParams&, size_t poly_size, size_t batch_size);
+// (brakedown_pcs: brakedown.hpp - it needs the hash transcript and the commitments of the polys the caller committed)
 
 // ------------------------------------------------------------------ Lasso
 // pieces of the argument shared by the standalone prover (lasso.cpp) and HyperPlonk's Lasso lookups (hyperplonk.cpp)
@@ -588,11 +596,13 @@ void lasso_verify(const PcsBatchVerify& batch_verify, const lh_lasso_table& tabl
 // the verifier's side of lasso_argue: Surge and memory-checking identities; claims left to check against commitments
 LassoClaims lasso_check(const lh_lasso_table& table, size_t num_vars, Transcript& tr);
 // chunks: points per commitment (vp's preprocess_comms / permutation_comms then hold that many per poly, poly-major)
+// read_commitments (optional): how the witness, m, h and z commitments are read (default: Transcript::read_commitments)
 void hyperplonk_verify(const PcsBatchVerify& batch_verify, const lh_hp_vparam& vp, const HFr* const* instances,
-                       Transcript& tr, size_t chunks = 1);
+                       Transcript& tr, size_t chunks = 1, const PcsReadCommitments& read_commitments = nullptr);
 void hyperplonk_verify_phases(const PcsBatchVerify& batch_verify, const lh_hp_vparam& vp,
                               const std::vector<size_t>& num_witness_polys, const std::vector<size_t>& num_challenges,
-                              const HFr* const* instances, Transcript& tr, size_t chunks = 1);
+                              const HFr* const* instances, Transcript& tr, size_t chunks = 1,
+                              const PcsReadCommitments& read_commitments = nullptr);
 
 // ------------------------------------------------------------------ HyperPlonk (hyperplonk.cpp)
 void hyperplonk_prove(Ctx&, const Pcs&, const lh_hp_param& pp, const HFr* const* instances,

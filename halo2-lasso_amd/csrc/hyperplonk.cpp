@@ -151,6 +151,8 @@ void hyperplonk_prove_phases(Ctx& c, const Pcs& pcs, const lh_hp_param& pp, cons
              "hyperplonk: phases are malformed");  // zip_eq, hyperplonk.rs:186-190
   const size_t nv = pp.num_vars, n = (size_t)1 << nv;
   LH_REQUIRE(nv >= 1 && nv < 32, LH_ERR_ARG, "hyperplonk: bad num_vars");
+  LH_REQUIRE(!pcs.commit_and_write || pp.num_lasso_lookups == 0, LH_ERR_ARG,
+             "hyperplonk: Lasso lookups need a PCS that commits to points");
   // One proof over the 2^rho ranks of the ctx's communicator (dev.hpp Shard; lh_hyperplonk_prove_sharded): every poly the
   // caller hands over - preprocess, permutation, witness - is THIS RANK'S shard (n_loc rows) and so is every poly made
   // here.  What crosses ranks: partial commitments (one exchange per commit round), the zero-check's partial sums and its
@@ -344,6 +346,8 @@ void hyperplonk_prove_phases(Ctx& c, const Pcs& pcs, const lh_hp_param& pp, cons
       comms.assign(out.begin(), out.begin() + w.size());
       lasso_comms.assign(out.begin() + w.size(), out.end());
       lasso_committed = true;
+    } else if (pcs.commit_and_write) {
+      pcs.commit_and_write(w.data(), w.size(), nv, tr);
     } else {
       comms = pcs.batch_commit(w.data(), w.size(), nv);
     }
@@ -374,8 +378,12 @@ void hyperplonk_prove_phases(Ctx& c, const Pcs& pcs, const lh_hp_param& pp, cons
   }
   {
     std::vector<const Fr*> mp(m_polys.begin(), m_polys.end());
-    std::vector<HG1> comms = pcs.batch_commit(mp.data(), mp.size(), nv);
-    tr.write_commitments(comms);
+    if (pcs.commit_and_write) {
+      pcs.commit_and_write(mp.data(), mp.size(), nv, tr);
+    } else {
+      std::vector<HG1> comms = pcs.batch_commit(mp.data(), mp.size(), nv);
+      tr.write_commitments(comms);
+    }
   }
   // Lasso lookups: their commitments - computed together with the last phase's witness commitments when the PCS allows
   // it (below) - enter the transcript here, framed with the identity mask (lasso.cpp)
@@ -430,8 +438,12 @@ void hyperplonk_prove_phases(Ctx& c, const Pcs& pcs, const lh_hp_param& pp, cons
   {
     std::vector<const Fr*> hz(h_polys.begin(), h_polys.end());
     hz.insert(hz.end(), z_polys.begin(), z_polys.end());
-    std::vector<HG1> comms = pcs.batch_commit(hz.data(), hz.size(), nv);
-    tr.write_commitments(comms);
+    if (pcs.commit_and_write) {
+      pcs.commit_and_write(hz.data(), hz.size(), nv, tr);
+    } else {
+      std::vector<HG1> comms = pcs.batch_commit(hz.data(), hz.size(), nv);
+      tr.write_commitments(comms);
+    }
   }
 
   pt.lap("h, z polys + commit");

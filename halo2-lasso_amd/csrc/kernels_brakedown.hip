@@ -6,6 +6,11 @@
 //                    registers; leaves from codeword_len up to 2^depth are zero
 //   bd_merkle_level  parent = keccak256(left || right)
 //   bd_combine       the proximity row(s) and the t_0 row in one pass over the polynomial
+// A batch of P polys (brakedown_batch_commit) is one slab of P * num_rows rows: the encoder stages above take it as it is
+// (rows are independent), and what is per poly gets blockIdx.y = poly:
+//   bd_load_rows           the P messages from a pointer table into the slab's rows
+//   bd_hash_columns_batch  / bd_merkle_level_batch: the same leaves and parents, poly p's tree at p * tree_stride
+//   bd_stage_columns       the encoded matrix transposed (column-major) through LDS tiles, for the staged open
 #include <hip/hip_runtime.h>
 #include "brakedown.hpp"
 
@@ -138,8 +143,8 @@ __device__ __forceinline__ void bd_absorb_block(uint64_t (&a)[25], const Fr* col
 }
 
 // (64-thread workgroups: the state, the permutation's temporaries and a Montgomery product fit without spilling)
-__global__ void __launch_bounds__(64)
-    bd_hash_columns_kernel(const Fr* __restrict__ rows, size_t num_rows, size_t cw, size_t width, uint64_t* __restrict__ leaves) {
+__device__ __forceinline__ void bd_hash_columns_body(const Fr* __restrict__ rows, size_t num_rows, size_t cw, size_t width,
+                                                     uint64_t* __restrict__ leaves) {
   GSTRIDE(c, width) {
     uint64_t a[25];
 #pragma unroll
@@ -166,14 +171,23 @@ __global__ void __launch_bounds__(64)
     store_digest(leaves + 4 * c, a);  // (the zero leaves past codeword_len: a is still all zero)
   }
 }
+__global__ void __launch_bounds__(64)
+    bd_hash_columns_kernel(const Fr* __restrict__ rows, size_t num_rows, size_t cw, size_t width, uint64_t* __restrict__ leaves) {
+  bd_hash_columns_body(rows, num_rows, cw, width, leaves);
+}
+// poly blockIdx.y of a slab: its rows at y * num_rows * cw, its tree at y * tree_stride words
+__global__ void __launch_bounds__(64)
+    bd_hash_columns_batch_kernel(const Fr* __restrict__ rows, size_t num_rows, size_t cw, size_t width,
+                                 uint64_t* __restrict__ trees, size_t tree_stride) {
+  bd_hash_columns_body(rows + (size_t)blockIdx.y * num_rows * cw, num_rows, cw, width, trees + (size_t)blockIdx.y * tree_stride);
+}
 void k_bd_hash_columns(Ctx& c, const Fr* rows, size_t num_rows, size_t cw, size_t width, uint64_t* leaves) {
   ProfScope ps(c, "bd_hash_columns", 32.0 * num_rows * cw + 32.0 * width, 0, (double)cw);
   hipLaunchKernelGGL(bd_hash_columns_kernel, grid_for(width, 64, 1 << 16), 64, 0, c.stream, rows, num_rows, cw, width,
                      leaves);
 }
 
-__global__ void __launch_bounds__(64)
-    bd_merkle_level_kernel(const uint64_t* __restrict__ in, size_t out_n, uint64_t* __restrict__ out) {
+__device__ __forceinline__ void bd_merkle_level_body(const uint64_t* __restrict__ in, size_t out_n, uint64_t* __restrict__ out) {
   GSTRIDE(i, out_n) {
     uint64_t a[25];
     const ulonglong2* src = (const ulonglong2*)(in + 8 * i);
@@ -190,9 +204,99 @@ __global__ void __launch_bounds__(64)
     store_digest(out + 4 * i, a);
   }
 }
+__global__ void __launch_bounds__(64)
+    bd_merkle_level_kernel(const uint64_t* __restrict__ in, size_t out_n, uint64_t* __restrict__ out) {
+  bd_merkle_level_body(in, out_n, out);
+}
+__global__ void __launch_bounds__(64)
+    bd_merkle_level_batch_kernel(uint64_t* __restrict__ trees, size_t tree_stride, size_t in_off, size_t out_n, size_t out_off) {
+  uint64_t* tree = trees + (size_t)blockIdx.y * tree_stride;
+  bd_merkle_level_body(tree + in_off, out_n, tree + out_off);
+}
 void k_bd_merkle_level(Ctx& c, const uint64_t* in, size_t out_n, uint64_t* out) {
   ProfScope ps(c, "bd_merkle_level", 96.0 * out_n, 0, (double)out_n);
   hipLaunchKernelGGL(bd_merkle_level_kernel, grid_for(out_n, 64, 1 << 16), 64, 0, c.stream, in, out_n, out);
+}
+
+// ------------------------------------------------------------------ a batch of polys in one slab
+constexpr size_t BD_MAX_BATCH = 65535;  // gridDim.y
+__global__ void bd_load_rows_kernel(const Fr* const* __restrict__ polys, size_t num_rows, size_t row_len, size_t cw,
+                                    Fr* __restrict__ rows) {
+  const Fr* __restrict__ src = polys[blockIdx.y];
+  Fr* dst = rows + (size_t)blockIdx.y * num_rows * cw;
+  GSTRIDE(t, num_rows * row_len) {
+    const size_t r = t / row_len, j = t - r * row_len;
+    dst[r * cw + j] = src[t];  // row r's message is poly[r * row_len ..]
+  }
+}
+void k_bd_load_rows(Ctx& c, const Fr* const* d_polys, size_t num_polys, size_t num_rows, size_t row_len, size_t cw, Fr* rows) {
+  LH_REQUIRE(num_polys >= 1 && num_polys <= BD_MAX_BATCH, LH_ERR_ARG, "brakedown: too many polys in one batch");
+  ProfScope ps(c, "bd_load_rows", 64.0 * num_polys * num_rows * row_len, 0, (double)num_polys * num_rows * row_len);
+  dim3 g = grid_for(num_rows * row_len);
+  g.y = (unsigned)num_polys;
+  hipLaunchKernelGGL(bd_load_rows_kernel, g, 256, 0, c.stream, d_polys, num_rows, row_len, cw, rows);
+}
+void k_bd_hash_columns_batch(Ctx& c, const Fr* rows, size_t num_polys, size_t num_rows, size_t cw, size_t width,
+                             uint64_t* trees, size_t tree_stride) {
+  LH_REQUIRE(num_polys >= 1 && num_polys <= BD_MAX_BATCH, LH_ERR_ARG, "brakedown: too many polys in one batch");
+  ProfScope ps(c, "bd_hash_columns", num_polys * (32.0 * num_rows * cw + 32.0 * width), 0, (double)num_polys * cw);
+  dim3 g = grid_for(width, 64, 1 << 16);
+  g.y = (unsigned)num_polys;
+  hipLaunchKernelGGL(bd_hash_columns_batch_kernel, g, 64, 0, c.stream, rows, num_rows, cw, width, trees, tree_stride);
+}
+void k_bd_merkle_level_batch(Ctx& c, uint64_t* trees, size_t num_polys, size_t tree_stride, size_t in_off, size_t out_n,
+                             size_t out_off) {
+  LH_REQUIRE(num_polys >= 1 && num_polys <= BD_MAX_BATCH, LH_ERR_ARG, "brakedown: too many polys in one batch");
+  ProfScope ps(c, "bd_merkle_level", 96.0 * num_polys * out_n, 0, (double)num_polys * out_n);
+  dim3 g = grid_for(out_n, 64, 1 << 16);
+  g.y = (unsigned)num_polys;
+  hipLaunchKernelGGL(bd_merkle_level_batch_kernel, g, 64, 0, c.stream, trees, tree_stride, in_off, out_n, out_off);
+}
+__global__ void bd_gather_roots_kernel(const uint64_t* __restrict__ trees, size_t tree_stride, size_t root_off,
+                                       size_t num_polys, uint64_t* __restrict__ out) {
+  GSTRIDE(t, 4 * num_polys) out[t] = trees[(t / 4) * tree_stride + root_off + (t & 3)];
+}
+void k_bd_gather_roots(Ctx& c, const uint64_t* trees, size_t num_polys, size_t tree_stride, size_t root_off, uint64_t* out) {
+  hipLaunchKernelGGL(bd_gather_roots_kernel, grid_for(4 * num_polys), 256, 0, c.stream, trees, tree_stride, root_off,
+                     num_polys, out);
+}
+
+// ------------------------------------------------------------------ staged open: the encoded matrix, column-major
+// out[c * num_rows + r] = rows[r * cw + c].  A workgroup moves a tile of BD_T x BD_T elements through the LDS: lane (ty, tx)
+// loads element (row r0 + ty, column c0 + tx) - adjacent lanes read adjacent 32-byte elements of a row - and stores element
+// (column c0 + ty, row r0 + tx) - adjacent lanes write adjacent elements of a column.  An element is two 16-byte halves
+// (ds_write_b128 / ds_read_b128).  A tile row is BD_T elements plus one 16-byte pad: without it the transposed read of a
+// 16-lane group walks a stride of 512 bytes, two bank rows of 256, and the lanes that share a tile column land on the same
+// four banks (8-way); with the pad the stride is 33 slots of 16 bytes and the slots differ (slot = r + 2 c + half mod 16: at
+// worst two pairs of lanes meet, where a group spans two tile columns).  The row-wise store is 2-way (ds_write_b128 banks
+// modulo 128 bytes, a lane every 32).  Each byte crosses HBM once in and once out, far below what the LDS carries even so.
+// Edge tiles: lanes beyond num_rows or cw neither load nor store.
+constexpr int BD_T = 16;
+constexpr int BD_T_STRIDE = 2 * BD_T + 1;  // 16-byte slots per tile row
+__global__ void __launch_bounds__(BD_T * BD_T)
+    bd_stage_columns_kernel(const Fr* __restrict__ rows, size_t num_rows, size_t cw, Fr* __restrict__ out) {
+  __shared__ uint4 tile[BD_T * BD_T_STRIDE];
+  const int tx = threadIdx.x % BD_T, ty = threadIdx.x / BD_T;
+  const size_t c0 = (size_t)blockIdx.x * BD_T, r0 = (size_t)blockIdx.y * BD_T;
+  if (r0 + ty < num_rows && c0 + tx < cw) {
+    const uint4* src = (const uint4*)(rows + (r0 + ty) * cw + c0 + tx);
+    tile[ty * BD_T_STRIDE + 2 * tx] = src[0];
+    tile[ty * BD_T_STRIDE + 2 * tx + 1] = src[1];
+  }
+  __syncthreads();
+  if (c0 + ty < cw && r0 + tx < num_rows) {
+    uint4* dst = (uint4*)(out + (c0 + ty) * num_rows + r0 + tx);
+    dst[0] = tile[tx * BD_T_STRIDE + 2 * ty];
+    dst[1] = tile[tx * BD_T_STRIDE + 2 * ty + 1];
+  }
+}
+void k_bd_stage_columns(Ctx& c, const Fr* rows, size_t num_rows, size_t cw, Fr* out) {
+  const size_t gx = (cw + BD_T - 1) / BD_T, gy = (num_rows + BD_T - 1) / BD_T;
+  LH_REQUIRE(num_rows >= 1 && cw >= 1 && gx < ((size_t)1 << 31) && gy <= 65535, LH_ERR_ARG,
+             "brakedown: matrix too large to stage");
+  ProfScope ps(c, "bd_stage_columns", 64.0 * num_rows * cw, 0, (double)num_rows * cw);
+  hipLaunchKernelGGL(bd_stage_columns_kernel, dim3((unsigned)gx, (unsigned)gy), BD_T * BD_T, 0, c.stream, rows, num_rows, cw,
+                     out);
 }
 
 // ------------------------------------------------------------------ open: combined rows

@@ -699,13 +699,18 @@ static HFr rotation_eval(const std::vector<HFr>& x, int rotation, const std::vec
 static void lasso_verify_check_table(const lh_lasso_table& tb, size_t n);
 
 void hyperplonk_verify(const PcsBatchVerify& batch_verify, const lh_hp_vparam& vp, const HFr* const* instances,
-                       Transcript& tr, size_t chunks) {
-  hyperplonk_verify_phases(batch_verify, vp, {vp.num_witness_polys}, {vp.num_challenges}, instances, tr, chunks);
+                       Transcript& tr, size_t chunks, const PcsReadCommitments& read_commitments) {
+  hyperplonk_verify_phases(batch_verify, vp, {vp.num_witness_polys}, {vp.num_challenges}, instances, tr, chunks,
+                           read_commitments);
 }
 
 void hyperplonk_verify_phases(const PcsBatchVerify& batch_verify, const lh_hp_vparam& vp,
                               const std::vector<size_t>& phase_witness_polys, const std::vector<size_t>& phase_challenges,
-                              const HFr* const* instances, Transcript& tr, size_t chunks) {
+                              const HFr* const* instances, Transcript& tr, size_t chunks,
+                              const PcsReadCommitments& read_commitments) {
+  auto read_comms = [&](size_t count) { return read_commitments ? read_commitments(tr, count) : tr.read_commitments(count); };
+  LH_REQUIRE(!read_commitments || vp.num_lasso_lookups == 0, LH_ERR_ARG,
+             "hyperplonk: Lasso lookups need a PCS that commits to points");
   // chunks: points per commitment (Hyrax's rows; 1 otherwise) - every commitment is read as that many points, the verifier
   // param holds that many per poly, and batch_verify gets the commitments as vectors, commitment-major
   LH_REQUIRE(chunks >= 1, LH_ERR_ARG, "hyperplonk: chunks must be at least 1");
@@ -726,13 +731,13 @@ void hyperplonk_verify_phases(const PcsBatchVerify& batch_verify, const lh_hp_vp
   std::vector<HG1> witness_comms;
   std::vector<HFr> challenges;
   for (size_t r = 0; r < phase_witness_polys.size(); r++) {
-    std::vector<HG1> cm = tr.read_commitments(phase_witness_polys[r] * chunks);
+    std::vector<HG1> cm = read_comms(phase_witness_polys[r] * chunks);
     witness_comms.insert(witness_comms.end(), cm.begin(), cm.end());
     std::vector<HFr> ch = tr.squeeze_challenges(phase_challenges[r]);
     challenges.insert(challenges.end(), ch.begin(), ch.end());
   }
   HFr beta = tr.squeeze_challenge();
-  std::vector<HG1> m_comms = tr.read_commitments(vp.num_lookups * chunks);
+  std::vector<HG1> m_comms = read_comms(vp.num_lookups * chunks);
   // Lasso lookups (oracle/pyref/hyperplonk.py LassoLookup): read_ts | E | final_cts per lookup, identity-mask framing
   std::vector<HG1> lasso_comms;
   if (vp.num_lasso_lookups) {
@@ -747,7 +752,7 @@ void hyperplonk_verify_phases(const PcsBatchVerify& batch_verify, const lh_hp_vp
     lasso_comms = lasso_read_commitments(tr, count, chunks);
   }
   HFr gamma = tr.squeeze_challenge();
-  std::vector<HG1> hz_comms = tr.read_commitments((vp.num_lookups + vp.num_permutation_z_polys) * chunks);
+  std::vector<HG1> hz_comms = read_comms((vp.num_lookups + vp.num_permutation_z_polys) * chunks);
   HFr alpha = tr.squeeze_challenge();
   std::vector<HFr> y = tr.squeeze_challenges(nv);
   challenges.push_back(beta);
@@ -1112,6 +1117,48 @@ void brakedown_verify(const BdParam& p, const uint8_t root[32], const HFr* point
   HFr acc = HFr::zero();  // consistency
   for (size_t c = 0; c < row_len; c++) acc += combined.back().second[c] * t_1[c];
   if (acc != eval) throw Error(LH_ERR_INVALID_PCS_OPEN, "Consistency failure");
+}
+
+// ------------------------------------------------------------------ HyperPlonk::verify over Brakedown
+// A root travels through hyperplonk_verify_phases in the first 32 bytes of a 64-byte commitment slot; instance polys keep
+// the all-zero slot and are never queried (verifier.rs:147-154).
+void brakedown_hyperplonk_verify_phases(const BdParam& p, const lh_hp_vparam& vp, const uint8_t* preprocess_roots,
+                                        const uint8_t* permutation_roots, const std::vector<size_t>& num_witness_polys,
+                                        const std::vector<size_t>& num_challenges, const HFr* const* instances,
+                                        Transcript& tr, HashTranscript& ht) {
+  LH_REQUIRE(vp.num_lasso_lookups == 0, LH_ERR_ARG,
+             "hyperplonk over brakedown: Lasso lookups are not supported (their column commitments are points)");
+  LH_REQUIRE(vp.num_vars == p.num_vars, LH_ERR_ARG,
+             "hyperplonk over brakedown: the circuit has " + std::to_string(vp.num_vars) + " variables, the param " +
+                 std::to_string(p.num_vars));
+  auto slots = [](const uint8_t* roots, size_t n) {
+    std::vector<lh_g1> v(std::max<size_t>(n, 1));
+    memset(v.data(), 0, v.size() * sizeof(lh_g1));
+    for (size_t i = 0; i < n; i++) memcpy(&v[i], roots + 32 * i, 32);
+    return v;
+  };
+  const std::vector<lh_g1> pre = slots(preprocess_roots, vp.num_preprocess_polys),
+                           perm = slots(permutation_roots, vp.num_permutation_polys);
+  lh_hp_vparam v2 = vp;
+  v2.preprocess_comms = pre.data(), v2.permutation_comms = perm.data();
+  hyperplonk_verify_phases(
+      [&p, &ht](size_t nv, const HG1* comms, size_t nc, const HFr* points, size_t np, const lh_evaluation* evals, size_t ne,
+                Transcript& t2) {
+        for (size_t i = 0; i < ne; i++) {  // batch_verify is one verify per evaluation (brakedown.rs:398-417)
+          const lh_evaluation& e = evals[i];
+          LH_REQUIRE(e.poly < nc && e.point < np, LH_ERR_ARG, "brakedown batch_verify: evaluation out of range");
+          HFr v;
+          memcpy(&v, &e.value, 32);
+          brakedown_verify(p, (const uint8_t*)&comms[e.poly], points + (size_t)e.point * nv, nv, v, t2, ht);
+        }
+      },
+      v2, num_witness_polys, num_challenges, instances, tr, 1,
+      [&ht](Transcript&, size_t n) {
+        std::vector<HG1> v(n);
+        if (n) memset((void*)v.data(), 0, n * sizeof(HG1));
+        for (size_t i = 0; i < n; i++) ht.read_hash((uint8_t*)&v[i]);
+        return v;
+      });
 }
 
 }  // namespace lh

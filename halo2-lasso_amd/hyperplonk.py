@@ -138,9 +138,13 @@ def batch_size(info):
 
 
 def _pcs_of(pcs_pp):
-    """the PolynomialCommitmentScheme a param belongs to: MultilinearKzg, Zeromorph, Gemini, Ipa or Hyrax
-    (backend/hyperplonk.rs:76-95); over Hyrax a commitment is a list of num_chunks points"""
+    """the PolynomialCommitmentScheme a param belongs to: MultilinearKzg, Zeromorph, Gemini, Ipa, Hyrax or Brakedown
+    (backend/hyperplonk.rs:76-95); over Hyrax a commitment is a list of num_chunks points, over Brakedown a
+    BrakedownCommitment (device-resident; the verifier param holds the 32-byte roots)"""
     from . import MultilinearKzg, Zeromorph, ZeromorphProverParam, Gemini, GeminiProverParam, Ipa, IpaParam, Hyrax, HyraxParam
+    from . import Brakedown, BrakedownParam
+    if isinstance(pcs_pp, BrakedownParam):
+        return Brakedown
     if isinstance(pcs_pp, HyraxParam):
         return Hyrax
     if isinstance(pcs_pp, IpaParam):
@@ -176,6 +180,10 @@ class HyperPlonk:
         vp.pcs, vp.num_vars, vp.info = pcs_vp, info.k, info
         vp.num_permutation_z_polys, vp.expression = pp.num_permutation_z_polys, pp.expression
         vp.preprocess_comms, vp.permutation_comms = list(pp.preprocess_comms), list(pp.permutation_comms)
+        from . import BrakedownParam
+        if isinstance(pcs_pp, BrakedownParam):  # (the verifier holds roots, not the device-resident commitments)
+            vp.preprocess_comms = [c.root for c in pp.preprocess_comms]
+            vp.permutation_comms = [c.root for c in pp.permutation_comms]
         return pp, vp
 
     @staticmethod
@@ -253,8 +261,16 @@ class HyperPlonk:
         prm.num_lasso_lookups, prm.lasso_lookups = len(info.lasso_lookups), lasso_arr
         inst_arrays = [_fr_array(i) for i in instances]
         inst = (C.POINTER(lh_fr) * max(len(instances), 1))(*[C.cast(a, C.POINTER(lh_fr)) for a in inst_arrays])
-        from . import ZeromorphProverParam, GeminiProverParam, IpaParam, HyraxParam
+        from . import ZeromorphProverParam, GeminiProverParam, IpaParam, HyraxParam, BrakedownParam
         lib = ctx.lib
+        brakedown = isinstance(pp.pcs, BrakedownParam)
+        if sharded and brakedown:
+            raise NotImplementedError("the sharded prove is wired for multilinear KZG")
+        if brakedown:  # (param, circuit, the commitments of the preprocess and permutation polys); the hash transcript last
+            pre_c = _ptr_array([c.h.value for c in pp.preprocess_comms])
+            perm_c = _ptr_array([c.h.value for c in pp.permutation_comms])
+            head = (ctx.h, pp.pcs.h, C.byref(prm), pre_c if pp.preprocess_comms else None,
+                    perm_c if pp.permutation_comms else None)
         if isinstance(pp.pcs, HyraxParam):  # (params, trim size, batch size)
             head = (ctx.h, pp.pcs.params.h, pp.pcs.poly_size, pp.pcs.batch_size, C.byref(prm))
         # PCS whose param is (params, trim size): over the univariate SRS, or the IPA
@@ -282,7 +298,10 @@ class HyperPlonk:
             nph = len(info.num_witness_polys)
             nw = (C.c_size_t * max(nph, 1))(*info.num_witness_polys)
             nc = (C.c_size_t * max(nph, 1))(*info.num_challenges)
-            if isinstance(pp.pcs, HyraxParam):
+            if brakedown:
+                rc = lib.lh_hyperplonk_prove_phases_brakedown(*head, nph, nw, nc, inst, C.byref(circ), transcript.p,
+                                                              C.byref(transcript.hash_io()))
+            elif isinstance(pp.pcs, HyraxParam):
                 rc = lib.lh_hyperplonk_prove_phases_hyrax(*head, nph, nw, nc, inst, C.byref(circ), transcript.p)
             elif univariate:
                 fn = lib.lh_hyperplonk_prove_phases_ipa if ipa else \
@@ -301,7 +320,9 @@ class HyperPlonk:
                 raise NotImplementedError("the sharded prove is wired for multilinear KZG")
             _check(ctx.lib.lh_hyperplonk_prove_sharded(ctx.h, pp.pcs.h, C.byref(prm), inst, wit, transcript.p))
             return
-        if isinstance(pp.pcs, HyraxParam):
+        if brakedown:
+            _check(lib.lh_hyperplonk_prove_brakedown(*head, inst, wit, transcript.p, C.byref(transcript.hash_io())))
+        elif isinstance(pp.pcs, HyraxParam):
             _check(lib.lh_hyperplonk_prove_hyrax(*head, inst, wit, transcript.p))
         elif univariate:
             fn = lib.lh_hyperplonk_prove_ipa if ipa else \
@@ -328,14 +349,27 @@ class HyperPlonk:
         prm.expression = ce
         lasso_arr = _lasso_lookups_c(info)
         prm.num_lasso_lookups, prm.lasso_lookups = len(info.lasso_lookups), lasso_arr
-        from . import HyraxParam
-        hyrax = isinstance(vp.pcs, HyraxParam)
+        from . import HyraxParam, BrakedownParam
+        hyrax, brakedown = isinstance(vp.pcs, HyraxParam), isinstance(vp.pcs, BrakedownParam)
         flat = (lambda comms: [p for cm in comms for p in cm]) if hyrax else list  # (over Hyrax: num_chunks points per poly)
-        pre, perm = _g1_array(flat(vp.preprocess_comms)), _g1_array(flat(vp.permutation_comms))
-        prm.num_preprocess_polys, prm.preprocess_comms = len(vp.preprocess_comms), pre
-        prm.num_permutation_polys, prm.permutation_comms = len(vp.permutation_comms), perm
+        prm.num_preprocess_polys, prm.num_permutation_polys = len(vp.preprocess_comms), len(vp.permutation_comms)
+        if not brakedown:
+            pre, perm = _g1_array(flat(vp.preprocess_comms)), _g1_array(flat(vp.permutation_comms))
+            prm.preprocess_comms, prm.permutation_comms = pre, perm
         inst_arrays = [_fr_array(i) for i in instances]
         inst = (C.POINTER(lh_fr) * max(len(instances), 1))(*[C.cast(a, C.POINTER(lh_fr)) for a in inst_arrays])
+        if brakedown:  # (roots as arguments, the hash transcript last; the param's two point arrays stay NULL)
+            roots = (b"".join(bytes(r) for r in vp.preprocess_comms) or None,
+                     b"".join(bytes(r) for r in vp.permutation_comms) or None)
+            tail = (inst, transcript.p, C.byref(transcript.hash_io()))
+            if len(info.num_witness_polys) != 1:
+                nph = len(info.num_witness_polys)
+                nw = (C.c_size_t * max(nph, 1))(*info.num_witness_polys)
+                nc = (C.c_size_t * max(nph, 1))(*info.num_challenges)
+                _check(vp.pcs.lib.lh_hyperplonk_verify_phases_brakedown(vp.pcs.h, C.byref(prm), *roots, nph, nw, nc, *tail))
+            else:
+                _check(vp.pcs.lib.lh_hyperplonk_verify_brakedown(vp.pcs.h, C.byref(prm), *roots, *tail))
+            return
         from . import ZeromorphVerifierParam, GeminiVerifierParam, IpaParam
         suffix = "_zeromorph" if isinstance(vp.pcs, ZeromorphVerifierParam) else \
             "_gemini" if isinstance(vp.pcs, GeminiVerifierParam) else "_hyrax" if hyrax else \

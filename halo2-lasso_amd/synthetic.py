@@ -276,12 +276,20 @@ def prover_param(pcs_pp, circuit, pcs_vp=None):
     pp.pcs, pp.num_vars, pp.info = pcs_pp, circuit.k, circuit.info
     pp.preprocess_polys, pp.permutation_polys = circuit.d_preprocess, circuit.d_permutation
     pp.num_permutation_z_polys, pp.expression = hp.compose(circuit.info)
+    pcs = hp._pcs_of(pcs_pp)
+    brakedown = isinstance(pcs_pp, hl.BrakedownParam)
+    if brakedown:  # (a Brakedown opening needs the commitment itself: the prover param keeps them, the verifier's the roots)
+        pp.preprocess_comms = pcs.batch_commit(pcs_pp, pp.preprocess_polys)
+        pp.permutation_comms = pcs.batch_commit(pcs_pp, pp.permutation_polys)
     if pcs_vp is None:
         return pp
     vp = hp.HyperPlonkVerifierParam()
     vp.pcs, vp.num_vars, vp.info = pcs_vp, circuit.k, circuit.info
     vp.num_permutation_z_polys, vp.expression = pp.num_permutation_z_polys, pp.expression
-    pcs = hp._pcs_of(pcs_pp)
+    if brakedown:
+        vp.preprocess_comms = [c.root for c in pp.preprocess_comms]
+        vp.permutation_comms = [c.root for c in pp.permutation_comms]
+        return pp, vp
     vp.preprocess_comms = pcs.batch_commit(pcs_pp, pp.preprocess_polys)
     vp.permutation_comms = pcs.batch_commit(pcs_pp, pp.permutation_polys)
     return pp, vp

@@ -285,6 +285,12 @@ lh_status lh_lasso_last_timing(lh_ctx*, double* out_ms);
  *   hyrax_rows           1    a Hyrax commit runs every row of every poly through the row kernels (csrc/kernels_hyrax.hip: the
  *                             terms of a row go into one bucket set over the generators' window table, nothing waits on
  *                             the host between rows); 0: one job of the batched MSM per row (48 jobs per planning pass)
+ *   brakedown_batch_commit 1  lh_brakedown_batch_commit runs its polys as ONE batch (a poly dimension on the load, column-hash
+ *                             and Merkle-level kernels, the encoder over all rows; one allocation, one copy of the roots);
+ *                             0: one commit per poly
+ *   brakedown_staged_open 0   lh_brakedown_batch_open stages the encoded matrix of a commitment on the host once (kernel
+ *                             bd_stage_columns + one copy) and reads the opened columns there; 0: one device-to-host copy
+ *                             per column.  (The HyperPlonk prover over Brakedown always stages.)
  *   comm_round           0    how the partial sums of a sharded sum-check round are combined over the ranks:
  *                             0 = ncclAllGather of every rank's sums + a one-thread sum-and-publish kernel;
  *                             1 = ONE collective: the round kernel leaves its sums as u64 lanes (32-bit limb | tag << 40),
@@ -676,7 +682,9 @@ lh_status lh_brakedown_trim(const lh_brakedown_param*, size_t poly_size);
 void lh_brakedown_param_free(lh_brakedown_param*);
 /* LinearCodes::encode (code/brakedown.rs:88-125) on the host: msg has row_len entries, out codeword_len */
 lh_status lh_brakedown_encode(const lh_brakedown_param*, const lh_fr* msg, lh_fr* out);
-/* commit / batch_commit (brakedown.rs:128-210): the rows and the tree stay on the ctx's device in the commitment */
+/* commit / batch_commit (brakedown.rs:128-210): the rows and the tree stay on the ctx's device in the commitment.
+ * batch_commit (option brakedown_batch_commit 1) runs the polys of the batch through the launches of one commit - rows, trees
+ * and roots bit-identical to a commit per poly - into one device allocation that the last commitment of the batch frees. */
 lh_status lh_brakedown_commit(lh_ctx*, const lh_brakedown_param*, const lh_fr* d_poly, size_t num_vars,
                               lh_brakedown_comm** out);
 lh_status lh_brakedown_batch_commit(lh_ctx*, const lh_brakedown_param*, const lh_fr* const* d_polys, size_t num_polys,
@@ -686,11 +694,18 @@ lh_status lh_brakedown_comm_root(const lh_brakedown_comm*, uint8_t* out32); /* A
 lh_status lh_brakedown_comm_rows(lh_ctx*, const lh_brakedown_comm*, lh_fr* out);
 /* the device address of the rows (tests: a change made after commit) */
 lh_status lh_brakedown_comm_rows_device(const lh_brakedown_comm*, lh_fr** d_out);
+/* the Merkle tree, a download: (2 << ceil(log2 codeword_len)) - 1 digests of 32 bytes, the leaves first, the root last */
+lh_status lh_brakedown_comm_tree(lh_ctx*, const lh_brakedown_comm*, uint8_t* out);
+/* the staged matrix of the open (kernel bd_stage_columns, then one copy): codeword_len x num_rows, column-major, i.e. the
+ * transpose of lh_brakedown_comm_rows */
+lh_status lh_brakedown_comm_stage(lh_ctx*, const lh_brakedown_param*, const lh_brakedown_comm*, lh_fr* out);
 void lh_brakedown_comm_free(lh_brakedown_comm*);
 /* open (brakedown.rs:212-276) */
 lh_status lh_brakedown_open(lh_ctx*, const lh_brakedown_param*, const lh_fr* d_poly, size_t num_vars,
                             lh_brakedown_comm* comm, const lh_fr* point, lh_transcript* t, lh_hash_transcript* ht);
-/* batch_open (brakedown.rs:278-300): one open per evaluation, in order */
+/* batch_open (brakedown.rs:278-300): one open per evaluation, in order.  Option brakedown_staged_open 1: the encoded
+ * matrix of a commitment crosses to pinned host memory once and the columns of all its opens (consecutive evaluations of
+ * one poly) are read there, instead of one device-to-host copy per column; the bytes written are the same. */
 lh_status lh_brakedown_batch_open(lh_ctx*, const lh_brakedown_param*, size_t num_vars, const lh_fr* const* d_polys,
                                   lh_brakedown_comm* const* comms, size_t num_polys, const lh_fr* points,
                                   size_t num_points, const lh_evaluation* evals, size_t num_evals, lh_transcript* t,
@@ -705,6 +720,35 @@ lh_status lh_brakedown_verify(const lh_brakedown_param*, const uint8_t* root32, 
 lh_status lh_brakedown_batch_verify(const lh_brakedown_param*, size_t num_vars, const uint8_t* roots, size_t num_comms,
                                     const lh_fr* points, size_t num_points, const lh_evaluation* evals,
                                     size_t num_evals, lh_transcript* t, lh_hash_transcript* ht);
+/* HyperPlonk over Brakedown (backend/hyperplonk.rs:421-426 runs HyperPlonk over this scheme too).  The
+ * arguments of the _zeromorph variants with the param in place of the SRS, the commitments of the preprocess and
+ * permutation polys (made once with lh_brakedown_batch_commit; NULL only when there are none) in place of nothing - an
+ * opening needs the commitment itself - and the hash transcript.  A commit round writes the raw roots through `ht` and
+ * changes no Fiat-Shamir state; the batch opening is one open per evaluation in pcs_query order, over the staged matrix.
+ * The witness, m, h and z commitments of the proof are batch commits into the ctx's arena, released when the prove
+ * returns.  LH_ERR_ARG for a circuit with Lasso lookups (num_lasso_lookups != 0), for a ctx inside a sharded prove and for a
+ * circuit whose num_vars is not the param's. */
+lh_status lh_hyperplonk_prove_brakedown(lh_ctx*, const lh_brakedown_param*, const lh_hp_param* pp,
+                                        lh_brakedown_comm* const* preprocess_comms,
+                                        lh_brakedown_comm* const* permutation_comms, const lh_fr* const* instances,
+                                        const lh_fr* const* d_witness_polys, lh_transcript* t, lh_hash_transcript* ht);
+lh_status lh_hyperplonk_prove_phases_brakedown(lh_ctx*, const lh_brakedown_param*, const lh_hp_param* pp,
+                                               lh_brakedown_comm* const* preprocess_comms,
+                                               lh_brakedown_comm* const* permutation_comms, size_t num_phases,
+                                               const size_t* num_witness_polys, const size_t* num_challenges,
+                                               const lh_fr* const* instances, const lh_hp_circuit* circuit, lh_transcript* t,
+                                               lh_hash_transcript* ht);
+/* host only.  The roots of the preprocess and permutation polys come as arguments (32 bytes each; NULL only when there
+ * are none): hvp's preprocess_comms / permutation_comms are ignored and may be NULL.  Ends in lh_brakedown_verify's check
+ * once per evaluation: LH_ERR_INVALID_PCS_OPEN with its messages, LH_ERR_INVALID_SNARK from the zero-check. */
+lh_status lh_hyperplonk_verify_brakedown(const lh_brakedown_param*, const lh_hp_vparam* hvp, const uint8_t* preprocess_roots,
+                                         const uint8_t* permutation_roots, const lh_fr* const* instances, lh_transcript* t,
+                                         lh_hash_transcript* ht);
+lh_status lh_hyperplonk_verify_phases_brakedown(const lh_brakedown_param*, const lh_hp_vparam* hvp,
+                                                const uint8_t* preprocess_roots, const uint8_t* permutation_roots,
+                                                size_t num_phases, const size_t* num_witness_polys,
+                                                const size_t* num_challenges, const lh_fr* const* instances, lh_transcript* t,
+                                                lh_hash_transcript* ht);
 
 /* ---------------------------------------------------------------- f5: the multilinear IPA (transparent AND additive)
  * PolynomialCommitmentScheme for MultilinearIpa<bn256::G1Affine> (pcs/multilinear/ipa.rs:23-337): no trusted setup, no
