@@ -98,6 +98,7 @@ pub const LH_U32_LINCOMB_MIXED: i32 = 4;
 pub const LH_U32_LINCOMB_FOLD_SMALL: i32 = 5;
 pub const LH_U32_LINCOMB_BIND2: i32 = 6;
 pub const LH_U32_SC_ROUND_BIND2: i32 = 7;
+pub const LH_U32_QUAD_SUMS: i32 = 9;
 #[repr(C)] #[derive(Clone, Copy)]
 pub struct lh_debug_u32_args {
     pub d_cols: *const *const u32, pub lens: *const usize, pub w: *const Fr, pub count: usize,
@@ -205,7 +206,8 @@ pub struct lh_lasso_route {
     pub resident_layers: u32,
     pub pp_folds: u32,
     pub msm_half_batches: u32,
-    pub reserved: [u32; 7],
+    pub open_shared_sums: u32,
+    pub reserved: [u32; 6],
 }
 
 extern "C" {

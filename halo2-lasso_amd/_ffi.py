@@ -118,7 +118,8 @@ class lh_debug_u32_args(C.Structure):  # (development: lh_debug_u32_columns)
 
 
 LH_U32_OPS = ("inner_products_small", "inner_products_small_half", "inner_products_small_quads", "inner_products_quads",
-              "lincomb_mixed", "lincomb_fold_small", "lincomb_bind2", "sc_round_u32_bind2")  # index = the op code
+              "lincomb_mixed", "lincomb_fold_small", "lincomb_bind2", "sc_round_u32_bind2", None,
+              "quad_sums")  # index = the op code (8 is not an operation)
 
 
 class lh_prof_rec(C.Structure):

@@ -2108,15 +2108,17 @@ lh_status lh_debug_u32_columns(lh_ctx* ctx, int op, const lh_debug_u32_args* a) 
   LH_TRY NEED_CTX(ctx);
   NEED(a);
   Ctx& c = ctx->c;
-  LH_REQUIRE(op >= LH_U32_INNER_PRODUCTS_SMALL && op <= LH_U32_SC_ROUND_BIND2, LH_ERR_ARG, "debug u32 columns: unknown operation");
+  LH_REQUIRE((op >= LH_U32_INNER_PRODUCTS_SMALL && op <= LH_U32_SC_ROUND_BIND2) || op == LH_U32_QUAD_SUMS, LH_ERR_ARG,
+             "debug u32 columns: unknown operation");
   LH_REQUIRE(a->n >= 1 && a->n < ((size_t)1 << 31), LH_ERR_ARG, "debug u32 columns: n must be in [1, 2^31)");
   const bool one_col = op == LH_U32_INNER_PRODUCTS_SMALL_QUADS || op == LH_U32_SC_ROUND_BIND2;
-  const bool has_lens = op == LH_U32_INNER_PRODUCTS_QUADS || op == LH_U32_LINCOMB_MIXED || op == LH_U32_LINCOMB_FOLD_SMALL ||
-                        op == LH_U32_LINCOMB_BIND2;
+  const bool has_lens = op == LH_U32_INNER_PRODUCTS_QUADS || op == LH_U32_QUAD_SUMS || op == LH_U32_LINCOMB_MIXED ||
+                        op == LH_U32_LINCOMB_FOLD_SMALL || op == LH_U32_LINCOMB_BIND2;
   const bool has_w = op == LH_U32_LINCOMB_MIXED || op == LH_U32_LINCOMB_FOLD_SMALL || op == LH_U32_LINCOMB_BIND2;
-  const bool quads = op == LH_U32_INNER_PRODUCTS_SMALL_QUADS || op == LH_U32_INNER_PRODUCTS_QUADS || op == LH_U32_LINCOMB_BIND2 ||
-                     op == LH_U32_SC_ROUND_BIND2;  // (the kernels that read a column as uint4)
-  const bool sums = op != LH_U32_INNER_PRODUCTS_QUADS && op != LH_U32_LINCOMB_MIXED && op != LH_U32_LINCOMB_FOLD_SMALL;
+  const bool quads = op == LH_U32_INNER_PRODUCTS_SMALL_QUADS || op == LH_U32_INNER_PRODUCTS_QUADS || op == LH_U32_QUAD_SUMS ||
+                     op == LH_U32_LINCOMB_BIND2 || op == LH_U32_SC_ROUND_BIND2;  // (the kernels that read a column as uint4)
+  const bool sums = op != LH_U32_INNER_PRODUCTS_QUADS && op != LH_U32_QUAD_SUMS && op != LH_U32_LINCOMB_MIXED &&
+                    op != LH_U32_LINCOMB_FOLD_SMALL;
   LH_REQUIRE(!one_col || a->count == 1, LH_ERR_ARG, "debug u32 columns: this operation takes one column");
   if (op == LH_U32_LINCOMB_MIXED)
     LH_REQUIRE(a->num_fr <= (size_t)LCM_MAX_FR && a->count <= (size_t)LCM_MAX_SMALL, LH_ERR_ARG, "debug u32 columns: too many inputs");
@@ -2154,6 +2156,7 @@ lh_status lh_debug_u32_columns(lh_ctx* ctx, int op, const lh_debug_u32_args* a) 
     case LH_U32_INNER_PRODUCTS_SMALL_HALF: k_inner_products_small_half(c, cols, a->count, dw, a->n, r0, (Fr*)a->out_host); break;
     case LH_U32_INNER_PRODUCTS_SMALL_QUADS: k_inner_products_small_quads(c, cols[0], dw, a->n, (Fr*)a->out_host); break;
     case LH_U32_INNER_PRODUCTS_QUADS: k_inner_products_quads(c, cols, a->lens, a->count, dw, a->n, (Fr*)a->d_out); break;
+    case LH_U32_QUAD_SUMS: k_quad_sums(c, cols, a->lens, a->count, dw, a->n, (Fr*)a->d_out); break;
     case LH_U32_LINCOMB_MIXED:
       k_lincomb_mixed(c, (const Fr* const*)a->d_fr, (const Fr*)a->w_fr, a->num_fr, cols, a->lens, (const Fr*)a->w, a->count, a->n,
                       (Fr*)a->d_out);

@@ -155,6 +155,7 @@ static constexpr struct KnobRow {
     // A/B switches of round 6's routes (the bytes never depend on them)
     {"LH_FIN_LANES_MIN_BYTES", REAL, 0, -1, 1e18},     // -1: no launch hands over in lanes
     {"LH_SC_U32", INT, 1, 0, 1}, {"LH_OPEN_U32_ROUNDS", INT, 1, 0, 1}, {"LH_OPEN_FOLD_COLS", INT, 1, 0, 1},
+    {"LH_OPEN_SHARE_SUMS", INT, 1, 0, 1, true},        // the opening takes the evaluation passes' quad sums (live: tests flip it)
     // operation
     {"LH_HOST_THREADS", INT, 48, 0, 4096},             // host pool threads, the caller's included
     {"LH_JIT_CACHE", INT, 1, 0, 1}, {"LH_JIT_CACHE_DIR", PATH, 0, 0, 0},

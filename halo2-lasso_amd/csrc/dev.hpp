@@ -166,7 +166,7 @@ struct Options {
 enum class Knob {  // (grouped as the table: thresholds, A/B switches, operation, diagnostics, test hooks)
   SC_TAIL_G, MSM_C_OFF, MSM_C_MAX, MSM_K2, MSM_SEG, MSM_SLAB_LOG, MSM_TREE_MAX, MSM_QUAD_MAX, MSM_TWO_LEVEL, MSM_HALF_MIN_LOG,
   MSM_HALF_COVER, EXPR_MONOMIALS, EXPR_JIT_MIN_VARS, EXPR_EF_MIN_VARS,
-  FIN_LANES_MIN_BYTES, SC_U32, OPEN_U32_ROUNDS, OPEN_FOLD_COLS,
+  FIN_LANES_MIN_BYTES, SC_U32, OPEN_U32_ROUNDS, OPEN_FOLD_COLS, OPEN_SHARE_SUMS,
   HOST_THREADS, JIT_CACHE, JIT_CACHE_DIR, EXPR_JIT, SC_TAIL_TIMEOUT_MS, GKR_START_TIMEOUT_MS, COMM_WAIT_TIMEOUT_MS, COMM_A2A,
   COMM_PROBE,
   HOST_TRACE, SC_TAIL_TRACE, GKR_TRACE, SC_DEBUG, MSM_DEBUG, HP_DEBUG, COMM_DEBUG, OPEN_SMALL_CHECK,
@@ -178,7 +178,8 @@ const char* knob_text(Knob k);  // a path knob's value (nullptr: unset or empty)
 struct RouteStats {  // lh_lasso_route (include/lasso_hip.h): counters of the last Lasso prove on the ctx
   uint32_t v[LH_LASSO_ROUTE_WORDS] = {0};
   enum { OPEN_DEPTH, OPEN_PASSES, EF_ROUNDS, STD_ROUNDS, RW_ROUNDS, TAILS, TAIL_ROUNDS, PACKED_TS, DERIVED, SORTED_REUSE,
-         SHARDED_ROUNDS, SHARD_EXCHANGES, WIN_TABLE_JOBS, OPEN_PRECOMMIT, RESIDENT_LAYERS, PP_FOLDS, MSM_HALF_BATCHES };
+         SHARDED_ROUNDS, SHARD_EXCHANGES, WIN_TABLE_JOBS, OPEN_PRECOMMIT, RESIDENT_LAYERS, PP_FOLDS, MSM_HALF_BATCHES,
+         OPEN_SHARED_SUMS };
 };
 
 // ------------------------------------------------------------------ a long-lived host thread (dev.cpp)
@@ -252,6 +253,17 @@ struct Ctx {
     bool sharded = false;  // this rank's shard of the table (sharded proofs)
   };
   std::vector<EqHalfEntry> eq_half_cache;
+  // quad sums S_t = sum_q E_1[q] col[4q + t], t = 0..3, of 32-bit columns at points of one proof (sumcheck.cpp quad_sums_*): the
+  // evaluation side makes them, the batch opening's column rounds take them.  Keyed by the column's device pointer, its length
+  // and ALL coordinates of the point - the arena hands out the same pointers proof after proof -; same lifetime as the eq
+  // tables above (EqHalfScope), cleared at the start of every prove.
+  struct QuadSumEntry {
+    const uint32_t* col;
+    size_t len;
+    std::vector<uint8_t> point;  // the bytes of y[0..n)
+    Fr s[4];
+  };
+  std::vector<QuadSumEntry> quad_sums;
   bool prof = false;
   std::vector<ProfRec> prof_recs;
   // LIVE records (lh_profile_enable(ctx, 2)): a HIP-event pair around every bucket-accumulation launch, on the stream it is
@@ -461,6 +473,10 @@ void k_inner_products_small_quads(Ctx&, const uint32_t* col, const Fr* e0, size_
 // d_out[4 k + t] (DEVICE, queued on the stream) = sum_q e1[q] cols[k][4 q + t], t = 0..3, q < quads; lens: multiples of 4
 void k_inner_products_quads(Ctx&, const uint32_t* const* cols, const size_t* lens, size_t count, const Fr* e1, size_t quads,
                             Fr* d_out);
+// the same sums of ALL the columns in one launch (per QS_MAX_COLS) against one read of e0 = the eq table of the point's tail
+// y[1..] (2 quads entries): d_out[4 k + t] (DEVICE, queued on the stream) = sum_q (e0[2q] + e0[2q+1]) cols[k][4 q + t]
+constexpr int QS_MAX_COLS = 24;
+void k_quad_sums(Ctx&, const uint32_t* const* cols, const size_t* lens, size_t count, const Fr* e0, size_t quads, Fr* d_out);
 // out[i] = sum_k w[k] (cols[k][4i..4i+3] bound with (r0, r1)), i < 2 size; out_host[e] = sum_b eq_level[b] out[2b + e]
 void k_lincomb_bind2(Ctx&, const uint32_t* const* cols, const size_t* lens, const Fr* w, size_t count, const Fr& r0, const Fr& r1,
                      const Fr* eq_level, size_t size, Fr* out, Fr* out_host);

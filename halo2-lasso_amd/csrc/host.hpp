@@ -168,12 +168,26 @@ SumCheckResult sum_check_prove(Ctx&, int prover_kind, size_t num_vars, const lh_
 // rank's shard of it with the rank's factor of the shard coordinates multiplied in
 const Fr* eq_half_lookup(Ctx&, const HFr* y, size_t num_vars, bool sharded = false);
 const Fr* eq_half_get(Ctx&, const HFr* y, size_t num_vars, bool sharded = false);  // built (in the arena, at the caller's depth) when absent
-struct EqHalfScope {  // forgets, on exit, what was cached after its creation
+struct EqHalfScope {  // forgets, on exit, what was cached after its creation (eq tables and quad sums alike)
   Ctx& c;
-  size_t mark;
-  explicit EqHalfScope(Ctx& c_) : c(c_), mark(c_.eq_half_cache.size()) {}
-  ~EqHalfScope() { c.eq_half_cache.resize(mark); }
+  size_t mark, mark_sums;
+  explicit EqHalfScope(Ctx& c_) : c(c_), mark(c_.eq_half_cache.size()), mark_sums(c_.quad_sums.size()) {}
+  ~EqHalfScope() {
+    c.eq_half_cache.resize(mark);
+    c.quad_sums.resize(mark_sums);
+  }
 };
+// Will a batch opening of num_vars-variable polys given as 32-bit columns take its rounds 0 and 1 from the columns' quad sums
+// (sumcheck.cpp, ScOptions::u32_terms)?  What can be known without the opening's expression: the sum-check adds its own
+// conditions on the round kernels; the argument asks before it decides how to make its evaluations.
+bool sc_open_column_rounds(const Ctx&, size_t num_vars, bool sharded);
+// The proof's table of quad sums (Ctx::quad_sums): S_0..S_3 of the column (col, len) at the point y, or null
+const Fr* quad_sums_lookup(const Ctx&, const uint32_t* col, size_t len, const HFr* y, size_t num_vars);
+void quad_sums_put(Ctx&, const uint32_t* col, size_t len, const HFr* y, size_t num_vars, const HFr s[4]);
+// evals[k] = cols[k](y) for `count` columns of 2^num_vars entries, num_vars >= 3, from ONE pass that makes every column's
+// quad sums against eq_half = the eq table of y[1..] (k_quad_sums) and leaves them in the table:
+//   col(y) = (1-y0)(1-y1) S_0 + y0 (1-y1) S_1 + (1-y0) y1 S_2 + y0 y1 S_3
+void quad_sums_evaluate(Ctx&, const uint32_t* const* cols, size_t count, const HFr* y, size_t num_vars, const Fr* eq_half, HFr* evals);
 
 // the round loop shared by every sum-check front end (sumcheck.cpp)
 typedef std::function<void(const Fr* const*, Fr* const*, const Fr&, bool, size_t, Fr*)> RoundFn;

@@ -798,6 +798,133 @@ void k_inner_products_quads(Ctx& c, const uint32_t* const* cols, const size_t* l
   }
 }
 
+// The quad sums of ALL columns of a point in one launch, against ONE read of the eq table: the evaluation side of a proof
+// (lasso.cpp, sumcheck.cpp quad_sums_evaluate) makes them where it used to make the even / odd halves, and the batch
+// opening takes them from the proof's table instead of summing again.  A workgroup takes a block of 256 QS_QPL quads; every
+// lane keeps the E_1 entries of its QS_QPL quads - made from e0 = eq(y[1..]) on the fly, E_1[q] = e0[2q] + e0[2q + 1], as
+// the Surge kernel does - in LDS slots of its own (no lane reads another's: no barrier anywhere; in registers they cost 8
+// each of a budget that four ten-limb accumulators with their carries already fill to ~100) and sweeps the columns over
+// them: four accumulators for the column in hand, flushed per column and WAVE.  The flush adds the lanes' accumulators as
+// integers (they are far from full: 64 QS_QPL terms below 2^286) with the four sums spread over the wave's quarters - 7
+// ten-limb additions and 70 lane exchanges instead of 24 and 240 - and leaves the unreduced limbs: quad_sums_reduce_kernel
+// adds the waves' partials and reduces ONCE per sum.
+// Quads per lane: 4 - 32 KB of LDS per workgroup, 123 registers, four workgroups per CU; the flush is about half of a
+// column's instructions.  8 (64 KB, two workgroups per CU, the flush a third) is slower: twelve columns of 2^24 entries
+// take 0.37 ms with 4 (2.9 TB/s of algorithmic bytes) and 0.44 ms with 8; the even / odd pass that made the same
+// evaluations (k_inner_products_small_half) took 0.70 ms, the opening's k_inner_products_quads over them 0.76 ms.
+constexpr int QS_QPL = 4;
+struct QuadSumsPack {
+  const uint32_t* p[QS_MAX_COLS];
+  uint64_t quads[QS_MAX_COLS];  // min(len / 4, quads of the table) of each column
+  int count;
+};
+__device__ __forceinline__ void wide_add(Wide& a, const Wide& b) {
+  uint64_t carry = 0;
+#pragma unroll
+  for (int k = 0; k < 10; k++) {
+    const uint64_t t = (uint64_t)a.l[k] + b.l[k] + carry;
+    a.l[k] = (uint32_t)t;
+    carry = t >> 32;
+  }
+}
+// both lanes of a pair (lane ^ mask) keep one of two values and hand the other over: keep + the partner's share of it
+__device__ __forceinline__ Wide wide_exchange_add(const Wide& lo, const Wide& hi, bool upper, int mask) {
+  Wide keep, recv;
+#pragma unroll
+  for (int k = 0; k < 10; k++) {
+    keep.l[k] = upper ? hi.l[k] : lo.l[k];
+    recv.l[k] = (uint32_t)__shfl_xor((int)(upper ? lo.l[k] : hi.l[k]), mask, 64);
+  }
+  wide_add(keep, recv);
+  return keep;
+}
+template <int QPL>
+__global__ __launch_bounds__(256, 4) void quad_sums_kernel(QuadSumsPack pk, const Fr* __restrict__ e0, size_t quads,
+                                                        uint32_t* __restrict__ partials) {
+  __shared__ uint4 hs[2][QPL * 256];  // E_1 of quad i of lane t: limbs 0..3 in hs[0][256 i + t], limbs 4..7 in hs[1][256 i + t]
+  const size_t base = (size_t)blockIdx.x * (256 * QPL) + threadIdx.x;  // quad i of this lane: base + 256 i
+#pragma unroll
+  for (int i = 0; i < QPL; i++) {
+    const size_t q = base + (size_t)i * 256;
+    const Fr h = q < quads ? add(e0[2 * q], e0[2 * q + 1]) : Fr::zero();
+    hs[0][256 * i + threadIdx.x] = make_uint4(h.l[0], h.l[1], h.l[2], h.l[3]);
+    hs[1][256 * i + threadIdx.x] = make_uint4(h.l[4], h.l[5], h.l[6], h.l[7]);
+  }
+  const int lane = threadIdx.x & 63;
+  const size_t rows = (size_t)gridDim.x * 4, row = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);  // a row per wave
+#pragma nounroll
+  for (int k = 0; k < pk.count; k++) {
+    const uint4* __restrict__ col = (const uint4*)pk.p[k];
+    const size_t cq = pk.quads[k];
+    Wide acc[4];
+#pragma unroll
+    for (int t = 0; t < 4; t++) acc[t] = Wide::zero();
+    uint4 a[QPL];  // QPL loads in flight per lane
+#pragma unroll
+    for (int i = 0; i < QPL; i++) {
+      const size_t q = base + (size_t)i * 256;
+      a[i] = q < cq ? col[q] : make_uint4(0u, 0u, 0u, 0u);
+    }
+#pragma unroll
+    for (int i = 0; i < QPL; i++) {
+      const uint4 lo = hs[0][256 * i + threadIdx.x], hi = hs[1][256 * i + threadIdx.x];
+      Fr h;
+      h.l[0] = lo.x, h.l[1] = lo.y, h.l[2] = lo.z, h.l[3] = lo.w, h.l[4] = hi.x, h.l[5] = hi.y, h.l[6] = hi.z, h.l[7] = hi.w;
+      wide_mac(acc[0], h, a[i].x), wide_mac(acc[1], h, a[i].y), wide_mac(acc[2], h, a[i].z), wide_mac(acc[3], h, a[i].w);
+      __builtin_amdgcn_sched_barrier(0);  // (a quad at a time: the scheduler otherwise fetches every E_1 entry first and spills)
+    }
+    // lanes 0..31 go on with S_0, S_1 and lanes 32..63 with S_2, S_3; then the quarters with one sum each: S_(lane / 16)
+    const bool up32 = (lane & 32) != 0, up16 = (lane & 16) != 0;
+    const Wide b0 = wide_exchange_add(acc[0], acc[2], up32, 32), b1 = wide_exchange_add(acc[1], acc[3], up32, 32);
+    Wide s = wide_exchange_add(b0, b1, up16, 16);
+#pragma unroll
+    for (int mask = 8; mask >= 1; mask >>= 1) {
+      Wide o;
+#pragma unroll
+      for (int j = 0; j < 10; j++) o.l[j] = (uint32_t)__shfl_xor((int)s.l[j], mask, 64);
+      wide_add(s, o);
+    }
+    if ((lane & 15) == 0) {
+      uint32_t* dst = partials + ((size_t)(4 * k + (lane >> 4)) * rows + row) * 10;
+#pragma unroll
+      for (int j = 0; j < 10; j++) dst[j] = s.l[j];
+    }
+  }
+}
+// out[r] = the sum of row r's `per_row` ten-limb partials, reduced once (a lane adds at most per_row / 256 of them, each
+// below 2^300: far inside ten limbs)
+__global__ __launch_bounds__(256) void quad_sums_reduce_kernel(const uint32_t* __restrict__ partials, size_t per_row,
+                                                               Fr* __restrict__ out) {
+  __shared__ Fr lds[4];
+  const uint32_t* row = partials + (size_t)blockIdx.x * per_row * 10;
+  Wide acc = Wide::zero();
+  for (size_t i = threadIdx.x; i < per_row; i += blockDim.x) {
+    Wide w;
+#pragma unroll
+    for (int j = 0; j < 10; j++) w.l[j] = row[i * 10 + j];
+    wide_add(acc, w);
+  }
+  const Fr v = block_reduce_sum(wide_reduce(acc), lds);
+  if (threadIdx.x == 0) out[blockIdx.x] = v;
+}
+void k_quad_sums(Ctx& c, const uint32_t* const* cols, const size_t* lens, size_t count, const Fr* e0, size_t quads, Fr* d_out) {
+  ProfScope ps(c, "quad_sums", 4.0 * 4 * quads * count + 64.0 * quads, 0.25 * quads * count, (double)quads);
+  if (!count) return;
+  LH_REQUIRE(quads >= 1, LH_ERR_ARG, "quad_sums: empty table");
+  const size_t per_block = (size_t)256 * QS_QPL, blocks = (quads + per_block - 1) / per_block, rows = blocks * 4;
+  LH_REQUIRE(blocks < ((size_t)1 << 31), LH_ERR_ARG, "quad_sums: table too large");
+  // (queued work reads it: the caller's arena scope holds it)
+  uint32_t* partials = c.arena.alloc_n<uint32_t>(rows * 10 * 4 * std::min<size_t>(count, QS_MAX_COLS));
+  for (size_t base = 0; base < count; base += QS_MAX_COLS) {
+    QuadSumsPack pk;
+    memset(&pk, 0, sizeof(pk));
+    pk.count = (int)std::min<size_t>(QS_MAX_COLS, count - base);
+    for (int i = 0; i < pk.count; i++) pk.p[i] = cols[base + i], pk.quads[i] = std::min(lens[base + i] / 4, quads);
+    hipLaunchKernelGGL(quad_sums_kernel<QS_QPL>, dim3((unsigned)blocks), 256, 0, c.stream, pk, e0, quads, partials);
+    hipLaunchKernelGGL(quad_sums_reduce_kernel, 4 * pk.count, 256, 0, c.stream, partials, rows, d_out + 4 * base);
+  }
+}
+
 // Round 2 of such a term: merged_m bound with (r0, r1) straight from its columns -
 //   out[i] = sum_k w_k ((1-r1)(1-r0) col_k[4i] + (1-r1) r0 col_k[4i+1] + r1 (1-r0) col_k[4i+2] + r1 r0 col_k[4i+3]),
 // 4 x 8 multiply-adds per column and ONE Montgomery reduction per bound entry (the 4 weights of a column arrive times R) -

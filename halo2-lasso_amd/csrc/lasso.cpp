@@ -260,6 +260,11 @@ LassoClaims lasso_argue(Ctx& c, const lh_lasso_table& tb, size_t n, const LassoC
   for (uint32_t m = 0; m < tb.num_terms; m++) linear_g = linear_g && tb.g_num_factors[m] == 1;
   Fr a_sums[4];  // (k_inner_products_small_quads: the claim's two halves - and rounds 0 and 1 of the Surge sum-check over a)
   bool have_a_sums = false;
+  // Where the batch opening will take its rounds 0 and 1 from the columns' quad sums (sc_open_column_rounds - a guess: the
+  // opening may still decide otherwise, then the table below is simply not read), the evaluations at r_z and r_N are made
+  // from those very sums, which stay in the proof's table (quad_sums_evaluate); Surge's round 0 leaves the entry of a at r.
+  // (n >= l: the opening's points are these, not zero-padded ones.)  LH_OPEN_SHARE_SUMS=0: as before, for A/B.
+  const bool share_sums = !shn && n >= 3 && n >= l && knob(Knob::OPEN_SHARE_SUMS) != 0 && sc_open_column_rounds(c, n, shn);
   if (a_small && n >= 2) {
     // against the eq table of r[1..] (half the entries), which the Surge sum-check and the batch opening at r use as well
     const Fr* eq_half = eq_half_get(c, cl.r.data(), n, shn);
@@ -268,6 +273,14 @@ LassoClaims lasso_argue(Ctx& c, const lh_lasso_table& tb, size_t n, const LassoC
       const HFr r0 = cl.r[0];
       cl.v = (HFr::one() - r0) * hst(a_sums[0]) + r0 * hst(a_sums[1]);
       have_a_sums = true;
+      // even = (1 - y1) S_0 + y1 S_2 and odd = (1 - y1) S_1 + y1 S_3 with y1 = r[1]: S_0 and S_1 from the kernel's four sums
+      const HFr y1 = cl.r[1], n1 = HFr::one() - y1;
+      if (share_sums && !n1.is_zero()) {
+        const HFr inv = n1.inv();
+        const HFr s4[4] = {(hst(a_sums[0]) - y1 * hst(a_sums[2])) * inv, (hst(a_sums[1]) - y1 * hst(a_sums[3])) * inv,
+                           hst(a_sums[2]), hst(a_sums[3])};
+        quad_sums_put(c, a_small, N, cl.r.data(), n, s4);
+      }
     } else {
       k_inner_products_small_half(c, &a_small, 1, eq_half, N / 2, dev(cl.r[0]), (Fr*)&cl.v);
     }
@@ -316,7 +329,8 @@ LassoClaims lasso_argue(Ctx& c, const lh_lasso_table& tb, size_t n, const LassoC
     sc.evals.assign(alpha, HFr::zero());
     if (n >= 2) {  // (the table of r_z[1..] stays for the batch opening at r_z)
       const Fr* eq_half = eq_half_get(c, sc.challenges.data(), n, shn);
-      k_inner_products_small_half(c, cols.data(), alpha, eq_half, N / 2, dev(sc.challenges[0]), (Fr*)sc.evals.data());
+      if (share_sums) quad_sums_evaluate(c, cols.data(), alpha, sc.challenges.data(), n, eq_half, sc.evals.data());
+      else k_inner_products_small_half(c, cols.data(), alpha, eq_half, N / 2, dev(sc.challenges[0]), (Fr*)sc.evals.data());
       sum_ranks(sc.evals.data(), alpha);
     } else {
       ArenaScope scope(c.arena);
@@ -396,7 +410,9 @@ LassoClaims lasso_argue(Ctx& c, const lh_lasso_table& tb, size_t n, const LassoC
     for (size_t i = 0; i < alpha; i++) at_n.push_back(w.E[i]);
     cl.ev_n.resize(at_n.size());
     Fr* eq = c.arena.alloc_n<Fr>(eq_half_n ? M : std::max(N, M));
-    if (eq_half_n) {
+    if (eq_half_n && share_sums) {
+      quad_sums_evaluate(c, at_n.data(), at_n.size(), cl.r_N.data(), n, eq_half_n, cl.ev_n.data());
+    } else if (eq_half_n) {
       k_inner_products_small_half(c, at_n.data(), at_n.size(), eq_half_n, N / 2, dev(cl.r_N[0]), (Fr*)cl.ev_n.data());
       sum_ranks(cl.ev_n.data(), cl.ev_n.size());
     } else {
@@ -455,6 +471,7 @@ void lasso_prove(Ctx& c, const Pcs& pcs, const lh_lasso_table& tb, size_t n, con
   };
 
   ArenaScope scope(c.arena);
+  c.quad_sums.clear();  // (nothing of an earlier prove: the arena hands out the same pointers again)
   EqHalfScope eq_scope(c);  // (the shared eq tables are arena memory of this scope)
   c.route = RouteStats();
   std::vector<uint32_t> count_ors(cc, 0);  // OR of every final_cts column (bounds its read_ts column) when computed

@@ -198,6 +198,45 @@ const Fr* eq_half_get(Ctx& c, const HFr* y, size_t num_vars, bool sharded) {
   return t;
 }
 
+// ------------------------------------------------------------------ the proof's table of quad sums (host.hpp)
+bool sc_open_column_rounds(const Ctx& c, size_t num_vars, bool sharded) {
+  // (from 2^22 entries on: below that the ~11 quad-sum launches of a proof are latency - 2^20 AND 11.35 -> 12.1 ms, 2^20 range
+  //  +0.15, 2^21 even, 2^22 range -0.25 ms; profiles/README.md round 6)
+  return knob(Knob::OPEN_U32_ROUNDS) != 0 /* (development A/B) */ && c.opt.sc_eq_factoring != 0 && !sharded && num_vars >= 22;
+}
+const Fr* quad_sums_lookup(const Ctx& c, const uint32_t* col, size_t len, const HFr* y, size_t num_vars) {
+  const size_t bytes = num_vars * sizeof(HFr);
+  for (const Ctx::QuadSumEntry& e : c.quad_sums)
+    if (e.col == col && e.len == len && e.point.size() == bytes && memcmp(e.point.data(), y, bytes) == 0) return e.s;
+  return nullptr;
+}
+void quad_sums_put(Ctx& c, const uint32_t* col, size_t len, const HFr* y, size_t num_vars, const HFr s[4]) {
+  if (quad_sums_lookup(c, col, len, y, num_vars)) return;  // (E = dim of an identity subtable: the same column twice)
+  Ctx::QuadSumEntry e;
+  e.col = col, e.len = len;
+  e.point.assign((const uint8_t*)y, (const uint8_t*)y + num_vars * sizeof(HFr));
+  for (int t = 0; t < 4; t++) e.s[t] = dev(s[t]);
+  c.quad_sums.push_back(std::move(e));
+}
+void quad_sums_evaluate(Ctx& c, const uint32_t* const* cols, size_t count, const HFr* y, size_t num_vars, const Fr* eq_half,
+                        HFr* evals) {
+  LH_REQUIRE(num_vars >= 3, LH_ERR_ARG, "quad sums: needs three variables");
+  if (!count) return;
+  ArenaScope scope(c.arena);
+  const size_t len = (size_t)1 << num_vars;
+  std::vector<size_t> lens(count, len);
+  Fr* d_s = c.arena.alloc_n<Fr>(4 * count);
+  k_quad_sums(c, cols, lens.data(), count, eq_half, len / 4, d_s);
+  std::vector<HFr> s(4 * count);
+  c.d2h(s.data(), d_s, s.size() * sizeof(HFr));
+  const HFr y0 = y[0], y1 = y[1], n0 = HFr::one() - y0, n1 = HFr::one() - y1;
+  const HFr w4[4] = {n0 * n1, y0 * n1, n0 * y1, y0 * y1};
+  for (size_t k = 0; k < count; k++) {
+    evals[k] = w4[0] * s[4 * k] + w4[1] * s[4 * k + 1] + w4[2] * s[4 * k + 2] + w4[3] * s[4 * k + 3];
+    quad_sums_put(c, cols[k], len, y, num_vars, &s[4 * k]);
+  }
+}
+
 // ------------------------------------------------------------------ the round loop of ClassicSumCheck::prove
 // (classic.rs:208-240) shared by the sum-of-products and the general-expression front ends.
 // `cur`: current tables (polys first), `used[i]`: the round kernel binds/stores table i itself,
@@ -797,11 +836,9 @@ SumCheckResult sum_check_prove(Ctx& c, int prover_kind, size_t num_vars, const l
   std::vector<Fr> u32t_sums;  // [term][4]: sum over the term's columns of w_k S_t(col_k)
   Fr u32t_r0;
   if (!u32t.polys.empty()) {
-    const bool u32t_off = knob(Knob::OPEN_U32_ROUNDS) == 0;  // (development A/B)
     LH_REQUIRE(u32t.polys.size() == num_polys, LH_ERR_ARG, "sum-check: the column hint does not match the polys");
-    // (from 2^22 entries on: below that the ~11 quad-sum launches of a proof are latency - 2^20 AND 11.35 -> 12.1 ms, 2^20 range
-    //  +0.15, 2^21 even, 2^22 range -0.25 ms; profiles/README.md round 6)
-    bool ok = !u32t_off && use_ef && ef.per_term && !sharded && degree == 2 && streams2 && num_vars >= 22 &&
+    // (sc_open_column_rounds: the part of the predicate that the argument can ask about before the opening exists)
+    bool ok = sc_open_column_rounds(c, num_vars, sharded) && use_ef && ef.per_term && degree == 2 && streams2 &&
               k_sc_round_streams(rd, degree, len0 >> 3) &&
               (len0 >> 2) > std::max<size_t>(k_sc_tail_capacity(c, rd, degree), (size_t)GKR_CAP * GKR_CAP);
     for (const ScU32Terms::Poly& pl : u32t.polys) {
@@ -932,19 +969,47 @@ SumCheckResult sum_check_prove(Ctx& c, int prover_kind, size_t num_vars, const l
         LH_REQUIRE(bind == (round >= 1), LH_ERR_ARG, "sum-check: the column rounds met another shape");
         const uint32_t M = rd.num_terms;
         if (round == 0) {
-          // the quad sums of every column against its term's E_1, one download; then per term the weighted sums
+          // the quad sums of every column against its term's E_1: from the proof's table where the evaluation at the same
+          // point left them (quad_sums_evaluate, Surge's round 0), one launch set per term and ONE download for the pairs
+          // that are missing (the short final_cts columns at r_M; everything with LH_OPEN_SHARE_SUMS=0) - none missing: no
+          // launch, no download; then per term the weighted sums
           ArenaScope scope(c.arena);
+          const bool share = knob(Knob::OPEN_SHARE_SUMS) != 0;
           size_t total = 0;
           for (uint32_t m = 0; m < M; m++) total += u32t.polys[term_poly[m]].col.size();
-          Fr* d_s = c.arena.alloc_n<Fr>(4 * total);
-          size_t off = 0;
+          std::vector<Fr> hs(4 * total);
+          std::vector<char> found(total, 0);
+          size_t off = 0, missing = 0;
           for (uint32_t m = 0; m < M; m++) {
             const ScU32Terms::Poly& pl = u32t.polys[term_poly[m]];
-            k_inner_products_quads(c, pl.col.data(), pl.len.data(), pl.col.size(), ef.eqs[m].level[1], size >> 1, d_s + 4 * off);
+            for (size_t k = 0; k < pl.col.size(); k++) {
+              const Fr* s4 = share ? quad_sums_lookup(c, pl.col[k], pl.len[k], ef.eqs[m].y, num_vars) : nullptr;
+              if (s4) memcpy(&hs[4 * (off + k)], s4, 4 * sizeof(Fr)), found[off + k] = 1;
+              else missing++;
+            }
             off += pl.col.size();
           }
-          std::vector<Fr> hs(4 * total);
-          c.d2h(hs.data(), d_s, hs.size() * sizeof(Fr));
+          c.route.v[RouteStats::OPEN_SHARED_SUMS] += (uint32_t)(total - missing);
+          if (missing) {
+            Fr* d_s = c.arena.alloc_n<Fr>(4 * missing);
+            size_t at = 0;
+            off = 0;
+            for (uint32_t m = 0; m < M; m++) {
+              const ScU32Terms::Poly& pl = u32t.polys[term_poly[m]];
+              std::vector<const uint32_t*> mc;
+              std::vector<size_t> ml;
+              for (size_t k = 0; k < pl.col.size(); k++)
+                if (!found[off + k]) mc.push_back(pl.col[k]), ml.push_back(pl.len[k]);
+              if (!mc.empty()) k_inner_products_quads(c, mc.data(), ml.data(), mc.size(), ef.eqs[m].level[1], size >> 1, d_s + 4 * at);
+              at += mc.size();
+              off += pl.col.size();
+            }
+            std::vector<Fr> ms(4 * missing);
+            c.d2h(ms.data(), d_s, ms.size() * sizeof(Fr));
+            at = 0;
+            for (size_t i = 0; i < total; i++)
+              if (!found[i]) memcpy(&hs[4 * i], &ms[4 * at++], 4 * sizeof(Fr));
+          }
           u32t_sums.assign(4 * (size_t)M, dev(HFr::zero()));
           off = 0;
           for (uint32_t m = 0; m < M; m++) {

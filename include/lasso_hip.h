@@ -323,7 +323,9 @@ typedef struct lh_lasso_route {
   uint32_t pp_folds;            /* sum-checks whose batching coefficients were folded into the left factors (sc_pp_fold) */
   uint32_t msm_half_batches;    /* MSM batches that ran as two pipelined halves (msm_half_batches; the slot was msm29_batches,
                                    always 0 since round 5) */
-  uint32_t reserved[7];
+  uint32_t open_shared_sums;    /* (column, point) pairs whose quad sums the batch opening's column rounds took from the
+                                   evaluation passes of the same proof instead of summing again (LH_OPEN_SHARE_SUMS) */
+  uint32_t reserved[6];
 } lh_lasso_route;
 lh_status lh_lasso_last_route(lh_ctx*, lh_lasso_route* out);
 
@@ -911,6 +913,8 @@ lh_status lh_debug_sort_plan(size_t n, unsigned bits, int key_bytes, unsigned* p
  *   INNER_PRODUCTS_SMALL_QUADS  one column of 4 n entries, d_weights = e0 (2 n entries); out_host[0..3] = sum_b e0[b] col[2b],
  *                               sum_b e0[b] col[2b+1], sum_q (e0[2q] + e0[2q+1]) col[4q+2], the same with col[4q+3]
  *   INNER_PRODUCTS_QUADS        d_out[4 k + t] = sum_{q < n} d_weights[q] d_cols[k][4 q + t]; entries from lens[k] on are zero
+ *   QUAD_SUMS                   the same sums of all the columns in one launch from d_weights = e0 (2 n entries):
+ *                               d_out[4 k + t] = sum_{q < n} (e0[2q] + e0[2q+1]) d_cols[k][4 q + t]; zero from lens[k] on
  *   LINCOMB_MIXED               d_out[i] = sum_k w_fr[k] d_fr[k][i] + sum_k w[k] d_cols[k][i], i < n (zero from lens[k] on)
  *   LINCOMB_FOLD_SMALL          d_out[i] = (1 - r0) g[i] + r0 g[i + n], g = sum_k w[k] d_cols[k] (zero from lens[k] on), i < n;
  *                               *taken = 0 and nothing written when count is 0 or above 24
@@ -919,7 +923,7 @@ lh_status lh_debug_sort_plan(size_t n, unsigned bits, int key_bytes, unsigned* p
  *   SC_ROUND_BIND2              the same of one column with weight one; out_host[0] = sum_{b < n} d_weights[b] d_out[2b + 1]
  * Refused with LH_ERR_ARG before anything is launched: a null pointer that the operation reads or writes, n == 0, more inputs
  * than a launch takes (LINCOMB_MIXED: 8 tables and 24 columns, LINCOMB_BIND2: 24 columns), and for the operations that read a
- * column 16 bytes at a time (the two QUADS and the two BIND2) a column that is not 16-byte aligned or a length that is no
+ * column 16 bytes at a time (the two QUADS, QUAD_SUMS and the two BIND2) a column that is not 16-byte aligned or a length that is no
  * multiple of 4.  The call returns after the stream has drained. */
 enum {
   LH_U32_INNER_PRODUCTS_SMALL = 0,
@@ -929,7 +933,8 @@ enum {
   LH_U32_LINCOMB_MIXED = 4,
   LH_U32_LINCOMB_FOLD_SMALL = 5,
   LH_U32_LINCOMB_BIND2 = 6,
-  LH_U32_SC_ROUND_BIND2 = 7
+  LH_U32_SC_ROUND_BIND2 = 7,
+  LH_U32_QUAD_SUMS = 9 /* (8 is not an operation: LH_ERR_ARG, like every other value) */
 };
 typedef struct lh_debug_u32_args {
   const uint32_t* const* d_cols; /* `count` columns */
