@@ -516,7 +516,76 @@ class Evaluation:
         self.poly, self.point, self.value = poly, point, value % R_MOD
 
 
+class _PointPcs:
+    """What the schemes whose commitments are G1 points share.  A scheme NAME has the entries lh_<NAME>_batch_commit / open /
+    batch_open(ctx, *pp.head(), ...) and lh_<NAME>_verify / batch_verify(*vp.head(), ...): a param says how it crosses the
+    boundary through head(), and names its lh_lasso_* / lh_hyperplonk_* entries through `suffix`."""
+    NAME = None
+
+    @staticmethod
+    def _chunks(pp):
+        """points per commitment where a commitment is a list of points (HyraxParam.num_chunks); None: it is one point"""
+        return getattr(pp, "num_chunks", None)
+
+    @staticmethod
+    def _points(vp, comms):
+        return list(comms) if _PointPcs._chunks(vp) is None else [p for cm in comms for p in cm]
+
+    @classmethod
+    def _fn(cls, what):
+        return getattr(_ffi.load(), "lh_%s_%s" % (cls.NAME, what))
+
+    @classmethod
+    def batch_commit(cls, pp, polys):
+        if not polys:
+            return []
+        k = cls._chunks(pp)
+        n = len(polys) * (k or 1)
+        out = (lh_g1 * n)()
+        _check(cls._fn("batch_commit")(pp.ctx.h, *pp.head(), _ptr_array(polys), len(polys), polys[0].num_vars, out))
+        raw = C.string_at(out, 64 * n)
+        pts = [g1_from_bytes(raw[64 * i:64 * i + 64]) for i in range(n)]
+        return pts if k is None else [pts[i * k:(i + 1) * k] for i in range(len(polys))]
+
+    @classmethod
+    def commit(cls, pp, poly):
+        return cls.batch_commit(pp, [poly])[0]
+
+    @classmethod
+    def batch_commit_and_write(cls, pp, polys, transcript):
+        comms = cls.batch_commit(pp, polys)
+        for comm in [comms] if cls._chunks(pp) is None else comms:
+            transcript.write_commitments(comm)
+        return comms
+
+    @classmethod
+    def open(cls, pp, poly, point, transcript):
+        _check(cls._fn("open")(pp.ctx.h, *pp.head(), poly.ptr, poly.num_vars, _fr_array(point), transcript.p))
+
+    @classmethod
+    def batch_open(cls, pp, num_vars, polys, points, evals, transcript):
+        for p in points:
+            if len(p) != num_vars:
+                raise InvalidPcsParam("Invalid point (expect point to have %d variates but got %d)" % (num_vars, len(p)))
+        flat = [v for p in points for v in p]
+        _check(cls._fn("batch_open")(pp.ctx.h, *pp.head(), num_vars, _ptr_array(polys), len(polys), _fr_array(flat),
+                                     len(points), _evaluations(evals), len(evals), transcript.p))
+
+    @classmethod
+    def verify(cls, vp, comm, point, eval_, transcript):
+        _check(cls._fn("verify")(*vp.head(), _g1_array(cls._points(vp, [comm])), _fr_array(point), len(point),
+                                 _fr_array([eval_]), transcript.p))
+
+    @classmethod
+    def batch_verify(cls, vp, num_vars, comms, points, evals, transcript):
+        flat = [v for p in points for v in p]
+        _check(cls._fn("batch_verify")(*vp.head(), num_vars, _g1_array(cls._points(vp, comms)), len(comms), _fr_array(flat),
+                                       len(points), _evaluations(evals), len(evals), transcript.p))
+
+
 class MultilinearKzgParams:
+    suffix = ""  # of the lh_lasso_* / lh_hyperplonk_* entries over this scheme
+
     def __init__(self, ctx, handle, borrowed=False):
         self.ctx, self.h, self.borrowed = ctx, handle, borrowed
 
@@ -524,6 +593,9 @@ class MultilinearKzgParams:
         """The same SRS (device memory, owned by this object - keep it alive) for use through another ctx of the same
         device: a second proof in flight on its own stream (bench.py two_proofs_in_flight / sharded_two_in_flight)."""
         return MultilinearKzgParams(ctx, self.h, borrowed=True)
+
+    def head(self):
+        return (self.h,)
 
     @property
     def num_vars(self):
@@ -557,8 +629,9 @@ class MultilinearKzgParams:
             pass
 
 
-class MultilinearKzg:
+class MultilinearKzg(_PointPcs):
     """pcs/multilinear/kzg.rs:150-361 (prover side)."""
+    NAME = "mkzg"
 
     @staticmethod
     def setup(ctx, ss):
@@ -587,24 +660,9 @@ class MultilinearKzg:
         _check(pp.ctx.lib.lh_mkzg_commit(pp.ctx.h, pp.h, poly.ptr, poly.num_vars, C.byref(out)))
         return g1_from_bytes(bytes(out))
 
-    @staticmethod
-    def batch_commit(pp, polys):
-        if not polys:
-            return []
-        out = (lh_g1 * len(polys))()
-        _check(pp.ctx.lib.lh_mkzg_batch_commit(pp.ctx.h, pp.h, _ptr_array(polys), len(polys), polys[0].num_vars, out))
-        raw = C.string_at(out, 64 * len(polys))
-        return [g1_from_bytes(raw[64 * i:64 * i + 64]) for i in range(len(polys))]
-
     verify = staticmethod(lambda vp, comm, point, eval_, transcript: mkzg_verify(vp, comm, point, eval_, transcript))
     batch_verify = staticmethod(lambda vp, num_vars, comms, points, evals, transcript:
                                 mkzg_batch_verify(vp, num_vars, comms, points, evals, transcript))
-
-    @staticmethod
-    def batch_commit_and_write(pp, polys, transcript):
-        comms = MultilinearKzg.batch_commit(pp, polys)
-        transcript.write_commitments(comms)
-        return comms
 
     @staticmethod
     def open(pp, poly, point, transcript):
@@ -613,19 +671,10 @@ class MultilinearKzg:
                                        C.byref(out)))
         return fr_from_bytes(bytes(out))
 
-    @staticmethod
-    def batch_open(pp, num_vars, polys, points, evals, transcript):
-        evs = _evaluations(evals)
-        flat = [v for p in points for v in p]
-        for p in points:
-            if len(p) != num_vars:
-                raise InvalidPcsParam("Invalid point (expect point to have %d variates but got %d)" % (num_vars, len(p)))
-        _check(pp.ctx.lib.lh_mkzg_batch_open(pp.ctx.h, pp.h, num_vars, _ptr_array(polys), len(polys), _fr_array(flat),
-                                             len(points), evs, len(evals), transcript.p))
-
 
 class MultilinearKzgVerifierParams:
     """MultilinearKzgVerifierParams (kzg.rs:79-101): g1, g2, ss[i] = s_i * g2.  Host only."""
+    suffix = ""
 
     def __init__(self, handle):
         self.lib, self.h = _ffi.load(), handle
@@ -647,6 +696,9 @@ class MultilinearKzgVerifierParams:
         C.memmove(arr, b"".join(g2_to_bytes(p) for p in ss), 128 * len(ss))
         _check(_ffi.load().lh_mkzg_vp_new(C.byref(a), C.byref(b), arr, len(ss), C.byref(h)))
         return cls(h)
+
+    def head(self):
+        return (self.h,)
 
     @property
     def num_vars(self):
@@ -722,14 +774,7 @@ def sum_check_verify(prover, num_vars, degree, sum_, transcript):
 def lasso_verify(vp, table, num_vars, transcript):
     """Verifier of the Lasso argument (oracle/pyref/lasso.py:219-261).  A Keccak256Transcript must be fully consumed."""
     t = table.to_c()
-    if isinstance(vp, HyraxParam):
-        _check(vp.lib.lh_lasso_verify_hyrax(vp.params.h, vp.poly_size, vp.batch_size, C.byref(t), num_vars, transcript.p))
-    elif isinstance(vp, IpaParam):
-        _check(vp.lib.lh_lasso_verify_ipa(vp.params.h, vp.poly_size, C.byref(t), num_vars, transcript.p))
-    else:
-        fn = vp.lib.lh_lasso_verify_zeromorph if isinstance(vp, ZeromorphVerifierParam) else \
-            vp.lib.lh_lasso_verify_gemini if isinstance(vp, GeminiVerifierParam) else vp.lib.lh_lasso_verify
-        _check(fn(vp.h, C.byref(t), num_vars, transcript.p))
+    _check(getattr(vp.lib, "lh_lasso_verify" + vp.suffix)(*vp.head(), C.byref(t), num_vars, transcript.p))
     if isinstance(transcript, Keccak256Transcript) and transcript.remaining():
         raise InvalidSnark("trailing bytes in proof")
 
@@ -765,16 +810,24 @@ class UnivariateKzgParams:
 
 class ZeromorphProverParam:
     """ZeromorphKzgProverParam (zeromorph.rs:29-40) = the device SRS + the trim size"""
+    suffix = "_zeromorph"
 
     def __init__(self, params, poly_size):
         self.params, self.poly_size, self.ctx = params, poly_size, params.ctx
 
+    def head(self):
+        return (self.params.h, self.poly_size)
+
 
 class ZeromorphVerifierParam:
     """ZeromorphKzgVerifierParam (zeromorph.rs:42-65), host only"""
+    suffix = "_zeromorph"
 
     def __init__(self, handle):
         self.lib, self.h = _ffi.load(), handle
+
+    def head(self):
+        return (self.h,)
 
     @classmethod
     def setup(cls, s, param_size, poly_size):
@@ -811,8 +864,9 @@ class ZeromorphVerifierParam:
             pass
 
 
-class Zeromorph:
+class Zeromorph(_PointPcs):
     """Zeromorph<UnivariateKzg<Bn256>> (pcs/multilinear/zeromorph.rs:67-256)"""
+    NAME = "zeromorph"
 
     @staticmethod
     def setup(ctx, s, poly_size):
@@ -834,52 +888,6 @@ class Zeromorph:
             raise InvalidPcsParam("Too large poly_size to trim to (param supports poly_size up to %d but got %d)"
                                   % (params.size, poly_size))
         return ZeromorphProverParam(params, poly_size)
-
-    @staticmethod
-    def batch_commit(pp, polys):
-        if not polys:
-            return []
-        out = (lh_g1 * len(polys))()
-        _check(pp.ctx.lib.lh_zeromorph_batch_commit(pp.ctx.h, pp.params.h, pp.poly_size, _ptr_array(polys), len(polys),
-                                                    polys[0].num_vars, out))
-        raw = C.string_at(out, 64 * len(polys))
-        return [g1_from_bytes(raw[64 * i:64 * i + 64]) for i in range(len(polys))]
-
-    @staticmethod
-    def commit(pp, poly):
-        return Zeromorph.batch_commit(pp, [poly])[0]
-
-    @staticmethod
-    def batch_commit_and_write(pp, polys, transcript):
-        comms = Zeromorph.batch_commit(pp, polys)
-        transcript.write_commitments(comms)
-        return comms
-
-    @staticmethod
-    def open(pp, poly, point, transcript):
-        _check(pp.ctx.lib.lh_zeromorph_open(pp.ctx.h, pp.params.h, pp.poly_size, poly.ptr, poly.num_vars,
-                                            _fr_array(point), transcript.p))
-
-    @staticmethod
-    def batch_open(pp, num_vars, polys, points, evals, transcript):
-        for p in points:
-            if len(p) != num_vars:
-                raise InvalidPcsParam("Invalid point (expect point to have %d variates but got %d)" % (num_vars, len(p)))
-        flat = [v for p in points for v in p]
-        _check(pp.ctx.lib.lh_zeromorph_batch_open(pp.ctx.h, pp.params.h, pp.poly_size, num_vars, _ptr_array(polys),
-                                                  len(polys), _fr_array(flat), len(points), _evaluations(evals),
-                                                  len(evals), transcript.p))
-
-    @staticmethod
-    def verify(vp, comm, point, eval_, transcript):
-        _check(vp.lib.lh_zeromorph_verify(vp.h, _g1_array([comm]), _fr_array(point), len(point), _fr_array([eval_]),
-                                          transcript.p))
-
-    @staticmethod
-    def batch_verify(vp, num_vars, comms, points, evals, transcript):
-        flat = [v for p in points for v in p]
-        _check(vp.lib.lh_zeromorph_batch_verify(vp.h, num_vars, _g1_array(comms), len(comms), _fr_array(flat),
-                                                len(points), _evaluations(evals), len(evals), transcript.p))
 
 
 # ------------------------------------------------------------------ pcs::univariate::kzg on its own, pcs::multilinear::gemini over it
@@ -1012,14 +1020,23 @@ class UnivariateKzg:
 
 class GeminiProverParam(UnivariateKzgProverParam):
     """Gemini's ProverParam is UnivariateKzg's (gemini.rs:36-37); a type of its own so that provers can dispatch on it"""
+    suffix = "_gemini"
+
+    def head(self):
+        return (self.params.h, self.poly_size)
 
 
 class GeminiVerifierParam(UnivariateKzgVerifierParam):
     """Gemini's VerifierParam is UnivariateKzg's (gemini.rs:38)"""
+    suffix = "_gemini"
+
+    def head(self):
+        return (self.h,)
 
 
-class Gemini:
+class Gemini(_PointPcs):
     """Gemini<UnivariateKzg<Bn256>> (pcs/multilinear/gemini.rs:29-211): the method set of Zeromorph"""
+    NAME = "gemini"
 
     setup = staticmethod(lambda ctx, s, poly_size: Zeromorph.setup(ctx, s, poly_size))
     upload = staticmethod(lambda ctx, powers: Zeromorph.upload(ctx, powers))
@@ -1030,31 +1047,6 @@ class Gemini:
             raise InvalidPcsParam("Too large poly_size to trim to (param supports poly_size up to %d but got %d)"
                                   % (params.size, poly_size))
         return GeminiProverParam(params, poly_size)
-
-    @staticmethod
-    def batch_commit(pp, polys):
-        if not polys:
-            return []
-        out = (lh_g1 * len(polys))()
-        _check(pp.ctx.lib.lh_gemini_batch_commit(pp.ctx.h, pp.params.h, pp.poly_size, _ptr_array(polys), len(polys),
-                                                 polys[0].num_vars, out))
-        raw = C.string_at(out, 64 * len(polys))
-        return [g1_from_bytes(raw[64 * i:64 * i + 64]) for i in range(len(polys))]
-
-    @staticmethod
-    def commit(pp, poly):
-        return Gemini.batch_commit(pp, [poly])[0]
-
-    @staticmethod
-    def batch_commit_and_write(pp, polys, transcript):
-        comms = Gemini.batch_commit(pp, polys)
-        transcript.write_commitments(comms)
-        return comms
-
-    @staticmethod
-    def open(pp, poly, point, transcript):
-        _check(pp.ctx.lib.lh_gemini_open(pp.ctx.h, pp.params.h, pp.poly_size, poly.ptr, poly.num_vars, _fr_array(point),
-                                         transcript.p))
 
     @staticmethod
     def folds(ctx, poly, point):
@@ -1069,27 +1061,6 @@ class Gemini:
             res.append(flat[off:off + (1 << (n - i))])
             off += 1 << (n - i)
         return res
-
-    @staticmethod
-    def batch_open(pp, num_vars, polys, points, evals, transcript):
-        for p in points:
-            if len(p) != num_vars:
-                raise InvalidPcsParam("Invalid point (expect point to have %d variates but got %d)" % (num_vars, len(p)))
-        flat = [v for p in points for v in p]
-        _check(pp.ctx.lib.lh_gemini_batch_open(pp.ctx.h, pp.params.h, pp.poly_size, num_vars, _ptr_array(polys),
-                                               len(polys), _fr_array(flat), len(points), _evaluations(evals), len(evals),
-                                               transcript.p))
-
-    @staticmethod
-    def verify(vp, comm, point, eval_, transcript):
-        _check(vp.lib.lh_gemini_verify(vp.h, _g1_array([comm]), _fr_array(point), len(point), _fr_array([eval_]),
-                                       transcript.p))
-
-    @staticmethod
-    def batch_verify(vp, num_vars, comms, points, evals, transcript):
-        flat = [v for p in points for v in p]
-        _check(vp.lib.lh_gemini_batch_verify(vp.h, num_vars, _g1_array(comms), len(comms), _fr_array(flat), len(points),
-                                             _evaluations(evals), len(evals), transcript.p))
 
 
 # ------------------------------------------------------------------ pcs::multilinear::ipa over bn256::G1Affine
@@ -1124,12 +1095,18 @@ class IpaParams:
 class IpaParam:
     """a trimmed MultilinearIpaParams (ipa.rs:129-145): the params and the trim size; prover and verifier param at once"""
 
+    suffix = "_ipa"
+
     def __init__(self, params, poly_size):
         self.params, self.poly_size, self.ctx, self.lib = params, poly_size, params.ctx, params.lib
 
+    def head(self):
+        return (self.params.h, self.poly_size)
 
-class Ipa:
+
+class Ipa(_PointPcs):
     """MultilinearIpa<bn256::G1Affine> (pcs/multilinear/ipa.rs:23-337): transparent and additive; the method set of Gemini"""
+    NAME = "ipa"
 
     @staticmethod
     def setup(ctx, poly_size):
@@ -1148,51 +1125,6 @@ class Ipa:
         return IpaParam(params, poly_size)
 
     @staticmethod
-    def batch_commit(pp, polys):
-        if not polys:
-            return []
-        out = (lh_g1 * len(polys))()
-        _check(pp.lib.lh_ipa_batch_commit(pp.ctx.h, pp.params.h, pp.poly_size, _ptr_array(polys), len(polys),
-                                          polys[0].num_vars, out))
-        raw = C.string_at(out, 64 * len(polys))
-        return [g1_from_bytes(raw[64 * i:64 * i + 64]) for i in range(len(polys))]
-
-    @staticmethod
-    def commit(pp, poly):
-        return Ipa.batch_commit(pp, [poly])[0]
-
-    @staticmethod
-    def batch_commit_and_write(pp, polys, transcript):
-        comms = Ipa.batch_commit(pp, polys)
-        transcript.write_commitments(comms)
-        return comms
-
-    @staticmethod
-    def open(pp, poly, point, transcript):
-        _check(pp.lib.lh_ipa_open(pp.ctx.h, pp.params.h, pp.poly_size, poly.ptr, poly.num_vars, _fr_array(point),
-                                  transcript.p))
-
-    @staticmethod
-    def batch_open(pp, num_vars, polys, points, evals, transcript):
-        for p in points:
-            if len(p) != num_vars:
-                raise InvalidPcsParam("Invalid point (expect point to have %d variates but got %d)" % (num_vars, len(p)))
-        flat = [v for p in points for v in p]
-        _check(pp.lib.lh_ipa_batch_open(pp.ctx.h, pp.params.h, pp.poly_size, num_vars, _ptr_array(polys), len(polys),
-                                        _fr_array(flat), len(points), _evaluations(evals), len(evals), transcript.p))
-
-    @staticmethod
-    def verify(vp, comm, point, eval_, transcript):
-        _check(vp.lib.lh_ipa_verify(vp.params.h, vp.poly_size, _g1_array([comm]), _fr_array(point), len(point),
-                                    _fr_array([eval_]), transcript.p))
-
-    @staticmethod
-    def batch_verify(vp, num_vars, comms, points, evals, transcript):
-        flat = [v for p in points for v in p]
-        _check(vp.lib.lh_ipa_batch_verify(vp.params.h, vp.poly_size, num_vars, _g1_array(comms), len(comms),
-                                          _fr_array(flat), len(points), _evaluations(evals), len(evals), transcript.p))
-
-    @staticmethod
     def g1_axpy(ctx, a, b, s):
         """the base fold of a round as a primitive: [a[j] + s b[j]] for lists of affine points (None = identity)"""
         n = len(a)
@@ -1207,14 +1139,20 @@ class HyraxParam:
     """a trimmed MultilinearHyraxParams (hyrax.rs:26-62): the inner IPA params and the trim arguments; prover and verifier
     param at once"""
 
+    suffix = "_hyrax"
+
     def __init__(self, params, poly_size, batch_size):
         self.params, self.poly_size, self.batch_size, self.ctx, self.lib = params, poly_size, batch_size, params.ctx, params.lib
         self.num_vars, self.batch_num_vars, self.row_num_vars = Hyrax.dims(poly_size, batch_size)
         self.num_chunks = 1 << (self.num_vars - self.row_num_vars)
 
+    def head(self):
+        return (self.params.h, self.poly_size, self.batch_size)
 
-class Hyrax:
+
+class Hyrax(_PointPcs):
     """MultilinearHyrax<bn256::G1Affine> (pcs/multilinear/hyrax.rs:23-321); a commitment is a list of num_chunks points"""
+    NAME = "hyrax"
 
     @staticmethod
     def dims(poly_size, batch_size):
@@ -1236,18 +1174,6 @@ class Hyrax:
         return HyraxParam(params, poly_size, batch_size)
 
     @staticmethod
-    def batch_commit(pp, polys):
-        if not polys:
-            return []
-        k = pp.num_chunks
-        out = (lh_g1 * (len(polys) * k))()
-        _check(pp.lib.lh_hyrax_batch_commit(pp.ctx.h, pp.params.h, pp.poly_size, pp.batch_size, _ptr_array(polys), len(polys),
-                                            polys[0].num_vars, out))
-        raw = C.string_at(out, 64 * len(polys) * k)
-        pts = [g1_from_bytes(raw[64 * i:64 * i + 64]) for i in range(len(polys) * k)]
-        return [pts[i * k:(i + 1) * k] for i in range(len(polys))]
-
-    @staticmethod
     def rows_msm(ctx, scalars_buf, n, row_len, bases_buf, u32=False, bits=0):
         """the row commitments as a primitive: [sum_c s[r row_len + c] bases[c]] for the ceil(n / row_len) rows of a device
         array of n scalars (Fr, or u32 values below 2^bits), against row_len device points (None = identity)"""
@@ -1259,47 +1185,17 @@ class Hyrax:
         raw = C.string_at(out, 64 * rows)
         return [g1_from_bytes(raw[64 * i:64 * i + 64]) for i in range(rows)]
 
-    @staticmethod
-    def commit(pp, poly):
-        return Hyrax.batch_commit(pp, [poly])[0]
-
-    @staticmethod
-    def batch_commit_and_write(pp, polys, transcript):
-        comms = Hyrax.batch_commit(pp, polys)
-        for comm in comms:
-            transcript.write_commitments(comm)
-        return comms
-
-    @staticmethod
-    def open(pp, poly, point, transcript):
-        _check(pp.lib.lh_hyrax_open(pp.ctx.h, pp.params.h, pp.poly_size, pp.batch_size, poly.ptr, poly.num_vars,
-                                    _fr_array(point), transcript.p))
-
-    @staticmethod
-    def batch_open(pp, num_vars, polys, points, evals, transcript):
-        for p in points:
-            if len(p) != num_vars:
-                raise InvalidPcsParam("Invalid point (expect point to have %d variates but got %d)" % (num_vars, len(p)))
-        flat = [v for p in points for v in p]
-        _check(pp.lib.lh_hyrax_batch_open(pp.ctx.h, pp.params.h, pp.poly_size, pp.batch_size, num_vars, _ptr_array(polys),
-                                          len(polys), _fr_array(flat), len(points), _evaluations(evals), len(evals),
-                                          transcript.p))
-
-    @staticmethod
-    def verify(vp, comm, point, eval_, transcript):
+    @classmethod
+    def verify(cls, vp, comm, point, eval_, transcript):
         if len(comm) != vp.num_chunks:
             raise ArgumentError("expected a commitment of %d points" % vp.num_chunks)  # assert_eq! hyrax.rs:295
-        _check(vp.lib.lh_hyrax_verify(vp.params.h, vp.poly_size, vp.batch_size, _g1_array(comm), _fr_array(point), len(point),
-                                      _fr_array([eval_]), transcript.p))
+        super().verify(vp, comm, point, eval_, transcript)
 
-    @staticmethod
-    def batch_verify(vp, num_vars, comms, points, evals, transcript):
+    @classmethod
+    def batch_verify(cls, vp, num_vars, comms, points, evals, transcript):
         if any(len(cm) != vp.num_chunks for cm in comms):
             raise ArgumentError("expected commitments of %d points" % vp.num_chunks)
-        flat = [v for p in points for v in p]
-        _check(vp.lib.lh_hyrax_batch_verify(vp.params.h, vp.poly_size, vp.batch_size, num_vars,
-                                            _g1_array([p for cm in comms for p in cm]), len(comms), _fr_array(flat), len(points),
-                                            _evaluations(evals), len(evals), transcript.p))
+        super().batch_verify(vp, num_vars, comms, points, evals, transcript)
 
 
 # ------------------------------------------------------------------ pcs::multilinear::brakedown
@@ -1513,16 +1409,8 @@ def lasso_prove(pp, table, num_vars, dims, transcript):
             or len(table.g_terms) > _ffi.LH_LASSO_MAX_TERMS:
         raise ArgumentError("table too large")
     t = table.to_c()
-    if isinstance(pp, HyraxParam):
-        _check(pp.ctx.lib.lh_lasso_prove_hyrax(pp.ctx.h, pp.params.h, pp.poly_size, pp.batch_size, C.byref(t), num_vars,
-                                               _ptr_array(dims), transcript.p))
-        return
-    if isinstance(pp, (ZeromorphProverParam, GeminiProverParam, IpaParam)):
-        fn = pp.ctx.lib.lh_lasso_prove_ipa if isinstance(pp, IpaParam) else \
-            pp.ctx.lib.lh_lasso_prove_gemini if isinstance(pp, GeminiProverParam) else pp.ctx.lib.lh_lasso_prove_zeromorph
-        _check(fn(pp.ctx.h, pp.params.h, pp.poly_size, C.byref(t), num_vars, _ptr_array(dims), transcript.p))
-        return
-    _check(pp.ctx.lib.lh_lasso_prove(pp.ctx.h, pp.h, C.byref(t), num_vars, _ptr_array(dims), transcript.p))
+    _check(getattr(pp.ctx.lib, "lh_lasso_prove" + pp.suffix)(pp.ctx.h, *pp.head(), C.byref(t), num_vars, _ptr_array(dims),
+                                                             transcript.p))
 
 
 def attach_comm(ctx, rank, size, all_gather, shard_bit):

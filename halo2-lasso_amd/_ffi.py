@@ -152,7 +152,8 @@ class lh_g2(C.Structure):
 
 _P = C.c_void_p
 _SZ = C.c_size_t
-# name -> (restype, argtypes); every symbol include/lasso_hip.h declares
+# name -> (restype, argtypes); every symbol include/lasso_hip.h declares (the Lasso / HyperPlonk entries of the point
+# commitment schemes are added below the literal rows)
 SIGNATURES = {
     "lh_last_error": (C.c_char_p, []),
     "lh_version": (C.c_char_p, []),
@@ -204,7 +205,6 @@ SIGNATURES = {
     "lh_mkzg_open": (C.c_int, [_P, _P, _P, _SZ, C.POINTER(lh_fr), C.POINTER(lh_transcript), C.POINTER(lh_fr)]),
     "lh_mkzg_batch_open": (C.c_int, [_P, _P, _SZ, C.POINTER(_P), _SZ, C.POINTER(lh_fr), _SZ,
                                      C.POINTER(lh_evaluation), _SZ, C.POINTER(lh_transcript)]),
-    "lh_lasso_prove": (C.c_int, [_P, _P, C.POINTER(lh_lasso_table), _SZ, C.POINTER(_P), C.POINTER(lh_transcript)]),
     "lh_lasso_last_timing": (C.c_int, [_P, C.POINTER(C.c_double)]),
     "lh_ctx_set_option": (C.c_int, [_P, C.c_char_p, C.c_int64]),
     "lh_ctx_get_option": (C.c_int, [_P, C.c_char_p, C.POINTER(C.c_int64)]),
@@ -220,16 +220,9 @@ SIGNATURES = {
     "lh_ctx_host_cpus": (C.c_int, [_P, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t]),
     "lh_lasso_prove_sharded": (C.c_int, [_P, _P, C.POINTER(lh_lasso_table), _SZ, C.POINTER(_P),
                                          C.POINTER(lh_transcript)]),
-    "lh_hyperplonk_prove": (C.c_int, [_P, _P, C.POINTER(lh_hp_param), C.POINTER(C.POINTER(lh_fr)), C.POINTER(_P),
-                                      C.POINTER(lh_transcript)]),
     "lh_shard_extract": (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _SZ, _SZ, _P]),
     "lh_hyperplonk_prove_sharded": (C.c_int, [_P, _P, C.POINTER(lh_hp_param), C.POINTER(C.POINTER(lh_fr)), C.POINTER(_P),
                                               C.POINTER(lh_transcript)]),
-    "lh_hyperplonk_prove_phases": (C.c_int, [_P, _P, C.POINTER(lh_hp_param), _SZ, C.POINTER(_SZ), C.POINTER(_SZ),
-                                             C.POINTER(C.POINTER(lh_fr)), C.POINTER(lh_hp_circuit),
-                                             C.POINTER(lh_transcript)]),
-    "lh_hyperplonk_verify_phases": (C.c_int, [_P, C.POINTER(lh_hp_vparam), _SZ, C.POINTER(_SZ), C.POINTER(_SZ),
-                                              C.POINTER(C.POINTER(lh_fr)), C.POINTER(lh_transcript)]),
     "lh_keccak_transcript_from_proof": (C.c_int, [C.c_char_p, _SZ, C.POINTER(C.POINTER(lh_transcript))]),
     "lh_keccak_transcript_remaining": (C.c_int, [C.POINTER(lh_transcript), C.POINTER(_SZ)]),
     "lh_mkzg_vp_setup": (C.c_int, [C.POINTER(lh_fr), _SZ, C.POINTER(_P)]),
@@ -244,9 +237,6 @@ SIGNATURES = {
                                        C.POINTER(lh_evaluation), _SZ, C.POINTER(lh_transcript)]),
     "lh_sumcheck_verify": (C.c_int, [C.c_int, _SZ, _SZ, C.POINTER(lh_fr), C.POINTER(lh_transcript),
                                      C.POINTER(lh_fr), C.POINTER(lh_fr)]),
-    "lh_lasso_verify": (C.c_int, [_P, C.POINTER(lh_lasso_table), _SZ, C.POINTER(lh_transcript)]),
-    "lh_hyperplonk_verify": (C.c_int, [_P, C.POINTER(lh_hp_vparam), C.POINTER(C.POINTER(lh_fr)),
-                                       C.POINTER(lh_transcript)]),
     "lh_ukzg_setup": (C.c_int, [_P, C.POINTER(lh_fr), _SZ, C.POINTER(_P)]),
     "lh_usrs_upload": (C.c_int, [_P, C.c_char_p, _SZ, C.POINTER(_P)]),
     "lh_usrs_download": (C.c_int, [_P, _P, C.c_char_p]),
@@ -265,18 +255,6 @@ SIGNATURES = {
                                       C.POINTER(lh_transcript)]),
     "lh_zeromorph_batch_verify": (C.c_int, [_P, _SZ, C.POINTER(lh_g1), _SZ, C.POINTER(lh_fr), _SZ,
                                             C.POINTER(lh_evaluation), _SZ, C.POINTER(lh_transcript)]),
-    "lh_lasso_prove_zeromorph": (C.c_int, [_P, _P, _SZ, C.POINTER(lh_lasso_table), _SZ, C.POINTER(_P),
-                                           C.POINTER(lh_transcript)]),
-    "lh_lasso_verify_zeromorph": (C.c_int, [_P, C.POINTER(lh_lasso_table), _SZ, C.POINTER(lh_transcript)]),
-    "lh_hyperplonk_prove_zeromorph": (C.c_int, [_P, _P, _SZ, C.POINTER(lh_hp_param), C.POINTER(C.POINTER(lh_fr)),
-                                                C.POINTER(_P), C.POINTER(lh_transcript)]),
-    "lh_hyperplonk_verify_zeromorph": (C.c_int, [_P, C.POINTER(lh_hp_vparam), C.POINTER(C.POINTER(lh_fr)),
-                                                 C.POINTER(lh_transcript)]),
-    "lh_hyperplonk_prove_phases_zeromorph": (C.c_int, [_P, _P, _SZ, C.POINTER(lh_hp_param), _SZ, C.POINTER(_SZ),
-                                                       C.POINTER(_SZ), C.POINTER(C.POINTER(lh_fr)),
-                                                       C.POINTER(lh_hp_circuit), C.POINTER(lh_transcript)]),
-    "lh_hyperplonk_verify_phases_zeromorph": (C.c_int, [_P, C.POINTER(lh_hp_vparam), _SZ, C.POINTER(_SZ), C.POINTER(_SZ),
-                                                        C.POINTER(C.POINTER(lh_fr)), C.POINTER(lh_transcript)]),
     "lh_ukzg_batch_commit": (C.c_int, [_P, _P, _SZ, C.POINTER(_P), C.POINTER(_SZ), _SZ, C.POINTER(lh_g1)]),
     "lh_ukzg_open": (C.c_int, [_P, _P, _SZ, _P, _SZ, C.POINTER(lh_fr), C.POINTER(lh_transcript)]),
     "lh_ukzg_batch_open": (C.c_int, [_P, _P, _SZ, C.POINTER(_P), C.POINTER(_SZ), _SZ, C.POINTER(lh_fr), _SZ,
@@ -297,18 +275,6 @@ SIGNATURES = {
                                    C.POINTER(lh_transcript)]),
     "lh_gemini_batch_verify": (C.c_int, [_P, _SZ, C.POINTER(lh_g1), _SZ, C.POINTER(lh_fr), _SZ,
                                          C.POINTER(lh_evaluation), _SZ, C.POINTER(lh_transcript)]),
-    "lh_lasso_prove_gemini": (C.c_int, [_P, _P, _SZ, C.POINTER(lh_lasso_table), _SZ, C.POINTER(_P),
-                                        C.POINTER(lh_transcript)]),
-    "lh_lasso_verify_gemini": (C.c_int, [_P, C.POINTER(lh_lasso_table), _SZ, C.POINTER(lh_transcript)]),
-    "lh_hyperplonk_prove_gemini": (C.c_int, [_P, _P, _SZ, C.POINTER(lh_hp_param), C.POINTER(C.POINTER(lh_fr)),
-                                             C.POINTER(_P), C.POINTER(lh_transcript)]),
-    "lh_hyperplonk_verify_gemini": (C.c_int, [_P, C.POINTER(lh_hp_vparam), C.POINTER(C.POINTER(lh_fr)),
-                                              C.POINTER(lh_transcript)]),
-    "lh_hyperplonk_prove_phases_gemini": (C.c_int, [_P, _P, _SZ, C.POINTER(lh_hp_param), _SZ, C.POINTER(_SZ),
-                                                    C.POINTER(_SZ), C.POINTER(C.POINTER(lh_fr)),
-                                                    C.POINTER(lh_hp_circuit), C.POINTER(lh_transcript)]),
-    "lh_hyperplonk_verify_phases_gemini": (C.c_int, [_P, C.POINTER(lh_hp_vparam), _SZ, C.POINTER(_SZ), C.POINTER(_SZ),
-                                                     C.POINTER(C.POINTER(lh_fr)), C.POINTER(lh_transcript)]),
     "lh_ipa_setup": (C.c_int, [_P, _SZ, C.POINTER(_P)]),
     "lh_ipa_param_free": (None, [_P, _P]),
     "lh_ipa_param_size": (_SZ, [_P]),
@@ -322,9 +288,6 @@ SIGNATURES = {
     "lh_ipa_batch_verify": (C.c_int, [_P, _SZ, _SZ, C.POINTER(lh_g1), _SZ, C.POINTER(lh_fr), _SZ,
                                       C.POINTER(lh_evaluation), _SZ, C.POINTER(lh_transcript)]),
     "lh_g1_axpy": (C.c_int, [_P, _P, _P, _SZ, C.POINTER(lh_fr), _P]),
-    "lh_lasso_prove_hyrax": (C.c_int, [_P, _P, _SZ, _SZ, C.POINTER(lh_lasso_table), _SZ, C.POINTER(_P),
-                                       C.POINTER(lh_transcript)]),
-    "lh_lasso_verify_hyrax": (C.c_int, [_P, _SZ, _SZ, C.POINTER(lh_lasso_table), _SZ, C.POINTER(lh_transcript)]),
     "lh_g1_rows_msm": (C.c_int, [_P, _P, C.c_int, C.c_uint32, _SZ, _SZ, _P, C.POINTER(lh_g1)]),
     "lh_hyrax_setup": (C.c_int, [_P, _SZ, _SZ, C.POINTER(_P)]),
     "lh_hyrax_dims": (C.c_int, [_SZ, _SZ, C.POINTER(_SZ), C.POINTER(_SZ), C.POINTER(_SZ)]),
@@ -337,27 +300,6 @@ SIGNATURES = {
                                   C.POINTER(lh_transcript)]),
     "lh_hyrax_batch_verify": (C.c_int, [_P, _SZ, _SZ, _SZ, C.POINTER(lh_g1), _SZ, C.POINTER(lh_fr), _SZ,
                                         C.POINTER(lh_evaluation), _SZ, C.POINTER(lh_transcript)]),
-    "lh_lasso_prove_ipa": (C.c_int, [_P, _P, _SZ, C.POINTER(lh_lasso_table), _SZ, C.POINTER(_P),
-                                     C.POINTER(lh_transcript)]),
-    "lh_lasso_verify_ipa": (C.c_int, [_P, _SZ, C.POINTER(lh_lasso_table), _SZ, C.POINTER(lh_transcript)]),
-    "lh_hyperplonk_prove_ipa": (C.c_int, [_P, _P, _SZ, C.POINTER(lh_hp_param), C.POINTER(C.POINTER(lh_fr)),
-                                          C.POINTER(_P), C.POINTER(lh_transcript)]),
-    "lh_hyperplonk_prove_hyrax": (C.c_int, [_P, _P, _SZ, _SZ, C.POINTER(lh_hp_param), C.POINTER(C.POINTER(lh_fr)),
-                                          C.POINTER(_P), C.POINTER(lh_transcript)]),
-    "lh_hyperplonk_verify_ipa": (C.c_int, [_P, _SZ, C.POINTER(lh_hp_vparam), C.POINTER(C.POINTER(lh_fr)),
-                                           C.POINTER(lh_transcript)]),
-    "lh_hyperplonk_verify_hyrax": (C.c_int, [_P, _SZ, _SZ, C.POINTER(lh_hp_vparam), C.POINTER(C.POINTER(lh_fr)),
-                                           C.POINTER(lh_transcript)]),
-    "lh_hyperplonk_prove_phases_ipa": (C.c_int, [_P, _P, _SZ, C.POINTER(lh_hp_param), _SZ, C.POINTER(_SZ),
-                                                 C.POINTER(_SZ), C.POINTER(C.POINTER(lh_fr)),
-                                                 C.POINTER(lh_hp_circuit), C.POINTER(lh_transcript)]),
-    "lh_hyperplonk_prove_phases_hyrax": (C.c_int, [_P, _P, _SZ, _SZ, C.POINTER(lh_hp_param), _SZ, C.POINTER(_SZ),
-                                                 C.POINTER(_SZ), C.POINTER(C.POINTER(lh_fr)),
-                                                 C.POINTER(lh_hp_circuit), C.POINTER(lh_transcript)]),
-    "lh_hyperplonk_verify_phases_ipa": (C.c_int, [_P, _SZ, C.POINTER(lh_hp_vparam), _SZ, C.POINTER(_SZ), C.POINTER(_SZ),
-                                                  C.POINTER(C.POINTER(lh_fr)), C.POINTER(lh_transcript)]),
-    "lh_hyperplonk_verify_phases_hyrax": (C.c_int, [_P, _SZ, _SZ, C.POINTER(lh_hp_vparam), _SZ, C.POINTER(_SZ), C.POINTER(_SZ),
-                                                  C.POINTER(C.POINTER(lh_fr)), C.POINTER(lh_transcript)]),
     "lh_debug_jit_source": (C.c_int, [C.POINTER(C.c_uint32), _SZ, C.c_uint32, C.c_uint32, C.c_int, C.c_char_p, _SZ,
                                       C.POINTER(_SZ)]),
     "lh_debug_sort_pairs": (C.c_int, [_P, C.c_int, C.POINTER(lh_debug_sort_slab), _SZ]),
@@ -407,6 +349,31 @@ SIGNATURES = {
     "lh_profile_enable": (C.c_int, [_P, C.c_int]),
     "lh_profile_read": (C.c_int, [_P, C.POINTER(lh_prof_rec), _SZ, C.POINTER(_SZ)]),
 }
+
+# Lasso and HyperPlonk exist once per point commitment scheme: lh_<kind><suffix>([ctx,] <the scheme's head>, <the kind's tail>)
+_PCS_HEADS = {  # suffix -> (prover param, verifier param)
+    "": ([_P], [_P]),
+    "_zeromorph": ([_P, _SZ], [_P]),
+    "_gemini": ([_P, _SZ], [_P]),
+    "_ipa": ([_P, _SZ], [_P, _SZ]),
+    "_hyrax": ([_P, _SZ, _SZ], [_P, _SZ, _SZ]),
+}
+_T, _INSTANCES, _PHASES = C.POINTER(lh_transcript), C.POINTER(C.POINTER(lh_fr)), [_SZ, C.POINTER(_SZ), C.POINTER(_SZ)]
+_PROVE_TAILS = {
+    "lh_lasso_prove": [C.POINTER(lh_lasso_table), _SZ, C.POINTER(_P), _T],
+    "lh_hyperplonk_prove": [C.POINTER(lh_hp_param), _INSTANCES, C.POINTER(_P), _T],
+    "lh_hyperplonk_prove_phases": [C.POINTER(lh_hp_param)] + _PHASES + [_INSTANCES, C.POINTER(lh_hp_circuit), _T],
+}
+_VERIFY_TAILS = {
+    "lh_lasso_verify": [C.POINTER(lh_lasso_table), _SZ, _T],
+    "lh_hyperplonk_verify": [C.POINTER(lh_hp_vparam), _INSTANCES, _T],
+    "lh_hyperplonk_verify_phases": [C.POINTER(lh_hp_vparam)] + _PHASES + [_INSTANCES, _T],
+}
+for _suffix, (_prover, _verifier) in _PCS_HEADS.items():
+    for _kind, _tail in _PROVE_TAILS.items():
+        SIGNATURES[_kind + _suffix] = (C.c_int, [_P] + _prover + _tail)
+    for _kind, _tail in _VERIFY_TAILS.items():
+        SIGNATURES[_kind + _suffix] = (C.c_int, _verifier + _tail)
 
 _lib = None
 

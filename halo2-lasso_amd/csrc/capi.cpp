@@ -71,6 +71,119 @@ struct DeviceGuard {
   NEED(ctx);          \
   DeviceGuard device_guard_((ctx)->c.device)
 
+// ---------------------------------------------------------------- Lasso and HyperPlonk over any PCS: one body per kind of entry
+// The exported functions (one per scheme, below) check their ctx and their own param handle and hand over the scheme's part
+// as a callable that builds its Pcs / PcsVerifier.  It runs after the problem's pointers and the transcript are checked:
+// which error a call with several defects reports is part of the boundary.  Hyrax's callables begin with its geometry check.
+
+// the phase loop's arguments as the prover wants them (hyperplonk.rs:185-205); a single-phase circuit: hp_single_phase
+static HpPhases hp_phases_of(const lh_hp_param* pp, size_t num_phases, const size_t* num_witness_polys,
+                             const size_t* num_challenges, const lh_hp_circuit* circuit) {
+  LH_REQUIRE(circuit->synthesize, LH_ERR_ARG, "circuit: synthesize callback missing");
+  LH_REQUIRE(num_phases == 0 || (num_witness_polys && num_challenges), LH_ERR_ARG, "null argument: phases");
+  HpPhases ph;
+  ph.num_witness_polys.assign(num_witness_polys, num_witness_polys + num_phases);
+  ph.num_challenges.assign(num_challenges, num_challenges + num_phases);
+  size_t tw = 0, tc = 0;
+  for (size_t r = 0; r < num_phases; r++) tw += num_witness_polys[r], tc += num_challenges[r];
+  LH_REQUIRE(tw == pp->num_witness_polys && tc == pp->num_challenges, LH_ERR_ARG,
+             "hyperplonk: phases do not add up to num_witness_polys / num_challenges");
+  const std::vector<size_t> per_phase = ph.num_witness_polys;
+  ph.synthesize = [circuit, per_phase](size_t round, const std::vector<HFr>& challenges) {
+    std::vector<const void*> out(per_phase[round], nullptr);
+    int rc = circuit->synthesize(circuit->user, round, (const lh_fr*)challenges.data(), challenges.size(), out.data(),
+                                 out.size());
+    if (rc != LH_OK) throw lh::Error(rc < 0 ? rc : LH_ERR_INVALID_SNARK, "circuit synthesize callback failed");
+    std::vector<const Fr*> w;
+    for (const void* p : out) {
+      LH_REQUIRE(p != nullptr, LH_ERR_ARG, "circuit synthesize left a witness poly unset");
+      w.push_back((const Fr*)p);
+    }
+    return w;
+  };
+  return ph;
+}
+// the per-phase counts as the verifier wants them
+struct VerifierPhases {
+  std::vector<size_t> num_witness_polys, num_challenges;
+};
+static VerifierPhases verifier_phases_of(size_t num_phases, const size_t* num_witness_polys, const size_t* num_challenges) {
+  LH_REQUIRE(num_phases == 0 || (num_witness_polys && num_challenges), LH_ERR_ARG, "null argument: phases");
+  return {std::vector<size_t>(num_witness_polys, num_witness_polys + num_phases),
+          std::vector<size_t>(num_challenges, num_challenges + num_phases)};
+}
+// the communicator checks of the sharded entries; the proof is sharded while the returned object lives
+static std::unique_ptr<ShardActive> shard_activate(Ctx& c, const char* entry) {
+  LH_REQUIRE(c.has_comm, LH_ERR_ARG, std::string(entry) + ": no communicator attached");
+  const size_t R = (size_t)c.comm.size;
+  LH_REQUIRE(R >= 1 && (R & (R - 1)) == 0, LH_ERR_ARG, "sharded prove: the number of ranks must be a power of two");
+  return std::unique_ptr<ShardActive>(new ShardActive(c));
+}
+
+template <class MakePcs>
+static void lasso_prove_entry(Ctx& c, const lh_lasso_table* table, size_t num_vars, const uint32_t* const* d_dims,
+                              lh_transcript* t, const MakePcs& make_pcs) {
+  NEED(table);
+  NEED(d_dims);
+  Transcript tr(t);
+  lasso_prove(c, make_pcs(), *table, num_vars, d_dims, tr);
+}
+template <class MakeVerifier>
+static void lasso_verify_entry(const lh_lasso_table* table, size_t num_vars, lh_transcript* t, const MakeVerifier& make_verifier) {
+  NEED(table);
+  Transcript tr(t);
+  lasso_verify(make_verifier(), *table, num_vars, tr);
+}
+template <class MakePcs>
+static void hyperplonk_prove_entry(Ctx& c, const lh_hp_param* pp, const lh_fr* const* instances,
+                                   const lh_fr* const* d_witness_polys, lh_transcript* t, const MakePcs& make_pcs) {
+  NEED(pp);
+  NEED_N(d_witness_polys, pp->num_witness_polys);
+  Transcript tr(t);
+  hyperplonk_prove(c, make_pcs(), *pp, (const HFr* const*)instances, (const Fr* const*)d_witness_polys, tr);
+}
+// `geometry` (Hyrax): its check of the circuit's size comes ahead of the phases' checks, its Pcs behind them
+template <class MakePcs>
+static void hyperplonk_prove_phases_entry(Ctx& c, const lh_hp_param* pp, size_t num_phases, const size_t* num_witness_polys,
+                                          const size_t* num_challenges, const lh_fr* const* instances,
+                                          const lh_hp_circuit* circuit, lh_transcript* t, const MakePcs& make_pcs,
+                                          const std::function<void()>& geometry = nullptr) {
+  NEED(pp);
+  NEED(circuit);
+  Transcript tr(t);
+  if (geometry) geometry();
+  const HpPhases ph = hp_phases_of(pp, num_phases, num_witness_polys, num_challenges, circuit);
+  hyperplonk_prove_phases(c, make_pcs(), *pp, ph, (const HFr* const*)instances, tr);
+}
+template <class MakeVerifier>
+static void hyperplonk_verify_entry(const lh_hp_vparam* hvp, const lh_fr* const* instances, lh_transcript* t,
+                                    const MakeVerifier& make_verifier) {
+  NEED(hvp);
+  Transcript tr(t);
+  hyperplonk_verify(make_verifier(), *hvp, (const HFr* const*)instances, tr);
+}
+template <class MakeVerifier>
+static void hyperplonk_verify_phases_entry(const lh_hp_vparam* hvp, size_t num_phases, const size_t* num_witness_polys,
+                                           const size_t* num_challenges, const lh_fr* const* instances, lh_transcript* t,
+                                           const MakeVerifier& make_verifier) {
+  NEED(hvp);
+  const VerifierPhases ph = verifier_phases_of(num_phases, num_witness_polys, num_challenges);
+  Transcript tr(t);
+  hyperplonk_verify_phases(make_verifier(), *hvp, ph.num_witness_polys, ph.num_challenges, (const HFr* const*)instances, tr);
+}
+// Hyrax commits only tables of exactly the param's num_vars (hyrax.rs groups rows by the param's count): Lasso's tables ...
+static void hyrax_lasso_vars(const IpaParams& p, size_t poly_size, size_t batch_size, const lh_lasso_table& tb, size_t num_vars) {
+  const HyraxDims d = hyrax_trim(p, poly_size, batch_size);
+  LH_REQUIRE(std::max<size_t>(num_vars, tb.chunk_bits) == d.num_vars, LH_ERR_ARG,
+             "lasso over hyrax: max(num_vars, chunk_bits) must equal log2(poly_size) (Hyrax commits only tables of the param's size)");
+}
+// ... and the circuit's k
+static void hyrax_hyperplonk_vars(const IpaParams& p, size_t poly_size, size_t batch_size, size_t num_vars) {
+  const HyraxDims d = hyrax_trim(p, poly_size, batch_size);
+  LH_REQUIRE(num_vars == d.num_vars, LH_ERR_ARG,
+             "hyperplonk over hyrax: the circuit's num_vars must equal log2(poly_size) (Hyrax commits only tables of the param's size)");
+}
+
 extern "C" {
 
 const char* lh_last_error(void) { return lh::get_last_error(); }
@@ -559,10 +672,7 @@ lh_status lh_lasso_prove(lh_ctx* ctx, const lh_srs* srs, const lh_lasso_table* t
                          const uint32_t* const* d_dims, lh_transcript* t) {
   LH_TRY NEED_CTX(ctx);
   NEED(srs);
-  NEED(table);
-  NEED(d_dims);
-  Transcript tr(t);
-  lasso_prove(ctx->c, mkzg_pcs(ctx->c, srs->s), *table, num_vars, d_dims, tr);
+  lasso_prove_entry(ctx->c, table, num_vars, d_dims, t, [&] { return mkzg_pcs(ctx->c, srs->s); });
   LH_CATCH
 }
 lh_status lh_lasso_last_timing(lh_ctx* ctx, double* out_ms) {
@@ -695,43 +805,18 @@ lh_status lh_ctx_host_cpus(lh_ctx* ctx, char* bus_id, size_t bus_id_cap, char* c
   }
   LH_CATCH
 }
+// ONE proof over the 2^rho ranks of the ctx's communicator: the same prover, with every table a shard
+// (dev.hpp Shard).  Same transcript, same proof bytes on every rank as lasso_prove on one GPU.
 lh_status lh_lasso_prove_sharded(lh_ctx* ctx, const lh_srs* srs, const lh_lasso_table* table, size_t num_vars,
                                  const uint32_t* const* d_dims, lh_transcript* t) {
   LH_TRY NEED_CTX(ctx);
   NEED(srs);
-  NEED(table);
-  NEED(d_dims);
-  Transcript tr(t);
-  lasso_prove_sharded(ctx->c, srs->s, *table, num_vars, d_dims, tr);
+  std::unique_ptr<ShardActive> active;
+  lasso_prove_entry(ctx->c, table, num_vars, d_dims, t, [&] {
+    active = shard_activate(ctx->c, "lasso_prove_sharded");
+    return mkzg_pcs(ctx->c, srs->s);
+  });
   LH_CATCH
-}
-
-// the phase loop's arguments as the prover wants them (hyperplonk.rs:185-205): shared by both PCS entry points
-static HpPhases hp_phases_of(const lh_hp_param* pp, size_t num_phases, const size_t* num_witness_polys,
-                             const size_t* num_challenges, const lh_hp_circuit* circuit) {
-  LH_REQUIRE(circuit->synthesize, LH_ERR_ARG, "circuit: synthesize callback missing");
-  LH_REQUIRE(num_phases == 0 || (num_witness_polys && num_challenges), LH_ERR_ARG, "null argument: phases");
-  HpPhases ph;
-  ph.num_witness_polys.assign(num_witness_polys, num_witness_polys + num_phases);
-  ph.num_challenges.assign(num_challenges, num_challenges + num_phases);
-  size_t tw = 0, tc = 0;
-  for (size_t r = 0; r < num_phases; r++) tw += num_witness_polys[r], tc += num_challenges[r];
-  LH_REQUIRE(tw == pp->num_witness_polys && tc == pp->num_challenges, LH_ERR_ARG,
-             "hyperplonk: phases do not add up to num_witness_polys / num_challenges");
-  const std::vector<size_t> per_phase = ph.num_witness_polys;
-  ph.synthesize = [circuit, per_phase](size_t round, const std::vector<HFr>& challenges) {
-    std::vector<const void*> out(per_phase[round], nullptr);
-    int rc = circuit->synthesize(circuit->user, round, (const lh_fr*)challenges.data(), challenges.size(), out.data(),
-                                 out.size());
-    if (rc != LH_OK) throw lh::Error(rc < 0 ? rc : LH_ERR_INVALID_SNARK, "circuit synthesize callback failed");
-    std::vector<const Fr*> w;
-    for (const void* p : out) {
-      LH_REQUIRE(p != nullptr, LH_ERR_ARG, "circuit synthesize left a witness poly unset");
-      w.push_back((const Fr*)p);
-    }
-    return w;
-  };
-  return ph;
 }
 
 lh_status lh_hyperplonk_prove_phases(lh_ctx* ctx, const lh_srs* srs, const lh_hp_param* pp, size_t num_phases,
@@ -739,11 +824,8 @@ lh_status lh_hyperplonk_prove_phases(lh_ctx* ctx, const lh_srs* srs, const lh_hp
                                      const lh_fr* const* instances, const lh_hp_circuit* circuit, lh_transcript* t) {
   LH_TRY NEED_CTX(ctx);
   NEED(srs);
-  NEED(pp);
-  NEED(circuit);
-  Transcript tr(t);
-  const HpPhases ph = hp_phases_of(pp, num_phases, num_witness_polys, num_challenges, circuit);
-  hyperplonk_prove_phases(ctx->c, mkzg_pcs(ctx->c, srs->s), *pp, ph, (const HFr* const*)instances, tr);
+  hyperplonk_prove_phases_entry(ctx->c, pp, num_phases, num_witness_polys, num_challenges, instances, circuit, t,
+                                [&] { return mkzg_pcs(ctx->c, srs->s); });
   LH_CATCH
 }
 
@@ -751,10 +833,7 @@ lh_status lh_hyperplonk_prove(lh_ctx* ctx, const lh_srs* srs, const lh_hp_param*
                               const lh_fr* const* d_witness_polys, lh_transcript* t) {
   LH_TRY NEED_CTX(ctx);
   NEED(srs);
-  NEED(pp);
-  NEED_N(d_witness_polys, pp->num_witness_polys);
-  Transcript tr(t);
-  hyperplonk_prove(ctx->c, mkzg_pcs(ctx->c, srs->s), *pp, (const HFr* const*)instances, (const Fr* const*)d_witness_polys, tr);
+  hyperplonk_prove_entry(ctx->c, pp, instances, d_witness_polys, t, [&] { return mkzg_pcs(ctx->c, srs->s); });
   LH_CATCH
 }
 
@@ -772,15 +851,10 @@ lh_status lh_hyperplonk_prove_sharded(lh_ctx* ctx, const lh_srs* srs, const lh_h
                                       const lh_fr* const* d_witness_polys, lh_transcript* t) {
   LH_TRY NEED_CTX(ctx);
   NEED(srs);
-  NEED(pp);
+  NEED(pp);  // (the communicator is checked behind the circuit's pointers and ahead of the transcript)
   NEED_N(d_witness_polys, pp->num_witness_polys);
-  Ctx& c = ctx->c;
-  LH_REQUIRE(c.has_comm, LH_ERR_ARG, "lh_hyperplonk_prove_sharded: no communicator attached");
-  const size_t R = (size_t)c.comm.size;
-  LH_REQUIRE(R >= 1 && (R & (R - 1)) == 0, LH_ERR_ARG, "sharded prove: the number of ranks must be a power of two");
-  ShardActive active(c);
-  Transcript tr(t);
-  hyperplonk_prove(c, mkzg_pcs(c, srs->s), *pp, (const HFr* const*)instances, (const Fr* const*)d_witness_polys, tr);
+  const std::unique_ptr<ShardActive> active = shard_activate(ctx->c, "lh_hyperplonk_prove_sharded");
+  hyperplonk_prove_entry(ctx->c, pp, instances, d_witness_polys, t, [&] { return mkzg_pcs(ctx->c, srs->s); });
   LH_CATCH
 }
 
@@ -866,24 +940,14 @@ lh_status lh_sumcheck_verify(int prover_kind, size_t num_vars, size_t degree, co
 lh_status lh_lasso_verify(const lh_mkzg_vp* vp, const lh_lasso_table* table, size_t num_vars, lh_transcript* t) {
   LH_TRY
   NEED(vp);
-  NEED(table);
-  Transcript tr(t);
-  const VerifierParams& pcs = *vp->p;
-  lasso_verify([&pcs](size_t nv, const HG1* comms, size_t nc, const HFr* points, size_t np, const lh_evaluation* evals,
-                      size_t ne, Transcript& t2) { mkzg_batch_verify(pcs, nv, comms, nc, points, np, evals, ne, t2); },
-               *table, num_vars, tr);
+  lasso_verify_entry(table, num_vars, t, [&] { return mkzg_verifier(*vp->p); });
   LH_CATCH
 }
 lh_status lh_hyperplonk_verify(const lh_mkzg_vp* vp, const lh_hp_vparam* hvp, const lh_fr* const* instances,
                                lh_transcript* t) {
   LH_TRY
   NEED(vp);
-  NEED(hvp);
-  Transcript tr(t);
-  const VerifierParams& pcs = *vp->p;
-  hyperplonk_verify([&pcs](size_t nv, const HG1* comms, size_t nc, const HFr* points, size_t np, const lh_evaluation* evals,
-                           size_t ne, Transcript& t2) { mkzg_batch_verify(pcs, nv, comms, nc, points, np, evals, ne, t2); },
-                    *hvp, (const HFr* const*)instances, tr);
+  hyperplonk_verify_entry(hvp, instances, t, [&] { return mkzg_verifier(*vp->p); });
   LH_CATCH
 }
 lh_status lh_hyperplonk_verify_phases(const lh_mkzg_vp* vp, const lh_hp_vparam* hvp, size_t num_phases,
@@ -891,15 +955,8 @@ lh_status lh_hyperplonk_verify_phases(const lh_mkzg_vp* vp, const lh_hp_vparam* 
                                       const lh_fr* const* instances, lh_transcript* t) {
   LH_TRY
   NEED(vp);
-  NEED(hvp);
-  LH_REQUIRE(num_phases == 0 || (num_witness_polys && num_challenges), LH_ERR_ARG, "null argument: phases");
-  Transcript tr(t);
-  const VerifierParams& pcs = *vp->p;
-  hyperplonk_verify_phases(
-      [&pcs](size_t nv, const HG1* comms, size_t nc, const HFr* points, size_t np, const lh_evaluation* evals, size_t ne,
-             Transcript& t2) { mkzg_batch_verify(pcs, nv, comms, nc, points, np, evals, ne, t2); },
-      *hvp, std::vector<size_t>(num_witness_polys, num_witness_polys + num_phases),
-      std::vector<size_t>(num_challenges, num_challenges + num_phases), (const HFr* const*)instances, tr);
+  hyperplonk_verify_phases_entry(hvp, num_phases, num_witness_polys, num_challenges, instances, t,
+                                 [&] { return mkzg_verifier(*vp->p); });
   LH_CATCH
 }
 
@@ -1279,12 +1336,7 @@ lh_status lh_hyperplonk_prove_brakedown(lh_ctx* ctx, const lh_brakedown_param* b
                              perm = bd_comms_of(permutation_comms, pp->num_permutation_polys, "permutation_comms");
   Transcript tr(t);
   HashTranscript h(ht);
-  HpPhases ph;  // single phase: synthesize(0, []) = d_witness_polys
-  ph.num_witness_polys = {pp->num_witness_polys};
-  ph.num_challenges = {pp->num_challenges};
-  ph.synthesize = [&](size_t, const std::vector<HFr>&) {
-    return std::vector<const Fr*>((const Fr* const*)d_witness_polys, (const Fr* const*)d_witness_polys + pp->num_witness_polys);
-  };
+  const HpPhases ph = hp_single_phase(*pp, (const Fr* const*)d_witness_polys);
   brakedown_hyperplonk_prove_phases(ctx->c, bp->p, *pp, pre.data(), perm.data(), ph, (const HFr* const*)instances, tr, h);
   LH_CATCH
 }
@@ -1318,12 +1370,10 @@ lh_status lh_hyperplonk_verify_phases_brakedown(const lh_brakedown_param* bp, co
   NEED_N(preprocess_roots, hvp->num_preprocess_polys);
   NEED_N(permutation_roots, hvp->num_permutation_polys);
   NEED_N(instances, hvp->num_instance_polys);
-  LH_REQUIRE(num_phases == 0 || (num_witness_polys && num_challenges), LH_ERR_ARG, "null argument: phases");
+  const VerifierPhases ph = verifier_phases_of(num_phases, num_witness_polys, num_challenges);
   Transcript tr(t);
   HashTranscript h(ht);
-  brakedown_hyperplonk_verify_phases(bp->p, *hvp, preprocess_roots, permutation_roots,
-                                     std::vector<size_t>(num_witness_polys, num_witness_polys + num_phases),
-                                     std::vector<size_t>(num_challenges, num_challenges + num_phases),
+  brakedown_hyperplonk_verify_phases(bp->p, *hvp, preprocess_roots, permutation_roots, ph.num_witness_polys, ph.num_challenges,
                                      (const HFr* const*)instances, tr, h);
   LH_CATCH
 }
@@ -1340,21 +1390,13 @@ lh_status lh_lasso_prove_zeromorph(lh_ctx* ctx, const lh_usrs* srs, size_t poly_
                                    size_t num_vars, const uint32_t* const* d_dims, lh_transcript* t) {
   LH_TRY NEED_CTX(ctx);
   NEED(srs);
-  NEED(table);
-  NEED(d_dims);
-  Transcript tr(t);
-  lasso_prove(ctx->c, zeromorph_pcs(ctx->c, srs->s, poly_size), *table, num_vars, d_dims, tr);
+  lasso_prove_entry(ctx->c, table, num_vars, d_dims, t, [&] { return zeromorph_pcs(ctx->c, srs->s, poly_size); });
   LH_CATCH
 }
 lh_status lh_lasso_verify_zeromorph(const lh_zm_vp* vp, const lh_lasso_table* table, size_t num_vars, lh_transcript* t) {
   LH_TRY
   NEED(vp);
-  NEED(table);
-  Transcript tr(t);
-  const ZmVerifierParams& pcs = *vp->p;
-  lasso_verify([&pcs](size_t nv, const HG1* comms, size_t nc, const HFr* points, size_t np, const lh_evaluation* evals,
-                      size_t ne, Transcript& t2) { zeromorph_batch_verify(pcs, nv, comms, nc, points, np, evals, ne, t2); },
-               *table, num_vars, tr);
+  lasso_verify_entry(table, num_vars, t, [&] { return zeromorph_verifier(*vp->p); });
   LH_CATCH
 }
 lh_status lh_hyperplonk_prove_zeromorph(lh_ctx* ctx, const lh_usrs* srs, size_t poly_size, const lh_hp_param* pp,
@@ -1362,23 +1404,14 @@ lh_status lh_hyperplonk_prove_zeromorph(lh_ctx* ctx, const lh_usrs* srs, size_t 
                                         lh_transcript* t) {
   LH_TRY NEED_CTX(ctx);
   NEED(srs);
-  NEED(pp);
-  NEED_N(d_witness_polys, pp->num_witness_polys);
-  Transcript tr(t);
-  hyperplonk_prove(ctx->c, zeromorph_pcs(ctx->c, srs->s, poly_size), *pp, (const HFr* const*)instances,
-                   (const Fr* const*)d_witness_polys, tr);
+  hyperplonk_prove_entry(ctx->c, pp, instances, d_witness_polys, t, [&] { return zeromorph_pcs(ctx->c, srs->s, poly_size); });
   LH_CATCH
 }
 lh_status lh_hyperplonk_verify_zeromorph(const lh_zm_vp* vp, const lh_hp_vparam* hvp, const lh_fr* const* instances,
                                          lh_transcript* t) {
   LH_TRY
   NEED(vp);
-  NEED(hvp);
-  Transcript tr(t);
-  const ZmVerifierParams& pcs = *vp->p;
-  hyperplonk_verify([&pcs](size_t nv, const HG1* comms, size_t nc, const HFr* points, size_t np, const lh_evaluation* evals,
-                           size_t ne, Transcript& t2) { zeromorph_batch_verify(pcs, nv, comms, nc, points, np, evals, ne, t2); },
-                    *hvp, (const HFr* const*)instances, tr);
+  hyperplonk_verify_entry(hvp, instances, t, [&] { return zeromorph_verifier(*vp->p); });
   LH_CATCH
 }
 
@@ -1388,11 +1421,8 @@ lh_status lh_hyperplonk_prove_phases_zeromorph(lh_ctx* ctx, const lh_usrs* srs, 
                                                const lh_hp_circuit* circuit, lh_transcript* t) {
   LH_TRY NEED_CTX(ctx);
   NEED(srs);
-  NEED(pp);
-  NEED(circuit);
-  Transcript tr(t);
-  const HpPhases ph = hp_phases_of(pp, num_phases, num_witness_polys, num_challenges, circuit);
-  hyperplonk_prove_phases(ctx->c, zeromorph_pcs(ctx->c, srs->s, poly_size), *pp, ph, (const HFr* const*)instances, tr);
+  hyperplonk_prove_phases_entry(ctx->c, pp, num_phases, num_witness_polys, num_challenges, instances, circuit, t,
+                                [&] { return zeromorph_pcs(ctx->c, srs->s, poly_size); });
   LH_CATCH
 }
 lh_status lh_hyperplonk_verify_phases_zeromorph(const lh_zm_vp* vp, const lh_hp_vparam* hvp, size_t num_phases,
@@ -1400,15 +1430,8 @@ lh_status lh_hyperplonk_verify_phases_zeromorph(const lh_zm_vp* vp, const lh_hp_
                                                 const lh_fr* const* instances, lh_transcript* t) {
   LH_TRY
   NEED(vp);
-  NEED(hvp);
-  LH_REQUIRE(num_phases == 0 || (num_witness_polys && num_challenges), LH_ERR_ARG, "null argument: phases");
-  Transcript tr(t);
-  const ZmVerifierParams& pcs = *vp->p;
-  hyperplonk_verify_phases(
-      [&pcs](size_t nv, const HG1* comms, size_t nc, const HFr* points, size_t np, const lh_evaluation* evals, size_t ne,
-             Transcript& t2) { zeromorph_batch_verify(pcs, nv, comms, nc, points, np, evals, ne, t2); },
-      *hvp, std::vector<size_t>(num_witness_polys, num_witness_polys + num_phases),
-      std::vector<size_t>(num_challenges, num_challenges + num_phases), (const HFr* const*)instances, tr);
+  hyperplonk_verify_phases_entry(hvp, num_phases, num_witness_polys, num_challenges, instances, t,
+                                 [&] { return zeromorph_verifier(*vp->p); });
   LH_CATCH
 }
 
@@ -1587,46 +1610,31 @@ lh_status lh_gemini_batch_verify(const lh_ukzg_vp* vp, size_t num_vars, const lh
   gemini_batch_verify(*vp->p, num_vars, (const HG1*)comms, num_comms, (const HFr*)points, num_points, evals, num_evals, tr);
   LH_CATCH
 }
-static PcsBatchVerify gemini_verifier(const UkzgVerifierParams& pcs) {
-  return [&pcs](size_t nv, const HG1* comms, size_t nc, const HFr* points, size_t np, const lh_evaluation* evals, size_t ne,
-                Transcript& t2) { gemini_batch_verify(pcs, nv, comms, nc, points, np, evals, ne, t2); };
-}
 lh_status lh_lasso_prove_gemini(lh_ctx* ctx, const lh_usrs* srs, size_t poly_size, const lh_lasso_table* table,
                                 size_t num_vars, const uint32_t* const* d_dims, lh_transcript* t) {
   LH_TRY NEED_CTX(ctx);
   NEED(srs);
-  NEED(table);
-  NEED(d_dims);
-  Transcript tr(t);
-  lasso_prove(ctx->c, gemini_pcs(ctx->c, srs->s, poly_size), *table, num_vars, d_dims, tr);
+  lasso_prove_entry(ctx->c, table, num_vars, d_dims, t, [&] { return gemini_pcs(ctx->c, srs->s, poly_size); });
   LH_CATCH
 }
 lh_status lh_lasso_verify_gemini(const lh_ukzg_vp* vp, const lh_lasso_table* table, size_t num_vars, lh_transcript* t) {
   LH_TRY
   NEED(vp);
-  NEED(table);
-  Transcript tr(t);
-  lasso_verify(gemini_verifier(*vp->p), *table, num_vars, tr);
+  lasso_verify_entry(table, num_vars, t, [&] { return gemini_verifier(*vp->p); });
   LH_CATCH
 }
 lh_status lh_hyperplonk_prove_gemini(lh_ctx* ctx, const lh_usrs* srs, size_t poly_size, const lh_hp_param* pp,
                                      const lh_fr* const* instances, const lh_fr* const* d_witness_polys, lh_transcript* t) {
   LH_TRY NEED_CTX(ctx);
   NEED(srs);
-  NEED(pp);
-  NEED_N(d_witness_polys, pp->num_witness_polys);
-  Transcript tr(t);
-  hyperplonk_prove(ctx->c, gemini_pcs(ctx->c, srs->s, poly_size), *pp, (const HFr* const*)instances,
-                   (const Fr* const*)d_witness_polys, tr);
+  hyperplonk_prove_entry(ctx->c, pp, instances, d_witness_polys, t, [&] { return gemini_pcs(ctx->c, srs->s, poly_size); });
   LH_CATCH
 }
 lh_status lh_hyperplonk_verify_gemini(const lh_ukzg_vp* vp, const lh_hp_vparam* hvp, const lh_fr* const* instances,
                                       lh_transcript* t) {
   LH_TRY
   NEED(vp);
-  NEED(hvp);
-  Transcript tr(t);
-  hyperplonk_verify(gemini_verifier(*vp->p), *hvp, (const HFr* const*)instances, tr);
+  hyperplonk_verify_entry(hvp, instances, t, [&] { return gemini_verifier(*vp->p); });
   LH_CATCH
 }
 lh_status lh_hyperplonk_prove_phases_gemini(lh_ctx* ctx, const lh_usrs* srs, size_t poly_size, const lh_hp_param* pp,
@@ -1634,11 +1642,8 @@ lh_status lh_hyperplonk_prove_phases_gemini(lh_ctx* ctx, const lh_usrs* srs, siz
                                             const lh_fr* const* instances, const lh_hp_circuit* circuit, lh_transcript* t) {
   LH_TRY NEED_CTX(ctx);
   NEED(srs);
-  NEED(pp);
-  NEED(circuit);
-  Transcript tr(t);
-  const HpPhases ph = hp_phases_of(pp, num_phases, num_witness_polys, num_challenges, circuit);
-  hyperplonk_prove_phases(ctx->c, gemini_pcs(ctx->c, srs->s, poly_size), *pp, ph, (const HFr* const*)instances, tr);
+  hyperplonk_prove_phases_entry(ctx->c, pp, num_phases, num_witness_polys, num_challenges, instances, circuit, t,
+                                [&] { return gemini_pcs(ctx->c, srs->s, poly_size); });
   LH_CATCH
 }
 lh_status lh_hyperplonk_verify_phases_gemini(const lh_ukzg_vp* vp, const lh_hp_vparam* hvp, size_t num_phases,
@@ -1646,11 +1651,8 @@ lh_status lh_hyperplonk_verify_phases_gemini(const lh_ukzg_vp* vp, const lh_hp_v
                                              const lh_fr* const* instances, lh_transcript* t) {
   LH_TRY
   NEED(vp);
-  NEED(hvp);
-  LH_REQUIRE(num_phases == 0 || (num_witness_polys && num_challenges), LH_ERR_ARG, "null argument: phases");
-  Transcript tr(t);
-  hyperplonk_verify_phases(gemini_verifier(*vp->p), *hvp, std::vector<size_t>(num_witness_polys, num_witness_polys + num_phases),
-                           std::vector<size_t>(num_challenges, num_challenges + num_phases), (const HFr* const*)instances, tr);
+  hyperplonk_verify_phases_entry(hvp, num_phases, num_witness_polys, num_challenges, instances, t,
+                                 [&] { return gemini_verifier(*vp->p); });
   LH_CATCH
 }
 
@@ -1864,76 +1866,45 @@ lh_status lh_hyrax_batch_verify(const lh_ipa_param* param, size_t poly_size, siz
                      evals, num_evals, tr);
   LH_CATCH
 }
-static PcsBatchVerify ipa_verifier(const IpaParams& pcs, size_t poly_size) {
-  return [&pcs, poly_size](size_t nv, const HG1* comms, size_t nc, const HFr* points, size_t np, const lh_evaluation* evals,
-                           size_t ne, Transcript& t2) { ipa_batch_verify(pcs, poly_size, nv, comms, nc, points, np, evals, ne, t2); };
-}
-// Hyrax commits only tables of exactly the param's num_vars (hyrax.rs groups rows by the param's count)
-static void hyrax_lasso_vars(const IpaParams& p, size_t poly_size, size_t batch_size, const lh_lasso_table& tb, size_t num_vars) {
-  const HyraxDims d = hyrax_trim(p, poly_size, batch_size);
-  LH_REQUIRE(std::max<size_t>(num_vars, tb.chunk_bits) == d.num_vars, LH_ERR_ARG,
-             "lasso over hyrax: max(num_vars, chunk_bits) must equal log2(poly_size) (Hyrax commits only tables of the param's size)");
-}
 lh_status lh_lasso_prove_hyrax(lh_ctx* ctx, const lh_ipa_param* param, size_t poly_size, size_t batch_size,
                                const lh_lasso_table* table, size_t num_vars, const uint32_t* const* d_dims, lh_transcript* t) {
   LH_TRY NEED_CTX(ctx);
   NEED(param);
-  NEED(table);
-  NEED(d_dims);
-  Transcript tr(t);
-  hyrax_lasso_vars(*param->p, poly_size, batch_size, *table, num_vars);
-  lasso_prove(ctx->c, hyrax_pcs(ctx->c, *param->p, poly_size, batch_size), *table, num_vars, d_dims, tr);
+  lasso_prove_entry(ctx->c, table, num_vars, d_dims, t, [&] {
+    hyrax_lasso_vars(*param->p, poly_size, batch_size, *table, num_vars);
+    return hyrax_pcs(ctx->c, *param->p, poly_size, batch_size);
+  });
   LH_CATCH
 }
 lh_status lh_lasso_verify_hyrax(const lh_ipa_param* param, size_t poly_size, size_t batch_size, const lh_lasso_table* table,
                                 size_t num_vars, lh_transcript* t) {
   LH_TRY
   NEED(param);
-  NEED(table);
-  Transcript tr(t);
-  hyrax_lasso_vars(*param->p, poly_size, batch_size, *table, num_vars);
-  const IpaParams& pcs = *param->p;
-  const PcsBatchVerify bv = [&pcs, poly_size, batch_size](size_t nv, const HG1* comms, size_t nc, const HFr* points, size_t np,
-                                                           const lh_evaluation* evals, size_t ne, Transcript& t2) {
-    hyrax_batch_verify(pcs, poly_size, batch_size, nv, comms, nc, points, np, evals, ne, t2);
-  };
-  lasso_verify(bv, *table, num_vars, tr, hyrax_trim(pcs, poly_size, batch_size).num_chunks());
+  lasso_verify_entry(table, num_vars, t, [&] {
+    hyrax_lasso_vars(*param->p, poly_size, batch_size, *table, num_vars);
+    return hyrax_verifier(*param->p, poly_size, batch_size);
+  });
   LH_CATCH
-}
-static PcsBatchVerify hyrax_verifier(const IpaParams& pcs, size_t poly_size, size_t batch_size) {
-  return [&pcs, poly_size, batch_size](size_t nv, const HG1* comms, size_t nc, const HFr* points, size_t np, const lh_evaluation* evals,
-                                       size_t ne, Transcript& t2) {
-    hyrax_batch_verify(pcs, poly_size, batch_size, nv, comms, nc, points, np, evals, ne, t2);
-  };
-}
-// Hyrax commits only polys of exactly the param's num_vars: the circuit's k
-static size_t hyrax_hp_chunks(const IpaParams& p, size_t poly_size, size_t batch_size, size_t num_vars) {
-  const HyraxDims d = hyrax_trim(p, poly_size, batch_size);
-  LH_REQUIRE(num_vars == d.num_vars, LH_ERR_ARG,
-             "hyperplonk over hyrax: the circuit's num_vars must equal log2(poly_size) (Hyrax commits only tables of the param's size)");
-  return d.num_chunks();
 }
 lh_status lh_hyperplonk_prove_hyrax(lh_ctx* ctx, const lh_ipa_param* param, size_t poly_size, size_t batch_size,
                                     const lh_hp_param* pp, const lh_fr* const* instances, const lh_fr* const* d_witness_polys,
                                     lh_transcript* t) {
   LH_TRY NEED_CTX(ctx);
   NEED(param);
-  NEED(pp);
-  NEED_N(d_witness_polys, pp->num_witness_polys);
-  Transcript tr(t);
-  hyrax_hp_chunks(*param->p, poly_size, batch_size, pp->num_vars);
-  hyperplonk_prove(ctx->c, hyrax_pcs(ctx->c, *param->p, poly_size, batch_size), *pp, (const HFr* const*)instances,
-                   (const Fr* const*)d_witness_polys, tr);
+  hyperplonk_prove_entry(ctx->c, pp, instances, d_witness_polys, t, [&] {
+    hyrax_hyperplonk_vars(*param->p, poly_size, batch_size, pp->num_vars);
+    return hyrax_pcs(ctx->c, *param->p, poly_size, batch_size);
+  });
   LH_CATCH
 }
 lh_status lh_hyperplonk_verify_hyrax(const lh_ipa_param* param, size_t poly_size, size_t batch_size, const lh_hp_vparam* hvp,
                                      const lh_fr* const* instances, lh_transcript* t) {
   LH_TRY
   NEED(param);
-  NEED(hvp);
-  Transcript tr(t);
-  const size_t chunks = hyrax_hp_chunks(*param->p, poly_size, batch_size, hvp->num_vars);
-  hyperplonk_verify(hyrax_verifier(*param->p, poly_size, batch_size), *hvp, (const HFr* const*)instances, tr, chunks);
+  hyperplonk_verify_entry(hvp, instances, t, [&] {
+    hyrax_hyperplonk_vars(*param->p, poly_size, batch_size, hvp->num_vars);
+    return hyrax_verifier(*param->p, poly_size, batch_size);
+  });
   LH_CATCH
 }
 lh_status lh_hyperplonk_prove_phases_hyrax(lh_ctx* ctx, const lh_ipa_param* param, size_t poly_size, size_t batch_size,
@@ -1942,12 +1913,10 @@ lh_status lh_hyperplonk_prove_phases_hyrax(lh_ctx* ctx, const lh_ipa_param* para
                                            const lh_hp_circuit* circuit, lh_transcript* t) {
   LH_TRY NEED_CTX(ctx);
   NEED(param);
-  NEED(pp);
-  NEED(circuit);
-  Transcript tr(t);
-  hyrax_hp_chunks(*param->p, poly_size, batch_size, pp->num_vars);
-  const HpPhases ph = hp_phases_of(pp, num_phases, num_witness_polys, num_challenges, circuit);
-  hyperplonk_prove_phases(ctx->c, hyrax_pcs(ctx->c, *param->p, poly_size, batch_size), *pp, ph, (const HFr* const*)instances, tr);
+  hyperplonk_prove_phases_entry(
+      ctx->c, pp, num_phases, num_witness_polys, num_challenges, instances, circuit, t,
+      [&] { return hyrax_pcs(ctx->c, *param->p, poly_size, batch_size); },
+      [&] { hyrax_hyperplonk_vars(*param->p, poly_size, batch_size, pp->num_vars); });
   LH_CATCH
 }
 lh_status lh_hyperplonk_verify_phases_hyrax(const lh_ipa_param* param, size_t poly_size, size_t batch_size, const lh_hp_vparam* hvp,
@@ -1955,52 +1924,38 @@ lh_status lh_hyperplonk_verify_phases_hyrax(const lh_ipa_param* param, size_t po
                                             const lh_fr* const* instances, lh_transcript* t) {
   LH_TRY
   NEED(param);
-  NEED(hvp);
-  LH_REQUIRE(num_phases == 0 || (num_witness_polys && num_challenges), LH_ERR_ARG, "null argument: phases");
-  Transcript tr(t);
-  const size_t chunks = hyrax_hp_chunks(*param->p, poly_size, batch_size, hvp->num_vars);
-  hyperplonk_verify_phases(hyrax_verifier(*param->p, poly_size, batch_size), *hvp,
-                           std::vector<size_t>(num_witness_polys, num_witness_polys + num_phases),
-                           std::vector<size_t>(num_challenges, num_challenges + num_phases), (const HFr* const*)instances, tr, chunks);
+  hyperplonk_verify_phases_entry(hvp, num_phases, num_witness_polys, num_challenges, instances, t, [&] {
+    hyrax_hyperplonk_vars(*param->p, poly_size, batch_size, hvp->num_vars);
+    return hyrax_verifier(*param->p, poly_size, batch_size);
+  });
   LH_CATCH
 }
 lh_status lh_lasso_prove_ipa(lh_ctx* ctx, const lh_ipa_param* param, size_t poly_size, const lh_lasso_table* table,
                              size_t num_vars, const uint32_t* const* d_dims, lh_transcript* t) {
   LH_TRY NEED_CTX(ctx);
   NEED(param);
-  NEED(table);
-  NEED(d_dims);
-  Transcript tr(t);
-  lasso_prove(ctx->c, ipa_pcs(ctx->c, *param->p, poly_size), *table, num_vars, d_dims, tr);
+  lasso_prove_entry(ctx->c, table, num_vars, d_dims, t, [&] { return ipa_pcs(ctx->c, *param->p, poly_size); });
   LH_CATCH
 }
 lh_status lh_lasso_verify_ipa(const lh_ipa_param* param, size_t poly_size, const lh_lasso_table* table, size_t num_vars,
                               lh_transcript* t) {
   LH_TRY
   NEED(param);
-  NEED(table);
-  Transcript tr(t);
-  lasso_verify(ipa_verifier(*param->p, poly_size), *table, num_vars, tr);
+  lasso_verify_entry(table, num_vars, t, [&] { return ipa_verifier(*param->p, poly_size); });
   LH_CATCH
 }
 lh_status lh_hyperplonk_prove_ipa(lh_ctx* ctx, const lh_ipa_param* param, size_t poly_size, const lh_hp_param* pp,
                                   const lh_fr* const* instances, const lh_fr* const* d_witness_polys, lh_transcript* t) {
   LH_TRY NEED_CTX(ctx);
   NEED(param);
-  NEED(pp);
-  NEED_N(d_witness_polys, pp->num_witness_polys);
-  Transcript tr(t);
-  hyperplonk_prove(ctx->c, ipa_pcs(ctx->c, *param->p, poly_size), *pp, (const HFr* const*)instances,
-                   (const Fr* const*)d_witness_polys, tr);
+  hyperplonk_prove_entry(ctx->c, pp, instances, d_witness_polys, t, [&] { return ipa_pcs(ctx->c, *param->p, poly_size); });
   LH_CATCH
 }
 lh_status lh_hyperplonk_verify_ipa(const lh_ipa_param* param, size_t poly_size, const lh_hp_vparam* hvp,
                                    const lh_fr* const* instances, lh_transcript* t) {
   LH_TRY
   NEED(param);
-  NEED(hvp);
-  Transcript tr(t);
-  hyperplonk_verify(ipa_verifier(*param->p, poly_size), *hvp, (const HFr* const*)instances, tr);
+  hyperplonk_verify_entry(hvp, instances, t, [&] { return ipa_verifier(*param->p, poly_size); });
   LH_CATCH
 }
 lh_status lh_hyperplonk_prove_phases_ipa(lh_ctx* ctx, const lh_ipa_param* param, size_t poly_size, const lh_hp_param* pp,
@@ -2008,11 +1963,8 @@ lh_status lh_hyperplonk_prove_phases_ipa(lh_ctx* ctx, const lh_ipa_param* param,
                                          const lh_fr* const* instances, const lh_hp_circuit* circuit, lh_transcript* t) {
   LH_TRY NEED_CTX(ctx);
   NEED(param);
-  NEED(pp);
-  NEED(circuit);
-  Transcript tr(t);
-  const HpPhases ph = hp_phases_of(pp, num_phases, num_witness_polys, num_challenges, circuit);
-  hyperplonk_prove_phases(ctx->c, ipa_pcs(ctx->c, *param->p, poly_size), *pp, ph, (const HFr* const*)instances, tr);
+  hyperplonk_prove_phases_entry(ctx->c, pp, num_phases, num_witness_polys, num_challenges, instances, circuit, t,
+                                [&] { return ipa_pcs(ctx->c, *param->p, poly_size); });
   LH_CATCH
 }
 lh_status lh_hyperplonk_verify_phases_ipa(const lh_ipa_param* param, size_t poly_size, const lh_hp_vparam* hvp, size_t num_phases,
@@ -2020,12 +1972,8 @@ lh_status lh_hyperplonk_verify_phases_ipa(const lh_ipa_param* param, size_t poly
                                           const lh_fr* const* instances, lh_transcript* t) {
   LH_TRY
   NEED(param);
-  NEED(hvp);
-  LH_REQUIRE(num_phases == 0 || (num_witness_polys && num_challenges), LH_ERR_ARG, "null argument: phases");
-  Transcript tr(t);
-  hyperplonk_verify_phases(ipa_verifier(*param->p, poly_size), *hvp,
-                           std::vector<size_t>(num_witness_polys, num_witness_polys + num_phases),
-                           std::vector<size_t>(num_challenges, num_challenges + num_phases), (const HFr* const*)instances, tr);
+  hyperplonk_verify_phases_entry(hvp, num_phases, num_witness_polys, num_challenges, instances, t,
+                                 [&] { return ipa_verifier(*param->p, poly_size); });
   LH_CATCH
 }
 

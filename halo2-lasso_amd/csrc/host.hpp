@@ -109,6 +109,16 @@ typedef std::function<void(size_t num_vars, const HG1* comms, size_t num_comms, 
 // optional, for a PCS whose commitments are not G1 points (Brakedown: 32-byte Merkle roots that cross the transcript
 // unabsorbed): reads n commitments, each into the first bytes of a 64-byte HG1 slot that only its own batch_verify interprets
 typedef std::function<std::vector<HG1>(Transcript& tr, size_t n)> PcsReadCommitments;
+// what the verifiers (Lasso, HyperPlonk) need from their PCS: the verifier-side twin of Pcs below.  Every scheme builds its
+// own next to its batch_verify (mkzg_verifier, zeromorph_verifier, gemini_verifier, ipa_verifier, hyrax_verifier); the param
+// it is built from must outlive it
+struct PcsVerifier {
+  PcsBatchVerify batch_verify;
+  // points per commitment (Hyrax's rows): every commitment is read as that many points, a HyperPlonk verifier param holds
+  // that many per poly (poly-major), and batch_verify gets the commitments as vectors, commitment-major
+  size_t chunks = 1;
+  PcsReadCommitments read_commitments;  // optional (default: Transcript::read_commitments)
+};
 
 // ------------------------------------------------------------------ poly helpers (host side, tiny inputs)
 std::vector<HFr> host_eq_xy(const std::vector<HFr>& y);           // multilinear.rs:91-127
@@ -375,6 +385,7 @@ void zeromorph_verify(const ZmVerifierParams&, const HG1& comm, const HFr* point
 void zeromorph_batch_verify(const ZmVerifierParams&, size_t num_vars, const HG1* comms, size_t num_comms,
                             const HFr* points, size_t num_points, const lh_evaluation* evals, size_t num_evals,
                             Transcript& tr);
+PcsVerifier zeromorph_verifier(const ZmVerifierParams&);
 
 // ------------------------------------------------------------------ pcs::univariate::kzg on its own, pcs::multilinear::gemini over it
 // (gemini.cpp; verifiers in verifier.cpp).  `poly_size` is the trim size (univariate/kzg.rs:220-240): pp = powers[..poly_size].
@@ -423,6 +434,7 @@ void gemini_verify(const UkzgVerifierParams&, const HG1& comm, const HFr* point,
                    Transcript& tr);
 void gemini_batch_verify(const UkzgVerifierParams&, size_t num_vars, const HG1* comms, size_t num_comms, const HFr* points,
                          size_t num_points, const lh_evaluation* evals, size_t num_evals, Transcript& tr);
+PcsVerifier gemini_verifier(const UkzgVerifierParams&);
 
 // ------------------------------------------------------------------ pcs::multilinear::ipa over bn256::G1Affine (ipa.cpp;
 // verifier in verifier.cpp).  MultilinearIpaParams (ipa.rs:25-44) is prover and verifier param at once: g on the device
@@ -456,6 +468,7 @@ void ipa_verify(const IpaParams&, size_t poly_size, const HG1& comm, const HFr* 
                 Transcript& tr);
 void ipa_batch_verify(const IpaParams&, size_t poly_size, size_t num_vars, const HG1* comms, size_t num_comms, const HFr* points,
                       size_t num_points, const lh_evaluation* evals, size_t num_evals, Transcript& tr);
+PcsVerifier ipa_verifier(const IpaParams&, size_t poly_size);
 
 // pcs::multilinear::hyrax on top of it (hyrax.rs:23-321): a table of 2^num_vars entries as 2^(num_vars - row_num_vars) rows of
 // 2^row_num_vars, one IPA commitment per row; MultilinearHyraxParams = these dimensions + an IpaParams of 2^row_num_vars.
@@ -478,6 +491,7 @@ void hyrax_verify(const IpaParams&, size_t poly_size, size_t batch_size, const H
                   const HFr& eval, Transcript& tr);
 void hyrax_batch_verify(const IpaParams&, size_t poly_size, size_t batch_size, size_t num_vars, const HG1* comms, size_t num_comms,
                         const HFr* points, size_t num_points, const lh_evaluation* evals, size_t num_evals, Transcript& tr);
+PcsVerifier hyrax_verifier(const IpaParams&, size_t poly_size, size_t batch_size);  // chunks from hyrax_trim
 
 // what the provers (Lasso, HyperPlonk and its Lasso lookups) need from their PCS: the PolynomialCommitmentScheme the
 // backend is generic over (backend/hyperplonk.rs:76-95), plus the bases themselves for the small-valued Lasso columns
@@ -584,8 +598,6 @@ void lasso_write_commitments(Transcript& tr, const std::vector<HG1>& comms, size
 std::vector<HG1> lasso_read_commitments(Transcript& tr, size_t count, size_t chunks = 1);
 void lasso_prove(Ctx&, const Pcs&, const lh_lasso_table& table, size_t num_vars, const uint32_t* const* d_dims,
                  Transcript& tr);
-void lasso_prove_sharded(Ctx&, const Srs&, const lh_lasso_table& table, size_t num_vars,
-                         const uint32_t* const* d_dims, Transcript& tr);
 
 // ------------------------------------------------------------------ verifiers (verifier.cpp; host only)
 HFr interpolate_evals(const std::vector<HFr>& evals, const HFr& x);  // barycentric over 0..d (arithmetic.rs:108-136)
@@ -601,22 +613,16 @@ void mkzg_verify(const VerifierParams&, const HG1& comm, const HFr* point, size_
                  Transcript& tr);
 void mkzg_batch_verify(const VerifierParams&, size_t num_vars, const HG1* comms, size_t num_comms, const HFr* points,
                        size_t num_points, const lh_evaluation* evals, size_t num_evals, Transcript& tr);
+PcsVerifier mkzg_verifier(const VerifierParams&);
 // -> (final claim, challenges)
 std::pair<HFr, std::vector<HFr>> sum_check_verify(int prover_kind, size_t num_vars, size_t degree, const HFr& sum,
                                                   Transcript& tr);
-// chunks: points per commitment (the batch_verify then gets count commitments of `chunks` points each, commitment-major)
-void lasso_verify(const PcsBatchVerify& batch_verify, const lh_lasso_table& table, size_t num_vars, Transcript& tr,
-                  size_t chunks = 1);
+void lasso_verify(const PcsVerifier& pcs, const lh_lasso_table& table, size_t num_vars, Transcript& tr);
 // the verifier's side of lasso_argue: Surge and memory-checking identities; claims left to check against commitments
 LassoClaims lasso_check(const lh_lasso_table& table, size_t num_vars, Transcript& tr);
-// chunks: points per commitment (vp's preprocess_comms / permutation_comms then hold that many per poly, poly-major)
-// read_commitments (optional): how the witness, m, h and z commitments are read (default: Transcript::read_commitments)
-void hyperplonk_verify(const PcsBatchVerify& batch_verify, const lh_hp_vparam& vp, const HFr* const* instances,
-                       Transcript& tr, size_t chunks = 1, const PcsReadCommitments& read_commitments = nullptr);
-void hyperplonk_verify_phases(const PcsBatchVerify& batch_verify, const lh_hp_vparam& vp,
-                              const std::vector<size_t>& num_witness_polys, const std::vector<size_t>& num_challenges,
-                              const HFr* const* instances, Transcript& tr, size_t chunks = 1,
-                              const PcsReadCommitments& read_commitments = nullptr);
+void hyperplonk_verify(const PcsVerifier& pcs, const lh_hp_vparam& vp, const HFr* const* instances, Transcript& tr);
+void hyperplonk_verify_phases(const PcsVerifier& pcs, const lh_hp_vparam& vp, const std::vector<size_t>& num_witness_polys,
+                              const std::vector<size_t>& num_challenges, const HFr* const* instances, Transcript& tr);
 
 // ------------------------------------------------------------------ HyperPlonk (hyperplonk.cpp)
 void hyperplonk_prove(Ctx&, const Pcs&, const lh_hp_param& pp, const HFr* const* instances,
@@ -627,6 +633,7 @@ struct HpPhases {
   std::vector<size_t> num_witness_polys, num_challenges;
   std::function<std::vector<const Fr*>(size_t round, const std::vector<HFr>& challenges)> synthesize;
 };
+HpPhases hp_single_phase(const lh_hp_param& pp, const Fr* const* d_witness);  // synthesize(0, []) = d_witness
 void hyperplonk_prove_phases(Ctx&, const Pcs&, const lh_hp_param& pp, const HpPhases& phases,
                              const HFr* const* instances, Transcript& tr);
 

@@ -132,16 +132,20 @@ struct PhaseTimer {  // LH_HP_DEBUG=1: wall-clock per phase on stderr (developme
 };
 }  // namespace
 
-void hyperplonk_prove(Ctx& c, const Pcs& pcs, const lh_hp_param& pp, const HFr* const* instances,
-                      const Fr* const* d_witness, Transcript& tr) {
-  // single phase: synthesize(0, []) = d_witness
+HpPhases hp_single_phase(const lh_hp_param& pp, const Fr* const* d_witness) {
   HpPhases ph;
   ph.num_witness_polys = {pp.num_witness_polys};
   ph.num_challenges = {pp.num_challenges};
-  ph.synthesize = [&](size_t, const std::vector<HFr>&) {
-    return std::vector<const Fr*>(d_witness, d_witness + pp.num_witness_polys);
+  const size_t count = pp.num_witness_polys;
+  ph.synthesize = [d_witness, count](size_t, const std::vector<HFr>&) {
+    return std::vector<const Fr*>(d_witness, d_witness + count);
   };
-  hyperplonk_prove_phases(c, pcs, pp, ph, instances, tr);
+  return ph;
+}
+
+void hyperplonk_prove(Ctx& c, const Pcs& pcs, const lh_hp_param& pp, const HFr* const* instances,
+                      const Fr* const* d_witness, Transcript& tr) {
+  hyperplonk_prove_phases(c, pcs, pp, hp_single_phase(pp, d_witness), instances, tr);
 }
 
 void hyperplonk_prove_phases(Ctx& c, const Pcs& pcs, const lh_hp_param& pp, const HpPhases& ph,

@@ -438,7 +438,7 @@ void lasso_prove(Ctx& c, const Pcs& pcs, const lh_lasso_table& tb, size_t n, con
   if (n > pcs.max_vars || l > pcs.max_vars)
     throw Error(LH_ERR_INVALID_PCS_PARAM, "Too many variates of poly to commit");
   // every committed poly is zero-padded to nv = max(n, l) variables (spec step 1)
-  // Inside a sharded proof (dev.hpp Shard, lasso_prove_sharded below) d_dims are this rank's shards of the lookup columns
+  // Inside a sharded proof (dev.hpp Shard, lh_lasso_prove_sharded) d_dims are this rank's shards of the lookup columns
   // and every n-variable column below is a shard of N = 2^(n - rho) entries; what crosses ranks: the access counters'
   // exchange, partial commitments, partial sums per round, residual tables (sumcheck.cpp, gkr.cpp, mkzg.cpp).  World of one: nothing.
   const Shard sh(c);
@@ -751,17 +751,6 @@ void lasso_prove(Ctx& c, const Pcs& pcs, const lh_lasso_table& tb, size_t n, con
   ph[7] = 0;
   ph[8] = now_ms() - t0;
   c.phase_ev_pending = true;
-}
-
-// ONE proof over the 2^rho ranks of the ctx's communicator: the same prover, with every table a shard
-// (dev.hpp Shard).  Same transcript, same proof bytes on every rank as lasso_prove on one GPU.
-void lasso_prove_sharded(Ctx& c, const Srs& srs, const lh_lasso_table& tb, size_t n, const uint32_t* const* d_dims_local,
-                         Transcript& tr) {
-  LH_REQUIRE(c.has_comm, LH_ERR_ARG, "lasso_prove_sharded: no communicator attached");
-  const size_t R = (size_t)c.comm.size;
-  LH_REQUIRE(R >= 1 && (R & (R - 1)) == 0, LH_ERR_ARG, "sharded prove: the number of ranks must be a power of two");
-  ShardActive active(c);
-  lasso_prove(c, mkzg_pcs(c, srs), tb, n, d_dims_local, tr);
 }
 
 }  // namespace lh

@@ -191,6 +191,10 @@ void mkzg_batch_verify(const VerifierParams& vp, size_t num_vars, const HG1* com
   additive_batch_verify(num_vars, comms, num_comms, points, num_points, evals, num_evals, tr,
                         [&](const HG1& comm, const HFr* x, const HFr& eval) { mkzg_verify(vp, comm, x, num_vars, eval, tr); });
 }
+// the scheme as a verifier's PCS: its batch_verify with the param bound (`args`: the arguments of PcsBatchVerify)
+PcsVerifier mkzg_verifier(const VerifierParams& vp) {
+  return {[&vp](auto&&... args) { mkzg_batch_verify(vp, args...); }};
+}
 
 // ------------------------------------------------------------------ Zeromorph::verify (zeromorph.rs:215-256)
 struct ZmVerifierParams {
@@ -249,6 +253,9 @@ void zeromorph_batch_verify(const ZmVerifierParams& vp, size_t num_vars, const H
                             Transcript& tr) {
   additive_batch_verify(num_vars, comms, num_comms, points, num_points, evals, num_evals, tr,
                         [&](const HG1& comm, const HFr* x, const HFr& eval) { zeromorph_verify(vp, comm, x, num_vars, eval, tr); });
+}
+PcsVerifier zeromorph_verifier(const ZmVerifierParams& vp) {
+  return {[&vp](auto&&... args) { zeromorph_batch_verify(vp, args...); }};
 }
 
 // ------------------------------------------------------------------ UnivariateKzg::{verify, batch_verify} (univariate/kzg.rs:366-555)
@@ -447,6 +454,9 @@ void gemini_batch_verify(const UkzgVerifierParams& vp, size_t num_vars, const HG
   additive_batch_verify(num_vars, comms, num_comms, points, num_points, evals, num_evals, tr,
                         [&](const HG1& comm, const HFr* x, const HFr& eval) { gemini_verify(vp, comm, x, num_vars, eval, tr); });
 }
+PcsVerifier gemini_verifier(const UkzgVerifierParams& vp) {
+  return {[&vp](auto&&... args) { gemini_batch_verify(vp, args...); }};
+}
 
 // ------------------------------------------------------------------ MultilinearIpa::{verify, batch_verify} (ipa.rs:269-337)
 // variable_base_msm: the bucket method, one window per item of the host pool; only the affine sum is observable
@@ -539,6 +549,9 @@ void ipa_batch_verify(const IpaParams& vp, size_t poly_size, size_t num_vars, co
     ipa_verify(vp, poly_size, comm, x, num_vars, eval, tr);
   });
 }
+PcsVerifier ipa_verifier(const IpaParams& vp, size_t poly_size) {
+  return {[&vp, poly_size](auto&&... args) { ipa_batch_verify(vp, poly_size, args...); }};
+}
 
 // ------------------------------------------------------------------ MultilinearHyrax::{verify, batch_verify} (hyrax.rs:288-320)
 void hyrax_verify(const IpaParams& vp, size_t poly_size, size_t batch_size, const HG1* comm, const HFr* point, size_t num_vars,
@@ -562,6 +575,10 @@ void hyrax_batch_verify(const IpaParams& vp, size_t poly_size, size_t batch_size
                                [&](const HG1* comm, const HFr* x, const HFr& eval) {
                                  hyrax_verify(vp, poly_size, batch_size, comm, x, num_vars, eval, tr);
                                });
+}
+PcsVerifier hyrax_verifier(const IpaParams& vp, size_t poly_size, size_t batch_size) {
+  const size_t chunks = hyrax_trim(vp, poly_size, batch_size).num_chunks();
+  return {[&vp, poly_size, batch_size](auto&&... args) { hyrax_batch_verify(vp, poly_size, batch_size, args...); }, chunks};
 }
 
 // ------------------------------------------------------------------ expressions on the host
@@ -698,18 +715,15 @@ static HFr rotation_eval(const std::vector<HFr>& x, int rotation, const std::vec
 // ------------------------------------------------------------------ HyperPlonk::verify
 static void lasso_verify_check_table(const lh_lasso_table& tb, size_t n);
 
-void hyperplonk_verify(const PcsBatchVerify& batch_verify, const lh_hp_vparam& vp, const HFr* const* instances,
-                       Transcript& tr, size_t chunks, const PcsReadCommitments& read_commitments) {
-  hyperplonk_verify_phases(batch_verify, vp, {vp.num_witness_polys}, {vp.num_challenges}, instances, tr, chunks,
-                           read_commitments);
+void hyperplonk_verify(const PcsVerifier& pcs, const lh_hp_vparam& vp, const HFr* const* instances, Transcript& tr) {
+  hyperplonk_verify_phases(pcs, vp, {vp.num_witness_polys}, {vp.num_challenges}, instances, tr);
 }
 
-void hyperplonk_verify_phases(const PcsBatchVerify& batch_verify, const lh_hp_vparam& vp,
-                              const std::vector<size_t>& phase_witness_polys, const std::vector<size_t>& phase_challenges,
-                              const HFr* const* instances, Transcript& tr, size_t chunks,
-                              const PcsReadCommitments& read_commitments) {
-  auto read_comms = [&](size_t count) { return read_commitments ? read_commitments(tr, count) : tr.read_commitments(count); };
-  LH_REQUIRE(!read_commitments || vp.num_lasso_lookups == 0, LH_ERR_ARG,
+void hyperplonk_verify_phases(const PcsVerifier& pcs, const lh_hp_vparam& vp, const std::vector<size_t>& phase_witness_polys,
+                              const std::vector<size_t>& phase_challenges, const HFr* const* instances, Transcript& tr) {
+  const size_t chunks = pcs.chunks;
+  auto read_comms = [&](size_t count) { return pcs.read_commitments ? pcs.read_commitments(tr, count) : tr.read_commitments(count); };
+  LH_REQUIRE(!pcs.read_commitments || vp.num_lasso_lookups == 0, LH_ERR_ARG,
              "hyperplonk: Lasso lookups need a PCS that commits to points");
   // chunks: points per commitment (Hyrax's rows; 1 otherwise) - every commitment is read as that many points, the verifier
   // param holds that many per poly, and batch_verify gets the commitments as vectors, commitment-major
@@ -889,7 +903,7 @@ void hyperplonk_verify_phases(const PcsBatchVerify& batch_verify, const lh_hp_vp
     for (size_t j = 0; j < cc; j++) push(base + cc + alpha + j, p0 + 3, cl.ev_l[j]);
     base += 2 * cc + alpha;
   }
-  batch_verify(nv, comms.data(), comms.size() / chunks, points.data(), num_points, evals.data(), evals.size(), tr);
+  pcs.batch_verify(nv, comms.data(), comms.size() / chunks, points.data(), num_points, evals.data(), evals.size(), tr);
 }
 
 // ------------------------------------------------------------------ Lasso verify (oracle/pyref/lasso.py:219-261)
@@ -1030,7 +1044,8 @@ LassoClaims lasso_check(const lh_lasso_table& tb, size_t n, Transcript& tr) {
   return cl;
 }
 
-void lasso_verify(const PcsBatchVerify& batch_verify, const lh_lasso_table& tb, size_t n, Transcript& tr, size_t chunks) {
+void lasso_verify(const PcsVerifier& pcs, const lh_lasso_table& tb, size_t n, Transcript& tr) {
+  const size_t chunks = pcs.chunks;
   lasso_verify_check_table(tb, n);
   const size_t c = tb.num_chunks, l = tb.chunk_bits, alpha = tb.num_memories;
   for (size_t v : {n, l, c, alpha}) tr.common_field_element(HFr::from_u64(v));
@@ -1058,7 +1073,7 @@ void lasso_verify(const PcsBatchVerify& batch_verify, const lh_lasso_table& tb, 
     points.insert(points.end(), pt->begin(), pt->end());
     points.insert(points.end(), nv - pt->size(), HFr::zero());
   }
-  batch_verify(nv, comms.data(), comms.size() / chunks, points.data(), 4, evals.data(), evals.size(), tr);
+  pcs.batch_verify(nv, comms.data(), comms.size() / chunks, points.data(), 4, evals.data(), evals.size(), tr);
 }
 
 // ------------------------------------------------------------------ Brakedown (pcs/multilinear/brakedown.rs:315-396)
@@ -1141,24 +1156,24 @@ void brakedown_hyperplonk_verify_phases(const BdParam& p, const lh_hp_vparam& vp
                            perm = slots(permutation_roots, vp.num_permutation_polys);
   lh_hp_vparam v2 = vp;
   v2.preprocess_comms = pre.data(), v2.permutation_comms = perm.data();
-  hyperplonk_verify_phases(
-      [&p, &ht](size_t nv, const HG1* comms, size_t nc, const HFr* points, size_t np, const lh_evaluation* evals, size_t ne,
-                Transcript& t2) {
-        for (size_t i = 0; i < ne; i++) {  // batch_verify is one verify per evaluation (brakedown.rs:398-417)
-          const lh_evaluation& e = evals[i];
-          LH_REQUIRE(e.poly < nc && e.point < np, LH_ERR_ARG, "brakedown batch_verify: evaluation out of range");
-          HFr v;
-          memcpy(&v, &e.value, 32);
-          brakedown_verify(p, (const uint8_t*)&comms[e.poly], points + (size_t)e.point * nv, nv, v, t2, ht);
-        }
-      },
-      v2, num_witness_polys, num_challenges, instances, tr, 1,
-      [&ht](Transcript&, size_t n) {
-        std::vector<HG1> v(n);
-        if (n) memset((void*)v.data(), 0, n * sizeof(HG1));
-        for (size_t i = 0; i < n; i++) ht.read_hash((uint8_t*)&v[i]);
-        return v;
-      });
+  PcsVerifier pcs;
+  pcs.batch_verify = [&p, &ht](size_t nv, const HG1* comms, size_t nc, const HFr* points, size_t np, const lh_evaluation* evals,
+                               size_t ne, Transcript& t2) {
+    for (size_t i = 0; i < ne; i++) {  // batch_verify is one verify per evaluation (brakedown.rs:398-417)
+      const lh_evaluation& e = evals[i];
+      LH_REQUIRE(e.poly < nc && e.point < np, LH_ERR_ARG, "brakedown batch_verify: evaluation out of range");
+      HFr v;
+      memcpy(&v, &e.value, 32);
+      brakedown_verify(p, (const uint8_t*)&comms[e.poly], points + (size_t)e.point * nv, nv, v, t2, ht);
+    }
+  };
+  pcs.read_commitments = [&ht](Transcript&, size_t n) {
+    std::vector<HG1> v(n);
+    if (n) memset((void*)v.data(), 0, n * sizeof(HG1));
+    for (size_t i = 0; i < n; i++) ht.read_hash((uint8_t*)&v[i]);
+    return v;
+  };
+  hyperplonk_verify_phases(pcs, v2, num_witness_polys, num_challenges, instances, tr);
 }
 
 }  // namespace lh

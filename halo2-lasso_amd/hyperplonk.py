@@ -52,6 +52,19 @@ def _lasso_lookups_c(info):
     return arr
 
 
+def _phases_c(info):
+    """(num_phases, num_witness_polys[], num_challenges[]) as the *_phases entries take them"""
+    nph = len(info.num_witness_polys)
+    return (nph, (C.c_size_t * max(nph, 1))(*info.num_witness_polys), (C.c_size_t * max(nph, 1))(*info.num_challenges))
+
+
+def _instances_c(instances):
+    """-> (the array of per-poly pointers, the arrays it points into: keep them alive over the call)"""
+    from . import _fr_array, lh_fr
+    arrays = [_fr_array(i) for i in instances]
+    return (C.POINTER(lh_fr) * max(len(instances), 1))(*[C.cast(a, C.POINTER(lh_fr)) for a in arrays]), arrays
+
+
 def lookup_constraints(info, beta, gamma):
     """preprocessor.rs:79-109"""
     m_offset = info.num_poly() + len(info.permutation_polys())
@@ -217,7 +230,7 @@ class HyperPlonk:
         """hyperplonk.rs:164-291.  `witness_polys`: the device tables of a single-phase circuit (`synthesize(0, [])`),
         or a callable synthesize(round, challenges) -> list of MultilinearPolynomial (PlonkishCircuit::synthesize,
         backend.rs:139) which the phase loop of hyperplonk.rs:185-205 calls once per phase."""
-        from . import _check, _ptr_array, _fr_array, lh_fr, ArgumentError
+        from . import _check, _ptr_array, ArgumentError, BrakedownParam
         info, ctx = pp.info, pp.pcs.ctx
         multi = callable(witness_polys)
         if sharded and multi:
@@ -259,23 +272,20 @@ class HyperPlonk:
         prm.expression = ce
         lasso_arr = _lasso_lookups_c(info)
         prm.num_lasso_lookups, prm.lasso_lookups = len(info.lasso_lookups), lasso_arr
-        inst_arrays = [_fr_array(i) for i in instances]
-        inst = (C.POINTER(lh_fr) * max(len(instances), 1))(*[C.cast(a, C.POINTER(lh_fr)) for a in inst_arrays])
-        from . import ZeromorphProverParam, GeminiProverParam, IpaParam, HyraxParam, BrakedownParam
+        inst, inst_arrays = _instances_c(instances)
         lib = ctx.lib
         brakedown = isinstance(pp.pcs, BrakedownParam)
-        if sharded and brakedown:
+        if sharded and (brakedown or pp.pcs.suffix):
             raise NotImplementedError("the sharded prove is wired for multilinear KZG")
         if brakedown:  # (param, circuit, the commitments of the preprocess and permutation polys); the hash transcript last
             pre_c = _ptr_array([c.h.value for c in pp.preprocess_comms])
             perm_c = _ptr_array([c.h.value for c in pp.permutation_comms])
+            suffix, tail = "_brakedown", (transcript.p, C.byref(transcript.hash_io()))
             head = (ctx.h, pp.pcs.h, C.byref(prm), pre_c if pp.preprocess_comms else None,
                     perm_c if pp.permutation_comms else None)
-        if isinstance(pp.pcs, HyraxParam):  # (params, trim size, batch size)
-            head = (ctx.h, pp.pcs.params.h, pp.pcs.poly_size, pp.pcs.batch_size, C.byref(prm))
-        # PCS whose param is (params, trim size): over the univariate SRS, or the IPA
-        univariate = isinstance(pp.pcs, (ZeromorphProverParam, GeminiProverParam, IpaParam))
-        gemini, ipa = isinstance(pp.pcs, GeminiProverParam), isinstance(pp.pcs, IpaParam)
+        else:  # (the PCS param as it crosses the boundary, circuit)
+            suffix, tail = pp.pcs.suffix, (transcript.p,)
+            head = (ctx.h, *pp.pcs.head(), C.byref(prm))
         if multi:
             from . import fr_from_bytes
             alive, failure = [], []
@@ -295,46 +305,19 @@ class HyperPlonk:
                     return _ffi.LH_ERR_INVALID_SNARK
             circ = _ffi.lh_hp_circuit()
             circ.user, circ.synthesize = None, _ffi._SYNTH_CB(synth)
-            nph = len(info.num_witness_polys)
-            nw = (C.c_size_t * max(nph, 1))(*info.num_witness_polys)
-            nc = (C.c_size_t * max(nph, 1))(*info.num_challenges)
-            if brakedown:
-                rc = lib.lh_hyperplonk_prove_phases_brakedown(*head, nph, nw, nc, inst, C.byref(circ), transcript.p,
-                                                              C.byref(transcript.hash_io()))
-            elif isinstance(pp.pcs, HyraxParam):
-                rc = lib.lh_hyperplonk_prove_phases_hyrax(*head, nph, nw, nc, inst, C.byref(circ), transcript.p)
-            elif univariate:
-                fn = lib.lh_hyperplonk_prove_phases_ipa if ipa else \
-                    lib.lh_hyperplonk_prove_phases_gemini if gemini else lib.lh_hyperplonk_prove_phases_zeromorph
-                rc = fn(ctx.h, pp.pcs.params.h, pp.pcs.poly_size, C.byref(prm), nph, nw, nc, inst, C.byref(circ), transcript.p)
-            else:
-                rc = ctx.lib.lh_hyperplonk_prove_phases(ctx.h, pp.pcs.h, C.byref(prm), nph, nw, nc, inst, C.byref(circ),
-                                                        transcript.p)
+            rc = getattr(lib, "lh_hyperplonk_prove_phases" + suffix)(*head, *_phases_c(info), inst, C.byref(circ), *tail)
             if failure:
                 raise failure[0]
             _check(rc)
             return
         wit = _ptr_array(witness_polys)
-        if sharded:
-            if univariate:
-                raise NotImplementedError("the sharded prove is wired for multilinear KZG")
-            _check(ctx.lib.lh_hyperplonk_prove_sharded(ctx.h, pp.pcs.h, C.byref(prm), inst, wit, transcript.p))
-            return
-        if brakedown:
-            _check(lib.lh_hyperplonk_prove_brakedown(*head, inst, wit, transcript.p, C.byref(transcript.hash_io())))
-        elif isinstance(pp.pcs, HyraxParam):
-            _check(lib.lh_hyperplonk_prove_hyrax(*head, inst, wit, transcript.p))
-        elif univariate:
-            fn = lib.lh_hyperplonk_prove_ipa if ipa else \
-                lib.lh_hyperplonk_prove_gemini if gemini else lib.lh_hyperplonk_prove_zeromorph
-            _check(fn(ctx.h, pp.pcs.params.h, pp.pcs.poly_size, C.byref(prm), inst, wit, transcript.p))
-        else:
-            _check(ctx.lib.lh_hyperplonk_prove(ctx.h, pp.pcs.h, C.byref(prm), inst, wit, transcript.p))
+        _check(getattr(lib, "lh_hyperplonk_prove" + ("_sharded" if sharded else suffix))(*head, inst, wit, *tail))
 
     @staticmethod
     def verify(vp, instances, transcript):
         """hyperplonk.rs:293-362 (host only).  Raises InvalidSumcheck / InvalidSnark / InvalidPcsOpen."""
-        from . import _check, _fr_array, _g1_array, lh_fr
+        from . import _check, _g1_array, BrakedownParam, _PointPcs
+        _points = _PointPcs._points
         info = vp.info
         if [len(i) for i in instances] != list(info.num_instances):
             raise AssertionError("instances do not match num_instances")  # assert_eq! hyperplonk.rs:300
@@ -349,43 +332,22 @@ class HyperPlonk:
         prm.expression = ce
         lasso_arr = _lasso_lookups_c(info)
         prm.num_lasso_lookups, prm.lasso_lookups = len(info.lasso_lookups), lasso_arr
-        from . import HyraxParam, BrakedownParam
-        hyrax, brakedown = isinstance(vp.pcs, HyraxParam), isinstance(vp.pcs, BrakedownParam)
-        flat = (lambda comms: [p for cm in comms for p in cm]) if hyrax else list  # (over Hyrax: num_chunks points per poly)
+        brakedown = isinstance(vp.pcs, BrakedownParam)
         prm.num_preprocess_polys, prm.num_permutation_polys = len(vp.preprocess_comms), len(vp.permutation_comms)
-        if not brakedown:
-            pre, perm = _g1_array(flat(vp.preprocess_comms)), _g1_array(flat(vp.permutation_comms))
-            prm.preprocess_comms, prm.permutation_comms = pre, perm
-        inst_arrays = [_fr_array(i) for i in instances]
-        inst = (C.POINTER(lh_fr) * max(len(instances), 1))(*[C.cast(a, C.POINTER(lh_fr)) for a in inst_arrays])
+        inst, inst_arrays = _instances_c(instances)
         if brakedown:  # (roots as arguments, the hash transcript last; the param's two point arrays stay NULL)
-            roots = (b"".join(bytes(r) for r in vp.preprocess_comms) or None,
-                     b"".join(bytes(r) for r in vp.permutation_comms) or None)
-            tail = (inst, transcript.p, C.byref(transcript.hash_io()))
-            if len(info.num_witness_polys) != 1:
-                nph = len(info.num_witness_polys)
-                nw = (C.c_size_t * max(nph, 1))(*info.num_witness_polys)
-                nc = (C.c_size_t * max(nph, 1))(*info.num_challenges)
-                _check(vp.pcs.lib.lh_hyperplonk_verify_phases_brakedown(vp.pcs.h, C.byref(prm), *roots, nph, nw, nc, *tail))
-            else:
-                _check(vp.pcs.lib.lh_hyperplonk_verify_brakedown(vp.pcs.h, C.byref(prm), *roots, *tail))
-            return
-        from . import ZeromorphVerifierParam, GeminiVerifierParam, IpaParam
-        suffix = "_zeromorph" if isinstance(vp.pcs, ZeromorphVerifierParam) else \
-            "_gemini" if isinstance(vp.pcs, GeminiVerifierParam) else "_hyrax" if hyrax else \
-            "_ipa" if isinstance(vp.pcs, IpaParam) else ""
-        # (the IPA's verifier param is its params and the trim size; Hyrax's also the batch size)
-        pcs_args = (vp.pcs.params.h, vp.pcs.poly_size, vp.pcs.batch_size) if hyrax else \
-            (vp.pcs.params.h, vp.pcs.poly_size) if isinstance(vp.pcs, IpaParam) else (vp.pcs.h,)
+            suffix, tail = "_brakedown", (inst, transcript.p, C.byref(transcript.hash_io()))
+            head = (vp.pcs.h, C.byref(prm), b"".join(bytes(r) for r in vp.preprocess_comms) or None,
+                    b"".join(bytes(r) for r in vp.permutation_comms) or None)
+        else:  # (a commitment of several points - Hyrax's rows - lies in the param's arrays point by point)
+            pre, perm = _g1_array(_points(vp.pcs, vp.preprocess_comms)), _g1_array(_points(vp.pcs, vp.permutation_comms))
+            prm.preprocess_comms, prm.permutation_comms = pre, perm
+            suffix, tail = vp.pcs.suffix, (inst, transcript.p)
+            head = (*vp.pcs.head(), C.byref(prm))
         if len(info.num_witness_polys) != 1:
-            nph = len(info.num_witness_polys)
-            nw = (C.c_size_t * max(nph, 1))(*info.num_witness_polys)
-            nc = (C.c_size_t * max(nph, 1))(*info.num_challenges)
-            fn = getattr(vp.pcs.lib, "lh_hyperplonk_verify_phases" + suffix)
-            _check(fn(*pcs_args, C.byref(prm), nph, nw, nc, inst, transcript.p))
-            return
-        fn = getattr(vp.pcs.lib, "lh_hyperplonk_verify" + suffix)
-        _check(fn(*pcs_args, C.byref(prm), inst, transcript.p))
+            _check(getattr(vp.pcs.lib, "lh_hyperplonk_verify_phases" + suffix)(*head, *_phases_c(info), *tail))
+        else:
+            _check(getattr(vp.pcs.lib, "lh_hyperplonk_verify" + suffix)(*head, *tail))
 
 
 # ------------------------------------------------------------------ the reference's sample circuits

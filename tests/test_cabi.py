@@ -161,3 +161,72 @@ def test_null_arguments_are_errors_not_crashes(hl, ctx):
     assert lib.lh_upload(h, None, None, 0) == _ffi.LH_OK
     # ... and the ctx still proves after all of that
     assert hl.MultilinearKzg.commit(pp, hl.MultilinearPolynomial(ctx, poly, 3)) is not None
+
+
+def _all_refused(lib, calls):
+    """every call returns LH_ERR_ARG at the boundary, its message naming a null argument (or the transcript)"""
+    from halo2_lasso_amd import _ffi
+    for i, call in enumerate(calls):
+        rc, msg = call(), lib.lh_last_error()
+        assert rc == _ffi.LH_ERR_ARG and (b"null argument" in msg or b"transcript" in msg), (i, rc, msg)
+
+
+def test_null_arguments_of_the_kzg_and_zeromorph_verifier_entry_points(hl):
+    """lh_lasso_verify / lh_hyperplonk_verify[_phases] over multilinear KZG and Zeromorph: each pointer in turn NULL"""
+    from halo2_lasso_amd import _ffi
+    lib = _ffi.load()
+    tbl, hvp, one = hl.LassoTable.range(2, 2).to_c(), _ffi.lh_hp_vparam(), (C.c_size_t * 1)(0)
+    t = hl.Keccak256Transcript.from_proof(b"")
+    for vp, suffix in ((hl.MultilinearKzgVerifierParams.setup([3, 5]), ""), (hl.ZeromorphVerifierParam.setup(7, 8, 8), "_zeromorph")):
+        lasso, hp, hp_phases = (getattr(lib, name + suffix) for name in
+                                ("lh_lasso_verify", "lh_hyperplonk_verify", "lh_hyperplonk_verify_phases"))
+        _all_refused(lib, [
+            lambda: lasso(None, C.byref(tbl), 2, t.p), lambda: lasso(vp.h, None, 2, t.p), lambda: lasso(vp.h, C.byref(tbl), 2, None),
+            lambda: hp(None, C.byref(hvp), None, t.p), lambda: hp(vp.h, None, None, t.p), lambda: hp(vp.h, C.byref(hvp), None, None),
+            lambda: hp_phases(None, C.byref(hvp), 1, one, one, None, t.p), lambda: hp_phases(vp.h, None, 1, one, one, None, t.p),
+            lambda: hp_phases(vp.h, C.byref(hvp), 1, None, one, None, t.p), lambda: hp_phases(vp.h, C.byref(hvp), 1, one, None, None, t.p),
+            lambda: hp_phases(vp.h, C.byref(hvp), 1, one, one, None, None)])
+
+
+@pytest.mark.gpu
+def test_null_arguments_of_the_kzg_and_zeromorph_prover_entry_points(hl, ctx):
+    """lh_lasso_prove / lh_hyperplonk_prove[_phases] over multilinear KZG (the sharded entries too) and Zeromorph: each pointer
+    in turn NULL returns at the boundary - nothing is proven - and the ctx still works"""
+    from halo2_lasso_amd import _ffi
+    lib, h = ctx.lib, ctx.h
+    srs, usrs = hl.MultilinearKzg.setup(ctx, [3, 5]), hl.Zeromorph.setup(ctx, 7, 8)
+    poly = ctx.upload(b"".join(hl.fr_to_bytes(v) for v in range(4)))
+    tbl, ptrs, one, tr = hl.LassoTable.range(2, 2).to_c(), (C.c_void_p * 1)(poly.ptr), (C.c_size_t * 1)(0), hl.Keccak256Transcript()
+    prm, prm1, circ = _ffi.lh_hp_param(), _ffi.lh_hp_param(), _ffi.lh_hp_circuit()
+    prm1.num_witness_polys = 1
+    circ.user, circ.synthesize = None, _ffi._SYNTH_CB(lambda *args: 0)
+    for head, suffix in (((srs.h,), ""), ((usrs.h, 8), "_zeromorph")):
+        none = (None,) + head[1:]
+        lasso, hp, hp_phases = (getattr(lib, name + suffix) for name in
+                                ("lh_lasso_prove", "lh_hyperplonk_prove", "lh_hyperplonk_prove_phases"))
+        _all_refused(lib, [
+            lambda: lasso(None, *head, C.byref(tbl), 2, ptrs, tr.p), lambda: lasso(h, *none, C.byref(tbl), 2, ptrs, tr.p),
+            lambda: lasso(h, *head, None, 2, ptrs, tr.p), lambda: lasso(h, *head, C.byref(tbl), 2, None, tr.p),
+            lambda: lasso(h, *head, C.byref(tbl), 2, ptrs, None),
+            lambda: hp(None, *head, C.byref(prm), None, None, tr.p), lambda: hp(h, *none, C.byref(prm), None, None, tr.p),
+            lambda: hp(h, *head, None, None, None, tr.p), lambda: hp(h, *head, C.byref(prm1), None, None, tr.p),
+            lambda: hp(h, *head, C.byref(prm), None, None, None),
+            lambda: hp_phases(None, *head, C.byref(prm), 1, one, one, None, C.byref(circ), tr.p),
+            lambda: hp_phases(h, *none, C.byref(prm), 1, one, one, None, C.byref(circ), tr.p),
+            lambda: hp_phases(h, *head, None, 1, one, one, None, C.byref(circ), tr.p),
+            lambda: hp_phases(h, *head, C.byref(prm), 1, one, one, None, None, tr.p),
+            lambda: hp_phases(h, *head, C.byref(prm), 1, None, one, None, C.byref(circ), tr.p),
+            lambda: hp_phases(h, *head, C.byref(prm), 1, one, None, None, C.byref(circ), tr.p),
+            lambda: hp_phases(h, *head, C.byref(prm), 1, one, one, None, C.byref(circ), None)])
+    _all_refused(lib, [
+        lambda: lib.lh_lasso_prove_sharded(None, srs.h, C.byref(tbl), 2, ptrs, tr.p),
+        lambda: lib.lh_lasso_prove_sharded(h, None, C.byref(tbl), 2, ptrs, tr.p),
+        lambda: lib.lh_lasso_prove_sharded(h, srs.h, None, 2, ptrs, tr.p),
+        lambda: lib.lh_lasso_prove_sharded(h, srs.h, C.byref(tbl), 2, None, tr.p),
+        lambda: lib.lh_lasso_prove_sharded(h, srs.h, C.byref(tbl), 2, ptrs, None),
+        lambda: lib.lh_hyperplonk_prove_sharded(None, srs.h, C.byref(prm), None, None, tr.p),
+        lambda: lib.lh_hyperplonk_prove_sharded(h, None, C.byref(prm), None, None, tr.p),
+        lambda: lib.lh_hyperplonk_prove_sharded(h, srs.h, None, None, None, tr.p),
+        lambda: lib.lh_hyperplonk_prove_sharded(h, srs.h, C.byref(prm1), None, None, tr.p)])
+    assert tr.into_proof() == b""
+    assert hl.MultilinearKzg.commit(srs, hl.MultilinearPolynomial(ctx, poly, 2)) is not None
