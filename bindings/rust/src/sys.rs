@@ -454,6 +454,9 @@ extern "C" {
                                out: *mut *mut c_void) -> lh_status;
     pub fn lh_brakedown_batch_commit(ctx: *mut lh_ctx, pp: *const c_void, d_polys: *const *const Fr, num_polys: usize,
                                      num_vars: usize, out: *mut *mut c_void) -> lh_status;
+    /// kinds: 0 = Fr (Montgomery), 1 = u32; column i is lens[i] <= 2^num_vars entries, committed zero-padded
+    pub fn lh_brakedown_commit_columns(ctx: *mut lh_ctx, pp: *const c_void, d_cols: *const *const c_void, kinds: *const c_int,
+                                       lens: *const usize, num_cols: usize, out: *mut *mut c_void) -> lh_status;
     pub fn lh_brakedown_comm_root(comm: *const c_void, out32: *mut u8) -> lh_status;
     pub fn lh_brakedown_comm_rows(ctx: *mut lh_ctx, comm: *const c_void, out: *mut Fr) -> lh_status;
     pub fn lh_brakedown_comm_rows_device(comm: *const c_void, d_out: *mut *mut Fr) -> lh_status;
@@ -493,4 +496,8 @@ extern "C" {
                                                  num_witness_polys: *const usize, num_challenges: *const usize,
                                                  instances: *const *const Fr, t: *mut lh_transcript,
                                                  ht: *mut lh_hash_transcript) -> lh_status;
+    pub fn lh_lasso_prove_brakedown(ctx: *mut lh_ctx, param: *const c_void, table: *const lh_lasso_table, num_vars: usize,
+                                    d_dims: *const *const u32, t: *mut lh_transcript, ht: *mut lh_hash_transcript) -> lh_status;
+    pub fn lh_lasso_verify_brakedown(param: *const c_void, table: *const lh_lasso_table, num_vars: usize, t: *mut lh_transcript,
+                                     ht: *mut lh_hash_transcript) -> lh_status;
 }

@@ -764,6 +764,12 @@ def mkzg_batch_verify(vp, num_vars, comms, points, evals, transcript):
                                        _evaluations(evals), len(evals), transcript.p))
 
 
+def _tail(param, transcript):
+    """the arguments a scheme's Lasso entries take behind the transcript (BrakedownParam.tail); most take none"""
+    tail = getattr(param, "tail", None)
+    return tail(transcript) if tail else ()
+
+
 def sum_check_verify(prover, num_vars, degree, sum_, transcript):
     """ClassicSumCheck::<P>::verify (classic.rs:242-272) -> (final claim, challenges)"""
     ev, ch = lh_fr(), (lh_fr * max(num_vars, 1))()
@@ -774,7 +780,8 @@ def sum_check_verify(prover, num_vars, degree, sum_, transcript):
 def lasso_verify(vp, table, num_vars, transcript):
     """Verifier of the Lasso argument (oracle/pyref/lasso.py:219-261).  A Keccak256Transcript must be fully consumed."""
     t = table.to_c()
-    _check(getattr(vp.lib, "lh_lasso_verify" + vp.suffix)(*vp.head(), C.byref(t), num_vars, transcript.p))
+    _check(getattr(vp.lib, "lh_lasso_verify" + vp.suffix)(*vp.head(), C.byref(t), num_vars, transcript.p,
+                                                          *_tail(vp, transcript)))
     if isinstance(transcript, Keccak256Transcript) and transcript.remaining():
         raise InvalidSnark("trailing bytes in proof")
 
@@ -1204,6 +1211,8 @@ class BrakedownParam:
     from a 32-byte seed (DESIGN.md §12).  Set up with a Context the matrices are also on its device (prover param);
     it is its own prover and verifier param, as in the reference."""
 
+    suffix = "_brakedown"  # of the lh_lasso_* entries over this scheme
+
     def __init__(self, ctx, handle, num_vars, spec):
         self.ctx, self.h, self.num_vars, self.spec = ctx, handle, num_vars, spec
         self.lib = _ffi.load()
@@ -1214,6 +1223,14 @@ class BrakedownParam:
 
     def info(self):
         return (self.row_len, self.num_rows, self.codeword_len, self.num_column_opening, self.num_proximity_testing)
+
+    def head(self):
+        return (self.h,)
+
+    @staticmethod
+    def tail(transcript):
+        """what the entries over this scheme take behind the transcript: its hash half (roots and Merkle paths)"""
+        return (C.byref(transcript.hash_io()),)
 
     def encode(self, msg):
         """LinearCodes::encode on the host (util/code/brakedown.rs:88-125): row_len values -> codeword_len values"""
@@ -1322,6 +1339,20 @@ class Brakedown:
         return [BrakedownCommitment(pp.ctx, C.c_void_p(out[i])) for i in range(len(polys))]
 
     @staticmethod
+    def commit_columns(pp, cols):
+        """cols: (device pointer, kind, len) per column, kind "u32" or "fr"; each committed as the table zero-padded to
+        pp.num_vars variables (lh_brakedown_commit_columns)"""
+        if not cols:
+            return []
+        n = len(cols)
+        ptrs = (C.c_void_p * n)(*[p for p, _, _ in cols])
+        kinds = (C.c_int * n)(*[{"fr": _ffi.LH_BD_COLUMN_FR, "u32": _ffi.LH_BD_COLUMN_U32}[k] for _, k, _ in cols])
+        lens = (C.c_size_t * n)(*[ln for _, _, ln in cols])
+        out = (C.c_void_p * n)()
+        _check(pp.lib.lh_brakedown_commit_columns(pp.ctx.h, pp.h, ptrs, kinds, lens, n, out))
+        return [BrakedownCommitment(pp.ctx, C.c_void_p(out[i])) for i in range(n)]
+
+    @staticmethod
     def commit(pp, poly):
         out = C.c_void_p()
         _check(pp.lib.lh_brakedown_commit(pp.ctx.h, pp.h, poly.ptr, poly.num_vars, C.byref(out)))
@@ -1410,7 +1441,7 @@ def lasso_prove(pp, table, num_vars, dims, transcript):
         raise ArgumentError("table too large")
     t = table.to_c()
     _check(getattr(pp.ctx.lib, "lh_lasso_prove" + pp.suffix)(pp.ctx.h, *pp.head(), C.byref(t), num_vars, _ptr_array(dims),
-                                                             transcript.p))
+                                                             transcript.p, *_tail(pp, transcript)))
 
 
 def attach_comm(ctx, rank, size, all_gather, shard_bit):

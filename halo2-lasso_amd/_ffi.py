@@ -16,6 +16,7 @@ LH_SC_EVALUATIONS, LH_SC_COEFFICIENTS = 0, 1
 LH_SC_MAX_TERMS, LH_SC_MAX_FACTORS = 48, 4
 LH_LASSO_MAX_CHUNKS, LH_LASSO_MAX_MEMORIES, LH_LASSO_MAX_TERMS = 8, 16, 16
 LH_LASSO_NUM_PHASES = 9
+LH_BD_COLUMN_FR, LH_BD_COLUMN_U32 = 0, 1
 
 
 class lh_fr(C.Structure):
@@ -317,6 +318,7 @@ SIGNATURES = {
     "lh_brakedown_encode": (C.c_int, [_P, C.POINTER(lh_fr), C.POINTER(lh_fr)]),
     "lh_brakedown_commit": (C.c_int, [_P, _P, _P, _SZ, C.POINTER(_P)]),
     "lh_brakedown_batch_commit": (C.c_int, [_P, _P, C.POINTER(_P), _SZ, _SZ, C.POINTER(_P)]),
+    "lh_brakedown_commit_columns": (C.c_int, [_P, _P, C.POINTER(_P), C.POINTER(C.c_int), C.POINTER(_SZ), _SZ, C.POINTER(_P)]),
     "lh_brakedown_comm_root": (C.c_int, [_P, C.c_char_p]),
     "lh_brakedown_comm_rows": (C.c_int, [_P, _P, _P]),
     "lh_brakedown_comm_rows_device": (C.c_int, [_P, C.POINTER(_P)]),
@@ -359,6 +361,7 @@ _PCS_HEADS = {  # suffix -> (prover param, verifier param)
     "_hyrax": ([_P, _SZ, _SZ], [_P, _SZ, _SZ]),
 }
 _T, _INSTANCES, _PHASES = C.POINTER(lh_transcript), C.POINTER(C.POINTER(lh_fr)), [_SZ, C.POINTER(_SZ), C.POINTER(_SZ)]
+_HT = C.POINTER(lh_hash_transcript)  # Brakedown's entries end in it: roots and Merkle paths are no field elements
 _PROVE_TAILS = {
     "lh_lasso_prove": [C.POINTER(lh_lasso_table), _SZ, C.POINTER(_P), _T],
     "lh_hyperplonk_prove": [C.POINTER(lh_hp_param), _INSTANCES, C.POINTER(_P), _T],
@@ -374,6 +377,10 @@ for _suffix, (_prover, _verifier) in _PCS_HEADS.items():
         SIGNATURES[_kind + _suffix] = (C.c_int, [_P] + _prover + _tail)
     for _kind, _tail in _VERIFY_TAILS.items():
         SIGNATURES[_kind + _suffix] = (C.c_int, _verifier + _tail)
+
+# Lasso over Brakedown: the same tails behind the param, the hash transcript behind them
+SIGNATURES["lh_lasso_prove_brakedown"] = (C.c_int, [_P, _P] + _PROVE_TAILS["lh_lasso_prove"] + [_HT])
+SIGNATURES["lh_lasso_verify_brakedown"] = (C.c_int, [_P] + _VERIFY_TAILS["lh_lasso_verify"] + [_HT])
 
 _lib = None
 

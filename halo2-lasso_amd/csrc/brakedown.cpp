@@ -270,11 +270,12 @@ static void check_vars(const BdParam& p, size_t num_vars, const char* what) {
 }
 
 // the cascade over `R` rows that hold their messages: a[k] forward, the Reed-Solomon tail, b[k] in reverse
-static void encode_rows(Ctx& c, const BdParam& p, Fr* rows, size_t R) {
+// (`first_done`: a[0]'s outputs are already there - the column commit's u32 gather)
+static void encode_rows(Ctx& c, const BdParam& p, Fr* rows, size_t R, bool first_done = false) {
   const size_t cw = p.codeword_len;
   size_t in_off = 0;
   for (size_t k = 0; k + 1 < p.a.size(); k++) {
-    k_bd_gather(c, rows, R, cw, in_off, in_off + p.a[k].dim.n, p.a[k]);
+    if (k || !first_done) k_bd_gather(c, rows, R, cw, in_off, in_off + p.a[k].dim.n, p.a[k]);
     in_off += p.a[k].dim.n;
   }
   const BdMatrix &al = p.a.back(), &bl = p.b.back();
@@ -319,6 +320,8 @@ static size_t batch_rows_bytes(const BdParam& p, size_t P) {
   return (P * p.num_rows * p.codeword_len * sizeof(Fr) + 255) & ~(size_t)255;
 }
 static size_t batch_tree_words(const BdParam& p) { return 4 * (((size_t)2 << p.depth) - 1); }
+static std::vector<std::unique_ptr<BdComm>> batch_trees(Ctx& c, const BdParam& p, size_t P, Fr* rows, uint64_t* trees,
+                                                        uint64_t* d_roots, const std::shared_ptr<void>& owner);
 size_t brakedown_batch_bytes(const BdParam& p, size_t P) {
   return batch_rows_bytes(p, P) + ((P * batch_tree_words(p) * 8 + 255) & ~(size_t)255) + ((P * 32 + 255) & ~(size_t)255) +
          ((P * sizeof(Fr*) + 255) & ~(size_t)255);
@@ -326,11 +329,10 @@ size_t brakedown_batch_bytes(const BdParam& p, size_t P) {
 
 std::vector<std::unique_ptr<BdComm>> brakedown_batch_commit(Ctx& c, const BdParam& p, const Fr* const* d_polys, size_t P,
                                                             size_t num_vars, void* slab_mem) {
-  std::vector<std::unique_ptr<BdComm>> comms;
-  if (!P) return comms;
+  if (!P) return {};
   check_vars(p, num_vars, "commit");
   LH_REQUIRE(p.device == c.device, LH_ERR_ARG, "brakedown: parameters were not set up on this ctx's device");
-  const size_t R = p.num_rows, cw = p.codeword_len, width = (size_t)1 << p.depth, tree_words = batch_tree_words(p);
+  const size_t R = p.num_rows, cw = p.codeword_len, tree_words = batch_tree_words(p);
   std::shared_ptr<void> owner;
   if (!slab_mem) {
     const int device = c.device;
@@ -347,6 +349,14 @@ std::vector<std::unique_ptr<BdComm>> brakedown_batch_commit(Ctx& c, const BdPara
   LH_HIP(hipMemcpyAsync(d_ptrs, d_polys, P * sizeof(Fr*), hipMemcpyHostToDevice, c.stream));
   k_bd_load_rows(c, d_ptrs, P, R, p.row_len, cw, rows);
   encode_rows(c, p, rows, P * R);  // (rows are independent: the slab is P * R of them)
+  return batch_trees(c, p, P, rows, trees, d_roots, owner);
+}
+
+// the column leaves, the trees and the roots of a slab whose P * num_rows rows are encoded -> the P commitments
+static std::vector<std::unique_ptr<BdComm>> batch_trees(Ctx& c, const BdParam& p, size_t P, Fr* rows, uint64_t* trees,
+                                                        uint64_t* d_roots, const std::shared_ptr<void>& owner) {
+  const size_t R = p.num_rows, cw = p.codeword_len, width = (size_t)1 << p.depth, tree_words = batch_tree_words(p);
+  std::vector<std::unique_ptr<BdComm>> comms;
   k_bd_hash_columns_batch(c, rows, P, R, cw, width, trees, tree_words);
   size_t off = 0;
   for (size_t w = width; w > 1; w >>= 1) {
@@ -365,6 +375,52 @@ std::vector<std::unique_ptr<BdComm>> brakedown_batch_commit(Ctx& c, const BdPara
     comms.push_back(std::move(comm));
   }
   return comms;
+}
+
+// ------------------------------------------------------------------ column commit: the batch without a table per column
+// The slab of a batch, its pointer table replaced by the column table.
+size_t brakedown_columns_bytes(const BdParam& p, size_t P) {
+  return batch_rows_bytes(p, P) + ((P * batch_tree_words(p) * 8 + 255) & ~(size_t)255) + ((P * 32 + 255) & ~(size_t)255) +
+         ((P * sizeof(BdColumn) + 255) & ~(size_t)255);
+}
+
+std::vector<std::unique_ptr<BdComm>> brakedown_commit_columns(Ctx& c, const BdParam& p, const BdColumn* cols, size_t P,
+                                                              void* slab_mem) {
+  if (!P) return {};
+  LH_REQUIRE(p.device == c.device, LH_ERR_ARG, "brakedown: parameters were not set up on this ctx's device");
+  bool any_u32 = false, any_fr = false;
+  for (size_t i = 0; i < P; i++) {
+    LH_REQUIRE(cols[i].len <= ((uint64_t)1 << p.num_vars), LH_ERR_ARG, "brakedown: a column is longer than 2^num_vars");
+    LH_REQUIRE(cols[i].data || !cols[i].len, LH_ERR_ARG, "brakedown: null column");
+    (cols[i].u32 ? any_u32 : any_fr) = true;
+  }
+  const size_t R = p.num_rows, cw = p.codeword_len, tree_words = batch_tree_words(p);
+  std::shared_ptr<void> owner;
+  if (!slab_mem) {
+    const int device = c.device;
+    LH_HIP(hipMalloc(&slab_mem, brakedown_columns_bytes(p, P)));
+    owner = std::shared_ptr<void>(slab_mem, [device](void* q) {
+      (void)hipSetDevice(device);
+      (void)hipFree(q);
+    });
+  }
+  Fr* rows = (Fr*)slab_mem;
+  uint64_t* trees = (uint64_t*)((char*)slab_mem + batch_rows_bytes(p, P));
+  uint64_t* d_roots = (uint64_t*)((char*)trees + ((P * tree_words * 8 + 255) & ~(size_t)255));
+  BdColumn* d_cols = (BdColumn*)((char*)d_roots + ((P * 32 + 255) & ~(size_t)255));
+  LH_HIP(hipMemcpyAsync(d_cols, cols, P * sizeof(BdColumn), hipMemcpyHostToDevice, c.stream));
+  k_bd_load_columns(c, d_cols, P, R, p.row_len, cw, rows);
+  // a[0] of the u32 columns from their 4-byte entries (there is an a[0] outside the Reed-Solomon tail when the cascade has
+  // more than one level); the field-element columns among them keep bd_gather, a column at a time
+  const bool u32_first = c.opt.brakedown_u32_gather != 0 && any_u32 && p.a.size() > 1;
+  if (u32_first) {
+    k_bd_gather_u32(c, d_cols, P, rows, R, p.row_len, cw, p.a[0]);
+    if (any_fr)
+      for (size_t i = 0; i < P; i++)
+        if (!cols[i].u32) k_bd_gather(c, rows + i * R * cw, R, cw, 0, p.row_len, p.a[0]);
+  }
+  encode_rows(c, p, rows, P * R, u32_first);
+  return batch_trees(c, p, P, rows, trees, d_roots, owner);  // (synchronises: the caller's table has been read by then)
 }
 
 // ------------------------------------------------------------------ open (brakedown.rs:212-276)
@@ -400,6 +456,9 @@ void brakedown_open(Ctx& c, const BdParam& p, const Fr* d_poly, size_t num_vars,
   LH_REQUIRE(comm.num_rows == p.num_rows && comm.codeword_len == p.codeword_len && comm.device == c.device, LH_ERR_ARG,
              "brakedown: commitment does not belong to these parameters");
   const size_t R = p.num_rows, row_len = p.row_len, cw = p.codeword_len, k_rows = log2_ceil(R);
+  // without a table the polynomial is the message part of the commitment's rows: the same values, row stride codeword_len
+  const size_t stride = d_poly ? row_len : cw;
+  if (!d_poly) d_poly = comm.d_rows;
   ArenaScope scope(c.arena);
   std::vector<HFr> row(row_len);
   if (R > 1) {
@@ -413,7 +472,7 @@ void brakedown_open(Ctx& c, const BdParam& p, const Fr* d_poly, size_t num_vars,
       const bool last = k + 1 == p.num_proximity_testing;  // the last proximity row and the t_0 row share one pass
       LH_HIP(hipMemcpyAsync(coeffs, cs.data(), R * 32, hipMemcpyHostToDevice, c.stream));
       if (last) LH_HIP(hipMemcpyAsync(coeffs + R, t_0.data(), R * 32, hipMemcpyHostToDevice, c.stream));
-      k_bd_combine(c, d_poly, R, row_len, coeffs, last ? 2 : 1, out);
+      k_bd_combine(c, d_poly, R, row_len, stride, coeffs, last ? 2 : 1, out);
       c.d2h(both.data(), out, (last ? 2 : 1) * row_len * 32);
       tr.write_field_elements(std::vector<HFr>(both.begin(), both.begin() + row_len));
     }
@@ -455,7 +514,7 @@ void brakedown_open(Ctx& c, const BdParam& p, const Fr* d_poly, size_t num_vars,
 // ------------------------------------------------------------------ the provers' PCS (backend/hyperplonk.rs:76-95)
 namespace {
 struct BdStore {
-  std::map<const Fr*, BdComm*> by_poly;
+  std::map<const void*, BdComm*> by_poly;  // (a table's pointer, or a u32 column's)
   std::vector<std::unique_ptr<BdComm>> own;  // (views into arena slabs of the proof's scope: nothing to free on the device)
   BdStage stage;
 };
@@ -479,15 +538,44 @@ Pcs brakedown_pcs(Ctx& c, const BdParam& p, HashTranscript& ht, const std::vecto
       store->own.push_back(std::move(comms[i]));
     }
   };
+  pcs.commit_columns_and_write = [&c, &p, &ht, store](const PcsColumn* cols, size_t nc, size_t nv, Transcript&) {
+    check_vars(p, nv, "commit");
+    std::vector<BdColumn> uniq;  // (a column handed over twice - E of an identity subtable is dim - is committed once)
+    std::vector<size_t> slot(nc);
+    for (size_t i = 0; i < nc; i++) {
+      LH_REQUIRE(cols[i].data, LH_ERR_ARG, "brakedown commit_columns: null column");
+      size_t k = 0;
+      while (k < uniq.size() && uniq[k].data != cols[i].data) k++;
+      if (k == uniq.size()) uniq.push_back(BdColumn{cols[i].data, cols[i].len, cols[i].u32 ? 1u : 0u, 0});
+      LH_REQUIRE(uniq[k].len == cols[i].len, LH_ERR_ARG, "brakedown commit_columns: one column under two lengths");
+      slot[i] = k;
+    }
+    if (uniq.empty()) return;
+    void* slab = c.arena.alloc(brakedown_columns_bytes(p, uniq.size()));  // released with the prove's ArenaScope
+    std::vector<std::unique_ptr<BdComm>> comms = brakedown_commit_columns(c, p, uniq.data(), uniq.size(), slab);
+    for (size_t i = 0; i < nc; i++) ht.write_hash(comms[slot[i]]->root);
+    for (size_t k = 0; k < uniq.size(); k++) {
+      store->by_poly[uniq[k].data] = comms[k].get();
+      store->own.push_back(std::move(comms[k]));
+    }
+  };
   pcs.batch_open = [&c, &p, &ht, store](size_t nv, const Fr* const* polys, size_t np, const HFr* points, size_t npts,
-                                        const lh_evaluation* evals, size_t ne, Transcript& tr, const SmallPoly*) {
-    for (size_t i = 0; i < ne; i++) {  // (poly-major: a poly queried at several points is staged once)
+                                        const lh_evaluation* evals, size_t ne, Transcript& tr, const SmallPoly* small) {
+    // (the stage holds ONE matrix, the last commitment's: HyperPlonk's evaluations come poly-major, so a poly queried at
+    // several points is staged once; Lasso's _evals order - a, E at r_z, dim, read_ts, E at r_N, final_cts - comes back to
+    // every E, and under an identity subtable to every dim, so those matrices are staged again: 1 + 3 c + 2 alpha stagings
+    // for 1 + 3 c + alpha commitments or fewer.  A stage per commitment would pin all of a proof's matrices at once.)
+    for (size_t i = 0; i < ne; i++) {
       const lh_evaluation& e = evals[i];
-      LH_REQUIRE(e.poly < np && e.point < npts && polys[e.poly], LH_ERR_ARG, "brakedown batch_open: evaluation out of range");
-      auto it = store->by_poly.find(polys[e.poly]);
+      LH_REQUIRE(e.poly < np && e.point < npts, LH_ERR_ARG, "brakedown batch_open: evaluation out of range");
+      // a poly that came as a u32 column was committed under the column's pointer and has no table to combine from
+      const bool by_column = small && small[e.poly].ptr && store->by_poly.count(small[e.poly].ptr);
+      LH_REQUIRE(by_column || polys[e.poly], LH_ERR_ARG, "brakedown batch_open: evaluation out of range");
+      auto it = store->by_poly.find(by_column ? (const void*)small[e.poly].ptr : (const void*)polys[e.poly]);
       LH_REQUIRE(it != store->by_poly.end(), LH_ERR_ARG, "brakedown batch_open: no commitment for an opened poly");
       brakedown_stage(c, p, *it->second, store->stage);
-      brakedown_open(c, p, polys[e.poly], nv, *it->second, points + (size_t)e.point * nv, tr, ht, &store->stage);
+      brakedown_open(c, p, by_column ? nullptr : polys[e.poly], nv, *it->second, points + (size_t)e.point * nv, tr, ht,
+                     &store->stage);
     }
   };
   return pcs;
@@ -516,6 +604,19 @@ void brakedown_hyperplonk_prove_phases(Ctx& c, const BdParam& p, const lh_hp_par
   }
   const Pcs pcs = brakedown_pcs(c, p, ht, given);  // (dies with this frame, also when the prove throws)
   hyperplonk_prove_phases(c, pcs, pp, ph, instances, tr);
+}
+
+void brakedown_lasso_prove(Ctx& c, const BdParam& p, const lh_lasso_table& tb, size_t num_vars, const uint32_t* const* d_dims,
+                           Transcript& tr, HashTranscript& ht) {
+  lasso_check_table(tb);
+  LH_REQUIRE(!Shard(c).on, LH_ERR_ARG, "lasso over brakedown: sharded proves are not supported");
+  LH_REQUIRE(p.num_vars == std::max<size_t>(num_vars, tb.chunk_bits), LH_ERR_ARG,
+             "lasso over brakedown: the columns have max(num_vars, chunk_bits) = " +
+                 std::to_string(std::max<size_t>(num_vars, tb.chunk_bits)) + " variables, the param " +
+                 std::to_string(p.num_vars));
+  LH_REQUIRE(p.device == c.device, LH_ERR_ARG, "brakedown: parameters were not set up on this ctx's device");
+  const Pcs pcs = brakedown_pcs(c, p, ht, {});  // (dies with this frame, also when the prove throws)
+  lasso_prove(c, pcs, tb, num_vars, d_dims, tr);
 }
 
 }  // namespace lh

@@ -88,6 +88,22 @@ BdComm* brakedown_commit(Ctx& c, const BdParam& p, const Fr* d_poly, size_t num_
 size_t brakedown_batch_bytes(const BdParam& p, size_t num_polys);
 std::vector<std::unique_ptr<BdComm>> brakedown_batch_commit(Ctx& c, const BdParam& p, const Fr* const* d_polys,
                                                             size_t num_polys, size_t num_vars, void* slab = nullptr);
+// A column of a column commit (brakedown_commit_columns): `len` <= 2^num_vars entries on the device, Fr (Montgomery) or u32,
+// committed as the table zero-padded to num_vars variables.  The kernels read this table from device memory.
+struct BdColumn {
+  const void* data;  // may be null when len == 0
+  uint64_t len;
+  uint32_t u32;  // 1: 4-byte integers, 0: field elements
+  uint32_t reserved;
+};
+// The commits of brakedown_batch_commit without a field-element table per column: the load converts u32 entries to
+// Montgomery form and zero-fills from `len` on, and under option brakedown_u32_gather the first encoder stage of the u32
+// columns reads the 4-byte entries themselves (kernels_brakedown.hip bd_gather_u32).  Rows, trees and roots are
+// bit-identical to brakedown_batch_commit of the zero-padded tables.  `slab` as there, of brakedown_columns_bytes.
+size_t brakedown_columns_bytes(const BdParam& p, size_t num_cols);
+std::vector<std::unique_ptr<BdComm>> brakedown_commit_columns(Ctx& c, const BdParam& p, const BdColumn* cols,
+                                                              size_t num_cols, void* slab = nullptr);
+// `d_poly` null: the polynomial is read from the commitment's own rows (the first row_len entries of each row).
 // `staged` (optional): the commitment's matrix on the host (brakedown_stage): the column openings read it instead of
 // fetching every column from the device; the bytes written are the same
 void brakedown_open(Ctx& c, const BdParam& p, const Fr* d_poly, size_t num_vars, BdComm& comm, const HFr* point,
@@ -102,6 +118,9 @@ void brakedown_verify(const BdParam& p, const uint8_t root[32], const HFr* point
 // batch_open is one open per evaluation in order (brakedown.rs:278-300), the commitment of a poly found by its device
 // pointer - the ones made here, or `given` (the preprocess and permutation polys, committed once by the caller) - and its
 // columns read from the staged matrix.  What the proof committed, and the pinned staging, go with the returned object.
+// commit_columns_and_write (Lasso) commits a proof's columns as ONE batch into one arena slab (brakedown_commit_columns;
+// columns that share a data pointer once), writes a root per column and keeps the commitments under the columns' device
+// pointers: batch_open looks a poly up by its SmallPoly pointer first and then combines from the commitment's own rows.
 struct BdGiven {
   const Fr* d_poly;
   BdComm* comm;
@@ -111,6 +130,12 @@ Pcs brakedown_pcs(Ctx& c, const BdParam& p, HashTranscript& ht, const std::vecto
 void brakedown_hyperplonk_prove_phases(Ctx& c, const BdParam& p, const lh_hp_param& pp, BdComm* const* preprocess_comms,
                                        BdComm* const* permutation_comms, const HpPhases& ph, const HFr* const* instances,
                                        Transcript& tr, HashTranscript& ht);
+// Lasso over Brakedown (DESIGN.md §12 "Provers"): oracle/pyref/lasso.py prove / verify with the roots written by write_hash.
+// Refuses (LH_ERR_ARG) a param whose num_vars is not max(num_vars, chunk_bits) and a ctx inside a sharded prove.
+void brakedown_lasso_prove(Ctx& c, const BdParam& p, const lh_lasso_table& table, size_t num_vars,
+                           const uint32_t* const* d_dims, Transcript& tr, HashTranscript& ht);
+void brakedown_lasso_verify(const BdParam& p, const lh_lasso_table& table, size_t num_vars, Transcript& tr,
+                            HashTranscript& ht);  // verifier.cpp
 // verifier.cpp: the roots of the witness, m, h and z polys read with read_hash, the preprocess and permutation roots from
 // the caller (vp's two lh_g1 arrays are ignored), brakedown_verify once per evaluation
 void brakedown_hyperplonk_verify_phases(const BdParam& p, const lh_hp_vparam& vp, const uint8_t* preprocess_roots,
@@ -130,6 +155,12 @@ void k_bd_merkle_level_batch(Ctx&, uint64_t* trees, size_t num_polys, size_t tre
                              size_t out_off);
 void k_bd_gather_roots(Ctx&, const uint64_t* trees, size_t num_polys, size_t tree_stride, size_t root_off, uint64_t* out);
 void k_bd_stage_columns(Ctx&, const Fr* rows, size_t num_rows, size_t cw, Fr* out);
-void k_bd_combine(Ctx&, const Fr* poly, size_t num_rows, size_t row_len, const Fr* coeffs, int num_sets, Fr* out);
+// `stride`: entries between the rows of `poly` (row_len for a table, codeword_len for a commitment's rows)
+void k_bd_combine(Ctx&, const Fr* poly, size_t num_rows, size_t row_len, size_t stride, const Fr* coeffs, int num_sets,
+                  Fr* out);
+void k_bd_load_columns(Ctx&, const BdColumn* d_cols, size_t num_cols, size_t num_rows, size_t row_len, size_t cw, Fr* rows);
+// the first forward stage (a[0]: inputs at 0, outputs at row_len) of the u32 columns of the table; Fr columns are left alone
+void k_bd_gather_u32(Ctx&, const BdColumn* d_cols, size_t num_cols, Fr* rows, size_t num_rows, size_t row_len, size_t cw,
+                     const BdMatrix& mat);
 
 }  // namespace lh

@@ -1191,6 +1191,31 @@ lh_status lh_brakedown_batch_commit(lh_ctx* ctx, const lh_brakedown_param* pp, c
                                     size_t num_polys, size_t num_vars, lh_brakedown_comm** out) {
   return bd_commit_entry(ctx, pp, d_polys, num_polys, num_vars, out, true);
 }
+lh_status lh_brakedown_commit_columns(lh_ctx* ctx, const lh_brakedown_param* pp, const void* const* d_cols, const int* kinds,
+                                      const size_t* lens, size_t num_cols, lh_brakedown_comm** out) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(pp);
+  NEED_N(d_cols, num_cols);
+  NEED_N(kinds, num_cols);
+  NEED_N(lens, num_cols);
+  NEED_N(out, num_cols);
+  std::vector<BdColumn> cols(num_cols);
+  for (size_t i = 0; i < num_cols; i++) {
+    LH_REQUIRE(kinds[i] == LH_BD_COLUMN_FR || kinds[i] == LH_BD_COLUMN_U32, LH_ERR_ARG, "brakedown commit_columns: unknown kind");
+    LH_REQUIRE(d_cols[i] || !lens[i], LH_ERR_ARG, "null argument: d_cols[i]");
+    cols[i] = BdColumn{d_cols[i], lens[i], kinds[i] == LH_BD_COLUMN_U32 ? 1u : 0u, 0};
+  }
+  std::vector<std::unique_ptr<BdComm>> batch = brakedown_commit_columns(ctx->c, pp->p, cols.data(), num_cols);
+  std::vector<std::unique_ptr<lh_brakedown_comm>> comms;
+  for (size_t i = 0; i < num_cols; i++) {
+    std::unique_ptr<lh_brakedown_comm> w(new lh_brakedown_comm());
+    std::swap(w->c, *batch[i]);
+    batch[i]->device = -1;
+    comms.push_back(std::move(w));
+  }
+  for (size_t i = 0; i < num_cols; i++) out[i] = comms[i].release();
+  LH_CATCH
+}
 lh_status lh_brakedown_comm_root(const lh_brakedown_comm* comm, uint8_t* out32) {
   LH_TRY
   NEED(comm);
@@ -1384,6 +1409,34 @@ lh_status lh_hyperplonk_verify_brakedown(const lh_brakedown_param* bp, const lh_
                                                          instances, t, ht);
   return lh_hyperplonk_verify_phases_brakedown(bp, hvp, preprocess_roots, permutation_roots, 1, &hvp->num_witness_polys,
                                                &hvp->num_challenges, instances, t, ht);
+}
+
+// Lasso over Brakedown (brakedown.cpp brakedown_lasso_prove; the verifier in verifier.cpp)
+lh_status lh_lasso_prove_brakedown(lh_ctx* ctx, const lh_brakedown_param* bp, const lh_lasso_table* table, size_t num_vars,
+                                   const uint32_t* const* d_dims, lh_transcript* t, lh_hash_transcript* ht) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(bp);
+  NEED(table);
+  NEED(d_dims);
+  Transcript tr(t);
+  HashTranscript h(ht);
+  brakedown_lasso_prove(ctx->c, bp->p, *table, num_vars, d_dims, tr, h);
+  LH_CATCH
+}
+lh_status lh_lasso_verify_brakedown(const lh_brakedown_param* bp, const lh_lasso_table* table, size_t num_vars,
+                                    lh_transcript* t, lh_hash_transcript* ht) {
+  LH_TRY
+  NEED(bp);
+  NEED(table);
+  Transcript tr(t);
+  HashTranscript h(ht);
+  brakedown_lasso_verify(bp->p, *table, num_vars, tr, h);
+  lh_hash_transcript own;  // the built-in transcript knows where its stream ends (a caller's own checks that itself)
+  if (keccak_transcript_hash_io(t, &own)) {
+    const KeccakTranscript* k = (const KeccakTranscript*)t->user;
+    if (k->pos != k->stream.size()) throw Error(LH_ERR_INVALID_SNARK, "trailing bytes in proof");
+  }
+  LH_CATCH
 }
 
 lh_status lh_lasso_prove_zeromorph(lh_ctx* ctx, const lh_usrs* srs, size_t poly_size, const lh_lasso_table* table,

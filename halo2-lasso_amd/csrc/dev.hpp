@@ -154,6 +154,8 @@ struct Options {
                                        // msm_batch job per row
   int64_t brakedown_batch_commit = 1;  // lh_brakedown_batch_commit runs its polys as one batch (brakedown.cpp); 0: a commit each
   int64_t brakedown_staged_open = 0;   // lh_brakedown_batch_open reads the opened columns from the matrix staged on the host
+  int64_t brakedown_u32_gather = 1;    // a column commit runs the first encoder stage of its u32 columns from the 4-byte
+                                       // entries (kernels_brakedown.hip bd_gather_u32); 0: bd_gather on the loaded message
   Options();                           // environment defaults (dev.cpp)
   int64_t* find(const char* name);
   static bool in_range(const char* name, int64_t value);  // the range lh_ctx_set_option accepts

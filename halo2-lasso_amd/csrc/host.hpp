@@ -514,6 +514,10 @@ struct Pcs {
   std::function<void(const Fr* const* d_polys, size_t num_polys, size_t num_vars, Transcript& tr)> commit_and_write;
   // optional (schemes without commit_bases: Hyrax): commits (small-valued) columns directly -> num_cols * chunks points
   std::function<std::vector<HG1>(const PcsColumn* cols, size_t num_cols, size_t nv)> commit_columns;
+  // optional (Brakedown): commit_columns as commit_and_write is to batch_commit - commits the columns as one batch (columns
+  // that share a data pointer once), writes one commitment per column itself and keeps them; its batch_open finds a
+  // column's commitment by the column's device pointer (SmallPoly::ptr, or the table's where there is no u32 form)
+  std::function<void(const PcsColumn* cols, size_t num_cols, size_t nv, Transcript& tr)> commit_columns_and_write;
   // bases whose first 2^nv points commit a zero-padded table of 2^nv entries (the eq basis of level nv, or the powers of
   // s): the small-valued Lasso columns are committed as u32 MSMs against them.  nv <= max_vars is the caller's check
   // (LH_ERR_INVALID_PCS_PARAM, "Too many variates of poly to commit")

@@ -11,8 +11,16 @@
 //   bd_load_rows           the P messages from a pointer table into the slab's rows
 //   bd_hash_columns_batch  / bd_merkle_level_batch: the same leaves and parents, poly p's tree at p * tree_stride
 //   bd_stage_columns       the encoded matrix transposed (column-major) through LDS tiles, for the staged open
+// A batch of COLUMNS (brakedown_commit_columns: Lasso's u32 witness columns, `len` entries, zero beyond) has a table of
+// (pointer, len, kind) in device memory, blockIdx.y = column:
+//   bd_load_columns        the messages into the slab's rows: u32 entries converted to Montgomery form, Fr entries copied,
+//                          zero from `len` on (an all-padding row is a zero message and encodes to a zero row)
+//   bd_gather_u32          the first forward stage a[0] from the 4-byte entries themselves: val[e] * x as a 256 x 32-bit
+//                          product of the Montgomery-form coefficient and the plain integer, a group's sum unreduced in
+//                          ten limbs (wide.cuh), one reduction per output to the canonical Montgomery value bd_gather stores
 #include <hip/hip_runtime.h>
 #include "brakedown.hpp"
+#include "wide.cuh"
 
 namespace lh {
 
@@ -44,6 +52,45 @@ void k_bd_gather(Ctx& c, Fr* rows, size_t num_rows, size_t cw, size_t in_off, si
                (double)num_rows * m);
   hipLaunchKernelGGL(bd_gather_kernel, grid_for(num_rows * m), 256, 0, c.stream, rows, num_rows, cw, in_off, out_off, m,
                      mat.d_ptr, mat.d_idx, mat.d_val);
+}
+
+// ------------------------------------------------------------------ a[0] of u32 columns
+// bd_gather on the loaded message computes sum_e mont(x_e) * val[e] = (sum_e x_e v_e) mod r as an integer, v_e the limbs of
+// val[e] (V_e R mod r) and x_e the plain entries.  Here the integer sum itself is formed with wide.cuh's accumulator (8
+// multiply-adds per term into ten limbs: a term is below 2^32 r < 2^286 and a group has fewer than 2^32 of them - the CSR
+// index type - so the sum is below 2^318) and reduced once per output by wide_reduce, whose result is the canonical value
+// in [0, r): bit for bit what bd_gather stores.
+__global__ void bd_gather_u32_kernel(const BdColumn* __restrict__ cols, Fr* __restrict__ rows, size_t num_rows,
+                                     size_t row_len, size_t cw, size_t m, const uint32_t* __restrict__ ptr,
+                                     const uint32_t* __restrict__ idx, const Fr* __restrict__ val) {
+  const BdColumn col = cols[blockIdx.y];
+  if (!col.u32) return;  // (a field-element column keeps bd_gather)
+  const uint32_t* __restrict__ x = (const uint32_t*)col.data;
+  Fr* dst = rows + (size_t)blockIdx.y * num_rows * cw;
+  GSTRIDE(t, num_rows * m) {
+    const size_t r = t / m, j = t - r * m, base = r * row_len;
+    Wide s = Wide::zero();
+    for (uint32_t e = ptr[j], end = ptr[j + 1]; e < end; e++) {
+      const size_t k = base + idx[e];
+      if (k >= col.len) continue;  // the zero padding: nothing is read past `len`
+      wide_mac(s, val[e], x[k]);
+    }
+    dst[r * cw + row_len + j] = wide_reduce(s);
+  }
+}
+constexpr size_t BD_MAX_BATCH = 65535;  // gridDim.y
+void k_bd_gather_u32(Ctx& c, const BdColumn* d_cols, size_t num_cols, Fr* rows, size_t num_rows, size_t row_len, size_t cw,
+                     const BdMatrix& mat) {
+  const size_t m = mat.dim.m;
+  LH_REQUIRE(num_cols >= 1 && num_cols <= BD_MAX_BATCH, LH_ERR_ARG, "brakedown: too many columns in one batch");
+  LH_REQUIRE(mat.dim.n == row_len && row_len + m <= cw, LH_ERR_ARG, "brakedown: not the first stage's matrix");
+  if (!m || !num_rows) return;
+  ProfScope ps(c, "bd_gather_u32", 40.0 * num_cols * num_rows * mat.dim.n * mat.dim.d,
+               (double)num_cols * num_rows * mat.dim.n * mat.dim.d / 8, (double)num_cols * num_rows * m);
+  dim3 g = grid_for(num_rows * m);
+  g.y = (unsigned)num_cols;
+  hipLaunchKernelGGL(bd_gather_u32_kernel, g, 256, 0, c.stream, d_cols, rows, num_rows, row_len, cw, m, mat.d_ptr,
+                     mat.d_idx, mat.d_val);
 }
 
 constexpr int BD_RS_MAX = 64;  // a_last.m <= n_0 <= 20 (dimensions stop at n <= n_0)
@@ -219,7 +266,6 @@ void k_bd_merkle_level(Ctx& c, const uint64_t* in, size_t out_n, uint64_t* out) 
 }
 
 // ------------------------------------------------------------------ a batch of polys in one slab
-constexpr size_t BD_MAX_BATCH = 65535;  // gridDim.y
 __global__ void bd_load_rows_kernel(const Fr* const* __restrict__ polys, size_t num_rows, size_t row_len, size_t cw,
                                     Fr* __restrict__ rows) {
   const Fr* __restrict__ src = polys[blockIdx.y];
@@ -235,6 +281,32 @@ void k_bd_load_rows(Ctx& c, const Fr* const* d_polys, size_t num_polys, size_t n
   dim3 g = grid_for(num_rows * row_len);
   g.y = (unsigned)num_polys;
   hipLaunchKernelGGL(bd_load_rows_kernel, g, 256, 0, c.stream, d_polys, num_rows, row_len, cw, rows);
+}
+__global__ void bd_load_columns_kernel(const BdColumn* __restrict__ cols, size_t num_rows, size_t row_len, size_t cw,
+                                       Fr* __restrict__ rows) {
+  const BdColumn col = cols[blockIdx.y];
+  Fr* dst = rows + (size_t)blockIdx.y * num_rows * cw;
+  GSTRIDE(t, num_rows * row_len) {
+    const size_t r = t / row_len, j = t - r * row_len;
+    Fr v = Fr::zero();
+    if (t < col.len) {
+      if (col.u32) {
+        const uint32_t x = ((const uint32_t*)col.data)[t];
+        if (x) v = from_u64<FrParams>(x);
+      } else {
+        v = ((const Fr*)col.data)[t];
+      }
+    }
+    dst[r * cw + j] = v;
+  }
+}
+void k_bd_load_columns(Ctx& c, const BdColumn* d_cols, size_t num_cols, size_t num_rows, size_t row_len, size_t cw, Fr* rows) {
+  LH_REQUIRE(num_cols >= 1 && num_cols <= BD_MAX_BATCH, LH_ERR_ARG, "brakedown: too many columns in one batch");
+  ProfScope ps(c, "bd_load_columns", 36.0 * num_cols * num_rows * row_len, (double)num_cols * num_rows * row_len,
+               (double)num_cols * num_rows * row_len);
+  dim3 g = grid_for(num_rows * row_len);
+  g.y = (unsigned)num_cols;
+  hipLaunchKernelGGL(bd_load_columns_kernel, g, 256, 0, c.stream, d_cols, num_rows, row_len, cw, rows);
 }
 void k_bd_hash_columns_batch(Ctx& c, const Fr* rows, size_t num_polys, size_t num_rows, size_t cw, size_t width,
                              uint64_t* trees, size_t tree_stride) {
@@ -301,14 +373,14 @@ void k_bd_stage_columns(Ctx& c, const Fr* rows, size_t num_rows, size_t cw, Fr* 
 
 // ------------------------------------------------------------------ open: combined rows
 constexpr int BD_MAX_SETS = 4;
-__global__ void bd_combine_kernel(const Fr* __restrict__ poly, size_t num_rows, size_t row_len,
+__global__ void bd_combine_kernel(const Fr* __restrict__ poly, size_t num_rows, size_t row_len, size_t stride,
                                   const Fr* __restrict__ coeffs, int num_sets, Fr* __restrict__ out) {
   GSTRIDE(col, row_len) {
     Fr acc[BD_MAX_SETS];
 #pragma unroll
     for (int k = 0; k < BD_MAX_SETS; k++) acc[k] = Fr::zero();
     for (size_t r = 0; r < num_rows; r++) {
-      const Fr x = poly[r * row_len + col];
+      const Fr x = poly[r * stride + col];
 #pragma unroll
       for (int k = 0; k < BD_MAX_SETS; k++)
         if (k < num_sets) acc[k] = add(acc[k], mul(coeffs[k * num_rows + r], x));
@@ -318,11 +390,12 @@ __global__ void bd_combine_kernel(const Fr* __restrict__ poly, size_t num_rows, 
       if (k < num_sets) out[k * row_len + col] = acc[k];
   }
 }
-void k_bd_combine(Ctx& c, const Fr* poly, size_t num_rows, size_t row_len, const Fr* coeffs, int num_sets, Fr* out) {
+void k_bd_combine(Ctx& c, const Fr* poly, size_t num_rows, size_t row_len, size_t stride, const Fr* coeffs, int num_sets,
+                  Fr* out) {
   LH_REQUIRE(num_sets >= 1 && num_sets <= BD_MAX_SETS, LH_ERR_ARG, "brakedown: too many combinations in one pass");
   ProfScope ps(c, "bd_combine", 32.0 * num_rows * row_len, (double)num_sets * num_rows * row_len, (double)row_len);
-  hipLaunchKernelGGL(bd_combine_kernel, grid_for(row_len), 256, 0, c.stream, poly, num_rows, row_len, coeffs, num_sets,
-                     out);
+  hipLaunchKernelGGL(bd_combine_kernel, grid_for(row_len), 256, 0, c.stream, poly, num_rows, row_len, stride, coeffs,
+                     num_sets, out);
 }
 
 }  // namespace lh

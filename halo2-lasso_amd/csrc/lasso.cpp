@@ -487,7 +487,8 @@ void lasso_prove(Ctx& c, const Pcs& pcs, const lh_lasso_table& tb, size_t n, con
   tr.common_field_element(HFr::from_u64(l));
   tr.common_field_element(HFr::from_u64(cc));
   tr.common_field_element(HFr::from_u64(alpha));
-  if (pcs.commit_columns) {
+  Fr* a_pad = nullptr;  // the output column zero-padded to nv variables, where that table is needed (l > n, no 32-bit form)
+  if (pcs.commit_columns || pcs.commit_columns_and_write) {
     // a scheme that commits columns itself (Hyrax: vectors of row commitments): a from its 32-bit form when there is one,
     // dim / read_ts / E / final_cts as u32 columns with the bounds known here; E_i of an identity subtable IS dim_j.  The
     // derived, packed and sorted-reuse routes are msm_batch features: their counters stay 0.
@@ -506,13 +507,29 @@ void lasso_prove(Ctx& c, const Pcs& pcs, const lh_lasso_table& tb, size_t n, con
     }
     for (size_t i = 0; i < alpha; i++)
       if (tb.memory_subtable[i] != LH_SUBTABLE_IDENTITY) cols[1 + 2 * cc + i] = PcsColumn{E[i], true, N, (uint32_t)std::max<size_t>(l / 2, 1)};
-    std::vector<HG1> comms = pcs.commit_columns(cols.data(), total, nv);
-    LH_REQUIRE(comms.size() == total * k, LH_ERR_ARG, "lasso: commit_columns returned the wrong number of points");
-    for (size_t i = 0; i < alpha; i++)
-      if (tb.memory_subtable[i] == LH_SUBTABLE_IDENTITY)
-        std::copy(comms.begin() + (1 + tb.memory_chunk[i]) * k, comms.begin() + (2 + tb.memory_chunk[i]) * k,
-                  comms.begin() + (1 + 2 * cc + i) * k);
-    lasso_write_commitments(tr, comms, k);
+    if (pcs.commit_columns_and_write) {
+      // a scheme whose commitments are no points (Brakedown: Merkle roots, and the zero column's is a root like any other,
+      // so the identity mask is zero): it writes them itself and finds them again by the columns' pointers at the opening -
+      // E_i of an identity subtable under dim_j's, and a without a 32-bit form under the table the opening will be handed
+      if (!a_small && N < NV) {
+        a_pad = c.arena.alloc_n<Fr>(NV);
+        LH_HIP(hipMemcpyAsync(a_pad, a, N * sizeof(Fr), hipMemcpyDeviceToDevice, c.stream));
+        LH_HIP(hipMemsetAsync(a_pad + N, 0, (NV - N) * sizeof(Fr), c.stream));
+        cols[0] = PcsColumn{a_pad, false, NV, 0};
+      }
+      for (size_t i = 0; i < alpha; i++)
+        if (tb.memory_subtable[i] == LH_SUBTABLE_IDENTITY) cols[1 + 2 * cc + i] = cols[1 + tb.memory_chunk[i]];
+      tr.write_field_element(HFr::zero());
+      pcs.commit_columns_and_write(cols.data(), total, nv, tr);
+    } else {
+      std::vector<HG1> comms = pcs.commit_columns(cols.data(), total, nv);
+      LH_REQUIRE(comms.size() == total * k, LH_ERR_ARG, "lasso: commit_columns returned the wrong number of points");
+      for (size_t i = 0; i < alpha; i++)
+        if (tb.memory_subtable[i] == LH_SUBTABLE_IDENTITY)
+          std::copy(comms.begin() + (1 + tb.memory_chunk[i]) * k, comms.begin() + (2 + tb.memory_chunk[i]) * k,
+                    comms.begin() + (1 + 2 * cc + i) * k);
+      lasso_write_commitments(tr, comms, k);
+    }
   } else {
     // zero padding adds nothing to an MSM: commit the unpadded columns against the first entries of the bases.
     // Commitments are linear, so columns that are linear in others need no MSM of their own (same group elements,
@@ -663,10 +680,12 @@ void lasso_prove(Ctx& c, const Pcs& pcs, const lh_lasso_table& tb, size_t n, con
     }
     small[0] = SmallPoly{a_small, N, 0, &a_linear};
   } else if (N < NV) {  // l > n: the output column needs the padding too
-    Fr* ap = c.arena.alloc_n<Fr>(NV);
-    LH_HIP(hipMemcpyAsync(ap, a, N * sizeof(Fr), hipMemcpyDeviceToDevice, c.stream));
-    LH_HIP(hipMemsetAsync(ap + N, 0, (NV - N) * sizeof(Fr), c.stream));
-    polys_n[0] = ap;
+    if (!a_pad) {
+      a_pad = c.arena.alloc_n<Fr>(NV);
+      LH_HIP(hipMemcpyAsync(a_pad, a, N * sizeof(Fr), hipMemcpyDeviceToDevice, c.stream));
+      LH_HIP(hipMemsetAsync(a_pad + N, 0, (NV - N) * sizeof(Fr), c.stream));
+    }
+    polys_n[0] = a_pad;
   } else {
     polys_n[0] = a;
   }

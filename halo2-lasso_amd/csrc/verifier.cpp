@@ -1050,7 +1050,14 @@ void lasso_verify(const PcsVerifier& pcs, const lh_lasso_table& tb, size_t n, Tr
   const size_t c = tb.num_chunks, l = tb.chunk_bits, alpha = tb.num_memories;
   for (size_t v : {n, l, c, alpha}) tr.common_field_element(HFr::from_u64(v));
   const size_t nv = std::max(n, l);
-  std::vector<HG1> comms = lasso_read_commitments(tr, 1 + 3 * c + alpha, chunks);
+  std::vector<HG1> comms;
+  if (pcs.read_commitments) {
+    // commitments that are no points (Brakedown's roots): none of them can be the identity, so the mask element is zero
+    if (!tr.read_field_element().is_zero()) throw Error(LH_ERR_INVALID_SNARK, "lasso: commitment mask out of range");
+    comms = pcs.read_commitments(tr, 1 + 3 * c + alpha);
+  } else {
+    comms = lasso_read_commitments(tr, 1 + 3 * c + alpha, chunks);
+  }
   LassoClaims cl = lasso_check(tb, n, tr);
   const HFr *dim_e = &cl.ev_n[0], *rts_e = &cl.ev_n[c], *e_e = &cl.ev_n[2 * c], *fc_e = &cl.ev_l[0];
 
@@ -1134,9 +1141,38 @@ void brakedown_verify(const BdParam& p, const uint8_t root[32], const HFr* point
   if (acc != eval) throw Error(LH_ERR_INVALID_PCS_OPEN, "Consistency failure");
 }
 
-// ------------------------------------------------------------------ HyperPlonk::verify over Brakedown
-// A root travels through hyperplonk_verify_phases in the first 32 bytes of a 64-byte commitment slot; instance polys keep
-// the all-zero slot and are never queried (verifier.rs:147-154).
+// ------------------------------------------------------------------ Lasso and HyperPlonk::verify over Brakedown
+// A root travels through lasso_verify / hyperplonk_verify_phases in the first 32 bytes of a 64-byte commitment slot; instance
+// polys keep the all-zero slot and are never queried (verifier.rs:147-154).
+static PcsVerifier brakedown_verifier(const BdParam& p, HashTranscript& ht) {
+  PcsVerifier pcs;
+  pcs.batch_verify = [&p, &ht](size_t nv, const HG1* comms, size_t nc, const HFr* points, size_t np, const lh_evaluation* evals,
+                               size_t ne, Transcript& t2) {
+    for (size_t i = 0; i < ne; i++) {  // batch_verify is one verify per evaluation (brakedown.rs:398-417)
+      const lh_evaluation& e = evals[i];
+      LH_REQUIRE(e.poly < nc && e.point < np, LH_ERR_ARG, "brakedown batch_verify: evaluation out of range");
+      HFr v;
+      memcpy(&v, &e.value, 32);
+      brakedown_verify(p, (const uint8_t*)&comms[e.poly], points + (size_t)e.point * nv, nv, v, t2, ht);
+    }
+  };
+  pcs.read_commitments = [&ht](Transcript&, size_t n) {
+    std::vector<HG1> v(n);
+    if (n) memset((void*)v.data(), 0, n * sizeof(HG1));
+    for (size_t i = 0; i < n; i++) ht.read_hash((uint8_t*)&v[i]);
+    return v;
+  };
+  return pcs;
+}
+
+void brakedown_lasso_verify(const BdParam& p, const lh_lasso_table& tb, size_t n, Transcript& tr, HashTranscript& ht) {
+  lasso_verify_check_table(tb, n);
+  if (std::max<size_t>(n, tb.chunk_bits) != p.num_vars)  // (brakedown_verify's own refusal, ahead of the argument)
+    throw Error(LH_ERR_INVALID_PCS_PARAM, "Invalid poly or point to verify (param supports " + std::to_string(p.num_vars) +
+                                              " variates but got " + std::to_string(std::max<size_t>(n, tb.chunk_bits)) + ")");
+  lasso_verify(brakedown_verifier(p, ht), tb, n, tr);
+}
+
 void brakedown_hyperplonk_verify_phases(const BdParam& p, const lh_hp_vparam& vp, const uint8_t* preprocess_roots,
                                         const uint8_t* permutation_roots, const std::vector<size_t>& num_witness_polys,
                                         const std::vector<size_t>& num_challenges, const HFr* const* instances,
@@ -1156,23 +1192,7 @@ void brakedown_hyperplonk_verify_phases(const BdParam& p, const lh_hp_vparam& vp
                            perm = slots(permutation_roots, vp.num_permutation_polys);
   lh_hp_vparam v2 = vp;
   v2.preprocess_comms = pre.data(), v2.permutation_comms = perm.data();
-  PcsVerifier pcs;
-  pcs.batch_verify = [&p, &ht](size_t nv, const HG1* comms, size_t nc, const HFr* points, size_t np, const lh_evaluation* evals,
-                               size_t ne, Transcript& t2) {
-    for (size_t i = 0; i < ne; i++) {  // batch_verify is one verify per evaluation (brakedown.rs:398-417)
-      const lh_evaluation& e = evals[i];
-      LH_REQUIRE(e.poly < nc && e.point < np, LH_ERR_ARG, "brakedown batch_verify: evaluation out of range");
-      HFr v;
-      memcpy(&v, &e.value, 32);
-      brakedown_verify(p, (const uint8_t*)&comms[e.poly], points + (size_t)e.point * nv, nv, v, t2, ht);
-    }
-  };
-  pcs.read_commitments = [&ht](Transcript&, size_t n) {
-    std::vector<HG1> v(n);
-    if (n) memset((void*)v.data(), 0, n * sizeof(HG1));
-    for (size_t i = 0; i < n; i++) ht.read_hash((uint8_t*)&v[i]);
-    return v;
-  };
+  const PcsVerifier pcs = brakedown_verifier(p, ht);
   hyperplonk_verify_phases(pcs, v2, num_witness_polys, num_challenges, instances, tr);
 }
 

@@ -290,7 +290,11 @@ lh_status lh_lasso_last_timing(lh_ctx*, double* out_ms);
  *                             0: one commit per poly
  *   brakedown_staged_open 0   lh_brakedown_batch_open stages the encoded matrix of a commitment on the host once (kernel
  *                             bd_stage_columns + one copy) and reads the opened columns there; 0: one device-to-host copy
- *                             per column.  (The HyperPlonk prover over Brakedown always stages.)
+ *                             per column.  (The HyperPlonk and Lasso provers over Brakedown always stage.)
+ *   brakedown_u32_gather 1    a column commit (lh_brakedown_commit_columns, the Lasso prover over Brakedown) runs the first
+ *                             encoder stage of its u32 columns from the 4-byte entries themselves (kernel bd_gather_u32: 256 x
+ *                             32-bit products, a group's sum unreduced, one reduction per output); 0: the generic bd_gather
+ *                             on the message as loaded in Montgomery form.  Rows, trees and roots are bit-identical.
  *   comm_round           0    how the partial sums of a sharded sum-check round are combined over the ranks:
  *                             0 = ncclAllGather of every rank's sums + a one-thread sum-and-publish kernel;
  *                             1 = ONE collective: the round kernel leaves its sums as u64 lanes (32-bit limb | tag << 40),
@@ -691,6 +695,15 @@ lh_status lh_brakedown_commit(lh_ctx*, const lh_brakedown_param*, const lh_fr* d
                               lh_brakedown_comm** out);
 lh_status lh_brakedown_batch_commit(lh_ctx*, const lh_brakedown_param*, const lh_fr* const* d_polys, size_t num_polys,
                                     size_t num_vars, lh_brakedown_comm** out);
+/* The commits of lh_brakedown_batch_commit of columns that are shorter than 2^num_vars or hold 32-bit integers, without a
+ * field-element table per column: column i is lens[i] <= 2^num_vars entries on the device (d_cols[i] may be NULL when
+ * lens[i] == 0), lh_fr in Montgomery form (LH_BD_COLUMN_FR) or uint32_t (LH_BD_COLUMN_U32), and is committed as the table
+ * zero-padded to the param's num_vars.  Rows, trees and roots are bit-identical to lh_brakedown_batch_commit of those tables
+ * (both values of option brakedown_u32_gather); one device allocation that the last commitment of the set frees. */
+#define LH_BD_COLUMN_FR 0
+#define LH_BD_COLUMN_U32 1
+lh_status lh_brakedown_commit_columns(lh_ctx*, const lh_brakedown_param*, const void* const* d_cols, const int* kinds,
+                                      const size_t* lens, size_t num_cols, lh_brakedown_comm** out);
 lh_status lh_brakedown_comm_root(const lh_brakedown_comm*, uint8_t* out32); /* AsRef<[Output<H>]> (brakedown.rs:83-87) */
 /* MultilinearBrakedownCommitment::rows (brakedown.rs:70-72): num_rows x codeword_len, row-major, a download */
 lh_status lh_brakedown_comm_rows(lh_ctx*, const lh_brakedown_comm*, lh_fr* out);
@@ -751,6 +764,21 @@ lh_status lh_hyperplonk_verify_phases_brakedown(const lh_brakedown_param*, const
                                                 size_t num_phases, const size_t* num_witness_polys,
                                                 const size_t* num_challenges, const lh_fr* const* instances, lh_transcript* t,
                                                 lh_hash_transcript* ht);
+/* Lasso over Brakedown: the arguments of lh_lasso_prove_zeromorph / lh_lasso_verify_zeromorph with the param in place of
+ * the SRS, and the hash transcript.  The schedule is oracle/pyref/lasso.py's over this scheme: the mask element of the
+ * commitment framing (always zero: the root of a zero column is a root like any other), then the 1 + 3 c + alpha roots
+ * a | dim | read_ts | E | final_cts through `ht` (E_i of an identity subtable is dim_j: committed once, its root written
+ * twice), the argument, and one open per evaluation (1 + 3 c + 2 alpha of them) over the staged matrix.  The columns are
+ * committed as ONE batch from their 32-bit forms (lh_brakedown_commit_columns) into the ctx's arena, released when the prove
+ * returns; the openings combine from the commitments' own rows.  The param must be set up for exactly max(num_vars,
+ * chunk_bits) variables: LH_ERR_ARG otherwise, and for a ctx inside a sharded prove.  The verifier is host only: a mask
+ * other than zero is LH_ERR_INVALID_SNARK ("lasso: commitment mask out of range"), a param of another size
+ * LH_ERR_INVALID_PCS_PARAM, then lasso_verify's and lh_brakedown_verify's errors, and bytes left in a built-in
+ * Keccak256 transcript LH_ERR_INVALID_SNARK ("trailing bytes in proof"). */
+lh_status lh_lasso_prove_brakedown(lh_ctx*, const lh_brakedown_param*, const lh_lasso_table* table, size_t num_vars,
+                                   const uint32_t* const* d_dims, lh_transcript* t, lh_hash_transcript* ht);
+lh_status lh_lasso_verify_brakedown(const lh_brakedown_param*, const lh_lasso_table* table, size_t num_vars, lh_transcript* t,
+                                    lh_hash_transcript* ht);
 
 /* ---------------------------------------------------------------- f5: the multilinear IPA (transparent AND additive)
  * PolynomialCommitmentScheme for MultilinearIpa<bn256::G1Affine> (pcs/multilinear/ipa.rs:23-337): no trusted setup, no
