@@ -207,7 +207,8 @@ pub struct lh_lasso_route {
     pub pp_folds: u32,
     pub msm_half_batches: u32,
     pub open_shared_sums: u32,
-    pub reserved: [u32; 6],
+    pub open_precommit_staged: u32,
+    pub reserved: [u32; 5],
 }
 
 extern "C" {

@@ -1548,7 +1548,7 @@ def lasso_last_timing(ctx):
 ROUTE_FIELDS = ["open_small_depth", "open_small_passes", "eq_factored_rounds", "standard_rounds", "rw_leaf_rounds",
                 "resident_tails", "resident_rounds", "packed_ts_pairs", "derived_commitments", "sorted_dim_reuse",
                 "sharded_rounds", "shard_exchanges", "window_table_jobs", "open_precommit", "resident_layers", "pp_folds", "msm_half_batches",
-                "open_shared_sums"]
+                "open_shared_sums", "open_precommit_staged"]
 
 
 def lasso_last_route(ctx):

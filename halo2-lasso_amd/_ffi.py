@@ -307,6 +307,8 @@ SIGNATURES = {
     "lh_debug_lasso_counters": (C.c_int, [_P, C.POINTER(_P), _SZ, _SZ, _SZ, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P),
                                           C.POINTER(_P)]),
     "lh_debug_sort_plan": (C.c_int, [_SZ, C.c_uint, C.c_int, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(_SZ)]),
+    "lh_debug_msm_plan": (C.c_int, [_SZ, C.POINTER(_SZ), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_int, C.c_int,
+                                    C.POINTER(C.c_uint64), C.POINTER(_SZ)]),
     "lh_debug_u32_columns": (C.c_int, [_P, C.c_int, C.POINTER(lh_debug_u32_args)]),
     "lh_keccak_transcript_hash_io": (C.c_int, [C.POINTER(lh_transcript), C.POINTER(lh_hash_transcript)]),
     "lh_brakedown_setup": (C.c_int, [_P, _SZ, C.c_int, C.c_char_p, C.POINTER(_P)]),

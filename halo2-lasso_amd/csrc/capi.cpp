@@ -249,6 +249,8 @@ void lh_ctx_destroy(lh_ctx* ctx) {
   delete ctx->c.worker;  // (joins; after the precommit it may still be running was cancelled above)
   ctx->c.worker = nullptr;
   if (ctx->c.handoff_ev) (void)hipEventDestroy(ctx->c.handoff_ev);
+  for (hipEvent_t& ev : ctx->c.stage_ev)
+    if (ev) (void)hipEventDestroy(ev), ev = nullptr;
   if (ctx->c.aux_stream) (void)hipStreamSynchronize(ctx->c.aux_stream), (void)hipStreamDestroy(ctx->c.aux_stream);
   if (ctx->c.aux_ev) (void)hipEventDestroy(ctx->c.aux_ev);
   for (hipEvent_t& ev : ctx->c.phase_ev)
@@ -2100,6 +2102,29 @@ lh_status lh_debug_sort_plan(size_t n, unsigned bits, int key_bytes, unsigned* p
   NEED(temp_bytes);
   LH_REQUIRE(key_bytes == 4 || key_bytes == 8, LH_ERR_ARG, "debug sort: key_bytes is 4 or 8");
   sort_plan(n, bits, (size_t)key_bytes, passes, rb, temp_bytes);
+  LH_CATCH
+}
+lh_status lh_debug_msm_plan(size_t num_jobs, const size_t* n, const uint32_t* bits, const uint32_t* kinds, int helper, int via_prepare,
+                            uint64_t* out, size_t* num_subs) {
+  LH_TRY
+  NEED(n);
+  NEED(bits);
+  NEED(kinds);
+  NEED(out);
+  NEED(num_subs);
+  LH_REQUIRE(num_jobs >= 1 && num_jobs <= 48, LH_ERR_ARG, "debug msm plan: 1 .. 48 jobs");
+  Ctx c;  // (options and knobs as a ctx of this process would have them; no device behind it, and the plan asks for none)
+  c.is_helper = helper != 0;
+  std::vector<MsmJob> jobs;
+  G1Affine second;
+  for (size_t j = 0; j < num_jobs; j++) {
+    LH_REQUIRE(bits[j] >= 1 && bits[j] <= (kinds[j] ? 32u : 254u), LH_ERR_ARG, "debug msm plan: bad width");
+    MsmJob jb{nullptr, kinds[j] != 0, nullptr, n[j]};
+    jb.known_bits = bits[j];
+    if (kinds[j] >= 4) jb.pack_shift = kinds[j], jb.out_second = &second;
+    jobs.push_back(jb);
+  }
+  *num_subs = msm_plan_shape(c, jobs.data(), num_jobs, via_prepare != 0, out);
   LH_CATCH
 }
 

@@ -82,6 +82,7 @@ static const struct {
     {"sc_tail", &Options::sc_tail, 0, 1},                          {"sc_tail_max_len", &Options::sc_tail_max_len, 0, (int64_t)1 << 20},
     {"shard_exchange_log", &Options::shard_exchange_log, 0, 40},   {"msm_window_tables", &Options::msm_window_tables, 0, 40},
     {"open_precommit", &Options::open_precommit, 0, 64},           {"gkr_resident", &Options::gkr_resident, 0, 1},
+    {"open_precommit_stages", &Options::open_precommit_stages, 0, 1},
     {"sc_pp_fold", &Options::sc_pp_fold, 0, 2},                    {"msm_half_batches", &Options::msm_half_batches, 0, 1},
     {"comm_round", &Options::comm_round, 0, 2},                    {"hyrax_rows", &Options::hyrax_rows, 0, 1},
     {"brakedown_batch_commit", &Options::brakedown_batch_commit, 0, 1}, {"brakedown_staged_open", &Options::brakedown_staged_open, 0, 1},
@@ -170,6 +171,10 @@ static constexpr struct KnobRow {
     {"LH_OPEN_SMALL_CHECK", INT, 0, 0, 1},
     // test hooks
     {"LH_COMM_A2A_SELF", INT, 0, 0, 1}, {"LH_COMM_PROBE_FAIL", INT, 0, 0, 1}, {"LH_SHARDED_COUNTERS_MIN_R", INT, 2, 1, 1 << 20},
+    // a Lasso prove's precommit (open_columns.cpp): 1 = the trees' callback does nothing, so a staged precommit is released only
+    // when the opening takes it (and a single-stage one never starts); 2 = the same, and the opening cancels it and commits
+    // the column-wise levels itself (live: tests flip it)
+    {"LH_TEST_PRECOMMIT_GATE", INT, 0, 0, 2, true},
 };
 static_assert(sizeof(KNOB_TABLE) / sizeof(KNOB_TABLE[0]) == (size_t)Knob::COUNT, "KNOB_TABLE: one row per Knob");
 

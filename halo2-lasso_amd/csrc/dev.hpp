@@ -5,6 +5,7 @@
 #include <stdarg.h>
 #include <stdio.h>
 #include <functional>
+#include <memory>
 #include <string>
 #include <vector>
 #include <utility>
@@ -131,6 +132,10 @@ struct Options {
   int64_t open_precommit = 1;          // proofs of >= 2^this lookups run the challenge-free half of the opening's column route
                                        // (the MSMs over differences of witness columns) on a helper ctx beside the sum-checks of
                                        // a Lasso prove (0: never; 1: always)
+  int64_t open_precommit_stages = 1;   // 1: that precommit runs in two stages - column differences, digits and sort (memory-bound)
+                                       // as soon as the commit batch's bucket accumulation has left the chip, the bucket
+                                       // accumulation (ALU-bound) when the product trees are built; 0: all of
+                                       // it when the trees are built.  Sharded proofs and profiled proves: one stage
   int64_t msm_window_tables = 0;       // SRS levels of <= 2^this points get a window table (MsmJob::win_table) on first use:
                                        // full-width columns over them reduce ONE bucket set (0: no tables)
   int64_t sc_pp_fold = 1;              // 0: the generic layers of the grand products keep their coefficients as products of
@@ -172,7 +177,7 @@ enum class Knob {  // (grouped as the table: thresholds, A/B switches, operation
   HOST_THREADS, JIT_CACHE, JIT_CACHE_DIR, EXPR_JIT, SC_TAIL_TIMEOUT_MS, GKR_START_TIMEOUT_MS, COMM_WAIT_TIMEOUT_MS, COMM_A2A,
   COMM_PROBE,
   HOST_TRACE, SC_TAIL_TRACE, GKR_TRACE, SC_DEBUG, MSM_DEBUG, HP_DEBUG, COMM_DEBUG, OPEN_SMALL_CHECK,
-  COMM_A2A_SELF, COMM_PROBE_FAIL, SHARDED_COUNTERS_MIN_R,
+  COMM_A2A_SELF, COMM_PROBE_FAIL, SHARDED_COUNTERS_MIN_R, TEST_PRECOMMIT_GATE,
   COUNT
 };
 double knob(Knob k);            // the value (switches 0 / 1; LH_COMM_A2A: 1 = allgather)
@@ -181,7 +186,7 @@ struct RouteStats {  // lh_lasso_route (include/lasso_hip.h): counters of the la
   uint32_t v[LH_LASSO_ROUTE_WORDS] = {0};
   enum { OPEN_DEPTH, OPEN_PASSES, EF_ROUNDS, STD_ROUNDS, RW_ROUNDS, TAILS, TAIL_ROUNDS, PACKED_TS, DERIVED, SORTED_REUSE,
          SHARDED_ROUNDS, SHARD_EXCHANGES, WIN_TABLE_JOBS, OPEN_PRECOMMIT, RESIDENT_LAYERS, PP_FOLDS, MSM_HALF_BATCHES,
-         OPEN_SHARED_SUMS };
+         OPEN_SHARED_SUMS, OPEN_PRECOMMIT_STAGED };
 };
 
 // ------------------------------------------------------------------ a long-lived host thread (dev.cpp)
@@ -291,6 +296,9 @@ struct Ctx {
   OpenPrecommit* precommit = nullptr;
   HostWorker* worker = nullptr;   // the host thread that drives THIS ctx when it is somebody's helper (created on first use)
   hipEvent_t handoff_ev = nullptr;  // recorded on this ctx's stream where a helper's stream may start reading its columns
+  // a staged precommit (Options::open_precommit_stages): [0], [1] behind the commit batch's accumulation launches on the
+  // stream and the aux stream - the helper's stage 1 waits for them -, [2] where the trees are built - its stage 2 does
+  hipEvent_t stage_ev[3] = {nullptr, nullptr, nullptr};
   // phase boundaries of the last Lasso prove as events on the stream (no host sync at a boundary: lasso.cpp lap)
   hipEvent_t phase_ev[LH_LASSO_NUM_PHASES] = {};
   bool phase_ev_pending = false;
@@ -949,6 +957,7 @@ constexpr uint32_t MSM_PACK_MAX_BITS = 20;
 constexpr size_t MSM_PACK_MIN_POINTS_PER_BUCKET = 8;
 Ctx& ctx_helper(Ctx&);            // the ctx's helper ctx (created on first use, destroyed with the ctx)
 void open_precommit_cancel(Ctx&);  // waits for a running precommit and drops it (open_columns.cpp)
+void open_precommit_release(Ctx&);  // a staged precommit's second stage may run from here on the ctx's stream (no-op otherwise)
 uint32_t msm_window_bits(size_t n);  // window width msm_batch picks for a full-width (254-bit) column of n points
 void k_msm_window_table(Ctx&, const G1Affine* bases, size_t n, uint32_t cbits, uint32_t W, G1Affine* out);
 // Runs all jobs as one batched Pippenger; out[j] is the affine sum (identity = (0,0)).
@@ -956,7 +965,27 @@ void k_msm_window_table(Ctx&, const G1Affine* bases, size_t n, uint32_t cbits, u
 // queued and before the host waits for the window sums (it overlaps the device's work instead of following it)
 // Returns whether the host waited for the ctx's stream on the way (false only for a batch without a single entry and with every
 // width promised: then nothing queued before the call is known to have run).
-bool msm_batch(Ctx&, const MsmJob* jobs, size_t num_jobs, G1Affine* out_host, const std::function<void()>* overlap = nullptr);
+// `acc_queued` (optional): called once, on the calling thread, right behind the batch's last bucket-accumulation launch (a
+// batch without entries: before the call returns) - `on_aux`: a second half's accumulation went to the ctx's aux stream.
+// An event recorded there on the stream(s) marks the end of the batch's ALU-bound stretch: only latency-bound tails follow
+bool msm_batch(Ctx&, const MsmJob* jobs, size_t num_jobs, G1Affine* out_host, const std::function<void()>* overlap = nullptr,
+               const std::function<void(bool on_aux)>* acc_queued = nullptr);
+// msm_batch in two calls, for a caller that wants the challenge-free front of a batch queued early and its ALU-bound part
+// held back (open_columns.cpp): msm_prepare plans the batch, allocates its workspace from the ctx's arena and queues digits
+// and sort - the sorted entry stream is then in the arena -; msm_run queues accumulation, continuation levels, reduction and
+// window sums, waits and combines on the host.  The caller's ArenaScope spans both calls, nothing else uses the ctx in
+// between, and `jobs` are the same array.  msm_batch is msm_prepare followed by msm_run.
+struct MsmPrepared;
+struct MsmPreparedDelete {
+  void operator()(MsmPrepared*) const;
+};
+typedef std::unique_ptr<MsmPrepared, MsmPreparedDelete> MsmPreparedPtr;
+MsmPreparedPtr msm_prepare(Ctx&, const MsmJob* jobs, size_t num_jobs);
+bool msm_run(Ctx&, MsmPrepared&, const MsmJob* jobs, size_t num_jobs, G1Affine* out_host);
+// the planning half alone (host only; lh_debug_msm_plan): the shape msm_prepare arrives at for jobs of these sizes, widths
+// (bits[j] significant bits, promised) and kinds, as SHAPE_WORDS numbers per sub-batch -> the number of sub-batches
+constexpr size_t MSM_SHAPE_WORDS = 12;
+size_t msm_plan_shape(Ctx&, const MsmJob* jobs, size_t num_jobs, bool via_prepare, uint64_t* out /* [2 * MSM_SHAPE_WORDS] */);
 // out[i] = scalars[i] * G (fixed-base), normalised to affine; all on device
 void k_fixed_base_mul_g(Ctx&, const Fr* scalars, size_t n, G1Affine* out);
 

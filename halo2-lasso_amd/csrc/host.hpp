@@ -350,8 +350,12 @@ struct SmallOpen {
 // Options::open_precommit: commit the challenge-free half of the coming batch opening's column route on the ctx's helper
 // ctx, starting now (the opening's polys, their small columns and the (poly, point) pairs as mkzg_batch_open will get them;
 // the evaluations' values are not used).  mkzg_open picks the results up when they fit, and commits as before when not.
-void open_precommit_start(Ctx&, const Srs&, size_t num_vars, const SmallPoly* small, size_t num_polys,
-                          const lh_evaluation* evals, size_t num_evals);
+// `staged` >= 0 (Options::open_precommit_stages; the caller is behind the last accumulation launch of its commit batch -
+// msm_batch's acc_queued -, 1: a half of it on the aux stream): the helper's differences, digits and sort start once those
+// launches have left the chip, its accumulation only from open_precommit_release on (or when the opening takes the plan).
+// Returns whether a staged precommit is under way.
+bool open_precommit_start(Ctx&, const Srs&, size_t num_vars, const SmallPoly* small, size_t num_polys,
+                          const lh_evaluation* evals, size_t num_evals, int staged = -1);
 // `open_small` (optional) is called instead of `open` when every opened poly came as a small-valued column
 void additive_batch_open(Ctx&, size_t num_vars, const Fr* const* d_polys, size_t num_polys, const HFr* points,
                          size_t num_points, const lh_evaluation* evals, size_t num_evals, Transcript& tr,
@@ -530,8 +534,10 @@ struct Pcs {
   std::function<void(size_t num_vars, const Fr* const* d_polys, size_t num_polys, const HFr* points, size_t num_points,
                      const lh_evaluation* evals, size_t num_evals, Transcript& tr, const SmallPoly* small)>
       batch_open;
-  // optional (multilinear KZG): start committing the challenge-free half of that batch opening now (open_precommit_start)
-  std::function<void(size_t num_vars, const SmallPoly* small, size_t num_polys, const lh_evaluation* evals, size_t num_evals)>
+  // optional (multilinear KZG): start committing the challenge-free half of that batch opening now (open_precommit_start;
+  // `staged` as there, -1: all of it now)
+  std::function<bool(size_t num_vars, const SmallPoly* small, size_t num_polys, const lh_evaluation* evals, size_t num_evals,
+                     int staged)>
       precommit;
 };
 Pcs mkzg_pcs(Ctx&, const Srs&);                            // mkzg.cpp

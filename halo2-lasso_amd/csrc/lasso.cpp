@@ -488,6 +488,60 @@ void lasso_prove(Ctx& c, const Pcs& pcs, const lh_lasso_table& tb, size_t n, con
   tr.common_field_element(HFr::from_u64(cc));
   tr.common_field_element(HFr::from_u64(alpha));
   Fr* a_pad = nullptr;  // the output column zero-padded to nv variables, where that table is needed (l > n, no 32-bit form)
+  // the committed polys as small-valued columns and the (poly, point) pairs of the batch opening at the end (step 8): r, r_z,
+  // r_N, r_M are points 0..3.  Challenge-free: made once the access counts' widths are known (count_ors) - by the commit
+  // batch when the opening's precommit is staged from there, behind the commitments otherwise
+  const size_t num_n = 1 + 2 * cc + alpha;
+  std::vector<SmallPoly> small;
+  std::vector<lh_evaluation> evs;
+  SmallLinear a_linear;  // a = sum_m coeff_m E_{f(m)} entry by entry (linear g)
+  auto open_columns = [&] {
+    if (!small.empty()) return;
+    small.assign(num_n + cc, SmallPoly());
+    if (a_small) {
+      for (uint32_t m = 0; m < tb.num_terms; m++) {
+        HFr co;
+        memcpy(&co, &tb.g_coeff[m], 32);
+        a_linear.poly.push_back(1 + 2 * cc + tb.g_factor[m][0]);
+        a_linear.coeff.push_back(co);
+      }
+      small[0] = SmallPoly{a_small, N, 0, &a_linear};
+    }
+    for (size_t j = 0; j < cc; j++) {
+      small[1 + j] = SmallPoly{d_dims[j], N, (uint32_t)l};
+      small[1 + cc + j] = SmallPoly{rts[j], N, count_ors[j] ? 32u - (uint32_t)__builtin_clz(count_ors[j]) : 0u};
+      small[num_n + j] = SmallPoly{fcs[j], M, 0};
+      if (shn) {
+        // the zero-padded n-variable final_cts column lives in the index range [0, 2^l), l <= shard_bit + rho: this rank's
+        // shard of it is the slice [rank * 2^shard_bit, (rank + 1) * 2^shard_bit) at its local indices [0, 2^shard_bit)
+        const size_t first = sh.rank << sh.j;
+        small[num_n + j] = first < M ? SmallPoly{fcs[j] + first, std::min(M - first, (size_t)1 << sh.j), 0} : SmallPoly{fcs[j], 0, 0};
+      }
+    }
+    for (size_t i = 0; i < alpha; i++)
+      small[1 + 2 * cc + i] = SmallPoly{E[i], N, (uint32_t)(tb.memory_subtable[i] == LH_SUBTABLE_IDENTITY ? l : l / 2)};
+    auto push = [&](size_t poly, size_t point) {
+      lh_evaluation e;
+      memset(&e, 0, sizeof(e));
+      e.poly = (uint32_t)poly;
+      e.point = (uint32_t)point;
+      evs.push_back(e);
+    };
+    push(0, 0);
+    for (size_t i = 0; i < alpha; i++) push(1 + 2 * cc + i, 1);
+    for (size_t j = 0; j < cc; j++) push(1 + j, 2);
+    for (size_t j = 0; j < cc; j++) push(1 + cc + j, 2);
+    for (size_t i = 0; i < alpha; i++) push(1 + 2 * cc + i, 2);
+    for (size_t j = 0; j < cc; j++) push(num_n + j, 3);
+  };
+  // the opening's column-wise commitments depend on the witness columns alone: on the helper ctx, beside the sum-checks
+  // (Options::open_precommit) - in two stages (Options::open_precommit_stages): differences, digits and sort as soon as this
+  // commit batch's accumulation is off the chip, the accumulation when the product trees are built
+  struct PrecommitGuard {  // (a prove that fails on the way drops what was started)
+    Ctx& c;
+    ~PrecommitGuard() { open_precommit_cancel(c); }
+  } precommit_guard{c};
+  bool precommit_staged = false;
   if (pcs.commit_columns || pcs.commit_columns_and_write) {
     // a scheme that commits columns itself (Hyrax: vectors of row commitments): a from its 32-bit form when there is one,
     // dim / read_ts / E / final_cts as u32 columns with the bounds known here; E_i of an identity subtable IS dim_j.  The
@@ -612,7 +666,15 @@ void lasso_prove(Ctx& c, const Pcs& pcs, const lh_lasso_table& tb, size_t n, con
       jobs.back().known_bits = count_ors[j] ? 32u - (uint32_t)__builtin_clz(count_ors[j]) : 0u;
     }
     std::vector<HG1> part(jobs.size()), comms(total);
-    msm_batch(c, jobs.data(), jobs.size(), (G1Affine*)part.data());
+    // (stage 1 of the opening's precommit goes to the helper from behind this batch's accumulation launches; not in a sharded
+    // proof, whose commit ends in an exchange, and not under the profiler)
+    std::function<void(bool)> stage1 = [&](bool on_aux) {
+      open_columns();
+      precommit_staged = pcs.precommit(nv, small.data(), small.size(), evs.data(), evs.size(), on_aux ? 1 : 0);
+      c.route.v[RouteStats::OPEN_PRECOMMIT_STAGED] = precommit_staged ? 1u : 0u;
+    };
+    const bool stage = pcs.precommit && c.opt.open_precommit_stages != 0 && !shn && !c.prof;
+    msm_batch(c, jobs.data(), jobs.size(), (G1Affine*)part.data(), nullptr, stage ? &stage1 : nullptr);
     c.host_stamp("commit:msm_done");
     if (shn) {
       // partial commitments of the shards (the second outputs of packed jobs included) -> their sums, one exchange
@@ -661,24 +723,15 @@ void lasso_prove(Ctx& c, const Pcs& pcs, const lh_lasso_table& tb, size_t n, con
   // ---- field-element views only where a sum-check needs tables (E for Surge when g is not linear); dim / read_ts /
   // final_cts (and E under a linear g) stay u32 all the way: fingerprints, evaluations and the batch opening's merge
   // read the 4-byte columns
-  const size_t num_n = 1 + 2 * cc + alpha;
   std::vector<const Fr*> polys_n(num_n, nullptr), polys_l(cc, nullptr);
-  std::vector<SmallPoly> small(num_n + cc);
+  open_columns();
   auto fr_view = [&](const uint32_t* src, size_t len) {
     Fr* d = c.arena.alloc_n<Fr>(NV);
     k_fr_from_u32(c, src, len, d);
     if (len < NV) LH_HIP(hipMemsetAsync(d + len, 0, (NV - len) * sizeof(Fr), c.stream));
     return d;
   };
-  SmallLinear a_linear;  // a = sum_m coeff_m E_{f(m)} entry by entry (linear g)
-  if (a_small) {
-    for (uint32_t m = 0; m < tb.num_terms; m++) {
-      HFr co;
-      memcpy(&co, &tb.g_coeff[m], 32);
-      a_linear.poly.push_back(1 + 2 * cc + tb.g_factor[m][0]);
-      a_linear.coeff.push_back(co);
-    }
-    small[0] = SmallPoly{a_small, N, 0, &a_linear};
+  if (a_small) {  // (the output column goes by its 32-bit form: small[0])
   } else if (N < NV) {  // l > n: the output column needs the padding too
     if (!a_pad) {
       a_pad = c.arena.alloc_n<Fr>(NV);
@@ -689,53 +742,23 @@ void lasso_prove(Ctx& c, const Pcs& pcs, const lh_lasso_table& tb, size_t n, con
   } else {
     polys_n[0] = a;
   }
-  for (size_t j = 0; j < cc; j++) {
-    small[1 + j] = SmallPoly{d_dims[j], N, (uint32_t)l};
-    small[1 + cc + j] = SmallPoly{rts[j], N, count_ors[j] ? 32u - (uint32_t)__builtin_clz(count_ors[j]) : 0u};
-    small[num_n + j] = SmallPoly{fcs[j], M, 0};
-    if (shn) {
-      // the zero-padded n-variable final_cts column lives in the index range [0, 2^l), l <= shard_bit + rho: this rank's
-      // shard of it is the slice [rank * 2^shard_bit, (rank + 1) * 2^shard_bit) at its local indices [0, 2^shard_bit)
-      const size_t first = sh.rank << sh.j;
-      small[num_n + j] = first < M ? SmallPoly{fcs[j] + first, std::min(M - first, (size_t)1 << sh.j), 0} : SmallPoly{fcs[j], 0, 0};
-    }
-  }
   bool linear_surge = true;  // (lasso_argue: the Surge sum-check then runs over the output column alone)
   for (uint32_t m = 0; m < tb.num_terms; m++) linear_surge = linear_surge && tb.g_num_factors[m] == 1;
-  for (size_t i = 0; i < alpha; i++) {
+  for (size_t i = 0; i < alpha; i++)
     if (!linear_surge) polys_n[1 + 2 * cc + i] = fr_view(E[i], N);
-    small[1 + 2 * cc + i] = SmallPoly{E[i], N, (uint32_t)(tb.memory_subtable[i] == LH_SUBTABLE_IDENTITY ? l : l / 2)};
-  }
   const Fr* const* E_fr = polys_n.data() + 1 + 2 * cc;
 
-  // (poly, point) pairs of the batch opening at the end (step 8): r, r_z, r_N, r_M are points 0..3
-  std::vector<lh_evaluation> evs;
-  {
-    auto push = [&](size_t poly, size_t point) {
-      lh_evaluation e;
-      memset(&e, 0, sizeof(e));
-      e.poly = (uint32_t)poly;
-      e.point = (uint32_t)point;
-      evs.push_back(e);
-    };
-    push(0, 0);
-    for (size_t i = 0; i < alpha; i++) push(1 + 2 * cc + i, 1);
-    for (size_t j = 0; j < cc; j++) push(1 + j, 2);
-    for (size_t j = 0; j < cc; j++) push(1 + cc + j, 2);
-    for (size_t i = 0; i < alpha; i++) push(1 + 2 * cc + i, 2);
-    for (size_t j = 0; j < cc; j++) push(num_n + j, 3);
-  }
-  // the opening's column-wise commitments depend on the witness columns alone: on the helper ctx from here on, beside
-  // the sum-checks (Options::open_precommit)
-  struct PrecommitGuard {  // (a prove that fails on the way drops what was started)
-    Ctx& c;
-    ~PrecommitGuard() { open_precommit_cancel(c); }
-  } precommit_guard{c};
-  // (started when the memory-checking argument has built its product trees - prove_grand_product's trees_built: beside the
-  // Surge rounds and the tree kernels, which stream at the HBM bound, the helper's sorts only get in the way: tree_up 1.2 ->
-  // 5.0 ms per proof)
+  // (one stage: all of the precommit starts when the memory-checking argument has built its product trees -
+  // prove_grand_product's trees_built: beside the Surge rounds and the tree kernels, which stream at the HBM bound, the
+  // helper's sorts only get in the way: tree_up 1.2 -> 5.0 ms per proof.  Two stages: the sorts are through by then, and the
+  // callback releases the accumulation)
   std::function<void()> precommit;
-  if (pcs.precommit) precommit = [&] { pcs.precommit(nv, small.data(), small.size(), evs.data(), evs.size()); };
+  if (pcs.precommit)
+    precommit = [&] {
+      if (knob(Knob::TEST_PRECOMMIT_GATE) != 0) return;  // (test hook: a prove on which nothing happens at trees_built)
+      if (precommit_staged) open_precommit_release(c);
+      else pcs.precommit(nv, small.data(), small.size(), evs.data(), evs.size(), -1);
+    };
 
   // ---- 2-7: Surge, memory checking, evaluations
   c.host_stamp("argue:start");

@@ -258,6 +258,7 @@ HFr mkzg_open(Ctx& c, const Srs& srs, const Fr* d_poly, size_t num_vars, const H
   const std::vector<HG1>* pre_out = nullptr;
   std::unique_ptr<OpenPrecommit> pre;
   if (small) {
+    if (knob(Knob::TEST_PRECOMMIT_GATE) == 2) open_precommit_cancel(c);  // (test hook: an opening that declines what was started)
     pre = open_precommit_take(c, srs, num_vars, small->cols, zero, own);
     if (pre) {
       plan = &pre->plan, pre_out = &pre->out;
@@ -478,8 +479,8 @@ Pcs mkzg_pcs(Ctx& c, const Srs& srs) {  // (mkzg_batch_commit / mkzg_batch_open 
                             const lh_evaluation* evals, size_t ne, Transcript& tr, const SmallPoly* small) {
     mkzg_batch_open(c, srs, nv, polys, np, points, npts, evals, ne, tr, small);
   };
-  p.precommit = [&c, &srs](size_t nv, const SmallPoly* small, size_t np, const lh_evaluation* evals, size_t ne) {
-    open_precommit_start(c, srs, nv, small, np, evals, ne);
+  p.precommit = [&c, &srs](size_t nv, const SmallPoly* small, size_t np, const lh_evaluation* evals, size_t ne, int staged) {
+    return open_precommit_start(c, srs, nv, small, np, evals, ne, staged);
   };
   return p;
 }

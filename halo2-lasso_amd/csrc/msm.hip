@@ -1082,11 +1082,24 @@ static void msm_sub_combine(MsmSub& s, std::vector<host::G1Xyzz>& sums /* [2 glo
   });
 }
 
-bool msm_batch(Ctx& c, const MsmJob* jobs, size_t num_jobs, G1Affine* out_host, const std::function<void()>* overlap) {
-  bool overlap_done = overlap == nullptr;
-  bool waited = false;  // the host waited for the ctx's stream at least once (everything queued before the batch has run)
-  for (size_t base = 0; base < num_jobs; base += MSM_MAX_JOBS) {
-    const size_t nj = std::min(num_jobs - base, (size_t)MSM_MAX_JOBS);
+// One planning pass of a batch: the jobs [base, base + nj), nj <= MSM_MAX_JOBS, as one sub-batch or two halves
+namespace {
+struct MsmChunk {
+  size_t base = 0, nj = 0, total_entries = 0;
+  std::vector<MsmSub> subs;
+  bool waited = false;  // the host waited for the ctx's stream while planning (the pass over the scalars' widths)
+};
+}  // namespace
+struct MsmPrepared {
+  MsmChunk first;  // the first planning pass of the batch, its entries sorted; what follows it runs whole in msm_run
+};
+void MsmPreparedDelete::operator()(MsmPrepared* p) const { delete p; }
+
+// plan (widths, derived jobs, halves, layout) - and, with `queue`, workspace from the arena (the caller's ArenaScope), digits
+// and sort on the ctx's stream
+static void msm_chunk_prepare(Ctx& c, const MsmJob* jobs, size_t base, size_t nj, MsmChunk& ch, bool queue = true) {
+  ch.base = base, ch.nj = nj;
+  {
     // significant bits of every column (one cheap pass)
     std::vector<uint32_t> job_bits(nj, 32);
     {
@@ -1115,7 +1128,7 @@ bool msm_batch(Ctx& c, const MsmJob* jobs, size_t num_jobs, G1Affine* out_host, 
         uint32_t* h_or = (uint32_t*)c.pin(8 * MSM_MAX_JOBS * sizeof(uint32_t));
         LH_HIP(hipMemcpyAsync(h_or, d_or, 8 * nj * sizeof(uint32_t), hipMemcpyDeviceToHost, c.stream));
         c.sync();
-        waited = true;
+        ch.waited = true;
         for (size_t j = 0; j < nj; j++) {
           uint32_t bits = 0;
           for (int k = 7; k >= 0 && !bits; k--)
@@ -1148,7 +1161,8 @@ bool msm_batch(Ctx& c, const MsmJob* jobs, size_t num_jobs, G1Affine* out_host, 
     std::vector<size_t> all(nj);
     for (size_t j = 0; j < nj; j++) all[j] = base + j;
     const std::vector<char> second = msm_pick_split(c, jobs, all, job_bits, derived);
-    std::vector<MsmSub> subs(second.empty() ? 1 : 2);
+    std::vector<MsmSub>& subs = ch.subs;
+    subs.assign(second.empty() ? 1 : 2, MsmSub());
     for (size_t j = 0; j < nj; j++) {
       MsmSub& s = subs[second.empty() ? 0 : (size_t)second[j]];
       s.idx.push_back(base + j), s.bits.push_back(job_bits[j]), s.derived.push_back(derived[j]);
@@ -1165,33 +1179,46 @@ bool msm_batch(Ctx& c, const MsmJob* jobs, size_t num_jobs, G1Affine* out_host, 
       msm_plan_sub(c, jobs, s, subs.size() == 2 ? &whole : nullptr);
       total_entries += s.max_entries, pin_total += s.pin_bytes();
     }
-    if (total_entries == 0) {
-      for (size_t j = 0; j < nj; j++) {
-        memset(&out_host[base + j], 0, sizeof(G1Affine));
-        if (jobs[base + j].out_second) memset(jobs[base + j].out_second, 0, sizeof(G1Affine));
-      }
-      continue;
-    }
+    ch.total_entries = total_entries;
+    if (total_entries == 0) return;
     if (subs.size() == 2 && (!subs[0].max_entries || !subs[1].max_entries)) {  // (cannot happen with msm_pick_split's floors)
       subs.assign(1, whole);
       pin_total = subs[0].pin_bytes();
     }
+    if (!queue) return;
+    uint8_t* pin_base = (uint8_t*)c.pin(pin_total);
+    for (MsmSub& s : subs) {
+      msm_sub_alloc(c, s, pin_base);
+      pin_base += s.pin_bytes();
+    }
+    // (two halves: both entry streams on the ctx's stream)
+    for (MsmSub& s : subs) msm_sub_entries(c, jobs, s);
+  }
+}
+
+// the rest of a prepared planning pass: accumulation, tails, the host's wait and combine -> out_host[base .. base + nj)
+static void msm_chunk_run(Ctx& c, const MsmJob* jobs, size_t num_jobs, G1Affine* out_host, MsmChunk& ch,
+                          const std::function<void()>* overlap, bool& overlap_done, const std::function<void(bool)>* acc_queued) {
+  const size_t base = ch.base, nj = ch.nj;
+  std::vector<MsmSub>& subs = ch.subs;
+  {
+    if (ch.total_entries == 0) {
+      for (size_t j = 0; j < nj; j++) {
+        memset(&out_host[base + j], 0, sizeof(G1Affine));
+        if (jobs[base + j].out_second) memset(jobs[base + j].out_second, 0, sizeof(G1Affine));
+      }
+      if (acc_queued) (*acc_queued)(false);
+      return;
+    }
     std::vector<host::G1Xyzz> sums_all(2 * num_jobs, host::G1Xyzz::identity());
     {
-      ArenaScope scope(c.arena);
-      uint8_t* pin_base = (uint8_t*)c.pin(pin_total);
-      for (MsmSub& s : subs) {
-        msm_sub_alloc(c, s, pin_base);
-        pin_base += s.pin_bytes();
-      }
       const bool piped = subs.size() == 2;
-      // One batch: everything on the ctx's stream.  Two halves: both entry streams on the ctx's stream; then the FIRST half's
+      // One batch: everything on the ctx's stream.  Two halves: both entry streams are on the ctx's stream; then the FIRST half's
       // accumulation and tails stay there, and the second half's go to the aux stream, whose priority is the lowest the device
       // offers - its accumulation gets the wave slots the first half's kernels do not ask for: the drain of the first
       // accumulation (two launches on one stream would each pay their own), then everything the first half's latency-bound
       // tails leave idle.  The second half's tails end the batch.  Under the profiler: one stream, the launches one after
       // the other.
-      for (MsmSub& s : subs) msm_sub_entries(c, jobs, s);
       hipStream_t side = c.stream;
       uint32_t seq_aux = 0;
       struct AuxGuard {  // an exception on the way out must not release the arena under kernels still queued on the aux stream
@@ -1214,6 +1241,7 @@ bool msm_batch(Ctx& c, const MsmJob* jobs, size_t num_jobs, G1Affine* out_host, 
       c.live_batch++;
       msm_sub_accumulate(c, subs[0], c.stream);
       if (piped) msm_sub_accumulate(c, subs[1], side);
+      if (acc_queued) (*acc_queued)(side != c.stream);
       const uint32_t seq = c.next_seq();
       msm_sub_tail(c, jobs, subs[0], c.stream, c.finish_for(subs[0].nshares, nullptr, seq));
       if (piped) {
@@ -1232,7 +1260,7 @@ bool msm_batch(Ctx& c, const MsmJob* jobs, size_t num_jobs, G1Affine* out_host, 
       }
       c.host_stamp("msm:queued");
       c.wait_flag(seq);
-      waited = true;
+      ch.waited = true;
       if (piped) {
         // the first half's window sums are in: its doublings run on the host while the device works through the second half
         memcpy(subs[0].wins.data(), subs[0].win_out, (size_t)subs[0].nshares * sizeof(G1Xyzz));
@@ -1265,9 +1293,69 @@ bool msm_batch(Ctx& c, const MsmJob* jobs, size_t num_jobs, G1Affine* out_host, 
     }
     c.host_stamp("msm:combined");
   }
+}
+
+// a batch from its first planning pass on (`first` prepared by the caller under an ArenaScope of its own, or null)
+static bool msm_batch_from(Ctx& c, MsmChunk* first, const MsmJob* jobs, size_t num_jobs, G1Affine* out_host,
+                           const std::function<void()>* overlap, const std::function<void(bool)>* acc_queued) {
+  bool overlap_done = overlap == nullptr;
+  bool waited = false;  // the host waited for the ctx's stream at least once (everything queued before the batch has run)
+  for (size_t base = 0; base < num_jobs; base += MSM_MAX_JOBS) {
+    const size_t nj = std::min(num_jobs - base, (size_t)MSM_MAX_JOBS);
+    const std::function<void(bool)>* hook = base + nj == num_jobs ? acc_queued : nullptr;
+    if (base == 0 && first) {
+      LH_REQUIRE(first->base == 0 && first->nj == nj, LH_ERR_ARG, "msm_run: not the batch that was prepared");
+      msm_chunk_run(c, jobs, num_jobs, out_host, *first, overlap, overlap_done, hook);
+      waited = waited || first->waited;
+      continue;
+    }
+    ArenaScope scope(c.arena);
+    MsmChunk ch;
+    msm_chunk_prepare(c, jobs, base, nj, ch);
+    msm_chunk_run(c, jobs, num_jobs, out_host, ch, overlap, overlap_done, hook);
+    waited = waited || ch.waited;
+  }
   // (a batch without entries still owes the caller its host work)
   if (!overlap_done) (*overlap)();
+  if (!num_jobs && acc_queued) (*acc_queued)(false);
   return waited;
+}
+
+bool msm_batch(Ctx& c, const MsmJob* jobs, size_t num_jobs, G1Affine* out_host, const std::function<void()>* overlap,
+               const std::function<void(bool)>* acc_queued) {
+  return msm_batch_from(c, nullptr, jobs, num_jobs, out_host, overlap, acc_queued);
+}
+MsmPreparedPtr msm_prepare(Ctx& c, const MsmJob* jobs, size_t num_jobs) {
+  MsmPreparedPtr p(new MsmPrepared());
+  msm_chunk_prepare(c, jobs, 0, std::min(num_jobs, (size_t)MSM_MAX_JOBS), p->first);
+  return p;
+}
+bool msm_run(Ctx& c, MsmPrepared& p, const MsmJob* jobs, size_t num_jobs, G1Affine* out_host) {
+  return msm_batch_from(c, &p.first, jobs, num_jobs, out_host, nullptr, nullptr);
+}
+
+// the planning half alone, for a test without a device: per sub-batch jobs, entries, small entries, buckets, segments, windows,
+// groups, shares, K, chunks, segment size, plain reduction
+size_t msm_plan_shape(Ctx& c, const MsmJob* jobs, size_t num_jobs, bool via_prepare, uint64_t* out) {
+  LH_REQUIRE(num_jobs >= 1 && num_jobs <= (size_t)MSM_MAX_JOBS, LH_ERR_ARG, "msm plan: 1 .. 48 jobs");
+  for (size_t j = 0; j < num_jobs; j++)
+    LH_REQUIRE(jobs[j].known_bits != 0 && jobs[j].n < ((size_t)1 << 31), LH_ERR_ARG, "msm plan: widths must be promised");
+  MsmChunk ch;
+  MsmPreparedPtr p;
+  if (via_prepare) {  // (the handle msm_prepare builds, without the device half)
+    p.reset(new MsmPrepared());
+    msm_chunk_prepare(c, jobs, 0, num_jobs, p->first, false);
+  } else {
+    msm_chunk_prepare(c, jobs, 0, num_jobs, ch, false);
+  }
+  const MsmChunk& got = via_prepare ? p->first : ch;
+  size_t k = 0;
+  for (const MsmSub& s : got.subs) {
+    const uint64_t w[MSM_SHAPE_WORDS] = {s.idx.size(), s.max_entries, s.small_entries, s.nbuckets, s.nsegs, s.nwins,
+                                         s.ngroups,    s.nshares,     s.K,             s.nchunks,  s.seg_size, s.plain_reduce ? 1u : 0u};
+    memcpy(out + MSM_SHAPE_WORDS * k++, w, sizeof(w));
+  }
+  return got.subs.size();
 }
 
 // ------------------------------------------------------------------ window tables (MsmJob::win_table)

@@ -182,8 +182,17 @@ bool column_route_on(const Ctx& c, const std::vector<SmallPoly>& cols, const std
 
 void open_precommit_cancel(Ctx& c) {
   if (!c.precommit) return;
-  delete c.precommit;  // (joins)
+  delete c.precommit;  // (opens a gate that is still closed as "cancelled", joins)
   c.precommit = nullptr;
+}
+// the trees are built (prove_grand_product's trees_built): a staged precommit's accumulation may follow what is queued on
+// the ctx's stream so far
+void open_precommit_release(Ctx& c) {
+  OpenPrecommit* pc = c.precommit;
+  if (!pc || !pc->staged) return;
+  if (!c.stage_ev[2]) LH_HIP(hipEventCreateWithFlags(&c.stage_ev[2], hipEventDisableTiming));
+  LH_HIP(hipEventRecord(c.stage_ev[2], c.stream));
+  pc->open_gate(false, c.stage_ev[2]);
 }
 // the columns of a batch opening whose polys are all small-valued columns: `used` polys, a linear column's coefficient
 // handed to the columns it combines, the same column under two names merged.  coef == nullptr: the structure alone
@@ -224,12 +233,12 @@ bool small_open_columns(const SmallPoly* small, size_t num_polys, const lh_evalu
   }
   return true;
 }
-void open_precommit_start(Ctx& c, const Srs& srs, size_t num_vars, const SmallPoly* small, size_t num_polys,
-                          const lh_evaluation* evals, size_t num_evals) {
+bool open_precommit_start(Ctx& c, const Srs& srs, size_t num_vars, const SmallPoly* small, size_t num_polys,
+                          const lh_evaluation* evals, size_t num_evals, int staged) {
   open_precommit_cancel(c);
   // (the option is the smallest proof that does it; default 1: every proof that takes the column route - 2^17..2^19 range
   // lookups gain too: 7.0 -> 6.4-6.9, 8.1-9.1 -> 7.3-7.7, 9.7-9.9 -> 9.3-9.4 ms)
-  if (c.opt.open_precommit <= 0 || (int64_t)num_vars < c.opt.open_precommit || !small || num_vars > srs.num_vars) return;
+  if (c.opt.open_precommit <= 0 || (int64_t)num_vars < c.opt.open_precommit || !small || num_vars > srs.num_vars) return false;
   // inside a sharded proof the columns are this rank's shards and the column-wise levels are committed against this rank's
   // share of the levels' bases (mkzg_open's geometry): nothing in this half of the route needs a peer
   const Shard sh(c);
@@ -237,9 +246,12 @@ void open_precommit_start(Ctx& c, const Srs& srs, size_t num_vars, const SmallPo
   const size_t lsh = sharded ? sh.rho : 0, cut = sharded ? sh.j + sh.rho : 0;
   const size_t n = (size_t)1 << (num_vars - lsh);
   SmallOpen so;
-  if (!small_open_columns(small, num_polys, evals, num_evals, n, nullptr, so)) return;
+  if (!small_open_columns(small, num_polys, evals, num_evals, n, nullptr, so)) return false;
   std::vector<char> zero(so.cols.size(), 0);
-  if (!column_route_on(c, so.cols, zero, num_vars, lsh, n, sharded, cut)) return;
+  if (!column_route_on(c, so.cols, zero, num_vars, lsh, n, sharded, cut)) return false;
+  // (a sharded proof's precommit is per rank and its commit ends in an exchange; a profiled prove runs its kernels one at
+  // a time: one stage both)
+  const bool two_stages = staged >= 0 && c.opt.open_precommit_stages != 0 && !sh.on && !c.prof;
   // the bases of the (at most two) column-wise levels, resolved here: a rank's share of a level is made on first use by a
   // ctx that knows the shard geometry - this one
   std::vector<const G1Affine*> bases_of(num_vars + 1, nullptr);
@@ -255,19 +267,34 @@ void open_precommit_start(Ctx& c, const Srs& srs, size_t num_vars, const SmallPo
   h.prof_recs.clear();
   OpenPrecommit* pc = new OpenPrecommit();
   pc->srs = &srs, pc->num_vars = num_vars, pc->cols = so.cols, pc->zero = zero;
+  pc->staged = two_stages;
   c.precommit = pc;
   // the witness columns are written by kernels queued on this ctx's stream and read by the helper's: an event between the
   // streams (not a host sync), and the helper's long-lived host thread (not a thread per proof)
-  if (!c.handoff_ev) LH_HIP(hipEventCreateWithFlags(&c.handoff_ev, hipEventDisableTiming));
-  LH_HIP(hipEventRecord(c.handoff_ev, c.stream));
-  hipEvent_t handoff = c.handoff_ev;
+  // (two stages: the caller stands behind the commit batch's accumulation launches - the event of the stream covers the
+  // witness kernels too, and the one of the aux stream the other half's accumulation.  Stage 1 is memory-bound and its
+  // scatter workgroups need a whole CU's LDS: beside an accumulation they would only wait for it to drain)
+  hipEvent_t handoff[2] = {nullptr, nullptr};
+  if (two_stages) {
+    for (int k = 0; k < (staged >= 1 && c.aux_stream ? 2 : 1); k++) {
+      if (!c.stage_ev[k]) LH_HIP(hipEventCreateWithFlags(&c.stage_ev[k], hipEventDisableTiming));
+      LH_HIP(hipEventRecord(c.stage_ev[k], k ? c.aux_stream : c.stream));
+      handoff[k] = c.stage_ev[k];
+    }
+  } else {
+    if (!c.handoff_ev) LH_HIP(hipEventCreateWithFlags(&c.handoff_ev, hipEventDisableTiming));
+    LH_HIP(hipEventRecord(c.handoff_ev, c.stream));
+    handoff[0] = c.handoff_ev;
+  }
+  const hipEvent_t handoff0 = handoff[0], handoff1 = handoff[1];
   const int device = c.device;
   if (!h.worker) h.worker = new HostWorker();
   pc->worker = h.worker;
-  h.worker->submit([pc, &h, &srs, num_vars, n, lsh, cut, sharded, bases_of, device, handoff] {
+  h.worker->submit([pc, &h, &srs, num_vars, n, lsh, cut, sharded, bases_of, device, handoff0, handoff1] {
     try {
       LH_HIP(hipSetDevice(device));
-      LH_HIP(hipStreamWaitEvent(h.stream, handoff, 0));
+      LH_HIP(hipStreamWaitEvent(h.stream, handoff0, 0));
+      if (handoff1) LH_HIP(hipStreamWaitEvent(h.stream, handoff1, 0));
       ArenaScope scope(h.arena);
       column_shape(h, pc->cols, pc->zero, n, num_vars, cut, pc->plan);
       column_jobs(h, srs, pc->cols, pc->zero, num_vars, lsh, sharded,
@@ -277,7 +304,29 @@ void open_precommit_start(Ctx& c, const Srs& srs, size_t num_vars, const SmallPo
                   },
                   pc->plan);
       pc->out.resize(pc->plan.jobs.size());
-      if (!pc->plan.jobs.empty()) msm_batch(h, pc->plan.jobs.data(), pc->plan.jobs.size(), (G1Affine*)pc->out.data());
+      const MsmJob* jobs = pc->plan.jobs.data();
+      const size_t num_jobs = pc->plan.jobs.size();
+      if (!pc->staged) {
+        if (num_jobs) msm_batch(h, jobs, num_jobs, (G1Affine*)pc->out.data());
+      } else {
+        // stage 1 ends with the sorted entries in this scope's arena memory; the gate is a host-side wait (nothing spins on
+        // the device), and what opens it says whether stage 2 runs and which event of the owner's stream it follows
+        MsmPreparedPtr prepared;
+        if (num_jobs) prepared = msm_prepare(h, jobs, num_jobs);
+        hipEvent_t release = nullptr;
+        bool cancelled = false;
+        {
+          std::unique_lock<std::mutex> lock(pc->gate_mu);
+          pc->gate_cv.wait(lock, [pc] { return pc->gate_open; });
+          cancelled = pc->cancelled, release = pc->release_ev;
+        }
+        if (cancelled) {  // (the stream is drained before the scope hands the entries' memory back: nothing of this plan is left)
+          h.sync();
+          return;
+        }
+        if (release) LH_HIP(hipStreamWaitEvent(h.stream, release, 0));
+        if (num_jobs) msm_run(h, *prepared, jobs, num_jobs, (G1Affine*)pc->out.data());
+      }
       h.sync();
       column_sums_store(srs, sharded, pc->plan, pc->out.data());
       pc->ok = true;
@@ -288,6 +337,7 @@ void open_precommit_start(Ctx& c, const Srs& srs, size_t num_vars, const SmallPo
     }
   });
   if (c.prof) pc->join();  // a profiled prove keeps its kernels one at a time (the records are merged when taken)
+  return two_stages;
 }
 // the precommitted plan if it is the plan this opening would build (same SRS, columns, zero pattern, widths, depth)
 std::unique_ptr<OpenPrecommit> open_precommit_take(Ctx& c, const Srs& srs, size_t num_vars,
@@ -296,6 +346,7 @@ std::unique_ptr<OpenPrecommit> open_precommit_take(Ctx& c, const Srs& srs, size_
   std::unique_ptr<OpenPrecommit> pc(c.precommit);
   c.precommit = nullptr;
   if (!pc) return nullptr;
+  pc->open_gate(false);  // (a staged plan nobody released - no trees_built on the way here -: its second stage runs now)
   pc->join();
   if (c.prof && c.helper) {
     c.prof_recs.insert(c.prof_recs.end(), c.helper->prof_recs.begin(), c.helper->prof_recs.end());

@@ -2,6 +2,7 @@
 // levels are committed column by column, the MSM jobs that do it (the challenge-free half - open_columns.cpp), and the plan
 // committed ahead on a helper ctx (Options::open_precommit).  Shared by mkzg.cpp (the opening) and open_columns.cpp.
 #pragma once
+#include <condition_variable>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -55,11 +56,30 @@ struct OpenPrecommit {
   std::vector<HG1> out;
   bool ok = false;
   std::string err;
+  // Two stages (Options::open_precommit_stages): the worker queues differences, digits and sort (stage 1), then waits HERE,
+  // on the host, for the gate before it queues the accumulation (stage 2).  The gate opens where the trees are built
+  // (open_precommit_release, with an event of the owner's stream for stage 2 to wait on), at the latest when the plan is
+  // taken; a cancel opens it with `cancelled`: stage 2 is skipped, the helper's stream drained, the arena scope unwound.
+  bool staged = false;
+  std::mutex gate_mu;
+  std::condition_variable gate_cv;
+  bool gate_open = false, cancelled = false;
+  hipEvent_t release_ev = nullptr;  // (set with the gate: recorded on the owner's stream, or null)
+  void open_gate(bool cancel, hipEvent_t ev = nullptr) {  // (the first call decides)
+    {
+      std::lock_guard<std::mutex> lock(gate_mu);
+      if (!gate_open) gate_open = true, cancelled = cancel, release_ev = ev;
+    }
+    gate_cv.notify_all();
+  }
   void join() {
     if (worker) worker->wait();
     worker = nullptr;
   }
-  ~OpenPrecommit() { join(); }
+  ~OpenPrecommit() {
+    open_gate(true);
+    join();
+  }
 };
 
 void column_shape(Ctx& c, const std::vector<SmallPoly>& cols, const std::vector<char>& zero, size_t n, size_t num_vars, size_t cut,

@@ -263,7 +263,13 @@ lh_status lh_lasso_last_timing(lh_ctx*, double* out_ms);
  *                             commitments of their opening - MSMs over differences of witness columns, challenge-free - on
  *                             a helper ctx (own stream and host thread) beside the memory-checking sum-checks; the opening
  *                             then only combines their results
- *   msm_window_tables    0    SRS levels of <= 2^this points get a window table on first use (2^(c w) multiples of every
+ *   open_precommit_stages 1   that precommit in two stages: the memory-bound half (column differences, digits, the sort of the
+ *                             entries) starts as soon as the commit batch's bucket accumulation has left the chip and is
+ *                             through before the product trees are built; the ALU-bound half (bucket accumulation, tails)
+ *                             is released where the trees are built and runs beside the resident grand-product kernel.
+ *                             0: all of it where the trees are built.  Sharded proofs and profiled proves always run one
+ *                             stage (DESIGN.md sections 4 and 11)
+ *   msm_window_tables    0   SRS levels of <= 2^this points get a window table on first use (2^(c w) multiples of every
  *                             base, W-fold the level's memory): the W windows of a full-width column then fill ONE
  *                             bucket set - one bucket reduction, no doublings.  Measured neutral at 2^24 lookups (shorter
  *                             reduction, longer bucket runs): off by default
@@ -329,7 +335,8 @@ typedef struct lh_lasso_route {
                                    always 0 since round 5) */
   uint32_t open_shared_sums;    /* (column, point) pairs whose quad sums the batch opening's column rounds took from the
                                    evaluation passes of the same proof instead of summing again (LH_OPEN_SHARE_SUMS) */
-  uint32_t reserved[6];
+  uint32_t open_precommit_staged; /* 1: the prove ran that precommit in two stages (open_precommit_stages) */
+  uint32_t reserved[5];
 } lh_lasso_route;
 lh_status lh_lasso_last_route(lh_ctx*, lh_lasso_route* out);
 
@@ -932,6 +939,14 @@ lh_status lh_debug_lasso_counters(lh_ctx*, const uint32_t* const* d_dims, size_t
 /* the pass plan of one slab (host only, no GPU needed): the number of radix passes, the digit width of each (rb[passes ..
  * 8) = 0; `bits` above the key width count as the key width) and the temporary device bytes the sort takes */
 lh_status lh_debug_sort_plan(size_t n, unsigned bits, int key_bytes, unsigned* passes, unsigned rb[8], size_t* temp_bytes);
+/* the planning half of a batched MSM (host only, no GPU needed) for jobs of n[j] points whose scalars have bits[j] significant
+ * bits; kinds[j]: 0 = field elements, 1 = a 32-bit column, >= 4 = a packed pair of 32-bit columns with that pack shift.
+ * helper != 0: planned as on a helper ctx (never two halves).  via_prepare: through the handle of the two-call form
+ * (prepare, then run) instead of the one-call batch.  *num_subs = 1 or 2 sub-batches; out[12 s ..] of sub-batch s: jobs,
+ * entries, small-job entries, buckets, segments, windows, groups, window-sum shares, entries per accumulate thread, chunks,
+ * segment size, plain reduction (0 / 1).  out holds 24 words. */
+lh_status lh_debug_msm_plan(size_t num_jobs, const size_t* n, const uint32_t* bits, const uint32_t* kinds, int helper, int via_prepare,
+                            uint64_t* out, size_t* num_subs);
 
 /* development / tests: the kernels that work on 32-bit columns without their field-element views (csrc/kernels_poly.hip,
  * "small-valued columns"), one host function per operation, for tests/test_gpu_u32_columns.py.  Pointers named d_ are
