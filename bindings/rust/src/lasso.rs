@@ -29,6 +29,58 @@ pub fn range_table(num_chunks: u32, chunk_bits: u32) -> lh_lasso_table {
 pub fn bitwise_table(xor: bool, num_chunks: u32, chunk_bits: u32) -> lh_lasso_table {
     table(num_chunks, chunk_bits, if xor { LH_SUBTABLE_XOR } else { LH_SUBTABLE_AND }, chunk_bits / 2)
 }
+/// OR of two (c*l/2)-bit operands (the bitwise table over LH_SUBTABLE_OR)
+pub fn or_table(num_chunks: u32, chunk_bits: u32) -> lh_lasso_table {
+    table(num_chunks, chunk_bits, LH_SUBTABLE_OR, chunk_bits / 2)
+}
+/// x == y for two (c*l/2)-bit operands, chunk 0 least significant: g = prod_j EQ_j.  None unless 1 <= c <= LH_SC_MAX_FACTORS.
+pub fn equal_table(num_chunks: u32, chunk_bits: u32) -> Option<lh_lasso_table> {
+    let c = num_chunks as usize;
+    if c < 1 || c > LH_SC_MAX_FACTORS {
+        return None;
+    }
+    let mut t: lh_lasso_table = unsafe { std::mem::zeroed() };
+    t.num_chunks = num_chunks;
+    t.chunk_bits = chunk_bits;
+    t.num_memories = num_chunks;
+    t.num_terms = 1;
+    t.g_coeff[0] = Fr::ONE;
+    t.g_num_factors[0] = c as u8;
+    for j in 0..c {
+        t.memory_chunk[j] = j as u32;
+        t.memory_subtable[j] = LH_SUBTABLE_EQ;
+        t.g_factor[0][j] = j as u8;
+    }
+    Some(t)
+}
+/// x < y (unsigned): memories LTU_0..LTU_{c-1}, EQ_1..EQ_{c-1}; g = sum_j LTU_j prod_{k > j} EQ_k.  None unless
+/// 1 <= c <= LH_SC_MAX_FACTORS (c = 4, l = 16: 32-bit operands).
+pub fn less_than_table(num_chunks: u32, chunk_bits: u32) -> Option<lh_lasso_table> {
+    let c = num_chunks as usize;
+    if c < 1 || c > LH_SC_MAX_FACTORS {
+        return None;
+    }
+    let mut t: lh_lasso_table = unsafe { std::mem::zeroed() };
+    t.num_chunks = num_chunks;
+    t.chunk_bits = chunk_bits;
+    t.num_memories = (2 * c - 1) as u32;
+    t.num_terms = num_chunks;
+    for j in 0..c {
+        t.memory_chunk[j] = j as u32;
+        t.memory_subtable[j] = LH_SUBTABLE_LTU;
+        if j >= 1 {
+            t.memory_chunk[c + j - 1] = j as u32;
+            t.memory_subtable[c + j - 1] = LH_SUBTABLE_EQ;
+        }
+        t.g_coeff[j] = Fr::ONE;
+        t.g_num_factors[j] = (c - j) as u8;
+        t.g_factor[j][0] = j as u8;
+        for k in (j + 1)..c {
+            t.g_factor[j][k - j] = (c + k - 1) as u8;
+        }
+    }
+    Some(t)
+}
 
 /// dims[j]: chunk indices (< 2^chunk_bits) of every lookup, 2^num_vars entries each
 pub fn prove(pp: &HipProverParam, table: &lh_lasso_table, num_vars: usize, dims: &[DeviceVec<u32>],

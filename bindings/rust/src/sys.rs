@@ -113,6 +113,9 @@ pub struct lh_evaluation { pub poly: u32, pub point: u32, pub value: Fr }
 pub const LH_SUBTABLE_IDENTITY: u32 = 0;
 pub const LH_SUBTABLE_AND: u32 = 1;
 pub const LH_SUBTABLE_XOR: u32 = 2;
+pub const LH_SUBTABLE_OR: u32 = 3;
+pub const LH_SUBTABLE_EQ: u32 = 4;
+pub const LH_SUBTABLE_LTU: u32 = 5;
 #[repr(C)] #[derive(Clone, Copy)]
 pub struct lh_lasso_table {
     pub num_chunks: u32,

@@ -21,6 +21,7 @@ _MONT_INV_R = pow(_MONT, -1, R_MOD)
 _MONT_INV_Q = pow(_MONT, -1, Q_MOD)
 
 SUBTABLE_IDENTITY, SUBTABLE_AND, SUBTABLE_XOR = 0, 1, 2
+SUBTABLE_OR, SUBTABLE_EQ, SUBTABLE_LTU = 3, 4, 5  # x | y; (x == y); (x < y) unsigned - index x || y as for AND and XOR
 
 
 # ------------------------------------------------------------------ errors (plonkish_backend/src/lib.rs:12-20)
@@ -1418,7 +1419,37 @@ class LassoTable:
         return cls(num_chunks, chunk_bits, [(j, kind) for j in range(num_chunks)],
                    [(1 << (chunk_bits // 2 * j), [j]) for j in range(num_chunks)])
 
+    @classmethod
+    def equal(cls, num_chunks=4, chunk_bits=16):
+        """x == y for two (c*l/2)-bit operands, chunk j = x_j || y_j (chunk 0 least significant): g = prod_j EQ_j.  The
+        term has c factors: c <= LH_SC_MAX_FACTORS."""
+        if not 1 <= num_chunks <= _ffi.LH_SC_MAX_FACTORS:
+            raise ArgumentError("equal: 1 to %d chunks (one factor of g each)" % _ffi.LH_SC_MAX_FACTORS)
+        return cls(num_chunks, chunk_bits, [(j, SUBTABLE_EQ) for j in range(num_chunks)], [(1, list(range(num_chunks)))])
+
+    @classmethod
+    def less_than(cls, num_chunks=4, chunk_bits=16):
+        """x < y (unsigned) for two (c*l/2)-bit operands, chunk j = x_j || y_j (chunk 0 least significant): memories
+        LTU_0..LTU_{c-1}, then EQ_1..EQ_{c-1} (alpha = 2c - 1); g = sum_j LTU_j prod_{k > j} EQ_k - the highest chunk that
+        differs decides.  The longest term has c factors: c <= LH_SC_MAX_FACTORS (c = 4, l = 16: 32-bit operands)."""
+        if not 1 <= num_chunks <= _ffi.LH_SC_MAX_FACTORS:
+            raise ArgumentError("less_than: 1 to %d chunks (the longest term of g has one factor each)" % _ffi.LH_SC_MAX_FACTORS)
+        c = num_chunks
+        memories = [(j, SUBTABLE_LTU) for j in range(c)] + [(j, SUBTABLE_EQ) for j in range(1, c)]
+        return cls(c, chunk_bits, memories, [(1, [j] + [c + k - 1 for k in range(j + 1, c)]) for j in range(c)])
+
+    def check(self):
+        """what to_c cannot express, or the library refuses anyway: ArgumentError before anything is marshalled"""
+        if len(self.memories) > _ffi.LH_LASSO_MAX_MEMORIES or self.c > _ffi.LH_LASSO_MAX_CHUNKS \
+                or len(self.g_terms) > _ffi.LH_LASSO_MAX_TERMS:
+            raise ArgumentError("table too large")
+        if any(not 0 <= kind <= SUBTABLE_LTU for _, kind in self.memories):
+            raise ArgumentError("lasso: unknown subtable")
+        if any(not 1 <= len(facs) <= _ffi.LH_SC_MAX_FACTORS for _, facs in self.g_terms):
+            raise ArgumentError("lasso: bad g term")
+
     def to_c(self):
+        self.check()
         t = lh_lasso_table()
         t.num_chunks, t.chunk_bits, t.num_memories = self.c, self.l, len(self.memories)
         for i, (j, kind) in enumerate(self.memories):
@@ -1436,9 +1467,6 @@ def lasso_prove(pp, table, num_vars, dims, transcript):
     """dims: c device buffers of u32[2^num_vars] chunk indices. Appends the proof to `transcript`."""
     if len(dims) != table.c:
         raise ArgumentError("expected %d dim columns" % table.c)
-    if len(table.memories) > _ffi.LH_LASSO_MAX_MEMORIES or table.c > _ffi.LH_LASSO_MAX_CHUNKS \
-            or len(table.g_terms) > _ffi.LH_LASSO_MAX_TERMS:
-        raise ArgumentError("table too large")
     t = table.to_c()
     _check(getattr(pp.ctx.lib, "lh_lasso_prove" + pp.suffix)(pp.ctx.h, *pp.head(), C.byref(t), num_vars, _ptr_array(dims),
                                                              transcript.p, *_tail(pp, transcript)))

@@ -15,6 +15,7 @@ LH_ERR_INVALID_SNARK, LH_ERR_SERIALIZATION, LH_ERR_TRANSCRIPT, LH_ERR_DEVICE, LH
 LH_SC_EVALUATIONS, LH_SC_COEFFICIENTS = 0, 1
 LH_SC_MAX_TERMS, LH_SC_MAX_FACTORS = 48, 4
 LH_LASSO_MAX_CHUNKS, LH_LASSO_MAX_MEMORIES, LH_LASSO_MAX_TERMS = 8, 16, 16
+LH_SUBTABLE_IDENTITY, LH_SUBTABLE_AND, LH_SUBTABLE_XOR, LH_SUBTABLE_OR, LH_SUBTABLE_EQ, LH_SUBTABLE_LTU = 0, 1, 2, 3, 4, 5
 LH_LASSO_NUM_PHASES = 9
 LH_BD_COLUMN_FR, LH_BD_COLUMN_U32 = 0, 1
 

@@ -158,6 +158,9 @@ static constexpr struct KnobRow {
     {"LH_FIN_LANES_MIN_BYTES", REAL, 0, -1, 1e18},     // -1: no launch hands over in lanes
     {"LH_SC_U32", INT, 1, 0, 1}, {"LH_OPEN_U32_ROUNDS", INT, 1, 0, 1}, {"LH_OPEN_FOLD_COLS", INT, 1, 0, 1},
     {"LH_OPEN_SHARE_SUMS", INT, 1, 0, 1, true},        // the opening takes the evaluation passes' quad sums (live: tests flip it)
+    // 1: a product g whose value fits 32 bits (less_than / equal tables) gets a 32-bit output column (lasso.cpp; off: its
+    // gain at 2^20 lookups stayed inside the spread; live: tests flip it)
+    {"LH_LASSO_PRODUCT_U32", INT, 0, 0, 1, true},
     // operation
     {"LH_HOST_THREADS", INT, 48, 0, 4096},             // host pool threads, the caller's included
     {"LH_JIT_CACHE", INT, 1, 0, 1}, {"LH_JIT_CACHE_DIR", PATH, 0, 0, 0},

@@ -173,7 +173,7 @@ struct Options {
 enum class Knob {  // (grouped as the table: thresholds, A/B switches, operation, diagnostics, test hooks)
   SC_TAIL_G, MSM_C_OFF, MSM_C_MAX, MSM_K2, MSM_SEG, MSM_SLAB_LOG, MSM_TREE_MAX, MSM_QUAD_MAX, MSM_TWO_LEVEL, MSM_HALF_MIN_LOG,
   MSM_HALF_COVER, EXPR_MONOMIALS, EXPR_JIT_MIN_VARS, EXPR_EF_MIN_VARS,
-  FIN_LANES_MIN_BYTES, SC_U32, OPEN_U32_ROUNDS, OPEN_FOLD_COLS, OPEN_SHARE_SUMS,
+  FIN_LANES_MIN_BYTES, SC_U32, OPEN_U32_ROUNDS, OPEN_FOLD_COLS, OPEN_SHARE_SUMS, LASSO_PRODUCT_U32,
   HOST_THREADS, JIT_CACHE, JIT_CACHE_DIR, EXPR_JIT, SC_TAIL_TIMEOUT_MS, GKR_START_TIMEOUT_MS, COMM_WAIT_TIMEOUT_MS, COMM_A2A,
   COMM_PROBE,
   HOST_TRACE, SC_TAIL_TRACE, GKR_TRACE, SC_DEBUG, MSM_DEBUG, HP_DEBUG, COMM_DEBUG, OPEN_SMALL_CHECK,
@@ -557,6 +557,16 @@ struct LassoGSmall {  // g = sum_t coeff[t] * E_{fac[t]} with 32-bit coefficient
   const uint32_t* e[LH_LASSO_MAX_MEMORIES];
 };
 void k_lasso_output_small(Ctx&, const LassoGSmall& g, size_t n, uint32_t* a);
+// g with product terms whose largest value fits 32 bits (lasso.cpp: the bound from the subtables' widths - the comparison
+// and equality tables): integer products of the 32-bit reads, no partial product can exceed the bound
+struct LassoGSmallProd {
+  uint32_t num_terms;
+  uint32_t coeff[LH_LASSO_MAX_TERMS];
+  uint8_t nfac[LH_LASSO_MAX_TERMS];
+  uint8_t fac[LH_LASSO_MAX_TERMS][LH_SC_MAX_FACTORS];
+  const uint32_t* e[LH_LASSO_MAX_MEMORIES];
+};
+void k_lasso_output_small_prod(Ctx&, const LassoGSmallProd& g, size_t n, uint32_t* a);
 // canonical value of every entry as u32; false if an entry is not below 2^bits
 bool k_fr_to_index(Ctx&, const Fr* in, size_t n, uint32_t bits, uint32_t* out);
 // both tables hold Montgomery residues in [0, r): equal values have equal limbs

@@ -554,6 +554,7 @@ Pcs hyrax_pcs(Ctx&, const IpaParams&, size_t poly_size, size_t batch_size);
 struct LassoColumns {  // small-valued witness columns as u32 (arena memory of the caller's scope)
   std::vector<uint32_t*> rts, fcs, E;
   std::vector<uint32_t*> dim_sorted, dim_index;  // (keep_sorted) every dim column sorted by value + source positions
+  uint32_t a_bits = 0;  // a 32-bit output column of a product g: every entry < 2^a_bits (0: none, or the linear g's column)
 };
 struct LassoClaims {  // points and claimed evaluations that remain to be opened
   std::vector<HFr> r, r_z, r_N, r_M;
@@ -562,23 +563,44 @@ struct LassoClaims {  // points and claimed evaluations that remain to be opened
   std::vector<HFr> ev_n;  // dim_j | read_ts_j | E_i at r_N
   std::vector<HFr> ev_l;  // final_cts_j at r_M
 };
-// T[d] and the d's sorted by T[d] for the bitwise subtables, on the device (arena memory of the caller's scope; the host
-// staging lives as long as this object, i.e. past the msm_batch that consumes them)
+constexpr uint32_t LH_SUBTABLE_KINDS = 6;  // IDENTITY .. LTU (include/lasso_hip.h)
+// THE width rule: every entry of a subtable of 2^l entries is below 2^lasso_subtable_bits(kind, l).  What is promised to
+// the u32 MSM and the column commits (known_bits) comes from here: a bound too small yields wrong commitments.
+inline uint32_t lasso_subtable_bits(uint32_t kind, size_t l) {
+  if (kind == LH_SUBTABLE_IDENTITY) return (uint32_t)l;
+  if (kind == LH_SUBTABLE_EQ || kind == LH_SUBTABLE_LTU) return 1;
+  return (uint32_t)(l / 2);  // AND, XOR, OR of two (l / 2)-bit halves
+}
+// entry m = x || y (y: the low l / 2 bits) of a non-identity subtable - the host's copy of kernels_poly.hip subtable_entry
+inline uint32_t lasso_subtable_entry_host(uint32_t kind, uint32_t m, size_t l) {
+  const size_t h = l / 2;
+  const uint32_t x = m >> h, y = m & (((uint32_t)1 << h) - 1u);
+  switch (kind) {
+    case LH_SUBTABLE_AND: return x & y;
+    case LH_SUBTABLE_XOR: return x ^ y;
+    case LH_SUBTABLE_OR: return x | y;
+    case LH_SUBTABLE_EQ: return x == y ? 1u : 0u;
+    case LH_SUBTABLE_LTU: return x < y ? 1u : 0u;
+    default: return m;
+  }
+}
+// T[d] and the d's sorted by T[d] for the non-identity subtables, on the device (arena memory of the caller's scope; the
+// host staging lives as long as this object, i.e. past the msm_batch that consumes them)
 struct SubtableOrders {
   Ctx& c;
   size_t l;
-  std::vector<uint32_t> h_tab[3], h_ord[3];
-  uint32_t *d_tab[3] = {nullptr, nullptr, nullptr}, *d_ord[3] = {nullptr, nullptr, nullptr};
+  std::vector<uint32_t> h_tab[LH_SUBTABLE_KINDS], h_ord[LH_SUBTABLE_KINDS];
+  uint32_t *d_tab[LH_SUBTABLE_KINDS] = {}, *d_ord[LH_SUBTABLE_KINDS] = {};
   SubtableOrders(Ctx& c_, size_t l_) : c(c_), l(l_) {}
   void get(int kind, const uint32_t** table, const uint32_t** order) {
+    LH_REQUIRE(kind > LH_SUBTABLE_IDENTITY && kind < (int)LH_SUBTABLE_KINDS, LH_ERR_ARG, "lasso: unknown subtable");
     if (!d_tab[kind]) {
-      const size_t M = (size_t)1 << l, h = l / 2, V = (size_t)1 << h;
+      const size_t M = (size_t)1 << l, V = (size_t)1 << lasso_subtable_bits((uint32_t)kind, l);
       std::vector<uint32_t>&tab = h_tab[kind], &ord = h_ord[kind];
       tab.resize(M), ord.resize(M);
       std::vector<uint32_t> start(V + 1, 0);
       for (size_t d = 0; d < M; d++) {
-        const uint32_t x = (uint32_t)(d >> h), y = (uint32_t)(d & (V - 1));
-        tab[d] = kind == LH_SUBTABLE_AND ? (x & y) : (x ^ y);
+        tab[d] = lasso_subtable_entry_host((uint32_t)kind, (uint32_t)d, l);
         start[tab[d] + 1]++;
       }
       for (size_t v = 0; v < V; v++) start[v + 1] += start[v];
@@ -594,7 +616,8 @@ struct SubtableOrders {
 
 void lasso_check_table(const lh_lasso_table& tb);
 // a_out (optional): the output column a = g(E) as field elements; a_small_out (optional): the same as a 32-bit column
-// when g is linear with small coefficients and the value fits (then *a_out stays null)
+// when g is linear with small coefficients and the value fits, or has product terms whose bound fits (LassoColumns::a_bits;
+// then *a_out stays null)
 LassoColumns lasso_witness_columns(Ctx&, const lh_lasso_table&, size_t n, const uint32_t* const* d_dims, Fr** a_out,
                                    uint32_t** a_small_out = nullptr, bool keep_sorted = false);
 // `a`: the output column as field elements, or null with `a_small` given

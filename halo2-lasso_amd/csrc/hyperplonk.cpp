@@ -312,7 +312,7 @@ void hyperplonk_prove_phases(Ctx& c, const Pcs& pcs, const lh_hp_param& pp, cons
         for (size_t j = 0; j < cc; j++) lasso_cols.push_back(PcsColumn{st.cols.rts[j], true, n_loc, 32});
         for (size_t i = 0; i < alpha; i++)
           lasso_cols.push_back(PcsColumn{st.cols.E[i], true, n_loc,
-                                         (uint32_t)(tb.memory_subtable[i] == LH_SUBTABLE_IDENTITY ? l : std::max<size_t>(l / 2, 1))});
+                                         std::max<uint32_t>(lasso_subtable_bits(tb.memory_subtable[i], l), 1)});
         for (size_t j = 0; j < cc; j++) lasso_cols.push_back(PcsColumn{st.cols.fcs[j], true, M, 32});
         continue;
       }

@@ -1196,7 +1196,14 @@ void k_quotient_step(Ctx& c, const Fr* rem, size_t half, const Fr& x, Fr* q, Fr*
 __device__ __forceinline__ uint32_t subtable_entry(int kind, uint32_t m, uint32_t bits) {
   uint32_t h = bits >> 1;
   uint32_t x = m >> h, y = m & ((1u << h) - 1u);
-  return kind == LH_SUBTABLE_IDENTITY ? m : kind == LH_SUBTABLE_AND ? (x & y) : (x ^ y);
+  switch (kind) {  // (host.hpp lasso_subtable_entry_host is the host's copy; the widths: lasso_subtable_bits)
+    case LH_SUBTABLE_IDENTITY: return m;
+    case LH_SUBTABLE_AND: return x & y;
+    case LH_SUBTABLE_XOR: return x ^ y;
+    case LH_SUBTABLE_OR: return x | y;
+    case LH_SUBTABLE_EQ: return x == y ? 1u : 0u;
+    default: return x < y ? 1u : 0u;  // LH_SUBTABLE_LTU (lasso_check_table lets no other kind through)
+  }
 }
 
 // read_ts[k] = number of earlier lookups of the same address; final_cts[a] = total count of address a.
@@ -1595,6 +1602,25 @@ __global__ void lasso_output_small_kernel(LassoGSmall g, size_t n, uint32_t* __r
 void k_lasso_output_small(Ctx& c, const LassoGSmall& g, size_t n, uint32_t* a) {
   ProfScope ps(c, "lasso_output", 4.0 * n * (g.num_terms + 1), 0.0, (double)n);
   if (n) hipLaunchKernelGGL(lasso_output_small_kernel, grid_for(n), 256, 0, c.stream, g, n, a);
+}
+// product terms whose value fits 32 bits (comparison / equality tables: a is a column of zeros and ones): integer
+// products of the 32-bit reads (a column that enters several terms is read again from the cache), 4 bytes written
+__global__ void lasso_output_small_prod_kernel(LassoGSmallProd g, size_t n, uint32_t* __restrict__ a) {
+  GSTRIDE(i, n) {
+    uint32_t acc = 0;
+    for (uint32_t t = 0; t < g.num_terms; t++) {
+      uint32_t v = g.coeff[t];
+      for (int k = 0; k < g.nfac[t]; k++) v *= g.e[g.fac[t][k]][i];
+      acc += v;
+    }
+    a[i] = acc;
+  }
+}
+void k_lasso_output_small_prod(Ctx& c, const LassoGSmallProd& g, size_t n, uint32_t* a) {
+  uint32_t num_mem = 0;
+  for (uint32_t m = 0; m < LH_LASSO_MAX_MEMORIES; m++) num_mem += g.e[m] ? 1 : 0;
+  ProfScope ps(c, "lasso_output_small_prod", 4.0 * n * (num_mem + 1), 0.0, (double)n);
+  if (n) hipLaunchKernelGGL(lasso_output_small_prod_kernel, grid_for(n), 256, 0, c.stream, g, n, a);
 }
 void k_lasso_output(Ctx& c, const LassoG& g, size_t n, Fr* a) {
   ProfScope ps(c, "lasso_output", 36.0 * n, 2.0 * n, (double)n);

@@ -61,7 +61,7 @@ void lasso_check_table(const lh_lasso_table& tb) {
   LH_REQUIRE(tb.num_terms >= 1 && tb.num_terms <= LH_LASSO_MAX_TERMS, LH_ERR_ARG, "lasso: bad g term count");
   for (size_t i = 0; i < alpha; i++) {
     LH_REQUIRE(tb.memory_chunk[i] < cc, LH_ERR_ARG, "lasso: memory chunk out of range");
-    LH_REQUIRE(tb.memory_subtable[i] <= LH_SUBTABLE_XOR, LH_ERR_ARG, "lasso: unknown subtable");
+    LH_REQUIRE(tb.memory_subtable[i] < LH_SUBTABLE_KINDS, LH_ERR_ARG, "lasso: unknown subtable");
     if (tb.memory_subtable[i] != LH_SUBTABLE_IDENTITY)
       LH_REQUIRE(l % 2 == 0, LH_ERR_ARG, "lasso: bitwise subtables need an even chunk_bits");
   }
@@ -207,7 +207,7 @@ LassoColumns lasso_witness_columns(Ctx& c, const lh_lasso_table& tb, size_t n, c
       uint64_t canon[4];
       co.to_canonical(canon);
       const size_t i = tb.g_factor[m][0];
-      const size_t ebits = tb.memory_subtable[i] == LH_SUBTABLE_IDENTITY ? l : l / 2;
+      const size_t ebits = lasso_subtable_bits(tb.memory_subtable[i], l);
       ok = tb.g_num_factors[m] == 1 && !canon[1] && !canon[2] && !canon[3] && canon[0] <= 0xffffffffull && ebits <= 32;
       if (!ok) break;
       max_val += canon[0] * (((uint64_t)1 << ebits) - 1);
@@ -221,6 +221,44 @@ LassoColumns lasso_witness_columns(Ctx& c, const lh_lasso_table& tb, size_t n, c
       k_lasso_output_small(c, gs, N, *a_small_out);
       if (a_out) *a_out = nullptr;
       return w;
+    }
+    // g with product terms (less_than / equal): bound = sum_m coeff_m prod_k (2^bits(E_f(m,k)) - 1) from the subtables'
+    // widths; with LH_LASSO_PRODUCT_U32=1 a 32-bit column when every coefficient and the bound fit 32 bits (default 0: the
+    // field-element column below - the proof bytes are the same)
+    bool product_g = false;
+    for (uint32_t m = 0; m < tb.num_terms; m++) product_g = product_g || tb.g_num_factors[m] > 1;
+    if (product_g && knob(Knob::LASSO_PRODUCT_U32) != 0) {
+      LassoGSmallProd gp;
+      memset(&gp, 0, sizeof(gp));
+      gp.num_terms = tb.num_terms;
+      unsigned __int128 bound = 0;
+      bool fits = true;
+      for (uint32_t m = 0; m < tb.num_terms && fits; m++) {
+        HFr co;
+        memcpy(&co, &tb.g_coeff[m], 32);
+        uint64_t canon[4];
+        co.to_canonical(canon);
+        fits = !canon[1] && !canon[2] && !canon[3] && canon[0] <= 0xffffffffull;
+        unsigned __int128 term = canon[0];  // (< 2^32, and every step below keeps it <= 2^32 * (2^32 - 1) < 2^128)
+        for (int k = 0; k < tb.g_num_factors[m] && fits; k++) {
+          const uint32_t eb = lasso_subtable_bits(tb.memory_subtable[tb.g_factor[m][k]], l);
+          term *= ((uint64_t)1 << eb) - 1;  // (eb <= l < 31)
+          fits = term <= 0xffffffffull;
+          gp.fac[m][k] = tb.g_factor[m][k];
+        }
+        bound += term;
+        fits = fits && bound <= 0xffffffffull;
+        gp.coeff[m] = (uint32_t)canon[0];
+        gp.nfac[m] = tb.g_num_factors[m];
+      }
+      if (fits) {
+        for (size_t i = 0; i < alpha; i++) gp.e[i] = w.E[i];
+        *a_small_out = c.arena.alloc_n<uint32_t>(N);
+        k_lasso_output_small_prod(c, gp, N, *a_small_out);
+        w.a_bits = bound ? 64u - (uint32_t)__builtin_clzll((uint64_t)bound) : 1u;
+        if (a_out) *a_out = nullptr;
+        return w;
+      }
     }
   }
   if (a_out) {
@@ -498,7 +536,9 @@ void lasso_prove(Ctx& c, const Pcs& pcs, const lh_lasso_table& tb, size_t n, con
   auto open_columns = [&] {
     if (!small.empty()) return;
     small.assign(num_n + cc, SmallPoly());
-    if (a_small) {
+    if (a_small && w.a_bits) {  // (product g: a column of its own, every entry below 2^a_bits)
+      small[0] = SmallPoly{a_small, N, w.a_bits};
+    } else if (a_small) {
       for (uint32_t m = 0; m < tb.num_terms; m++) {
         HFr co;
         memcpy(&co, &tb.g_coeff[m], 32);
@@ -519,7 +559,7 @@ void lasso_prove(Ctx& c, const Pcs& pcs, const lh_lasso_table& tb, size_t n, con
       }
     }
     for (size_t i = 0; i < alpha; i++)
-      small[1 + 2 * cc + i] = SmallPoly{E[i], N, (uint32_t)(tb.memory_subtable[i] == LH_SUBTABLE_IDENTITY ? l : l / 2)};
+      small[1 + 2 * cc + i] = SmallPoly{E[i], N, lasso_subtable_bits(tb.memory_subtable[i], l)};
     auto push = [&](size_t poly, size_t point) {
       lh_evaluation e;
       memset(&e, 0, sizeof(e));
@@ -553,14 +593,14 @@ void lasso_prove(Ctx& c, const Pcs& pcs, const lh_lasso_table& tb, size_t n, con
     }
     const size_t total = 1 + 3 * cc + alpha, k = pcs.chunks;
     std::vector<PcsColumn> cols(total, PcsColumn{nullptr, true, 0, 1});
-    cols[0] = a_small ? PcsColumn{a_small, true, N, 32} : PcsColumn{a, false, N, 0};
+    cols[0] = a_small ? PcsColumn{a_small, true, N, w.a_bits ? w.a_bits : 32u} : PcsColumn{a, false, N, 0};
     for (size_t j = 0; j < cc; j++) {
       cols[1 + j] = PcsColumn{d_dims[j], true, N, (uint32_t)l};
       cols[1 + cc + j] = PcsColumn{rts[j], true, N, bits_of(count_ors[j])};
       cols[1 + 2 * cc + alpha + j] = PcsColumn{fcs[j], true, M, bits_of(count_ors[j])};
     }
     for (size_t i = 0; i < alpha; i++)
-      if (tb.memory_subtable[i] != LH_SUBTABLE_IDENTITY) cols[1 + 2 * cc + i] = PcsColumn{E[i], true, N, (uint32_t)std::max<size_t>(l / 2, 1)};
+      if (tb.memory_subtable[i] != LH_SUBTABLE_IDENTITY) cols[1 + 2 * cc + i] = PcsColumn{E[i], true, N, std::max<uint32_t>(lasso_subtable_bits(tb.memory_subtable[i], l), 1)};
     if (pcs.commit_columns_and_write) {
       // a scheme whose commitments are no points (Brakedown: Merkle roots, and the zero column's is a root like any other,
       // so the identity mask is zero): it writes them itself and finds them again by the columns' pointers at the opening -
@@ -601,7 +641,12 @@ void lasso_prove(Ctx& c, const Pcs& pcs, const lh_lasso_table& tb, size_t n, con
       jobs.push_back(MsmJob{col, u32, bases, len});
       slot.push_back(pos);
     };
-    if (!linear_g) add_job(0, a, false, N);
+    if (!linear_g && a_small) {  // (product g with a 32-bit output column: a u32 job, every entry below 2^a_bits)
+      add_job(0, a_small, true, N);
+      jobs.back().known_bits = w.a_bits;
+    } else if (!linear_g) {
+      add_job(0, a, false, N);
+    }
     std::vector<size_t> dim_job(cc);
     for (size_t j = 0; j < cc; j++) {
       dim_job[j] = jobs.size(), add_job(1 + j, d_dims[j], true, N);
@@ -647,14 +692,15 @@ void lasso_prove(Ctx& c, const Pcs& pcs, const lh_lasso_table& tb, size_t n, con
     for (size_t i = 0; i < alpha; i++)
       if (tb.memory_subtable[i] != LH_SUBTABLE_IDENTITY) {
         add_job(1 + 2 * cc + i, E[i], true, N);
-        if (l <= 20) {
+        // (the derived route has no bucket for dim = 0 - msm.hip: T[0] must be 0 - and EQ has T[0] = 1: an ordinary column)
+        if (l <= 20 && tb.memory_subtable[i] != LH_SUBTABLE_EQ) {
           MsmJob& jb = jobs.back();
           jb.derived_parent = (int)dim_job[tb.memory_chunk[i]];
           orders.get((int)tb.memory_subtable[i], &jb.d_table, &jb.d_order);
-          jb.table_in_bits = (uint32_t)l, jb.table_out_bits = (uint32_t)(l / 2);
+          jb.table_in_bits = (uint32_t)l, jb.table_out_bits = lasso_subtable_bits(tb.memory_subtable[i], l);
           c.route.v[RouteStats::DERIVED]++;
         }
-        jobs.back().known_bits = (uint32_t)(l / 2);  // AND / XOR of two (l/2)-bit halves
+        jobs.back().known_bits = lasso_subtable_bits(tb.memory_subtable[i], l);  // (l/2)-bit halves combined, or one bit
       }
     // final_cts (2^l entries) is replicated - but an MSM is additive over point ranges (the chunk-then-sum of
     // util/arithmetic/msm.rs:101-114): rank s commits the counts [s 2^l / R, (s + 1) 2^l / R) against the same range of

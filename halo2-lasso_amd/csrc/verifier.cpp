@@ -962,11 +962,23 @@ static std::vector<HFr> verify_grand_product(const std::vector<size_t>& depth, T
 static HFr subtable_mle_eval(uint32_t kind, const std::vector<HFr>& point) {  // lasso.py:55-72
   if (kind == LH_SUBTABLE_IDENTITY) return identity_eval(point);
   const size_t h = point.size() / 2;
+  if (kind == LH_SUBTABLE_EQ || kind == LH_SUBTABLE_LTU) {
+    // e_i = x_i y_i + (1 - x_i)(1 - y_i);  EQ = prod_i e_i;  LTU = sum_i (1 - x_i) y_i prod_{k > i} e_k (the high bits
+    // decide first): from the top bit down, `eq` is the product of the e_k above bit i
+    HFr eq = HFr::one(), lt = HFr::zero();
+    for (size_t i = h; i-- > 0;) {
+      const HFr &yi = point[i], &xi = point[h + i];
+      const HFr xy = xi * yi;
+      lt += (yi - xy) * eq;
+      eq *= xy.dbl() + HFr::one() - xi - yi;
+    }
+    return kind == LH_SUBTABLE_EQ ? eq : lt;
+  }
   HFr acc = HFr::zero(), p = HFr::one();
   for (size_t i = 0; i < h; i++) {
     const HFr &yi = point[i], &xi = point[h + i];
     HFr xy = xi * yi;
-    acc += (kind == LH_SUBTABLE_AND ? xy : xi + yi - xy.dbl()) * p;
+    acc += (kind == LH_SUBTABLE_AND ? xy : kind == LH_SUBTABLE_OR ? xi + yi - xy : xi + yi - xy.dbl()) * p;
     p = p.dbl();
   }
   return acc;
@@ -979,7 +991,7 @@ static void lasso_verify_check_table(const lh_lasso_table& tb, size_t n) {
              LH_ERR_ARG, "lasso: bad table");
   LH_REQUIRE(n >= 1 && l >= 1 && n < 32 && l < 32, LH_ERR_ARG, "lasso: need at least one variable");
   for (size_t i = 0; i < alpha; i++)
-    LH_REQUIRE(tb.memory_chunk[i] < c && tb.memory_subtable[i] <= LH_SUBTABLE_XOR, LH_ERR_ARG, "lasso: bad memory");
+    LH_REQUIRE(tb.memory_chunk[i] < c && tb.memory_subtable[i] < LH_SUBTABLE_KINDS, LH_ERR_ARG, "lasso: bad memory");
   LH_REQUIRE(tb.num_terms >= 1, LH_ERR_ARG, "lasso: bad g term count");
   for (size_t m = 0; m < tb.num_terms; m++)
     LH_REQUIRE(tb.g_num_factors[m] >= 1 && tb.g_num_factors[m] <= LH_SC_MAX_FACTORS, LH_ERR_ARG, "lasso: bad g term");

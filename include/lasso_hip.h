@@ -220,6 +220,16 @@ lh_status lh_mkzg_batch_open(lh_ctx*, const lh_srs*, size_t num_vars,
 #define LH_SUBTABLE_IDENTITY 0
 #define LH_SUBTABLE_AND 1
 #define LH_SUBTABLE_XOR 2
+/* Index m = x || y with y in the low chunk_bits / 2 bits, as for AND and XOR (an even chunk_bits, or LH_ERR_ARG):
+ *   OR   T[m] = x | y        values of chunk_bits / 2 bits
+ *   EQ   T[m] = (x == y)     one bit
+ *   LTU  T[m] = (x <  y)     one bit, unsigned
+ * Equality of two (c chunk_bits / 2)-bit operands is g = prod_j E_EQ_j, unsigned less-than is
+ * g = sum_j E_LTU_j prod_{k > j} E_EQ_k (chunk 0 least significant): the longest term has c factors, so such a table has
+ * c <= LH_SC_MAX_FACTORS chunks (a term with more factors is LH_ERR_ARG like any other bad g term). */
+#define LH_SUBTABLE_OR 3
+#define LH_SUBTABLE_EQ 4
+#define LH_SUBTABLE_LTU 5
 #define LH_LASSO_MAX_CHUNKS 8
 #define LH_LASSO_MAX_MEMORIES 16
 #define LH_LASSO_MAX_TERMS 16
