@@ -82,6 +82,45 @@ pub fn less_than_table(num_chunks: u32, chunk_bits: u32) -> Option<lh_lasso_tabl
     Some(t)
 }
 
+/// A caller-registered subtable (lh_subtable_register): 2^chunk_bits 32-bit entries, chunk_bits <= LH_SUBTABLE_CUSTOM_MAX_BITS.
+/// The registry is process-wide and needs no ctx; `kind()` is what `lh_lasso_table::memory_subtable` names.  Kinds are never
+/// reused: once the `Subtable` is dropped its kind is refused (LH_ERR_ARG).  A prove or verify that has looked the table up
+/// keeps its entries alive.
+pub struct Subtable {
+    kind: u32,
+    chunk_bits: u32,
+    value_bits: u32,
+    digest: [u8; 32],
+}
+impl Subtable {
+    /// `values.len()` must be 2^chunk_bits with 1 <= chunk_bits <= LH_SUBTABLE_CUSTOM_MAX_BITS
+    pub fn register(values: &[u32]) -> Result<Self, Error> {
+        let n = values.len();
+        if n < 2 || !n.is_power_of_two() {
+            check(LH_ERR_ARG)?; // (the library reads 2^chunk_bits values: the length must be that)
+        }
+        let mut t = Subtable { kind: 0, chunk_bits: 0, value_bits: 0, digest: [0; 32] };
+        check(unsafe { lh_subtable_register(values.as_ptr(), n.trailing_zeros(), &mut t.kind) })?;
+        check(unsafe { lh_subtable_info(t.kind, &mut t.chunk_bits, &mut t.value_bits, t.digest.as_mut_ptr()) })?;
+        Ok(t)
+    }
+    pub fn kind(&self) -> u32 { self.kind }
+    pub fn chunk_bits(&self) -> u32 { self.chunk_bits }
+    /// bit length of the largest entry (0: an all-zero table)
+    pub fn value_bits(&self) -> u32 { self.value_bits }
+    /// Keccak-256 of the entries as little-endian words: for comparing registrations across hosts, in no transcript
+    pub fn digest(&self) -> &[u8; 32] { &self.digest }
+}
+impl Drop for Subtable {
+    fn drop(&mut self) {
+        unsafe { lh_subtable_unregister(self.kind) };
+    }
+}
+/// one memory per chunk into the registered subtable, g = sum_j 2^(shift_bits * j) * E_j (the shape of the bitwise tables)
+pub fn custom_table(subtable: &Subtable, num_chunks: u32, shift_bits: u32) -> lh_lasso_table {
+    table(num_chunks, subtable.chunk_bits(), subtable.kind(), shift_bits)
+}
+
 /// dims[j]: chunk indices (< 2^chunk_bits) of every lookup, 2^num_vars entries each
 pub fn prove(pp: &HipProverParam, table: &lh_lasso_table, num_vars: usize, dims: &[DeviceVec<u32>],
              transcript: &mut impl TranscriptWrite<G1Affine, Fr>) -> Result<(), Error> {

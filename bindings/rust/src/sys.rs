@@ -116,6 +116,10 @@ pub const LH_SUBTABLE_XOR: u32 = 2;
 pub const LH_SUBTABLE_OR: u32 = 3;
 pub const LH_SUBTABLE_EQ: u32 = 4;
 pub const LH_SUBTABLE_LTU: u32 = 5;
+// caller-registered subtables (lh_subtable_register): kinds from LH_SUBTABLE_CUSTOM_BASE up; 6 .. 0xFF stay LH_ERR_ARG
+pub const LH_SUBTABLE_CUSTOM_BASE: u32 = 0x100;
+pub const LH_SUBTABLE_CUSTOM_MAX: usize = 64;
+pub const LH_SUBTABLE_CUSTOM_MAX_BITS: u32 = 20;
 #[repr(C)] #[derive(Clone, Copy)]
 pub struct lh_lasso_table {
     pub num_chunks: u32,
@@ -293,6 +297,10 @@ extern "C" {
     pub fn lh_ctx_set_option(ctx: *mut lh_ctx, name: *const c_char, value: i64) -> lh_status;
     pub fn lh_ctx_get_option(ctx: *mut lh_ctx, name: *const c_char, out: *mut i64) -> lh_status;
     pub fn lh_lasso_last_route(ctx: *mut lh_ctx, out: *mut lh_lasso_route) -> lh_status;
+    // caller-registered subtables: host only, no ctx (lasso.rs Subtable)
+    pub fn lh_subtable_register(values: *const u32, chunk_bits: u32, out_kind: *mut u32) -> lh_status;
+    pub fn lh_subtable_unregister(kind: u32) -> lh_status;
+    pub fn lh_subtable_info(kind: u32, chunk_bits: *mut u32, value_bits: *mut u32, digest32: *mut u8) -> lh_status;
     pub fn lh_lasso_prove_sharded(ctx: *mut lh_ctx, srs: *const lh_srs, table: *const lh_lasso_table, num_vars: usize,
                                   d_dims_local: *const *const u32, t: *mut lh_transcript) -> lh_status;
     // HyperPlonk
@@ -332,6 +340,9 @@ extern "C" {
                               temp_bytes: *mut usize) -> lh_status;
     // (development) the 32-bit column kernels on their own
     pub fn lh_debug_u32_columns(ctx: *mut lh_ctx, op: i32, args: *const lh_debug_u32_args) -> lh_status;
+    // (development) the Lasso witness's subtable read for one memory, built-in or registered kind
+    pub fn lh_debug_lasso_subtable_read(ctx: *mut lh_ctx, kind: u32, chunk_bits: u32, d_dim: *const u32, n: usize,
+                                        d_out: *mut u32) -> lh_status;
     // Zeromorph over univariate KZG: lh_ukzg_setup, lh_usrs_*, lh_zeromorph_* follow the same shapes
     // (include/lasso_hip.h, section f3) and are bound the same way when HyperPlonk<Zeromorph<..>> is wanted.
     // Univariate KZG on its own and Gemini over it (include/lasso_hip.h, section f3b); lh_usrs / lh_ukzg_vp are opaque here

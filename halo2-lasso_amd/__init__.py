@@ -1402,8 +1402,58 @@ class Brakedown:
 
 
 # ------------------------------------------------------------------ Lasso
+class Subtable:
+    """A caller-registered subtable (lh_subtable_register): 2^chunk_bits 32-bit entries, chunk_bits <= 20.  The registry is
+    process-wide and needs no Context; `kind` is what a memory of a LassoTable names (the Subtable itself does as well).
+    Kinds are never reused: after close() the kind is refused.  At most LH_SUBTABLE_CUSTOM_MAX are live at a time.
+
+        with hl.Subtable.register(sbox) as t:
+            table = hl.LassoTable(1, 8, [(0, t)], [(1, [0])])
+    """
+
+    def __init__(self, kind):
+        self.kind = int(kind)
+        cb, vb, dg = C.c_uint32(), C.c_uint32(), C.create_string_buffer(32)
+        _check(_ffi.load().lh_subtable_info(self.kind, C.byref(cb), C.byref(vb), dg))
+        self.chunk_bits, self.value_bits, self.digest = cb.value, vb.value, dg.raw
+
+    @classmethod
+    def register(cls, values):
+        values = [int(v) for v in values]
+        n = len(values)
+        if n < 2 or n & (n - 1) or n > 1 << _ffi.LH_SUBTABLE_CUSTOM_MAX_BITS:
+            raise ArgumentError("subtable: 2^chunk_bits values, chunk_bits in [1, %d]" % _ffi.LH_SUBTABLE_CUSTOM_MAX_BITS)
+        if any(not 0 <= v < 1 << 32 for v in values):
+            raise ArgumentError("subtable: values are 32-bit unsigned")
+        kind = C.c_uint32()
+        _check(_ffi.load().lh_subtable_register((C.c_uint32 * n)(*values), n.bit_length() - 1, C.byref(kind)))
+        return cls(kind.value)
+
+    def close(self):
+        if self.kind is not None:
+            kind, self.kind = self.kind, None
+            _check(_ffi.load().lh_subtable_unregister(kind))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __int__(self):
+        if self.kind is None:
+            raise ArgumentError("subtable: closed")
+        return self.kind
+
+    __index__ = __int__
+
+
+_LTS_SUBTABLES = {}  # chunk_bits -> the signed top-chunk subtable of less_than_signed, registered once per process
+
+
 class LassoTable:
-    """Decomposable table: c chunks of l bits, memories (chunk, subtable), g = sum coeff * prod E_i."""
+    """Decomposable table: c chunks of l bits, memories (chunk, subtable), g = sum coeff * prod E_i.  A memory's subtable
+    is a SUBTABLE_* kind, a Subtable, or the kind of one."""
 
     def __init__(self, num_chunks, chunk_bits, memories, g_terms):
         self.c, self.l, self.memories = num_chunks, chunk_bits, list(memories)
@@ -1438,13 +1488,41 @@ class LassoTable:
         memories = [(j, SUBTABLE_LTU) for j in range(c)] + [(j, SUBTABLE_EQ) for j in range(1, c)]
         return cls(c, chunk_bits, memories, [(1, [j] + [c + k - 1 for k in range(j + 1, c)]) for j in range(c)])
 
+    @classmethod
+    def less_than_signed(cls, num_chunks=4, chunk_bits=16):
+        """sx < sy for two two's-complement (c*l/2)-bit operands: less_than's shape with the top chunk's LTU replaced by a
+        registered subtable, (sx < sy) on the signed l/2-bit halves of that chunk (below the top chunk the comparison is the
+        unsigned one).  That subtable has T[0] = 0; it is registered once per chunk_bits and kept for the process."""
+        if not 1 <= num_chunks <= _ffi.LH_SC_MAX_FACTORS:
+            raise ArgumentError("less_than_signed: 1 to %d chunks (the longest term of g has one factor each)" % _ffi.LH_SC_MAX_FACTORS)
+        if chunk_bits % 2 or not 2 <= chunk_bits <= _ffi.LH_SUBTABLE_CUSTOM_MAX_BITS:
+            raise ArgumentError("less_than_signed: an even chunk_bits in [2, %d]" % _ffi.LH_SUBTABLE_CUSTOM_MAX_BITS)
+        if chunk_bits not in _LTS_SUBTABLES:
+            h = chunk_bits // 2
+            signed = lambda v: v - (1 << h) if v >> (h - 1) else v
+            _LTS_SUBTABLES[chunk_bits] = Subtable.register(
+                [int(signed(m >> h) < signed(m & ((1 << h) - 1))) for m in range(1 << chunk_bits)])
+        c = num_chunks
+        memories = [(j, SUBTABLE_LTU) for j in range(c - 1)] + [(c - 1, _LTS_SUBTABLES[chunk_bits])] \
+            + [(j, SUBTABLE_EQ) for j in range(1, c)]
+        return cls(c, chunk_bits, memories, [(1, [j] + [c + k - 1 for k in range(j + 1, c)]) for j in range(c)])
+
     def check(self):
         """what to_c cannot express, or the library refuses anyway: ArgumentError before anything is marshalled"""
         if len(self.memories) > _ffi.LH_LASSO_MAX_MEMORIES or self.c > _ffi.LH_LASSO_MAX_CHUNKS \
                 or len(self.g_terms) > _ffi.LH_LASSO_MAX_TERMS:
             raise ArgumentError("table too large")
-        if any(not 0 <= kind <= SUBTABLE_LTU for _, kind in self.memories):
-            raise ArgumentError("lasso: unknown subtable")
+        for _, kind in self.memories:
+            kind = int(kind)
+            if 0 <= kind <= SUBTABLE_LTU:
+                continue
+            if kind < _ffi.LH_SUBTABLE_CUSTOM_BASE:
+                raise ArgumentError("lasso: unknown subtable")
+            cb = C.c_uint32()  # a registered kind, and of this table's chunk size
+            if _ffi.load().lh_subtable_info(kind, C.byref(cb), None, None) != _ffi.LH_OK:
+                raise ArgumentError("lasso: subtable kind %d is not registered" % kind)
+            if cb.value != self.l:
+                raise ArgumentError("lasso: chunk_bits %d differs from the registered subtable's %d" % (self.l, cb.value))
         if any(not 1 <= len(facs) <= _ffi.LH_SC_MAX_FACTORS for _, facs in self.g_terms):
             raise ArgumentError("lasso: bad g term")
 
@@ -1453,7 +1531,7 @@ class LassoTable:
         t = lh_lasso_table()
         t.num_chunks, t.chunk_bits, t.num_memories = self.c, self.l, len(self.memories)
         for i, (j, kind) in enumerate(self.memories):
-            t.memory_chunk[i], t.memory_subtable[i] = j, kind
+            t.memory_chunk[i], t.memory_subtable[i] = j, int(kind)
         t.num_terms = len(self.g_terms)
         for m, (co, facs) in enumerate(self.g_terms):
             C.memmove(C.byref(t.g_coeff[m]), fr_to_bytes(co), 32)

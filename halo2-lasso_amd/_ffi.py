@@ -16,6 +16,7 @@ LH_SC_EVALUATIONS, LH_SC_COEFFICIENTS = 0, 1
 LH_SC_MAX_TERMS, LH_SC_MAX_FACTORS = 48, 4
 LH_LASSO_MAX_CHUNKS, LH_LASSO_MAX_MEMORIES, LH_LASSO_MAX_TERMS = 8, 16, 16
 LH_SUBTABLE_IDENTITY, LH_SUBTABLE_AND, LH_SUBTABLE_XOR, LH_SUBTABLE_OR, LH_SUBTABLE_EQ, LH_SUBTABLE_LTU = 0, 1, 2, 3, 4, 5
+LH_SUBTABLE_CUSTOM_BASE, LH_SUBTABLE_CUSTOM_MAX, LH_SUBTABLE_CUSTOM_MAX_BITS = 0x100, 64, 20  # lh_subtable_register
 LH_LASSO_NUM_PHASES = 9
 LH_BD_COLUMN_FR, LH_BD_COLUMN_U32 = 0, 1
 
@@ -211,6 +212,9 @@ SIGNATURES = {
     "lh_ctx_set_option": (C.c_int, [_P, C.c_char_p, C.c_int64]),
     "lh_ctx_get_option": (C.c_int, [_P, C.c_char_p, C.POINTER(C.c_int64)]),
     "lh_lasso_last_route": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
+    "lh_subtable_register": (C.c_int, [C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]),
+    "lh_subtable_unregister": (C.c_int, [C.c_uint32]),
+    "lh_subtable_info": (C.c_int, [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_char_p]),
     "lh_ctx_set_comm": (C.c_int, [_P, C.POINTER(lh_comm), _SZ]),
     "lh_rccl_unique_id": (C.c_int, [C.c_char_p]),
     "lh_ctx_set_comm_rccl": (C.c_int, [_P, C.c_int, C.c_int, C.c_char_p, _SZ]),
@@ -311,6 +315,7 @@ SIGNATURES = {
     "lh_debug_msm_plan": (C.c_int, [_SZ, C.POINTER(_SZ), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_int, C.c_int,
                                     C.POINTER(C.c_uint64), C.POINTER(_SZ)]),
     "lh_debug_u32_columns": (C.c_int, [_P, C.c_int, C.POINTER(lh_debug_u32_args)]),
+    "lh_debug_lasso_subtable_read": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _SZ, _P]),
     "lh_keccak_transcript_hash_io": (C.c_int, [C.POINTER(lh_transcript), C.POINTER(lh_hash_transcript)]),
     "lh_brakedown_setup": (C.c_int, [_P, _SZ, C.c_int, C.c_char_p, C.POINTER(_P)]),
     "lh_brakedown_derive": (C.c_int, [_SZ, C.c_int, C.POINTER(_P)]),

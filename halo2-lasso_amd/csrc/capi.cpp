@@ -711,6 +711,29 @@ lh_status lh_lasso_last_route(lh_ctx* ctx, lh_lasso_route* out) {
   LH_CATCH
 }
 
+// caller-registered subtables (subtable.cpp): host only, no ctx
+lh_status lh_subtable_register(const uint32_t* values, uint32_t chunk_bits, uint32_t* out_kind) {
+  LH_TRY
+  NEED(values);
+  NEED(out_kind);
+  *out_kind = subtable_register(values, chunk_bits);
+  LH_CATCH
+}
+lh_status lh_subtable_unregister(uint32_t kind) {
+  LH_TRY
+  subtable_unregister(kind);
+  LH_CATCH
+}
+lh_status lh_subtable_info(uint32_t kind, uint32_t* chunk_bits, uint32_t* value_bits, uint8_t digest32[32]) {
+  LH_TRY
+  const std::shared_ptr<const CustomSubtable> t = subtable_find(kind);
+  LH_REQUIRE(t != nullptr, LH_ERR_ARG, "subtable: not a registered kind");
+  if (chunk_bits) *chunk_bits = t->chunk_bits;
+  if (value_bits) *value_bits = t->value_bits;
+  if (digest32) memcpy(digest32, t->digest, 32);
+  LH_CATCH
+}
+
 lh_status lh_ctx_set_comm(lh_ctx* ctx, const lh_comm* comm, size_t shard_bit) {
   LH_TRY NEED_CTX(ctx);
   ctx->c.sync();
@@ -2202,6 +2225,32 @@ lh_status lh_debug_u32_columns(lh_ctx* ctx, int op, const lh_debug_u32_args* a) 
       }
     }
   }
+  c.sync();
+  LH_CATCH
+}
+
+// (development) the witness step's subtable read for one memory: tests/test_gpu_lasso_custom.py
+lh_status lh_debug_lasso_subtable_read(lh_ctx* ctx, uint32_t kind, uint32_t chunk_bits, const uint32_t* d_dim, size_t n,
+                                       uint32_t* d_out) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(d_dim);
+  NEED(d_out);
+  Ctx& c = ctx->c;
+  LH_REQUIRE(n >= 1 && n < ((size_t)1 << 31), LH_ERR_ARG, "debug subtable read: n must be in [1, 2^31)");
+  LH_REQUIRE(chunk_bits >= 1 && chunk_bits < 31, LH_ERR_ARG, "lasso: need at least one variable");
+  if (subtable_is_custom(kind)) {
+    subtable_require(kind, chunk_bits);
+  } else {
+    LH_REQUIRE(kind < LH_SUBTABLE_KINDS, LH_ERR_ARG, "lasso: unknown subtable");
+    if (kind != LH_SUBTABLE_IDENTITY)
+      LH_REQUIRE(chunk_bits % 2 == 0, LH_ERR_ARG, "lasso: bitwise subtables need an even chunk_bits");
+  }
+  ArenaScope scope(c.arena);
+  SubtableOrders tables(c, chunk_bits);  // (its staging outlives the sync below)
+  if (kind == LH_SUBTABLE_IDENTITY)
+    LH_HIP(hipMemcpyAsync(d_out, d_dim, n * 4, hipMemcpyDeviceToDevice, c.stream));  // (the witness step shares the column)
+  else
+    k_lasso_subtable_read(c, (int)kind, chunk_bits, d_dim, n, d_out, subtable_is_custom(kind) ? tables.custom_table(kind) : nullptr);
   c.sync();
   LH_CATCH
 }

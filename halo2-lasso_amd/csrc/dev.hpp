@@ -515,7 +515,7 @@ void k_lasso_rw_leaves_up(Ctx&, const uint32_t* dim, const uint32_t* e, const ui
                           const Fr& gamma2, const Fr& tau, Fr* rs, Fr* ws, Fr* rs_up, Fr* ws_up);
 // init = m*g2 + T[m]*g - tau ; fin = init + final_cts[m]
 void k_lasso_if_leaves(Ctx&, int subtable, uint32_t chunk_bits, const uint32_t* final_cts, size_t m,
-                       const Fr& gamma, const Fr& gamma2, const Fr& tau, Fr* init, Fr* fin);
+                       const Fr& gamma, const Fr& gamma2, const Fr& tau, Fr* init, Fr* fin, const uint32_t* tab = nullptr);
 // Lasso witness: counters and subtable reads
 // keep_sorted / keep_index (optional, n entries each): the column sorted by value and the positions it came from
 // OR of all entries of every column (its bit length bounds the values); synchronises
@@ -540,7 +540,9 @@ void k_cs_rank(Ctx&, const uint32_t* const* recv, const size_t* n_recv, size_t c
                uint32_t* const* ret, uint32_t* counts);
 void k_cs_scatter(Ctx&, const uint32_t* const* back, const uint32_t* const* sidx, size_t cc, size_t n, uint32_t* const* read_ts);
 void k_cs_final(Ctx&, const uint32_t* all_counts, size_t cc, size_t m, unsigned rho, size_t m_loc, uint32_t* const* final_cts);
-void k_lasso_subtable_read(Ctx&, int subtable, uint32_t chunk_bits, const uint32_t* dim, size_t n, uint32_t* e);
+// (tab: the device entries of a registered subtable - a masked gather; null: the built-in kind's computed entry)
+void k_lasso_subtable_read(Ctx&, int subtable, uint32_t chunk_bits, const uint32_t* dim, size_t n, uint32_t* e,
+                           const uint32_t* tab = nullptr);
 // a[k] = g(E_0[k],..): small-integer evaluation into Fr
 struct LassoG {
   uint32_t num_terms;

@@ -2,8 +2,10 @@
 // (piop::sum_check, piop::gkr, pcs::multilinear::kzg) on top of the device kernels.
 #pragma once
 #include <string.h>
+#include <algorithm>
 #include <functional>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <vector>
 #include "dev.hpp"
@@ -551,8 +553,11 @@ Pcs hyrax_pcs(Ctx&, const IpaParams&, size_t poly_size, size_t batch_size);
 
 // ------------------------------------------------------------------ Lasso
 // pieces of the argument shared by the standalone prover (lasso.cpp) and HyperPlonk's Lasso lookups (hyperplonk.cpp)
+struct SubtableOrders;
 struct LassoColumns {  // small-valued witness columns as u32 (arena memory of the caller's scope)
   std::vector<uint32_t*> rts, fcs, E;
+  std::vector<const uint32_t*> T;  // per memory: the device entries of a registered subtable (null: a built-in kind)
+  std::shared_ptr<SubtableOrders> tables;  // owner of those (and of the derived commitments' orders); one upload per kind
   std::vector<uint32_t*> dim_sorted, dim_index;  // (keep_sorted) every dim column sorted by value + source positions
   uint32_t a_bits = 0;  // a 32-bit output column of a product g: every entry < 2^a_bits (0: none, or the linear g's column)
 };
@@ -564,9 +569,24 @@ struct LassoClaims {  // points and claimed evaluations that remain to be opened
   std::vector<HFr> ev_l;  // final_cts_j at r_M
 };
 constexpr uint32_t LH_SUBTABLE_KINDS = 6;  // IDENTITY .. LTU (include/lasso_hip.h)
+// Caller-registered subtables (subtable.cpp; include/lasso_hip.h lh_subtable_register): kinds from LH_SUBTABLE_CUSTOM_BASE up.
+// Immutable once registered; the shared_ptr of a lookup keeps the entries alive past an unregister on another thread.
+struct CustomSubtable {
+  uint32_t kind = 0, chunk_bits = 0, value_bits = 0;  // value_bits: bit length of the largest entry (0: all zero)
+  uint8_t digest[32] = {0};                           // Keccak-256 of the entries as little-endian words
+  std::vector<uint32_t> values;                       // 2^chunk_bits entries
+  std::vector<uint32_t> order;                        // T[0] = 0 only: the indices sorted by entry (MsmJob::d_order)
+};
+uint32_t subtable_register(const uint32_t* values, uint32_t chunk_bits);
+void subtable_unregister(uint32_t kind);
+std::shared_ptr<const CustomSubtable> subtable_find(uint32_t kind);  // null: not registered
+// the registered subtable a memory of a table of 2^l-entry chunks names: LH_ERR_ARG when there is none or its size differs
+std::shared_ptr<const CustomSubtable> subtable_require(uint32_t kind, size_t l);
+inline bool subtable_is_custom(uint32_t kind) { return kind >= LH_SUBTABLE_CUSTOM_BASE; }
 // THE width rule: every entry of a subtable of 2^l entries is below 2^lasso_subtable_bits(kind, l).  What is promised to
 // the u32 MSM and the column commits (known_bits) comes from here: a bound too small yields wrong commitments.
 inline uint32_t lasso_subtable_bits(uint32_t kind, size_t l) {
+  if (subtable_is_custom(kind)) return subtable_require(kind, l)->value_bits;  // (0: an all-zero table)
   if (kind == LH_SUBTABLE_IDENTITY) return (uint32_t)l;
   if (kind == LH_SUBTABLE_EQ || kind == LH_SUBTABLE_LTU) return 1;
   return (uint32_t)(l / 2);  // AND, XOR, OR of two (l / 2)-bit halves
@@ -585,32 +605,63 @@ inline uint32_t lasso_subtable_entry_host(uint32_t kind, uint32_t m, size_t l) {
   }
 }
 // T[d] and the d's sorted by T[d] for the non-identity subtables, on the device (arena memory of the caller's scope; the
-// host staging lives as long as this object, i.e. past the msm_batch that consumes them)
+// host staging lives as long as this object, i.e. past the msm_batch that consumes them).  A registered kind is served
+// from the registry's entries, which this object keeps alive; its device T is what the witness and leaf kernels gather from.
 struct SubtableOrders {
+  struct Entry {
+    std::vector<uint32_t> h_tab, h_ord;
+    std::shared_ptr<const CustomSubtable> custom;
+    uint32_t *d_tab = nullptr, *d_ord = nullptr;
+  };
   Ctx& c;
   size_t l;
-  std::vector<uint32_t> h_tab[LH_SUBTABLE_KINDS], h_ord[LH_SUBTABLE_KINDS];
-  uint32_t *d_tab[LH_SUBTABLE_KINDS] = {}, *d_ord[LH_SUBTABLE_KINDS] = {};
+  std::map<uint32_t, Entry> entries;  // one per distinct kind
   SubtableOrders(Ctx& c_, size_t l_) : c(c_), l(l_) {}
-  void get(int kind, const uint32_t** table, const uint32_t** order) {
-    LH_REQUIRE(kind > LH_SUBTABLE_IDENTITY && kind < (int)LH_SUBTABLE_KINDS, LH_ERR_ARG, "lasso: unknown subtable");
-    if (!d_tab[kind]) {
-      const size_t M = (size_t)1 << l, V = (size_t)1 << lasso_subtable_bits((uint32_t)kind, l);
-      std::vector<uint32_t>&tab = h_tab[kind], &ord = h_ord[kind];
+  // T of a registered kind alone (one upload per kind); its first entry: *t0
+  const uint32_t* custom_table(uint32_t kind, uint32_t* t0 = nullptr) {
+    Entry& e = entries[kind];
+    if (!e.d_tab) {
+      e.custom = subtable_require(kind, l);
+      const size_t M = (size_t)1 << l;
+      e.d_tab = c.arena.alloc_n<uint32_t>(M);
+      LH_HIP(hipMemcpyAsync(e.d_tab, e.custom->values.data(), M * 4, hipMemcpyHostToDevice, c.stream));
+    }
+    if (t0) *t0 = e.custom->values[0];
+    return e.d_tab;
+  }
+  void get(uint32_t kind, const uint32_t** table, const uint32_t** order) {
+    const size_t M = (size_t)1 << l;
+    if (subtable_is_custom(kind)) {
+      *table = custom_table(kind);
+      Entry& e = entries[kind];
+      if (!e.d_ord) {
+        // (sorted by entry once, at registration: 32-bit values rule out the counting sort below)
+        LH_REQUIRE(e.custom->order.size() == M, LH_ERR_ARG, "lasso: a derived commitment needs T[0] = 0");
+        e.d_ord = c.arena.alloc_n<uint32_t>(M);
+        LH_HIP(hipMemcpyAsync(e.d_ord, e.custom->order.data(), M * 4, hipMemcpyHostToDevice, c.stream));
+      }
+      *order = e.d_ord;
+      return;
+    }
+    LH_REQUIRE(kind > LH_SUBTABLE_IDENTITY && kind < LH_SUBTABLE_KINDS, LH_ERR_ARG, "lasso: unknown subtable");
+    Entry& e = entries[kind];
+    if (!e.d_tab) {
+      const size_t V = (size_t)1 << lasso_subtable_bits(kind, l);
+      std::vector<uint32_t>&tab = e.h_tab, &ord = e.h_ord;
       tab.resize(M), ord.resize(M);
       std::vector<uint32_t> start(V + 1, 0);
       for (size_t d = 0; d < M; d++) {
-        tab[d] = lasso_subtable_entry_host((uint32_t)kind, (uint32_t)d, l);
+        tab[d] = lasso_subtable_entry_host(kind, (uint32_t)d, l);
         start[tab[d] + 1]++;
       }
       for (size_t v = 0; v < V; v++) start[v + 1] += start[v];
       for (size_t d = 0; d < M; d++) ord[start[tab[d]]++] = (uint32_t)d;  // counting sort by T
-      d_tab[kind] = c.arena.alloc_n<uint32_t>(M);
-      d_ord[kind] = c.arena.alloc_n<uint32_t>(M);
-      LH_HIP(hipMemcpyAsync(d_tab[kind], tab.data(), M * 4, hipMemcpyHostToDevice, c.stream));
-      LH_HIP(hipMemcpyAsync(d_ord[kind], ord.data(), M * 4, hipMemcpyHostToDevice, c.stream));
+      e.d_tab = c.arena.alloc_n<uint32_t>(M);
+      e.d_ord = c.arena.alloc_n<uint32_t>(M);
+      LH_HIP(hipMemcpyAsync(e.d_tab, tab.data(), M * 4, hipMemcpyHostToDevice, c.stream));
+      LH_HIP(hipMemcpyAsync(e.d_ord, ord.data(), M * 4, hipMemcpyHostToDevice, c.stream));
     }
-    *table = d_tab[kind], *order = d_ord[kind];
+    *table = e.d_tab, *order = e.d_ord;
   }
 };
 

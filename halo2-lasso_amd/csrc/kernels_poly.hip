@@ -1533,8 +1533,45 @@ __global__ void lasso_subtable_read_kernel(int kind, uint32_t bits, const uint32
                                            uint32_t* __restrict__ e) {
   GSTRIDE(i, n) e[i] = subtable_entry(kind, dim[i], bits);
 }
-void k_lasso_subtable_read(Ctx& c, int subtable, uint32_t chunk_bits, const uint32_t* dim, size_t n, uint32_t* e) {
-  if (n) hipLaunchKernelGGL(lasso_subtable_read_kernel, grid_for(n), 256, 0, c.stream, subtable, chunk_bits, dim, n, e);
+// A registered subtable (lh_subtable_register): e[i] = T[dim[i] & mask], T the 2^bits entries on the device.  THE MASK IS
+// NOT OPTIONAL: the access counters' verdict on an index >= 2^bits is read back after this kernel has run, and where the
+// built-in kinds compute an entry from any m, an unmasked gather would read past T.  Four lookups per lane: the dims as one
+// 16-byte load, the stores as one; T through the caches (2^16 entries are 256 KiB, 2^20 are 4 MiB - an XCD's L2).
+__global__ __launch_bounds__(256) void lasso_subtable_gather_kernel(const uint32_t* __restrict__ tab, uint32_t mask,
+                                                                    const uint32_t* __restrict__ dim, size_t n,
+                                                                    uint32_t* __restrict__ e) {
+  const size_t quads = n / 4;
+  GSTRIDE(q, quads) {
+    const uint4 d = reinterpret_cast<const uint4*>(dim)[q];
+    uint4 v;
+    v.x = tab[d.x & mask], v.y = tab[d.y & mask], v.z = tab[d.z & mask], v.w = tab[d.w & mask];
+    reinterpret_cast<uint4*>(e)[q] = v;
+  }
+  // (the last n mod 4 lookups: the first lanes of the grid)
+  const size_t i = 4 * quads + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) e[i] = tab[dim[i] & mask];
+}
+// the same for columns that are not 16-byte aligned (a caller's offset pointer)
+__global__ __launch_bounds__(256) void lasso_subtable_gather1_kernel(const uint32_t* __restrict__ tab, uint32_t mask,
+                                                                     const uint32_t* __restrict__ dim, size_t n,
+                                                                     uint32_t* __restrict__ e) {
+  GSTRIDE(i, n) e[i] = tab[dim[i] & mask];
+}
+// `tab`: the device entries of a registered kind (SubtableOrders::custom_table), null for the built-in kinds
+void k_lasso_subtable_read(Ctx& c, int subtable, uint32_t chunk_bits, const uint32_t* dim, size_t n, uint32_t* e,
+                           const uint32_t* tab) {
+  if (!tab) {
+    if (n) hipLaunchKernelGGL(lasso_subtable_read_kernel, grid_for(n), 256, 0, c.stream, subtable, chunk_bits, dim, n, e);
+    return;
+  }
+  ProfScope ps(c, "lasso_subtable_gather", 12.0 * n, 0.0, (double)n);
+  LH_REQUIRE(chunk_bits >= 1 && chunk_bits <= LH_SUBTABLE_CUSTOM_MAX_BITS, LH_ERR_ARG, "lasso: bad chunk_bits of a registered subtable");
+  if (!n) return;
+  const uint32_t mask = (1u << chunk_bits) - 1u;
+  if (((uintptr_t)dim | (uintptr_t)e) % 16 == 0)
+    hipLaunchKernelGGL(lasso_subtable_gather_kernel, grid_for((n + 3) / 4), 256, 0, c.stream, tab, mask, dim, n, e);
+  else
+    hipLaunchKernelGGL(lasso_subtable_gather1_kernel, grid_for(n), 256, 0, c.stream, tab, mask, dim, n, e);
 }
 
 // HyperPlonk's Lasso lookups take their chunk columns from the circuit's (field-element) polys: canonical value of
@@ -1749,10 +1786,25 @@ __global__ void lasso_if_leaves_kernel(int kind, uint32_t bits, const uint32_t* 
     fin[i] = add(h, from_u64<FrParams>(final_cts[i]));
   }
 }
+// the same leaves over the entries of a registered subtable: v = T[i] gamma, i < m = the table's size (in range by construction)
+__global__ void lasso_if_leaves_table_kernel(const uint32_t* __restrict__ tab, const uint32_t* __restrict__ final_cts, size_t m,
+                                             Fr gamma, Fr gamma2, Fr tau, Fr* __restrict__ init, Fr* __restrict__ fin) {
+  GSTRIDE(i, m) {
+    Fr a = mul(from_u64<FrParams>(i), gamma2);
+    Fr v = mul(from_u64<FrParams>(tab[i]), gamma);
+    Fr h = sub(add(a, v), tau);
+    init[i] = h;
+    fin[i] = add(h, from_u64<FrParams>(final_cts[i]));
+  }
+}
+// `tab`: the device entries of a registered kind (m of them), null for the built-in kinds
 void k_lasso_if_leaves(Ctx& c, int subtable, uint32_t chunk_bits, const uint32_t* final_cts, size_t m,
-                       const Fr& gamma, const Fr& gamma2, const Fr& tau, Fr* init, Fr* fin) {
-  ProfScope ps(c, "lasso_if_leaves", (4.0 + 64.0) * m, 5.0 * m, (double)m);
-  if (m)
+                       const Fr& gamma, const Fr& gamma2, const Fr& tau, Fr* init, Fr* fin, const uint32_t* tab) {
+  ProfScope ps(c, "lasso_if_leaves", ((tab ? 8.0 : 4.0) + 64.0) * m, 5.0 * m, (double)m);
+  if (m && tab)
+    hipLaunchKernelGGL(lasso_if_leaves_table_kernel, grid_for(m), 256, 0, c.stream, tab, final_cts, m, gamma, gamma2, tau,
+                       init, fin);
+  else if (m)
     hipLaunchKernelGGL(lasso_if_leaves_kernel, grid_for(m), 256, 0, c.stream, subtable, chunk_bits, final_cts, m,
                        gamma, gamma2, tau, init, fin);
 }

@@ -61,6 +61,10 @@ void lasso_check_table(const lh_lasso_table& tb) {
   LH_REQUIRE(tb.num_terms >= 1 && tb.num_terms <= LH_LASSO_MAX_TERMS, LH_ERR_ARG, "lasso: bad g term count");
   for (size_t i = 0; i < alpha; i++) {
     LH_REQUIRE(tb.memory_chunk[i] < cc, LH_ERR_ARG, "lasso: memory chunk out of range");
+    if (subtable_is_custom(tb.memory_subtable[i])) {  // (registered: its own size, odd or even)
+      subtable_require(tb.memory_subtable[i], l);
+      continue;
+    }
     LH_REQUIRE(tb.memory_subtable[i] < LH_SUBTABLE_KINDS, LH_ERR_ARG, "lasso: unknown subtable");
     if (tb.memory_subtable[i] != LH_SUBTABLE_IDENTITY)
       LH_REQUIRE(l % 2 == 0, LH_ERR_ARG, "lasso: bitwise subtables need an even chunk_bits");
@@ -160,7 +164,8 @@ LassoColumns lasso_witness_columns(Ctx& c, const lh_lasso_table& tb, size_t n, c
   const Shard sh(c);
   const size_t N = (size_t)1 << (n - sh.rho), M = (size_t)1 << l;  // N: entries of this rank's columns
   LassoColumns w;
-  w.rts.resize(cc), w.fcs.resize(cc), w.E.resize(alpha);
+  w.rts.resize(cc), w.fcs.resize(cc), w.E.resize(alpha), w.T.assign(alpha, nullptr);
+  w.tables = std::make_shared<SubtableOrders>(c, l);
   for (size_t j = 0; j < cc; j++) {
     w.rts[j] = c.arena.alloc_n<uint32_t>(N);
     w.fcs[j] = c.arena.alloc_n<uint32_t>(M);
@@ -189,7 +194,9 @@ LassoColumns lasso_witness_columns(Ctx& c, const lh_lasso_table& tb, size_t n, c
       w.E[i] = const_cast<uint32_t*>(d_dims[tb.memory_chunk[i]]);
     } else {
       w.E[i] = c.arena.alloc_n<uint32_t>(N);
-      k_lasso_subtable_read(c, (int)tb.memory_subtable[i], (uint32_t)l, d_dims[tb.memory_chunk[i]], N, w.E[i]);
+      // (a registered kind: a gather from its entries, uploaded once per kind; the kernel masks the index)
+      if (subtable_is_custom(tb.memory_subtable[i])) w.T[i] = w.tables->custom_table(tb.memory_subtable[i]);
+      k_lasso_subtable_read(c, (int)tb.memory_subtable[i], (uint32_t)l, d_dims[tb.memory_chunk[i]], N, w.E[i], w.T[i]);
     }
     g.e[i] = w.E[i];
   }
@@ -422,7 +429,8 @@ LassoClaims lasso_argue(Ctx& c, const lh_lasso_table& tb, size_t n, const LassoC
       } else {
         k_lasso_rw_leaves(c, d_dims[j], w.E[i], w.rts[j], N, dev(gamma), dev(gamma2), dev(tau), rs, ws);
       }
-      k_lasso_if_leaves(c, (int)tb.memory_subtable[i], (uint32_t)l, w.fcs[j], M, dev(gamma), dev(gamma2), dev(tau), in, fi);
+      k_lasso_if_leaves(c, (int)tb.memory_subtable[i], (uint32_t)l, w.fcs[j], M, dev(gamma), dev(gamma2), dev(tau), in, fi,
+                        w.T.empty() ? nullptr : w.T[i]);
       leaves[2 * i] = rs, leaves[2 * i + 1] = ws;
       plus_one[2 * i + 1] = 1;
       leaves[2 * alpha + 2 * i] = in, leaves[2 * alpha + 2 * i + 1] = fi;
@@ -688,15 +696,22 @@ void lasso_prove(Ctx& c, const Pcs& pcs, const lh_lasso_table& tb, size_t n, con
     // E_i = T[dim_j]: commit(E_i) = sum_d T[d] * B_d over the BUCKET sums B_d of dim_j's commitment - no second pass
     // over the N points (msm.hip, MsmJob::derived_parent; falls back to an ordinary column when the window shape of
     // dim_j does not allow it)
-    SubtableOrders orders(c, l);
+    SubtableOrders& orders = *w.tables;
     for (size_t i = 0; i < alpha; i++)
       if (tb.memory_subtable[i] != LH_SUBTABLE_IDENTITY) {
         add_job(1 + 2 * cc + i, E[i], true, N);
         // (the derived route has no bucket for dim = 0 - msm.hip: T[0] must be 0 - and EQ has T[0] = 1: an ordinary column)
-        if (l <= 20 && tb.memory_subtable[i] != LH_SUBTABLE_EQ) {
+        // A registered subtable asks for the route exactly when its T[0] is 0 (its l is at most 20 by registration).
+        bool derive = l <= 20 && tb.memory_subtable[i] != LH_SUBTABLE_EQ;
+        if (subtable_is_custom(tb.memory_subtable[i])) {
+          uint32_t t0 = 0;
+          orders.custom_table(tb.memory_subtable[i], &t0);
+          derive = t0 == 0;
+        }
+        if (derive) {
           MsmJob& jb = jobs.back();
           jb.derived_parent = (int)dim_job[tb.memory_chunk[i]];
-          orders.get((int)tb.memory_subtable[i], &jb.d_table, &jb.d_order);
+          orders.get(tb.memory_subtable[i], &jb.d_table, &jb.d_order);
           jb.table_in_bits = (uint32_t)l, jb.table_out_bits = lasso_subtable_bits(tb.memory_subtable[i], l);
           c.route.v[RouteStats::DERIVED]++;
         }

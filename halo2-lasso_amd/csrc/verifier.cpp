@@ -960,6 +960,23 @@ static std::vector<HFr> verify_grand_product(const std::vector<size_t>& depth, T
 }
 
 static HFr subtable_mle_eval(uint32_t kind, const std::vector<HFr>& point) {  // lasso.py:55-72
+  if (subtable_is_custom(kind)) {
+    // a registered subtable: the dense MLE of its entries, one fold over 2^l values (variable i = index bit i); the fold of
+    // the first variable reads the 32-bit entries
+    const std::shared_ptr<const CustomSubtable> t = subtable_require(kind, point.size());
+    const std::vector<uint32_t>& T = t->values;
+    std::vector<HFr> cur(T.size() / 2);
+    for (size_t k = 0; k < cur.size(); k++) {
+      const HFr lo = HFr::from_u64(T[2 * k]), hi = HFr::from_u64(T[2 * k + 1]);
+      cur[k] = lo + point[0] * (hi - lo);
+    }
+    for (size_t i = 1; i < point.size(); i++) {
+      const size_t half = cur.size() / 2;
+      for (size_t k = 0; k < half; k++) cur[k] = cur[2 * k] + point[i] * (cur[2 * k + 1] - cur[2 * k]);
+      cur.resize(half);
+    }
+    return cur[0];
+  }
   if (kind == LH_SUBTABLE_IDENTITY) return identity_eval(point);
   const size_t h = point.size() / 2;
   if (kind == LH_SUBTABLE_EQ || kind == LH_SUBTABLE_LTU) {
@@ -990,8 +1007,13 @@ static void lasso_verify_check_table(const lh_lasso_table& tb, size_t n) {
                  tb.num_terms <= LH_LASSO_MAX_TERMS,
              LH_ERR_ARG, "lasso: bad table");
   LH_REQUIRE(n >= 1 && l >= 1 && n < 32 && l < 32, LH_ERR_ARG, "lasso: need at least one variable");
-  for (size_t i = 0; i < alpha; i++)
+  for (size_t i = 0; i < alpha; i++) {
+    if (tb.memory_chunk[i] < c && subtable_is_custom(tb.memory_subtable[i])) {  // (registered, and of this table's size)
+      subtable_require(tb.memory_subtable[i], l);
+      continue;
+    }
     LH_REQUIRE(tb.memory_chunk[i] < c && tb.memory_subtable[i] < LH_SUBTABLE_KINDS, LH_ERR_ARG, "lasso: bad memory");
+  }
   LH_REQUIRE(tb.num_terms >= 1, LH_ERR_ARG, "lasso: bad g term count");
   for (size_t m = 0; m < tb.num_terms; m++)
     LH_REQUIRE(tb.g_num_factors[m] >= 1 && tb.g_num_factors[m] <= LH_SC_MAX_FACTORS, LH_ERR_ARG, "lasso: bad g term");

@@ -230,6 +230,30 @@ lh_status lh_mkzg_batch_open(lh_ctx*, const lh_srs*, size_t num_vars,
 #define LH_SUBTABLE_OR 3
 #define LH_SUBTABLE_EQ 4
 #define LH_SUBTABLE_LTU 5
+/* Caller-registered subtables: any table of 2^chunk_bits 32-bit entries the caller can write down (a signed comparison's
+ * top chunk, a shift, an S-box, a popcount).  Lasso needs no formula for a subtable: the prover reads the entries, the
+ * verifier evaluates their multilinear extension at one point (O(2^chunk_bits) host work).  The registry is process-wide,
+ * thread-safe and needs no ctx (the verifier has none).
+ *   lh_subtable_register   copies the 2^chunk_bits host values and returns a new kind, LH_SUBTABLE_CUSTOM_BASE + the number
+ *                          of registrations made before it in this process: kinds are never reused, so a stale kind is
+ *                          refused and never silently another table.  Kinds 6 .. 0xFF stay LH_ERR_ARG.
+ *   lh_subtable_unregister forgets the kind; a prove or verify that has already looked the table up keeps its entries alive.
+ *   lh_subtable_info       chunk_bits, value_bits (the bit length of the largest entry; 0 for an all-zero table) and the
+ *                          Keccak-256 digest of the entries as little-endian 32-bit words (any of the three may be NULL).
+ *                          The digest lets a prover and a verifier on different hosts compare what they registered.  It is
+ *                          NOT absorbed into any transcript: the table is part of the statement, as the kinds are.
+ * LH_ERR_ARG: a NULL `values` / `out_kind`, chunk_bits 0 or above LH_SUBTABLE_CUSTOM_MAX_BITS, more than
+ * LH_SUBTABLE_CUSTOM_MAX live registrations, an unknown kind.
+ * A memory of an lh_lasso_table may name a registered kind: the table's chunk_bits must equal the registered one
+ * (LH_ERR_ARG otherwise; an odd chunk_bits is fine - the even rule belongs to the x || y kinds above).  Such a memory's
+ * column E = T[dim] is committed from the buckets of dim's commitment when T[0] = 0 and as an ordinary 32-bit column
+ * otherwise; every prover and every PCS that takes an lh_lasso_table takes it. */
+#define LH_SUBTABLE_CUSTOM_BASE 0x100u
+#define LH_SUBTABLE_CUSTOM_MAX 64
+#define LH_SUBTABLE_CUSTOM_MAX_BITS 20
+lh_status lh_subtable_register(const uint32_t* values /* host, 2^chunk_bits */, uint32_t chunk_bits, uint32_t* out_kind);
+lh_status lh_subtable_unregister(uint32_t kind);
+lh_status lh_subtable_info(uint32_t kind, uint32_t* chunk_bits, uint32_t* value_bits, uint8_t digest32[32]);
 #define LH_LASSO_MAX_CHUNKS 8
 #define LH_LASSO_MAX_MEMORIES 16
 #define LH_LASSO_MAX_TERMS 16
@@ -238,7 +262,7 @@ typedef struct lh_lasso_table {
   uint32_t chunk_bits;   /* l : subtable size 2^l */
   uint32_t num_memories; /* alpha */
   uint32_t memory_chunk[LH_LASSO_MAX_MEMORIES];    /* j(i) */
-  uint32_t memory_subtable[LH_LASSO_MAX_MEMORIES]; /* LH_SUBTABLE_* */
+  uint32_t memory_subtable[LH_LASSO_MAX_MEMORIES]; /* LH_SUBTABLE_*, or a kind of lh_subtable_register */
   uint32_t num_terms; /* g = sum_m coeff[m] * prod_{k < num_factors[m]} E_{factor[m][k]} */
   lh_fr g_coeff[LH_LASSO_MAX_TERMS];
   uint8_t g_num_factors[LH_LASSO_MAX_TERMS];
@@ -1005,6 +1029,13 @@ typedef struct lh_debug_u32_args {
   int* taken;                    /* LINCOMB_FOLD_SMALL */
 } lh_debug_u32_args;
 lh_status lh_debug_u32_columns(lh_ctx*, int op, const lh_debug_u32_args*);
+/* (development) the subtable-read step of the Lasso witness alone: d_out[i] = T[d_dim[i]] for a memory of `kind` over
+ * chunks of `chunk_bits` bits, by exactly what a prove runs for that memory - the computed entry of a built-in kind, the
+ * masked gather from the registered entries otherwise (an index >= 2^chunk_bits reads T[index mod 2^chunk_bits]: a prove
+ * refuses such a column by its access counters).  IDENTITY copies.  Returns after the stream has drained.
+ * tests/test_gpu_lasso_custom.py. */
+lh_status lh_debug_lasso_subtable_read(lh_ctx*, uint32_t kind, uint32_t chunk_bits, const uint32_t* d_dim, size_t n,
+                                       uint32_t* d_out);
 
 /* ---------------------------------------------------------------- measurement (bench.py)
  * Per-kernel HIP-event timing on the ctx stream.  While enabled every instrumented launch is
