@@ -281,6 +281,11 @@ extern "C" {
                           d_dims: *const *const u32, t: *mut lh_transcript) -> lh_status;
     pub fn lh_lasso_verify(vp: *const lh_mkzg_vp, table: *const lh_lasso_table, num_vars: usize,
                            t: *mut lh_transcript) -> lh_status;
+    // lookups into several tables in one proof (at most LH_LASSO_BATCH_MAX_TABLES = 8): d_dims[t][j] is chunk column j of table t
+    pub fn lh_lasso_prove_batch(ctx: *mut lh_ctx, srs: *const lh_srs, tables: *const *const lh_lasso_table, num_tables: usize,
+                                num_vars: usize, d_dims: *const *const *const u32, t: *mut lh_transcript) -> lh_status;
+    pub fn lh_lasso_verify_batch(vp: *const lh_mkzg_vp, tables: *const *const lh_lasso_table, num_tables: usize,
+                                 num_vars: usize, t: *mut lh_transcript) -> lh_status;
     // one proof over several GPUs
     pub fn lh_ctx_set_comm(ctx: *mut lh_ctx, comm: *const lh_comm, shard_bit: usize) -> lh_status;
     pub fn lh_rccl_unique_id(out: *mut u8) -> lh_status;

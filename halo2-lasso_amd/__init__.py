@@ -787,6 +787,15 @@ def lasso_verify(vp, table, num_vars, transcript):
         raise InvalidSnark("trailing bytes in proof")
 
 
+def lasso_verify_batch(vp, tables, num_vars, transcript):
+    """Verifier of lasso_prove_batch (tests/lasso_batch_ref.py verify).  A Keccak256Transcript must be fully consumed."""
+    arr, keep = _table_list(tables)
+    _check(vp.lib.lh_lasso_verify_batch(vp.h, arr, len(tables), num_vars, transcript.p))
+    del keep
+    if isinstance(transcript, Keccak256Transcript) and transcript.remaining():
+        raise InvalidSnark("trailing bytes in proof")
+
+
 # ------------------------------------------------------------------ pcs::multilinear::zeromorph over pcs::univariate::kzg
 class UnivariateKzgParams:
     """UnivariateKzgParam (pcs/univariate/kzg.rs:38-66): powers_of_s_g1 resident on the device"""
@@ -1548,6 +1557,31 @@ def lasso_prove(pp, table, num_vars, dims, transcript):
     t = table.to_c()
     _check(getattr(pp.ctx.lib, "lh_lasso_prove" + pp.suffix)(pp.ctx.h, *pp.head(), C.byref(t), num_vars, _ptr_array(dims),
                                                              transcript.p, *_tail(pp, transcript)))
+
+
+def _table_list(tables):
+    """K tables as the `const lh_lasso_table* const*` of the batch entries -> (pointer array, keepalive)"""
+    if not 1 <= len(tables) <= _ffi.LH_LASSO_BATCH_MAX_TABLES:
+        raise ArgumentError("lasso batch: 1 to %d tables" % _ffi.LH_LASSO_BATCH_MAX_TABLES)
+    cs = [t.to_c() for t in tables]
+    arr = (C.POINTER(lh_lasso_table) * len(cs))(*[C.pointer(c) for c in cs])
+    return arr, cs
+
+
+def lasso_prove_batch(pp, tables, num_vars, dims, transcript):
+    """Lookups into several tables in ONE proof over multilinear KZG (include/lasso_hip.h lh_lasso_prove_batch):
+    tables: K LassoTable; dims[t]: the c_t device buffers of u32[2^num_vars] chunk indices of table t.  Two tables of equal
+    chunk_bits handed the same buffer for a chunk column share that column's counters and commitments."""
+    if len(dims) != len(tables):
+        raise ArgumentError("expected one list of dim columns per table")
+    for t, (table, cols) in enumerate(zip(tables, dims)):
+        if len(cols) != table.c:
+            raise ArgumentError("table %d: expected %d dim columns" % (t, table.c))
+    arr, keep = _table_list(tables)
+    cols = [_ptr_array(d) for d in dims]
+    col_arr = (C.POINTER(C.c_void_p) * len(cols))(*[C.cast(c, C.POINTER(C.c_void_p)) for c in cols])
+    _check(pp.ctx.lib.lh_lasso_prove_batch(pp.ctx.h, pp.h, arr, len(tables), num_vars, col_arr, transcript.p))
+    del keep
 
 
 def attach_comm(ctx, rank, size, all_gather, shard_bit):

@@ -390,6 +390,12 @@ for _suffix, (_prover, _verifier) in _PCS_HEADS.items():
 SIGNATURES["lh_lasso_prove_brakedown"] = (C.c_int, [_P, _P] + _PROVE_TAILS["lh_lasso_prove"] + [_HT])
 SIGNATURES["lh_lasso_verify_brakedown"] = (C.c_int, [_P] + _VERIFY_TAILS["lh_lasso_verify"] + [_HT])
 
+# several tables in one proof (multilinear KZG): lists of table pointers, and per table a list of chunk column pointers
+LH_LASSO_BATCH_MAX_TABLES = 8
+SIGNATURES["lh_lasso_prove_batch"] = (C.c_int, [_P, _P, C.POINTER(C.POINTER(lh_lasso_table)), _SZ, _SZ,
+                                                C.POINTER(C.POINTER(_P)), _T])
+SIGNATURES["lh_lasso_verify_batch"] = (C.c_int, [_P, C.POINTER(C.POINTER(lh_lasso_table)), _SZ, _SZ, _T])
+
 _lib = None
 
 

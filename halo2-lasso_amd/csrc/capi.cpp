@@ -677,6 +677,16 @@ lh_status lh_lasso_prove(lh_ctx* ctx, const lh_srs* srs, const lh_lasso_table* t
   lasso_prove_entry(ctx->c, table, num_vars, d_dims, t, [&] { return mkzg_pcs(ctx->c, srs->s); });
   LH_CATCH
 }
+lh_status lh_lasso_prove_batch(lh_ctx* ctx, const lh_srs* srs, const lh_lasso_table* const* tables, size_t num_tables,
+                               size_t num_vars, const uint32_t* const* const* d_dims, lh_transcript* t) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(srs);
+  NEED(tables);
+  NEED(d_dims);
+  Transcript tr(t);
+  lasso_prove_batch(ctx->c, mkzg_pcs(ctx->c, srs->s), tables, num_tables, num_vars, d_dims, tr);
+  LH_CATCH
+}
 lh_status lh_lasso_last_timing(lh_ctx* ctx, double* out_ms) {
   LH_TRY NEED_CTX(ctx);
   NEED(out_ms);
@@ -966,6 +976,17 @@ lh_status lh_lasso_verify(const lh_mkzg_vp* vp, const lh_lasso_table* table, siz
   LH_TRY
   NEED(vp);
   lasso_verify_entry(table, num_vars, t, [&] { return mkzg_verifier(*vp->p); });
+  LH_CATCH
+}
+lh_status lh_lasso_verify_batch(const lh_mkzg_vp* vp, const lh_lasso_table* const* tables, size_t num_tables, size_t num_vars,
+                                lh_transcript* t) {
+  LH_TRY
+  NEED(vp);
+  NEED(tables);
+  Transcript tr(t);
+  if (lasso_batch_check(tables, num_tables, num_vars) > mkzg_vp_num_vars(*vp->p))
+    throw lh::Error(LH_ERR_INVALID_PCS_PARAM, "Too many variates of poly to verify");
+  lasso_verify_batch(mkzg_verifier(*vp->p), tables, num_tables, num_vars, tr);
   LH_CATCH
 }
 lh_status lh_hyperplonk_verify(const lh_mkzg_vp* vp, const lh_hp_vparam* hvp, const lh_fr* const* instances,

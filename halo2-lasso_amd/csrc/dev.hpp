@@ -513,6 +513,17 @@ void k_lasso_rw_leaves(Ctx&, const uint32_t* dim, const uint32_t* e, const uint3
 // the same plus the level above the leaves of both trees (rs_up[i] = rs[i] * rs[i + n/2], n/2 entries each)
 void k_lasso_rw_leaves_up(Ctx&, const uint32_t* dim, const uint32_t* e, const uint32_t* ts, size_t n, const Fr& gamma,
                           const Fr& gamma2, const Fr& tau, Fr* rs, Fr* ws, Fr* rs_up, Fr* ws_up);
+// the read / write leaves of ALL memories of a batch proof (lasso.cpp lasso_prove_batch) in one launch, the memory index in
+// blockIdx.y: per memory the three u32 columns and where its leaves go.  `up`: the level above the leaves comes with them
+// as in k_lasso_rw_leaves_up (rs_up / ws_up: n / 2 nodes each; ws[m] may then be null: the write leaves are not stored);
+// otherwise rs_up / ws_up are not read.  All memories have n entries.
+constexpr int LASSO_RW_BATCH_MAX = 8;
+struct LassoRwBatch {
+  const uint32_t *dim[LASSO_RW_BATCH_MAX], *e[LASSO_RW_BATCH_MAX], *ts[LASSO_RW_BATCH_MAX];
+  Fr *rs[LASSO_RW_BATCH_MAX], *ws[LASSO_RW_BATCH_MAX], *rs_up[LASSO_RW_BATCH_MAX], *ws_up[LASSO_RW_BATCH_MAX];
+};
+void k_lasso_rw_leaves_batch(Ctx&, const LassoRwBatch& p, size_t num_memories, size_t n, bool up, const Fr& gamma,
+                             const Fr& gamma2, const Fr& tau);
 // init = m*g2 + T[m]*g - tau ; fin = init + final_cts[m]
 void k_lasso_if_leaves(Ctx&, int subtable, uint32_t chunk_bits, const uint32_t* final_cts, size_t m,
                        const Fr& gamma, const Fr& gamma2, const Fr& tau, Fr* init, Fr* fin, const uint32_t* tab = nullptr);

@@ -668,9 +668,11 @@ struct SubtableOrders {
 void lasso_check_table(const lh_lasso_table& tb);
 // a_out (optional): the output column a = g(E) as field elements; a_small_out (optional): the same as a 32-bit column
 // when g is linear with small coefficients and the value fits, or has product terms whose bound fits (LassoColumns::a_bits;
-// then *a_out stays null)
+// then *a_out stays null); reuse (optional; rts / fcs sized num_chunks): a non-null rts[j] / fcs[j] pair is taken for chunk j
+// instead of counting the column again (a batch whose tables share chunk columns)
 LassoColumns lasso_witness_columns(Ctx&, const lh_lasso_table&, size_t n, const uint32_t* const* d_dims, Fr** a_out,
-                                   uint32_t** a_small_out = nullptr, bool keep_sorted = false);
+                                   uint32_t** a_small_out = nullptr, bool keep_sorted = false,
+                                   const LassoColumns* reuse = nullptr);
 // `a`: the output column as field elements, or null with `a_small` given
 LassoClaims lasso_argue(Ctx&, const lh_lasso_table&, size_t n, const LassoColumns& w, const uint32_t* const* d_dims,
                         const Fr* a, const Fr* const* E_fr, Transcript& tr,
@@ -682,6 +684,12 @@ void lasso_write_commitments(Transcript& tr, const std::vector<HG1>& comms, size
 std::vector<HG1> lasso_read_commitments(Transcript& tr, size_t count, size_t chunks = 1);
 void lasso_prove(Ctx&, const Pcs&, const lh_lasso_table& table, size_t num_vars, const uint32_t* const* d_dims,
                  Transcript& tr);
+// Lookups into several tables (the same number of lookups each) in ONE proof: one commit batch, one Surge sum-check, one
+// grand-product GKR, one batch opening (tests/lasso_batch_ref.py).  d_dims[t][j]: chunk column j of table t.
+// lasso_batch_check: the limits of a batch that need no device (shared with the verifier); returns nv = max(n, max l_t)
+size_t lasso_batch_check(const lh_lasso_table* const* tables, size_t num_tables, size_t num_vars);
+void lasso_prove_batch(Ctx&, const Pcs&, const lh_lasso_table* const* tables, size_t num_tables, size_t num_vars,
+                       const uint32_t* const* const* d_dims, Transcript& tr);
 
 // ------------------------------------------------------------------ verifiers (verifier.cpp; host only)
 HFr interpolate_evals(const std::vector<HFr>& evals, const HFr& x);  // barycentric over 0..d (arithmetic.rs:108-136)
@@ -702,6 +710,8 @@ PcsVerifier mkzg_verifier(const VerifierParams&);
 std::pair<HFr, std::vector<HFr>> sum_check_verify(int prover_kind, size_t num_vars, size_t degree, const HFr& sum,
                                                   Transcript& tr);
 void lasso_verify(const PcsVerifier& pcs, const lh_lasso_table& table, size_t num_vars, Transcript& tr);
+void lasso_verify_batch(const PcsVerifier& pcs, const lh_lasso_table* const* tables, size_t num_tables, size_t num_vars,
+                        Transcript& tr);
 // the verifier's side of lasso_argue: Surge and memory-checking identities; claims left to check against commitments
 LassoClaims lasso_check(const lh_lasso_table& table, size_t num_vars, Transcript& tr);
 void hyperplonk_verify(const PcsVerifier& pcs, const lh_hp_vparam& vp, const HFr* const* instances, Transcript& tr);

@@ -1776,6 +1776,89 @@ void k_lasso_rw_leaves(Ctx& c, const uint32_t* dim, const uint32_t* e, const uin
     hipLaunchKernelGGL(lasso_rw_leaves_kernel, grid_for(n), 256, 0, c.stream, dim, e, ts, n, prescale_r(gamma),
                        prescale_r(gamma2), prescale_r(Fr::one()), tau, rs, ws);
 }
+// The read / write leaves of every memory of a batch proof in ONE launch (blockIdx.y = the memory; the column pointers
+// travel as a table in the kernel arguments, as tree_up_multi_kernel's do): per-memory launches are the fixed cost a
+// batch exists to amortise.  A workgroup takes tiles of 1024 leaves: VEC reads the three u32 columns 16 bytes per lane into
+// LDS (a tile is 4 KB per column) and every lane then takes the leaves tile + 256 k + lane, k < 4, so that the 32-byte
+// leaves of a wave leave as whole lines; !VEC (fewer than 4 leaves, or a column that is not 16-byte aligned) reads the
+// columns 4 bytes per lane.  UP: `count` = n / 2 and the lane that makes leaves i and i + count makes their products too.
+template <bool UP, bool VEC>
+__global__ __launch_bounds__(256) void lasso_rw_leaves_batch_kernel(LassoRwBatch p, size_t count, Fr gamma_r, Fr gamma2_r,
+                                                                    Fr one_r, Fr tau) {
+  constexpr int SEG = UP ? 2 : 1;
+  __shared__ __align__(16) uint32_t tile[SEG][3][1024];
+  const unsigned m = blockIdx.y;
+  const uint32_t* const cols[3] = {p.dim[m], p.e[m], p.ts[m]};
+  Fr* const rs = p.rs[m];
+  Fr* const ws = p.ws[m];
+  const Fr one = Fr::one();
+  const size_t tiles = (count + 1023) / 1024;
+  for (size_t t = blockIdx.x; t < tiles; t += gridDim.x) {  // (uniform per workgroup: the barriers below are reached by all)
+    const size_t base = t * 1024;
+    if (VEC) {
+      const size_t q = base + 4 * (size_t)threadIdx.x;  // (count is a multiple of 4: q + 3 < count)
+      if (q < count) {
+#pragma unroll
+        for (int s = 0; s < SEG; s++)
+#pragma unroll
+          for (int c = 0; c < 3; c++)
+            *reinterpret_cast<uint4*>(&tile[s][c][4 * threadIdx.x]) = *reinterpret_cast<const uint4*>(cols[c] + s * count + q);
+      }
+      __syncthreads();
+    }
+#pragma unroll 1
+    for (int k = 0; k < 4; k++) {
+      const size_t i = base + 256 * (size_t)k + threadIdx.x;
+      if (i >= count) break;
+      Fr h[SEG];
+#pragma unroll
+      for (int s = 0; s < SEG; s++) {
+        const size_t j = i + s * count;
+        const uint32_t lane = 256 * k + threadIdx.x;
+        const uint32_t d = VEC ? tile[s][0][lane] : cols[0][j];
+        const uint32_t e = VEC ? tile[s][1][lane] : cols[1][j];
+        const uint32_t ts = VEC ? tile[s][2][lane] : cols[2][j];
+        Wide w = Wide::zero();
+        wide_mac(w, gamma2_r, d);
+        wide_mac(w, gamma_r, e);
+        wide_mac(w, one_r, ts);
+        h[s] = sub(wide_redc(w), tau);
+        rs[j] = h[s];
+      }
+      if (UP) {
+        const Fr w0 = add(h[0], one), w1 = add(h[SEG - 1], one);
+        if (ws) {
+          ws[i] = w0;
+          ws[i + count] = w1;
+        }
+        p.rs_up[m][i] = mul(h[0], h[SEG - 1]);
+        p.ws_up[m][i] = mul(w0, w1);
+      } else {
+        ws[i] = add(h[0], one);
+      }
+    }
+    if (VEC) __syncthreads();  // (the tile is overwritten by the next turn)
+  }
+}
+void k_lasso_rw_leaves_batch(Ctx& c, const LassoRwBatch& p, size_t num_memories, size_t n, bool up, const Fr& gamma,
+                             const Fr& gamma2, const Fr& tau) {
+  LH_REQUIRE(num_memories >= 1 && num_memories <= (size_t)LASSO_RW_BATCH_MAX && n >= 2, LH_ERR_ARG, "lasso_rw_leaves_batch: bad shape");
+  const size_t count = up ? n / 2 : n;
+  bool vec = count % 4 == 0;
+  for (size_t m = 0; m < num_memories; m++) {
+    LH_REQUIRE(p.dim[m] && p.e[m] && p.ts[m] && p.rs[m] && (up ? p.rs_up[m] && p.ws_up[m] : p.ws[m] != nullptr), LH_ERR_ARG,
+               "lasso_rw_leaves_batch: null column");
+    vec = vec && ((uintptr_t)p.dim[m] | (uintptr_t)p.e[m] | (uintptr_t)p.ts[m]) % 16 == 0;
+  }
+  ProfScope ps(c, "lasso_rw_leaves_batch", (12.0 + 64.0 + (up ? 32.0 : 0.0)) * n * num_memories, (up ? 6.0 : 5.0) * n * num_memories,
+               (double)n * num_memories);
+  const dim3 grid((unsigned)std::min<size_t>((count + 1023) / 1024, (size_t)c.num_cus * 8), (unsigned)num_memories);
+  const Fr g1 = prescale_r(gamma), g2 = prescale_r(gamma2), o1 = prescale_r(Fr::one());
+  if (up && vec) hipLaunchKernelGGL((lasso_rw_leaves_batch_kernel<true, true>), grid, dim3(256), 0, c.stream, p, count, g1, g2, o1, tau);
+  else if (up) hipLaunchKernelGGL((lasso_rw_leaves_batch_kernel<true, false>), grid, dim3(256), 0, c.stream, p, count, g1, g2, o1, tau);
+  else if (vec) hipLaunchKernelGGL((lasso_rw_leaves_batch_kernel<false, true>), grid, dim3(256), 0, c.stream, p, count, g1, g2, o1, tau);
+  else hipLaunchKernelGGL((lasso_rw_leaves_batch_kernel<false, false>), grid, dim3(256), 0, c.stream, p, count, g1, g2, o1, tau);
+}
 __global__ void lasso_if_leaves_kernel(int kind, uint32_t bits, const uint32_t* __restrict__ final_cts, size_t m,
                                        Fr gamma, Fr gamma2, Fr tau, Fr* __restrict__ init, Fr* __restrict__ fin) {
   GSTRIDE(i, m) {

@@ -159,32 +159,41 @@ static void lasso_counters_sharded(Ctx& c, const Shard& sh, const uint32_t* cons
 // Inside a sharded proof d_dims are this rank's shards of the lookup columns and so are read_ts / E / a; final_cts (2^l
 // entries, l <= shard_bit + rho) is replicated.
 LassoColumns lasso_witness_columns(Ctx& c, const lh_lasso_table& tb, size_t n, const uint32_t* const* d_dims, Fr** a_out,
-                                   uint32_t** a_small_out, bool keep_sorted) {
+                                   uint32_t** a_small_out, bool keep_sorted, const LassoColumns* reuse) {
   const size_t cc = tb.num_chunks, l = tb.chunk_bits, alpha = tb.num_memories;
   const Shard sh(c);
   const size_t N = (size_t)1 << (n - sh.rho), M = (size_t)1 << l;  // N: entries of this rank's columns
   LassoColumns w;
   w.rts.resize(cc), w.fcs.resize(cc), w.E.resize(alpha), w.T.assign(alpha, nullptr);
   w.tables = std::make_shared<SubtableOrders>(c, l);
+  // reuse (a batch proof, not sharded): rts[j] / fcs[j] given say that chunk column j was counted for an earlier table
+  std::vector<const uint32_t*> own_dims;
+  std::vector<uint32_t*> own_rts, own_fcs;
   for (size_t j = 0; j < cc; j++) {
+    if (reuse && reuse->rts[j]) {
+      w.rts[j] = reuse->rts[j], w.fcs[j] = reuse->fcs[j];
+      continue;
+    }
     w.rts[j] = c.arena.alloc_n<uint32_t>(N);
     w.fcs[j] = c.arena.alloc_n<uint32_t>(M);
+    own_dims.push_back(d_dims[j]), own_rts.push_back(w.rts[j]), own_fcs.push_back(w.fcs[j]);
   }
   // LH_SHARDED_COUNTERS_MIN_R=1 (tests): a world of one takes the repartitioned counters too (the personalised exchange
   // then has one peer, itself: the transport's point-to-point path on a one-GPU box)
   const size_t counters_min_r = (size_t)knob(Knob::SHARDED_COUNTERS_MIN_R);
   keep_sorted = keep_sorted && !(sh.on && sh.R >= counters_min_r);
   if (sh.on && sh.R >= counters_min_r) {
+    LH_REQUIRE(own_dims.size() == cc, LH_ERR_ARG, "lasso: shared chunk columns inside a sharded prove");
     lasso_counters_sharded(c, sh, d_dims, cc, n, l, w.rts.data(), w.fcs.data());
-  } else {
+  } else if (!own_dims.empty()) {
     if (keep_sorted)
-      for (size_t j = 0; j < cc; j++) {
+      for (size_t j = 0; j < own_dims.size(); j++) {  // (one pair per column counted here, in their order)
         w.dim_sorted.push_back(c.arena.alloc_n<uint32_t>(N));
         w.dim_index.push_back(c.arena.alloc_n<uint32_t>(N));
       }
     // all chunk columns in one launch set, one bad-index readback (kernels_poly.hip)
-    k_lasso_counters(c, d_dims, cc, N, M, w.rts.data(), w.fcs.data(), keep_sorted ? w.dim_sorted.data() : nullptr,
-                     keep_sorted ? w.dim_index.data() : nullptr);
+    k_lasso_counters(c, own_dims.data(), own_dims.size(), N, M, own_rts.data(), own_fcs.data(),
+                     keep_sorted ? w.dim_sorted.data() : nullptr, keep_sorted ? w.dim_index.data() : nullptr);
   }
   LassoG g;
   memset(&g, 0, sizeof(g));
@@ -476,6 +485,187 @@ LassoClaims lasso_argue(Ctx& c, const lh_lasso_table& tb, size_t n, const LassoC
   return cl;
 }
 
+// the phase boundaries of a prove (lasso_prove, lasso_prove_batch): events on the prover's stream, lh_lasso_last_timing
+struct LassoPhases {
+  Ctx& c;
+  explicit LassoPhases(Ctx& c_) : c(c_) {
+    for (int k = 0; k < 8; k++)
+      if (!c.phase_ev[k]) LH_HIP(hipEventCreate(&c.phase_ev[k]));
+    c.phase_ev_pending = false;
+    LH_HIP(hipEventRecord(c.phase_ev[0], c.stream));
+    c.comm_phase = 0;
+  }
+  ~LassoPhases() { c.comm_phase = 7; }  // (collectives issued after the prove - or after it failed - count as outside)
+  void lap(int idx) {
+    LH_HIP(hipEventRecord(c.phase_ev[idx + 1], c.stream));
+    c.comm_phase = idx + 1;
+  }
+};
+
+// One table's share of a commit batch (msm_batch): which jobs of the batch are its own and where their results go in its
+// commitment list a | dim | read_ts | E | final_cts.  lasso_prove runs one table's jobs, lasso_prove_batch every table's in
+// one batch; both build them here.
+struct LassoCommitPlan {
+  std::vector<size_t> job, slot;  // job[k]: index in the batch; slot[k]: position of its result in the table's commitments
+  std::vector<HG1> second;        // per chunk: the second output of a packed read_ts pair (MsmJob::out_second points here)
+  std::vector<size_t> second_of;  // chunks whose read_ts commitment comes back through `second`
+  std::vector<size_t> dim_job;    // per chunk: the job of the batch that commits dim_j (this table's, or the one it shares)
+};
+// Appends the table's jobs to `jobs`: the output column only when g is not linear (a linear g's follows from the E
+// commitments), dim (with the sorted columns of the access counters where kept), read_ts (two columns packed into one pass
+// where their widths allow), E of the non-identity subtables (derived from dim's buckets where the route applies) and
+// final_cts.  count_ors: OR of every final_cts column; computed here when the packing looks at it unless `ors_known`.
+// shared_dim_job (optional, per chunk): >= 0 says that this chunk column, its counters and their commitments belong to an
+// earlier table of the batch whose dim job that is - no dim / read_ts / final_cts job is made for it (the caller copies
+// those three commitments), and a derived E names that job as its parent.
+static void lasso_commit_jobs(Ctx& c, const Pcs& pcs, const lh_lasso_table& tb, size_t n, size_t nv, const uint32_t* const* d_dims,
+                              const LassoColumns& w, const Fr* a, const uint32_t* a_small, std::vector<uint32_t>& count_ors,
+                              bool ors_known, const int* shared_dim_job, std::vector<MsmJob>& jobs, LassoCommitPlan& plan) {
+  const size_t cc = tb.num_chunks, l = tb.chunk_bits, alpha = tb.num_memories;
+  const Shard sh(c);
+  const bool shn = sh.on;
+  const size_t N = (size_t)1 << (n - sh.rho), M = (size_t)1 << l;
+  const std::vector<uint32_t*>&rts = w.rts, &fcs = w.fcs, &E = w.E;
+  auto shared = [&](size_t j) { return shared_dim_job != nullptr && shared_dim_job[j] >= 0; };
+  const G1Affine* bases = shn ? pcs.shard_bases(nv) : pcs.commit_bases(nv);
+  bool linear_g = true;
+  for (uint32_t m = 0; m < tb.num_terms; m++) linear_g = linear_g && tb.g_num_factors[m] == 1;
+  auto add_job = [&](size_t pos, const void* col, bool u32, size_t len) {
+    plan.job.push_back(jobs.size());
+    jobs.push_back(MsmJob{col, u32, bases, len});
+    plan.slot.push_back(pos);
+  };
+  if (!linear_g && a_small) {  // (product g with a 32-bit output column: a u32 job, every entry below 2^a_bits)
+    add_job(0, a_small, true, N);
+    jobs.back().known_bits = w.a_bits;
+  } else if (!linear_g) {
+    add_job(0, a, false, N);
+  }
+  std::vector<size_t>& dim_job = plan.dim_job;
+  dim_job.assign(cc, 0);
+  size_t own = 0;  // (the sorted columns are kept for the chunks this table counted itself, in their order)
+  for (size_t j = 0; j < cc; j++) {
+    if (shared(j)) {
+      dim_job[j] = (size_t)shared_dim_job[j];
+      continue;
+    }
+    dim_job[j] = jobs.size(), add_job(1 + j, d_dims[j], true, N);
+    jobs.back().known_bits = (uint32_t)l;  // (the access counters rejected any index >= 2^l)
+    if (!w.dim_sorted.empty()) {
+      jobs.back().sorted_scalars = w.dim_sorted[own], jobs.back().sorted_index = w.dim_index[own];
+      c.route.v[RouteStats::SORTED_REUSE]++;
+    }
+    own++;
+  }
+  // read_ts columns are small (a cell's access count): two of them share one pass over the points when their bit
+  // lengths allow (MsmJob::pack_shift; the access counts bound the timestamps)
+  plan.second.assign(cc, HG1());
+  std::vector<HG1>& second = plan.second;
+  {
+    std::vector<uint32_t>& ors = count_ors;
+    std::vector<const uint32_t*> cols(fcs.begin(), fcs.end());
+    const bool pack_on = c.opt.lasso_pack_ts != 0;  // 0: one MSM pass per read_ts column (A/B measurements)
+    if (!ors_known && pack_on && cc >= 2 && N >= ((size_t)1 << 12)) k_or_u32(c, cols.data(), cc, M, ors.data());
+    auto bits_of = [](uint32_t v) { return v ? 32u - (uint32_t)__builtin_clz(v) : 0u; };
+    for (size_t j = 0; j < cc; j++) {
+      if (shared(j)) continue;
+      const bool next = j + 1 < cc && !shared(j + 1);
+      const uint32_t b0 = std::max(bits_of(ors[j]), 4u), b1 = next ? bits_of(ors[j + 1]) : 0;
+      if (ors[j] && next && ors[j + 1] && b0 + b1 <= MSM_PACK_MAX_BITS &&
+          N >= ((size_t)MSM_PACK_MIN_POINTS_PER_BUCKET << (b0 + b1))) {  // (worth it while the points outnumber the buckets)
+        uint32_t* packed = c.arena.alloc_n<uint32_t>(N);
+        k_pack_u32(c, rts[j], rts[j + 1], b0, N, packed);
+        add_job(1 + cc + j, packed, true, N);
+        jobs.back().known_bits = b0 + b1;
+        jobs.back().pack_shift = b0;
+        jobs.back().out_second = (G1Affine*)&second[j + 1];
+        plan.second_of.push_back(j + 1);
+        c.route.v[RouteStats::PACKED_TS]++;
+        j++;
+      } else {
+        add_job(1 + cc + j, rts[j], true, N);
+        jobs.back().known_bits = bits_of(ors[j]);  // (0 when the counts were not looked at: measured then)
+      }
+    }
+  }
+  // E_i = T[dim_j]: commit(E_i) = sum_d T[d] * B_d over the BUCKET sums B_d of dim_j's commitment - no second pass
+  // over the N points (msm.hip, MsmJob::derived_parent; falls back to an ordinary column when the window shape of
+  // dim_j does not allow it)
+  SubtableOrders& orders = *w.tables;
+  for (size_t i = 0; i < alpha; i++)
+    if (tb.memory_subtable[i] != LH_SUBTABLE_IDENTITY) {
+      add_job(1 + 2 * cc + i, E[i], true, N);
+      // (the derived route has no bucket for dim = 0 - msm.hip: T[0] must be 0 - and EQ has T[0] = 1: an ordinary column)
+      // A registered subtable asks for the route exactly when its T[0] is 0 (its l is at most 20 by registration).
+      bool derive = l <= 20 && tb.memory_subtable[i] != LH_SUBTABLE_EQ;
+      if (subtable_is_custom(tb.memory_subtable[i])) {
+        uint32_t t0 = 0;
+        orders.custom_table(tb.memory_subtable[i], &t0);
+        derive = t0 == 0;
+      }
+      if (derive) {
+        MsmJob& jb = jobs.back();
+        jb.derived_parent = (int)dim_job[tb.memory_chunk[i]];
+        orders.get(tb.memory_subtable[i], &jb.d_table, &jb.d_order);
+        jb.table_in_bits = (uint32_t)l, jb.table_out_bits = lasso_subtable_bits(tb.memory_subtable[i], l);
+        c.route.v[RouteStats::DERIVED]++;
+      }
+      jobs.back().known_bits = lasso_subtable_bits(tb.memory_subtable[i], l);  // (l/2)-bit halves combined, or one bit
+    }
+  // final_cts (2^l entries) is replicated - but an MSM is additive over point ranges (the chunk-then-sum of
+  // util/arithmetic/msm.rs:101-114): rank s commits the counts [s 2^l / R, (s + 1) 2^l / R) against the same range of
+  // the level's first bases, and the partial commitments join the exchange below - no rank repeats another's additions
+  const ReplicatedRange fc_range(sh, M);
+  for (size_t j = 0; j < cc; j++) {
+    if (shared(j)) continue;
+    add_job(1 + 2 * cc + alpha + j, fcs[j] + fc_range.first, true, fc_range.count);
+    jobs.back().bases = pcs.commit_bases(nv) + fc_range.first;
+    jobs.back().known_bits = count_ors[j] ? 32u - (uint32_t)__builtin_clz(count_ors[j]) : 0u;
+  }
+}
+// the batch's results -> the table's commitments, as far as its own jobs made them (what lasso_commit_derive adds, and
+// what a table of a batch shares with an earlier one, is still missing)
+static std::vector<HG1> lasso_commit_collect(const lh_lasso_table& tb, const LassoCommitPlan& plan, const std::vector<HG1>& part) {
+  const size_t cc = tb.num_chunks, alpha = tb.num_memories;
+  std::vector<HG1> comms(1 + 3 * cc + alpha);
+  for (size_t k = 0; k < plan.job.size(); k++) comms[plan.slot[k]] = part[plan.job[k]];
+  for (size_t j : plan.second_of) comms[1 + cc + j] = plan.second[j];
+  return comms;
+}
+// the commitments that follow from others by linearity: E_i = dim_j of an identity subtable, a = sum_m coeff_m E_{f(m)}
+// under a linear g
+static void lasso_commit_derive(const lh_lasso_table& tb, std::vector<HG1>& comms) {
+  const size_t cc = tb.num_chunks, alpha = tb.num_memories;
+  bool linear_g = true;
+  for (uint32_t m = 0; m < tb.num_terms; m++) linear_g = linear_g && tb.g_num_factors[m] == 1;
+  for (size_t i = 0; i < alpha; i++)
+    if (tb.memory_subtable[i] == LH_SUBTABLE_IDENTITY) comms[1 + 2 * cc + i] = comms[1 + tb.memory_chunk[i]];
+  if (!linear_g) return;
+  std::vector<host::G1Xyzz> terms(tb.num_terms);
+  // (the coefficients of the range / AND / XOR tables are powers of two below 2^64: a few dozen doublings each, done
+  // here - waking the host pool for them cost more than they do; wide coefficients go to the pool)
+  bool small_coeffs = true;
+  for (uint32_t m = 0; m < tb.num_terms && small_coeffs; m++) {
+    HFr co;
+    memcpy(&co, &tb.g_coeff[m], 32);
+    uint64_t canon[4];
+    co.to_canonical(canon);
+    small_coeffs = !canon[1] && !canon[2] && !canon[3];
+  }
+  auto term = [&](size_t m) {
+    HFr co;
+    memcpy(&co, &tb.g_coeff[m], 32);
+    terms[m] = host::g1_mul(host::g1_from_affine(comms[1 + 2 * cc + tb.g_factor[m][0]]), co);
+  };
+  if (small_coeffs)
+    for (size_t m = 0; m < tb.num_terms; m++) term(m);
+  else
+    host_parallel_for(tb.num_terms, term);
+  host::G1Xyzz acc = host::G1Xyzz::identity();
+  for (auto& t : terms) acc = host::g1_add(acc, t);
+  comms[0] = host::g1_to_affine(acc);
+}
+
 void lasso_prove(Ctx& c, const Pcs& pcs, const lh_lasso_table& tb, size_t n, const uint32_t* const* d_dims,
                  Transcript& tr) {
   lasso_check_table(tb);
@@ -502,19 +692,8 @@ void lasso_prove(Ctx& c, const Pcs& pcs, const lh_lasso_table& tb, size_t n, con
   // times when asked (Ctx::phase_times_resolve); lasso_ms[8], the total, is the host's wall clock
   const double t0 = now_ms();
   double* ph = c.lasso_ms;
-  for (int k = 0; k < 8; k++)
-    if (!c.phase_ev[k]) LH_HIP(hipEventCreate(&c.phase_ev[k]));
-  c.phase_ev_pending = false;
-  LH_HIP(hipEventRecord(c.phase_ev[0], c.stream));
-  c.comm_phase = 0;
-  struct PhaseGuard {  // (collectives issued after the prove - or after it failed - count as outside)
-    Ctx& c;
-    ~PhaseGuard() { c.comm_phase = 7; }
-  } phase_guard{c};
-  auto lap = [&](int idx) {
-    LH_HIP(hipEventRecord(c.phase_ev[idx + 1], c.stream));
-    c.comm_phase = idx + 1;
-  };
+  LassoPhases phase_guard(c);
+  auto lap = [&](int idx) { phase_guard.lap(idx); };
 
   ArenaScope scope(c.arena);
   c.quad_sums.clear();  // (nothing of an earlier prove: the arena hands out the same pointers again)
@@ -639,94 +818,12 @@ void lasso_prove(Ctx& c, const Pcs& pcs, const lh_lasso_table& tb, size_t n, con
     // (range / AND / XOR tables): 4 of 9 column MSMs instead of 9 for the range check.
     // (sharded: this rank's share of the bases; every MSM below is the commitment of a shard - the chunk-split-then-sum
     // of util/arithmetic/msm.rs:101-114 with the shards as chunks - and the partial commitments are added at the end)
-    const G1Affine* bases = shn ? pcs.shard_bases(nv) : pcs.commit_bases(nv);
-    bool linear_g = true;
-    for (uint32_t m = 0; m < tb.num_terms; m++) linear_g = linear_g && tb.g_num_factors[m] == 1;
-    const size_t total = 1 + 3 * cc + alpha;
     std::vector<MsmJob> jobs;
-    std::vector<size_t> slot;  // position of each job's result in `comms`
-    auto add_job = [&](size_t pos, const void* col, bool u32, size_t len) {
-      jobs.push_back(MsmJob{col, u32, bases, len});
-      slot.push_back(pos);
-    };
-    if (!linear_g && a_small) {  // (product g with a 32-bit output column: a u32 job, every entry below 2^a_bits)
-      add_job(0, a_small, true, N);
-      jobs.back().known_bits = w.a_bits;
-    } else if (!linear_g) {
-      add_job(0, a, false, N);
-    }
-    std::vector<size_t> dim_job(cc);
-    for (size_t j = 0; j < cc; j++) {
-      dim_job[j] = jobs.size(), add_job(1 + j, d_dims[j], true, N);
-      jobs.back().known_bits = (uint32_t)l;  // (the access counters rejected any index >= 2^l)
-      if (!w.dim_sorted.empty()) {
-        jobs.back().sorted_scalars = w.dim_sorted[j], jobs.back().sorted_index = w.dim_index[j];
-        c.route.v[RouteStats::SORTED_REUSE]++;
-      }
-    }
-    // read_ts columns are small (a cell's access count): two of them share one pass over the points when their bit
-    // lengths allow (MsmJob::pack_shift; the access counts bound the timestamps)
-    std::vector<HG1> second(cc);
-    std::vector<size_t> second_of;  // chunks whose commitment comes back through `second`
-    {
-      std::vector<uint32_t>& ors = count_ors;
-      std::vector<const uint32_t*> cols(fcs.begin(), fcs.end());
-      const bool pack_on = c.opt.lasso_pack_ts != 0;  // 0: one MSM pass per read_ts column (A/B measurements)
-      if (pack_on && cc >= 2 && N >= ((size_t)1 << 12)) k_or_u32(c, cols.data(), cc, M, ors.data());
-      auto bits_of = [](uint32_t v) { return v ? 32u - (uint32_t)__builtin_clz(v) : 0u; };
-      for (size_t j = 0; j < cc; j++) {
-        const uint32_t b0 = std::max(bits_of(ors[j]), 4u), b1 = j + 1 < cc ? bits_of(ors[j + 1]) : 0;
-        if (ors[j] && j + 1 < cc && ors[j + 1] && b0 + b1 <= MSM_PACK_MAX_BITS &&
-            N >= ((size_t)MSM_PACK_MIN_POINTS_PER_BUCKET << (b0 + b1))) {  // (worth it while the points outnumber the buckets)
-          uint32_t* packed = c.arena.alloc_n<uint32_t>(N);
-          k_pack_u32(c, rts[j], rts[j + 1], b0, N, packed);
-          add_job(1 + cc + j, packed, true, N);
-          jobs.back().known_bits = b0 + b1;
-          jobs.back().pack_shift = b0;
-          jobs.back().out_second = (G1Affine*)&second[j + 1];
-          second_of.push_back(j + 1);
-          c.route.v[RouteStats::PACKED_TS]++;
-          j++;
-        } else {
-          add_job(1 + cc + j, rts[j], true, N);
-          jobs.back().known_bits = bits_of(ors[j]);  // (0 when the counts were not looked at: measured then)
-        }
-      }
-    }
-    // E_i = T[dim_j]: commit(E_i) = sum_d T[d] * B_d over the BUCKET sums B_d of dim_j's commitment - no second pass
-    // over the N points (msm.hip, MsmJob::derived_parent; falls back to an ordinary column when the window shape of
-    // dim_j does not allow it)
-    SubtableOrders& orders = *w.tables;
-    for (size_t i = 0; i < alpha; i++)
-      if (tb.memory_subtable[i] != LH_SUBTABLE_IDENTITY) {
-        add_job(1 + 2 * cc + i, E[i], true, N);
-        // (the derived route has no bucket for dim = 0 - msm.hip: T[0] must be 0 - and EQ has T[0] = 1: an ordinary column)
-        // A registered subtable asks for the route exactly when its T[0] is 0 (its l is at most 20 by registration).
-        bool derive = l <= 20 && tb.memory_subtable[i] != LH_SUBTABLE_EQ;
-        if (subtable_is_custom(tb.memory_subtable[i])) {
-          uint32_t t0 = 0;
-          orders.custom_table(tb.memory_subtable[i], &t0);
-          derive = t0 == 0;
-        }
-        if (derive) {
-          MsmJob& jb = jobs.back();
-          jb.derived_parent = (int)dim_job[tb.memory_chunk[i]];
-          orders.get(tb.memory_subtable[i], &jb.d_table, &jb.d_order);
-          jb.table_in_bits = (uint32_t)l, jb.table_out_bits = lasso_subtable_bits(tb.memory_subtable[i], l);
-          c.route.v[RouteStats::DERIVED]++;
-        }
-        jobs.back().known_bits = lasso_subtable_bits(tb.memory_subtable[i], l);  // (l/2)-bit halves combined, or one bit
-      }
-    // final_cts (2^l entries) is replicated - but an MSM is additive over point ranges (the chunk-then-sum of
-    // util/arithmetic/msm.rs:101-114): rank s commits the counts [s 2^l / R, (s + 1) 2^l / R) against the same range of
-    // the level's first bases, and the partial commitments join the exchange below - no rank repeats another's additions
-    const ReplicatedRange fc_range(sh, M);
-    for (size_t j = 0; j < cc; j++) {
-      add_job(1 + 2 * cc + alpha + j, fcs[j] + fc_range.first, true, fc_range.count);
-      jobs.back().bases = pcs.commit_bases(nv) + fc_range.first;
-      jobs.back().known_bits = count_ors[j] ? 32u - (uint32_t)__builtin_clz(count_ors[j]) : 0u;
-    }
-    std::vector<HG1> part(jobs.size()), comms(total);
+    LassoCommitPlan plan;
+    lasso_commit_jobs(c, pcs, tb, n, nv, d_dims, w, a, a_small, count_ors, false, nullptr, jobs, plan);
+    std::vector<HG1>& second = plan.second;
+    const std::vector<size_t>& second_of = plan.second_of;
+    std::vector<HG1> part(jobs.size()), comms;
     // (stage 1 of the opening's precommit goes to the helper from behind this batch's accumulation launches; not in a sharded
     // proof, whose commit ends in an exchange, and not under the profiler)
     std::function<void(bool)> stage1 = [&](bool on_aux) {
@@ -746,35 +843,8 @@ void lasso_prove(Ctx& c, const Pcs& pcs, const lh_lasso_table& tb, size_t n, con
       for (size_t q = 0; q < second_of.size(); q++) second[second_of[q]] = sums[part.size() + q];
     }
     c.host_stamp("commit:summed");
-    for (size_t k = 0; k < jobs.size(); k++) comms[slot[k]] = part[k];
-    for (size_t j : second_of) comms[1 + cc + j] = second[j];
-    for (size_t i = 0; i < alpha; i++)
-      if (tb.memory_subtable[i] == LH_SUBTABLE_IDENTITY) comms[1 + 2 * cc + i] = comms[1 + tb.memory_chunk[i]];
-    if (linear_g) {
-      std::vector<host::G1Xyzz> terms(tb.num_terms);
-      // (the coefficients of the range / AND / XOR tables are powers of two below 2^64: a few dozen doublings each, done
-      // here - waking the host pool for them cost more than they do; wide coefficients go to the pool)
-      bool small_coeffs = true;
-      for (uint32_t m = 0; m < tb.num_terms && small_coeffs; m++) {
-        HFr co;
-        memcpy(&co, &tb.g_coeff[m], 32);
-        uint64_t canon[4];
-        co.to_canonical(canon);
-        small_coeffs = !canon[1] && !canon[2] && !canon[3];
-      }
-      auto term = [&](size_t m) {
-        HFr co;
-        memcpy(&co, &tb.g_coeff[m], 32);
-        terms[m] = host::g1_mul(host::g1_from_affine(comms[1 + 2 * cc + tb.g_factor[m][0]]), co);
-      };
-      if (small_coeffs)
-        for (size_t m = 0; m < tb.num_terms; m++) term(m);
-      else
-        host_parallel_for(tb.num_terms, term);
-      host::G1Xyzz acc = host::G1Xyzz::identity();
-      for (auto& t : terms) acc = host::g1_add(acc, t);
-      comms[0] = host::g1_to_affine(acc);
-    }
+    comms = lasso_commit_collect(tb, plan, part);
+    lasso_commit_derive(tb, comms);
     c.host_stamp("commit:linear");
     lasso_write_commitments(tr, comms);
     c.host_stamp("commit:written");
@@ -851,6 +921,409 @@ void lasso_prove(Ctx& c, const Pcs& pcs, const lh_lasso_table& tb, size_t n, con
   lap(6);
   c.host_stamp("open:end");
   c.host_stamps_print();
+  ph[7] = 0;
+  ph[8] = now_ms() - t0;
+  c.phase_ev_pending = true;
+}
+
+// ------------------------------------------------------------------ several tables in one proof (tests/lasso_batch_ref.py)
+size_t lasso_batch_check(const lh_lasso_table* const* tables, size_t K, size_t n) {
+  LH_REQUIRE(K >= 1 && K <= (size_t)LH_LASSO_BATCH_MAX_TABLES, LH_ERR_ARG,
+             "lasso batch: 1 to " + std::to_string(LH_LASSO_BATCH_MAX_TABLES) + " tables");
+  LH_REQUIRE(tables != nullptr, LH_ERR_ARG, "null argument: tables");
+  LH_REQUIRE(n >= 1 && n < 31, LH_ERR_ARG, "lasso: need at least one variable");
+  size_t nv = n, memories = 0, terms = 0, at_n = 0;
+  for (size_t t = 0; t < K; t++) {
+    LH_REQUIRE(tables[t] != nullptr, LH_ERR_ARG, "null argument: table " + std::to_string(t));
+    const lh_lasso_table& tb = *tables[t];
+    lasso_check_table(tb);
+    // one identity mask (a field element read as 63 bits) frames a table's commitments
+    LH_REQUIRE(1 + 3 * (size_t)tb.num_chunks + tb.num_memories <= 63, LH_ERR_ARG,
+               "lasso batch: table " + std::to_string(t) + " has more than 63 commitments (one identity mask per table)");
+    nv = std::max<size_t>(nv, tb.chunk_bits);
+    memories += tb.num_memories, terms += tb.num_terms, at_n += 2 * (size_t)tb.num_chunks + tb.num_memories;
+  }
+  // 4 product trees per memory in ONE grand-product GKR, whose layers take 2 B + 1 <= SC_MAX_TABLES tables (gkr.cpp), and the
+  // paired leaf layer SC_RW_MAX_PAIRS read / write pairs
+  LH_REQUIRE(memories <= (size_t)LASSO_RW_BATCH_MAX && 8 * memories + 1 <= (size_t)SC_MAX_TABLES, LH_ERR_ARG,
+             "lasso batch: more than " + std::to_string(LASSO_RW_BATCH_MAX) + " memories in all (4 product trees each in one GKR batch)");
+  LH_REQUIRE(terms <= (size_t)LH_SC_MAX_TERMS, LH_ERR_ARG, "lasso batch: too many g terms in all for one Surge sum-check");
+  // the batch opening merges every column opened at r_N into one table in one launch (k_lincomb_mixed)
+  LH_REQUIRE(at_n <= (size_t)LCM_MAX_SMALL, LH_ERR_ARG, "lasso batch: too many columns opened at one point");
+  return nv;
+}
+
+void lasso_prove_batch(Ctx& c, const Pcs& pcs, const lh_lasso_table* const* tables, size_t K, size_t n,
+                       const uint32_t* const* const* d_dims, Transcript& tr) {
+  const size_t nv = lasso_batch_check(tables, K, n);
+  LH_REQUIRE(d_dims != nullptr, LH_ERR_ARG, "null argument: d_dims");
+  for (size_t t = 0; t < K; t++) {
+    LH_REQUIRE(d_dims[t] != nullptr, LH_ERR_ARG, "null argument: d_dims of table " + std::to_string(t));
+    for (size_t j = 0; j < tables[t]->num_chunks; j++)
+      LH_REQUIRE(d_dims[t][j] != nullptr, LH_ERR_ARG, "null argument: a chunk column of table " + std::to_string(t));
+  }
+  LH_REQUIRE(!Shard(c).on && !(c.has_comm && c.comm.size > 1), LH_ERR_ARG,
+             "lasso batch: sharded batches are not supported (the ctx is inside a sharded prove or has a communicator of several ranks)");
+  LH_REQUIRE(pcs.commit_bases && !pcs.commit_columns && !pcs.commit_columns_and_write, LH_ERR_ARG,
+             "lasso batch: implemented for schemes that commit columns against bases");
+  if (nv > pcs.max_vars) throw Error(LH_ERR_INVALID_PCS_PARAM, "Too many variates of poly to commit");
+  const size_t N = (size_t)1 << n, NV = (size_t)1 << nv;
+  struct Table {
+    const lh_lasso_table* tb;
+    const uint32_t* const* dims;
+    size_t cc, l, alpha, M;
+    bool linear_g;
+    LassoColumns w;
+    Fr* a = nullptr;
+    uint32_t* a_small = nullptr;
+    std::vector<uint32_t> count_ors;
+    std::vector<int> shared_dim_job, shared_table, shared_chunk;  // per chunk: the earlier table's column it shares (-1: none)
+    LassoCommitPlan plan;
+    std::vector<HG1> comms;
+    size_t poly_base = 0, mem_base = 0;  // of its polys in the opening, of its memories in the batch
+    SmallLinear a_linear;
+    HFr v;
+    std::vector<HFr> ev;  // dim | read_ts | E at r_N, final_cts at r_M(l)
+  };
+  std::vector<Table> T(K);
+  std::vector<size_t> ls;  // the distinct chunk sizes in order of first appearance: r_M(ls[q]) is point 3 + q
+  size_t A = 0, num_polys = 0;
+  bool all_linear = true;
+  for (size_t t = 0; t < K; t++) {
+    Table& x = T[t];
+    x.tb = tables[t], x.dims = d_dims[t];
+    x.cc = x.tb->num_chunks, x.l = x.tb->chunk_bits, x.alpha = x.tb->num_memories, x.M = (size_t)1 << x.l;
+    x.linear_g = true;
+    for (uint32_t m = 0; m < x.tb->num_terms; m++) x.linear_g = x.linear_g && x.tb->g_num_factors[m] == 1;
+    all_linear = all_linear && x.linear_g;
+    x.mem_base = A, x.poly_base = num_polys;
+    A += x.alpha, num_polys += 1 + 3 * x.cc + x.alpha;
+    if (std::find(ls.begin(), ls.end(), x.l) == ls.end()) ls.push_back(x.l);
+  }
+  auto point_of_l = [&](size_t l) { return 3 + (size_t)(std::find(ls.begin(), ls.end(), l) - ls.begin()); };
+
+  const double t0 = now_ms();
+  double* ph = c.lasso_ms;
+  LassoPhases phases(c);
+  ArenaScope scope(c.arena);
+  c.quad_sums.clear();      // (nothing of an earlier prove: the arena hands out the same pointers again)
+  EqHalfScope eq_scope(c);  // (the shared eq tables are arena memory of this scope)
+  open_precommit_cancel(c);
+  c.route = RouteStats();
+
+  // ---- witness, table by table.  A chunk column that an earlier table of the same chunk size was handed too (the same device
+  // pointer: AND and XOR over the same operands) is counted once: its read_ts and final_cts serve both tables
+  const bool keep_sorted = n >= (size_t)knob(Knob::MSM_SLAB_LOG);
+  for (size_t t = 0; t < K; t++) {
+    Table& x = T[t];
+    LassoColumns reuse;
+    reuse.rts.assign(x.cc, nullptr), reuse.fcs.assign(x.cc, nullptr);
+    x.shared_table.assign(x.cc, -1), x.shared_chunk.assign(x.cc, -1), x.shared_dim_job.assign(x.cc, -1);
+    for (size_t j = 0; j < x.cc; j++)
+      for (size_t s = 0; s < t && x.shared_table[j] < 0; s++)
+        for (size_t k = 0; k < T[s].cc && T[s].l == x.l; k++)
+          if (T[s].dims[k] == x.dims[j] && T[s].shared_table[k] < 0) {  // (the table that counted it)
+            x.shared_table[j] = (int)s, x.shared_chunk[j] = (int)k;
+            reuse.rts[j] = T[s].w.rts[k], reuse.fcs[j] = T[s].w.fcs[k];
+            break;
+          }
+    x.w = lasso_witness_columns(c, *x.tb, n, x.dims, &x.a, &x.a_small, keep_sorted, &reuse);
+  }
+  phases.lap(0);
+
+  // ---- 0/1: domain separation, then every table's commitments from ONE batched MSM
+  tr.common_field_element(HFr::from_u64(K));
+  tr.common_field_element(HFr::from_u64(n));
+  for (const Table& x : T)
+    for (size_t v : {x.l, x.cc, x.alpha}) tr.common_field_element(HFr::from_u64(v));
+  {
+    // the access counts' widths (they bound the timestamps: packing, known_bits): one readback per distinct chunk size
+    const bool want_ors = c.opt.lasso_pack_ts != 0 && N >= ((size_t)1 << 12);
+    for (Table& x : T) x.count_ors.assign(x.cc, 0);
+    if (want_ors)
+      for (size_t l : ls) {
+        std::vector<const uint32_t*> cols;
+        for (const Table& x : T)
+          if (x.l == l) cols.insert(cols.end(), x.w.fcs.begin(), x.w.fcs.end());
+        std::vector<uint32_t> ors(cols.size(), 0);
+        k_or_u32(c, cols.data(), cols.size(), (size_t)1 << l, ors.data());
+        size_t at = 0;
+        for (Table& x : T)
+          if (x.l == l)
+            for (size_t j = 0; j < x.cc; j++) x.count_ors[j] = ors[at++];
+      }
+    std::vector<MsmJob> jobs;
+    for (size_t t = 0; t < K; t++) {
+      Table& x = T[t];
+      for (size_t j = 0; j < x.cc; j++)
+        if (x.shared_table[j] >= 0) x.shared_dim_job[j] = (int)T[x.shared_table[j]].plan.dim_job[x.shared_chunk[j]];
+      lasso_commit_jobs(c, pcs, *x.tb, n, nv, x.dims, x.w, x.a, x.a_small, x.count_ors, true, x.shared_dim_job.data(), jobs, x.plan);
+    }
+    std::vector<HG1> part(jobs.size());
+    msm_batch(c, jobs.data(), jobs.size(), (G1Affine*)part.data());
+    for (Table& x : T) {
+      x.comms = lasso_commit_collect(*x.tb, x.plan, part);
+      for (size_t j = 0; j < x.cc; j++)
+        if (x.shared_table[j] >= 0) {
+          const Table& s = T[x.shared_table[j]];
+          const size_t k = (size_t)x.shared_chunk[j];
+          x.comms[1 + j] = s.comms[1 + k];
+          x.comms[1 + x.cc + j] = s.comms[1 + s.cc + k];
+          x.comms[1 + 2 * x.cc + x.alpha + j] = s.comms[1 + 2 * s.cc + s.alpha + k];
+        }
+      lasso_commit_derive(*x.tb, x.comms);
+      lasso_write_commitments(tr, x.comms);
+    }
+  }
+  phases.lap(1);
+
+  // ---- 2: r, and a_t(r) for every table
+  const std::vector<HFr> r = tr.squeeze_challenges(n);
+  {
+    std::vector<const uint32_t*> cols;
+    std::vector<const Fr*> frs;
+    for (const Table& x : T) {
+      if (x.a_small) cols.push_back(x.a_small);
+      else frs.push_back(x.a);
+    }
+    std::vector<HFr> vs(cols.size()), vf;
+    if (!cols.empty() && n >= 2) {
+      const Fr* eq_half = eq_half_get(c, r.data(), n, false);
+      k_inner_products_small_half(c, cols.data(), cols.size(), eq_half, N / 2, dev(r[0]), (Fr*)vs.data());
+    } else if (!cols.empty()) {
+      ArenaScope inner(c.arena);
+      Fr* eq = c.arena.alloc_n<Fr>(N);
+      k_eq_xy(c, (const Fr*)r.data(), n, eq);
+      k_inner_products_small(c, cols.data(), cols.size(), eq, N, (Fr*)vs.data());
+    }
+    if (!frs.empty()) vf = evaluate_polys(c, frs.data(), frs.size(), n, r.data(), false);
+    size_t is = 0, ifr = 0;
+    for (Table& x : T) x.v = x.a_small ? vs[is++] : vf[ifr++];
+  }
+  for (const Table& x : T) tr.write_field_element(x.v);
+
+  // ---- 3: ONE Surge sum-check over eq * sum_t rho^t g_t
+  const HFr rho = tr.squeeze_challenge();
+  std::vector<HFr> rho_pow(K, HFr::one());
+  for (size_t t = 1; t < K; t++) rho_pow[t] = rho_pow[t - 1] * rho;
+  HFr claim = HFr::zero();
+  for (size_t t = 0; t < K; t++) claim += rho_pow[t] * T[t].v;
+  std::vector<const Fr*> E_fr(A, nullptr);  // field-element views of the E columns (a g with product terms in the batch)
+  std::vector<HFr> r_z, e_rz;
+  if (all_linear) {
+    // every g linear: the summand is eq * sum_t rho^t a_t entry by entry - ONE table, as in lasso_argue's linear case -
+    // formed from the output columns; the evaluations E_t,i(r_z) are inner products of the 32-bit columns with eq(r_z)
+    {
+      ArenaScope inner(c.arena);
+      Fr* comb = c.arena.alloc_n<Fr>(N);
+      std::vector<const Fr*> frs;
+      std::vector<Fr> wfr, wsm;
+      std::vector<const uint32_t*> sm;
+      std::vector<size_t> sm_len;
+      for (size_t t = 0; t < K; t++) {
+        if (T[t].a_small) sm.push_back(T[t].a_small), sm_len.push_back(N), wsm.push_back(dev(rho_pow[t]));
+        else frs.push_back(T[t].a), wfr.push_back(dev(rho_pow[t]));
+      }
+      k_lincomb_mixed(c, frs.data(), wfr.data(), frs.size(), sm.data(), sm_len.data(), wsm.data(), sm.size(), N, comb);
+      lh_sop one_term;
+      memset(&one_term, 0, sizeof(one_term));
+      one_term.global_eq = 0;
+      one_term.num_terms = 1;
+      const HFr one = HFr::one();
+      memcpy(&one_term.coeff[0], &one, 32);
+      one_term.num_factors[0] = 1;
+      one_term.factor[0][0] = 0;
+      ScOptions so;
+      so.sum_is_exact = true;
+      const Fr* tab = comb;
+      SumCheckResult sc = sum_check_prove(c, LH_SC_EVALUATIONS, n, one_term, &tab, 1, r.data(), 1, claim, tr, so);
+      r_z = sc.challenges;
+    }
+    std::vector<const uint32_t*> cols;
+    for (const Table& x : T) cols.insert(cols.end(), x.w.E.begin(), x.w.E.end());
+    e_rz.assign(A, HFr::zero());
+    if (n >= 2) {  // (the table of r_z[1..] stays for the batch opening at r_z)
+      const Fr* eq_half = eq_half_get(c, r_z.data(), n, false);
+      k_inner_products_small_half(c, cols.data(), A, eq_half, N / 2, dev(r_z[0]), (Fr*)e_rz.data());
+    } else {
+      ArenaScope inner(c.arena);
+      Fr* eq = c.arena.alloc_n<Fr>(N);
+      k_eq_xy(c, (const Fr*)r_z.data(), n, eq);
+      k_inner_products_small(c, cols.data(), A, eq, N, (Fr*)e_rz.data());
+    }
+  } else {
+    // one expression with every table's terms, table t's scaled by rho^t, over the field-element views of all E columns
+    lh_sop surge;
+    memset(&surge, 0, sizeof(surge));
+    surge.global_eq = 0;
+    uint32_t nt = 0;
+    for (size_t t = 0; t < K; t++) {
+      const Table& x = T[t];
+      for (size_t i = 0; i < x.alpha; i++) {
+        Fr* d = c.arena.alloc_n<Fr>(N);
+        k_fr_from_u32(c, x.w.E[i], N, d);
+        E_fr[x.mem_base + i] = d;
+      }
+      for (uint32_t m = 0; m < x.tb->num_terms; m++, nt++) {
+        HFr co;
+        memcpy(&co, &x.tb->g_coeff[m], 32);
+        co *= rho_pow[t];
+        memcpy(&surge.coeff[nt], &co, 32);
+        surge.num_factors[nt] = x.tb->g_num_factors[m];
+        for (int k = 0; k < x.tb->g_num_factors[m]; k++) surge.factor[nt][k] = (uint8_t)(x.mem_base + x.tb->g_factor[m][k]);
+      }
+    }
+    surge.num_terms = nt;
+    ScOptions so;
+    so.sum_is_exact = true;
+    SumCheckResult sc = sum_check_prove(c, LH_SC_EVALUATIONS, n, surge, E_fr.data(), A, r.data(), 1, claim, tr, so);
+    r_z = sc.challenges, e_rz = sc.evals;
+  }
+  tr.write_field_elements(e_rz);
+  phases.lap(2);
+
+  // ---- 4: memory checking, ONE grand-product GKR: the n-variable trees RS, WS of every memory, then Init, Final of every memory
+  const HFr gamma = tr.squeeze_challenge(), tau = tr.squeeze_challenge(), gamma2 = gamma * gamma;
+  std::vector<HFr> r_N;
+  std::vector<std::vector<HFr>> r_M(ls.size());
+  {
+    ArenaScope inner(c.arena);
+    std::vector<const Fr*> leaves(4 * A), level_up(4 * A, nullptr);
+    std::vector<size_t> depths(4 * A);
+    std::vector<uint8_t> plus_one(4 * A, 0);
+    // (lasso_argue: the level above the leaves comes with them from 2^12 lookups on, and where the n-variable trees are alone
+    // at their leaf layer - n above every chunk size - that layer runs over the read set and the write leaves are not stored)
+    const size_t max_l = *std::max_element(ls.begin(), ls.end());
+    const bool fused_up = n >= 12, ws_implicit = fused_up && n > max_l;
+    LassoRwBatch rw;
+    memset(&rw, 0, sizeof(rw));
+    for (const Table& x : T)
+      for (size_t i = 0; i < x.alpha; i++) {
+        const size_t b = x.mem_base + i, j = x.tb->memory_chunk[i];
+        rw.dim[b] = x.dims[j], rw.e[b] = x.w.E[i], rw.ts[b] = x.w.rts[j];
+        rw.rs[b] = c.arena.alloc_n<Fr>(N);
+        rw.ws[b] = ws_implicit ? nullptr : c.arena.alloc_n<Fr>(N);
+        if (fused_up) {
+          rw.rs_up[b] = c.arena.alloc_n<Fr>(N / 2), rw.ws_up[b] = c.arena.alloc_n<Fr>(N / 2);
+          level_up[2 * b] = rw.rs_up[b], level_up[2 * b + 1] = rw.ws_up[b];
+        }
+        leaves[2 * b] = rw.rs[b], leaves[2 * b + 1] = rw.ws[b];
+        plus_one[2 * b + 1] = 1;
+        depths[2 * b] = depths[2 * b + 1] = n;
+        Fr* in = c.arena.alloc_n<Fr>(x.M);
+        Fr* fi = c.arena.alloc_n<Fr>(x.M);
+        k_lasso_if_leaves(c, (int)x.tb->memory_subtable[i], (uint32_t)x.l, x.w.fcs[j], x.M, dev(gamma), dev(gamma2), dev(tau), in, fi,
+                          x.w.T.empty() ? nullptr : x.w.T[i]);
+        leaves[2 * A + 2 * b] = in, leaves[2 * A + 2 * b + 1] = fi;
+        depths[2 * A + 2 * b] = depths[2 * A + 2 * b + 1] = x.l;
+      }
+    k_lasso_rw_leaves_batch(c, rw, A, N, fused_up, dev(gamma), dev(gamma2), dev(tau));
+    phases.lap(3);
+    GrandProductResult gp = prove_grand_product(c, 4 * A, leaves.data(), depths.data(), tr, level_up.data(), plus_one.data());
+    r_N = gp.points[0];
+    for (const Table& x : T) r_M[point_of_l(x.l) - 3] = gp.points[2 * A + 2 * x.mem_base];
+  }
+  phases.lap(4);
+
+  // ---- 5: evaluations at r_N (dim | read_ts | E of every table, one pass) and at r_M(l) (final_cts, per chunk size)
+  // (the eq table of r_N[1..] is made OUTSIDE the scope below: it stays cached for the batch opening at r_N)
+  const Fr* eq_half_n = n >= 2 ? eq_half_get(c, r_N.data(), n, false) : nullptr;
+  {
+    ArenaScope inner(c.arena);
+    std::vector<const uint32_t*> at_n;
+    for (const Table& x : T) {
+      for (size_t j = 0; j < x.cc; j++) at_n.push_back(x.dims[j]);
+      for (size_t j = 0; j < x.cc; j++) at_n.push_back(x.w.rts[j]);
+      for (size_t i = 0; i < x.alpha; i++) at_n.push_back(x.w.E[i]);
+    }
+    std::vector<HFr> ev_n(at_n.size());
+    if (eq_half_n) {
+      k_inner_products_small_half(c, at_n.data(), at_n.size(), eq_half_n, N / 2, dev(r_N[0]), (Fr*)ev_n.data());
+    } else {
+      Fr* eq = c.arena.alloc_n<Fr>(N);
+      k_eq_xy(c, (const Fr*)r_N.data(), n, eq);
+      k_inner_products_small(c, at_n.data(), at_n.size(), eq, N, (Fr*)ev_n.data());
+    }
+    size_t at = 0;
+    for (Table& x : T) {
+      x.ev.assign(ev_n.begin() + at, ev_n.begin() + at + 2 * x.cc + x.alpha);
+      at += 2 * x.cc + x.alpha;
+    }
+    for (size_t q = 0; q < ls.size(); q++) {
+      std::vector<const uint32_t*> at_l;
+      for (const Table& x : T)
+        if (x.l == ls[q]) at_l.insert(at_l.end(), x.w.fcs.begin(), x.w.fcs.end());
+      std::vector<HFr> ev_l(at_l.size());
+      const size_t M = (size_t)1 << ls[q];
+      Fr* eq = c.arena.alloc_n<Fr>(M);
+      k_eq_xy(c, (const Fr*)r_M[q].data(), ls[q], eq);
+      k_inner_products_small(c, at_l.data(), at_l.size(), eq, M, (Fr*)ev_l.data());
+      size_t k = 0;
+      for (Table& x : T)
+        if (x.l == ls[q])
+          for (size_t j = 0; j < x.cc; j++) x.ev.push_back(ev_l[k++]);
+    }
+  }
+  for (const Table& x : T) tr.write_field_elements(x.ev);
+  phases.lap(5);
+
+  // ---- 6: ONE batch opening over nv variables: polys table-major, points r, r_z, r_N, r_M per chunk size (zero-padded)
+  // (the opening's precommit on the helper ctx is not started on this path: DESIGN.md §17)
+  {
+    std::vector<SmallPoly> small(num_polys, SmallPoly());
+    std::vector<const Fr*> polys(num_polys, nullptr);
+    std::vector<lh_evaluation> evs;
+    auto push = [&](size_t poly, size_t point, const HFr& val) {
+      lh_evaluation e;
+      memset(&e, 0, sizeof(e));
+      e.poly = (uint32_t)poly, e.point = (uint32_t)point;
+      memcpy(&e.value, &val, 32);
+      evs.push_back(e);
+    };
+    for (size_t t = 0; t < K; t++) {
+      Table& x = T[t];
+      const size_t p0 = x.poly_base, cc = x.cc, alpha = x.alpha;
+      if (x.a_small && x.w.a_bits) {  // (product g: a column of its own, every entry below 2^a_bits)
+        small[p0] = SmallPoly{x.a_small, N, x.w.a_bits};
+      } else if (x.a_small) {
+        for (uint32_t m = 0; m < x.tb->num_terms; m++) {
+          HFr co;
+          memcpy(&co, &x.tb->g_coeff[m], 32);
+          x.a_linear.poly.push_back(p0 + 1 + 2 * cc + x.tb->g_factor[m][0]);
+          x.a_linear.coeff.push_back(co);
+        }
+        small[p0] = SmallPoly{x.a_small, N, 0, &x.a_linear};
+      } else if (N < NV) {  // (no 32-bit form, and a chunk size above n: the table needs the padding)
+        Fr* a_pad = c.arena.alloc_n<Fr>(NV);
+        LH_HIP(hipMemcpyAsync(a_pad, x.a, N * sizeof(Fr), hipMemcpyDeviceToDevice, c.stream));
+        LH_HIP(hipMemsetAsync(a_pad + N, 0, (NV - N) * sizeof(Fr), c.stream));
+        polys[p0] = a_pad;
+      } else {
+        polys[p0] = x.a;
+      }
+      for (size_t j = 0; j < cc; j++) {
+        small[p0 + 1 + j] = SmallPoly{x.dims[j], N, (uint32_t)x.l};
+        small[p0 + 1 + cc + j] = SmallPoly{x.w.rts[j], N, x.count_ors[j] ? 32u - (uint32_t)__builtin_clz(x.count_ors[j]) : 0u};
+        small[p0 + 1 + 2 * cc + alpha + j] = SmallPoly{x.w.fcs[j], x.M, 0};
+      }
+      for (size_t i = 0; i < alpha; i++)
+        small[p0 + 1 + 2 * cc + i] = SmallPoly{x.w.E[i], N, lasso_subtable_bits(x.tb->memory_subtable[i], x.l)};
+      push(p0, 0, x.v);
+      for (size_t i = 0; i < alpha; i++) push(p0 + 1 + 2 * cc + i, 1, e_rz[x.mem_base + i]);
+      for (size_t j = 0; j < cc; j++) push(p0 + 1 + j, 2, x.ev[j]);
+      for (size_t j = 0; j < cc; j++) push(p0 + 1 + cc + j, 2, x.ev[cc + j]);
+      for (size_t i = 0; i < alpha; i++) push(p0 + 1 + 2 * cc + i, 2, x.ev[2 * cc + i]);
+      for (size_t j = 0; j < cc; j++) push(p0 + 1 + 2 * cc + alpha + j, point_of_l(x.l), x.ev[2 * cc + alpha + j]);
+    }
+    const size_t num_points = 3 + ls.size();
+    std::vector<HFr> points(num_points * nv, HFr::zero());
+    std::copy(r.begin(), r.end(), points.begin());
+    std::copy(r_z.begin(), r_z.end(), points.begin() + nv);
+    std::copy(r_N.begin(), r_N.end(), points.begin() + 2 * nv);
+    for (size_t q = 0; q < ls.size(); q++) std::copy(r_M[q].begin(), r_M[q].end(), points.begin() + (3 + q) * nv);
+    pcs.batch_open(nv, polys.data(), num_polys, points.data(), num_points, evs.data(), evs.size(), tr, small.data());
+  }
+  phases.lap(6);
   ph[7] = 0;
   ph[8] = now_ms() - t0;
   c.phase_ev_pending = true;

@@ -1117,6 +1117,127 @@ void lasso_verify(const PcsVerifier& pcs, const lh_lasso_table& tb, size_t n, Tr
   pcs.batch_verify(nv, comms.data(), comms.size() / chunks, points.data(), 4, evals.data(), evals.size(), tr);
 }
 
+// the verifier of lasso_prove_batch (tests/lasso_batch_ref.py verify): lasso_verify / lasso_check over K tables that share
+// r, rho, gamma and tau, one Surge sum-check, one grand product and one batch opening
+static void lasso_verify_batch_checked(const PcsVerifier& pcs, const lh_lasso_table* const* tables, size_t K, size_t n, size_t nv,
+                                       Transcript& tr) {
+  std::vector<size_t> ls, mem_base(K), poly_base(K);  // ls: the distinct chunk sizes, r_M(ls[q]) is point 3 + q
+  size_t A = 0, num_polys = 0, g_degree = 0;
+  for (size_t t = 0; t < K; t++) {
+    const lh_lasso_table& tb = *tables[t];
+    mem_base[t] = A, poly_base[t] = num_polys;
+    A += tb.num_memories, num_polys += 1 + 3 * (size_t)tb.num_chunks + tb.num_memories;
+    if (std::find(ls.begin(), ls.end(), (size_t)tb.chunk_bits) == ls.end()) ls.push_back(tb.chunk_bits);
+    for (size_t m = 0; m < tb.num_terms; m++) g_degree = std::max<size_t>(g_degree, tb.g_num_factors[m]);
+  }
+  auto point_of_l = [&](size_t l) { return 3 + (size_t)(std::find(ls.begin(), ls.end(), l) - ls.begin()); };
+  tr.common_field_element(HFr::from_u64(K));
+  tr.common_field_element(HFr::from_u64(n));
+  for (size_t t = 0; t < K; t++)
+    for (size_t v : {(size_t)tables[t]->chunk_bits, (size_t)tables[t]->num_chunks, (size_t)tables[t]->num_memories})
+      tr.common_field_element(HFr::from_u64(v));
+  std::vector<HG1> comms;
+  for (size_t t = 0; t < K; t++) {
+    std::vector<HG1> block = lasso_read_commitments(tr, 1 + 3 * (size_t)tables[t]->num_chunks + tables[t]->num_memories);
+    comms.insert(comms.end(), block.begin(), block.end());
+  }
+
+  const std::vector<HFr> r = tr.squeeze_challenges(n);
+  const std::vector<HFr> vs = tr.read_field_elements(K);
+  const HFr rho = tr.squeeze_challenge();
+  HFr claim = HFr::zero(), power = HFr::one();
+  for (size_t t = 0; t < K; t++) {
+    claim += power * vs[t];
+    power *= rho;
+  }
+  auto surge = sum_check_verify(LH_SC_EVALUATIONS, n, g_degree + 1, claim, tr);
+  const std::vector<HFr>& r_z = surge.second;
+  const std::vector<HFr> e_rz = tr.read_field_elements(A);
+  HFr want = HFr::zero();
+  power = HFr::one();
+  for (size_t t = 0; t < K; t++) {
+    const lh_lasso_table& tb = *tables[t];
+    HFr acc = HFr::zero();
+    for (size_t m = 0; m < tb.num_terms; m++) {
+      HFr term;
+      memcpy(&term, &tb.g_coeff[m], 32);
+      for (size_t k = 0; k < tb.g_num_factors[m]; k++) term *= e_rz[mem_base[t] + tb.g_factor[m][k]];
+      acc += term;
+    }
+    want += power * acc;
+    power *= rho;
+  }
+  if (surge.first != host_eq_xy_eval(r_z.data(), r.data(), n) * want)
+    throw Error(LH_ERR_INVALID_SNARK, "Surge sum-check final evaluation mismatch");
+
+  const HFr gamma = tr.squeeze_challenge(), tau = tr.squeeze_challenge();
+  std::vector<size_t> depth(2 * A, n);
+  for (size_t t = 0; t < K; t++) depth.insert(depth.end(), 2 * (size_t)tables[t]->num_memories, (size_t)tables[t]->chunk_bits);
+  std::vector<GpClaim> claims;
+  const std::vector<HFr> roots = verify_grand_product(depth, tr, claims);
+  for (size_t b = 0; b < A; b++)
+    if (roots[2 * A + 2 * b] * roots[2 * b + 1] != roots[2 * b] * roots[2 * A + 2 * b + 1])
+      throw Error(LH_ERR_INVALID_SNARK, "memory " + std::to_string(b) + ": Init*WS != RS*Final");
+  const std::vector<HFr> r_N = claims[0].point;
+  std::vector<std::vector<HFr>> r_M(ls.size());
+  for (size_t t = 0; t < K; t++) r_M[point_of_l(tables[t]->chunk_bits) - 3] = claims[2 * A + 2 * mem_base[t]].point;
+
+  std::vector<lh_evaluation> evals;
+  auto push = [&](size_t poly, size_t point, const HFr& val) {
+    lh_evaluation e;
+    e.poly = (uint32_t)poly, e.point = (uint32_t)point;
+    memcpy(&e.value, &val, 32);
+    evals.push_back(e);
+  };
+  auto fingerprint = [&](const HFr& a, const HFr& val, const HFr& ts) { return a * gamma * gamma + val * gamma + ts - tau; };
+  const HFr one = HFr::one();
+  for (size_t t = 0; t < K; t++) {
+    const lh_lasso_table& tb = *tables[t];
+    const size_t c = tb.num_chunks, alpha = tb.num_memories, p0 = poly_base[t];
+    const std::vector<HFr> vals = tr.read_field_elements(3 * c + alpha);
+    const HFr *dim_e = &vals[0], *rts_e = &vals[c], *e_e = &vals[2 * c], *fc_e = &vals[2 * c + alpha];
+    const std::vector<HFr>& pt = r_M[point_of_l(tb.chunk_bits) - 3];
+    const HFr id_M = identity_eval(pt);
+    for (size_t i = 0; i < alpha; i++) {
+      const size_t j = tb.memory_chunk[i], b = mem_base[t] + i;
+      const HFr rs = fingerprint(dim_e[j], e_e[i], rts_e[j]);
+      const HFr init = fingerprint(id_M, subtable_mle_eval(tb.memory_subtable[i], pt), HFr::zero());
+      if (claims[2 * b].claim != rs || claims[2 * b + 1].claim != rs + one || claims[2 * A + 2 * b].claim != init ||
+          claims[2 * A + 2 * b + 1].claim != init + fc_e[j])
+        throw Error(LH_ERR_INVALID_SNARK, "memory " + std::to_string(b) + ": leaf claim mismatch");
+    }
+    push(p0, 0, vs[t]);
+    for (size_t i = 0; i < alpha; i++) push(p0 + 1 + 2 * c + i, 1, e_rz[mem_base[t] + i]);
+    for (size_t j = 0; j < c; j++) push(p0 + 1 + j, 2, dim_e[j]);
+    for (size_t j = 0; j < c; j++) push(p0 + 1 + c + j, 2, rts_e[j]);
+    for (size_t i = 0; i < alpha; i++) push(p0 + 1 + 2 * c + i, 2, e_e[i]);
+    for (size_t j = 0; j < c; j++) push(p0 + 1 + 2 * c + alpha + j, point_of_l(tb.chunk_bits), fc_e[j]);
+  }
+  std::vector<HFr> points;
+  std::vector<const std::vector<HFr>*> pts = {&r, &r_z, &r_N};
+  for (const std::vector<HFr>& pt : r_M) pts.push_back(&pt);
+  for (const std::vector<HFr>* pt : pts) {
+    points.insert(points.end(), pt->begin(), pt->end());
+    points.insert(points.end(), nv - pt->size(), HFr::zero());
+  }
+  pcs.batch_verify(nv, comms.data(), comms.size(), points.data(), pts.size(), evals.data(), evals.size(), tr);
+}
+// A proof that does not verify is LH_ERR_INVALID_SNARK whichever piece found it out (a round message, an opening, bytes that
+// are no point or no field element, a proof that ends early): the message keeps the piece's own words.  What is wrong with
+// the call, not with the proof, keeps its code (LH_ERR_ARG, LH_ERR_INVALID_PCS_PARAM).
+void lasso_verify_batch(const PcsVerifier& pcs, const lh_lasso_table* const* tables, size_t K, size_t n, Transcript& tr) {
+  const size_t nv = lasso_batch_check(tables, K, n);
+  LH_REQUIRE(pcs.chunks == 1 && !pcs.read_commitments, LH_ERR_ARG, "lasso batch: implemented for commitments of one point");
+  try {
+    lasso_verify_batch_checked(pcs, tables, K, n, nv, tr);
+  } catch (const Error& e) {
+    if (e.code == LH_ERR_INVALID_SUMCHECK || e.code == LH_ERR_INVALID_PCS_OPEN || e.code == LH_ERR_TRANSCRIPT ||
+        e.code == LH_ERR_SERIALIZATION)
+      throw Error(LH_ERR_INVALID_SNARK, "lasso batch: " + e.msg);
+    throw;
+  }
+}
+
 // ------------------------------------------------------------------ Brakedown (pcs/multilinear/brakedown.rs:315-396)
 void brakedown_verify(const BdParam& p, const uint8_t root[32], const HFr* point, size_t num_vars, const HFr& eval,
                       Transcript& tr, HashTranscript& ht) {

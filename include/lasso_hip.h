@@ -272,6 +272,29 @@ typedef struct lh_lasso_table {
 lh_status lh_lasso_prove(lh_ctx*, const lh_srs*, const lh_lasso_table*, size_t num_vars,
                          const uint32_t* const* d_dims, lh_transcript* t);
 
+/* ---------------------------------------------------------------- a'': lookups into several tables in ONE proof
+ * num_tables tables with the same number of lookups 2^num_vars, each with its own lh_lasso_table and its own chunk
+ * columns (d_dims[t][j]: chunk column j of table t), argued over one transcript with one commit batch, one Surge
+ * sum-check (eq * sum_t rho^t g_t), one grand-product GKR over all memories and one batch opening; multilinear KZG.  The
+ * protocol is specified in tests/lasso_batch_ref.py; num_tables = 1 is not special-cased and its bytes
+ * differ from lh_lasso_prove's.  Every poly is zero-padded to nv = max(num_vars, max_t chunk_bits_t) variables, so a
+ * table's commitment block is the block of its own lh_lasso_prove proof whenever that proof's nv is the same.  Two tables
+ * of equal chunk_bits that are handed the SAME device pointer for a chunk column (AND and XOR over the same operands) share
+ * that column's counters, read_ts, final_cts and commitment jobs; the transcript still carries both blocks.
+ * Limits (LH_ERR_ARG with a message, checked on entry):
+ *   1 <= num_tables <= LH_LASSO_BATCH_MAX_TABLES; no NULL table, column or list; every table passes lh_lasso_prove's checks
+ *   sum of num_memories <= 8     the batch has 4 * that many product trees, and one GKR layer takes 2 B + 1 <= 72 tables
+ *   sum of num_terms <= LH_SC_MAX_TERMS   the Surge sum-check's terms
+ *   1 + 3 num_chunks + num_memories <= 63 per table   one identity mask per table
+ *   sum of 2 num_chunks + num_memories <= 24   the columns the batch opening merges at one point in one launch
+ *   not on a ctx inside a sharded prove, nor on one with a communicator of more than one rank attached
+ * LH_ERR_INVALID_PCS_PARAM when nv exceeds the SRS.  lh_lasso_last_timing and lh_lasso_last_route report a batch prove
+ * like a single one.  The verifier is host only. */
+#define LH_LASSO_BATCH_MAX_TABLES 8
+lh_status lh_lasso_prove_batch(lh_ctx*, const lh_srs*, const lh_lasso_table* const* tables, size_t num_tables, size_t num_vars,
+                               const uint32_t* const* const* d_dims, lh_transcript* t);
+/* (lh_lasso_verify_batch: with the verifiers below) */
+
 /* per-phase wall-clock of the last lh_lasso_prove on this ctx, milliseconds:
  * [witness, commit, surge, leaves+trees, gkr, evals, open_n, open_l, total] */
 #define LH_LASSO_NUM_PHASES 9
@@ -557,6 +580,12 @@ lh_status lh_mkzg_batch_verify(const lh_mkzg_vp*, size_t num_vars, const lh_g1* 
 lh_status lh_sumcheck_verify(int prover_kind, size_t num_vars, size_t degree, const lh_fr* sum,
                              lh_transcript* t, lh_fr* out_eval, lh_fr* out_x);
 lh_status lh_lasso_verify(const lh_mkzg_vp*, const lh_lasso_table*, size_t num_vars, lh_transcript* t);
+/* the verifier of lh_lasso_prove_batch (tests/lasso_batch_ref.py verify): the same argument refusals as the prover's that
+ * need no device, LH_ERR_INVALID_PCS_PARAM when max(num_vars, max chunk_bits) exceeds the param; a proof that does not
+ * verify is LH_ERR_INVALID_SNARK whichever piece finds it out (a sum-check round, the opening, bytes that are no point or no
+ * field element, a proof that ends early) - the message keeps that piece's words */
+lh_status lh_lasso_verify_batch(const lh_mkzg_vp* vp, const lh_lasso_table* const* tables, size_t num_tables, size_t num_vars,
+                                lh_transcript* t);
 typedef struct lh_hp_vparam { /* HyperPlonkVerifierParam (hyperplonk.rs:57-74) */
   size_t num_vars;
   size_t num_instance_polys;
