@@ -568,6 +568,101 @@ struct LassoClaims {  // points and claimed evaluations that remain to be opened
   std::vector<HFr> ev_n;  // dim_j | read_ts_j | E_i at r_N
   std::vector<HFr> ev_l;  // final_cts_j at r_M
 };
+// One table's shape and THE proof layout: the positions of its committed polys inside its commitment block,
+// a | dim_j | read_ts_j | E_i | final_cts_j.  Every prover, verifier and opening list takes its positions from here.
+struct LassoLayout {
+  size_t cc = 0, l = 0, alpha = 0;
+  bool linear_g = true;  // every term of g has one factor (range / AND / XOR / OR): a = sum_m coeff_m E_f(m) entry by entry
+  size_t g_degree = 0;   // the most factors in a term of g
+  LassoLayout() = default;
+  explicit LassoLayout(const lh_lasso_table& tb) : cc(tb.num_chunks), l(tb.chunk_bits), alpha(tb.num_memories) {
+    // (a table nobody has validated yet may be handed in - HyperPlonk counts its commitments before it checks its lookups:
+    // no read past the arrays; lasso_check_table refuses such a term count)
+    for (uint32_t m = 0; m < tb.num_terms && m < LH_LASSO_MAX_TERMS; m++) {
+      linear_g = linear_g && tb.g_num_factors[m] == 1;
+      g_degree = std::max<size_t>(g_degree, tb.g_num_factors[m]);
+    }
+  }
+  size_t a() const { return 0; }
+  size_t dim(size_t j) const { return 1 + j; }
+  size_t read_ts(size_t j) const { return 1 + cc + j; }
+  size_t E(size_t i) const { return 1 + 2 * cc + i; }
+  size_t final_cts(size_t j) const { return 1 + 2 * cc + alpha + j; }
+  size_t num_polys() const { return 1 + 3 * cc + alpha; }
+  size_t num_at_n() const { return 2 * cc + alpha; }  // the evaluations at r_N: dim_j | read_ts_j | E_i (LassoClaims::ev_n)
+};
+// Where a table's polys and points sit in a batch opening: the poly index of a, of every dim_j, and of the first read_ts, E
+// and final_cts (each group consecutive); the point indices of r, r_z, r_N, r_M.
+struct LassoOpening {
+  size_t a = 0;
+  std::vector<size_t> dim;
+  size_t read_ts = 0, E = 0, final_cts = 0;
+  size_t r = 0, r_z = 1, r_N = 2, r_M = 3;
+  // a commitment block of the layout's own at poly `poly_base`; points 0, 1, 2 and `r_M`
+  static LassoOpening block(const LassoLayout& lay, size_t poly_base = 0, size_t r_M = 3) {
+    LassoOpening o;
+    o.a = poly_base + lay.a(), o.read_ts = poly_base + lay.read_ts(0), o.E = poly_base + lay.E(0), o.final_cts = poly_base + lay.final_cts(0);
+    for (size_t j = 0; j < lay.cc; j++) o.dim.push_back(poly_base + lay.dim(j));
+    o.r_M = r_M;
+    return o;
+  }
+  // a lookup of a HyperPlonk circuit: a and dim_j are circuit polys, read_ts | E | final_cts start at `base`; points from p0
+  static LassoOpening in_circuit(const LassoLayout& lay, size_t output_poly, const size_t* chunk_polys, size_t base, size_t p0) {
+    LassoOpening o;
+    o.a = output_poly, o.dim.assign(chunk_polys, chunk_polys + lay.cc);
+    o.read_ts = base, o.E = base + lay.cc, o.final_cts = base + lay.cc + lay.alpha;
+    o.r = p0, o.r_z = p0 + 1, o.r_N = p0 + 2, o.r_M = p0 + 3;
+    return o;
+  }
+  static size_t circuit_polys(const LassoLayout& lay) { return lay.num_polys() - 1 - lay.cc; }  // read_ts | E | final_cts
+};
+// THE opening list of a Lasso argument, walked once: a at r; E_i at r_z; dim_j | read_ts_j | E_i at r_N; final_cts_j at r_M.
+// f(poly, point, value) per entry; value is null without claims (the pairs alone, before the challenges exist).
+template <class F>
+inline void lasso_opening_walk(const LassoLayout& lay, const LassoOpening& o, const LassoClaims* cl, F&& f) {
+  auto at = [&](const std::vector<HFr> LassoClaims::*group, size_t k) { return cl ? &(cl->*group)[k] : nullptr; };
+  f(o.a, o.r, cl ? &cl->v : nullptr);
+  for (size_t i = 0; i < lay.alpha; i++) f(o.E + i, o.r_z, at(&LassoClaims::e_rz, i));
+  for (size_t j = 0; j < lay.cc; j++) f(o.dim[j], o.r_N, at(&LassoClaims::ev_n, j));
+  for (size_t j = 0; j < lay.cc; j++) f(o.read_ts + j, o.r_N, at(&LassoClaims::ev_n, lay.cc + j));
+  for (size_t i = 0; i < lay.alpha; i++) f(o.E + i, o.r_N, at(&LassoClaims::ev_n, 2 * lay.cc + i));
+  for (size_t j = 0; j < lay.cc; j++) f(o.final_cts + j, o.r_M, at(&LassoClaims::ev_l, j));
+}
+// the list appended to `evs`, with the values of `cl` or (null) zeros that lasso_evaluation_values fills later
+inline void lasso_evaluation_list(const LassoLayout& lay, const LassoOpening& o, const LassoClaims* cl, std::vector<lh_evaluation>& evs) {
+  lasso_opening_walk(lay, o, cl, [&](size_t poly, size_t point, const HFr* val) {
+    lh_evaluation e;
+    memset(&e, 0, sizeof(e));
+    e.poly = (uint32_t)poly, e.point = (uint32_t)point;
+    if (val) memcpy(&e.value, val, 32);
+    evs.push_back(e);
+  });
+}
+// the values of a list made without claims, in place: the same walk
+inline void lasso_evaluation_values(const LassoLayout& lay, const LassoOpening& o, const LassoClaims& cl, lh_evaluation* evs) {
+  lasso_opening_walk(lay, o, &cl, [&](size_t, size_t, const HFr* val) { memcpy(&(evs++)->value, val, 32); });
+}
+// the points of the argument join those of a batch opening over nv variables, each zero-padded
+inline void lasso_append_points(std::vector<HFr>& points, const std::vector<const std::vector<HFr>*>& pts, size_t nv) {
+  for (const std::vector<HFr>* pt : pts) {
+    points.insert(points.end(), pt->begin(), pt->end());
+    points.insert(points.end(), nv - pt->size(), HFr::zero());
+  }
+}
+// term m's coefficient of g; whether it is an integer below 2^bits (bits <= 64; *low: that integer)
+inline HFr lasso_g_coeff(const lh_lasso_table& tb, size_t m) {
+  HFr co;
+  memcpy(&co, &tb.g_coeff[m], 32);
+  return co;
+}
+inline bool lasso_g_coeff_fits(const lh_lasso_table& tb, size_t m, unsigned bits, uint64_t* low = nullptr) {
+  uint64_t canon[4];
+  lasso_g_coeff(tb, m).to_canonical(canon);
+  if (low) *low = canon[0];
+  return !canon[1] && !canon[2] && !canon[3] && (bits >= 64 || !(canon[0] >> bits));
+}
+// bit length of v (0 for 0); a width that must be at least one bit says std::max(bit_length(v), 1u)
+inline uint32_t bit_length(uint64_t v) { return v ? 64u - (uint32_t)__builtin_clzll(v) : 0u; }
 constexpr uint32_t LH_SUBTABLE_KINDS = 6;  // IDENTITY .. LTU (include/lasso_hip.h)
 // Caller-registered subtables (subtable.cpp; include/lasso_hip.h lh_subtable_register): kinds from LH_SUBTABLE_CUSTOM_BASE up.
 // Immutable once registered; the shared_ptr of a lookup keeps the entries alive past an unregister on another thread.

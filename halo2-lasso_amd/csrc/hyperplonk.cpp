@@ -241,7 +241,7 @@ void hyperplonk_prove_phases(Ctx& c, const Pcs& pcs, const lh_hp_param& pp, cons
       // all Lasso commitments of a proof share ONE identity mask (a field element read as 63 bits, lasso.cpp)
       size_t total = 0;
       for (size_t k = 0; k < pp.num_lasso_lookups; k++)
-        total += 2 * (size_t)pp.lasso_lookups[k].table.num_chunks + pp.lasso_lookups[k].table.num_memories;
+        total += LassoOpening::circuit_polys(LassoLayout(pp.lasso_lookups[k].table));
       LH_REQUIRE(total <= LH_HP_LASSO_MAX_COMMITMENTS, LH_ERR_ARG,
                  "hyperplonk: the Lasso lookups of one circuit commit to more than 63 polys (sum of 2 * chunks + memories)");
     }
@@ -507,33 +507,16 @@ void hyperplonk_prove_phases(Ctx& c, const Pcs& pcs, const lh_hp_param& pp, cons
   // Lasso lookups: the argument itself, then its claims join the one batch opening
   for (LassoState& st : lasso) {
     const lh_lasso_table& tb = st.lk->table;
-    const size_t cc = tb.num_chunks, l = tb.chunk_bits, alpha = tb.num_memories;
-    tr.common_field_element(HFr::from_u64(nv));
-    tr.common_field_element(HFr::from_u64(l));
-    tr.common_field_element(HFr::from_u64(cc));
-    tr.common_field_element(HFr::from_u64(alpha));
+    const LassoLayout lay(tb);
+    for (size_t v : {nv, lay.l, lay.cc, lay.alpha}) tr.common_field_element(HFr::from_u64(v));
     LassoClaims cl = lasso_argue(c, tb, nv, st.cols, st.dims.data(), polys[st.lk->output_poly], st.E_fr.data(), tr);
     const size_t base = polys.size(), p0 = num_points;
     for (const Fr* p : st.rts_fr) polys.push_back(p);
     for (const Fr* p : st.E_fr) polys.push_back(p);
     for (const Fr* p : st.fcs_fr) polys.push_back(p);
-    for (const std::vector<HFr>* ptv : {&cl.r, &cl.r_z, &cl.r_N, &cl.r_M}) {
-      points.insert(points.end(), ptv->begin(), ptv->end());
-      points.insert(points.end(), nv - ptv->size(), HFr::zero());
-    }
+    lasso_append_points(points, {&cl.r, &cl.r_z, &cl.r_N, &cl.r_M}, nv);
     num_points += 4;
-    auto push = [&](size_t poly, size_t point, const HFr& val) {
-      lh_evaluation e;
-      e.poly = (uint32_t)poly, e.point = (uint32_t)point;
-      memcpy(&e.value, &val, 32);
-      evals.push_back(e);
-    };
-    push(st.lk->output_poly, p0, cl.v);
-    for (size_t i = 0; i < alpha; i++) push(base + cc + i, p0 + 1, cl.e_rz[i]);
-    for (size_t j = 0; j < cc; j++) push(st.lk->chunk_polys[j], p0 + 2, cl.ev_n[j]);
-    for (size_t j = 0; j < cc; j++) push(base + j, p0 + 2, cl.ev_n[cc + j]);
-    for (size_t i = 0; i < alpha; i++) push(base + cc + i, p0 + 2, cl.ev_n[2 * cc + i]);
-    for (size_t j = 0; j < cc; j++) push(base + cc + alpha + j, p0 + 3, cl.ev_l[j]);
+    lasso_evaluation_list(lay, LassoOpening::in_circuit(lay, st.lk->output_poly, st.lk->chunk_polys, base, p0), &cl, evals);
   }
   if (!lasso.empty()) pt.lap("lasso lookups");
   pcs.batch_open(nv, polys.data(), polys.size(), points.data(), num_points, evals.data(), evals.size(), tr, nullptr);

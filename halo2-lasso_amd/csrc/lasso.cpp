@@ -218,17 +218,14 @@ LassoColumns lasso_witness_columns(Ctx& c, const lh_lasso_table& tb, size_t n, c
     bool ok = true;
     uint64_t max_val = 0;
     for (uint32_t m = 0; m < tb.num_terms && ok; m++) {
-      HFr co;
-      memcpy(&co, &tb.g_coeff[m], 32);
-      uint64_t canon[4];
-      co.to_canonical(canon);
+      uint64_t co = 0;
       const size_t i = tb.g_factor[m][0];
       const size_t ebits = lasso_subtable_bits(tb.memory_subtable[i], l);
-      ok = tb.g_num_factors[m] == 1 && !canon[1] && !canon[2] && !canon[3] && canon[0] <= 0xffffffffull && ebits <= 32;
+      ok = tb.g_num_factors[m] == 1 && lasso_g_coeff_fits(tb, m, 32, &co) && ebits <= 32;
       if (!ok) break;
-      max_val += canon[0] * (((uint64_t)1 << ebits) - 1);
+      max_val += co * (((uint64_t)1 << ebits) - 1);
       ok = max_val <= 0xffffffffull;
-      gs.coeff[m] = (uint32_t)canon[0];
+      gs.coeff[m] = (uint32_t)co;
       gs.fac[m] = (uint8_t)i;
     }
     if (ok) {
@@ -250,12 +247,9 @@ LassoColumns lasso_witness_columns(Ctx& c, const lh_lasso_table& tb, size_t n, c
       unsigned __int128 bound = 0;
       bool fits = true;
       for (uint32_t m = 0; m < tb.num_terms && fits; m++) {
-        HFr co;
-        memcpy(&co, &tb.g_coeff[m], 32);
-        uint64_t canon[4];
-        co.to_canonical(canon);
-        fits = !canon[1] && !canon[2] && !canon[3] && canon[0] <= 0xffffffffull;
-        unsigned __int128 term = canon[0];  // (< 2^32, and every step below keeps it <= 2^32 * (2^32 - 1) < 2^128)
+        uint64_t co = 0;
+        fits = lasso_g_coeff_fits(tb, m, 32, &co);
+        unsigned __int128 term = co;  // (< 2^32, and every step below keeps it <= 2^32 * (2^32 - 1) < 2^128)
         for (int k = 0; k < tb.g_num_factors[m] && fits; k++) {
           const uint32_t eb = lasso_subtable_bits(tb.memory_subtable[tb.g_factor[m][k]], l);
           term *= ((uint64_t)1 << eb) - 1;  // (eb <= l < 31)
@@ -264,14 +258,14 @@ LassoColumns lasso_witness_columns(Ctx& c, const lh_lasso_table& tb, size_t n, c
         }
         bound += term;
         fits = fits && bound <= 0xffffffffull;
-        gp.coeff[m] = (uint32_t)canon[0];
+        gp.coeff[m] = (uint32_t)co;
         gp.nfac[m] = tb.g_num_factors[m];
       }
       if (fits) {
         for (size_t i = 0; i < alpha; i++) gp.e[i] = w.E[i];
         *a_small_out = c.arena.alloc_n<uint32_t>(N);
         k_lasso_output_small_prod(c, gp, N, *a_small_out);
-        w.a_bits = bound ? 64u - (uint32_t)__builtin_clzll((uint64_t)bound) : 1u;
+        w.a_bits = std::max(bit_length((uint64_t)bound), 1u);
         if (a_out) *a_out = nullptr;
         return w;
       }
@@ -290,28 +284,101 @@ LassoColumns lasso_witness_columns(Ctx& c, const lh_lasso_table& tb, size_t n, c
   return w;
 }
 
+// ------------------------------------------------------------------ steps shared by lasso_argue, lasso_prove and lasso_prove_batch
+// u32 columns of `len` = 2^vars entries evaluated at `point`, against its full eq table (scratch of this call): final_cts at
+// r_M, and any column of fewer than two variables
+static void lasso_evaluate_u32_full(Ctx& c, const uint32_t* const* cols, size_t count, const HFr* point, size_t vars, HFr* out) {
+  ArenaScope scope(c.arena);
+  const size_t len = (size_t)1 << vars;
+  Fr* eq = c.arena.alloc_n<Fr>(len);
+  k_eq_xy(c, (const Fr*)point, vars, eq);
+  k_inner_products_small(c, cols, count, eq, len, (Fr*)out);
+}
+// u32 columns of n variables (this rank's shards inside a sharded proof: partial sums added over the ranks) evaluated at
+// `point`: against the eq table of point[1..] (half the entries), which the sum-checks and the batch opening at that point
+// use as well.  The eq table that stays cached for the opening is obtained OUTSIDE any inner ArenaScope.
+// share_sums: from the columns' quad sums, which stay in the proof's table for the opening (quad_sums_evaluate).
+static void lasso_evaluate_u32(Ctx& c, const uint32_t* const* cols, size_t count, const HFr* point, size_t n, bool shn, HFr* out,
+                               bool share_sums = false) {
+  if (n < 2) return lasso_evaluate_u32_full(c, cols, count, point, n, out);
+  const Fr* eq_half = eq_half_get(c, point, n, shn);
+  const size_t N = (size_t)1 << (n - Shard(c).rho);
+  if (share_sums) quad_sums_evaluate(c, cols, count, point, n, eq_half, out);
+  else k_inner_products_small_half(c, cols, count, eq_half, N / 2, dev(point[0]), (Fr*)out);
+  if (shn) comm_sum_fr(c, out, count);
+}
+// the expression of the linear Surge case: one term, table 0, coefficient one
+static lh_sop lasso_one_term() {
+  lh_sop e;
+  memset(&e, 0, sizeof(e));
+  const HFr one = HFr::one();
+  e.num_terms = 1, e.num_factors[0] = 1;
+  memcpy(&e.coeff[0], &one, 32);
+  return e;
+}
+// appends g's terms to `e` over tables whose memory i is table mem_base + i; coefficients times *scale where given
+static void lasso_append_g(lh_sop& e, const lh_lasso_table& tb, size_t mem_base = 0, const HFr* scale = nullptr) {
+  for (uint32_t m = 0; m < tb.num_terms; m++) {
+    const uint32_t t = e.num_terms++;
+    const HFr co = scale ? lasso_g_coeff(tb, m) * *scale : lasso_g_coeff(tb, m);
+    memcpy(&e.coeff[t], &co, 32);
+    e.num_factors[t] = tb.g_num_factors[m];
+    for (int k = 0; k < tb.g_num_factors[m]; k++) e.factor[t][k] = (uint8_t)(mem_base + tb.g_factor[m][k]);
+  }
+}
+// The four product trees per memory of ONE grand-product GKR over A memories: RS, WS of memory b (n variables) at 2 b and
+// 2 b + 1, behind them Init, Final (l variables) at 2 A + 2 b and 2 A + 2 b + 1.  write leaf = read leaf + 1: where the
+// n-variable trees are alone at their leaf layer that layer runs over the read-set tables only (prove_grand_product:
+// plus_one) and the write-set leaves are never stored (ws_implicit).  The caller fills the leaves.
+struct LassoTrees {
+  size_t A;
+  std::vector<const Fr*> leaves, level_up;
+  std::vector<size_t> depths;
+  std::vector<uint8_t> plus_one;
+  LassoTrees(size_t A_, size_t n) : A(A_), leaves(4 * A_), level_up(4 * A_, nullptr), depths(4 * A_, n), plus_one(4 * A_, 0) {}
+  struct Memory {
+    Fr *rs, *ws, *rs_up, *ws_up, *init, *fin;
+  };
+  // memory b's leaf tables (N and M = 2^l entries; fused_up: the level above the n-variable leaves comes with them)
+  Memory add(Ctx& c, size_t b, size_t N, size_t l, bool fused_up, bool ws_implicit) {
+    Memory m{};
+    m.rs = c.arena.alloc_n<Fr>(N);
+    m.ws = ws_implicit ? nullptr : c.arena.alloc_n<Fr>(N);
+    if (fused_up) {
+      m.rs_up = c.arena.alloc_n<Fr>(N / 2), m.ws_up = c.arena.alloc_n<Fr>(N / 2);
+      level_up[2 * b] = m.rs_up, level_up[2 * b + 1] = m.ws_up;
+    }
+    m.init = c.arena.alloc_n<Fr>((size_t)1 << l), m.fin = c.arena.alloc_n<Fr>((size_t)1 << l);
+    leaves[2 * b] = m.rs, leaves[2 * b + 1] = m.ws;
+    plus_one[2 * b + 1] = 1;
+    leaves[2 * A + 2 * b] = m.init, leaves[2 * A + 2 * b + 1] = m.fin;
+    depths[2 * A + 2 * b] = depths[2 * A + 2 * b + 1] = l;
+    return m;
+  }
+  GrandProductResult prove(Ctx& c, Transcript& tr, const std::function<void()>& trees_built = nullptr) {
+    return prove_grand_product(c, 4 * A, leaves.data(), depths.data(), tr, level_up.data(), plus_one.data(), trees_built);
+  }
+};
+
 // Steps 2-7 of the argument (oracle/pyref/lasso.py argue): Surge sum-check, memory-checking grand products,
 // evaluations.  The Fr tables hold at least 2^n (fcs_fr: 2^l) entries; `lap` (optional) receives phase boundaries,
 // `trees_built` (optional) is prove_grand_product's.
 LassoClaims lasso_argue(Ctx& c, const lh_lasso_table& tb, size_t n, const LassoColumns& w, const uint32_t* const* d_dims,
                         const Fr* a, const Fr* const* E_fr, Transcript& tr, const std::function<void(int)>& lap,
                         const uint32_t* a_small, const std::function<void()>& trees_built) {
-  const size_t cc = tb.num_chunks, l = tb.chunk_bits, alpha = tb.num_memories;
+  const LassoLayout lay(tb);
+  const size_t cc = lay.cc, l = lay.l, alpha = lay.alpha;
+  const bool linear_g = lay.linear_g;
   // inside a sharded proof (dev.hpp Shard) every n-variable column is this rank's shard (N entries); sums over a column -
   // evaluations, round messages - are partial sums added over the ranks; the 2^l-entry subtable side is replicated
   const Shard sh(c);
   const bool shn = sh.on;
   if (shn) LH_REQUIRE(sh.sharded(n) && l <= sh.j + sh.rho, LH_ERR_ARG, "lasso: shard geometry does not fit the table");
   const size_t N = (size_t)1 << (n - sh.rho), M = (size_t)1 << l;
-  auto sum_ranks = [&](HFr* v, size_t count) {
-    if (shn) comm_sum_fr(c, v, count);
-  };
   LassoClaims cl;
   // ---- 2-4: Surge primary sum-check
   cl.r = tr.squeeze_challenges(n);
   c.host_stamp("argue:squeezed");
-  bool linear_g = true;
-  for (uint32_t m = 0; m < tb.num_terms; m++) linear_g = linear_g && tb.g_num_factors[m] == 1;
   Fr a_sums[4];  // (k_inner_products_small_quads: the claim's two halves - and rounds 0 and 1 of the Surge sum-check over a)
   bool have_a_sums = false;
   // Where the batch opening will take its rounds 0 and 1 from the columns' quad sums (sc_open_column_rounds - a guess: the
@@ -319,31 +386,23 @@ LassoClaims lasso_argue(Ctx& c, const lh_lasso_table& tb, size_t n, const LassoC
   // from those very sums, which stay in the proof's table (quad_sums_evaluate); Surge's round 0 leaves the entry of a at r.
   // (n >= l: the opening's points are these, not zero-padded ones.)  LH_OPEN_SHARE_SUMS=0: as before, for A/B.
   const bool share_sums = !shn && n >= 3 && n >= l && knob(Knob::OPEN_SHARE_SUMS) != 0 && sc_open_column_rounds(c, n, shn);
-  if (a_small && n >= 2) {
+  if (a_small && !a && linear_g && !shn && n >= 3) {
     // against the eq table of r[1..] (half the entries), which the Surge sum-check and the batch opening at r use as well
     const Fr* eq_half = eq_half_get(c, cl.r.data(), n, shn);
-    if (!a && linear_g && !shn && n >= 3) {
-      k_inner_products_small_quads(c, a_small, eq_half, N / 4, a_sums);
-      const HFr r0 = cl.r[0];
-      cl.v = (HFr::one() - r0) * hst(a_sums[0]) + r0 * hst(a_sums[1]);
-      have_a_sums = true;
-      // even = (1 - y1) S_0 + y1 S_2 and odd = (1 - y1) S_1 + y1 S_3 with y1 = r[1]: S_0 and S_1 from the kernel's four sums
-      const HFr y1 = cl.r[1], n1 = HFr::one() - y1;
-      if (share_sums && !n1.is_zero()) {
-        const HFr inv = n1.inv();
-        const HFr s4[4] = {(hst(a_sums[0]) - y1 * hst(a_sums[2])) * inv, (hst(a_sums[1]) - y1 * hst(a_sums[3])) * inv,
-                           hst(a_sums[2]), hst(a_sums[3])};
-        quad_sums_put(c, a_small, N, cl.r.data(), n, s4);
-      }
-    } else {
-      k_inner_products_small_half(c, &a_small, 1, eq_half, N / 2, dev(cl.r[0]), (Fr*)&cl.v);
+    k_inner_products_small_quads(c, a_small, eq_half, N / 4, a_sums);
+    const HFr r0 = cl.r[0];
+    cl.v = (HFr::one() - r0) * hst(a_sums[0]) + r0 * hst(a_sums[1]);
+    have_a_sums = true;
+    // even = (1 - y1) S_0 + y1 S_2 and odd = (1 - y1) S_1 + y1 S_3 with y1 = r[1]: S_0 and S_1 from the kernel's four sums
+    const HFr y1 = cl.r[1], n1 = HFr::one() - y1;
+    if (share_sums && !n1.is_zero()) {
+      const HFr inv = n1.inv();
+      const HFr s4[4] = {(hst(a_sums[0]) - y1 * hst(a_sums[2])) * inv, (hst(a_sums[1]) - y1 * hst(a_sums[3])) * inv,
+                         hst(a_sums[2]), hst(a_sums[3])};
+      quad_sums_put(c, a_small, N, cl.r.data(), n, s4);
     }
-    sum_ranks(&cl.v, 1);
   } else if (a_small) {
-    ArenaScope scope(c.arena);
-    Fr* eq = c.arena.alloc_n<Fr>(N);
-    k_eq_xy(c, (const Fr*)cl.r.data(), n, eq);
-    k_inner_products_small(c, &a_small, 1, eq, N, (Fr*)&cl.v);
+    lasso_evaluate_u32(c, &a_small, 1, cl.r.data(), n, shn, &cl.v);
   } else {
     cl.v = evaluate_polys(c, &a, 1, n, cl.r.data(), shn)[0];
   }
@@ -369,39 +428,15 @@ LassoClaims lasso_argue(Ctx& c, const lh_lasso_table& tb, size_t n, const LassoC
         if (have_a_sums) u32.odd = a_sums[1], u32.s2 = a_sums[2], u32.s3 = a_sums[3];
         so.u32 = &u32;
       }
-      lh_sop one_term;
-      memset(&one_term, 0, sizeof(one_term));
-      one_term.global_eq = 0;
-      one_term.num_terms = 1;
-      const HFr one = HFr::one();
-      memcpy(&one_term.coeff[0], &one, 32);
-      one_term.num_factors[0] = 1;
-      one_term.factor[0][0] = 0;
-      sc = sum_check_prove(c, LH_SC_EVALUATIONS, n, one_term, &a_tab, 1, cl.r.data(), 1, cl.v, tr, so);
+      sc = sum_check_prove(c, LH_SC_EVALUATIONS, n, lasso_one_term(), &a_tab, 1, cl.r.data(), 1, cl.v, tr, so);
     }
     std::vector<const uint32_t*> cols(w.E.begin(), w.E.end());
-    sc.evals.assign(alpha, HFr::zero());
-    if (n >= 2) {  // (the table of r_z[1..] stays for the batch opening at r_z)
-      const Fr* eq_half = eq_half_get(c, sc.challenges.data(), n, shn);
-      if (share_sums) quad_sums_evaluate(c, cols.data(), alpha, sc.challenges.data(), n, eq_half, sc.evals.data());
-      else k_inner_products_small_half(c, cols.data(), alpha, eq_half, N / 2, dev(sc.challenges[0]), (Fr*)sc.evals.data());
-      sum_ranks(sc.evals.data(), alpha);
-    } else {
-      ArenaScope scope(c.arena);
-      Fr* eq = c.arena.alloc_n<Fr>(N);
-      k_eq_xy(c, (const Fr*)sc.challenges.data(), n, eq);
-      k_inner_products_small(c, cols.data(), alpha, eq, N, (Fr*)sc.evals.data());
-    }
+    sc.evals.assign(alpha, HFr::zero());  // (the table of r_z[1..] stays for the batch opening at r_z)
+    lasso_evaluate_u32(c, cols.data(), alpha, sc.challenges.data(), n, shn, sc.evals.data(), share_sums);
   } else {
     lh_sop surge;
     memset(&surge, 0, sizeof(surge));
-    surge.global_eq = 0;
-    surge.num_terms = tb.num_terms;
-    for (uint32_t m = 0; m < tb.num_terms; m++) {
-      surge.coeff[m] = tb.g_coeff[m];
-      surge.num_factors[m] = tb.g_num_factors[m];
-      for (int k = 0; k < LH_SC_MAX_FACTORS; k++) surge.factor[m][k] = tb.g_factor[m][k];
-    }
+    lasso_append_g(surge, tb);
     ScOptions so;
     so.sum_is_exact = true, so.sharded = shn;
     sc = sum_check_prove(c, LH_SC_EVALUATIONS, n, surge, E_fr, alpha, cl.r.data(), 1, cl.v, tr, so);
@@ -417,88 +452,80 @@ LassoClaims lasso_argue(Ctx& c, const lh_lasso_table& tb, size_t n, const LassoC
   HFr gamma2 = gamma * gamma;
   {
     ArenaScope scope(c.arena);
-    std::vector<const Fr*> leaves(4 * alpha), level_up(4 * alpha, nullptr);
-    std::vector<size_t> depths(4 * alpha);
-    std::vector<uint8_t> plus_one(4 * alpha, 0);
-    // write leaf = read leaf + 1: when the n-variable trees are alone at their leaf layer (n > l) that layer runs over the
-    // read-set tables only (prove_grand_product: plus_one) and the write-set leaves are never stored
+    LassoTrees trees(alpha, n);
     // (sharded: the level above the leaves must itself be held in shards, else it is exchanged by the tree builder)
     const bool fused_up = n >= 12 && (!shn || sh.sharded(n - 1)), ws_implicit = fused_up && n > l;
     for (size_t i = 0; i < alpha; i++) {
-      size_t j = tb.memory_chunk[i];
-      Fr* rs = c.arena.alloc_n<Fr>(N);
-      Fr* ws = ws_implicit ? nullptr : c.arena.alloc_n<Fr>(N);
-      Fr* in = c.arena.alloc_n<Fr>(M);
-      Fr* fi = c.arena.alloc_n<Fr>(M);
-      if (fused_up) {  // the level above the leaves comes with them (no tree_up pass over the largest level)
-        Fr* rs_up = c.arena.alloc_n<Fr>(N / 2);
-        Fr* ws_up = c.arena.alloc_n<Fr>(N / 2);
-        k_lasso_rw_leaves_up(c, d_dims[j], w.E[i], w.rts[j], N, dev(gamma), dev(gamma2), dev(tau), rs, ws, rs_up, ws_up);
-        level_up[2 * i] = rs_up, level_up[2 * i + 1] = ws_up;
-      } else {
-        k_lasso_rw_leaves(c, d_dims[j], w.E[i], w.rts[j], N, dev(gamma), dev(gamma2), dev(tau), rs, ws);
-      }
-      k_lasso_if_leaves(c, (int)tb.memory_subtable[i], (uint32_t)l, w.fcs[j], M, dev(gamma), dev(gamma2), dev(tau), in, fi,
+      const size_t j = tb.memory_chunk[i];
+      const LassoTrees::Memory m = trees.add(c, i, N, l, fused_up, ws_implicit);
+      if (fused_up)  // the level above the leaves comes with them (no tree_up pass over the largest level)
+        k_lasso_rw_leaves_up(c, d_dims[j], w.E[i], w.rts[j], N, dev(gamma), dev(gamma2), dev(tau), m.rs, m.ws, m.rs_up, m.ws_up);
+      else
+        k_lasso_rw_leaves(c, d_dims[j], w.E[i], w.rts[j], N, dev(gamma), dev(gamma2), dev(tau), m.rs, m.ws);
+      k_lasso_if_leaves(c, (int)tb.memory_subtable[i], (uint32_t)l, w.fcs[j], M, dev(gamma), dev(gamma2), dev(tau), m.init, m.fin,
                         w.T.empty() ? nullptr : w.T[i]);
-      leaves[2 * i] = rs, leaves[2 * i + 1] = ws;
-      plus_one[2 * i + 1] = 1;
-      leaves[2 * alpha + 2 * i] = in, leaves[2 * alpha + 2 * i + 1] = fi;
-      depths[2 * i] = depths[2 * i + 1] = n;
-      depths[2 * alpha + 2 * i] = depths[2 * alpha + 2 * i + 1] = l;
     }
     if (lap) lap(3);
-    GrandProductResult gp = prove_grand_product(c, 4 * alpha, leaves.data(), depths.data(), tr, level_up.data(), plus_one.data(), trees_built);
+    GrandProductResult gp = trees.prove(c, tr, trees_built);
     cl.r_N = gp.points[0];
     cl.r_M = gp.points[2 * alpha];
   }
   if (lap) lap(4);
 
   // ---- 7: evaluations at r_N / r_M: dim | read_ts | E, then final_cts - straight from the u32 columns (no
-  // field-element views: 4 bytes read and 8 multiply-adds per entry); at r_N against the eq table of r_N[1..], which the
-  // batch opening at r_N uses as well
-  const Fr* eq_half_n = n >= 2 ? eq_half_get(c, cl.r_N.data(), n, shn) : nullptr;
-  {
-    ArenaScope scope(c.arena);
-    std::vector<const uint32_t*> at_n;
-    for (size_t j = 0; j < cc; j++) at_n.push_back(d_dims[j]);
-    for (size_t j = 0; j < cc; j++) at_n.push_back(w.rts[j]);
-    for (size_t i = 0; i < alpha; i++) at_n.push_back(w.E[i]);
-    cl.ev_n.resize(at_n.size());
-    Fr* eq = c.arena.alloc_n<Fr>(eq_half_n ? M : std::max(N, M));
-    if (eq_half_n && share_sums) {
-      quad_sums_evaluate(c, at_n.data(), at_n.size(), cl.r_N.data(), n, eq_half_n, cl.ev_n.data());
-    } else if (eq_half_n) {
-      k_inner_products_small_half(c, at_n.data(), at_n.size(), eq_half_n, N / 2, dev(cl.r_N[0]), (Fr*)cl.ev_n.data());
-      sum_ranks(cl.ev_n.data(), cl.ev_n.size());
-    } else {
-      k_eq_xy(c, (const Fr*)cl.r_N.data(), n, eq);
-      k_inner_products_small(c, at_n.data(), at_n.size(), eq, N, (Fr*)cl.ev_n.data());
-    }
-    std::vector<const uint32_t*> at_l(w.fcs.begin(), w.fcs.end());
-    cl.ev_l.resize(cc);
-    k_eq_xy(c, (const Fr*)cl.r_M.data(), l, eq);
-    k_inner_products_small(c, at_l.data(), cc, eq, M, (Fr*)cl.ev_l.data());
-  }
+  // field-element views: 4 bytes read and 8 multiply-adds per entry)
+  std::vector<const uint32_t*> at_n(d_dims, d_dims + cc);
+  at_n.insert(at_n.end(), w.rts.begin(), w.rts.end());
+  at_n.insert(at_n.end(), w.E.begin(), w.E.end());
+  cl.ev_n.resize(at_n.size());
+  lasso_evaluate_u32(c, at_n.data(), at_n.size(), cl.r_N.data(), n, shn, cl.ev_n.data(), share_sums);
+  std::vector<const uint32_t*> at_l(w.fcs.begin(), w.fcs.end());
+  cl.ev_l.resize(cc);
+  lasso_evaluate_u32_full(c, at_l.data(), cc, cl.r_M.data(), l, cl.ev_l.data());
   tr.write_field_elements(cl.ev_n);
   tr.write_field_elements(cl.ev_l);
   if (lap) lap(5);
   return cl;
 }
 
-// the phase boundaries of a prove (lasso_prove, lasso_prove_batch): events on the prover's stream, lh_lasso_last_timing
+// The scope of a prove (lasso_prove, lasso_prove_batch).  Its phase boundaries are EVENTS on the prover's stream (a
+// hipStreamSynchronize at each of them drained the queue seven times per proof for the sake of a number nobody reads in
+// production): lh_lasso_last_timing turns them into phase times when asked (Ctx::phase_times_resolve); lasso_ms[8], the
+// total, is the host's wall clock.  Everything the prove allocates, caches and starts ends with it: arena memory, the shared
+// eq tables and quad sums, the route counters of an earlier prove, a precommit still running.  The cancel on entry was the
+// batch prover's, the one on exit the single prover's guard (a prove that fails on the way drops what it started); with
+// no precommit pending either is a no-op, so each path gained one without effect.
 struct LassoPhases {
   Ctx& c;
-  explicit LassoPhases(Ctx& c_) : c(c_) {
-    for (int k = 0; k < 8; k++)
-      if (!c.phase_ev[k]) LH_HIP(hipEventCreate(&c.phase_ev[k]));
-    c.phase_ev_pending = false;
-    LH_HIP(hipEventRecord(c.phase_ev[0], c.stream));
-    c.comm_phase = 0;
+  const double t0 = now_ms();
+  struct Start {  // (ahead of the scopes below)
+    explicit Start(Ctx& c) {
+      for (int k = 0; k < 8; k++)
+        if (!c.phase_ev[k]) LH_HIP(hipEventCreate(&c.phase_ev[k]));
+      c.phase_ev_pending = false;
+      LH_HIP(hipEventRecord(c.phase_ev[0], c.stream));
+      c.comm_phase = 0;
+      c.quad_sums.clear();  // (nothing of an earlier prove: the arena hands out the same pointers again)
+    }
+  } start;
+  ArenaScope scope;
+  EqHalfScope eq_scope;  // (the shared eq tables are arena memory of this scope)
+  explicit LassoPhases(Ctx& c_) : c(c_), start(c_), scope(c_.arena), eq_scope(c_) {
+    open_precommit_cancel(c);
+    c.route = RouteStats();
   }
-  ~LassoPhases() { c.comm_phase = 7; }  // (collectives issued after the prove - or after it failed - count as outside)
+  ~LassoPhases() {
+    open_precommit_cancel(c);
+    c.comm_phase = 7;  // (collectives issued after the prove - or after it failed - count as outside)
+  }
   void lap(int idx) {
     LH_HIP(hipEventRecord(c.phase_ev[idx + 1], c.stream));
     c.comm_phase = idx + 1;
+  }
+  void done() {  // the prove went through: its times may be read
+    c.lasso_ms[7] = 0;
+    c.lasso_ms[8] = now_ms() - t0;
+    c.phase_ev_pending = true;
   }
 };
 
@@ -511,6 +538,20 @@ struct LassoCommitPlan {
   std::vector<size_t> second_of;  // chunks whose read_ts commitment comes back through `second`
   std::vector<size_t> dim_job;    // per chunk: the job of the batch that commits dim_j (this table's, or the one it shares)
 };
+// one table of a prove: lasso_prove works on one of these, lasso_prove_batch on K
+struct LassoTable {
+  const lh_lasso_table* tb = nullptr;
+  LassoLayout lay;
+  const uint32_t* const* dims = nullptr;  // the chunk columns (device)
+  LassoColumns w;
+  Fr* a = nullptr;  // the output column: as field elements, or (then a stays null) in its 32-bit form
+  uint32_t* a_small = nullptr;
+  std::vector<uint32_t> count_ors;  // OR of every final_cts column (bounds its read_ts column) where computed, else 0
+  LassoCommitPlan plan;
+  SmallLinear a_linear;  // a = sum_m coeff_m E_{f(m)} entry by entry (linear g): what lasso_open_columns points small[a] at
+  LassoClaims cl;
+  LassoTable(const lh_lasso_table& tb_, const uint32_t* const* dims_) : tb(&tb_), lay(tb_), dims(dims_), count_ors(lay.cc, 0) {}
+};
 // Appends the table's jobs to `jobs`: the output column only when g is not linear (a linear g's follows from the E
 // commitments), dim (with the sorted columns of the access counters where kept), read_ts (two columns packed into one pass
 // where their widths allow), E of the non-identity subtables (derived from dim's buckets where the route applies) and
@@ -518,28 +559,31 @@ struct LassoCommitPlan {
 // shared_dim_job (optional, per chunk): >= 0 says that this chunk column, its counters and their commitments belong to an
 // earlier table of the batch whose dim job that is - no dim / read_ts / final_cts job is made for it (the caller copies
 // those three commitments), and a derived E names that job as its parent.
-static void lasso_commit_jobs(Ctx& c, const Pcs& pcs, const lh_lasso_table& tb, size_t n, size_t nv, const uint32_t* const* d_dims,
-                              const LassoColumns& w, const Fr* a, const uint32_t* a_small, std::vector<uint32_t>& count_ors,
-                              bool ors_known, const int* shared_dim_job, std::vector<MsmJob>& jobs, LassoCommitPlan& plan) {
-  const size_t cc = tb.num_chunks, l = tb.chunk_bits, alpha = tb.num_memories;
+static void lasso_commit_jobs(Ctx& c, const Pcs& pcs, LassoTable& x, size_t n, size_t nv, bool ors_known, const int* shared_dim_job,
+                              std::vector<MsmJob>& jobs) {
+  const lh_lasso_table& tb = *x.tb;
+  const LassoLayout& lay = x.lay;
+  const LassoColumns& w = x.w;
+  LassoCommitPlan& plan = x.plan;
+  std::vector<uint32_t>& count_ors = x.count_ors;
+  const uint32_t* const* d_dims = x.dims;
+  const size_t cc = lay.cc, l = lay.l, alpha = lay.alpha;
   const Shard sh(c);
   const bool shn = sh.on;
   const size_t N = (size_t)1 << (n - sh.rho), M = (size_t)1 << l;
   const std::vector<uint32_t*>&rts = w.rts, &fcs = w.fcs, &E = w.E;
   auto shared = [&](size_t j) { return shared_dim_job != nullptr && shared_dim_job[j] >= 0; };
   const G1Affine* bases = shn ? pcs.shard_bases(nv) : pcs.commit_bases(nv);
-  bool linear_g = true;
-  for (uint32_t m = 0; m < tb.num_terms; m++) linear_g = linear_g && tb.g_num_factors[m] == 1;
   auto add_job = [&](size_t pos, const void* col, bool u32, size_t len) {
     plan.job.push_back(jobs.size());
     jobs.push_back(MsmJob{col, u32, bases, len});
     plan.slot.push_back(pos);
   };
-  if (!linear_g && a_small) {  // (product g with a 32-bit output column: a u32 job, every entry below 2^a_bits)
-    add_job(0, a_small, true, N);
+  if (!lay.linear_g && x.a_small) {  // (product g with a 32-bit output column: a u32 job, every entry below 2^a_bits)
+    add_job(lay.a(), x.a_small, true, N);
     jobs.back().known_bits = w.a_bits;
-  } else if (!linear_g) {
-    add_job(0, a, false, N);
+  } else if (!lay.linear_g) {
+    add_job(lay.a(), x.a, false, N);
   }
   std::vector<size_t>& dim_job = plan.dim_job;
   dim_job.assign(cc, 0);
@@ -549,7 +593,7 @@ static void lasso_commit_jobs(Ctx& c, const Pcs& pcs, const lh_lasso_table& tb, 
       dim_job[j] = (size_t)shared_dim_job[j];
       continue;
     }
-    dim_job[j] = jobs.size(), add_job(1 + j, d_dims[j], true, N);
+    dim_job[j] = jobs.size(), add_job(lay.dim(j), d_dims[j], true, N);
     jobs.back().known_bits = (uint32_t)l;  // (the access counters rejected any index >= 2^l)
     if (!w.dim_sorted.empty()) {
       jobs.back().sorted_scalars = w.dim_sorted[own], jobs.back().sorted_index = w.dim_index[own];
@@ -566,16 +610,15 @@ static void lasso_commit_jobs(Ctx& c, const Pcs& pcs, const lh_lasso_table& tb, 
     std::vector<const uint32_t*> cols(fcs.begin(), fcs.end());
     const bool pack_on = c.opt.lasso_pack_ts != 0;  // 0: one MSM pass per read_ts column (A/B measurements)
     if (!ors_known && pack_on && cc >= 2 && N >= ((size_t)1 << 12)) k_or_u32(c, cols.data(), cc, M, ors.data());
-    auto bits_of = [](uint32_t v) { return v ? 32u - (uint32_t)__builtin_clz(v) : 0u; };
     for (size_t j = 0; j < cc; j++) {
       if (shared(j)) continue;
       const bool next = j + 1 < cc && !shared(j + 1);
-      const uint32_t b0 = std::max(bits_of(ors[j]), 4u), b1 = next ? bits_of(ors[j + 1]) : 0;
+      const uint32_t b0 = std::max(bit_length(ors[j]), 4u), b1 = next ? bit_length(ors[j + 1]) : 0;
       if (ors[j] && next && ors[j + 1] && b0 + b1 <= MSM_PACK_MAX_BITS &&
           N >= ((size_t)MSM_PACK_MIN_POINTS_PER_BUCKET << (b0 + b1))) {  // (worth it while the points outnumber the buckets)
         uint32_t* packed = c.arena.alloc_n<uint32_t>(N);
         k_pack_u32(c, rts[j], rts[j + 1], b0, N, packed);
-        add_job(1 + cc + j, packed, true, N);
+        add_job(lay.read_ts(j), packed, true, N);
         jobs.back().known_bits = b0 + b1;
         jobs.back().pack_shift = b0;
         jobs.back().out_second = (G1Affine*)&second[j + 1];
@@ -583,8 +626,8 @@ static void lasso_commit_jobs(Ctx& c, const Pcs& pcs, const lh_lasso_table& tb, 
         c.route.v[RouteStats::PACKED_TS]++;
         j++;
       } else {
-        add_job(1 + cc + j, rts[j], true, N);
-        jobs.back().known_bits = bits_of(ors[j]);  // (0 when the counts were not looked at: measured then)
+        add_job(lay.read_ts(j), rts[j], true, N);
+        jobs.back().known_bits = bit_length(ors[j]);  // (0 when the counts were not looked at: measured then)
       }
     }
   }
@@ -594,7 +637,7 @@ static void lasso_commit_jobs(Ctx& c, const Pcs& pcs, const lh_lasso_table& tb, 
   SubtableOrders& orders = *w.tables;
   for (size_t i = 0; i < alpha; i++)
     if (tb.memory_subtable[i] != LH_SUBTABLE_IDENTITY) {
-      add_job(1 + 2 * cc + i, E[i], true, N);
+      add_job(lay.E(i), E[i], true, N);
       // (the derived route has no bucket for dim = 0 - msm.hip: T[0] must be 0 - and EQ has T[0] = 1: an ordinary column)
       // A registered subtable asks for the route exactly when its T[0] is 0 (its l is at most 20 by registration).
       bool derive = l <= 20 && tb.memory_subtable[i] != LH_SUBTABLE_EQ;
@@ -618,44 +661,34 @@ static void lasso_commit_jobs(Ctx& c, const Pcs& pcs, const lh_lasso_table& tb, 
   const ReplicatedRange fc_range(sh, M);
   for (size_t j = 0; j < cc; j++) {
     if (shared(j)) continue;
-    add_job(1 + 2 * cc + alpha + j, fcs[j] + fc_range.first, true, fc_range.count);
+    add_job(lay.final_cts(j), fcs[j] + fc_range.first, true, fc_range.count);
     jobs.back().bases = pcs.commit_bases(nv) + fc_range.first;
-    jobs.back().known_bits = count_ors[j] ? 32u - (uint32_t)__builtin_clz(count_ors[j]) : 0u;
+    jobs.back().known_bits = bit_length(count_ors[j]);
   }
 }
 // the batch's results -> the table's commitments, as far as its own jobs made them (what lasso_commit_derive adds, and
 // what a table of a batch shares with an earlier one, is still missing)
-static std::vector<HG1> lasso_commit_collect(const lh_lasso_table& tb, const LassoCommitPlan& plan, const std::vector<HG1>& part) {
-  const size_t cc = tb.num_chunks, alpha = tb.num_memories;
-  std::vector<HG1> comms(1 + 3 * cc + alpha);
-  for (size_t k = 0; k < plan.job.size(); k++) comms[plan.slot[k]] = part[plan.job[k]];
-  for (size_t j : plan.second_of) comms[1 + cc + j] = plan.second[j];
+static std::vector<HG1> lasso_commit_collect(const LassoTable& x, const std::vector<HG1>& part) {
+  std::vector<HG1> comms(x.lay.num_polys());
+  for (size_t k = 0; k < x.plan.job.size(); k++) comms[x.plan.slot[k]] = part[x.plan.job[k]];
+  for (size_t j : x.plan.second_of) comms[x.lay.read_ts(j)] = x.plan.second[j];
   return comms;
 }
 // the commitments that follow from others by linearity: E_i = dim_j of an identity subtable, a = sum_m coeff_m E_{f(m)}
 // under a linear g
-static void lasso_commit_derive(const lh_lasso_table& tb, std::vector<HG1>& comms) {
-  const size_t cc = tb.num_chunks, alpha = tb.num_memories;
-  bool linear_g = true;
-  for (uint32_t m = 0; m < tb.num_terms; m++) linear_g = linear_g && tb.g_num_factors[m] == 1;
-  for (size_t i = 0; i < alpha; i++)
-    if (tb.memory_subtable[i] == LH_SUBTABLE_IDENTITY) comms[1 + 2 * cc + i] = comms[1 + tb.memory_chunk[i]];
-  if (!linear_g) return;
+static void lasso_commit_derive(const LassoTable& x, std::vector<HG1>& comms) {
+  const lh_lasso_table& tb = *x.tb;
+  const LassoLayout& lay = x.lay;
+  for (size_t i = 0; i < lay.alpha; i++)
+    if (tb.memory_subtable[i] == LH_SUBTABLE_IDENTITY) comms[lay.E(i)] = comms[lay.dim(tb.memory_chunk[i])];
+  if (!lay.linear_g) return;
   std::vector<host::G1Xyzz> terms(tb.num_terms);
   // (the coefficients of the range / AND / XOR tables are powers of two below 2^64: a few dozen doublings each, done
   // here - waking the host pool for them cost more than they do; wide coefficients go to the pool)
   bool small_coeffs = true;
-  for (uint32_t m = 0; m < tb.num_terms && small_coeffs; m++) {
-    HFr co;
-    memcpy(&co, &tb.g_coeff[m], 32);
-    uint64_t canon[4];
-    co.to_canonical(canon);
-    small_coeffs = !canon[1] && !canon[2] && !canon[3];
-  }
+  for (uint32_t m = 0; m < tb.num_terms && small_coeffs; m++) small_coeffs = lasso_g_coeff_fits(tb, m, 64);
   auto term = [&](size_t m) {
-    HFr co;
-    memcpy(&co, &tb.g_coeff[m], 32);
-    terms[m] = host::g1_mul(host::g1_from_affine(comms[1 + 2 * cc + tb.g_factor[m][0]]), co);
+    terms[m] = host::g1_mul(host::g1_from_affine(comms[lay.E(tb.g_factor[m][0])]), lasso_g_coeff(tb, m));
   };
   if (small_coeffs)
     for (size_t m = 0; m < tb.num_terms; m++) term(m);
@@ -663,13 +696,58 @@ static void lasso_commit_derive(const lh_lasso_table& tb, std::vector<HG1>& comm
     host_parallel_for(tb.num_terms, term);
   host::G1Xyzz acc = host::G1Xyzz::identity();
   for (auto& t : terms) acc = host::g1_add(acc, t);
-  comms[0] = host::g1_to_affine(acc);
+  comms[lay.a()] = host::g1_to_affine(acc);
 }
 
+// the output column zero-padded to NV entries (a chunk size above n and no 32-bit form: the table the opening is handed)
+static Fr* lasso_pad_a(Ctx& c, const Fr* a, size_t N, size_t NV) {
+  Fr* a_pad = c.arena.alloc_n<Fr>(NV);
+  LH_HIP(hipMemcpyAsync(a_pad, a, N * sizeof(Fr), hipMemcpyDeviceToDevice, c.stream));
+  LH_HIP(hipMemsetAsync(a_pad + N, 0, (NV - N) * sizeof(Fr), c.stream));
+  return a_pad;
+}
+// One table's committed polys as the small-valued columns of the batch opening, its block at small[poly_base]: dim, read_ts
+// (below 2^bits of its access counts where known), E, final_cts, and a where it has a 32-bit form - a column of its own under
+// a product g (every entry below 2^a_bits), the linear combination x.a_linear of the E columns under a linear g.
+// Challenge-free: made as soon as the access counts' widths are known (count_ors).
+static void lasso_open_columns(Ctx& c, LassoTable& x, size_t n, size_t poly_base, SmallPoly* small) {
+  const lh_lasso_table& tb = *x.tb;
+  const LassoLayout& lay = x.lay;
+  const Shard sh(c);
+  const size_t N = (size_t)1 << (n - sh.rho), M = (size_t)1 << lay.l;
+  SmallPoly* s = small + poly_base;
+  if (x.a_small && x.w.a_bits) {
+    s[lay.a()] = SmallPoly{x.a_small, N, x.w.a_bits};
+  } else if (x.a_small) {
+    for (uint32_t m = 0; m < tb.num_terms; m++) {
+      x.a_linear.poly.push_back(poly_base + lay.E(tb.g_factor[m][0]));
+      x.a_linear.coeff.push_back(lasso_g_coeff(tb, m));
+    }
+    s[lay.a()] = SmallPoly{x.a_small, N, 0, &x.a_linear};
+  }
+  for (size_t j = 0; j < lay.cc; j++) {
+    s[lay.dim(j)] = SmallPoly{x.dims[j], N, (uint32_t)lay.l};
+    s[lay.read_ts(j)] = SmallPoly{x.w.rts[j], N, bit_length(x.count_ors[j])};
+    s[lay.final_cts(j)] = SmallPoly{x.w.fcs[j], M, 0};
+    if (sh.on) {
+      // the zero-padded n-variable final_cts column lives in the index range [0, 2^l), l <= shard_bit + rho: this rank's
+      // shard of it is the slice [rank * 2^shard_bit, (rank + 1) * 2^shard_bit) at its local indices [0, 2^shard_bit)
+      const size_t first = sh.rank << sh.j;
+      s[lay.final_cts(j)] = first < M ? SmallPoly{x.w.fcs[j] + first, std::min(M - first, (size_t)1 << sh.j), 0} : SmallPoly{x.w.fcs[j], 0, 0};
+    }
+  }
+  for (size_t i = 0; i < lay.alpha; i++) s[lay.E(i)] = SmallPoly{x.w.E[i], N, lasso_subtable_bits(tb.memory_subtable[i], lay.l)};
+}
+
+// The schedule of one table's proof: header, witness, commit, then lasso_argue (r and a(r), Surge, memory check, evaluations)
+// and ONE batch opening.  Single-table only: the sharded route, a scheme that commits columns itself, the staged precommit
+// (and, inside lasso_argue, ScU32 and the shared quad sums).
 void lasso_prove(Ctx& c, const Pcs& pcs, const lh_lasso_table& tb, size_t n, const uint32_t* const* d_dims,
                  Transcript& tr) {
   lasso_check_table(tb);
-  const size_t cc = tb.num_chunks, l = tb.chunk_bits, alpha = tb.num_memories;
+  LassoTable x(tb, d_dims);
+  const LassoLayout& lay = x.lay;
+  const size_t cc = lay.cc, l = lay.l, alpha = lay.alpha;
   LH_REQUIRE(n >= 1 && n < 31, LH_ERR_ARG, "lasso: need at least one variable");
   if (n > pcs.max_vars || l > pcs.max_vars)
     throw Error(LH_ERR_INVALID_PCS_PARAM, "Too many variates of poly to commit");
@@ -687,128 +765,72 @@ void lasso_prove(Ctx& c, const Pcs& pcs, const lh_lasso_table& tb, size_t n, con
   }
   const size_t nv = std::max(n, l), NV = (size_t)1 << (nv - sh.rho);
   const size_t N = (size_t)1 << (n - sh.rho), M = (size_t)1 << l;
-  // phase boundaries are EVENTS on the prover's stream (a hipStreamSynchronize at each of them drained the queue seven
-  // times per proof for the sake of a number nobody reads in production): lh_lasso_last_timing turns them into phase
-  // times when asked (Ctx::phase_times_resolve); lasso_ms[8], the total, is the host's wall clock
-  const double t0 = now_ms();
-  double* ph = c.lasso_ms;
-  LassoPhases phase_guard(c);
-  auto lap = [&](int idx) { phase_guard.lap(idx); };
-
-  ArenaScope scope(c.arena);
-  c.quad_sums.clear();  // (nothing of an earlier prove: the arena hands out the same pointers again)
-  EqHalfScope eq_scope(c);  // (the shared eq tables are arena memory of this scope)
-  c.route = RouteStats();
-  std::vector<uint32_t> count_ors(cc, 0);  // OR of every final_cts column (bounds its read_ts column) when computed
-  // ---- witness: counters, subtable reads, lookup outputs
-  Fr* a = nullptr;
-  uint32_t* a_small = nullptr;
-  // (the sorted dim columns only pay off where the MSM sorts slab by slab: msm.hip LH_MSM_SLAB_LOG)
-  LassoColumns w = lasso_witness_columns(c, tb, n, d_dims, &a, &a_small, n >= (size_t)knob(Knob::MSM_SLAB_LOG));
-  std::vector<uint32_t*>&rts = w.rts, &fcs = w.fcs, &E = w.E;
-  lap(0);
-  // ---- 0/1: domain separation + commitments (one batched MSM)
-  tr.common_field_element(HFr::from_u64(n));
-  tr.common_field_element(HFr::from_u64(l));
-  tr.common_field_element(HFr::from_u64(cc));
-  tr.common_field_element(HFr::from_u64(alpha));
-  Fr* a_pad = nullptr;  // the output column zero-padded to nv variables, where that table is needed (l > n, no 32-bit form)
   // the committed polys as small-valued columns and the (poly, point) pairs of the batch opening at the end (step 8): r, r_z,
-  // r_N, r_M are points 0..3.  Challenge-free: made once the access counts' widths are known (count_ors) - by the commit
-  // batch when the opening's precommit is staged from there, behind the commitments otherwise
-  const size_t num_n = 1 + 2 * cc + alpha;
+  // r_N, r_M are points 0..3.  Made by the commit batch when the opening's precommit is staged from there, behind the
+  // commitments otherwise.  (Ahead of the scope: a precommit on the helper reads them until the scope's end cancels it.)
   std::vector<SmallPoly> small;
   std::vector<lh_evaluation> evs;
-  SmallLinear a_linear;  // a = sum_m coeff_m E_{f(m)} entry by entry (linear g)
+  const LassoOpening where = LassoOpening::block(lay);
   auto open_columns = [&] {
     if (!small.empty()) return;
-    small.assign(num_n + cc, SmallPoly());
-    if (a_small && w.a_bits) {  // (product g: a column of its own, every entry below 2^a_bits)
-      small[0] = SmallPoly{a_small, N, w.a_bits};
-    } else if (a_small) {
-      for (uint32_t m = 0; m < tb.num_terms; m++) {
-        HFr co;
-        memcpy(&co, &tb.g_coeff[m], 32);
-        a_linear.poly.push_back(1 + 2 * cc + tb.g_factor[m][0]);
-        a_linear.coeff.push_back(co);
-      }
-      small[0] = SmallPoly{a_small, N, 0, &a_linear};
-    }
-    for (size_t j = 0; j < cc; j++) {
-      small[1 + j] = SmallPoly{d_dims[j], N, (uint32_t)l};
-      small[1 + cc + j] = SmallPoly{rts[j], N, count_ors[j] ? 32u - (uint32_t)__builtin_clz(count_ors[j]) : 0u};
-      small[num_n + j] = SmallPoly{fcs[j], M, 0};
-      if (shn) {
-        // the zero-padded n-variable final_cts column lives in the index range [0, 2^l), l <= shard_bit + rho: this rank's
-        // shard of it is the slice [rank * 2^shard_bit, (rank + 1) * 2^shard_bit) at its local indices [0, 2^shard_bit)
-        const size_t first = sh.rank << sh.j;
-        small[num_n + j] = first < M ? SmallPoly{fcs[j] + first, std::min(M - first, (size_t)1 << sh.j), 0} : SmallPoly{fcs[j], 0, 0};
-      }
-    }
-    for (size_t i = 0; i < alpha; i++)
-      small[1 + 2 * cc + i] = SmallPoly{E[i], N, lasso_subtable_bits(tb.memory_subtable[i], l)};
-    auto push = [&](size_t poly, size_t point) {
-      lh_evaluation e;
-      memset(&e, 0, sizeof(e));
-      e.poly = (uint32_t)poly;
-      e.point = (uint32_t)point;
-      evs.push_back(e);
-    };
-    push(0, 0);
-    for (size_t i = 0; i < alpha; i++) push(1 + 2 * cc + i, 1);
-    for (size_t j = 0; j < cc; j++) push(1 + j, 2);
-    for (size_t j = 0; j < cc; j++) push(1 + cc + j, 2);
-    for (size_t i = 0; i < alpha; i++) push(1 + 2 * cc + i, 2);
-    for (size_t j = 0; j < cc; j++) push(num_n + j, 3);
+    small.assign(lay.num_polys(), SmallPoly());
+    lasso_open_columns(c, x, n, 0, small.data());
+    lasso_evaluation_list(lay, where, nullptr, evs);
   };
+  LassoPhases phases(c);
+  auto lap = [&](int idx) { phases.lap(idx); };
+
+  // ---- witness: counters, subtable reads, lookup outputs
+  // (the sorted dim columns only pay off where the MSM sorts slab by slab: msm.hip LH_MSM_SLAB_LOG)
+  x.w = lasso_witness_columns(c, tb, n, d_dims, &x.a, &x.a_small, n >= (size_t)knob(Knob::MSM_SLAB_LOG));
+  Fr* const a = x.a;
+  uint32_t* const a_small = x.a_small;
+  const std::vector<uint32_t*>&rts = x.w.rts, &fcs = x.w.fcs, &E = x.w.E;
+  lap(0);
+  // ---- 0/1: domain separation + commitments (one batched MSM)
+  for (size_t v : {n, l, cc, alpha}) tr.common_field_element(HFr::from_u64(v));
+  Fr* a_pad = nullptr;  // the output column zero-padded to nv variables, where that table is needed (l > n, no 32-bit form)
   // the opening's column-wise commitments depend on the witness columns alone: on the helper ctx, beside the sum-checks
   // (Options::open_precommit) - in two stages (Options::open_precommit_stages): differences, digits and sort as soon as this
   // commit batch's accumulation is off the chip, the accumulation when the product trees are built
-  struct PrecommitGuard {  // (a prove that fails on the way drops what was started)
-    Ctx& c;
-    ~PrecommitGuard() { open_precommit_cancel(c); }
-  } precommit_guard{c};
   bool precommit_staged = false;
   if (pcs.commit_columns || pcs.commit_columns_and_write) {
     // a scheme that commits columns itself (Hyrax: vectors of row commitments): a from its 32-bit form when there is one,
     // dim / read_ts / E / final_cts as u32 columns with the bounds known here; E_i of an identity subtable IS dim_j.  The
     // derived, packed and sorted-reuse routes are msm_batch features: their counters stay 0.
-    auto bits_of = [](uint32_t v) { return v ? 32u - (uint32_t)__builtin_clz(v) : 1u; };
     {
       std::vector<const uint32_t*> cols(fcs.begin(), fcs.end());
-      k_or_u32(c, cols.data(), cc, M, count_ors.data());  // (the access counts bound the timestamps)
+      k_or_u32(c, cols.data(), cc, M, x.count_ors.data());  // (the access counts bound the timestamps)
     }
-    const size_t total = 1 + 3 * cc + alpha, k = pcs.chunks;
+    const size_t total = lay.num_polys(), k = pcs.chunks;
     std::vector<PcsColumn> cols(total, PcsColumn{nullptr, true, 0, 1});
-    cols[0] = a_small ? PcsColumn{a_small, true, N, w.a_bits ? w.a_bits : 32u} : PcsColumn{a, false, N, 0};
+    cols[lay.a()] = a_small ? PcsColumn{a_small, true, N, x.w.a_bits ? x.w.a_bits : 32u} : PcsColumn{a, false, N, 0};
     for (size_t j = 0; j < cc; j++) {
-      cols[1 + j] = PcsColumn{d_dims[j], true, N, (uint32_t)l};
-      cols[1 + cc + j] = PcsColumn{rts[j], true, N, bits_of(count_ors[j])};
-      cols[1 + 2 * cc + alpha + j] = PcsColumn{fcs[j], true, M, bits_of(count_ors[j])};
+      const uint32_t count_bits = std::max(bit_length(x.count_ors[j]), 1u);
+      cols[lay.dim(j)] = PcsColumn{d_dims[j], true, N, (uint32_t)l};
+      cols[lay.read_ts(j)] = PcsColumn{rts[j], true, N, count_bits};
+      cols[lay.final_cts(j)] = PcsColumn{fcs[j], true, M, count_bits};
     }
     for (size_t i = 0; i < alpha; i++)
-      if (tb.memory_subtable[i] != LH_SUBTABLE_IDENTITY) cols[1 + 2 * cc + i] = PcsColumn{E[i], true, N, std::max<uint32_t>(lasso_subtable_bits(tb.memory_subtable[i], l), 1)};
+      if (tb.memory_subtable[i] != LH_SUBTABLE_IDENTITY)
+        cols[lay.E(i)] = PcsColumn{E[i], true, N, std::max(lasso_subtable_bits(tb.memory_subtable[i], l), 1u)};
     if (pcs.commit_columns_and_write) {
       // a scheme whose commitments are no points (Brakedown: Merkle roots, and the zero column's is a root like any other,
       // so the identity mask is zero): it writes them itself and finds them again by the columns' pointers at the opening -
       // E_i of an identity subtable under dim_j's, and a without a 32-bit form under the table the opening will be handed
-      if (!a_small && N < NV) {
-        a_pad = c.arena.alloc_n<Fr>(NV);
-        LH_HIP(hipMemcpyAsync(a_pad, a, N * sizeof(Fr), hipMemcpyDeviceToDevice, c.stream));
-        LH_HIP(hipMemsetAsync(a_pad + N, 0, (NV - N) * sizeof(Fr), c.stream));
-        cols[0] = PcsColumn{a_pad, false, NV, 0};
-      }
+      if (!a_small && N < NV) cols[lay.a()] = PcsColumn{a_pad = lasso_pad_a(c, a, N, NV), false, NV, 0};
       for (size_t i = 0; i < alpha; i++)
-        if (tb.memory_subtable[i] == LH_SUBTABLE_IDENTITY) cols[1 + 2 * cc + i] = cols[1 + tb.memory_chunk[i]];
+        if (tb.memory_subtable[i] == LH_SUBTABLE_IDENTITY) cols[lay.E(i)] = cols[lay.dim(tb.memory_chunk[i])];
       tr.write_field_element(HFr::zero());
       pcs.commit_columns_and_write(cols.data(), total, nv, tr);
     } else {
       std::vector<HG1> comms = pcs.commit_columns(cols.data(), total, nv);
       LH_REQUIRE(comms.size() == total * k, LH_ERR_ARG, "lasso: commit_columns returned the wrong number of points");
       for (size_t i = 0; i < alpha; i++)
-        if (tb.memory_subtable[i] == LH_SUBTABLE_IDENTITY)
-          std::copy(comms.begin() + (1 + tb.memory_chunk[i]) * k, comms.begin() + (2 + tb.memory_chunk[i]) * k,
-                    comms.begin() + (1 + 2 * cc + i) * k);
+        if (tb.memory_subtable[i] == LH_SUBTABLE_IDENTITY) {
+          const auto dim = comms.begin() + lay.dim(tb.memory_chunk[i]) * k;
+          std::copy(dim, dim + k, comms.begin() + lay.E(i) * k);
+        }
       lasso_write_commitments(tr, comms, k);
     }
   } else {
@@ -819,10 +841,9 @@ void lasso_prove(Ctx& c, const Pcs& pcs, const lh_lasso_table& tb, size_t n, con
     // (sharded: this rank's share of the bases; every MSM below is the commitment of a shard - the chunk-split-then-sum
     // of util/arithmetic/msm.rs:101-114 with the shards as chunks - and the partial commitments are added at the end)
     std::vector<MsmJob> jobs;
-    LassoCommitPlan plan;
-    lasso_commit_jobs(c, pcs, tb, n, nv, d_dims, w, a, a_small, count_ors, false, nullptr, jobs, plan);
-    std::vector<HG1>& second = plan.second;
-    const std::vector<size_t>& second_of = plan.second_of;
+    lasso_commit_jobs(c, pcs, x, n, nv, false, nullptr, jobs);
+    std::vector<HG1>& second = x.plan.second;
+    const std::vector<size_t>& second_of = x.plan.second_of;
     std::vector<HG1> part(jobs.size()), comms;
     // (stage 1 of the opening's precommit goes to the helper from behind this batch's accumulation launches; not in a sharded
     // proof, whose commit ends in an exchange, and not under the profiler)
@@ -843,8 +864,8 @@ void lasso_prove(Ctx& c, const Pcs& pcs, const lh_lasso_table& tb, size_t n, con
       for (size_t q = 0; q < second_of.size(); q++) second[second_of[q]] = sums[part.size() + q];
     }
     c.host_stamp("commit:summed");
-    comms = lasso_commit_collect(tb, plan, part);
-    lasso_commit_derive(tb, comms);
+    comms = lasso_commit_collect(x, part);
+    lasso_commit_derive(x, comms);
     c.host_stamp("commit:linear");
     lasso_write_commitments(tr, comms);
     c.host_stamp("commit:written");
@@ -854,30 +875,22 @@ void lasso_prove(Ctx& c, const Pcs& pcs, const lh_lasso_table& tb, size_t n, con
   // ---- field-element views only where a sum-check needs tables (E for Surge when g is not linear); dim / read_ts /
   // final_cts (and E under a linear g) stay u32 all the way: fingerprints, evaluations and the batch opening's merge
   // read the 4-byte columns
-  std::vector<const Fr*> polys_n(num_n, nullptr), polys_l(cc, nullptr);
+  std::vector<const Fr*> polys(lay.num_polys(), nullptr);
   open_columns();
-  auto fr_view = [&](const uint32_t* src, size_t len) {
-    Fr* d = c.arena.alloc_n<Fr>(NV);
-    k_fr_from_u32(c, src, len, d);
-    if (len < NV) LH_HIP(hipMemsetAsync(d + len, 0, (NV - len) * sizeof(Fr), c.stream));
-    return d;
-  };
-  if (a_small) {  // (the output column goes by its 32-bit form: small[0])
+  if (a_small) {  // (the output column goes by its 32-bit form: small[a])
   } else if (N < NV) {  // l > n: the output column needs the padding too
-    if (!a_pad) {
-      a_pad = c.arena.alloc_n<Fr>(NV);
-      LH_HIP(hipMemcpyAsync(a_pad, a, N * sizeof(Fr), hipMemcpyDeviceToDevice, c.stream));
-      LH_HIP(hipMemsetAsync(a_pad + N, 0, (NV - N) * sizeof(Fr), c.stream));
-    }
-    polys_n[0] = a_pad;
+    polys[lay.a()] = a_pad ? a_pad : lasso_pad_a(c, a, N, NV);
   } else {
-    polys_n[0] = a;
+    polys[lay.a()] = a;
   }
-  bool linear_surge = true;  // (lasso_argue: the Surge sum-check then runs over the output column alone)
-  for (uint32_t m = 0; m < tb.num_terms; m++) linear_surge = linear_surge && tb.g_num_factors[m] == 1;
-  for (size_t i = 0; i < alpha; i++)
-    if (!linear_surge) polys_n[1 + 2 * cc + i] = fr_view(E[i], N);
-  const Fr* const* E_fr = polys_n.data() + 1 + 2 * cc;
+  if (!lay.linear_g)  // (under a linear g lasso_argue's Surge sum-check runs over the output column alone)
+    for (size_t i = 0; i < alpha; i++) {
+      Fr* d = c.arena.alloc_n<Fr>(NV);
+      k_fr_from_u32(c, E[i], N, d);
+      if (N < NV) LH_HIP(hipMemsetAsync(d + N, 0, (NV - N) * sizeof(Fr), c.stream));
+      polys[lay.E(i)] = d;
+    }
+  const Fr* const* E_fr = polys.data() + lay.E(0);
 
   // (one stage: all of the precommit starts when the memory-checking argument has built its product trees -
   // prove_grand_product's trees_built: beside the Surge rounds and the tree kernels, which stream at the HBM bound, the
@@ -893,37 +906,18 @@ void lasso_prove(Ctx& c, const Pcs& pcs, const lh_lasso_table& tb, size_t n, con
 
   // ---- 2-7: Surge, memory checking, evaluations
   c.host_stamp("argue:start");
-  LassoClaims cl = lasso_argue(c, tb, n, w, d_dims, polys_n[0], E_fr, tr, lap, a_small, precommit);
+  const LassoClaims cl = lasso_argue(c, tb, n, x.w, d_dims, polys[lay.a()], E_fr, tr, lap, a_small, precommit);
   c.host_stamp("argue:end");
-  const std::vector<HFr>&r = cl.r, &r_z = cl.r_z, &r_N = cl.r_N, &r_M = cl.r_M, &ev_n = cl.ev_n, &ev_l = cl.ev_l;
-  const HFr& v = cl.v;
 
   // ---- 8: ONE batch opening of all committed polys (nv variables) at r, r_z, r_N, r_M (zero-padded)
-  {
-    std::vector<HFr> points(4 * nv, HFr::zero());
-    std::copy(r.begin(), r.end(), points.begin());
-    std::copy(r_z.begin(), r_z.end(), points.begin() + nv);
-    std::copy(r_N.begin(), r_N.end(), points.begin() + 2 * nv);
-    std::copy(r_M.begin(), r_M.end(), points.begin() + 3 * nv);
-    size_t next = 0;
-    auto value = [&](const HFr& val) { memcpy(&evs[next++].value, &val, 32); };  // (in the order the pairs were listed)
-    value(v);
-    for (size_t i = 0; i < alpha; i++) value(cl.e_rz[i]);
-    for (size_t j = 0; j < cc; j++) value(ev_n[j]);
-    for (size_t j = 0; j < cc; j++) value(ev_n[cc + j]);
-    for (size_t i = 0; i < alpha; i++) value(ev_n[2 * cc + i]);
-    for (size_t j = 0; j < cc; j++) value(ev_l[j]);
-    LH_REQUIRE(next == evs.size(), LH_ERR_ARG, "lasso: evaluation list out of step");
-    std::vector<const Fr*> all(polys_n);
-    all.insert(all.end(), polys_l.begin(), polys_l.end());
-    pcs.batch_open(nv, all.data(), all.size(), points.data(), 4, evs.data(), evs.size(), tr, small.data());
-  }
+  std::vector<HFr> points;
+  lasso_append_points(points, {&cl.r, &cl.r_z, &cl.r_N, &cl.r_M}, nv);
+  lasso_evaluation_values(lay, where, cl, evs.data());
+  pcs.batch_open(nv, polys.data(), polys.size(), points.data(), 4, evs.data(), evs.size(), tr, small.data());
   lap(6);
   c.host_stamp("open:end");
   c.host_stamps_print();
-  ph[7] = 0;
-  ph[8] = now_ms() - t0;
-  c.phase_ev_pending = true;
+  phases.done();
 }
 
 // ------------------------------------------------------------------ several tables in one proof (tests/lasso_batch_ref.py)
@@ -937,11 +931,12 @@ size_t lasso_batch_check(const lh_lasso_table* const* tables, size_t K, size_t n
     LH_REQUIRE(tables[t] != nullptr, LH_ERR_ARG, "null argument: table " + std::to_string(t));
     const lh_lasso_table& tb = *tables[t];
     lasso_check_table(tb);
+    const LassoLayout lay(tb);
     // one identity mask (a field element read as 63 bits) frames a table's commitments
-    LH_REQUIRE(1 + 3 * (size_t)tb.num_chunks + tb.num_memories <= 63, LH_ERR_ARG,
+    LH_REQUIRE(lay.num_polys() <= 63, LH_ERR_ARG,
                "lasso batch: table " + std::to_string(t) + " has more than 63 commitments (one identity mask per table)");
     nv = std::max<size_t>(nv, tb.chunk_bits);
-    memories += tb.num_memories, terms += tb.num_terms, at_n += 2 * (size_t)tb.num_chunks + tb.num_memories;
+    memories += lay.alpha, terms += tb.num_terms, at_n += lay.num_at_n();
   }
   // 4 product trees per memory in ONE grand-product GKR, whose layers take 2 B + 1 <= SC_MAX_TABLES tables (gkr.cpp), and the
   // paired leaf layer SC_RW_MAX_PAIRS read / write pairs
@@ -968,60 +963,40 @@ void lasso_prove_batch(Ctx& c, const Pcs& pcs, const lh_lasso_table* const* tabl
              "lasso batch: implemented for schemes that commit columns against bases");
   if (nv > pcs.max_vars) throw Error(LH_ERR_INVALID_PCS_PARAM, "Too many variates of poly to commit");
   const size_t N = (size_t)1 << n, NV = (size_t)1 << nv;
-  struct Table {
-    const lh_lasso_table* tb;
-    const uint32_t* const* dims;
-    size_t cc, l, alpha, M;
-    bool linear_g;
-    LassoColumns w;
-    Fr* a = nullptr;
-    uint32_t* a_small = nullptr;
-    std::vector<uint32_t> count_ors;
+  struct Table : LassoTable {
+    using LassoTable::LassoTable;
     std::vector<int> shared_dim_job, shared_table, shared_chunk;  // per chunk: the earlier table's column it shares (-1: none)
-    LassoCommitPlan plan;
     std::vector<HG1> comms;
     size_t poly_base = 0, mem_base = 0;  // of its polys in the opening, of its memories in the batch
-    SmallLinear a_linear;
-    HFr v;
-    std::vector<HFr> ev;  // dim | read_ts | E at r_N, final_cts at r_M(l)
   };
-  std::vector<Table> T(K);
+  std::vector<Table> T;  // (K entries, reserved: SmallPoly::linear points at a table's a_linear)
+  T.reserve(K);
   std::vector<size_t> ls;  // the distinct chunk sizes in order of first appearance: r_M(ls[q]) is point 3 + q
   size_t A = 0, num_polys = 0;
   bool all_linear = true;
   for (size_t t = 0; t < K; t++) {
-    Table& x = T[t];
-    x.tb = tables[t], x.dims = d_dims[t];
-    x.cc = x.tb->num_chunks, x.l = x.tb->chunk_bits, x.alpha = x.tb->num_memories, x.M = (size_t)1 << x.l;
-    x.linear_g = true;
-    for (uint32_t m = 0; m < x.tb->num_terms; m++) x.linear_g = x.linear_g && x.tb->g_num_factors[m] == 1;
-    all_linear = all_linear && x.linear_g;
+    T.emplace_back(*tables[t], d_dims[t]);
+    Table& x = T.back();
+    all_linear = all_linear && x.lay.linear_g;
     x.mem_base = A, x.poly_base = num_polys;
-    A += x.alpha, num_polys += 1 + 3 * x.cc + x.alpha;
-    if (std::find(ls.begin(), ls.end(), x.l) == ls.end()) ls.push_back(x.l);
+    A += x.lay.alpha, num_polys += x.lay.num_polys();
+    if (std::find(ls.begin(), ls.end(), x.lay.l) == ls.end()) ls.push_back(x.lay.l);
   }
   auto point_of_l = [&](size_t l) { return 3 + (size_t)(std::find(ls.begin(), ls.end(), l) - ls.begin()); };
-
-  const double t0 = now_ms();
-  double* ph = c.lasso_ms;
   LassoPhases phases(c);
-  ArenaScope scope(c.arena);
-  c.quad_sums.clear();      // (nothing of an earlier prove: the arena hands out the same pointers again)
-  EqHalfScope eq_scope(c);  // (the shared eq tables are arena memory of this scope)
-  open_precommit_cancel(c);
-  c.route = RouteStats();
 
   // ---- witness, table by table.  A chunk column that an earlier table of the same chunk size was handed too (the same device
   // pointer: AND and XOR over the same operands) is counted once: its read_ts and final_cts serve both tables
   const bool keep_sorted = n >= (size_t)knob(Knob::MSM_SLAB_LOG);
   for (size_t t = 0; t < K; t++) {
     Table& x = T[t];
+    const size_t cc = x.lay.cc;
     LassoColumns reuse;
-    reuse.rts.assign(x.cc, nullptr), reuse.fcs.assign(x.cc, nullptr);
-    x.shared_table.assign(x.cc, -1), x.shared_chunk.assign(x.cc, -1), x.shared_dim_job.assign(x.cc, -1);
-    for (size_t j = 0; j < x.cc; j++)
+    reuse.rts.assign(cc, nullptr), reuse.fcs.assign(cc, nullptr);
+    x.shared_table.assign(cc, -1), x.shared_chunk.assign(cc, -1), x.shared_dim_job.assign(cc, -1);
+    for (size_t j = 0; j < cc; j++)
       for (size_t s = 0; s < t && x.shared_table[j] < 0; s++)
-        for (size_t k = 0; k < T[s].cc && T[s].l == x.l; k++)
+        for (size_t k = 0; k < T[s].lay.cc && T[s].lay.l == x.lay.l; k++)
           if (T[s].dims[k] == x.dims[j] && T[s].shared_table[k] < 0) {  // (the table that counted it)
             x.shared_table[j] = (int)s, x.shared_chunk[j] = (int)k;
             reuse.rts[j] = T[s].w.rts[k], reuse.fcs[j] = T[s].w.fcs[k];
@@ -1035,43 +1010,40 @@ void lasso_prove_batch(Ctx& c, const Pcs& pcs, const lh_lasso_table* const* tabl
   tr.common_field_element(HFr::from_u64(K));
   tr.common_field_element(HFr::from_u64(n));
   for (const Table& x : T)
-    for (size_t v : {x.l, x.cc, x.alpha}) tr.common_field_element(HFr::from_u64(v));
+    for (size_t v : {x.lay.l, x.lay.cc, x.lay.alpha}) tr.common_field_element(HFr::from_u64(v));
   {
     // the access counts' widths (they bound the timestamps: packing, known_bits): one readback per distinct chunk size
-    const bool want_ors = c.opt.lasso_pack_ts != 0 && N >= ((size_t)1 << 12);
-    for (Table& x : T) x.count_ors.assign(x.cc, 0);
-    if (want_ors)
+    if (c.opt.lasso_pack_ts != 0 && N >= ((size_t)1 << 12))
       for (size_t l : ls) {
         std::vector<const uint32_t*> cols;
         for (const Table& x : T)
-          if (x.l == l) cols.insert(cols.end(), x.w.fcs.begin(), x.w.fcs.end());
+          if (x.lay.l == l) cols.insert(cols.end(), x.w.fcs.begin(), x.w.fcs.end());
         std::vector<uint32_t> ors(cols.size(), 0);
         k_or_u32(c, cols.data(), cols.size(), (size_t)1 << l, ors.data());
         size_t at = 0;
         for (Table& x : T)
-          if (x.l == l)
-            for (size_t j = 0; j < x.cc; j++) x.count_ors[j] = ors[at++];
+          if (x.lay.l == l)
+            for (uint32_t& o : x.count_ors) o = ors[at++];
       }
     std::vector<MsmJob> jobs;
-    for (size_t t = 0; t < K; t++) {
-      Table& x = T[t];
-      for (size_t j = 0; j < x.cc; j++)
+    for (Table& x : T) {
+      for (size_t j = 0; j < x.lay.cc; j++)
         if (x.shared_table[j] >= 0) x.shared_dim_job[j] = (int)T[x.shared_table[j]].plan.dim_job[x.shared_chunk[j]];
-      lasso_commit_jobs(c, pcs, *x.tb, n, nv, x.dims, x.w, x.a, x.a_small, x.count_ors, true, x.shared_dim_job.data(), jobs, x.plan);
+      lasso_commit_jobs(c, pcs, x, n, nv, true, x.shared_dim_job.data(), jobs);
     }
     std::vector<HG1> part(jobs.size());
     msm_batch(c, jobs.data(), jobs.size(), (G1Affine*)part.data());
     for (Table& x : T) {
-      x.comms = lasso_commit_collect(*x.tb, x.plan, part);
-      for (size_t j = 0; j < x.cc; j++)
+      x.comms = lasso_commit_collect(x, part);
+      for (size_t j = 0; j < x.lay.cc; j++)
         if (x.shared_table[j] >= 0) {
           const Table& s = T[x.shared_table[j]];
           const size_t k = (size_t)x.shared_chunk[j];
-          x.comms[1 + j] = s.comms[1 + k];
-          x.comms[1 + x.cc + j] = s.comms[1 + s.cc + k];
-          x.comms[1 + 2 * x.cc + x.alpha + j] = s.comms[1 + 2 * s.cc + s.alpha + k];
+          x.comms[x.lay.dim(j)] = s.comms[s.lay.dim(k)];
+          x.comms[x.lay.read_ts(j)] = s.comms[s.lay.read_ts(k)];
+          x.comms[x.lay.final_cts(j)] = s.comms[s.lay.final_cts(k)];
         }
-      lasso_commit_derive(*x.tb, x.comms);
+      lasso_commit_derive(x, x.comms);
       lasso_write_commitments(tr, x.comms);
     }
   }
@@ -1087,29 +1059,22 @@ void lasso_prove_batch(Ctx& c, const Pcs& pcs, const lh_lasso_table* const* tabl
       else frs.push_back(x.a);
     }
     std::vector<HFr> vs(cols.size()), vf;
-    if (!cols.empty() && n >= 2) {
-      const Fr* eq_half = eq_half_get(c, r.data(), n, false);
-      k_inner_products_small_half(c, cols.data(), cols.size(), eq_half, N / 2, dev(r[0]), (Fr*)vs.data());
-    } else if (!cols.empty()) {
-      ArenaScope inner(c.arena);
-      Fr* eq = c.arena.alloc_n<Fr>(N);
-      k_eq_xy(c, (const Fr*)r.data(), n, eq);
-      k_inner_products_small(c, cols.data(), cols.size(), eq, N, (Fr*)vs.data());
-    }
+    if (!cols.empty()) lasso_evaluate_u32(c, cols.data(), cols.size(), r.data(), n, false, vs.data());
     if (!frs.empty()) vf = evaluate_polys(c, frs.data(), frs.size(), n, r.data(), false);
     size_t is = 0, ifr = 0;
-    for (Table& x : T) x.v = x.a_small ? vs[is++] : vf[ifr++];
+    for (Table& x : T) x.cl.v = x.a_small ? vs[is++] : vf[ifr++];
   }
-  for (const Table& x : T) tr.write_field_element(x.v);
+  for (const Table& x : T) tr.write_field_element(x.cl.v);
 
   // ---- 3: ONE Surge sum-check over eq * sum_t rho^t g_t
   const HFr rho = tr.squeeze_challenge();
   std::vector<HFr> rho_pow(K, HFr::one());
   for (size_t t = 1; t < K; t++) rho_pow[t] = rho_pow[t - 1] * rho;
   HFr claim = HFr::zero();
-  for (size_t t = 0; t < K; t++) claim += rho_pow[t] * T[t].v;
-  std::vector<const Fr*> E_fr(A, nullptr);  // field-element views of the E columns (a g with product terms in the batch)
+  for (size_t t = 0; t < K; t++) claim += rho_pow[t] * T[t].cl.v;
   std::vector<HFr> r_z, e_rz;
+  ScOptions so;
+  so.sum_is_exact = true;
   if (all_linear) {
     // every g linear: the summand is eq * sum_t rho^t a_t entry by entry - ONE table, as in lasso_argue's linear case -
     // formed from the output columns; the evaluations E_t,i(r_z) are inner products of the 32-bit columns with eq(r_z)
@@ -1125,61 +1090,32 @@ void lasso_prove_batch(Ctx& c, const Pcs& pcs, const lh_lasso_table* const* tabl
         else frs.push_back(T[t].a), wfr.push_back(dev(rho_pow[t]));
       }
       k_lincomb_mixed(c, frs.data(), wfr.data(), frs.size(), sm.data(), sm_len.data(), wsm.data(), sm.size(), N, comb);
-      lh_sop one_term;
-      memset(&one_term, 0, sizeof(one_term));
-      one_term.global_eq = 0;
-      one_term.num_terms = 1;
-      const HFr one = HFr::one();
-      memcpy(&one_term.coeff[0], &one, 32);
-      one_term.num_factors[0] = 1;
-      one_term.factor[0][0] = 0;
-      ScOptions so;
-      so.sum_is_exact = true;
       const Fr* tab = comb;
-      SumCheckResult sc = sum_check_prove(c, LH_SC_EVALUATIONS, n, one_term, &tab, 1, r.data(), 1, claim, tr, so);
-      r_z = sc.challenges;
+      r_z = sum_check_prove(c, LH_SC_EVALUATIONS, n, lasso_one_term(), &tab, 1, r.data(), 1, claim, tr, so).challenges;
     }
     std::vector<const uint32_t*> cols;
     for (const Table& x : T) cols.insert(cols.end(), x.w.E.begin(), x.w.E.end());
-    e_rz.assign(A, HFr::zero());
-    if (n >= 2) {  // (the table of r_z[1..] stays for the batch opening at r_z)
-      const Fr* eq_half = eq_half_get(c, r_z.data(), n, false);
-      k_inner_products_small_half(c, cols.data(), A, eq_half, N / 2, dev(r_z[0]), (Fr*)e_rz.data());
-    } else {
-      ArenaScope inner(c.arena);
-      Fr* eq = c.arena.alloc_n<Fr>(N);
-      k_eq_xy(c, (const Fr*)r_z.data(), n, eq);
-      k_inner_products_small(c, cols.data(), A, eq, N, (Fr*)e_rz.data());
-    }
+    e_rz.assign(A, HFr::zero());  // (the table of r_z[1..] stays for the batch opening at r_z)
+    lasso_evaluate_u32(c, cols.data(), A, r_z.data(), n, false, e_rz.data());
   } else {
     // one expression with every table's terms, table t's scaled by rho^t, over the field-element views of all E columns
+    std::vector<const Fr*> E_fr(A, nullptr);
     lh_sop surge;
     memset(&surge, 0, sizeof(surge));
-    surge.global_eq = 0;
-    uint32_t nt = 0;
     for (size_t t = 0; t < K; t++) {
       const Table& x = T[t];
-      for (size_t i = 0; i < x.alpha; i++) {
+      for (size_t i = 0; i < x.lay.alpha; i++) {
         Fr* d = c.arena.alloc_n<Fr>(N);
         k_fr_from_u32(c, x.w.E[i], N, d);
         E_fr[x.mem_base + i] = d;
       }
-      for (uint32_t m = 0; m < x.tb->num_terms; m++, nt++) {
-        HFr co;
-        memcpy(&co, &x.tb->g_coeff[m], 32);
-        co *= rho_pow[t];
-        memcpy(&surge.coeff[nt], &co, 32);
-        surge.num_factors[nt] = x.tb->g_num_factors[m];
-        for (int k = 0; k < x.tb->g_num_factors[m]; k++) surge.factor[nt][k] = (uint8_t)(x.mem_base + x.tb->g_factor[m][k]);
-      }
+      lasso_append_g(surge, *x.tb, x.mem_base, &rho_pow[t]);
     }
-    surge.num_terms = nt;
-    ScOptions so;
-    so.sum_is_exact = true;
     SumCheckResult sc = sum_check_prove(c, LH_SC_EVALUATIONS, n, surge, E_fr.data(), A, r.data(), 1, claim, tr, so);
     r_z = sc.challenges, e_rz = sc.evals;
   }
   tr.write_field_elements(e_rz);
+  for (Table& x : T) x.cl.e_rz.assign(e_rz.begin() + x.mem_base, e_rz.begin() + x.mem_base + x.lay.alpha);
   phases.lap(2);
 
   // ---- 4: memory checking, ONE grand-product GKR: the n-variable trees RS, WS of every memory, then Init, Final of every memory
@@ -1188,83 +1124,57 @@ void lasso_prove_batch(Ctx& c, const Pcs& pcs, const lh_lasso_table* const* tabl
   std::vector<std::vector<HFr>> r_M(ls.size());
   {
     ArenaScope inner(c.arena);
-    std::vector<const Fr*> leaves(4 * A), level_up(4 * A, nullptr);
-    std::vector<size_t> depths(4 * A);
-    std::vector<uint8_t> plus_one(4 * A, 0);
-    // (lasso_argue: the level above the leaves comes with them from 2^12 lookups on, and where the n-variable trees are alone
-    // at their leaf layer - n above every chunk size - that layer runs over the read set and the write leaves are not stored)
+    LassoTrees trees(A, n);
+    // (lasso_argue: the level above the leaves comes with them from 2^12 lookups on, and the write leaves are not stored
+    // where n is above every chunk size)
     const size_t max_l = *std::max_element(ls.begin(), ls.end());
     const bool fused_up = n >= 12, ws_implicit = fused_up && n > max_l;
     LassoRwBatch rw;
     memset(&rw, 0, sizeof(rw));
     for (const Table& x : T)
-      for (size_t i = 0; i < x.alpha; i++) {
+      for (size_t i = 0; i < x.lay.alpha; i++) {
         const size_t b = x.mem_base + i, j = x.tb->memory_chunk[i];
+        const LassoTrees::Memory m = trees.add(c, b, N, x.lay.l, fused_up, ws_implicit);
         rw.dim[b] = x.dims[j], rw.e[b] = x.w.E[i], rw.ts[b] = x.w.rts[j];
-        rw.rs[b] = c.arena.alloc_n<Fr>(N);
-        rw.ws[b] = ws_implicit ? nullptr : c.arena.alloc_n<Fr>(N);
-        if (fused_up) {
-          rw.rs_up[b] = c.arena.alloc_n<Fr>(N / 2), rw.ws_up[b] = c.arena.alloc_n<Fr>(N / 2);
-          level_up[2 * b] = rw.rs_up[b], level_up[2 * b + 1] = rw.ws_up[b];
-        }
-        leaves[2 * b] = rw.rs[b], leaves[2 * b + 1] = rw.ws[b];
-        plus_one[2 * b + 1] = 1;
-        depths[2 * b] = depths[2 * b + 1] = n;
-        Fr* in = c.arena.alloc_n<Fr>(x.M);
-        Fr* fi = c.arena.alloc_n<Fr>(x.M);
-        k_lasso_if_leaves(c, (int)x.tb->memory_subtable[i], (uint32_t)x.l, x.w.fcs[j], x.M, dev(gamma), dev(gamma2), dev(tau), in, fi,
-                          x.w.T.empty() ? nullptr : x.w.T[i]);
-        leaves[2 * A + 2 * b] = in, leaves[2 * A + 2 * b + 1] = fi;
-        depths[2 * A + 2 * b] = depths[2 * A + 2 * b + 1] = x.l;
+        rw.rs[b] = m.rs, rw.ws[b] = m.ws, rw.rs_up[b] = m.rs_up, rw.ws_up[b] = m.ws_up;
+        k_lasso_if_leaves(c, (int)x.tb->memory_subtable[i], (uint32_t)x.lay.l, x.w.fcs[j], (size_t)1 << x.lay.l, dev(gamma),
+                          dev(gamma2), dev(tau), m.init, m.fin, x.w.T.empty() ? nullptr : x.w.T[i]);
       }
     k_lasso_rw_leaves_batch(c, rw, A, N, fused_up, dev(gamma), dev(gamma2), dev(tau));
     phases.lap(3);
-    GrandProductResult gp = prove_grand_product(c, 4 * A, leaves.data(), depths.data(), tr, level_up.data(), plus_one.data());
+    GrandProductResult gp = trees.prove(c, tr);
     r_N = gp.points[0];
-    for (const Table& x : T) r_M[point_of_l(x.l) - 3] = gp.points[2 * A + 2 * x.mem_base];
+    for (const Table& x : T) r_M[point_of_l(x.lay.l) - 3] = gp.points[2 * A + 2 * x.mem_base];
   }
   phases.lap(4);
 
   // ---- 5: evaluations at r_N (dim | read_ts | E of every table, one pass) and at r_M(l) (final_cts, per chunk size)
-  // (the eq table of r_N[1..] is made OUTSIDE the scope below: it stays cached for the batch opening at r_N)
-  const Fr* eq_half_n = n >= 2 ? eq_half_get(c, r_N.data(), n, false) : nullptr;
   {
-    ArenaScope inner(c.arena);
     std::vector<const uint32_t*> at_n;
     for (const Table& x : T) {
-      for (size_t j = 0; j < x.cc; j++) at_n.push_back(x.dims[j]);
-      for (size_t j = 0; j < x.cc; j++) at_n.push_back(x.w.rts[j]);
-      for (size_t i = 0; i < x.alpha; i++) at_n.push_back(x.w.E[i]);
+      at_n.insert(at_n.end(), x.dims, x.dims + x.lay.cc);
+      at_n.insert(at_n.end(), x.w.rts.begin(), x.w.rts.end());
+      at_n.insert(at_n.end(), x.w.E.begin(), x.w.E.end());
     }
     std::vector<HFr> ev_n(at_n.size());
-    if (eq_half_n) {
-      k_inner_products_small_half(c, at_n.data(), at_n.size(), eq_half_n, N / 2, dev(r_N[0]), (Fr*)ev_n.data());
-    } else {
-      Fr* eq = c.arena.alloc_n<Fr>(N);
-      k_eq_xy(c, (const Fr*)r_N.data(), n, eq);
-      k_inner_products_small(c, at_n.data(), at_n.size(), eq, N, (Fr*)ev_n.data());
-    }
+    lasso_evaluate_u32(c, at_n.data(), at_n.size(), r_N.data(), n, false, ev_n.data());
     size_t at = 0;
     for (Table& x : T) {
-      x.ev.assign(ev_n.begin() + at, ev_n.begin() + at + 2 * x.cc + x.alpha);
-      at += 2 * x.cc + x.alpha;
+      x.cl.ev_n.assign(ev_n.begin() + at, ev_n.begin() + at + x.lay.num_at_n());
+      at += x.lay.num_at_n();
     }
     for (size_t q = 0; q < ls.size(); q++) {
       std::vector<const uint32_t*> at_l;
       for (const Table& x : T)
-        if (x.l == ls[q]) at_l.insert(at_l.end(), x.w.fcs.begin(), x.w.fcs.end());
+        if (x.lay.l == ls[q]) at_l.insert(at_l.end(), x.w.fcs.begin(), x.w.fcs.end());
       std::vector<HFr> ev_l(at_l.size());
-      const size_t M = (size_t)1 << ls[q];
-      Fr* eq = c.arena.alloc_n<Fr>(M);
-      k_eq_xy(c, (const Fr*)r_M[q].data(), ls[q], eq);
-      k_inner_products_small(c, at_l.data(), at_l.size(), eq, M, (Fr*)ev_l.data());
+      lasso_evaluate_u32_full(c, at_l.data(), at_l.size(), r_M[q].data(), ls[q], ev_l.data());
       size_t k = 0;
       for (Table& x : T)
-        if (x.l == ls[q])
-          for (size_t j = 0; j < x.cc; j++) x.ev.push_back(ev_l[k++]);
+        if (x.lay.l == ls[q]) x.cl.ev_l.assign(ev_l.begin() + k, ev_l.begin() + k + x.lay.cc), k += x.lay.cc;
     }
   }
-  for (const Table& x : T) tr.write_field_elements(x.ev);
+  for (const Table& x : T) tr.write_field_elements(x.cl.ev_n), tr.write_field_elements(x.cl.ev_l);
   phases.lap(5);
 
   // ---- 6: ONE batch opening over nv variables: polys table-major, points r, r_z, r_N, r_M per chunk size (zero-padded)
@@ -1273,60 +1183,20 @@ void lasso_prove_batch(Ctx& c, const Pcs& pcs, const lh_lasso_table* const* tabl
     std::vector<SmallPoly> small(num_polys, SmallPoly());
     std::vector<const Fr*> polys(num_polys, nullptr);
     std::vector<lh_evaluation> evs;
-    auto push = [&](size_t poly, size_t point, const HFr& val) {
-      lh_evaluation e;
-      memset(&e, 0, sizeof(e));
-      e.poly = (uint32_t)poly, e.point = (uint32_t)point;
-      memcpy(&e.value, &val, 32);
-      evs.push_back(e);
-    };
-    for (size_t t = 0; t < K; t++) {
-      Table& x = T[t];
-      const size_t p0 = x.poly_base, cc = x.cc, alpha = x.alpha;
-      if (x.a_small && x.w.a_bits) {  // (product g: a column of its own, every entry below 2^a_bits)
-        small[p0] = SmallPoly{x.a_small, N, x.w.a_bits};
-      } else if (x.a_small) {
-        for (uint32_t m = 0; m < x.tb->num_terms; m++) {
-          HFr co;
-          memcpy(&co, &x.tb->g_coeff[m], 32);
-          x.a_linear.poly.push_back(p0 + 1 + 2 * cc + x.tb->g_factor[m][0]);
-          x.a_linear.coeff.push_back(co);
-        }
-        small[p0] = SmallPoly{x.a_small, N, 0, &x.a_linear};
-      } else if (N < NV) {  // (no 32-bit form, and a chunk size above n: the table needs the padding)
-        Fr* a_pad = c.arena.alloc_n<Fr>(NV);
-        LH_HIP(hipMemcpyAsync(a_pad, x.a, N * sizeof(Fr), hipMemcpyDeviceToDevice, c.stream));
-        LH_HIP(hipMemsetAsync(a_pad + N, 0, (NV - N) * sizeof(Fr), c.stream));
-        polys[p0] = a_pad;
-      } else {
-        polys[p0] = x.a;
-      }
-      for (size_t j = 0; j < cc; j++) {
-        small[p0 + 1 + j] = SmallPoly{x.dims[j], N, (uint32_t)x.l};
-        small[p0 + 1 + cc + j] = SmallPoly{x.w.rts[j], N, x.count_ors[j] ? 32u - (uint32_t)__builtin_clz(x.count_ors[j]) : 0u};
-        small[p0 + 1 + 2 * cc + alpha + j] = SmallPoly{x.w.fcs[j], x.M, 0};
-      }
-      for (size_t i = 0; i < alpha; i++)
-        small[p0 + 1 + 2 * cc + i] = SmallPoly{x.w.E[i], N, lasso_subtable_bits(x.tb->memory_subtable[i], x.l)};
-      push(p0, 0, x.v);
-      for (size_t i = 0; i < alpha; i++) push(p0 + 1 + 2 * cc + i, 1, e_rz[x.mem_base + i]);
-      for (size_t j = 0; j < cc; j++) push(p0 + 1 + j, 2, x.ev[j]);
-      for (size_t j = 0; j < cc; j++) push(p0 + 1 + cc + j, 2, x.ev[cc + j]);
-      for (size_t i = 0; i < alpha; i++) push(p0 + 1 + 2 * cc + i, 2, x.ev[2 * cc + i]);
-      for (size_t j = 0; j < cc; j++) push(p0 + 1 + 2 * cc + alpha + j, point_of_l(x.l), x.ev[2 * cc + alpha + j]);
+    for (Table& x : T) {
+      lasso_open_columns(c, x, n, x.poly_base, small.data());
+      // (no 32-bit form: the field-element table - padded where a chunk size is above n)
+      if (!x.a_small) polys[x.poly_base + x.lay.a()] = N < NV ? lasso_pad_a(c, x.a, N, NV) : x.a;
+      lasso_evaluation_list(x.lay, LassoOpening::block(x.lay, x.poly_base, point_of_l(x.lay.l)), &x.cl, evs);
     }
-    const size_t num_points = 3 + ls.size();
-    std::vector<HFr> points(num_points * nv, HFr::zero());
-    std::copy(r.begin(), r.end(), points.begin());
-    std::copy(r_z.begin(), r_z.end(), points.begin() + nv);
-    std::copy(r_N.begin(), r_N.end(), points.begin() + 2 * nv);
-    for (size_t q = 0; q < ls.size(); q++) std::copy(r_M[q].begin(), r_M[q].end(), points.begin() + (3 + q) * nv);
-    pcs.batch_open(nv, polys.data(), num_polys, points.data(), num_points, evs.data(), evs.size(), tr, small.data());
+    std::vector<const std::vector<HFr>*> pts = {&r, &r_z, &r_N};
+    for (const std::vector<HFr>& pt : r_M) pts.push_back(&pt);
+    std::vector<HFr> points;
+    lasso_append_points(points, pts, nv);
+    pcs.batch_open(nv, polys.data(), num_polys, points.data(), pts.size(), evs.data(), evs.size(), tr, small.data());
   }
   phases.lap(6);
-  ph[7] = 0;
-  ph[8] = now_ms() - t0;
-  c.phase_ev_pending = true;
+  phases.done();
 }
 
 }  // namespace lh

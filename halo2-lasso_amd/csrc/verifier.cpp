@@ -761,7 +761,7 @@ void hyperplonk_verify_phases(const PcsVerifier& pcs, const lh_hp_vparam& vp, co
       const lh_hp_lasso_lookup& lk = vp.lasso_lookups[k];
       lasso_verify_check_table(lk.table, nv);
       if (lk.table.chunk_bits > nv) throw Error(LH_ERR_INVALID_SNARK, "Lasso subtable larger than the circuit");
-      count += 2 * lk.table.num_chunks + lk.table.num_memories;
+      count += LassoOpening::circuit_polys(LassoLayout(lk.table));
     }
     lasso_comms = lasso_read_commitments(tr, count, chunks);
   }
@@ -872,7 +872,8 @@ void hyperplonk_verify_phases(const PcsVerifier& pcs, const lh_hp_vparam& vp, co
   for (size_t k = 0; k < vp.num_lasso_lookups; k++) {
     const lh_hp_lasso_lookup& lk = vp.lasso_lookups[k];
     const lh_lasso_table& tb = lk.table;
-    const size_t cc = tb.num_chunks, l = tb.chunk_bits, alpha = tb.num_memories;
+    const LassoLayout lay(tb);
+    const size_t cc = lay.cc, l = lay.l, alpha = lay.alpha;
     // the prover's range (hyperplonk.cpp): preprocess and witness polys - instance polys have no commitment to open, the
     // polys after the witness do not exist yet when the lookup's columns are read
     const size_t first_committed = vp.num_instance_polys;
@@ -884,24 +885,10 @@ void hyperplonk_verify_phases(const PcsVerifier& pcs, const lh_hp_vparam& vp, co
     for (size_t v : {nv, l, cc, alpha}) tr.common_field_element(HFr::from_u64(v));
     LassoClaims cl = lasso_check(tb, nv, tr);
     const size_t p0 = num_points;
-    for (const std::vector<HFr>* ptv : {&cl.r, &cl.r_z, &cl.r_N, &cl.r_M}) {
-      points.insert(points.end(), ptv->begin(), ptv->end());
-      points.insert(points.end(), nv - ptv->size(), HFr::zero());
-    }
+    lasso_append_points(points, {&cl.r, &cl.r_z, &cl.r_N, &cl.r_M}, nv);
     num_points += 4;
-    auto push = [&](size_t poly, size_t point, const HFr& val) {
-      lh_evaluation e;
-      e.poly = (uint32_t)poly, e.point = (uint32_t)point;
-      memcpy(&e.value, &val, 32);
-      evals.push_back(e);
-    };
-    push(lk.output_poly, p0, cl.v);
-    for (size_t i = 0; i < alpha; i++) push(base + cc + i, p0 + 1, cl.e_rz[i]);
-    for (size_t j = 0; j < cc; j++) push(lk.chunk_polys[j], p0 + 2, cl.ev_n[j]);
-    for (size_t j = 0; j < cc; j++) push(base + j, p0 + 2, cl.ev_n[cc + j]);
-    for (size_t i = 0; i < alpha; i++) push(base + cc + i, p0 + 2, cl.ev_n[2 * cc + i]);
-    for (size_t j = 0; j < cc; j++) push(base + cc + alpha + j, p0 + 3, cl.ev_l[j]);
-    base += 2 * cc + alpha;
+    lasso_evaluation_list(lay, LassoOpening::in_circuit(lay, lk.output_poly, lk.chunk_polys, base, p0), &cl, evals);
+    base += LassoOpening::circuit_polys(lay);
   }
   pcs.batch_verify(nv, comms.data(), comms.size() / chunks, points.data(), num_points, evals.data(), evals.size(), tr);
 }
@@ -1019,149 +1006,44 @@ static void lasso_verify_check_table(const lh_lasso_table& tb, size_t n) {
     LH_REQUIRE(tb.g_num_factors[m] >= 1 && tb.g_num_factors[m] <= LH_SC_MAX_FACTORS, LH_ERR_ARG, "lasso: bad g term");
 }
 
-// the verifier's side of lasso_argue (oracle/pyref/lasso.py check): reads the messages, checks Surge and the
-// memory-checking identities, returns the points and claimed evaluations left to check against the commitments
-LassoClaims lasso_check(const lh_lasso_table& tb, size_t n, Transcript& tr) {
-  const size_t c = tb.num_chunks, l = tb.chunk_bits, alpha = tb.num_memories;
-  auto g_eval = [&](const std::vector<HFr>& vals) {
-    HFr acc = HFr::zero();
-    for (size_t m = 0; m < tb.num_terms; m++) {
-      HFr t;
-      memcpy(&t, &tb.g_coeff[m], 32);
-      for (size_t k = 0; k < tb.g_num_factors[m]; k++) {
-        LH_REQUIRE(tb.g_factor[m][k] < alpha, LH_ERR_ARG, "lasso: bad g factor");
-        t *= vals[tb.g_factor[m][k]];
-      }
-      acc += t;
-    }
-    return acc;
-  };
-  size_t g_degree = 0;
-  for (size_t m = 0; m < tb.num_terms; m++) g_degree = std::max<size_t>(g_degree, tb.g_num_factors[m]);
-
-  LassoClaims cl;
-  cl.r = tr.squeeze_challenges(n);
-  cl.v = tr.read_field_element();
-  auto surge = sum_check_verify(LH_SC_EVALUATIONS, n, g_degree + 1, cl.v, tr);
-  cl.r_z = surge.second;
-  cl.e_rz = tr.read_field_elements(alpha);
-  if (surge.first != host_eq_xy_eval(cl.r_z.data(), cl.r.data(), n) * g_eval(cl.e_rz))
-    throw Error(LH_ERR_INVALID_SNARK, "Surge sum-check final evaluation mismatch");
-
-  HFr gamma = tr.squeeze_challenge(), tau = tr.squeeze_challenge();
-  std::vector<size_t> depth(2 * alpha, n);
-  depth.insert(depth.end(), 2 * alpha, l);
-  std::vector<GpClaim> claims;
-  std::vector<HFr> roots = verify_grand_product(depth, tr, claims);
-  for (size_t i = 0; i < alpha; i++) {
-    const HFr &rs = roots[2 * i], &ws = roots[2 * i + 1], &init = roots[2 * alpha + 2 * i],
-              &fin = roots[2 * alpha + 2 * i + 1];
-    if (init * ws != rs * fin)
-      throw Error(LH_ERR_INVALID_SNARK, "memory " + std::to_string(i) + ": Init*WS != RS*Final");
-  }
-  cl.r_N = claims[0].point, cl.r_M = claims[2 * alpha].point;
-
-  std::vector<HFr> vals = tr.read_field_elements(3 * c + alpha);
-  const HFr *dim_e = &vals[0], *rts_e = &vals[c], *e_e = &vals[2 * c], *fc_e = &vals[2 * c + alpha];
-  auto fingerprint = [&](const HFr& a, const HFr& val, const HFr& t) { return a * gamma * gamma + val * gamma + t - tau; };
-  const HFr id_M = identity_eval(cl.r_M), one = HFr::one();
-  for (size_t i = 0; i < alpha; i++) {
-    const size_t j = tb.memory_chunk[i];
-    HFr rs = fingerprint(dim_e[j], e_e[i], rts_e[j]);
-    HFr init = fingerprint(id_M, subtable_mle_eval(tb.memory_subtable[i], cl.r_M), HFr::zero());
-    if (claims[2 * i].claim != rs || claims[2 * i + 1].claim != rs + one || claims[2 * alpha + 2 * i].claim != init ||
-        claims[2 * alpha + 2 * i + 1].claim != init + fc_e[j])
-      throw Error(LH_ERR_INVALID_SNARK, "memory " + std::to_string(i) + ": leaf claim mismatch");
-  }
-  cl.ev_n.assign(vals.begin(), vals.begin() + 2 * c + alpha);
-  cl.ev_l.assign(vals.begin() + 2 * c + alpha, vals.end());
-  return cl;
-}
-
-void lasso_verify(const PcsVerifier& pcs, const lh_lasso_table& tb, size_t n, Transcript& tr) {
-  const size_t chunks = pcs.chunks;
-  lasso_verify_check_table(tb, n);
-  const size_t c = tb.num_chunks, l = tb.chunk_bits, alpha = tb.num_memories;
-  for (size_t v : {n, l, c, alpha}) tr.common_field_element(HFr::from_u64(v));
-  const size_t nv = std::max(n, l);
-  std::vector<HG1> comms;
-  if (pcs.read_commitments) {
-    // commitments that are no points (Brakedown's roots): none of them can be the identity, so the mask element is zero
-    if (!tr.read_field_element().is_zero()) throw Error(LH_ERR_INVALID_SNARK, "lasso: commitment mask out of range");
-    comms = pcs.read_commitments(tr, 1 + 3 * c + alpha);
-  } else {
-    comms = lasso_read_commitments(tr, 1 + 3 * c + alpha, chunks);
-  }
-  LassoClaims cl = lasso_check(tb, n, tr);
-  const HFr *dim_e = &cl.ev_n[0], *rts_e = &cl.ev_n[c], *e_e = &cl.ev_n[2 * c], *fc_e = &cl.ev_l[0];
-
-  std::vector<lh_evaluation> evals;
-  auto push = [&](size_t poly, size_t point, const HFr& val) {
-    lh_evaluation e;
-    e.poly = (uint32_t)poly, e.point = (uint32_t)point;
-    memcpy(&e.value, &val, 32);
-    evals.push_back(e);
-  };
-  push(0, 0, cl.v);
-  for (size_t i = 0; i < alpha; i++) push(1 + 2 * c + i, 1, cl.e_rz[i]);
-  for (size_t j = 0; j < c; j++) push(1 + j, 2, dim_e[j]);
-  for (size_t j = 0; j < c; j++) push(1 + c + j, 2, rts_e[j]);
-  for (size_t i = 0; i < alpha; i++) push(1 + 2 * c + i, 2, e_e[i]);
-  for (size_t j = 0; j < c; j++) push(1 + 2 * c + alpha + j, 3, fc_e[j]);
-  std::vector<HFr> points;
-  const std::vector<HFr>* pts[4] = {&cl.r, &cl.r_z, &cl.r_N, &cl.r_M};
-  for (const std::vector<HFr>* pt : pts) {
-    points.insert(points.end(), pt->begin(), pt->end());
-    points.insert(points.end(), nv - pt->size(), HFr::zero());
-  }
-  pcs.batch_verify(nv, comms.data(), comms.size() / chunks, points.data(), 4, evals.data(), evals.size(), tr);
-}
-
-// the verifier of lasso_prove_batch (tests/lasso_batch_ref.py verify): lasso_verify / lasso_check over K tables that share
-// r, rho, gamma and tau, one Surge sum-check, one grand product and one batch opening
-static void lasso_verify_batch_checked(const PcsVerifier& pcs, const lh_lasso_table* const* tables, size_t K, size_t n, size_t nv,
-                                       Transcript& tr) {
-  std::vector<size_t> ls, mem_base(K), poly_base(K);  // ls: the distinct chunk sizes, r_M(ls[q]) is point 3 + q
-  size_t A = 0, num_polys = 0, g_degree = 0;
+// the verifier's side of lasso_argue, over K tables that share r, gamma and tau, one Surge sum-check and one grand product
+// (oracle/pyref/lasso.py check for K = 1, tests/lasso_batch_ref.py verify with `squeeze_rho`: then rho is squeezed behind the
+// a_t(r) and table t's g counts rho^t; without it the one table counts once).  Reads the messages, checks Surge and the
+// memory-checking identities table by table, returns every table's points and claimed evaluations left to check against
+// the commitments: r, r_z, r_N are the same for all, r_M for all of one chunk size.
+static std::vector<LassoClaims> lasso_check_tables(const lh_lasso_table* const* tables, size_t K, size_t n, bool squeeze_rho,
+                                                   Transcript& tr) {
+  std::vector<LassoLayout> lay(K);
+  std::vector<size_t> mem_base(K);
+  size_t A = 0, g_degree = 0;
   for (size_t t = 0; t < K; t++) {
-    const lh_lasso_table& tb = *tables[t];
-    mem_base[t] = A, poly_base[t] = num_polys;
-    A += tb.num_memories, num_polys += 1 + 3 * (size_t)tb.num_chunks + tb.num_memories;
-    if (std::find(ls.begin(), ls.end(), (size_t)tb.chunk_bits) == ls.end()) ls.push_back(tb.chunk_bits);
-    for (size_t m = 0; m < tb.num_terms; m++) g_degree = std::max<size_t>(g_degree, tb.g_num_factors[m]);
+    lay[t] = LassoLayout(*tables[t]);
+    mem_base[t] = A, A += lay[t].alpha;
+    g_degree = std::max(g_degree, lay[t].g_degree);
   }
-  auto point_of_l = [&](size_t l) { return 3 + (size_t)(std::find(ls.begin(), ls.end(), l) - ls.begin()); };
-  tr.common_field_element(HFr::from_u64(K));
-  tr.common_field_element(HFr::from_u64(n));
-  for (size_t t = 0; t < K; t++)
-    for (size_t v : {(size_t)tables[t]->chunk_bits, (size_t)tables[t]->num_chunks, (size_t)tables[t]->num_memories})
-      tr.common_field_element(HFr::from_u64(v));
-  std::vector<HG1> comms;
-  for (size_t t = 0; t < K; t++) {
-    std::vector<HG1> block = lasso_read_commitments(tr, 1 + 3 * (size_t)tables[t]->num_chunks + tables[t]->num_memories);
-    comms.insert(comms.end(), block.begin(), block.end());
-  }
-
+  std::vector<LassoClaims> cls(K);
   const std::vector<HFr> r = tr.squeeze_challenges(n);
-  const std::vector<HFr> vs = tr.read_field_elements(K);
-  const HFr rho = tr.squeeze_challenge();
+  for (LassoClaims& cl : cls) cl.v = tr.read_field_element();
+  const HFr rho = squeeze_rho ? tr.squeeze_challenge() : HFr::one();
   HFr claim = HFr::zero(), power = HFr::one();
   for (size_t t = 0; t < K; t++) {
-    claim += power * vs[t];
+    claim += power * cls[t].v;
     power *= rho;
   }
   auto surge = sum_check_verify(LH_SC_EVALUATIONS, n, g_degree + 1, claim, tr);
   const std::vector<HFr>& r_z = surge.second;
-  const std::vector<HFr> e_rz = tr.read_field_elements(A);
   HFr want = HFr::zero();
   power = HFr::one();
+  for (size_t t = 0; t < K; t++) cls[t].e_rz = tr.read_field_elements(lay[t].alpha);
   for (size_t t = 0; t < K; t++) {
     const lh_lasso_table& tb = *tables[t];
     HFr acc = HFr::zero();
     for (size_t m = 0; m < tb.num_terms; m++) {
-      HFr term;
-      memcpy(&term, &tb.g_coeff[m], 32);
-      for (size_t k = 0; k < tb.g_num_factors[m]; k++) term *= e_rz[mem_base[t] + tb.g_factor[m][k]];
+      HFr term = lasso_g_coeff(tb, m);
+      for (size_t k = 0; k < tb.g_num_factors[m]; k++) {
+        LH_REQUIRE(tb.g_factor[m][k] < lay[t].alpha, LH_ERR_ARG, "lasso: bad g factor");
+        term *= cls[t].e_rz[tb.g_factor[m][k]];
+      }
       acc += term;
     }
     want += power * acc;
@@ -1170,56 +1052,94 @@ static void lasso_verify_batch_checked(const PcsVerifier& pcs, const lh_lasso_ta
   if (surge.first != host_eq_xy_eval(r_z.data(), r.data(), n) * want)
     throw Error(LH_ERR_INVALID_SNARK, "Surge sum-check final evaluation mismatch");
 
+  // the n-variable trees RS, WS of every memory, then Init, Final of every memory
   const HFr gamma = tr.squeeze_challenge(), tau = tr.squeeze_challenge();
   std::vector<size_t> depth(2 * A, n);
-  for (size_t t = 0; t < K; t++) depth.insert(depth.end(), 2 * (size_t)tables[t]->num_memories, (size_t)tables[t]->chunk_bits);
+  for (size_t t = 0; t < K; t++) depth.insert(depth.end(), 2 * lay[t].alpha, lay[t].l);
   std::vector<GpClaim> claims;
   const std::vector<HFr> roots = verify_grand_product(depth, tr, claims);
+  const HFr *rw = roots.data(), *inf = roots.data() + 2 * A;  // (RS, WS) and (Init, Final) of memory b at [2 b], [2 b + 1]
   for (size_t b = 0; b < A; b++)
-    if (roots[2 * A + 2 * b] * roots[2 * b + 1] != roots[2 * b] * roots[2 * A + 2 * b + 1])
+    if (inf[2 * b] * rw[2 * b + 1] != rw[2 * b] * inf[2 * b + 1])
       throw Error(LH_ERR_INVALID_SNARK, "memory " + std::to_string(b) + ": Init*WS != RS*Final");
-  const std::vector<HFr> r_N = claims[0].point;
-  std::vector<std::vector<HFr>> r_M(ls.size());
-  for (size_t t = 0; t < K; t++) r_M[point_of_l(tables[t]->chunk_bits) - 3] = claims[2 * A + 2 * mem_base[t]].point;
 
-  std::vector<lh_evaluation> evals;
-  auto push = [&](size_t poly, size_t point, const HFr& val) {
-    lh_evaluation e;
-    e.poly = (uint32_t)poly, e.point = (uint32_t)point;
-    memcpy(&e.value, &val, 32);
-    evals.push_back(e);
-  };
   auto fingerprint = [&](const HFr& a, const HFr& val, const HFr& ts) { return a * gamma * gamma + val * gamma + ts - tau; };
   const HFr one = HFr::one();
+  const GpClaim *rw_c = claims.data(), *inf_c = claims.data() + 2 * A;
   for (size_t t = 0; t < K; t++) {
     const lh_lasso_table& tb = *tables[t];
-    const size_t c = tb.num_chunks, alpha = tb.num_memories, p0 = poly_base[t];
-    const std::vector<HFr> vals = tr.read_field_elements(3 * c + alpha);
-    const HFr *dim_e = &vals[0], *rts_e = &vals[c], *e_e = &vals[2 * c], *fc_e = &vals[2 * c + alpha];
-    const std::vector<HFr>& pt = r_M[point_of_l(tb.chunk_bits) - 3];
-    const HFr id_M = identity_eval(pt);
-    for (size_t i = 0; i < alpha; i++) {
+    LassoClaims& cl = cls[t];
+    cl.r = r, cl.r_z = r_z, cl.r_N = rw_c[0].point, cl.r_M = inf_c[2 * mem_base[t]].point;
+    cl.ev_n = tr.read_field_elements(lay[t].num_at_n());
+    cl.ev_l = tr.read_field_elements(lay[t].cc);
+    const HFr *dim_e = cl.ev_n.data(), *rts_e = dim_e + lay[t].cc, *e_e = rts_e + lay[t].cc, *fc_e = cl.ev_l.data();
+    const HFr id_M = identity_eval(cl.r_M);
+    for (size_t i = 0; i < lay[t].alpha; i++) {
       const size_t j = tb.memory_chunk[i], b = mem_base[t] + i;
       const HFr rs = fingerprint(dim_e[j], e_e[i], rts_e[j]);
-      const HFr init = fingerprint(id_M, subtable_mle_eval(tb.memory_subtable[i], pt), HFr::zero());
-      if (claims[2 * b].claim != rs || claims[2 * b + 1].claim != rs + one || claims[2 * A + 2 * b].claim != init ||
-          claims[2 * A + 2 * b + 1].claim != init + fc_e[j])
+      const HFr init = fingerprint(id_M, subtable_mle_eval(tb.memory_subtable[i], cl.r_M), HFr::zero());
+      if (rw_c[2 * b].claim != rs || rw_c[2 * b + 1].claim != rs + one || inf_c[2 * b].claim != init ||
+          inf_c[2 * b + 1].claim != init + fc_e[j])
         throw Error(LH_ERR_INVALID_SNARK, "memory " + std::to_string(b) + ": leaf claim mismatch");
     }
-    push(p0, 0, vs[t]);
-    for (size_t i = 0; i < alpha; i++) push(p0 + 1 + 2 * c + i, 1, e_rz[mem_base[t] + i]);
-    for (size_t j = 0; j < c; j++) push(p0 + 1 + j, 2, dim_e[j]);
-    for (size_t j = 0; j < c; j++) push(p0 + 1 + c + j, 2, rts_e[j]);
-    for (size_t i = 0; i < alpha; i++) push(p0 + 1 + 2 * c + i, 2, e_e[i]);
-    for (size_t j = 0; j < c; j++) push(p0 + 1 + 2 * c + alpha + j, point_of_l(tb.chunk_bits), fc_e[j]);
+  }
+  return cls;
+}
+LassoClaims lasso_check(const lh_lasso_table& tb, size_t n, Transcript& tr) {
+  const lh_lasso_table* one = &tb;
+  return lasso_check_tables(&one, 1, n, false, tr)[0];
+}
+
+void lasso_verify(const PcsVerifier& pcs, const lh_lasso_table& tb, size_t n, Transcript& tr) {
+  const size_t chunks = pcs.chunks;
+  lasso_verify_check_table(tb, n);
+  const LassoLayout lay(tb);
+  for (size_t v : {n, lay.l, lay.cc, lay.alpha}) tr.common_field_element(HFr::from_u64(v));
+  const size_t nv = std::max(n, lay.l);
+  std::vector<HG1> comms;
+  if (pcs.read_commitments) {
+    // commitments that are no points (Brakedown's roots): none of them can be the identity, so the mask element is zero
+    if (!tr.read_field_element().is_zero()) throw Error(LH_ERR_INVALID_SNARK, "lasso: commitment mask out of range");
+    comms = pcs.read_commitments(tr, lay.num_polys());
+  } else {
+    comms = lasso_read_commitments(tr, lay.num_polys(), chunks);
+  }
+  const LassoClaims cl = lasso_check(tb, n, tr);
+  std::vector<lh_evaluation> evals;
+  lasso_evaluation_list(lay, LassoOpening::block(lay), &cl, evals);
+  std::vector<HFr> points;
+  lasso_append_points(points, {&cl.r, &cl.r_z, &cl.r_N, &cl.r_M}, nv);
+  pcs.batch_verify(nv, comms.data(), comms.size() / chunks, points.data(), 4, evals.data(), evals.size(), tr);
+}
+
+// the verifier of lasso_prove_batch (tests/lasso_batch_ref.py verify): its header and block-wise commitments, the argument's
+// checks over the K tables with rho, one batch opening; r_M of the q-th distinct chunk size is point 3 + q
+static void lasso_verify_batch_checked(const PcsVerifier& pcs, const lh_lasso_table* const* tables, size_t K, size_t n, size_t nv,
+                                       Transcript& tr) {
+  std::vector<LassoLayout> lay(K);
+  for (size_t t = 0; t < K; t++) lay[t] = LassoLayout(*tables[t]);
+  tr.common_field_element(HFr::from_u64(K));
+  tr.common_field_element(HFr::from_u64(n));
+  for (size_t t = 0; t < K; t++)
+    for (size_t v : {lay[t].l, lay[t].cc, lay[t].alpha}) tr.common_field_element(HFr::from_u64(v));
+  std::vector<HG1> comms;
+  for (size_t t = 0; t < K; t++) {
+    std::vector<HG1> block = lasso_read_commitments(tr, lay[t].num_polys());
+    comms.insert(comms.end(), block.begin(), block.end());
+  }
+  const std::vector<LassoClaims> cls = lasso_check_tables(tables, K, n, true, tr);
+  std::vector<const std::vector<HFr>*> pts = {&cls[0].r, &cls[0].r_z, &cls[0].r_N};
+  std::vector<size_t> ls;  // the distinct chunk sizes in order of first appearance
+  std::vector<lh_evaluation> evals;
+  size_t poly_base = 0;
+  for (size_t t = 0; t < K; t++) {
+    const size_t q = (size_t)(std::find(ls.begin(), ls.end(), lay[t].l) - ls.begin());
+    if (q == ls.size()) ls.push_back(lay[t].l), pts.push_back(&cls[t].r_M);
+    lasso_evaluation_list(lay[t], LassoOpening::block(lay[t], poly_base, 3 + q), &cls[t], evals);
+    poly_base += lay[t].num_polys();
   }
   std::vector<HFr> points;
-  std::vector<const std::vector<HFr>*> pts = {&r, &r_z, &r_N};
-  for (const std::vector<HFr>& pt : r_M) pts.push_back(&pt);
-  for (const std::vector<HFr>* pt : pts) {
-    points.insert(points.end(), pt->begin(), pt->end());
-    points.insert(points.end(), nv - pt->size(), HFr::zero());
-  }
+  lasso_append_points(points, pts, nv);
   pcs.batch_verify(nv, comms.data(), comms.size(), points.data(), pts.size(), evals.data(), evals.size(), tr);
 }
 // A proof that does not verify is LH_ERR_INVALID_SNARK whichever piece found it out (a round message, an opening, bytes that
