@@ -67,6 +67,13 @@ pub struct lh_sop {
     pub factor: [[u8; LH_SC_MAX_FACTORS]; LH_SC_MAX_TERMS],
 }
 
+pub const LH_LOGUP_MAX_LOOKUPS: usize = 8;
+pub const LH_LOGUP_MAX_WIDTH: usize = 8;
+pub const LH_LOGUP_MAX_TABLE_VARS: usize = 24;
+// one lookup of lh_logup_gkr_prove: `width` device input columns of 2^num_vars Fr, `width` host table columns of 2^table_vars
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct lh_logup_lookup { pub width: u32, pub d_inputs: *const *const Fr, pub table: *const *const Fr }
+
 pub const LH_EX_CONSTANT: u32 = 0;
 pub const LH_EX_IDENTITY: u32 = 1;
 pub const LH_EX_LAGRANGE: u32 = 2;
@@ -286,6 +293,15 @@ extern "C" {
                                 num_vars: usize, d_dims: *const *const *const u32, t: *mut lh_transcript) -> lh_status;
     pub fn lh_lasso_verify_batch(vp: *const lh_mkzg_vp, tables: *const *const lh_lasso_table, num_tables: usize,
                                  num_vars: usize, t: *mut lh_transcript) -> lh_status;
+    // LogUp-GKR: lookups by value into unstructured tables (tests/logup_gkr_ref.py); the verifier ignores d_inputs
+    pub fn lh_logup_gkr_prove(ctx: *mut lh_ctx, srs: *const lh_srs, lookups: *const lh_logup_lookup, num_lookups: usize,
+                              num_vars: usize, table_vars: usize, t: *mut lh_transcript) -> lh_status;
+    pub fn lh_logup_gkr_verify(vp: *const lh_mkzg_vp, lookups: *const lh_logup_lookup, num_lookups: usize, num_vars: usize,
+                               table_vars: usize, t: *mut lh_transcript) -> lh_status;
+    // the host verifier of lh_gkr_fractional_prove; the roots p_0s / q_0s come back with the final claims and the point
+    pub fn lh_gkr_fractional_verify(num_batching: usize, num_vars: usize, claimed_p_0s: *const *const Fr,
+                                    claimed_q_0s: *const *const Fr, t: *mut lh_transcript, out_p_0s: *mut Fr,
+                                    out_q_0s: *mut Fr, out_p_xs: *mut Fr, out_q_xs: *mut Fr, out_x: *mut Fr) -> lh_status;
     // one proof over several GPUs
     pub fn lh_ctx_set_comm(ctx: *mut lh_ctx, comm: *const lh_comm, shard_bit: usize) -> lh_status;
     pub fn lh_rccl_unique_id(out: *mut u8) -> lh_status;

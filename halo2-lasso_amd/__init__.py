@@ -1584,6 +1584,108 @@ def lasso_prove_batch(pp, tables, num_vars, dims, transcript):
     del keep
 
 
+# ------------------------------------------------------------------ LogUp-GKR (include/lasso_hip.h lh_logup_gkr_prove)
+class LogupLookup:
+    """One lookup of a LogUp-GKR proof: `inputs`, w device columns (MultilinearPolynomial / DeviceBuffer of 2^num_vars Fr;
+    None for a verifier), looked up by value in `table`, w lists of 2^table_vars ints - a row is a tuple of w elements."""
+
+    def __init__(self, inputs, table):
+        self.inputs = None if inputs is None else list(inputs)
+        self.table = [list(col) for col in table]
+
+    @property
+    def width(self):
+        return len(self.table)
+
+    @property
+    def table_vars(self):
+        return len(self.table[0]).bit_length() - 1 if self.table and self.table[0] else 0
+
+    def check(self, prover):
+        """ArgumentError before anything is marshalled or the device is touched"""
+        if not 1 <= self.width <= _ffi.LH_LOGUP_MAX_WIDTH:
+            raise ArgumentError("logup: width out of range (1 to %d)" % _ffi.LH_LOGUP_MAX_WIDTH)
+        rows = len(self.table[0])
+        if rows < 2 or rows & (rows - 1) or any(len(col) != rows for col in self.table):
+            raise ArgumentError("logup: table columns of one power-of-two length >= 2")
+        if self.table_vars > _ffi.LH_LOGUP_MAX_TABLE_VARS:
+            raise ArgumentError("logup: table_vars out of range (1 to %d)" % _ffi.LH_LOGUP_MAX_TABLE_VARS)
+        if prover and (self.inputs is None or len(self.inputs) != self.width):
+            raise ArgumentError("logup: expected %d input columns" % self.width)
+
+
+def _logup_list(lookups, num_vars, prover):
+    """-> (lh_logup_lookup array, table_vars, keepalive)"""
+    if not 1 <= len(lookups) <= _ffi.LH_LOGUP_MAX_LOOKUPS:
+        raise ArgumentError("logup: 1 to %d lookups" % _ffi.LH_LOGUP_MAX_LOOKUPS)
+    for lk in lookups:
+        lk.check(prover)
+    table_vars = lookups[0].table_vars
+    if any(lk.table_vars != table_vars for lk in lookups):
+        raise ArgumentError("logup: every table has 2^table_vars rows")
+    if not 1 <= num_vars < 31:
+        raise ArgumentError("logup: num_vars out of range (1 to 30)")
+    if sum(lk.width for lk in lookups) > 63:
+        raise ArgumentError("logup: more than 63 input columns in all (one identity mask)")
+    arr, keep = (_ffi.lh_logup_lookup * len(lookups))(), []
+    for k, lk in enumerate(lookups):
+        cols = [_fr_array(col) for col in lk.table]
+        tab = (C.POINTER(lh_fr) * lk.width)(*[C.cast(col, C.POINTER(lh_fr)) for col in cols])
+        arr[k].width, arr[k].table = lk.width, tab
+        keep += [cols, tab]
+        if prover:
+            if any(getattr(p, "num_vars", num_vars) != num_vars for p in lk.inputs):
+                raise ArgumentError("logup: input columns of 2^num_vars entries")
+            ins = _ptr_array(lk.inputs)
+            arr[k].d_inputs = C.cast(ins, C.POINTER(C.c_void_p))
+            keep.append(ins)
+    return arr, table_vars, keep
+
+
+def logup_gkr_prove(pp, lookups, transcript, num_vars=None):
+    """LogUp-GKR over multilinear KZG (tests/logup_gkr_ref.py): every input row of every lookup is a row of its table.
+    num_vars: of the input columns (default: the first column's, a MultilinearPolynomial).  Appends the proof."""
+    if num_vars is None:
+        if not lookups or not lookups[0].inputs or not hasattr(lookups[0].inputs[0], "num_vars"):
+            raise ArgumentError("logup: num_vars is needed with raw device buffers")
+        num_vars = lookups[0].inputs[0].num_vars
+    arr, table_vars, keep = _logup_list(lookups, num_vars, True)
+    _check(pp.ctx.lib.lh_logup_gkr_prove(pp.ctx.h, pp.h, arr, len(lookups), num_vars, table_vars, transcript.p))
+    del keep
+
+
+def logup_gkr_verify(vp, lookups, num_vars, transcript):
+    """Verifier of logup_gkr_prove (host only; the lookups' inputs are ignored).  A Keccak256Transcript must be fully
+    consumed."""
+    arr, table_vars, keep = _logup_list(lookups, num_vars, False)
+    _check(vp.lib.lh_logup_gkr_verify(vp.h, arr, len(lookups), num_vars, table_vars, transcript.p))
+    del keep
+    if isinstance(transcript, Keccak256Transcript) and transcript.remaining():
+        raise InvalidSnark("trailing bytes in proof")
+
+
+def verify_fractional_sum_check(num_vars, claimed_p_0s, claimed_q_0s, transcript):
+    """fractional_sum_check.rs:193-270, the host verifier of prove_fractional_sum_check (a claim None: the root is read)
+    -> (p_0s, q_0s, p_xs, q_xs, x): the roots come back because a caller checks a relation between them."""
+    B = len(claimed_p_0s)
+    if B != len(claimed_q_0s):
+        raise ArgumentError("length mismatch")
+
+    def opt(claims):
+        keep = [_fr_array([c]) if c is not None else None for c in claims]
+        arr = (C.POINTER(lh_fr) * max(B, 1))()
+        for i, k in enumerate(keep):
+            arr[i] = C.cast(k, C.POINTER(lh_fr)) if k is not None else None
+        return arr, keep
+
+    cp, keep_p = opt(claimed_p_0s)
+    cq, keep_q = opt(claimed_q_0s)
+    outs = [(lh_fr * max(B, 1))() for _ in range(4)]
+    x = (lh_fr * max(num_vars, 1))()
+    _check(_ffi.load().lh_gkr_fractional_verify(B, num_vars, cp, cq, transcript.p, *outs, x))
+    return tuple(_fr_list(o, B) for o in outs) + (_fr_list(x, num_vars),)
+
+
 def attach_comm(ctx, rank, size, all_gather, shard_bit):
     """Attach a caller-supplied communicator to the context (sharded proving): the transport of the
     CPU / one-GPU tests.  all_gather(send: bytes) -> bytes of size * len(send), rank-major; device-side gathers are

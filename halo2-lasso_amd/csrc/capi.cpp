@@ -687,6 +687,16 @@ lh_status lh_lasso_prove_batch(lh_ctx* ctx, const lh_srs* srs, const lh_lasso_ta
   lasso_prove_batch(ctx->c, mkzg_pcs(ctx->c, srs->s), tables, num_tables, num_vars, d_dims, tr);
   LH_CATCH
 }
+// ---------------------------------------------------------------- LogUp-GKR
+lh_status lh_logup_gkr_prove(lh_ctx* ctx, const lh_srs* srs, const lh_logup_lookup* lookups, size_t num_lookups, size_t num_vars,
+                             size_t table_vars, lh_transcript* t) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(srs);
+  NEED(lookups);
+  Transcript tr(t);
+  logup_gkr_prove(ctx->c, mkzg_pcs(ctx->c, srs->s), lookups, num_lookups, num_vars, table_vars, tr);
+  LH_CATCH
+}
 lh_status lh_lasso_last_timing(lh_ctx* ctx, double* out_ms) {
   LH_TRY NEED_CTX(ctx);
   NEED(out_ms);
@@ -987,6 +997,31 @@ lh_status lh_lasso_verify_batch(const lh_mkzg_vp* vp, const lh_lasso_table* cons
   if (lasso_batch_check(tables, num_tables, num_vars) > mkzg_vp_num_vars(*vp->p))
     throw lh::Error(LH_ERR_INVALID_PCS_PARAM, "Too many variates of poly to verify");
   lasso_verify_batch(mkzg_verifier(*vp->p), tables, num_tables, num_vars, tr);
+  LH_CATCH
+}
+lh_status lh_gkr_fractional_verify(size_t num_batching, size_t num_vars, const lh_fr* const* claimed_p_0s,
+                                   const lh_fr* const* claimed_q_0s, lh_transcript* t, lh_fr* out_p_0s, lh_fr* out_q_0s,
+                                   lh_fr* out_p_xs, lh_fr* out_q_xs, lh_fr* out_x) {
+  LH_TRY
+  Transcript tr(t);
+  const FracVerifyResult r = verify_fractional_sum_check(num_batching, num_vars, (const HFr* const*)claimed_p_0s,
+                                                         (const HFr* const*)claimed_q_0s, tr);
+  if (out_p_0s) memcpy(out_p_0s, r.p_0s.data(), r.p_0s.size() * 32);
+  if (out_q_0s) memcpy(out_q_0s, r.q_0s.data(), r.q_0s.size() * 32);
+  if (out_p_xs) memcpy(out_p_xs, r.p_xs.data(), r.p_xs.size() * 32);
+  if (out_q_xs) memcpy(out_q_xs, r.q_xs.data(), r.q_xs.size() * 32);
+  if (out_x) memcpy(out_x, r.x.data(), r.x.size() * 32);
+  LH_CATCH
+}
+lh_status lh_logup_gkr_verify(const lh_mkzg_vp* vp, const lh_logup_lookup* lookups, size_t num_lookups, size_t num_vars,
+                              size_t table_vars, lh_transcript* t) {
+  LH_TRY
+  NEED(vp);
+  NEED(lookups);
+  Transcript tr(t);
+  if (logup_check(lookups, num_lookups, num_vars, table_vars, false) > mkzg_vp_num_vars(*vp->p))
+    throw lh::Error(LH_ERR_INVALID_PCS_PARAM, "Too many variates of poly to verify");
+  logup_gkr_verify(mkzg_verifier(*vp->p), lookups, num_lookups, num_vars, table_vars, tr);
   LH_CATCH
 }
 lh_status lh_hyperplonk_verify(const lh_mkzg_vp* vp, const lh_hp_vparam* hvp, const lh_fr* const* instances,

@@ -86,7 +86,7 @@ static const struct {
     {"sc_pp_fold", &Options::sc_pp_fold, 0, 2},                    {"msm_half_batches", &Options::msm_half_batches, 0, 1},
     {"comm_round", &Options::comm_round, 0, 2},                    {"hyrax_rows", &Options::hyrax_rows, 0, 1},
     {"brakedown_batch_commit", &Options::brakedown_batch_commit, 0, 1}, {"brakedown_staged_open", &Options::brakedown_staged_open, 0, 1},
-    {"brakedown_u32_gather", &Options::brakedown_u32_gather, 0, 1},
+    {"brakedown_u32_gather", &Options::brakedown_u32_gather, 0, 1}, {"logup_fused_leaves", &Options::logup_fused_leaves, 0, 1},
 };
 
 int64_t* Options::find(const char* name) {

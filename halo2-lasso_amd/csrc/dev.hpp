@@ -161,6 +161,8 @@ struct Options {
   int64_t brakedown_staged_open = 0;   // lh_brakedown_batch_open reads the opened columns from the matrix staged on the host
   int64_t brakedown_u32_gather = 1;    // a column commit runs the first encoder stage of its u32 columns from the 4-byte
                                        // entries (kernels_brakedown.hip bd_gather_u32); 0: bd_gather on the loaded message
+  int64_t logup_fused_leaves = 1;      // LogUp-GKR (logup.cpp): the leaves of a side's fractions and the level above them in
+                                       // ONE launch (kernels_logup.hip logup_leaves_up); 0: the leaves, then one frac_up each
   Options();                           // environment defaults (dev.cpp)
   int64_t* find(const char* name);
   static bool in_range(const char* name, int64_t value);  // the range lh_ctx_set_option accepts
@@ -828,6 +830,31 @@ void k_expr_rows(Ctx&, const RowsExpr& e, size_t n, Fr* out);
 // ------------------------------------------------------------------ HyperPlonk witness polys (kernels_plonk.hip)
 // m[j] = #{i : input[i] == table[j]} on the LAST row j holding that value; false if an input is missing
 bool k_lookup_m(Ctx&, const Fr* input, const Fr* table, size_t n, Fr* m_out);
+// the same join with sizes of their own and the counts as the result: counts[r] = how many of the n inputs equal table row r,
+// r < m (among equal rows the LAST takes every count; `counts` holds m + 1 words, the last is scratch); false: an input that
+// is in no row.  Launch record "logup_m", n items
+bool k_logup_multiplicities(Ctx&, const Fr* input, size_t n, const Fr* table, size_t m, uint32_t* counts);
+
+// ------------------------------------------------------------------ LogUp-GKR (kernels_logup.hip)
+constexpr int LOGUP_MAX = 8;  // LH_LOGUP_MAX_LOOKUPS and LH_LOGUP_MAX_WIDTH (include/lasso_hip.h)
+// out[i] = sum_j pows[j] cols[j][i] over `width` (2 .. LOGUP_MAX) columns of n entries; pows[0] is one and is not applied
+void k_logup_compress(Ctx&, const Fr* const* cols, const Fr* pows, size_t width, size_t n, Fr* out);
+// The leaves of `count` fractions of 2^num_vars entries in ONE launch (blockIdx.y = the fraction), and with `up` the level
+// above them (node i from the leaves i and i + half, fractional_sum_check.rs:62-85) in the same pass:
+//   input side (m null):  q = gamma + c,  p == 1: the table `ones` shared by all fractions is filled, the level above is
+//                         (q_l + q_r, q_l q_r) - no table of ones is read
+//   table side:           p = -m (32-bit counts), q = gamma + c, the level above by the general formula
+// Launch record "logup_leaves_up" (up) or "logup_leaves", count * 2^(num_vars - 1) items.
+struct LogupLeaves {
+  const Fr* c[LOGUP_MAX];
+  const uint32_t* m[LOGUP_MAX];
+  Fr* ones;
+  Fr* p[LOGUP_MAX];  // table side
+  Fr* q[LOGUP_MAX];
+  Fr* p_up[LOGUP_MAX];
+  Fr* q_up[LOGUP_MAX];
+};
+void k_logup_leaves(Ctx&, const LogupLeaves&, size_t count, size_t num_vars, bool table_side, bool up, const Fr& gamma);
 void k_lookup_h(Ctx&, const Fr* input, const Fr* table, const Fr* m, const Fr& gamma, size_t n, Fr* h);
 void k_permutation_z(Ctx&, const Fr* const* values, const Fr* const* perms, size_t num_perm, size_t num_chunks,
                      size_t num_vars, const Fr& beta, const Fr& gamma, const uint32_t* d_order, const uint32_t* d_nth,

@@ -15,7 +15,8 @@ namespace lh {
 // reference piop/gkr/fractional_sum_check.rs:89-190
 FracSumCheckResult prove_fractional_sum_check(Ctx& c, size_t B, size_t num_vars, const HFr* const* claimed_p_0s,
                                               const HFr* const* claimed_q_0s, const Fr* const* d_ps,
-                                              const Fr* const* d_qs, Transcript& tr) {
+                                              const Fr* const* d_qs, Transcript& tr, const Fr* const* d_p_up,
+                                              const Fr* const* d_q_up) {
   LH_REQUIRE(B != 0, LH_ERR_ARG, "fractional sum-check: num_batching == 0");  // :103 assert
   LH_REQUIRE(num_vars >= 1, LH_ERR_ARG, "fractional sum-check: num_vars == 0");
   LH_REQUIRE(3 * B <= LH_SC_MAX_TERMS && 4 * B + 1 <= (size_t)SC_MAX_TABLES, LH_ERR_ARG,
@@ -29,6 +30,14 @@ FracSumCheckResult prove_fractional_sum_check(Ctx& c, size_t B, size_t num_vars,
   }
   for (size_t h = 1; h < num_vars; h++) {
     size_t half = (size_t)1 << (num_vars - h);
+    if (h == 1 && d_p_up && d_q_up) {  // (the caller made this level together with the leaves)
+      for (size_t b = 0; b < B; b++) {
+        LH_REQUIRE(d_p_up[b] && d_q_up[b], LH_ERR_ARG, "fractional sum-check: null level above the leaves");
+        lp[1].push_back(d_p_up[b]);
+        lq[1].push_back(d_q_up[b]);
+      }
+      continue;
+    }
     for (size_t b = 0; b < B; b++) {
       Fr* vp = c.arena.alloc_n<Fr>(half);
       Fr* vq = c.arena.alloc_n<Fr>(half);

@@ -269,9 +269,12 @@ void eq_xy_shard(Ctx&, const Shard&, const HFr* y, size_t num_vars, size_t first
 struct FracSumCheckResult {
   std::vector<HFr> p_xs, q_xs, x;
 };
+// d_p_up / d_q_up (optional, both or neither): per fraction the level above the leaves (2^(num_vars-1) nodes, Layer::up of the
+// leaves) when the caller made it together with the leaves; ignored for num_vars == 1, which has no such level
 FracSumCheckResult prove_fractional_sum_check(Ctx&, size_t num_batching, size_t num_vars,
                                               const HFr* const* claimed_p_0s, const HFr* const* claimed_q_0s,
-                                              const Fr* const* d_ps, const Fr* const* d_qs, Transcript& tr);
+                                              const Fr* const* d_ps, const Fr* const* d_qs, Transcript& tr,
+                                              const Fr* const* d_p_up = nullptr, const Fr* const* d_q_up = nullptr);
 struct GrandProductResult {
   std::vector<HFr> roots, claims;
   std::vector<std::vector<HFr>> points;
@@ -786,6 +789,14 @@ size_t lasso_batch_check(const lh_lasso_table* const* tables, size_t num_tables,
 void lasso_prove_batch(Ctx&, const Pcs&, const lh_lasso_table* const* tables, size_t num_tables, size_t num_vars,
                        const uint32_t* const* const* d_dims, Transcript& tr);
 
+// ------------------------------------------------------------------ LogUp-GKR (logup.cpp; tests/logup_gkr_ref.py)
+// the limits that need no device (shared with the verifier, which has no input columns): returns nv = max(n, l)
+size_t logup_check(const lh_logup_lookup* lookups, size_t num_lookups, size_t num_vars, size_t table_vars, bool prover);
+void logup_gkr_prove(Ctx&, const Pcs&, const lh_logup_lookup* lookups, size_t num_lookups, size_t num_vars, size_t table_vars,
+                     Transcript& tr);
+void logup_gkr_verify(const PcsVerifier& pcs, const lh_logup_lookup* lookups, size_t num_lookups, size_t num_vars,
+                      size_t table_vars, Transcript& tr);
+
 // ------------------------------------------------------------------ verifiers (verifier.cpp; host only)
 HFr interpolate_evals(const std::vector<HFr>& evals, const HFr& x);  // barycentric over 0..d (arithmetic.rs:108-136)
 HFr horner(const std::vector<HFr>& coeffs, const HFr& x);
@@ -804,6 +815,13 @@ PcsVerifier mkzg_verifier(const VerifierParams&);
 // -> (final claim, challenges)
 std::pair<HFr, std::vector<HFr>> sum_check_verify(int prover_kind, size_t num_vars, size_t degree, const HFr& sum,
                                                   Transcript& tr);
+// verify_fractional_sum_check (fractional_sum_check.rs:193-270; host only): claimed_*[b] null = the root is read.  The
+// roots come back too: whoever argues with fractions checks a relation between them.  A mismatch: LH_ERR_INVALID_SUMCHECK
+struct FracVerifyResult {
+  std::vector<HFr> p_0s, q_0s, p_xs, q_xs, x;
+};
+FracVerifyResult verify_fractional_sum_check(size_t num_batching, size_t num_vars, const HFr* const* claimed_p_0s,
+                                             const HFr* const* claimed_q_0s, Transcript& tr);
 void lasso_verify(const PcsVerifier& pcs, const lh_lasso_table& table, size_t num_vars, Transcript& tr);
 void lasso_verify_batch(const PcsVerifier& pcs, const lh_lasso_table* const* tables, size_t num_tables, size_t num_vars,
                         Transcript& tr);

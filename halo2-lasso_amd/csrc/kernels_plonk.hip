@@ -31,12 +31,12 @@ __global__ void m_keys_kernel(const Fr* __restrict__ table, size_t n, uint64_t* 
   }
 }
 __global__ void m_probe_kernel(const Fr* __restrict__ input, const Fr* __restrict__ table,
-                               const uint64_t* __restrict__ skeys, const uint32_t* __restrict__ sidx, size_t n,
+                               const uint64_t* __restrict__ skeys, const uint32_t* __restrict__ sidx, size_t n, size_t m,
                                uint32_t* __restrict__ counts, uint32_t* __restrict__ missing) {
-  GSTRIDE(i, n) {
+  GSTRIDE(i, n) {  // n probes into the m sorted keys
     const Fr v = input[i];
     const uint64_t k = key_of(v);
-    size_t lo = 0, hi = n;
+    size_t lo = 0, hi = m;
     while (lo < hi) {  // upper bound: first key > k
       size_t mid = (lo + hi) >> 1;
       if (skeys[mid] <= k) lo = mid + 1;
@@ -68,21 +68,34 @@ __global__ void m_probe_kernel(const Fr* __restrict__ input, const Fr* __restric
   }
 }
 
+// n inputs joined against the m table rows: counts[r], r < m, and counts[m] = the inputs found in no row (m + 1 words, zeroed here)
+static void lookup_counts(Ctx& c, const Fr* input, size_t n, const Fr* table, size_t m, uint32_t* counts) {
+  ArenaScope scope(c.arena);
+  uint64_t* keys = c.arena.alloc_n<uint64_t>(m);
+  uint64_t* skeys = c.arena.alloc_n<uint64_t>(m);
+  uint32_t* idx = c.arena.alloc_n<uint32_t>(m);
+  uint32_t* sidx = c.arena.alloc_n<uint32_t>(m);
+  LH_HIP(hipMemsetAsync(counts, 0, (m + 1) * sizeof(uint32_t), c.stream));
+  hipLaunchKernelGGL(m_keys_kernel, grid_for(m), 256, 0, c.stream, table, m, keys, idx);
+  sort_pairs_u64(c, keys, skeys, idx, sidx, m, 64);  // stable: equal values keep their row order (prover.rs:151)
+  hipLaunchKernelGGL(m_probe_kernel, grid_for(n), 256, 0, c.stream, input, table, skeys, sidx, n, m, counts, counts + m);
+}
 bool k_lookup_m(Ctx& c, const Fr* input, const Fr* table, size_t n, Fr* m_out) {
   ProfScope ps(c, "lookup_m", (64.0 + 32.0 + 24.0 * 4) * n, 0.0, (double)n);
   ArenaScope scope(c.arena);
-  uint64_t* keys = c.arena.alloc_n<uint64_t>(n);
-  uint64_t* skeys = c.arena.alloc_n<uint64_t>(n);
-  uint32_t* idx = c.arena.alloc_n<uint32_t>(n);
-  uint32_t* sidx = c.arena.alloc_n<uint32_t>(n);
   uint32_t* counts = c.arena.alloc_n<uint32_t>(n + 1);
-  LH_HIP(hipMemsetAsync(counts, 0, (n + 1) * sizeof(uint32_t), c.stream));
-  hipLaunchKernelGGL(m_keys_kernel, grid_for(n), 256, 0, c.stream, table, n, keys, idx);
-  sort_pairs_u64(c, keys, skeys, idx, sidx, n, 64);  // stable: equal values keep their row order (prover.rs:151)
-  hipLaunchKernelGGL(m_probe_kernel, grid_for(n), 256, 0, c.stream, input, table, skeys, sidx, n, counts, counts + n);
+  lookup_counts(c, input, n, table, n, counts);
   k_fr_from_u32(c, counts, n, m_out);
   uint32_t missing = 0;
   c.d2h(&missing, counts + n, 4);
+  return missing == 0;
+}
+// the counts themselves, for sizes of their own (LogUp-GKR, logup.cpp): `counts` holds m + 1 words, word m is scratch
+bool k_logup_multiplicities(Ctx& c, const Fr* input, size_t n, const Fr* table, size_t m, uint32_t* counts) {
+  ProfScope ps(c, "logup_m", 32.0 * n + (32.0 + 24.0 * 4 + 4.0) * m, 0.0, (double)n);
+  lookup_counts(c, input, n, table, m, counts);
+  uint32_t missing = 0;
+  c.d2h(&missing, counts + m, 4);
   return missing == 0;
 }
 

@@ -1,0 +1,249 @@
+// LogUp-GKR: a stand-alone lookup argument for unstructured tables looked up by value.  The LogUp identity
+//   sum_i 1 / (gamma + f[i]) = sum_r m[r] / (gamma + t[r])
+// is proved by two fractional sum-checks (gkr.cpp prove_fractional_sum_check; piop/gkr/fractional_sum_check.rs and the paper
+// it cites) instead of a committed helper column: only the inputs and the small-valued multiplicities are committed.
+// The reference holds no such argument; protocol and transcript schedule are specified in tests/logup_gkr_ref.py and
+// reproduced here byte for byte.  Written against the PCS description (host.hpp Pcs / PcsVerifier), as lasso_prove_batch is.
+#include <algorithm>
+#include "host.hpp"
+
+namespace lh {
+
+size_t logup_check(const lh_logup_lookup* lookups, size_t L, size_t n, size_t l, bool prover) {
+  LH_REQUIRE(lookups != nullptr, LH_ERR_ARG, "null argument: lookups");
+  LH_REQUIRE(L >= 1 && L <= (size_t)LH_LOGUP_MAX_LOOKUPS, LH_ERR_ARG,
+             "logup: 1 to " + std::to_string(LH_LOGUP_MAX_LOOKUPS) + " lookups");
+  LH_REQUIRE(n >= 1 && n < 31, LH_ERR_ARG, "logup: num_vars out of range (1 to 30)");
+  LH_REQUIRE(l >= 1 && l <= (size_t)LH_LOGUP_MAX_TABLE_VARS, LH_ERR_ARG,
+             "logup: table_vars out of range (1 to " + std::to_string(LH_LOGUP_MAX_TABLE_VARS) + ")");
+  size_t total = 0;
+  for (size_t k = 0; k < L; k++) {
+    const lh_logup_lookup& lk = lookups[k];
+    LH_REQUIRE(lk.width >= 1 && lk.width <= (uint32_t)LH_LOGUP_MAX_WIDTH, LH_ERR_ARG,
+               "logup: lookup " + std::to_string(k) + ": width out of range (1 to " + std::to_string(LH_LOGUP_MAX_WIDTH) + ")");
+    LH_REQUIRE(lk.table != nullptr, LH_ERR_ARG, "null argument: table of lookup " + std::to_string(k));
+    LH_REQUIRE(!prover || lk.d_inputs != nullptr, LH_ERR_ARG, "null argument: d_inputs of lookup " + std::to_string(k));
+    for (uint32_t j = 0; j < lk.width; j++) {
+      LH_REQUIRE(lk.table[j] != nullptr, LH_ERR_ARG, "null argument: a table column of lookup " + std::to_string(k));
+      LH_REQUIRE(!prover || lk.d_inputs[j] != nullptr, LH_ERR_ARG, "null argument: an input column of lookup " + std::to_string(k));
+    }
+    total += lk.width;
+  }
+  // one identity mask (a field element read as 63 bits) frames the input commitments
+  LH_REQUIRE(total <= 63, LH_ERR_ARG, "logup: more than 63 input columns in all (one identity mask)");
+  return std::max(n, l);
+}
+
+static void logup_header(Transcript& tr, const lh_logup_lookup* lookups, size_t L, size_t n, size_t l) {
+  for (size_t v : {L, n, l}) tr.common_field_element(HFr::from_u64(v));
+  for (size_t k = 0; k < L; k++) tr.common_field_element(HFr::from_u64(lookups[k].width));
+}
+// beta^0 .. beta^(LH_LOGUP_MAX_WIDTH - 1)
+static std::vector<HFr> logup_powers(const HFr& beta) {
+  std::vector<HFr> pw(LH_LOGUP_MAX_WIDTH, HFr::one());
+  for (size_t j = 1; j < pw.size(); j++) pw[j] = pw[j - 1] * beta;
+  return pw;
+}
+// the opening list shared by prover and verifier: input column i at point 0 (x_n), m_k (poly W + k) at point 1 (x_l)
+static std::vector<lh_evaluation> logup_evaluations(const std::vector<HFr>& f_e, const std::vector<HFr>& m_e) {
+  std::vector<lh_evaluation> evs(f_e.size() + m_e.size());
+  for (size_t i = 0; i < evs.size(); i++) {
+    memset(&evs[i], 0, sizeof(lh_evaluation));
+    evs[i].poly = (uint32_t)i, evs[i].point = i < f_e.size() ? 0u : 1u;
+    memcpy(&evs[i].value, i < f_e.size() ? &f_e[i] : &m_e[i - f_e.size()], 32);
+  }
+  return evs;
+}
+
+void logup_gkr_prove(Ctx& c, const Pcs& pcs, const lh_logup_lookup* lookups, size_t L, size_t n, size_t l, Transcript& tr) {
+  const size_t nv = logup_check(lookups, L, n, l, true);
+  LH_REQUIRE(!Shard(c).on && !(c.has_comm && c.comm.size > 1), LH_ERR_ARG,
+             "logup: sharded proofs are not supported (the ctx is inside a sharded prove or has a communicator of several ranks)");
+  LH_REQUIRE(pcs.chunks == 1 && pcs.batch_commit && pcs.commit_bases && !pcs.commit_and_write && !pcs.commit_columns_and_write,
+             LH_ERR_ARG, "logup: implemented for schemes whose commitment is one point over bases");
+  if (nv > pcs.max_vars) throw Error(LH_ERR_INVALID_PCS_PARAM, "Too many variates of poly to commit");
+  const size_t N = (size_t)1 << n, M = (size_t)1 << l, NV = (size_t)1 << nv;
+  open_precommit_cancel(c);
+  ArenaScope scope(c.arena);
+  EqHalfScope eq_scope(c);  // (the opening shares eq tables of its points: arena memory of this scope)
+  size_t W = 0;
+  std::vector<size_t> first(L);  // the first input column of every lookup
+  for (size_t k = 0; k < L; k++) first[k] = W, W += lookups[k].width;
+
+  // ---- 0/1: header, the input columns' commitments (each zero-padded to nv variables: the table the opening is handed too)
+  logup_header(tr, lookups, L, n, l);
+  std::vector<const Fr*> f(W), polys(W + L, nullptr);
+  for (size_t k = 0; k < L; k++)
+    for (uint32_t j = 0; j < lookups[k].width; j++) {
+      const Fr* col = (const Fr*)lookups[k].d_inputs[j];
+      f[first[k] + j] = polys[first[k] + j] = col;
+      if (N < NV) {
+        Fr* pad = c.arena.alloc_n<Fr>(NV);
+        LH_HIP(hipMemcpyAsync(pad, col, N * sizeof(Fr), hipMemcpyDeviceToDevice, c.stream));
+        LH_HIP(hipMemsetAsync(pad + N, 0, (NV - N) * sizeof(Fr), c.stream));
+        polys[first[k] + j] = pad;
+      }
+    }
+  lasso_write_commitments(tr, pcs.batch_commit(polys.data(), W, nv));
+
+  // ---- 2: beta, the compressed columns cf_k (device inputs) and ct_k (the public table, uploaded)
+  const std::vector<HFr> pw = logup_powers(tr.squeeze_challenge());
+  std::vector<const Fr*> cf(L), ct(L);
+  for (size_t k = 0; k < L; k++) {
+    const size_t w = lookups[k].width;
+    std::vector<const Fr*> t(w);
+    for (size_t j = 0; j < w; j++) {
+      Fr* d = c.arena.alloc_n<Fr>(M);
+      LH_HIP(hipMemcpyAsync(d, lookups[k].table[j], M * sizeof(Fr), hipMemcpyHostToDevice, c.stream));
+      t[j] = d;
+    }
+    cf[k] = f[first[k]], ct[k] = t[0];  // (w = 1: the column itself, nothing launched)
+    if (w > 1) {
+      Fr* dcf = c.arena.alloc_n<Fr>(N);
+      Fr* dct = c.arena.alloc_n<Fr>(M);
+      k_logup_compress(c, f.data() + first[k], (const Fr*)pw.data(), w, N, dcf);
+      k_logup_compress(c, t.data(), (const Fr*)pw.data(), w, M, dct);
+      cf[k] = dcf, ct[k] = dct;
+    }
+  }
+
+  // ---- 3: multiplicities (prover.rs:145-192 lookup_m_poly: the LAST of equal rows takes every count) as u32 columns, committed
+  // like Lasso's counters: against the bases of level nv, widths promised from the OR of the counts
+  std::vector<uint32_t*> m(L);
+  for (size_t k = 0; k < L; k++) {
+    m[k] = c.arena.alloc_n<uint32_t>(M + 1);
+    if (!k_logup_multiplicities(c, cf[k], N, ct[k], M, m[k])) throw Error(LH_ERR_INVALID_SNARK, "Invalid lookup input");
+  }
+  std::vector<uint32_t> ors(L, 0);
+  {
+    std::vector<const uint32_t*> cols(m.begin(), m.end());
+    k_or_u32(c, cols.data(), L, M, ors.data());
+    std::vector<MsmJob> jobs;
+    for (size_t k = 0; k < L; k++) {
+      jobs.push_back(MsmJob{m[k], true, pcs.commit_bases(nv), M});
+      jobs.back().known_bits = std::max(bit_length(ors[k]), 1u);
+    }
+    std::vector<HG1> comms(L);
+    msm_batch(c, jobs.data(), jobs.size(), (G1Affine*)comms.data());
+    lasso_write_commitments(tr, comms);
+  }
+
+  // ---- 4-6: gamma, the leaves of both sides (and, fused, the level above them), the two fractional sum-checks
+  const HFr gamma = tr.squeeze_challenge();
+  const bool fused = c.opt.logup_fused_leaves != 0;
+  auto side = [&](bool table_side, size_t vars, const std::vector<const Fr*>& cols) {
+    const size_t len = (size_t)1 << vars;
+    const bool up = fused && vars >= 2;  // (one variable: the leaves are the top layer)
+    LogupLeaves a;
+    memset(&a, 0, sizeof(a));
+    std::vector<const Fr*> ps(L), qs(L), p_up(L), q_up(L);
+    if (!table_side) a.ones = c.arena.alloc_n<Fr>(len);
+    for (size_t k = 0; k < L; k++) {
+      a.c[k] = cols[k];
+      a.q[k] = c.arena.alloc_n<Fr>(len);
+      if (table_side) a.m[k] = m[k], a.p[k] = c.arena.alloc_n<Fr>(len);
+      if (up) a.p_up[k] = c.arena.alloc_n<Fr>(len / 2), a.q_up[k] = c.arena.alloc_n<Fr>(len / 2);
+      ps[k] = table_side ? a.p[k] : a.ones, qs[k] = a.q[k], p_up[k] = a.p_up[k], q_up[k] = a.q_up[k];
+    }
+    k_logup_leaves(c, a, L, vars, table_side, up, dev(gamma));
+    return prove_fractional_sum_check(c, L, vars, nullptr, nullptr, ps.data(), qs.data(), tr, up ? p_up.data() : nullptr,
+                                      up ? q_up.data() : nullptr);
+  };
+  const std::vector<HFr> x_n = side(false, n, cf).x;
+  const std::vector<HFr> x_l = side(true, l, ct).x;
+
+  // ---- 7: f_kj(x_n) lookup-major, then m_k(x_l)
+  const std::vector<HFr> f_e = evaluate_polys(c, f.data(), W, n, x_n.data());
+  std::vector<HFr> m_e(L);
+  {
+    ArenaScope inner(c.arena);
+    Fr* eq = c.arena.alloc_n<Fr>(M);
+    k_eq_xy(c, (const Fr*)x_l.data(), l, eq);
+    std::vector<const uint32_t*> cols(m.begin(), m.end());
+    k_inner_products_small(c, cols.data(), L, eq, M, (Fr*)m_e.data());
+  }
+  tr.write_field_elements(f_e);
+  tr.write_field_elements(m_e);
+
+  // ---- 8: ONE batch opening over nv variables; the multiplicities go as their 32-bit columns
+  std::vector<SmallPoly> small(W + L);
+  for (size_t k = 0; k < L; k++) small[W + k] = SmallPoly{m[k], M, std::max(bit_length(ors[k]), 1u)};
+  std::vector<HFr> points;
+  lasso_append_points(points, {&x_n, &x_l}, nv);
+  const std::vector<lh_evaluation> evs = logup_evaluations(f_e, m_e);
+  pcs.batch_open(nv, polys.data(), polys.size(), points.data(), 2, evs.data(), evs.size(), tr, small.data());
+}
+
+// sum_j beta^j t~_j(x): the multilinear extension of the compressed table column, one fold over its 2^l rows (variable i =
+// index bit i); the first fold reads the w columns
+static HFr logup_table_eval(const lh_logup_lookup& lk, size_t l, const std::vector<HFr>& pw, const std::vector<HFr>& x) {
+  const size_t M = (size_t)1 << l;
+  auto row = [&](size_t r) {
+    HFr acc = ((const HFr*)lk.table[0])[r];
+    for (uint32_t j = 1; j < lk.width; j++) acc += pw[j] * ((const HFr*)lk.table[j])[r];
+    return acc;
+  };
+  std::vector<HFr> cur(M / 2);
+  const size_t chunks = std::min<size_t>(cur.size(), 64);  // (the pool hands out items one by one)
+  host_parallel_for(chunks, [&](size_t ch) {
+    for (size_t k = ch * cur.size() / chunks; k < (ch + 1) * cur.size() / chunks; k++) {
+      const HFr lo = row(2 * k), hi = row(2 * k + 1);
+      cur[k] = lo + x[0] * (hi - lo);
+    }
+  });
+  for (size_t i = 1; i < l; i++) {
+    const size_t half = cur.size() / 2;
+    for (size_t k = 0; k < half; k++) cur[k] = cur[2 * k] + x[i] * (cur[2 * k + 1] - cur[2 * k]);
+    cur.resize(half);
+  }
+  return cur[0];
+}
+
+static void logup_gkr_verify_checked(const PcsVerifier& pcs, const lh_logup_lookup* lookups, size_t L, size_t n, size_t l, size_t nv,
+                                     Transcript& tr) {
+  size_t W = 0;
+  for (size_t k = 0; k < L; k++) W += lookups[k].width;
+  logup_header(tr, lookups, L, n, l);
+  std::vector<HG1> comms = lasso_read_commitments(tr, W);
+  const std::vector<HFr> pw = logup_powers(tr.squeeze_challenge());
+  {
+    const std::vector<HG1> block = lasso_read_commitments(tr, L);
+    comms.insert(comms.end(), block.begin(), block.end());
+  }
+  const HFr gamma = tr.squeeze_challenge();
+  const FracVerifyResult in = verify_fractional_sum_check(L, n, nullptr, nullptr, tr);
+  const FracVerifyResult tb = verify_fractional_sum_check(L, l, nullptr, nullptr, tr);
+  // the LogUp identity on the roots: P_f / Q_f + P_t / Q_t = 0 with both denominators non-zero
+  for (size_t k = 0; k < L; k++)
+    if (in.q_0s[k].is_zero() || tb.q_0s[k].is_zero() || !(in.p_0s[k] * tb.q_0s[k] + tb.p_0s[k] * in.q_0s[k]).is_zero())
+      throw Error(LH_ERR_INVALID_SNARK, "lookup " + std::to_string(k) + ": the fractions do not sum to zero");
+  const std::vector<HFr> f_e = tr.read_field_elements(W), m_e = tr.read_field_elements(L);
+  size_t at = 0;
+  for (size_t k = 0; k < L; k++) {
+    HFr q_in = gamma;
+    for (uint32_t j = 0; j < lookups[k].width; j++) q_in += pw[j] * f_e[at + j];
+    at += lookups[k].width;
+    const HFr q_tab = gamma + logup_table_eval(lookups[k], l, pw, tb.x);
+    if (in.p_xs[k] != HFr::one() || in.q_xs[k] != q_in || tb.p_xs[k] != HFr::zero() - m_e[k] || tb.q_xs[k] != q_tab)
+      throw Error(LH_ERR_INVALID_SNARK, "lookup " + std::to_string(k) + ": leaf claim mismatch");
+  }
+  std::vector<HFr> points;
+  lasso_append_points(points, {&in.x, &tb.x}, nv);
+  const std::vector<lh_evaluation> evs = logup_evaluations(f_e, m_e);
+  pcs.batch_verify(nv, comms.data(), comms.size(), points.data(), 2, evs.data(), evs.size(), tr);
+}
+// A proof that does not verify is LH_ERR_INVALID_SNARK whichever piece found it out; what is wrong with the call keeps its code
+void logup_gkr_verify(const PcsVerifier& pcs, const lh_logup_lookup* lookups, size_t L, size_t n, size_t l, Transcript& tr) {
+  const size_t nv = logup_check(lookups, L, n, l, false);
+  LH_REQUIRE(pcs.chunks == 1 && !pcs.read_commitments, LH_ERR_ARG, "logup: implemented for commitments of one point");
+  try {
+    logup_gkr_verify_checked(pcs, lookups, L, n, l, nv, tr);
+  } catch (const Error& e) {
+    if (e.code == LH_ERR_INVALID_SUMCHECK || e.code == LH_ERR_INVALID_PCS_OPEN || e.code == LH_ERR_TRANSCRIPT ||
+        e.code == LH_ERR_SERIALIZATION)
+      throw Error(LH_ERR_INVALID_SNARK, "logup: " + e.msg);
+    throw;
+  }
+}
+
+}  // namespace lh

@@ -946,6 +946,71 @@ static std::vector<HFr> verify_grand_product(const std::vector<size_t>& depth, T
   return roots;
 }
 
+// fractional_sum_check.rs:193-270 (oracle/pyref/gkr.py verify_fractional_sum_check), the roots returned with the rest
+FracVerifyResult verify_fractional_sum_check(size_t B, size_t num_vars, const HFr* const* claimed_p_0s,
+                                             const HFr* const* claimed_q_0s, Transcript& tr) {
+  LH_REQUIRE(B != 0, LH_ERR_ARG, "fractional sum-check: num_batching == 0");
+  LH_REQUIRE(num_vars >= 1 && num_vars < 64, LH_ERR_ARG, "fractional sum-check: num_vars out of range");
+  LH_REQUIRE(3 * B <= LH_SC_MAX_TERMS, LH_ERR_ARG, "fractional sum-check: more fractions than the prover's layer sum-check takes");
+  FracVerifyResult res;
+  for (int side = 0; side < 2; side++) {  // :207-222: Some -> common, None -> read
+    const HFr* const* claimed = side ? claimed_q_0s : claimed_p_0s;
+    std::vector<HFr>& roots = side ? res.q_0s : res.p_0s;
+    for (size_t b = 0; b < B; b++) {
+      if (claimed && claimed[b]) {
+        tr.common_field_element(*claimed[b]);
+        roots.push_back(*claimed[b]);
+      } else {
+        roots.push_back(tr.read_field_element());
+      }
+    }
+  }
+  std::vector<HFr> claimed_p = res.p_0s, claimed_q = res.q_0s, y;
+  const char* const mismatch = "Unmatched between sum_check output and query evaluation";
+  for (size_t nv = 0; nv < num_vars; nv++) {
+    std::vector<HFr> x, evals;
+    if (nv == 0) {
+      evals = tr.read_field_elements(4 * B);
+      for (size_t b = 0; b < B; b++) {
+        const HFr &p_l = evals[4 * b], &p_r = evals[4 * b + 1], &q_l = evals[4 * b + 2], &q_r = evals[4 * b + 3];
+        if (claimed_p[b] != p_l * q_r + p_r * q_l || claimed_q[b] != q_l * q_r) throw Error(LH_ERR_INVALID_SUMCHECK, mismatch);
+      }
+    } else {
+      const HFr gamma = tr.squeeze_challenge();
+      HFr claim = HFr::zero(), power = HFr::one();
+      for (size_t b = 0; b < B; b++) {  // sum_check_claim (:283-288)
+        claim += claimed_p[b] * power;
+        power *= gamma;
+        claim += claimed_q[b] * power;
+        power *= gamma;
+      }
+      auto sc = sum_check_verify(LH_SC_EVALUATIONS, nv, 3, claim, tr);
+      x = sc.second;
+      evals = tr.read_field_elements(4 * B);
+      HFr acc = HFr::zero();  // sum_check_expression (:272-281) at the evaluations
+      power = HFr::one();
+      for (size_t b = 0; b < B; b++) {
+        const HFr &p_l = evals[4 * b], &p_r = evals[4 * b + 1], &q_l = evals[4 * b + 2], &q_r = evals[4 * b + 3];
+        acc += (p_l * q_r + p_r * q_l) * power;
+        power *= gamma;
+        acc += q_l * q_r * power;
+        power *= gamma;
+      }
+      if (sc.first != acc * host_eq_xy_eval(x.data(), y.data(), nv)) throw Error(LH_ERR_INVALID_SUMCHECK, mismatch);
+    }
+    const HFr mu = tr.squeeze_challenge();
+    for (size_t b = 0; b < B; b++) {  // layer_down_claim (:290-296)
+      const HFr &p_l = evals[4 * b], &p_r = evals[4 * b + 1], &q_l = evals[4 * b + 2], &q_r = evals[4 * b + 3];
+      claimed_p[b] = p_l + mu * (p_r - p_l);
+      claimed_q[b] = q_l + mu * (q_r - q_l);
+    }
+    x.push_back(mu);
+    y = x;
+  }
+  res.p_xs = claimed_p, res.q_xs = claimed_q, res.x = y;
+  return res;
+}
+
 static HFr subtable_mle_eval(uint32_t kind, const std::vector<HFr>& point) {  // lasso.py:55-72
   if (subtable_is_custom(kind)) {
     // a registered subtable: the dense MLE of its entries, one fold over 2^l values (variable i = index bit i); the fold of

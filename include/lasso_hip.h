@@ -295,6 +295,40 @@ lh_status lh_lasso_prove_batch(lh_ctx*, const lh_srs*, const lh_lasso_table* con
                                const uint32_t* const* const* d_dims, lh_transcript* t);
 /* (lh_lasso_verify_batch: with the verifiers below) */
 
+/* ---------------------------------------------------------------- a''': LogUp-GKR, a lookup argument for unstructured tables
+ * Lasso serves tables that decompose into subtables read by index.  This argument serves the others: a table whose rows
+ * are arbitrary field elements, or tuples of them, looked up BY VALUE (a ROM of constants, an opcode / operand / result
+ * relation, a round-constant schedule).  It proves the LogUp identity
+ *     sum_i 1 / (gamma + f[i])  =  sum_r m[r] / (gamma + t[r])
+ * with two fractional sum-checks (piop/gkr/fractional_sum_check.rs, the paper it cites) and commits only the inputs and the
+ * small-valued multiplicities m - no helper column.  The protocol is specified in tests/logup_gkr_ref.py.
+ *
+ * num_lookups lookups share num_vars (2^num_vars input rows each) and table_vars (2^table_vars table rows each; a shorter
+ * table is padded by repeating a row - duplicates are legal, the LAST of equal rows takes every count).  Lookup k:
+ *   width     w_k columns: a row is a tuple of w_k field elements, compressed as sum_j beta^j column_j
+ *   d_inputs  w_k DEVICE columns of 2^num_vars Montgomery lh_fr; the verifier ignores them: NULL allowed there
+ *   table     w_k HOST columns of 2^table_vars Montgomery lh_fr, the same values for prover and verifier
+ * The table is part of the statement, like the entries of a registered subtable: it is NOT absorbed into the transcript.
+ * Every committed poly is zero-padded to nv = max(num_vars, table_vars) variables.
+ * Limits (LH_ERR_ARG with a message, checked on entry):
+ *   1 <= num_lookups <= LH_LOGUP_MAX_LOOKUPS, 1 <= width <= LH_LOGUP_MAX_WIDTH   one launch per side, columns in the arguments
+ *   sum of widths <= 63                    one identity mask frames the input commitments (another the multiplicities')
+ *   1 <= num_vars < 31, 1 <= table_vars <= LH_LOGUP_MAX_TABLE_VARS   the verifier's table evaluation is linear in the table
+ *   no NULL lookup, column or list; not on a ctx inside a sharded prove, nor on one with a communicator of several ranks
+ * LH_ERR_INVALID_PCS_PARAM when nv exceeds the SRS; LH_ERR_INVALID_SNARK "Invalid lookup input" when an input row is in
+ * no table row (the ctx stays usable).  Route option logup_fused_leaves below. */
+#define LH_LOGUP_MAX_LOOKUPS 8
+#define LH_LOGUP_MAX_WIDTH 8
+#define LH_LOGUP_MAX_TABLE_VARS 24
+typedef struct lh_logup_lookup {
+  uint32_t width;
+  const lh_fr* const* d_inputs; /* device */
+  const lh_fr* const* table;    /* host */
+} lh_logup_lookup;
+lh_status lh_logup_gkr_prove(lh_ctx*, const lh_srs*, const lh_logup_lookup* lookups, size_t num_lookups, size_t num_vars,
+                             size_t table_vars, lh_transcript* t);
+/* (lh_logup_gkr_verify, lh_gkr_fractional_verify: with the verifiers below) */
+
 /* per-phase wall-clock of the last lh_lasso_prove on this ctx, milliseconds:
  * [witness, commit, surge, leaves+trees, gkr, evals, open_n, open_l, total] */
 #define LH_LASSO_NUM_PHASES 9
@@ -358,6 +392,9 @@ lh_status lh_lasso_last_timing(lh_ctx*, double* out_ms);
  *                             encoder stage of its u32 columns from the 4-byte entries themselves (kernel bd_gather_u32: 256 x
  *                             32-bit products, a group's sum unreduced, one reduction per output); 0: the generic bd_gather
  *                             on the message as loaded in Montgomery form.  Rows, trees and roots are bit-identical.
+ *   logup_fused_leaves   1    lh_logup_gkr_prove makes the leaves of a side's fractions and the level above them in ONE launch
+ *                             (csrc/kernels_logup.hip logup_leaves_up: the input side never reads a table of ones); 0: the
+ *                             leaves in one launch, then one frac_up launch per fraction
  *   comm_round           0    how the partial sums of a sharded sum-check round are combined over the ranks:
  *                             0 = ncclAllGather of every rank's sums + a one-thread sum-and-publish kernel;
  *                             1 = ONE collective: the round kernel leaves its sums as u64 lanes (32-bit limb | tag << 40),
@@ -586,6 +623,20 @@ lh_status lh_lasso_verify(const lh_mkzg_vp*, const lh_lasso_table*, size_t num_v
  * field element, a proof that ends early) - the message keeps that piece's words */
 lh_status lh_lasso_verify_batch(const lh_mkzg_vp* vp, const lh_lasso_table* const* tables, size_t num_tables, size_t num_vars,
                                 lh_transcript* t);
+/* verify_fractional_sum_check (piop/gkr/fractional_sum_check.rs:193-270), the host verifier of lh_gkr_fractional_prove:
+ * claimed_*[b] NULL (None => the root is read from the proof) or a claim (Some => only hashed).  Outputs, each optional:
+ * the roots p_0s[B], q_0s[B] (read or given - a caller that argues with fractions checks a relation between them), the
+ * final claims p_xs[B], q_xs[B] and the point x[num_vars].  LH_ERR_INVALID_SUMCHECK when a layer does not match;
+ * LH_ERR_ARG for num_batching = 0, num_vars = 0 or more fractions than one layer sum-check takes. */
+lh_status lh_gkr_fractional_verify(size_t num_batching, size_t num_vars, const lh_fr* const* claimed_p_0s,
+                                   const lh_fr* const* claimed_q_0s, lh_transcript* t, lh_fr* out_p_0s, lh_fr* out_q_0s,
+                                   lh_fr* out_p_xs, lh_fr* out_q_xs, lh_fr* out_x);
+/* the verifier of lh_logup_gkr_prove (tests/logup_gkr_ref.py verify; host only): d_inputs of the lookups are ignored and may
+ * be NULL.  The same argument refusals as the prover's that need no device; LH_ERR_INVALID_PCS_PARAM when
+ * max(num_vars, table_vars) exceeds the param; a proof that does not verify is LH_ERR_INVALID_SNARK whichever piece finds
+ * it out.  The tables' multilinear extensions are evaluated here, O(width 2^table_vars) field operations per lookup. */
+lh_status lh_logup_gkr_verify(const lh_mkzg_vp* vp, const lh_logup_lookup* lookups, size_t num_lookups, size_t num_vars,
+                              size_t table_vars, lh_transcript* t);
 typedef struct lh_hp_vparam { /* HyperPlonkVerifierParam (hyperplonk.rs:57-74) */
   size_t num_vars;
   size_t num_instance_polys;
