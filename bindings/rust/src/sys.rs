@@ -73,6 +73,13 @@ pub const LH_LOGUP_MAX_TABLE_VARS: usize = 24;
 // one lookup of lh_logup_gkr_prove: `width` device input columns of 2^num_vars Fr, `width` host table columns of 2^table_vars
 #[repr(C)] #[derive(Clone, Copy)]
 pub struct lh_logup_lookup { pub width: u32, pub d_inputs: *const *const Fr, pub table: *const *const Fr }
+pub const LH_LOGUP_COL_FR: u8 = 0;   // lh_fr[2^num_vars], Montgomery
+pub const LH_LOGUP_COL_U32: u8 = 1;  // uint32_t[2^num_vars], any 32-bit value
+// one lookup of lh_logup_gkr_prove_columns: input column j has the type kinds[j] says (kinds null: every column LH_LOGUP_COL_FR)
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct lh_logup_columns {
+    pub width: u32, pub d_inputs: *const *const c_void, pub kinds: *const u8, pub table: *const *const Fr,
+}
 
 pub const LH_EX_CONSTANT: u32 = 0;
 pub const LH_EX_IDENTITY: u32 = 1;
@@ -296,6 +303,9 @@ extern "C" {
     // LogUp-GKR: lookups by value into unstructured tables (tests/logup_gkr_ref.py); the verifier ignores d_inputs
     pub fn lh_logup_gkr_prove(ctx: *mut lh_ctx, srs: *const lh_srs, lookups: *const lh_logup_lookup, num_lookups: usize,
                               num_vars: usize, table_vars: usize, t: *mut lh_transcript) -> lh_status;
+    // the same proof (same bytes, same verifier) from input columns of which some are uint32_t
+    pub fn lh_logup_gkr_prove_columns(ctx: *mut lh_ctx, srs: *const lh_srs, lookups: *const lh_logup_columns,
+                                      num_lookups: usize, num_vars: usize, table_vars: usize, t: *mut lh_transcript) -> lh_status;
     pub fn lh_logup_gkr_verify(vp: *const lh_mkzg_vp, lookups: *const lh_logup_lookup, num_lookups: usize, num_vars: usize,
                                table_vars: usize, t: *mut lh_transcript) -> lh_status;
     // the host verifier of lh_gkr_fractional_prove; the roots p_0s / q_0s come back with the final claims and the point

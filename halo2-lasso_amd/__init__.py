@@ -1585,9 +1585,22 @@ def lasso_prove_batch(pp, tables, num_vars, dims, transcript):
 
 
 # ------------------------------------------------------------------ LogUp-GKR (include/lasso_hip.h lh_logup_gkr_prove)
+class U32Column:
+    """An input column of a LogUp-GKR lookup held as uint32_t[2^num_vars] in a DeviceBuffer: the same polynomial as the
+    values widened to Fr - and the same proof bytes - committed, compressed, evaluated and opened as a 32-bit column."""
+
+    def __init__(self, buf, num_vars):
+        self.buf, self.num_vars = buf, num_vars
+
+    @property
+    def ptr(self):
+        return self.buf.ptr
+
+
 class LogupLookup:
-    """One lookup of a LogUp-GKR proof: `inputs`, w device columns (MultilinearPolynomial / DeviceBuffer of 2^num_vars Fr;
-    None for a verifier), looked up by value in `table`, w lists of 2^table_vars ints - a row is a tuple of w elements."""
+    """One lookup of a LogUp-GKR proof: `inputs`, w device columns (MultilinearPolynomial / DeviceBuffer of 2^num_vars Fr, or
+    U32Column, in any mix; None for a verifier), looked up by value in `table`, w lists of 2^table_vars ints - a row is a
+    tuple of w elements."""
 
     def __init__(self, inputs, table):
         self.inputs = None if inputs is None else list(inputs)
@@ -1614,8 +1627,8 @@ class LogupLookup:
             raise ArgumentError("logup: expected %d input columns" % self.width)
 
 
-def _logup_list(lookups, num_vars, prover):
-    """-> (lh_logup_lookup array, table_vars, keepalive)"""
+def _logup_list(lookups, num_vars, prover, columns=False):
+    """-> (lh_logup_lookup array, table_vars, keepalive); columns: an lh_logup_columns array, U32Column inputs allowed"""
     if not 1 <= len(lookups) <= _ffi.LH_LOGUP_MAX_LOOKUPS:
         raise ArgumentError("logup: 1 to %d lookups" % _ffi.LH_LOGUP_MAX_LOOKUPS)
     for lk in lookups:
@@ -1627,7 +1640,7 @@ def _logup_list(lookups, num_vars, prover):
         raise ArgumentError("logup: num_vars out of range (1 to 30)")
     if sum(lk.width for lk in lookups) > 63:
         raise ArgumentError("logup: more than 63 input columns in all (one identity mask)")
-    arr, keep = (_ffi.lh_logup_lookup * len(lookups))(), []
+    arr, keep = ((_ffi.lh_logup_columns if columns else _ffi.lh_logup_lookup) * len(lookups))(), []
     for k, lk in enumerate(lookups):
         cols = [_fr_array(col) for col in lk.table]
         tab = (C.POINTER(lh_fr) * lk.width)(*[C.cast(col, C.POINTER(lh_fr)) for col in cols])
@@ -1636,6 +1649,15 @@ def _logup_list(lookups, num_vars, prover):
         if prover:
             if any(getattr(p, "num_vars", num_vars) != num_vars for p in lk.inputs):
                 raise ArgumentError("logup: input columns of 2^num_vars entries")
+            for j, p in enumerate(lk.inputs):
+                if isinstance(p, U32Column) and getattr(p.buf, "nbytes", 4 << num_vars) < 4 << num_vars:
+                    raise ArgumentError("logup: lookup %d, column %d: a u32 column of 2^num_vars entries needs %d bytes"
+                                        % (k, j, 4 << num_vars))
+            if columns:
+                kinds = (C.c_uint8 * lk.width)(*[_ffi.LH_LOGUP_COL_U32 if isinstance(p, U32Column) else _ffi.LH_LOGUP_COL_FR
+                                                 for p in lk.inputs])
+                arr[k].kinds = kinds
+                keep.append(kinds)
             ins = _ptr_array(lk.inputs)
             arr[k].d_inputs = C.cast(ins, C.POINTER(C.c_void_p))
             keep.append(ins)
@@ -1644,13 +1666,16 @@ def _logup_list(lookups, num_vars, prover):
 
 def logup_gkr_prove(pp, lookups, transcript, num_vars=None):
     """LogUp-GKR over multilinear KZG (tests/logup_gkr_ref.py): every input row of every lookup is a row of its table.
-    num_vars: of the input columns (default: the first column's, a MultilinearPolynomial).  Appends the proof."""
+    num_vars: of the input columns (default: the first column's, a MultilinearPolynomial or U32Column).  Inputs that are
+    U32Column go through lh_logup_gkr_prove_columns; the bytes do not depend on the kinds.  Appends the proof."""
     if num_vars is None:
         if not lookups or not lookups[0].inputs or not hasattr(lookups[0].inputs[0], "num_vars"):
             raise ArgumentError("logup: num_vars is needed with raw device buffers")
         num_vars = lookups[0].inputs[0].num_vars
-    arr, table_vars, keep = _logup_list(lookups, num_vars, True)
-    _check(pp.ctx.lib.lh_logup_gkr_prove(pp.ctx.h, pp.h, arr, len(lookups), num_vars, table_vars, transcript.p))
+    columns = any(isinstance(p, U32Column) for lk in lookups for p in (lk.inputs or ()))
+    arr, table_vars, keep = _logup_list(lookups, num_vars, True, columns)
+    prove = pp.ctx.lib.lh_logup_gkr_prove_columns if columns else pp.ctx.lib.lh_logup_gkr_prove
+    _check(prove(pp.ctx.h, pp.h, arr, len(lookups), num_vars, table_vars, transcript.p))
     del keep
 
 

@@ -19,6 +19,7 @@ LH_SUBTABLE_IDENTITY, LH_SUBTABLE_AND, LH_SUBTABLE_XOR, LH_SUBTABLE_OR, LH_SUBTA
 LH_SUBTABLE_CUSTOM_BASE, LH_SUBTABLE_CUSTOM_MAX, LH_SUBTABLE_CUSTOM_MAX_BITS = 0x100, 64, 20  # lh_subtable_register
 LH_LASSO_NUM_PHASES = 9
 LH_LOGUP_MAX_LOOKUPS, LH_LOGUP_MAX_WIDTH, LH_LOGUP_MAX_TABLE_VARS = 8, 8, 24  # lh_logup_gkr_prove
+LH_LOGUP_COL_FR, LH_LOGUP_COL_U32 = 0, 1  # lh_logup_columns.kinds
 LH_BD_COLUMN_FR, LH_BD_COLUMN_U32 = 0, 1
 
 
@@ -57,6 +58,11 @@ class lh_lasso_table(C.Structure):
 
 class lh_logup_lookup(C.Structure):
     _fields_ = [("width", C.c_uint32), ("d_inputs", C.POINTER(C.c_void_p)), ("table", C.POINTER(C.POINTER(lh_fr)))]
+
+
+class lh_logup_columns(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("d_inputs", C.POINTER(C.c_void_p)), ("kinds", C.POINTER(C.c_uint8)),
+                ("table", C.POINTER(C.POINTER(lh_fr)))]
 
 
 class lh_hp_lasso_lookup(C.Structure):
@@ -401,6 +407,7 @@ SIGNATURES["lh_lasso_prove_batch"] = (C.c_int, [_P, _P, C.POINTER(C.POINTER(lh_l
                                                 C.POINTER(C.POINTER(_P)), _T])
 SIGNATURES["lh_lasso_verify_batch"] = (C.c_int, [_P, C.POINTER(C.POINTER(lh_lasso_table)), _SZ, _SZ, _T])
 SIGNATURES["lh_logup_gkr_prove"] = (C.c_int, [_P, _P, C.POINTER(lh_logup_lookup), _SZ, _SZ, _SZ, _T])
+SIGNATURES["lh_logup_gkr_prove_columns"] = (C.c_int, [_P, _P, C.POINTER(lh_logup_columns), _SZ, _SZ, _SZ, _T])
 SIGNATURES["lh_logup_gkr_verify"] = (C.c_int, [_P, C.POINTER(lh_logup_lookup), _SZ, _SZ, _SZ, _T])
 SIGNATURES["lh_gkr_fractional_verify"] = (C.c_int, [_SZ, _SZ, C.POINTER(C.POINTER(lh_fr)), C.POINTER(C.POINTER(lh_fr)), _T,
                                                     C.POINTER(lh_fr), C.POINTER(lh_fr), C.POINTER(lh_fr), C.POINTER(lh_fr),

@@ -697,6 +697,15 @@ lh_status lh_logup_gkr_prove(lh_ctx* ctx, const lh_srs* srs, const lh_logup_look
   logup_gkr_prove(ctx->c, mkzg_pcs(ctx->c, srs->s), lookups, num_lookups, num_vars, table_vars, tr);
   LH_CATCH
 }
+lh_status lh_logup_gkr_prove_columns(lh_ctx* ctx, const lh_srs* srs, const lh_logup_columns* lookups, size_t num_lookups,
+                                     size_t num_vars, size_t table_vars, lh_transcript* t) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(srs);
+  NEED(lookups);
+  Transcript tr(t);
+  logup_gkr_prove_columns(ctx->c, mkzg_pcs(ctx->c, srs->s), lookups, num_lookups, num_vars, table_vars, tr);
+  LH_CATCH
+}
 lh_status lh_lasso_last_timing(lh_ctx* ctx, double* out_ms) {
   LH_TRY NEED_CTX(ctx);
   NEED(out_ms);

@@ -839,6 +839,11 @@ bool k_logup_multiplicities(Ctx&, const Fr* input, size_t n, const Fr* table, si
 constexpr int LOGUP_MAX = 8;  // LH_LOGUP_MAX_LOOKUPS and LH_LOGUP_MAX_WIDTH (include/lasso_hip.h)
 // out[i] = sum_j pows[j] cols[j][i] over `width` (2 .. LOGUP_MAX) columns of n entries; pows[0] is one and is not applied
 void k_logup_compress(Ctx&, const Fr* const* cols, const Fr* pows, size_t width, size_t n, Fr* out);
+// the same sum over `width` (1 .. LOGUP_MAX) columns of which column j is a uint32_t column where u32[j] is set and an Fr
+// column otherwise (at least one u32 column; width 1 widens it): a u32 entry costs 8 multiply-adds into the row's wide
+// accumulator, which is reduced once.  pows[j] are the plain powers (Montgomery): the factor R of wide.cuh is applied here.
+// Launch record "logup_compress_cols", algorithmic bytes sum_j (4 or 32) n + 32 n
+void k_logup_compress_cols(Ctx&, const void* const* cols, const uint8_t* u32, const Fr* pows, size_t width, size_t n, Fr* out);
 // The leaves of `count` fractions of 2^num_vars entries in ONE launch (blockIdx.y = the fraction), and with `up` the level
 // above them (node i from the leaves i and i + half, fractional_sum_check.rs:62-85) in the same pass:
 //   input side (m null):  q = gamma + c,  p == 1: the table `ones` shared by all fractions is filled, the level above is

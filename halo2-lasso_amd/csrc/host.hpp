@@ -794,6 +794,10 @@ void lasso_prove_batch(Ctx&, const Pcs&, const lh_lasso_table* const* tables, si
 size_t logup_check(const lh_logup_lookup* lookups, size_t num_lookups, size_t num_vars, size_t table_vars, bool prover);
 void logup_gkr_prove(Ctx&, const Pcs&, const lh_logup_lookup* lookups, size_t num_lookups, size_t num_vars, size_t table_vars,
                      Transcript& tr);
+// the same prover over columns of either kind (lh_logup_columns: some input columns are uint32_t); the entry above is this one
+// with every kind LH_LOGUP_COL_FR
+void logup_gkr_prove_columns(Ctx&, const Pcs&, const lh_logup_columns* lookups, size_t num_lookups, size_t num_vars,
+                             size_t table_vars, Transcript& tr);
 void logup_gkr_verify(const PcsVerifier& pcs, const lh_logup_lookup* lookups, size_t num_lookups, size_t num_vars,
                       size_t table_vars, Transcript& tr);
 

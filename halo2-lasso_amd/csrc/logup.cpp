@@ -34,7 +34,8 @@ size_t logup_check(const lh_logup_lookup* lookups, size_t L, size_t n, size_t l,
   return std::max(n, l);
 }
 
-static void logup_header(Transcript& tr, const lh_logup_lookup* lookups, size_t L, size_t n, size_t l) {
+template <class Lookup>  // (lh_logup_lookup or lh_logup_columns: the widths)
+static void logup_header(Transcript& tr, const Lookup* lookups, size_t L, size_t n, size_t l) {
   for (size_t v : {L, n, l}) tr.common_field_element(HFr::from_u64(v));
   for (size_t k = 0; k < L; k++) tr.common_field_element(HFr::from_u64(lookups[k].width));
 }
@@ -55,8 +56,34 @@ static std::vector<lh_evaluation> logup_evaluations(const std::vector<HFr>& f_e,
   return evs;
 }
 
+// the limits of the prover over columns of either kind: those of logup_check on the same lists, then the kinds
+static size_t logup_columns_check(const lh_logup_columns* lookups, size_t L, size_t n, size_t l) {
+  LH_REQUIRE(lookups != nullptr, LH_ERR_ARG, "null argument: lookups");
+  std::vector<lh_logup_lookup> plain(LH_LOGUP_MAX_LOOKUPS);  // (a count out of range is logup_check's to refuse)
+  for (size_t k = 0; k < std::min<size_t>(L, plain.size()); k++)
+    plain[k] = lh_logup_lookup{lookups[k].width, (const lh_fr* const*)lookups[k].d_inputs, lookups[k].table};
+  const size_t nv = logup_check(plain.data(), L, n, l, true);
+  for (size_t k = 0; k < L; k++)
+    for (uint32_t j = 0; lookups[k].kinds && j < lookups[k].width; j++)
+      LH_REQUIRE(lookups[k].kinds[j] == LH_LOGUP_COL_FR || lookups[k].kinds[j] == LH_LOGUP_COL_U32, LH_ERR_ARG,
+                 "logup: lookup " + std::to_string(k) + ", column " + std::to_string(j) + ": unknown column kind " +
+                     std::to_string(lookups[k].kinds[j]));
+  return nv;
+}
+
 void logup_gkr_prove(Ctx& c, const Pcs& pcs, const lh_logup_lookup* lookups, size_t L, size_t n, size_t l, Transcript& tr) {
-  const size_t nv = logup_check(lookups, L, n, l, true);
+  logup_check(lookups, L, n, l, true);
+  std::vector<lh_logup_columns> cols(L);
+  for (size_t k = 0; k < L; k++)
+    cols[k] = lh_logup_columns{lookups[k].width, (const void* const*)lookups[k].d_inputs, nullptr, lookups[k].table};
+  logup_gkr_prove_columns(c, pcs, cols.data(), L, n, l, tr);
+}
+
+// One body for both entries; the kind is a property of a column.  A u32 column is committed, compressed, evaluated and opened
+// as the 32-bit column it is (never widened, never padded) - the way the multiplicities go.
+void logup_gkr_prove_columns(Ctx& c, const Pcs& pcs, const lh_logup_columns* lookups, size_t L, size_t n, size_t l,
+                             Transcript& tr) {
+  const size_t nv = logup_columns_check(lookups, L, n, l);
   LH_REQUIRE(!Shard(c).on && !(c.has_comm && c.comm.size > 1), LH_ERR_ARG,
              "logup: sharded proofs are not supported (the ctx is inside a sharded prove or has a communicator of several ranks)");
   LH_REQUIRE(pcs.chunks == 1 && pcs.batch_commit && pcs.commit_bases && !pcs.commit_and_write && !pcs.commit_columns_and_write,
@@ -70,21 +97,56 @@ void logup_gkr_prove(Ctx& c, const Pcs& pcs, const lh_logup_lookup* lookups, siz
   std::vector<size_t> first(L);  // the first input column of every lookup
   for (size_t k = 0; k < L; k++) first[k] = W, W += lookups[k].width;
 
-  // ---- 0/1: header, the input columns' commitments (each zero-padded to nv variables: the table the opening is handed too)
+  // ---- 0/1: header, the input columns' commitments, lookup-major in column order whatever the kinds.  An Fr column is
+  // zero-padded to nv variables (the table the opening is handed too); a u32 column is a 32-bit MSM over its 2^n entries
+  // against the bases of level nv, its width promised from the OR of its entries - neither widened nor padded
   logup_header(tr, lookups, L, n, l);
-  std::vector<const Fr*> f(W), polys(W + L, nullptr);
+  std::vector<const void*> f(W);              // input column i as it was handed in ...
+  std::vector<uint8_t> u32(W, 0);             // ... a uint32_t column?
+  std::vector<size_t> fr_at, sm_at;           // the columns of either kind, in column order
+  std::vector<const Fr*> polys(W + L, nullptr);  // the opening's tables (null: a 32-bit column, SmallPoly below)
+  std::vector<uint32_t> f_bits(W, 0);
   for (size_t k = 0; k < L; k++)
     for (uint32_t j = 0; j < lookups[k].width; j++) {
-      const Fr* col = (const Fr*)lookups[k].d_inputs[j];
-      f[first[k] + j] = polys[first[k] + j] = col;
+      const size_t i = first[k] + j;
+      f[i] = lookups[k].d_inputs[j];
+      u32[i] = lookups[k].kinds != nullptr && lookups[k].kinds[j] == LH_LOGUP_COL_U32;
+      (u32[i] ? sm_at : fr_at).push_back(i);
+      if (u32[i]) continue;
+      const Fr* col = (const Fr*)f[i];
+      polys[i] = col;
       if (N < NV) {
         Fr* pad = c.arena.alloc_n<Fr>(NV);
         LH_HIP(hipMemcpyAsync(pad, col, N * sizeof(Fr), hipMemcpyDeviceToDevice, c.stream));
         LH_HIP(hipMemsetAsync(pad + N, 0, (NV - N) * sizeof(Fr), c.stream));
-        polys[first[k] + j] = pad;
+        polys[i] = pad;
       }
     }
-  lasso_write_commitments(tr, pcs.batch_commit(polys.data(), W, nv));
+  {
+    std::vector<HG1> comms(W);
+    if (!fr_at.empty()) {
+      std::vector<const Fr*> tables;
+      for (size_t i : fr_at) tables.push_back(polys[i]);
+      const std::vector<HG1> out = pcs.batch_commit(tables.data(), tables.size(), nv);
+      for (size_t t = 0; t < fr_at.size(); t++) comms[fr_at[t]] = out[t];
+    }
+    if (!sm_at.empty()) {
+      std::vector<const uint32_t*> cols;
+      for (size_t i : sm_at) cols.push_back((const uint32_t*)f[i]);
+      std::vector<uint32_t> ors(cols.size(), 0);
+      k_or_u32(c, cols.data(), cols.size(), N, ors.data());
+      std::vector<MsmJob> jobs;
+      for (size_t t = 0; t < sm_at.size(); t++) {
+        f_bits[sm_at[t]] = std::max(bit_length(ors[t]), 1u);
+        jobs.push_back(MsmJob{cols[t], true, pcs.commit_bases(nv), N});
+        jobs.back().known_bits = f_bits[sm_at[t]];
+      }
+      std::vector<HG1> out(jobs.size());
+      msm_batch(c, jobs.data(), jobs.size(), (G1Affine*)out.data());
+      for (size_t t = 0; t < sm_at.size(); t++) comms[sm_at[t]] = out[t];
+    }
+    lasso_write_commitments(tr, comms);
+  }
 
   // ---- 2: beta, the compressed columns cf_k (device inputs) and ct_k (the public table, uploaded)
   const std::vector<HFr> pw = logup_powers(tr.squeeze_challenge());
@@ -97,13 +159,21 @@ void logup_gkr_prove(Ctx& c, const Pcs& pcs, const lh_logup_lookup* lookups, siz
       LH_HIP(hipMemcpyAsync(d, lookups[k].table[j], M * sizeof(Fr), hipMemcpyHostToDevice, c.stream));
       t[j] = d;
     }
-    cf[k] = f[first[k]], ct[k] = t[0];  // (w = 1: the column itself, nothing launched)
-    if (w > 1) {
+    cf[k] = (const Fr*)f[first[k]], ct[k] = t[0];  // (w = 1 and an Fr column: the column itself, nothing launched)
+    const bool any_u32 = std::any_of(u32.begin() + first[k], u32.begin() + first[k] + w, [](uint8_t b) { return b != 0; });
+    if (any_u32) {  // (the join and the leaves read cf_k as field elements: a single u32 column is widened by the same kernel)
       Fr* dcf = c.arena.alloc_n<Fr>(N);
+      k_logup_compress_cols(c, f.data() + first[k], u32.data() + first[k], (const Fr*)pw.data(), w, N, dcf);
+      cf[k] = dcf;
+    } else if (w > 1) {
+      Fr* dcf = c.arena.alloc_n<Fr>(N);
+      k_logup_compress(c, (const Fr* const*)(f.data() + first[k]), (const Fr*)pw.data(), w, N, dcf);
+      cf[k] = dcf;
+    }
+    if (w > 1) {
       Fr* dct = c.arena.alloc_n<Fr>(M);
-      k_logup_compress(c, f.data() + first[k], (const Fr*)pw.data(), w, N, dcf);
       k_logup_compress(c, t.data(), (const Fr*)pw.data(), w, M, dct);
-      cf[k] = dcf, ct[k] = dct;
+      ct[k] = dct;
     }
   }
 
@@ -153,7 +223,23 @@ void logup_gkr_prove(Ctx& c, const Pcs& pcs, const lh_logup_lookup* lookups, siz
   const std::vector<HFr> x_l = side(true, l, ct).x;
 
   // ---- 7: f_kj(x_n) lookup-major, then m_k(x_l)
-  const std::vector<HFr> f_e = evaluate_polys(c, f.data(), W, n, x_n.data());
+  std::vector<HFr> f_e(W);
+  if (!fr_at.empty()) {
+    std::vector<const Fr*> tables;
+    for (size_t i : fr_at) tables.push_back((const Fr*)f[i]);
+    const std::vector<HFr> out = evaluate_polys(c, tables.data(), tables.size(), n, x_n.data());
+    for (size_t t = 0; t < fr_at.size(); t++) f_e[fr_at[t]] = out[t];
+  }
+  if (!sm_at.empty()) {  // the u32 columns against eq(x_n), as the multiplicities against eq(x_l) below
+    ArenaScope inner(c.arena);
+    Fr* eq = c.arena.alloc_n<Fr>(N);
+    k_eq_xy(c, (const Fr*)x_n.data(), n, eq);
+    std::vector<const uint32_t*> cols;
+    for (size_t i : sm_at) cols.push_back((const uint32_t*)f[i]);
+    std::vector<HFr> out(cols.size());
+    k_inner_products_small(c, cols.data(), cols.size(), eq, N, (Fr*)out.data());
+    for (size_t t = 0; t < sm_at.size(); t++) f_e[sm_at[t]] = out[t];
+  }
   std::vector<HFr> m_e(L);
   {
     ArenaScope inner(c.arena);
@@ -165,8 +251,12 @@ void logup_gkr_prove(Ctx& c, const Pcs& pcs, const lh_logup_lookup* lookups, siz
   tr.write_field_elements(f_e);
   tr.write_field_elements(m_e);
 
-  // ---- 8: ONE batch opening over nv variables; the multiplicities go as their 32-bit columns
+  // ---- 8: ONE batch opening over nv variables; the multiplicities and the u32 inputs go as their 32-bit columns.  When every
+  // input is one, every opened poly is a small column and the opening takes them as columns (mkzg.cpp all_small; from
+  // Options::open_small_min_vars on its largest quotients are committed column by column).  Nothing is committed ahead - no
+  // Pcs::precommit call, the opening builds its column plan itself; the bytes do not depend on the route
   std::vector<SmallPoly> small(W + L);
+  for (size_t i : sm_at) small[i] = SmallPoly{(const uint32_t*)f[i], N, f_bits[i]};
   for (size_t k = 0; k < L; k++) small[W + k] = SmallPoly{m[k], M, std::max(bit_length(ors[k]), 1u)};
   std::vector<HFr> points;
   lasso_append_points(points, {&x_n, &x_l}, nv);

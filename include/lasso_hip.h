@@ -327,6 +327,22 @@ typedef struct lh_logup_lookup {
 } lh_logup_lookup;
 lh_status lh_logup_gkr_prove(lh_ctx*, const lh_srs*, const lh_logup_lookup* lookups, size_t num_lookups, size_t num_vars,
                              size_t table_vars, lh_transcript* t);
+/* The same proof from input columns of which some (or all) are 32-bit words: column j of a lookup has the type kinds[j]
+ * says.  A u32 column and the same values as lh_fr are the same polynomial: the proof bytes are those of lh_logup_gkr_prove on
+ * the widened columns and are verified by lh_logup_gkr_verify with the plain lh_logup_lookup list (no verifier entry of its
+ * own).  A u32 column is committed as a 32-bit MSM over its 2^num_vars entries, compressed by 8 multiply-adds per entry,
+ * evaluated and opened as a small column - never widened, never padded.  Limits and errors as above; a kind
+ * other than the two below is LH_ERR_ARG with a message naming the lookup and the column. */
+#define LH_LOGUP_COL_FR  0   /* lh_fr[2^num_vars], Montgomery */
+#define LH_LOGUP_COL_U32 1   /* uint32_t[2^num_vars], any 32-bit value */
+typedef struct lh_logup_columns {
+  uint32_t width;
+  const void* const* d_inputs;   /* device; column j has the type kinds[j] says */
+  const uint8_t* kinds;          /* width entries; NULL = all LH_LOGUP_COL_FR */
+  const lh_fr* const* table;     /* host, as in lh_logup_lookup */
+} lh_logup_columns;
+lh_status lh_logup_gkr_prove_columns(lh_ctx*, const lh_srs*, const lh_logup_columns* lookups, size_t num_lookups,
+                                     size_t num_vars, size_t table_vars, lh_transcript* t);
 /* (lh_logup_gkr_verify, lh_gkr_fractional_verify: with the verifiers below) */
 
 /* per-phase wall-clock of the last lh_lasso_prove on this ctx, milliseconds:
