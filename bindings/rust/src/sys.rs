@@ -80,6 +80,10 @@ pub const LH_LOGUP_COL_U32: u8 = 1;  // uint32_t[2^num_vars], any 32-bit value
 pub struct lh_logup_columns {
     pub width: u32, pub d_inputs: *const *const c_void, pub kinds: *const u8, pub table: *const *const Fr,
 }
+pub const LH_MEMCHECK_MAX_INIT_VARS: usize = 24;
+// the trace of lh_memcheck_prove: three device columns of 2^num_vars uint32_t (cell, value before, value after)
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct lh_memcheck_trace { pub d_addr: *const u32, pub d_rv: *const u32, pub d_wv: *const u32 }
 
 pub const LH_EX_CONSTANT: u32 = 0;
 pub const LH_EX_IDENTITY: u32 = 1;
@@ -308,6 +312,15 @@ extern "C" {
                                       num_lookups: usize, num_vars: usize, table_vars: usize, t: *mut lh_transcript) -> lh_status;
     pub fn lh_logup_gkr_verify(vp: *const lh_mkzg_vp, lookups: *const lh_logup_lookup, num_lookups: usize, num_vars: usize,
                                table_vars: usize, t: *mut lh_transcript) -> lh_status;
+    // read-write memory checking of a RAM trace (tests/memcheck_ref.py); init: host, 2^mem_vars words, or null (all zero)
+    pub fn lh_memcheck_prove(ctx: *mut lh_ctx, srs: *const lh_srs, trace: *const lh_memcheck_trace, num_vars: usize,
+                             mem_vars: usize, init: *const u32, t: *mut lh_transcript) -> lh_status;
+    pub fn lh_memcheck_verify(vp: *const lh_mkzg_vp, num_vars: usize, mem_vars: usize, init: *const u32,
+                              t: *mut lh_transcript) -> lh_status;
+    // (development) its witness kernels on their own; *out_bad = 1: an invalid trace
+    pub fn lh_debug_memcheck_witness(ctx: *mut lh_ctx, trace: *const lh_memcheck_trace, num_vars: usize, mem_vars: usize,
+                                     init: *const u32, d_rt: *mut u32, d_fv: *mut u32, d_ft: *mut u32, d_m: *mut u32,
+                                     out_bad: *mut i32) -> lh_status;
     // the host verifier of lh_gkr_fractional_prove; the roots p_0s / q_0s come back with the final claims and the point
     pub fn lh_gkr_fractional_verify(num_batching: usize, num_vars: usize, claimed_p_0s: *const *const Fr,
                                     claimed_q_0s: *const *const Fr, t: *mut lh_transcript, out_p_0s: *mut Fr,

@@ -1689,6 +1689,82 @@ def logup_gkr_verify(vp, lookups, num_vars, transcript):
         raise InvalidSnark("trailing bytes in proof")
 
 
+# ------------------------------------------------------------------ read-write memory checking (lh_memcheck_prove)
+def _memcheck_statement(num_vars, mem_vars, init):
+    """ArgumentError before anything is marshalled or the device is touched -> the image as a uint32 array, or None"""
+    if not (isinstance(num_vars, int) and 1 <= num_vars < 31):
+        raise ArgumentError("memcheck: num_vars out of range (1 to 30)")
+    top = _ffi.LH_MEMCHECK_MAX_INIT_VARS if init is not None else 30
+    if not (isinstance(mem_vars, int) and 1 <= mem_vars <= top):
+        raise ArgumentError("memcheck: mem_vars out of range (1 to %d)" % top)
+    if init is None:
+        return None
+    if len(init) != 1 << mem_vars:
+        raise ArgumentError("memcheck: an initial image of 2^mem_vars words")
+    if isinstance(init, C.Array) and init._type_ is C.c_uint32:  # (marshalled by the caller, once for many calls)
+        return init
+    if any(not 0 <= v < 1 << 32 for v in init):
+        raise ArgumentError("memcheck: the words of the image are 32-bit")
+    return (C.c_uint32 * len(init))(*init)
+
+
+def _memcheck_trace(addr, rv, wv, num_vars):
+    """-> (lh_memcheck_trace, num_vars); the columns are u32 DeviceBuffers or U32Columns of 2^num_vars entries"""
+    cols = (addr, rv, wv)
+    if any(c is None for c in cols):
+        raise ArgumentError("memcheck: the trace is three columns, addr, rv and wv")
+    if num_vars is None:
+        if not hasattr(addr, "num_vars"):
+            raise ArgumentError("memcheck: num_vars is needed with raw device buffers")
+        num_vars = addr.num_vars
+    if any(getattr(c, "num_vars", num_vars) != num_vars for c in cols):
+        raise ArgumentError("memcheck: trace columns of 2^num_vars entries")
+    if isinstance(num_vars, int) and 1 <= num_vars < 31:
+        for c in cols:
+            if getattr(getattr(c, "buf", c), "nbytes", 4 << num_vars) < 4 << num_vars:
+                raise ArgumentError("memcheck: a trace column of 2^num_vars entries needs %d bytes" % (4 << num_vars))
+    trace = _ffi.lh_memcheck_trace()
+    trace.d_addr, trace.d_rv, trace.d_wv = [C.cast(C.c_void_p(c.ptr if hasattr(c, "ptr") else c), C.POINTER(C.c_uint32))
+                                            for c in cols]
+    return trace, num_vars
+
+
+def memcheck_prove(pp, addr, rv, wv, mem_vars, transcript, init=None, num_vars=None):
+    """Read-write memory checking over multilinear KZG (tests/memcheck_ref.py): the trace addr / rv / wv - u32 DeviceBuffers
+    or U32Columns of 2^num_vars entries - is consistent over a memory of 2^mem_vars 32-bit cells that starts as `init`
+    (2^mem_vars ints, or a ctypes c_uint32 array marshalled once by the caller; None: all zero): every rv is the wv of the latest earlier operation on its cell, or the image's
+    word.  An inconsistent trace or an address >= 2^mem_vars: InvalidSnark "Invalid memory trace".  Appends the proof."""
+    trace, num_vars = _memcheck_trace(addr, rv, wv, num_vars)
+    image = _memcheck_statement(num_vars, mem_vars, init)
+    _check(pp.ctx.lib.lh_memcheck_prove(pp.ctx.h, pp.h, C.byref(trace), num_vars, mem_vars, image, transcript.p))
+
+
+def memcheck_verify(vp, num_vars, mem_vars, transcript, init=None):
+    """Verifier of memcheck_prove (host only).  A Keccak256Transcript must be fully consumed."""
+    image = _memcheck_statement(num_vars, mem_vars, init)
+    _check(vp.lib.lh_memcheck_verify(vp.h, num_vars, mem_vars, image, transcript.p))
+    if isinstance(transcript, Keccak256Transcript) and transcript.remaining():
+        raise InvalidSnark("trailing bytes in proof")
+
+
+def memcheck_witness(ctx, addr, rv, wv, mem_vars, init=None, num_vars=None):
+    """(development) the witness kernels of memcheck_prove alone (lh_debug_memcheck_witness) -> (rt, fv, ft, m, bad): the
+    previous-write times, the final values and times of the cells, the multiplicities of i - rt[i] as lists of ints, and
+    whether the trace is invalid (the lists are then unspecified)."""
+    import array
+    trace, num_vars = _memcheck_trace(addr, rv, wv, num_vars)
+    image = _memcheck_statement(num_vars, mem_vars, init)
+    sizes = [4 << num_vars, 4 << mem_vars, 4 << mem_vars, 4 << num_vars]
+    bufs = [ctx.alloc(s) for s in sizes]
+    bad = C.c_int(0)
+    _check(ctx.lib.lh_debug_memcheck_witness(ctx.h, C.byref(trace), num_vars, mem_vars, image, *[b.ptr for b in bufs],
+                                             C.byref(bad)))
+    out = [array.array("I", b.read()).tolist() for b in bufs]
+    for b in bufs:
+        b.free()
+    return out[0], out[1], out[2], out[3], bool(bad.value)
+
+
 def verify_fractional_sum_check(num_vars, claimed_p_0s, claimed_q_0s, transcript):
     """fractional_sum_check.rs:193-270, the host verifier of prove_fractional_sum_check (a claim None: the root is read)
     -> (p_0s, q_0s, p_xs, q_xs, x): the roots come back because a caller checks a relation between them."""

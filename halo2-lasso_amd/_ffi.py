@@ -20,6 +20,7 @@ LH_SUBTABLE_CUSTOM_BASE, LH_SUBTABLE_CUSTOM_MAX, LH_SUBTABLE_CUSTOM_MAX_BITS = 0
 LH_LASSO_NUM_PHASES = 9
 LH_LOGUP_MAX_LOOKUPS, LH_LOGUP_MAX_WIDTH, LH_LOGUP_MAX_TABLE_VARS = 8, 8, 24  # lh_logup_gkr_prove
 LH_LOGUP_COL_FR, LH_LOGUP_COL_U32 = 0, 1  # lh_logup_columns.kinds
+LH_MEMCHECK_MAX_INIT_VARS = 24  # lh_memcheck_prove: mem_vars with an initial image
 LH_BD_COLUMN_FR, LH_BD_COLUMN_U32 = 0, 1
 
 
@@ -58,6 +59,10 @@ class lh_lasso_table(C.Structure):
 
 class lh_logup_lookup(C.Structure):
     _fields_ = [("width", C.c_uint32), ("d_inputs", C.POINTER(C.c_void_p)), ("table", C.POINTER(C.POINTER(lh_fr)))]
+
+
+class lh_memcheck_trace(C.Structure):
+    _fields_ = [("d_addr", C.POINTER(C.c_uint32)), ("d_rv", C.POINTER(C.c_uint32)), ("d_wv", C.POINTER(C.c_uint32))]
 
 
 class lh_logup_columns(C.Structure):
@@ -409,6 +414,10 @@ SIGNATURES["lh_lasso_verify_batch"] = (C.c_int, [_P, C.POINTER(C.POINTER(lh_lass
 SIGNATURES["lh_logup_gkr_prove"] = (C.c_int, [_P, _P, C.POINTER(lh_logup_lookup), _SZ, _SZ, _SZ, _T])
 SIGNATURES["lh_logup_gkr_prove_columns"] = (C.c_int, [_P, _P, C.POINTER(lh_logup_columns), _SZ, _SZ, _SZ, _T])
 SIGNATURES["lh_logup_gkr_verify"] = (C.c_int, [_P, C.POINTER(lh_logup_lookup), _SZ, _SZ, _SZ, _T])
+SIGNATURES["lh_memcheck_prove"] = (C.c_int, [_P, _P, C.POINTER(lh_memcheck_trace), _SZ, _SZ, C.POINTER(C.c_uint32), _T])
+SIGNATURES["lh_memcheck_verify"] = (C.c_int, [_P, _SZ, _SZ, C.POINTER(C.c_uint32), _T])
+SIGNATURES["lh_debug_memcheck_witness"] = (C.c_int, [_P, C.POINTER(lh_memcheck_trace), _SZ, _SZ, C.POINTER(C.c_uint32), _P, _P, _P,
+                                                     _P, C.POINTER(C.c_int)])
 SIGNATURES["lh_gkr_fractional_verify"] = (C.c_int, [_SZ, _SZ, C.POINTER(C.POINTER(lh_fr)), C.POINTER(C.POINTER(lh_fr)), _T,
                                                     C.POINTER(lh_fr), C.POINTER(lh_fr), C.POINTER(lh_fr), C.POINTER(lh_fr),
                                                     C.POINTER(lh_fr)])

@@ -706,6 +706,16 @@ lh_status lh_logup_gkr_prove_columns(lh_ctx* ctx, const lh_srs* srs, const lh_lo
   logup_gkr_prove_columns(ctx->c, mkzg_pcs(ctx->c, srs->s), lookups, num_lookups, num_vars, table_vars, tr);
   LH_CATCH
 }
+// ---------------------------------------------------------------- read-write memory checking
+lh_status lh_memcheck_prove(lh_ctx* ctx, const lh_srs* srs, const lh_memcheck_trace* trace, size_t num_vars, size_t mem_vars,
+                            const uint32_t* init, lh_transcript* t) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(srs);
+  NEED(trace);
+  Transcript tr(t);
+  memcheck_prove(ctx->c, mkzg_pcs(ctx->c, srs->s), *trace, num_vars, mem_vars, init, tr);
+  LH_CATCH
+}
 lh_status lh_lasso_last_timing(lh_ctx* ctx, double* out_ms) {
   LH_TRY NEED_CTX(ctx);
   NEED(out_ms);
@@ -1031,6 +1041,15 @@ lh_status lh_logup_gkr_verify(const lh_mkzg_vp* vp, const lh_logup_lookup* looku
   if (logup_check(lookups, num_lookups, num_vars, table_vars, false) > mkzg_vp_num_vars(*vp->p))
     throw lh::Error(LH_ERR_INVALID_PCS_PARAM, "Too many variates of poly to verify");
   logup_gkr_verify(mkzg_verifier(*vp->p), lookups, num_lookups, num_vars, table_vars, tr);
+  LH_CATCH
+}
+lh_status lh_memcheck_verify(const lh_mkzg_vp* vp, size_t num_vars, size_t mem_vars, const uint32_t* init, lh_transcript* t) {
+  LH_TRY
+  NEED(vp);
+  Transcript tr(t);
+  if (memcheck_check(num_vars, mem_vars, init != nullptr) > mkzg_vp_num_vars(*vp->p))
+    throw lh::Error(LH_ERR_INVALID_PCS_PARAM, "Too many variates of poly to verify");
+  memcheck_verify(mkzg_verifier(*vp->p), num_vars, mem_vars, init, tr);
   LH_CATCH
 }
 lh_status lh_hyperplonk_verify(const lh_mkzg_vp* vp, const lh_hp_vparam* hvp, const lh_fr* const* instances,
@@ -2181,6 +2200,18 @@ lh_status lh_debug_lasso_counters(lh_ctx* ctx, const uint32_t* const* d_dims, si
   }
   k_lasso_counters(ctx->c, d_dims, num_cols, n, m, d_read_ts, d_final_cts, d_keep_sorted, d_keep_index);
   ctx->c.sync();
+  LH_CATCH
+}
+lh_status lh_debug_memcheck_witness(lh_ctx* ctx, const lh_memcheck_trace* trace, size_t num_vars, size_t mem_vars,
+                                    const uint32_t* init, uint32_t* d_rt, uint32_t* d_fv, uint32_t* d_ft, uint32_t* d_m, int* out_bad) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(trace);
+  NEED(d_rt);
+  NEED(d_fv);
+  NEED(d_ft);
+  NEED(d_m);
+  NEED(out_bad);
+  *out_bad = memcheck_witness(ctx->c, *trace, num_vars, mem_vars, init, d_rt, d_fv, d_ft, d_m) ? 0 : 1;
   LH_CATCH
 }
 lh_status lh_debug_sort_plan(size_t n, unsigned bits, int key_bytes, unsigned* passes, unsigned rb[8], size_t* temp_bytes) {

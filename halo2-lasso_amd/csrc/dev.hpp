@@ -860,6 +860,41 @@ struct LogupLeaves {
   Fr* q_up[LOGUP_MAX];
 };
 void k_logup_leaves(Ctx&, const LogupLeaves&, size_t count, size_t num_vars, bool table_side, bool up, const Fr& gamma);
+
+// ------------------------------------------------------------------ read-write memory checking (kernels_memcheck.hip)
+// The witness of a trace of 2^num_vars operations (addr, rv, wv: device u32 columns) over 2^mem_vars cells whose image is
+// d_init (device; null: all zero): rt[i] = the time of the previous write to addr[i] (operation q writes at time q + 1; 0:
+// none), fv[a] / ft[a] = the final value and time of cell a.  A stable sort of (addr, position) by the low mem_vars bits and one
+// pass over the sorted positions; false (after ONE flag readback): an address >= 2^mem_vars or a read that does not return
+// the last value written - the columns are then unspecified, but nothing is read or written out of bounds.
+// Launch record "memcheck_trace", 2^num_vars items, algorithmic bytes 36 * 2^num_vars + 16 * 2^mem_vars
+bool k_memcheck_trace(Ctx&, const uint32_t* addr, const uint32_t* rv, const uint32_t* wv, size_t num_vars, size_t mem_vars,
+                      const uint32_t* d_init, uint32_t* rt, uint32_t* fv, uint32_t* ft);
+// m[d] = #{i < n : i - rt[i] = d}, d < n, by wave-aggregated atomics.  Launch record "memcheck_m", n items, 12 n bytes
+void k_memcheck_m(Ctx&, const uint32_t* rt, size_t n, uint32_t* m);
+// The leaves of the four product trees in ONE launch, the side in blockIdx.y, h(a, v, t) = a gamma^2 + v gamma + t - tau:
+//   side 0 (2^num_vars operations): col = addr, rv, rt, wv;        leaf = RS = h(addr, rv, rt), WS = h(addr, wv, i + 1)
+//   side 1 (2^mem_vars cells):      col = init (null: 0), fv, ft;  leaf = Init = h(a, init, 0), Final = h(a, fv, ft)
+// up[side] (both or neither of a side): the level above that side's leaves (node i = leaf[i] * leaf[i + half]) in the same pass.
+// Launch record "memcheck_leaves", 2^num_vars + 2^mem_vars items.  `count` is filled by the launcher.
+struct MemcheckLeaves {
+  const uint32_t* col[2][4];
+  Fr* leaf[2][2];
+  Fr* up[2][2];
+  size_t count[2];
+};
+void k_memcheck_leaves(Ctx&, const MemcheckLeaves&, size_t num_vars, size_t mem_vars, const Fr& gamma, const Fr& gamma2,
+                       const Fr& tau);
+// The leaves of the range check's two fractions over 2^num_vars entries in one launch, and with `up` the level above them:
+//   fraction 0: p == 1 (`ones` is filled), q0 = delta + i - rt[i];   fraction 1: p1 = -m[i], q1 = delta + i
+// Launch record "memcheck_range_leaves", 2^num_vars items
+struct MemcheckRangeLeaves {
+  const uint32_t *rt, *m;
+  Fr *ones, *q0, *p1, *q1;
+  Fr *p0_up, *q0_up, *p1_up, *q1_up;
+};
+void k_memcheck_range_leaves(Ctx&, const MemcheckRangeLeaves&, size_t num_vars, bool up, const Fr& delta);
+
 void k_lookup_h(Ctx&, const Fr* input, const Fr* table, const Fr* m, const Fr& gamma, size_t n, Fr* h);
 void k_permutation_z(Ctx&, const Fr* const* values, const Fr* const* perms, size_t num_perm, size_t num_chunks,
                      size_t num_vars, const Fr& beta, const Fr& gamma, const uint32_t* d_order, const uint32_t* d_nth,

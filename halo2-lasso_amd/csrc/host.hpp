@@ -801,7 +801,26 @@ void logup_gkr_prove_columns(Ctx&, const Pcs&, const lh_logup_columns* lookups, 
 void logup_gkr_verify(const PcsVerifier& pcs, const lh_logup_lookup* lookups, size_t num_lookups, size_t num_vars,
                       size_t table_vars, Transcript& tr);
 
+// ------------------------------------------------------------------ read-write memory checking (memcheck.cpp; tests/memcheck_ref.py)
+// the limits that need no device (shared with the verifier): returns nv = max(num_vars, mem_vars)
+size_t memcheck_check(size_t num_vars, size_t mem_vars, bool has_init);
+// trace: three device u32 columns of 2^num_vars entries; init: HOST, 2^mem_vars words, or null for an all-zero image
+void memcheck_prove(Ctx&, const Pcs&, const lh_memcheck_trace& trace, size_t num_vars, size_t mem_vars, const uint32_t* init,
+                    Transcript& tr);
+void memcheck_verify(const PcsVerifier& pcs, size_t num_vars, size_t mem_vars, const uint32_t* init, Transcript& tr);
+// the witness kernels alone (lh_debug_memcheck_witness): false when the trace is invalid
+bool memcheck_witness(Ctx&, const lh_memcheck_trace& trace, size_t num_vars, size_t mem_vars, const uint32_t* init, uint32_t* d_rt,
+                      uint32_t* d_fv, uint32_t* d_ft, uint32_t* d_m);
+
 // ------------------------------------------------------------------ verifiers (verifier.cpp; host only)
+HFr identity_eval(const std::vector<HFr>& x);  // sum_i 2^i x_i (sum_check.rs:123-125)
+// verify_grand_product (oracle/pyref/gkr.py): trees of the given depths; -> the roots, and per tree the claim about its
+// leaves' multilinear extension and the point it is made at.  A mismatch: LH_ERR_INVALID_SUMCHECK
+struct GpClaim {
+  HFr claim;
+  std::vector<HFr> point;
+};
+std::vector<HFr> verify_grand_product(const std::vector<size_t>& depth, Transcript& tr, std::vector<GpClaim>& out);
 HFr interpolate_evals(const std::vector<HFr>& evals, const HFr& x);  // barycentric over 0..d (arithmetic.rs:108-136)
 HFr horner(const std::vector<HFr>& coeffs, const HFr& x);
 struct VerifierParams;  // MultilinearKzgVerifierParams (kzg.rs:79-101)

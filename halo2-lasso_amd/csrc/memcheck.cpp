@@ -1,0 +1,249 @@
+// Read-write memory checking: a stand-alone argument for RAM traces.  A trace of loads and stores over a mutable memory is
+// consistent - every read returns the last value written to its cell - iff
+//   Init u WS = RS u Final   as multisets of (address, value, time) triples, and every read's time precedes its own.
+// The multiset identity is one grand-product GKR over four trees of fingerprints (gkr.cpp prove_grand_product), the order of
+// the times a LogUp range check of the differences i - rt[i] in [0, 2^n) by one fractional sum-check over two fractions
+// (prove_fractional_sum_check) with the identity table in closed form.  The reference holds no such argument; protocol and
+// transcript schedule are specified in tests/memcheck_ref.py and reproduced here byte for byte.  Written against the PCS
+// description (host.hpp Pcs / PcsVerifier), as logup.cpp is.
+#include <algorithm>
+#include "host.hpp"
+
+namespace lh {
+
+namespace {
+constexpr size_t NUM_POLYS = 7;  // commitment order: addr, rv, wv, rt, fv, ft, m
+enum { ADDR, RV, WV, RT, FV, FT, MULT };
+// (poly, point) of the opened evaluations in the order they are written; points: 0 = r_N, 1 = r_M, 2 = x
+constexpr uint32_t OPENINGS[8][2] = {{ADDR, 0}, {RV, 0}, {WV, 0}, {RT, 0}, {FV, 1}, {FT, 1}, {RT, 2}, {MULT, 2}};
+
+void memcheck_header(Transcript& tr, size_t n, size_t l, bool has_init) {
+  for (size_t v : {n, l, (size_t)has_init}) tr.common_field_element(HFr::from_u64(v));
+}
+std::vector<lh_evaluation> memcheck_evaluations(const std::vector<HFr>& vals) {
+  std::vector<lh_evaluation> evs(vals.size());
+  for (size_t i = 0; i < evs.size(); i++) {
+    memset(&evs[i], 0, sizeof(lh_evaluation));
+    evs[i].poly = OPENINGS[i][0], evs[i].point = OPENINGS[i][1];
+    memcpy(&evs[i].value, &vals[i], 32);
+  }
+  return evs;
+}
+}  // namespace
+
+size_t memcheck_check(size_t n, size_t l, bool has_init) {
+  LH_REQUIRE(n >= 1 && n < 31, LH_ERR_ARG, "memcheck: num_vars out of range (1 to 30)");
+  // (with an image the verifier folds its 2^mem_vars host words)
+  LH_REQUIRE(!has_init || (l >= 1 && l <= (size_t)LH_MEMCHECK_MAX_INIT_VARS), LH_ERR_ARG,
+             "memcheck: mem_vars out of range with an initial image (1 to " + std::to_string(LH_MEMCHECK_MAX_INIT_VARS) + ")");
+  LH_REQUIRE(l >= 1 && l < 31, LH_ERR_ARG, "memcheck: mem_vars out of range (1 to 30)");
+  return std::max(n, l);
+}
+
+static void memcheck_trace_check(const lh_memcheck_trace& trace) {
+  LH_REQUIRE(trace.d_addr != nullptr, LH_ERR_ARG, "null argument: d_addr of the trace");
+  LH_REQUIRE(trace.d_rv != nullptr, LH_ERR_ARG, "null argument: d_rv of the trace");
+  LH_REQUIRE(trace.d_wv != nullptr, LH_ERR_ARG, "null argument: d_wv of the trace");
+}
+// the image on the device (arena memory of the caller's scope), null without one
+static const uint32_t* memcheck_upload(Ctx& c, const uint32_t* init, size_t M) {
+  if (!init) return nullptr;
+  uint32_t* d = c.arena.alloc_n<uint32_t>(M);
+  LH_HIP(hipMemcpyAsync(d, init, M * sizeof(uint32_t), hipMemcpyHostToDevice, c.stream));
+  return d;
+}
+
+bool memcheck_witness(Ctx& c, const lh_memcheck_trace& trace, size_t n, size_t l, const uint32_t* init, uint32_t* d_rt,
+                      uint32_t* d_fv, uint32_t* d_ft, uint32_t* d_m) {
+  memcheck_check(n, l, init != nullptr);
+  memcheck_trace_check(trace);
+  ArenaScope scope(c.arena);
+  const uint32_t* d_init = memcheck_upload(c, init, (size_t)1 << l);
+  const bool ok = k_memcheck_trace(c, trace.d_addr, trace.d_rv, trace.d_wv, n, l, d_init, d_rt, d_fv, d_ft);
+  k_memcheck_m(c, d_rt, (size_t)1 << n, d_m);
+  c.sync();  // (the image's arena memory goes back with this scope)
+  return ok;
+}
+
+void memcheck_prove(Ctx& c, const Pcs& pcs, const lh_memcheck_trace& trace, size_t n, size_t l, const uint32_t* init,
+                    Transcript& tr) {
+  const size_t nv = memcheck_check(n, l, init != nullptr);
+  memcheck_trace_check(trace);
+  LH_REQUIRE(!Shard(c).on && !(c.has_comm && c.comm.size > 1), LH_ERR_ARG,
+             "memcheck: sharded proofs are not supported (the ctx is inside a sharded prove or has a communicator of several ranks)");
+  LH_REQUIRE(pcs.chunks == 1 && pcs.commit_bases && !pcs.commit_and_write && !pcs.commit_columns_and_write, LH_ERR_ARG,
+             "memcheck: implemented for schemes whose commitment is one point over bases");
+  if (nv > pcs.max_vars) throw Error(LH_ERR_INVALID_PCS_PARAM, "Too many variates of poly to commit");
+  const size_t N = (size_t)1 << n, M = (size_t)1 << l;
+  open_precommit_cancel(c);
+  ArenaScope scope(c.arena);
+  EqHalfScope eq_scope(c);  // (the opening shares eq tables of its points: arena memory of this scope)
+
+  // ---- 0/1: header; the witness (one flag readback); ONE block of seven commitments, every column a 32-bit MSM over its own
+  // length against the bases of level nv, its width promised from the OR of its entries - the way LogUp-GKR commits m_k
+  memcheck_header(tr, n, l, init != nullptr);
+  const uint32_t* d_init = memcheck_upload(c, init, M);
+  uint32_t* rt = c.arena.alloc_n<uint32_t>(N);
+  uint32_t* fv = c.arena.alloc_n<uint32_t>(M);
+  uint32_t* ft = c.arena.alloc_n<uint32_t>(M);
+  uint32_t* m = c.arena.alloc_n<uint32_t>(N);
+  if (!k_memcheck_trace(c, trace.d_addr, trace.d_rv, trace.d_wv, n, l, d_init, rt, fv, ft))
+    throw Error(LH_ERR_INVALID_SNARK, "Invalid memory trace");
+  k_memcheck_m(c, rt, N, m);
+  const uint32_t* col[NUM_POLYS] = {trace.d_addr, trace.d_rv, trace.d_wv, rt, fv, ft, m};
+  const size_t len[NUM_POLYS] = {N, N, N, N, M, M, N};
+  uint32_t bits[NUM_POLYS];
+  {
+    const uint32_t* over_n[5] = {col[ADDR], col[RV], col[WV], col[RT], col[MULT]};
+    const uint32_t* over_m[2] = {col[FV], col[FT]};
+    uint32_t or_n[5], or_m[2];
+    k_or_u32(c, over_n, 5, N, or_n);
+    k_or_u32(c, over_m, 2, M, or_m);
+    const uint32_t ors[NUM_POLYS] = {or_n[0], or_n[1], or_n[2], or_n[3], or_m[0], or_m[1], or_n[4]};
+    std::vector<MsmJob> jobs;
+    for (size_t i = 0; i < NUM_POLYS; i++) {
+      bits[i] = std::max(bit_length(ors[i]), 1u);
+      jobs.push_back(MsmJob{col[i], true, pcs.commit_bases(nv), len[i]});
+      jobs.back().known_bits = bits[i];
+    }
+    std::vector<HG1> comms(NUM_POLYS);
+    msm_batch(c, jobs.data(), jobs.size(), (G1Affine*)comms.data());
+    lasso_write_commitments(tr, comms);
+  }
+
+  // ---- 2: gamma, tau; the four trees' leaves in one launch (and, fused, the level above the large ones); the grand product
+  const HFr gamma = tr.squeeze_challenge(), tau = tr.squeeze_challenge();
+  const bool fused = c.opt.logup_fused_leaves != 0;
+  std::vector<HFr> r_N, r_M;
+  {
+    MemcheckLeaves a;
+    memset(&a, 0, sizeof(a));
+    const uint32_t* cols[2][4] = {{col[ADDR], col[RV], col[RT], col[WV]}, {d_init, col[FV], col[FT], nullptr}};
+    const size_t vars[2] = {n, l};
+    const Fr* leaves[4];
+    const Fr* level_up[4];
+    for (int side = 0; side < 2; side++) {
+      const size_t count = (size_t)1 << vars[side];
+      const bool up = fused && vars[side] >= 12;  // (the tree builder takes the level from 11 variables on; as lasso.cpp)
+      for (int k = 0; k < 4; k++) a.col[side][k] = cols[side][k];
+      for (int t = 0; t < 2; t++) {
+        a.leaf[side][t] = c.arena.alloc_n<Fr>(count);
+        a.up[side][t] = up ? c.arena.alloc_n<Fr>(count / 2) : nullptr;
+        leaves[2 * side + t] = a.leaf[side][t], level_up[2 * side + t] = a.up[side][t];
+      }
+    }
+    k_memcheck_leaves(c, a, n, l, dev(gamma), dev(gamma * gamma), dev(tau));
+    const size_t depths[4] = {n, n, l, l};
+    const GrandProductResult gp = prove_grand_product(c, 4, leaves, depths, tr, level_up);
+    r_N = gp.points[0], r_M = gp.points[2];
+  }
+
+  // ---- 3: delta; the range check i - rt[i] in [0, 2^n): sum_i 1 / (delta + i - rt[i]) = sum_d m[d] / (delta + d)
+  const HFr delta = tr.squeeze_challenge();
+  std::vector<HFr> x;
+  {
+    const bool up = fused && n >= 2;  // (one variable: the leaves are the top layer)
+    MemcheckRangeLeaves a;
+    memset(&a, 0, sizeof(a));
+    a.rt = rt, a.m = m;
+    a.ones = c.arena.alloc_n<Fr>(N), a.q0 = c.arena.alloc_n<Fr>(N), a.p1 = c.arena.alloc_n<Fr>(N), a.q1 = c.arena.alloc_n<Fr>(N);
+    if (up) {
+      a.p0_up = c.arena.alloc_n<Fr>(N / 2), a.q0_up = c.arena.alloc_n<Fr>(N / 2);
+      a.p1_up = c.arena.alloc_n<Fr>(N / 2), a.q1_up = c.arena.alloc_n<Fr>(N / 2);
+    }
+    k_memcheck_range_leaves(c, a, n, up, dev(delta));
+    const Fr* ps[2] = {a.ones, a.p1};
+    const Fr* qs[2] = {a.q0, a.q1};
+    const Fr* p_up[2] = {a.p0_up, a.p1_up};
+    const Fr* q_up[2] = {a.q0_up, a.q1_up};
+    x = prove_fractional_sum_check(c, 2, n, nullptr, nullptr, ps, qs, tr, up ? p_up : nullptr, up ? q_up : nullptr).x;
+  }
+
+  // ---- 4: the eight evaluations, every column against the eq table of its point
+  std::vector<HFr> vals(8);
+  auto evaluate = [&](const std::vector<HFr>& point, std::initializer_list<size_t> polys, size_t first) {
+    ArenaScope inner(c.arena);
+    const size_t count = (size_t)1 << point.size();
+    Fr* eq = c.arena.alloc_n<Fr>(count);
+    k_eq_xy(c, (const Fr*)point.data(), point.size(), eq);
+    std::vector<const uint32_t*> cols;
+    for (size_t i : polys) cols.push_back(col[i]);
+    k_inner_products_small(c, cols.data(), cols.size(), eq, count, (Fr*)(vals.data() + first));
+  };
+  evaluate(r_N, {ADDR, RV, WV, RT}, 0);
+  evaluate(r_M, {FV, FT}, 4);
+  evaluate(x, {RT, MULT}, 6);
+  tr.write_field_elements(vals);
+
+  // ---- 5: ONE batch opening over nv variables; every poly goes as its 32-bit column (mkzg.cpp all_small).  Nothing is
+  // committed ahead - no Pcs::precommit call, the opening builds its column plan itself; the bytes do not depend on the route
+  std::vector<const Fr*> polys(NUM_POLYS, nullptr);
+  std::vector<SmallPoly> small(NUM_POLYS);
+  for (size_t i = 0; i < NUM_POLYS; i++) small[i] = SmallPoly{col[i], len[i], bits[i]};
+  std::vector<HFr> points;
+  lasso_append_points(points, {&r_N, &r_M, &x}, nv);
+  const std::vector<lh_evaluation> evs = memcheck_evaluations(vals);
+  pcs.batch_open(nv, polys.data(), polys.size(), points.data(), 3, evs.data(), evs.size(), tr, small.data());
+}
+
+// the multilinear extension of the image at x (variable i = index bit i): one fold over its 2^l words
+static HFr memcheck_init_eval(const uint32_t* init, size_t l, const std::vector<HFr>& x) {
+  const size_t M = (size_t)1 << l;
+  std::vector<HFr> cur(M / 2);
+  const size_t chunks = std::min<size_t>(cur.size(), 64);  // (the pool hands out items one by one)
+  host_parallel_for(chunks, [&](size_t ch) {
+    for (size_t k = ch * cur.size() / chunks; k < (ch + 1) * cur.size() / chunks; k++) {
+      const HFr lo = HFr::from_u64(init[2 * k]), hi = HFr::from_u64(init[2 * k + 1]);
+      cur[k] = lo + x[0] * (hi - lo);
+    }
+  });
+  for (size_t i = 1; i < l; i++) {
+    const size_t half = cur.size() / 2;
+    for (size_t k = 0; k < half; k++) cur[k] = cur[2 * k] + x[i] * (cur[2 * k + 1] - cur[2 * k]);
+    cur.resize(half);
+  }
+  return cur[0];
+}
+
+static void memcheck_verify_checked(const PcsVerifier& pcs, size_t n, size_t l, size_t nv, const uint32_t* init, Transcript& tr) {
+  memcheck_header(tr, n, l, init != nullptr);
+  const std::vector<HG1> comms = lasso_read_commitments(tr, NUM_POLYS);
+  const HFr gamma = tr.squeeze_challenge(), tau = tr.squeeze_challenge();
+  std::vector<GpClaim> claims;
+  const std::vector<HFr> roots = verify_grand_product({n, n, l, l}, tr, claims);  // RS, WS, Init, Final
+  if (roots[2] * roots[1] != roots[0] * roots[3]) throw Error(LH_ERR_INVALID_SNARK, "memcheck: Init*WS != RS*Final");
+  const std::vector<HFr>&r_N = claims[0].point, &r_M = claims[2].point;
+  const HFr delta = tr.squeeze_challenge();
+  const FracVerifyResult fr = verify_fractional_sum_check(2, n, nullptr, nullptr, tr);
+  // the LogUp identity on the roots: P_0 / Q_0 + P_1 / Q_1 = 0 with both denominators non-zero
+  if (fr.q_0s[0].is_zero() || fr.q_0s[1].is_zero() || !(fr.p_0s[0] * fr.q_0s[1] + fr.p_0s[1] * fr.q_0s[0]).is_zero())
+    throw Error(LH_ERR_INVALID_SNARK, "memcheck: the fractions do not sum to zero");
+  const std::vector<HFr> v = tr.read_field_elements(8);  // addr, rv, wv, rt at r_N; fv, ft at r_M; rt, m at x
+  auto h = [&](const HFr& a, const HFr& val, const HFr& ts) { return a * gamma * gamma + val * gamma + ts - tau; };
+  const HFr one = HFr::one(), id_N = identity_eval(r_N), id_M = identity_eval(r_M), id_x = identity_eval(fr.x);
+  const HFr init_e = init ? memcheck_init_eval(init, l, r_M) : HFr::zero();
+  if (claims[0].claim != h(v[0], v[1], v[3]) || claims[1].claim != h(v[0], v[2], id_N + one) ||
+      claims[2].claim != h(id_M, init_e, HFr::zero()) || claims[3].claim != h(id_M, v[4], v[5]))
+    throw Error(LH_ERR_INVALID_SNARK, "memcheck: leaf claim mismatch");
+  if (fr.p_xs[0] != one || fr.q_xs[0] != delta + id_x - v[6] || fr.p_xs[1] != HFr::zero() - v[7] || fr.q_xs[1] != delta + id_x)
+    throw Error(LH_ERR_INVALID_SNARK, "memcheck: range leaf claim mismatch");
+  std::vector<HFr> points;
+  lasso_append_points(points, {&r_N, &r_M, &fr.x}, nv);
+  const std::vector<lh_evaluation> evs = memcheck_evaluations(v);
+  pcs.batch_verify(nv, comms.data(), comms.size(), points.data(), 3, evs.data(), evs.size(), tr);
+}
+// A proof that does not verify is LH_ERR_INVALID_SNARK whichever piece found it out; what is wrong with the call keeps its code
+void memcheck_verify(const PcsVerifier& pcs, size_t n, size_t l, const uint32_t* init, Transcript& tr) {
+  const size_t nv = memcheck_check(n, l, init != nullptr);
+  LH_REQUIRE(pcs.chunks == 1 && !pcs.read_commitments, LH_ERR_ARG, "memcheck: implemented for commitments of one point");
+  try {
+    memcheck_verify_checked(pcs, n, l, nv, init, tr);
+  } catch (const Error& e) {
+    if (e.code == LH_ERR_INVALID_SUMCHECK || e.code == LH_ERR_INVALID_PCS_OPEN || e.code == LH_ERR_TRANSCRIPT ||
+        e.code == LH_ERR_SERIALIZATION)
+      throw Error(LH_ERR_INVALID_SNARK, "memcheck: " + e.msg);
+    throw;
+  }
+}
+
+}  // namespace lh

@@ -648,7 +648,7 @@ static HFr eval_expr(const lh_expr& e, const EvalCtx& cx) {  // piop/sum_check.r
   return v.back();
 }
 
-static HFr identity_eval(const std::vector<HFr>& x) {  // sum_check.rs:123-125
+HFr identity_eval(const std::vector<HFr>& x) {  // sum_check.rs:123-125
   HFr acc = HFr::zero(), p = HFr::one();
   for (auto& xi : x) {
     acc += xi * p;
@@ -894,13 +894,8 @@ void hyperplonk_verify_phases(const PcsVerifier& pcs, const lh_hp_vparam& vp, co
 }
 
 // ------------------------------------------------------------------ Lasso verify (oracle/pyref/lasso.py:219-261)
-struct GpClaim {
-  HFr claim;
-  std::vector<HFr> point;
-};
-// oracle/pyref/gkr.py:197-227 (layer schedule of fractional_sum_check.rs:193-270 with p dropped)
-static std::vector<HFr> verify_grand_product(const std::vector<size_t>& depth, Transcript& tr,
-                                             std::vector<GpClaim>& out) {
+// oracle/pyref/gkr.py:197-227 (layer schedule of fractional_sum_check.rs:193-270 with p dropped; GpClaim: host.hpp)
+std::vector<HFr> verify_grand_product(const std::vector<size_t>& depth, Transcript& tr, std::vector<GpClaim>& out) {
   const size_t B = depth.size();
   size_t max_depth = 0;
   for (size_t d : depth) max_depth = std::max(max_depth, d);

@@ -345,6 +345,38 @@ lh_status lh_logup_gkr_prove_columns(lh_ctx*, const lh_srs*, const lh_logup_colu
                                      size_t num_vars, size_t table_vars, lh_transcript* t);
 /* (lh_logup_gkr_verify, lh_gkr_fractional_verify: with the verifiers below) */
 
+/* ---------------------------------------------------------------- a'''': read-write memory checking, an argument for RAM traces
+ * Lasso and LogUp-GKR check memories that never change.  This argument checks one that does: a memory of 2^mem_vars cells of
+ * 32-bit words and a trace of 2^num_vars operations, three DEVICE columns of uint32_t[2^num_vars].  Operation i says that cell
+ * d_addr[i] held d_rv[i] before it and holds d_wv[i] after it (a load: wv = rv).  Proven: every address is below 2^mem_vars,
+ * and every rv[i] is the wv of the latest earlier operation on the same cell, or init[addr[i]] when there is none.  Operation i
+ * writes at time i + 1, the image has time 0; no timestamp is handed in.  The protocol is specified in tests/memcheck_ref.py
+ * (DESIGN.md §21): offline memory checking (Init u WS = RS u Final as multisets, one grand-product GKR over four trees) plus
+ * a LogUp range check of the differences i - rt[i] in [0, 2^num_vars) (one fractional sum-check over two fractions) - without
+ * the latter a read from the future would pass.
+ *
+ * init is HOST memory, 2^mem_vars words, or NULL for an all-zero image.  It is part of the statement, like a LogUp-GKR table:
+ * it is NOT absorbed into the transcript; init given and NULL are different statements even when every word is zero.
+ * The proof commits seven 32-bit columns - addr, rv, wv, the previous-write times rt, the final values fv and times ft, the
+ * multiplicities m of the differences - each over its own length against the bases of nv = max(num_vars, mem_vars) variables,
+ * in ONE block framed by an identity mask.  The first three commitments of the proof are addr, rv, wv at nv variables: what a
+ * caller links to another proof about the same columns.
+ * Limits (LH_ERR_ARG with a message, checked on entry):
+ *   1 <= num_vars < 31                       positions and times are 32-bit words
+ *   1 <= mem_vars <= LH_MEMCHECK_MAX_INIT_VARS with an image   the verifier folds the 2^mem_vars words of the image
+ *   1 <= mem_vars < 31 without one           addresses are 32-bit words
+ *   no NULL trace or column; not on a ctx inside a sharded prove, nor on one with a communicator of several ranks
+ * LH_ERR_INVALID_PCS_PARAM when nv exceeds the SRS; LH_ERR_INVALID_SNARK "Invalid memory trace" when the trace is not
+ * consistent or an address is out of range (the ctx stays usable).  Multilinear KZG only.  Route option logup_fused_leaves
+ * below covers the leaf kernels of this argument too. */
+#define LH_MEMCHECK_MAX_INIT_VARS 24
+typedef struct lh_memcheck_trace {
+  const uint32_t *d_addr, *d_rv, *d_wv; /* device, 2^num_vars each */
+} lh_memcheck_trace;
+lh_status lh_memcheck_prove(lh_ctx*, const lh_srs*, const lh_memcheck_trace*, size_t num_vars, size_t mem_vars,
+                            const uint32_t* init /* host, 2^mem_vars, or NULL */, lh_transcript* t);
+/* (lh_memcheck_verify: with the verifiers below; lh_debug_memcheck_witness: with the debug entries) */
+
 /* per-phase wall-clock of the last lh_lasso_prove on this ctx, milliseconds:
  * [witness, commit, surge, leaves+trees, gkr, evals, open_n, open_l, total] */
 #define LH_LASSO_NUM_PHASES 9
@@ -410,7 +442,8 @@ lh_status lh_lasso_last_timing(lh_ctx*, double* out_ms);
  *                             on the message as loaded in Montgomery form.  Rows, trees and roots are bit-identical.
  *   logup_fused_leaves   1    lh_logup_gkr_prove makes the leaves of a side's fractions and the level above them in ONE launch
  *                             (csrc/kernels_logup.hip logup_leaves_up: the input side never reads a table of ones); 0: the
- *                             leaves in one launch, then one frac_up launch per fraction
+ *                             leaves in one launch, then one frac_up launch per fraction.  lh_memcheck_prove's two leaf
+ *                             kernels follow the same switch (the level above the trees' and the fractions' leaves)
  *   comm_round           0    how the partial sums of a sharded sum-check round are combined over the ranks:
  *                             0 = ncclAllGather of every rank's sums + a one-thread sum-and-publish kernel;
  *                             1 = ONE collective: the round kernel leaves its sums as u64 lanes (32-bit limb | tag << 40),
@@ -653,6 +686,11 @@ lh_status lh_gkr_fractional_verify(size_t num_batching, size_t num_vars, const l
  * it out.  The tables' multilinear extensions are evaluated here, O(width 2^table_vars) field operations per lookup. */
 lh_status lh_logup_gkr_verify(const lh_mkzg_vp* vp, const lh_logup_lookup* lookups, size_t num_lookups, size_t num_vars,
                               size_t table_vars, lh_transcript* t);
+/* the verifier of lh_memcheck_prove (tests/memcheck_ref.py verify; host only).  The same limits as the prover's;
+ * LH_ERR_INVALID_PCS_PARAM when max(num_vars, mem_vars) exceeds the param; a proof that does not verify is
+ * LH_ERR_INVALID_SNARK whichever piece finds it out.  The image's multilinear extension is evaluated here, 2^mem_vars field
+ * operations. */
+lh_status lh_memcheck_verify(const lh_mkzg_vp* vp, size_t num_vars, size_t mem_vars, const uint32_t* init, lh_transcript* t);
 typedef struct lh_hp_vparam { /* HyperPlonkVerifierParam (hyperplonk.rs:57-74) */
   size_t num_vars;
   size_t num_instance_polys;
@@ -1066,6 +1104,12 @@ lh_status lh_debug_sort_pairs(lh_ctx*, int key_bytes, const lh_debug_sort_slab* 
 lh_status lh_debug_lasso_counters(lh_ctx*, const uint32_t* const* d_dims, size_t num_cols, size_t n, size_t m,
                                   uint32_t* const* d_read_ts, uint32_t* const* d_final_cts, uint32_t* const* d_keep_sorted,
                                   uint32_t* const* d_keep_index);
+/* the witness kernels of lh_memcheck_prove on their own (trace, sizes and init as there): d_rt[2^num_vars] the previous-write
+ * times, d_fv / d_ft[2^mem_vars] the final values and times, d_m[2^num_vars] the multiplicities of i - rt[i] (all device).
+ * *out_bad = 1 when the trace is invalid (an address >= 2^mem_vars, a read that does not return the last value written); the
+ * columns are then unspecified.  The call itself still returns LH_OK. */
+lh_status lh_debug_memcheck_witness(lh_ctx*, const lh_memcheck_trace*, size_t num_vars, size_t mem_vars, const uint32_t* init,
+                                    uint32_t* d_rt, uint32_t* d_fv, uint32_t* d_ft, uint32_t* d_m, int* out_bad);
 /* the pass plan of one slab (host only, no GPU needed): the number of radix passes, the digit width of each (rb[passes ..
  * 8) = 0; `bits` above the key width count as the key width) and the temporary device bytes the sort takes */
 lh_status lh_debug_sort_plan(size_t n, unsigned bits, int key_bytes, unsigned* passes, unsigned rb[8], size_t* temp_bytes);
