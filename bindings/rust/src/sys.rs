@@ -28,6 +28,7 @@ pub const LH_RCCL_UNIQUE_ID_BYTES: usize = 128;
 #[repr(C)] pub struct lh_srs { _p: [u8; 0] }
 #[repr(C)] pub struct lh_usrs { _p: [u8; 0] }
 #[repr(C)] pub struct lh_mkzg_vp { _p: [u8; 0] }
+#[repr(C)] pub struct lh_spark_poly { _p: [u8; 0] }  // a committed sparse polynomial (lh_spark_commit)
 #[repr(C)] pub struct lh_zm_vp { _p: [u8; 0] }
 
 pub type FeCb = unsafe extern "C" fn(*mut c_void, *const Fr) -> c_int;
@@ -81,6 +82,8 @@ pub struct lh_logup_columns {
     pub width: u32, pub d_inputs: *const *const c_void, pub kinds: *const u8, pub table: *const *const Fr,
 }
 pub const LH_MEMCHECK_MAX_INIT_VARS: usize = 24;
+pub const LH_SPARK_MAX_DIMS: usize = 3;
+pub const LH_SPARK_MAX_DIM_VARS: usize = 24;
 // the trace of lh_memcheck_prove: three device columns of 2^num_vars uint32_t (cell, value before, value after)
 #[repr(C)] #[derive(Clone, Copy)]
 pub struct lh_memcheck_trace { pub d_addr: *const u32, pub d_rv: *const u32, pub d_wv: *const u32 }
@@ -321,6 +324,21 @@ extern "C" {
     pub fn lh_debug_memcheck_witness(ctx: *mut lh_ctx, trace: *const lh_memcheck_trace, num_vars: usize, mem_vars: usize,
                                      init: *const u32, d_rt: *mut u32, d_fv: *mut u32, d_ft: *mut u32, d_m: *mut u32,
                                      out_bad: *mut i32) -> lh_status;
+    // Spark (tests/spark_ref.py): commit a sparse polynomial once - 2^num_vars entries (d_dims[j][k] < 2^dim_vars, d_val[k]),
+    // device columns - and prove its evaluations at any number of points; the handle owns its device memory
+    pub fn lh_spark_commit(ctx: *mut lh_ctx, srs: *const lh_srs, num_vars: usize, dim_vars: usize, num_dims: usize,
+                           d_dims: *const *const u32, d_val: *const Fr, out: *mut *mut lh_spark_poly) -> lh_status;
+    // out null: the length alone; else *len is the room in and the length out
+    pub fn lh_spark_commitment(poly: *const lh_spark_poly, out: *mut u8, len: *mut usize) -> lh_status;
+    // point: num_dims * dim_vars host coordinates; the proof is appended to t
+    pub fn lh_spark_open(ctx: *mut lh_ctx, srs: *const lh_srs, poly: *const lh_spark_poly, point: *const Fr, out_value: *mut Fr,
+                         t: *mut lh_transcript) -> lh_status;
+    pub fn lh_spark_free(ctx: *mut lh_ctx, poly: *mut lh_spark_poly);
+    pub fn lh_spark_verify(vp: *const lh_mkzg_vp, num_vars: usize, dim_vars: usize, num_dims: usize, commitment: *const u8,
+                           commitment_len: usize, point: *const Fr, value: *const Fr, t: *mut lh_transcript) -> lh_status;
+    // (development) the memory kernel of an opening on its own: d_E[j][k] = eq(r_j, d_dims[j][k]) and the value
+    pub fn lh_debug_spark_e(ctx: *mut lh_ctx, num_vars: usize, dim_vars: usize, num_dims: usize, d_dims: *const *const u32,
+                            d_val: *const Fr, point: *const Fr, d_E: *const *mut Fr, out_value: *mut Fr) -> lh_status;
     // the host verifier of lh_gkr_fractional_prove; the roots p_0s / q_0s come back with the final claims and the point
     pub fn lh_gkr_fractional_verify(num_batching: usize, num_vars: usize, claimed_p_0s: *const *const Fr,
                                     claimed_q_0s: *const *const Fr, t: *mut lh_transcript, out_p_0s: *mut Fr,

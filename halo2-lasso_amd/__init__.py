@@ -1765,6 +1765,120 @@ def memcheck_witness(ctx, addr, rv, wv, mem_vars, init=None, num_vars=None):
     return out[0], out[1], out[2], out[3], bool(bad.value)
 
 
+# ------------------------------------------------------------------ Spark: sparse polynomial commitment (lh_spark_commit)
+def _spark_shape(num_vars, dim_vars, num_dims):
+    """ArgumentError before anything is marshalled or the device is touched"""
+    if not (isinstance(num_dims, int) and 1 <= num_dims <= _ffi.LH_SPARK_MAX_DIMS):
+        raise ArgumentError("spark: num_dims out of range (1 to %d)" % _ffi.LH_SPARK_MAX_DIMS)
+    if not (isinstance(dim_vars, int) and 1 <= dim_vars <= _ffi.LH_SPARK_MAX_DIM_VARS):
+        raise ArgumentError("spark: dim_vars out of range (1 to %d)" % _ffi.LH_SPARK_MAX_DIM_VARS)
+    if not (isinstance(num_vars, int) and 1 <= num_vars < 31):
+        raise ArgumentError("spark: num_vars out of range (1 to 30)")
+
+
+class SparkPoly:
+    """A committed sparse multilinear polynomial (`lh_spark_poly`): owns device copies of its entries, the access counters
+    and the commitment.  Open it any number of times with spark_open; free() (or `with`) gives the device memory back -
+    it also goes with the ctx.  `commitment`: the bytes spark_verify takes."""
+
+    def __init__(self, ctx, h, num_vars, dim_vars, num_dims):
+        self.ctx, self.h, self.num_vars, self.dim_vars, self.num_dims = ctx, h, num_vars, dim_vars, num_dims
+        n = C.c_size_t(0)
+        _check(ctx.lib.lh_spark_commitment(h, None, C.byref(n)))
+        out = (C.c_uint8 * n.value)()
+        _check(ctx.lib.lh_spark_commitment(h, out, C.byref(n)))
+        self.commitment = bytes(out[:n.value])
+
+    def free(self):
+        if self.h and self.ctx.h:  # (a ctx that is gone has taken its polynomials with it)
+            self.ctx.lib.lh_spark_free(self.ctx.h, self.h)
+        self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def spark_commit(ctx, srs, dims, val, dim_vars, num_vars=None):
+    """Commit the sparse polynomial sum_k val[k] prod_j eq(r_j, dims[j][k]) in len(dims) * dim_vars variables over
+    multilinear KZG (tests/spark_ref.py): `dims` are 1 to 3 u32 columns (U32Column / DeviceBuffer, 2^num_vars indices below
+    2^dim_vars), `val` a MultilinearPolynomial or DeviceBuffer of 2^num_vars Fr.  An index out of range: ArgumentError."""
+    dims = list(dims) if dims is not None else []
+    if val is None or any(d is None for d in dims):
+        raise ArgumentError("spark: null argument: dims or val")
+    if num_vars is None:
+        if not hasattr(val, "num_vars"):
+            raise ArgumentError("spark: num_vars is needed with raw device buffers")
+        num_vars = val.num_vars
+    _spark_shape(num_vars, dim_vars, len(dims))
+    if any(getattr(p, "num_vars", num_vars) != num_vars for p in dims + [val]):
+        raise ArgumentError("spark: columns of 2^num_vars entries")
+    for p, width in [(d, 4) for d in dims] + [(val, 32)]:
+        if getattr(getattr(p, "buf", p), "nbytes", width << num_vars) < width << num_vars:
+            raise ArgumentError("spark: a column of 2^num_vars entries needs %d bytes" % (width << num_vars))
+    cols = _ptr_array(dims)
+    h = C.c_void_p()
+    _check(ctx.lib.lh_spark_commit(ctx.h, srs.h, num_vars, dim_vars, len(dims), C.cast(cols, C.POINTER(C.POINTER(C.c_uint32))),
+                                   C.cast(C.c_void_p(val.ptr if hasattr(val, "ptr") else val), C.POINTER(lh_fr)), C.byref(h)))
+    return SparkPoly(ctx, h, num_vars, dim_vars, len(dims))
+
+
+def spark_open(ctx, srs, poly, point, transcript=None):
+    """Prove the evaluation of a SparkPoly at `point` (num_dims * dim_vars ints) -> (value, proof bytes); with a transcript
+    given the proof is appended to it and (value, None) returned."""
+    if not isinstance(poly, SparkPoly) or not poly.h:
+        raise ArgumentError("spark: the polynomial has been freed")
+    if len(point) != poly.num_dims * poly.dim_vars:
+        raise ArgumentError("spark: a point of num_dims * dim_vars coordinates")
+    t = transcript if transcript is not None else Keccak256Transcript()
+    out = (lh_fr * 1)()
+    _check(ctx.lib.lh_spark_open(ctx.h, srs.h, poly.h, _fr_array(point), out, t.p))
+    return _fr_list(out, 1)[0], (t.into_proof() if transcript is None else None)
+
+
+def spark_verify(vp, num_vars, dim_vars, num_dims, commitment, point, value, proof):
+    """Verifier of spark_open (host only): `commitment` the bytes of SparkPoly.commitment, `proof` bytes or a transcript.
+    A Keccak256Transcript must be fully consumed."""
+    _spark_shape(num_vars, dim_vars, num_dims)
+    if commitment is None or point is None or value is None or proof is None:
+        raise ArgumentError("spark: null argument")
+    if len(point) != num_dims * dim_vars:
+        raise ArgumentError("spark: a point of num_dims * dim_vars coordinates")
+    t = Keccak256Transcript.from_proof(bytes(proof)) if isinstance(proof, (bytes, bytearray)) else proof
+    blob = (C.c_uint8 * max(len(commitment), 1)).from_buffer_copy(bytes(commitment) or b"\0")
+    _check(vp.lib.lh_spark_verify(vp.h, num_vars, dim_vars, num_dims, blob, len(commitment), _fr_array(point),
+                                  _fr_array([value]), t.p))
+    if isinstance(t, Keccak256Transcript) and t.remaining():
+        raise InvalidSnark("trailing bytes in proof")
+
+
+def spark_e(ctx, dims, val, dim_vars, point, num_vars=None):
+    """(development) the memory kernel of spark_open alone (lh_debug_spark_e) -> (E, value): the num_dims memories
+    E[j][k] = eq(r_j, dims[j][k]) as lists of ints and sum_k val[k] prod_j E[j][k]."""
+    dims = list(dims)
+    num_vars = val.num_vars if num_vars is None else num_vars
+    _spark_shape(num_vars, dim_vars, len(dims))
+    if len(point) != len(dims) * dim_vars:
+        raise ArgumentError("spark: a point of num_dims * dim_vars coordinates")
+    bufs = [ctx.alloc(32 << num_vars) for _ in dims]
+    out = (lh_fr * 1)()
+    _check(ctx.lib.lh_debug_spark_e(ctx.h, num_vars, dim_vars, len(dims), C.cast(_ptr_array(dims), C.POINTER(C.POINTER(C.c_uint32))),
+                                    C.cast(C.c_void_p(val.ptr if hasattr(val, "ptr") else val), C.POINTER(lh_fr)), _fr_array(point),
+                                    C.cast(_ptr_array(bufs), C.POINTER(C.POINTER(lh_fr))), out))
+    E = [frs_from_bytes(b.read()) for b in bufs]
+    for b in bufs:
+        b.free()
+    return E, _fr_list(out, 1)[0]
+
+
 def verify_fractional_sum_check(num_vars, claimed_p_0s, claimed_q_0s, transcript):
     """fractional_sum_check.rs:193-270, the host verifier of prove_fractional_sum_check (a claim None: the root is read)
     -> (p_0s, q_0s, p_xs, q_xs, x): the roots come back because a caller checks a relation between them."""

@@ -21,6 +21,7 @@ LH_LASSO_NUM_PHASES = 9
 LH_LOGUP_MAX_LOOKUPS, LH_LOGUP_MAX_WIDTH, LH_LOGUP_MAX_TABLE_VARS = 8, 8, 24  # lh_logup_gkr_prove
 LH_LOGUP_COL_FR, LH_LOGUP_COL_U32 = 0, 1  # lh_logup_columns.kinds
 LH_MEMCHECK_MAX_INIT_VARS = 24  # lh_memcheck_prove: mem_vars with an initial image
+LH_SPARK_MAX_DIMS, LH_SPARK_MAX_DIM_VARS = 3, 24  # lh_spark_commit
 LH_BD_COLUMN_FR, LH_BD_COLUMN_U32 = 0, 1
 
 
@@ -418,6 +419,13 @@ SIGNATURES["lh_memcheck_prove"] = (C.c_int, [_P, _P, C.POINTER(lh_memcheck_trace
 SIGNATURES["lh_memcheck_verify"] = (C.c_int, [_P, _SZ, _SZ, C.POINTER(C.c_uint32), _T])
 SIGNATURES["lh_debug_memcheck_witness"] = (C.c_int, [_P, C.POINTER(lh_memcheck_trace), _SZ, _SZ, C.POINTER(C.c_uint32), _P, _P, _P,
                                                      _P, C.POINTER(C.c_int)])
+# Spark: the handle is an opaque pointer; lh_spark_free returns nothing
+SIGNATURES["lh_spark_commit"] = (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _P, C.POINTER(_P)])
+SIGNATURES["lh_spark_commitment"] = (C.c_int, [_P, _P, C.POINTER(_SZ)])
+SIGNATURES["lh_spark_open"] = (C.c_int, [_P, _P, _P, C.POINTER(lh_fr), C.POINTER(lh_fr), _T])
+SIGNATURES["lh_spark_free"] = (None, [_P, _P])
+SIGNATURES["lh_spark_verify"] = (C.c_int, [_P, _SZ, _SZ, _SZ, _P, _SZ, C.POINTER(lh_fr), C.POINTER(lh_fr), _T])
+SIGNATURES["lh_debug_spark_e"] = (C.c_int, [_P, _SZ, _SZ, _SZ, _P, _P, C.POINTER(lh_fr), _P, C.POINTER(lh_fr)])
 SIGNATURES["lh_gkr_fractional_verify"] = (C.c_int, [_SZ, _SZ, C.POINTER(C.POINTER(lh_fr)), C.POINTER(C.POINTER(lh_fr)), _T,
                                                     C.POINTER(lh_fr), C.POINTER(lh_fr), C.POINTER(lh_fr), C.POINTER(lh_fr),
                                                     C.POINTER(lh_fr)])

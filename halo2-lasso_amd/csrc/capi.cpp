@@ -242,6 +242,7 @@ void lh_ctx_destroy(lh_ctx* ctx) {
     open_precommit_cancel(ctx->c);
   } catch (...) {
   }
+  spark_free_all(ctx->c);  // (committed sparse polynomials nobody freed: their device memory goes with the ctx)
   if (ctx->c.helper_handle) {
     lh_ctx_destroy(ctx->c.helper_handle);
     ctx->c.helper_handle = nullptr, ctx->c.helper = nullptr;
@@ -716,6 +717,47 @@ lh_status lh_memcheck_prove(lh_ctx* ctx, const lh_srs* srs, const lh_memcheck_tr
   memcheck_prove(ctx->c, mkzg_pcs(ctx->c, srs->s), *trace, num_vars, mem_vars, init, tr);
   LH_CATCH
 }
+// ---------------------------------------------------------------- Spark: commit a sparse polynomial once, open it many times
+lh_status lh_spark_commit(lh_ctx* ctx, const lh_srs* srs, size_t num_vars, size_t dim_vars, size_t num_dims,
+                          const uint32_t* const* d_dims, const lh_fr* d_val, lh_spark_poly** out) {
+  LH_TRY
+  spark_check(num_vars, dim_vars, num_dims);  // (the shape first: refused before the param or the device is touched)
+  NEED_CTX(ctx);
+  NEED(srs);
+  NEED(out);
+  *out = nullptr;
+  *out = (lh_spark_poly*)spark_commit(ctx->c, mkzg_pcs(ctx->c, srs->s), num_vars, dim_vars, num_dims, d_dims, (const Fr*)d_val);
+  LH_CATCH
+}
+lh_status lh_spark_commitment(const lh_spark_poly* poly, uint8_t* out, size_t* len) {
+  LH_TRY
+  NEED(poly);
+  NEED(len);
+  const std::vector<uint8_t>& blob = ((const SparkPoly*)poly)->blob;
+  if (out) {
+    LH_REQUIRE(*len >= blob.size(), LH_ERR_ARG, "spark: the buffer is shorter than the commitment");
+    memcpy(out, blob.data(), blob.size());
+  }
+  *len = blob.size();
+  LH_CATCH
+}
+lh_status lh_spark_open(lh_ctx* ctx, const lh_srs* srs, const lh_spark_poly* poly, const lh_fr* point, lh_fr* out_value,
+                        lh_transcript* t) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(srs);
+  NEED(poly);
+  NEED(point);
+  NEED(out_value);
+  Transcript tr(t);
+  const HFr v = spark_open(ctx->c, mkzg_pcs(ctx->c, srs->s), *(const SparkPoly*)poly, (const HFr*)point, tr);
+  memcpy(out_value, &v, 32);
+  LH_CATCH
+}
+void lh_spark_free(lh_ctx* ctx, lh_spark_poly* poly) {
+  if (!ctx || !poly) return;
+  (void)hipSetDevice(ctx->c.device);
+  spark_free(ctx->c, (SparkPoly*)poly);
+}
 lh_status lh_lasso_last_timing(lh_ctx* ctx, double* out_ms) {
   LH_TRY NEED_CTX(ctx);
   NEED(out_ms);
@@ -1050,6 +1092,21 @@ lh_status lh_memcheck_verify(const lh_mkzg_vp* vp, size_t num_vars, size_t mem_v
   if (memcheck_check(num_vars, mem_vars, init != nullptr) > mkzg_vp_num_vars(*vp->p))
     throw lh::Error(LH_ERR_INVALID_PCS_PARAM, "Too many variates of poly to verify");
   memcheck_verify(mkzg_verifier(*vp->p), num_vars, mem_vars, init, tr);
+  LH_CATCH
+}
+lh_status lh_spark_verify(const lh_mkzg_vp* vp, size_t num_vars, size_t dim_vars, size_t num_dims, const uint8_t* commitment,
+                          size_t commitment_len, const lh_fr* point, const lh_fr* value, lh_transcript* t) {
+  LH_TRY
+  NEED(vp);
+  NEED(commitment);
+  NEED(point);
+  NEED(value);
+  Transcript tr(t);
+  if (spark_check(num_vars, dim_vars, num_dims) > mkzg_vp_num_vars(*vp->p))
+    throw lh::Error(LH_ERR_INVALID_PCS_PARAM, "Too many variates of poly to verify");
+  HFr v;
+  memcpy(&v, value, 32);
+  spark_verify(mkzg_verifier(*vp->p), num_vars, dim_vars, num_dims, commitment, commitment_len, (const HFr*)point, v, tr);
   LH_CATCH
 }
 lh_status lh_hyperplonk_verify(const lh_mkzg_vp* vp, const lh_hp_vparam* hvp, const lh_fr* const* instances,
@@ -2212,6 +2269,16 @@ lh_status lh_debug_memcheck_witness(lh_ctx* ctx, const lh_memcheck_trace* trace,
   NEED(d_m);
   NEED(out_bad);
   *out_bad = memcheck_witness(ctx->c, *trace, num_vars, mem_vars, init, d_rt, d_fv, d_ft, d_m) ? 0 : 1;
+  LH_CATCH
+}
+lh_status lh_debug_spark_e(lh_ctx* ctx, size_t num_vars, size_t dim_vars, size_t num_dims, const uint32_t* const* d_dims,
+                           const lh_fr* d_val, const lh_fr* point, lh_fr* const* d_E, lh_fr* out_value) {
+  LH_TRY
+  spark_check(num_vars, dim_vars, num_dims);
+  NEED_CTX(ctx);
+  NEED(out_value);
+  const HFr v = spark_debug_e(ctx->c, num_vars, dim_vars, num_dims, d_dims, (const Fr*)d_val, (const HFr*)point, (Fr* const*)d_E);
+  memcpy(out_value, &v, 32);
   LH_CATCH
 }
 lh_status lh_debug_sort_plan(size_t n, unsigned bits, int key_bytes, unsigned* passes, unsigned rb[8], size_t* temp_bytes) {

@@ -306,6 +306,8 @@ struct Ctx {
   bool phase_ev_pending = false;
   void phase_times_resolve();  // events -> lasso_ms (waits for the last one)
   hipEvent_t prof_ev[2] = {nullptr, nullptr};
+  // committed sparse polynomials (spark.cpp SparkPoly): device memory outside the arena, freed by lh_spark_free or with the ctx
+  std::vector<struct SparkPoly*> spark_polys;
   void* pin(size_t bytes);  // grows the pinned buffer if needed
   // small device -> host download through a second pinned staging buffer, synchronising: an async copy into
   // pageable memory makes the runtime pin pages on the fly (hundreds of microseconds for a few KB)
@@ -894,6 +896,35 @@ struct MemcheckRangeLeaves {
   Fr *p0_up, *q0_up, *p1_up, *q1_up;
 };
 void k_memcheck_range_leaves(Ctx&, const MemcheckRangeLeaves&, size_t num_vars, bool up, const Fr& delta);
+
+// ------------------------------------------------------------------ Spark (kernels_spark.hip; spark.cpp, tests/spark_ref.py)
+constexpr int SPARK_MAX_DIMS = 3;
+// The memories of an opening in ONE launch: E[j][k] = T[j][dim[j][k]] for the `num_dims` dimensions (T[j]: 2^dim_vars field
+// elements, a 32-byte gather by a u32 index - masked to dim_vars bits, so no index reads out of bounds), and the value
+// v = sum_k val[k] prod_j E[j][k]: per-workgroup partial sums, then one workgroup adds them in a fixed order (the field
+// sum is exact: the order does not matter for the bytes).  *out_value on the host; synchronises.
+// Launch record "spark_e", n items, algorithmic bytes (32 + 68 num_dims) n
+struct SparkE {
+  const uint32_t* dim[SPARK_MAX_DIMS];
+  const Fr* T[SPARK_MAX_DIMS];
+  Fr* E[SPARK_MAX_DIMS];
+  const Fr* val;
+};
+void k_spark_e(Ctx&, const SparkE&, size_t num_dims, size_t n, size_t dim_vars, Fr* out_value);
+// The leaves of the 4 num_dims product trees in ONE launch, side and dimension in blockIdx.y (y = side * num_dims + j),
+// h(a, v, t) = a gamma^2 + v gamma + t - tau:
+//   side 0 (n entries): RS_j[k] = h(dim_j[k], E_j[k], read_ts_j[k]); WS_j = RS_j + 1 is written only where ws[j] is given
+//   side 1 (2^dim_vars cells): Init_j[m] = h(m, T_j[m], 0), Final_j[m] = Init_j[m] + final_cts_j[m]
+// up_n / up_l: the level above that side's leaves (node i = leaf[i] * leaf[i + half]) comes with them (rs_up, ws_up /
+// init_up, fin_up: half the entries each).  Launch record "spark_leaves", num_dims (n + 2^dim_vars) items
+struct SparkLeaves {
+  const uint32_t *dim[SPARK_MAX_DIMS], *rts[SPARK_MAX_DIMS], *fcs[SPARK_MAX_DIMS];
+  const Fr *E[SPARK_MAX_DIMS], *T[SPARK_MAX_DIMS];
+  Fr *rs[SPARK_MAX_DIMS], *ws[SPARK_MAX_DIMS], *init[SPARK_MAX_DIMS], *fin[SPARK_MAX_DIMS];
+  Fr *rs_up[SPARK_MAX_DIMS], *ws_up[SPARK_MAX_DIMS], *init_up[SPARK_MAX_DIMS], *fin_up[SPARK_MAX_DIMS];
+};
+void k_spark_leaves(Ctx&, const SparkLeaves&, size_t num_dims, size_t n, size_t dim_vars, bool up_n, bool up_l, const Fr& gamma,
+                    const Fr& gamma2, const Fr& tau);
 
 void k_lookup_h(Ctx&, const Fr* input, const Fr* table, const Fr* m, const Fr& gamma, size_t n, Fr* h);
 void k_permutation_z(Ctx&, const Fr* const* values, const Fr* const* perms, size_t num_perm, size_t num_chunks,

@@ -812,6 +812,34 @@ void memcheck_verify(const PcsVerifier& pcs, size_t num_vars, size_t mem_vars, c
 bool memcheck_witness(Ctx&, const lh_memcheck_trace& trace, size_t num_vars, size_t mem_vars, const uint32_t* init, uint32_t* d_rt,
                       uint32_t* d_fv, uint32_t* d_ft, uint32_t* d_m);
 
+// ------------------------------------------------------------------ Spark (spark.cpp; tests/spark_ref.py)
+// A committed sparse polynomial: 2^n entries (dim_0 .. dim_{c-1}, val) with indices below 2^l.  Owns ONE device block outside
+// the arena - copies of the index columns, val zero-padded to nv = max(n, l) variables, the access counters - and the
+// commitments of [val | dim_j | read_ts_j | final_cts_j]; listed in Ctx::spark_polys until spark_free or the ctx's end.
+struct SparkPoly {
+  Ctx* ctx = nullptr;
+  size_t n = 0, l = 0, c = 0, nv = 0;
+  void* block = nullptr;
+  const Fr* val = nullptr;  // 2^nv entries
+  const uint32_t *dim[SPARK_MAX_DIMS] = {}, *rts[SPARK_MAX_DIMS] = {}, *fcs[SPARK_MAX_DIMS] = {};  // 2^n, 2^n, 2^l entries
+  uint32_t dim_bits[SPARK_MAX_DIMS] = {}, rts_bits[SPARK_MAX_DIMS] = {}, fcs_bits[SPARK_MAX_DIMS] = {};  // widths (>= 1)
+  std::vector<HG1> comms;     // 1 + 3 c, commitment order
+  std::vector<uint8_t> blob;  // lasso_write_commitments of them on a fresh transcript: the mask element, the points
+};
+// the limits that need no device (shared with the verifier): returns nv = max(num_vars, dim_vars)
+size_t spark_check(size_t num_vars, size_t dim_vars, size_t num_dims);
+SparkPoly* spark_commit(Ctx&, const Pcs&, size_t num_vars, size_t dim_vars, size_t num_dims, const uint32_t* const* d_dims,
+                        const Fr* d_val);
+void spark_free(Ctx&, SparkPoly*);  // (not one of this ctx's: nothing happens)
+void spark_free_all(Ctx&);
+// point: num_dims * dim_vars coordinates; appends the proof, returns the value
+HFr spark_open(Ctx&, const Pcs&, const SparkPoly&, const HFr* point, Transcript& tr);
+void spark_verify(const PcsVerifier& pcs, size_t num_vars, size_t dim_vars, size_t num_dims, const uint8_t* commitment,
+                  size_t commitment_len, const HFr* point, const HFr& value, Transcript& tr);
+// the memory kernel alone (lh_debug_spark_e)
+HFr spark_debug_e(Ctx&, size_t num_vars, size_t dim_vars, size_t num_dims, const uint32_t* const* d_dims, const Fr* d_val,
+                  const HFr* point, Fr* const* d_E);
+
 // ------------------------------------------------------------------ verifiers (verifier.cpp; host only)
 HFr identity_eval(const std::vector<HFr>& x);  // sum_i 2^i x_i (sum_check.rs:123-125)
 // verify_grand_product (oracle/pyref/gkr.py): trees of the given depths; -> the roots, and per tree the claim about its

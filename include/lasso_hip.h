@@ -377,6 +377,40 @@ lh_status lh_memcheck_prove(lh_ctx*, const lh_srs*, const lh_memcheck_trace*, si
                             const uint32_t* init /* host, 2^mem_vars, or NULL */, lh_transcript* t);
 /* (lh_memcheck_verify: with the verifiers below; lh_debug_memcheck_witness: with the debug entries) */
 
+/* Spark (Lasso paper §4; the sparse commitment of Spartan): commit a sparse multilinear polynomial ONCE, prove its
+ * evaluations at any number of points.  D in num_dims * dim_vars variables is given by 2^num_vars entries
+ * (d_dims[0][k], .., d_dims[num_dims-1][k], d_val[k]): DEVICE columns uint32_t[2^num_vars] with values < 2^dim_vars and a
+ * DEVICE column of 2^num_vars field elements (Montgomery form, as every device table here).
+ *   D~(r_0, .., r_{num_dims-1}) = sum_k val[k] prod_j eq(r_j, dims[j][k]),   r_j = point[j dim_vars .. (j + 1) dim_vars)
+ * Coordinate i of r_j belongs to bit i of dims[j]; the dense index is sum_j dims[j] << (j dim_vars); entries with the same
+ * index add up; pad with val = 0 entries.  num_dims = 1 is a sparse vector, 2 a matrix.  Commit and open cost follows
+ * 2^num_vars + 2^dim_vars, never 2^(num_dims dim_vars).  The protocol is specified in tests/spark_ref.py.
+ *
+ * lh_spark_commit copies the columns, counts the accesses (read_ts, final_cts) and commits the 1 + 3 num_dims polys
+ * [val | dims | read_ts | final_cts], each zero-padded to nv = max(num_vars, dim_vars) variables.  The handle owns its
+ * device memory (outside the proof arena) and the commitment; it is freed by lh_spark_free or with its ctx, and may be
+ * opened any number of times: an opening runs no counter, no sort and no MSM over the committed columns.
+ * lh_spark_commitment: the commitment bytes - the identity mask (one field element, big-endian as on a transcript), then the
+ * non-identity points; out NULL: *len alone; else *len is the room in and the length out.
+ * lh_spark_open appends the proof of D~(point) to t and returns the value in *out_value (point and value: HOST lh_fr).
+ * Limits (LH_ERR_ARG with a message, checked on entry):
+ *   1 <= num_dims <= LH_SPARK_MAX_DIMS       one sum-check term of num_dims + 1 <= LH_SC_MAX_FACTORS factors
+ *   1 <= dim_vars <= LH_SPARK_MAX_DIM_VARS   an eq table per dimension: 2^dim_vars * 32 B
+ *   1 <= num_vars < 31                       Lasso's bound: the access counters and their sort index entries by 32-bit words
+ *   an index >= 2^dim_vars: "spark: index out of range" (the ctx stays usable)
+ *   no NULL argument; not on a ctx inside a sharded prove, nor on one with a communicator of several ranks
+ * LH_ERR_INVALID_PCS_PARAM when nv exceeds the SRS.  Multilinear KZG only. */
+#define LH_SPARK_MAX_DIMS 3
+#define LH_SPARK_MAX_DIM_VARS 24
+typedef struct lh_spark_poly lh_spark_poly;
+lh_status lh_spark_commit(lh_ctx*, const lh_srs*, size_t num_vars, size_t dim_vars, size_t num_dims,
+                          const uint32_t* const* d_dims, const lh_fr* d_val, lh_spark_poly** out);
+lh_status lh_spark_commitment(const lh_spark_poly*, uint8_t* out, size_t* len);
+lh_status lh_spark_open(lh_ctx*, const lh_srs*, const lh_spark_poly*, const lh_fr* point /* num_dims * dim_vars */,
+                        lh_fr* out_value, lh_transcript* t);
+void lh_spark_free(lh_ctx*, lh_spark_poly*);
+/* (lh_spark_verify: with the verifiers below; lh_debug_spark_e: with the debug entries) */
+
 /* per-phase wall-clock of the last lh_lasso_prove on this ctx, milliseconds:
  * [witness, commit, surge, leaves+trees, gkr, evals, open_n, open_l, total] */
 #define LH_LASSO_NUM_PHASES 9
@@ -444,6 +478,7 @@ lh_status lh_lasso_last_timing(lh_ctx*, double* out_ms);
  *                             (csrc/kernels_logup.hip logup_leaves_up: the input side never reads a table of ones); 0: the
  *                             leaves in one launch, then one frac_up launch per fraction.  lh_memcheck_prove's two leaf
  *                             kernels follow the same switch (the level above the trees' and the fractions' leaves)
+ *                             and so does lh_spark_open's leaf kernel (0: the leaves only, and every write leaf stored)
  *   comm_round           0    how the partial sums of a sharded sum-check round are combined over the ranks:
  *                             0 = ncclAllGather of every rank's sums + a one-thread sum-and-publish kernel;
  *                             1 = ONE collective: the round kernel leaves its sums as u64 lanes (32-bit limb | tag << 40),
@@ -691,6 +726,13 @@ lh_status lh_logup_gkr_verify(const lh_mkzg_vp* vp, const lh_logup_lookup* looku
  * LH_ERR_INVALID_SNARK whichever piece finds it out.  The image's multilinear extension is evaluated here, 2^mem_vars field
  * operations. */
 lh_status lh_memcheck_verify(const lh_mkzg_vp* vp, size_t num_vars, size_t mem_vars, const uint32_t* init, lh_transcript* t);
+/* the verifier of lh_spark_open (tests/spark_ref.py verify; host only): `commitment` are the bytes of lh_spark_commitment,
+ * `point` the num_dims * dim_vars coordinates, `value` the claimed D~(point).  The same limits as the prover's;
+ * LH_ERR_INVALID_PCS_PARAM when max(num_vars, dim_vars) exceeds the param; a proof that does not verify, a proof of another
+ * value and a malformed commitment (mask out of range, wrong length, a point off the curve) are LH_ERR_INVALID_SNARK.  The eq
+ * tables' extensions come in closed form: no work of order 2^dim_vars. */
+lh_status lh_spark_verify(const lh_mkzg_vp* vp, size_t num_vars, size_t dim_vars, size_t num_dims, const uint8_t* commitment,
+                          size_t commitment_len, const lh_fr* point, const lh_fr* value, lh_transcript* t);
 typedef struct lh_hp_vparam { /* HyperPlonkVerifierParam (hyperplonk.rs:57-74) */
   size_t num_vars;
   size_t num_instance_polys;
@@ -1110,6 +1152,11 @@ lh_status lh_debug_lasso_counters(lh_ctx*, const uint32_t* const* d_dims, size_t
  * columns are then unspecified.  The call itself still returns LH_OK. */
 lh_status lh_debug_memcheck_witness(lh_ctx*, const lh_memcheck_trace*, size_t num_vars, size_t mem_vars, const uint32_t* init,
                                     uint32_t* d_rt, uint32_t* d_fv, uint32_t* d_ft, uint32_t* d_m, int* out_bad);
+/* the memory kernel of lh_spark_open on its own (csrc/kernels_spark.hip spark_e): d_E[j][k] = eq(r_j, d_dims[j][k]) for the
+ * num_dims dimensions (DEVICE, 2^num_vars field elements each), *out_value = sum_k d_val[k] prod_j d_E[j][k] (host).  Shapes
+ * and limits as lh_spark_commit; an index >= 2^dim_vars is LH_ERR_ARG "spark: index out of range". */
+lh_status lh_debug_spark_e(lh_ctx*, size_t num_vars, size_t dim_vars, size_t num_dims, const uint32_t* const* d_dims,
+                           const lh_fr* d_val, const lh_fr* point, lh_fr* const* d_E, lh_fr* out_value);
 /* the pass plan of one slab (host only, no GPU needed): the number of radix passes, the digit width of each (rb[passes ..
  * 8) = 0; `bits` above the key width count as the key width) and the temporary device bytes the sort takes */
 lh_status lh_debug_sort_plan(size_t n, unsigned bits, int key_bytes, unsigned* passes, unsigned rb[8], size_t* temp_bytes);
