@@ -290,6 +290,9 @@ GrandProductResult prove_grand_product(Ctx&, size_t num_trees, const Fr* const* 
                                        Transcript& tr, const Fr* const* d_level_up = nullptr,
                                        const uint8_t* plus_one = nullptr,
                                        const std::function<void()>& trees_built = nullptr);
+// from this many variables on a caller makes the level above a tree's leaves together with them (the tree builder takes the
+// level from 11 variables on)
+constexpr size_t GP_LEVEL_UP_MIN_VARS = 12;
 
 // ------------------------------------------------------------------ pcs::multilinear::kzg
 struct Srs {
@@ -554,6 +557,76 @@ Pcs ipa_pcs(Ctx&, const IpaParams&, size_t poly_size);     // ipa.cpp (no shard_
 Pcs hyrax_pcs(Ctx&, const IpaParams&, size_t poly_size, size_t batch_size);
 // (brakedown_pcs: brakedown.hpp - it needs the hash transcript and the commitments of the polys the caller committed)
 
+// ------------------------------------------------------------------ steps shared by the arguments (argument.cpp)
+// What Lasso, LogUp-GKR, memory checking and Spark all do, defined once; a new argument starts from these.
+// bit length of v (0 for 0); a width that must be at least one bit says std::max(bit_length(v), 1u)
+inline uint32_t bit_length(uint64_t v) { return v ? 64u - (uint32_t)__builtin_clzll(v) : 0u; }
+// one entry of an opening list: poly `poly` at point `point` is *value (null: zero, to be filled in later)
+inline lh_evaluation make_evaluation(size_t poly, size_t point, const HFr* value) {
+  lh_evaluation e;
+  memset(&e, 0, sizeof(e));
+  e.poly = (uint32_t)poly, e.point = (uint32_t)point;
+  if (value) memcpy(&e.value, value, 32);
+  return e;
+}
+// The refusals of the stand-alone argument `name` (the prefix of every message).  Prover: no sharded proofs; a scheme whose
+// commitment is one point over bases (batch_commit too where the argument commits field-element tables) that reaches nv
+// variables.  Verifier: commitments of one point.
+void argument_not_sharded(Ctx&, const std::string& name);
+void argument_pcs_check(const Pcs&, size_t nv, const std::string& name, bool needs_batch_commit);
+void argument_pcs_check(const PcsVerifier&, const std::string& name);
+// Commits u32 columns of their own lengths, each a 32-bit MSM against the bases of level nv (zero-padding is implicit) whose
+// width max(bit_length(OR of its entries), 1) is promised to the MSM: ONE k_or_u32 per distinct length over the columns
+// whose OR the caller does not hold already (known_or), ONE msm_batch.  -> the points; bits[k]: column k's width, which the
+// opening is promised too (SmallPoly::bits).  A width that differs between the two gives a wrong commitment: THE rule is here.
+struct U32Column {
+  const uint32_t* ptr;
+  size_t len;
+  const uint32_t* known_or = nullptr;
+};
+std::vector<HG1> commit_u32_columns(Ctx&, const Pcs&, size_t nv, const std::vector<U32Column>& cols, uint32_t* bits);
+// u32 columns of 2^vars entries evaluated at `point`, against its full eq table (scratch of this call)
+void evaluate_u32_columns(Ctx&, const uint32_t* const* cols, size_t count, const HFr* point, size_t vars, HFr* out);
+// The four product trees per memory of ONE grand-product GKR over A memories: RS, WS of memory b (n variables) at 2 b and
+// 2 b + 1, behind them Init, Final (l variables) at 2 A + 2 b and 2 A + 2 b + 1.  ws_plus_one (Lasso, Spark): write leaf =
+// read leaf + 1: where the n-variable trees are alone at their leaf layer that layer runs over the read-set tables only
+// (prove_grand_product: plus_one) and the write-set leaves are never stored (ws_implicit).  The caller fills the leaves.
+struct MemoryTrees {
+  size_t A;
+  bool ws_plus_one;
+  std::vector<const Fr*> leaves, level_up;
+  std::vector<size_t> depths;
+  std::vector<uint8_t> plus_one;
+  MemoryTrees(size_t A_, size_t n, bool ws_plus_one_ = true)
+      : A(A_), ws_plus_one(ws_plus_one_), leaves(4 * A_), level_up(4 * A_, nullptr), depths(4 * A_, n), plus_one(4 * A_, 0) {}
+  struct Memory {
+    Fr *rs, *ws, *rs_up, *ws_up, *init, *fin, *init_up, *fin_up;
+  };
+  // memory b's leaf tables (N and M = 2^l entries; up_n / up_l: the level above the n- / l-variable leaves comes with them)
+  Memory add(Ctx& c, size_t b, size_t N, size_t l, bool up_n, bool ws_implicit, bool up_l = false);
+  GrandProductResult prove(Ctx& c, Transcript& tr, const std::function<void()>& trees_built = nullptr) {
+    return prove_grand_product(c, 4 * A, leaves.data(), depths.data(), tr, level_up.data(), ws_plus_one ? plus_one.data() : nullptr,
+                               trees_built);
+  }
+};
+// the verifiers' side of those trees: the fingerprint h(a, v, t) = a gamma^2 + v gamma + t - tau of a memory operation
+struct Fingerprint {
+  HFr gamma, tau;
+  HFr operator()(const HFr& a, const HFr& v, const HFr& t) const { return a * gamma * gamma + v * gamma + t - tau; }
+};
+// the LogUp identity on the roots of two fractions: P_0 / Q_0 + P_1 / Q_1 = 0 with both denominators non-zero
+inline bool logup_roots_cancel(const HFr& p0, const HFr& q0, const HFr& p1, const HFr& q1) {
+  return !q0.is_zero() && !q1.is_zero() && (p0 * q1 + p1 * q0).is_zero();
+}
+// the multilinear extension at x (variable i = index bit i) of a host table of 2^l rows, row(r) its entry r: one fold over
+// the rows (the first, which reads them, over the host pool)
+HFr host_table_eval(size_t l, const std::vector<HFr>& x, const std::function<HFr(size_t)>& row);
+// The verdict of a verifier entry: a proof that does not verify is LH_ERR_INVALID_SNARK whichever piece found it out (a round
+// message, an opening, bytes that are no point or no field element, a proof that ends early): the message keeps the piece's
+// own words behind "<name>: ".  What is wrong with the call, not with the proof, keeps its code (LH_ERR_ARG,
+// LH_ERR_INVALID_PCS_PARAM).
+void argument_verdict(const std::string& name, const std::function<void()>& verify);
+
 // ------------------------------------------------------------------ Lasso
 // pieces of the argument shared by the standalone prover (lasso.cpp) and HyperPlonk's Lasso lookups (hyperplonk.cpp)
 struct SubtableOrders;
@@ -633,13 +706,7 @@ inline void lasso_opening_walk(const LassoLayout& lay, const LassoOpening& o, co
 }
 // the list appended to `evs`, with the values of `cl` or (null) zeros that lasso_evaluation_values fills later
 inline void lasso_evaluation_list(const LassoLayout& lay, const LassoOpening& o, const LassoClaims* cl, std::vector<lh_evaluation>& evs) {
-  lasso_opening_walk(lay, o, cl, [&](size_t poly, size_t point, const HFr* val) {
-    lh_evaluation e;
-    memset(&e, 0, sizeof(e));
-    e.poly = (uint32_t)poly, e.point = (uint32_t)point;
-    if (val) memcpy(&e.value, val, 32);
-    evs.push_back(e);
-  });
+  lasso_opening_walk(lay, o, cl, [&](size_t poly, size_t point, const HFr* val) { evs.push_back(make_evaluation(poly, point, val)); });
 }
 // the values of a list made without claims, in place: the same walk
 inline void lasso_evaluation_values(const LassoLayout& lay, const LassoOpening& o, const LassoClaims& cl, lh_evaluation* evs) {
@@ -664,8 +731,6 @@ inline bool lasso_g_coeff_fits(const lh_lasso_table& tb, size_t m, unsigned bits
   if (low) *low = canon[0];
   return !canon[1] && !canon[2] && !canon[3] && (bits >= 64 || !(canon[0] >> bits));
 }
-// bit length of v (0 for 0); a width that must be at least one bit says std::max(bit_length(v), 1u)
-inline uint32_t bit_length(uint64_t v) { return v ? 64u - (uint32_t)__builtin_clzll(v) : 0u; }
 constexpr uint32_t LH_SUBTABLE_KINDS = 6;  // IDENTITY .. LTU (include/lasso_hip.h)
 // Caller-registered subtables (subtable.cpp; include/lasso_hip.h lh_subtable_register): kinds from LH_SUBTABLE_CUSTOM_BASE up.
 // Immutable once registered; the shared_ptr of a lookup keeps the entries alive past an unregister on another thread.

@@ -20,18 +20,12 @@
 //                          ten limbs (wide.cuh), one reduction per output to the canonical Montgomery value bd_gather stores
 #include <hip/hip_runtime.h>
 #include "brakedown.hpp"
+#include "launch.cuh"
 #include "wide.cuh"
 
 namespace lh {
 
-#define GSTRIDE(i, n) \
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (size_t)gridDim.x * blockDim.x)
-static inline dim3 grid_for(size_t n, int block = 256, size_t cap = 8192) {
-  size_t g = (n + block - 1) / block;
-  if (g < 1) g = 1;
-  if (g > cap) g = cap;
-  return dim3((unsigned)g);
-}
+constexpr size_t BD_GRID_CAP = 8192;  // (the cap of this file's element-wise launches)
 
 // ------------------------------------------------------------------ encoder stages
 __global__ void bd_gather_kernel(Fr* __restrict__ rows, size_t num_rows, size_t cw, size_t in_off, size_t out_off,
@@ -50,7 +44,7 @@ void k_bd_gather(Ctx& c, Fr* rows, size_t num_rows, size_t cw, size_t in_off, si
   if (!m || !num_rows) return;
   ProfScope ps(c, "bd_gather", 64.0 * num_rows * mat.dim.n * mat.dim.d, (double)num_rows * mat.dim.n * mat.dim.d,
                (double)num_rows * m);
-  hipLaunchKernelGGL(bd_gather_kernel, grid_for(num_rows * m), 256, 0, c.stream, rows, num_rows, cw, in_off, out_off, m,
+  hipLaunchKernelGGL(bd_gather_kernel, grid_for(num_rows * m, 256, BD_GRID_CAP), 256, 0, c.stream, rows, num_rows, cw, in_off, out_off, m,
                      mat.d_ptr, mat.d_idx, mat.d_val);
 }
 
@@ -87,7 +81,7 @@ void k_bd_gather_u32(Ctx& c, const BdColumn* d_cols, size_t num_cols, Fr* rows, 
   if (!m || !num_rows) return;
   ProfScope ps(c, "bd_gather_u32", 40.0 * num_cols * num_rows * mat.dim.n * mat.dim.d,
                (double)num_cols * num_rows * mat.dim.n * mat.dim.d / 8, (double)num_cols * num_rows * m);
-  dim3 g = grid_for(num_rows * m);
+  dim3 g = grid_for(num_rows * m, 256, BD_GRID_CAP);
   g.y = (unsigned)num_cols;
   hipLaunchKernelGGL(bd_gather_u32_kernel, g, 256, 0, c.stream, d_cols, rows, num_rows, row_len, cw, m, mat.d_ptr,
                      mat.d_idx, mat.d_val);
@@ -278,7 +272,7 @@ __global__ void bd_load_rows_kernel(const Fr* const* __restrict__ polys, size_t 
 void k_bd_load_rows(Ctx& c, const Fr* const* d_polys, size_t num_polys, size_t num_rows, size_t row_len, size_t cw, Fr* rows) {
   LH_REQUIRE(num_polys >= 1 && num_polys <= BD_MAX_BATCH, LH_ERR_ARG, "brakedown: too many polys in one batch");
   ProfScope ps(c, "bd_load_rows", 64.0 * num_polys * num_rows * row_len, 0, (double)num_polys * num_rows * row_len);
-  dim3 g = grid_for(num_rows * row_len);
+  dim3 g = grid_for(num_rows * row_len, 256, BD_GRID_CAP);
   g.y = (unsigned)num_polys;
   hipLaunchKernelGGL(bd_load_rows_kernel, g, 256, 0, c.stream, d_polys, num_rows, row_len, cw, rows);
 }
@@ -304,7 +298,7 @@ void k_bd_load_columns(Ctx& c, const BdColumn* d_cols, size_t num_cols, size_t n
   LH_REQUIRE(num_cols >= 1 && num_cols <= BD_MAX_BATCH, LH_ERR_ARG, "brakedown: too many columns in one batch");
   ProfScope ps(c, "bd_load_columns", 36.0 * num_cols * num_rows * row_len, (double)num_cols * num_rows * row_len,
                (double)num_cols * num_rows * row_len);
-  dim3 g = grid_for(num_rows * row_len);
+  dim3 g = grid_for(num_rows * row_len, 256, BD_GRID_CAP);
   g.y = (unsigned)num_cols;
   hipLaunchKernelGGL(bd_load_columns_kernel, g, 256, 0, c.stream, d_cols, num_rows, row_len, cw, rows);
 }
@@ -329,7 +323,7 @@ __global__ void bd_gather_roots_kernel(const uint64_t* __restrict__ trees, size_
   GSTRIDE(t, 4 * num_polys) out[t] = trees[(t / 4) * tree_stride + root_off + (t & 3)];
 }
 void k_bd_gather_roots(Ctx& c, const uint64_t* trees, size_t num_polys, size_t tree_stride, size_t root_off, uint64_t* out) {
-  hipLaunchKernelGGL(bd_gather_roots_kernel, grid_for(4 * num_polys), 256, 0, c.stream, trees, tree_stride, root_off,
+  hipLaunchKernelGGL(bd_gather_roots_kernel, grid_for(4 * num_polys, 256, BD_GRID_CAP), 256, 0, c.stream, trees, tree_stride, root_off,
                      num_polys, out);
 }
 
@@ -394,7 +388,7 @@ void k_bd_combine(Ctx& c, const Fr* poly, size_t num_rows, size_t row_len, size_
                   Fr* out) {
   LH_REQUIRE(num_sets >= 1 && num_sets <= BD_MAX_SETS, LH_ERR_ARG, "brakedown: too many combinations in one pass");
   ProfScope ps(c, "bd_combine", 32.0 * num_rows * row_len, (double)num_sets * num_rows * row_len, (double)row_len);
-  hipLaunchKernelGGL(bd_combine_kernel, grid_for(row_len), 256, 0, c.stream, poly, num_rows, row_len, stride, coeffs,
+  hipLaunchKernelGGL(bd_combine_kernel, grid_for(row_len, 256, BD_GRID_CAP), 256, 0, c.stream, poly, num_rows, row_len, stride, coeffs,
                      num_sets, out);
 }
 

@@ -13,20 +13,11 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include "dev.hpp"
+#include "launch.cuh"
 #include "reduce.cuh"
 #include "resident.cuh"
 
 namespace lh {
-
-#define GSTRIDE(i, n) \
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (size_t)gridDim.x * blockDim.x)
-
-static inline dim3 grid_for(size_t n, int block = 256, size_t cap = 4096) {
-  size_t g = (n + block - 1) / block;
-  if (g < 1) g = 1;
-  if (g > cap) g = cap;
-  return dim3((unsigned)g);
-}
 
 // ------------------------------------------------------------------ BooleanHypercube on the device (bh.rs:143-153)
 __device__ __forceinline__ uint32_t bh_rotate(uint32_t b, int rot, uint32_t num_vars, uint32_t primitive, uint32_t x_inv) {
@@ -234,9 +225,7 @@ void k_sc_round_ext(Ctx& c, const ExtRound& rd, int degree, bool bind, size_t si
   ArenaScope scope(c.arena);
   // one thread per (pair, monomial) while that still fits a few waves per SIMD, else one thread per pair
   const uint32_t tp = (rd.num_terms > 1 && size * rd.num_terms <= ((size_t)1 << 19)) ? rd.num_terms : 1u;
-  size_t g = (size * tp + 255) / 256;
-  size_t cap = (size_t)c.num_cus * 8;
-  if (g > cap) g = cap;
+  const size_t g = cu_grid(c, size * tp);
   evals_host = c.round_out(evals_host);  // (sharded rounds: the sums stay on the device, sumcheck.cpp)
   Fr* partials = g == 1 ? evals_host : c.arena.alloc_n<Fr>(g * degree);
   const ScFinishArgs fin = c.finish_for((uint32_t)g, evals_host, seq);

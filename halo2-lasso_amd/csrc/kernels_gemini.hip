@@ -11,12 +11,11 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include "dev.hpp"
+#include "launch.cuh"
 #include "reduce.cuh"
 
 namespace lh {
 
-#define GSTRIDE(i, n) \
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (size_t)gridDim.x * blockDim.x)
 static inline unsigned blocks_for(size_t n, size_t block = 256, size_t cap = 4096) {
   size_t g = (n + block - 1) / block;
   return (unsigned)(g < 1 ? 1 : g > cap ? cap : g);

@@ -12,12 +12,11 @@
 #include <algorithm>
 #include "dev.hpp"
 #include "ff_host.hpp"
+#include "launch.cuh"
 #include "reduce.cuh"
 
 namespace lh {
 
-#define GSTRIDE(i, n) \
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (size_t)gridDim.x * blockDim.x)
 static inline unsigned blocks_for(size_t n, size_t block, size_t cap) {
   size_t g = (n + block - 1) / block;
   return (unsigned)(g < 1 ? 1 : g > cap ? cap : g);

@@ -6,12 +6,10 @@
 #include <cstring>
 #include "dev.hpp"
 #include "ff_host.hpp"
+#include "launch.cuh"
 #include "wide.cuh"
 
 namespace lh {
-
-#define GSTRIDE(i, n) \
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (size_t)gridDim.x * blockDim.x)
 
 // ------------------------------------------------------------------ compress: out = sum_j beta^j col_j
 // One pass: width * 32 B read and 32 B written per row; the column pointers and the powers travel in the kernel arguments
@@ -37,7 +35,7 @@ void k_logup_compress(Ctx& c, const Fr* const* cols, const Fr* pows, size_t widt
     p.col[j] = cols[j], p.pow[j] = pows[j];
   }
   ProfScope ps(c, "logup_compress", (width + 1) * 32.0 * n, (width - 1.0) * n, (double)n);
-  const unsigned grid = (unsigned)std::min<size_t>((n + 255) / 256, (size_t)c.num_cus * 8);
+  const unsigned grid = cu_grid(c, n);
   hipLaunchKernelGGL(logup_compress_kernel, dim3(grid), dim3(256), 0, c.stream, p, n, out);
 }
 
@@ -80,18 +78,6 @@ __global__ __launch_bounds__(256) void logup_compress_cols_kernel(LogupCompressC
     }
   }
 }
-// host: w (Montgomery form) -> w R (Montgomery form), the weight wide_redc expects (kernels_poly.hip's prescale_r, which is
-// local to that file)
-static Fr logup_prescale_r(const Fr& w) {
-  uint64_t c[4];
-  for (int k = 0; k < 4; k++) c[k] = (uint64_t)FrParams::r1(2 * k) | ((uint64_t)FrParams::r1(2 * k + 1) << 32);
-  host::Fr h;
-  memcpy(&h, &w, sizeof(h));
-  h = h * host::Fr::from_canonical(c);  // the field element R mod r
-  Fr out;
-  memcpy(&out, &h, sizeof(out));
-  return out;
-}
 void k_logup_compress_cols(Ctx& c, const void* const* cols, const uint8_t* u32, const Fr* pows, size_t width, size_t n, Fr* out) {
   LH_REQUIRE(width >= 1 && width <= (size_t)LOGUP_MAX && n >= 1, LH_ERR_ARG, "logup_compress_cols: bad shape");
   LogupCompressCols p;
@@ -99,7 +85,7 @@ void k_logup_compress_cols(Ctx& c, const void* const* cols, const uint8_t* u32, 
   for (size_t j = 0; j < width; j++) {
     LH_REQUIRE(cols[j] != nullptr, LH_ERR_ARG, "logup_compress_cols: null column");
     if (u32[j]) {
-      p.sm[p.num_sm] = (const uint32_t*)cols[j], p.wsm[p.num_sm++] = logup_prescale_r(pows[j]);
+      p.sm[p.num_sm] = (const uint32_t*)cols[j], p.wsm[p.num_sm++] = prescale_r(pows[j]);
     } else {
       p.fr[p.num_fr] = (const Fr*)cols[j], p.wfr[p.num_fr++] = pows[j];
     }
@@ -108,7 +94,7 @@ void k_logup_compress_cols(Ctx& c, const void* const* cols, const uint8_t* u32, 
   ProfScope ps(c, "logup_compress_cols", (4.0 * p.num_sm + 32.0 * p.num_fr + 32.0) * n, (0.07 * p.num_sm + 0.6 + p.num_fr) * n,
                (double)n);
   const bool four = n % 1024 == 0;
-  const unsigned grid = (unsigned)std::min<size_t>((n + (four ? 1023 : 255)) / (four ? 1024 : 256), (size_t)c.num_cus * 8);
+  const unsigned grid = cu_grid(c, n, four ? 1024 : 256);
   if (four) hipLaunchKernelGGL(logup_compress_cols_kernel<4>, dim3(grid), dim3(256), 0, c.stream, p, n, out);
   else hipLaunchKernelGGL(logup_compress_cols_kernel<1>, dim3(grid), dim3(256), 0, c.stream, p, n, out);
 }
@@ -150,7 +136,7 @@ void k_logup_leaves(Ctx& c, const LogupLeaves& a, size_t count, size_t num_vars,
   const double per = table_side ? 2 * (4.0 + 32.0 + 64.0) + (up ? 64.0 : 0.0) : 2 * (32.0 + 32.0) + (up ? 64.0 : 0.0);
   ProfScope ps(c, up ? "logup_leaves_up" : "logup_leaves", per * half * count + (table_side ? 0.0 : 64.0 * half),
                ((table_side ? 2.0 : 0.0) + (up ? (table_side ? 3.0 : 1.0) : 0.0)) * half * count, (double)half * count);
-  const dim3 grid((unsigned)std::min<size_t>((half + 255) / 256, (size_t)c.num_cus * 8), (unsigned)count);
+  const dim3 grid(cu_grid(c, half), (unsigned)count);
   if (table_side && up) hipLaunchKernelGGL((logup_leaves_kernel<true, true>), grid, dim3(256), 0, c.stream, a, half, gamma);
   else if (table_side) hipLaunchKernelGGL((logup_leaves_kernel<true, false>), grid, dim3(256), 0, c.stream, a, half, gamma);
   else if (up) hipLaunchKernelGGL((logup_leaves_kernel<false, true>), grid, dim3(256), 0, c.stream, a, half, gamma);

@@ -7,34 +7,10 @@
 #include <cstring>
 #include "dev.hpp"
 #include "ff_host.hpp"
+#include "launch.cuh"
 #include "wide.cuh"
 
 namespace lh {
-
-#define GSTRIDE(i, n) \
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (size_t)gridDim.x * blockDim.x)
-
-static unsigned memcheck_grid(const Ctx& c, size_t work, size_t per_block = 256) {
-  return (unsigned)std::max<size_t>(1, std::min<size_t>((work + per_block - 1) / per_block, (size_t)c.num_cus * 8));
-}
-// host: w (Montgomery form) -> w R (Montgomery form), the weight wide_redc expects (kernels_poly.hip's prescale_r, which is
-// local to that file)
-static Fr memcheck_prescale_r(const Fr& w) {
-  uint64_t c[4];
-  for (int k = 0; k < 4; k++) c[k] = (uint64_t)FrParams::r1(2 * k) | ((uint64_t)FrParams::r1(2 * k + 1) << 32);
-  host::Fr h;
-  memcpy(&h, &w, sizeof(h));
-  h = h * host::Fr::from_canonical(c);  // the field element R mod r
-  Fr out;
-  memcpy(&out, &h, sizeof(out));
-  return out;
-}
-// a 32-bit integer as a field element: 8 multiply-adds and one reduction (one_r = R^2 mod r, the prescaled one)
-__device__ __forceinline__ Fr memcheck_small(const Fr& one_r, uint32_t v) {
-  Wide w = Wide::zero();
-  wide_mac(w, one_r, v);
-  return wide_redc(w);
-}
 
 // ------------------------------------------------------------------ 1. the trace's witness
 // The operations sorted stably by cell (skey: the addresses, sidx: the positions they came from - ascending inside a cell's
@@ -82,7 +58,7 @@ bool k_memcheck_trace(Ctx& c, const uint32_t* addr, const uint32_t* rv, const ui
   else LH_HIP(hipMemsetAsync(fv, 0, cells * sizeof(uint32_t), c.stream));
   LH_HIP(hipMemsetAsync(ft, 0, cells * sizeof(uint32_t), c.stream));
   sort_pairs_u32(c, addr, skey, nullptr, sidx, n, (unsigned)mem_vars);  // (no values given: the positions)
-  hipLaunchKernelGGL(memcheck_trace_kernel, dim3(memcheck_grid(c, n)), dim3(256), 0, c.stream, skey, sidx, rv, wv, d_init, n, cells,
+  hipLaunchKernelGGL(memcheck_trace_kernel, dim3(cu_grid(c, n)), dim3(256), 0, c.stream, skey, sidx, rv, wv, d_init, n, cells,
                      rt, fv, ft, bad);
   uint32_t h_bad = 0;
   c.d2h(&h_bad, bad, sizeof(uint32_t));  // the one flag readback of a proof
@@ -127,7 +103,7 @@ void k_memcheck_m(Ctx& c, const uint32_t* rt, size_t n, uint32_t* m) {
   // 4 n read, 4 n cleared, at most 4 n added
   ProfScope ps(c, "memcheck_m", 12.0 * n, 0.0, (double)n);
   LH_HIP(hipMemsetAsync(m, 0, n * sizeof(uint32_t), c.stream));
-  hipLaunchKernelGGL(memcheck_m_kernel, dim3(memcheck_grid(c, n)), dim3(256), 0, c.stream, rt, n, m);
+  hipLaunchKernelGGL(memcheck_m_kernel, dim3(cu_grid(c, n)), dim3(256), 0, c.stream, rt, n, m);
 }
 
 // ------------------------------------------------------------------ 3. memory leaves (+ the level above), both sides in one launch
@@ -230,8 +206,8 @@ void k_memcheck_leaves(Ctx& c, const MemcheckLeaves& a, size_t num_vars, size_t 
   }
   // per operation 16 B read and two leaves (64 B) written, per cell 12 B (8 without an image) and 64 B; + 32 B with the level above
   ProfScope ps(c, "memcheck_leaves", bytes, 6.0 * (len[0] + len[1]), (double)(len[0] + len[1]));
-  const dim3 grid((unsigned)std::min<size_t>(tiles, (size_t)c.num_cus * 8), 2u);
-  const Fr g1 = memcheck_prescale_r(gamma), g2 = memcheck_prescale_r(gamma2), o1 = memcheck_prescale_r(Fr::one());
+  const dim3 grid(cu_grid(c, tiles, 1), 2u);
+  const Fr g1 = prescale_r(gamma), g2 = prescale_r(gamma2), o1 = prescale_r(Fr::one());
   if (vec) hipLaunchKernelGGL(memcheck_leaves_kernel<true>, grid, dim3(256), 0, c.stream, p, g1, g2, o1, tau);
   else hipLaunchKernelGGL(memcheck_leaves_kernel<false>, grid, dim3(256), 0, c.stream, p, g1, g2, o1, tau);
 }
@@ -249,9 +225,9 @@ __global__ __launch_bounds__(256) void memcheck_range_leaves_kernel(MemcheckRang
 #pragma unroll
     for (int s = 0; s < 2; s++) {
       const size_t j = i + (s ? half : 0);
-      q0[s] = add(delta, memcheck_small(one_r, (uint32_t)j - a.rt[j]));
-      p1[s] = neg(memcheck_small(one_r, a.m[j]));
-      q1[s] = add(delta, memcheck_small(one_r, (uint32_t)j));
+      q0[s] = add(delta, wide_small(one_r, (uint32_t)j - a.rt[j]));
+      p1[s] = neg(wide_small(one_r, a.m[j]));
+      q1[s] = add(delta, wide_small(one_r, (uint32_t)j));
       a.ones[j] = one;
       a.q0[j] = q0[s];
       a.p1[j] = p1[s];
@@ -272,9 +248,9 @@ void k_memcheck_range_leaves(Ctx& c, const MemcheckRangeLeaves& a, size_t num_va
   const size_t half = (size_t)1 << (num_vars - 1);
   ProfScope ps(c, "memcheck_range_leaves", (2 * (8.0 + 4 * 32.0) + (up ? 4 * 32.0 : 0.0)) * half, (up ? 4.0 : 0.0) * half,
                (double)(2 * half));
-  const Fr o1 = memcheck_prescale_r(Fr::one());
-  if (up) hipLaunchKernelGGL(memcheck_range_leaves_kernel<true>, dim3(memcheck_grid(c, half)), dim3(256), 0, c.stream, a, half, delta, o1);
-  else hipLaunchKernelGGL(memcheck_range_leaves_kernel<false>, dim3(memcheck_grid(c, half)), dim3(256), 0, c.stream, a, half, delta, o1);
+  const Fr o1 = prescale_r(Fr::one());
+  if (up) hipLaunchKernelGGL(memcheck_range_leaves_kernel<true>, dim3(cu_grid(c, half)), dim3(256), 0, c.stream, a, half, delta, o1);
+  else hipLaunchKernelGGL(memcheck_range_leaves_kernel<false>, dim3(cu_grid(c, half)), dim3(256), 0, c.stream, a, half, delta, o1);
 }
 
 }  // namespace lh

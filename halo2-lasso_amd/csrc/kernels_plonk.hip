@@ -6,17 +6,9 @@
 #include <hip/hip_runtime.h>
 #include <cstring>
 #include "dev.hpp"
+#include "launch.cuh"
 
 namespace lh {
-
-#define GSTRIDE(i, n) \
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (size_t)gridDim.x * blockDim.x)
-static inline dim3 grid_for(size_t n, int block = 256, size_t cap = 4096) {
-  size_t g = (n + block - 1) / block;
-  if (g < 1) g = 1;
-  if (g > cap) g = cap;
-  return dim3((unsigned)g);
-}
 
 // ------------------------------------------------------------------ lookup_m_poly: sort-merge join
 // key = low 64 bits of the (Montgomery) value: equal values have equal keys, a key collision between

@@ -6,20 +6,12 @@
 #include <algorithm>
 #include "dev.hpp"
 #include "ff_host.hpp"
+#include "launch.cuh"
 #include "reduce.cuh"
 #include "resident.cuh"
 #include "wide.cuh"
 
 namespace lh {
-
-static inline dim3 grid_for(size_t n, int block = 256, size_t cap = 4096) {
-  size_t g = (n + block - 1) / block;
-  if (g < 1) g = 1;
-  if (g > cap) g = cap;
-  return dim3((unsigned)g);
-}
-#define GSTRIDE(i, n) \
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (size_t)gridDim.x * blockDim.x)
 
 // ------------------------------------------------------------------ conversions
 __global__ void fr_from_u64_kernel(const uint64_t* __restrict__ in, size_t n, Fr* __restrict__ out) {
@@ -515,21 +507,7 @@ void k_inner_products(Ctx& c, const Fr* const* polys, size_t count, const Fr* we
 }
 
 // ------------------------------------------------------------------ small-valued columns (Lasso's dim / read_ts / E / final_cts)
-// Wide, wide_mac, wide_reduce and wide_redc: wide.cuh
-// host: w (Montgomery form) -> w R (Montgomery form), the weight wide_redc expects
-static Fr prescale_r(const Fr& w) {
-  static const host::Fr scale = [] {
-    uint64_t c[4];
-    for (int k = 0; k < 4; k++) c[k] = (uint64_t)FrParams::r1(2 * k) | ((uint64_t)FrParams::r1(2 * k + 1) << 32);
-    return host::Fr::from_canonical(c);  // the field element R mod r
-  }();
-  host::Fr h;
-  memcpy(&h, &w, sizeof(h));
-  h = h * scale;
-  Fr out;
-  memcpy(&out, &h, sizeof(out));
-  return out;
-}
+// Wide, wide_mac, wide_reduce and wide_redc: wide.cuh; the weights times R that wide_redc expects: prescale_r (launch.cuh)
 
 // out[i] = sum_k w_k fr_k[i] + sum_k w'_k u32_k[i]  (u32 columns of their own lengths, zero beyond)
 struct LcMixed {
@@ -1001,7 +979,7 @@ void k_lincomb_bind2(Ctx& c, const uint32_t* const* cols, const size_t* lens, co
   }
   LcBind2* d_pk = (LcBind2*)c.arena.alloc(sizeof(LcBind2));
   LH_HIP(hipMemcpyAsync(d_pk, h_pk, sizeof(LcBind2), hipMemcpyHostToDevice, c.stream));
-  const size_t g = std::min<size_t>((entries + 255) / 256, (size_t)c.num_cus * 8);
+  const size_t g = cu_grid(c, entries);
   Fr* partials = c.arena.alloc_n<Fr>(g * 2);
   const ScFinishArgs fin = c.finish_for((uint32_t)g, out_host, seq, 32.0 * (double)entries);
   {
@@ -1058,7 +1036,7 @@ void k_sc_round_u32_bind2(Ctx& c, const uint32_t* col, const Fr* eq_level, const
   const uint32_t seq = c.next_seq();
   ArenaScope scope(c.arena);
   const size_t entries = 2 * size;
-  const size_t g = std::min<size_t>((entries + 255) / 256, (size_t)c.num_cus * 8);
+  const size_t g = cu_grid(c, entries);
   Fr* partials = c.arena.alloc_n<Fr>(g);
   const ScFinishArgs fin = c.finish_for((uint32_t)g, out_host, seq, 32.0 * (double)entries);
   host::Fr h0, h1;
@@ -1852,7 +1830,7 @@ void k_lasso_rw_leaves_batch(Ctx& c, const LassoRwBatch& p, size_t num_memories,
   }
   ProfScope ps(c, "lasso_rw_leaves_batch", (12.0 + 64.0 + (up ? 32.0 : 0.0)) * n * num_memories, (up ? 6.0 : 5.0) * n * num_memories,
                (double)n * num_memories);
-  const dim3 grid((unsigned)std::min<size_t>((count + 1023) / 1024, (size_t)c.num_cus * 8), (unsigned)num_memories);
+  const dim3 grid(cu_grid(c, count, 1024), (unsigned)num_memories);
   const Fr g1 = prescale_r(gamma), g2 = prescale_r(gamma2), o1 = prescale_r(Fr::one());
   if (up && vec) hipLaunchKernelGGL((lasso_rw_leaves_batch_kernel<true, true>), grid, dim3(256), 0, c.stream, p, count, g1, g2, o1, tau);
   else if (up) hipLaunchKernelGGL((lasso_rw_leaves_batch_kernel<true, false>), grid, dim3(256), 0, c.stream, p, count, g1, g2, o1, tau);

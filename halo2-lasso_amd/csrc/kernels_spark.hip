@@ -8,25 +8,11 @@
 #include <cstring>
 #include "dev.hpp"
 #include "ff_host.hpp"
+#include "launch.cuh"
 #include "reduce.cuh"
 #include "wide.cuh"
 
 namespace lh {
-
-static unsigned spark_grid(const Ctx& c, size_t work, size_t per_block = 256) {
-  return (unsigned)std::max<size_t>(1, std::min<size_t>((work + per_block - 1) / per_block, (size_t)c.num_cus * 8));
-}
-// host: w (Montgomery form) -> w R (Montgomery form), the weight wide_redc expects (as kernels_memcheck.hip's)
-static Fr spark_prescale_r(const Fr& w) {
-  uint64_t c[4];
-  for (int k = 0; k < 4; k++) c[k] = (uint64_t)FrParams::r1(2 * k) | ((uint64_t)FrParams::r1(2 * k + 1) << 32);
-  host::Fr h;
-  memcpy(&h, &w, sizeof(h));
-  h = h * host::Fr::from_canonical(c);  // the field element R mod r
-  Fr out;
-  memcpy(&out, &h, sizeof(out));
-  return out;
-}
 
 // ------------------------------------------------------------------ 1. E_j = T_j[dim_j] and v = sum val prod_j E_j
 // A lane takes entry k of ALL dimensions: C index loads (4 B, coalesced), C gathers of 32 B (two dwordx4 of one aligned
@@ -66,7 +52,7 @@ void k_spark_e(Ctx& c, const SparkE& p, size_t num_dims, size_t n, size_t dim_va
   // per entry: val (32 B), per dimension an index (4 B), a gathered element (32 B) and a stored one (32 B)
   ProfScope ps(c, "spark_e", (32.0 + 68.0 * num_dims) * n, (double)(num_dims * n), (double)n);
   ArenaScope scope(c.arena);
-  const unsigned grid = spark_grid(c, n);
+  const unsigned grid = cu_grid(c, n);
   Fr* partial = c.arena.alloc_n<Fr>(grid + 1);
   const uint32_t mask = (uint32_t)(((uint64_t)1 << dim_vars) - 1);
   if (num_dims == 1) hipLaunchKernelGGL(spark_e_kernel<1>, dim3(grid), dim3(256), 0, c.stream, p, n, mask, partial);
@@ -149,9 +135,9 @@ void k_spark_leaves(Ctx& c, const SparkLeaves& p, size_t num_dims, size_t n, siz
   const double muls = (1.0 + (up_n ? 1.0 : 0.0)) * num_dims * n + (1.0 + (up_l ? 1.0 : 0.0)) * num_dims * cells;
   ProfScope ps(c, "spark_leaves", bytes, muls, (double)(num_dims * (n + cells)));
   const size_t most = std::max(up_n ? n / 2 : n, up_l ? cells / 2 : cells);
-  const dim3 grid(spark_grid(c, most), (unsigned)(2 * num_dims));
+  const dim3 grid(cu_grid(c, most), (unsigned)(2 * num_dims));
   hipLaunchKernelGGL(spark_leaves_kernel, grid, dim3(256), 0, c.stream, p, (unsigned)num_dims, n, cells, up_n, up_l, gamma,
-                     spark_prescale_r(gamma2), spark_prescale_r(Fr::one()), tau);
+                     prescale_r(gamma2), prescale_r(Fr::one()), tau);
 }
 
 }  // namespace lh

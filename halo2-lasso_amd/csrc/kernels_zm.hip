@@ -8,17 +8,9 @@
 //                  second pass seeded with the chunk's carry.
 #include <hip/hip_runtime.h>
 #include "dev.hpp"
+#include "launch.cuh"
 
 namespace lh {
-
-#define GSTRIDE(i, n) \
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (size_t)gridDim.x * blockDim.x)
-static inline dim3 grid_for(size_t n, int block = 256, size_t cap = 4096) {
-  size_t g = (n + block - 1) / block;
-  if (g < 1) g = 1;
-  if (g > cap) g = cap;
-  return dim3((unsigned)g);
-}
 
 // out[i] = s^i : thread i starts from s^(64 * (i / 64)) by square-and-multiply and walks its 64-chunk
 __global__ void powers_kernel(Fr s, size_t n, Fr* __restrict__ out) {

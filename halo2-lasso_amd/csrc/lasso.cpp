@@ -285,22 +285,14 @@ LassoColumns lasso_witness_columns(Ctx& c, const lh_lasso_table& tb, size_t n, c
 }
 
 // ------------------------------------------------------------------ steps shared by lasso_argue, lasso_prove and lasso_prove_batch
-// u32 columns of `len` = 2^vars entries evaluated at `point`, against its full eq table (scratch of this call): final_cts at
-// r_M, and any column of fewer than two variables
-static void lasso_evaluate_u32_full(Ctx& c, const uint32_t* const* cols, size_t count, const HFr* point, size_t vars, HFr* out) {
-  ArenaScope scope(c.arena);
-  const size_t len = (size_t)1 << vars;
-  Fr* eq = c.arena.alloc_n<Fr>(len);
-  k_eq_xy(c, (const Fr*)point, vars, eq);
-  k_inner_products_small(c, cols, count, eq, len, (Fr*)out);
-}
+// (final_cts at r_M, and any column of fewer than two variables: evaluate_u32_columns, against the point's full eq table)
 // u32 columns of n variables (this rank's shards inside a sharded proof: partial sums added over the ranks) evaluated at
 // `point`: against the eq table of point[1..] (half the entries), which the sum-checks and the batch opening at that point
 // use as well.  The eq table that stays cached for the opening is obtained OUTSIDE any inner ArenaScope.
 // share_sums: from the columns' quad sums, which stay in the proof's table for the opening (quad_sums_evaluate).
 static void lasso_evaluate_u32(Ctx& c, const uint32_t* const* cols, size_t count, const HFr* point, size_t n, bool shn, HFr* out,
                                bool share_sums = false) {
-  if (n < 2) return lasso_evaluate_u32_full(c, cols, count, point, n, out);
+  if (n < 2) return evaluate_u32_columns(c, cols, count, point, n, out);
   const Fr* eq_half = eq_half_get(c, point, n, shn);
   const size_t N = (size_t)1 << (n - Shard(c).rho);
   if (share_sums) quad_sums_evaluate(c, cols, count, point, n, eq_half, out);
@@ -326,39 +318,6 @@ static void lasso_append_g(lh_sop& e, const lh_lasso_table& tb, size_t mem_base 
     for (int k = 0; k < tb.g_num_factors[m]; k++) e.factor[t][k] = (uint8_t)(mem_base + tb.g_factor[m][k]);
   }
 }
-// The four product trees per memory of ONE grand-product GKR over A memories: RS, WS of memory b (n variables) at 2 b and
-// 2 b + 1, behind them Init, Final (l variables) at 2 A + 2 b and 2 A + 2 b + 1.  write leaf = read leaf + 1: where the
-// n-variable trees are alone at their leaf layer that layer runs over the read-set tables only (prove_grand_product:
-// plus_one) and the write-set leaves are never stored (ws_implicit).  The caller fills the leaves.
-struct LassoTrees {
-  size_t A;
-  std::vector<const Fr*> leaves, level_up;
-  std::vector<size_t> depths;
-  std::vector<uint8_t> plus_one;
-  LassoTrees(size_t A_, size_t n) : A(A_), leaves(4 * A_), level_up(4 * A_, nullptr), depths(4 * A_, n), plus_one(4 * A_, 0) {}
-  struct Memory {
-    Fr *rs, *ws, *rs_up, *ws_up, *init, *fin;
-  };
-  // memory b's leaf tables (N and M = 2^l entries; fused_up: the level above the n-variable leaves comes with them)
-  Memory add(Ctx& c, size_t b, size_t N, size_t l, bool fused_up, bool ws_implicit) {
-    Memory m{};
-    m.rs = c.arena.alloc_n<Fr>(N);
-    m.ws = ws_implicit ? nullptr : c.arena.alloc_n<Fr>(N);
-    if (fused_up) {
-      m.rs_up = c.arena.alloc_n<Fr>(N / 2), m.ws_up = c.arena.alloc_n<Fr>(N / 2);
-      level_up[2 * b] = m.rs_up, level_up[2 * b + 1] = m.ws_up;
-    }
-    m.init = c.arena.alloc_n<Fr>((size_t)1 << l), m.fin = c.arena.alloc_n<Fr>((size_t)1 << l);
-    leaves[2 * b] = m.rs, leaves[2 * b + 1] = m.ws;
-    plus_one[2 * b + 1] = 1;
-    leaves[2 * A + 2 * b] = m.init, leaves[2 * A + 2 * b + 1] = m.fin;
-    depths[2 * A + 2 * b] = depths[2 * A + 2 * b + 1] = l;
-    return m;
-  }
-  GrandProductResult prove(Ctx& c, Transcript& tr, const std::function<void()>& trees_built = nullptr) {
-    return prove_grand_product(c, 4 * A, leaves.data(), depths.data(), tr, level_up.data(), plus_one.data(), trees_built);
-  }
-};
 
 // Steps 2-7 of the argument (oracle/pyref/lasso.py argue): Surge sum-check, memory-checking grand products,
 // evaluations.  The Fr tables hold at least 2^n (fcs_fr: 2^l) entries; `lap` (optional) receives phase boundaries,
@@ -452,12 +411,12 @@ LassoClaims lasso_argue(Ctx& c, const lh_lasso_table& tb, size_t n, const LassoC
   HFr gamma2 = gamma * gamma;
   {
     ArenaScope scope(c.arena);
-    LassoTrees trees(alpha, n);
+    MemoryTrees trees(alpha, n);
     // (sharded: the level above the leaves must itself be held in shards, else it is exchanged by the tree builder)
-    const bool fused_up = n >= 12 && (!shn || sh.sharded(n - 1)), ws_implicit = fused_up && n > l;
+    const bool fused_up = n >= GP_LEVEL_UP_MIN_VARS && (!shn || sh.sharded(n - 1)), ws_implicit = fused_up && n > l;
     for (size_t i = 0; i < alpha; i++) {
       const size_t j = tb.memory_chunk[i];
-      const LassoTrees::Memory m = trees.add(c, i, N, l, fused_up, ws_implicit);
+      const MemoryTrees::Memory m = trees.add(c, i, N, l, fused_up, ws_implicit);
       if (fused_up)  // the level above the leaves comes with them (no tree_up pass over the largest level)
         k_lasso_rw_leaves_up(c, d_dims[j], w.E[i], w.rts[j], N, dev(gamma), dev(gamma2), dev(tau), m.rs, m.ws, m.rs_up, m.ws_up);
       else
@@ -481,7 +440,7 @@ LassoClaims lasso_argue(Ctx& c, const lh_lasso_table& tb, size_t n, const LassoC
   lasso_evaluate_u32(c, at_n.data(), at_n.size(), cl.r_N.data(), n, shn, cl.ev_n.data(), share_sums);
   std::vector<const uint32_t*> at_l(w.fcs.begin(), w.fcs.end());
   cl.ev_l.resize(cc);
-  lasso_evaluate_u32_full(c, at_l.data(), cc, cl.r_M.data(), l, cl.ev_l.data());
+  evaluate_u32_columns(c, at_l.data(), cc, cl.r_M.data(), l, cl.ev_l.data());
   tr.write_field_elements(cl.ev_n);
   tr.write_field_elements(cl.ev_l);
   if (lap) lap(5);
@@ -1124,17 +1083,17 @@ void lasso_prove_batch(Ctx& c, const Pcs& pcs, const lh_lasso_table* const* tabl
   std::vector<std::vector<HFr>> r_M(ls.size());
   {
     ArenaScope inner(c.arena);
-    LassoTrees trees(A, n);
+    MemoryTrees trees(A, n);
     // (lasso_argue: the level above the leaves comes with them from 2^12 lookups on, and the write leaves are not stored
     // where n is above every chunk size)
     const size_t max_l = *std::max_element(ls.begin(), ls.end());
-    const bool fused_up = n >= 12, ws_implicit = fused_up && n > max_l;
+    const bool fused_up = n >= GP_LEVEL_UP_MIN_VARS, ws_implicit = fused_up && n > max_l;
     LassoRwBatch rw;
     memset(&rw, 0, sizeof(rw));
     for (const Table& x : T)
       for (size_t i = 0; i < x.lay.alpha; i++) {
         const size_t b = x.mem_base + i, j = x.tb->memory_chunk[i];
-        const LassoTrees::Memory m = trees.add(c, b, N, x.lay.l, fused_up, ws_implicit);
+        const MemoryTrees::Memory m = trees.add(c, b, N, x.lay.l, fused_up, ws_implicit);
         rw.dim[b] = x.dims[j], rw.e[b] = x.w.E[i], rw.ts[b] = x.w.rts[j];
         rw.rs[b] = m.rs, rw.ws[b] = m.ws, rw.rs_up[b] = m.rs_up, rw.ws_up[b] = m.ws_up;
         k_lasso_if_leaves(c, (int)x.tb->memory_subtable[i], (uint32_t)x.lay.l, x.w.fcs[j], (size_t)1 << x.lay.l, dev(gamma),
@@ -1168,7 +1127,7 @@ void lasso_prove_batch(Ctx& c, const Pcs& pcs, const lh_lasso_table* const* tabl
       for (const Table& x : T)
         if (x.lay.l == ls[q]) at_l.insert(at_l.end(), x.w.fcs.begin(), x.w.fcs.end());
       std::vector<HFr> ev_l(at_l.size());
-      lasso_evaluate_u32_full(c, at_l.data(), at_l.size(), r_M[q].data(), ls[q], ev_l.data());
+      evaluate_u32_columns(c, at_l.data(), at_l.size(), r_M[q].data(), ls[q], ev_l.data());
       size_t k = 0;
       for (Table& x : T)
         if (x.lay.l == ls[q]) x.cl.ev_l.assign(ev_l.begin() + k, ev_l.begin() + k + x.lay.cc), k += x.lay.cc;

@@ -1,0 +1,43 @@
+// What the kernel files share around a launch: the grid-stride loop, the two grid rules and the host-side weight scaling
+// of the wide accumulator (wide.cuh).  Included by the kernels_*.hip files only; none of it is device code of its own.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <string.h>
+#include <algorithm>
+#include "dev.hpp"
+#include "ff.cuh"
+#include "ff_host.hpp"
+
+namespace lh {
+
+#define GSTRIDE(i, n) \
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (size_t)gridDim.x * blockDim.x)
+
+// ceil(n / block) workgroups, at least one and at most `cap`
+static inline dim3 grid_for(size_t n, int block = 256, size_t cap = 4096) {
+  size_t g = (n + block - 1) / block;
+  if (g < 1) g = 1;
+  if (g > cap) g = cap;
+  return dim3((unsigned)g);
+}
+// the CU-bounded grid of the streaming kernels: ceil(work / per_block) workgroups, at least one and at most 8 per CU
+static inline unsigned cu_grid(const Ctx& c, size_t work, size_t per_block = 256) {
+  return (unsigned)std::max<size_t>(1, std::min<size_t>((work + per_block - 1) / per_block, (size_t)c.num_cus * 8));
+}
+
+// host: w (Montgomery form) -> w R (Montgomery form), the weight wide_redc expects
+static inline Fr prescale_r(const Fr& w) {
+  static const host::Fr scale = [] {
+    uint64_t c[4];
+    for (int k = 0; k < 4; k++) c[k] = (uint64_t)FrParams::r1(2 * k) | ((uint64_t)FrParams::r1(2 * k + 1) << 32);
+    return host::Fr::from_canonical(c);  // the field element R mod r
+  }();
+  host::Fr h;
+  memcpy(&h, &w, sizeof(h));
+  h = h * scale;
+  Fr out;
+  memcpy(&out, &h, sizeof(out));
+  return out;
+}
+
+}  // namespace lh

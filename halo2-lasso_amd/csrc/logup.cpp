@@ -47,12 +47,9 @@ static std::vector<HFr> logup_powers(const HFr& beta) {
 }
 // the opening list shared by prover and verifier: input column i at point 0 (x_n), m_k (poly W + k) at point 1 (x_l)
 static std::vector<lh_evaluation> logup_evaluations(const std::vector<HFr>& f_e, const std::vector<HFr>& m_e) {
-  std::vector<lh_evaluation> evs(f_e.size() + m_e.size());
-  for (size_t i = 0; i < evs.size(); i++) {
-    memset(&evs[i], 0, sizeof(lh_evaluation));
-    evs[i].poly = (uint32_t)i, evs[i].point = i < f_e.size() ? 0u : 1u;
-    memcpy(&evs[i].value, i < f_e.size() ? &f_e[i] : &m_e[i - f_e.size()], 32);
-  }
+  std::vector<lh_evaluation> evs;
+  for (const HFr& v : f_e) evs.push_back(make_evaluation(evs.size(), 0, &v));
+  for (const HFr& v : m_e) evs.push_back(make_evaluation(evs.size(), 1, &v));
   return evs;
 }
 
@@ -84,11 +81,8 @@ void logup_gkr_prove(Ctx& c, const Pcs& pcs, const lh_logup_lookup* lookups, siz
 void logup_gkr_prove_columns(Ctx& c, const Pcs& pcs, const lh_logup_columns* lookups, size_t L, size_t n, size_t l,
                              Transcript& tr) {
   const size_t nv = logup_columns_check(lookups, L, n, l);
-  LH_REQUIRE(!Shard(c).on && !(c.has_comm && c.comm.size > 1), LH_ERR_ARG,
-             "logup: sharded proofs are not supported (the ctx is inside a sharded prove or has a communicator of several ranks)");
-  LH_REQUIRE(pcs.chunks == 1 && pcs.batch_commit && pcs.commit_bases && !pcs.commit_and_write && !pcs.commit_columns_and_write,
-             LH_ERR_ARG, "logup: implemented for schemes whose commitment is one point over bases");
-  if (nv > pcs.max_vars) throw Error(LH_ERR_INVALID_PCS_PARAM, "Too many variates of poly to commit");
+  argument_not_sharded(c, "logup");
+  argument_pcs_check(pcs, nv, "logup", true);
   const size_t N = (size_t)1 << n, M = (size_t)1 << l, NV = (size_t)1 << nv;
   open_precommit_cancel(c);
   ArenaScope scope(c.arena);
@@ -131,19 +125,11 @@ void logup_gkr_prove_columns(Ctx& c, const Pcs& pcs, const lh_logup_columns* loo
       for (size_t t = 0; t < fr_at.size(); t++) comms[fr_at[t]] = out[t];
     }
     if (!sm_at.empty()) {
-      std::vector<const uint32_t*> cols;
-      for (size_t i : sm_at) cols.push_back((const uint32_t*)f[i]);
-      std::vector<uint32_t> ors(cols.size(), 0);
-      k_or_u32(c, cols.data(), cols.size(), N, ors.data());
-      std::vector<MsmJob> jobs;
-      for (size_t t = 0; t < sm_at.size(); t++) {
-        f_bits[sm_at[t]] = std::max(bit_length(ors[t]), 1u);
-        jobs.push_back(MsmJob{cols[t], true, pcs.commit_bases(nv), N});
-        jobs.back().known_bits = f_bits[sm_at[t]];
-      }
-      std::vector<HG1> out(jobs.size());
-      msm_batch(c, jobs.data(), jobs.size(), (G1Affine*)out.data());
-      for (size_t t = 0; t < sm_at.size(); t++) comms[sm_at[t]] = out[t];
+      std::vector<U32Column> cols;
+      for (size_t i : sm_at) cols.push_back(U32Column{(const uint32_t*)f[i], N});
+      std::vector<uint32_t> bits(cols.size());
+      const std::vector<HG1> out = commit_u32_columns(c, pcs, nv, cols, bits.data());
+      for (size_t t = 0; t < sm_at.size(); t++) comms[sm_at[t]] = out[t], f_bits[sm_at[t]] = bits[t];
     }
     lasso_write_commitments(tr, comms);
   }
@@ -178,24 +164,17 @@ void logup_gkr_prove_columns(Ctx& c, const Pcs& pcs, const lh_logup_columns* loo
   }
 
   // ---- 3: multiplicities (prover.rs:145-192 lookup_m_poly: the LAST of equal rows takes every count) as u32 columns, committed
-  // like Lasso's counters: against the bases of level nv, widths promised from the OR of the counts
+  // like the u32 inputs (commit_u32_columns)
   std::vector<uint32_t*> m(L);
-  for (size_t k = 0; k < L; k++) {
-    m[k] = c.arena.alloc_n<uint32_t>(M + 1);
-    if (!k_logup_multiplicities(c, cf[k], N, ct[k], M, m[k])) throw Error(LH_ERR_INVALID_SNARK, "Invalid lookup input");
-  }
-  std::vector<uint32_t> ors(L, 0);
+  std::vector<uint32_t> m_bits(L);
   {
-    std::vector<const uint32_t*> cols(m.begin(), m.end());
-    k_or_u32(c, cols.data(), L, M, ors.data());
-    std::vector<MsmJob> jobs;
+    std::vector<U32Column> cols;
     for (size_t k = 0; k < L; k++) {
-      jobs.push_back(MsmJob{m[k], true, pcs.commit_bases(nv), M});
-      jobs.back().known_bits = std::max(bit_length(ors[k]), 1u);
+      m[k] = c.arena.alloc_n<uint32_t>(M + 1);
+      if (!k_logup_multiplicities(c, cf[k], N, ct[k], M, m[k])) throw Error(LH_ERR_INVALID_SNARK, "Invalid lookup input");
+      cols.push_back(U32Column{m[k], M});
     }
-    std::vector<HG1> comms(L);
-    msm_batch(c, jobs.data(), jobs.size(), (G1Affine*)comms.data());
-    lasso_write_commitments(tr, comms);
+    lasso_write_commitments(tr, commit_u32_columns(c, pcs, nv, cols, m_bits.data()));
   }
 
   // ---- 4-6: gamma, the leaves of both sides (and, fused, the level above them), the two fractional sum-checks
@@ -231,23 +210,14 @@ void logup_gkr_prove_columns(Ctx& c, const Pcs& pcs, const lh_logup_columns* loo
     for (size_t t = 0; t < fr_at.size(); t++) f_e[fr_at[t]] = out[t];
   }
   if (!sm_at.empty()) {  // the u32 columns against eq(x_n), as the multiplicities against eq(x_l) below
-    ArenaScope inner(c.arena);
-    Fr* eq = c.arena.alloc_n<Fr>(N);
-    k_eq_xy(c, (const Fr*)x_n.data(), n, eq);
     std::vector<const uint32_t*> cols;
     for (size_t i : sm_at) cols.push_back((const uint32_t*)f[i]);
     std::vector<HFr> out(cols.size());
-    k_inner_products_small(c, cols.data(), cols.size(), eq, N, (Fr*)out.data());
+    evaluate_u32_columns(c, cols.data(), cols.size(), x_n.data(), n, out.data());
     for (size_t t = 0; t < sm_at.size(); t++) f_e[sm_at[t]] = out[t];
   }
   std::vector<HFr> m_e(L);
-  {
-    ArenaScope inner(c.arena);
-    Fr* eq = c.arena.alloc_n<Fr>(M);
-    k_eq_xy(c, (const Fr*)x_l.data(), l, eq);
-    std::vector<const uint32_t*> cols(m.begin(), m.end());
-    k_inner_products_small(c, cols.data(), L, eq, M, (Fr*)m_e.data());
-  }
+  evaluate_u32_columns(c, m.data(), L, x_l.data(), l, m_e.data());
   tr.write_field_elements(f_e);
   tr.write_field_elements(m_e);
 
@@ -257,36 +227,21 @@ void logup_gkr_prove_columns(Ctx& c, const Pcs& pcs, const lh_logup_columns* loo
   // Pcs::precommit call, the opening builds its column plan itself; the bytes do not depend on the route
   std::vector<SmallPoly> small(W + L);
   for (size_t i : sm_at) small[i] = SmallPoly{(const uint32_t*)f[i], N, f_bits[i]};
-  for (size_t k = 0; k < L; k++) small[W + k] = SmallPoly{m[k], M, std::max(bit_length(ors[k]), 1u)};
+  for (size_t k = 0; k < L; k++) small[W + k] = SmallPoly{m[k], M, m_bits[k]};
   std::vector<HFr> points;
   lasso_append_points(points, {&x_n, &x_l}, nv);
   const std::vector<lh_evaluation> evs = logup_evaluations(f_e, m_e);
   pcs.batch_open(nv, polys.data(), polys.size(), points.data(), 2, evs.data(), evs.size(), tr, small.data());
 }
 
-// sum_j beta^j t~_j(x): the multilinear extension of the compressed table column, one fold over its 2^l rows (variable i =
-// index bit i); the first fold reads the w columns
+// sum_j beta^j t~_j(x): the multilinear extension of the compressed table column, one fold over its 2^l rows; a row reads
+// the w columns
 static HFr logup_table_eval(const lh_logup_lookup& lk, size_t l, const std::vector<HFr>& pw, const std::vector<HFr>& x) {
-  const size_t M = (size_t)1 << l;
-  auto row = [&](size_t r) {
+  return host_table_eval(l, x, [&](size_t r) {
     HFr acc = ((const HFr*)lk.table[0])[r];
     for (uint32_t j = 1; j < lk.width; j++) acc += pw[j] * ((const HFr*)lk.table[j])[r];
     return acc;
-  };
-  std::vector<HFr> cur(M / 2);
-  const size_t chunks = std::min<size_t>(cur.size(), 64);  // (the pool hands out items one by one)
-  host_parallel_for(chunks, [&](size_t ch) {
-    for (size_t k = ch * cur.size() / chunks; k < (ch + 1) * cur.size() / chunks; k++) {
-      const HFr lo = row(2 * k), hi = row(2 * k + 1);
-      cur[k] = lo + x[0] * (hi - lo);
-    }
   });
-  for (size_t i = 1; i < l; i++) {
-    const size_t half = cur.size() / 2;
-    for (size_t k = 0; k < half; k++) cur[k] = cur[2 * k] + x[i] * (cur[2 * k + 1] - cur[2 * k]);
-    cur.resize(half);
-  }
-  return cur[0];
 }
 
 static void logup_gkr_verify_checked(const PcsVerifier& pcs, const lh_logup_lookup* lookups, size_t L, size_t n, size_t l, size_t nv,
@@ -303,9 +258,8 @@ static void logup_gkr_verify_checked(const PcsVerifier& pcs, const lh_logup_look
   const HFr gamma = tr.squeeze_challenge();
   const FracVerifyResult in = verify_fractional_sum_check(L, n, nullptr, nullptr, tr);
   const FracVerifyResult tb = verify_fractional_sum_check(L, l, nullptr, nullptr, tr);
-  // the LogUp identity on the roots: P_f / Q_f + P_t / Q_t = 0 with both denominators non-zero
-  for (size_t k = 0; k < L; k++)
-    if (in.q_0s[k].is_zero() || tb.q_0s[k].is_zero() || !(in.p_0s[k] * tb.q_0s[k] + tb.p_0s[k] * in.q_0s[k]).is_zero())
+  for (size_t k = 0; k < L; k++)  // the LogUp identity on the roots: P_f / Q_f + P_t / Q_t = 0
+    if (!logup_roots_cancel(in.p_0s[k], in.q_0s[k], tb.p_0s[k], tb.q_0s[k]))
       throw Error(LH_ERR_INVALID_SNARK, "lookup " + std::to_string(k) + ": the fractions do not sum to zero");
   const std::vector<HFr> f_e = tr.read_field_elements(W), m_e = tr.read_field_elements(L);
   size_t at = 0;
@@ -322,18 +276,10 @@ static void logup_gkr_verify_checked(const PcsVerifier& pcs, const lh_logup_look
   const std::vector<lh_evaluation> evs = logup_evaluations(f_e, m_e);
   pcs.batch_verify(nv, comms.data(), comms.size(), points.data(), 2, evs.data(), evs.size(), tr);
 }
-// A proof that does not verify is LH_ERR_INVALID_SNARK whichever piece found it out; what is wrong with the call keeps its code
 void logup_gkr_verify(const PcsVerifier& pcs, const lh_logup_lookup* lookups, size_t L, size_t n, size_t l, Transcript& tr) {
   const size_t nv = logup_check(lookups, L, n, l, false);
-  LH_REQUIRE(pcs.chunks == 1 && !pcs.read_commitments, LH_ERR_ARG, "logup: implemented for commitments of one point");
-  try {
-    logup_gkr_verify_checked(pcs, lookups, L, n, l, nv, tr);
-  } catch (const Error& e) {
-    if (e.code == LH_ERR_INVALID_SUMCHECK || e.code == LH_ERR_INVALID_PCS_OPEN || e.code == LH_ERR_TRANSCRIPT ||
-        e.code == LH_ERR_SERIALIZATION)
-      throw Error(LH_ERR_INVALID_SNARK, "logup: " + e.msg);
-    throw;
-  }
+  argument_pcs_check(pcs, "logup");
+  argument_verdict("logup", [&] { logup_gkr_verify_checked(pcs, lookups, L, n, l, nv, tr); });
 }
 
 }  // namespace lh

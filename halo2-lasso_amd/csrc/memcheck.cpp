@@ -21,12 +21,8 @@ void memcheck_header(Transcript& tr, size_t n, size_t l, bool has_init) {
   for (size_t v : {n, l, (size_t)has_init}) tr.common_field_element(HFr::from_u64(v));
 }
 std::vector<lh_evaluation> memcheck_evaluations(const std::vector<HFr>& vals) {
-  std::vector<lh_evaluation> evs(vals.size());
-  for (size_t i = 0; i < evs.size(); i++) {
-    memset(&evs[i], 0, sizeof(lh_evaluation));
-    evs[i].poly = OPENINGS[i][0], evs[i].point = OPENINGS[i][1];
-    memcpy(&evs[i].value, &vals[i], 32);
-  }
+  std::vector<lh_evaluation> evs;
+  for (size_t i = 0; i < vals.size(); i++) evs.push_back(make_evaluation(OPENINGS[i][0], OPENINGS[i][1], &vals[i]));
   return evs;
 }
 }  // namespace
@@ -69,18 +65,15 @@ void memcheck_prove(Ctx& c, const Pcs& pcs, const lh_memcheck_trace& trace, size
                     Transcript& tr) {
   const size_t nv = memcheck_check(n, l, init != nullptr);
   memcheck_trace_check(trace);
-  LH_REQUIRE(!Shard(c).on && !(c.has_comm && c.comm.size > 1), LH_ERR_ARG,
-             "memcheck: sharded proofs are not supported (the ctx is inside a sharded prove or has a communicator of several ranks)");
-  LH_REQUIRE(pcs.chunks == 1 && pcs.commit_bases && !pcs.commit_and_write && !pcs.commit_columns_and_write, LH_ERR_ARG,
-             "memcheck: implemented for schemes whose commitment is one point over bases");
-  if (nv > pcs.max_vars) throw Error(LH_ERR_INVALID_PCS_PARAM, "Too many variates of poly to commit");
+  argument_not_sharded(c, "memcheck");
+  argument_pcs_check(pcs, nv, "memcheck", false);  // (every poly is a u32 column: nothing goes through batch_commit)
   const size_t N = (size_t)1 << n, M = (size_t)1 << l;
   open_precommit_cancel(c);
   ArenaScope scope(c.arena);
   EqHalfScope eq_scope(c);  // (the opening shares eq tables of its points: arena memory of this scope)
 
   // ---- 0/1: header; the witness (one flag readback); ONE block of seven commitments, every column a 32-bit MSM over its own
-  // length against the bases of level nv, its width promised from the OR of its entries - the way LogUp-GKR commits m_k
+  // length (commit_u32_columns)
   memcheck_header(tr, n, l, init != nullptr);
   const uint32_t* d_init = memcheck_upload(c, init, M);
   uint32_t* rt = c.arena.alloc_n<uint32_t>(N);
@@ -94,21 +87,9 @@ void memcheck_prove(Ctx& c, const Pcs& pcs, const lh_memcheck_trace& trace, size
   const size_t len[NUM_POLYS] = {N, N, N, N, M, M, N};
   uint32_t bits[NUM_POLYS];
   {
-    const uint32_t* over_n[5] = {col[ADDR], col[RV], col[WV], col[RT], col[MULT]};
-    const uint32_t* over_m[2] = {col[FV], col[FT]};
-    uint32_t or_n[5], or_m[2];
-    k_or_u32(c, over_n, 5, N, or_n);
-    k_or_u32(c, over_m, 2, M, or_m);
-    const uint32_t ors[NUM_POLYS] = {or_n[0], or_n[1], or_n[2], or_n[3], or_m[0], or_m[1], or_n[4]};
-    std::vector<MsmJob> jobs;
-    for (size_t i = 0; i < NUM_POLYS; i++) {
-      bits[i] = std::max(bit_length(ors[i]), 1u);
-      jobs.push_back(MsmJob{col[i], true, pcs.commit_bases(nv), len[i]});
-      jobs.back().known_bits = bits[i];
-    }
-    std::vector<HG1> comms(NUM_POLYS);
-    msm_batch(c, jobs.data(), jobs.size(), (G1Affine*)comms.data());
-    lasso_write_commitments(tr, comms);
+    std::vector<U32Column> cols;
+    for (size_t i = 0; i < NUM_POLYS; i++) cols.push_back(U32Column{col[i], len[i]});
+    lasso_write_commitments(tr, commit_u32_columns(c, pcs, nv, cols, bits));
   }
 
   // ---- 2: gamma, tau; the four trees' leaves in one launch (and, fused, the level above the large ones); the grand product
@@ -116,25 +97,14 @@ void memcheck_prove(Ctx& c, const Pcs& pcs, const lh_memcheck_trace& trace, size
   const bool fused = c.opt.logup_fused_leaves != 0;
   std::vector<HFr> r_N, r_M;
   {
-    MemcheckLeaves a;
-    memset(&a, 0, sizeof(a));
-    const uint32_t* cols[2][4] = {{col[ADDR], col[RV], col[RT], col[WV]}, {d_init, col[FV], col[FT], nullptr}};
-    const size_t vars[2] = {n, l};
-    const Fr* leaves[4];
-    const Fr* level_up[4];
-    for (int side = 0; side < 2; side++) {
-      const size_t count = (size_t)1 << vars[side];
-      const bool up = fused && vars[side] >= 12;  // (the tree builder takes the level from 11 variables on; as lasso.cpp)
-      for (int k = 0; k < 4; k++) a.col[side][k] = cols[side][k];
-      for (int t = 0; t < 2; t++) {
-        a.leaf[side][t] = c.arena.alloc_n<Fr>(count);
-        a.up[side][t] = up ? c.arena.alloc_n<Fr>(count / 2) : nullptr;
-        leaves[2 * side + t] = a.leaf[side][t], level_up[2 * side + t] = a.up[side][t];
-      }
-    }
+    MemoryTrees trees(1, n, false);  // (one memory; its write leaves are no read leaves + 1)
+    const MemoryTrees::Memory t = trees.add(c, 0, N, l, fused && n >= GP_LEVEL_UP_MIN_VARS, false, fused && l >= GP_LEVEL_UP_MIN_VARS);
+    const MemcheckLeaves a = {{{col[ADDR], col[RV], col[RT], col[WV]}, {d_init, col[FV], col[FT], nullptr}},
+                              {{t.rs, t.ws}, {t.init, t.fin}},
+                              {{t.rs_up, t.ws_up}, {t.init_up, t.fin_up}},
+                              {0, 0}};
     k_memcheck_leaves(c, a, n, l, dev(gamma), dev(gamma * gamma), dev(tau));
-    const size_t depths[4] = {n, n, l, l};
-    const GrandProductResult gp = prove_grand_product(c, 4, leaves, depths, tr, level_up);
+    const GrandProductResult gp = trees.prove(c, tr);
     r_N = gp.points[0], r_M = gp.points[2];
   }
 
@@ -162,13 +132,9 @@ void memcheck_prove(Ctx& c, const Pcs& pcs, const lh_memcheck_trace& trace, size
   // ---- 4: the eight evaluations, every column against the eq table of its point
   std::vector<HFr> vals(8);
   auto evaluate = [&](const std::vector<HFr>& point, std::initializer_list<size_t> polys, size_t first) {
-    ArenaScope inner(c.arena);
-    const size_t count = (size_t)1 << point.size();
-    Fr* eq = c.arena.alloc_n<Fr>(count);
-    k_eq_xy(c, (const Fr*)point.data(), point.size(), eq);
     std::vector<const uint32_t*> cols;
     for (size_t i : polys) cols.push_back(col[i]);
-    k_inner_products_small(c, cols.data(), cols.size(), eq, count, (Fr*)(vals.data() + first));
+    evaluate_u32_columns(c, cols.data(), cols.size(), point.data(), point.size(), vals.data() + first);
   };
   evaluate(r_N, {ADDR, RV, WV, RT}, 0);
   evaluate(r_M, {FV, FT}, 4);
@@ -186,25 +152,6 @@ void memcheck_prove(Ctx& c, const Pcs& pcs, const lh_memcheck_trace& trace, size
   pcs.batch_open(nv, polys.data(), polys.size(), points.data(), 3, evs.data(), evs.size(), tr, small.data());
 }
 
-// the multilinear extension of the image at x (variable i = index bit i): one fold over its 2^l words
-static HFr memcheck_init_eval(const uint32_t* init, size_t l, const std::vector<HFr>& x) {
-  const size_t M = (size_t)1 << l;
-  std::vector<HFr> cur(M / 2);
-  const size_t chunks = std::min<size_t>(cur.size(), 64);  // (the pool hands out items one by one)
-  host_parallel_for(chunks, [&](size_t ch) {
-    for (size_t k = ch * cur.size() / chunks; k < (ch + 1) * cur.size() / chunks; k++) {
-      const HFr lo = HFr::from_u64(init[2 * k]), hi = HFr::from_u64(init[2 * k + 1]);
-      cur[k] = lo + x[0] * (hi - lo);
-    }
-  });
-  for (size_t i = 1; i < l; i++) {
-    const size_t half = cur.size() / 2;
-    for (size_t k = 0; k < half; k++) cur[k] = cur[2 * k] + x[i] * (cur[2 * k + 1] - cur[2 * k]);
-    cur.resize(half);
-  }
-  return cur[0];
-}
-
 static void memcheck_verify_checked(const PcsVerifier& pcs, size_t n, size_t l, size_t nv, const uint32_t* init, Transcript& tr) {
   memcheck_header(tr, n, l, init != nullptr);
   const std::vector<HG1> comms = lasso_read_commitments(tr, NUM_POLYS);
@@ -215,13 +162,13 @@ static void memcheck_verify_checked(const PcsVerifier& pcs, size_t n, size_t l, 
   const std::vector<HFr>&r_N = claims[0].point, &r_M = claims[2].point;
   const HFr delta = tr.squeeze_challenge();
   const FracVerifyResult fr = verify_fractional_sum_check(2, n, nullptr, nullptr, tr);
-  // the LogUp identity on the roots: P_0 / Q_0 + P_1 / Q_1 = 0 with both denominators non-zero
-  if (fr.q_0s[0].is_zero() || fr.q_0s[1].is_zero() || !(fr.p_0s[0] * fr.q_0s[1] + fr.p_0s[1] * fr.q_0s[0]).is_zero())
+  if (!logup_roots_cancel(fr.p_0s[0], fr.q_0s[0], fr.p_0s[1], fr.q_0s[1]))  // the LogUp identity on the roots
     throw Error(LH_ERR_INVALID_SNARK, "memcheck: the fractions do not sum to zero");
   const std::vector<HFr> v = tr.read_field_elements(8);  // addr, rv, wv, rt at r_N; fv, ft at r_M; rt, m at x
-  auto h = [&](const HFr& a, const HFr& val, const HFr& ts) { return a * gamma * gamma + val * gamma + ts - tau; };
+  const Fingerprint h{gamma, tau};
   const HFr one = HFr::one(), id_N = identity_eval(r_N), id_M = identity_eval(r_M), id_x = identity_eval(fr.x);
-  const HFr init_e = init ? memcheck_init_eval(init, l, r_M) : HFr::zero();
+  // (the image's extension at r_M: one fold over its 2^l words)
+  const HFr init_e = init ? host_table_eval(l, r_M, [&](size_t a) { return HFr::from_u64(init[a]); }) : HFr::zero();
   if (claims[0].claim != h(v[0], v[1], v[3]) || claims[1].claim != h(v[0], v[2], id_N + one) ||
       claims[2].claim != h(id_M, init_e, HFr::zero()) || claims[3].claim != h(id_M, v[4], v[5]))
     throw Error(LH_ERR_INVALID_SNARK, "memcheck: leaf claim mismatch");
@@ -232,18 +179,10 @@ static void memcheck_verify_checked(const PcsVerifier& pcs, size_t n, size_t l, 
   const std::vector<lh_evaluation> evs = memcheck_evaluations(v);
   pcs.batch_verify(nv, comms.data(), comms.size(), points.data(), 3, evs.data(), evs.size(), tr);
 }
-// A proof that does not verify is LH_ERR_INVALID_SNARK whichever piece found it out; what is wrong with the call keeps its code
 void memcheck_verify(const PcsVerifier& pcs, size_t n, size_t l, const uint32_t* init, Transcript& tr) {
   const size_t nv = memcheck_check(n, l, init != nullptr);
-  LH_REQUIRE(pcs.chunks == 1 && !pcs.read_commitments, LH_ERR_ARG, "memcheck: implemented for commitments of one point");
-  try {
-    memcheck_verify_checked(pcs, n, l, nv, init, tr);
-  } catch (const Error& e) {
-    if (e.code == LH_ERR_INVALID_SUMCHECK || e.code == LH_ERR_INVALID_PCS_OPEN || e.code == LH_ERR_TRANSCRIPT ||
-        e.code == LH_ERR_SERIALIZATION)
-      throw Error(LH_ERR_INVALID_SNARK, "memcheck: " + e.msg);
-    throw;
-  }
+  argument_pcs_check(pcs, "memcheck");
+  argument_verdict("memcheck", [&] { memcheck_verify_checked(pcs, n, l, nv, init, tr); });
 }
 
 }  // namespace lh

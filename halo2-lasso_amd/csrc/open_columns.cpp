@@ -8,8 +8,6 @@
 
 namespace lh {
 
-static inline uint32_t bits_of_u32(uint32_t v) { return v ? 32u - (uint32_t)__builtin_clz(v) : 0u; }
-
 // ---- which quotient levels go column by column: the largest always; the second largest too when few columns take
 // part.  After d folds the remainder is sum_s w_s g'[s 2^(n-d) + .] over the 2^d settings s of the top d index bits
 // (w_s = the product of x_j or 1 - x_j over those bits), so the quotient of level n-1-d is the same kind of sum of
@@ -36,7 +34,7 @@ void column_shape(Ctx& c, const std::vector<SmallPoly>& cols, const std::vector<
   size_t passes = 0, narrow_cols = 0;
   for (size_t k = 0; k < K; k++) {
     if (cols[k].len <= half_top || zero[k] || !ors[k]) continue;
-    const uint32_t b1 = bits_of_u32(ors[k]) + 1;
+    const uint32_t b1 = bit_length(ors[k]) + 1;
     if (b1 > 32) passes += 2;
     else if (b1 <= MSM_PACK_MAX_BITS - 4) narrow_cols++;
     else passes += 1;
@@ -84,7 +82,7 @@ void column_jobs(Ctx& c, const Srs& srs, const std::vector<SmallPoly>& cols, con
           cl.terms.push_back(ColTerm{jobs.size() - 1, false, k, sidx, -1});
           continue;
         }
-        const uint32_t b = bits_of_u32(ors[k]);
+        const uint32_t b = bit_length(ors[k]);
         if (!b) continue;  // an all-zero column
         const uint64_t off = (uint64_t)1 << b;
         cl.offsets.push_back(ColOffset{k, sidx, off});

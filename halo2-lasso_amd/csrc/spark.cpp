@@ -28,13 +28,7 @@ struct SparkLayout {
 std::vector<lh_evaluation> spark_evaluations(const SparkLayout& lay, const std::vector<HFr>& at_rz, const std::vector<HFr>& at_leaves) {
   const size_t c = lay.c;
   std::vector<lh_evaluation> evs;
-  auto put = [&](size_t poly, size_t point, const HFr& v) {
-    lh_evaluation e;
-    memset(&e, 0, sizeof(e));
-    e.poly = (uint32_t)poly, e.point = (uint32_t)point;
-    memcpy(&e.value, &v, 32);
-    evs.push_back(e);
-  };
+  auto put = [&](size_t poly, size_t point, const HFr& v) { evs.push_back(make_evaluation(poly, point, &v)); };
   put(lay.val(), 0, at_rz[0]);
   for (size_t j = 0; j < c; j++) put(lay.E(j), 0, at_rz[1 + j]);
   for (size_t j = 0; j < c; j++) put(lay.dim(j), 1, at_leaves[j]);
@@ -53,15 +47,6 @@ void spark_header(Transcript& tr, size_t n, size_t l, size_t c, const std::vecto
   for (const HG1& cm : comms)
     if (!cm.is_identity()) tr.common_commitment(cm);
   for (size_t i = 0; i < c * l; i++) tr.common_field_element(point[i]);
-}
-void spark_not_sharded(Ctx& c) {
-  LH_REQUIRE(!Shard(c).on && !(c.has_comm && c.comm.size > 1), LH_ERR_ARG,
-             "spark: sharded proofs are not supported (the ctx is inside a sharded prove or has a communicator of several ranks)");
-}
-void spark_pcs_check(const Pcs& pcs, size_t nv) {
-  LH_REQUIRE(pcs.chunks == 1 && pcs.batch_commit && pcs.commit_bases && !pcs.commit_and_write && !pcs.commit_columns_and_write,
-             LH_ERR_ARG, "spark: implemented for schemes whose commitment is one point over bases");
-  if (nv > pcs.max_vars) throw Error(LH_ERR_INVALID_PCS_PARAM, "Too many variates of poly to commit");
 }
 // every index below 2^l?  The OR of a column decides it exactly: 2^l is a power of two
 void spark_range_check(Ctx& c, const uint32_t* const* dims, size_t cc, size_t N, size_t l, uint32_t* ors) {
@@ -106,8 +91,8 @@ SparkPoly* spark_commit(Ctx& c, const Pcs& pcs, size_t n, size_t l, size_t cc, c
   LH_REQUIRE(d_dims != nullptr, LH_ERR_ARG, "null argument: d_dims");
   for (size_t j = 0; j < cc; j++) LH_REQUIRE(d_dims[j] != nullptr, LH_ERR_ARG, "null argument: d_dims[" + std::to_string(j) + "]");
   LH_REQUIRE(d_val != nullptr, LH_ERR_ARG, "null argument: d_val");
-  spark_not_sharded(c);
-  spark_pcs_check(pcs, nv);
+  argument_not_sharded(c, "spark");
+  argument_pcs_check(pcs, nv, "spark", true);
   const size_t N = (size_t)1 << n, M = (size_t)1 << l, NV = (size_t)1 << nv;
   open_precommit_cancel(c);
   ArenaScope scope(c.arena);
@@ -136,30 +121,23 @@ SparkPoly* spark_commit(Ctx& c, const Pcs& pcs, size_t n, size_t l, size_t cc, c
     uint32_t* dim = words + j * (2 * N + M);
     LH_HIP(hipMemcpyAsync(dim, d_dims[j], N * sizeof(uint32_t), hipMemcpyDeviceToDevice, c.stream));
     p.dim[j] = dim, p.rts[j] = rts[j] = dim + N, p.fcs[j] = fcs[j] = dim + 2 * N;
-    p.dim_bits[j] = std::max(bit_length(or_dim[j]), 1u);
   }
   // (the copies are checked columns: what the caller does to its own afterwards does not reach the handle.  Between the
   // check above and the copy the caller's columns are the caller's to leave alone, as during any prove)
   k_lasso_counters(c, p.dim, cc, N, M, rts, fcs);
 
-  // ---- the commitments: val through batch_commit, every u32 column as a 32-bit MSM over its own length against the bases of
-  // level nv, its width promised from the OR of its entries - the way LogUp-GKR and memcheck commit theirs
-  const SparkLayout lay{cc};
-  p.comms.resize(lay.committed());
-  p.comms[lay.val()] = pcs.batch_commit(&p.val, 1, nv)[0];
+  // ---- the commitments: val through batch_commit, every u32 column as a 32-bit MSM over its own length (commit_u32_columns;
+  // the dims' ORs are the range check's), in commitment order (SparkLayout)
+  p.comms = pcs.batch_commit(&p.val, 1, nv);
   {
-    uint32_t or_rts[SPARK_MAX_DIMS], or_fcs[SPARK_MAX_DIMS];
-    k_or_u32(c, p.rts, cc, N, or_rts);
-    k_or_u32(c, p.fcs, cc, M, or_fcs);
-    std::vector<MsmJob> jobs;
-    auto job = [&](const uint32_t* col, size_t len, uint32_t bits) {
-      jobs.push_back(MsmJob{col, true, pcs.commit_bases(nv), len});
-      jobs.back().known_bits = bits;
-    };
-    for (size_t j = 0; j < cc; j++) job(p.dim[j], N, p.dim_bits[j]);
-    for (size_t j = 0; j < cc; j++) job(p.rts[j], N, p.rts_bits[j] = std::max(bit_length(or_rts[j]), 1u));
-    for (size_t j = 0; j < cc; j++) job(p.fcs[j], M, p.fcs_bits[j] = std::max(bit_length(or_fcs[j]), 1u));
-    msm_batch(c, jobs.data(), jobs.size(), (G1Affine*)(p.comms.data() + 1));
+    std::vector<U32Column> cols;
+    for (size_t j = 0; j < cc; j++) cols.push_back(U32Column{p.dim[j], N, &or_dim[j]});
+    for (size_t j = 0; j < cc; j++) cols.push_back(U32Column{p.rts[j], N});
+    for (size_t j = 0; j < cc; j++) cols.push_back(U32Column{p.fcs[j], M});
+    std::vector<uint32_t> bits(cols.size());
+    const std::vector<HG1> out = commit_u32_columns(c, pcs, nv, cols, bits.data());
+    p.comms.insert(p.comms.end(), out.begin(), out.end());
+    for (size_t j = 0; j < cc; j++) p.dim_bits[j] = bits[j], p.rts_bits[j] = bits[cc + j], p.fcs_bits[j] = bits[2 * cc + j];
   }
   {
     KeccakTranscript kt;
@@ -178,8 +156,8 @@ HFr spark_open(Ctx& c, const Pcs& pcs, const SparkPoly& p, const HFr* point, Tra
   LH_REQUIRE(std::find(c.spark_polys.begin(), c.spark_polys.end(), &p) != c.spark_polys.end(), LH_ERR_ARG,
              "spark: the polynomial was not committed on this ctx (or has been freed)");
   const size_t n = p.n, l = p.l, cc = p.c, nv = p.nv;
-  spark_not_sharded(c);
-  spark_pcs_check(pcs, nv);
+  argument_not_sharded(c, "spark");
+  argument_pcs_check(pcs, nv, "spark", true);
   const size_t N = (size_t)1 << n, M = (size_t)1 << l, NV = (size_t)1 << nv;
   const SparkLayout lay{cc};
   open_precommit_cancel(c);
@@ -233,51 +211,34 @@ HFr spark_open(Ctx& c, const Pcs& pcs, const SparkPoly& p, const HFr* point, Tra
   {
     ArenaScope inner(c.arena);
     const bool fused = c.opt.logup_fused_leaves != 0;
-    const bool up_n = fused && n >= 12, up_l = fused && l >= 12;  // (the tree builder takes the level from 11 variables on)
+    const bool up_n = fused && n >= GP_LEVEL_UP_MIN_VARS, up_l = fused && l >= GP_LEVEL_UP_MIN_VARS;
     const bool ws_implicit = up_n && n > l;
     SparkLeaves a;
     memset(&a, 0, sizeof(a));
-    std::vector<const Fr*> leaves(4 * cc), level_up(4 * cc, nullptr);
-    std::vector<size_t> depths(4 * cc, n);
-    std::vector<uint8_t> plus_one(4 * cc, 0);
+    MemoryTrees trees(cc, n);
     for (size_t j = 0; j < cc; j++) {
+      const MemoryTrees::Memory m = trees.add(c, j, N, l, up_n, ws_implicit, up_l);
       a.dim[j] = p.dim[j], a.rts[j] = p.rts[j], a.fcs[j] = p.fcs[j], a.E[j] = E[j], a.T[j] = T[j];
-      a.rs[j] = c.arena.alloc_n<Fr>(N);
-      a.ws[j] = ws_implicit ? nullptr : c.arena.alloc_n<Fr>(N);
-      a.init[j] = c.arena.alloc_n<Fr>(M), a.fin[j] = c.arena.alloc_n<Fr>(M);
-      if (up_n) a.rs_up[j] = c.arena.alloc_n<Fr>(N / 2), a.ws_up[j] = c.arena.alloc_n<Fr>(N / 2);
-      if (up_l) a.init_up[j] = c.arena.alloc_n<Fr>(M / 2), a.fin_up[j] = c.arena.alloc_n<Fr>(M / 2);
-      leaves[2 * j] = a.rs[j], leaves[2 * j + 1] = a.ws[j], plus_one[2 * j + 1] = 1;
-      level_up[2 * j] = a.rs_up[j], level_up[2 * j + 1] = a.ws_up[j];
-      leaves[2 * cc + 2 * j] = a.init[j], leaves[2 * cc + 2 * j + 1] = a.fin[j];
-      level_up[2 * cc + 2 * j] = a.init_up[j], level_up[2 * cc + 2 * j + 1] = a.fin_up[j];
-      depths[2 * cc + 2 * j] = depths[2 * cc + 2 * j + 1] = l;
+      a.rs[j] = m.rs, a.ws[j] = m.ws, a.rs_up[j] = m.rs_up, a.ws_up[j] = m.ws_up;
+      a.init[j] = m.init, a.fin[j] = m.fin, a.init_up[j] = m.init_up, a.fin_up[j] = m.fin_up;
     }
     k_spark_leaves(c, a, cc, N, l, up_n, up_l, dev(gamma), dev(gamma * gamma), dev(tau));
-    const GrandProductResult gp = prove_grand_product(c, 4 * cc, leaves.data(), depths.data(), tr, level_up.data(), plus_one.data());
+    const GrandProductResult gp = trees.prove(c, tr);
     r_N = gp.points[0], r_M = gp.points[2 * cc];
   }
 
   // ---- 6: dim_j | read_ts_j | E_j at r_N, final_cts_j at r_M: the u32 columns against the eq table of their point
   std::vector<HFr> at_leaves(4 * cc);
   {
-    ArenaScope inner(c.arena);
-    Fr* eq = c.arena.alloc_n<Fr>(N);
-    k_eq_xy(c, (const Fr*)r_N.data(), n, eq);
     std::vector<const uint32_t*> cols(p.dim, p.dim + cc);
     cols.insert(cols.end(), p.rts, p.rts + cc);
-    k_inner_products_small(c, cols.data(), cols.size(), eq, N, (Fr*)at_leaves.data());
+    evaluate_u32_columns(c, cols.data(), cols.size(), r_N.data(), n, at_leaves.data());
   }
   {
     const std::vector<HFr> e = evaluate_polys(c, E, cc, n, r_N.data());
     std::copy(e.begin(), e.end(), at_leaves.begin() + 2 * cc);
   }
-  {
-    ArenaScope inner(c.arena);
-    Fr* eq = c.arena.alloc_n<Fr>(M);
-    k_eq_xy(c, (const Fr*)r_M.data(), l, eq);
-    k_inner_products_small(c, p.fcs, cc, eq, M, (Fr*)(at_leaves.data() + 3 * cc));
-  }
+  evaluate_u32_columns(c, p.fcs, cc, r_M.data(), l, at_leaves.data() + 3 * cc);
   tr.write_field_elements(at_leaves);
 
   // ---- 7: ONE batch opening over nv variables: the u32 columns go as their 32-bit columns, val and E_j as tables - the mixed
@@ -357,7 +318,7 @@ static void spark_verify_checked(const PcsVerifier& pcs, size_t n, size_t l, siz
       throw Error(LH_ERR_INVALID_SNARK, "spark: dimension " + std::to_string(j) + ": Init*WS != RS*Final");
   const std::vector<HFr>&r_N = claims[0].point, &r_M = claims[2 * cc].point;
   const std::vector<HFr> at_leaves = tr.read_field_elements(4 * cc);  // dim_j | read_ts_j | E_j at r_N, final_cts_j at r_M
-  auto h = [&](const HFr& a, const HFr& val, const HFr& ts) { return a * gamma * gamma + val * gamma + ts - tau; };
+  const Fingerprint h{gamma, tau};
   const HFr one = HFr::one(), id_M = identity_eval(r_M);
   for (size_t j = 0; j < cc; j++) {
     // the memory's extension in closed form: T_j~(r_M) = eq(r_M, r_j) - the verifier never sees a table
@@ -372,20 +333,12 @@ static void spark_verify_checked(const PcsVerifier& pcs, size_t n, size_t l, siz
   const std::vector<lh_evaluation> evs = spark_evaluations(lay, at_rz, at_leaves);
   pcs.batch_verify(nv, comms.data(), comms.size(), points.data(), 3, evs.data(), evs.size(), tr);
 }
-// A proof that does not verify is LH_ERR_INVALID_SNARK whichever piece found it out; what is wrong with the call keeps its code
 void spark_verify(const PcsVerifier& pcs, size_t n, size_t l, size_t cc, const uint8_t* commitment, size_t commitment_len,
                   const HFr* point, const HFr& value, Transcript& tr) {
   const size_t nv = spark_check(n, l, cc);
   LH_REQUIRE(commitment != nullptr && point != nullptr, LH_ERR_ARG, "null argument: commitment or point");
-  LH_REQUIRE(pcs.chunks == 1 && !pcs.read_commitments, LH_ERR_ARG, "spark: implemented for commitments of one point");
-  try {
-    spark_verify_checked(pcs, n, l, cc, nv, commitment, commitment_len, point, value, tr);
-  } catch (const Error& e) {
-    if (e.code == LH_ERR_INVALID_SUMCHECK || e.code == LH_ERR_INVALID_PCS_OPEN || e.code == LH_ERR_TRANSCRIPT ||
-        e.code == LH_ERR_SERIALIZATION)
-      throw Error(LH_ERR_INVALID_SNARK, "spark: " + e.msg);
-    throw;
-  }
+  argument_pcs_check(pcs, "spark");
+  argument_verdict("spark", [&] { spark_verify_checked(pcs, n, l, cc, nv, commitment, commitment_len, point, value, tr); });
 }
 
 }  // namespace lh

@@ -1123,7 +1123,7 @@ static std::vector<LassoClaims> lasso_check_tables(const lh_lasso_table* const* 
     if (inf[2 * b] * rw[2 * b + 1] != rw[2 * b] * inf[2 * b + 1])
       throw Error(LH_ERR_INVALID_SNARK, "memory " + std::to_string(b) + ": Init*WS != RS*Final");
 
-  auto fingerprint = [&](const HFr& a, const HFr& val, const HFr& ts) { return a * gamma * gamma + val * gamma + ts - tau; };
+  const Fingerprint fingerprint{gamma, tau};
   const HFr one = HFr::one();
   const GpClaim *rw_c = claims.data(), *inf_c = claims.data() + 2 * A;
   for (size_t t = 0; t < K; t++) {
@@ -1202,20 +1202,10 @@ static void lasso_verify_batch_checked(const PcsVerifier& pcs, const lh_lasso_ta
   lasso_append_points(points, pts, nv);
   pcs.batch_verify(nv, comms.data(), comms.size(), points.data(), pts.size(), evals.data(), evals.size(), tr);
 }
-// A proof that does not verify is LH_ERR_INVALID_SNARK whichever piece found it out (a round message, an opening, bytes that
-// are no point or no field element, a proof that ends early): the message keeps the piece's own words.  What is wrong with
-// the call, not with the proof, keeps its code (LH_ERR_ARG, LH_ERR_INVALID_PCS_PARAM).
 void lasso_verify_batch(const PcsVerifier& pcs, const lh_lasso_table* const* tables, size_t K, size_t n, Transcript& tr) {
   const size_t nv = lasso_batch_check(tables, K, n);
-  LH_REQUIRE(pcs.chunks == 1 && !pcs.read_commitments, LH_ERR_ARG, "lasso batch: implemented for commitments of one point");
-  try {
-    lasso_verify_batch_checked(pcs, tables, K, n, nv, tr);
-  } catch (const Error& e) {
-    if (e.code == LH_ERR_INVALID_SUMCHECK || e.code == LH_ERR_INVALID_PCS_OPEN || e.code == LH_ERR_TRANSCRIPT ||
-        e.code == LH_ERR_SERIALIZATION)
-      throw Error(LH_ERR_INVALID_SNARK, "lasso batch: " + e.msg);
-    throw;
-  }
+  argument_pcs_check(pcs, "lasso batch");
+  argument_verdict("lasso batch", [&] { lasso_verify_batch_checked(pcs, tables, K, n, nv, tr); });
 }
 
 // ------------------------------------------------------------------ Brakedown (pcs/multilinear/brakedown.rs:315-396)

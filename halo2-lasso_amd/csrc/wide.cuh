@@ -1,5 +1,6 @@
-// Wide integer accumulation of Fr weights times small integers (device only): kernels_poly.hip's small-valued column
-// kernels and the field-edge probe (ff_probe.hip) include it.
+// Wide integer accumulation of Fr weights times small integers (device only): the small-valued column kernels of
+// kernels_poly.hip, kernels_logup.hip, kernels_memcheck.hip, kernels_spark.hip and kernels_brakedown.hip and the field-edge
+// probe (ff_probe.hip) include it.
 #pragma once
 #include "ff.cuh"
 
@@ -72,6 +73,12 @@ __device__ __forceinline__ Fr wide_redc(const Wide& acc) {
 #pragma unroll
   for (int k = 0; k < 8; k++) r.l[k] = a[8 + k];
   return reduce_once(r);
+}
+// a 32-bit integer as a field element: 8 multiply-adds and one reduction (one_r = R^2 mod r, the prescaled one)
+__device__ __forceinline__ Fr wide_small(const Fr& one_r, uint32_t v) {
+  Wide w = Wide::zero();
+  wide_mac(w, one_r, v);
+  return wide_redc(w);
 }
 
 }  // namespace lh

@@ -156,6 +156,7 @@ CASES = {
     "loads_only": (4, 3, True),
     "edges": (3, 2, True),
     "mid": (13, 9, True),
+    "wide": (9, 12, True),  # more cells than operations: the cell side's leaves come with the level above them
 }
 SMALL = [c for c in CASES if max(CASES[c][:2]) <= 6]  # the cases the golden SRS of six variables covers
 EDGE_WORDS = [0, 1, 1 << 16, 1 << 31, (1 << 32) - 1]

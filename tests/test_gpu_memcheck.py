@@ -110,7 +110,7 @@ def test_bytes_do_not_depend_on_the_switches(hl, ctx, kzg6, kzg16, case):
 
 
 # ------------------------------------------------------------------ 3. launch records
-@pytest.mark.parametrize("case", ["small_mem", "mid"])
+@pytest.mark.parametrize("case", ["small_mem", "mid", "wide"])  # (wide: the level above comes with the cells' leaves alone)
 def test_launch_records(hl, ctx, kzg6, kzg16, case):
     pp, _ = kzg6 if case in mcr.SMALL else kzg16
     n, l, _ = mcr.CASES[case]

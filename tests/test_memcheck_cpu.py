@@ -51,8 +51,8 @@ def verify(hl, vp, case, proof=None, **over):
 
 # ------------------------------------------------------------------ 1. the specification
 def test_the_cases_are_the_named_ones():
-    assert set(GOLDEN) == set(mcr.CASES) and len(mcr.CASES) == 9 and set(FORGED) == set(mcr.FORGERIES)
-    assert mcr.SMALL == [c for c in CASES if c != "mid"] and len(SS) == 6
+    assert set(GOLDEN) == set(mcr.CASES) and len(mcr.CASES) == 10 and set(FORGED) == set(mcr.FORGERIES)
+    assert mcr.SMALL == [c for c in CASES if c not in ("mid", "wide")] and len(SS) == 6
     for case, (n, l, has_init) in mcr.CASES.items():
         g = GOLDEN[case]
         assert (g["n"], g["l"], g["init"]) == (n, l, has_init) and (mcr.case_init(case) is not None) == has_init
