@@ -13,6 +13,7 @@
 
 #include "../../include/lasso_hip.h"
 #include "ec.cuh"
+#include "round.cuh"  // ScFinishArgs, SC_LANE_TAG_SHIFT
 
 namespace lh {
 
@@ -90,29 +91,7 @@ struct ProfRec {
   double items;  // work items (pairs, points, ...)
 };
 
-struct ScFinishArgs {
-  uint32_t* ticket;      // device counter
-  uint32_t last_ticket;  // value the last workgroup of this launch draws
-  Fr* out_host;          // pinned
-  uint32_t* flag;        // pinned
-  uint32_t seq;
-  // sharded rounds, all-reduce variant (Options::comm_round, comm.cpp comm_sum_publish): the sums ALSO leave as 8 u64
-  // lanes each, lane = 32-bit limb | tag << SC_LANE_TAG_SHIFT - what ncclAllReduce(ncclSum, ncclUint64) adds over the ranks
-  // without losing a carry; null otherwise
-  uint64_t* wide;
-  uint32_t tag;
-  // the workgroups' partial sums on their way to the workgroup that draws the launch's last ticket, as 8-byte lanes
-  // (limb | seq << 32) in a buffer that holds nothing else (Ctx::fin_lanes, resident.cuh fin_put / fin_get): each lane
-  // validates itself, so the hand-off needs no fence - an agent-scope release per workgroup makes the L2 of its XCD walk its
-  // dirty lines, ~27 ns per workgroup of a launch that has just stored a table (tools/ubench/u32_bind.hip: a 2^24-entry
-  // bind 0.147 -> 0.108 ms).  Null: the partials travel through `partials` under release / acquire fences.
-  uint64_t* lanes;
-};
 constexpr uint32_t FIN_LANE_SUMS = 65536;  // partial sums the lane buffer holds (a launch's workgroups x its sums per workgroup)
-// a lane of the all-reduce variant: bits [0, 40) the sum of <= 2^8 32-bit limbs, bits [40, 64) the sum of the ranks' tags -
-// every rank stamps the same tag < 2^24 / R, so a lane whose upper bits read R * tag is the finished sum of THIS round
-// (lanes are 8-byte stores: each validates itself, no flag and no ordering between them is needed)
-constexpr unsigned SC_LANE_TAG_SHIFT = 40;
 
 // ------------------------------------------------------------------ route options and the route a proof took
 // The switches that decide WHICH code proves (not how fast a kernel runs).  Per ctx: set through lh_ctx_set_option
@@ -364,6 +343,28 @@ struct Ctx {
   void wait_chunks(const struct TailChunk* chunks, size_t count, uint32_t seq, Fr* out);
   // the same; false (nothing copied) when the first chunk carries `alt` instead
   bool wait_chunks_or(const struct TailChunk* chunks, size_t count, uint32_t seq, uint32_t alt, Fr* out);
+};
+
+// The host's half of a round kernel's hand-off (round.cuh), for the duration of one k_* wrapper: takes the round's
+// sequence number, opens an arena scope, redirects the output of a sharded round (Ctx::sc_redirect); hand_off() then
+// chooses `partials` - the output buffer itself when the launch is one workgroup with one slot of sums, arena memory
+// otherwise - and makes the kernel's ScFinishArgs; wait() is the host's wait for the sums.
+struct RoundLaunch {
+  Ctx& c;
+  const uint32_t seq;
+  ArenaScope scope;
+  Fr* const out;  // where the launch's sums go
+  Fr* partials = nullptr;
+  ScFinishArgs fin;
+  RoundLaunch(Ctx& c_, Fr* out_host) : c(c_), seq(c_.next_seq()), scope(c_.arena), out(c_.round_out(out_host)) {}
+  // `grid` workgroups that leave `slots` x `sums` partial sums each (slots > 1: finish_round_waves, whose single workgroup
+  // still draws a ticket - which finish_for does not count)
+  void hand_off(size_t grid, size_t sums, double stored_bytes = 0, size_t slots = 1) {
+    partials = grid * slots == 1 ? out : c.arena.alloc_n<Fr>(grid * slots * sums);
+    fin = c.finish_for((uint32_t)grid, out, seq, stored_bytes);
+    if (grid == 1 && slots > 1) c.ticket_base += 1;
+  }
+  void wait() { c.wait_round(seq); }
 };
 
 struct ShardActive {  // Ctx::shard_active for the duration of one sharded prove, whatever way it ends

@@ -25,7 +25,7 @@
 #include <string>
 #include <vector>
 #include "dev.hpp"
-#include "jit_sources.inc"  // JIT_FF_CUH, JIT_FF_COLS_INC, JIT_REDUCE_CUH: the text of ff.cuh / ff_cols.inc / reduce.cuh (Makefile)
+#include "jit_sources.inc"  // JIT_HEADERS[]: {name, text} of the device headers the compiled kernel includes (Makefile JIT_HDRS)
 
 namespace lh {
 
@@ -38,7 +38,7 @@ struct JitKernel {
 };
 
 namespace {
-struct JitArgs {  // mirrored in the generated source
+struct JitArgs {  // `Args` of the generated source (its ScFinishArgs is round.cuh's own: one definition for both compilers)
   const Fr* in[SC_MAX_TABLES];
   const Fr* consts;
   unsigned long long size;
@@ -57,11 +57,10 @@ std::string operand(uint32_t kind, uint32_t idx) {
 
 std::string generate(const uint32_t* code, size_t num_instrs, uint32_t num_regs, uint32_t result_reg, int D) {
   std::ostringstream s;
-  s << "#include \"ff.cuh\"\n#include \"reduce.cuh\"\nusing namespace lh;\n"
-       "struct Fin { unsigned* ticket; unsigned last_ticket; Fr* out_host; unsigned* flag; unsigned seq; unsigned long long* wide; unsigned tag; unsigned long long* lanes; };\n"
+  s << "#include \"ff.cuh\"\n#include \"reduce.cuh\"\n#include \"round.cuh\"\nusing namespace lh;\n"
        "struct Args { const Fr* in["
     << SC_MAX_TABLES
-    << "]; const Fr* consts; unsigned long long size; Fr* partials; Fin fin; };\n"
+    << "]; const Fr* consts; unsigned long long size; Fr* partials; ScFinishArgs fin; };\n"
        "// value of a bound table at the wave's evaluation point X = xm1 + 1: hi + (X - 1)(hi - lo)\n"
        "static __device__ __forceinline__ Fr at_x(const Fr* __restrict__ t, unsigned long long b, int xm1) {\n"
        "  const Fr lo = t[2 * b], hi = t[2 * b + 1];\n"
@@ -78,7 +77,6 @@ std::string generate(const uint32_t* code, size_t num_instrs, uint32_t num_regs,
        // X is the fast grid dimension so that the D workgroups reading the same pairs run at the same time and share
        // the tables through L2.
        "extern \"C\" __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void sc_round_jit(Args a) {\n"
-       "  __shared__ int is_last;\n"
        "  const int D = gridDim.x, NW = 4;\n"
        "  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, wave = blockIdx.x;  // wave = X - 1\n"
        "  const unsigned long long group = (unsigned long long)blockIdx.y * NW + w, ngroups = (unsigned long long)gridDim.y * NW;\n"
@@ -205,70 +203,10 @@ std::string generate(const uint32_t* code, size_t num_instrs, uint32_t num_regs,
     << ");\n"
        "    }\n"
        "  }\n"
-       // epilogue: wave sums to global memory, the workgroup that draws the launch's last ticket adds them up per
-       // evaluation point and publishes to pinned memory + flag (the protocol of sc_round_prog_kernel)
+       // epilogue: the closing step of a round kernel in its wave-per-point form (round.cuh) - slot = group of 64 pairs
        "  acc = wave_reduce_sum(acc);\n"
-       // (with a lane buffer - dev.hpp ScFinishArgs::lanes, the protocol of resident.cuh fin_put / fin_get - the wave sums
-       //  travel as self-validating 8-byte lanes and nobody fences)
-       "  unsigned long long* const lanes = a.fin.lanes;\n"
-       "  if (lane == 0) {\n"
-       "    if (lanes) {\n"
-       "      for (int k = 0; k < 8; k++)\n"
-       "        __hip_atomic_store(&lanes[(group * D + wave) * 8 + k], (unsigned long long)acc.l[k] | ((unsigned long long)a.fin.seq << 32),\n"
-       "                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n"
-       "    } else {\n"
-       "      a.partials[group * D + wave] = acc;\n"
-       "      __threadfence();\n"
-       "    }\n"
-       "  }\n"
-       "  __syncthreads();\n"
-       "  if (threadIdx.x == 0) {\n"
-       "    const unsigned t = lanes ? __hip_atomic_fetch_add(a.fin.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)\n"
-       "                             : __hip_atomic_fetch_add(a.fin.ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);\n"
-       "    is_last = t == a.fin.last_ticket;\n"
-       "  }\n"
-       "  __syncthreads();\n"
-       "  if (!is_last) return;\n"
-       "  if (!lanes) __threadfence();\n"
-       "  for (int x = w; x < D; x += NW) {\n"
-       "    Fr a2 = Fr::zero();\n"
-       "    for (unsigned long long i = lane; i < ngroups; i += 64) {\n"
-       "      Fr p;\n"
-       "      if (lanes) {\n"
-       "        for (int k = 0; k < 8; k++) {\n"
-       "          unsigned long long v = __hip_atomic_load(&lanes[(i * D + x) * 8 + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n"
-       "          for (unsigned spin = 0; (unsigned)(v >> 32) != a.fin.seq; spin++) {\n"
-       "            if (spin > (1u << 22)) __builtin_trap();\n"
-       "            __builtin_amdgcn_s_sleep(1);\n"
-       "            v = __hip_atomic_load(&lanes[(i * D + x) * 8 + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n"
-       "          }\n"
-       "          p.l[k] = (unsigned)v;\n"
-       "        }\n"
-       "      } else {\n"
-       "        p = a.partials[i * D + x];\n"
-       "      }\n"
-       "      a2 = add(a2, p);\n"
-       "    }\n"
-       "    a2 = wave_reduce_sum(a2);\n"
-       "    if (lane == 0) {\n"
-       "      a.fin.out_host[x] = a2;\n"
-       "      __threadfence_system();\n"
-       "    }\n"
-       "  }\n"
-       "  __syncthreads();\n"
-       // (dev.hpp ScFinishArgs::wide - sharded rounds of the all-reduce variant: the sums once more as tagged u64 lanes,
-       //  the protocol of resident.cuh publish_round)
-       "  if (threadIdx.x == 0) {\n"
-       "    if (a.fin.wide)\n"
-       "      for (int x = 0; x < D; x++)\n"
-       "        for (int k = 0; k < 8; k++) {\n"
-       "          const unsigned limb = __hip_atomic_load(&a.fin.out_host[x].l[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);\n"
-       "          a.fin.wide[8 * x + k] = (unsigned long long)limb | ((unsigned long long)a.fin.tag << "
-    << SC_LANE_TAG_SHIFT
-    << ");\n"
-       "        }\n"
-       "    __hip_atomic_store(a.fin.flag, a.fin.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);\n"
-       "  }\n"
+       "  if (lane == 0) fin_put(a.fin, a.partials, group * D + wave, acc);\n"
+       "  finish_round_waves(a.fin, a.partials, D, (unsigned)ngroups);\n"
        "}\n";
   return s.str();
 }
@@ -294,6 +232,14 @@ namespace {
 uint64_t fnv1a(const void* p, size_t n, uint64_t h) {
   const unsigned char* b = (const unsigned char*)p;
   for (size_t i = 0; i < n; i++) h = (h ^ b[i]) * 0x100000001b3ull;
+  return h;
+}
+constexpr int JIT_NUM_HEADERS = sizeof JIT_HEADERS / sizeof JIT_HEADERS[0];
+uint64_t hash_headers(uint64_t h) {  // every header the compiler is handed, name and text (with their terminators)
+  for (int i = 0; i < JIT_NUM_HEADERS; i++) {
+    h = fnv1a(JIT_HEADERS[i].name, strlen(JIT_HEADERS[i].name) + 1, h);
+    h = fnv1a(JIT_HEADERS[i].text, strlen(JIT_HEADERS[i].text) + 1, h);
+  }
   return h;
 }
 struct DiskHeader {
@@ -347,9 +293,7 @@ std::string disk_name(const std::string& src) {
                                      h = fnv1a(HIP_VERSION_GITHASH, sizeof HIP_VERSION_GITHASH, h);
                                      { const int patch = HIP_VERSION_PATCH; h = fnv1a(&patch, sizeof patch, h); }
                                      for (int i = 0; i < JIT_NUM_OPTS; i++) h = fnv1a(JIT_OPTS[i], strlen(JIT_OPTS[i]) + 1, h);
-                                     h = fnv1a(JIT_FF_CUH, sizeof JIT_FF_CUH, h);
-                                     h = fnv1a(JIT_FF_COLS_INC, sizeof JIT_FF_COLS_INC, h);
-                                     return fnv1a(JIT_REDUCE_CUH, sizeof JIT_REDUCE_CUH, h);
+                                     return hash_headers(h);
                                    }(),
                                    0};
   const uint64_t h0 = fnv1a(src.data(), src.size(), base[0]);
@@ -362,9 +306,7 @@ std::string disk_name(const std::string& src) {
 void source_hash(const std::string& src, uint64_t out[2]) {
   uint64_t h = 0xcbf29ce484222325ull;
   for (int i = 0; i < JIT_NUM_OPTS; i++) h = fnv1a(JIT_OPTS[i], strlen(JIT_OPTS[i]) + 1, h);
-  h = fnv1a(JIT_FF_CUH, sizeof JIT_FF_CUH, h);
-  h = fnv1a(JIT_FF_COLS_INC, sizeof JIT_FF_COLS_INC, h);
-  h = fnv1a(JIT_REDUCE_CUH, sizeof JIT_REDUCE_CUH, h);
+  h = hash_headers(h);
   out[0] = fnv1a(src.data(), src.size(), h);
   out[1] = fnv1a(src.data(), src.size(), out[0] ^ 0x9e3779b97f4a7c15ull);
 }
@@ -436,9 +378,9 @@ const JitKernel* jit_sc_round(const Ctx& c, const uint32_t* code, size_t num_ins
   size_t n = bin.size();
   if (!from_disk) {
     hiprtcProgram prog;
-    const char* hdr[] = {JIT_FF_CUH, JIT_REDUCE_CUH, JIT_FF_COLS_INC};
-    const char* names[] = {"ff.cuh", "reduce.cuh", "ff_cols.inc"};
-    if (hiprtcCreateProgram(&prog, src.c_str(), "sc_round_jit.hip", 3, hdr, names) != HIPRTC_SUCCESS) return nullptr;
+    const char *hdr[JIT_NUM_HEADERS], *names[JIT_NUM_HEADERS];
+    for (int i = 0; i < JIT_NUM_HEADERS; i++) hdr[i] = JIT_HEADERS[i].text, names[i] = JIT_HEADERS[i].name;
+    if (hiprtcCreateProgram(&prog, src.c_str(), "sc_round_jit.hip", JIT_NUM_HEADERS, hdr, names) != HIPRTC_SUCCESS) return nullptr;
     const hiprtcResult r = hiprtcCompileProgram(prog, JIT_NUM_OPTS, (const char**)JIT_OPTS);
     if (r != HIPRTC_SUCCESS) {
       size_t ln = 0;

@@ -13,9 +13,9 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include "dev.hpp"
+#include "round.cuh"
 #include "launch.cuh"
 #include "reduce.cuh"
-#include "resident.cuh"
 
 namespace lh {
 
@@ -106,29 +106,10 @@ void k_one_hot_table(Ctx& c, size_t n, size_t hot, Fr* out) {
 }
 
 // ------------------------------------------------------------------ sum-check round, monomials in device memory
-template <bool BIND>
-__device__ __forceinline__ void load_pair_ext(const Fr* __restrict__ in, Fr* __restrict__ out, size_t b, const Fr& r,
-                                              bool store, Fr& v0, Fr& v1) {
-  if (BIND) {
-    const Fr* p = in + 4 * b;
-    Fr e0 = p[0], e1 = p[1], e2 = p[2], e3 = p[3];
-    v0 = add(mul(sub(e1, e0), r), e0);
-    v1 = add(mul(sub(e3, e2), r), e2);
-    if (store) {
-      out[2 * b] = v0;
-      out[2 * b + 1] = v1;
-    }
-  } else {
-    v0 = in[2 * b];
-    v1 = in[2 * b + 1];
-  }
-}
-
 template <int D, bool BIND>
 __global__ __launch_bounds__(256) void sc_round_ext_kernel(ExtRound rd, size_t size, uint32_t tp,
                                                            Fr* __restrict__ partials, ScFinishArgs fin) {
   __shared__ Fr lds[4];
-  __shared__ int is_last;
   Fr acc[D];
 #pragma unroll
   for (int x = 0; x < D; x++) acc[x] = Fr::zero();
@@ -147,7 +128,7 @@ __global__ __launch_bounds__(256) void sc_round_ext_kernel(ExtRound rd, size_t s
       for (uint32_t k = 0; k < nf; k++) {
         const int t = rd.fac[o0 + k];
         Fr v0, v1;
-        load_pair_ext<BIND>(rd.in[t], rd.out[t], b, rd.r, rd.store[o0 + k] != 0, v0, v1);
+        load_pair<BIND>(rd.in[t], rd.out[t], b, rd.r, rd.store[o0 + k] != 0, v0, v1);
         if (k == 0) {
           if (!rd.is_one[m]) {
             v0 = mul(v0, rd.coeff[m]);
@@ -175,75 +156,30 @@ __global__ __launch_bounds__(256) void sc_round_ext_kernel(ExtRound rd, size_t s
 #pragma unroll
   for (int x = 0; x < D; x++) {
     Fr v = block_reduce_sum(acc[x], lds);
-    if (threadIdx.x == 0) partials[(size_t)blockIdx.x * D + x] = v;
+    if (threadIdx.x == 0) fin_put(fin, partials, (size_t)blockIdx.x * D + x, v);
   }
-  if (gridDim.x == 1) {
-    if (threadIdx.x == 0) publish_round(fin, D);
-    return;
-  }
-  // last-workgroup final reduction (same protocol as kernels_sumcheck.hip::finish_round)
-  if (threadIdx.x < 64) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (threadIdx.x == 0) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      const uint32_t t = __hip_atomic_fetch_add(fin.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const int last = t == fin.last_ticket;
-      if (last) {
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
-      is_last = last;
-    }
-  }
-  __syncthreads();
-  if (!is_last) return;
-  const uint32_t blocks = gridDim.x;
-#pragma unroll
-  for (int x = 0; x < D; x++) {
-    Fr a2 = Fr::zero();
-    for (uint32_t i = threadIdx.x; i < blocks; i += blockDim.x) a2 = add(a2, partials[(size_t)i * D + x]);
-    a2 = block_reduce_sum(a2, lds);
-    if (threadIdx.x == 0) fin.out_host[x] = a2;
-  }
-  if (threadIdx.x == 0) publish_round(fin, D);
-}
-
-template <int D>
-static void launch_ext(Ctx& c, const ExtRound& rd, bool bind, size_t size, uint32_t tp, unsigned grid, Fr* partials,
-                       const ScFinishArgs& fin) {
-  if (bind)
-    hipLaunchKernelGGL((sc_round_ext_kernel<D, true>), dim3(grid), dim3(256), 0, c.stream, rd, size, tp, partials, fin);
-  else
-    hipLaunchKernelGGL((sc_round_ext_kernel<D, false>), dim3(grid), dim3(256), 0, c.stream, rd, size, tp, partials, fin);
+  finish_round<D>(fin, partials, lds);
 }
 
 void k_sc_round_ext(Ctx& c, const ExtRound& rd, int degree, bool bind, size_t size, Fr* evals_host) {
   LH_REQUIRE(degree >= 2 && degree <= 8, LH_ERR_ARG, "sum-check degree must be in 2..8");
   LH_REQUIRE(size >= 1, LH_ERR_ARG, "sum-check round over an empty table");
-  const uint32_t seq = c.next_seq();
-  ArenaScope scope(c.arena);
+  RoundLaunch rl(c, evals_host);
   // one thread per (pair, monomial) while that still fits a few waves per SIMD, else one thread per pair
   const uint32_t tp = (rd.num_terms > 1 && size * rd.num_terms <= ((size_t)1 << 19)) ? rd.num_terms : 1u;
   const size_t g = cu_grid(c, size * tp);
-  evals_host = c.round_out(evals_host);  // (sharded rounds: the sums stay on the device, sumcheck.cpp)
-  Fr* partials = g == 1 ? evals_host : c.arena.alloc_n<Fr>(g * degree);
-  const ScFinishArgs fin = c.finish_for((uint32_t)g, evals_host, seq);
+  rl.hand_off(g, degree);
   {
     char name[40];
     snprintf(name, sizeof name, "sc_round_ext<%d,%s>%s", degree, bind ? "bind" : "first", tp > 1 ? "/tp" : "");
     ProfScope ps(c, name, (bind ? 192.0 : 64.0) * (double)size * rd.num_tables, 0, (double)size);
-    switch (degree) {
-      case 2: launch_ext<2>(c, rd, bind, size, tp, (unsigned)g, partials, fin); break;
-      case 3: launch_ext<3>(c, rd, bind, size, tp, (unsigned)g, partials, fin); break;
-      case 4: launch_ext<4>(c, rd, bind, size, tp, (unsigned)g, partials, fin); break;
-      case 5: launch_ext<5>(c, rd, bind, size, tp, (unsigned)g, partials, fin); break;
-      case 6: launch_ext<6>(c, rd, bind, size, tp, (unsigned)g, partials, fin); break;
-      case 7: launch_ext<7>(c, rd, bind, size, tp, (unsigned)g, partials, fin); break;
-      default: launch_ext<8>(c, rd, bind, size, tp, (unsigned)g, partials, fin); break;
-    }
+    dispatch_int<2, 8>(degree, [&](auto D) {
+      dispatch_bool(bind, [&](auto B) {
+        hipLaunchKernelGGL((sc_round_ext_kernel<D(), B()>), dim3((unsigned)g), dim3(256), 0, c.stream, rd, size, tp, rl.partials, rl.fin);
+      });
+    });
   }
-  c.wait_round(seq);
+  rl.wait();
 }
 
 // ------------------------------------------------------------------ sum-check round as a register program
@@ -279,7 +215,6 @@ __device__ __forceinline__ Fr prog_operand(const ProgRound& pr, const uint32_t* 
 __global__ __launch_bounds__(512) void sc_round_prog_kernel(ProgRound pr, size_t size, int D, Fr* __restrict__ partials,
                                                             ScFinishArgs fin) {
   extern __shared__ uint32_t prog_regs[];
-  __shared__ int is_last;
   const uint32_t nthreads = blockDim.x;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;  // wave = X - 1
   // the instruction stream lives in LDS behind the register file: a scalar load from global memory per
@@ -310,46 +245,15 @@ __global__ __launch_bounds__(512) void sc_round_prog_kernel(ProgRound pr, size_t
     }
   }
   acc = wave_reduce_sum(acc);
-  if (gridDim.x == 1) {
-    if (lane == 0) {
-      fin.out_host[wave] = acc;
-      __threadfence_system();
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) publish_round(fin, D);
-    return;
-  }
-  // (the partial sums travel as self-validating lanes when the launch has a lane buffer - resident.cuh fin_put: no fence)
-  if (lane == 0) {
-    fin_put(fin, partials, (size_t)blockIdx.x * D + wave, acc);
-    if (!fin.lanes) __threadfence();
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const uint32_t t = fin.lanes ? __hip_atomic_fetch_add(fin.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                                 : __hip_atomic_fetch_add(fin.ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-    is_last = t == fin.last_ticket;
-  }
-  __syncthreads();
-  if (!is_last) return;
-  if (!fin.lanes) __threadfence();
-  Fr a2 = Fr::zero();
-  for (uint32_t i = lane; i < gridDim.x; i += 64) a2 = add(a2, fin_get(fin, partials, (size_t)i * D + wave));
-  a2 = wave_reduce_sum(a2);
-  if (lane == 0) {
-    fin.out_host[wave] = a2;
-    __threadfence_system();
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) publish_round(fin, D);
+  if (lane == 0) fin_put(fin, partials, (size_t)blockIdx.x * D + wave, acc);
+  finish_round_waves(fin, partials, D, gridDim.x);
 }
 
 // (`degree`: the evaluation points X = 1..degree of this launch - the expression's degree, or one fewer in an eq-factored round)
 void k_sc_round_prog(Ctx& c, const ProgRound& pr, int degree, size_t size, Fr* evals_host, const JitKernel* jit) {
   LH_REQUIRE(degree >= 1 && degree <= 8, LH_ERR_ARG, "sum-check round: 1..8 evaluation points");
   LH_REQUIRE(size >= 1 && pr.num_regs >= 1 && pr.num_regs <= PROG_MAX_REGS, LH_ERR_ARG, "sum-check program: bad shape");
-  const uint32_t seq = c.next_seq();
-  ArenaScope scope(c.arena);
+  RoundLaunch rl(c, evals_host);
   const unsigned threads = 64u * (unsigned)degree;
   const size_t lds_bytes = (size_t)pr.num_regs * 32 * threads + (size_t)pr.num_instrs * 8;
   LH_REQUIRE(lds_bytes <= 150 * 1024, LH_ERR_ARG, "sum-check program: too large for LDS");
@@ -373,30 +277,26 @@ void k_sc_round_prog(Ctx& c, const ProgRound& pr, int degree, size_t size, Fr* e
   // compiled form: one wave per workgroup and a grid of (g, degree) workgroups, all of which draw a ticket
   const size_t cap = jit ? std::max<size_t>(1, (size_t)c.num_cus * (size_t)per_cu / (size_t)degree) : (size_t)c.num_cus * (size_t)per_cu;
   if (g > cap) g = cap;
-  evals_host = c.round_out(evals_host);  // (sharded rounds: the sums stay on the device, sumcheck.cpp)
-  // (compiled form: a workgroup is four groups of 64 pairs, each with a partial sum per point)
-  Fr* partials = (g == 1 && !jit) ? evals_host : c.arena.alloc_n<Fr>((jit ? 4 : 1) * g * degree);
-  const ScFinishArgs fin = c.finish_for((uint32_t)(jit ? g * degree : g), evals_host, seq);
-  // (the compiled kernel draws a ticket even when it is the launch's only workgroup - one point of an eq-factored round over a
-  //  few pairs -, which finish_for does not count)
-  if (jit && g * (size_t)degree == 1) c.ticket_base += 1;
+  // (compiled form: a workgroup is one point of four groups - slots - of 64 pairs; even the only workgroup of a launch - one
+  //  point of an eq-factored round over a few pairs - adds up four slots, behind a ticket)
+  if (jit) rl.hand_off(g * degree, 1, 0.0, 4);
+  else rl.hand_off(g, degree);
   {
     char name[40];
     snprintf(name, sizeof name, jit ? "sc_round_jit<%d>" : "sc_round_prog<%d>", degree);
     ProfScope ps(c, name, 64.0 * (double)size * pr.num_tables, 0, (double)size);
     if (jit)
-      jit_launch(c, jit, pr, (unsigned)degree, (unsigned)g, size, partials, fin);
+      jit_launch(c, jit, pr, (unsigned)degree, (unsigned)g, size, rl.partials, rl.fin);
     else
       hipLaunchKernelGGL(sc_round_prog_kernel, dim3((unsigned)g), dim3(threads), lds_bytes, c.stream, pr, size, degree,
-                         partials, fin);
+                         rl.partials, rl.fin);
   }
-  c.wait_round(seq);
+  rl.wait();
 }
 
 // ------------------------------------------------------------------ plain pair sums of a few tables (the zero-check's linear part)
 __global__ __launch_bounds__(256) void lin_sums_kernel(LinSums ls, size_t size, Fr* __restrict__ partials, ScFinishArgs fin) {
   __shared__ Fr lds[4];
-  __shared__ int is_last;
   Fr ev = Fr::zero(), od = Fr::zero();
   for (uint32_t i = 0; i < ls.count; i++) {
     const Fr* __restrict__ t = ls.t[i];
@@ -410,33 +310,19 @@ __global__ __launch_bounds__(256) void lin_sums_kernel(LinSums ls, size_t size, 
   }
   ev = block_reduce_sum(ev, lds);
   od = block_reduce_sum(od, lds);
-  if (gridDim.x == 1) {
-    if (threadIdx.x == 0) {
-      fin.out_host[0] = ev, fin.out_host[1] = od;
-      publish_round(fin, 2);
-    }
-    return;
-  }
   if (threadIdx.x == 0) {
     fin_put(fin, partials, (size_t)blockIdx.x * 2, ev), fin_put(fin, partials, (size_t)blockIdx.x * 2 + 1, od);
   }
-  if (!fin_ticket(fin, &is_last)) return;
-  for (int x = 0; x < 2; x++) {
-    Fr a2 = Fr::zero();
-    for (uint32_t i = threadIdx.x; i < gridDim.x; i += blockDim.x) a2 = add(a2, fin_get(fin, partials, (size_t)i * 2 + x));
-    a2 = block_reduce_sum(a2, lds);
-    if (threadIdx.x == 0) fin.out_host[x] = a2;
-  }
-  if (threadIdx.x == 0) publish_round(fin, 2);
+  finish_round<2>(fin, partials, lds);
 }
 void k_lin_sums(Ctx& c, const LinSums& ls, size_t size, Fr* out_host) {
   LH_REQUIRE(ls.count >= 1 && ls.count <= (uint32_t)LIN_MAX_TABLES && size >= 1, LH_ERR_ARG, "lin_sums: bad shape");
   const size_t g = std::min<size_t>((size + 255) / 256, (size_t)c.num_cus * 4);
-  // (nobody waits for this launch alone: the round's kernel behind it publishes the sequence number the host waits for;
-  //  the partials live as long as the caller's arena scope - the round's)
-  Fr* partials = c.arena.alloc_n<Fr>(2 * g);
-  const uint32_t seq = c.next_seq();
-  const ScFinishArgs fin = c.finish_for((uint32_t)g, c.round_out(out_host), seq);
+  // (no RoundLaunch: nobody waits for this launch alone - the round's kernel behind it publishes the sequence number the
+  //  host waits for - and the partials live as long as the caller's arena scope, the round's)
+  out_host = c.round_out(out_host);
+  Fr* partials = g == 1 ? out_host : c.arena.alloc_n<Fr>(2 * g);
+  const ScFinishArgs fin = c.finish_for((uint32_t)g, out_host, c.next_seq());
   ProfScope ps(c, "lin_sums", 64.0 * (double)size * ls.count, 0, (double)size);
   hipLaunchKernelGGL(lin_sums_kernel, dim3((unsigned)g), dim3(256), 0, c.stream, ls, size, partials, fin);
 }

@@ -267,7 +267,7 @@ __global__ __launch_bounds__(GKR_THREADS) void gkr_resident_kernel(GkrResArgs a)
           if (l5 == 0) part[wg * 2 + half] = v;
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
           last = 0;
-          if (lane == 0) last = tail_ticket(a.ticket, my_tbase + batch * g + g - 1) ? 1u : 0u;
+          if (lane == 0) last = draw_ticket(a.ticket, my_tbase + batch * g + g - 1) ? 1u : 0u;
           last = __shfl(last, 0, 64);
           if (last) {
             Fr w = Fr::zero();
@@ -319,7 +319,7 @@ __global__ __launch_bounds__(GKR_THREADS) void gkr_resident_kernel(GkrResArgs a)
             a.hand[(size_t)T * g + wg] = E[0];
           }
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          if (lane == 0) last_sh = tail_ticket(a.ticket, my_tbase + batch * g + g - 1) ? 1u : 0u;
+          if (lane == 0) last_sh = draw_ticket(a.ticket, my_tbase + batch * g + g - 1) ? 1u : 0u;
         }
         __syncthreads();
         if (!last_sh) {

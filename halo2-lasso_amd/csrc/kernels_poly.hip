@@ -8,7 +8,7 @@
 #include "ff_host.hpp"
 #include "launch.cuh"
 #include "reduce.cuh"
-#include "resident.cuh"
+#include "round.cuh"
 #include "wide.cuh"
 
 namespace lh {
@@ -917,7 +917,6 @@ __global__ __launch_bounds__(256) void lincomb_bind2_kernel(const LcBind2* __res
                                                             size_t entries, Fr* __restrict__ out, Fr* __restrict__ partials,
                                                             ScFinishArgs fin) {
   __shared__ Fr lds[4];
-  __shared__ int is_last;
   const LcBind2& pk = *pkp;
   const bool odd = threadIdx.x & 1;
   Fr acc = Fr::zero();
@@ -932,30 +931,15 @@ __global__ __launch_bounds__(256) void lincomb_bind2_kernel(const LcBind2* __res
     out[i] = v;
     acc = add(acc, mul(v, eq_level[i >> 1]));
   }
-  const Fr q0 = block_reduce_sum(odd ? Fr::zero() : acc, lds);
-  const Fr q1 = block_reduce_sum(odd ? acc : Fr::zero(), lds);
-  if (gridDim.x == 1) {
-    if (threadIdx.x == 0) {
-      fin.out_host[0] = q0, fin.out_host[1] = q1;
-      publish_round(fin, 2);
-    }
-    return;
-  }
+  Fr q0, q1;
+  reduce_by_parity(acc, odd, lds, q0, q1);
   if (threadIdx.x == 0) fin_put(fin, partials, (size_t)blockIdx.x * 2, q0), fin_put(fin, partials, (size_t)blockIdx.x * 2 + 1, q1);
-  if (!fin_ticket(fin, &is_last)) return;
-  for (int x = 0; x < 2; x++) {
-    Fr a2 = Fr::zero();
-    for (uint32_t i = threadIdx.x; i < gridDim.x; i += blockDim.x) a2 = add(a2, fin_get(fin, partials, (size_t)i * 2 + x));
-    a2 = block_reduce_sum(a2, lds);
-    if (threadIdx.x == 0) fin.out_host[x] = a2;
-  }
-  if (threadIdx.x == 0) publish_round(fin, 2);
+  finish_round<2>(fin, partials, lds);
 }
 void k_lincomb_bind2(Ctx& c, const uint32_t* const* cols, const size_t* lens, const Fr* w, size_t count, const Fr& r0, const Fr& r1,
                      const Fr* eq_level, size_t size, Fr* out, Fr* out_host) {
   LH_REQUIRE(count >= 1 && count <= (size_t)LCB_MAX && size >= 1 && !c.sc_redirect, LH_ERR_ARG, "lincomb_bind2: bad shape");
-  const uint32_t seq = c.next_seq();
-  ArenaScope scope(c.arena);
+  RoundLaunch rl(c, out_host);  // (no sharded form: sc_redirect is refused above)
   const size_t entries = 2 * size;
   host::Fr h0, h1;
   const host::Fr one = host::Fr::one();
@@ -980,13 +964,12 @@ void k_lincomb_bind2(Ctx& c, const uint32_t* const* cols, const size_t* lens, co
   LcBind2* d_pk = (LcBind2*)c.arena.alloc(sizeof(LcBind2));
   LH_HIP(hipMemcpyAsync(d_pk, h_pk, sizeof(LcBind2), hipMemcpyHostToDevice, c.stream));
   const size_t g = cu_grid(c, entries);
-  Fr* partials = c.arena.alloc_n<Fr>(g * 2);
-  const ScFinishArgs fin = c.finish_for((uint32_t)g, out_host, seq, 32.0 * (double)entries);
+  rl.hand_off(g, 2, 32.0 * (double)entries);
   {
     ProfScope ps(c, "lincomb<bind2,u32>", (16.0 * count + 32.0 + 16.0) * (double)entries, (0.25 * count + 1.6) * (double)entries, (double)size);
-    hipLaunchKernelGGL(lincomb_bind2_kernel, dim3((unsigned)g), dim3(256), 0, c.stream, d_pk, eq_level, entries, out, partials, fin);
+    hipLaunchKernelGGL(lincomb_bind2_kernel, dim3((unsigned)g), dim3(256), 0, c.stream, d_pk, eq_level, entries, out, rl.partials, rl.fin);
   }
-  c.wait_round(seq);  // (the pinned staging block is free again: the copy in front of the kernel has run)
+  rl.wait();  // (the pinned staging block is free again: the copy in front of the kernel has run)
 }
 
 // Round 2 of the same sum-check binds r0 AND r1 straight from the column: bound entry i is
@@ -1002,7 +985,6 @@ __global__ __launch_bounds__(256) void sc_round_u32_bind2_kernel(const uint32_t*
                                                                  U32Bind2 k, size_t entries, Fr* __restrict__ out,
                                                                  Fr* __restrict__ partials, ScFinishArgs fin) {
   __shared__ Fr lds[4];
-  __shared__ int is_last;
   Fr acc = Fr::zero();
   GSTRIDE(i, entries) {
     const uint4 a = ((const uint4*)col)[i];
@@ -1013,32 +995,16 @@ __global__ __launch_bounds__(256) void sc_round_u32_bind2_kernel(const uint32_t*
     if (i & 1) acc = add(acc, mul(v, eq_level[i >> 1]));
   }
   acc = block_reduce_sum(acc, lds);
-  if (gridDim.x == 1) {
-    if (threadIdx.x == 0) {
-      fin.out_host[0] = acc;
-      publish_round(fin, 1);
-    }
-    return;
-  }
   if (threadIdx.x == 0) fin_put(fin, partials, blockIdx.x, acc);
-  if (!fin_ticket(fin, &is_last)) return;
-  Fr a2 = Fr::zero();
-  for (uint32_t i = threadIdx.x; i < gridDim.x; i += blockDim.x) a2 = add(a2, fin_get(fin, partials, i));
-  a2 = block_reduce_sum(a2, lds);
-  if (threadIdx.x == 0) {
-    fin.out_host[0] = a2;
-    publish_round(fin, 1);
-  }
+  finish_round<1>(fin, partials, lds);
 }
 void k_sc_round_u32_bind2(Ctx& c, const uint32_t* col, const Fr* eq_level, const Fr& r0, const Fr& r1, size_t size, Fr* out,
                           Fr* out_host) {
   LH_REQUIRE(size >= 1 && !c.sc_redirect, LH_ERR_ARG, "sc_round_u32_bind2: bad shape");
-  const uint32_t seq = c.next_seq();
-  ArenaScope scope(c.arena);
+  RoundLaunch rl(c, out_host);  // (no sharded form: sc_redirect is refused above)
   const size_t entries = 2 * size;
   const size_t g = cu_grid(c, entries);
-  Fr* partials = c.arena.alloc_n<Fr>(g);
-  const ScFinishArgs fin = c.finish_for((uint32_t)g, out_host, seq, 32.0 * (double)entries);
+  rl.hand_off(g, 1, 32.0 * (double)entries);
   host::Fr h0, h1;
   const host::Fr one = host::Fr::one();
   memcpy(&h0, &r0, sizeof(h0));
@@ -1053,9 +1019,9 @@ void k_sc_round_u32_bind2(Ctx& c, const uint32_t* col, const Fr* eq_level, const
   {
     // per bound entry: 16 B of column, 32 B stored, 16 B of eq level; a reduction and half a product
     ProfScope ps(c, "sc_round_u32<bind2>", 64.0 * (double)entries, 1.2 * (double)entries, (double)size);
-    hipLaunchKernelGGL(sc_round_u32_bind2_kernel, dim3((unsigned)g), dim3(256), 0, c.stream, col, eq_level, k, entries, out, partials, fin);
+    hipLaunchKernelGGL(sc_round_u32_bind2_kernel, dim3((unsigned)g), dim3(256), 0, c.stream, col, eq_level, k, entries, out, rl.partials, rl.fin);
   }
-  c.wait_round(seq);
+  rl.wait();
 }
 
 // ------------------------------------------------------------------ GKR layer-up

@@ -15,6 +15,8 @@
 #include <stdlib.h>
 #include <algorithm>
 #include "dev.hpp"
+#include "round.cuh"
+#include "launch.cuh"
 #include "reduce.cuh"
 #include "resident.cuh"
 
@@ -25,50 +27,12 @@ struct ScArgs {
   uint8_t store[LH_SC_MAX_TERMS][LH_SC_MAX_FACTORS];  // first occurrence of a table stores its bound pair
 };
 
-template <bool BIND>
-__device__ __forceinline__ void load_pair(const Fr* __restrict__ in, Fr* __restrict__ out, size_t b, const Fr& r,
-                                          bool store, Fr& v0, Fr& v1) {
-  if (BIND) {
-    const Fr* p = in + 4 * b;
-    Fr e0 = p[0], e1 = p[1], e2 = p[2], e3 = p[3];
-    v0 = add(mul(sub(e1, e0), r), e0);
-    v1 = add(mul(sub(e3, e2), r), e2);
-    if (store) {
-      out[2 * b] = v0;
-      out[2 * b + 1] = v1;
-    }
-  } else {
-    v0 = in[2 * b];
-    v1 = in[2 * b + 1];
-  }
-}
-
 // `tp` (term parallelism) is 1 or num_terms: in the late, small rounds one thread per (pair, term)
 // keeps the dependent chain of a thread at one term (~15 field multiplications) instead of the
 // whole expression; the eq factor is linear, so it is applied per term before the reduction.
 
-// Final cross-workgroup reduction WITHOUT a second launch.  Every workgroup has stored its D partial sums
-// (threads of wave 0, plain stores); it then draws a ticket from a counter that only ever grows (the host
-// knows its value before the launch, so nothing has to be zeroed).  The workgroup that draws the last
-// ticket of the launch re-reads all partials, sums them and publishes the result to the host.
-// Hand-off protocol: cdna_hip_programming.md Guideline 16 (agent-scope release by every producer,
-// agent-scope acquire by the one consumer, never placement-dependent).
+// (the round's closing step - partial sums, ticket, final reduction by the last workgroup, publish: round.cuh)
 typedef ScFinishArgs ScFinish;
-
-template <int D>
-__device__ __forceinline__ void finish_round(const ScFinish& f, const Fr* __restrict__ partials, Fr* lds) {
-  __shared__ int is_last;
-  if (!fin_ticket(f, &is_last)) return;
-  const uint32_t blocks = gridDim.x;
-#pragma unroll
-  for (int x = 0; x < D; x++) {
-    Fr acc = Fr::zero();
-    for (uint32_t i = threadIdx.x; i < blocks; i += blockDim.x) acc = add(acc, fin_get(f, partials, (size_t)i * D + x));
-    acc = block_reduce_sum(acc, lds);
-    if (threadIdx.x == 0) f.out_host[x] = acc;
-  }
-  if (threadIdx.x == 0) publish_round(f, D);
-}
 
 // Occupancy of the streaming round kernels: the degree-2 instantiations (GKR layers, Surge, the batch opening: the
 // ones that run at 2^24) are asked for 4 waves per SIMD instead of the 3 the register allocator settles on by itself
@@ -148,10 +112,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(D <= 2 ? 4 
     Fr v = block_reduce_sum(acc[x], lds);
     if (threadIdx.x == 0) fin_put(fin, partials, (size_t)blockIdx.x * D + x, v);
   }
-  if (gridDim.x == 1) {  // single workgroup: `partials` IS the host buffer
-    if (threadIdx.x == 0) publish_round(fin, D);
-    return;
-  }
   finish_round<D>(fin, partials, lds);
 }
 
@@ -184,11 +144,6 @@ __device__ __forceinline__ Fr at_lane_point(const Fr& v, bool odd) {
   const Fr o = dpp_xor1(v);
   return odd ? v : sub(dbl(o), v);
 }
-// masked block reductions: even lanes' sum, then odd lanes' sum
-__device__ __forceinline__ void reduce_by_parity(const Fr& acc, bool odd, Fr* lds, Fr& even_sum, Fr& odd_sum) {
-  even_sum = block_reduce_sum(odd ? Fr::zero() : acc, lds);
-  odd_sum = block_reduce_sum(odd ? acc : Fr::zero(), lds);
-}
 
 // q(1), q(2) of  sum_b eq_level[b] * sum_m coeff_m prod_k table_{m,k}  (ScRound with eq_level): partials[.][0] = q(1)
 template <bool BIND>
@@ -217,10 +172,6 @@ __global__ __launch_bounds__(256) void sc_round_e2_kernel(ScArgs a, size_t size,
   if (threadIdx.x == 0) {
     fin_put(fin, partials, (size_t)blockIdx.x * 2, q1);
     fin_put(fin, partials, (size_t)blockIdx.x * 2 + 1, q2);
-  }
-  if (gridDim.x == 1) {
-    if (threadIdx.x == 0) publish_round(fin, 2);
-    return;
   }
   finish_round<2>(fin, partials, lds);
 }
@@ -296,10 +247,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
   if (threadIdx.x == 0) {
     fin_put(fin, partials, (size_t)blockIdx.x * 2, q1);
     fin_put(fin, partials, (size_t)blockIdx.x * 2 + 1, q2);
-  }
-  if (gridDim.x == 1) {
-    if (threadIdx.x == 0) publish_round(fin, 2);
-    return;
   }
   finish_round<2>(fin, partials, lds);
 }
@@ -394,34 +341,9 @@ __global__ __launch_bounds__(256) void sc_round_lds_kernel(ScLdsArgs g, size_t s
     Fr s = Fr::zero();
     for (uint32_t m = 0; m < rd.num_terms; m++) s = add(s, red[m * D + threadIdx.x]);
     fin_put(fin, partials, (size_t)blockIdx.x * D + threadIdx.x, s);
-    if (gridDim.x == 1) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+    if (gridDim.x == 1) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");  // (straight into the host buffer, by D threads)
   }
-  if (gridDim.x == 1) {  // single workgroup: `partials` IS the host buffer
-    __syncthreads();
-    if (threadIdx.x == 0) publish_round(fin, D);
-    return;
-  }
-  finish_round<D>(fin, partials, vals);  // vals is free again: 4 slots of it serve as reduction scratch
-}
-
-template <int D>
-static void launch_lds(Ctx& c, const ScLdsArgs& g, bool bind, size_t size, unsigned grid, Fr* partials,
-                       const ScFinish& fin) {
-  const size_t red_entries = std::max<size_t>((size_t)g.a.rd.num_terms * D * g.P, (size_t)g.a.rd.num_terms * D);
-  const size_t lds = ((size_t)g.vals_entries + red_entries) * sizeof(Fr);
-  if (bind)
-    hipLaunchKernelGGL((sc_round_lds_kernel<D, true>), dim3(grid), dim3(256), lds, c.stream, g, size, partials, fin);
-  else
-    hipLaunchKernelGGL((sc_round_lds_kernel<D, false>), dim3(grid), dim3(256), lds, c.stream, g, size, partials, fin);
-}
-
-template <int D>
-static void launch_round(Ctx& c, const ScArgs& a, bool bind, size_t size, uint32_t tp, unsigned grid, Fr* partials,
-                         const ScFinish& fin) {
-  if (bind)
-    hipLaunchKernelGGL((sc_round_kernel<D, true>), dim3(grid), dim3(256), 0, c.stream, a, size, tp, partials, fin);
-  else
-    hipLaunchKernelGGL((sc_round_kernel<D, false>), dim3(grid), dim3(256), 0, c.stream, a, size, tp, partials, fin);
+  finish_round<D, true>(fin, partials, vals);  // vals is free again: 4 slots of it serve as reduction scratch
 }
 
 // ------------------------------------------------------------------ resident tail (dev.hpp: k_sc_tail_*)
@@ -549,7 +471,7 @@ __global__ __launch_bounds__(TAIL_THREADS) void sc_tail_kernel(ScTailArgs a) {
           part[wg * 8 + tid] = s;
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (tid == 0) last_sh = tail_ticket(a.ticket, a.ticket_base + batch * G + G - 1) ? 1u : 0u;
+        if (tid == 0) last_sh = draw_ticket(a.ticket, a.ticket_base + batch * G + G - 1) ? 1u : 0u;
       }
       batch++;
       __syncthreads();
@@ -603,7 +525,7 @@ __global__ __launch_bounds__(TAIL_THREADS) void sc_tail_kernel(ScTailArgs a) {
           hand[(size_t)t * G + wg] = add(mul(sub(v1, v0), r), v0);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (tid == 0) last_sh = tail_ticket(a.ticket, a.ticket_base + batch * G + G - 1) ? 1u : 0u;
+        if (tid == 0) last_sh = draw_ticket(a.ticket, a.ticket_base + batch * G + G - 1) ? 1u : 0u;
       }
       __syncthreads();
       if (!last_sh) return;
@@ -841,44 +763,25 @@ __global__ __launch_bounds__(256) void sc_round_open_kernel(ScOpenRound rd, size
       fin_put(fin, partials, (size_t)blockIdx.x * NQ + 2 * m + 1, q1);
     }
   }
-  if (gridDim.x == 1) {
-    if (threadIdx.x == 0) publish_round(fin, NQ);
-    return;
-  }
   finish_round<NQ>(fin, partials, lds);
-}
-
-template <int M>
-static void launch_open(Ctx& c, const ScOpenRound& rd, bool bind, size_t size, unsigned g, Fr* partials, const ScFinish& fin) {
-  if (bind)
-    hipLaunchKernelGGL((sc_round_open_kernel<M, true>), dim3(g), dim3(256), 0, c.stream, rd, size, partials, fin);
-  else
-    hipLaunchKernelGGL((sc_round_open_kernel<M, false>), dim3(g), dim3(256), 0, c.stream, rd, size, partials, fin);
 }
 
 void k_sc_round_open(Ctx& c, const ScOpenRound& rd, bool bind, size_t size, Fr* out_host) {
   LH_REQUIRE(rd.num_terms >= 1 && rd.num_terms <= (uint32_t)SC_OPEN_MAX_TERMS && size >= 1, LH_ERR_ARG, "sc_round_open: bad shape");
-  const uint32_t seq = c.next_seq();
-  ArenaScope scope(c.arena);
-  out_host = c.round_out(out_host);  // (sharded rounds: the sums stay on the device, sumcheck.cpp)
-  size_t g = sc_entry_grid(c, 2 * size);
-  const int nq = 2 * (int)rd.num_terms;
-  Fr* partials = g == 1 ? out_host : c.arena.alloc_n<Fr>(g * nq);
-  const ScFinish fin = c.finish_for((uint32_t)g, out_host, seq, bind ? 64.0 * (double)size * rd.num_terms : 0.0);
+  RoundLaunch rl(c, out_host);
+  const size_t g = sc_entry_grid(c, 2 * size);
+  rl.hand_off(g, 2 * rd.num_terms, bind ? 64.0 * (double)size * rd.num_terms : 0.0);
   {
     // algorithmic bytes: 96 B per bound entry of the polys (192 B per pair and term) + the eq-level entry
     ProfScope ps(c, bind ? "sc_round_open<bind>" : "sc_round_open<first>", ((bind ? 192.0 : 64.0) + 32.0) * (double)size * rd.num_terms,
                  (bind ? 4.0 : 2.0) * (double)size * rd.num_terms, (double)size);
-    switch (rd.num_terms) {
-      case 1: launch_open<1>(c, rd, bind, size, (unsigned)g, partials, fin); break;
-      case 2: launch_open<2>(c, rd, bind, size, (unsigned)g, partials, fin); break;
-      case 3: launch_open<3>(c, rd, bind, size, (unsigned)g, partials, fin); break;
-      case 4: launch_open<4>(c, rd, bind, size, (unsigned)g, partials, fin); break;
-      case 5: launch_open<5>(c, rd, bind, size, (unsigned)g, partials, fin); break;
-      default: launch_open<6>(c, rd, bind, size, (unsigned)g, partials, fin); break;
-    }
+    dispatch_int<1, SC_OPEN_MAX_TERMS>((int)rd.num_terms, [&](auto M) {
+      dispatch_bool(bind, [&](auto B) {
+        hipLaunchKernelGGL((sc_round_open_kernel<M(), B()>), dim3((unsigned)g), dim3(256), 0, c.stream, rd, size, rl.partials, rl.fin);
+      });
+    });
   }
-  c.wait_round(seq);
+  rl.wait();
 }
 
 // ------------------------------------------------------------------ grand-product layer over (A, A + 1) tree pairs
@@ -917,51 +820,30 @@ __global__ __launch_bounds__(256) void sc_round_rw_kernel(ScRwRound rd, size_t s
     fin_put(fin, partials, (size_t)blockIdx.x * 2, q1);
     fin_put(fin, partials, (size_t)blockIdx.x * 2 + 1, q2);
   }
-  if (gridDim.x == 1) {
-    if (threadIdx.x == 0) publish_round(fin, 2);
-    return;
-  }
   finish_round<2>(fin, partials, lds);
-}
-
-template <int P>
-static void launch_rw(Ctx& c, const ScRwRound& rd, bool bind, bool fold, size_t size, unsigned g, Fr* partials, const ScFinish& fin) {
-  if (bind && fold)
-    hipLaunchKernelGGL((sc_round_rw_kernel<P, true, true>), dim3(g), dim3(256), 0, c.stream, rd, size, partials, fin);
-  else if (bind)
-    hipLaunchKernelGGL((sc_round_rw_kernel<P, true, false>), dim3(g), dim3(256), 0, c.stream, rd, size, partials, fin);
-  else
-    hipLaunchKernelGGL((sc_round_rw_kernel<P, false, false>), dim3(g), dim3(256), 0, c.stream, rd, size, partials, fin);
 }
 
 void k_sc_round_rw(Ctx& c, const ScRwRound& rd, bool bind, size_t size, Fr* out_host, bool fold) {
   LH_REQUIRE(!fold || bind, LH_ERR_ARG, "sc_round_rw: folding is part of a binding round");
   LH_REQUIRE(rd.num_pairs >= 1 && rd.num_pairs <= (uint32_t)SC_RW_MAX_PAIRS && size >= 1 && rd.eq_level, LH_ERR_ARG,
              "sc_round_rw: bad shape");
-  const uint32_t seq = c.next_seq();
-  ArenaScope scope(c.arena);
-  out_host = c.round_out(out_host);
-  size_t g = sc_entry_grid(c, 2 * size);
-  Fr* partials = g == 1 ? out_host : c.arena.alloc_n<Fr>(g * 2);
-  const ScFinish fin = c.finish_for((uint32_t)g, out_host, seq, bind ? 64.0 * (double)size * 2.0 * rd.num_pairs : 0.0);
+  RoundLaunch rl(c, out_host);
+  const size_t g = sc_entry_grid(c, 2 * size);
+  rl.hand_off(g, 2, bind ? 64.0 * (double)size * 2.0 * rd.num_pairs : 0.0);
   {
     // algorithmic bytes: 96 B per bound entry of the 2 P tables read (192 B per pair and table) + the eq-level entry;
     // products per pair: 4 per tree pair (+ 4 binds), 2 for the eq factor
     const double P = (double)rd.num_pairs;
     ProfScope ps(c, bind ? "sc_round_rw<bind>" : "sc_round_rw<first>", ((bind ? 192.0 : 64.0) * 2.0 * P + 32.0) * (double)size,
                  ((bind ? 8.0 : 4.0) * P + 2.0) * (double)size, (double)size);
-    switch (rd.num_pairs) {
-      case 1: launch_rw<1>(c, rd, bind, fold, size, (unsigned)g, partials, fin); break;
-      case 2: launch_rw<2>(c, rd, bind, fold, size, (unsigned)g, partials, fin); break;
-      case 3: launch_rw<3>(c, rd, bind, fold, size, (unsigned)g, partials, fin); break;
-      case 4: launch_rw<4>(c, rd, bind, fold, size, (unsigned)g, partials, fin); break;
-      case 5: launch_rw<5>(c, rd, bind, fold, size, (unsigned)g, partials, fin); break;
-      case 6: launch_rw<6>(c, rd, bind, fold, size, (unsigned)g, partials, fin); break;
-      case 7: launch_rw<7>(c, rd, bind, fold, size, (unsigned)g, partials, fin); break;
-      default: launch_rw<8>(c, rd, bind, fold, size, (unsigned)g, partials, fin); break;
-    }
+    const dim3 grid((unsigned)g), block(256);
+    dispatch_int<1, SC_RW_MAX_PAIRS>((int)rd.num_pairs, [&](auto P) {  // (three of the four (BIND, FOLD) forms exist)
+      if (bind && fold) hipLaunchKernelGGL((sc_round_rw_kernel<P(), true, true>), grid, block, 0, c.stream, rd, size, rl.partials, rl.fin);
+      else if (bind) hipLaunchKernelGGL((sc_round_rw_kernel<P(), true, false>), grid, block, 0, c.stream, rd, size, rl.partials, rl.fin);
+      else hipLaunchKernelGGL((sc_round_rw_kernel<P(), false, false>), grid, block, 0, c.stream, rd, size, rl.partials, rl.fin);
+    });
   }
-  c.wait_round(seq);
+  rl.wait();
 }
 
 bool k_sc_round(Ctx& c, const ScRound& rd, int degree, bool bind, size_t size, Fr* evals_host) {
@@ -987,14 +869,9 @@ bool k_sc_round(Ctx& c, const ScRound& rd, int degree, bool bind, size_t size, F
   // algorithmic bytes: fused round = bind bytes only, 96 B per bound entry = 192 B per pair
   // and table; the unfused first round reads 64 B per pair and table.
   const double bytes = (bind ? 192.0 : 64.0) * (double)size * (double)tabs + (rd.eq_level ? 32.0 * (double)size : 0.0);
-  const uint32_t seq = c.next_seq();
-  ArenaScope scope(c.arena);
-  // sharded rounds (sumcheck.cpp): the D sums stay on the device (all-gather and sum-and-publish follow on the stream)
-  evals_host = c.round_out(evals_host);
-  // (bytes a binding round stores: half of what it moves)
-  auto finish = [&](size_t grid, bool streams = false) {
-    return c.finish_for((uint32_t)grid, evals_host, seq, streams && bind ? bytes / 3.0 : 0.0);
-  };
+  // (sharded rounds, sumcheck.cpp: the D sums stay on the device - all-gather and sum-and-publish follow on the stream)
+  RoundLaunch rl(c, evals_host);
+  const double stored = bind ? bytes / 3.0 : 0.0;  // (bytes a streaming binding round stores: half of what it moves)
 
   // pairs per workgroup of the LDS-staged kernel
   uint32_t P = (uint32_t)std::min<size_t>(size, 64);
@@ -1017,23 +894,21 @@ bool k_sc_round(Ctx& c, const ScRound& rd, int degree, bool bind, size_t size, F
       }
     g.P = P;
     g.vals_entries = std::max<uint32_t>(g.num_used * P * 2, 8);
-    size_t grid = (size + P - 1) / P;
-    Fr* partials = grid == 1 ? evals_host : c.arena.alloc_n<Fr>(grid * degree);
-    const ScFinish kflag = finish(grid);
+    const size_t grid = (size + P - 1) / P;
+    rl.hand_off(grid, degree);
     {
       char name[40];
       snprintf(name, sizeof name, "sc_round<%d,%s>/lds", degree, bind ? "bind" : "first");
       ProfScope ps(c, name, bytes, muls_pair * (double)size, (double)size);
-      switch (degree) {
-        case 1: launch_lds<1>(c, g, bind, size, (unsigned)grid, partials, kflag); break;
-        case 2: launch_lds<2>(c, g, bind, size, (unsigned)grid, partials, kflag); break;
-        case 3: launch_lds<3>(c, g, bind, size, (unsigned)grid, partials, kflag); break;
-        case 4: launch_lds<4>(c, g, bind, size, (unsigned)grid, partials, kflag); break;
-        case 5: launch_lds<5>(c, g, bind, size, (unsigned)grid, partials, kflag); break;
-        default: launch_lds<6>(c, g, bind, size, (unsigned)grid, partials, kflag); break;
-      }
+      dispatch_int<1, 6>(degree, [&](auto D) {
+        const size_t red_entries = std::max<size_t>((size_t)rd.num_terms * D() * g.P, (size_t)rd.num_terms * D());
+        const size_t lds = ((size_t)g.vals_entries + red_entries) * sizeof(Fr);
+        dispatch_bool(bind, [&](auto B) {
+          hipLaunchKernelGGL((sc_round_lds_kernel<D(), B()>), dim3((unsigned)grid), dim3(256), lds, c.stream, g, size, rl.partials, rl.fin);
+        });
+      });
     }
-    c.wait_round(seq);
+    rl.wait();
     return false;
   }
 
@@ -1042,43 +917,36 @@ bool k_sc_round(Ctx& c, const ScRound& rd, int degree, bool bind, size_t size, F
   const uint32_t tp = (rd.num_terms > 1 && size * rd.num_terms <= ((size_t)1 << 17)) ? rd.num_terms : 1u;
   if (degree == 2 && rd.eq_level && tp == 1) {
     // the factored degree-2 rounds (GKR layers, Surge over one table): one lane per bound entry
-    size_t g2 = sc_entry_grid(c, 2 * size);
-    Fr* partials = g2 == 1 ? evals_host : c.arena.alloc_n<Fr>(g2 * 2);
-    const ScFinish kflag = finish(g2, true);
+    const dim3 g2((unsigned)sc_entry_grid(c, 2 * size)), block(256);
+    rl.hand_off(g2.x, 2, stored);
     if (rd.pp) {
       // products per pair: binds, one per coefficient still applied on the way, ~0.62 per term for the shared reductions
       // (two points), the eq entry
       const double mp = (bind ? 2.0 * nfac : 0.0) + ncoef + 2.0 * 0.62 * rd.num_terms + 2.0;
       ProfScope ps(c, bind ? "sc_round_pp<bind>" : "sc_round_pp<first>", bytes, mp * (double)size, (double)size);
-      if (bind) hipLaunchKernelGGL((sc_round_pp_kernel<true>), dim3((unsigned)g2), dim3(256), 0, c.stream, a, size, partials, kflag);
-      else hipLaunchKernelGGL((sc_round_pp_kernel<false>), dim3((unsigned)g2), dim3(256), 0, c.stream, a, size, partials, kflag);
+      dispatch_bool(bind, [&](auto B) { hipLaunchKernelGGL((sc_round_pp_kernel<B()>), g2, block, 0, c.stream, a, size, rl.partials, rl.fin); });
     } else {
       ProfScope ps(c, bind ? "sc_round<2,bind>" : "sc_round<2,first>", bytes, muls_pair * (double)size, (double)size);
-      if (bind) hipLaunchKernelGGL((sc_round_e2_kernel<true>), dim3((unsigned)g2), dim3(256), 0, c.stream, a, size, partials, kflag);
-      else hipLaunchKernelGGL((sc_round_e2_kernel<false>), dim3((unsigned)g2), dim3(256), 0, c.stream, a, size, partials, kflag);
+      dispatch_bool(bind, [&](auto B) { hipLaunchKernelGGL((sc_round_e2_kernel<B()>), g2, block, 0, c.stream, a, size, rl.partials, rl.fin); });
     }
-    c.wait_round(seq);
+    rl.wait();
     return rd.pp == 2 && bind;  // (the product-pair kernel ran a folding round)
   }
   size_t g = (size * tp + 255) / 256;
   size_t cap = (size_t)c.num_cus * 4;
   if (g > cap) g = cap;
-  Fr* partials = g == 1 ? evals_host : c.arena.alloc_n<Fr>(g * degree);
-  const ScFinish kflag = finish(g, true);
+  rl.hand_off(g, degree, stored);
   {
     char name[40];
     snprintf(name, sizeof name, "sc_round<%d,%s>%s", degree, bind ? "bind" : "first", tp > 1 ? "/tp" : "");
     ProfScope ps(c, name, bytes, muls_pair * (double)size, (double)size);
-    switch (degree) {
-      case 1: launch_round<1>(c, a, bind, size, tp, (unsigned)g, partials, kflag); break;
-      case 2: launch_round<2>(c, a, bind, size, tp, (unsigned)g, partials, kflag); break;
-      case 3: launch_round<3>(c, a, bind, size, tp, (unsigned)g, partials, kflag); break;
-      case 4: launch_round<4>(c, a, bind, size, tp, (unsigned)g, partials, kflag); break;
-      case 5: launch_round<5>(c, a, bind, size, tp, (unsigned)g, partials, kflag); break;
-      default: launch_round<6>(c, a, bind, size, tp, (unsigned)g, partials, kflag); break;
-    }
+    dispatch_int<1, 6>(degree, [&](auto D) {
+      dispatch_bool(bind, [&](auto B) {
+        hipLaunchKernelGGL((sc_round_kernel<D(), B()>), dim3((unsigned)g), dim3(256), 0, c.stream, a, size, tp, rl.partials, rl.fin);
+      });
+    });
   }
-  c.wait_round(seq);
+  rl.wait();
   return false;
 }
 

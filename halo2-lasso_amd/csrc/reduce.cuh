@@ -35,4 +35,11 @@ __device__ __forceinline__ Fp<P> block_reduce_sum(Fp<P> v, Fp<P>* lds) {
   return v;
 }
 
+// masked block reductions: even lanes' sum, then odd lanes' sum (the round kernels that give a lane one bound entry)
+template <class P>
+__device__ __forceinline__ void reduce_by_parity(const Fp<P>& acc, bool odd, Fp<P>* lds, Fp<P>& even_sum, Fp<P>& odd_sum) {
+  even_sum = block_reduce_sum(odd ? Fp<P>::zero() : acc, lds);
+  odd_sum = block_reduce_sum(odd ? acc : Fp<P>::zero(), lds);
+}
+
 }  // namespace lh

@@ -54,7 +54,7 @@ def test_sum_check_lagrange(hl, ctx, num_vars):
     run(hl, ctx, num_vars, o_expr, g_expr, tables, [rng.randrange(P)], [rng.randrange(P) for _ in range(num_vars)])
 
 
-@pytest.mark.parametrize("num_vars", [2, 3, 5, 8])
+@pytest.mark.parametrize("num_vars", [2, 3, 5, 8, 9])  # (9: 256 pairs in round 0 - more than one workgroup in every form)
 def test_sum_check_rotation(hl, ctx, num_vars):
     """sum_check.rs:248-301: poly_k queried at rotation (n-1-k) equals poly_{k+1} at rotation (n-2-k)"""
     rng = random.Random(100 + num_vars)
@@ -173,3 +173,17 @@ def test_eq_factored_expression_rounds_match_the_oracle(env):
                                 "and not eq_factored and not sharded"],
                          cwd=root, env=dict(os.environ, **env), capture_output=True, text=True, timeout=1500)
     assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-2000:]
+
+
+def test_expression_rounds_under_the_ticket_finish():
+    """LH_FIN_LANES_MIN_BYTES=-1 (read once per process): no launch hands its partial sums over in lanes, so the round
+    kernels of general expressions go through the fenced ticket of csrc/round.cuh.  The rotation tests - 2^9 rows give
+    round 0 several workgroups - again in one child process per form of the round kernel: the interpreted register
+    program, the expanded monomials, the runtime-compiled program; byte for byte the oracle's messages in each."""
+    import os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for form in ({}, {"LH_EXPR_MONOMIALS": "1"}, {"LH_EXPR_JIT_MIN_VARS": "1"}):
+        res = subprocess.run([sys.executable, "-m", "pytest", "tests/test_gpu_expression.py", "-m", "gpu", "-x", "-q",
+                              "-k", "test_sum_check_rotation"], cwd=root,
+                             env=dict(os.environ, LH_FIN_LANES_MIN_BYTES="-1", **form), capture_output=True, text=True, timeout=300)
+        assert res.returncode == 0 and "5 passed" in res.stdout, (form, res.stdout[-3000:] + res.stderr[-2000:])

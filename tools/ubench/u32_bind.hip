@@ -138,7 +138,7 @@ __global__ __launch_bounds__(256) void bind2(const uint32_t* __restrict__ col, c
     __syncthreads();
     if (!is_last) return;
     __threadfence();
-  } else {  // MODE 6: kernels_sumcheck.hip finish_round - release by every producer, acquire by the one consumer
+  } else {  // MODE 6: csrc/round.cuh finish_round - release by every producer, acquire by the one consumer
     if (threadIdx.x == 0) {
       partials[blockIdx.x] = acc;
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
