@@ -29,6 +29,7 @@ pub const LH_RCCL_UNIQUE_ID_BYTES: usize = 128;
 #[repr(C)] pub struct lh_usrs { _p: [u8; 0] }
 #[repr(C)] pub struct lh_mkzg_vp { _p: [u8; 0] }
 #[repr(C)] pub struct lh_spark_poly { _p: [u8; 0] }  // a committed sparse polynomial (lh_spark_commit)
+#[repr(C)] pub struct lh_r1cs_key { _p: [u8; 0] }  // the key of an R1CS instance (lh_r1cs_commit)
 #[repr(C)] pub struct lh_zm_vp { _p: [u8; 0] }
 
 pub type FeCb = unsafe extern "C" fn(*mut c_void, *const Fr) -> c_int;
@@ -84,6 +85,11 @@ pub struct lh_logup_columns {
 pub const LH_MEMCHECK_MAX_INIT_VARS: usize = 24;
 pub const LH_SPARK_MAX_DIMS: usize = 3;
 pub const LH_SPARK_MAX_DIM_VARS: usize = 24;
+pub const LH_SPARTAN_MIN_DIM_VARS: usize = 2;
+pub const LH_SPARTAN_MAX_DIM_VARS: usize = 24;
+// one matrix of lh_r1cs_commit: three device columns of 2^num_vars entries (row, col: uint32_t; val: field elements)
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct lh_r1cs_matrix { pub d_row: *const u32, pub d_col: *const u32, pub d_val: *const Fr }
 // the trace of lh_memcheck_prove: three device columns of 2^num_vars uint32_t (cell, value before, value after)
 #[repr(C)] #[derive(Clone, Copy)]
 pub struct lh_memcheck_trace { pub d_addr: *const u32, pub d_rv: *const u32, pub d_wv: *const u32 }
@@ -339,6 +345,21 @@ extern "C" {
     // (development) the memory kernel of an opening on its own: d_E[j][k] = eq(r_j, d_dims[j][k]) and the value
     pub fn lh_debug_spark_e(ctx: *mut lh_ctx, num_vars: usize, dim_vars: usize, num_dims: usize, d_dims: *const *const u32,
                             d_val: *const Fr, point: *const Fr, d_E: *const *mut Fr, out_value: *mut Fr) -> lh_status;
+    // Spartan (tests/spartan_ref.py): the key of an R1CS instance once - m: three matrices A, B, C -, then any number of proofs
+    // of assignments z = (d_w, x, 0); the key owns its device memory
+    pub fn lh_r1cs_commit(ctx: *mut lh_ctx, srs: *const lh_srs, num_vars: usize, dim_vars: usize, m: *const lh_r1cs_matrix,
+                          out: *mut *mut lh_r1cs_key) -> lh_status;
+    // out null: the length alone; else *len is the room in and the length out
+    pub fn lh_r1cs_commitment(key: *const lh_r1cs_key, out: *mut u8, len: *mut usize) -> lh_status;
+    // d_w: 2^(dim_vars - 1) device elements; x: num_public host elements; the proof is appended to t
+    pub fn lh_spartan_prove(ctx: *mut lh_ctx, srs: *const lh_srs, key: *const lh_r1cs_key, d_w: *const Fr, x: *const Fr,
+                            num_public: usize, t: *mut lh_transcript) -> lh_status;
+    pub fn lh_r1cs_free(ctx: *mut lh_ctx, key: *mut lh_r1cs_key);
+    pub fn lh_spartan_verify(vp: *const lh_mkzg_vp, num_vars: usize, dim_vars: usize, commitment: *const u8,
+                             commitment_len: usize, x: *const Fr, num_public: usize, t: *mut lh_transcript) -> lh_status;
+    // (development) the keyed field sum alone: direction 0 by rows, 1 by columns; d_out: three device tables of 2^dim_vars
+    pub fn lh_debug_spartan_spmv(ctx: *mut lh_ctx, key: *const lh_r1cs_key, direction: c_int, d_x: *const Fr,
+                                 d_out: *const *mut Fr) -> lh_status;
     // the host verifier of lh_gkr_fractional_prove; the roots p_0s / q_0s come back with the final claims and the point
     pub fn lh_gkr_fractional_verify(num_batching: usize, num_vars: usize, claimed_p_0s: *const *const Fr,
                                     claimed_q_0s: *const *const Fr, t: *mut lh_transcript, out_p_0s: *mut Fr,

@@ -1879,6 +1879,137 @@ def spark_e(ctx, dims, val, dim_vars, point, num_vars=None):
     return E, _fr_list(out, 1)[0]
 
 
+# ------------------------------------------------------------------ Spartan: R1CS over the Spark-committed matrices (lh_r1cs_commit)
+def _spartan_shape(num_vars, dim_vars, num_public):
+    """ArgumentError before anything is marshalled or the device is touched"""
+    lo, hi = _ffi.LH_SPARTAN_MIN_DIM_VARS, _ffi.LH_SPARTAN_MAX_DIM_VARS
+    if not (isinstance(dim_vars, int) and lo <= dim_vars <= hi):
+        raise ArgumentError("spartan: dim_vars out of range (%d to %d)" % (lo, hi))
+    if not (isinstance(num_vars, int) and 1 <= num_vars < 31):
+        raise ArgumentError("spartan: num_vars out of range (1 to 30)")
+    if not (isinstance(num_public, int) and 1 <= num_public <= 1 << (dim_vars - 1)):
+        raise ArgumentError("spartan: num_public out of range (1 to 2^(dim_vars - 1))")
+
+
+def _raw_ptr(p):
+    return p.ptr if hasattr(p, "ptr") else p
+
+
+class R1csKey:
+    """The key of an R1CS instance (`lh_r1cs_key`): the Spark commitments of A, B, C and their entries sorted by row and by
+    column, on the device.  Prove any number of assignments with spartan_prove; free() (or `with`) gives the device memory
+    back - it also goes with the ctx.  `commitment`: the bytes spartan_verify takes."""
+
+    def __init__(self, ctx, h, num_vars, dim_vars):
+        self.ctx, self.h, self.num_vars, self.dim_vars = ctx, h, num_vars, dim_vars
+        n = C.c_size_t(0)
+        _check(ctx.lib.lh_r1cs_commitment(h, None, C.byref(n)))
+        out = (C.c_uint8 * n.value)()
+        _check(ctx.lib.lh_r1cs_commitment(h, out, C.byref(n)))
+        self.commitment = bytes(out[:n.value])
+
+    def free(self):
+        if self.h and self.ctx.h:  # (a ctx that is gone has taken its keys with it)
+            self.ctx.lib.lh_r1cs_free(self.ctx.h, self.h)
+        self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def r1cs_commit(ctx, srs, matrices, dim_vars, num_vars=None):
+    """The key of the R1CS instance A, B, C over multilinear KZG (tests/spartan_ref.py): `matrices` are three
+    (row, col, val) - row, col u32 columns (U32Column / DeviceBuffer, 2^num_vars indices below 2^dim_vars), val a
+    MultilinearPolynomial or DeviceBuffer of 2^num_vars Fr.  An index out of range: ArgumentError."""
+    matrices = [tuple(m) if m is not None else () for m in matrices] if matrices is not None else []
+    if len(matrices) != 3 or any(len(m) != 3 or any(col is None for col in m) for m in matrices):
+        raise ArgumentError("spartan: three matrices of (row, col, val)")
+    if num_vars is None:
+        if not hasattr(matrices[0][2], "num_vars"):
+            raise ArgumentError("spartan: num_vars is needed with raw device buffers")
+        num_vars = matrices[0][2].num_vars
+    _spartan_shape(num_vars, dim_vars, 1)
+    for m in matrices:
+        if any(getattr(col, "num_vars", num_vars) != num_vars for col in m):
+            raise ArgumentError("spartan: columns of 2^num_vars entries, the same for the three matrices")
+        for col, width in zip(m, (4, 4, 32)):
+            if getattr(getattr(col, "buf", col), "nbytes", width << num_vars) < width << num_vars:
+                raise ArgumentError("spartan: a column of 2^num_vars entries needs %d bytes" % (width << num_vars))
+    ms = (_ffi.lh_r1cs_matrix * 3)()
+    for i, (row, col, val) in enumerate(matrices):
+        ms[i].d_row = C.cast(C.c_void_p(_raw_ptr(row)), C.POINTER(C.c_uint32))
+        ms[i].d_col = C.cast(C.c_void_p(_raw_ptr(col)), C.POINTER(C.c_uint32))
+        ms[i].d_val = C.cast(C.c_void_p(_raw_ptr(val)), C.POINTER(lh_fr))
+    h = C.c_void_p()
+    _check(ctx.lib.lh_r1cs_commit(ctx.h, srs.h, num_vars, dim_vars, ms, C.byref(h)))
+    return R1csKey(ctx, h, num_vars, dim_vars)
+
+
+def spartan_prove(ctx, srs, key, w, x, transcript=None):
+    """Prove that z = (w, x, 0) satisfies the instance of `key`: `w` a MultilinearPolynomial or DeviceBuffer of
+    2^(dim_vars - 1) Fr, `x` the public inputs (ints, x[0] the constant 1 if the instance uses one) -> the proof bytes; with a
+    transcript given the proof is appended to it and None returned.  A witness that does not satisfy: ArgumentError."""
+    if not isinstance(key, R1csKey) or not key.h:
+        raise ArgumentError("spartan: the key has been freed")
+    if w is None or x is None:
+        raise ArgumentError("spartan: null argument: w or x")
+    x = list(x)
+    _spartan_shape(key.num_vars, key.dim_vars, len(x))
+    if getattr(w, "num_vars", key.dim_vars - 1) != key.dim_vars - 1:
+        raise ArgumentError("spartan: a witness of 2^(dim_vars - 1) entries")
+    if getattr(getattr(w, "buf", w), "nbytes", 32 << (key.dim_vars - 1)) < 32 << (key.dim_vars - 1):
+        raise ArgumentError("spartan: a witness of 2^(dim_vars - 1) entries needs %d bytes" % (32 << (key.dim_vars - 1)))
+    t = transcript if transcript is not None else Keccak256Transcript()
+    _check(ctx.lib.lh_spartan_prove(ctx.h, srs.h, key.h, C.cast(C.c_void_p(_raw_ptr(w)), C.POINTER(lh_fr)), _fr_array(x), len(x),
+                                    t.p))
+    return t.into_proof() if transcript is None else None
+
+
+def spartan_verify(vp, num_vars, dim_vars, commitment, x, proof):
+    """Verifier of spartan_prove (host only): `commitment` the bytes of R1csKey.commitment, `x` the public inputs, `proof`
+    bytes or a transcript.  A Keccak256Transcript must be fully consumed."""
+    if commitment is None or x is None or proof is None:
+        raise ArgumentError("spartan: null argument")
+    x = list(x)
+    _spartan_shape(num_vars, dim_vars, len(x))
+    t = Keccak256Transcript.from_proof(bytes(proof)) if isinstance(proof, (bytes, bytearray)) else proof
+    blob = (C.c_uint8 * max(len(commitment), 1)).from_buffer_copy(bytes(commitment) or b"\0")
+    _check(vp.lib.lh_spartan_verify(vp.h, num_vars, dim_vars, blob, len(commitment), _fr_array(x), len(x), t.p))
+    if isinstance(t, Keccak256Transcript) and t.remaining():
+        raise InvalidSnark("spartan: trailing bytes in proof")
+
+
+def spartan_spmv(ctx, key, direction, x):
+    """(development) the keyed field sum of spartan_prove alone (lh_debug_spartan_spmv) -> three lists of 2^dim_vars ints:
+    direction 0, M x for M = A, B, C (sums by row); direction 1, M^T x (sums by column).  `x`: 2^dim_vars ints.  The output
+    buffers are filled with non-zero bytes first: the kernel owes every cell."""
+    if not isinstance(key, R1csKey) or not key.h:
+        raise ArgumentError("spartan: the key has been freed")
+    if direction not in (0, 1):
+        raise ArgumentError("spartan: direction is 0 (by rows) or 1 (by columns)")
+    x = list(x)
+    if len(x) != 1 << key.dim_vars:
+        raise ArgumentError("spartan: a vector of 2^dim_vars entries")
+    size = 32 << key.dim_vars
+    d_x = ctx.upload(frs_to_bytes(x))
+    bufs = [ctx.upload(b"\xa5" * size) for _ in range(3)]
+    _check(ctx.lib.lh_debug_spartan_spmv(ctx.h, key.h, direction, C.cast(C.c_void_p(d_x.ptr), C.POINTER(lh_fr)),
+                                         C.cast(_ptr_array(bufs), C.POINTER(C.POINTER(lh_fr)))))
+    out = [frs_from_bytes(b.read()) for b in bufs]
+    for b in bufs + [d_x]:
+        b.free()
+    return out
+
+
 def verify_fractional_sum_check(num_vars, claimed_p_0s, claimed_q_0s, transcript):
     """fractional_sum_check.rs:193-270, the host verifier of prove_fractional_sum_check (a claim None: the root is read)
     -> (p_0s, q_0s, p_xs, q_xs, x): the roots come back because a caller checks a relation between them."""

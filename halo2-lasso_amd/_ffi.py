@@ -22,6 +22,7 @@ LH_LOGUP_MAX_LOOKUPS, LH_LOGUP_MAX_WIDTH, LH_LOGUP_MAX_TABLE_VARS = 8, 8, 24  # 
 LH_LOGUP_COL_FR, LH_LOGUP_COL_U32 = 0, 1  # lh_logup_columns.kinds
 LH_MEMCHECK_MAX_INIT_VARS = 24  # lh_memcheck_prove: mem_vars with an initial image
 LH_SPARK_MAX_DIMS, LH_SPARK_MAX_DIM_VARS = 3, 24  # lh_spark_commit
+LH_SPARTAN_MIN_DIM_VARS, LH_SPARTAN_MAX_DIM_VARS = 2, 24  # lh_r1cs_commit
 LH_BD_COLUMN_FR, LH_BD_COLUMN_U32 = 0, 1
 
 
@@ -64,6 +65,10 @@ class lh_logup_lookup(C.Structure):
 
 class lh_memcheck_trace(C.Structure):
     _fields_ = [("d_addr", C.POINTER(C.c_uint32)), ("d_rv", C.POINTER(C.c_uint32)), ("d_wv", C.POINTER(C.c_uint32))]
+
+
+class lh_r1cs_matrix(C.Structure):
+    _fields_ = [("d_row", C.POINTER(C.c_uint32)), ("d_col", C.POINTER(C.c_uint32)), ("d_val", C.POINTER(lh_fr))]
 
 
 class lh_logup_columns(C.Structure):
@@ -426,6 +431,13 @@ SIGNATURES["lh_spark_open"] = (C.c_int, [_P, _P, _P, C.POINTER(lh_fr), C.POINTER
 SIGNATURES["lh_spark_free"] = (None, [_P, _P])
 SIGNATURES["lh_spark_verify"] = (C.c_int, [_P, _SZ, _SZ, _SZ, _P, _SZ, C.POINTER(lh_fr), C.POINTER(lh_fr), _T])
 SIGNATURES["lh_debug_spark_e"] = (C.c_int, [_P, _SZ, _SZ, _SZ, _P, _P, C.POINTER(lh_fr), _P, C.POINTER(lh_fr)])
+# Spartan: the key is an opaque pointer; lh_r1cs_free returns nothing
+SIGNATURES["lh_r1cs_commit"] = (C.c_int, [_P, _P, _SZ, _SZ, C.POINTER(lh_r1cs_matrix), C.POINTER(_P)])
+SIGNATURES["lh_r1cs_commitment"] = (C.c_int, [_P, _P, C.POINTER(_SZ)])
+SIGNATURES["lh_spartan_prove"] = (C.c_int, [_P, _P, _P, C.POINTER(lh_fr), C.POINTER(lh_fr), _SZ, _T])
+SIGNATURES["lh_r1cs_free"] = (None, [_P, _P])
+SIGNATURES["lh_spartan_verify"] = (C.c_int, [_P, _SZ, _SZ, _P, _SZ, C.POINTER(lh_fr), _SZ, _T])
+SIGNATURES["lh_debug_spartan_spmv"] = (C.c_int, [_P, _P, C.c_int, C.POINTER(lh_fr), C.POINTER(C.POINTER(lh_fr))])
 SIGNATURES["lh_gkr_fractional_verify"] = (C.c_int, [_SZ, _SZ, C.POINTER(C.POINTER(lh_fr)), C.POINTER(C.POINTER(lh_fr)), _T,
                                                     C.POINTER(lh_fr), C.POINTER(lh_fr), C.POINTER(lh_fr), C.POINTER(lh_fr),
                                                     C.POINTER(lh_fr)])

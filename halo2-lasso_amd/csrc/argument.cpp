@@ -99,4 +99,18 @@ void argument_verdict(const std::string& name, const std::function<void()>& veri
   }
 }
 
+std::vector<HG1> argument_read_commitment_blob(const std::string& name, const uint8_t* blob, size_t len, size_t count) {
+  KeccakTranscript kt;
+  kt.stream.assign(blob, blob + len);
+  Transcript tr(&kt.vt);
+  std::vector<HG1> comms;
+  try {
+    comms = lasso_read_commitments(tr, count);
+  } catch (const Error& e) {
+    throw Error(LH_ERR_INVALID_SNARK, name + ": malformed commitment: " + e.msg);
+  }
+  if (kt.pos != kt.stream.size()) throw Error(LH_ERR_INVALID_SNARK, name + ": malformed commitment: wrong length");
+  return comms;
+}
+
 }  // namespace lh

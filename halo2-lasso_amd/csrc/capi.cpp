@@ -242,6 +242,7 @@ void lh_ctx_destroy(lh_ctx* ctx) {
     open_precommit_cancel(ctx->c);
   } catch (...) {
   }
+  spartan_free_all(ctx->c);  // (R1CS keys nobody freed: before the polynomials they own)
   spark_free_all(ctx->c);  // (committed sparse polynomials nobody freed: their device memory goes with the ctx)
   if (ctx->c.helper_handle) {
     lh_ctx_destroy(ctx->c.helper_handle);
@@ -758,6 +759,47 @@ void lh_spark_free(lh_ctx* ctx, lh_spark_poly* poly) {
   (void)hipSetDevice(ctx->c.device);
   spark_free(ctx->c, (SparkPoly*)poly);
 }
+// ---------------------------------------------------------------- Spartan: R1CS over the Spark-committed matrices
+lh_status lh_r1cs_commit(lh_ctx* ctx, const lh_srs* srs, size_t num_vars, size_t dim_vars, const lh_r1cs_matrix m[3],
+                         lh_r1cs_key** out) {
+  LH_TRY
+  spartan_check(num_vars, dim_vars, 1);  // (the shape first: refused before the param or the device is touched)
+  NEED_CTX(ctx);
+  NEED(srs);
+  NEED(m);
+  NEED(out);
+  *out = nullptr;
+  *out = (lh_r1cs_key*)spartan_commit(ctx->c, mkzg_pcs(ctx->c, srs->s), num_vars, dim_vars, m);
+  LH_CATCH
+}
+lh_status lh_r1cs_commitment(const lh_r1cs_key* key, uint8_t* out, size_t* len) {
+  LH_TRY
+  NEED(key);
+  NEED(len);
+  const std::vector<uint8_t>& blob = ((const R1csKey*)key)->blob;
+  if (out) {
+    LH_REQUIRE(*len >= blob.size(), LH_ERR_ARG, "spartan: the buffer is shorter than the key");
+    memcpy(out, blob.data(), blob.size());
+  }
+  *len = blob.size();
+  LH_CATCH
+}
+lh_status lh_spartan_prove(lh_ctx* ctx, const lh_srs* srs, const lh_r1cs_key* key, const lh_fr* d_w, const lh_fr* x,
+                           size_t num_public, lh_transcript* t) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(srs);
+  NEED(key);
+  NEED(d_w);
+  NEED(x);
+  Transcript tr(t);
+  spartan_prove(ctx->c, mkzg_pcs(ctx->c, srs->s), *(const R1csKey*)key, (const Fr*)d_w, (const HFr*)x, num_public, tr);
+  LH_CATCH
+}
+void lh_r1cs_free(lh_ctx* ctx, lh_r1cs_key* key) {
+  if (!ctx || !key) return;
+  (void)hipSetDevice(ctx->c.device);
+  spartan_free(ctx->c, (R1csKey*)key);
+}
 lh_status lh_lasso_last_timing(lh_ctx* ctx, double* out_ms) {
   LH_TRY NEED_CTX(ctx);
   NEED(out_ms);
@@ -1107,6 +1149,18 @@ lh_status lh_spark_verify(const lh_mkzg_vp* vp, size_t num_vars, size_t dim_vars
   HFr v;
   memcpy(&v, value, 32);
   spark_verify(mkzg_verifier(*vp->p), num_vars, dim_vars, num_dims, commitment, commitment_len, (const HFr*)point, v, tr);
+  LH_CATCH
+}
+lh_status lh_spartan_verify(const lh_mkzg_vp* vp, size_t num_vars, size_t dim_vars, const uint8_t* commitment, size_t commitment_len,
+                            const lh_fr* x, size_t num_public, lh_transcript* t) {
+  LH_TRY
+  NEED(vp);
+  NEED(commitment);
+  NEED(x);
+  Transcript tr(t);
+  if (spartan_check(num_vars, dim_vars, num_public) > mkzg_vp_num_vars(*vp->p))
+    throw lh::Error(LH_ERR_INVALID_PCS_PARAM, "Too many variates of poly to verify");
+  spartan_verify(mkzg_verifier(*vp->p), num_vars, dim_vars, commitment, commitment_len, (const HFr*)x, num_public, tr);
   LH_CATCH
 }
 lh_status lh_hyperplonk_verify(const lh_mkzg_vp* vp, const lh_hp_vparam* hvp, const lh_fr* const* instances,
@@ -2279,6 +2333,12 @@ lh_status lh_debug_spark_e(lh_ctx* ctx, size_t num_vars, size_t dim_vars, size_t
   NEED(out_value);
   const HFr v = spark_debug_e(ctx->c, num_vars, dim_vars, num_dims, d_dims, (const Fr*)d_val, (const HFr*)point, (Fr* const*)d_E);
   memcpy(out_value, &v, 32);
+  LH_CATCH
+}
+lh_status lh_debug_spartan_spmv(lh_ctx* ctx, const lh_r1cs_key* key, int direction, const lh_fr* d_x, lh_fr* const d_out[3]) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(key);
+  spartan_debug_spmv(ctx->c, *(const R1csKey*)key, direction, (const Fr*)d_x, (Fr* const*)d_out);
   LH_CATCH
 }
 lh_status lh_debug_sort_plan(size_t n, unsigned bits, int key_bytes, unsigned* passes, unsigned rb[8], size_t* temp_bytes) {

@@ -287,6 +287,9 @@ struct Ctx {
   hipEvent_t prof_ev[2] = {nullptr, nullptr};
   // committed sparse polynomials (spark.cpp SparkPoly): device memory outside the arena, freed by lh_spark_free or with the ctx
   std::vector<struct SparkPoly*> spark_polys;
+  // R1CS keys (spartan.cpp R1csKey): each owns three of the polynomials above and one device block of its own; freed by
+  // lh_r1cs_free or with the ctx, before the polynomials
+  std::vector<struct R1csKey*> r1cs_keys;
   void* pin(size_t bytes);  // grows the pinned buffer if needed
   // small device -> host download through a second pinned staging buffer, synchronising: an async copy into
   // pageable memory makes the runtime pin pages on the fly (hundreds of microseconds for a few KB)
@@ -926,6 +929,29 @@ struct SparkLeaves {
 };
 void k_spark_leaves(Ctx&, const SparkLeaves&, size_t num_dims, size_t n, size_t dim_vars, bool up_n, bool up_l, const Fr& gamma,
                     const Fr& gamma2, const Fr& tau);
+
+// ------------------------------------------------------------------ Spartan (kernels_spartan.hip; spartan.cpp, tests/spartan_ref.py)
+// The keyed field sum of the three matrices in ONE launch set (the matrix in blockIdx.y):
+//   out[m][s] = sum_{k: seg[m][k] = s} val[m][perm[m][k]] X[other[m][k]]      s < 2^dim_vars
+// over the entry stream SORTED by seg (the R1CS key holds it: seg ascending, other and perm permuted along; perm[k] is the
+// entry's position in the caller's order, where its value lives).  Entry-parallel: per-lane products, a segmented
+// reduction by key over wave shuffles, the open ends of the 64-entry wave rows folded through LDS by one wave per tile, the
+// open ends of the tiles by a short second kernel - a segment may span every tile; the cost follows n, not the longest
+// segment.  Indices are masked to dim_vars bits and perm to n: nothing is read or written out of bounds whatever the
+// columns hold.  out is zeroed first: segments without entries are zero.  carry_k / carry_v: the launcher's (arena).
+// Launch record "spartan_spmv", 3 n items and products, algorithmic bytes 3 (76 n + 32 * 2^dim_vars)
+constexpr int SPMV_TILE = 2048;  // entries per workgroup: THE tile (at most 4096: tests/test_gpu_spartan_spmv.py rests on that)
+struct SpartanSpmv {
+  const uint32_t *seg[3], *other[3], *perm[3];
+  const Fr* val[3];
+  const Fr* X;
+  Fr* out[3];
+  uint32_t* carry_k;
+  Fr* carry_v;
+};
+void k_spartan_spmv(Ctx&, const SpartanSpmv&, size_t n, size_t dim_vars);
+// the number of rows i < rows with az[i] bz[i] != cz[i]; synchronises.  Launch record "spartan_unsatisfied"
+size_t k_spartan_unsatisfied(Ctx&, const Fr* az, const Fr* bz, const Fr* cz, size_t rows);
 
 void k_lookup_h(Ctx&, const Fr* input, const Fr* table, const Fr* m, const Fr& gamma, size_t n, Fr* h);
 void k_permutation_z(Ctx&, const Fr* const* values, const Fr* const* perms, size_t num_perm, size_t num_chunks,

@@ -626,6 +626,9 @@ HFr host_table_eval(size_t l, const std::vector<HFr>& x, const std::function<HFr
 // own words behind "<name>: ".  What is wrong with the call, not with the proof, keeps its code (LH_ERR_ARG,
 // LH_ERR_INVALID_PCS_PARAM).
 void argument_verdict(const std::string& name, const std::function<void()>& verify);
+// A commitment blob - a transcript's stream of its own: the mask element, then the non-identity points, nothing else - read
+// back as `count` commitments; malformed: LH_ERR_INVALID_SNARK "<name>: malformed commitment: ..."
+std::vector<HG1> argument_read_commitment_blob(const std::string& name, const uint8_t* blob, size_t len, size_t count);
 
 // ------------------------------------------------------------------ Lasso
 // pieces of the argument shared by the standalone prover (lasso.cpp) and HyperPlonk's Lasso lookups (hyperplonk.cpp)
@@ -904,6 +907,31 @@ void spark_verify(const PcsVerifier& pcs, size_t num_vars, size_t dim_vars, size
 // the memory kernel alone (lh_debug_spark_e)
 HFr spark_debug_e(Ctx&, size_t num_vars, size_t dim_vars, size_t num_dims, const uint32_t* const* d_dims, const Fr* d_val,
                   const HFr* point, Fr* const* d_E);
+
+// ------------------------------------------------------------------ Spartan (spartan.cpp; tests/spartan_ref.py)
+// The key of an R1CS instance: the Spark commitments of A, B, C (ordinary polynomials of this ctx: spark_open takes them) and,
+// per matrix and direction (0: by rows, 1: by columns), the entry stream sorted by that index - the sorted keys, the other
+// index permuted along, the position of every entry's value - in ONE device block outside the arena (18 * 2^n words): a
+// prove runs no sort.  Listed in Ctx::r1cs_keys until spartan_free or the ctx's end.
+struct R1csKey {
+  Ctx* ctx = nullptr;
+  size_t n = 0, l = 0;
+  SparkPoly* mat[3] = {};
+  void* block = nullptr;
+  const uint32_t *seg[2][3] = {}, *other[2][3] = {}, *perm[2][3] = {};
+  std::vector<uint8_t> blob;  // the three commitment blobs one after the other
+};
+// the limits that need no device (shared with the verifier): returns max(num_vars, dim_vars)
+size_t spartan_check(size_t num_vars, size_t dim_vars, size_t num_public);
+R1csKey* spartan_commit(Ctx&, const Pcs&, size_t num_vars, size_t dim_vars, const lh_r1cs_matrix* m);
+void spartan_free(Ctx&, R1csKey*);  // (not one of this ctx's: nothing happens)
+void spartan_free_all(Ctx&);
+// d_w: 2^(dim_vars - 1) device field elements; x: num_public host ones; appends the proof
+void spartan_prove(Ctx&, const Pcs&, const R1csKey&, const Fr* d_w, const HFr* x, size_t num_public, Transcript& tr);
+void spartan_verify(const PcsVerifier& pcs, size_t num_vars, size_t dim_vars, const uint8_t* key, size_t key_len, const HFr* x,
+                    size_t num_public, Transcript& tr);
+// the keyed-sum kernel alone (lh_debug_spartan_spmv): direction 0, d_out[m] = M_m d_x; 1, d_out[m] = M_m^T d_x
+void spartan_debug_spmv(Ctx&, const R1csKey&, int direction, const Fr* d_x, Fr* const* d_out);
 
 // ------------------------------------------------------------------ verifiers (verifier.cpp; host only)
 HFr identity_eval(const std::vector<HFr>& x);  // sum_i 2^i x_i (sum_check.rs:123-125)

@@ -282,19 +282,7 @@ HFr spark_debug_e(Ctx& c, size_t n, size_t l, size_t cc, const uint32_t* const* 
 static void spark_verify_checked(const PcsVerifier& pcs, size_t n, size_t l, size_t cc, size_t nv, const uint8_t* commitment,
                                  size_t commitment_len, const HFr* point, const HFr& value, Transcript& tr) {
   const SparkLayout lay{cc};
-  // the commitment blob is a transcript's stream of its own: the mask element, then the non-identity points, nothing else
-  std::vector<HG1> comms;
-  {
-    KeccakTranscript kt;
-    kt.stream.assign(commitment, commitment + commitment_len);
-    Transcript blob(&kt.vt);
-    try {
-      comms = lasso_read_commitments(blob, lay.committed());
-    } catch (const Error& e) {
-      throw Error(LH_ERR_INVALID_SNARK, "spark: malformed commitment: " + e.msg);
-    }
-    if (kt.pos != kt.stream.size()) throw Error(LH_ERR_INVALID_SNARK, "spark: malformed commitment: wrong length");
-  }
+  std::vector<HG1> comms = argument_read_commitment_blob("spark", commitment, commitment_len, lay.committed());
   spark_header(tr, n, l, cc, comms, point);
   {
     const std::vector<HG1> block = lasso_read_commitments(tr, cc);

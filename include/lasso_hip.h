@@ -411,6 +411,42 @@ lh_status lh_spark_open(lh_ctx*, const lh_srs*, const lh_spark_poly*, const lh_f
 void lh_spark_free(lh_ctx*, lh_spark_poly*);
 /* (lh_spark_verify: with the verifiers below; lh_debug_spark_e: with the debug entries) */
 
+/* Spartan: prove that an R1CS instance is satisfied, over the Spark-committed matrices (tests/spartan_ref.py).
+ * Instance: A, B, C of 2^dim_vars x 2^dim_vars, each 2^num_vars entries (d_row[k], d_col[k], d_val[k]) - DEVICE columns
+ * uint32_t[2^num_vars] with values < 2^dim_vars and a DEVICE column of 2^num_vars field elements; the same num_vars for the
+ * three; entries with the same position add up; pad with d_val = 0.  Assignment z of 2^dim_vars elements:
+ * z[y] = w[y] for y < 2^(dim_vars-1) (the witness, DEVICE), z[2^(dim_vars-1) + i] = x[i] for i < num_public (HOST), 0 above;
+ * the constant 1 is the caller's x[0].  Satisfied: (Az)[i] (Bz)[i] = (Cz)[i] for every row i.
+ *
+ * lh_r1cs_commit makes the key ONCE: the Spark commitments of A, B, C in the caller's entry order (dim 0 = row, dim 1 = col)
+ * and, per matrix and direction, the entries sorted by row and by column (18 * 2^num_vars words of device memory outside
+ * the proof arena).  The key owns its device memory; it is freed by lh_r1cs_free or with its ctx and proves any number of
+ * assignments: a prove runs no sort.  lh_r1cs_commitment: the key bytes the verifier takes - the three lh_spark_commitment
+ * blobs one after the other (A | B | C); out NULL: *len alone; else *len is the room in and the length out.
+ * lh_spartan_prove appends the proof to t.  A witness that does not satisfy the instance is LH_ERR_ARG "spartan: the
+ * witness does not satisfy K of the 2^l constraints": nothing is written to t and the ctx stays usable.
+ * Limits (LH_ERR_ARG with a message, checked on entry):
+ *   LH_SPARTAN_MIN_DIM_VARS <= dim_vars <= LH_SPARTAN_MAX_DIM_VARS   a witness half and a public half; Spark's bound
+ *   1 <= num_vars < 31                                              Spark's
+ *   1 <= num_public <= 2^(dim_vars - 1)
+ *   an index >= 2^dim_vars: "spark: index out of range" (the ctx stays usable)
+ *   no NULL argument; not on a ctx inside a sharded prove, nor on one with a communicator of several ranks
+ * LH_ERR_INVALID_PCS_PARAM when max(num_vars, dim_vars) exceeds the SRS.  Multilinear KZG only. */
+#define LH_SPARTAN_MIN_DIM_VARS 2
+#define LH_SPARTAN_MAX_DIM_VARS 24
+typedef struct lh_r1cs_matrix {
+  const uint32_t* d_row;
+  const uint32_t* d_col;
+  const lh_fr* d_val;
+} lh_r1cs_matrix;
+typedef struct lh_r1cs_key lh_r1cs_key;
+lh_status lh_r1cs_commit(lh_ctx*, const lh_srs*, size_t num_vars, size_t dim_vars, const lh_r1cs_matrix m[3], lh_r1cs_key** out);
+lh_status lh_r1cs_commitment(const lh_r1cs_key*, uint8_t* out, size_t* len);
+lh_status lh_spartan_prove(lh_ctx*, const lh_srs*, const lh_r1cs_key*, const lh_fr* d_w, const lh_fr* x /* host */,
+                           size_t num_public, lh_transcript* t);
+void lh_r1cs_free(lh_ctx*, lh_r1cs_key*);
+/* (lh_spartan_verify: with the verifiers below; lh_debug_spartan_spmv: with the debug entries) */
+
 /* per-phase wall-clock of the last lh_lasso_prove on this ctx, milliseconds:
  * [witness, commit, surge, leaves+trees, gkr, evals, open_n, open_l, total] */
 #define LH_LASSO_NUM_PHASES 9
@@ -733,6 +769,12 @@ lh_status lh_memcheck_verify(const lh_mkzg_vp* vp, size_t num_vars, size_t mem_v
  * tables' extensions come in closed form: no work of order 2^dim_vars. */
 lh_status lh_spark_verify(const lh_mkzg_vp* vp, size_t num_vars, size_t dim_vars, size_t num_dims, const uint8_t* commitment,
                           size_t commitment_len, const lh_fr* point, const lh_fr* value, lh_transcript* t);
+/* the verifier of lh_spartan_prove (tests/spartan_ref.py verify; host only): `commitment` are the bytes of
+ * lh_r1cs_commitment, `x` the num_public public inputs.  The same limits as the prover's; LH_ERR_INVALID_PCS_PARAM when
+ * max(num_vars, dim_vars) exceeds the param; a proof that does not verify and a malformed key are LH_ERR_INVALID_SNARK
+ * "spartan: ...".  The public half of z~ costs num_public field operations, the matrices none: Spark proves their values. */
+lh_status lh_spartan_verify(const lh_mkzg_vp* vp, size_t num_vars, size_t dim_vars, const uint8_t* commitment, size_t commitment_len,
+                            const lh_fr* x, size_t num_public, lh_transcript* t);
 typedef struct lh_hp_vparam { /* HyperPlonkVerifierParam (hyperplonk.rs:57-74) */
   size_t num_vars;
   size_t num_instance_polys;
@@ -1157,6 +1199,10 @@ lh_status lh_debug_memcheck_witness(lh_ctx*, const lh_memcheck_trace*, size_t nu
  * and limits as lh_spark_commit; an index >= 2^dim_vars is LH_ERR_ARG "spark: index out of range". */
 lh_status lh_debug_spark_e(lh_ctx*, size_t num_vars, size_t dim_vars, size_t num_dims, const uint32_t* const* d_dims,
                            const lh_fr* d_val, const lh_fr* point, lh_fr* const* d_E, lh_fr* out_value);
+/* the keyed field sum of lh_spartan_prove on its own (csrc/kernels_spartan.hip spartan_spmv), the three matrices of the key
+ * in one launch set: direction 0, d_out[m] = M_m d_x (sums by row); direction 1, d_out[m] = M_m^T d_x (sums by column).
+ * d_x and every d_out[m]: DEVICE, 2^dim_vars field elements; d_out is overwritten in full. */
+lh_status lh_debug_spartan_spmv(lh_ctx*, const lh_r1cs_key*, int direction, const lh_fr* d_x, lh_fr* const d_out[3]);
 /* the pass plan of one slab (host only, no GPU needed): the number of radix passes, the digit width of each (rb[passes ..
  * 8) = 0; `bits` above the key width count as the key width) and the temporary device bytes the sort takes */
 lh_status lh_debug_sort_plan(size_t n, unsigned bits, int key_bytes, unsigned* passes, unsigned rb[8], size_t* temp_bytes);
