@@ -360,6 +360,30 @@ extern "C" {
     // (development) the keyed field sum alone: direction 0 by rows, 1 by columns; d_out: three device tables of 2^dim_vars
     pub fn lh_debug_spartan_spmv(ctx: *mut lh_ctx, key: *const lh_r1cs_key, direction: c_int, d_x: *const Fr,
                                  d_out: *const *mut Fr) -> lh_status;
+    // Nova folding over an R1CS key (tests/nova_ref.py).  An instance blob is at most 160 + 32 num_public bytes; an entry that
+    // makes one writes it to out_instance (*out_len: the room in, the length out).  d_e1 / d_e2 / d_e null: zero
+    pub fn lh_nova_instance(ctx: *mut lh_ctx, srs: *const lh_srs, key: *const lh_r1cs_key, d_w: *const Fr, x: *const Fr,
+                            num_public: usize, out_instance: *mut u8, out_len: *mut usize) -> lh_status;
+    pub fn lh_nova_fold(ctx: *mut lh_ctx, srs: *const lh_srs, key: *const lh_r1cs_key, instance1: *const u8, instance1_len: usize,
+                        instance2: *const u8, instance2_len: usize, d_w1: *const Fr, d_e1: *const Fr, d_w2: *const Fr,
+                        d_e2: *const Fr, d_w_out: *mut Fr, d_e_out: *mut Fr, out_instance: *mut u8, out_len: *mut usize,
+                        t: *mut lh_transcript) -> lh_status;
+    pub fn lh_spartan_prove_relaxed(ctx: *mut lh_ctx, srs: *const lh_srs, key: *const lh_r1cs_key, instance: *const u8,
+                                    instance_len: usize, d_w: *const Fr, d_e: *const Fr, t: *mut lh_transcript) -> lh_status;
+    pub fn lh_nova_fold_verify(num_vars: usize, dim_vars: usize, commitment: *const u8, commitment_len: usize, instance1: *const u8,
+                               instance1_len: usize, instance2: *const u8, instance2_len: usize, out_instance: *mut u8,
+                               out_len: *mut usize, t: *mut lh_transcript) -> lh_status;
+    pub fn lh_spartan_verify_relaxed(vp: *const lh_mkzg_vp, num_vars: usize, dim_vars: usize, commitment: *const u8,
+                                     commitment_len: usize, instance: *const u8, instance_len: usize, num_public: usize,
+                                     t: *mut lh_transcript) -> lh_status;
+    // (development) the kernels of a fold alone
+    pub fn lh_debug_nova_spmv2(ctx: *mut lh_ctx, key: *const lh_r1cs_key, direction: c_int, d_x1: *const Fr, d_x2: *const Fr,
+                               d_out1: *const *mut Fr, d_out2: *const *mut Fr) -> lh_status;
+    pub fn lh_debug_nova_cross_term(ctx: *mut lh_ctx, dim_vars: usize, d_mz1: *const *const Fr, d_mz2: *const *const Fr,
+                                    d_e1: *const Fr, d_e2: *const Fr, u1: *const Fr, u2: *const Fr, d_t: *mut Fr,
+                                    out_bad: *mut usize) -> lh_status;
+    pub fn lh_debug_nova_fold(ctx: *mut lh_ctx, dim_vars: usize, d_w1: *const Fr, d_w2: *const Fr, d_w_out: *mut Fr, d_e1: *const Fr,
+                              d_t: *const Fr, d_e2: *const Fr, d_e_out: *mut Fr, r: *const Fr) -> lh_status;
     // the host verifier of lh_gkr_fractional_prove; the roots p_0s / q_0s come back with the final claims and the point
     pub fn lh_gkr_fractional_verify(num_batching: usize, num_vars: usize, claimed_p_0s: *const *const Fr,
                                     claimed_q_0s: *const *const Fr, t: *mut lh_transcript, out_p_0s: *mut Fr,

@@ -2010,6 +2010,178 @@ def spartan_spmv(ctx, key, direction, x):
     return out
 
 
+# ------------------------------------------------------------------ Nova folding over an R1CS key; relaxed Spartan (tests/nova_ref.py)
+def _fr_ptr(p):
+    """a device vector (MultilinearPolynomial / DeviceBuffer / raw pointer) or None as lh_fr*"""
+    return C.cast(C.c_void_p(_raw_ptr(p)), C.POINTER(lh_fr)) if p is not None else None
+
+
+def _bytes_arg(b):
+    return (C.c_uint8 * max(len(b), 1)).from_buffer_copy(bytes(b) or b"\0")
+
+
+def _nova_vector(key, p, vars_, what):
+    if getattr(p, "num_vars", vars_) != vars_ or getattr(getattr(p, "buf", p), "nbytes", 32 << vars_) < 32 << vars_:
+        raise ArgumentError("nova: %s of 2^%d entries (%d bytes)" % (what, vars_, 32 << vars_))
+
+
+def _nova_key(key, name="nova"):
+    if not isinstance(key, R1csKey) or not key.h:
+        raise ArgumentError("%s: the key has been freed" % name)
+
+
+def nova_instance_bytes(num_public):
+    """the most bytes an instance blob of num_public public inputs takes (LH_NOVA_INSTANCE_BYTES)"""
+    return 160 + 32 * num_public
+
+
+def _nova_room(instance):
+    """the room the fold of `instance` takes: LH_NOVA_INSTANCE_BYTES of its number of public inputs, which follows from its
+    mask and its length (a blob that cannot be read is the library's to refuse: any room will do)"""
+    points = 2 - bin(instance[31] & 3).count("1") if len(instance) >= 32 else 0
+    return nova_instance_bytes(max(len(instance) - 32 - 64 * points, 0) // 32)
+
+
+def nova_instance(ctx, srs, key, w, x):
+    """The fresh relaxed instance of an assignment z = (w, x, 0) that satisfies the instance of `key`, x[0] = 1 -> the
+    instance blob (bytes): the commitment of w, C_E the identity, x.  Its witness is (w, None)."""
+    _nova_key(key)
+    if w is None or x is None:
+        raise ArgumentError("nova: null argument: w or x")
+    x = list(x)
+    _spartan_shape(key.num_vars, key.dim_vars, len(x))
+    _nova_vector(key, w, key.dim_vars - 1, "a witness")
+    out, n = (C.c_uint8 * nova_instance_bytes(len(x)))(), C.c_size_t(nova_instance_bytes(len(x)))
+    _check(ctx.lib.lh_nova_instance(ctx.h, srs.h, key.h, _fr_ptr(w), _fr_array(x), len(x), out, C.byref(n)))
+    return bytes(out[:n.value])
+
+
+def nova_fold(ctx, srs, key, instance1, w1, e1, instance2, w2, e2, w_out, e_out, transcript=None):
+    """Fold the relaxed instances (instance1, w1, e1) and (instance2, w2, e2) of `key` - blobs, device vectors of
+    2^(dim_vars - 1) and 2^dim_vars Fr, e1 / e2 None for zero - into the caller's w_out and e_out (which may be w1 and e1)
+    -> (the folded instance blob, the proof bytes); with a transcript given the proof is appended to it and None returned
+    in its place.  An input that fails its own relaxed relation: ArgumentError, nothing written."""
+    _nova_key(key)
+    if any(v is None for v in (instance1, instance2, w1, w2, w_out, e_out)):
+        raise ArgumentError("nova: null argument: an instance, a witness or an output")
+    l = key.dim_vars
+    for p, vars_, what in ((w1, l - 1, "a witness"), (w2, l - 1, "a witness"), (w_out, l - 1, "a witness"), (e_out, l, "an error vector")) + \
+            tuple((e, l, "an error vector") for e in (e1, e2) if e is not None):
+        _nova_vector(key, p, vars_, what)
+    room = _nova_room(bytes(instance1))
+    out, n = (C.c_uint8 * room)(), C.c_size_t(room)
+    t = transcript if transcript is not None else Keccak256Transcript()
+    _check(ctx.lib.lh_nova_fold(ctx.h, srs.h, key.h, _bytes_arg(instance1), len(instance1), _bytes_arg(instance2), len(instance2),
+                                _fr_ptr(w1), _fr_ptr(e1), _fr_ptr(w2), _fr_ptr(e2), _fr_ptr(w_out), _fr_ptr(e_out), out, C.byref(n), t.p))
+    return bytes(out[:n.value]), (t.into_proof() if transcript is None else None)
+
+
+def nova_fold_verify(num_vars, dim_vars, commitment, instance1, instance2, proof, lib=None):
+    """Verifier of nova_fold (host only; no param): `commitment` the bytes of R1csKey.commitment, the two instance blobs,
+    `proof` bytes or a transcript -> the folded instance blob.  A Keccak256Transcript must be fully consumed."""
+    if commitment is None or instance1 is None or instance2 is None or proof is None:
+        raise ArgumentError("nova: null argument")
+    _spartan_shape(num_vars, dim_vars, 1)
+    t = Keccak256Transcript.from_proof(bytes(proof)) if isinstance(proof, (bytes, bytearray)) else proof
+    room = _nova_room(bytes(instance1))
+    out, n = (C.c_uint8 * room)(), C.c_size_t(room)
+    _check((lib or _ffi.load()).lh_nova_fold_verify(num_vars, dim_vars, _bytes_arg(commitment), len(commitment), _bytes_arg(instance1),
+                                                    len(instance1), _bytes_arg(instance2), len(instance2), out, C.byref(n), t.p))
+    if isinstance(t, Keccak256Transcript) and t.remaining():
+        raise InvalidSnark("nova: trailing bytes in proof")
+    return bytes(out[:n.value])
+
+
+def spartan_prove_relaxed(ctx, srs, key, instance, w, e, transcript=None):
+    """Prove the relaxed instance `instance` (a blob of nova_instance / nova_fold) of `key` with the witness (w, e), e None
+    for an instance whose C_E is the identity -> the proof bytes; with a transcript given the proof is appended to it and
+    None returned.  A witness that fails the relaxed relation: ArgumentError."""
+    _nova_key(key, "spartan")
+    if instance is None or w is None:
+        raise ArgumentError("spartan: null argument: the instance or w")
+    _nova_vector(key, w, key.dim_vars - 1, "a witness")
+    if e is not None:
+        _nova_vector(key, e, key.dim_vars, "an error vector")
+    t = transcript if transcript is not None else Keccak256Transcript()
+    _check(ctx.lib.lh_spartan_prove_relaxed(ctx.h, srs.h, key.h, _bytes_arg(instance), len(instance), _fr_ptr(w), _fr_ptr(e), t.p))
+    return t.into_proof() if transcript is None else None
+
+
+def spartan_verify_relaxed(vp, num_vars, dim_vars, commitment, instance, num_public, proof):
+    """Verifier of spartan_prove_relaxed (host only): `commitment` the bytes of R1csKey.commitment, `instance` the blob,
+    `proof` bytes or a transcript.  A Keccak256Transcript must be fully consumed."""
+    if commitment is None or instance is None or proof is None:
+        raise ArgumentError("spartan: null argument")
+    _spartan_shape(num_vars, dim_vars, num_public)
+    t = Keccak256Transcript.from_proof(bytes(proof)) if isinstance(proof, (bytes, bytearray)) else proof
+    _check(vp.lib.lh_spartan_verify_relaxed(vp.h, num_vars, dim_vars, _bytes_arg(commitment), len(commitment), _bytes_arg(instance),
+                                            len(instance), num_public, t.p))
+    if isinstance(t, Keccak256Transcript) and t.remaining():
+        raise InvalidSnark("spartan: trailing bytes in proof")
+
+
+def nova_spmv2(ctx, key, direction, x1, x2):
+    """(development) the keyed field sum with two right-hand sides alone (lh_debug_nova_spmv2) -> (M x1, M x2), each three
+    lists of 2^dim_vars ints (direction as spartan_spmv).  x2 `is` x1: one device vector for both.  The output buffers are
+    filled with non-zero bytes first: the kernel owes every cell."""
+    _nova_key(key)
+    if direction not in (0, 1):
+        raise ArgumentError("nova: direction is 0 (by rows) or 1 (by columns)")
+    if len(x1) != 1 << key.dim_vars or len(x2) != 1 << key.dim_vars:
+        raise ArgumentError("nova: vectors of 2^dim_vars entries")
+    size = 32 << key.dim_vars
+    d_x1 = ctx.upload(frs_to_bytes(list(x1)))
+    d_x2 = d_x1 if x2 is x1 else ctx.upload(frs_to_bytes(list(x2)))
+    bufs = [ctx.upload(b"\xa5" * size) for _ in range(6)]
+    fr_pp = lambda bs: C.cast(_ptr_array(bs), C.POINTER(C.POINTER(lh_fr)))
+    try:
+        _check(ctx.lib.lh_debug_nova_spmv2(ctx.h, key.h, direction, _fr_ptr(d_x1), _fr_ptr(d_x2), fr_pp(bufs[:3]), fr_pp(bufs[3:])))
+        out = [frs_from_bytes(b.read()) for b in bufs]
+    finally:
+        for b in bufs + [d_x1] + ([d_x2] if d_x2 is not d_x1 else []):
+            b.free()
+    return out[:3], out[3:]
+
+
+def nova_cross_term(ctx, dim_vars, mz1, mz2, e1, e2, u1, u2):
+    """(development) the cross-term kernel alone (lh_debug_nova_cross_term): mz1, mz2 three lists of 2^dim_vars ints each,
+    e1 / e2 lists or None -> (T, [bad1, bad2]).  T's buffer is filled with non-zero bytes first."""
+    M = 1 << dim_vars
+    ups = [ctx.upload(frs_to_bytes(list(v))) for v in list(mz1) + list(mz2)]
+    es = [ctx.upload(frs_to_bytes(list(e))) if e is not None else None for e in (e1, e2)]
+    d_t = ctx.upload(b"\xa5" * (32 * M))
+    bad = (C.c_size_t * 2)()
+    fr_pp = lambda bs: C.cast(_ptr_array(bs), C.POINTER(C.POINTER(lh_fr)))
+    try:
+        _check(ctx.lib.lh_debug_nova_cross_term(ctx.h, dim_vars, fr_pp(ups[:3]), fr_pp(ups[3:]), _fr_ptr(es[0]), _fr_ptr(es[1]),
+                                                _fr_array([u1]), _fr_array([u2]), _fr_ptr(d_t), bad))
+        T = frs_from_bytes(d_t.read())
+    finally:
+        for b in ups + [e for e in es if e is not None] + [d_t]:
+            b.free()
+    return T, [bad[0], bad[1]]
+
+
+def nova_fold_vectors(ctx, dim_vars, w1, w2, e1, t, e2, r, in_place=False):
+    """(development) the linear-combination kernel alone (lh_debug_nova_fold) -> (w1 + r w2, e1 + r t + r^2 e2) as lists;
+    e1 / e2 None for zero.  in_place: the outputs are the buffers of w1 and e1 (e1 given); else fresh buffers filled with
+    non-zero bytes."""
+    M = 1 << dim_vars
+    d = {k: ctx.upload(frs_to_bytes(list(v))) for k, v in (("w1", w1), ("w2", w2), ("e1", e1), ("t", t), ("e2", e2)) if v is not None}
+    if in_place:
+        d_w, d_e = d["w1"], d["e1"]
+    else:
+        d_w, d_e = ctx.upload(b"\xa5" * (16 * M)), ctx.upload(b"\xa5" * (32 * M))
+    try:
+        _check(ctx.lib.lh_debug_nova_fold(ctx.h, dim_vars, _fr_ptr(d["w1"]), _fr_ptr(d["w2"]), _fr_ptr(d_w), _fr_ptr(d.get("e1")),
+                                          _fr_ptr(d["t"]), _fr_ptr(d.get("e2")), _fr_ptr(d_e), _fr_array([r])))
+        out = frs_from_bytes(d_w.read()), frs_from_bytes(d_e.read())
+    finally:
+        for b in list(d.values()) + ([] if in_place else [d_w, d_e]):
+            b.free()
+    return out
+
+
 def verify_fractional_sum_check(num_vars, claimed_p_0s, claimed_q_0s, transcript):
     """fractional_sum_check.rs:193-270, the host verifier of prove_fractional_sum_check (a claim None: the root is read)
     -> (p_0s, q_0s, p_xs, q_xs, x): the roots come back because a caller checks a relation between them."""

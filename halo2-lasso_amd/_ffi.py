@@ -438,6 +438,16 @@ SIGNATURES["lh_spartan_prove"] = (C.c_int, [_P, _P, _P, C.POINTER(lh_fr), C.POIN
 SIGNATURES["lh_r1cs_free"] = (None, [_P, _P])
 SIGNATURES["lh_spartan_verify"] = (C.c_int, [_P, _SZ, _SZ, _P, _SZ, C.POINTER(lh_fr), _SZ, _T])
 SIGNATURES["lh_debug_spartan_spmv"] = (C.c_int, [_P, _P, C.c_int, C.POINTER(lh_fr), C.POINTER(C.POINTER(lh_fr))])
+# Nova folding: instance blobs in and out as bytes (out: the buffer and its room in / length out)
+_FR = C.POINTER(lh_fr)
+SIGNATURES["lh_nova_instance"] = (C.c_int, [_P, _P, _P, _FR, _FR, _SZ, _P, C.POINTER(_SZ)])
+SIGNATURES["lh_nova_fold"] = (C.c_int, [_P, _P, _P, _P, _SZ, _P, _SZ, _FR, _FR, _FR, _FR, _FR, _FR, _P, C.POINTER(_SZ), _T])
+SIGNATURES["lh_spartan_prove_relaxed"] = (C.c_int, [_P, _P, _P, _P, _SZ, _FR, _FR, _T])
+SIGNATURES["lh_nova_fold_verify"] = (C.c_int, [_SZ, _SZ, _P, _SZ, _P, _SZ, _P, _SZ, _P, C.POINTER(_SZ), _T])
+SIGNATURES["lh_spartan_verify_relaxed"] = (C.c_int, [_P, _SZ, _SZ, _P, _SZ, _P, _SZ, _SZ, _T])
+SIGNATURES["lh_debug_nova_spmv2"] = (C.c_int, [_P, _P, C.c_int, _FR, _FR, C.POINTER(_FR), C.POINTER(_FR)])
+SIGNATURES["lh_debug_nova_cross_term"] = (C.c_int, [_P, _SZ, C.POINTER(_FR), C.POINTER(_FR), _FR, _FR, _FR, _FR, _FR, C.POINTER(_SZ)])
+SIGNATURES["lh_debug_nova_fold"] = (C.c_int, [_P, _SZ, _FR, _FR, _FR, _FR, _FR, _FR, _FR, _FR])
 SIGNATURES["lh_gkr_fractional_verify"] = (C.c_int, [_SZ, _SZ, C.POINTER(C.POINTER(lh_fr)), C.POINTER(C.POINTER(lh_fr)), _T,
                                                     C.POINTER(lh_fr), C.POINTER(lh_fr), C.POINTER(lh_fr), C.POINTER(lh_fr),
                                                     C.POINTER(lh_fr)])

@@ -99,6 +99,15 @@ void argument_verdict(const std::string& name, const std::function<void()>& veri
   }
 }
 
+void argument_absorb_commitments(Transcript& tr, const std::vector<HG1>& comms) {
+  uint64_t mask = 0;
+  for (size_t i = 0; i < comms.size(); i++)
+    if (comms[i].is_identity()) mask |= (uint64_t)1 << i;
+  tr.common_field_element(HFr::from_u64(mask));
+  for (const HG1& cm : comms)
+    if (!cm.is_identity()) tr.common_commitment(cm);
+}
+
 std::vector<HG1> argument_read_commitment_blob(const std::string& name, const uint8_t* blob, size_t len, size_t count) {
   KeccakTranscript kt;
   kt.stream.assign(blob, blob + len);

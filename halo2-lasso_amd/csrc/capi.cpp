@@ -800,6 +800,59 @@ void lh_r1cs_free(lh_ctx* ctx, lh_r1cs_key* key) {
   (void)hipSetDevice(ctx->c.device);
   spartan_free(ctx->c, (R1csKey*)key);
 }
+// ---------------------------------------------------------------- Nova folding over an R1CS key; relaxed Spartan
+// an entry's instance blob goes to the caller's buffer: *len is the room in - the entry checks it against
+// LH_NOVA_INSTANCE_BYTES(num_public) before any work - and the length out
+static size_t nova_blob_room(const uint8_t* out, const size_t* len) {
+  LH_REQUIRE(out != nullptr && len != nullptr, LH_ERR_ARG, "null argument: out_instance or out_len");
+  return *len;
+}
+static void nova_blob_out(const std::vector<uint8_t>& blob, uint8_t* out, size_t* len) {
+  memcpy(out, blob.data(), blob.size());
+  *len = blob.size();
+}
+lh_status lh_nova_instance(lh_ctx* ctx, const lh_srs* srs, const lh_r1cs_key* key, const lh_fr* d_w, const lh_fr* x, size_t num_public,
+                           uint8_t* out_instance, size_t* out_len) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(srs);
+  NEED(key);
+  NEED(d_w);
+  NEED(x);
+  const size_t room = nova_blob_room(out_instance, out_len);
+  nova_blob_out(nova_instance(ctx->c, mkzg_pcs(ctx->c, srs->s), *(const R1csKey*)key, (const Fr*)d_w, (const HFr*)x, num_public, room),
+                out_instance, out_len);
+  LH_CATCH
+}
+lh_status lh_nova_fold(lh_ctx* ctx, const lh_srs* srs, const lh_r1cs_key* key, const uint8_t* instance1, size_t instance1_len,
+                       const uint8_t* instance2, size_t instance2_len, const lh_fr* d_w1, const lh_fr* d_e1, const lh_fr* d_w2,
+                       const lh_fr* d_e2, lh_fr* d_w_out, lh_fr* d_e_out, uint8_t* out_instance, size_t* out_len, lh_transcript* t) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(srs);
+  NEED(key);
+  NEED(instance1);
+  NEED(instance2);
+  NEED(d_w1);
+  NEED(d_w2);
+  NEED(d_w_out);
+  NEED(d_e_out);
+  Transcript tr(t);
+  const size_t room = nova_blob_room(out_instance, out_len);
+  nova_blob_out(nova_fold(ctx->c, mkzg_pcs(ctx->c, srs->s), *(const R1csKey*)key, instance1, instance1_len, instance2, instance2_len,
+                          (const Fr*)d_w1, (const Fr*)d_e1, (const Fr*)d_w2, (const Fr*)d_e2, (Fr*)d_w_out, (Fr*)d_e_out, room, tr),
+                out_instance, out_len);
+  LH_CATCH
+}
+lh_status lh_spartan_prove_relaxed(lh_ctx* ctx, const lh_srs* srs, const lh_r1cs_key* key, const uint8_t* instance, size_t instance_len,
+                                   const lh_fr* d_w, const lh_fr* d_e, lh_transcript* t) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(srs);
+  NEED(key);
+  NEED(instance);
+  NEED(d_w);
+  Transcript tr(t);
+  spartan_prove_relaxed(ctx->c, mkzg_pcs(ctx->c, srs->s), *(const R1csKey*)key, instance, instance_len, (const Fr*)d_w, (const Fr*)d_e, tr);
+  LH_CATCH
+}
 lh_status lh_lasso_last_timing(lh_ctx* ctx, double* out_ms) {
   LH_TRY NEED_CTX(ctx);
   NEED(out_ms);
@@ -1161,6 +1214,33 @@ lh_status lh_spartan_verify(const lh_mkzg_vp* vp, size_t num_vars, size_t dim_va
   if (spartan_check(num_vars, dim_vars, num_public) > mkzg_vp_num_vars(*vp->p))
     throw lh::Error(LH_ERR_INVALID_PCS_PARAM, "Too many variates of poly to verify");
   spartan_verify(mkzg_verifier(*vp->p), num_vars, dim_vars, commitment, commitment_len, (const HFr*)x, num_public, tr);
+  LH_CATCH
+}
+lh_status lh_nova_fold_verify(size_t num_vars, size_t dim_vars, const uint8_t* commitment, size_t commitment_len, const uint8_t* instance1,
+                              size_t instance1_len, const uint8_t* instance2, size_t instance2_len, uint8_t* out_instance, size_t* out_len,
+                              lh_transcript* t) {
+  LH_TRY
+  spartan_check(num_vars, dim_vars, 1);
+  NEED(commitment);
+  NEED(instance1);
+  NEED(instance2);
+  Transcript tr(t);
+  const size_t room = nova_blob_room(out_instance, out_len);
+  nova_blob_out(nova_fold_verify(num_vars, dim_vars, commitment, commitment_len, instance1, instance1_len, instance2, instance2_len, room,
+                                 tr),
+                out_instance, out_len);
+  LH_CATCH
+}
+lh_status lh_spartan_verify_relaxed(const lh_mkzg_vp* vp, size_t num_vars, size_t dim_vars, const uint8_t* commitment, size_t commitment_len,
+                                    const uint8_t* instance, size_t instance_len, size_t num_public, lh_transcript* t) {
+  LH_TRY
+  NEED(vp);
+  NEED(commitment);
+  NEED(instance);
+  Transcript tr(t);
+  if (spartan_check(num_vars, dim_vars, num_public) > mkzg_vp_num_vars(*vp->p))
+    throw lh::Error(LH_ERR_INVALID_PCS_PARAM, "Too many variates of poly to verify");
+  spartan_verify_relaxed(mkzg_verifier(*vp->p), num_vars, dim_vars, commitment, commitment_len, instance, instance_len, num_public, tr);
   LH_CATCH
 }
 lh_status lh_hyperplonk_verify(const lh_mkzg_vp* vp, const lh_hp_vparam* hvp, const lh_fr* const* instances,
@@ -2339,6 +2419,42 @@ lh_status lh_debug_spartan_spmv(lh_ctx* ctx, const lh_r1cs_key* key, int directi
   LH_TRY NEED_CTX(ctx);
   NEED(key);
   spartan_debug_spmv(ctx->c, *(const R1csKey*)key, direction, (const Fr*)d_x, (Fr* const*)d_out);
+  LH_CATCH
+}
+lh_status lh_debug_nova_spmv2(lh_ctx* ctx, const lh_r1cs_key* key, int direction, const lh_fr* d_x1, const lh_fr* d_x2,
+                              lh_fr* const d_out1[3], lh_fr* const d_out2[3]) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(key);
+  nova_debug_spmv2(ctx->c, *(const R1csKey*)key, direction, (const Fr*)d_x1, (const Fr*)d_x2, (Fr* const*)d_out1, (Fr* const*)d_out2);
+  LH_CATCH
+}
+lh_status lh_debug_nova_cross_term(lh_ctx* ctx, size_t dim_vars, const lh_fr* const d_mz1[3], const lh_fr* const d_mz2[3],
+                                   const lh_fr* d_e1, const lh_fr* d_e2, const lh_fr* u1, const lh_fr* u2, lh_fr* d_t, size_t out_bad[2]) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(d_mz1);
+  NEED(d_mz2);
+  NEED(u1);
+  NEED(u2);
+  NEED(d_t);
+  NEED(out_bad);
+  LH_REQUIRE(dim_vars >= 1 && dim_vars <= (size_t)LH_SPARTAN_MAX_DIM_VARS, LH_ERR_ARG, "nova: dim_vars out of range");
+  lh::NovaCross p;
+  for (int m = 0; m < 3; m++) p.mz1[m] = (const Fr*)d_mz1[m], p.mz2[m] = (const Fr*)d_mz2[m];
+  p.e1 = (const Fr*)d_e1, p.e2 = (const Fr*)d_e2, p.t = (Fr*)d_t;
+  k_nova_cross_term(ctx->c, p, *(const Fr*)u1, *(const Fr*)u2, (size_t)1 << dim_vars, out_bad);
+  LH_CATCH
+}
+lh_status lh_debug_nova_fold(lh_ctx* ctx, size_t dim_vars, const lh_fr* d_w1, const lh_fr* d_w2, lh_fr* d_w_out, const lh_fr* d_e1,
+                             const lh_fr* d_t, const lh_fr* d_e2, lh_fr* d_e_out, const lh_fr* r) {
+  LH_TRY NEED_CTX(ctx);
+  NEED(r);
+  LH_REQUIRE(dim_vars >= 1 && dim_vars <= (size_t)LH_SPARTAN_MAX_DIM_VARS, LH_ERR_ARG, "nova: dim_vars out of range");
+  HFr hr, hr2;
+  memcpy(&hr, r, 32);
+  hr2 = hr * hr;
+  k_nova_fold(ctx->c, (const Fr*)d_w1, (const Fr*)d_w2, (Fr*)d_w_out, (const Fr*)d_e1, (const Fr*)d_t, (const Fr*)d_e2, (Fr*)d_e_out,
+              *(const Fr*)&hr, *(const Fr*)&hr2, (size_t)1 << (dim_vars - 1), (size_t)1 << dim_vars);
+  ctx->c.sync();
   LH_CATCH
 }
 lh_status lh_debug_sort_plan(size_t n, unsigned bits, int key_bytes, unsigned* passes, unsigned rb[8], size_t* temp_bytes) {

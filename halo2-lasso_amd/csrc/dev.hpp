@@ -953,6 +953,35 @@ void k_spartan_spmv(Ctx&, const SpartanSpmv&, size_t n, size_t dim_vars);
 // the number of rows i < rows with az[i] bz[i] != cz[i]; synchronises.  Launch record "spartan_unsatisfied"
 size_t k_spartan_unsatisfied(Ctx&, const Fr* az, const Fr* bz, const Fr* cz, size_t rows);
 
+// ------------------------------------------------------------------ Nova folding (kernels_nova.hip; nova.cpp, tests/nova_ref.py)
+// spartan_spmv with TWO right-hand sides in one pass over the sorted stream: out1[m][s] = sum val X1[other], out2[m][s] = sum
+// val X2[other].  Key, other index, position and the value are loaded once for both; the same tile, scan, store-or-carry and
+// fold structure with carry items of a key and two sums.  X1 and X2 may be one vector.  Both outs are zeroed first.
+// Launch record "nova_spmv2", 3 n items, 6 n products, algorithmic bytes 3 (108 n + 64 * 2^dim_vars)
+struct NovaSpmv2 {
+  const uint32_t *seg[3], *other[3], *perm[3];
+  const Fr* val[3];
+  const Fr *X1, *X2;
+  Fr *out1[3], *out2[3];
+  uint32_t* carry_k;
+  Fr *carry_v1, *carry_v2;
+};
+void k_nova_spmv2(Ctx&, const NovaSpmv2&, size_t n, size_t dim_vars);
+// t[i] = mz1[0][i] mz2[1][i] + mz2[0][i] mz1[1][i] - u1 mz2[2][i] - u2 mz1[2][i], and bad[k] = the number of rows at which
+// input k fails mz[0] mz[1] = u mz[2] + e (e1 / e2 null: zero); synchronises.  Launch record "nova_cross_term"
+struct NovaCross {
+  const Fr *mz1[3], *mz2[3];
+  const Fr *e1, *e2;
+  Fr* t;
+};
+void k_nova_cross_term(Ctx&, const NovaCross&, const Fr& u1, const Fr& u2, size_t rows, size_t bad[2]);
+// the count alone, of one input; synchronises.  Launch record "nova_unsatisfied"
+size_t k_nova_unsatisfied(Ctx&, const Fr* az, const Fr* bz, const Fr* cz, const Fr& u, const Fr* e, size_t rows);
+// w_out = w1 + r w2 over `half` entries and e_out = e1 + r t + r2 e2 over `rows` in ONE launch (e1, e2 null: zero); the outputs
+// may be the inputs.  Launch record "nova_fold"
+void k_nova_fold(Ctx&, const Fr* w1, const Fr* w2, Fr* w_out, const Fr* e1, const Fr* t, const Fr* e2, Fr* e_out, const Fr& r,
+                 const Fr& r2, size_t half, size_t rows);
+
 void k_lookup_h(Ctx&, const Fr* input, const Fr* table, const Fr* m, const Fr& gamma, size_t n, Fr* h);
 void k_permutation_z(Ctx&, const Fr* const* values, const Fr* const* perms, size_t num_perm, size_t num_chunks,
                      size_t num_vars, const Fr& beta, const Fr& gamma, const uint32_t* d_order, const uint32_t* d_nth,

@@ -629,6 +629,8 @@ void argument_verdict(const std::string& name, const std::function<void()>& veri
 // A commitment blob - a transcript's stream of its own: the mask element, then the non-identity points, nothing else - read
 // back as `count` commitments; malformed: LH_ERR_INVALID_SNARK "<name>: malformed commitment: ..."
 std::vector<HG1> argument_read_commitment_blob(const std::string& name, const uint8_t* blob, size_t len, size_t count);
+// commitments that are part of a statement: the mask element (bit i: commitment i is the identity), then the other points
+void argument_absorb_commitments(Transcript& tr, const std::vector<HG1>& comms);
 
 // ------------------------------------------------------------------ Lasso
 // pieces of the argument shared by the standalone prover (lasso.cpp) and HyperPlonk's Lasso lookups (hyperplonk.cpp)
@@ -932,6 +934,49 @@ void spartan_verify(const PcsVerifier& pcs, size_t num_vars, size_t dim_vars, co
                     size_t num_public, Transcript& tr);
 // the keyed-sum kernel alone (lh_debug_spartan_spmv): direction 0, d_out[m] = M_m d_x; 1, d_out[m] = M_m^T d_x
 void spartan_debug_spmv(Ctx&, const R1csKey&, int direction, const Fr* d_x, Fr* const* d_out);
+// The steps the relaxed form and the fold (nova.cpp) take too.  spartan_key_header: n, l, p, then per matrix the commitment's
+// mask and its non-identity points; spartan_doubled_evaluation: THE opening list of one poly at one point - batch_open takes at
+// least two evaluations (eq_xy of an empty point is the zero poly), so the one evaluation is listed twice: the merged poly is
+// ((1 - t) + t) w; spartan_assignment: z = (w, x, 0) of 2^l entries
+void spartan_key_header(Transcript& tr, size_t n, size_t l, size_t p, const std::vector<HG1>* comms);
+std::vector<lh_evaluation> spartan_doubled_evaluation(const HFr& e);
+void spartan_spmv(Ctx&, const R1csKey&, int direction, const Fr* X, Fr* const* out);
+void spartan_require_key(Ctx&, const R1csKey&, const char* name);
+void spartan_assignment(Ctx&, size_t l, const Fr* d_w, const HFr* x, size_t p, Fr* z);
+void spartan_inner_prove(Ctx&, const Pcs&, const R1csKey&, const Fr* z, const Fr* d_w, Fr* const* Mz, const std::vector<HFr>& r_x,
+                         const HFr* at_rx, Transcript& tr, std::vector<HFr>& r_y, std::vector<HFr>& e);
+void spartan_open_matrices(Ctx&, const Pcs&, const R1csKey&, const std::vector<HFr>& r_x, const std::vector<HFr>& r_y,
+                           const std::vector<HFr>& e, Transcript& tr);
+struct SpartanKeyBlob {  // the key bytes taken apart: per matrix its commitment blob (into the caller's bytes) and its points
+  const uint8_t* blob[3];
+  size_t blob_len[3];
+  std::vector<HG1> comms[3];
+};
+SpartanKeyBlob spartan_read_key(const char* name, const uint8_t* key, size_t key_len);  // malformed: LH_ERR_INVALID_SNARK "<name>: malformed key: ..."
+void spartan_inner_verify(const PcsVerifier& pcs, size_t l, const HFr* x, size_t p, const HG1& cw, const HFr* v, Transcript& tr,
+                          std::vector<HFr>& r_y, std::vector<HFr>& e);
+void spartan_verify_matrices(const PcsVerifier& pcs, size_t n, size_t l, const SpartanKeyBlob& k, const std::vector<HFr>& r_x,
+                             const std::vector<HFr>& r_y, const std::vector<HFr>& e, Transcript& tr);
+
+// ------------------------------------------------------------------ Nova folding (nova.cpp; tests/nova_ref.py)
+// A relaxed instance (C_W, C_E, x), u = x[0], travels as a blob: lasso_write_commitments of [C_W, C_E] on a fresh transcript,
+// then the elements of x; its number of public inputs follows from its mask and its length.  Every entry returns the blob it
+// makes; `room` is what the caller's buffer takes, checked against LH_NOVA_INSTANCE_BYTES(num_public) before any work.  A blob
+// that cannot be read is LH_ERR_ARG at the provers, whose call it is part of, LH_ERR_INVALID_SNARK at the verifiers.
+// the fresh instance of a satisfying assignment with x[0] = 1: C_E the identity
+std::vector<uint8_t> nova_instance(Ctx&, const Pcs&, const R1csKey&, const Fr* d_w, const HFr* x, size_t num_public, size_t room);
+// d_e1 / d_e2 null: zero.  d_w_out (2^(l-1)) and d_e_out (2^l) may be input 1's.  Appends the proof (the T block)
+std::vector<uint8_t> nova_fold(Ctx&, const Pcs&, const R1csKey&, const uint8_t* blob1, size_t len1, const uint8_t* blob2, size_t len2,
+                               const Fr* d_w1, const Fr* d_e1, const Fr* d_w2, const Fr* d_e2, Fr* d_w_out, Fr* d_e_out, size_t room,
+                               Transcript& tr);
+std::vector<uint8_t> nova_fold_verify(size_t num_vars, size_t dim_vars, const uint8_t* key, size_t key_len, const uint8_t* blob1,
+                                      size_t len1, const uint8_t* blob2, size_t len2, size_t room, Transcript& tr);
+void spartan_prove_relaxed(Ctx&, const Pcs&, const R1csKey&, const uint8_t* blob, size_t len, const Fr* d_w, const Fr* d_e,
+                           Transcript& tr);
+void spartan_verify_relaxed(const PcsVerifier& pcs, size_t num_vars, size_t dim_vars, const uint8_t* key, size_t key_len,
+                            const uint8_t* blob, size_t len, size_t num_public, Transcript& tr);
+// the kernels alone (lh_debug_nova_spmv2, lh_debug_nova_cross_term)
+void nova_debug_spmv2(Ctx&, const R1csKey&, int direction, const Fr* d_x1, const Fr* d_x2, Fr* const* d_out1, Fr* const* d_out2);
 
 // ------------------------------------------------------------------ verifiers (verifier.cpp; host only)
 HFr identity_eval(const std::vector<HFr>& x);  // sum_i 2^i x_i (sum_check.rs:123-125)

@@ -13,22 +13,11 @@ namespace lh {
 namespace {
 constexpr size_t SPARTAN_COMMITTED = 1 + 3 * 2;  // the polys of a matrix's Spark commitment (c = 2)
 
-// step 0: n, l, p; per matrix the commitment's mask and its non-identity points (as spark_header absorbs them); x
+// step 0: the key part (spartan_key_header), then x
 void spartan_header(Transcript& tr, size_t n, size_t l, size_t p, const std::vector<HG1>* comms, const HFr* x) {
-  for (size_t v : {n, l, p}) tr.common_field_element(HFr::from_u64(v));
-  for (size_t m = 0; m < 3; m++) {
-    uint64_t mask = 0;
-    for (size_t i = 0; i < comms[m].size(); i++)
-      if (comms[m][i].is_identity()) mask |= (uint64_t)1 << i;
-    tr.common_field_element(HFr::from_u64(mask));
-    for (const HG1& cm : comms[m])
-      if (!cm.is_identity()) tr.common_commitment(cm);
-  }
+  spartan_key_header(tr, n, l, p, comms);
   for (size_t i = 0; i < p; i++) tr.common_field_element(x[i]);
 }
-// THE opening list of w: batch_open takes at least two evaluations (eq_xy of an empty point is the zero poly), so the one
-// evaluation is listed twice - the merged poly is ((1 - t) + t) w
-std::vector<lh_evaluation> witness_evaluations(const HFr& e_w) { return {make_evaluation(0, 0, &e_w), make_evaluation(0, 0, &e_w)}; }
 
 lh_sop outer_expression() {  // eq(tau, .) (Poly0 Poly1 - Poly2)
   lh_sop sop;
@@ -51,7 +40,15 @@ lh_sop inner_expression(const HFr& rho) {  // (M_A + rho M_B + rho^2 M_C) z over
   }
   return sop;
 }
-void spmv(Ctx& c, const R1csKey& key, int direction, const Fr* X, Fr* const* out) {
+}  // namespace
+
+void spartan_key_header(Transcript& tr, size_t n, size_t l, size_t p, const std::vector<HG1>* comms) {
+  for (size_t v : {n, l, p}) tr.common_field_element(HFr::from_u64(v));
+  for (size_t m = 0; m < 3; m++) argument_absorb_commitments(tr, comms[m]);
+}
+std::vector<lh_evaluation> spartan_doubled_evaluation(const HFr& e) { return {make_evaluation(0, 0, &e), make_evaluation(0, 0, &e)}; }
+
+void spartan_spmv(Ctx& c, const R1csKey& key, int direction, const Fr* X, Fr* const* out) {
   SpartanSpmv a;
   memset(&a, 0, sizeof(a));
   for (size_t m = 0; m < 3; m++) {
@@ -61,11 +58,16 @@ void spmv(Ctx& c, const R1csKey& key, int direction, const Fr* X, Fr* const* out
   a.X = X;
   k_spartan_spmv(c, a, (size_t)1 << key.n, key.l);
 }
-void require_key(Ctx& c, const R1csKey& key) {
+void spartan_require_key(Ctx& c, const R1csKey& key, const char* name) {
   LH_REQUIRE(std::find(c.r1cs_keys.begin(), c.r1cs_keys.end(), &key) != c.r1cs_keys.end(), LH_ERR_ARG,
-             "spartan: the key was not committed on this ctx (or has been freed)");
+             std::string(name) + ": the key was not committed on this ctx (or has been freed)");
 }
-}  // namespace
+void spartan_assignment(Ctx& c, size_t l, const Fr* d_w, const HFr* x, size_t p, Fr* z) {
+  const size_t half = (size_t)1 << (l - 1);
+  LH_HIP(hipMemcpyAsync(z, d_w, half * sizeof(Fr), hipMemcpyDeviceToDevice, c.stream));
+  LH_HIP(hipMemcpyAsync(z + half, x, p * sizeof(Fr), hipMemcpyHostToDevice, c.stream));
+  if (p < half) LH_HIP(hipMemsetAsync(z + half + p, 0, (half - p) * sizeof(Fr), c.stream));
+}
 
 size_t spartan_check(size_t n, size_t l, size_t p) {
   LH_REQUIRE(l >= (size_t)LH_SPARTAN_MIN_DIM_VARS && l <= (size_t)LH_SPARTAN_MAX_DIM_VARS, LH_ERR_ARG,
@@ -143,35 +145,33 @@ R1csKey* spartan_commit(Ctx& c, const Pcs& pcs, size_t n, size_t l, const lh_r1c
 }
 
 void spartan_debug_spmv(Ctx& c, const R1csKey& key, int direction, const Fr* d_x, Fr* const* d_out) {
-  require_key(c, key);
+  spartan_require_key(c, key, "spartan");
   LH_REQUIRE(direction == 0 || direction == 1, LH_ERR_ARG, "spartan: direction is 0 (by rows) or 1 (by columns)");
   LH_REQUIRE(d_x && d_out && d_out[0] && d_out[1] && d_out[2], LH_ERR_ARG, "null argument: d_x or d_out");
-  spmv(c, key, direction, d_x, d_out);
+  spartan_spmv(c, key, direction, d_x, d_out);
   c.sync();
 }
 
 void spartan_prove(Ctx& c, const Pcs& pcs, const R1csKey& key, const Fr* d_w, const HFr* x, size_t p, Transcript& tr) {
-  require_key(c, key);
+  spartan_require_key(c, key, "spartan");
   const size_t n = key.n, l = key.l;
   const size_t nv = spartan_check(n, l, p);
   LH_REQUIRE(d_w != nullptr && x != nullptr, LH_ERR_ARG, "null argument: d_w or x");
   argument_not_sharded(c, "spartan");
   argument_pcs_check(pcs, nv, "spartan", true);
-  const size_t M = (size_t)1 << l, half = M / 2;
+  const size_t M = (size_t)1 << l;
   open_precommit_cancel(c);
-  std::vector<HFr> r_x, r_y, e(3);
+  std::vector<HFr> r_x, r_y, e;
   {
     ArenaScope scope(c.arena);
     EqHalfScope eq_scope(c);
     // ---- 3 first: z = (w, x, 0), Az, Bz, Cz and the satisfaction count need no challenge - a witness that does not
     // satisfy the instance is refused before the transcript is touched
     Fr* z = c.arena.alloc_n<Fr>(M);
-    LH_HIP(hipMemcpyAsync(z, d_w, half * sizeof(Fr), hipMemcpyDeviceToDevice, c.stream));
-    LH_HIP(hipMemcpyAsync(z + half, x, p * sizeof(Fr), hipMemcpyHostToDevice, c.stream));
-    if (p < half) LH_HIP(hipMemsetAsync(z + half + p, 0, (half - p) * sizeof(Fr), c.stream));
+    spartan_assignment(c, l, d_w, x, p, z);
     Fr* Mz[3];
     for (Fr*& t : Mz) t = c.arena.alloc_n<Fr>(M);
-    spmv(c, key, 0, z, Mz);
+    spartan_spmv(c, key, 0, z, Mz);
     const size_t bad = k_spartan_unsatisfied(c, Mz[0], Mz[1], Mz[2], M);
     LH_REQUIRE(bad == 0, LH_ERR_ARG,
                "spartan: the witness does not satisfy " + std::to_string(bad) + " of the 2^" + std::to_string(l) + " constraints");
@@ -194,31 +194,47 @@ void spartan_prove(Ctx& c, const Pcs& pcs, const R1csKey& key, const Fr* d_w, co
     }
     tr.write_field_elements(at_rx);
 
-    // ---- 5/6/7: rho; the matrices bound at r_x (the same keyed sum by columns, over the eq table of r_x; the tables of
-    // step 3 are done with and take the result); the inner sum-check, then the values at r_y
-    const HFr rho = tr.squeeze_challenge();
-    const HFr T = at_rx[0] + rho * at_rx[1] + rho * rho * at_rx[2];
-    {
-      ArenaScope inner(c.arena);
-      Fr* eq_rx = c.arena.alloc_n<Fr>(M);
-      k_eq_xy(c, (const Fr*)r_x.data(), l, eq_rx);
-      spmv(c, key, 1, eq_rx, Mz);
-    }
-    {
-      const Fr* polys[4] = {Mz[0], Mz[1], Mz[2], z};
-      SumCheckResult sc = sum_check_prove(c, LH_SC_EVALUATIONS, l, inner_expression(rho), polys, 4, nullptr, 0, T, tr, so);
-      r_y = sc.challenges;
-      std::copy(sc.evals.begin(), sc.evals.begin() + 3, e.begin());
-    }
-    tr.write_field_elements(e);
-    const HFr e_w = evaluate_polys(c, &d_w, 1, l - 1, r_y.data())[0];
-    tr.write_field_element(e_w);
-
-    // ---- 8: the opening of w at r_y[0 .. l-1)
-    const std::vector<lh_evaluation> evs = witness_evaluations(e_w);
-    pcs.batch_open(l - 1, &d_w, 1, r_y.data(), 1, evs.data(), evs.size(), tr, nullptr);
+    // ---- 5 to 8: the inner half
+    spartan_inner_prove(c, pcs, key, z, d_w, Mz, r_x, at_rx.data(), tr, r_y, e);
   }
   // ---- 9: the three Spark openings at r_x || r_y, on the same transcript
+  spartan_open_matrices(c, pcs, key, r_x, r_y, e, tr);
+}
+
+// steps 5 to 8, from rho to the opening of w: what the plain and the relaxed prover share.  Mz: the three tables of step 3,
+// done with - they take the matrices bound at r_x
+void spartan_inner_prove(Ctx& c, const Pcs& pcs, const R1csKey& key, const Fr* z, const Fr* d_w, Fr* const* Mz,
+                         const std::vector<HFr>& r_x, const HFr* at_rx, Transcript& tr, std::vector<HFr>& r_y, std::vector<HFr>& e) {
+  const size_t l = key.l, M = (size_t)1 << l;
+  ScOptions so;
+  so.sum_is_exact = true;
+  e.resize(3);
+  // ---- 5/6/7: rho; the matrices bound at r_x (the same keyed sum by columns, over the eq table of r_x; the tables of
+  // step 3 are done with and take the result); the inner sum-check, then the values at r_y
+  const HFr rho = tr.squeeze_challenge();
+  const HFr T = at_rx[0] + rho * at_rx[1] + rho * rho * at_rx[2];
+  {
+    ArenaScope inner(c.arena);
+    Fr* eq_rx = c.arena.alloc_n<Fr>(M);
+    k_eq_xy(c, (const Fr*)r_x.data(), l, eq_rx);
+    spartan_spmv(c, key, 1, eq_rx, Mz);
+  }
+  {
+    const Fr* polys[4] = {Mz[0], Mz[1], Mz[2], z};
+    SumCheckResult sc = sum_check_prove(c, LH_SC_EVALUATIONS, l, inner_expression(rho), polys, 4, nullptr, 0, T, tr, so);
+    r_y = sc.challenges;
+    std::copy(sc.evals.begin(), sc.evals.begin() + 3, e.begin());
+  }
+  tr.write_field_elements(e);
+  const HFr e_w = evaluate_polys(c, &d_w, 1, l - 1, r_y.data())[0];
+  tr.write_field_element(e_w);
+
+  // ---- 8: the opening of w at r_y[0 .. l-1)
+  const std::vector<lh_evaluation> evs = spartan_doubled_evaluation(e_w);
+  pcs.batch_open(l - 1, &d_w, 1, r_y.data(), 1, evs.data(), evs.size(), tr, nullptr);
+}
+void spartan_open_matrices(Ctx& c, const Pcs& pcs, const R1csKey& key, const std::vector<HFr>& r_x, const std::vector<HFr>& r_y,
+                           const std::vector<HFr>& e, Transcript& tr) {
   std::vector<HFr> point(r_x);
   point.insert(point.end(), r_y.begin(), r_y.end());
   for (size_t m = 0; m < 3; m++) {
@@ -227,38 +243,35 @@ void spartan_prove(Ctx& c, const Pcs& pcs, const R1csKey& key, const Fr* d_w, co
   }
 }
 
-static void spartan_verify_checked(const PcsVerifier& pcs, size_t n, size_t l, const uint8_t* key, size_t key_len, const HFr* x,
-                                   size_t p, Transcript& tr) {
+SpartanKeyBlob spartan_read_key(const char* name, const uint8_t* key, size_t key_len) {
+  const std::string malformed = std::string(name) + ": malformed key: ";
+  SpartanKeyBlob k;
+  const uint8_t** blob = k.blob;
+  size_t* blob_len = k.blob_len;
+  std::vector<HG1>* comms = k.comms;
   // the key blob: three commitment blobs, each its mask element and its non-identity points
-  const uint8_t* blob[3];
-  size_t blob_len[3];
-  std::vector<HG1> comms[3];
   size_t at = 0;
   for (size_t m = 0; m < 3; m++) {
-    if (key_len < at + 32) throw Error(LH_ERR_INVALID_SNARK, "spartan: malformed key: too short");
+    if (key_len < at + 32) throw Error(LH_ERR_INVALID_SNARK, malformed + "too short");
     size_t absent = 0;
     for (size_t i = 0; i < 32; i++) absent += (size_t)__builtin_popcount(key[at + i]);
     // (a mask out of range is refused by the reader below; here it must only not run the length negative)
     const size_t len = 32 + 64 * (SPARTAN_COMMITTED - std::min(absent, SPARTAN_COMMITTED));
-    if (key_len < at + len) throw Error(LH_ERR_INVALID_SNARK, "spartan: malformed key: too short");
+    if (key_len < at + len) throw Error(LH_ERR_INVALID_SNARK, malformed + "too short");
     blob[m] = key + at, blob_len[m] = len;
-    comms[m] = argument_read_commitment_blob("spartan", blob[m], len, SPARTAN_COMMITTED);
+    comms[m] = argument_read_commitment_blob(name, blob[m], len, SPARTAN_COMMITTED);
     at += len;
   }
-  if (at != key_len) throw Error(LH_ERR_INVALID_SNARK, "spartan: malformed key: wrong length");
-
-  spartan_header(tr, n, l, p, comms, x);
-  const std::vector<HG1> cw = lasso_read_commitments(tr, 1);
-  const std::vector<HFr> tau = tr.squeeze_challenges(l);
-  const std::pair<HFr, std::vector<HFr>> outer = sum_check_verify(LH_SC_EVALUATIONS, l, 3, HFr::zero(), tr);
-  const std::vector<HFr>& r_x = outer.second;
-  const std::vector<HFr> v = tr.read_field_elements(3);
-  if (outer.first != host_eq_xy_eval(tau.data(), r_x.data(), l) * (v[0] * v[1] - v[2]))
-    throw Error(LH_ERR_INVALID_SNARK, "spartan: outer sum-check final evaluation mismatch");
+  if (at != key_len) throw Error(LH_ERR_INVALID_SNARK, malformed + "wrong length");
+  return k;
+}
+// the verifier's steps 5 to 8, from rho to the opening of w (cw: its commitment; v: vA, vB, vC) -> r_y and eA, eB, eC
+void spartan_inner_verify(const PcsVerifier& pcs, size_t l, const HFr* x, size_t p, const HG1& cw, const HFr* v, Transcript& tr,
+                          std::vector<HFr>& r_y, std::vector<HFr>& e) {
   const HFr rho = tr.squeeze_challenge();
   const std::pair<HFr, std::vector<HFr>> inner = sum_check_verify(LH_SC_EVALUATIONS, l, 2, v[0] + rho * v[1] + rho * rho * v[2], tr);
-  const std::vector<HFr>& r_y = inner.second;
-  const std::vector<HFr> e = tr.read_field_elements(3);
+  r_y = inner.second;
+  e = tr.read_field_elements(3);
   const HFr e_w = tr.read_field_element();
   // z~(r_y): the public half at a cost that follows p - x padded to 2^q, the first q coordinates, the rest of the half's
   // coordinates at their zero side
@@ -269,18 +282,38 @@ static void spartan_verify_checked(const PcsVerifier& pcs, size_t n, size_t l, c
   const HFr z_ry = (HFr::one() - r_y[l - 1]) * e_w + r_y[l - 1] * x_ry;
   if (inner.first != (e[0] + rho * e[1] + rho * rho * e[2]) * z_ry)
     throw Error(LH_ERR_INVALID_SNARK, "spartan: inner sum-check final evaluation mismatch");
-  const std::vector<lh_evaluation> evs = witness_evaluations(e_w);
-  pcs.batch_verify(l - 1, cw.data(), 1, r_y.data(), 1, evs.data(), evs.size(), tr);
+  const std::vector<lh_evaluation> evs = spartan_doubled_evaluation(e_w);
+  pcs.batch_verify(l - 1, &cw, 1, r_y.data(), 1, evs.data(), evs.size(), tr);
+}
+void spartan_verify_matrices(const PcsVerifier& pcs, size_t n, size_t l, const SpartanKeyBlob& k, const std::vector<HFr>& r_x,
+                             const std::vector<HFr>& r_y, const std::vector<HFr>& e, Transcript& tr) {
   std::vector<HFr> point(r_x);
   point.insert(point.end(), r_y.begin(), r_y.end());
   for (size_t m = 0; m < 3; m++) {
     try {
-      spark_verify(pcs, n, l, 2, blob[m], blob_len[m], point.data(), e[m], tr);
+      spark_verify(pcs, n, l, 2, k.blob[m], k.blob_len[m], point.data(), e[m], tr);
     } catch (const Error& err) {
       if (err.code != LH_ERR_INVALID_SNARK) throw;
       throw Error(LH_ERR_INVALID_SNARK, std::string("spartan: matrix ") + "ABC"[m] + ": " + err.msg);
     }
   }
+}
+
+static void spartan_verify_checked(const PcsVerifier& pcs, size_t n, size_t l, const uint8_t* key, size_t key_len, const HFr* x,
+                                   size_t p, Transcript& tr) {
+  const SpartanKeyBlob k = spartan_read_key("spartan", key, key_len);
+  const std::vector<HG1>* comms = k.comms;
+  spartan_header(tr, n, l, p, comms, x);
+  const std::vector<HG1> cw = lasso_read_commitments(tr, 1);
+  const std::vector<HFr> tau = tr.squeeze_challenges(l);
+  const std::pair<HFr, std::vector<HFr>> outer = sum_check_verify(LH_SC_EVALUATIONS, l, 3, HFr::zero(), tr);
+  const std::vector<HFr>& r_x = outer.second;
+  const std::vector<HFr> v = tr.read_field_elements(3);
+  if (outer.first != host_eq_xy_eval(tau.data(), r_x.data(), l) * (v[0] * v[1] - v[2]))
+    throw Error(LH_ERR_INVALID_SNARK, "spartan: outer sum-check final evaluation mismatch");
+  std::vector<HFr> r_y, e;
+  spartan_inner_verify(pcs, l, x, p, cw[0], v.data(), tr, r_y, e);
+  spartan_verify_matrices(pcs, n, l, k, r_x, r_y, e, tr);
 }
 void spartan_verify(const PcsVerifier& pcs, size_t n, size_t l, const uint8_t* key, size_t key_len, const HFr* x, size_t p,
                     Transcript& tr) {

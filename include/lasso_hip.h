@@ -447,6 +447,37 @@ lh_status lh_spartan_prove(lh_ctx*, const lh_srs*, const lh_r1cs_key*, const lh_
 void lh_r1cs_free(lh_ctx*, lh_r1cs_key*);
 /* (lh_spartan_verify: with the verifiers below; lh_debug_spartan_spmv: with the debug entries) */
 
+/* Nova folding over an R1CS key, and the relaxed form of Spartan that closes a chain of folds (tests/nova_ref.py).
+ * A relaxed instance is (C_W, C_E, x): C_W the commitment of w over dim_vars - 1 variables, C_E the one of the error vector E
+ * over dim_vars variables, x the num_public public inputs with the relaxation scalar u = x[0]; its witness is (w, E) on the
+ * DEVICE, its relation (Az)[i] (Bz)[i] = u (Cz)[i] + E[i] with z = (w, x, 0) as above.  It travels as ONE blob: the mask
+ * element and the non-identity points of [C_W, C_E] as a commitment block writes them, then the elements of x - at most
+ * LH_NOVA_INSTANCE_BYTES(num_public) bytes.  Every entry that makes an instance writes it to out_instance: *out_len is the room
+ * in (at least LH_NOVA_INSTANCE_BYTES(num_public)) and the length out.
+ *
+ * lh_nova_instance: the fresh instance of an assignment that satisfies the key's instance as lh_spartan_prove takes it, with
+ * x[0] = 1: E = 0, C_E the identity.  A witness that does not satisfy: LH_ERR_ARG "nova: the witness does not satisfy ...".
+ * lh_nova_fold folds (instance1, d_w1, d_e1) and (instance2, d_w2, d_e2), either of them fresh or folded (d_e1 / d_e2 NULL:
+ * zero), into d_w_out (2^(dim_vars-1) elements) and d_e_out (2^dim_vars) - which may be d_w1 and d_e1: a running accumulator
+ * folds in place - and out_instance; the proof (the commitment block of the cross term: 96 bytes, 32 when it is zero) is
+ * appended to t.  An input that fails its own relation is LH_ERR_ARG "nova: input K does not satisfy J of the 2^l
+ * constraints": nothing is written to t and the ctx stays usable.  A fold runs no sort and no Spark kernel.  It does not check
+ * that a blob's commitments open to the given vectors: the relaxed proof does.
+ * lh_spartan_prove_relaxed proves a relaxed instance (d_e NULL: zero, for an instance whose C_E is the identity; a d_e given
+ * beside such an instance has to be zero).  A witness that fails the relaxed relation, a NULL d_e beside a C_E that is a
+ * point and a non-zero d_e beside the identity are LH_ERR_ARG before anything is written to t.
+ * Limits and refusals are lh_spartan_prove's; also LH_ERR_ARG: a blob of the wrong length or with a mask out of range, two
+ * instances with different numbers of public inputs.  Multilinear KZG only. */
+#define LH_NOVA_INSTANCE_BYTES(num_public) (160 + 32 * (size_t)(num_public))
+lh_status lh_nova_instance(lh_ctx*, const lh_srs*, const lh_r1cs_key*, const lh_fr* d_w, const lh_fr* x /* host */, size_t num_public,
+                           uint8_t* out_instance, size_t* out_len);
+lh_status lh_nova_fold(lh_ctx*, const lh_srs*, const lh_r1cs_key*, const uint8_t* instance1, size_t instance1_len,
+                       const uint8_t* instance2, size_t instance2_len, const lh_fr* d_w1, const lh_fr* d_e1, const lh_fr* d_w2,
+                       const lh_fr* d_e2, lh_fr* d_w_out, lh_fr* d_e_out, uint8_t* out_instance, size_t* out_len, lh_transcript* t);
+lh_status lh_spartan_prove_relaxed(lh_ctx*, const lh_srs*, const lh_r1cs_key*, const uint8_t* instance, size_t instance_len,
+                                   const lh_fr* d_w, const lh_fr* d_e, lh_transcript* t);
+/* (lh_nova_fold_verify, lh_spartan_verify_relaxed: with the verifiers below; lh_debug_nova_*: with the debug entries) */
+
 /* per-phase wall-clock of the last lh_lasso_prove on this ctx, milliseconds:
  * [witness, commit, surge, leaves+trees, gkr, evals, open_n, open_l, total] */
 #define LH_LASSO_NUM_PHASES 9
@@ -775,6 +806,17 @@ lh_status lh_spark_verify(const lh_mkzg_vp* vp, size_t num_vars, size_t dim_vars
  * "spartan: ...".  The public half of z~ costs num_public field operations, the matrices none: Spark proves their values. */
 lh_status lh_spartan_verify(const lh_mkzg_vp* vp, size_t num_vars, size_t dim_vars, const uint8_t* commitment, size_t commitment_len,
                             const lh_fr* x, size_t num_public, lh_transcript* t);
+/* the verifier of lh_nova_fold (tests/nova_ref.py fold_verify; host only, no pairing and no param): absorbs the key and the two
+ * instances, reads the cross term's commitment from t, and writes the folded instance - the prover's, byte for byte - to
+ * out_instance (*out_len: room in, length out).  Blobs that cannot be read, of different numbers of public inputs, or a proof
+ * that ends early are LH_ERR_INVALID_SNARK "nova: ...".  Nothing in a fold is checked: the relaxed proof of the result is. */
+lh_status lh_nova_fold_verify(size_t num_vars, size_t dim_vars, const uint8_t* commitment, size_t commitment_len, const uint8_t* instance1,
+                              size_t instance1_len, const uint8_t* instance2, size_t instance2_len, uint8_t* out_instance, size_t* out_len,
+                              lh_transcript* t);
+/* the verifier of lh_spartan_prove_relaxed (tests/nova_ref.py verify_relaxed; host only): as lh_spartan_verify, with the
+ * instance blob in place of x.  An instance whose C_E is the identity carries no opening of E and must have vE = 0. */
+lh_status lh_spartan_verify_relaxed(const lh_mkzg_vp* vp, size_t num_vars, size_t dim_vars, const uint8_t* commitment, size_t commitment_len,
+                                    const uint8_t* instance, size_t instance_len, size_t num_public, lh_transcript* t);
 typedef struct lh_hp_vparam { /* HyperPlonkVerifierParam (hyperplonk.rs:57-74) */
   size_t num_vars;
   size_t num_instance_polys;
@@ -1203,6 +1245,17 @@ lh_status lh_debug_spark_e(lh_ctx*, size_t num_vars, size_t dim_vars, size_t num
  * in one launch set: direction 0, d_out[m] = M_m d_x (sums by row); direction 1, d_out[m] = M_m^T d_x (sums by column).
  * d_x and every d_out[m]: DEVICE, 2^dim_vars field elements; d_out is overwritten in full. */
 lh_status lh_debug_spartan_spmv(lh_ctx*, const lh_r1cs_key*, int direction, const lh_fr* d_x, lh_fr* const d_out[3]);
+/* the kernels of lh_nova_fold on their own (csrc/kernels_nova.hip).  nova_spmv2: lh_debug_spartan_spmv with two right-hand sides
+ * in one pass, d_out1[m] = M_m d_x1 and d_out2[m] = M_m d_x2 (d_x1 and d_x2 may be one vector).  nova_cross_term over 2^dim_vars
+ * rows: d_t = mz1[0] mz2[1] + mz2[0] mz1[1] - u1 mz2[2] - u2 mz1[2] and out_bad[k] = the rows at which input k fails
+ * mz[0] mz[1] = u mz[2] + e (d_e1 / d_e2 NULL: zero; u1, u2: host).  nova_fold: d_w_out = d_w1 + r d_w2 over 2^(dim_vars-1)
+ * and d_e_out = d_e1 + r d_t + r^2 d_e2 over 2^dim_vars in one launch (d_e1 / d_e2 NULL: zero); the outputs may be the inputs. */
+lh_status lh_debug_nova_spmv2(lh_ctx*, const lh_r1cs_key*, int direction, const lh_fr* d_x1, const lh_fr* d_x2, lh_fr* const d_out1[3],
+                              lh_fr* const d_out2[3]);
+lh_status lh_debug_nova_cross_term(lh_ctx*, size_t dim_vars, const lh_fr* const d_mz1[3], const lh_fr* const d_mz2[3], const lh_fr* d_e1,
+                                   const lh_fr* d_e2, const lh_fr* u1, const lh_fr* u2, lh_fr* d_t, size_t out_bad[2]);
+lh_status lh_debug_nova_fold(lh_ctx*, size_t dim_vars, const lh_fr* d_w1, const lh_fr* d_w2, lh_fr* d_w_out, const lh_fr* d_e1,
+                             const lh_fr* d_t, const lh_fr* d_e2, lh_fr* d_e_out, const lh_fr* r);
 /* the pass plan of one slab (host only, no GPU needed): the number of radix passes, the digit width of each (rb[passes ..
  * 8) = 0; `bits` above the key width count as the key width) and the temporary device bytes the sort takes */
 lh_status lh_debug_sort_plan(size_t n, unsigned bits, int key_bytes, unsigned* passes, unsigned rb[8], size_t* temp_bytes);
