@@ -87,6 +87,7 @@ pub const LH_SPARK_MAX_DIMS: usize = 3;
 pub const LH_SPARK_MAX_DIM_VARS: usize = 24;
 pub const LH_SPARTAN_MIN_DIM_VARS: usize = 2;
 pub const LH_SPARTAN_MAX_DIM_VARS: usize = 24;
+pub const LH_SPARTAN_BATCH_MAX_VARS: usize = 26;
 // one matrix of lh_r1cs_commit: three device columns of 2^num_vars entries (row, col: uint32_t; val: field elements)
 #[repr(C)] #[derive(Clone, Copy)]
 pub struct lh_r1cs_matrix { pub d_row: *const u32, pub d_col: *const u32, pub d_val: *const Fr }
@@ -384,6 +385,11 @@ extern "C" {
                                     out_bad: *mut usize) -> lh_status;
     pub fn lh_debug_nova_fold(ctx: *mut lh_ctx, dim_vars: usize, d_w1: *const Fr, d_w2: *const Fr, d_w_out: *mut Fr, d_e1: *const Fr,
                               d_t: *const Fr, d_e2: *const Fr, d_e_out: *mut Fr, r: *const Fr) -> lh_status;
+    // Batched Spartan, the verifier (tests/spartan_batch_ref.py): num_instances >= 2 assignments of one key in one proof; x:
+    // num_instances * num_public elements, instance by instance
+    pub fn lh_spartan_verify_batch(vp: *const lh_mkzg_vp, num_vars: usize, dim_vars: usize, commitment: *const u8,
+                                   commitment_len: usize, x: *const Fr, num_instances: usize, num_public: usize,
+                                   t: *mut lh_transcript) -> lh_status;
     // the host verifier of lh_gkr_fractional_prove; the roots p_0s / q_0s come back with the final claims and the point
     pub fn lh_gkr_fractional_verify(num_batching: usize, num_vars: usize, claimed_p_0s: *const *const Fr,
                                     claimed_q_0s: *const *const Fr, t: *mut lh_transcript, out_p_0s: *mut Fr,

@@ -2182,6 +2182,41 @@ def nova_fold_vectors(ctx, dim_vars, w1, w2, e1, t, e2, r, in_place=False):
     return out
 
 
+# ------------------------------------------------------------------ batched Spartan, the verifier: several assignments of one key (tests/spartan_batch_ref.py)
+def _batch_vars(count):
+    return max((count - 1).bit_length(), 1)
+
+
+def _spartan_batch_shape(num_vars, dim_vars, num_public, count):
+    _spartan_shape(num_vars, dim_vars, num_public)
+    if not (isinstance(count, int) and count >= 2):
+        raise ArgumentError("spartan: num_instances out of range (at least 2)")
+    if dim_vars + _batch_vars(count) > _ffi.LH_SPARTAN_BATCH_MAX_VARS:
+        raise ArgumentError("spartan: dim_vars + batch_vars out of range (at most %d)" % _ffi.LH_SPARTAN_BATCH_MAX_VARS)
+
+
+def _batch_publics(xs):
+    xs = [list(x) for x in xs]
+    if not xs or any(len(x) != len(xs[0]) for x in xs):
+        raise ArgumentError("spartan: num_public public inputs for every instance")
+    return xs, len(xs[0])
+
+
+def spartan_verify_batch(vp, num_vars, dim_vars, commitment, xs, proof):
+    """Verifier of a batched Spartan proof - len(xs) >= 2 assignments of one key in one proof, tests/spartan_batch_ref.py -
+    (host only): `commitment` the bytes of R1csKey.commitment, `xs` the public inputs per instance, `proof` bytes or a
+    transcript.  A Keccak256Transcript must be fully consumed."""
+    if commitment is None or xs is None or proof is None:
+        raise ArgumentError("spartan: null argument")
+    xs, p = _batch_publics(xs)
+    _spartan_batch_shape(num_vars, dim_vars, p, len(xs))
+    t = Keccak256Transcript.from_proof(bytes(proof)) if isinstance(proof, (bytes, bytearray)) else proof
+    _check(vp.lib.lh_spartan_verify_batch(vp.h, num_vars, dim_vars, _bytes_arg(commitment), len(commitment),
+                                          _fr_array([v for x in xs for v in x]), len(xs), p, t.p))
+    if isinstance(t, Keccak256Transcript) and t.remaining():
+        raise InvalidSnark("spartan: trailing bytes in proof")
+
+
 def verify_fractional_sum_check(num_vars, claimed_p_0s, claimed_q_0s, transcript):
     """fractional_sum_check.rs:193-270, the host verifier of prove_fractional_sum_check (a claim None: the root is read)
     -> (p_0s, q_0s, p_xs, q_xs, x): the roots come back because a caller checks a relation between them."""

@@ -23,6 +23,7 @@ LH_LOGUP_COL_FR, LH_LOGUP_COL_U32 = 0, 1  # lh_logup_columns.kinds
 LH_MEMCHECK_MAX_INIT_VARS = 24  # lh_memcheck_prove: mem_vars with an initial image
 LH_SPARK_MAX_DIMS, LH_SPARK_MAX_DIM_VARS = 3, 24  # lh_spark_commit
 LH_SPARTAN_MIN_DIM_VARS, LH_SPARTAN_MAX_DIM_VARS = 2, 24  # lh_r1cs_commit
+LH_SPARTAN_BATCH_MAX_VARS = 26  # lh_spartan_verify_batch: dim_vars + batch_vars
 LH_BD_COLUMN_FR, LH_BD_COLUMN_U32 = 0, 1
 
 
@@ -448,6 +449,8 @@ SIGNATURES["lh_spartan_verify_relaxed"] = (C.c_int, [_P, _SZ, _SZ, _P, _SZ, _P, 
 SIGNATURES["lh_debug_nova_spmv2"] = (C.c_int, [_P, _P, C.c_int, _FR, _FR, C.POINTER(_FR), C.POINTER(_FR)])
 SIGNATURES["lh_debug_nova_cross_term"] = (C.c_int, [_P, _SZ, C.POINTER(_FR), C.POINTER(_FR), _FR, _FR, _FR, _FR, _FR, C.POINTER(_SZ)])
 SIGNATURES["lh_debug_nova_fold"] = (C.c_int, [_P, _SZ, _FR, _FR, _FR, _FR, _FR, _FR, _FR, _FR])
+# batched Spartan, the verifier: the public inputs instance by instance
+SIGNATURES["lh_spartan_verify_batch"] = (C.c_int, [_P, _SZ, _SZ, _P, _SZ, _FR, _SZ, _SZ, _T])
 SIGNATURES["lh_gkr_fractional_verify"] = (C.c_int, [_SZ, _SZ, C.POINTER(C.POINTER(lh_fr)), C.POINTER(C.POINTER(lh_fr)), _T,
                                                     C.POINTER(lh_fr), C.POINTER(lh_fr), C.POINTER(lh_fr), C.POINTER(lh_fr),
                                                     C.POINTER(lh_fr)])

@@ -1243,6 +1243,19 @@ lh_status lh_spartan_verify_relaxed(const lh_mkzg_vp* vp, size_t num_vars, size_
   spartan_verify_relaxed(mkzg_verifier(*vp->p), num_vars, dim_vars, commitment, commitment_len, instance, instance_len, num_public, tr);
   LH_CATCH
 }
+lh_status lh_spartan_verify_batch(const lh_mkzg_vp* vp, size_t num_vars, size_t dim_vars, const uint8_t* commitment, size_t commitment_len,
+                                  const lh_fr* x, size_t num_instances, size_t num_public, lh_transcript* t) {
+  LH_TRY
+  NEED(vp);
+  NEED(commitment);
+  NEED(x);
+  Transcript tr(t);
+  spartan_check(num_vars, dim_vars, num_public);
+  if (std::max(num_vars, spartan_batch_check(dim_vars, num_instances) + dim_vars - 1) > mkzg_vp_num_vars(*vp->p))
+    throw lh::Error(LH_ERR_INVALID_PCS_PARAM, "Too many variates of poly to verify");
+  spartan_verify_batch(mkzg_verifier(*vp->p), num_vars, dim_vars, commitment, commitment_len, (const HFr*)x, num_instances, num_public, tr);
+  LH_CATCH
+}
 lh_status lh_hyperplonk_verify(const lh_mkzg_vp* vp, const lh_hp_vparam* hvp, const lh_fr* const* instances,
                                lh_transcript* t) {
   LH_TRY

@@ -955,8 +955,24 @@ struct SpartanKeyBlob {  // the key bytes taken apart: per matrix its commitment
 SpartanKeyBlob spartan_read_key(const char* name, const uint8_t* key, size_t key_len);  // malformed: LH_ERR_INVALID_SNARK "<name>: malformed key: ..."
 void spartan_inner_verify(const PcsVerifier& pcs, size_t l, const HFr* x, size_t p, const HG1& cw, const HFr* v, Transcript& tr,
                           std::vector<HFr>& r_y, std::vector<HFr>& e);
+// its two halves, which the batch verifier (spartan_batch.cpp) calls with statements of its own: rho, the inner rounds and
+// eA, eB, eC; then e_w, the final claim over the public half x and the opening of the witness (`vars` variables, at `point`)
+struct SpartanInnerClaim {
+  HFr rho, final;
+  std::vector<HFr> r_y, e;
+};
+SpartanInnerClaim spartan_inner_rounds_verify(size_t l, const HFr* v, Transcript& tr);
+void spartan_witness_verify(const PcsVerifier& pcs, const SpartanInnerClaim& claim, size_t l, const HFr* x, size_t p, const HG1& cw,
+                            size_t vars, const HFr* point, Transcript& tr);
 void spartan_verify_matrices(const PcsVerifier& pcs, size_t n, size_t l, const SpartanKeyBlob& k, const std::vector<HFr>& r_x,
                              const std::vector<HFr>& r_y, const std::vector<HFr>& e, Transcript& tr);
+
+// ------------------------------------------------------------------ batched Spartan, the verifier (spartan_batch.cpp;
+// tests/spartan_batch_ref.py): num_instances >= 2 assignments of one key in one proof, batch_vars = ceil(log2 num_instances).
+// -> batch_vars; the limits that need no device, after spartan_check's
+size_t spartan_batch_check(size_t dim_vars, size_t num_instances);
+void spartan_verify_batch(const PcsVerifier& pcs, size_t num_vars, size_t dim_vars, const uint8_t* key, size_t key_len, const HFr* x,
+                          size_t num_instances, size_t num_public, Transcript& tr);
 
 // ------------------------------------------------------------------ Nova folding (nova.cpp; tests/nova_ref.py)
 // A relaxed instance (C_W, C_E, x), u = x[0], travels as a blob: lasso_write_commitments of [C_W, C_E] on a fresh transcript,

@@ -265,13 +265,29 @@ SpartanKeyBlob spartan_read_key(const char* name, const uint8_t* key, size_t key
   if (at != key_len) throw Error(LH_ERR_INVALID_SNARK, malformed + "wrong length");
   return k;
 }
-// the verifier's steps 5 to 8, from rho to the opening of w (cw: its commitment; v: vA, vB, vC) -> r_y and eA, eB, eC
+// the verifier's steps 5 to 8, from rho to the opening of w (cw: its commitment; v: vA, vB, vC) -> r_y and eA, eB, eC: its two
+// halves in their order
 void spartan_inner_verify(const PcsVerifier& pcs, size_t l, const HFr* x, size_t p, const HG1& cw, const HFr* v, Transcript& tr,
                           std::vector<HFr>& r_y, std::vector<HFr>& e) {
-  const HFr rho = tr.squeeze_challenge();
+  const SpartanInnerClaim claim = spartan_inner_rounds_verify(l, v, tr);
+  r_y = claim.r_y, e = claim.e;
+  spartan_witness_verify(pcs, claim, l, x, p, cw, l - 1, r_y.data(), tr);
+}
+SpartanInnerClaim spartan_inner_rounds_verify(size_t l, const HFr* v, Transcript& tr) {
+  SpartanInnerClaim claim;
+  claim.rho = tr.squeeze_challenge();
+  const HFr& rho = claim.rho;
   const std::pair<HFr, std::vector<HFr>> inner = sum_check_verify(LH_SC_EVALUATIONS, l, 2, v[0] + rho * v[1] + rho * rho * v[2], tr);
-  r_y = inner.second;
-  e = tr.read_field_elements(3);
+  claim.final = inner.first, claim.r_y = inner.second;
+  claim.e = tr.read_field_elements(3);
+  return claim;
+}
+// e_w, the inner final claim over z~(r_y) = (1 - r_y[l-1]) e_w + r_y[l-1] x~(r_y[0 .. l-1)), the opening of the witness of
+// `vars` variables at `point` (the batch verifier's: the stacked witness, at r_b || r_y[0 .. l-1))
+void spartan_witness_verify(const PcsVerifier& pcs, const SpartanInnerClaim& claim, size_t l, const HFr* x, size_t p, const HG1& cw,
+                            size_t vars, const HFr* point, Transcript& tr) {
+  const std::vector<HFr>&r_y = claim.r_y, &e = claim.e;
+  const HFr& rho = claim.rho;
   const HFr e_w = tr.read_field_element();
   // z~(r_y): the public half at a cost that follows p - x padded to 2^q, the first q coordinates, the rest of the half's
   // coordinates at their zero side
@@ -280,10 +296,10 @@ void spartan_inner_verify(const PcsVerifier& pcs, size_t l, const HFr* x, size_t
   HFr x_ry = q == 0 ? x[0] : host_table_eval(q, r_y, [&](size_t i) { return i < p ? x[i] : HFr::zero(); });
   for (size_t i = q; i + 1 < l; i++) x_ry = x_ry * (HFr::one() - r_y[i]);
   const HFr z_ry = (HFr::one() - r_y[l - 1]) * e_w + r_y[l - 1] * x_ry;
-  if (inner.first != (e[0] + rho * e[1] + rho * rho * e[2]) * z_ry)
+  if (claim.final != (e[0] + rho * e[1] + rho * rho * e[2]) * z_ry)
     throw Error(LH_ERR_INVALID_SNARK, "spartan: inner sum-check final evaluation mismatch");
   const std::vector<lh_evaluation> evs = spartan_doubled_evaluation(e_w);
-  pcs.batch_verify(l - 1, &cw, 1, r_y.data(), 1, evs.data(), evs.size(), tr);
+  pcs.batch_verify(vars, &cw, 1, point, 1, evs.data(), evs.size(), tr);
 }
 void spartan_verify_matrices(const PcsVerifier& pcs, size_t n, size_t l, const SpartanKeyBlob& k, const std::vector<HFr>& r_x,
                              const std::vector<HFr>& r_y, const std::vector<HFr>& e, Transcript& tr) {

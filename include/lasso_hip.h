@@ -817,6 +817,20 @@ lh_status lh_nova_fold_verify(size_t num_vars, size_t dim_vars, const uint8_t* c
  * instance blob in place of x.  An instance whose C_E is the identity carries no opening of E and must have vE = 0. */
 lh_status lh_spartan_verify_relaxed(const lh_mkzg_vp* vp, size_t num_vars, size_t dim_vars, const uint8_t* commitment, size_t commitment_len,
                                     const uint8_t* instance, size_t instance_len, size_t num_public, lh_transcript* t);
+/* Batched Spartan, the verifier (tests/spartan_batch_ref.py verify; host only): num_instances >= 2 assignments of
+ * ONE R1CS key in one proof.  batch_vars = ceil(log2 num_instances), K = 2^batch_vars; the instances num_instances <= i < K
+ * are zero (z = 0 satisfies every R1CS), so any count is allowed.  The assignments are stacked instance-minor, Z[i + K y], the
+ * instance index in the LOW batch_vars coordinates; one outer sum-check over batch_vars + dim_vars variables brings every
+ * instance to one r_x, one inner sum-check over the eq-weighted combination of the assignments, ONE opening of the stacked
+ * witness (batch_vars + dim_vars - 1 variables) and ONE set of three Spark openings finish it.  `commitment` are the bytes of
+ * lh_r1cs_commitment, `x` the num_instances * num_public public inputs instance by instance; the public half costs
+ * num_instances * num_public products.  Limits (LH_ERR_ARG with a message): lh_spartan_verify's; num_instances >= 2;
+ * dim_vars + batch_vars <= LH_SPARTAN_BATCH_MAX_VARS (the rows of the largest sum-check).  LH_ERR_INVALID_PCS_PARAM when
+ * max(num_vars, batch_vars + dim_vars - 1) exceeds the param; a proof that does not verify and a malformed key are
+ * LH_ERR_INVALID_SNARK "spartan: ...".  The proofs are the specification's: the library has no device prover for them yet. */
+#define LH_SPARTAN_BATCH_MAX_VARS 26
+lh_status lh_spartan_verify_batch(const lh_mkzg_vp* vp, size_t num_vars, size_t dim_vars, const uint8_t* commitment, size_t commitment_len,
+                                  const lh_fr* x, size_t num_instances, size_t num_public, lh_transcript* t);
 typedef struct lh_hp_vparam { /* HyperPlonkVerifierParam (hyperplonk.rs:57-74) */
   size_t num_vars;
   size_t num_instance_polys;
