@@ -94,6 +94,9 @@ pub struct lh_r1cs_matrix { pub d_row: *const u32, pub d_col: *const u32, pub d_
 // the trace of lh_memcheck_prove: three device columns of 2^num_vars uint32_t (cell, value before, value after)
 #[repr(C)] #[derive(Clone, Copy)]
 pub struct lh_memcheck_trace { pub d_addr: *const u32, pub d_rv: *const u32, pub d_wv: *const u32 }
+// the operations of lh_memcheck_replay: three device columns of 2^num_vars uint32_t (cell, store != 0, word to store)
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct lh_memcheck_ops { pub d_addr: *const u32, pub d_store: *const u32, pub d_val: *const u32 }
 
 pub const LH_EX_CONSTANT: u32 = 0;
 pub const LH_EX_IDENTITY: u32 = 1;
@@ -331,6 +334,15 @@ extern "C" {
     pub fn lh_debug_memcheck_witness(ctx: *mut lh_ctx, trace: *const lh_memcheck_trace, num_vars: usize, mem_vars: usize,
                                      init: *const u32, d_rt: *mut u32, d_fv: *mut u32, d_ft: *mut u32, d_m: *mut u32,
                                      out_bad: *mut i32) -> lh_status;
+    // the trace from the operations, on the device: rv, wv and the final cells (d_image, d_final: device, or null)
+    pub fn lh_memcheck_replay(ctx: *mut lh_ctx, ops: *const lh_memcheck_ops, num_vars: usize, mem_vars: usize,
+                              d_image: *const u32, d_rv: *mut u32, d_wv: *mut u32, d_final: *mut u32) -> lh_status;
+    // memory checking in segments (tests/memcheck_segment_ref.py): the image a committed device column; the verifier returns
+    // the commitments of the image and of the final values (identity = (0, 0)), each may be null
+    pub fn lh_memcheck_prove_segment(ctx: *mut lh_ctx, srs: *const lh_srs, trace: *const lh_memcheck_trace, num_vars: usize,
+                                     mem_vars: usize, d_image: *const u32, d_final: *mut u32, t: *mut lh_transcript) -> lh_status;
+    pub fn lh_memcheck_verify_segment(vp: *const lh_mkzg_vp, num_vars: usize, mem_vars: usize, t: *mut lh_transcript,
+                                      image_commitment: *mut G1Affine, final_commitment: *mut G1Affine) -> lh_status;
     // Spark (tests/spark_ref.py): commit a sparse polynomial once - 2^num_vars entries (d_dims[j][k] < 2^dim_vars, d_val[k]),
     // device columns - and prove its evaluations at any number of points; the handle owns its device memory
     pub fn lh_spark_commit(ctx: *mut lh_ctx, srs: *const lh_srs, num_vars: usize, dim_vars: usize, num_dims: usize,

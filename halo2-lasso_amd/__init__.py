@@ -1765,6 +1765,102 @@ def memcheck_witness(ctx, addr, rv, wv, mem_vars, init=None, num_vars=None):
     return out[0], out[1], out[2], out[3], bool(bad.value)
 
 
+def _memcheck_shape(num_vars, mem_vars):
+    """the limits without a public image (lh_memcheck_replay, the segment proofs): ArgumentError before the device is touched"""
+    if not (isinstance(num_vars, int) and 1 <= num_vars < 31):
+        raise ArgumentError("memcheck: num_vars out of range (1 to 30)")
+    if not (isinstance(mem_vars, int) and 1 <= mem_vars < 31):
+        raise ArgumentError("memcheck: mem_vars out of range (1 to 30)")
+
+
+def _u32_ptr(col, words, what):
+    """a device column of at least `words` uint32 (DeviceBuffer or U32Column; a raw pointer is taken as it is) -> c_void_p"""
+    buf = getattr(col, "buf", col)
+    if getattr(buf, "nbytes", 4 * words) < 4 * words:
+        raise ArgumentError("memcheck: %s needs %d bytes" % (what, 4 * words))
+    return C.c_void_p(col.ptr if hasattr(col, "ptr") else col)
+
+
+def memcheck_replay(ctx, addr, store, val, mem_vars, image=None, num_vars=None):
+    """The trace from the operations, on the device (lh_memcheck_replay): addr / store / val are u32 DeviceBuffers or
+    U32Columns of 2^num_vars entries - operation i stores val[i] when store[i] != 0, else it loads -, image a u32 device
+    column of 2^mem_vars words or None (all zero).  -> (rv, wv, final) as U32Columns on the device (final: mem_vars
+    variables): rv[i] is the word of the latest earlier store to addr[i], or the image's; wv[i] = val[i] for a store, rv[i] for
+    a load; final[a] the cell's word after the trace.  (addr, rv, wv) is what memcheck_prove and memcheck_prove_segment take.
+    An address >= 2^mem_vars: InvalidSnark "Invalid memory trace"."""
+    if any(c is None for c in (addr, store, val)):
+        raise ArgumentError("memcheck: the operations are three columns, addr, store and val")
+    if num_vars is None:
+        if not hasattr(addr, "num_vars"):
+            raise ArgumentError("memcheck: num_vars is needed with raw device buffers")
+        num_vars = addr.num_vars
+    _memcheck_shape(num_vars, mem_vars)
+    if any(getattr(c, "num_vars", num_vars) != num_vars for c in (addr, store, val)):
+        raise ArgumentError("memcheck: operation columns of 2^num_vars entries")
+    ops = _ffi.lh_memcheck_ops()
+    ops.d_addr, ops.d_store, ops.d_val = [C.cast(_u32_ptr(c, 1 << num_vars, "an operation column"), C.POINTER(C.c_uint32))
+                                          for c in (addr, store, val)]
+    d_image = _u32_ptr(image, 1 << mem_vars, "the image") if image is not None else None
+    rv, wv, final = ctx.alloc(4 << num_vars), ctx.alloc(4 << num_vars), ctx.alloc(4 << mem_vars)
+    try:
+        _check(ctx.lib.lh_memcheck_replay(ctx.h, C.byref(ops), num_vars, mem_vars, d_image, rv.ptr, wv.ptr, final.ptr))
+    except Exception:
+        for b in (rv, wv, final):
+            b.free()
+        raise
+    return U32Column(rv, num_vars), U32Column(wv, num_vars), U32Column(final, mem_vars)
+
+
+def memcheck_prove_segment(pp, addr, rv, wv, mem_vars, image, transcript, num_vars=None, final=None):
+    """One segment of a memory-checking chain over multilinear KZG (tests/memcheck_segment_ref.py): memcheck_prove with the
+    image as a COMMITTED column - `image` is a u32 device column of 2^mem_vars words, never None - so that the next segment
+    can start from this one's final values.  final: a u32 device column of 2^mem_vars words that receives them (None: one is
+    allocated).  Appends the proof; -> the final values as a U32Column on the device."""
+    trace, num_vars = _memcheck_trace(addr, rv, wv, num_vars)
+    _memcheck_shape(num_vars, mem_vars)
+    if image is None:
+        raise ArgumentError("memcheck: a segment needs its image, a device column of 2^mem_vars words")
+    d_image = _u32_ptr(image, 1 << mem_vars, "the image")
+    out = final if final is not None else U32Column(pp.ctx.alloc(4 << mem_vars), mem_vars)
+    d_final = _u32_ptr(out, 1 << mem_vars, "the final values")
+    _check(pp.ctx.lib.lh_memcheck_prove_segment(pp.ctx.h, pp.h, C.byref(trace), num_vars, mem_vars, d_image, d_final, transcript.p))
+    return out
+
+
+def memcheck_verify_segment(vp, num_vars, mem_vars, transcript):
+    """Verifier of memcheck_prove_segment (host only) -> (image commitment, final commitment) as read from the proof: affine
+    (x, y), None for the identity (an all-zero column).  A Keccak256Transcript must be fully consumed."""
+    _memcheck_shape(num_vars, mem_vars)
+    iv, fv = lh_g1(), lh_g1()
+    _check(vp.lib.lh_memcheck_verify_segment(vp.h, num_vars, mem_vars, transcript.p, C.byref(iv), C.byref(fv)))
+    if isinstance(transcript, Keccak256Transcript) and transcript.remaining():
+        raise InvalidSnark("trailing bytes in proof")
+    return g1_from_bytes(bytes(iv)), g1_from_bytes(bytes(fv))
+
+
+def memcheck_verify_chain(vp, mem_vars, segments):
+    """A chain of segment proofs over one memory: segments = [(num_vars, proof bytes), ..] in order.  Verifies every segment
+    and requires segment k + 1's image commitment to equal segment k's final commitment -> (first image commitment, last
+    final commitment).  A column's commitment depends on the number of variables it is committed over, so segments that
+    differ in max(num_vars, mem_vars) can never link: ArgumentError."""
+    segments = list(segments)
+    if not segments:
+        raise ArgumentError("memcheck chain: no segment")
+    for num_vars, _ in segments:
+        _memcheck_shape(num_vars, mem_vars)
+    if len({max(num_vars, mem_vars) for num_vars, _ in segments}) != 1:
+        raise ArgumentError("memcheck chain: the segments differ in max(num_vars, mem_vars), their commitments cannot link")
+    first = last = None
+    for k, (num_vars, proof) in enumerate(segments):
+        iv, fv = memcheck_verify_segment(vp, num_vars, mem_vars, Keccak256Transcript.from_proof(proof))
+        if k == 0:
+            first = iv
+        elif iv != last:
+            raise InvalidSnark("memcheck chain: segment %d does not start where segment %d ends" % (k, k - 1))
+        last = fv
+    return first, last
+
+
 # ------------------------------------------------------------------ Spark: sparse polynomial commitment (lh_spark_commit)
 def _spark_shape(num_vars, dim_vars, num_dims):
     """ArgumentError before anything is marshalled or the device is touched"""

@@ -68,6 +68,10 @@ class lh_memcheck_trace(C.Structure):
     _fields_ = [("d_addr", C.POINTER(C.c_uint32)), ("d_rv", C.POINTER(C.c_uint32)), ("d_wv", C.POINTER(C.c_uint32))]
 
 
+class lh_memcheck_ops(C.Structure):
+    _fields_ = [("d_addr", C.POINTER(C.c_uint32)), ("d_store", C.POINTER(C.c_uint32)), ("d_val", C.POINTER(C.c_uint32))]
+
+
 class lh_r1cs_matrix(C.Structure):
     _fields_ = [("d_row", C.POINTER(C.c_uint32)), ("d_col", C.POINTER(C.c_uint32)), ("d_val", C.POINTER(lh_fr))]
 
@@ -425,6 +429,10 @@ SIGNATURES["lh_memcheck_prove"] = (C.c_int, [_P, _P, C.POINTER(lh_memcheck_trace
 SIGNATURES["lh_memcheck_verify"] = (C.c_int, [_P, _SZ, _SZ, C.POINTER(C.c_uint32), _T])
 SIGNATURES["lh_debug_memcheck_witness"] = (C.c_int, [_P, C.POINTER(lh_memcheck_trace), _SZ, _SZ, C.POINTER(C.c_uint32), _P, _P, _P,
                                                      _P, C.POINTER(C.c_int)])
+# (d_image, d_rv, d_wv, d_final: device pointers)
+SIGNATURES["lh_memcheck_replay"] = (C.c_int, [_P, C.POINTER(lh_memcheck_ops), _SZ, _SZ, _P, _P, _P, _P])
+SIGNATURES["lh_memcheck_prove_segment"] = (C.c_int, [_P, _P, C.POINTER(lh_memcheck_trace), _SZ, _SZ, _P, _P, _T])
+SIGNATURES["lh_memcheck_verify_segment"] = (C.c_int, [_P, _SZ, _SZ, _T, C.POINTER(lh_g1), C.POINTER(lh_g1)])
 # Spark: the handle is an opaque pointer; lh_spark_free returns nothing
 SIGNATURES["lh_spark_commit"] = (C.c_int, [_P, _P, _SZ, _SZ, _SZ, _P, _P, C.POINTER(_P)])
 SIGNATURES["lh_spark_commitment"] = (C.c_int, [_P, _P, C.POINTER(_SZ)])

@@ -718,6 +718,29 @@ lh_status lh_memcheck_prove(lh_ctx* ctx, const lh_srs* srs, const lh_memcheck_tr
   memcheck_prove(ctx->c, mkzg_pcs(ctx->c, srs->s), *trace, num_vars, mem_vars, init, tr);
   LH_CATCH
 }
+lh_status lh_memcheck_replay(lh_ctx* ctx, const lh_memcheck_ops* ops, size_t num_vars, size_t mem_vars, const uint32_t* d_image,
+                             uint32_t* d_rv, uint32_t* d_wv, uint32_t* d_final) {
+  LH_TRY
+  memcheck_check(num_vars, mem_vars, false);  // (the shape first: refused before the device is touched)
+  NEED_CTX(ctx);
+  NEED(ops);
+  NEED(d_rv);
+  NEED(d_wv);
+  memcheck_replay(ctx->c, *ops, num_vars, mem_vars, d_image, d_rv, d_wv, d_final);
+  LH_CATCH
+}
+lh_status lh_memcheck_prove_segment(lh_ctx* ctx, const lh_srs* srs, const lh_memcheck_trace* trace, size_t num_vars, size_t mem_vars,
+                                    const uint32_t* d_image, uint32_t* d_final, lh_transcript* t) {
+  LH_TRY
+  memcheck_segment_check(num_vars, mem_vars);
+  NEED_CTX(ctx);
+  NEED(srs);
+  NEED(trace);
+  NEED(d_image);
+  Transcript tr(t);
+  memcheck_prove_segment(ctx->c, mkzg_pcs(ctx->c, srs->s), *trace, num_vars, mem_vars, d_image, d_final, tr);
+  LH_CATCH
+}
 // ---------------------------------------------------------------- Spark: commit a sparse polynomial once, open it many times
 lh_status lh_spark_commit(lh_ctx* ctx, const lh_srs* srs, size_t num_vars, size_t dim_vars, size_t num_dims,
                           const uint32_t* const* d_dims, const lh_fr* d_val, lh_spark_poly** out) {
@@ -1187,6 +1210,19 @@ lh_status lh_memcheck_verify(const lh_mkzg_vp* vp, size_t num_vars, size_t mem_v
   if (memcheck_check(num_vars, mem_vars, init != nullptr) > mkzg_vp_num_vars(*vp->p))
     throw lh::Error(LH_ERR_INVALID_PCS_PARAM, "Too many variates of poly to verify");
   memcheck_verify(mkzg_verifier(*vp->p), num_vars, mem_vars, init, tr);
+  LH_CATCH
+}
+lh_status lh_memcheck_verify_segment(const lh_mkzg_vp* vp, size_t num_vars, size_t mem_vars, lh_transcript* t,
+                                     lh_g1* image_commitment, lh_g1* final_commitment) {
+  LH_TRY
+  NEED(vp);
+  Transcript tr(t);
+  if (memcheck_segment_check(num_vars, mem_vars) > mkzg_vp_num_vars(*vp->p))
+    throw lh::Error(LH_ERR_INVALID_PCS_PARAM, "Too many variates of poly to verify");
+  HG1 iv, fv;
+  memcheck_verify_segment(mkzg_verifier(*vp->p), num_vars, mem_vars, tr, &iv, &fv);
+  if (image_commitment) memcpy(image_commitment, &iv, 64);
+  if (final_commitment) memcpy(final_commitment, &fv, 64);
   LH_CATCH
 }
 lh_status lh_spark_verify(const lh_mkzg_vp* vp, size_t num_vars, size_t dim_vars, size_t num_dims, const uint8_t* commitment,

@@ -900,6 +900,14 @@ struct MemcheckRangeLeaves {
   Fr *p0_up, *q0_up, *p1_up, *q1_up;
 };
 void k_memcheck_range_leaves(Ctx&, const MemcheckRangeLeaves&, size_t num_vars, bool up, const Fr& delta);
+// The replay of 2^num_vars operations (addr, store != 0, val: device u32 columns) over 2^mem_vars cells whose image is d_image
+// (device; null: all zero): rv[i] = the word of the latest earlier store to addr[i], or the image's; wv[i] = store ? val : rv;
+// fin[a] (null: not wanted) = the cell's word after the trace.  The stable sort of k_memcheck_trace, then an exclusive
+// segmented scan over the sorted order in tiles of 2048 (three launches: tiles, the tiles' carries, the open operations).
+// false (after ONE flag readback): an address >= 2^mem_vars - the outputs are then unspecified, nothing is out of bounds.
+// Launch record "memcheck_replay", 2^num_vars items, algorithmic bytes 36 * 2^num_vars + (12 | 8 | 0) * 2^mem_vars
+bool k_memcheck_replay(Ctx&, const uint32_t* addr, const uint32_t* store, const uint32_t* val, size_t num_vars, size_t mem_vars,
+                       const uint32_t* d_image, uint32_t* rv, uint32_t* wv, uint32_t* fin);
 
 // ------------------------------------------------------------------ Spark (kernels_spark.hip; spark.cpp, tests/spark_ref.py)
 constexpr int SPARK_MAX_DIMS = 3;

@@ -881,6 +881,16 @@ void memcheck_verify(const PcsVerifier& pcs, size_t num_vars, size_t mem_vars, c
 // the witness kernels alone (lh_debug_memcheck_witness): false when the trace is invalid
 bool memcheck_witness(Ctx&, const lh_memcheck_trace& trace, size_t num_vars, size_t mem_vars, const uint32_t* init, uint32_t* d_rt,
                       uint32_t* d_fv, uint32_t* d_ft, uint32_t* d_m);
+// the trace's rv and wv (and the final cells; null: not wanted) from the operations, on the device; d_image null: all zero
+void memcheck_replay(Ctx&, const lh_memcheck_ops& ops, size_t num_vars, size_t mem_vars, const uint32_t* d_image, uint32_t* d_rv,
+                     uint32_t* d_wv, uint32_t* d_final);
+// Segment proofs (tests/memcheck_segment_ref.py): the image a committed DEVICE column, never null; d_final (device, or null)
+// receives the final values - the next segment's image.  The verifier returns the commitments of image and final values.
+size_t memcheck_segment_check(size_t num_vars, size_t mem_vars);
+void memcheck_prove_segment(Ctx&, const Pcs&, const lh_memcheck_trace& trace, size_t num_vars, size_t mem_vars,
+                            const uint32_t* d_image, uint32_t* d_final, Transcript& tr);
+void memcheck_verify_segment(const PcsVerifier& pcs, size_t num_vars, size_t mem_vars, Transcript& tr, HG1* image_commitment,
+                             HG1* final_commitment);
 
 // ------------------------------------------------------------------ Spark (spark.cpp; tests/spark_ref.py)
 // A committed sparse polynomial: 2^n entries (dim_0 .. dim_{c-1}, val) with indices below 2^l.  Owns ONE device block outside

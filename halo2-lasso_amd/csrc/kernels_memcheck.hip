@@ -1,6 +1,7 @@
 // Device half of the read-write memory-checking argument (memcheck.cpp; tests/memcheck_ref.py): the witness of a RAM trace
 // (previous-write times, final cells, the multiplicities of the time differences) and the leaves of its two GKR arguments
-// with the level above them.  Streaming kernels over 32-bit columns; a leaf is three 8-multiply-add terms into a wide
+// with the level above them, and the replay that derives a trace's read values from its stores (a segmented scan over the
+// sorted operations; tests/memcheck_segment_ref.py is the specification of the segment proofs it feeds).  Streaming kernels over 32-bit columns; a leaf is three 8-multiply-add terms into a wide
 // accumulator and ONE Montgomery reduction (wide.cuh), an Fr leaves as two dwordx4.
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -251,6 +252,232 @@ void k_memcheck_range_leaves(Ctx& c, const MemcheckRangeLeaves& a, size_t num_va
   const Fr o1 = prescale_r(Fr::one());
   if (up) hipLaunchKernelGGL(memcheck_range_leaves_kernel<true>, dim3(cu_grid(c, half)), dim3(256), 0, c.stream, a, half, delta, o1);
   else hipLaunchKernelGGL(memcheck_range_leaves_kernel<false>, dim3(cu_grid(c, half)), dim3(256), 0, c.stream, a, half, delta, o1);
+}
+
+// ------------------------------------------------------------------ 5. the replay: read values from stores (lh_memcheck_replay)
+// The operations sorted stably by cell, as for the witness above.  The value an operation reads is an EXCLUSIVE SEGMENTED SCAN
+// over the sorted order: segments are the runs of one address, the operator is "the right operand wins if it is a store", the
+// identity the cell's image word.  What the scan carries over a range of sorted operations is a ReplayState: the key of the
+// range's last segment, whether that segment holds a store inside the range (HAS) and the last such store's word, and whether
+// the range is ONE segment (SPAN) - a range that is SPAN and not HAS is transparent: joined to the right of another state of
+// the same key it changes nothing, so a carry passes through any number of store-free tiles of a hot cell.
+//
+// The shape of spartan_spmv (spmv.cuh): a workgroup of 256 lanes takes a tile of REPLAY_TILE sorted operations, lane t the run
+// of REPLAY_RUN consecutive ones from 8 t; the lanes' states are scanned over wave shuffles, the four waves' ends joined in
+// LDS.  An operation whose value the tile knows - an earlier store of its segment inside the tile, or a segment that begins
+// inside the tile - is written at once: rv[p], wv[p] scattered to its position p, final[a] by the last operation of a segment.
+// The others are OPEN: the leading operations of the tile's first segment up to and including its first store, open_len of
+// them.  memcheck_replay_carry_kernel scans the tiles' states (one workgroup, the same block scan, 2048 tiles per turn) and
+// memcheck_replay_open_kernel writes the open operations from their tile's carry.  No atomics; every word is written once.
+// An address >= cells sets *bad and reads no image word and writes no final cell (its positions p are in range: rv, wv).
+constexpr int REPLAY_RUN = 8;
+constexpr int REPLAY_TILE = 256 * REPLAY_RUN;
+static_assert(REPLAY_TILE <= 4096, "tests/test_gpu_memcheck_replay.py places its stores around tiles of at most 4096");
+enum : uint32_t { RP_HAS = 1u, RP_SPAN = 2u, RP_EMPTY = 4u };
+struct ReplayState {
+  uint32_t key, val, flags;
+};
+__device__ __forceinline__ ReplayState replay_empty() { return ReplayState{0u, 0u, RP_EMPTY}; }
+__device__ __forceinline__ ReplayState replay_item(uint32_t key, bool store, uint32_t val) {
+  return ReplayState{key, val, RP_SPAN | (store ? RP_HAS : 0u)};
+}
+// (by value and select by select on the words: a choice between the two states as objects goes through scratch)
+__device__ __forceinline__ ReplayState replay_join(const ReplayState l, const ReplayState r) {
+  // r goes on with l's last segment and ends in it; else r's last segment begins inside r, or at its first operation
+  const bool on = (r.flags & RP_SPAN) && r.key == l.key;
+  uint32_t key = r.key;
+  uint32_t val = on && !(r.flags & RP_HAS) ? l.val : r.val;
+  uint32_t flags = on ? (l.flags & (RP_HAS | RP_SPAN)) | (r.flags & RP_HAS) : r.flags & RP_HAS;
+  if (l.flags & RP_EMPTY) val = r.val, flags = r.flags;
+  if (r.flags & RP_EMPTY) key = l.key, val = l.val, flags = l.flags;
+  return ReplayState{key, val, flags};
+}
+__device__ __forceinline__ ReplayState replay_shfl_up(const ReplayState& s, int off) {
+  return ReplayState{__shfl_up(s.key, off, 64), __shfl_up(s.val, off, 64), __shfl_up(s.flags, off, 64)};
+}
+__device__ __forceinline__ uint4 replay_pack(const ReplayState& s) { return make_uint4(s.key, s.val, s.flags, 0u); }
+__device__ __forceinline__ ReplayState replay_unpack(const uint4& u) { return ReplayState{u.x, u.y, u.z}; }
+// The state of everything the lanes below this one hold (EMPTY for lane 0 of the workgroup), *total: of all 256 lanes.
+// Reached by whole workgroups (two barriers); `ends` - the four waves' ends, field by field - is free again on return.
+__device__ __forceinline__ ReplayState replay_block_scan(ReplayState s, uint32_t (*ends)[4], ReplayState* total) {
+  const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const ReplayState o = replay_shfl_up(s, off);
+    if (lane >= off) s = replay_join(o, s);
+  }
+  ReplayState x = replay_shfl_up(s, 1);
+  if (lane == 0) x.key = 0u, x.val = 0u, x.flags = RP_EMPTY;
+  if (lane == 63) ends[0][wave] = s.key, ends[1][wave] = s.val, ends[2][wave] = s.flags;
+  __syncthreads();
+  ReplayState before = replay_empty(), all = replay_empty();
+#pragma unroll
+  for (int w = 0; w < 4; w++) {
+    const ReplayState e = {ends[0][w], ends[1][w], ends[2][w]};
+    if (w < wave) before = replay_join(before, e);
+    all = replay_join(all, e);
+  }
+  __syncthreads();
+  *total = all;
+  return replay_join(before, x);
+}
+// what an operation on cell `key` reads, given the state of everything before it in the scanned range: the last store's
+// word (true), or nothing known (false: the identity, or - open - the range's carry)
+__device__ __forceinline__ bool replay_hit(const ReplayState& x, uint32_t key) {
+  return !(x.flags & RP_EMPTY) && x.key == key && (x.flags & RP_HAS);
+}
+__device__ __forceinline__ bool replay_open(const ReplayState& x, uint32_t key) {
+  return (x.flags & RP_EMPTY) || (x.key == key && (x.flags & (RP_HAS | RP_SPAN)) == RP_SPAN);
+}
+
+__global__ __launch_bounds__(256) void memcheck_replay_tile_kernel(
+    const uint32_t* __restrict__ skey, const uint32_t* __restrict__ sidx, const uint32_t* __restrict__ store,
+    const uint32_t* __restrict__ val, const uint32_t* __restrict__ image, size_t n, size_t cells, size_t tiles,
+    uint32_t* __restrict__ rv, uint32_t* __restrict__ wv, uint32_t* __restrict__ fin, uint4* __restrict__ tile_state,
+    uint32_t* __restrict__ open_len, uint32_t* __restrict__ bad) {
+  __shared__ uint32_t ends[3][4];
+  __shared__ uint32_t opens[4];
+  const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
+  for (size_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {  // (uniform per workgroup: the barriers are reached by all)
+    const size_t i0 = tile * REPLAY_TILE + (size_t)threadIdx.x * REPLAY_RUN;
+    uint32_t a[REPLAY_RUN], p[REPLAY_RUN], v[REPLAY_RUN], st[REPLAY_RUN];
+    if (i0 + REPLAY_RUN <= n) {  // (the arena's blocks are 256-byte aligned, a run's offset 32-byte)
+#pragma unroll
+      for (int k = 0; k < REPLAY_RUN; k += 4) {
+        const uint4 ka = *reinterpret_cast<const uint4*>(skey + i0 + k), kp = *reinterpret_cast<const uint4*>(sidx + i0 + k);
+        a[k] = ka.x, a[k + 1] = ka.y, a[k + 2] = ka.z, a[k + 3] = ka.w;
+        p[k] = kp.x, p[k + 1] = kp.y, p[k + 2] = kp.z, p[k + 3] = kp.w;
+      }
+    } else {  // (past the end: dead operations behind every live one - they are before nobody, and write nothing)
+#pragma unroll
+      for (int k = 0; k < REPLAY_RUN; k++) {
+        const bool live = i0 + k < n;
+        a[k] = live ? skey[i0 + k] : 0u, p[k] = live ? sidx[i0 + k] : 0u;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < REPLAY_RUN; k++) {
+      const bool live = i0 + k < n;
+      st[k] = live ? store[p[k]] : 0u;
+      v[k] = live ? val[p[k]] : 0u;
+    }
+    const uint32_t next = i0 + REPLAY_RUN < n ? skey[i0 + REPLAY_RUN] : 0u;  // (read only where there is a next operation)
+    ReplayState s = replay_empty();
+#pragma unroll
+    for (int k = 0; k < REPLAY_RUN; k++) s = replay_join(s, replay_item(a[k], st[k] != 0u, v[k]));
+    ReplayState total;
+    ReplayState x = replay_block_scan(s, ends, &total);
+    uint32_t nopen = 0u;
+#pragma unroll
+    for (int k = 0; k < REPLAY_RUN; k++) {
+      const size_t i = i0 + k;
+      if (i < n) {
+        const bool inside = a[k] < cells;
+        if (!inside) *bad = 1u;
+        if (replay_open(x, a[k])) {
+          nopen++;
+        } else {
+          const uint32_t r = replay_hit(x, a[k]) ? x.val : (inside && image ? image[a[k]] : 0u);
+          const uint32_t w = st[k] ? v[k] : r;
+          rv[p[k]] = r, wv[p[k]] = w;
+          const uint32_t after = k + 1 < REPLAY_RUN ? a[(k + 1) % REPLAY_RUN] : next;
+          const bool last = i + 1 == n || after != a[k];
+          if (last && inside && fin) fin[a[k]] = w;
+        }
+      }
+      x = replay_join(x, replay_item(a[k], st[k] != 0u, v[k]));
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) nopen += __shfl_xor(nopen, off, 64);
+    if (lane == 0) opens[wave] = nopen;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      open_len[tile] = opens[0] + opens[1] + opens[2] + opens[3];
+      tile_state[tile] = replay_pack(total);
+    }
+    __syncthreads();  // (opens is overwritten by the next turn)
+  }
+}
+// carry[t] = the state of every operation before tile t (EMPTY for tile 0): one workgroup, REPLAY_TILE tiles per turn
+__global__ __launch_bounds__(256) void memcheck_replay_carry_kernel(const uint4* __restrict__ tile_state, size_t tiles,
+                                                                    uint4* __restrict__ carry) {
+  __shared__ uint32_t ends[3][4];
+  ReplayState run = replay_empty();
+  for (size_t base = 0; base < tiles; base += REPLAY_TILE) {
+    const size_t t0 = base + (size_t)threadIdx.x * REPLAY_RUN;
+    uint32_t sk[REPLAY_RUN], sv[REPLAY_RUN], sf[REPLAY_RUN];
+    ReplayState agg = replay_empty();
+#pragma unroll
+    for (int k = 0; k < REPLAY_RUN; k++) {
+      sk[k] = 0u, sv[k] = 0u, sf[k] = RP_EMPTY;  // (past the last tile)
+      if (t0 + k < tiles) {
+        const uint4 u = tile_state[t0 + k];
+        sk[k] = u.x, sv[k] = u.y, sf[k] = u.z;
+      }
+      agg = replay_join(agg, ReplayState{sk[k], sv[k], sf[k]});
+    }
+    ReplayState total;
+    ReplayState x = replay_join(run, replay_block_scan(agg, ends, &total));
+#pragma unroll
+    for (int k = 0; k < REPLAY_RUN; k++) {
+      if (t0 + k < tiles) carry[t0 + k] = replay_pack(x);
+      x = replay_join(x, ReplayState{sk[k], sv[k], sf[k]});
+    }
+    run = replay_join(run, total);
+  }
+}
+// the open operations of every tile: all on the tile's first cell, all loads but perhaps the last one
+__global__ __launch_bounds__(256) void memcheck_replay_open_kernel(
+    const uint32_t* __restrict__ skey, const uint32_t* __restrict__ sidx, const uint32_t* __restrict__ store,
+    const uint32_t* __restrict__ val, const uint32_t* __restrict__ image, size_t n, size_t cells, size_t tiles,
+    const uint4* __restrict__ carry, const uint32_t* __restrict__ open_len, uint32_t* __restrict__ rv, uint32_t* __restrict__ wv,
+    uint32_t* __restrict__ fin) {
+  for (size_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const size_t base = tile * REPLAY_TILE;
+    const uint32_t a = skey[base], len = open_len[tile];
+    const bool inside = a < cells;
+    const ReplayState c = replay_unpack(carry[tile]);
+    const uint32_t r = replay_hit(c, a) ? c.val : (inside && image ? image[a] : 0u);
+    for (uint32_t j = threadIdx.x; j < len; j += blockDim.x) {
+      const size_t i = base + j;
+      const uint32_t p = sidx[i];
+      const uint32_t w = store[p] != 0u ? val[p] : r;
+      rv[p] = r, wv[p] = w;
+      if (fin && inside && (i + 1 == n || skey[i + 1] != a)) fin[a] = w;
+    }
+  }
+}
+bool k_memcheck_replay(Ctx& c, const uint32_t* addr, const uint32_t* store, const uint32_t* val, size_t num_vars, size_t mem_vars,
+                       const uint32_t* d_image, uint32_t* rv, uint32_t* wv, uint32_t* fin) {
+  LH_REQUIRE(num_vars >= 1 && num_vars < 31 && mem_vars >= 1 && mem_vars < 31, LH_ERR_ARG, "memcheck_replay: bad shape");
+  LH_REQUIRE(addr && store && val && rv && wv, LH_ERR_ARG, "memcheck_replay: null column");
+  const size_t n = (size_t)1 << num_vars, cells = (size_t)1 << mem_vars, tiles = (n + REPLAY_TILE - 1) / REPLAY_TILE;
+  // algorithmic bytes: the sort reads the addresses and writes (key, position) pairs (4 + 8), the scan reads the pairs (8), gathers
+  // store[p], val[p] (8) and scatters rv[p], wv[p] (8); the final cells are pre-filled (read 4 with an image, write 4) and the
+  // touched ones rewritten (4).  (Not counted: 32 B per tile of states and carries, the second visit of the open operations.)
+  ProfScope ps(c, "memcheck_replay", 36.0 * n + (fin ? (d_image ? 12.0 : 8.0) * cells : 0.0), 0.0, (double)n);
+  ArenaScope scope(c.arena);  // (everything below is queued on the ctx's stream: the next user of this memory comes behind it)
+  uint32_t* skey = c.arena.alloc_n<uint32_t>(n);
+  uint32_t* sidx = c.arena.alloc_n<uint32_t>(n);
+  uint4* tile_state = c.arena.alloc_n<uint4>(tiles);
+  uint4* carry = c.arena.alloc_n<uint4>(tiles);
+  uint32_t* open_len = c.arena.alloc_n<uint32_t>(tiles);
+  uint32_t* bad = c.arena.alloc_n<uint32_t>(1);
+  LH_HIP(hipMemsetAsync(bad, 0, sizeof(uint32_t), c.stream));
+  if (fin) {
+    if (d_image) LH_HIP(hipMemcpyAsync(fin, d_image, cells * sizeof(uint32_t), hipMemcpyDeviceToDevice, c.stream));
+    else LH_HIP(hipMemsetAsync(fin, 0, cells * sizeof(uint32_t), c.stream));
+  }
+  sort_pairs_u32(c, addr, skey, nullptr, sidx, n, (unsigned)mem_vars);  // (no values given: the positions)
+  const unsigned grid = cu_grid(c, tiles, 1);
+  hipLaunchKernelGGL(memcheck_replay_tile_kernel, dim3(grid), dim3(256), 0, c.stream, skey, sidx, store, val, d_image, n, cells,
+                     tiles, rv, wv, fin, tile_state, open_len, bad);
+  hipLaunchKernelGGL(memcheck_replay_carry_kernel, dim3(1), dim3(256), 0, c.stream, tile_state, tiles, carry);
+  hipLaunchKernelGGL(memcheck_replay_open_kernel, dim3(grid), dim3(256), 0, c.stream, skey, sidx, store, val, d_image, n, cells,
+                     tiles, carry, open_len, rv, wv, fin);
+  uint32_t h_bad = 0;
+  c.d2h(&h_bad, bad, sizeof(uint32_t));  // the one flag readback
+  return h_bad == 0;
 }
 
 }  // namespace lh

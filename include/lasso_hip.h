@@ -377,6 +377,33 @@ lh_status lh_memcheck_prove(lh_ctx*, const lh_srs*, const lh_memcheck_trace*, si
                             const uint32_t* init /* host, 2^mem_vars, or NULL */, lh_transcript* t);
 /* (lh_memcheck_verify: with the verifiers below; lh_debug_memcheck_witness: with the debug entries) */
 
+/* The trace from the operations, on the device.  A front end knows (address, load or store, stored word) per
+ * operation: operation i is a store of d_val[i] when d_store[i] != 0, otherwise a load (d_val[i] is ignored).  Written:
+ *   d_rv[i]    the word stored by the latest earlier store to d_addr[i], or d_image[d_addr[i]] when there is none
+ *   d_wv[i]    d_store[i] ? d_val[i] : d_rv[i]
+ *   d_final[a] the word of cell a after the trace (NULL: not wanted)
+ * (d_addr, d_rv, d_wv) is then the trace lh_memcheck_prove and lh_memcheck_prove_segment take.  d_image is DEVICE memory,
+ * 2^mem_vars words, or NULL for an all-zero image.  Limits: 1 <= num_vars < 31, 1 <= mem_vars < 31, no NULL column
+ * (LH_ERR_ARG).  An address >= 2^mem_vars: LH_ERR_INVALID_SNARK "Invalid memory trace" (one flag readback; the outputs are
+ * then unspecified, the ctx stays usable).  Nothing else can be invalid. */
+typedef struct lh_memcheck_ops {
+  const uint32_t *d_addr, *d_store, *d_val; /* device, 2^num_vars each */
+} lh_memcheck_ops;
+lh_status lh_memcheck_replay(lh_ctx*, const lh_memcheck_ops*, size_t num_vars, size_t mem_vars,
+                             const uint32_t* d_image /* device, 2^mem_vars, or NULL = all zero */, uint32_t* d_rv, uint32_t* d_wv,
+                             uint32_t* d_final /* device, 2^mem_vars, or NULL */);
+
+/* Memory checking in segments (tests/memcheck_segment_ref.py): the argument above with the image as a
+ * COMMITTED column, so that a proof can start from the memory another proof ended in.  d_image is DEVICE memory, 2^mem_vars
+ * words, never NULL; d_final (device, 2^mem_vars words, or NULL; it may be d_image itself, which is overwritten behind the
+ * proof's last read of it) receives the final values fv - the next segment's image, without a host trip.  The proof commits eight columns, addr, rv, wv, iv, fv, rt, ft, m; its header differs from
+ * lh_memcheck_prove's, so neither verifier takes the other's proof.  The verifier folds no image: 1 <= mem_vars < 31 and
+ * the SRS are the limits; everything else is lh_memcheck_prove's.  A chain of segments is consistent when every segment
+ * verifies and segment k + 1's image commitment (lh_memcheck_verify_segment) equals segment k's final commitment; a column's
+ * commitment depends on nv = max(num_vars, mem_vars), so the segments of a chain share nv. */
+lh_status lh_memcheck_prove_segment(lh_ctx*, const lh_srs*, const lh_memcheck_trace*, size_t num_vars, size_t mem_vars,
+                                    const uint32_t* d_image, uint32_t* d_final, lh_transcript* t);
+
 /* Spark (Lasso paper §4; the sparse commitment of Spartan): commit a sparse multilinear polynomial ONCE, prove its
  * evaluations at any number of points.  D in num_dims * dim_vars variables is given by 2^num_vars entries
  * (d_dims[0][k], .., d_dims[num_dims-1][k], d_val[k]): DEVICE columns uint32_t[2^num_vars] with values < 2^dim_vars and a
@@ -793,6 +820,13 @@ lh_status lh_logup_gkr_verify(const lh_mkzg_vp* vp, const lh_logup_lookup* looku
  * LH_ERR_INVALID_SNARK whichever piece finds it out.  The image's multilinear extension is evaluated here, 2^mem_vars field
  * operations. */
 lh_status lh_memcheck_verify(const lh_mkzg_vp* vp, size_t num_vars, size_t mem_vars, const uint32_t* init, lh_transcript* t);
+/* the verifier of lh_memcheck_prove_segment (tests/memcheck_segment_ref.py verify; host only; no work of order 2^mem_vars).
+ * On LH_OK *image_commitment and *final_commitment (either may be NULL) are the commitments of iv and fv as read from the
+ * proof: lh_g1 as everywhere at this ABI, affine Montgomery coordinates, the identity - the commitment of an all-zero
+ * column - as (0, 0).  They are written only when the proof verifies.  Limits and errors as lh_memcheck_verify's without an
+ * image. */
+lh_status lh_memcheck_verify_segment(const lh_mkzg_vp* vp, size_t num_vars, size_t mem_vars, lh_transcript* t,
+                                     lh_g1* image_commitment, lh_g1* final_commitment);
 /* the verifier of lh_spark_open (tests/spark_ref.py verify; host only): `commitment` are the bytes of lh_spark_commitment,
  * `point` the num_dims * dim_vars coordinates, `value` the claimed D~(point).  The same limits as the prover's;
  * LH_ERR_INVALID_PCS_PARAM when max(num_vars, dim_vars) exceeds the param; a proof that does not verify, a proof of another
