@@ -463,6 +463,10 @@ extern "C" {
                                    d_keep_sorted: *const *mut u32, d_keep_index: *const *mut u32) -> lh_status;
     pub fn lh_debug_sort_plan(n: usize, bits: u32, key_bytes: i32, passes: *mut u32, rb: *mut u32,
                               temp_bytes: *mut usize) -> lh_status;
+    // (development) the owners of device resources: live counts (device blocks, pinned blocks, events, streams) and a
+    // one-shot failure of the (n + 1)-th acquisition from now on (n < 0: off); host only
+    pub fn lh_debug_live_resources(out: *mut u64) -> lh_status;
+    pub fn lh_debug_fail_acquire_after(n: i64) -> lh_status;
     // (development) the 32-bit column kernels on their own
     pub fn lh_debug_u32_columns(ctx: *mut lh_ctx, op: i32, args: *const lh_debug_u32_args) -> lh_status;
     // (development) the Lasso witness's subtable read for one memory, built-in or registered kind

@@ -341,6 +341,8 @@ SIGNATURES = {
     "lh_debug_sort_plan": (C.c_int, [_SZ, C.c_uint, C.c_int, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(_SZ)]),
     "lh_debug_msm_plan": (C.c_int, [_SZ, C.POINTER(_SZ), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_int, C.c_int,
                                     C.POINTER(C.c_uint64), C.POINTER(_SZ)]),
+    "lh_debug_live_resources": (C.c_int, [C.POINTER(C.c_uint64)]),
+    "lh_debug_fail_acquire_after": (C.c_int, [C.c_int64]),
     "lh_debug_u32_columns": (C.c_int, [_P, C.c_int, C.POINTER(lh_debug_u32_args)]),
     "lh_debug_lasso_subtable_read": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _SZ, _P]),
     "lh_keccak_transcript_hash_io": (C.c_int, [C.POINTER(lh_transcript), C.POINTER(lh_hash_transcript)]),

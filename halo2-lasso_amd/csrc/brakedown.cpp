@@ -150,9 +150,10 @@ void upload(Ctx& c, BdMatrix& mat) {  // transposed CSR, grouped by output index
       idx[e] = (uint32_t)i;
       val[e] = mat.coeffs[i * d.d + k];
     }
-  LH_HIP(hipMalloc((void**)&mat.d_ptr, ptr.size() * 4));
-  LH_HIP(hipMalloc((void**)&mat.d_idx, std::max<size_t>(idx.size(), 1) * 4));
-  LH_HIP(hipMalloc((void**)&mat.d_val, std::max<size_t>(val.size(), 1) * 32));
+  mat.mem[0].alloc(ptr.size() * 4);
+  mat.mem[1].alloc(std::max<size_t>(idx.size(), 1) * 4);
+  mat.mem[2].alloc(std::max<size_t>(val.size(), 1) * 32);
+  mat.d_ptr = mat.mem[0], mat.d_idx = mat.mem[1], mat.d_val = mat.mem[2];
   LH_HIP(hipMemcpyAsync(mat.d_ptr, ptr.data(), ptr.size() * 4, hipMemcpyHostToDevice, c.stream));
   if (!idx.empty()) {
     LH_HIP(hipMemcpyAsync(mat.d_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, c.stream));
@@ -161,27 +162,6 @@ void upload(Ctx& c, BdMatrix& mat) {  // transposed CSR, grouped by output index
   c.sync();
 }
 }  // namespace
-
-BdParam::~BdParam() {
-  if (device < 0) return;
-  (void)hipSetDevice(device);
-  for (auto* v : {&a, &b})
-    for (BdMatrix& m : *v) {
-      if (m.d_ptr) (void)hipFree(m.d_ptr);
-      if (m.d_idx) (void)hipFree(m.d_idx);
-      if (m.d_val) (void)hipFree(m.d_val);
-    }
-}
-BdComm::~BdComm() {
-  if (device < 0) return;
-  if (slab || borrowed) return;  // (a batch's allocation goes with its last commitment; borrowed memory is the caller's)
-  (void)hipSetDevice(device);
-  if (d_rows) (void)hipFree(d_rows);
-  if (d_hashes) (void)hipFree(d_hashes);
-}
-BdStage::~BdStage() {
-  if (cols) (void)hipHostFree(cols);
-}
 
 void brakedown_derive(BdParam& p, size_t num_vars, int spec) {
   LH_REQUIRE(spec >= 1 && spec <= 6, LH_ERR_ARG, "brakedown: spec must be 1..6");
@@ -198,8 +178,8 @@ void brakedown_derive(BdParam& p, size_t num_vars, int spec) {
   p.num_rows = ((size_t)1 << num_vars) / row_len;
   std::vector<BdDim> a, b;
   dimensions(s, row_len, p.n_0, a, b);
-  p.a.assign(a.size(), BdMatrix());
-  p.b.assign(b.size(), BdMatrix());
+  p.a = std::vector<BdMatrix>(a.size());
+  p.b = std::vector<BdMatrix>(b.size());
   for (size_t k = 0; k < a.size(); k++) p.a[k].dim = a[k], p.b[k].dim = b[k];
   p.codeword_len = codeword_len(s, row_len, p.n_0);
   p.num_column_opening = num_column_opening(s);
@@ -208,17 +188,17 @@ void brakedown_derive(BdParam& p, size_t num_vars, int spec) {
   LH_REQUIRE(p.codeword_len < ((size_t)1 << 32), LH_ERR_ARG, "brakedown: codeword too long");
 }
 
-BdParam* brakedown_setup(Ctx* c, size_t num_vars, int spec, const uint8_t seed[32]) {
-  std::unique_ptr<BdParam> p(new BdParam());
-  brakedown_derive(*p, num_vars, spec);
+BdParam brakedown_setup(Ctx* c, size_t num_vars, int spec, const uint8_t seed[32]) {
+  BdParam p;
+  brakedown_derive(p, num_vars, spec);
   WordStream ws;
   memcpy(ws.seed, seed, 32);
-  for (size_t k = 0; k < p->a.size(); k++) sample(ws, p->a[k]), sample(ws, p->b[k]);  // a[0], b[0], a[1], b[1], ..
+  for (size_t k = 0; k < p.a.size(); k++) sample(ws, p.a[k]), sample(ws, p.b[k]);  // a[0], b[0], a[1], b[1], ..
   if (c) {
-    p->device = c->device;
-    for (size_t k = 0; k < p->a.size(); k++) upload(*c, p->a[k]), upload(*c, p->b[k]);
+    p.device = c->device;
+    for (size_t k = 0; k < p.a.size(); k++) upload(*c, p.a[k]), upload(*c, p.b[k]);
   }
-  return p.release();
+  return p;
 }
 
 void brakedown_trim(const BdParam& p, size_t poly_size) {
@@ -290,15 +270,16 @@ static void encode_rows(Ctx& c, const BdParam& p, Fr* rows, size_t R, bool first
   LH_REQUIRE(in_off == p.row_len && out_off == cw, LH_ERR_ARG, "brakedown: cascade does not tile the codeword");
 }
 
-BdComm* brakedown_commit(Ctx& c, const BdParam& p, const Fr* d_poly, size_t num_vars) {
+std::unique_ptr<BdComm> brakedown_commit(Ctx& c, const BdParam& p, const Fr* d_poly, size_t num_vars) {
   check_vars(p, num_vars, "commit");
   LH_REQUIRE(p.device == c.device, LH_ERR_ARG, "brakedown: parameters were not set up on this ctx's device");
   const size_t R = p.num_rows, cw = p.codeword_len, width = (size_t)1 << p.depth;
   std::unique_ptr<BdComm> comm(new BdComm());
   comm->num_rows = R, comm->codeword_len = cw, comm->depth = p.depth, comm->device = c.device;
-  LH_HIP(hipMalloc((void**)&comm->d_rows, R * cw * sizeof(Fr)));
-  LH_HIP(hipMalloc((void**)&comm->d_hashes, ((2 * width) - 1) * 32));
-  Fr* rows = comm->d_rows;
+  comm->rows_mem.alloc(R * cw * sizeof(Fr));
+  comm->hashes_mem.alloc(((2 * width) - 1) * 32);
+  Fr* rows = comm->d_rows = comm->rows_mem;
+  comm->d_hashes = comm->hashes_mem;
   // row r's message is poly[r * row_len ..]
   LH_HIP(hipMemcpy2DAsync(rows, cw * sizeof(Fr), d_poly, p.row_len * sizeof(Fr), p.row_len * sizeof(Fr), R,
                           hipMemcpyDeviceToDevice, c.stream));
@@ -311,7 +292,7 @@ BdComm* brakedown_commit(Ctx& c, const BdParam& p, const Fr* d_poly, size_t num_
     off += w;
   }
   c.d2h(comm->root, comm->d_hashes + 4 * off, 32);
-  return comm.release();
+  return comm;
 }
 
 // ------------------------------------------------------------------ batch commit: P polys, the launches of one
@@ -321,7 +302,15 @@ static size_t batch_rows_bytes(const BdParam& p, size_t P) {
 }
 static size_t batch_tree_words(const BdParam& p) { return 4 * (((size_t)2 << p.depth) - 1); }
 static std::vector<std::unique_ptr<BdComm>> batch_trees(Ctx& c, const BdParam& p, size_t P, Fr* rows, uint64_t* trees,
-                                                        uint64_t* d_roots, const std::shared_ptr<void>& owner);
+                                                        uint64_t* d_roots, const std::shared_ptr<DevMem>& owner);
+// the slab of a batch: the caller's memory, or (null) one allocation that the batch's commitments share
+struct BatchSlab {
+  std::shared_ptr<DevMem> owner;
+  char* mem;
+  BatchSlab(void* given, size_t bytes) : mem((char*)given) {
+    if (!given) owner = std::make_shared<DevMem>(bytes), mem = owner->as<char>();
+  }
+};
 size_t brakedown_batch_bytes(const BdParam& p, size_t P) {
   return batch_rows_bytes(p, P) + ((P * batch_tree_words(p) * 8 + 255) & ~(size_t)255) + ((P * 32 + 255) & ~(size_t)255) +
          ((P * sizeof(Fr*) + 255) & ~(size_t)255);
@@ -333,28 +322,20 @@ std::vector<std::unique_ptr<BdComm>> brakedown_batch_commit(Ctx& c, const BdPara
   check_vars(p, num_vars, "commit");
   LH_REQUIRE(p.device == c.device, LH_ERR_ARG, "brakedown: parameters were not set up on this ctx's device");
   const size_t R = p.num_rows, cw = p.codeword_len, tree_words = batch_tree_words(p);
-  std::shared_ptr<void> owner;
-  if (!slab_mem) {
-    const int device = c.device;
-    LH_HIP(hipMalloc(&slab_mem, brakedown_batch_bytes(p, P)));
-    owner = std::shared_ptr<void>(slab_mem, [device](void* q) {
-      (void)hipSetDevice(device);
-      (void)hipFree(q);
-    });
-  }
-  Fr* rows = (Fr*)slab_mem;
-  uint64_t* trees = (uint64_t*)((char*)slab_mem + batch_rows_bytes(p, P));
+  const BatchSlab slab(slab_mem, brakedown_batch_bytes(p, P));
+  Fr* rows = (Fr*)slab.mem;
+  uint64_t* trees = (uint64_t*)(slab.mem + batch_rows_bytes(p, P));
   uint64_t* d_roots = (uint64_t*)((char*)trees + ((P * tree_words * 8 + 255) & ~(size_t)255));
   const Fr** d_ptrs = (const Fr**)((char*)d_roots + ((P * 32 + 255) & ~(size_t)255));
   LH_HIP(hipMemcpyAsync(d_ptrs, d_polys, P * sizeof(Fr*), hipMemcpyHostToDevice, c.stream));
   k_bd_load_rows(c, d_ptrs, P, R, p.row_len, cw, rows);
   encode_rows(c, p, rows, P * R);  // (rows are independent: the slab is P * R of them)
-  return batch_trees(c, p, P, rows, trees, d_roots, owner);
+  return batch_trees(c, p, P, rows, trees, d_roots, slab.owner);
 }
 
 // the column leaves, the trees and the roots of a slab whose P * num_rows rows are encoded -> the P commitments
 static std::vector<std::unique_ptr<BdComm>> batch_trees(Ctx& c, const BdParam& p, size_t P, Fr* rows, uint64_t* trees,
-                                                        uint64_t* d_roots, const std::shared_ptr<void>& owner) {
+                                                        uint64_t* d_roots, const std::shared_ptr<DevMem>& owner) {
   const size_t R = p.num_rows, cw = p.codeword_len, width = (size_t)1 << p.depth, tree_words = batch_tree_words(p);
   std::vector<std::unique_ptr<BdComm>> comms;
   k_bd_hash_columns_batch(c, rows, P, R, cw, width, trees, tree_words);
@@ -395,17 +376,9 @@ std::vector<std::unique_ptr<BdComm>> brakedown_commit_columns(Ctx& c, const BdPa
     (cols[i].u32 ? any_u32 : any_fr) = true;
   }
   const size_t R = p.num_rows, cw = p.codeword_len, tree_words = batch_tree_words(p);
-  std::shared_ptr<void> owner;
-  if (!slab_mem) {
-    const int device = c.device;
-    LH_HIP(hipMalloc(&slab_mem, brakedown_columns_bytes(p, P)));
-    owner = std::shared_ptr<void>(slab_mem, [device](void* q) {
-      (void)hipSetDevice(device);
-      (void)hipFree(q);
-    });
-  }
-  Fr* rows = (Fr*)slab_mem;
-  uint64_t* trees = (uint64_t*)((char*)slab_mem + batch_rows_bytes(p, P));
+  const BatchSlab slab(slab_mem, brakedown_columns_bytes(p, P));
+  Fr* rows = (Fr*)slab.mem;
+  uint64_t* trees = (uint64_t*)(slab.mem + batch_rows_bytes(p, P));
   uint64_t* d_roots = (uint64_t*)((char*)trees + ((P * tree_words * 8 + 255) & ~(size_t)255));
   BdColumn* d_cols = (BdColumn*)((char*)d_roots + ((P * 32 + 255) & ~(size_t)255));
   LH_HIP(hipMemcpyAsync(d_cols, cols, P * sizeof(BdColumn), hipMemcpyHostToDevice, c.stream));
@@ -420,7 +393,7 @@ std::vector<std::unique_ptr<BdComm>> brakedown_commit_columns(Ctx& c, const BdPa
         if (!cols[i].u32) k_bd_gather(c, rows + i * R * cw, R, cw, 0, p.row_len, p.a[0]);
   }
   encode_rows(c, p, rows, P * R, u32_first);
-  return batch_trees(c, p, P, rows, trees, d_roots, owner);  // (synchronises: the caller's table has been read by then)
+  return batch_trees(c, p, P, rows, trees, d_roots, slab.owner);  // (synchronises: the caller's table has been read by then)
 }
 
 // ------------------------------------------------------------------ open (brakedown.rs:212-276)
@@ -430,12 +403,7 @@ void brakedown_stage(Ctx& c, const BdParam& p, const BdComm& comm, BdStage& st) 
   if (st.of == &comm) return;
   const size_t R = p.num_rows, cw = p.codeword_len, bytes = R * cw * sizeof(Fr);
   st.of = nullptr;
-  if (bytes > st.capacity) {
-    if (st.cols) (void)hipHostFree(st.cols);
-    st.cols = nullptr, st.capacity = 0;
-    LH_HIP(hipHostMalloc((void**)&st.cols, bytes, hipHostMallocDefault));
-    st.capacity = bytes;
-  }
+  st.cols.reserve(bytes);
   if (R == 1) {  // the row is its own transpose
     LH_HIP(hipMemcpyAsync(st.cols, comm.d_rows, bytes, hipMemcpyDeviceToHost, c.stream));
     c.sync();
@@ -496,7 +464,7 @@ void brakedown_open(Ctx& c, const BdParam& p, const Fr* d_poly, size_t num_vars,
     const size_t column = (size_t)(((uint32_t)repr[0] | (uint32_t)repr[1] << 8 | (uint32_t)repr[2] << 16 |
                                     (uint32_t)repr[3] << 24) % cw);
     if (staged) {
-      col = staged->cols + column * R;
+      col = staged->cols.as<HFr>() + column * R;
     } else {
       LH_HIP(hipMemcpy2DAsync(col, 32, comm.d_rows + column, cw * sizeof(Fr), 32, R, hipMemcpyDeviceToHost, c.stream));
       c.sync();

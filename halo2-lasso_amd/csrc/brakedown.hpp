@@ -20,6 +20,7 @@ struct BdMatrix {
   uint32_t* d_ptr = nullptr;  // m + 1
   uint32_t* d_idx = nullptr;  // nnz input indices
   Fr* d_val = nullptr;        // nnz coefficients
+  DevMem mem[3];              // the blocks behind them
 };
 
 struct BdParam {
@@ -28,7 +29,6 @@ struct BdParam {
   int spec = 0;
   std::vector<BdMatrix> a, b;
   int device = -1;  // >= 0: the matrices are on this device too
-  ~BdParam();
 };
 
 // MultilinearBrakedownCommitment: the encoded rows and the Merkle tree stay on the device
@@ -39,11 +39,11 @@ struct BdComm {
   uint64_t* d_hashes = nullptr; // (2 << depth) - 1 digests of 4 words: leaves, then each level up, the root last
   uint8_t root[32];
   std::vector<uint64_t> host_tree;  // filled by the first open: the paths are read on the host
+  DevMem rows_mem, hashes_mem;  // a commitment of its own (brakedown_commit): the blocks behind d_rows and d_hashes
   // a commitment of a batch (brakedown_batch_commit): d_rows / d_hashes point into the batch's one allocation, which the
   // last commitment of the batch frees; or into memory the caller owns (`borrowed`: an arena slab of a proof)
-  std::shared_ptr<void> slab;
+  std::shared_ptr<DevMem> slab;
   bool borrowed = false;
-  ~BdComm();
 };
 
 // The encoded matrix of ONE commitment on the host, column-major (column c's num_rows entries at c * num_rows), in pinned
@@ -51,12 +51,7 @@ struct BdComm {
 // commitment replaces it; the buffer grows to the largest matrix staged and is freed with this object.
 struct BdStage {
   const BdComm* of = nullptr;
-  HFr* cols = nullptr;
-  size_t capacity = 0;  // bytes
-  BdStage() = default;
-  BdStage(const BdStage&) = delete;
-  BdStage& operator=(const BdStage&) = delete;
-  ~BdStage();
+  PinnedMem cols;  // HFr entries
 };
 
 // TranscriptWrite / TranscriptRead<Output<Keccak256>, Fr> (util/transcript.rs:240-265): raw 32 bytes, not absorbed
@@ -77,11 +72,11 @@ bool keccak_transcript_hash_io(lh_transcript* t, lh_hash_transcript* out);
 
 // parameters only (no matrices): throws LH_ERR_ARG where the reference panics
 void brakedown_derive(BdParam& p, size_t num_vars, int spec);
-BdParam* brakedown_setup(Ctx* c, size_t num_vars, int spec, const uint8_t seed[32]);
+BdParam brakedown_setup(Ctx* c, size_t num_vars, int spec, const uint8_t seed[32]);
 void brakedown_trim(const BdParam& p, size_t poly_size);
 // LinearCodes::encode: `cw` holds the message in its first row_len entries and gets the codeword
 void brakedown_encode_host(const BdParam& p, HFr* cw);
-BdComm* brakedown_commit(Ctx& c, const BdParam& p, const Fr* d_poly, size_t num_vars);
+std::unique_ptr<BdComm> brakedown_commit(Ctx& c, const BdParam& p, const Fr* d_poly, size_t num_vars);
 // P commits in the launches of one (kernels_brakedown.hip): rows, trees and roots bit-identical to P brakedown_commit
 // calls, the roots back in one copy.  `slab` null: one allocation for the batch, shared by the commitments; otherwise the
 // caller's memory of brakedown_batch_bytes (256-byte aligned), which outlives them.

@@ -7,6 +7,7 @@ using namespace lh;
 
 struct lh_ctx {
   Ctx c;
+  explicit lh_ctx(int device_id) : c(device_id) {}
 };
 struct lh_srs {
   Srs s;
@@ -24,7 +25,7 @@ struct lh_ukzg_vp {
   UkzgVerifierParams* p;
 };
 struct lh_ipa_param {
-  IpaParams* p;
+  std::unique_ptr<IpaParams> p;
 };
 struct lh_brakedown_param {
   BdParam p;
@@ -53,23 +54,9 @@ struct lh_brakedown_comm {
 // The current HIP device is a per-host-thread setting: every entry point that takes a ctx makes the ctx's device
 // current for the duration of the call (workspace growth, SRS shards and runtime-compiled modules must land on the
 // device the ctx's stream belongs to, whichever thread calls) and restores the caller's device afterwards.
-struct DeviceGuard {
-  int prev = -1;
-  bool switched = false;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) {
-      LH_HIP(hipSetDevice(dev));
-      switched = true;
-    }
-  }
-  ~DeviceGuard() {
-    if (switched && prev >= 0) (void)hipSetDevice(prev);
-  }
-};
 #define NEED_CTX(ctx) \
   NEED(ctx);          \
-  DeviceGuard device_guard_((ctx)->c.device)
+  OnDevice device_guard_((ctx)->c.device)
 
 // ---------------------------------------------------------------- Lasso and HyperPlonk over any PCS: one body per kind of entry
 // The exported functions (one per scheme, below) check their ctx and their own param handle and hand over the scheme's part
@@ -192,90 +179,13 @@ const char* lh_version(void) { return "lasso-hip 0.1 (gfx950)"; }
 lh_status lh_ctx_create(int device_id, lh_ctx** out) {
   LH_TRY
   NEED(out);
-  int count = 0;
-  hipError_t e = hipGetDeviceCount(&count);
-  if (e != hipSuccess || count <= 0)
-    throw lh::Error(LH_ERR_DEVICE, "no HIP device available (this library has no CPU fallback)");
-  LH_REQUIRE(device_id >= 0 && device_id < count, LH_ERR_DEVICE, "device id out of range");
-  LH_HIP(hipSetDevice(device_id));
-  lh_ctx* ctx = new lh_ctx();
-  ctx->c.device = device_id;
-  LH_HIP(hipStreamCreateWithFlags(&ctx->c.stream, hipStreamNonBlocking));
-  hipDeviceProp_t prop;
-  LH_HIP(hipGetDeviceProperties(&prop, device_id));
-  ctx->c.num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  int khz = 0;
-  if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device_id) == hipSuccess && khz > 0)
-    ctx->c.wall_clock_khz = khz;
-  ctx->c.pin(65536);
-  ctx->c.host_trace_on = knob(Knob::HOST_TRACE) != 0;
-  // line 0: device -> host sequence flag; lines 1-2: host -> device mailbox of the resident sum-check tail
-  LH_HIP(hipHostMalloc((void**)&ctx->c.flag, 256, hipHostMallocCoherent | hipHostMallocMapped));
-  memset(ctx->c.flag, 0, 256);
-  LH_HIP(hipMalloc((void**)&ctx->c.ticket, 256));  // word 0: ticket, word 8: device flag, words 32..47: the tail's relay chunks
-  LH_HIP(hipMemset(ctx->c.ticket, 0, 256));
-  LH_HIP(hipMalloc((void**)&ctx->c.fin_lanes, (size_t)FIN_LANE_SUMS * 64));
-  LH_HIP(hipMemset(ctx->c.fin_lanes, 0, (size_t)FIN_LANE_SUMS * 64));
-  *out = ctx;
+  *out = new lh_ctx(device_id);  // (a constructor that throws has released what it made)
   LH_CATCH
 }
 
-}  // extern "C"
-namespace lh {
-Ctx& ctx_helper(Ctx& c) {
-  if (!c.helper) {
-    lh_ctx* h = nullptr;
-    if (lh_ctx_create(c.device, &h) != LH_OK || !h) throw Error(LH_ERR_DEVICE, std::string("helper ctx: ") + get_last_error());
-    c.helper_handle = h;
-    c.helper = &h->c;
-    h->c.is_helper = true;
-  }
-  return *c.helper;
-}
-}  // namespace lh
-extern "C" {
-
 void lh_ctx_destroy(lh_ctx* ctx) {
   if (!ctx) return;
-  (void)hipSetDevice(ctx->c.device);
-  try {
-    open_precommit_cancel(ctx->c);
-  } catch (...) {
-  }
-  spartan_free_all(ctx->c);  // (R1CS keys nobody freed: before the polynomials they own)
-  spark_free_all(ctx->c);  // (committed sparse polynomials nobody freed: their device memory goes with the ctx)
-  if (ctx->c.helper_handle) {
-    lh_ctx_destroy(ctx->c.helper_handle);
-    ctx->c.helper_handle = nullptr, ctx->c.helper = nullptr;
-  }
-  delete ctx->c.worker;  // (joins; after the precommit it may still be running was cancelled above)
-  ctx->c.worker = nullptr;
-  if (ctx->c.handoff_ev) (void)hipEventDestroy(ctx->c.handoff_ev);
-  for (hipEvent_t& ev : ctx->c.stage_ev)
-    if (ev) (void)hipEventDestroy(ev), ev = nullptr;
-  if (ctx->c.aux_stream) (void)hipStreamSynchronize(ctx->c.aux_stream), (void)hipStreamDestroy(ctx->c.aux_stream);
-  if (ctx->c.aux_ev) (void)hipEventDestroy(ctx->c.aux_ev);
-  for (hipEvent_t& ev : ctx->c.phase_ev)
-    if (ev) (void)hipEventDestroy(ev), ev = nullptr;
-  (void)hipStreamSynchronize(ctx->c.stream);
-  try {
-    comm_detach(ctx->c);
-  } catch (...) {
-  }
-  if (ctx->c.gkr_mbox) (void)hipHostFree(ctx->c.gkr_mbox);
-  if (ctx->c.gkr_relay) (void)hipFree(ctx->c.gkr_relay);
-  if (ctx->c.comm_stage) (void)hipFree(ctx->c.comm_stage);
-  if (ctx->c.pinned) (void)hipHostFree(ctx->c.pinned);
-  if (ctx->c.stage) (void)hipHostFree(ctx->c.stage);
-  for (int k = 0; k < 2; k++) {
-    if (ctx->c.sort_stage[k]) (void)hipHostFree(ctx->c.sort_stage[k]);
-    if (ctx->c.sort_ev[k]) (void)hipEventDestroy(ctx->c.sort_ev[k]);
-  }
-  if (ctx->c.flag) (void)hipHostFree(ctx->c.flag);
-  if (ctx->c.lanes_host) (void)hipHostFree(ctx->c.lanes_host);
-  if (ctx->c.ticket) (void)hipFree(ctx->c.ticket);
-  if (ctx->c.fin_lanes) (void)hipFree(ctx->c.fin_lanes);
-  (void)hipStreamDestroy(ctx->c.stream);
+  OnDevice on(ctx->c.device, true);
   delete ctx;
 }
 
@@ -577,11 +487,7 @@ lh_status lh_mkzg_setup(lh_ctx* ctx, const lh_fr* ss, size_t num_vars, lh_srs** 
   LH_TRY NEED_CTX(ctx);
   NEED(out);
   NEED_N(ss, num_vars);
-  Srs* s = mkzg_setup(ctx->c, (const HFr*)ss, num_vars);
-  lh_srs* w = new lh_srs();
-  w->s = *s;
-  delete s;
-  *out = w;
+  *out = new lh_srs{mkzg_setup(ctx->c, (const HFr*)ss, num_vars)};
   LH_CATCH
 }
 lh_status lh_srs_upload(lh_ctx* ctx, const lh_g1* eqs_flat, size_t num_vars, lh_srs** out) {
@@ -589,15 +495,13 @@ lh_status lh_srs_upload(lh_ctx* ctx, const lh_g1* eqs_flat, size_t num_vars, lh_
   NEED(out);
   NEED(eqs_flat);
   LH_REQUIRE(num_vars < 31, LH_ERR_ARG, "srs: num_vars too large");
-  std::unique_ptr<lh_srs> w(new lh_srs());  // (a failed allocation or copy below must not leak the wrapper)
+  std::unique_ptr<lh_srs> w(new lh_srs());
   w->s.num_vars = num_vars;
   size_t total = ((size_t)2 << num_vars) - 1;
-  LH_HIP(hipMalloc((void**)&w->s.d_eqs, total * sizeof(G1Affine)));
+  w->s.d_eqs.alloc(total * sizeof(G1Affine));
   if (hipMemcpyAsync(w->s.d_eqs, eqs_flat, total * sizeof(G1Affine), hipMemcpyHostToDevice, ctx->c.stream) != hipSuccess ||
-      hipStreamSynchronize(ctx->c.stream) != hipSuccess) {
-    (void)hipFree(w->s.d_eqs);
+      hipStreamSynchronize(ctx->c.stream) != hipSuccess)
     throw lh::Error(LH_ERR_DEVICE, "srs upload failed");
-  }
   *out = w.release();
   LH_CATCH
 }
@@ -614,15 +518,6 @@ size_t lh_srs_num_vars(const lh_srs* srs) { return srs ? srs->s.num_vars : 0; }
 void lh_srs_free(lh_ctx* ctx, lh_srs* srs) {
   if (!srs) return;
   if (ctx) (void)hipStreamSynchronize(ctx->c.stream);
-  if (srs->s.d_eqs) {
-    (void)hipFree(srs->s.d_eqs);
-  }
-  for (G1Affine* p : srs->s.shard_levels)
-    if (p) {
-      (void)hipFree(p);
-    }
-  for (auto& kv : srs->s.win_tables)
-    if (kv.second.d) (void)hipFree(kv.second.d);
   delete srs;
 }
 
@@ -779,7 +674,6 @@ lh_status lh_spark_open(lh_ctx* ctx, const lh_srs* srs, const lh_spark_poly* pol
 }
 void lh_spark_free(lh_ctx* ctx, lh_spark_poly* poly) {
   if (!ctx || !poly) return;
-  (void)hipSetDevice(ctx->c.device);
   spark_free(ctx->c, (SparkPoly*)poly);
 }
 // ---------------------------------------------------------------- Spartan: R1CS over the Spark-committed matrices
@@ -820,7 +714,6 @@ lh_status lh_spartan_prove(lh_ctx* ctx, const lh_srs* srs, const lh_r1cs_key* ke
 }
 void lh_r1cs_free(lh_ctx* ctx, lh_r1cs_key* key) {
   if (!ctx || !key) return;
-  (void)hipSetDevice(ctx->c.device);
   spartan_free(ctx->c, (R1csKey*)key);
 }
 // ---------------------------------------------------------------- Nova folding over an R1CS key; relaxed Spartan
@@ -879,7 +772,6 @@ lh_status lh_spartan_prove_relaxed(lh_ctx* ctx, const lh_srs* srs, const lh_r1cs
 lh_status lh_lasso_last_timing(lh_ctx* ctx, double* out_ms) {
   LH_TRY NEED_CTX(ctx);
   NEED(out_ms);
-  LH_HIP(hipSetDevice(ctx->c.device));
   ctx->c.phase_times_resolve();  // (the phase boundaries are events on the stream: lasso.cpp lap)
   memcpy(out_ms, ctx->c.lasso_ms, sizeof(ctx->c.lasso_ms));
   LH_CATCH
@@ -1316,9 +1208,7 @@ lh_status lh_ukzg_setup(lh_ctx* ctx, const lh_fr* s, size_t poly_size, lh_usrs**
   NEED(out);
   HFr sv;
   memcpy(&sv, s, 32);
-  USrs* u = ukzg_setup(ctx->c, sv, poly_size);
-  *out = new lh_usrs{*u};
-  delete u;
+  *out = new lh_usrs{ukzg_setup(ctx->c, sv, poly_size)};
   LH_CATCH
 }
 lh_status lh_usrs_upload(lh_ctx* ctx, const lh_g1* powers, size_t poly_size, lh_usrs** out) {
@@ -1328,12 +1218,10 @@ lh_status lh_usrs_upload(lh_ctx* ctx, const lh_g1* powers, size_t poly_size, lh_
   LH_REQUIRE(poly_size >= 1 && poly_size < ((size_t)1 << 31), LH_ERR_ARG, "univariate srs: bad poly_size");
   std::unique_ptr<lh_usrs> w(new lh_usrs());
   w->s.size = poly_size;
-  LH_HIP(hipMalloc((void**)&w->s.d_powers, poly_size * sizeof(G1Affine)));
+  w->s.d_powers.alloc(poly_size * sizeof(G1Affine));
   if (hipMemcpyAsync(w->s.d_powers, powers, poly_size * sizeof(G1Affine), hipMemcpyHostToDevice, ctx->c.stream) != hipSuccess ||
-      hipStreamSynchronize(ctx->c.stream) != hipSuccess) {
-    (void)hipFree(w->s.d_powers);
+      hipStreamSynchronize(ctx->c.stream) != hipSuccess)
     throw lh::Error(LH_ERR_DEVICE, "univariate srs upload failed");
-  }
   *out = w.release();
   LH_CATCH
 }
@@ -1349,7 +1237,6 @@ size_t lh_usrs_size(const lh_usrs* srs) { return srs ? srs->s.size : 0; }
 void lh_usrs_free(lh_ctx* ctx, lh_usrs* srs) {
   if (!srs) return;
   if (ctx) (void)hipStreamSynchronize(ctx->c.stream);
-  if (srs->s.d_powers) (void)hipFree(srs->s.d_powers);
   delete srs;
 }
 lh_status lh_zeromorph_batch_commit(lh_ctx* ctx, const lh_usrs* srs, size_t poly_size, const lh_fr* const* d_polys,
@@ -1460,12 +1347,8 @@ lh_status lh_brakedown_setup(lh_ctx* ctx, size_t num_vars, int spec, const uint8
   LH_TRY
   NEED(seed32);
   NEED(out);
-  std::unique_ptr<DeviceGuard> guard(ctx ? new DeviceGuard(ctx->c.device) : nullptr);
-  std::unique_ptr<BdParam> p(brakedown_setup(ctx ? &ctx->c : nullptr, num_vars, spec, seed32));
-  std::unique_ptr<lh_brakedown_param> w(new lh_brakedown_param());
-  std::swap(w->p, *p);  // (the moved-from param owns nothing on the device)
-  p->device = -1;
-  *out = w.release();
+  OnDevice on(ctx ? ctx->c.device : -1);
+  *out = new lh_brakedown_param{brakedown_setup(ctx ? &ctx->c : nullptr, num_vars, spec, seed32)};
   LH_CATCH
 }
 lh_status lh_brakedown_derive(size_t num_vars, int spec, lh_brakedown_param** out) {
@@ -1522,12 +1405,8 @@ static lh_status bd_commit_entry(lh_ctx* ctx, const lh_brakedown_param* pp, cons
   if (as_batch && num_polys && ctx->c.opt.brakedown_batch_commit)
     batch = brakedown_batch_commit(ctx->c, pp->p, (const Fr* const*)d_polys, num_polys, num_vars);
   for (size_t i = 0; i < num_polys; i++) {
-    std::unique_ptr<BdComm> c(batch.empty() ? brakedown_commit(ctx->c, pp->p, (const Fr*)d_polys[i], num_vars)
-                                            : batch[i].release());
-    std::unique_ptr<lh_brakedown_comm> w(new lh_brakedown_comm());
-    std::swap(w->c, *c);
-    c->device = -1;
-    comms.push_back(std::move(w));
+    std::unique_ptr<BdComm> c = batch.empty() ? brakedown_commit(ctx->c, pp->p, (const Fr*)d_polys[i], num_vars) : std::move(batch[i]);
+    comms.emplace_back(new lh_brakedown_comm{std::move(*c)});
   }
   for (size_t i = 0; i < num_polys; i++) out[i] = comms[i].release();
   LH_CATCH
@@ -1557,10 +1436,7 @@ lh_status lh_brakedown_commit_columns(lh_ctx* ctx, const lh_brakedown_param* pp,
   std::vector<std::unique_ptr<BdComm>> batch = brakedown_commit_columns(ctx->c, pp->p, cols.data(), num_cols);
   std::vector<std::unique_ptr<lh_brakedown_comm>> comms;
   for (size_t i = 0; i < num_cols; i++) {
-    std::unique_ptr<lh_brakedown_comm> w(new lh_brakedown_comm());
-    std::swap(w->c, *batch[i]);
-    batch[i]->device = -1;
-    comms.push_back(std::move(w));
+    comms.emplace_back(new lh_brakedown_comm{std::move(*batch[i])});
   }
   for (size_t i = 0; i < num_cols; i++) out[i] = comms[i].release();
   LH_CATCH
@@ -2062,18 +1938,13 @@ lh_status lh_hyperplonk_verify_phases_gemini(const lh_ukzg_vp* vp, const lh_hp_v
 lh_status lh_ipa_setup(lh_ctx* ctx, size_t poly_size, lh_ipa_param** out) {
   LH_TRY
   NEED(out);
-  if (ctx) {
-    DeviceGuard device_guard_(ctx->c.device);
-    *out = new lh_ipa_param{ipa_setup(&ctx->c, poly_size)};
-  } else {
-    *out = new lh_ipa_param{ipa_setup(nullptr, poly_size)};
-  }
+  OnDevice on(ctx ? ctx->c.device : -1);
+  *out = new lh_ipa_param{ipa_setup(ctx ? &ctx->c : nullptr, poly_size)};
   LH_CATCH
 }
 void lh_ipa_param_free(lh_ctx* ctx, lh_ipa_param* param) {
   if (!param) return;
   if (ctx) (void)hipStreamSynchronize(ctx->c.stream);
-  ipa_free(param->p);
   delete param;
 }
 size_t lh_ipa_param_size(const lh_ipa_param* param) { return param ? (size_t)1 << param->p->num_vars : 0; }
@@ -2183,12 +2054,8 @@ lh_status lh_hyrax_setup(lh_ctx* ctx, size_t poly_size, size_t batch_size, lh_ip
   LH_TRY
   NEED(out);
   const HyraxDims d = hyrax_dims(poly_size, batch_size);
-  if (ctx) {
-    DeviceGuard device_guard_(ctx->c.device);
-    *out = new lh_ipa_param{ipa_setup(&ctx->c, (size_t)1 << d.row_num_vars)};
-  } else {
-    *out = new lh_ipa_param{ipa_setup(nullptr, (size_t)1 << d.row_num_vars)};
-  }
+  OnDevice on(ctx ? ctx->c.device : -1);
+  *out = new lh_ipa_param{ipa_setup(ctx ? &ctx->c : nullptr, (size_t)1 << d.row_num_vars)};
   LH_CATCH
 }
 lh_status lh_hyrax_dims(size_t poly_size, size_t batch_size, size_t* num_vars, size_t* batch_num_vars, size_t* row_num_vars) {
@@ -2536,6 +2403,17 @@ lh_status lh_debug_msm_plan(size_t num_jobs, const size_t* n, const uint32_t* bi
     jobs.push_back(jb);
   }
   *num_subs = msm_plan_shape(c, jobs.data(), num_jobs, via_prepare != 0, out);
+  LH_CATCH
+}
+lh_status lh_debug_live_resources(uint64_t out[4]) {
+  LH_TRY
+  NEED(out);
+  owned_live(out);
+  LH_CATCH
+}
+lh_status lh_debug_fail_acquire_after(int64_t n) {
+  LH_TRY
+  owned_fail_acquire_after(n);
   LH_CATCH
 }
 

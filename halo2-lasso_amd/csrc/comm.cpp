@@ -87,16 +87,8 @@ void rccl_check(ncclResult_t r, const char* what) {
 }
 
 void* comm_device_stage(Ctx& c, size_t bytes) {
-  if (bytes > c.comm_stage_bytes) {
-    if (c.comm_stage) {
-      c.sync();
-      (void)hipFree(c.comm_stage);
-    }
-    size_t want = bytes < ((size_t)1 << 16) ? ((size_t)1 << 16) : bytes;
-    LH_HIP(hipMalloc(&c.comm_stage, want));
-    c.comm_stage_bytes = want;
-  }
-  return c.comm_stage;
+  if (bytes > c.comm_stage.size() && c.comm_stage) c.sync();
+  return c.comm_stage.reserve(bytes, (size_t)1 << 16);
 }
 }  // namespace
 
@@ -146,10 +138,7 @@ void comm_probe_host_recv(Ctx& c) {
   const bool force_fail = knob(Knob::COMM_PROBE_FAIL) != 0;
   const RcclApi& api = rccl();
   const size_t R = (size_t)c.comm.size, n = 16;
-  if (!c.lanes_host) {
-    LH_HIP(hipHostMalloc((void**)&c.lanes_host, 128 * sizeof(uint64_t), hipHostMallocCoherent | hipHostMallocMapped));
-    memset(c.lanes_host, 0, 128 * sizeof(uint64_t));
-  }
+  uint64_t* const lanes_host = c.lanes_host_block();
   ArenaScope scope(c.arena);
   uint64_t* d = c.arena.alloc_n<uint64_t>(2 * n);
   const uint64_t tag = 0x5a5;  // (R * tag < 2^24 for R <= 256; a lane is a limb | tag << 40, as in a round)
@@ -158,10 +147,10 @@ void comm_probe_host_recv(Ctx& c) {
   LH_HIP(hipMemcpyAsync(d, h, sizeof(h), hipMemcpyHostToDevice, c.stream));
   c.sync();
   bool ok = !force_fail;
-  volatile uint64_t* hl = c.lanes_host;
+  volatile uint64_t* hl = lanes_host;
   for (size_t i = 0; i < n; i++) hl[64 + i] = 0;
   if (ok) {
-    const ncclResult_t r = api.AllReduce(d, c.lanes_host + 64, n, ncclUint64, ncclSum, (ncclComm_t)c.rccl_comm, c.stream);
+    const ncclResult_t r = api.AllReduce(d, lanes_host + 64, n, ncclUint64, ncclSum, (ncclComm_t)c.rccl_comm, c.stream);
     ok = r == ncclSuccess;
     if (ok) {
       const auto t0 = std::chrono::steady_clock::now();
@@ -362,21 +351,18 @@ void comm_sum_lanes(Ctx& c, uint64_t* d_lanes, uint64_t* d_scratch, size_t count
   const size_t R = (size_t)c.comm.size, n = 8 * count;
   LH_REQUIRE(count >= 1 && count <= 16 && R <= 256, LH_ERR_ARG, "comm_sum_lanes: bad size");
   comm_trace(c, "all_reduce_lanes", n * sizeof(uint64_t));
-  if (!c.lanes_host) {
-    LH_HIP(hipHostMalloc((void**)&c.lanes_host, 128 * sizeof(uint64_t), hipHostMallocCoherent | hipHostMallocMapped));
-    memset(c.lanes_host, 0, 128 * sizeof(uint64_t));
-  }
-  volatile uint64_t* hl = c.lanes_host;
+  uint64_t* const lanes_host = c.lanes_host_block();
+  volatile uint64_t* hl = lanes_host;
   const bool via_device = c.opt.comm_round == 2 || !c.comm_host_recv_ok;  // (comm_probe_host_recv: this fabric refused host memory)
-  uint64_t* dst = via_device ? d_scratch : c.lanes_host;
+  uint64_t* dst = via_device ? d_scratch : lanes_host;
   if (c.comm_loopback) {
     c.comm_stats[0]++;
     k_loopback_allreduce_lanes(c, d_lanes, n, R, dst);
-    if (via_device) LH_HIP(hipMemcpyAsync(c.lanes_host, d_scratch, n * sizeof(uint64_t), hipMemcpyDeviceToHost, c.stream));
+    if (via_device) LH_HIP(hipMemcpyAsync(lanes_host, d_scratch, n * sizeof(uint64_t), hipMemcpyDeviceToHost, c.stream));
   } else if (c.rccl_comm) {
     c.comm_stats[0]++;
     rccl_check(rccl().AllReduce(d_lanes, dst, n, ncclUint64, ncclSum, (ncclComm_t)c.rccl_comm, c.stream), "ncclAllReduce");
-    if (via_device) LH_HIP(hipMemcpyAsync(c.lanes_host, d_scratch, n * sizeof(uint64_t), hipMemcpyDeviceToHost, c.stream));
+    if (via_device) LH_HIP(hipMemcpyAsync(lanes_host, d_scratch, n * sizeof(uint64_t), hipMemcpyDeviceToHost, c.stream));
   } else {
     // callback transports (gloo in the tests): the lanes are all-gathered through the host and added there - the same
     // arithmetic, the same lanes, the same wait below

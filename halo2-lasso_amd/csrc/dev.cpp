@@ -14,7 +14,7 @@
 #include <hip/hip_ext.h>
 #include <vector>
 #include <chrono>
-#include "dev.hpp"
+#include "host.hpp"  // spark_free_all, spartan_free_all (Ctx::~Ctx)
 
 namespace lh {
 
@@ -22,9 +22,111 @@ static thread_local std::string g_last_error;
 void set_last_error(const char* msg) { g_last_error = msg ? msg : ""; }
 const char* get_last_error() { return g_last_error.c_str(); }
 
-Arena::~Arena() {
-  for (auto& b : blocks_) (void)hipFree(b.p);
+// ------------------------------------------------------------------ owners (owned.hpp)
+namespace {
+enum { LIVE_DEV, LIVE_PINNED, LIVE_EVENT, LIVE_STREAM };
+std::atomic<uint64_t> g_live[4];
+std::atomic<int64_t> g_fail_after{-1};
+// ahead of every acquisition: false when this one is the injected failure
+bool acquire_allowed() {
+  return g_fail_after.load(std::memory_order_relaxed) < 0 || g_fail_after.fetch_sub(1, std::memory_order_relaxed) != 0;
 }
+void acquire_gate() {
+  if (!acquire_allowed()) throw Error(LH_ERR_DEVICE, "injected acquisition failure (lh_debug_fail_acquire_after)");
+}
+void live(int kind, int by) { g_live[kind].fetch_add((uint64_t)(int64_t)by, std::memory_order_relaxed); }
+}  // namespace
+void owned_live(uint64_t out[4]) {
+  for (int k = 0; k < 4; k++) out[k] = g_live[k].load(std::memory_order_relaxed);
+}
+void owned_fail_acquire_after(int64_t n) { g_fail_after.store(n < 0 ? -1 : n, std::memory_order_relaxed); }
+
+OnDevice::OnDevice(int device, bool nothrow) {
+  if (device < 0) return;
+  if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+  if (prev == device) return;
+  const hipError_t e = hipSetDevice(device);
+  if (e == hipSuccess) switched = true;
+  else if (!nothrow) throw Error(LH_ERR_DEVICE, std::string("hipSetDevice(device): ") + hipGetErrorString(e));
+}
+OnDevice::~OnDevice() {
+  if (switched && prev >= 0) (void)hipSetDevice(prev);
+}
+
+bool DevMem::try_alloc(size_t bytes) {
+  reset();
+  if (!acquire_allowed() || hipGetDevice(&device_) != hipSuccess || hipMalloc(&p_, bytes) != hipSuccess) {
+    p_ = nullptr;
+    return false;
+  }
+  bytes_ = bytes;
+  live(LIVE_DEV, 1);
+  return true;
+}
+void DevMem::alloc(size_t bytes) {
+  reset();
+  acquire_gate();
+  LH_HIP(hipGetDevice(&device_));
+  LH_HIP(hipMalloc(&p_, bytes));
+  bytes_ = bytes;
+  live(LIVE_DEV, 1);
+}
+void DevMem::forget() {
+  p_ = nullptr, bytes_ = 0;
+  live(LIVE_DEV, -1);
+}
+void DevMem::reset() {
+  if (!p_) return;
+  OnDevice on(device_, true);
+  (void)hipFree(p_);
+  forget();
+}
+
+void PinnedMem::alloc(size_t bytes) {
+  reset();
+  acquire_gate();
+  LH_HIP(hipHostMalloc(&p_, bytes, flags_));
+  bytes_ = bytes;
+  live(LIVE_PINNED, 1);
+}
+void PinnedMem::reset() {
+  if (!p_) return;
+  (void)hipHostFree(p_);
+  p_ = nullptr, bytes_ = 0;
+  live(LIVE_PINNED, -1);
+}
+
+void Event::create() {
+  acquire_gate();
+  LH_HIP(hipEventCreateWithFlags(&ev_, flags_));
+  live(LIVE_EVENT, 1);
+}
+void Event::reset() {
+  if (!ev_) return;
+  (void)hipEventDestroy(ev_);
+  ev_ = nullptr;
+  live(LIVE_EVENT, -1);
+}
+
+void Stream::create(unsigned flags) {
+  reset();
+  acquire_gate();
+  LH_HIP(hipStreamCreateWithFlags(&s_, flags));
+  live(LIVE_STREAM, 1);
+}
+void Stream::create(unsigned flags, int priority) {
+  reset();
+  acquire_gate();
+  LH_HIP(hipStreamCreateWithPriority(&s_, flags, priority));
+  live(LIVE_STREAM, 1);
+}
+void Stream::reset() {
+  if (!s_) return;
+  (void)hipStreamDestroy(s_);
+  s_ = nullptr;
+  live(LIVE_STREAM, -1);
+}
+
 
 void* Arena::alloc(size_t bytes) {
   bytes = (bytes + 255) & ~(size_t)255;
@@ -36,7 +138,7 @@ void* Arena::alloc_raw(size_t bytes) {
     if (!blocks_.empty()) {
       Block& b = blocks_[cur_];
       if (b.used + bytes <= b.size) {
-        void* p = b.p + b.used;
+        void* p = b.mem.as<char>() + b.used;
         b.used += bytes;
         size_t tot = 0;
         for (size_t i = 0; i <= cur_; i++) tot += blocks_[i].used;
@@ -51,9 +153,7 @@ void* Arena::alloc_raw(size_t bytes) {
     }
     size_t want = blocks_.empty() ? ((size_t)64 << 20) : blocks_.back().size * 2;
     if (want < bytes) want = bytes;
-    void* p = nullptr;
-    LH_HIP(hipMalloc(&p, want));
-    blocks_.push_back(Block{(char*)p, want, 0});
+    blocks_.push_back(Block{DevMem(want), want, 0});
     cur_ = blocks_.size() - 1;
   }
 }
@@ -63,6 +163,63 @@ void Arena::release(Mark m) {
   for (size_t i = m.block + 1; i < blocks_.size(); i++) blocks_[i].used = 0;
   cur_ = m.block;
   blocks_[cur_].used = m.used;
+}
+
+Ctx::Ctx(int device_id) : device(device_id) {
+  int count = 0;
+  hipError_t e = hipGetDeviceCount(&count);
+  if (e != hipSuccess || count <= 0)
+    throw Error(LH_ERR_DEVICE, "no HIP device available (this library has no CPU fallback)");
+  LH_REQUIRE(device_id >= 0 && device_id < count, LH_ERR_DEVICE, "device id out of range");
+  LH_HIP(hipSetDevice(device_id));
+  stream.create(hipStreamNonBlocking);
+  hipDeviceProp_t prop;
+  LH_HIP(hipGetDeviceProperties(&prop, device_id));
+  num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+  int khz = 0;
+  if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device_id) == hipSuccess && khz > 0) wall_clock_khz = khz;
+  pin(65536);
+  host_trace_on = knob(Knob::HOST_TRACE) != 0;
+  // line 0: device -> host sequence flag; lines 1-2: host -> device mailbox of the resident sum-check tail
+  flag.alloc(256);
+  memset(flag.get(), 0, 256);
+  ticket.alloc(256);  // word 0: ticket, word 8: device flag, words 32..47: the tail's relay chunks
+  LH_HIP(hipMemset(ticket, 0, 256));
+  fin_lanes.alloc((size_t)FIN_LANE_SUMS * 64);
+  LH_HIP(hipMemset(fin_lanes, 0, (size_t)FIN_LANE_SUMS * 64));
+}
+
+Ctx::~Ctx() {
+  try {
+    open_precommit_cancel(*this);
+  } catch (...) {
+  }
+  spartan_free_all(*this);  // (R1CS keys nobody freed: before the polynomials they own)
+  spark_free_all(*this);    // (committed sparse polynomials nobody freed: their device memory goes with the ctx)
+  helper.reset();
+  worker.reset();  // (joins; after the precommit it may still be running was cancelled above)
+  if (aux_stream) (void)hipStreamSynchronize(aux_stream);
+  if (stream) (void)hipStreamSynchronize(stream);
+  try {
+    comm_detach(*this);
+  } catch (...) {
+  }
+}
+
+Ctx& ctx_helper(Ctx& c) {
+  if (!c.helper) {
+    c.helper.reset(new Ctx(c.device));
+    c.helper->is_helper = true;
+  }
+  return *c.helper;
+}
+
+uint64_t* Ctx::lanes_host_block() {
+  if (!lanes_host) {
+    lanes_host.alloc(128 * sizeof(uint64_t));
+    memset(lanes_host.get(), 0, 128 * sizeof(uint64_t));
+  }
+  return lanes_host;
 }
 
 void Ctx::opt_in_lds(const void* fn, int bytes) {
@@ -240,14 +397,13 @@ void Ctx::wait_flag(uint32_t seq) {
   }
 }
 
-hipEvent_t Ctx::live_event() {
+Event Ctx::live_event() {
+  Event e;
   if (!live_pool.empty()) {
-    hipEvent_t e = live_pool.back();
+    e = std::move(live_pool.back());
     live_pool.pop_back();
-    return e;
   }
-  hipEvent_t e = nullptr;
-  LH_HIP(hipEventCreate(&e));
+  (void)e.get();
   return e;
 }
 void Ctx::live_resolve(std::vector<ProfRec>& out) {
@@ -262,8 +418,8 @@ void Ctx::live_resolve(std::vector<ProfRec>& out) {
     for (; j < live_recs.size() && live_recs[j].batch == live_recs[i].batch; j++) {
       LiveRec& r = live_recs[j];
       float ms = 0, end = 0;
-      (void)hipEventElapsedTime(&ms, r.e0, r.e1);
-      (void)hipEventElapsedTime(&end, live_recs[i].e0, r.e1);  // (the batch's first launch starts first: the others wait for an event behind it)
+      (void)hipEventElapsedTime(&ms, r.e0.get(), r.e1.get());
+      (void)hipEventElapsedTime(&end, live_recs[i].e0.get(), r.e1.get());  // (the batch's first launch starts first: the others wait for an event behind it)
       r.rec.ms = ms;
       span = std::max(span, end);
       sum.bytes += r.rec.bytes, sum.muls += r.rec.muls, sum.items += r.rec.items;
@@ -273,7 +429,7 @@ void Ctx::live_resolve(std::vector<ProfRec>& out) {
     out.push_back(sum);
     i = j;
   }
-  for (LiveRec& r : live_recs) live_pool.push_back(r.e0), live_pool.push_back(r.e1);
+  for (LiveRec& r : live_recs) live_pool.push_back(std::move(r.e0)), live_pool.push_back(std::move(r.e1));
   live_recs.clear();
 }
 
@@ -282,16 +438,16 @@ void Ctx::aux_streams() {
   // (the LOWEST priority the device offers: what runs here fills the wave slots the ctx's stream leaves idle)
   int prio_least = 0, prio_greatest = 0;
   LH_HIP(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
-  LH_HIP(hipStreamCreateWithPriority(&aux_stream, hipStreamNonBlocking, prio_least));
-  LH_HIP(hipEventCreateWithFlags(&aux_ev, hipEventDisableTiming));
+  aux_stream.create(hipStreamNonBlocking, prio_least);
+  (void)aux_ev.get();
 }
 ScFinishArgs Ctx::finish_for_aux(uint32_t grid, uint32_t seq) {
-  ScFinishArgs f{ticket + 16, (uint32_t)(aux_ticket_base + grid - 1), nullptr, flag + 4, seq, nullptr, 0, nullptr};
+  ScFinishArgs f{ticket.as<uint32_t>() + 16, (uint32_t)(aux_ticket_base + grid - 1), nullptr, flag.as<uint32_t>() + 4, seq, nullptr, 0, nullptr};
   if (grid > 1) aux_ticket_base += grid;
   return f;
 }
 void Ctx::wait_flag_aux(uint32_t seq) {
-  volatile uint32_t* f = flag + 4;
+  volatile uint32_t* f = flag.as<uint32_t>() + 4;
   for (uint64_t spin = 0;; spin++) {
     if (*f == seq) return;
     __builtin_ia32_pause();
@@ -313,8 +469,8 @@ ScFinishArgs Ctx::finish_for(uint32_t grid, Fr* out_host, uint32_t seq, double s
   // LH_FIN_LANES_MIN_BYTES: the smallest launch (by the bytes its workgroups store) that does - development A/B; -1: none
   const double lanes_min = knob(Knob::FIN_LANES_MIN_BYTES);
   const bool lanes = lanes_min >= 0 && stored_bytes >= lanes_min && grid > 1 && (uint64_t)grid * 16 <= FIN_LANE_SUMS;
-  ScFinishArgs f{ticket, (uint32_t)(ticket_base + grid - 1), out_host, flag, seq, nullptr, 0, lanes ? fin_lanes : nullptr};
-  if (sc_redirect) f.out_host = sc_redirect, f.flag = ticket + 8, f.wide = sc_wide, f.tag = sc_tag;  // sharded round: a device word nobody waits on
+  ScFinishArgs f{ticket, (uint32_t)(ticket_base + grid - 1), out_host, flag, seq, nullptr, 0, lanes ? fin_lanes.as<uint64_t>() : nullptr};
+  if (sc_redirect) f.out_host = sc_redirect, f.flag = ticket.as<uint32_t>() + 8, f.wide = sc_wide, f.tag = sc_tag;  // sharded round: a device word nobody waits on
   if (grid > 1) ticket_base += grid;  // single-workgroup launches draw no ticket
   return f;
 }
@@ -340,28 +496,29 @@ void Ctx::mbox_abort() {
 }
 
 void Ctx::gkr_boxes() {
-  if (gkr_mbox) return;
-  LH_HIP(hipHostMalloc((void**)&gkr_mbox, GKR_MSG_CHUNKS * sizeof(TailChunk), hipHostMallocCoherent | hipHostMallocMapped));
-  memset((void*)gkr_mbox, 0, GKR_MSG_CHUNKS * sizeof(TailChunk));
-  LH_HIP(hipMalloc((void**)&gkr_relay, (4 + GKR_MSG_CHUNKS) * sizeof(TailChunk)));
+  if (gkr_relay) return;
+  gkr_mbox.alloc(GKR_MSG_CHUNKS * sizeof(TailChunk));
+  memset(gkr_mbox.get(), 0, GKR_MSG_CHUNKS * sizeof(TailChunk));
+  gkr_relay.alloc((4 + GKR_MSG_CHUNKS) * sizeof(TailChunk));
   LH_HIP(hipMemset(gkr_relay, 0, (4 + GKR_MSG_CHUNKS) * sizeof(TailChunk)));
 }
 void Ctx::gkr_send_layer(const Fr* vals, size_t count, uint32_t seq) {
   LH_REQUIRE(3 * count <= GKR_MSG_CHUNKS, LH_ERR_ARG, "resident layers: layer message too long");
   for (size_t i = 0; i < count; i++) {
     const Fr& r = vals[i];
-    store_chunk(&gkr_mbox[3 * i + 0], seq, r.l[0], r.l[1], r.l[2]);
-    store_chunk(&gkr_mbox[3 * i + 1], seq, r.l[3], r.l[4], r.l[5]);
-    store_chunk(&gkr_mbox[3 * i + 2], seq, r.l[6], r.l[7], 0);
+    TailChunk* box = gkr_mbox.as<TailChunk>() + 3 * i;
+    store_chunk(box + 0, seq, r.l[0], r.l[1], r.l[2]);
+    store_chunk(box + 1, seq, r.l[3], r.l[4], r.l[5]);
+    store_chunk(box + 2, seq, r.l[6], r.l[7], 0);
   }
 }
 void Ctx::gkr_abort() {
   mbox_abort();
-  if (gkr_mbox) store_chunk(&gkr_mbox[0], SC_TAIL_ABORT, 0, 0, 0);
+  if (gkr_mbox) store_chunk(gkr_mbox.as<TailChunk>(), SC_TAIL_ABORT, 0, 0, 0);
 }
 void Ctx::gkr_resync() {
   if (gkr_relay) LH_HIP(hipMemsetAsync(gkr_relay, 0, (4 + GKR_MSG_CHUNKS) * sizeof(TailChunk), stream));
-  if (gkr_mbox) memset((void*)gkr_mbox, 0, GKR_MSG_CHUNKS * sizeof(TailChunk));
+  if (gkr_mbox) memset(gkr_mbox.get(), 0, GKR_MSG_CHUNKS * sizeof(TailChunk));
   k_sc_tail_resync(*this);
 }
 
@@ -398,16 +555,6 @@ bool Ctx::wait_chunks_or(const TailChunk* chunks, size_t count, uint32_t seq, ui
   }
 }
 
-void* Ctx::pin(size_t bytes) {
-  if (bytes > pinned_bytes) {
-    if (pinned) (void)hipHostFree(pinned);
-    size_t want = bytes < 65536 ? 65536 : bytes;
-    LH_HIP(hipHostMalloc(&pinned, want, hipHostMallocCoherent | hipHostMallocMapped));
-    pinned_bytes = want;
-  }
-  return pinned;
-}
-
 void Ctx::d2h(void* dst, const void* d_src, size_t bytes) {
   if (!bytes) return;
   if (bytes > ((size_t)8 << 20)) {  // bulk: let the runtime stream it
@@ -415,15 +562,10 @@ void Ctx::d2h(void* dst, const void* d_src, size_t bytes) {
     sync();
     return;
   }
-  if (bytes > stage_bytes) {
-    if (stage) (void)hipHostFree(stage);
-    size_t want = bytes < ((size_t)1 << 20) ? ((size_t)1 << 20) : bytes;
-    LH_HIP(hipHostMalloc(&stage, want, hipHostMallocCoherent | hipHostMallocMapped));
-    stage_bytes = want;
-  }
-  LH_HIP(hipMemcpyAsync(stage, d_src, bytes, hipMemcpyDeviceToHost, stream));
+  void* via = stage.reserve(bytes, (size_t)1 << 20);
+  LH_HIP(hipMemcpyAsync(via, d_src, bytes, hipMemcpyDeviceToHost, stream));
   sync();
-  memcpy(dst, stage, bytes);
+  memcpy(dst, via, bytes);
 }
 
 // ------------------------------------------------------------------ HostWorker
@@ -483,11 +625,11 @@ void Ctx::phase_times_resolve() {
   if (!phase_ev_pending) return;
   phase_ev_pending = false;
   // ev[0] = start of the prove, ev[k + 1] = end of phase k (k = 0..6); [7] stays 0, [8] (total) is the host's wall clock
-  if (!phase_ev[0]) return;
-  LH_HIP(hipEventSynchronize(phase_ev[7]));
+  if (!phase_ev[0].created()) return;
+  LH_HIP(hipEventSynchronize(phase_ev[7].get()));
   for (int k = 0; k < 7; k++) {
     float ms = 0;
-    LH_HIP(hipEventElapsedTime(&ms, phase_ev[k], phase_ev[k + 1]));
+    LH_HIP(hipEventElapsedTime(&ms, phase_ev[k].get(), phase_ev[k + 1].get()));
     lasso_ms[k] = (double)ms;
   }
 }

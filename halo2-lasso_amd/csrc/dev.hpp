@@ -39,6 +39,10 @@ void set_last_error(const char* msg);
     if (!(cond)) throw ::lh::Error((code), (text)); \
   } while (0)
 
+}  // namespace lh
+#include "owned.hpp"
+namespace lh {
+
 // ------------------------------------------------------------------ workspace arena
 // Stack-disciplined device allocator: the prover's temporaries nest (per sum-check, per layer),
 // so a bump pointer with mark/release avoids hipMalloc/hipFree (both synchronise) on the hot path.
@@ -47,7 +51,6 @@ class Arena {
   struct Mark {
     size_t block, used;
   };
-  ~Arena();
   void* alloc(size_t bytes);
   void* alloc_raw(size_t bytes);
   template <class T>
@@ -65,7 +68,7 @@ class Arena {
 
  private:
   struct Block {
-    char* p;
+    DevMem mem;
     size_t size, used;
   };
   std::vector<Block> blocks_;
@@ -190,11 +193,16 @@ struct Ctx {
   Options opt;
   RouteStats route;
   int device = 0;
-  hipStream_t stream = nullptr;
+  Ctx() = default;  // options and knobs only, no device behind it (lh_debug_msm_plan)
+  // on `device_id`, which it leaves current; throws LH_ERR_DEVICE (what was created by then goes with the members)
+  explicit Ctx(int device_id);
+  ~Ctx();  // the ordered part of the teardown (dev.cpp); the members release themselves
+  Ctx(const Ctx&) = delete;
+  Ctx& operator=(const Ctx&) = delete;
+  Stream stream;
   Arena arena;
   // pinned host staging for small D2H results (round messages, window sums)
-  void* pinned = nullptr;
-  size_t pinned_bytes = 0;
+  PinnedMem pinned{hipHostMallocCoherent | hipHostMallocMapped};
   int num_cus = 256;
   int wall_clock_khz = 100000;  // rate of wall_clock64() on the device
   double lasso_ms[LH_LASSO_NUM_PHASES] = {0};
@@ -207,8 +215,7 @@ struct Ctx {
   // then takes its tables as this rank's shards (struct Shard below); otherwise an attached communicator is ignored
   bool shard_active = false;
   void* rccl_comm = nullptr;      // ncclComm_t of the built-in RCCL backend (comm.cpp)
-  void* comm_stage = nullptr;     // device staging of host-side gathers over a device-only communicator
-  size_t comm_stage_bytes = 0;
+  DevMem comm_stage;              // device staging of host-side gathers over a device-only communicator
   uint64_t comm_stats[2] = {0, 0};  // collectives issued: device-side, host callback
   // the same by phase of the Lasso prove that issued them (index = the phase in progress: witness, commit, surge, leaves,
   // gkr, evals, open; 7 = outside a Lasso prove): [phase][0] collectives, [phase][1] bytes this rank contributed
@@ -220,7 +227,8 @@ struct Ctx {
   uint64_t* sc_wide = nullptr;  // all-reduce variant: the round kernel also leaves its sums as tagged u64 lanes here (device)
   uint32_t sc_tag = 0;          // the tag of the round in progress (ScFinishArgs::tag)
   uint32_t sc_tag_seq = 0;      // tags handed out so far
-  uint64_t* lanes_host = nullptr;  // pinned: where the all-reduce leaves the lanes' sums (created on first use)
+  PinnedMem lanes_host{hipHostMallocCoherent | hipHostMallocMapped};  // where the all-reduce leaves the lanes' sums (created on first use)
+  uint64_t* lanes_host_block();  // 128 words, zeroed when created
   bool comm_host_recv_ok = true;   // the attach-time probe (comm.cpp comm_probe_host_recv): RCCL delivers into pinned host memory here
   Fr* round_out(Fr* out_host) const { return sc_redirect ? sc_redirect : out_host; }
   void wait_round(uint32_t seq) {  // the host's wait for a round kernel's sums (nothing to wait for when they stay on the device)
@@ -261,64 +269,58 @@ struct Ctx {
   bool live = false;
   struct LiveRec {
     ProfRec rec;
-    hipEvent_t e0, e1;
+    Event e0, e1;
     uint32_t batch;
   };
   std::vector<LiveRec> live_recs;
-  std::vector<hipEvent_t> live_pool;  // events not in use
+  std::vector<Event> live_pool;  // events not in use
   uint32_t live_batch = 0;
-  hipEvent_t live_event();
+  Event live_event();
   void live_resolve(std::vector<ProfRec>& out);  // waits for the streams, appends per-launch and per-batch records, recycles the events
-  // helper ctx (same device, own stream / arena / pinned blocks; capi.cpp ctx_helper) and what it is committing ahead of
+  // helper ctx (same device, own stream / arena / pinned blocks; dev.cpp ctx_helper) and what it is committing ahead of
   // the opening (open_columns.cpp open_precommit_*): both owned by this ctx
   bool is_helper = false;  // this ctx is somebody's helper: its throughput kernels leave wave slots to the owner's stream
-  Ctx* helper = nullptr;
-  lh_ctx* helper_handle = nullptr;
+  std::unique_ptr<Ctx> helper;
   OpenPrecommit* precommit = nullptr;
-  HostWorker* worker = nullptr;   // the host thread that drives THIS ctx when it is somebody's helper (created on first use)
-  hipEvent_t handoff_ev = nullptr;  // recorded on this ctx's stream where a helper's stream may start reading its columns
+  std::unique_ptr<HostWorker> worker;  // the host thread that drives THIS ctx when it is somebody's helper (created on first use)
+  Event handoff_ev{hipEventDisableTiming};  // recorded on this ctx's stream where a helper's stream may start reading its columns
   // a staged precommit (Options::open_precommit_stages): [0], [1] behind the commit batch's accumulation launches on the
   // stream and the aux stream - the helper's stage 1 waits for them -, [2] where the trees are built - its stage 2 does
-  hipEvent_t stage_ev[3] = {nullptr, nullptr, nullptr};
+  Event stage_ev[3] = {Event(hipEventDisableTiming), Event(hipEventDisableTiming), Event(hipEventDisableTiming)};
   // phase boundaries of the last Lasso prove as events on the stream (no host sync at a boundary: lasso.cpp lap)
-  hipEvent_t phase_ev[LH_LASSO_NUM_PHASES] = {};
+  Event phase_ev[LH_LASSO_NUM_PHASES];
   bool phase_ev_pending = false;
   void phase_times_resolve();  // events -> lasso_ms (waits for the last one)
-  hipEvent_t prof_ev[2] = {nullptr, nullptr};
+  Event prof_ev[2];
   // committed sparse polynomials (spark.cpp SparkPoly): device memory outside the arena, freed by lh_spark_free or with the ctx
   std::vector<struct SparkPoly*> spark_polys;
   // R1CS keys (spartan.cpp R1csKey): each owns three of the polynomials above and one device block of its own; freed by
   // lh_r1cs_free or with the ctx, before the polynomials
   std::vector<struct R1csKey*> r1cs_keys;
-  void* pin(size_t bytes);  // grows the pinned buffer if needed
+  void* pin(size_t bytes) { return pinned.reserve(bytes, 65536); }  // grows the pinned buffer if needed
   // small device -> host download through a second pinned staging buffer, synchronising: an async copy into
   // pageable memory makes the runtime pin pages on the fly (hundreds of microseconds for a few KB)
-  void* stage = nullptr;
-  size_t stage_bytes = 0;
+  PinnedMem stage{hipHostMallocCoherent | hipHostMallocMapped};
   // pinned staging of the radix sort's slab descriptors (sort.hip) and the event after their last upload
-  void* sort_stage[2] = {nullptr, nullptr};
-  size_t sort_stage_bytes[2] = {0, 0};
-  hipEvent_t sort_ev[2] = {nullptr, nullptr};
-  hipEvent_t sort_stage_done(int side) {
-    if (!sort_ev[side]) LH_HIP(hipEventCreateWithFlags(&sort_ev[side], hipEventDisableTiming));
-    return sort_ev[side];
-  }
+  PinnedMem sort_stage[2];
+  Event sort_ev[2] = {Event(hipEventDisableTiming), Event(hipEventDisableTiming)};
+  hipEvent_t sort_stage_done(int side) { return sort_ev[side].get(); }
   void d2h(void* dst, const void* d_src, size_t bytes);
   void sync() { LH_HIP(hipStreamSynchronize(stream)); }
   // Round-trip fast path: a kernel publishes its (small) result into pinned memory and then stores a
   // sequence number with system-scope release; the host spins on it instead of going through
   // hipStreamSynchronize (tens of microseconds per call, paid once per sum-check round).
-  uint32_t* flag = nullptr;  // pinned, coherent
+  PinnedMem flag{hipHostMallocCoherent | hipHostMallocMapped};  // 64 words
   uint32_t flag_seq = 0;
-  uint32_t* ticket = nullptr;  // device counter for in-launch final reductions; only ever grows (word 8: device flag;
+  DevMem ticket;               // device counter for in-launch final reductions; only ever grows (word 8: device flag;
                                // word 10: the resident grand-product kernel's start verdict; words 32..47: the resident
                                // tail's relay chunks)
   uint32_t ticket_base = 0;    // its value before the next launch
-  uint64_t* fin_lanes = nullptr;  // ScFinishArgs::lanes: 8 lanes per partial sum, FIN_LANE_SUMS of them; zeroed once, then only tagged lanes
+  DevMem fin_lanes;  // ScFinishArgs::lanes: 8 lanes per partial sum, FIN_LANE_SUMS of them; zeroed once, then only tagged lanes
   // a second stream of the ctx for work that runs BESIDE the ctx's stream inside one call (msm.hip: the tails of a batch's
   // first half); its kernels draw tickets from word 16 and publish to flag word 4, so the two streams never share a counter
-  hipStream_t aux_stream = nullptr;
-  hipEvent_t aux_ev = nullptr;
+  Stream aux_stream;
+  Event aux_ev{hipEventDisableTiming};
   uint32_t aux_ticket_base = 0;
   void aux_streams();  // creates them on first use
   struct ScFinishArgs finish_for_aux(uint32_t grid, uint32_t seq);
@@ -327,13 +329,13 @@ struct Ctx {
   struct ScFinishArgs finish_for(uint32_t grid, Fr* out_host, uint32_t seq, double stored_bytes = 0);
   uint32_t next_seq() { return ++flag_seq; }
   // host -> resident kernel mailbox (second cache line of the flag allocation)
-  struct TailMbox* mbox() { return (struct TailMbox*)((char*)flag + 64); }
+  struct TailMbox* mbox() { return (struct TailMbox*)(flag.as<char>() + 64); }
   void mbox_send(const Fr& r, uint32_t seq);
   void mbox_abort();
   // the resident grand-product kernel's boxes (kernels_gkr.hip): host -> kernel layer messages (pinned) and the device
   // relay of whatever one workgroup fetched from the host; created on first use
-  struct TailChunk* gkr_mbox = nullptr;
-  struct TailChunk* gkr_relay = nullptr;
+  PinnedMem gkr_mbox{hipHostMallocCoherent | hipHostMallocMapped};
+  DevMem gkr_relay;
   void gkr_boxes();
   void gkr_send_layer(const Fr* vals, size_t count, uint32_t seq);
   void gkr_abort();   // mbox_abort + the layer box
@@ -434,18 +436,15 @@ struct ProfScope {
     if (!on) return;
     snprintf(rec.name, sizeof rec.name, "%s", name);
     rec.bytes = bytes, rec.muls = muls, rec.items = items, rec.ms = 0;
-    if (!c.prof_ev[0]) {
-      LH_HIP(hipEventCreate(&c.prof_ev[0]));
-      LH_HIP(hipEventCreate(&c.prof_ev[1]));
-    }
-    LH_HIP(hipEventRecord(c.prof_ev[0], c.stream));
+    (void)c.prof_ev[1].get();  // (both exist from here on: the destructor creates nothing)
+    LH_HIP(hipEventRecord(c.prof_ev[0].get(), c.stream));
   }
   ~ProfScope() {
     if (!on) return;
-    (void)hipEventRecord(c.prof_ev[1], c.stream);
-    (void)hipEventSynchronize(c.prof_ev[1]);
+    (void)hipEventRecord(c.prof_ev[1].get(), c.stream);
+    (void)hipEventSynchronize(c.prof_ev[1].get());
     float ms = 0;
-    (void)hipEventElapsedTime(&ms, c.prof_ev[0], c.prof_ev[1]);
+    (void)hipEventElapsedTime(&ms, c.prof_ev[0].get(), c.prof_ev[1].get());
     rec.ms = ms;
     c.prof_recs.push_back(rec);
   }

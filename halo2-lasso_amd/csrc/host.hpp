@@ -296,11 +296,11 @@ constexpr size_t GP_LEVEL_UP_MIN_VARS = 12;
 
 // ------------------------------------------------------------------ pcs::multilinear::kzg
 struct Srs {
-  G1Affine* d_eqs = nullptr;  // flat: level k at offset 2^k - 1
+  DevMem d_eqs;  // flat: level k at offset 2^k - 1
   size_t num_vars = 0;
-  const G1Affine* eq(size_t k) const { return d_eqs + (((size_t)1 << k) - 1); }
+  const G1Affine* eq(size_t k) const { return d_eqs.as<G1Affine>() + (((size_t)1 << k) - 1); }
   // this rank's share of the bases of every sharded level (sharded proving; built on first use)
-  mutable std::vector<G1Affine*> shard_levels;
+  mutable std::vector<DevMem> shard_levels;
   mutable int shard_rank = -1;
   mutable size_t shard_R = 0, shard_j = 0;
   // sum of all bases of a level (mkzg_open over small-valued columns), computed on first use
@@ -308,7 +308,7 @@ struct Srs {
   mutable std::map<size_t, HG1> shard_level_sums;  // the same over this rank's share of a sharded level
   // window tables of whole levels (dev.hpp MsmJob::win_table; Options::msm_window_tables), built on first use
   struct WinTable {
-    G1Affine* d = nullptr;
+    DevMem d;  // (empty: the level has no table)
     uint32_t c = 0, W = 0;
   };
   mutable std::map<size_t, WinTable> win_tables;
@@ -316,7 +316,7 @@ struct Srs {
 // the window table of a level (nullptr: tables are off for this level - Options::msm_window_tables - or do not fit)
 const Srs::WinTable* srs_window_table(Ctx&, const Srs&, size_t level);
 const G1Affine* srs_shard_level(Ctx&, const Srs&, size_t level);  // this rank's share of a level's bases (sharded proofs)
-Srs* mkzg_setup(Ctx&, const HFr* ss, size_t num_vars);
+Srs mkzg_setup(Ctx&, const HFr* ss, size_t num_vars);
 std::vector<HG1> mkzg_batch_commit(Ctx&, const Srs&, const Fr* const* d_polys, size_t num_polys, size_t num_vars);
 std::vector<HG1> mkzg_batch_commit_u32(Ctx&, const Srs&, const uint32_t* const* d_polys, size_t num_polys,
                                        size_t num_vars);
@@ -373,10 +373,10 @@ void additive_batch_open(Ctx&, size_t num_vars, const Fr* const* d_polys, size_t
 
 // ------------------------------------------------------------------ pcs::multilinear::zeromorph over pcs::univariate::kzg
 struct USrs {  // UnivariateKzgParam (univariate/kzg.rs:38-66): powers_of_s_g1 on the device
-  G1Affine* d_powers = nullptr;
+  DevMem d_powers;
   size_t size = 0;
 };
-USrs* ukzg_setup(Ctx&, const HFr& s, size_t poly_size);
+USrs ukzg_setup(Ctx&, const HFr& s, size_t poly_size);
 // poly_size: the trim size (zeromorph.rs:90-108): commits use powers[..poly_size], the final quotient powers[size - poly_size..]
 std::vector<HG1> zeromorph_batch_commit(Ctx&, const USrs&, size_t poly_size, const Fr* const* d_polys, size_t num_polys,
                                         size_t num_vars);
@@ -453,18 +453,16 @@ PcsVerifier gemini_verifier(const UkzgVerifierParams&);
 // when set up with a ctx, on the host when not (or on first use by a verifier); `poly_size` is the trim size (a prefix of g).
 struct IpaParams {
   size_t num_vars = 0;
-  G1Affine* d_g = nullptr;
-  int device = -1;  // the device d_g lives on
+  DevMem d_g;
   HG1 h;
   mutable std::vector<HG1> host_g;  // through ipa_host_g
   mutable std::mutex mu;
   // window tables of prefixes of g for the row kernels (dev.hpp k_g1_rows_msm): key = row_len, entry w row_len + i =
   // 2^(8 w) g[i], w < 32; built on first use (ipa.cpp ipa_rows_table), freed with the param
-  mutable std::map<size_t, G1Affine*> rows_tables;
+  mutable std::map<size_t, DevMem> rows_tables;
 };
 HG1 ipa_hash_to_point(const uint8_t* message, size_t len);
-IpaParams* ipa_setup(Ctx* c, size_t poly_size);             // c null: host only
-void ipa_free(IpaParams*);
+std::unique_ptr<IpaParams> ipa_setup(Ctx* c, size_t poly_size);  // c null: host only
 const std::vector<HG1>& ipa_host_g(const IpaParams&);
 const G1Affine* ipa_rows_table(Ctx&, const IpaParams&, size_t row_len);  // the window table of g[0 .. row_len) (ipa.cpp)
 size_t ipa_trim_vars(const IpaParams&, size_t poly_size);   // ipa.rs:129-145 -> num_vars of the trimmed param
@@ -899,7 +897,7 @@ void memcheck_verify_segment(const PcsVerifier& pcs, size_t num_vars, size_t mem
 struct SparkPoly {
   Ctx* ctx = nullptr;
   size_t n = 0, l = 0, c = 0, nv = 0;
-  void* block = nullptr;
+  DevMem block;
   const Fr* val = nullptr;  // 2^nv entries
   const uint32_t *dim[SPARK_MAX_DIMS] = {}, *rts[SPARK_MAX_DIMS] = {}, *fcs[SPARK_MAX_DIMS] = {};  // 2^n, 2^n, 2^l entries
   uint32_t dim_bits[SPARK_MAX_DIMS] = {}, rts_bits[SPARK_MAX_DIMS] = {}, fcs_bits[SPARK_MAX_DIMS] = {};  // widths (>= 1)
@@ -928,10 +926,11 @@ HFr spark_debug_e(Ctx&, size_t num_vars, size_t dim_vars, size_t num_dims, const
 struct R1csKey {
   Ctx* ctx = nullptr;
   size_t n = 0, l = 0;
-  SparkPoly* mat[3] = {};
-  void* block = nullptr;
+  SparkPoly* mat[3] = {};  // freed with the key
+  DevMem block;
   const uint32_t *seg[2][3] = {}, *other[2][3] = {}, *perm[2][3] = {};
   std::vector<uint8_t> blob;  // the three commitment blobs one after the other
+  ~R1csKey();
 };
 // the limits that need no device (shared with the verifier): returns max(num_vars, dim_vars)
 size_t spartan_check(size_t num_vars, size_t dim_vars, size_t num_public);

@@ -64,7 +64,7 @@ static size_t log2_exact(size_t v, const char* what) {
   return k;
 }
 
-IpaParams* ipa_setup(Ctx* c, size_t poly_size) {
+std::unique_ptr<IpaParams> ipa_setup(Ctx* c, size_t poly_size) {
   const size_t nv = log2_exact(poly_size, "ipa setup");
   LH_REQUIRE(nv >= 1 && nv <= 32, LH_ERR_ARG, "ipa setup: num_vars must be in 1..32");  // (h_coeffs asserts on 0, ipa.rs:320)
   std::unique_ptr<IpaParams> p(new IpaParams());
@@ -72,31 +72,14 @@ IpaParams* ipa_setup(Ctx* c, size_t poly_size) {
   const uint8_t one = 1;
   p->h = ipa_hash_to_point(&one, 1);  // ipa.rs:124
   if (c) {
-    p->device = c->device;
-    LH_HIP(hipMalloc((void**)&p->d_g, poly_size * sizeof(G1Affine)));
-    try {
-      k_ipa_generators(*c, 0, poly_size, p->d_g);
-      c->sync();
-    } catch (...) {
-      (void)hipFree(p->d_g);
-      throw;
-    }
+    p->d_g.alloc(poly_size * sizeof(G1Affine));
+    k_ipa_generators(*c, 0, poly_size, p->d_g);
+    c->sync();
   } else {
     ipa_host_g(*p);
   }
-  return p.release();
+  return p;
 }
-
-struct OnDevice {  // the param's device current for a scope (the verifier entries and free take no ctx)
-  int prev = -1;
-  explicit OnDevice(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (dev >= 0 && dev != prev) (void)hipSetDevice(dev);
-  }
-  ~OnDevice() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
 
 // the verifier's copy of g: a download when the bases are on a device (they were final when setup returned), derived on
 // the host pool when not
@@ -105,7 +88,7 @@ const std::vector<HG1>& ipa_host_g(const IpaParams& p) {
   if (p.host_g.empty()) {
     std::vector<HG1> g((size_t)1 << p.num_vars);
     if (p.d_g) {
-      OnDevice on(p.device);
+      OnDevice on(p.d_g.device());  // (the verifier entries take no ctx)
       LH_HIP(hipMemcpy(g.data(), p.d_g, g.size() * sizeof(HG1), hipMemcpyDeviceToHost));
       p.host_g.swap(g);
       return p.host_g;
@@ -118,16 +101,6 @@ const std::vector<HG1>& ipa_host_g(const IpaParams& p) {
     p.host_g.swap(g);
   }
   return p.host_g;
-}
-
-void ipa_free(IpaParams* p) {
-  if (!p) return;
-  if (p->d_g) {
-    OnDevice on(p->device);
-    (void)hipFree(p->d_g);
-    for (auto& kv : p->rows_tables) (void)hipFree(kv.second);
-  }
-  delete p;
 }
 
 // ipa.rs:129-145 -> the trimmed param's num_vars
@@ -145,7 +118,7 @@ static void check_vars(size_t pp_vars, size_t num_vars, const char* what) {  // 
                                               std::to_string(pp_vars) + " but got " + std::to_string(num_vars) + ")");
 }
 static const G1Affine* device_g(const IpaParams& p) {
-  LH_REQUIRE(p.d_g != nullptr, LH_ERR_ARG, "ipa: the param was set up without a ctx (verifier param): it has no device bases");
+  LH_REQUIRE(p.d_g, LH_ERR_ARG, "ipa: the param was set up without a ctx (verifier param): it has no device bases");
   return p.d_g;
 }
 
@@ -261,22 +234,15 @@ constexpr uint32_t HYRAX_ROWS_CBITS = 8, HYRAX_ROWS_W = 32;
 const G1Affine* ipa_rows_table(Ctx& c, const IpaParams& p, size_t row_len) {
   const G1Affine* g = device_g(p);
   // (the table is built by this ctx's stream and lives beside g: both on the param's device)
-  LH_REQUIRE(c.device == p.device, LH_ERR_ARG, "hyrax commit: the ctx and the param's bases are on different devices");
-  OnDevice on(p.device);
+  LH_REQUIRE(c.device == p.d_g.device(), LH_ERR_ARG, "hyrax commit: the ctx and the param's bases are on different devices");
+  OnDevice on(c.device);
   std::lock_guard<std::mutex> lk(p.mu);
   auto it = p.rows_tables.find(row_len);
   if (it != p.rows_tables.end()) return it->second;
-  G1Affine* t = nullptr;
-  LH_HIP(hipMalloc((void**)&t, row_len * HYRAX_ROWS_W * sizeof(G1Affine)));
-  try {
-    k_msm_window_table(c, g, row_len, HYRAX_ROWS_CBITS, HYRAX_ROWS_W, t);
-    c.sync();
-  } catch (...) {
-    (void)hipFree(t);
-    throw;
-  }
-  p.rows_tables[row_len] = t;
-  return t;
+  DevMem t(row_len * HYRAX_ROWS_W * sizeof(G1Affine));
+  k_msm_window_table(c, g, row_len, HYRAX_ROWS_CBITS, HYRAX_ROWS_W, t);
+  c.sync();
+  return p.rows_tables[row_len] = std::move(t);
 }
 
 // Options::hyrax_rows 1: every row of every poly in ONE call of the row kernels (kernels_hyrax.hip); 0: every row a job of

@@ -436,7 +436,7 @@ void k_gkr_resident_launch(Ctx& c, const GkrLayerDev* layers, size_t num_layers,
   a.flag = c.flag;
   a.poll_ticks = (uint64_t)(knob(Knob::SC_TAIL_TIMEOUT_MS) * (double)c.wall_clock_khz);
   a.start_ticks = (uint64_t)(knob(Knob::GKR_START_TIMEOUT_MS) * (double)c.wall_clock_khz);
-  a.start_word = c.ticket + 10;  // (word 0: tickets, word 8: the sharded rounds' device flag, words 32..: the tail's relay)
+  a.start_word = c.ticket.as<uint32_t>() + 10;  // (word 0: tickets, word 8: the sharded rounds' device flag, words 32..: the tail's relay)
   a.start_id = layers[0].seq;    // (sequence numbers only grow: no two launches of a ctx share one)
   a.trace = nullptr;
   if (knob(Knob::GKR_TRACE) != 0) {

@@ -459,10 +459,9 @@ struct LassoPhases {
   const double t0 = now_ms();
   struct Start {  // (ahead of the scopes below)
     explicit Start(Ctx& c) {
-      for (int k = 0; k < 8; k++)
-        if (!c.phase_ev[k]) LH_HIP(hipEventCreate(&c.phase_ev[k]));
+      for (int k = 0; k < 8; k++) (void)c.phase_ev[k].get();  // (all of them exist before the first is recorded)
       c.phase_ev_pending = false;
-      LH_HIP(hipEventRecord(c.phase_ev[0], c.stream));
+      LH_HIP(hipEventRecord(c.phase_ev[0].get(), c.stream));
       c.comm_phase = 0;
       c.quad_sums.clear();  // (nothing of an earlier prove: the arena hands out the same pointers again)
     }
@@ -478,7 +477,7 @@ struct LassoPhases {
     c.comm_phase = 7;  // (collectives issued after the prove - or after it failed - count as outside)
   }
   void lap(int idx) {
-    LH_HIP(hipEventRecord(c.phase_ev[idx + 1], c.stream));
+    LH_HIP(hipEventRecord(c.phase_ev[idx + 1].get(), c.stream));
     c.comm_phase = idx + 1;
   }
   void done() {  // the prove went through: its times may be read

@@ -11,17 +11,17 @@ namespace lh {
 
 // ------------------------------------------------------------------ MultilinearKzg
 // setup: reference pcs/multilinear/kzg.rs:166-228 with the trapdoor supplied by the caller.
-Srs* mkzg_setup(Ctx& c, const HFr* ss, size_t num_vars) {
+Srs mkzg_setup(Ctx& c, const HFr* ss, size_t num_vars) {
   LH_REQUIRE(num_vars < 31, LH_ERR_ARG, "setup: num_vars too large");
-  Srs* srs = new Srs();
-  srs->num_vars = num_vars;
+  Srs srs;
+  srs.num_vars = num_vars;
   size_t total = ((size_t)2 << num_vars) - 1;
-  LH_HIP(hipMalloc((void**)&srs->d_eqs, total * sizeof(G1Affine)));
+  srs.d_eqs.alloc(total * sizeof(G1Affine));
   ArenaScope scope(c.arena);
   Fr* scal = c.arena.alloc_n<Fr>(total);
   // eqs[k] = eq table of (s_0..s_{k-1}) with s_{k-1} the top bit (kzg.rs:178-194) == eq_xy(s[..k])
   for (size_t k = 0; k <= num_vars; k++) k_eq_xy(c, (const Fr*)ss, k, scal + (((size_t)1 << k) - 1));
-  k_fixed_base_mul_g(c, scal, total, srs->d_eqs);
+  k_fixed_base_mul_g(c, scal, total, srs.d_eqs);
   return srs;
 }
 
@@ -78,22 +78,18 @@ const G1Affine* srs_shard_level(Ctx& c, const Srs& srs, size_t lvl) {
   LH_REQUIRE(g.on, LH_ERR_ARG, "srs shard: no sharded proof is running");
   std::lock_guard<std::mutex> lock(srs_cache_mu);
   if (srs.shard_rank != (int)g.rank || srs.shard_R != g.R || srs.shard_j != g.j) {
-    for (G1Affine* p : srs.shard_levels)
-      if (p) {
-        (void)hipFree(p);
-      }
-    srs.shard_levels.assign(srs.num_vars + 1, nullptr);
+    srs.shard_levels.clear();
+    srs.shard_levels.resize(srs.num_vars + 1);
     srs.shard_level_sums.clear();
     srs.shard_rank = (int)g.rank, srs.shard_R = g.R, srs.shard_j = g.j;
   }
   LH_REQUIRE(lvl <= srs.num_vars && lvl >= g.j + g.rho, LH_ERR_ARG, "srs shard: level is not sharded");
   if (!srs.shard_levels[lvl]) {
     const size_t n_local = (size_t)1 << (lvl - g.rho);
-    G1Affine* p = nullptr;
-    LH_HIP(hipMalloc((void**)&p, n_local * sizeof(G1Affine)));
+    DevMem p(n_local * sizeof(G1Affine));
     k_shard_extract(c, srs.eq(lvl), n_local, g.j, g.rho, g.rank, sizeof(G1Affine), p);
     c.sync();
-    srs.shard_levels[lvl] = p;
+    srs.shard_levels[lvl] = std::move(p);
   }
   return srs.shard_levels[lvl];
 }
@@ -113,16 +109,14 @@ const Srs::WinTable* srs_window_table(Ctx& c, const Srs& srs, size_t lvl) {
   const size_t bytes = (size_t)t.W * n * sizeof(G1Affine);
   size_t free_b = 0, total_b = 0;
   if ((size_t)t.W * n >= ((size_t)1 << 31) || hipMemGetInfo(&free_b, &total_b) != hipSuccess || bytes > free_b / 4 ||
-      hipMalloc((void**)&t.d, bytes) != hipSuccess) {
+      !t.d.try_alloc(bytes)) {
     (void)hipGetLastError();
-    t.d = nullptr;
-    srs.win_tables[lvl] = t;  // (remembered: not asked again)
+    srs.win_tables[lvl] = std::move(t);  // (remembered: not asked again)
     return nullptr;
   }
   k_msm_window_table(c, srs.eq(lvl), n, t.c, t.W, t.d);
   c.sync();
-  srs.win_tables[lvl] = t;
-  return &srs.win_tables[lvl];
+  return &(srs.win_tables[lvl] = std::move(t));
 }
 
 // open: kzg.rs:276-302 + quotients pcs/multilinear.rs:72-107.  The n quotient polynomials are laid out
@@ -318,7 +312,7 @@ HFr mkzg_open(Ctx& c, const Srs& srs, const Fr* d_poly, size_t num_vars, const H
   const bool ahead = plan && pre_out && depth > 0;
   // the remainder (the opened value) is final before the MSM starts: its copy to the host is queued in front of the batch
   // and read behind it (fourth cache line of the ctx's pinned flag block) - not a synchronising download after it
-  Fr* rem_host = (Fr*)((char*)c.flag + 192);
+  Fr* rem_host = (Fr*)(c.flag.as<char>() + 192);
   LH_HIP(hipMemcpyAsync(rem_host, rem, sizeof(Fr), hipMemcpyDeviceToHost, c.stream));
   const bool batch_waited = msm_batch(c, jobs.data(), jobs.size(), (G1Affine*)out.data(), ahead ? &combine_columns : nullptr);
   std::vector<HG1> comms(out.begin(), out.begin() + plain);

@@ -973,13 +973,13 @@ static void msm_sub_accumulate(Ctx& c, MsmSub& s, hipStream_t stream) {
       lr.rec.bytes = 96.0 * s.full_pts + 68.0 * (s.total_pts - s.full_pts), lr.rec.muls = 10.0 * (double)s.max_entries;
       lr.rec.items = (double)s.max_entries;
       lr.e0 = c.live_event(), lr.e1 = c.live_event(), lr.batch = c.live_batch;
-      LH_HIP(hipEventRecord(lr.e0, stream));
+      LH_HIP(hipEventRecord(lr.e0.get(), stream));
     }
     hipLaunchKernelGGL(msm_accumulate0_kernel, dim3((unsigned)acc_grid), dim3(128), 0, stream, plan, s.max_entries, s.skey, s.sidx,
                        s.K, s.buckets, s.ckey, s.cpt, s.nchunks, s.lvl_cnt);
     if (c.live) {
-      LH_HIP(hipEventRecord(lr.e1, stream));
-      c.live_recs.push_back(lr);
+      LH_HIP(hipEventRecord(lr.e1.get(), stream));
+      c.live_recs.push_back(std::move(lr));
     }
   }
 }
@@ -1232,8 +1232,8 @@ static void msm_chunk_run(Ctx& c, const MsmJob* jobs, size_t num_jobs, G1Affine*
         c.route.v[RouteStats::MSM_HALF_BATCHES]++;
         if (!c.prof) {
           c.aux_streams();
-          LH_HIP(hipEventRecord(c.aux_ev, c.stream));
-          LH_HIP(hipStreamWaitEvent(c.aux_stream, c.aux_ev, 0));
+          LH_HIP(hipEventRecord(c.aux_ev.get(), c.stream));
+          LH_HIP(hipStreamWaitEvent(c.aux_stream, c.aux_ev.get(), 0));
           side = c.aux_stream;
           aux_guard.armed = true;
         }

@@ -188,9 +188,8 @@ void open_precommit_cancel(Ctx& c) {
 void open_precommit_release(Ctx& c) {
   OpenPrecommit* pc = c.precommit;
   if (!pc || !pc->staged) return;
-  if (!c.stage_ev[2]) LH_HIP(hipEventCreateWithFlags(&c.stage_ev[2], hipEventDisableTiming));
-  LH_HIP(hipEventRecord(c.stage_ev[2], c.stream));
-  pc->open_gate(false, c.stage_ev[2]);
+  LH_HIP(hipEventRecord(c.stage_ev[2].get(), c.stream));
+  pc->open_gate(false, c.stage_ev[2].get());
 }
 // the columns of a batch opening whose polys are all small-valued columns: `used` polys, a linear column's coefficient
 // handed to the columns it combines, the same column under two names merged.  coef == nullptr: the structure alone
@@ -275,22 +274,20 @@ bool open_precommit_start(Ctx& c, const Srs& srs, size_t num_vars, const SmallPo
   hipEvent_t handoff[2] = {nullptr, nullptr};
   if (two_stages) {
     for (int k = 0; k < (staged >= 1 && c.aux_stream ? 2 : 1); k++) {
-      if (!c.stage_ev[k]) LH_HIP(hipEventCreateWithFlags(&c.stage_ev[k], hipEventDisableTiming));
-      LH_HIP(hipEventRecord(c.stage_ev[k], k ? c.aux_stream : c.stream));
-      handoff[k] = c.stage_ev[k];
+      handoff[k] = c.stage_ev[k].get();
+      LH_HIP(hipEventRecord(handoff[k], k ? c.aux_stream : c.stream));
     }
   } else {
-    if (!c.handoff_ev) LH_HIP(hipEventCreateWithFlags(&c.handoff_ev, hipEventDisableTiming));
-    LH_HIP(hipEventRecord(c.handoff_ev, c.stream));
-    handoff[0] = c.handoff_ev;
+    handoff[0] = c.handoff_ev.get();
+    LH_HIP(hipEventRecord(handoff[0], c.stream));
   }
   const hipEvent_t handoff0 = handoff[0], handoff1 = handoff[1];
   const int device = c.device;
-  if (!h.worker) h.worker = new HostWorker();
-  pc->worker = h.worker;
+  if (!h.worker) h.worker.reset(new HostWorker());
+  pc->worker = h.worker.get();
   h.worker->submit([pc, &h, &srs, num_vars, n, lsh, cut, sharded, bases_of, device, handoff0, handoff1] {
     try {
-      LH_HIP(hipSetDevice(device));
+      OnDevice on(device);
       LH_HIP(hipStreamWaitEvent(h.stream, handoff0, 0));
       if (handoff1) LH_HIP(hipStreamWaitEvent(h.stream, handoff1, 0));
       ArenaScope scope(h.arena);

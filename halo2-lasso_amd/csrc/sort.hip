@@ -341,16 +341,8 @@ void rs_sort_batch(Ctx& c, const RsJob* slabs, size_t count, void* temp, size_t 
   // (the descriptors go up through a pinned staging buffer of their own - Ctx::pin holds round messages and MSM tables that
   // may still be in flight; an async copy out of pageable memory would pin pages on the fly)
   const size_t stage_bytes = host.size() * sizeof(RsSlab);
-  if (stage_bytes > c.sort_stage_bytes[side]) {
-    if (c.sort_stage[side]) {
-      LH_HIP(hipStreamSynchronize(stream));
-      (void)hipHostFree(c.sort_stage[side]);
-      c.sort_stage[side] = nullptr;
-    }
-    c.sort_stage_bytes[side] = std::max<size_t>(stage_bytes, 16384);
-    LH_HIP(hipHostMalloc(&c.sort_stage[side], c.sort_stage_bytes[side], hipHostMallocDefault));
-  }
-  RsSlab* stage = (RsSlab*)c.sort_stage[side];
+  if (stage_bytes > c.sort_stage[side].size() && c.sort_stage[side]) LH_HIP(hipStreamSynchronize(stream));
+  RsSlab* stage = (RsSlab*)c.sort_stage[side].reserve(stage_bytes, 16384);
   LH_HIP(hipEventSynchronize(c.sort_stage_done(side)));  // (the previous batch's upload; long done in practice)
   memcpy(stage, host.data(), stage_bytes);
   LH_HIP(hipMemcpyAsync(d_slabs, stage, host.size() * sizeof(RsSlab), hipMemcpyHostToDevice, stream));

@@ -79,7 +79,6 @@ void spark_free(Ctx& c, SparkPoly* p) {
   if (it == c.spark_polys.end()) return;
   c.spark_polys.erase(it);
   (void)hipStreamSynchronize(c.stream);  // (an opening queued on the stream may still read the columns)
-  if (p->block) (void)hipFree(p->block);
   delete p;
 }
 void spark_free_all(Ctx& c) {
@@ -104,14 +103,8 @@ SparkPoly* spark_commit(Ctx& c, const Pcs& pcs, size_t n, size_t l, size_t cc, c
   SparkPoly& p = *owner;
   p.ctx = &c, p.n = n, p.l = l, p.c = cc, p.nv = nv;
   const size_t bytes = NV * sizeof(Fr) + cc * (2 * N + M) * sizeof(uint32_t);
-  LH_HIP(hipMalloc(&p.block, bytes));
-  struct Release {  // (a refusal below gives the block back: the unique_ptr only knows the host part)
-    SparkPoly* p;
-    ~Release() {
-      if (p && p->block) (void)hipFree(p->block);
-    }
-  } release{&p};
-  Fr* val = (Fr*)p.block;
+  p.block.alloc(bytes);
+  Fr* val = p.block.as<Fr>();
   uint32_t* words = (uint32_t*)(val + NV);
   LH_HIP(hipMemcpyAsync(val, d_val, N * sizeof(Fr), hipMemcpyDeviceToDevice, c.stream));
   if (N < NV) LH_HIP(hipMemsetAsync(val + N, 0, (NV - N) * sizeof(Fr), c.stream));
@@ -146,7 +139,6 @@ SparkPoly* spark_commit(Ctx& c, const Pcs& pcs, size_t n, size_t l, size_t cc, c
     p.blob = kt.stream;
   }
   c.sync();
-  release.p = nullptr;
   c.spark_polys.push_back(&p);
   return owner.release();
 }

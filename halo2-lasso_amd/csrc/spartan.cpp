@@ -83,9 +83,11 @@ void spartan_free(Ctx& c, R1csKey* key) {
   if (it == c.r1cs_keys.end()) return;
   c.r1cs_keys.erase(it);
   (void)hipStreamSynchronize(c.stream);  // (a prove queued on the stream may still read the streams)
-  if (key->block) (void)hipFree(key->block);
-  for (SparkPoly* p : key->mat) spark_free(c, p);
   delete key;
+}
+R1csKey::~R1csKey() {
+  for (SparkPoly* p : mat)
+    if (p) spark_free(*ctx, p);
 }
 void spartan_free_all(Ctx& c) {
   while (!c.r1cs_keys.empty()) spartan_free(c, c.r1cs_keys.back());
@@ -102,16 +104,7 @@ R1csKey* spartan_commit(Ctx& c, const Pcs& pcs, size_t n, size_t l, const lh_r1c
   std::unique_ptr<R1csKey> owner(new R1csKey());
   R1csKey& key = *owner;
   key.ctx = &c, key.n = n, key.l = l;
-  struct Release {  // (a refusal below - an index out of range in B, say - gives back what was made)
-    Ctx& c;
-    R1csKey* key;
-    ~Release() {
-      if (!key) return;
-      if (key->block) (void)hipFree(key->block);
-      for (SparkPoly* p : key->mat)
-        if (p) spark_free(c, p);
-    }
-  } release{c, &key};
+  // (a refusal below - an index out of range in B, say - gives back what was made: the key's destructor)
   // ---- the three Spark commitments, in the caller's entry order: what three separate spark_commit calls give
   for (size_t i = 0; i < 3; i++) {
     const uint32_t* dims[2] = {m[i].d_row, m[i].d_col};
@@ -120,10 +113,10 @@ R1csKey* spartan_commit(Ctx& c, const Pcs& pcs, size_t n, size_t l, const lh_r1c
   }
   // ---- the sorted streams: per matrix and direction two stable sorts of the handle's (checked) copies by the same key -
   // one carries the other index along, one the positions - all twelve as ONE launch set per radix pass
-  LH_HIP(hipMalloc(&key.block, 18 * N * sizeof(uint32_t)));
+  key.block.alloc(18 * N * sizeof(uint32_t));
   {
     ArenaScope scope(c.arena);
-    uint32_t* words = (uint32_t*)key.block;
+    uint32_t* words = key.block.as<uint32_t>();
     uint32_t* again = c.arena.alloc_n<uint32_t>(6 * N);  // (the second sorts' keys: the first ones' once more)
     std::vector<SortSlab> slabs;
     for (int d = 0; d < 2; d++)
@@ -139,7 +132,6 @@ R1csKey* spartan_commit(Ctx& c, const Pcs& pcs, size_t n, size_t l, const lh_r1c
     sort_pairs_u32_batched(c, slabs.data(), slabs.size());
     c.sync();
   }
-  release.key = nullptr;
   c.r1cs_keys.push_back(&key);
   return owner.release();
 }

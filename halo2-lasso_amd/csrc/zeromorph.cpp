@@ -7,15 +7,15 @@
 
 namespace lh {
 
-USrs* ukzg_setup(Ctx& c, const HFr& s, size_t poly_size) {
+USrs ukzg_setup(Ctx& c, const HFr& s, size_t poly_size) {
   LH_REQUIRE(poly_size >= 1 && poly_size < ((size_t)1 << 31), LH_ERR_ARG, "univariate setup: bad poly_size");
-  USrs* srs = new USrs();
-  srs->size = poly_size;
-  LH_HIP(hipMalloc((void**)&srs->d_powers, poly_size * sizeof(G1Affine)));
+  USrs srs;
+  srs.size = poly_size;
+  srs.d_powers.alloc(poly_size * sizeof(G1Affine));
   ArenaScope scope(c.arena);
   Fr* scal = c.arena.alloc_n<Fr>(poly_size);
   k_powers(c, dev(s), poly_size, scal);
-  k_fixed_base_mul_g(c, scal, poly_size, srs->d_powers);
+  k_fixed_base_mul_g(c, scal, poly_size, srs.d_powers);
   return srs;
 }
 
@@ -106,7 +106,7 @@ void zeromorph_open(Ctx& c, const USrs& srs, size_t poly_size, const Fr* d_poly,
   // UnivariateKzg::open at x with open_pp = powers[offset..]: quotient[i] = S_{i+1}
   Fr* S = c.arena.alloc_n<Fr>(n);
   k_suffix_horner(c, f, n, dev(x), S);
-  MsmJob job{S + 1, false, srs.d_powers + offset, n - 1};
+  MsmJob job{S + 1, false, srs.d_powers.as<G1Affine>() + offset, n - 1};
   HG1 pi;
   msm_batch(c, &job, 1, (G1Affine*)&pi);
   tr.write_commitment(pi);

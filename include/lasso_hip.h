@@ -1315,6 +1315,12 @@ lh_status lh_debug_sort_plan(size_t n, unsigned bits, int key_bytes, unsigned* p
  * segment size, plain reduction (0 / 1).  out holds 24 words. */
 lh_status lh_debug_msm_plan(size_t num_jobs, const size_t* n, const uint32_t* bits, const uint32_t* kinds, int helper, int via_prepare,
                             uint64_t* out, size_t* num_subs);
+/* the library's owners of device resources (csrc/owned.hpp; host only).  live_resources: how many hold a resource in this
+ * process right now - out[0] device blocks, [1] pinned host blocks, [2] events, [3] streams (memory of lh_alloc is the
+ * caller's and is not counted).  fail_acquire_after: the (n + 1)-th acquisition of an owner from now on fails with
+ * LH_ERR_DEVICE, once; n < 0 turns a pending failure off.  Process-wide, for tests of the failure paths of creation entries. */
+lh_status lh_debug_live_resources(uint64_t out[4]);
+lh_status lh_debug_fail_acquire_after(int64_t n);
 
 /* development / tests: the kernels that work on 32-bit columns without their field-element views (csrc/kernels_poly.hip,
  * "small-valued columns"), one host function per operation, for tests/test_gpu_u32_columns.py.  Pointers named d_ are

@@ -71,6 +71,47 @@ def test_no_gpu_means_loud_failure(hl):
         hl.Context(0)
 
 
+def _live(lib):
+    """lh_debug_live_resources: (device blocks, pinned blocks, events, streams) the library's owners hold right now"""
+    out = (C.c_uint64 * 4)()
+    assert lib.lh_debug_live_resources(out) == 0
+    return tuple(out)
+
+
+def test_a_failed_context_holds_nothing(hl):
+    """without a GPU Context(0) fails and the process holds nothing at all; beside one, a device that does not exist"""
+    from halo2_lasso_amd import _ffi
+    lib = _ffi.load()
+    assert lib.lh_debug_live_resources(None) == _ffi.LH_ERR_ARG
+    before = _live(lib)
+    try:
+        hl.Context(0).close()
+    except hl.DeviceError:
+        assert _live(lib) == before == (0, 0, 0, 0)
+        return
+    with pytest.raises(hl.DeviceError):
+        hl.Context(1 << 20)
+    assert _live(lib) == before
+
+
+def test_host_only_handles_hold_no_device_resource(hl):
+    """handles made without a ctx come and go with the counts unchanged (a failure injected into the owners never meets them)"""
+    from halo2_lasso_amd import _ffi
+    lib = _ffi.load()
+    before = _live(lib)
+    assert lib.lh_debug_fail_acquire_after(0) == 0
+    try:
+        made = [hl.BrakedownVerifierParam.derive(6, 1), hl.BrakedownVerifierParam.setup(4, 1, bytes(range(32))),
+                hl.MultilinearKzgVerifierParams.setup([3, 5]), hl.ZeromorphVerifierParam.setup(7, 8, 8),
+                hl.UnivariateKzgVerifierParam.setup(7), hl.Ipa.setup(None, 8)]
+        assert _live(lib) == before
+        for h in made:
+            h.free()
+        assert _live(lib) == before
+    finally:
+        assert lib.lh_debug_fail_acquire_after(-1) == 0
+
+
 def test_cpu_list_format(hl):
     """the kernel's CPU list format of sysfs local_cpulist, as Context.host_cpus reads it"""
     assert hl.parse_cpulist("0-3,8,10-11\n") == {0, 1, 2, 3, 8, 10, 11}
