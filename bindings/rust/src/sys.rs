@@ -588,6 +588,10 @@ extern "C" {
     pub fn lh_brakedown_setup(ctx: *mut lh_ctx, num_vars: usize, spec: c_int, seed32: *const u8,
                               out: *mut *mut c_void) -> lh_status;
     pub fn lh_brakedown_derive(num_vars: usize, spec: c_int, out: *mut *mut c_void) -> lh_status;
+    // Ligero (section f4b): the same scheme over Reed-Solomon rows; `row_vars` usize::MAX chooses the row length
+    pub fn lh_ligero_setup(ctx: *mut lh_ctx, num_vars: usize, log_inv_rate: c_int, row_vars: usize,
+                           out: *mut *mut c_void) -> lh_status;
+    pub fn lh_ligero_derive(num_vars: usize, log_inv_rate: c_int, row_vars: usize, out: *mut *mut c_void) -> lh_status;
     pub fn lh_brakedown_param_info(pp: *const c_void, row_len: *mut usize, num_rows: *mut usize,
                                    codeword_len: *mut usize, num_column_opening: *mut usize,
                                    num_proximity_testing: *mut usize) -> lh_status;

@@ -1279,6 +1279,49 @@ class BrakedownVerifierParam(BrakedownParam):
         return cls(None, h, num_vars, spec)
 
 
+class LigeroParam(BrakedownParam):
+    """The param of the Ligero PCS: Brakedown's scheme with rows encoded by a systematic Reed-Solomon code of rate
+    2^-log_inv_rate (tests/ligero_ref.py).  A BrakedownParam to every entry that takes one; `spec` is 0."""
+
+    def __init__(self, ctx, handle, num_vars, log_inv_rate):
+        super().__init__(ctx, handle, num_vars, 0)
+        self.log_inv_rate = log_inv_rate
+        self.row_vars = self.row_len.bit_length() - 1
+
+    @classmethod
+    def _make(cls, entry, ctx, num_vars, log_inv_rate, row_vars):
+        if row_vars is None:
+            row_vars = _ffi.LH_LIGERO_ROW_VARS_AUTO
+        if not (isinstance(row_vars, int) and 0 <= row_vars <= _ffi.LH_LIGERO_ROW_VARS_AUTO):
+            raise ArgumentError("ligero: row_vars must be None or a non-negative integer")
+        h = C.c_void_p()
+        head = () if entry == "lh_ligero_derive" else (ctx.h if ctx is not None else None,)
+        _check(getattr(_ffi.load(), entry)(*head, num_vars, log_inv_rate, row_vars, C.byref(h)))
+        return cls(ctx, h, num_vars, log_inv_rate)
+
+
+class LigeroVerifierParam(LigeroParam):
+    """the host-only param a verifier holds"""
+
+    @classmethod
+    def derive(cls, num_vars, log_inv_rate=2, row_vars=None):
+        """the parameters alone, without the table of roots: info() and trim only"""
+        return cls._make("lh_ligero_derive", None, num_vars, log_inv_rate, row_vars)
+
+    @classmethod
+    def setup(cls, num_vars, log_inv_rate=2, row_vars=None):
+        return cls._make("lh_ligero_setup", None, num_vars, log_inv_rate, row_vars)
+
+
+class Ligero:
+    """Setup of the Ligero PCS; commit, open and verify are hl.Brakedown's over the returned param."""
+
+    @staticmethod
+    def setup(ctx, num_vars, log_inv_rate=2, row_vars=None):
+        """row_vars None: the row length of the smallest proof"""
+        return LigeroParam._make("lh_ligero_setup", ctx, num_vars, log_inv_rate, row_vars)
+
+
 class BrakedownCommitment:
     """MultilinearBrakedownCommitment (brakedown.rs:55-60): the encoded rows and the Merkle tree stay on the device"""
 

@@ -25,6 +25,7 @@ LH_SPARK_MAX_DIMS, LH_SPARK_MAX_DIM_VARS = 3, 24  # lh_spark_commit
 LH_SPARTAN_MIN_DIM_VARS, LH_SPARTAN_MAX_DIM_VARS = 2, 24  # lh_r1cs_commit
 LH_SPARTAN_BATCH_MAX_VARS = 26  # lh_spartan_verify_batch: dim_vars + batch_vars
 LH_BD_COLUMN_FR, LH_BD_COLUMN_U32 = 0, 1
+LH_LIGERO_ROW_VARS_AUTO = (1 << 64) - 1  # (size_t)-1
 
 
 class lh_fr(C.Structure):
@@ -348,6 +349,8 @@ SIGNATURES = {
     "lh_keccak_transcript_hash_io": (C.c_int, [C.POINTER(lh_transcript), C.POINTER(lh_hash_transcript)]),
     "lh_brakedown_setup": (C.c_int, [_P, _SZ, C.c_int, C.c_char_p, C.POINTER(_P)]),
     "lh_brakedown_derive": (C.c_int, [_SZ, C.c_int, C.POINTER(_P)]),
+    "lh_ligero_setup": (C.c_int, [_P, _SZ, C.c_int, _SZ, C.POINTER(_P)]),
+    "lh_ligero_derive": (C.c_int, [_SZ, C.c_int, _SZ, C.POINTER(_P)]),
     "lh_brakedown_param_info": (C.c_int, [_P, C.POINTER(_SZ), C.POINTER(_SZ), C.POINTER(_SZ), C.POINTER(_SZ),
                                           C.POINTER(_SZ)]),
     "lh_brakedown_trim": (C.c_int, [_P, _SZ]),

@@ -201,6 +201,100 @@ BdParam brakedown_setup(Ctx* c, size_t num_vars, int spec, const uint8_t seed[32
   return p;
 }
 
+// ------------------------------------------------------------------ Ligero: the Reed-Solomon code (tests/ligero_ref.py)
+namespace {
+// num_column_opening of a code of relative distance 1 - 2^-b, the reference's formula in IEEE double
+size_t rs_num_column_opening(int b) {
+  const double delta = 1.0 - 1.0 / (double)((size_t)1 << b);
+  return ceil_(-LAMBDA / log2(1.0 - delta / 3.0));
+}
+size_t rs_num_proximity_testing(size_t log2_n) { return ceil_(LAMBDA / ((double)LOG2_Q - (double)log2_n)); }
+
+// w_(2^28) = 7^((r - 1) / 2^28), raised to 2^(28 - log2_m)
+HFr root_of_unity(size_t log2_m) {
+  uint64_t e[4];
+  memcpy(e, host::FrTag::MOD, 32);
+  e[0] -= 1;
+  for (int i = 0; i < 4; i++) e[i] = (e[i] >> 28) | (i < 3 ? e[i + 1] << 36 : 0);
+  HFr w = HFr::from_u64(7).pow(e);
+  for (size_t k = log2_m; k < 28; k++) w = w.sqr();
+  return w;
+}
+
+// in place, natural order in and out: x[s] <- sum_t x[t] w^(+-ts), w = tw[step]; tw has `m * step` entries of period m * step
+void host_ntt(HFr* x, size_t log2_m, const HFr* tw, size_t step, bool inverse) {
+  const size_t m = (size_t)1 << log2_m, period = m * step;
+  for (size_t i = 0, j = 0; i < m; i++) {  // bit reversal
+    if (i < j) std::swap(x[i], x[j]);
+    size_t bit = m >> 1;
+    for (; bit && (j & bit); bit >>= 1) j ^= bit;
+    j |= bit;
+  }
+  for (size_t h = 1; h < m; h <<= 1) {
+    const size_t ts = period / (2 * h);
+    for (size_t g = 0; g < m; g += 2 * h)
+      for (size_t k = 0; k < h; k++) {
+        const HFr& w = tw[inverse ? (period - k * ts) & (period - 1) : k * ts];
+        const HFr u = x[g + k], v = x[g + k + h] * w;
+        x[g + k] = u + v, x[g + k + h] = u - v;
+      }
+  }
+}
+
+void rs_encode_host(const BdParam& p, HFr* t) {
+  LH_REQUIRE(p.tw.size() == p.codeword_len, LH_ERR_ARG, "ligero: parameters without the table of roots");
+  const size_t K = p.row_len, N = p.codeword_len, k = p.depth - (size_t)p.log_inv_rate, cosets = N / K;
+  std::vector<HFr> f(t, t + K);
+  host_ntt(f.data(), k, p.tw.data(), cosets, true);
+  const HFr k_inv = HFr::from_u64(K).inv();
+  for (HFr& v : f) v *= k_inv;
+  for (size_t i = 1; i < cosets; i++) {  // f(w_N^i x) on the K-th roots: coefficient t scaled by w_N^(i t)
+    HFr* out = t + i * K;
+    for (size_t j = 0; j < K; j++) out[j] = f[j] * p.tw[(i * j) & (N - 1)];
+    host_ntt(out, k, p.tw.data(), cosets, false);
+  }
+}
+}  // namespace
+
+void ligero_derive(BdParam& p, size_t num_vars, int b, size_t row_vars) {
+  LH_REQUIRE(b >= 1 && b <= 3, LH_ERR_ARG, "ligero: log_inv_rate must be 1..3");
+  LH_REQUIRE(num_vars >= 1 && num_vars <= 26, LH_ERR_ARG, "ligero: num_vars must be 1..26");
+  LH_REQUIRE(row_vars == LIGERO_ROW_VARS_AUTO || row_vars <= num_vars, LH_ERR_ARG, "ligero: row_vars exceeds num_vars");
+  const size_t t = rs_num_column_opening(b);
+  if (row_vars == LIGERO_ROW_VARS_AUTO) {
+    size_t best = SIZE_MAX;
+    for (size_t rv = 0; rv <= num_vars; rv++) {  // the smallest proof; the smallest row on a tie
+      const size_t ps = (1 + rs_num_proximity_testing(rv + b)) * ((size_t)1 << rv) + t * ((size_t)1 << (num_vars - rv));
+      if (ps < best) best = ps, row_vars = rv;
+    }
+  }
+  LH_REQUIRE(row_vars + (size_t)b <= 28, LH_ERR_ARG, "ligero: the codeword exceeds the field's 2^28 roots of unity");
+  p.code = BD_CODE_RS, p.log_inv_rate = b, p.spec = 0, p.num_vars = num_vars, p.n_0 = 0;
+  p.row_len = (size_t)1 << row_vars;
+  p.num_rows = (size_t)1 << (num_vars - row_vars);
+  p.depth = row_vars + (size_t)b;
+  p.codeword_len = (size_t)1 << p.depth;
+  p.num_column_opening = t;
+  p.num_proximity_testing = rs_num_proximity_testing(p.depth);
+}
+
+BdParam ligero_setup(Ctx* c, size_t num_vars, int b, size_t row_vars) {
+  BdParam p;
+  ligero_derive(p, num_vars, b, row_vars);
+  const HFr w = root_of_unity(p.depth);
+  p.tw.resize(p.codeword_len);
+  p.tw[0] = HFr::one();
+  for (size_t i = 1; i < p.codeword_len; i++) p.tw[i] = p.tw[i - 1] * w;
+  if (c) {
+    p.device = c->device;
+    p.tw_mem.alloc(p.tw.size() * sizeof(Fr));
+    p.d_tw = p.tw_mem;
+    LH_HIP(hipMemcpyAsync(p.d_tw, p.tw.data(), p.tw.size() * sizeof(Fr), hipMemcpyHostToDevice, c->stream));
+    c->sync();
+  }
+  return p;
+}
+
 void brakedown_trim(const BdParam& p, size_t poly_size) {
   LH_REQUIRE(poly_size && !(poly_size & (poly_size - 1)), LH_ERR_ARG, "brakedown: poly_size must be a power of two");
   LH_REQUIRE(poly_size == ((size_t)1 << p.num_vars), LH_ERR_INVALID_PCS_PARAM,
@@ -215,6 +309,7 @@ static void dot_into(const BdMatrix& mat, const HFr* in, HFr* out) {
 }
 
 void brakedown_encode_host(const BdParam& p, HFr* t) {
+  if (p.code == BD_CODE_RS) return rs_encode_host(p, t);
   LH_REQUIRE(!p.a.empty() && p.a[0].cols.size() == p.a[0].dim.n * p.a[0].dim.d, LH_ERR_ARG,
              "brakedown: parameters without matrices");
   for (size_t i = p.row_len; i < p.codeword_len; i++) t[i] = HFr::zero();
@@ -253,6 +348,10 @@ static void check_vars(const BdParam& p, size_t num_vars, const char* what) {
 // (`first_done`: a[0]'s outputs are already there - the column commit's u32 gather)
 static void encode_rows(Ctx& c, const BdParam& p, Fr* rows, size_t R, bool first_done = false) {
   const size_t cw = p.codeword_len;
+  if (p.code == BD_CODE_RS) {  // one code, no cascade: kernels_ntt.hip
+    LH_REQUIRE(p.d_tw && !first_done, LH_ERR_ARG, "ligero: parameters were set up without a device");
+    return k_bd_rs_encode(c, rows, R, cw, p.depth - (size_t)p.log_inv_rate, p.log_inv_rate, p.d_tw);
+  }
   size_t in_off = 0;
   for (size_t k = 0; k + 1 < p.a.size(); k++) {
     if (k || !first_done) k_bd_gather(c, rows, R, cw, in_off, in_off + p.a[k].dim.n, p.a[k]);
@@ -385,7 +484,8 @@ std::vector<std::unique_ptr<BdComm>> brakedown_commit_columns(Ctx& c, const BdPa
   k_bd_load_columns(c, d_cols, P, R, p.row_len, cw, rows);
   // a[0] of the u32 columns from their 4-byte entries (there is an a[0] outside the Reed-Solomon tail when the cascade has
   // more than one level); the field-element columns among them keep bd_gather, a column at a time
-  const bool u32_first = c.opt.brakedown_u32_gather != 0 && any_u32 && p.a.size() > 1;
+  // (a Reed-Solomon param has no a[0]: load, then encode, whatever the option says)
+  const bool u32_first = p.code == BD_CODE_EXPANDER && c.opt.brakedown_u32_gather != 0 && any_u32 && p.a.size() > 1;
   if (u32_first) {
     k_bd_gather_u32(c, d_cols, P, rows, R, p.row_len, cw, p.a[0]);
     if (any_fr)

@@ -28,8 +28,18 @@ struct BdParam {
          num_proximity_testing = 0, depth = 0;
   int spec = 0;
   std::vector<BdMatrix> a, b;
-  int device = -1;  // >= 0: the matrices are on this device too
+  int device = -1;  // >= 0: the matrices (or the twiddle table) are on this device too
+  // The code the rows are encoded with.  BD_CODE_RS (ligero_derive / ligero_setup): a systematic
+  // Reed-Solomon code of rate 2^-log_inv_rate over the 2^depth-th roots of unity; no matrices, `spec` is 0 and n_0 unused.
+  int code = 0;  // BD_CODE_EXPANDER
+  int log_inv_rate = 0;
+  std::vector<HFr> tw;  // w_N^t for t < codeword_len (setup; a derived param has none)
+  Fr* d_tw = nullptr;   // the same table on the device (setup with a ctx)
+  DevMem tw_mem;
 };
+enum { BD_CODE_EXPANDER = 0, BD_CODE_RS = 1 };
+constexpr size_t LIGERO_ROW_VARS_AUTO = (size_t)-1;
+constexpr size_t LIGERO_MAX_DEVICE_ROW_VARS = 22;  // the longest row k_bd_rs_encode takes (two passes of 2^11)
 
 // MultilinearBrakedownCommitment: the encoded rows and the Merkle tree stay on the device
 struct BdComm {
@@ -73,6 +83,11 @@ bool keccak_transcript_hash_io(lh_transcript* t, lh_hash_transcript* out);
 // parameters only (no matrices): throws LH_ERR_ARG where the reference panics
 void brakedown_derive(BdParam& p, size_t num_vars, int spec);
 BdParam brakedown_setup(Ctx* c, size_t num_vars, int spec, const uint8_t seed[32]);
+// The Ligero PCS: the same scheme over the Reed-Solomon code (tests/ligero_ref.py).  `row_vars` LIGERO_ROW_VARS_AUTO: the
+// row length of the smallest proof.  Throws LH_ERR_ARG for log_inv_rate outside 1..3, num_vars outside 1..26,
+// row_vars > num_vars and row_vars + log_inv_rate > 28.  Setup needs no seed: the table of roots is all there is.
+void ligero_derive(BdParam& p, size_t num_vars, int log_inv_rate, size_t row_vars);
+BdParam ligero_setup(Ctx* c, size_t num_vars, int log_inv_rate, size_t row_vars);
 void brakedown_trim(const BdParam& p, size_t poly_size);
 // LinearCodes::encode: `cw` holds the message in its first row_len entries and gets the codeword
 void brakedown_encode_host(const BdParam& p, HFr* cw);
@@ -157,5 +172,10 @@ void k_bd_load_columns(Ctx&, const BdColumn* d_cols, size_t num_cols, size_t num
 // the first forward stage (a[0]: inputs at 0, outputs at row_len) of the u32 columns of the table; Fr columns are left alone
 void k_bd_gather_u32(Ctx&, const BdColumn* d_cols, size_t num_cols, Fr* rows, size_t num_rows, size_t row_len, size_t cw,
                      const BdMatrix& mat);
+
+// kernels_ntt.hip: the Reed-Solomon encoder, every row of a slab in place (the message in a row's first 2^row_vars
+// entries, coset i of the codeword at i << row_vars).  `twiddles`: w_N^t, t < 2^(row_vars + log_inv_rate), on the device.
+void k_bd_rs_encode(Ctx&, Fr* rows, size_t num_rows_total, size_t cw, size_t row_vars, int log_inv_rate,
+                    const Fr* twiddles);
 
 }  // namespace lh

@@ -1359,6 +1359,21 @@ lh_status lh_brakedown_derive(size_t num_vars, int spec, lh_brakedown_param** ou
   *out = w.release();
   LH_CATCH
 }
+lh_status lh_ligero_setup(lh_ctx* ctx, size_t num_vars, int log_inv_rate, size_t row_vars, lh_brakedown_param** out) {
+  LH_TRY
+  NEED(out);
+  OnDevice on(ctx ? ctx->c.device : -1);
+  *out = new lh_brakedown_param{ligero_setup(ctx ? &ctx->c : nullptr, num_vars, log_inv_rate, row_vars)};
+  LH_CATCH
+}
+lh_status lh_ligero_derive(size_t num_vars, int log_inv_rate, size_t row_vars, lh_brakedown_param** out) {
+  LH_TRY
+  NEED(out);
+  std::unique_ptr<lh_brakedown_param> w(new lh_brakedown_param());
+  ligero_derive(w->p, num_vars, log_inv_rate, row_vars);
+  *out = w.release();
+  LH_CATCH
+}
 lh_status lh_brakedown_param_info(const lh_brakedown_param* pp, size_t* row_len, size_t* num_rows, size_t* codeword_len,
                                   size_t* num_column_opening, size_t* num_proximity_testing) {
   LH_TRY

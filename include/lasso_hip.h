@@ -1129,6 +1129,23 @@ lh_status lh_lasso_prove_brakedown(lh_ctx*, const lh_brakedown_param*, const lh_
 lh_status lh_lasso_verify_brakedown(const lh_brakedown_param*, const lh_lasso_table* table, size_t num_vars, lh_transcript* t,
                                     lh_hash_transcript* ht);
 
+/* ---------------------------------------------------------------- f4b: Ligero (Brakedown's scheme over Reed-Solomon rows)
+ * The scheme of f4 with the one other code a LinearCodes trait (util/code.rs) is expected to have: a systematic
+ * Reed-Solomon code of rate 2^-log_inv_rate (1..3) over the roots of unity of bn256::Fr, encoded by a number-theoretic
+ * transform (the specification is tests/ligero_ref.py).  row_len = 2^row_vars, codeword_len = row_len <<
+ * log_inv_rate; position i * row_len + j of a codeword is f(w_N^i w_K^j) for the f that takes the message on the K-th
+ * roots, so the first row_len entries are the message.  The code is MDS: 487 / 309 / 258 column openings at rate 1/2, 1/4,
+ * 1/8 where Spec6 opens 3 755.  row_vars LH_LIGERO_ROW_VARS_AUTO: the row length of the smallest proof (the smallest on a
+ * tie).  No seed: the param holds the table of roots, and with a ctx a copy of it on the device, freed with the param.
+ * LH_ERR_ARG: log_inv_rate outside 1..3, num_vars outside 1..26, row_vars > num_vars (unless AUTO), row_vars + log_inv_rate
+ * > 28, NULL out.  The param is an lh_brakedown_param: every lh_brakedown_*, lh_lasso_*_brakedown and
+ * lh_hyperplonk_*_brakedown entry takes it unchanged (option brakedown_u32_gather has nothing to act on and is ignored);
+ * lh_ligero_derive is parameters only (param_info and trim).  The device encoder takes rows up to 2^22. */
+#define LH_LIGERO_ROW_VARS_AUTO ((size_t)-1)
+lh_status lh_ligero_setup(lh_ctx* ctx /* NULL: host only */, size_t num_vars, int log_inv_rate, size_t row_vars,
+                          lh_brakedown_param** out);
+lh_status lh_ligero_derive(size_t num_vars, int log_inv_rate, size_t row_vars, lh_brakedown_param** out);
+
 /* ---------------------------------------------------------------- f5: the multilinear IPA (transparent AND additive)
  * PolynomialCommitmentScheme for MultilinearIpa<bn256::G1Affine> (pcs/multilinear/ipa.rs:23-337): no trusted setup, no
  * pairing, commitments are G1 points - so additive::batch_open, Lasso and HyperPlonk apply to it as to the KZG family.
